@@ -18,9 +18,13 @@ over the whole batch (init, 11 iterations, un-normalise; preconditioner already 
             CG matvec" with its roofline fraction by SURVEY 8(d)'s bytes)
   value   = whole-job aggregate over all ranks (weak scaling: every rank owns 512 members; the solutions are
             all-gathered over RCCL when N > 1, as north_star prescribes: --gather end | step)
-Also reported: end-to-end solves/s (preconditioner build included), what a solve costs when its preconditioner cache
-serves 1 / 25 / 100 solves, the roofline line of the dominant kernel (live HIP-event timing on the launch stream), and
-the CPU oracle timed on the host cores.
+A plain run does only what the headline needs: set-up (operator, preconditioner cache), the ramp (the same step for
+--min-seconds, 1 s by default: clocks and the cache's diagonal form in their steady state), W warm-up steps, the K
+timed steps, the outputs (--dump-outputs DIR) and the JSON line.
+With --full, also reported: the quick numbers of the other BASELINE configs, end-to-end solves/s (preconditioner build
+included), what a solve costs when its preconditioner cache serves 1 / 25 / 100 solves, the other engines timed over
+the same K steps, the accuracy of the timed solve against the fp64 closed form, the roofline line of the dominant
+kernel (live HIP-event timing on the launch stream), and the CPU oracle timed on the host cores.
 """
 from __future__ import annotations
 
@@ -46,6 +50,24 @@ PROFILE_DIR = "r06"  # profiles/<dir>/ holds the rocprofv3 summaries of this com
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 HBM_ACHIEVABLE_GBS = 6300.0  # the guide's measured float4-copy rate: the ceiling a streaming kernel can reach
 MFMA_F32_PEAK_TFLOPS = 157.3  # dense fp32 matrix peak (v_mfma_f32_16x16x4_f32 / 32x32x2, MI355X_MICROARCH.md)
+DUMP_BUDGET_BYTES = 64 * 10**6  # --dump-outputs writes at most this much (64 MB)
+
+
+def dump_outputs(directory, arrays, seed=0):
+    """--dump-outputs: what the timed path returned in its last step, one DIR/<name>.npy per tensor (float32 / float64).
+    When the tensors exceed DUMP_BUDGET_BYTES together, each is cut to the same fixed, seeded sample of its leading
+    (batch) axis, so that two runs with the same arguments write the same members."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    arrays = {k: (t.detach() if t.dtype == torch.float64 else t.detach().float()) for k, t in arrays.items()}
+    total = sum(t.numel() * t.element_size() for t in arrays.values())
+    for name, t in arrays.items():
+        if total > DUMP_BUDGET_BYTES:
+            keep = max(1, t.shape[0] * DUMP_BUDGET_BYTES // total)
+            idx = np.sort(np.random.default_rng(seed).choice(t.shape[0], keep, replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(directory, name + ".npy"), t.cpu().numpy())
 
 
 def make_problem(device, seed):
@@ -672,6 +694,11 @@ def strong_scaling(args, device, dist, rank, world):
         elapsed = float(t.item())
     if rank != 0:
         return None
+    if getattr(args, "dump_outputs", None):
+        outs = {"x": res.x}  # the last chunk's
+        if res.t_mat is not None:
+            outs["t_mat"] = res.t_mat.transpose(0, 1)  # [members, probes, m, m]: members lead, as in x
+        dump_outputs(args.dump_outputs, outs)
     return {
         "metric": "cg_member_matvecs_per_sec", "value": total * res.matvecs * args.steps / elapsed,
         "unit": "member-matvecs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -761,6 +788,8 @@ def stub_run(args, rank, world):
         dist.destroy_process_group()
     else:
         ok = True
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"x": x})
     ms = max(rank_ms)
     return {"metric": "stub", "value": world * 4 * 11 / (ms * 1e-3), "unit": "member-matvecs/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms, "higher_is_better": True, "scaling": "weak",
@@ -778,26 +807,39 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the quick numbers for the other BASELINE configs")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: the other BASELINE configs, the box's HBM ceilings, "
+                         "the other engines and gather modes over the same K steps, end-to-end and roofline figures, "
+                         "accuracy checks, the CPU baselines (a plain run: set-up, ramp, W + K steps, the JSON line)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (rank 0: its solutions x) as "
+                         "DIR/<name>.npy, float32, at most 64 MB (a fixed, seeded sample of the members beyond that)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="--full: skip the quick numbers for the other BASELINE configs")
     ap.add_argument("--workload", choices=["headline", "cfg4", "cfg5"], default="headline",
                     help="headline (default, weak scaling, the driver's contract) or BASELINE cfg4 / cfg5 at their "
                          "full batch split over the ranks (strong scaling)")
-    ap.add_argument("--min-seconds", type=float, default=3.0,
-                    help="after the timed K steps: keep stepping (each step timed on its own) for about this much wall "
-                         "time -- per-step min / median / max for the JSON line, and a GPU that an external "
-                         "utilisation sampler sees busy.  0 = off.  `value` / `ms_per_step` come from the K steps only")
+    ap.add_argument("--min-seconds", type=float, default=None,
+                    help="before the W warm-up and the timed K steps: keep stepping (each step timed on its own) for about "
+                         "this much wall time (default 1, with --full 3) -- the ramp to steady clocks and to the cache's "
+                         "diagonal form, per-step min / median / max for the JSON line (`soak`), and a GPU that an "
+                         "external utilisation sampler sees busy.  0 = off.  `value` / `ms_per_step` come from the K "
+                         "steps only")
     ap.add_argument("--gather", choices=["step", "end"], default="end",
                     help="N > 1: `end` (default) = ONE all-gather of the solutions after the K steps, inside the timed "
                          "region (north_star: `an RCCL all-gather over xGMI at the end`); `step` = one all-gather per "
                          "solve, overlapped with the next solve (the demanding reading: 16 MB per rank every 0.25 ms).  "
-                         "The other mode is timed over the same K steps as well and reported under `gather_modes`")
+                         "With --full, the other mode is timed over the same K steps as well and reported under "
+                         "`gather_modes`")
     ap.add_argument("--inject-timeouts", type=int, default=0,
                     help="treat the first n resident CG launches of the soak as timed out (exercises the cool-down / "
                          "re-arm gate of the resident kernels; the JSON line reports what the gate did)")
     ap.add_argument("--chunk-members", type=int, default=128,
                     help="cfg5: members resident at a time per rank (1 GiB each)")
     args = ap.parse_args()
+    if args.min_seconds is None:
+        args.min_seconds = 3.0 if args.full else 1.0
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -857,12 +899,13 @@ def main():
         # CU with two workgroups; a workgroup RCCL's kernel displaces stalls its whole group until the gather ends.
         # Leaving 32 CUs' worth of slots unused (liblo_amd reads the variable at every launch) gives RCCL room.
         reserve_default = os.environ.get("LO_OC_RESERVE_CUS")  # (an explicit setting of the caller wins in both modes)
-    # The quick numbers of the other BASELINE configs run FIRST (single GPU): several seconds of the library's own
+    # --full: the quick numbers of the other BASELINE configs run FIRST (single GPU): several seconds of the library's own
     # kernels, after which the device sits at its steady clocks -- right after start-up the same solve is ~7 % slower
     # and speeds up over its first ~40 launches (tools/mb_step_ramp.py: 0.400 -> 0.372 ms per step), a ramp that would
-    # otherwise fall into the W warm-up + K timed steps.  The timed region itself is exactly the contract's.
+    # otherwise fall into the W warm-up + K timed steps (a plain run leaves the ramp to the soak below).  The timed
+    # region itself is exactly the contract's.
     extras, extras_error = None, None
-    if world == 1 and rank == 0 and not args.no_extras:
+    if args.full and world == 1 and rank == 0 and not args.no_extras:
         try:
             extras = other_configs(device)
         except Exception as e:  # noqa: BLE001 -- the headline line must not be lost to an extra
@@ -922,7 +965,7 @@ def main():
 
     # ---- this box's HBM ceilings (reported beside the spec peak), measured first: 1 GiB arrays ----
     triad_gbs = copy_gbs = None
-    if rank == 0:
+    if args.full and rank == 0:
         try:
             triad_gbs = round(_hip.hbm_stream_gbs(device, "triad"), 1)
             copy_gbs = round(_hip.hbm_stream_gbs(device, "copy"), 1)
@@ -932,9 +975,10 @@ def main():
     # ---- validation BEFORE the timed region: one solve checked against the fp64 Woodbury closed form of the same systems
     # (the exact solution; torch fp64 library ops as the CHECKER).  The kernels are bitwise reproducible, so this is the
     # very result every timed step computes (asserted after the timed region).
-    res_check = K.cg_solve(desc, rhs, precond=pre, tolerance=TOL)
-    solve_rel_err = woodbury_fp64_rel_err(Cm, d, rhs, res_check.x)
-    x_check = res_check.x.clone()
+    if args.full:
+        res_check = K.cg_solve(desc, rhs, precond=pre, tolerance=TOL)
+        solve_rel_err = woodbury_fp64_rel_err(Cm, d, rhs, res_check.x)
+        x_check = res_check.x.clone()
     res = None
     # soak FIRST: the same step again and again for >= --min-seconds, every step timed on its own (host clock around a
     # synchronous solve).  It doubles as the ramp: the first ~40 solves after ANY pause of the device (the validation
@@ -985,9 +1029,12 @@ def main():
     step_stats = _step_stats([stamps[i + 1] - stamps[i] for i in range(args.steps)])
     per_rank_ms = [elapsed / args.steps * 1e3]
     allgather_ms = None
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"x": res.x})
     if use_dist:
         per_rank_ms = _gather_rank_ms(dist, per_rank_ms[0], device)
         elapsed = max(per_rank_ms) * 1e-3 * args.steps  # the MAX over the ranks is the job's time
+    if use_dist and args.full:
         # the collective on its own (blocking, nothing to hide behind): what one all-gather of the solutions costs
         torch.cuda.synchronize(device)
         dist.barrier()
@@ -999,6 +1046,79 @@ def main():
     matvecs_per_solve = res.matvecs
     total_members = world * B_PER_GPU
     value = total_members * matvecs_per_solve * args.steps / elapsed
+    # ---- per-rank engine and gate of the resident kernels: a line measured on the streaming engine says so ----
+    engines = [engine_timed]
+    gates = [gate]
+    if use_dist:
+        engines = [None] * world
+        gates = [None] * world
+        dist.all_gather_object(engines, engine_timed)
+        dist.all_gather_object(gates, gate)
+
+    def headline_line():
+        """The JSON line of a plain run; --full adds its figures to it."""
+        line = {
+            "metric": "cg_member_matvecs_per_sec",
+            "value": value,
+            "unit": "member-matvecs/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": elapsed / args.steps * 1e3,
+            "step_ms": step_stats,
+            "soak": soak,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f32",
+            "data": "synthetic",
+            "config": {
+                "workload": "north_star headline (cfg3 operator, 1 rhs column): AddedDiag(LowRankRoot(C[512,8192,32]), "
+                            "Diag(d[512,8192])) per GPU, linear_cg with rank-15 pivoted-Cholesky preconditioner, "
+                            "cg_tolerance 1e-4 -> 11 iterations (floor)",
+                "batch_per_gpu": B_PER_GPU, "N": N, "R": R, "rhs_columns": C_COLS, "precond_rank": RANK_K,
+                "iterations": res.iterations, "matvecs_per_solve": matvecs_per_solve,
+                "sharding": ((f"batch x{world}, no collective inside the solve; ONE all_gather of the solutions after the K "
+                              "steps, inside the timed region (--gather end; the per-solve overlapped gather is timed "
+                              "beside it: gather_modes)") if args.gather == "end" else
+                             (f"batch x{world}, one all_gather of the solutions per solve, issued asynchronously and "
+                              "overlapped with the next solve; resident kernels leave "
+                              f"{os.environ.get('LO_OC_RESERVE_CUS', '0')} CUs' worth of slots to RCCL (--gather step)"))
+                if world > 1 else "single GPU",
+            },
+            "value_kind": ("cg-iteration-equivalents (operator read once per solve): members x the 11 operator "
+                           "applications the reference's linear_cg performs / wall time of the solve.  The timed engine "
+                           "(k_cg_rspace) reads C from HBM ONCE per solve and carries the 11 iterations on R + 1 Krylov "
+                           "coordinates in fp64: no product with C is executed per iteration.  The engine that applies "
+                           "the operator 11 times on the rows is `operator_applications_per_sec`; ONE application of the "
+                           "operator as an HBM pass (C read once) is `hbm_matvec`")
+                          if engine_timed.startswith("resident R-space") else "operator applications on the rows of C",
+            "final_mean_residual": res.mean_residual,
+            "rccl_ranks": world if use_dist else 0,
+            "per_rank_ms": per_rank_ms,
+            "engine": engine_timed,
+            "engine_per_rank": engines,
+            "resident_timeouts": sum(g_["timeouts"] for g_ in gates),
+            "resident_gate_per_rank": gates,
+        }
+        if args.inject_timeouts > 0:
+            line["inject_timeouts"] = {"injected": args.inject_timeouts, "soak_engines": engines_seen,
+                                       "note": "engines of the soak's solves after the injected hand-off timeouts: "
+                                               "cool-down on the streaming engine, then the resident kernel again"}
+        return line
+
+    def finish(line):
+        if use_dist:
+            dist.barrier()
+            dist.destroy_process_group()
+        sys.stdout.flush()
+        if rank == 0:
+            os.write(real_stdout, (json.dumps(line) + "\n").encode())
+        os.close(real_stdout)
+
+    if not args.full:
+        finish(headline_line() if rank == 0 else None)
+        return
 
     def timed_region(n_steps):
         """W warm-up + n_steps timed steps between two fences, maximum over the ranks (ms per step)."""
@@ -1066,14 +1186,6 @@ def main():
                                        "eigendecompositions each), paid ONCE per preconditioner cache when it serves its "
                                        "25th single-column solve (kernels._eigform_due: when the solves served have paid for it) -- "
                                        "outside the timed region, as the pivoted Cholesky and the root form are"}
-    # ---- per-rank engine and gate of the resident kernels: a line measured on the streaming engine says so ----
-    engines = [engine_timed]
-    gates = [gate]
-    if use_dist:
-        engines = [None] * world
-        gates = [None] * world
-        dist.all_gather_object(engines, engine_timed)
-        dist.all_gather_object(gates, gate)
 
     # ---- end-to-end solves/s (pivoted Cholesky + preconditioner build + CG), local rank ----
     # Through the PUBLIC path: A.solve(rhs) of AddedDiagLinearOperator(LowRankRootLinearOperator(C), DiagLinearOperator(d))
@@ -1244,45 +1356,11 @@ def main():
             if tj.get("prof_name") == dom and tj.get("kernel", "").replace(" ", "").startswith(dom_kernel.replace(" ", "").rstrip(">")):
                 traffic = tj["traffic_bytes_per_launch"]
                 traffic_source = (f"profiles/{PROFILE_DIR}/traffic.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of "
-                                  f"`bench.py --no-extras`, kernel {tj['kernel']}, FETCH x2 (gfx950 correction) + WRITE")
+                                  f"`bench.py --full --no-extras`, kernel {tj['kernel']}, FETCH x2 (gfx950 correction) + WRITE")
         except Exception:  # noqa: BLE001
             pass
-        out = {
-            "metric": "cg_member_matvecs_per_sec",
-            "value": value,
-            "unit": "member-matvecs/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
-            "step_ms": step_stats,
-            "soak": soak,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic",
-            "config": {
-                "workload": "north_star headline (cfg3 operator, 1 rhs column): AddedDiag(LowRankRoot(C[512,8192,32]), "
-                            "Diag(d[512,8192])) per GPU, linear_cg with rank-15 pivoted-Cholesky preconditioner, "
-                            "cg_tolerance 1e-4 -> 11 iterations (floor)",
-                "batch_per_gpu": B_PER_GPU, "N": N, "R": R, "rhs_columns": C_COLS, "precond_rank": RANK_K,
-                "iterations": res.iterations, "matvecs_per_solve": matvecs_per_solve,
-                "sharding": ((f"batch x{world}, no collective inside the solve; ONE all_gather of the solutions after the K "
-                              "steps, inside the timed region (--gather end; the per-solve overlapped gather is timed "
-                              "beside it: gather_modes)") if args.gather == "end" else
-                             (f"batch x{world}, one all_gather of the solutions per solve, issued asynchronously and "
-                              "overlapped with the next solve; resident kernels leave "
-                              f"{os.environ.get('LO_OC_RESERVE_CUS', '0')} CUs' worth of slots to RCCL (--gather step)"))
-                if world > 1 else "single GPU",
-            },
-            "value_kind": ("cg-iteration-equivalents (operator read once per solve): members x the 11 operator "
-                           "applications the reference's linear_cg performs / wall time of the solve.  The timed engine "
-                           "(k_cg_rspace) reads C from HBM ONCE per solve and carries the 11 iterations on R + 1 Krylov "
-                           "coordinates in fp64: no product with C is executed per iteration.  The engine that applies "
-                           "the operator 11 times on the rows is `operator_applications_per_sec`; ONE application of the "
-                           "operator as an HBM pass (C read once) is `hbm_matvec`")
-                          if engine_timed.startswith("resident R-space") else "operator applications on the rows of C",
+        out = headline_line()
+        out.update({
             "operator_applications_per_sec": (matvec_engine or {}).get("value"),
             "operator_applications_engine": (matvec_engine or {}).get("engine"),
             "hbm_matvec": hbm_matvec,
@@ -1331,7 +1409,6 @@ def main():
             "end_to_end_solve_rel_err": woodbury_fp64_rel_err(Cm, d, rhs, x_e2e),
             "end_to_end_three_launch_ms": e2e3 * 1e3,
             "kernels": kernels,
-            "final_mean_residual": res.mean_residual,
             "solve_rel_err": solve_rel_err,
             "timed_result_bitwise_equals_checked_result": timed_equals_checked,
             "first_solve_of_the_cache": {"solve_rel_err": solve_rel_err_first, "bitwise_equals_timed_result": first_equals_timed,
@@ -1342,17 +1419,11 @@ def main():
             "solve_rel_err_note": "max over the 512 members of ||x - x*|| / ||x*||, x* = fp64 Woodbury closed form of the "
                                   "same systems (north_star bar 1e-4); logdet rel-err with identical probes: "
                                   "cpu_baseline.parity_sample",
-            "rccl_ranks": world if use_dist else 0,
-            "per_rank_ms": per_rank_ms,
             "allgather_ms": allgather_ms,
             "gather_modes": gather_modes,
-            "engine": engine_timed,
-            "engine_per_rank": engines,
-            "resident_timeouts": sum(g_["timeouts"] for g_ in gates),
-            "resident_gate_per_rank": gates,
             "matvec_engine": matvec_engine,
             "rspace_dense_engine": rspace_dense_engine,
-        }
+        })
         if cache_use and "error" not in cache_use and rspace_dense_engine:
             t_diag, t_dense = elapsed / args.steps * 1e3, rspace_dense_engine["ms_per_step"]
             t_eig, due = rspace_dense_engine["eigform_build_ms"], 25
@@ -1379,10 +1450,6 @@ def main():
                 "step pays `end_to_end_ms`")
         elif cache_use:
             out["solve_ms_at_cache_use"] = cache_use
-        if args.inject_timeouts > 0:
-            out["inject_timeouts"] = {"injected": args.inject_timeouts, "soak_engines": engines_seen,
-                                      "note": "engines of the soak's solves after the injected hand-off timeouts: "
-                                              "cool-down on the streaming engine, then the resident kernel again"}
         # the one-launch end-to-end kernel at the headline shape: live HIP-event time, compulsory bytes per launch
         with lo_settings.cg_tolerance(TOL):
             prof_e = _profiled(e2e_api)
@@ -1417,13 +1484,7 @@ def main():
                     out["config_baselines"] = config_baselines(device)
                 except Exception as e:  # noqa: BLE001
                     out["config_baselines_error"] = repr(e)
-    if use_dist:
-        dist.barrier()
-        dist.destroy_process_group()
-    sys.stdout.flush()
-    if rank == 0:
-        os.write(real_stdout, (json.dumps(out) + "\n").encode())
-    os.close(real_stdout)
+    finish(out)
 
 
 if __name__ == "__main__":

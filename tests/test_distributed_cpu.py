@@ -201,3 +201,30 @@ def test_bench_single_rank_contract_and_world_size_mismatch():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"], env=env, capture_output=True,
                        text=True, timeout=120)
     assert p.returncode != 0 and "WORLD_SIZE=1" in p.stderr  # a launcher that started the wrong number of ranks
+
+
+def test_bench_dump_outputs_of_the_last_timed_step(tmp_path):
+    """`--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy (float32); `--full` is an option of
+    the same command line."""
+    for extra in ([], ["--full"]):
+        out = _run_bench_stub({}, ["--steps", "4", "--warmup", "1", "--dump-outputs", str(tmp_path / "out")] + extra)
+        assert out["steps"] == 4 and out["ms_per_step"] > 0
+        x = np.load(tmp_path / "out" / "x.npy")
+        assert x.dtype == np.float32 and x.shape == (4, 8, 1) and np.all(x == 0)  # rank 0's stub solution
+
+
+def test_bench_dump_outputs_samples_the_same_members_within_the_budget(tmp_path, monkeypatch):
+    """Outputs beyond the budget: whole members, the same ones for every tensor and in every run, dtypes kept."""
+    import bench
+
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 2048)
+    x = torch.arange(64 * 10, dtype=torch.float32).reshape(64, 10)
+    t = torch.arange(64 * 3, dtype=torch.float64).reshape(64, 3)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"x": x, "t": t})
+    xa, ta = np.load(tmp_path / "a" / "x.npy"), np.load(tmp_path / "a" / "t.npy")
+    assert xa.dtype == np.float32 and ta.dtype == np.float64
+    assert xa.nbytes + ta.nbytes <= 2048 and 0 < xa.shape[0] < 64 and xa.shape[1:] == (10,)
+    assert np.array_equal(xa, np.load(tmp_path / "b" / "x.npy")) and np.array_equal(ta, np.load(tmp_path / "b" / "t.npy"))
+    rows = xa[:, 0].astype(np.int64) // 10  # the members kept, in order, whole
+    assert np.all(np.diff(rows) > 0) and np.array_equal(xa, x.numpy()[rows]) and np.array_equal(ta, t.numpy()[rows])

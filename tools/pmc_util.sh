@@ -3,8 +3,9 @@
 set -u
 OUT=$GRAFT_REPO_ROOT/gpurun_out/prof
 mkdir -p $OUT
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
-B="python $GRAFT_REPO_ROOT/bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-extras"
+B="python $REPO/bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-extras"
 : > $OUT/pmc_utilisation.txt
 for c in VALUBusy SALUBusy LdsUtil VALUUtilization SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CU_CYCLES; do
   rm -rf /tmp/p_u

@@ -31,5 +31,5 @@ PY
   done
   cat $OUT/pmc_wave_cycles_$name.txt
 }
-run bench k_cg_onchip5 python $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-extras
+run bench k_cg_onchip5 python $R/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-extras
 run lockstep k_cg_lockstep python $R/tools/mb_lockstep.py

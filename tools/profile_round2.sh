@@ -7,7 +7,7 @@ OUT=$GRAFT_REPO_ROOT/gpurun_out/prof2
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
-B="python $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-extras"
+B="python $R/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-extras"
 stats() {  # name, command...
   local name=$1; shift
   rm -rf /tmp/p_$name
@@ -87,7 +87,7 @@ per = [sum(v) for v in rows.values()]
 print(f"{c}: k_cg_onchip5 dispatches {len(per)}, per dispatch avg {sum(per)/len(per):.6g}")
 PY
 done
-cd $R && timeout 900 python bench.py --steps 20 --warmup 3 > $OUT/bench.json 2> $OUT/bench.stderr
+cd $R && timeout 900 python bench.py --full --steps 20 --warmup 3 > $OUT/bench.json 2> $OUT/bench.stderr
 tail -c 1500 $OUT/bench.json
 timeout 600 python bench.py --workload cfg4 --steps 2 --warmup 1 > $OUT/bench_cfg4_strong.json 2>> $OUT/bench.stderr
 timeout 900 python bench.py --workload cfg5 --steps 1 --warmup 0 --chunk-members 16 > $OUT/bench_cfg5_strong.json 2>> $OUT/bench.stderr

@@ -8,7 +8,7 @@ OUT=$GRAFT_REPO_ROOT/gpurun_out/prof5
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
-B="python $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-extras"
+B="python $R/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-extras"
 stats() {  # name, command...
   local name=$1; shift
   rm -rf /tmp/p_$name
@@ -109,7 +109,7 @@ for c in SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIV
 done
 cd $R
 for m in 3 200 400; do LO_OC_DEBUG=$m python tools/mb_rspace_time.py 2>&1 | grep -E "onchip member" | tail -1; done > $OUT/rspace_member_phases.txt
-python bench.py > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 timeout 600 python bench.py --workload cfg4 --steps 2 --warmup 1 > $OUT/bench_cfg4_strong.json 2>> $OUT/bench.err
 timeout 600 python bench.py --workload cfg5 --steps 1 --warmup 1 > $OUT/bench_cfg5_strong.json 2>> $OUT/bench.err
 ls -la $OUT

@@ -8,7 +8,7 @@ OUT=$GRAFT_REPO_ROOT/gpurun_out/prof5b
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
-B="python $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-extras"
+B="python $R/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-extras"
 rm -rf /tmp/p_bench
 timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_bench -- $B > $OUT/bench_under_rocprof.log 2>&1
 cp "$(find /tmp/p_bench -name '*kernel_stats.csv' | head -1)" $OUT/kernel_stats_bench.csv
@@ -47,5 +47,5 @@ rm -rf /tmp/p_e
 timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_e -- python check_eigform.py > $OUT/check_eigform.txt 2>&1
 grep -E "Name|eigform|k_cg_rspace|k_rs_gram64|k_pb_rootform|k_pc_onchip4" "$(find /tmp/p_e -name '*kernel_stats.csv' | head -1)" | cut -c1-220 > $OUT/kernel_stats_eigform.csv
 cd $R
-python bench.py > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 ls -la $OUT

@@ -9,7 +9,7 @@ OUT=$GRAFT_REPO_ROOT/gpurun_out/prof6
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
-B="python $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-extras"
+B="python $R/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-extras"
 MV="python $R/tools/mb_lowrank_mv.py 1 300"
 stats() {  # name, command...
   local name=$1; shift
@@ -94,5 +94,5 @@ cd /tmp; rm -rf /tmp/tl; timeout 300 rocprofv3 --kernel-trace --output-format cs
 f=$(find /tmp/tl -name '*kernel_trace.csv' | head -1)
 if [ -n "$f" ]; then timeout 60 python $R/tools/iql_timeline.py parse $f > $OUT/iql_train_timeline.txt; fi
 cd $R
-timeout 900 python bench.py > $OUT/bench.json 2> $OUT/bench.err
+timeout 900 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 ls -la $OUT
