@@ -50,11 +50,17 @@ extern "C" {
 #define LO_OP_SUM 4          /* SumLinearOperator / PsdSum of up to LO_MAX_TERMS structured terms (+ one diagonal):
                               *   y = sum_i A_i v + d o v   (sum_linear_operator.py:47-51)              */
 #define LO_MAX_TERMS 4
+#define LO_OP_SKI_DIAG 5      /* AddedDiag(Interpolated(Toeplitz(t), W_l, W_r), Diag(d)):  y = W_l T W_r^T v + d o v
+                               * (interpolated_linear_operator.py:192-219 over toeplitz_linear_operator.py:42-53)      */
+#define LO_OP_TOEPLITZ_DIAG 6 /* AddedDiag(Toeplitz(t), Diag(d)):          y = T v + d o v   (T symmetric, N == M)  */
+#define LO_TOEPLITZ_MAX_M 16384 /* grid sizes the native Toeplitz product takes (larger: LO_ERR_UNSUPPORTED)         */
 
 /* diagonal storage */
 #define LO_DIAG_NONE 0  /* no diagonal term (plain Root / Dense / Kron operator)                    */
 #define LO_DIAG_FULL 1  /* DiagLinearOperator._diag [B, N]         (diag_linear_operator.py:25)      */
 #define LO_DIAG_CONST 2 /* ConstantDiagLinearOperator.diag_values [B] (diag_linear_operator.py:313)  */
+
+struct lo_interp_desc;
 
 /* Operator descriptor ("op-tree lowering" of an AddedDiag/Sum tree). */
 typedef struct lo_op_desc {
@@ -69,10 +75,30 @@ typedef struct lo_op_desc {
   const float* d;    /* diagonal, layout per diag_mode (NULL if LO_DIAG_NONE)                      */
   int32_t nterms;    /* SUM: number of terms (2 .. LO_MAX_TERMS); others 0                         */
   int32_t reserved;
-  const struct lo_op_desc* terms; /* SUM: HOST array of nterms descriptors of kind LOWRANK / DENSE / KRON with
+  union {
+    const struct lo_op_desc* terms; /* SUM: HOST array of nterms descriptors of kind LOWRANK / DENSE / KRON with
                       * diag_mode LO_DIAG_NONE and the same B, N (summed left to right, like the reference's
                       * Python sum()); the SUM's own (diag_mode, d) is the one diagonal of the tree */
+    const struct lo_interp_desc* interp; /* SKI (ABI 16): HOST pointer to the two interpolation matrices      */
+  };
+  /* ABI 16 kinds.  TOEPLITZ: A0 = first column t [B, M] of the symmetric Toeplitz matrix, R = M = N.
+   * SKI: A0 = t [B, M], R = M (grid size), n2 = J (interpolation points per row), `interp` as below.
+   * (The kinds reuse the existing fields: the size and layout of lo_op_desc are those of ABI 15.)              */
 } lo_op_desc;
+
+/* The interpolation matrices of an LO_OP_SKI_DIAG descriptor (interpolated_linear_operator.py:43-92): row n of W_l
+ * holds left_vals[b, n, :] at grid points left_idx[b, n, :] (int64, exactly as the operator stores them), W_r likewise.
+ * The right side may share the left side's pointers.  Index entries outside [0, M) contribute nothing (the kernels
+ * never read out of bounds).  Device pointers in a host struct.
+ * right_plan: NULL, or the grid-major copy of W_r that lo_interp_plan_build made from right_idx (same B, N, J, M) and
+ * the caller keeps across calls; with NULL every matvec plan (one per lo_matvec_f32 / solve call) builds its own.  */
+typedef struct lo_interp_desc {
+  const int64_t* left_idx;   /* [B, N, J] */
+  const float* left_vals;    /* [B, N, J] */
+  const int64_t* right_idx;  /* [B, N, J] */
+  const float* right_vals;   /* [B, N, J] */
+  const void* right_plan;    /* optional, see above */
+} lo_interp_desc;
 
 /* Callbacks for LO_OP_CALLBACK and for a user preconditioner closure.
  * v, y: device pointers [B, N, c] fp32 contiguous.  Must enqueue on `stream`.  Return 0 on success. */
@@ -589,6 +615,42 @@ size_t lo_lanczos_f64_workspace_bytes(int64_t B, int64_t N, int64_t P, int32_t m
 int lo_lanczos_tridiag_f64(const double* A, const double* diag, lo_matvec_cb_f64 matvec, void* matvec_user,
                            const double* init_vecs, int64_t B, int64_t N, int64_t P, int32_t max_iter, double tol,
                            double* q_mat, double* t_mat, int32_t* iters_out, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- Toeplitz / interpolation building blocks (ABI 16; csrc/lo_ski.hip) ------------------------------------------
+ * Symmetric Toeplitz T = toeplitz(t), t [B, M]; interpolation W [B, N, M] stored as idx int64 [B, N, J] and vals fp32
+ * [B, N, J] (utils/interpolation.py, utils/toeplitz.py).  Vectors [B, rows, c], c innermost.  Deterministic: the same
+ * inputs give bitwise the same outputs (no float atomics; W^T v runs as a segmented gather over a grid-major copy of
+ * W built with an integer counting sort, entries of one grid point in ascending (n, j) order).
+ *   lo_interp_f32          y [B, N, c] = W u,  u [B, M, c]                               (left_interp)
+ *   lo_interp_t_f32        out [B, M, c] = W^T v,  v [B, N, c]                           (left_t_interp)
+ *   lo_interp_plan_build   the grid-major copy of W (lo_interp_plan_bytes bytes, device memory the caller keeps) that
+ *                          lo_interp_t_planned_f32 and lo_interp_desc.right_plan reuse: W^T v without the per-call build.
+ *                          Cost of the build: linear in B N J, plus sum over grid points of count^2 / 64 (the rank sort
+ *                          that fixes the order of a grid point's entries, a wave per point): a grid point that
+ *                          receives k entries costs k^2 comparisons, so heavily repeated inputs make the build slow.
+ *   lo_toeplitz_mv_f32     y [B, M, c] = T u                                             (sym_toeplitz_matmul)
+ *   lo_toeplitz_bilinear_f32  g [B, M]: g_k = sum_s u_s^T (dT/dt_k) v_s, u, v [B, M, S]
+ *                          (sym_toeplitz_derivative_quadratic_form)
+ *   lo_interp_values_grad_f32  g [B, N, J]: g[n, j] = sum_s lv[n, s] R[idx[n, j], s],  lv [B, N, S], R [B, M, S]
+ *                          (the gather-dot of InterpolatedLinearOperator._bilinear_derivative)
+ * M <= LO_TOEPLITZ_MAX_M for the Toeplitz product and the lag correlation, else LO_ERR_UNSUPPORTED.               */
+int lo_interp_f32(const int64_t* idx, const float* vals, int64_t B, int64_t N, int64_t J, int64_t M, const float* u,
+                  int64_t c, float* y, void* stream);
+size_t lo_interp_t_workspace_bytes(int64_t B, int64_t N, int64_t J, int64_t M);
+int lo_interp_t_f32(const int64_t* idx, const float* vals, int64_t B, int64_t N, int64_t J, int64_t M, const float* v,
+                    int64_t c, float* out, void* ws, size_t ws_bytes, void* stream);
+size_t lo_interp_plan_bytes(int64_t B, int64_t N, int64_t J, int64_t M);
+int lo_interp_plan_build(const int64_t* idx, int64_t B, int64_t N, int64_t J, int64_t M, void* plan, size_t plan_bytes,
+                         void* stream);
+int lo_interp_t_planned_f32(const void* plan, const float* vals, int64_t B, int64_t N, int64_t J, int64_t M,
+                            const float* v, int64_t c, float* out, void* stream);
+size_t lo_toeplitz_workspace_bytes(int64_t B, int64_t M, int64_t c);
+int lo_toeplitz_mv_f32(const float* t, int64_t B, int64_t M, const float* u, int64_t c, float* y, void* ws,
+                       size_t ws_bytes, void* stream);
+int lo_toeplitz_bilinear_f32(const float* u, const float* v, int64_t B, int64_t M, int64_t S, float* g, void* ws,
+                             size_t ws_bytes, void* stream);
+int lo_interp_values_grad_f32(const int64_t* idx, int64_t B, int64_t N, int64_t J, int64_t M, const float* lv,
+                              const float* R, int64_t S, float* g, void* stream);
 
 /* ---- measurement aid (no reference counterpart) ------------------------------------------------ */
 /* Opt-in HIP-event timing of every kernel launch of the library, recorded on the launch stream.

@@ -18,8 +18,10 @@ _lib = None
 
 LO_OP_LOWRANK_DIAG, LO_OP_DENSE_DIAG, LO_OP_KRON_DIAG, LO_OP_CALLBACK, LO_OP_SUM = 0, 1, 2, 3, 4
 LO_MAX_TERMS = 4
+LO_OP_SKI_DIAG, LO_OP_TOEPLITZ_DIAG = 5, 6
+LO_TOEPLITZ_MAX_M = 16384
 LO_DIAG_NONE, LO_DIAG_FULL, LO_DIAG_CONST = 0, 1, 2
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 LO_ERR_UNSUPPORTED = -4
 LO_FUSED_OK, LO_FUSED_EARLY_STOP, LO_FUSED_CONTINUE, LO_FUSED_TIMEOUT = 0, 1, 2, 3
@@ -49,6 +51,9 @@ EXPORTS = [
     "lo_bilinear_kron_workspace_bytes", "lo_bilinear_kron_f32", "lo_root_apply_add_f32",
     "lo_minres_workspace_bytes", "lo_minres_f32",
     "lo_probe_vectors_workspace_bytes", "lo_probe_vectors_f32", "lo_iql_backward_factors_f32",
+    "lo_interp_f32", "lo_interp_t_workspace_bytes", "lo_interp_t_f32", "lo_interp_plan_bytes", "lo_interp_plan_build",
+    "lo_interp_t_planned_f32", "lo_toeplitz_workspace_bytes", "lo_toeplitz_mv_f32",
+    "lo_toeplitz_bilinear_f32", "lo_interp_values_grad_f32",
     "lo_prof_enable", "lo_prof_report", "lo_hbm_triad_f32", "lo_hbm_copy_f32", "lo_hbm_stream_dev", "lo_peer_gather_set",
 ]
 
@@ -67,6 +72,13 @@ class OpDesc(C.Structure):
 OpDesc._fields_ = [("kind", C.c_int32), ("diag_mode", C.c_int32), ("B", C.c_int64), ("N", C.c_int64), ("R", C.c_int64),
                    ("n2", C.c_int64), ("A0", C.c_void_p), ("A1", C.c_void_p), ("d", C.c_void_p),
                    ("nterms", C.c_int32), ("reserved", C.c_int32), ("terms", C.POINTER(OpDesc))]
+
+
+class InterpDesc(C.Structure):
+    """lo_interp_desc (include/lo_amd.h): the interpolation matrices of an LO_OP_SKI_DIAG descriptor, reached through the
+    descriptor's `terms` slot (a union in C)."""
+    _fields_ = [("left_idx", C.c_void_p), ("left_vals", C.c_void_p), ("right_idx", C.c_void_p),
+                ("right_vals", C.c_void_p), ("right_plan", C.c_void_p)]
 
 
 class PrecondDesc(C.Structure):
@@ -336,6 +348,31 @@ def load():
     lib.lo_iql_backward_factors_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_float, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    i64 = C.c_int64
+    lib.lo_interp_f32.restype = C.c_int
+    lib.lo_interp_f32.argtypes = [C.c_void_p, C.c_void_p, i64, i64, i64, i64, C.c_void_p, i64, C.c_void_p, C.c_void_p]
+    lib.lo_interp_t_workspace_bytes.restype = sz
+    lib.lo_interp_t_workspace_bytes.argtypes = [i64, i64, i64, i64]
+    lib.lo_interp_t_f32.restype = C.c_int
+    lib.lo_interp_t_f32.argtypes = [C.c_void_p, C.c_void_p, i64, i64, i64, i64, C.c_void_p, i64, C.c_void_p, C.c_void_p,
+                                    sz, C.c_void_p]
+    lib.lo_interp_plan_bytes.restype = sz
+    lib.lo_interp_plan_bytes.argtypes = [i64, i64, i64, i64]
+    lib.lo_interp_plan_build.restype = C.c_int
+    lib.lo_interp_plan_build.argtypes = [C.c_void_p, i64, i64, i64, i64, C.c_void_p, sz, C.c_void_p]
+    lib.lo_interp_t_planned_f32.restype = C.c_int
+    lib.lo_interp_t_planned_f32.argtypes = [C.c_void_p, C.c_void_p, i64, i64, i64, i64, C.c_void_p, i64, C.c_void_p,
+                                            C.c_void_p]
+    lib.lo_toeplitz_workspace_bytes.restype = sz
+    lib.lo_toeplitz_workspace_bytes.argtypes = [i64, i64, i64]
+    lib.lo_toeplitz_mv_f32.restype = C.c_int
+    lib.lo_toeplitz_mv_f32.argtypes = [C.c_void_p, i64, i64, C.c_void_p, i64, C.c_void_p, C.c_void_p, sz, C.c_void_p]
+    lib.lo_toeplitz_bilinear_f32.restype = C.c_int
+    lib.lo_toeplitz_bilinear_f32.argtypes = [C.c_void_p, C.c_void_p, i64, i64, i64, C.c_void_p, C.c_void_p, sz,
+                                             C.c_void_p]
+    lib.lo_interp_values_grad_f32.restype = C.c_int
+    lib.lo_interp_values_grad_f32.argtypes = [C.c_void_p, i64, i64, i64, i64, C.c_void_p, C.c_void_p, i64, C.c_void_p,
+                                              C.c_void_p]
     lib.lo_hbm_triad_f32.restype = C.c_int
     lib.lo_hbm_triad_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, sz, C.c_void_p]
     lib.lo_hbm_copy_f32.restype = C.c_int

@@ -155,6 +155,14 @@ struct MatvecPlan {
   int nterms;
   MatvecPlan* sub;
   float* ytmp;        // [B,N,c]
+  // LO_OP_SKI_DIAG / LO_OP_TOEPLITZ_DIAG (lo_ski.hip): the interpolation matrices, the grid-major copy of W_r built by
+  // matvec_plan_init, the grid-sized intermediates u = W_r^T v and T u, and the split-k partials of the Toeplitz product
+  lo_interp_desc ski;
+  int* csr_ptr;       // [B, M+1]
+  int* csr_ids;       // [B, N*J]
+  float* ski_u;       // [B, M, c]
+  float* ski_t;       // [B, M, c]
+  float* tz_part;
 };
 void matvec_plan_free(MatvecPlan* pl);
 // releases a plan's sub-plans on every exit path of the function that owns it
@@ -180,6 +188,11 @@ bool matvec_can_fuse_pupdate(const MatvecPlan* pl);
 // p = z + beta p (first: p = z); y = A p; dot partials
 int matvec_run_pupdate(const MatvecPlan* pl, float* p, const float* z, const float* beta, int first, float* y,
                        float* dot_part, const int* stop, hipStream_t st);
+
+// ---- SKI / Toeplitz (lo_ski.hip) ------------------------------------------------------------------------------------
+size_t ski_plan_bytes(const lo_op_desc* op, int64_t c);
+int ski_plan_init(MatvecPlan* pl, const lo_op_desc* op, int64_t c, Arena* ar, hipStream_t st);
+int ski_matvec_run(const MatvecPlan* pl, const float* v, float* y, const int* stop, hipStream_t st);
 
 // dense / kron kernels
 int dense_matvec(const float* K, const float* d, int dd_mode, const float* v, float* y, float* dot_part, int64_t B,

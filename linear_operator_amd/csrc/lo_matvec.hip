@@ -40,6 +40,8 @@ size_t matvec_plan_bytes(const lo_op_desc* op, int64_t c, Split sp) {
   } else if (op->kind == LO_OP_DENSE_DIAG) {
     const int ks = dense_mfma_slices(op->B, op->N, c);
     if (ks > 1) ar.take<float>((size_t)ks * op->B * op->N * c);
+  } else if (op->kind == LO_OP_SKI_DIAG || op->kind == LO_OP_TOEPLITZ_DIAG) {
+    return ski_plan_bytes(op, c) + 256;
   }
   return ar.off + 256;
 }
@@ -61,6 +63,9 @@ int matvec_plan_init(MatvecPlan* pl, const lo_op_desc* op, lo_matvec_cb cb, void
   pl->nterms = 0;
   pl->sub = nullptr;
   pl->ytmp = nullptr;
+  pl->ski = lo_interp_desc{};
+  pl->csr_ptr = pl->csr_ids = nullptr;
+  pl->ski_u = pl->ski_t = pl->tz_part = nullptr;
   if (op->B < 1 || op->N < 1 || c < 1) return LO_ERR_BADARG;
   if (op->diag_mode != LO_DIAG_NONE && !op->d) return LO_ERR_BADARG;
   switch (op->kind) {
@@ -96,6 +101,12 @@ int matvec_plan_init(MatvecPlan* pl, const lo_op_desc* op, lo_matvec_cb cb, void
       if (!op->A0 || !op->A1 || op->R * op->n2 != op->N) return LO_ERR_BADARG;
       pl->kron_tmp = ar->take<float>((size_t)op->B * op->N * c * (kron_mfma_cols_ok((int)op->R, (int)op->n2, c) ? 2 : 1));
       pl->S_dot = kron_S_dot((int)op->R, (int)op->n2, c, sp.S);
+      break;
+    }
+    case LO_OP_SKI_DIAG:
+    case LO_OP_TOEPLITZ_DIAG: {
+      const int rc = ski_plan_init(pl, op, c, ar, st);
+      if (rc) return rc;
       break;
     }
     case LO_OP_CALLBACK:
@@ -169,6 +180,11 @@ int matvec_run(const MatvecPlan* pl, const float* v, float* y, float* dot_part, 
       }
       if (dot_part) rc = vec_dot_part(v, y, pl->c, dot_part, op.B, op.N, pl->sp, stop, st);
       return rc;
+    case LO_OP_SKI_DIAG:  // W_l T W_r^T v + d o v: segmented gather over the grid-major W_r, Toeplitz product, gather
+    case LO_OP_TOEPLITZ_DIAG:
+      rc = ski_matvec_run(pl, v, y, stop, st);
+      if (!rc && dot_part) rc = vec_dot_part(v, y, pl->c, dot_part, op.B, op.N, pl->sp, stop, st);
+      return rc;
     case LO_OP_CALLBACK:
       rc = pl->cb(pl->cb_user, v, y, op.B, op.N, pl->c, (void*)st);
       if (rc) return LO_ERR_LAUNCH;
@@ -205,7 +221,7 @@ using namespace lo;
 
 extern "C" {
 
-int lo_abi_version(void) { return 15; }
+int lo_abi_version(void) { return 16; }
 const char* lo_target_arch(void) { return "gfx950"; }
 
 size_t lo_matvec_workspace_bytes(const lo_op_desc* op, int64_t c) {

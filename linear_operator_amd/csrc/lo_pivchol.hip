@@ -5,6 +5,11 @@
 //   Root/LowRankRoot: row[i] = sum_r C[p,r] C[i,r]          (root_linear_operator.py:37-50, diag :22-28)
 //   Dense:            row[i] = K[p,i]                        (dense_linear_operator.py:47-50, diag :37-40)
 //   Kron:             row[i] = K1[p1,i1] K2[p2,i2]           (kronecker_product_linear_operator.py:198-216)
+//   Toeplitz:         row[i] = t[|p - i|]                    (toeplitz_linear_operator.py:38-40, diag :25-31)
+//   SKI:              row[i] = sum_b sum_a t[|li[p,a] - ri[i,b]|] (lv[p,a] rv[i,b])
+//                                                            (interpolated_linear_operator.py:130-144); the diagonal
+//                     is the reference's APPROXIMATE one, (W_l sqrt(t0)) o (W_r sqrt(t0)) (:94-101,
+//                     functions/_pivoted_cholesky.py:25): pivots are chosen on it, rows come from the true matrix
 // Integer results (pivots, permutation) must match the CPU path bit for bit, so every value that feeds
 // a pivot decision is computed per element in a FIXED order with individually rounded operations
 // (products rounded before summation, sequential in r and in j; this file is compiled with
@@ -39,6 +44,7 @@ struct PcDevT {
   // reference, sum_linear_operator.py:31-45): one entry for a plain operator
   int nterms;
   lo_op_desc terms[LO_MAX_TERMS];
+  lo_interp_desc ski;  // LO_OP_SKI_DIAG: the interpolation matrices (a device-side copy of the host struct op.interp)
   int64_t B, N;
   int S, rows;     // position split
   int max_rank;
@@ -111,6 +117,25 @@ __device__ __forceinline__ T src_diag(const PcDevT<T>& d, const lo_op_desc& op, 
     return A0[((size_t)b * d.N + i) * d.N + i];
   } else if (op.kind == LO_OP_CALLBACK) {  // generic operator: A1 = matrix._diagonal(), A0 = the fetched pivot rows
     return A1[(size_t)b * d.N + i];
+  } else if (op.kind == LO_OP_TOEPLITZ_DIAG) {
+    return A0[(size_t)b * op.R];
+  } else if (op.kind == LO_OP_SKI_DIAG) {  // (left_interp(li, lv, sqrt t0) * left_interp(ri, rv, sqrt t0)), :94-101
+    // (an index outside [0, M) contributes nothing, as in the rows below)
+    const int J = (int)op.n2;
+    const int64_t M = op.R;
+    const T s = pc_sqrt<T>(A0[(size_t)b * M]);
+    const int64_t* li = d.ski.left_idx + ((size_t)b * d.N + i) * J;
+    const int64_t* ri = d.ski.right_idx + ((size_t)b * d.N + i) * J;
+    const T* lv = pc_ptr<T>(d.ski.left_vals) + ((size_t)b * d.N + i) * J;
+    const T* rv = pc_ptr<T>(d.ski.right_vals) + ((size_t)b * d.N + i) * J;
+    T l = T(0), r = T(0);
+    for (int j = 0; j < J; ++j) {
+      const T lt = (li[j] >= 0 && li[j] < M) ? s * lv[j] : T(0);
+      const T rt = (ri[j] >= 0 && ri[j] < M) ? s * rv[j] : T(0);
+      l = (j == 0) ? lt : l + lt;
+      r = (j == 0) ? rt : r + rt;
+    }
+    return l * r;
   } else {
     const int n1 = (int)op.R, n2 = (int)op.n2;
     const int i1 = i / n2, i2 = i % n2;
@@ -369,6 +394,27 @@ __global__ __launch_bounds__(kThreads) void k_pc_update(PcDevT<T> d, int m) {
           tv = pc_ptr<T>(tm.A0)[((size_t)b * N + pim) * N + i];
         } else if (tm.kind == LO_OP_CALLBACK) {
           tv = pc_ptr<T>(tm.A0)[(size_t)b * N + i];  // row pi_m of this member, fetched by the host callback for this pivot
+        } else if (tm.kind == LO_OP_TOEPLITZ_DIAG) {
+          const int lag = pim > i ? pim - i : i - pim;
+          tv = pc_ptr<T>(tm.A0)[(size_t)b * tm.R + lag];
+        } else if (tm.kind == LO_OP_SKI_DIAG) {
+          // base_vals[b', a] * (lv[p, a] rv[i, b']) summed over both (:139-144); out-of-grid entries contribute nothing
+          const int J = (int)tm.n2;
+          const int64_t M = tm.R;
+          const T* col = pc_ptr<T>(tm.A0) + (size_t)b * M;
+          const int64_t* li = d.ski.left_idx + ((size_t)b * N + pim) * J;
+          const T* lv = pc_ptr<T>(d.ski.left_vals) + ((size_t)b * N + pim) * J;
+          const int64_t* ri = d.ski.right_idx + ((size_t)b * N + i) * J;
+          const T* rv = pc_ptr<T>(d.ski.right_vals) + ((size_t)b * N + i) * J;
+          for (int bb = 0; bb < J; ++bb) {
+            const int64_t q = ri[bb];
+            for (int a = 0; a < J; ++a) {
+              const int64_t p = li[a];
+              const int64_t lag = p > q ? p - q : q - p;
+              const T base = (p >= 0 && p < M && q >= 0 && q < M) ? col[lag] : T(0);
+              tv = (bb == 0 && a == 0) ? base * (lv[a] * rv[bb]) : tv + base * (lv[a] * rv[bb]);
+            }
+          }
         } else {
           const int n1 = (int)tm.R, n2 = (int)tm.n2;
           const int p1 = pim / n2, p2 = pim % n2, i1 = i / n2, i2 = i % n2;
@@ -421,6 +467,7 @@ static void pc_layout(const lo_op_desc* op, int max_rank, Arena& ar, PcDevT<T>* 
     d->nterms = 1;
     d->terms[0] = *op;
   }
+  d->ski = (op->kind == LO_OP_SKI_DIAG && op->interp) ? *op->interp : lo_interp_desc{};
   d->B = B; d->N = N; d->S = sp.S; d->rows = sp.rows; d->max_rank = max_rank;
   d->ctrl = ar.take<PcCtrl>(1);
   d->diag = ar.take<T>((size_t)B * N);
@@ -528,6 +575,12 @@ static int pc_check_desc(const lo_op_desc* op) {
           t.N != op->N)
         return LO_ERR_BADARG;
     }
+  } else if (op->kind == LO_OP_TOEPLITZ_DIAG) {
+    if (!op->A0 || op->R != op->N) return LO_ERR_BADARG;
+  } else if (op->kind == LO_OP_SKI_DIAG) {
+    const lo_interp_desc* w = op->interp;
+    if (!op->A0 || op->R < 1 || op->n2 < 1 || !w || !w->left_idx || !w->left_vals || !w->right_idx || !w->right_vals)
+      return LO_ERR_BADARG;
   } else if (op->kind != LO_OP_LOWRANK_DIAG && op->kind != LO_OP_DENSE_DIAG && op->kind != LO_OP_KRON_DIAG) {
     return LO_ERR_UNSUPPORTED;
   }
@@ -596,6 +649,7 @@ size_t lo_pivoted_cholesky_f64_workspace_bytes(const lo_op_desc* op, int32_t max
 int lo_pivoted_cholesky_f64(const lo_op_desc* op, int32_t max_rank, double error_tol, double* L_rows, int64_t* perm,
                             int32_t* rank_out, void* ws, size_t ws_bytes, void* stream) {
   if (!op || !L_rows || !perm || !rank_out || !ws || max_rank < 1) return LO_ERR_BADARG;
+  if (op->kind == LO_OP_SKI_DIAG || op->kind == LO_OP_TOEPLITZ_DIAG) return LO_ERR_UNSUPPORTED;  // (fp32 kinds)
   if (const int rc = pc_check_desc(op)) return rc;
   return pc_stream_t<double>(op, nullptr, nullptr, nullptr, max_rank, error_tol, L_rows, perm, rank_out, ws, ws_bytes,
                              (hipStream_t)stream);

@@ -31,6 +31,8 @@ class OperatorDescriptor:
     n2: int = 0
     batch_shape: torch.Size = torch.Size()
     terms: tuple = ()  # LO_OP_SUM: the summed structured terms (descriptors without a diagonal), left to right
+    interp: tuple = ()  # LO_OP_SKI_DIAG: (left_idx, left_vals, right_idx, right_vals), [B, N, J] int64 / fp32
+    interp_plan: Optional[torch.Tensor] = None  # LO_OP_SKI_DIAG: grid-major copy of W_r kept across calls (interp_plan)
 
     @property
     def device(self):
@@ -39,6 +41,8 @@ class OperatorDescriptor:
                 return t.device
         for term in self.terms:
             return term.device
+        for t in self.interp:
+            return t.device
         raise ValueError("empty descriptor")
 
     def c_struct(self) -> _hip.OpDesc:
@@ -52,11 +56,16 @@ class OperatorDescriptor:
             arr = (_hip.OpDesc * len(self.terms))(*[t.c_struct() for t in self.terms])
             s.terms = C.cast(arr, C.POINTER(_hip.OpDesc))
             s._terms_keepalive = arr
+        if self.interp:  # the union slot `interp`: a host struct of the four device pointers
+            w = _hip.InterpDesc(*[t.data_ptr() for t in self.interp],
+                                None if self.interp_plan is None else self.interp_plan.data_ptr())
+            s.terms = C.cast(C.pointer(w), C.POINTER(_hip.OpDesc))
+            s._interp_keepalive = w
         return s
 
     def without_diag(self) -> "OperatorDescriptor":
         return OperatorDescriptor(self.kind, self.B, self.N, self.A0, self.A1, None, _hip.LO_DIAG_NONE, self.R,
-                                  self.n2, self.batch_shape, self.terms)
+                                  self.n2, self.batch_shape, self.terms, self.interp, self.interp_plan)
 
 
 def sum_descriptor(terms, d: Optional[torch.Tensor] = None, const_diag: bool = False):
@@ -105,6 +114,163 @@ def kron_diag_descriptor(K1: torch.Tensor, K2: torch.Tensor, d: Optional[torch.T
     Bm = _flat(K2, 2)
     return _with_diag(OperatorDescriptor(_hip.LO_OP_KRON_DIAG, A.shape[0], n1 * n2, A0=A, A1=Bm, R=n1, n2=n2,
                                          batch_shape=batch), d, const_diag)
+
+
+def toeplitz_diag_descriptor(column: torch.Tensor, d: Optional[torch.Tensor], const_diag: bool = False):
+    """AddedDiag(Toeplitz(column), Diag(d)) (or the Toeplitz operator alone): y = T v + d o v, column [*batch, M].
+    None when M exceeds the native Toeplitz product's LO_TOEPLITZ_MAX_M (the caller takes the torch composition)."""
+    _hip.require_hip(column, d)
+    M = column.shape[-1]
+    if M > _hip.LO_TOEPLITZ_MAX_M:
+        return None
+    col = _flat(column, 1)
+    return _with_diag(OperatorDescriptor(_hip.LO_OP_TOEPLITZ_DIAG, col.shape[0], M, A0=col, R=M,
+                                         batch_shape=column.shape[:-1]), d, const_diag)
+
+
+def ski_diag_descriptor(column: torch.Tensor, left_idx: torch.Tensor, left_vals: torch.Tensor,
+                        right_idx: torch.Tensor, right_vals: torch.Tensor, d: Optional[torch.Tensor],
+                        const_diag: bool = False, right_plan: Optional[torch.Tensor] = None):
+    """AddedDiag(Interpolated(Toeplitz(column), W_l, W_r), Diag(d)): y = W_l T W_r^T v + d o v.  column [*batch, M],
+    indices int64 / values fp32 [*batch, N, J] (one batch shape for all, square: both sides N rows).  None when the
+    shapes are outside what the kind takes.  `right_plan`: interp_plan(right_idx, M) of the same batch, kept by the
+    caller (else every matvec / solve builds the grid-major copy of W_r itself)."""
+    _hip.require_hip(column, left_vals, right_vals, d)
+    batch = column.shape[:-1]
+    M = column.shape[-1]
+    N, J = left_idx.shape[-2:]
+    if (M > _hip.LO_TOEPLITZ_MAX_M or right_idx.shape[-2:] != (N, J) or left_idx.dtype != torch.int64
+            or right_idx.dtype != torch.int64 or not left_idx.is_cuda or not right_idx.is_cuda):
+        return None
+    col = _flat(column, 1)
+    B = col.shape[0]
+
+    def flat(t):
+        return t.expand(*batch, N, J).contiguous().reshape(B, N, J)
+
+    li, lv = flat(left_idx), flat(left_vals)
+    shared = right_idx is left_idx and right_vals is left_vals  # (one copy: the kernels read the same arrays twice)
+    ri, rv = (li, lv) if shared else (flat(right_idx), flat(right_vals))
+    return _with_diag(OperatorDescriptor(_hip.LO_OP_SKI_DIAG, B, N, A0=col, R=M, n2=J, batch_shape=batch,
+                                         interp=(li, lv, ri, rv), interp_plan=right_plan), d, const_diag)
+
+
+def interp_plan_build(idx: torch.Tensor, M: int) -> torch.Tensor:
+    """The grid-major copy of W (idx int64 [B, N, J], grid of M points) as a device byte tensor (lo_interp_plan_build)."""
+    lib = _hip.load()
+    idx = idx.contiguous()
+    B, N, J = idx.shape
+    plan = _hip.workspace(lib.lo_interp_plan_bytes(B, N, J, M), idx.device)
+    _hip.check(lib.lo_interp_plan_build(_hip.ptr(idx), B, N, J, M, _hip.ptr(plan), plan.numel(),
+                                        _hip.stream_ptr(idx.device)), "lo_interp_plan_build")
+    return plan
+
+
+# Memo of the grid-major copies, keyed on the index tensor the operator holds (address, version counter, layout) and
+# the batch / grid the copy was built for; the entry keeps the tensor alive, so its address cannot be reused by other
+# data, and an in-place update bumps the version counter (writes through `.data` do not: clear_interp_plan_memo()).
+INTERP_PLAN_MEMO_SIZE = 4
+_interp_plan_memo: "list[tuple]" = []
+
+
+def interp_plan(idx: torch.Tensor, batch_shape, M: int) -> Optional[torch.Tensor]:
+    """interp_plan_build of `idx` [*b, N, J] expanded to batch_shape, memoised across calls; None for inference
+    tensors (no version counter: the caller lets every plan build its own copy)."""
+    if idx.is_inference():
+        return None
+    key = (idx.data_ptr(), idx._version, tuple(idx.shape), tuple(idx.stride()), tuple(batch_shape), int(M))
+    for entry in _interp_plan_memo:
+        if entry[0] == key:
+            return entry[2]
+    N, J = idx.shape[-2:]
+    plan = interp_plan_build(idx.expand(*batch_shape, N, J).reshape(-1, N, J), M)
+    _interp_plan_memo.insert(0, (key, idx, plan))
+    del _interp_plan_memo[INTERP_PLAN_MEMO_SIZE:]
+    return plan
+
+
+def clear_interp_plan_memo():
+    _interp_plan_memo.clear()
+
+
+def interp_t_planned(plan: torch.Tensor, vals: torch.Tensor, v: torch.Tensor, M: int) -> torch.Tensor:
+    """W^T v from a kept grid-major copy (interp_plan): vals [B, N, J], v [B, N, c] -> [B, M, c]."""
+    lib = _hip.load()
+    _hip.require_hip(vals, v)
+    B, N, J = vals.shape
+    c = v.shape[-1]
+    vals, v = vals.contiguous(), v.contiguous()
+    out = torch.empty(B, M, c, dtype=torch.float32, device=v.device)
+    _hip.check(lib.lo_interp_t_planned_f32(_hip.ptr(plan), _hip.ptr(vals), B, N, J, M, _hip.ptr(v), c, _hip.ptr(out),
+                                           _hip.stream_ptr(v.device)), "lo_interp_t_planned_f32")
+    return out
+
+
+def interp(idx: torch.Tensor, vals: torch.Tensor, u: torch.Tensor) -> torch.Tensor:
+    """W u: idx int64 / vals fp32 [B, N, J], u [B, M, c] -> [B, N, c] (lo_interp_f32)."""
+    lib = _hip.load()
+    _hip.require_hip(vals, u)
+    B, N, J = idx.shape
+    M, c = u.shape[-2:]
+    idx, vals, u = idx.contiguous(), vals.contiguous(), u.contiguous()
+    y = torch.empty(B, N, c, dtype=torch.float32, device=u.device)
+    _hip.check(lib.lo_interp_f32(_hip.ptr(idx), _hip.ptr(vals), B, N, J, M, _hip.ptr(u), c, _hip.ptr(y),
+                                 _hip.stream_ptr(u.device)), "lo_interp_f32")
+    return y
+
+
+def interp_t(idx: torch.Tensor, vals: torch.Tensor, v: torch.Tensor, M: int) -> torch.Tensor:
+    """W^T v: idx / vals [B, N, J], v [B, N, c] -> [B, M, c] (lo_interp_t_f32, deterministic)."""
+    lib = _hip.load()
+    _hip.require_hip(vals, v)
+    B, N, J = idx.shape
+    c = v.shape[-1]
+    idx, vals, v = idx.contiguous(), vals.contiguous(), v.contiguous()
+    out = torch.empty(B, M, c, dtype=torch.float32, device=v.device)
+    ws = _hip.workspace(lib.lo_interp_t_workspace_bytes(B, N, J, M), v.device)
+    _hip.check(lib.lo_interp_t_f32(_hip.ptr(idx), _hip.ptr(vals), B, N, J, M, _hip.ptr(v), c, _hip.ptr(out),
+                                   _hip.ptr(ws), ws.numel(), _hip.stream_ptr(v.device)), "lo_interp_t_f32")
+    return out
+
+
+def toeplitz_mv(column: torch.Tensor, u: torch.Tensor) -> torch.Tensor:
+    """T u for the symmetric Toeplitz matrix of column [B, M]; u [B, M, c] (lo_toeplitz_mv_f32)."""
+    lib = _hip.load()
+    _hip.require_hip(column, u)
+    B, M = column.shape
+    c = u.shape[-1]
+    column, u = column.contiguous(), u.contiguous()
+    y = torch.empty(B, M, c, dtype=torch.float32, device=u.device)
+    ws = _hip.workspace(lib.lo_toeplitz_workspace_bytes(B, M, c), u.device)
+    _hip.check(lib.lo_toeplitz_mv_f32(_hip.ptr(column), B, M, _hip.ptr(u), c, _hip.ptr(y), _hip.ptr(ws), ws.numel(),
+                                      _hip.stream_ptr(u.device)), "lo_toeplitz_mv_f32")
+    return y
+
+
+def toeplitz_bilinear(u: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
+    """g [B, M]: g_k = sum_s u_s^T (dT/dt_k) v_s for u, v [B, M, S] (lo_toeplitz_bilinear_f32)."""
+    lib = _hip.load()
+    _hip.require_hip(u, v)
+    B, M, S = u.shape
+    u, v = u.contiguous(), v.contiguous()
+    g = torch.empty(B, M, dtype=torch.float32, device=u.device)
+    ws = _hip.workspace(lib.lo_toeplitz_workspace_bytes(B, M, 1), u.device)
+    _hip.check(lib.lo_toeplitz_bilinear_f32(_hip.ptr(u), _hip.ptr(v), B, M, S, _hip.ptr(g), _hip.ptr(ws), ws.numel(),
+                                            _hip.stream_ptr(u.device)), "lo_toeplitz_bilinear_f32")
+    return g
+
+
+def interp_values_grad(idx: torch.Tensor, lv: torch.Tensor, R: torch.Tensor) -> torch.Tensor:
+    """g [B, N, J]: g[n, j] = sum_s lv[n, s] R[idx[n, j], s]; idx [B, N, J], lv [B, N, S], R [B, M, S]."""
+    lib = _hip.load()
+    _hip.require_hip(lv, R)
+    B, N, J = idx.shape
+    M, S = R.shape[-2:]
+    idx, lv, R = idx.contiguous(), lv.contiguous(), R.contiguous()
+    g = torch.empty(B, N, J, dtype=torch.float32, device=R.device)
+    _hip.check(lib.lo_interp_values_grad_f32(_hip.ptr(idx), B, N, J, M, _hip.ptr(lv), _hip.ptr(R), S, _hip.ptr(g),
+                                             _hip.stream_ptr(R.device)), "lo_interp_values_grad_f32")
+    return g
 
 
 def _with_diag(desc: OperatorDescriptor, d, const_diag):

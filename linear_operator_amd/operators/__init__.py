@@ -4,6 +4,7 @@ from .added_diag_linear_operator import AddedDiagLinearOperator
 from .dense_linear_operator import DenseLinearOperator, to_linear_operator
 from .diag_linear_operator import ConstantDiagLinearOperator, DiagLinearOperator
 from .identity_linear_operator import IdentityLinearOperator
+from .interpolated_linear_operator import InterpolatedLinearOperator
 from .kronecker_product_linear_operator import KroneckerProductDiagLinearOperator, KroneckerProductLinearOperator
 from .kronecker_product_added_diag_linear_operator import KroneckerProductAddedDiagLinearOperator
 from .linear_operator_representation_tree import LinearOperatorRepresentationTree
@@ -11,6 +12,7 @@ from .low_rank_root_added_diag_linear_operator import LowRankRootAddedDiagLinear
 from .matmul_linear_operator import MatmulLinearOperator
 from .root_linear_operator import LowRankRootLinearOperator, RootLinearOperator
 from .sum_linear_operator import PsdSumLinearOperator, SumLinearOperator
+from .toeplitz_linear_operator import ToeplitzLinearOperator
 from .triangular_linear_operator import TriangularLinearOperator
 
 __all__ = [
@@ -18,5 +20,6 @@ __all__ = [
     "LinearOperator", "to_dense", "to_linear_operator", "AddedDiagLinearOperator", "DenseLinearOperator",
     "DiagLinearOperator", "ConstantDiagLinearOperator", "IdentityLinearOperator", "KroneckerProductLinearOperator", "KroneckerProductDiagLinearOperator",
     "LinearOperatorRepresentationTree", "RootLinearOperator", "LowRankRootLinearOperator", "SumLinearOperator",
-    "PsdSumLinearOperator", "TriangularLinearOperator", "MatmulLinearOperator",
+    "PsdSumLinearOperator", "TriangularLinearOperator", "MatmulLinearOperator", "InterpolatedLinearOperator",
+    "ToeplitzLinearOperator",
 ]

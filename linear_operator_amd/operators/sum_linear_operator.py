@@ -60,8 +60,9 @@ class SumLinearOperator(LinearOperator):
         terms = []
         for op in others:
             desc = op._kernel_descriptor(batch_shape)
-            if desc is None or desc.diag_mode != 0 or desc.kind == K._hip.LO_OP_SUM:
-                return None
+            if desc is None or desc.diag_mode != 0 or desc.kind not in (
+                    K._hip.LO_OP_LOWRANK_DIAG, K._hip.LO_OP_DENSE_DIAG, K._hip.LO_OP_KRON_DIAG):
+                return None  # (a sum's terms: low-rank / dense / Kronecker; SKI and Toeplitz terms take the closure)
             terms.append(desc)
         if len({(t.B, t.N) for t in terms}) != 1:
             return None
