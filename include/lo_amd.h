@@ -269,18 +269,19 @@ typedef struct lo_cg_plan {
   int32_t poll_chunk;           /* streaming iterations enqueued between two reads of the control block              */
   int32_t first_stop_iteration; /* min(10, max_iter-1), raised to min(max_tridiag_iter, max_iter-1) with tridiagonals
                                  * (linear_cg.py:302-308)                                                            */
-  int32_t reserved;
-  int32_t rspace;               /* round 5 (needs lo_precond_desc.RS): the result-only first pass runs the iterations on
+  int32_t streaming_iterations; /* lo_cg_last_executed: streaming iterations enqueued after the resident phase (all of
+                                 * them when resident == 0); 0 in a plan                                              */
+  int32_t rspace;              /* round 5 (needs lo_precond_desc.RS): the result-only first pass runs the iterations on
                                  * R + 1 coordinates (csrc/lo_rspace.hip): 2 = the single column inside the resident
                                  * launch of `serial_engine` (one all-reduce per member), 1 = ALL columns in three
                                  * streaming launches (k_rs_part / k_rs_iter / k_rs_apply) -- lockstep_cols /
                                  * serial_engine then name the engines of the repeat with the state                  */
-  int32_t reserved2;            /* lo_cg_last_executed: 1 = the rspace == 2 launch ran the diagonal form (RSD)           */
+  int32_t rspace_diag;          /* lo_cg_last_executed: 1 = the rspace == 2 launch ran the diagonal form (RSD)           */
 } lo_cg_plan;
 int lo_cg_plan_f32(const lo_op_desc* op, const lo_precond_desc* pre, int has_precond_cb, int has_x0,
                    const lo_cg_params* prm, int cus, lo_cg_plan* plan);
-/* The plan as the calling thread's last successful lo_cg_solve_f32 EXECUTED it (after run-time fall-backs; `reserved`
- * = streaming iterations enqueued after the resident phase): the GPU tests compare it with lo_cg_plan_f32.          */
+/* The plan as the calling thread's last successful lo_cg_solve_f32 EXECUTED it (after run-time fall-backs, with
+ * `streaming_iterations` and `rspace_diag` filled in): the GPU tests compare it with lo_cg_plan_f32.          */
 int lo_cg_last_executed(lo_cg_plan* plan);
 
 /* ---- fused end-to-end solve: ONE resident launch ------------------------------------------------- */

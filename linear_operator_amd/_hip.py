@@ -106,7 +106,8 @@ class CgPlan(C.Structure):
     """lo_cg_plan (include/lo_amd.h): the engine selection of lo_cg_solve_f32."""
     _fields_ = [(n, C.c_int32) for n in (
         "resident", "resident_iterations", "lockstep_cols", "lockstep_group", "serial_engine", "serial_group", "lean",
-        "needs_q", "streaming_precond", "poll_chunk", "first_stop_iteration", "reserved", "rspace", "reserved2")]
+        "needs_q", "streaming_precond", "poll_chunk", "first_stop_iteration", "streaming_iterations", "rspace",
+        "rspace_diag")]
 
 
 class ResidentStatus(C.Structure):

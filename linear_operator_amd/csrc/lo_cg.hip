@@ -125,56 +125,6 @@ static void lean_miss_note(const lo_op_desc* op, const lo_cg_params* prm, int ge
 static thread_local lo_cg_plan tls_last_exec = {};    // what the last lo_cg_solve_f32 of this thread actually launched
 static thread_local bool tls_no_fused_precond = false;  // set while a solve is redone after a timed-out hand-off
 
-// hipGraph of one CG iteration: captured on a private side stream, replayed on the caller's stream.
-struct GraphReplay {
-  hipStream_t side = nullptr;
-  hipGraph_t graph = nullptr;
-  hipGraphExec_t exec = nullptr;
-  bool capturing = false;
-  bool begin() {
-    if (!side && hipStreamCreateWithFlags(&side, hipStreamNonBlocking) != hipSuccess) {
-      side = nullptr;
-      (void)hipGetLastError();
-      return false;
-    }
-    if (hipStreamBeginCapture(side, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-      (void)hipGetLastError();
-      return false;
-    }
-    capturing = true;
-    return true;
-  }
-  bool end() {
-    capturing = false;
-    if (hipStreamEndCapture(side, &graph) != hipSuccess || !graph) {
-      (void)hipGetLastError();
-      graph = nullptr;
-      return false;
-    }
-    if (hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) {
-      (void)hipGetLastError();
-      exec = nullptr;
-      return false;
-    }
-    return true;
-  }
-  void reset() {
-    if (capturing) {
-      hipGraph_t g2 = nullptr;
-      (void)hipStreamEndCapture(side, &g2);
-      if (g2) (void)hipGraphDestroy(g2);
-      capturing = false;
-    }
-    if (exec) (void)hipGraphExecDestroy(exec);
-    if (graph) (void)hipGraphDestroy(graph);
-    exec = nullptr;
-    graph = nullptr;
-  }
-  ~GraphReplay() {
-    reset();
-    if (side) (void)hipStreamDestroy(side);
-  }
-};
 // A chunk of columns goes to the column-lockstep kernel (16 at a time on the matrix cores) when it has at least this
 // many live columns; fewer are cheaper one after the other on the second-generation kernel.
 constexpr int kLockstepMinCols = 4;
@@ -571,25 +521,11 @@ __global__ __launch_bounds__(kThreads) void k_cg_final(CgDev d, float* __restric
 }
 
 // ---- host engine -----------------------------------------------------------------------------------
-struct CgLayout {
-  Split sp;
-  int S_dot;
-  bool precond;
-  int pre_R4;
-  bool pre_pad;
-};
-
-static int padded_rank_k(int k) {
-  int rq = (k + 3) / 4, p = 1;
-  while (p < rq) p <<= 1;
-  return 4 * p;
-}
-
 // ---- engine selection: a PURE function of the shapes, the pointers' null-ness, the parameters and the number of
 // workgroup slots (no device memory is read, nothing is launched).  lo_cg_solve_f32 executes this plan; the only
 // decisions left to run time are the fall-backs after an occupancy query refuses a kernel or a hand-off times out.
 // Exported as lo_cg_plan_f32 so that the selection matrix has a table-driven test (tests/test_host_api.py).
-static int padded_rank_c(int64_t R) {  // floats per row of the root as the skinny kernels read it (lo_matvec.hip)
+static int padded_rank(int64_t R) {  // floats per row of a rank-R factor (C, Q) as the skinny kernels read it
   int64_t rq = (R + 3) / 4, p = 1;
   while (p < rq) p <<= 1;
   return (int)(4 * p);
@@ -606,18 +542,49 @@ static CgShape cg_shape(const lo_op_desc* op, const lo_precond_desc* pre, bool p
   s.has_ab = s.oc_shape && prm->n_tridiag > 0;
   s.has_ls_gbuf = s.oc_shape && c >= kLockstepMinCols && N <= 8192;
   s.has_zero_q = !pre && !pre_cb && s.oc_shape;
-  s.rs_cols = s.oc_shape && pre && pre->RS && rspace_cols_eligible(padded_rank_c(op->R), N, c);
+  s.rs_cols = s.oc_shape && pre && pre->RS && rspace_cols_eligible(padded_rank(op->R), N, c);
   const Split sp = choose_split(B, N, 256);
-  s.pf_shape = pre && precond_fused_eligible(B, N, c, padded_rank_k(pre->k), sp.S);
+  s.pf_shape = pre && precond_fused_eligible(B, N, c, padded_rank(pre->k), sp.S);
   // every other streaming shape of up to 32 columns and 16384 rows: the whole step behind the product in one launch
-  const int ldq = pre ? padded_rank_k(pre->k) : 0;
+  const int ldq = pre ? padded_rank(pre->k) : 0;
   s.sc_alloc = !s.pf_shape && ldq <= 16 && cg_step_cols_eligible(B, N, c, ldq);  // (the sizing pass assumes a closure)
   s.sc_shape = s.sc_alloc && !pre_cb;
   return s;
 }
 
+// The LO_* switches of the CG driver, read once per solve.
+struct CgSwitches {
+  bool no_lockstep, gw8, keep_state, no_rspace_cols, no_rspace, no_wrec, no_kron_root;  // engine selection (cg_plan)
+  bool no_fused_ctrl;     // the fused apply / column step leave the control step to k_cg_scal / k_cg_ctrl
+  bool oc_test_fallback;  // the resident kernels start with the error word set, as if a hand-off had timed out
+  int sc_test_fallback;   // the error word set behind the fused column step of iteration k (-1: never)
+};
+
+static CgSwitches cg_switches() {
+  auto on = [](const char* name) { return getenv(name) != nullptr; };
+  const char* sc = getenv("LO_SC_TEST_FALLBACK");
+  return {on("LO_OC_NO_LOCKSTEP"), on("LO_OC_GW8"), on("LO_OC_KEEP_STATE"), on("LO_NO_RSPACE_COLS"), on("LO_OC_NO_RSPACE"),
+          on("LO_OC_NO_WREC"), on("LO_NO_KRON_ROOT"), on("LO_NO_FUSED_CTRL"), on("LO_OC_TEST_FALLBACK"), sc ? atoi(sc) : -1};
+}
+
+// The serial resident kernel of the columns [c - ncols, c) and its group size: the root form when it fits and the
+// preconditioner's root is the operator's own (or there is none), else the Q form (second generation), else none.
+// cg_plan chooses through it, and so does the resident phase when the lockstep kernel does not fit the device.
+struct SerialChoice { int engine, group; };
+
+static SerialChoice serial_choice(const lo_precond_desc* pre, bool oc_nopre, int RC, int ocR4, int64_t N, int ncols,
+                                  const CgSwitches& sw) {
+  const bool pre_root = pre && pre->F && pre->EF && pre->rf_ld > 0;
+  const bool root_match = oc_nopre || (pre_root && pre->rf_ld == RC);
+  if (ncols > 0 && onchip5_eligible(RC, N, ncols) && root_match)
+    return {LO_ENGINE_RESIDENT_ROOT, (sw.gw8 && N <= 32768) ? onchip4_group_size(N) : onchip5_group_size(N)};
+  if (ncols > 0 && onchip4_eligible(RC, ocR4, N, ncols) && (!pre || pre->Q))
+    return {LO_ENGINE_RESIDENT_GEN2, onchip4_group_size(N)};
+  return {LO_ENGINE_NONE, 0};
+}
+
 static void cg_plan(const lo_op_desc* op, const lo_precond_desc* pre, bool pre_cb, bool has_x0, const lo_cg_params* prm,
-                    int oc_nwg, lo_cg_plan* out) {
+                    int oc_nwg, const CgSwitches& sw, lo_cg_plan* out) {
   memset(out, 0, sizeof(*out));
   const int64_t B = op->B, N = op->N;
   const int c = (int)prm->c;
@@ -628,8 +595,8 @@ static void cg_plan(const lo_op_desc* op, const lo_precond_desc* pre, bool pre_c
   out->first_stop_iteration = kfloor0;
   const bool global_rule = prm->stop_reduce != nullptr;
   const bool pre_root = pre && pre->F && pre->EF && pre->rf_ld > 0;
-  const int RC = op->kind == LO_OP_LOWRANK_DIAG ? padded_rank_c(op->R) : 0;
-  const int preR4 = pre ? padded_rank_k(pre->k) : 0;
+  const int RC = op->kind == LO_OP_LOWRANK_DIAG ? padded_rank(op->R) : 0;
+  const int preR4 = pre ? padded_rank(pre->k) : 0;
   // no preconditioner (N < min_preconditioning_size in the host API): the resident kernels run with Q = 0 and
   // 1/d = 1, i.e. z = r and r.z = ||r||^2, which is the reference's unpreconditioned update (linear_cg.py:49-95)
   const bool oc_nopre = !pre && !pre_cb && sh.has_zero_q;
@@ -641,19 +608,17 @@ static void cg_plan(const lo_op_desc* op, const lo_precond_desc* pre, bool pre_c
                        (prm->n_tridiag == 0 || sh.has_ab) && B < (1 << 24) - 1024;
   // column split: full chunks of 16 (and a last chunk of at least kLockstepMinCols) -> lockstep kernel, the rest serial
   int ls_cols = 0;
-  if (oc_base && sh.has_ls_gbuf && !getenv("LO_OC_NO_LOCKSTEP") && (!pre || pre->Q) &&
+  if (oc_base && sh.has_ls_gbuf && !sw.no_lockstep && (!pre || pre->Q) &&
       lockstep_eligible(RC, pre ? preR4 : 0, pre != nullptr, N, c)) {
     const int full = (c / 16) * 16, rem = c - full;
     ls_cols = full + (rem >= kLockstepMinCols ? rem : 0);
   }
-  const bool root_match = oc_nopre || (pre_root && pre->rf_ld == RC);
-  const bool oc_root_ok = ls_cols < c && !getenv("LO_OC_GEN2") && onchip5_eligible(RC, N, c - ls_cols) && root_match;
-  const bool gen2_ok = ls_cols < c && onchip4_eligible(RC, ocR4, N, c - ls_cols) && (!pre || pre->Q);
-  const bool oc_ok = oc_base && (ls_cols == c || oc_root_ok || gen2_ok);
+  const SerialChoice serial = serial_choice(pre, oc_nopre, RC, ocR4, N, c - ls_cols, sw);
+  const bool oc_ok = oc_base && (ls_cols == c || serial.engine != LO_ENGINE_NONE);
   out->streaming_precond = pre_cb ? LO_STREAM_PRE_CLOSURE : (pre ? LO_STREAM_PRE_TWO_PASS : LO_STREAM_PRE_NONE);
   if (pre && pre->Q && sh.pf_shape && !tls_no_fused_precond && oc_nwg >= 64) {
     const bool kron = op->kind == LO_OP_KRON_DIAG && op->diag_mode == LO_DIAG_CONST && pre->constant_diag && pre->kron_a &&
-                      pre->kron_b && pre->kron_F && pre->k <= 16 && !getenv("LO_NO_KRON_ROOT");
+                      pre->kron_b && pre->kron_F && pre->k <= 16 && !sw.no_kron_root;
     out->streaming_precond = kron ? LO_STREAM_PRE_FUSED_KRON : LO_STREAM_PRE_FUSED_Q;
   }
   if ((out->streaming_precond == LO_STREAM_PRE_TWO_PASS || out->streaming_precond == LO_STREAM_PRE_NONE) && sh.sc_shape &&
@@ -664,35 +629,29 @@ static void cg_plan(const lo_op_desc* op, const lo_precond_desc* pre, bool pre_c
   out->poll_chunk = (opaque || global_rule) ? 1 : 4;
   // a root-form-only preconditioner cannot feed the streaming engine: without a resident kernel the caller is told to
   // build the Q form (LO_ERR_UNSUPPORTED)
-  out->needs_q = (pre && !pre->Q && !(oc_ok && (ls_cols == c || oc_root_ok))) ? 1 : 0;
+  const bool root_serial = serial.engine == LO_ENGINE_RESIDENT_ROOT;
+  out->needs_q = (pre && !pre->Q && !(oc_ok && (ls_cols == c || root_serial))) ? 1 : 0;
   if (!oc_ok) return;
   out->resident = 1;
   out->resident_iterations = kfloor0 + 1;
   out->lockstep_cols = ls_cols;
   out->lockstep_group = ls_cols ? lockstep_group_size(N) : 0;
   if (ls_cols < c) {
-    if (oc_root_ok) {
-      out->serial_engine = LO_ENGINE_RESIDENT_ROOT;
-      out->serial_group = (getenv("LO_OC_GW8") && N <= 32768) ? onchip4_group_size(N) : onchip5_group_size(N);
-    } else {
-      out->serial_engine = LO_ENGINE_RESIDENT_GEN2;
-      out->serial_group = onchip4_group_size(N);
-    }
+    out->serial_engine = serial.engine;
+    out->serial_group = serial.group;
   }
   // Result-only first pass ("lean"): the resident kernels that take it (root-form serial columns, lockstep) write the
   // scaled result but not x / r / p / z of a possible continuation -- 4 of the 5 vectors they used to store.  All
   // BASELINE shapes stop at the floor; when the rule does not hold there, the same launches are repeated with the state
   // (deterministic kernels: the continuation starts from the very numbers the first pass computed).
-  out->lean = (!global_rule && !getenv("LO_OC_KEEP_STATE") && (ls_cols == c || out->serial_engine == LO_ENGINE_RESIDENT_ROOT))
-                  ? 1 : 0;
+  out->lean = (!global_rule && !sw.keep_state && (ls_cols == c || root_serial)) ? 1 : 0;
   // R-space forms of the result-only pass (lo_rspace.hip), with the fp64 Gram matrices of the root at hand
-  const bool rs_base = pre && pre->RS && pre_root && pre->rf_ld == RC && !global_rule && !getenv("LO_OC_KEEP_STATE");
-  if (rs_base && sh.rs_cols && (c >= 2 || prm->n_tridiag > 0) && !getenv("LO_NO_RSPACE_COLS")) {
+  const bool rs_base = pre && pre->RS && pre_root && pre->rf_ld == RC && !global_rule && !sw.keep_state;
+  if (rs_base && sh.rs_cols && (c >= 2 || prm->n_tridiag > 0) && !sw.no_rspace_cols) {
     out->rspace = 1;  // all columns, three streaming launches; the engines above are the repeat with the state
     out->lean = 1;
-  } else if (rs_base && out->lean && ls_cols == 0 && c == 1 && prm->n_tridiag == 0 && pre->E &&
-             out->serial_engine == LO_ENGINE_RESIDENT_ROOT && rspace_eligible(RC, N, c) && !getenv("LO_OC_NO_RSPACE") &&
-             !getenv("LO_OC_NO_WREC")) {
+  } else if (rs_base && out->lean && ls_cols == 0 && c == 1 && prm->n_tridiag == 0 && pre->E && root_serial &&
+             rspace_eligible(RC, N, c) && !sw.no_rspace && !sw.no_wrec) {
     out->rspace = 2;  // the single column inside the resident launch
   }
 }
@@ -756,7 +715,7 @@ static size_t cg_layout(const lo_op_desc* op, const lo_precond_desc* pre, bool p
   dd.oc_ab = shp.has_ab ? ar.take<float>(2 * oc_n * oc_iters) : nullptr;
   dd.oc_maxoff = ar.take<int>((size_t)std::max(1, (int)prm->max_tridiag_iter) + 1);
   dd.oc_dbg = ar.take<long long>(16);
-  dd.rs_ws = shp.rs_cols ? ar.take<double>(rspace_cols_ws_doubles(B, N, padded_rank_c(op->R), (int)c)) : nullptr;
+  dd.rs_ws = shp.rs_cols ? ar.take<double>(rspace_cols_ws_doubles(B, N, padded_rank(op->R), (int)c)) : nullptr;
   dd.ls_gbuf = shp.has_ls_gbuf
                    ? ar.take<unsigned long long>(lockstep_gbuf_bytes(32, 16) / sizeof(unsigned long long))
                    : nullptr;
@@ -776,7 +735,7 @@ static size_t cg_layout(const lo_op_desc* op, const lo_precond_desc* pre, bool p
   }
   // preconditioner staging
   if (pre) {
-    const int R4 = padded_rank_k(pre->k);
+    const int R4 = padded_rank(pre->k);
     float* up = ar.take<float>((size_t)B * sp.S * R4 * c);
     if (upart) *upart = up;
     if (pre->Q && pre->ldq != R4) {
@@ -794,8 +753,6 @@ static size_t cg_layout(const lo_op_desc* op, const lo_precond_desc* pre, bool p
     }
   }
   // matvec plan
-  size_t before = ar.off;
-  (void)before;
   if (init) {
     int rc = matvec_plan_init(pl, op, mv_cb, mv_user, c, sp, &ar, st);
     if (rc && rc_out) *rc_out = rc;
@@ -805,6 +762,635 @@ static size_t cg_layout(const lo_op_desc* op, const lo_precond_desc* pre, bool p
   if (d) *d = dd;
   if (init && !ar.ok && rc_out && *rc_out == LO_OK) *rc_out = LO_ERR_WORKSPACE;
   return ar.off + 1024;
+}
+
+// Phase timers of the resident and fused-column kernels, printed to stderr after the launches that wrote them
+// (tools/mb_oc_debug.py, mb_lockstep.py, mb_rsdiag_phases.py): LO_LS_DEBUG=<member> (lockstep kernel),
+// LO_OC_DEBUG=<member> (serial-column kernels), LO_SC_DEBUG (fused column step of the streaming loop).
+struct CgDebug {
+  bool ls = false, oc = false, sc = false;
+  int member = 0;
+  static CgDebug read(int64_t B) {  // (sc: only where the fused column step runs, see cg_streaming)
+    const char *els = getenv("LO_LS_DEBUG"), *eoc = getenv("LO_OC_DEBUG");
+    const bool ls = els && B >= 8, oc = !ls && eoc && B >= 8;
+    return {ls, oc, getenv("LO_SC_DEBUG") != nullptr, oc ? atoi(eoc) : (ls ? atoi(els) : 0)};
+  }
+  int report_resident(const long long* dev) const {
+    long long ts[12];
+    if (ls) {
+      LO_HIP_CHECK(hipMemcpy(ts, dev, 10 * sizeof(long long), hipMemcpyDeviceToHost));
+      fprintf(stderr, "lockstep item (100 MHz ticks): load+H %lld init %lld iters %lld store %lld | direction %lld "
+              "alpha+x+r %lld reduce-mfma %lld cross-wave %lld group-sum %lld\n",
+              ts[1] - ts[0], ts[2] - ts[1], ts[3] - ts[2], ts[4] - ts[3], ts[5], ts[6], ts[7], ts[8], ts[9]);
+    }
+    if (oc) {
+      LO_HIP_CHECK(hipMemcpy(ts, dev, 12 * sizeof(long long), hipMemcpyDeviceToHost));
+      if (ts[8] || ts[9])
+        fprintf(stderr, "  root-form kernel phases: updates %lld, w partials + all-reduce %lld, first-wave algebra %lld\n",
+                ts[8], ts[9], ts[10]);
+      fprintf(stderr, "onchip member0 (100 MHz ticks): load %lld init %lld iters %lld store %lld | wg-wait %lld publish %lld poll %lld\n",
+              ts[1] - ts[0], ts[2] - ts[1], ts[3] - ts[2], ts[4] - ts[3], ts[5], ts[6], ts[7]);
+    }
+    return LO_OK;
+  }
+  int report_streaming(const long long* dev) const {
+    if (!sc) return LO_OK;
+    long long ts[8];
+    LO_HIP_CHECK(hipMemcpy(ts, dev, sizeof(ts), hipMemcpyDeviceToHost));
+    if (ts[5])
+      fprintf(stderr, "cg_step_cols member 0, first workgroup (100 MHz ticks per launch): loads+alpha %.1f update+mfma %.1f "
+              "all-reduce %.1f beta+control %.1f p %.1f\n", (double)ts[0] / ts[5], (double)ts[1] / ts[5], (double)ts[2] / ts[5],
+              (double)ts[3] / ts[5], (double)ts[4] / ts[5]);
+    return LO_OK;
+  }
+};
+
+// Host-side state of one lo_cg_solve_f32.  The set-up fills it; the resident phase (the guaranteed iterations in
+// operator-resident launches, lo_cg_onchip.hip) and the streaming phase (the iterations after them, or all of them)
+// advance it; the close writes the result and the report.
+struct CgSolve {
+  const lo_op_desc* op;
+  const lo_precond_desc* pre;
+  lo_matvec_cb precond_cb;
+  void* precond_user;
+  const lo_cg_params* prm;
+  const float *rhs, *x0;
+  float* x;
+  hipStream_t st;
+  int64_t B, N;
+  int c;
+  CgDev d;
+  MatvecPlan pl;
+  const float* Qp = nullptr;  // Q padded to preR4 floats per row
+  float* upart = nullptr;
+  Split sp;
+  int preR4, fmi, oc_nwg;
+  bool precond, global_rule, oc_nopre;
+  CgSwitches sw;
+  CgDebug dbg;
+  lo_cg_plan plan, exec;  // exec: the plan as executed -- every run-time fall-back is an edit of it (lo_cg_last_executed)
+  CgCtrl h;               // host copy of the control block
+  int k_start = 0, launched = 0;  // iterations the resident phase completed / iterations enqueued in all
+  int matvecs = 0;                // operator applications outside the iterations (x0)
+  bool x_written = false;         // the resident kernels already wrote result * rhs_norm
+  dim3 gridv, block;
+};
+
+static int cg_setup(CgSolve& s, lo_matvec_cb matvec, void* matvec_user, float* t_mat, void* ws, size_t ws_bytes) {
+  const lo_op_desc* op = s.op; const lo_precond_desc* pre = s.pre; const lo_cg_params* prm = s.prm;
+  s.sw = cg_switches();
+  s.dbg = CgDebug::read(s.B);
+  int rc = LO_OK;
+  cg_layout(op, pre, s.precond_cb != nullptr, prm, ws, ws_bytes, &s.d, &s.pl, matvec, matvec_user, &s.Qp, &s.upart, s.st,
+            &rc, true);
+  if (rc) return rc;
+  CgDev& d = s.d;
+  s.sp = s.pl.sp;
+  s.fmi = prm->floor_max_iter > 0 ? prm->floor_max_iter : prm->max_iter;  // (linear_cg.py:303-305)
+  d.n_tridiag = prm->n_tridiag; d.max_iter = s.fmi; d.n_tridiag_iter = d.T = prm->max_tridiag_iter;
+  // batch-global stopping rule over several ranks (lo_stop_reduce_cb): the device never decides the tolerance stop
+  // itself (tol = -1 can not be undercut by a mean of norms); the host evaluates the rule on the all-reduced statistic
+  s.global_rule = prm->stop_reduce != nullptr;
+  d.tol = s.global_rule ? -1.0f : prm->tolerance;
+  d.eps = prm->eps; d.stop_after = prm->stop_updating_after; d.check_nan_first = (s.x0 == nullptr); d.t_mat = t_mat;
+  s.precond = (pre != nullptr) || (s.precond_cb != nullptr);
+  s.preR4 = pre ? padded_rank(pre->k) : 0;
+  s.oc_nopre = !pre && !s.precond_cb && d.oc_zero_q != nullptr;
+  s.gridv = dim3(s.sp.S, (unsigned)s.B); s.block = dim3(kThreads);
+  {  // control block (+ the granule buffer behind it when a resident kernel may run)
+    const bool oc_possible = op->kind == LO_OP_LOWRANK_DIAG && !resident_off();
+    const size_t span = oc_possible ? (size_t)(reinterpret_cast<char*>(d.oc_close + s.B + 2) - reinterpret_cast<char*>(d.ctrl))
+                                    : sizeof(CgCtrl);
+    rc = zero_span(d.ctrl, span, s.st);
+    if (rc) return rc;
+  }
+  if (prm->n_tridiag)
+    LO_HIP_CHECK(hipMemsetAsync(t_mat, 0, sizeof(float) * (size_t)prm->n_tridiag * s.B * d.T * d.T, s.st));
+  memset(&s.h, 0, sizeof(s.h));
+  s.oc_nwg = onchip_num_workgroups();
+  // ---- the plan (pure: cg_plan above; lo_cg_plan_f32 reports the same decisions to the tests) ----
+  cg_plan(op, pre, s.precond_cb != nullptr, s.x0 != nullptr, prm, s.oc_nwg, s.sw, &s.plan);
+  tls_rspace_resident_ran = false;
+  s.exec = s.plan;
+  s.exec.resident = 0;
+  s.exec.rspace = 0;
+  return LO_OK;
+}
+
+// linear_cg.py:302-308 on the statistic of ALL ranks; called exactly once per completed iteration k >= first stop
+static int cg_global_check(CgSolve& s) {
+  if (!s.global_rule) return LO_OK;
+  const lo_cg_params* prm = s.prm; CgCtrl& h = s.h; const int kdone = h.iterations - 1;
+  double vals[3] = {(double)h.mean_resid * (double)(s.B * s.c), (double)(s.B * s.c), h.stop ? 1.0 : 0.0};
+  if (prm->stop_reduce(prm->stop_reduce_user, vals)) return LO_ERR_LAUNCH;
+  const float gmean = (float)(vals[0] / vals[1]);
+  h.mean_resid = gmean;
+  if (vals[2] > 0.0) {  // some rank stopped on its own (NaN in a product): everybody stops
+    h.stop = 1;
+    return LO_OK;
+  }
+  const int kfl = std::min(10, s.fmi - 1);
+  const bool stopnow = kdone >= kfl && gmean < prm->tolerance &&
+                       !(prm->n_tridiag && kdone < std::min(prm->max_tridiag_iter, s.fmi - 1));
+  if (stopnow) {
+    h.tol_reached = 1;
+    h.stop = 1;
+  }
+  return LO_OK;
+}
+
+// ---- resident phase ----------------------------------------------------------------------------------
+// One attempt runs the engines of s.exec for the first_stop_iteration + 1 guaranteed iterations and closes them (stop
+// rule, NaN / skip conditions, tridiagonal entries).  What comes next:
+enum class OcNext {
+  kDone,       // the iterations ran: the streaming phase continues from k_start (or the solve is over)
+  kStream,     // no resident kernel takes the solve, or a hand-off timed out: the streaming engine from iteration 0
+  kRedoDense,  // the diagonal R-space form asked for the dense one (CgCtrl::rs_redo): the result-only pass again
+  kRedoState   // the result-only pass missed the floor, or a kernel without that mode has columns: again with the state
+};
+
+// Control launches behind the resident kernels, the wait for their decision, and what it means for the next attempt.
+static int resident_close(CgSolve& s, const OnchipArgs& a, bool lean, bool dense, bool rs_cols_ran, unsigned close_ticket,
+                          OcNext* next) {
+  CgDev& d = s.d; const lo_cg_params* prm = s.prm; hipStream_t st = s.st; CgCtrl& h = s.h;
+  const int ktri = prm->n_tridiag ? std::min(a.iters, (int)prm->max_tridiag_iter) : 0;
+  const unsigned tri_grid = (unsigned)(((size_t)s.B * std::max(1, (int)prm->n_tridiag) + kThreads - 1) / kThreads);
+  if (ktri) {
+    LO_HIP_CHECK(hipMemsetAsync(d.oc_maxoff, 0, sizeof(int) * (prm->max_tridiag_iter + 1), st));
+    hipLaunchKernelGGL(k_oc_maxoff, dim3(tri_grid), s.block, 0, st, d, d.oc_ab, ktri);
+  }
+  // (with tridiagonals k_oc_tridiag follows and does not touch the control block: the mirror is final either way)
+  CgCtrl* mirror = static_cast<CgCtrl*>(pinned_status_block());
+  const unsigned ticket = close_ticket ? close_ticket : next_ticket();
+  if (!close_ticket)  // (0: the kernel did not close the solve itself)
+    hipLaunchKernelGGL(k_cg_ctrl_onchip, dim3(1), s.block, 0, st, d, d.oc_resid, d.oc_init_conv, a.iters, ktri, mirror,
+                       ticket);
+  if (ktri) hipLaunchKernelGGL(k_oc_tridiag, dim3(tri_grid), s.block, 0, st, d, d.oc_ab, ktri);
+  LO_LAUNCH_CHECK();
+  if (mirror) {
+    // (with tridiagonals k_oc_tridiag is still queued behind the control kernel: drain the stream as before)
+    if (ktri) LO_HIP_CHECK(hipStreamSynchronize(st));
+    else if (wait_ticket(reinterpret_cast<volatile unsigned*>(mirror) + 63, ticket, st)) return LO_ERR_LAUNCH;
+    memcpy(&h, mirror, sizeof(CgCtrl));
+  } else {
+    LO_HIP_CHECK(hipMemcpyAsync(&h, d.ctrl, sizeof(CgCtrl), hipMemcpyDeviceToHost, st));
+    LO_HIP_CHECK(hipStreamSynchronize(st));
+  }
+  int rc = LO_OK;
+  if (h.oc_err == 0) {
+    rc = cg_global_check(s);
+    if (rc) return rc;
+  }
+  rc = s.dbg.report_resident(d.oc_dbg);
+  if (rc) return rc;
+  if (h.oc_err == 0 && lean && h.rs_redo && tls_rspace_diag_ran && !dense) {
+    *next = OcNext::kRedoDense;
+  } else if (h.oc_err == 0 && lean && !h.stop) {
+    // the stop rule does not hold at the floor and the state was not written: the same launches once more, in full
+    // (a root-form-only preconditioner cannot continue on the streaming engine anyway: the caller builds Q first)
+    lean_miss_note(s.op, prm, s.pre ? s.pre->generation : 0);
+    if (s.pre && !s.pre->Q) return LO_ERR_UNSUPPORTED;
+    *next = OcNext::kRedoState;
+  } else if (h.oc_err == 0) {
+    s.k_start = a.iters; s.x_written = true;
+    resident_note_ok();
+    lo_cg_plan& ex = s.exec;
+    ex.resident = 1;
+    if (rs_cols_ran) ex.lockstep_cols = 0, ex.serial_engine = LO_ENGINE_NONE;  // (the plan's: a repeat's engines)
+    ex.lean = lean ? 1 : 0;
+    ex.rspace = rs_cols_ran ? 1 : ((lean && tls_rspace_resident_ran) ? 2 : 0);
+    ex.rspace_diag = (ex.rspace == 2 && tls_rspace_diag_ran) ? 1 : 0;
+    *next = OcNext::kDone;
+  } else {  // a group hand-off timed out: redo everything with the streaming engine
+    fprintf(stderr, "liblo_amd: operator-resident CG timed out, falling back to the streaming engine\n");
+    onchip_note_timeout();
+    LO_HIP_CHECK(hipMemsetAsync(d.ctrl, 0, sizeof(CgCtrl), st));
+    memset(&h, 0, sizeof(h));
+    *next = OcNext::kStream;
+  }
+  return LO_OK;
+}
+
+// One attempt of the resident phase: lean = result-only pass, dense = the dense form of the R-space iteration.
+static int resident_attempt(CgSolve& s, int attempt, bool lean, bool dense, OcNext* next) {
+  CgDev& d = s.d; const lo_precond_desc* pre = s.pre; const lo_cg_params* prm = s.prm; lo_cg_plan& ex = s.exec;
+  const int64_t B = s.B, N = s.N; const int c = s.c, RC = s.pl.R4, ocR4 = s.oc_nopre ? 4 : s.preR4;
+  hipStream_t st = s.st;
+  *next = OcNext::kStream;
+  OnchipArgs a;
+  a.C = s.pl.Apad; a.d = s.op->d; a.d_mode = s.op->diag_mode;
+  if (s.oc_nopre) {
+    if (ex.lockstep_cols < c && ex.serial_engine == LO_ENGINE_RESIDENT_GEN2) {  // (the root form needs no Q)
+      LO_HIP_CHECK(hipMemsetAsync(d.oc_zero_q, 0, sizeof(float) * (size_t)B * N * 4, st));
+      LO_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)d.oc_ones, 0x3f800000, (size_t)B, st));  // 1.0f
+    }
+    a.Q = d.oc_zero_q; a.dinv = d.oc_ones; a.dinv_mode = LO_DIAG_CONST;
+  } else {
+    a.Q = s.Qp; a.dinv = pre->dinv; a.dinv_mode = pre->constant_diag ? LO_DIAG_CONST : LO_DIAG_FULL;
+  }
+  a.rhs = s.rhs; a.B = B; a.N = (int)N; a.c = c; a.ab_rec = prm->n_tridiag ? d.oc_ab : nullptr;
+  a.col0 = 0; a.ncols = c; a.RK = pre ? s.preR4 : 0; a.RCg = RC;
+  a.F = nullptr; a.EF = nullptr; a.E = nullptr; a.RS = nullptr; a.RSD = nullptr;
+  a.close_gran = nullptr; a.close_count = nullptr; a.close_ctrl = nullptr; a.close_mirror = nullptr;
+  a.close_ticket = 0; a.close_tol = 0.f; a.close_floor_ok = 0;
+  a.iters = s.plan.first_stop_iteration + 1; a.eps = prm->eps; a.stop_after = prm->stop_updating_after;
+  a.x = d.x; a.r = d.r; a.p = d.p; a.z = d.z;
+  auto lean_state = [&](bool on) {  // (kernels without the result-only mode get the state pointers back)
+    a.x = on ? nullptr : d.x; a.r = on ? nullptr : d.r; a.p = on ? nullptr : d.p; a.z = on ? nullptr : d.z;
+  };
+  a.rhs_norm = d.rhs_norm; a.rz = d.rz; a.alpha = d.alpha; a.beta = d.beta; a.resid_norm = d.resid_norm;
+  a.rhs_is_zero = d.rhs_is_zero; a.has_conv = d.has_conv;
+  a.resid_rec = d.oc_resid; a.init_conv = d.oc_init_conv; a.err = d.oc_err;
+  a.allow_l2_handoff = onchip_l2_handoff_allowed();
+  a.prefetch = 1;  // (read by no CG kernel)
+  a.dbg = nullptr; a.dbg_member = s.dbg.member;
+  // LO_OC_TEST_FALLBACK: start with the error word set, as if a hand-off had timed out (exercises the host fallback)
+  // (error word and member counters live in the control block: cleared with it, copied back with it)
+  // lo_resident_inject_timeouts(n): the same through the real bookkeeping (cool-down, re-arm) -- the multi-rank tests
+  if (s.sw.oc_test_fallback || (attempt == 0 && resident_take_injection()))
+    LO_HIP_CHECK(hipMemsetAsync(d.oc_err, 1, 1, st));
+  if (s.dbg.oc || s.dbg.ls) LO_HIP_CHECK(hipMemsetAsync(d.oc_dbg, 0, 16 * sizeof(long long), st));
+  int rc = LO_OK; int ls = ex.lockstep_cols;
+  bool rs_cols_ran = false;  // all columns are done on R + 1 coordinates
+  unsigned close_ticket = 0;  // non-zero: the root-form kernel closes the solve itself
+  if (s.plan.rspace == 1 && lean && d.rs_ws) {  // all columns on R + 1 coordinates: three streaming launches
+    a.xout = s.x;
+    lean_state(true);
+    a.F = pre->F; a.EF = pre->EF; a.E = pre->E; a.RS = pre->RS; a.RSD = pre->RSD;
+    rc = rspace_cols_launch(RC, a, d.rs_ws, st);
+    if (rc == LO_OK) {
+      rs_cols_ran = true;
+      ls = 0;
+    } else if (rc != LO_ERR_UNSUPPORTED) {
+      return rc;
+    }
+  }
+  if (ls) {  // third generation: columns [0, ls)
+    a.ncols = ls;
+    a.xout = s.x;
+    lean_state(lean);
+    a.gbuf = d.ls_gbuf; a.next_member = d.oc_err + 2;
+    a.dbg = s.dbg.ls ? d.oc_dbg : nullptr;
+    LO_HIP_CHECK(hipMemsetAsync(d.ls_gbuf, 0, lockstep_gbuf_bytes(32, 16), st));
+    a.GW = ex.lockstep_group;
+    a.RW = (int)((N + a.GW - 1) / a.GW);
+    rc = lockstep_launch(RC, pre != nullptr, a, std::min(s.oc_nwg, 256), st);
+    if (rc == LO_ERR_UNSUPPORTED && a.GW == 16) {  // (two workgroups per CU do not fit: one 1024-row workgroup)
+      a.GW = ex.lockstep_group = 8;
+      a.RW = (int)((N + 7) / 8);
+      rc = lockstep_launch(RC, pre != nullptr, a, std::min(s.oc_nwg, 256), st);
+    }
+    if (rc == LO_ERR_UNSUPPORTED) {  // (does not fit this device: all columns go to the serial kernels)
+      ex.lockstep_cols = ls = 0;
+      ex.lockstep_group = 0;
+      if (!onchip4_eligible(RC, ocR4, N, c)) return LO_OK;
+      const SerialChoice serial = serial_choice(pre, s.oc_nopre, RC, ocR4, N, c, s.sw);
+      ex.serial_engine = serial.engine;
+      ex.serial_group = serial.group;
+    } else if (rc) {
+      return rc;
+    }
+  }
+  if (!rs_cols_ran && ls < c && ex.serial_engine == LO_ENGINE_RESIDENT_ROOT) {
+    // root-form serial-column kernel (one all-reduce per iteration): columns [ls, c)
+    a.GW = ex.serial_group;
+    a.RW = (int)((N + a.GW - 1) / a.GW);
+    a.col0 = ls; a.ncols = c - ls;
+    a.xout = s.x;
+    lean_state(lean);
+    a.F = s.oc_nopre ? nullptr : pre->F; a.EF = s.oc_nopre ? nullptr : pre->EF; a.E = s.oc_nopre ? nullptr : pre->E;
+    a.RS = (s.oc_nopre || s.plan.rspace != 2) ? nullptr : pre->RS;
+    a.RSD = (a.RS && !dense) ? pre->RSD : nullptr;
+    tls_rspace_resident_ran = false;
+    a.gbuf = d.oc_gbuf; a.next_member = d.oc_err + 1;
+    a.dbg = s.dbg.oc ? d.oc_dbg : nullptr;
+    // one column, no tridiagonals, no lockstep launch in front: the kernel closes the solve itself (stop rule, NaN /
+    // skip conditions, mirror + ticket) -- no separate control launch
+    if (c == 1 && ls == 0 && prm->n_tridiag == 0 && !s.dbg.oc && pinned_status_block() != nullptr) {
+      a.close_gran = d.oc_close; a.close_count = reinterpret_cast<int*>(d.oc_close + B);
+      a.close_ctrl = d.ctrl;
+      a.close_mirror = static_cast<CgCtrl*>(pinned_status_block());
+      a.close_ticket = close_ticket = next_ticket();
+      a.close_tol = d.tol;
+      a.close_floor_ok = (a.iters - 1 >= std::min(10, d.max_iter - 1)) ? 1 : 0;
+    }
+    rc = onchip5_launch(RC, a, s.oc_nwg, st);  // (d.oc_gbuf was cleared together with the control block)
+    if (rc == LO_ERR_UNSUPPORTED) {  // (does not fit this device: the Q form, after a repeat with the state if lean)
+      close_ticket = 0; a.close_gran = nullptr;
+      if (pre && !pre->Q) return LO_OK;  // (root form only)
+      if (lean) {  // (the Q form has no result-only mode: start over, and try the root form again with the state)
+        *next = OcNext::kRedoState;
+        return LO_OK;
+      }
+      if (!onchip4_eligible(RC, ocR4, N, c - ls)) return LO_OK;
+      ex.serial_engine = LO_ENGINE_RESIDENT_GEN2;
+      ex.serial_group = onchip4_group_size(N);
+    } else if (rc) {
+      return rc;
+    }
+  }
+  if (!rs_cols_ran && ls < c && ex.serial_engine == LO_ENGINE_RESIDENT_GEN2) {
+    // second generation (Q form, with the state): columns [ls, c)
+    if (lean) {  // (no result-only mode: start over)
+      *next = OcNext::kRedoState;
+      return LO_OK;
+    }
+    lean_state(false);
+    a.GW = ex.serial_group; a.RW = (int)((N + a.GW - 1) / a.GW);
+    a.col0 = ls; a.ncols = c - ls; a.xout = s.x;
+    a.gbuf = d.oc_gbuf; a.next_member = d.oc_err + 1;
+    a.dbg = s.dbg.oc ? d.oc_dbg : nullptr;
+    LO_HIP_CHECK(hipMemsetAsync(d.oc_gbuf, 0, onchip_gbuf_bytes(66), st));  // whole allocation
+    rc = onchip4_launch(RC, ocR4, a, s.oc_nwg, st);
+    if (rc == LO_ERR_UNSUPPORTED) return LO_OK;
+    if (rc) return rc;
+  } else if (!rs_cols_ran && ls < c && ex.serial_engine != LO_ENGINE_RESIDENT_ROOT) {
+    return LO_OK;  // (no serial kernel for these columns)
+  }
+  return resident_close(s, a, lean, dense, rs_cols_ran, close_ticket, next);
+}
+
+// The guaranteed iterations in resident launches, in at most three attempts (see OcNext): the first pass (result-only
+// when the plan says lean); the same pass on the dense R-space form; the repeat with the state.
+static int cg_resident(CgSolve& s) {
+  if (!s.plan.resident) return LO_OK;
+  bool lean = s.plan.lean != 0;
+  const int miss_slot = lean ? lean_miss_find(s.op, s.prm, s.pre ? s.pre->generation : 0) : -1;
+  const bool lean_skipped = miss_slot >= 0 && s.pre && s.pre->Q;
+  if (lean_skipped) lean = false;  // this operator missed the floor last time: write the state in the first pass
+  bool dense = false;
+  for (int attempt = 0; attempt < 3; ++attempt) {
+    OcNext next;
+    int rc = resident_attempt(s, attempt, lean, dense, &next);
+    if (rc) return rc;
+    if (next == OcNext::kDone && lean_skipped && s.h.stop)
+      tls_lean_miss[miss_slot].valid = 0;  // (it stops at the floor now: speculate again)
+    if (next == OcNext::kDone || next == OcNext::kStream) return LO_OK;
+    // (kRedoDense needs lean && !dense, kRedoState needs lean: the third attempt is never repeated)
+    if (next == OcNext::kRedoDense) dense = true;
+    else lean = false;
+    // control block and granules as at the start of the solve
+    rc = zero_span(s.d.ctrl, (size_t)(reinterpret_cast<char*>(s.d.oc_close + s.B + 2) - reinterpret_cast<char*>(s.d.ctrl)),
+                   s.st);
+    if (rc) return rc;
+    memset(&s.h, 0, sizeof(s.h));
+  }
+  return LO_OK;
+}
+
+// ---- streaming phase ---------------------------------------------------------------------------------
+static int cg_apply_precond(CgSolve& s, const float* r, float* z, float* dotp) {
+  const int* stop = &s.d.ctrl->stop;
+  if (s.pre) {
+    int e = skinny_tn(s.Qp, s.preR4, s.preR4, r, s.c, s.upart, s.B, s.N, s.sp, stop, s.st);
+    if (e) return e;
+    return skinny_nn(s.Qp, s.preR4, s.preR4, s.upart, s.pre->dinv, s.pre->constant_diag ? LO_DIAG_CONST : LO_DIAG_FULL,
+                     -1.0f, r, s.c, z, dotp, s.B, s.N, s.sp, stop, s.st);
+  }
+  int e = s.precond_cb(s.precond_user, r, z, s.B, s.N, s.c, (void*)s.st);
+  if (e) return LO_ERR_LAUNCH;
+  return vec_dot_part(r, z, s.c, dotp, s.B, s.N, s.sp, stop, s.st);
+}
+
+static int cg_poll(CgSolve& s) {
+  void* hp = pinned_status_block();
+  LO_HIP_CHECK(hipMemcpyAsync(hp ? hp : &s.h, s.d.ctrl, sizeof(CgCtrl), hipMemcpyDeviceToHost, s.st));
+  LO_HIP_CHECK(hipStreamSynchronize(s.st));
+  if (hp) memcpy(&s.h, hp, sizeof(CgCtrl));
+  return LO_OK;
+}
+
+// initialisation of the streaming engine (linear_cg.py:177-215)
+static int cg_init(CgSolve& s) {
+  CgDev& d = s.d; const int64_t B = s.B, N = s.N; const int c = s.c; hipStream_t st = s.st;
+  int rc = vec_dot_part(s.rhs, s.rhs, c, d.pAp_part, B, N, s.sp, nullptr, st);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_cg_init_scal, dim3(1), s.block, 0, st, d, d.pAp_part);
+  hipLaunchKernelGGL(k_cg_init_vec, s.gridv, s.block, 0, st, d, s.rhs, s.x0, s.sp.rows);
+  LO_LAUNCH_CHECK();
+  if (s.x0) {
+    rc = matvec_run(&s.pl, d.x, d.Ap, nullptr, nullptr, st);
+    if (rc) return rc;
+    ++s.matvecs;
+    const size_t nv = (size_t)B * N * c;
+    hipLaunchKernelGGL(k_cg_sub, dim3((unsigned)std::min<size_t>((nv + 255) / 256, 8192)), s.block, 0, st, d.r, d.Ap, nv);
+    LO_LAUNCH_CHECK();
+  }
+  rc = vec_dot_part(d.r, d.r, c, d.rr_part, B, N, s.sp, nullptr, st);
+  if (rc) return rc;
+  if (s.precond) {
+    rc = cg_apply_precond(s, d.r, d.z, d.rz_part);
+    if (rc) return rc;
+  }
+  hipLaunchKernelGGL(k_cg_ctrl_init, dim3(1), s.block, 0, st, d);
+  LO_LAUNCH_CHECK();
+  return LO_OK;
+}
+
+// What the iterations of the streaming loop launch, and what one iteration leaves for the next.
+struct CgIter {
+  const float* zsrc;  // z, or r without a preconditioner
+  int ctrl_G;         // workgroups of k_cg_scal
+  // large-N single-column solves: the preconditioner apply fused with the r / x update, Q read once per iteration
+  bool pf_on;
+  // Kronecker operator with a constant diagonal: the rows of the preconditioner's tall matrix are formed on the fly from
+  // the pivot rows of the two factors (lo_precond_desc.kron_*): 7 instead of 23 floats of traffic per row and iteration
+  bool pf_kron; PfKron kron;
+  // up to 32 columns, up to 16384 rows: alpha, r / x, the preconditioner, beta, p and the control step in one launch
+  bool sc_on;
+  bool p_done;  // the fused apply of the previous iteration already wrote this iteration's p
+};
+
+// The launches of iteration k.
+static int cg_issue(CgSolve& s, CgIter& it, int k) {
+  CgDev& d = s.d; const lo_precond_desc* pre = s.pre; const lo_cg_params* prm = s.prm; const int64_t B = s.B, N = s.N;
+  const int* stop = &d.ctrl->stop; hipStream_t st = s.st; int rc;
+  if (it.p_done) {
+    rc = matvec_run(&s.pl, d.p, d.Ap, d.pAp_part, stop, st);
+    if (rc) return rc;
+  } else if (matvec_can_fuse_pupdate(&s.pl)) {
+    rc = matvec_run_pupdate(&s.pl, d.p, it.zsrc, d.beta, k == 0 ? 1 : 0, d.Ap, d.pAp_part, stop, st);
+    if (rc) return rc;
+  } else {
+    LO_PROF_BEGIN("cg_update_p", st);
+    hipLaunchKernelGGL(k_cg_update_p, s.gridv, s.block, 0, st, d, it.zsrc, k == 0 ? 1 : 0, s.sp.rows);
+    LO_PROF_END(st);
+    LO_LAUNCH_CHECK();
+    rc = matvec_run(&s.pl, d.p, d.Ap, d.pAp_part, stop, st);
+    if (rc) return rc;
+  }
+  bool pre_done = false;
+  bool ctrl_done = false;  // the fused apply also took the iteration's control step
+  if (pre && it.pf_on) {
+    PfCtrl cf;
+    cf.on = (d.n_tridiag == 0 && k > 0 && !s.sw.no_fused_ctrl) ? 1 : 0;
+    cf.rhs_is_zero = d.rhs_is_zero; cf.rz = d.rz; cf.beta = d.beta; cf.resid_norm = d.resid_norm;
+    cf.has_conv = d.has_conv; cf.stop_after = d.stop_after; cf.tol = d.tol;
+    cf.kfloor = std::min(10, d.max_iter - 1);
+    cf.done = d.pf_ctr + (std::max(1, (int)prm->max_iter) + 1);
+    cf.ctrl = d.ctrl;
+    cf.gran = d.pf_gran;
+    // single pass over Q: r / x update, Q^T r, group all-reduce, z = r/d - Q u, p = z + beta p (lo_precond_fused.hip)
+    rc = precond_fused_rupdate(s.Qp, pre->dinv, pre->constant_diag ? LO_DIAG_CONST : LO_DIAG_FULL, d.r, d.Ap, d.p, d.x,
+                               d.z, d.pAp_part, d.S_dot, d.rz, d.has_conv, d.eps, d.alpha, d.rr_part, d.rz_part, s.sp.S,
+                               B, N, d.pf_gbuf, d.oc_err, d.pf_ctr, k, nullptr, (int)prm->max_iter, stop, s.oc_nwg, &cf,
+                               it.pf_kron ? &it.kron : nullptr, st);
+    if (rc == LO_ERR_UNSUPPORTED) {  // (does not fit this device: the two-launch path from now on)
+      it.pf_on = false;
+      s.exec.streaming_precond = LO_STREAM_PRE_TWO_PASS;
+    } else if (rc) {
+      return rc;
+    } else {
+      pre_done = it.p_done = true;
+      ctrl_done = cf.on != 0;
+    }
+  }
+  if (!pre_done && it.sc_on) {
+    ScCtrl cf;
+    cf.on = s.sw.no_fused_ctrl ? 0 : 1;
+    cf.rhs_is_zero = d.rhs_is_zero; cf.beta = d.beta; cf.resid_norm = d.resid_norm;
+    cf.stop_after = d.stop_after; cf.tol = d.tol; cf.max_iter = d.max_iter;
+    cf.n_tridiag = d.n_tridiag; cf.n_tridiag_iter = d.n_tridiag_iter; cf.T = d.T; cf.t_mat = d.t_mat;
+    cf.prev_ar = d.prev_ar; cf.prev_beta = d.prev_beta; cf.check_nan_first = d.check_nan_first;
+    cf.done = d.sc_ctr + (std::max(1, (int)prm->max_iter) + 1);
+    cf.gran = d.sc_gran;
+    cf.ctrl = d.ctrl;
+    rc = cg_step_cols(pre ? s.Qp : nullptr, s.preR4, pre ? pre->dinv : nullptr,
+                      (pre && pre->constant_diag) ? LO_DIAG_CONST : LO_DIAG_FULL, d.r, d.Ap, d.p, d.x, s.c, d.pAp_part,
+                      d.S_dot, d.rz, d.has_conv, d.eps, d.alpha, d.rr_part, d.rz_part, s.sp.S, B, N, d.sc_gbuf, d.oc_err,
+                      d.sc_ctr, k, (int)prm->max_iter, stop, s.oc_nwg, &cf, s.dbg.sc ? d.oc_dbg : nullptr, st);
+    if (rc == LO_ERR_UNSUPPORTED) {  // (does not fit this device: the multi-launch path from now on)
+      it.sc_on = false;
+      s.exec.streaming_precond = pre ? LO_STREAM_PRE_TWO_PASS : LO_STREAM_PRE_NONE;
+    } else if (rc) {
+      return rc;
+    } else {
+      pre_done = it.p_done = true;
+      ctrl_done = cf.on != 0;
+      // LO_SC_TEST_FALLBACK=<k>: the error word set behind launch k, as if a hand-off had timed out (host redo path)
+      if (s.sw.sc_test_fallback == k) LO_HIP_CHECK(hipMemsetAsync(d.oc_err, 1, 1, st));
+    }
+  }
+  if (!pre_done) it.p_done = false;  // (the two-launch path below leaves the p update to the next iteration's first step)
+  if (pre_done) {
+  } else if (pre) {
+    // r-update, x-update and the residual norm ride on the first pass over Q
+    rc = skinny_tn_rupdate(s.Qp, s.preR4, s.preR4, d.r, d.Ap, d.p, d.x, d.pAp_part, d.S_dot, d.rz, d.has_conv, d.eps,
+                           d.alpha, d.rr_part, s.c, s.upart, B, N, s.sp, stop, st);
+    if (rc) return rc;
+    rc = skinny_nn(s.Qp, s.preR4, s.preR4, s.upart, pre->dinv, pre->constant_diag ? LO_DIAG_CONST : LO_DIAG_FULL, -1.0f,
+                   d.r, s.c, d.z, d.rz_part, B, N, s.sp, stop, st);
+    if (rc) return rc;
+  } else {
+    LO_PROF_BEGIN("cg_update_xr", st);
+    hipLaunchKernelGGL(k_cg_update_xr, s.gridv, s.block, 0, st, d, s.sp.rows);
+    LO_PROF_END(st);
+    LO_LAUNCH_CHECK();
+    if (s.precond) {
+      rc = cg_apply_precond(s, d.r, d.z, d.rz_part);
+      if (rc) return rc;
+    }
+  }
+  if (ctrl_done) return LO_OK;
+  LO_PROF_BEGIN("cg_ctrl", st);
+  if (it.ctrl_G == 1) {
+    hipLaunchKernelGGL(k_cg_scal_ctrl, dim3(1), s.block, 0, st, d, k);
+  } else {
+    hipLaunchKernelGGL(k_cg_scal, dim3(it.ctrl_G), s.block, 0, st, d, k);
+    hipLaunchKernelGGL(k_cg_ctrl, dim3(1), s.block, 0, st, d, k, it.ctrl_G);
+  }
+  LO_PROF_END(st);
+  LO_LAUNCH_CHECK();
+  return LO_OK;
+}
+
+// The iterations from s.k_start on, with reads of the control block in between.  *redo: a hand-off of the fused apply /
+// column step timed out, and the whole solve has to run again on the two-pass kernels.
+static int cg_streaming(CgSolve& s, bool* redo) {
+  CgDev& d = s.d; const lo_cg_params* prm = s.prm; hipStream_t st = s.st; CgCtrl& h = s.h;
+  *redo = false;
+  int rc;
+  if (s.k_start == 0) {
+    rc = cg_init(s);
+    if (rc) return rc;
+  }
+  const int first_poll = s.plan.first_stop_iteration;
+  const bool opaque = (s.op->kind == LO_OP_CALLBACK) || (s.precond_cb != nullptr); const int chunk = s.plan.poll_chunk;
+  if (opaque || prm->max_iter == 0) {  // closures cannot see the stop word: look before the first product
+    rc = cg_poll(s);
+    if (rc) return rc;
+  }
+  const int mode = s.plan.streaming_precond;
+  CgIter it;
+  it.zsrc = s.precond ? d.z : d.r;
+  it.ctrl_G = (int)std::min<int64_t>(kCtrlMaxG, ((int64_t)s.B * s.c + kThreads - 1) / kThreads);
+  it.pf_on = d.pf_gbuf && (mode == LO_STREAM_PRE_FUSED_Q || mode == LO_STREAM_PRE_FUSED_KRON);
+  it.pf_kron = it.pf_on && mode == LO_STREAM_PRE_FUSED_KRON;
+  it.kron = it.pf_kron ? PfKron{s.pre->kron_a, s.pre->kron_b, s.pre->kron_F, (int)s.op->R, (int)s.op->n2}
+                       : PfKron{nullptr, nullptr, nullptr, 0, 0};
+  it.sc_on = d.sc_gbuf && (mode == LO_STREAM_PRE_FUSED_COLS || mode == LO_STREAM_NOPRE_FUSED_COLS);
+  it.p_done = false;
+  s.dbg.sc = s.dbg.sc && it.sc_on;
+  if (s.dbg.sc) LO_HIP_CHECK(hipMemsetAsync(d.oc_dbg, 0, 16 * sizeof(long long), st));
+  // (a solve the resident phase has already closed launches no streaming iteration: its three clears -- 3 hipMemsetAsync =
+  //  4 fill kernels, ~15 us of stream time behind every headline solve -- are skipped)
+  const bool will_stream = s.k_start < prm->max_iter && !h.stop;
+  const size_t ctr_bytes = sizeof(int) * 2 * ((size_t)std::max(1, (int)prm->max_iter) + 1);  // hand-out | done
+  if (it.sc_on && will_stream) {  // cleared once per solve (tags are unique per launch)
+    LO_HIP_CHECK(hipMemsetAsync(d.sc_gbuf, 0, cg_step_cols_gbuf_bytes(), st));
+    LO_HIP_CHECK(hipMemsetAsync(d.sc_ctr, 0, ctr_bytes, st));
+    LO_HIP_CHECK(hipMemsetAsync(d.sc_gran, 0, sizeof(unsigned long long) * 3 * (size_t)s.B, st));
+  }
+  if (it.pf_on && will_stream) {  // granules and hand-out counters of the fused apply: the same
+    LO_HIP_CHECK(hipMemsetAsync(d.pf_gbuf, 0, precond_fused_gbuf_bytes(), st));
+    LO_HIP_CHECK(hipMemsetAsync(d.pf_ctr, 0, ctr_bytes, st));
+    LO_HIP_CHECK(hipMemsetAsync(d.pf_gran, 0, sizeof(unsigned long long) * (size_t)s.B, st));
+  }
+  s.launched = s.k_start;
+  for (int k = s.k_start; k < prm->max_iter && !h.stop; ++k) {
+    rc = cg_issue(s, it, k);
+    if (rc) return rc;
+    ++s.launched;
+    const bool at_poll = (k >= first_poll) && (((k - first_poll) % chunk) == 0);
+    if (at_poll || k == prm->max_iter - 1 || (opaque && k == 0)) {
+      rc = cg_poll(s);
+      if (rc) return rc;
+      if ((it.pf_on || it.sc_on) && h.oc_err) break;  // a hand-off of the fused apply timed out: redo the solve
+      if (k >= first_poll) {  // (one collective per iteration from the first possible stop on, on every rank)
+        rc = cg_global_check(s);
+        if (rc) return rc;
+      }
+    }
+  }
+  if (s.launched == 0 || !h.stop) {
+    rc = cg_poll(s);
+    if (rc) return rc;
+  }
+  *redo = (it.pf_on || it.sc_on) && h.oc_err;
+  return LO_OK;
+}
+
+// ---- close: the result and the report --------------------------------------------------------------
+static int cg_close(CgSolve& s, lo_cg_info* info) {
+  const CgCtrl& h = s.h;
+  if (!(s.x_written && s.launched == s.k_start)) {  // (no streaming iteration after the resident phase: x is final already)
+    hipLaunchKernelGGL(k_cg_final, s.gridv, s.block, 0, s.st, s.d, s.x, s.sp.rows);
+    LO_LAUNCH_CHECK();
+    LO_HIP_CHECK(hipStreamSynchronize(s.st));
+  }
+  const int rc = s.dbg.report_streaming(s.d.oc_dbg);
+  if (rc) return rc;
+  info->iterations = h.iterations; info->matvecs = s.matvecs + h.iterations; info->tolerance_reached = h.tol_reached;
+  info->nan_detected = h.nan_detected; info->skipped = h.skipped; info->last_tridiag_iter = h.last_tridiag_iter;
+  info->mean_residual = h.mean_resid; info->reserved = 0.f;
+  lo_cg_plan& ex = s.exec;
+  if (!ex.resident) {
+    ex.resident_iterations = ex.lockstep_cols = ex.lockstep_group = ex.serial_group = ex.lean = 0;
+    ex.serial_engine = LO_ENGINE_NONE;
+  }
+  ex.streaming_iterations = s.launched - s.k_start;
+  tls_last_exec = ex;
+  return LO_OK;
 }
 
 }  // namespace lo
@@ -841,618 +1427,29 @@ int lo_cg_solve_f32(const lo_op_desc* op, lo_matvec_cb matvec, void* matvec_user
   if (pre && precond_cb) return LO_ERR_BADARG;
   const bool pre_root = pre && pre->F && pre->EF && pre->rf_ld > 0;  // root form of the preconditioner available
   if (pre && (pre->k < 1 || pre->k > kMaxRank || !pre->dinv || (!pre->Q && !pre_root))) return LO_ERR_BADARG;
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t B = op->B, N = op->N;
-  const int c = (int)prm->c;
   resident_tick();
 
-  CgDev d;
-  MatvecPlan pl;
-  PlanGuard pl_guard(&pl);
-  const float* Qp = nullptr;
-  float* upart = nullptr;
-  int rc = LO_OK;
-  cg_layout(op, pre, precond_cb != nullptr, prm, ws, ws_bytes, &d, &pl, matvec, matvec_user, &Qp, &upart, st, &rc, true);
+  CgSolve s{op, pre, precond_cb, precond_user, prm, rhs, x0, x, (hipStream_t)stream, op->B, op->N, (int)prm->c};
+  PlanGuard pl_guard(&s.pl);
+  int rc = cg_setup(s, matvec, matvec_user, t_mat, ws, ws_bytes);
   if (rc) return rc;
-  const Split sp = pl.sp;
-  d.n_tridiag = prm->n_tridiag;
-  const int fmi = prm->floor_max_iter > 0 ? prm->floor_max_iter : prm->max_iter;  // (linear_cg.py:303-305)
-  d.max_iter = fmi;
-  d.n_tridiag_iter = prm->max_tridiag_iter;
-  d.T = prm->max_tridiag_iter;
-  // batch-global stopping rule over several ranks (lo_stop_reduce_cb): the device never decides the tolerance stop
-  // itself (tol = -1 can not be undercut by a mean of norms); the host evaluates the rule on the all-reduced statistic
-  const bool global_rule = prm->stop_reduce != nullptr;
-  d.tol = global_rule ? -1.0f : prm->tolerance;
-  d.eps = prm->eps;
-  d.stop_after = prm->stop_updating_after;
-  d.check_nan_first = (x0 == nullptr);
-  d.t_mat = t_mat;
-  const bool precond = (pre != nullptr) || (precond_cb != nullptr);
-  const int preR4 = pre ? padded_rank_k(pre->k) : 0;
-  const int* stop = &d.ctrl->stop;
-  dim3 gridv(sp.S, (unsigned)B), block(kThreads);
-
-  {  // control block (+ the granule buffer behind it when a resident kernel may run)
-    const bool oc_possible = op->kind == LO_OP_LOWRANK_DIAG && !resident_off();
-    const size_t span = oc_possible ? (size_t)(reinterpret_cast<char*>(d.oc_close + B + 2) - reinterpret_cast<char*>(d.ctrl))
-                                    : sizeof(CgCtrl);
-    rc = zero_span(d.ctrl, span, st);
-    if (rc) return rc;
-  }
-  if (prm->n_tridiag)
-    LO_HIP_CHECK(hipMemsetAsync(t_mat, 0, sizeof(float) * (size_t)prm->n_tridiag * B * d.T * d.T, st));
-
-  auto apply_precond = [&](const float* r, float* z, float* dotp) -> int {
-    if (pre) {
-      int e = skinny_tn(Qp, preR4, preR4, r, c, upart, B, N, sp, stop, st);
-      if (e) return e;
-      return skinny_nn(Qp, preR4, preR4, upart, pre->dinv, pre->constant_diag ? LO_DIAG_CONST : LO_DIAG_FULL, -1.0f, r,
-                       c, z, dotp, B, N, sp, stop, st);
-    }
-    int e = precond_cb(precond_user, r, z, B, N, c, (void*)st);
-    if (e) return LO_ERR_LAUNCH;
-    return vec_dot_part(r, z, c, dotp, B, N, sp, stop, st);
-  };
-
-  // ---- operator-resident fast path for the guaranteed iterations (lo_cg_onchip.hip) ----
-  int k_start = 0;
-  bool x_written = false;  // the resident kernel already wrote result * rhs_norm
-  CgCtrl h;
-  memset(&h, 0, sizeof(h));
-  // linear_cg.py:302-308 on the statistic of ALL ranks; called exactly once per completed iteration k >= first stop
-  auto global_check = [&]() -> int {
-    if (!global_rule) return LO_OK;
-    const int kdone = h.iterations - 1;
-    double vals[3] = {(double)h.mean_resid * (double)(B * c), (double)(B * c), h.stop ? 1.0 : 0.0};
-    if (prm->stop_reduce(prm->stop_reduce_user, vals)) return LO_ERR_LAUNCH;
-    const float gmean = (float)(vals[0] / vals[1]);
-    h.mean_resid = gmean;
-    if (vals[2] > 0.0) {  // some rank stopped on its own (NaN in a product): everybody stops
-      h.stop = 1;
-      return LO_OK;
-    }
-    const int kfl = std::min(10, fmi - 1);
-    const bool stopnow = kdone >= kfl && gmean < prm->tolerance &&
-                         !(prm->n_tridiag && kdone < std::min(prm->max_tridiag_iter, fmi - 1));
-    if (stopnow) {
-      h.tol_reached = 1;
-      h.stop = 1;
-    }
-    return LO_OK;
-  };
-  const int oc_nwg = onchip_num_workgroups();
-  // ---- the plan (pure: cg_plan above; lo_cg_plan_f32 reports the same decisions to the tests) ----
-  lo_cg_plan plan;
-  cg_plan(op, pre, precond_cb != nullptr, x0 != nullptr, prm, oc_nwg, &plan);
-  const int kfloor0 = plan.first_stop_iteration;
-  const bool oc_nopre = !pre && !precond_cb && d.oc_zero_q != nullptr;
-  const int ocR4 = oc_nopre ? 4 : preR4;
-  const bool oc_ok = plan.resident != 0;
-  int ls_cols = plan.lockstep_cols;
-  bool lean = plan.lean != 0;
-  const int miss_slot = lean ? lean_miss_find(op, prm, pre ? pre->generation : 0) : -1;
-  const bool lean_skipped = miss_slot >= 0 && pre && pre->Q && !getenv("LO_OC_NO_LEAN_MEMO");
-  if (lean_skipped) lean = false;  // this operator missed the floor last time: write the state in the first pass
-  lo_cg_plan exec = plan;  // the plan as executed: run-time fall-backs are recorded here (lo_cg_last_executed)
-  exec.resident = 0;
-  exec.serial_engine = LO_ENGINE_NONE;
-  exec.rspace = 0;
-  tls_rspace_resident_ran = false;
-  bool rs_force_dense = false;  // the diagonal form asked for the dense one (CgCtrl::rs_redo): one more result-only pass
-  for (int oc_pass = 0; oc_pass < 3; ++oc_pass) {
-  bool oc_redo = false;
-  if (oc_ok) {
-    OnchipArgs a;
-    a.C = pl.Apad; a.d = op->d;
-    a.d_mode = op->diag_mode;
-    if (oc_nopre) {
-      if (ls_cols < c && (getenv("LO_OC_GEN2") || !onchip5_eligible(pl.R4, N, c - ls_cols))) {  // (second generation only)
-        LO_HIP_CHECK(hipMemsetAsync(d.oc_zero_q, 0, sizeof(float) * (size_t)B * N * 4, st));
-        LO_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)d.oc_ones, 0x3f800000, (size_t)B, st));  // 1.0f
-      }
-      a.Q = d.oc_zero_q; a.dinv = d.oc_ones; a.dinv_mode = LO_DIAG_CONST;
-    } else {
-      a.Q = Qp; a.dinv = pre->dinv; a.dinv_mode = pre->constant_diag ? LO_DIAG_CONST : LO_DIAG_FULL;
-    }
-    a.rhs = rhs; a.B = B; a.N = (int)N;
-    a.c = c; a.ab_rec = prm->n_tridiag ? d.oc_ab : nullptr;
-    a.col0 = 0; a.ncols = c; a.RK = pre ? preR4 : 0; a.RCg = pl.R4;
-    a.F = nullptr; a.EF = nullptr; a.E = nullptr; a.RS = nullptr; a.RSD = nullptr;
-    a.close_gran = nullptr; a.close_count = nullptr; a.close_ctrl = nullptr; a.close_mirror = nullptr;
-    a.close_ticket = 0; a.close_tol = 0.f; a.close_floor_ok = 0;
-    bool close_in_kernel = false;
-    unsigned close_ticket = 0;
-    a.iters = kfloor0 + 1;
-    a.eps = prm->eps; a.stop_after = prm->stop_updating_after;
-    a.x = d.x; a.r = d.r; a.p = d.p; a.z = d.z;
-    auto lean_state = [&](bool on) {  // (kernels without the result-only mode get the state pointers back)
-      a.x = on ? nullptr : d.x; a.r = on ? nullptr : d.r; a.p = on ? nullptr : d.p; a.z = on ? nullptr : d.z;
-    };
-    a.rhs_norm = d.rhs_norm; a.rz = d.rz; a.alpha = d.alpha; a.beta = d.beta; a.resid_norm = d.resid_norm;
-    a.rhs_is_zero = d.rhs_is_zero; a.has_conv = d.has_conv;
-    a.resid_rec = d.oc_resid; a.init_conv = d.oc_init_conv; a.err = d.oc_err;
-    a.allow_l2_handoff = onchip_l2_handoff_allowed();
-    a.prefetch = getenv("LO_OC_NO_PREFETCH") ? 0 : 1;
-    // LO_OC_DEBUG=<member index to time> (serial-column kernels), LO_LS_DEBUG=<member> (lockstep kernel)
-    const bool ls_dbg = getenv("LO_LS_DEBUG") != nullptr && B >= 8;
-    const bool oc_dbg = !ls_dbg && getenv("LO_OC_DEBUG") != nullptr && B >= 8;
-    a.dbg = nullptr;
-    a.dbg_member = oc_dbg ? atoi(getenv("LO_OC_DEBUG")) : (ls_dbg ? atoi(getenv("LO_LS_DEBUG")) : 0);
-    // LO_OC_TEST_FALLBACK: start with the error word set, as if a hand-off had timed out (exercises the host fallback)
-    // (error word and member counters live in the control block: cleared with it, copied back with it)
-    // lo_resident_inject_timeouts(n): the same through the real bookkeeping (cool-down, re-arm) -- the multi-rank tests
-    if (getenv("LO_OC_TEST_FALLBACK") || (oc_pass == 0 && resident_take_injection()))
-      LO_HIP_CHECK(hipMemsetAsync(d.oc_err, 1, 1, st));
-    if (oc_dbg || ls_dbg) LO_HIP_CHECK(hipMemsetAsync(d.oc_dbg, 0, 16 * sizeof(long long), st));
-    rc = LO_OK;
-    bool xout_ok = true;  // every launched kernel wrote result * rhs_norm itself
-    bool serial_done = false;
-    bool rs_cols_ran = false;
-    if (plan.rspace == 1 && lean && d.rs_ws) {  // all columns on R + 1 coordinates: three streaming launches
-      a.xout = x;
-      lean_state(true);
-      a.F = pre->F; a.EF = pre->EF; a.E = pre->E; a.RS = pre->RS; a.RSD = pre->RSD;
-      rc = rspace_cols_launch(pl.R4, a, d.rs_ws, st);
-      if (rc == LO_OK) {
-        serial_done = true;
-        rs_cols_ran = true;
-      } else if (rc == LO_ERR_UNSUPPORTED) {
-        rc = LO_OK;
-      }
-    }
-    const int ls_plan = ls_cols;
-    if (rs_cols_ran) ls_cols = 0;
-    if (ls_cols) {  // third generation: columns [0, ls_cols)
-      a.ncols = ls_cols;
-      a.xout = x;
-      lean_state(lean);
-      a.gbuf = d.ls_gbuf; a.next_member = d.oc_err + 2;
-      a.dbg = ls_dbg ? d.oc_dbg : nullptr;
-      LO_HIP_CHECK(hipMemsetAsync(d.ls_gbuf, 0, lockstep_gbuf_bytes(32, 16), st));
-      a.GW = lockstep_group_size(N);
-      a.RW = (int)((N + a.GW - 1) / a.GW);
-      rc = lockstep_launch(pl.R4, pre != nullptr, a, std::min(oc_nwg, 256), st);
-      if (rc == LO_ERR_UNSUPPORTED && a.GW == 16) {  // (two workgroups per CU do not fit: one 1024-row workgroup)
-        a.GW = 8;
-        a.RW = (int)((N + 7) / 8);
-        rc = lockstep_launch(pl.R4, pre != nullptr, a, std::min(oc_nwg, 256), st);
-      }
-      if (rc == LO_OK) exec.lockstep_group = a.GW;
-      if (rc == LO_ERR_UNSUPPORTED) {  // (does not fit this device: all columns go to the serial kernels)
-        ls_cols = 0;
-        rc = onchip4_eligible(pl.R4, ocR4, N, c) ? LO_OK : LO_ERR_UNSUPPORTED;
-      }
-    }
-    // (the plan chose the root-form kernel for the serial columns -- or the lockstep kernel did not fit this device and
-    // its columns come here as well)
-    if (rc == LO_OK && !serial_done && ls_cols < c && !getenv("LO_OC_GEN2") && onchip5_eligible(pl.R4, N, c - ls_cols) &&
-        (oc_nopre || (pre_root && pre->rf_ld == pl.R4))) {
-      // root-form serial-column kernel (one all-reduce per iteration): columns [ls_cols, c)
-      a.GW = (getenv("LO_OC_GW8") && N <= 32768) ? onchip4_group_size(N) : onchip5_group_size(N);
-      a.RW = (int)((N + a.GW - 1) / a.GW);
-      a.col0 = ls_cols; a.ncols = c - ls_cols;
-      a.xout = x;
-      lean_state(lean);
-      a.F = oc_nopre ? nullptr : pre->F;
-      a.EF = oc_nopre ? nullptr : pre->EF;
-      a.E = oc_nopre ? nullptr : pre->E;
-      a.RS = (oc_nopre || plan.rspace != 2) ? nullptr : pre->RS;
-      a.RSD = (a.RS && !rs_force_dense) ? pre->RSD : nullptr;
-      tls_rspace_resident_ran = false;
-      a.gbuf = d.oc_gbuf; a.next_member = d.oc_err + 1;
-      a.dbg = oc_dbg ? d.oc_dbg : nullptr;
-      // one column, no tridiagonals, no lockstep launch in front: the kernel closes the solve itself (stop rule, NaN /
-      // skip conditions, mirror + ticket) -- no separate control launch
-      close_in_kernel = c == 1 && ls_cols == 0 && prm->n_tridiag == 0 && !oc_dbg && !getenv("LO_OC_NO_INKERNEL_CLOSE") &&
-                        pinned_status_block() != nullptr;
-      if (close_in_kernel) {
-        a.close_gran = d.oc_close;
-        a.close_count = reinterpret_cast<int*>(d.oc_close + B);
-        a.close_ctrl = d.ctrl;
-        a.close_mirror = static_cast<CgCtrl*>(pinned_status_block());
-        a.close_ticket = close_ticket = next_ticket();
-        a.close_tol = d.tol;
-        a.close_floor_ok = (a.iters - 1 >= std::min(10, d.max_iter - 1)) ? 1 : 0;
-      }
-      rc = onchip5_launch(pl.R4, a, oc_nwg, st);  // (d.oc_gbuf was cleared together with the control block)
-      if (rc != LO_OK) {
-        close_in_kernel = false;
-        a.close_gran = nullptr;
-      }
-      if (rc == LO_OK) {
-        serial_done = true;
-        exec.serial_engine = LO_ENGINE_RESIDENT_ROOT;
-        exec.serial_group = a.GW;
-      }
-      else if (rc == LO_ERR_UNSUPPORTED) rc = LO_OK;  // (does not fit: the Q-form kernels below)
-    }
-    if (rc == LO_OK && ls_cols < c && !serial_done && pre && !pre->Q) rc = LO_ERR_UNSUPPORTED;  // (root form only)
-    if (rc == LO_OK && ls_cols < c && !serial_done) {  // second (first) generation: columns [ls_cols, c)
-      if (lean) {  // (the root-form kernel did not fit after all; these kernels have no result-only mode: start over)
-        lean = false;
-        oc_redo = true;
-      }
-    }
-    if (rc == LO_OK && ls_cols < c && !serial_done && !oc_redo) {
-      lean_state(false);
-      const bool gen2 = onchip4_eligible(pl.R4, ocR4, N, c - ls_cols);
-      a.GW = gen2 ? onchip4_group_size(N) : 8;
-      a.RW = (int)((N + a.GW - 1) / a.GW);
-      a.col0 = ls_cols; a.ncols = c - ls_cols;
-      a.xout = gen2 ? x : nullptr;
-      a.gbuf = d.oc_gbuf; a.next_member = d.oc_err + 1;
-      a.dbg = oc_dbg ? d.oc_dbg : nullptr;
-      LO_HIP_CHECK(hipMemsetAsync(d.oc_gbuf, 0, onchip_gbuf_bytes(66), st));  // whole allocation
-      rc = LO_ERR_UNSUPPORTED;
-      if (gen2) rc = onchip4_launch(pl.R4, ocR4, a, oc_nwg, st);
-      if (gen2 && rc == LO_OK) {
-        exec.serial_engine = LO_ENGINE_RESIDENT_GEN2;
-        exec.serial_group = a.GW;
-      }
-      xout_ok = gen2 && rc == LO_OK;
-    }
-    if (rc && rc != LO_ERR_UNSUPPORTED) return rc;
-    if (rc == LO_OK && !oc_redo) {  // (LO_ERR_UNSUPPORTED: no resident kernel fits this device / shape -> streaming engine)
-      const int ktri = prm->n_tridiag ? std::min(a.iters, (int)prm->max_tridiag_iter) : 0;
-      const unsigned tri_grid = (unsigned)(((size_t)B * std::max(1, (int)prm->n_tridiag) + kThreads - 1) / kThreads);
-      if (ktri) {
-        LO_HIP_CHECK(hipMemsetAsync(d.oc_maxoff, 0, sizeof(int) * (prm->max_tridiag_iter + 1), st));
-        hipLaunchKernelGGL(k_oc_maxoff, dim3(tri_grid), block, 0, st, d, d.oc_ab, ktri);
-      }
-      // (with tridiagonals k_oc_tridiag follows and does not touch the control block: the mirror is final either way)
-      CgCtrl* mirror = static_cast<CgCtrl*>(pinned_status_block());
-      const unsigned ticket = close_in_kernel ? close_ticket : next_ticket();
-      if (!close_in_kernel)
-        hipLaunchKernelGGL(k_cg_ctrl_onchip, dim3(1), block, 0, st, d, d.oc_resid, d.oc_init_conv, a.iters, ktri, mirror,
-                           ticket);
-      if (ktri) hipLaunchKernelGGL(k_oc_tridiag, dim3(tri_grid), block, 0, st, d, d.oc_ab, ktri);
-      LO_LAUNCH_CHECK();
-      if (mirror) {
-        // (with tridiagonals k_oc_tridiag is still queued behind the control kernel: drain the stream as before)
-        if (ktri) LO_HIP_CHECK(hipStreamSynchronize(st));
-        else if (wait_ticket(reinterpret_cast<volatile unsigned*>(mirror) + 63, ticket, st)) return LO_ERR_LAUNCH;
-        memcpy(&h, mirror, sizeof(CgCtrl));
-      } else {
-        LO_HIP_CHECK(hipMemcpyAsync(&h, d.ctrl, sizeof(CgCtrl), hipMemcpyDeviceToHost, st));
-        LO_HIP_CHECK(hipStreamSynchronize(st));
-      }
-      const int oc_err = h.oc_err;
-      if (oc_err == 0) {
-        rc = global_check();
-        if (rc) return rc;
-      }
-      if (ls_dbg) {
-        long long ts[10];
-        LO_HIP_CHECK(hipMemcpy(ts, d.oc_dbg, sizeof(ts), hipMemcpyDeviceToHost));
-        fprintf(stderr, "lockstep item (100 MHz ticks): load+H %lld init %lld iters %lld store %lld | direction %lld "
-                "alpha+x+r %lld reduce-mfma %lld cross-wave %lld group-sum %lld\n",
-                ts[1] - ts[0], ts[2] - ts[1], ts[3] - ts[2], ts[4] - ts[3], ts[5], ts[6], ts[7], ts[8], ts[9]);
-      }
-      if (oc_dbg) {
-        long long ts[12];
-        LO_HIP_CHECK(hipMemcpy(ts, d.oc_dbg, sizeof(ts), hipMemcpyDeviceToHost));
-        if (ts[8] || ts[9])
-          fprintf(stderr, "  root-form kernel phases: updates %lld, w partials + all-reduce %lld, first-wave algebra %lld\n",
-                  ts[8], ts[9], ts[10]);
-        fprintf(stderr, "onchip member0 (100 MHz ticks): load %lld init %lld iters %lld store %lld | wg-wait %lld publish %lld poll %lld\n",
-                ts[1] - ts[0], ts[2] - ts[1], ts[3] - ts[2], ts[4] - ts[3], ts[5], ts[6], ts[7]);
-      }
-      if (oc_err == 0 && lean && h.rs_redo && tls_rspace_diag_ran && !rs_force_dense) {
-        rs_force_dense = true;  // (the result-only pass again, on the dense R-space form)
-        oc_redo = true;
-      } else if (oc_err == 0 && lean && !h.stop) {
-        // the stop rule does not hold at the floor and the state was not written: the same launches once more, in full
-        // (a root-form-only preconditioner cannot continue on the streaming engine anyway: the caller builds Q first)
-        lean_miss_note(op, prm, pre ? pre->generation : 0);
-        if (pre && !pre->Q) return LO_ERR_UNSUPPORTED;
-        lean = false;
-        oc_redo = true;
-        if (rs_cols_ran) ls_cols = ls_plan;  // (the repeat runs the engines of the plan)
-      } else if (oc_err == 0) {
-        k_start = a.iters;
-        resident_note_ok();
-        if (lean_skipped && h.stop) tls_lean_miss[miss_slot].valid = 0;  // (it stops at the floor now: speculate again)
-        exec.resident = 1;
-        exec.lockstep_cols = ls_cols;
-        exec.lean = lean ? 1 : 0;
-        exec.rspace = rs_cols_ran ? 1 : ((lean && tls_rspace_resident_ran) ? 2 : 0);
-        exec.reserved2 = (exec.rspace == 2 && tls_rspace_diag_ran) ? 1 : 0;  // 1: the diagonal form of the R-space iteration ran
-        x_written = xout_ok;
-      } else {  // a group hand-off timed out: redo everything with the streaming engine
-        fprintf(stderr, "liblo_amd: operator-resident CG timed out, falling back to the streaming engine\n");
-        onchip_note_timeout();
-        LO_HIP_CHECK(hipMemsetAsync(d.ctrl, 0, sizeof(CgCtrl), st));
-        memset(&h, 0, sizeof(h));
-      }
-    }
-  }
-  if (!oc_redo) break;
-  {  // second pass: control block and granules as at the start of the solve
-    const size_t span = (size_t)(reinterpret_cast<char*>(d.oc_close + B + 2) - reinterpret_cast<char*>(d.ctrl));
-    rc = zero_span(d.ctrl, span, st);
-    if (rc) return rc;
-    memset(&h, 0, sizeof(h));
-  }
-  }  // oc_pass
+  rc = cg_resident(s);
+  if (rc) return rc;
   // a root-form-only preconditioner cannot feed the streaming engine (initial run, redo after a timeout, or the
   // continuation beyond the resident iterations): the caller builds the Q form and calls again
-  if (pre && !pre->Q && (k_start == 0 || !h.stop)) return LO_ERR_UNSUPPORTED;
-  int matvecs = 0;
-  if (k_start == 0) {
-    // ---- initialisation (linear_cg.py:177-215) ----
-    rc = vec_dot_part(rhs, rhs, c, d.pAp_part, B, N, sp, nullptr, st);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_cg_init_scal, dim3(1), block, 0, st, d, d.pAp_part);
-    hipLaunchKernelGGL(k_cg_init_vec, gridv, block, 0, st, d, rhs, x0, sp.rows);
-    LO_LAUNCH_CHECK();
-    if (x0) {
-      rc = matvec_run(&pl, d.x, d.Ap, nullptr, nullptr, st);
-      if (rc) return rc;
-      ++matvecs;
-      const size_t nv = (size_t)B * N * c;
-      hipLaunchKernelGGL(k_cg_sub, dim3((unsigned)std::min<size_t>((nv + 255) / 256, 8192)), block, 0, st, d.r, d.Ap, nv);
-      LO_LAUNCH_CHECK();
-    }
-    rc = vec_dot_part(d.r, d.r, c, d.rr_part, B, N, sp, nullptr, st);
-    if (rc) return rc;
-    if (precond) {
-      rc = apply_precond(d.r, d.z, d.rz_part);
-      if (rc) return rc;
-    }
-    hipLaunchKernelGGL(k_cg_ctrl_init, dim3(1), block, 0, st, d);
-    LO_LAUNCH_CHECK();
-  }  // k_start == 0
-
-  // ---- iterations ----
-  const float* zsrc = precond ? d.z : d.r;
-  const int kfloor = std::min(10, fmi - 1);
-  int first_poll = kfloor;
-  if (prm->n_tridiag) first_poll = std::max(first_poll, std::min(prm->max_tridiag_iter, fmi - 1));
-  const bool opaque = (op->kind == LO_OP_CALLBACK) || (precond_cb != nullptr);
-  const int chunk = plan.poll_chunk;
-  auto poll = [&]() -> int {
-    void* hp = pinned_status_block();
-    LO_HIP_CHECK(hipMemcpyAsync(hp ? hp : &h, d.ctrl, sizeof(CgCtrl), hipMemcpyDeviceToHost, st));
-    LO_HIP_CHECK(hipStreamSynchronize(st));
-    if (hp) memcpy(&h, hp, sizeof(CgCtrl));
-    return LO_OK;
-  };
-  if (opaque || prm->max_iter == 0) {  // closures cannot see the stop word: look before the first product
-    rc = poll();
-    if (rc) return rc;
-  }
-  const int ctrl_G = (int)std::min<int64_t>(kCtrlMaxG, ((int64_t)B * c + kThreads - 1) / kThreads);
-  int k = k_start;
-  int launched = k_start;
-  // large-N single-column solves: the preconditioner apply fused with the r / x update, Q read once per iteration
-  bool pf_on = d.pf_gbuf && (plan.streaming_precond == LO_STREAM_PRE_FUSED_Q ||
-                             plan.streaming_precond == LO_STREAM_PRE_FUSED_KRON);
-  // Kronecker operator with a constant diagonal: the rows of the preconditioner's tall matrix are formed on the fly from
-  // the pivot rows of the two factors (lo_precond_desc.kron_*): 7 instead of 23 floats of traffic per row and iteration
-  PfKron kron{nullptr, nullptr, nullptr, 0, 0};
-  const bool pf_kron = pf_on && plan.streaming_precond == LO_STREAM_PRE_FUSED_KRON;
-  if (pf_kron) kron = PfKron{pre->kron_a, pre->kron_b, pre->kron_F, (int)op->R, (int)op->n2};
-  bool p_done = false;  // the fused apply of the previous iteration already wrote this iteration's p
-  // up to 32 columns, up to 16384 rows: alpha, r / x, the preconditioner, beta, p and the control step in one launch
-  bool sc_on = d.sc_gbuf && (plan.streaming_precond == LO_STREAM_PRE_FUSED_COLS ||
-                            plan.streaming_precond == LO_STREAM_NOPRE_FUSED_COLS);
-  const bool sc_dbg = sc_on && getenv("LO_SC_DEBUG") != nullptr;
-  if (sc_dbg) LO_HIP_CHECK(hipMemsetAsync(d.oc_dbg, 0, 16 * sizeof(long long), st));
-  // (a solve the resident phase has already closed launches no streaming iteration: its three clears -- 3 hipMemsetAsync =
-  //  4 fill kernels, ~15 us of stream time behind every headline solve -- are skipped)
-  const bool will_stream = k_start < prm->max_iter && !h.stop;
-  if (sc_on && will_stream) {  // cleared once per solve (tags are unique per launch)
-    LO_HIP_CHECK(hipMemsetAsync(d.sc_gbuf, 0, cg_step_cols_gbuf_bytes(), st));
-    LO_HIP_CHECK(hipMemsetAsync(d.sc_ctr, 0, sizeof(int) * 2 * ((size_t)std::max(1, (int)prm->max_iter) + 1), st));
-    LO_HIP_CHECK(hipMemsetAsync(d.sc_gran, 0, sizeof(unsigned long long) * 3 * (size_t)B, st));
-  }
-  if (pf_on && will_stream) {  // granules and hand-out counters of the fused apply: cleared once per solve (tags are unique per launch)
-    LO_HIP_CHECK(hipMemsetAsync(d.pf_gbuf, 0, precond_fused_gbuf_bytes(), st));
-    LO_HIP_CHECK(hipMemsetAsync(d.pf_ctr, 0, sizeof(int) * 2 * ((size_t)std::max(1, (int)prm->max_iter) + 1), st));
-    LO_HIP_CHECK(hipMemsetAsync(d.pf_gran, 0, sizeof(unsigned long long) * (size_t)B, st));
-  }
-  // One iteration's launches on stream `ls`.  dyn: the kernels that need the iteration index read it from the control
-  // block (the same launch sequence is then valid for every later iteration: it is captured once and replayed as a
-  // hipGraph -- the iterations of small / single operators are launch-bound: ~100 us of kernels, ~50 us of gaps).
-  auto issue = [&](int kk, bool dyn, hipStream_t ls) -> int {
-    int rcb;
-    if (p_done) {
-      rcb = matvec_run(&pl, d.p, d.Ap, d.pAp_part, stop, ls);
-      if (rcb) return rcb;
-    } else if (matvec_can_fuse_pupdate(&pl)) {
-      rcb = matvec_run_pupdate(&pl, d.p, zsrc, d.beta, kk == 0 ? 1 : 0, d.Ap, d.pAp_part, stop, ls);
-      if (rcb) return rcb;
-    } else {
-      LO_PROF_BEGIN("cg_update_p", ls);
-      hipLaunchKernelGGL(k_cg_update_p, gridv, block, 0, ls, d, zsrc, kk == 0 ? 1 : 0, sp.rows);
-      LO_PROF_END(ls);
-      LO_LAUNCH_CHECK();
-      rcb = matvec_run(&pl, d.p, d.Ap, d.pAp_part, stop, ls);
-      if (rcb) return rcb;
-    }
-    bool pre_done = false;
-    bool ctrl_done = false;  // the fused apply also took the iteration's control step
-    if (pre && pf_on) {
-      PfCtrl cf;
-      cf.on = (d.n_tridiag == 0 && kk > 0 && !getenv("LO_NO_FUSED_CTRL")) ? 1 : 0;
-      cf.rhs_is_zero = d.rhs_is_zero; cf.rz = d.rz; cf.beta = d.beta; cf.resid_norm = d.resid_norm;
-      cf.has_conv = d.has_conv; cf.stop_after = d.stop_after; cf.tol = d.tol;
-      cf.kfloor = std::min(10, d.max_iter - 1);
-      cf.done = d.pf_ctr + (std::max(1, (int)prm->max_iter) + 1);
-      cf.ctrl = d.ctrl;
-      cf.gran = d.pf_gran;
-      // single pass over Q: r / x update, Q^T r, group all-reduce, z = r/d - Q u, p = z + beta p (lo_precond_fused.hip)
-      rcb = precond_fused_rupdate(Qp, pre->dinv, pre->constant_diag ? LO_DIAG_CONST : LO_DIAG_FULL, d.r, d.Ap, d.p, d.x,
-                                  d.z, d.pAp_part, d.S_dot, d.rz, d.has_conv, d.eps, d.alpha, d.rr_part, d.rz_part, sp.S,
-                                  B, N, d.pf_gbuf, d.oc_err, d.pf_ctr, kk, dyn ? &d.ctrl->iterations : nullptr,
-                                  (int)prm->max_iter, stop, oc_nwg, &cf, pf_kron ? &kron : nullptr, ls);
-      if (rcb == LO_ERR_UNSUPPORTED) {  // (does not fit this device: the two-launch path from now on)
-        pf_on = false;
-        exec.streaming_precond = LO_STREAM_PRE_TWO_PASS;
-      }
-      else if (rcb) return rcb;
-      else {
-        pre_done = p_done = true;
-        ctrl_done = cf.on != 0;
-      }
-    }
-    if (!pre_done && sc_on) {
-      if (dyn) return LO_ERR_UNSUPPORTED;  // (not replayed as a graph node)
-      ScCtrl cf;
-      cf.on = getenv("LO_NO_FUSED_CTRL") ? 0 : 1;
-      cf.rhs_is_zero = d.rhs_is_zero; cf.beta = d.beta; cf.resid_norm = d.resid_norm;
-      cf.stop_after = d.stop_after; cf.tol = d.tol; cf.max_iter = d.max_iter;
-      cf.n_tridiag = d.n_tridiag; cf.n_tridiag_iter = d.n_tridiag_iter; cf.T = d.T; cf.t_mat = d.t_mat;
-      cf.prev_ar = d.prev_ar; cf.prev_beta = d.prev_beta; cf.check_nan_first = d.check_nan_first;
-      cf.done = d.sc_ctr + (std::max(1, (int)prm->max_iter) + 1);
-      cf.gran = d.sc_gran;
-      cf.ctrl = d.ctrl;
-      rcb = cg_step_cols(pre ? Qp : nullptr, preR4, pre ? pre->dinv : nullptr,
-                         (pre && pre->constant_diag) ? LO_DIAG_CONST : LO_DIAG_FULL, d.r, d.Ap, d.p, d.x, c, d.pAp_part,
-                         d.S_dot, d.rz, d.has_conv, d.eps, d.alpha, d.rr_part, d.rz_part, sp.S, B, N, d.sc_gbuf, d.oc_err,
-                         d.sc_ctr, kk, (int)prm->max_iter, stop, oc_nwg, &cf, sc_dbg ? d.oc_dbg : nullptr, ls);
-      if (rcb == LO_ERR_UNSUPPORTED) {  // (does not fit this device: the multi-launch path from now on)
-        sc_on = false;
-        exec.streaming_precond = pre ? LO_STREAM_PRE_TWO_PASS : LO_STREAM_PRE_NONE;
-      } else if (rcb) {
-        return rcb;
-      } else {
-        pre_done = p_done = true;
-        ctrl_done = cf.on != 0;
-        // LO_SC_TEST_FALLBACK=<k>: the error word set behind launch k, as if a hand-off had timed out (host redo path)
-        if (const char* e = getenv("LO_SC_TEST_FALLBACK"))
-          if (atoi(e) == kk) LO_HIP_CHECK(hipMemsetAsync(d.oc_err, 1, 1, ls));
-      }
-    }
-    if (!pre_done) p_done = false;  // (the two-launch path below leaves the p update to the next iteration's first step)
-    if (pre_done) {
-    } else if (pre) {
-      // r-update, x-update and the residual norm ride on the first pass over Q
-      rcb = skinny_tn_rupdate(Qp, preR4, preR4, d.r, d.Ap, d.p, d.x, d.pAp_part, d.S_dot, d.rz, d.has_conv, d.eps,
-                              d.alpha, d.rr_part, c, upart, B, N, sp, stop, ls);
-      if (rcb) return rcb;
-      rcb = skinny_nn(Qp, preR4, preR4, upart, pre->dinv, pre->constant_diag ? LO_DIAG_CONST : LO_DIAG_FULL, -1.0f, d.r,
-                      c, d.z, d.rz_part, B, N, sp, stop, ls);
-      if (rcb) return rcb;
-    } else {
-      LO_PROF_BEGIN("cg_update_xr", ls);
-      hipLaunchKernelGGL(k_cg_update_xr, gridv, block, 0, ls, d, sp.rows);
-      LO_PROF_END(ls);
-      LO_LAUNCH_CHECK();
-      if (precond) {
-        if (dyn) return LO_ERR_UNSUPPORTED;  // (closure preconditioners are not replayed)
-        rcb = apply_precond(d.r, d.z, d.rz_part);
-        if (rcb) return rcb;
-      }
-    }
-    if (ctrl_done) return LO_OK;
-    const int karg = dyn ? -1 : kk;
-    LO_PROF_BEGIN("cg_ctrl", ls);
-    if (ctrl_G == 1) {
-      hipLaunchKernelGGL(k_cg_scal_ctrl, dim3(1), block, 0, ls, d, karg);
-    } else {
-      hipLaunchKernelGGL(k_cg_scal, dim3(ctrl_G), block, 0, ls, d, karg);
-      hipLaunchKernelGGL(k_cg_ctrl, dim3(1), block, 0, ls, d, karg, ctrl_G);
-    }
-    LO_PROF_END(ls);
-    LO_LAUNCH_CHECK();
-    return LO_OK;
-  };
-  GraphReplay gr;  // (destroys the graph objects on every exit path)
-  // MEASURED SLOWER on ROCm 7.0 / MI355X (cfg4 shard 39.7 vs 38.2 ms, one dense GP of N = 4000 10.4 vs 9.8 ms: the
-  // replayed nodes start no closer together than individually launched kernels and the instantiation costs ~0.3 ms):
-  // opt-in only (LO_CG_GRAPH=1).
-  bool graph_ok = getenv("LO_CG_GRAPH") && !g_prof_on && !opaque && !precond_cb && op->kind != LO_OP_CALLBACK;
-  while (k < prm->max_iter && !h.stop) {
-    bool ran = false;
-    if (gr.exec) {
-      ran = hipGraphLaunch(gr.exec, st) == hipSuccess;
-      if (!ran) {
-        (void)hipGetLastError();
-        gr.reset();
-        graph_ok = false;
-      }
-    } else if (graph_ok && k >= k_start + 2 && prm->max_iter - k >= 8) {
-      // steady state reached (first-iteration flags gone, p_done settled): capture this iteration on a side stream
-      // (the caller's may be the legacy default stream, which cannot be captured) and replay it on the caller's
-      const bool pf0 = pf_on, pd0 = p_done;
-      if (gr.begin()) {
-        tls_graph_capture = true;
-        const int rcb = issue(k, true, gr.side);
-        tls_graph_capture = false;
-        const bool ok = gr.end() && rcb == LO_OK && pf_on == pf0 && p_done == pd0;
-        if (ok && hipGraphLaunch(gr.exec, st) == hipSuccess) {
-          ran = true;
-        } else {
-          (void)hipGetLastError();
-          gr.reset();
-          graph_ok = false;
-          pf_on = pf0;
-          p_done = pd0;
-        }
-      } else {
-        graph_ok = false;
-      }
-    }
-    if (!ran) {
-      rc = issue(k, false, st);
-      if (rc) return rc;
-    }
-    ++launched;
-    const bool at_poll = (k >= first_poll) && (((k - first_poll) % chunk) == 0);
-    if (at_poll || k == prm->max_iter - 1 || (opaque && k == 0)) {
-      rc = poll();
-      if (rc) return rc;
-      if ((pf_on || sc_on) && h.oc_err) break;  // a hand-off of the fused apply timed out: redo below
-      if (k >= first_poll) {  // (one collective per iteration from the first possible stop on, on every rank)
-        rc = global_check();
-        if (rc) return rc;
-      }
-    }
-    ++k;
-  }
-  if (launched == 0 || !h.stop) {
-    rc = poll();
-    if (rc) return rc;
-  }
-  if ((pf_on || sc_on) && h.oc_err) {  // (co-residency lost -- never seen on a dedicated GPU): the two-launch path for the whole solve
+  if (pre && !pre->Q && (s.k_start == 0 || !s.h.stop)) return LO_ERR_UNSUPPORTED;
+  bool redo = false;
+  rc = cg_streaming(s, &redo);
+  if (rc) return rc;
+  if (redo) {  // (co-residency lost -- never seen on a dedicated GPU): the two-launch path for the whole solve
     fprintf(stderr, "liblo_amd: fused preconditioner apply timed out, redoing the solve with the two-pass kernels\n");
     tls_no_fused_precond = true;
-    const int rc2 = lo_cg_solve_f32(op, matvec, matvec_user, pre, precond_cb, precond_user, prm, rhs, x0, x, t_mat, ws,
-                                    ws_bytes, info, stream);
+    rc = lo_cg_solve_f32(op, matvec, matvec_user, pre, precond_cb, precond_user, prm, rhs, x0, x, t_mat, ws, ws_bytes, info,
+                         stream);
     tls_no_fused_precond = false;
-    return rc2;
+    return rc;
   }
-  if (!(x_written && launched == k_start)) {  // (no streaming iteration after the resident phase: x is final already)
-    hipLaunchKernelGGL(k_cg_final, gridv, block, 0, st, d, x, sp.rows);
-    LO_LAUNCH_CHECK();
-    LO_HIP_CHECK(hipStreamSynchronize(st));
-  }
-
-  if (sc_dbg) {
-    long long ts[8];
-    LO_HIP_CHECK(hipMemcpy(ts, d.oc_dbg, sizeof(ts), hipMemcpyDeviceToHost));
-    if (ts[5])
-      fprintf(stderr, "cg_step_cols member 0, first workgroup (100 MHz ticks per launch): loads+alpha %.1f update+mfma %.1f "
-              "all-reduce %.1f beta+control %.1f p %.1f\n", (double)ts[0] / ts[5], (double)ts[1] / ts[5], (double)ts[2] / ts[5],
-              (double)ts[3] / ts[5], (double)ts[4] / ts[5]);
-  }
-  info->iterations = h.iterations;
-  info->matvecs = matvecs + h.iterations;
-  info->tolerance_reached = h.tol_reached;
-  info->nan_detected = h.nan_detected;
-  info->skipped = h.skipped;
-  info->last_tridiag_iter = h.last_tridiag_iter;
-  info->mean_residual = h.mean_resid;
-  info->reserved = 0.f;
-  if (!exec.resident) {
-    exec.resident_iterations = exec.lockstep_cols = exec.lockstep_group = exec.serial_group = exec.lean = 0;
-    exec.serial_engine = LO_ENGINE_NONE;
-  }
-  exec.reserved = launched - k_start;  // streaming iterations enqueued after the resident phase
-  tls_last_exec = exec;
-  return LO_OK;
+  return cg_close(s, info);
 }
 
 // The engine selection of lo_cg_solve_f32 for these arguments (pure; see cg_plan).  cus <= 0: the current device (with
@@ -1463,12 +1460,11 @@ int lo_cg_plan_f32(const lo_op_desc* op, const lo_precond_desc* pre, int has_pre
   if (prm->c < 1 || prm->c > kMaxCols) return LO_ERR_UNSUPPORTED;
   if (pre && has_precond_cb) return LO_ERR_BADARG;
   const int nwg = cus > 0 ? (cus / 32) * 32 : onchip_num_workgroups();
-  cg_plan(op, pre, has_precond_cb != 0, has_x0 != 0, prm, nwg, plan);
+  cg_plan(op, pre, has_precond_cb != 0, has_x0 != 0, prm, nwg, cg_switches(), plan);
   return LO_OK;
 }
 
-// What the calling thread's last successful lo_cg_solve_f32 launched: the plan after its run-time fall-backs
-// (`reserved` = number of streaming iterations enqueued after the resident phase).
+// What the calling thread's last successful lo_cg_solve_f32 launched: the plan after its run-time fall-backs.
 int lo_cg_last_executed(lo_cg_plan* out) {
   if (!out) return LO_ERR_BADARG;
   *out = tls_last_exec;
@@ -1505,7 +1501,7 @@ int lo_resident_inject_timeouts(int32_t n) {
 // z = P^{-1} r as a standalone call (precondition_closure, added_diag_linear_operator.py:135-140)
 size_t lo_precond_apply_workspace_bytes(int64_t B, int64_t N, int32_t k, int64_t c) {
   Split sp = choose_split(B, N, 256);
-  const int R4 = padded_rank_k(k);
+  const int R4 = padded_rank(k);
   return align_up((size_t)B * sp.S * R4 * c * sizeof(float), 256) + align_up((size_t)B * N * R4 * sizeof(float), 256) +
          1024;
 }
@@ -1515,7 +1511,7 @@ int lo_precond_apply_f32(const lo_precond_desc* pre, const float* r, float* z, i
   if (!pre || !r || !z || !ws) return LO_ERR_BADARG;
   hipStream_t st = (hipStream_t)stream;
   Split sp = choose_split(B, N, 256);
-  const int R4 = padded_rank_k(pre->k);
+  const int R4 = padded_rank(pre->k);
   Arena ar(ws, ws_bytes);
   float* upart = ar.take<float>((size_t)B * sp.S * R4 * c);
   const float* Qp = pre->Q;

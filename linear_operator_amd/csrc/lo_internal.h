@@ -249,7 +249,6 @@ struct ResidentLaunch {
   ResidentLaunch(const ResidentLaunch&) = delete;
   ResidentLaunch& operator=(const ResidentLaunch&) = delete;
 };
-extern thread_local bool tls_graph_capture;  // a CG iteration is being captured: no cross-stream event traffic
 extern bool g_onchip_disabled;  // lo_cg_set_onchip(0): streaming engines only (tests compare the two)
 extern int g_onchip_fused_timeouts;  // group exchanges of the fused solve that timed out in this process
 // A REAL hand-off timeout (co-residency lost: another process / kernel holds part of the CUs) sends the next calls to

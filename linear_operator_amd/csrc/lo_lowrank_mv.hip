@@ -517,7 +517,7 @@ bool lowrank_mv_eligible(int R4, int64_t N, int64_t c) {
 
 int lowrank_mv_run(const float* C, int R4, const float* d, int d_mode, const float* v, float* y, int64_t B, int64_t N,
                    int64_t c, const int* stop, hipStream_t st) {
-  if (!lowrank_mv_eligible(R4, N, c) || resident_off() || tls_graph_capture) return LO_ERR_UNSUPPORTED;
+  if (!lowrank_mv_eligible(R4, N, c) || resident_off()) return LO_ERR_UNSUPPORTED;
   const int ncu = onchip_num_workgroups();
   const int ct = c == 1 ? 1 : (c == 2 ? 2 : 4);
   ResidentLaunch guard(st);

@@ -51,7 +51,7 @@ while time.time() < t_end:
             dx = (r.x - runs[-1].x).abs().max().item()
             print(f"  run {i}: iterations {r.iterations} reached {r.tolerance_reached} mean residual {r.mean_residual:.3e} "
                   f"max |x - x_last| {dx:.3e}", flush=True)
-        for env in ("LO_OC_NO_WREC", "LO_OC_KEEP_STATE", "LO_OC_NO_LEAN_MEMO", "LO_OC_NO_INKERNEL_CLOSE", "LO_OC_NO_PREFETCH"):
+        for env in ("LO_OC_NO_WREC", "LO_OC_KEEP_STATE"):
             os.environ[env] = "1"
             a = K.cg_solve(desc, rhs, precond=pre, n_tridiag=nt, tolerance=tol, max_iter=max_iter)
             b = K.cg_solve(desc, rhs, precond=pre, n_tridiag=nt, tolerance=tol, max_iter=max_iter)
