@@ -54,6 +54,9 @@ extern "C" {
                                * (interpolated_linear_operator.py:192-219 over toeplitz_linear_operator.py:42-53)      */
 #define LO_OP_TOEPLITZ_DIAG 6 /* AddedDiag(Toeplitz(t), Diag(d)):          y = T v + d o v   (T symmetric, N == M)  */
 #define LO_TOEPLITZ_MAX_M 16384 /* grid sizes the native Toeplitz product takes (larger: LO_ERR_UNSUPPORTED)         */
+#define LO_OP_HADAMARD_DIAG 7 /* AddedDiag(Mul(Root(F), Root(G)), Diag(d)):  y = (F F^T o G G^T) v + d o v
+                               * (mul_linear_operator.py:54-80); A0 = F [B, N, p], R = p, A1 = G [B, N, q], n2 = q     */
+#define LO_HADAMARD_MAX_RANK 128 /* p, q the native Hadamard kernels take (larger: LO_ERR_UNSUPPORTED); any column count */
 
 /* diagonal storage */
 #define LO_DIAG_NONE 0  /* no diagonal term (plain Root / Dense / Kron operator)                    */
@@ -83,7 +86,10 @@ typedef struct lo_op_desc {
   };
   /* ABI 16 kinds.  TOEPLITZ: A0 = first column t [B, M] of the symmetric Toeplitz matrix, R = M = N.
    * SKI: A0 = t [B, M], R = M (grid size), n2 = J (interpolation points per row), `interp` as below.
-   * (The kinds reuse the existing fields: the size and layout of lo_op_desc are those of ABI 15.)              */
+   * (The kinds reuse the existing fields: the size and layout of lo_op_desc are those of ABI 15.)
+   * ABI 17 kind.  HADAMARD: A0 = F [B, N, p], R = p, A1 = G [B, N, q], n2 = q (same layout again).  Lowered for
+   * lo_matvec_f32, the streaming CG, Lanczos, fp32 MINRES and the fp32 pivoted Cholesky; fp64 entry points return
+   * LO_ERR_UNSUPPORTED; not a term kind of LO_OP_SUM.                                                              */
 } lo_op_desc;
 
 /* The interpolation matrices of an LO_OP_SKI_DIAG descriptor (interpolated_linear_operator.py:43-92): row n of W_l
@@ -652,6 +658,19 @@ int lo_toeplitz_bilinear_f32(const float* u, const float* v, int64_t B, int64_t 
                              size_t ws_bytes, void* stream);
 int lo_interp_values_grad_f32(const int64_t* idx, int64_t B, int64_t N, int64_t J, int64_t M, const float* lv,
                               const float* R, int64_t S, float* g, void* stream);
+
+/* ---- Hadamard product of two roots (ABI 17; csrc/lo_hadamard.hip) -------------------------------------------------
+ * K = (F F^T) o (G G^T), F [B, N, p], G [B, N, q], p, q <= LO_HADAMARD_MAX_RANK; U, V [B, N, S], S columns innermost.
+ *   lo_hadamard_bilinear_f32   dF [B, N, p], dG [B, N, q]: the derivatives of sum_s u_s^T K v_s with respect to F and G
+ *                              (mul_linear_operator.py:91-126 summed over both roots):
+ *                                dF[n] = sum_s u[n,s] M^v_s G[n] + v[n,s] M^u_s G[n],  M^v_s = F^T diag(v_s) G
+ *                                dG[n] = sum_s u[n,s] M^v_s^T F[n] + v[n,s] M^u_s^T F[n]
+ * Deterministic (fixed-order sums, no float atomics).  The workspace comes from the _workspace_bytes query (0: shapes
+ * outside what the kernels take).                                                                                      */
+size_t lo_hadamard_bilinear_workspace_bytes(int64_t B, int64_t N, int64_t p, int64_t q, int64_t S);
+int lo_hadamard_bilinear_f32(const float* F, const float* G, const float* U, const float* V, int64_t B, int64_t N,
+                             int64_t p, int64_t q, int64_t S, float* dF, float* dG, void* ws, size_t ws_bytes,
+                             void* stream);
 
 /* ---- measurement aid (no reference counterpart) ------------------------------------------------ */
 /* Opt-in HIP-event timing of every kernel launch of the library, recorded on the launch stream.

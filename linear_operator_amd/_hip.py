@@ -20,8 +20,10 @@ LO_OP_LOWRANK_DIAG, LO_OP_DENSE_DIAG, LO_OP_KRON_DIAG, LO_OP_CALLBACK, LO_OP_SUM
 LO_MAX_TERMS = 4
 LO_OP_SKI_DIAG, LO_OP_TOEPLITZ_DIAG = 5, 6
 LO_TOEPLITZ_MAX_M = 16384
+LO_OP_HADAMARD_DIAG = 7
+LO_HADAMARD_MAX_RANK = 128
 LO_DIAG_NONE, LO_DIAG_FULL, LO_DIAG_CONST = 0, 1, 2
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 LO_ERR_UNSUPPORTED = -4
 LO_FUSED_OK, LO_FUSED_EARLY_STOP, LO_FUSED_CONTINUE, LO_FUSED_TIMEOUT = 0, 1, 2, 3
@@ -54,6 +56,7 @@ EXPORTS = [
     "lo_interp_f32", "lo_interp_t_workspace_bytes", "lo_interp_t_f32", "lo_interp_plan_bytes", "lo_interp_plan_build",
     "lo_interp_t_planned_f32", "lo_toeplitz_workspace_bytes", "lo_toeplitz_mv_f32",
     "lo_toeplitz_bilinear_f32", "lo_interp_values_grad_f32",
+    "lo_hadamard_bilinear_workspace_bytes", "lo_hadamard_bilinear_f32",
     "lo_prof_enable", "lo_prof_report", "lo_hbm_triad_f32", "lo_hbm_copy_f32", "lo_hbm_stream_dev", "lo_peer_gather_set",
 ]
 
@@ -374,6 +377,11 @@ def load():
     lib.lo_interp_values_grad_f32.restype = C.c_int
     lib.lo_interp_values_grad_f32.argtypes = [C.c_void_p, i64, i64, i64, i64, C.c_void_p, C.c_void_p, i64, C.c_void_p,
                                               C.c_void_p]
+    lib.lo_hadamard_bilinear_workspace_bytes.restype = sz
+    lib.lo_hadamard_bilinear_workspace_bytes.argtypes = [i64, i64, i64, i64, i64]
+    lib.lo_hadamard_bilinear_f32.restype = C.c_int
+    lib.lo_hadamard_bilinear_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, i64, i64, i64, i64, i64,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, sz, C.c_void_p]
     lib.lo_hbm_triad_f32.restype = C.c_int
     lib.lo_hbm_triad_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, sz, C.c_void_p]
     lib.lo_hbm_copy_f32.restype = C.c_int

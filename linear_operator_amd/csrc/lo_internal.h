@@ -163,6 +163,9 @@ struct MatvecPlan {
   float* ski_u;       // [B, M, c]
   float* ski_t;       // [B, M, c]
   float* tz_part;
+  // LO_OP_HADAMARD_DIAG (lo_hadamard.hip): the contraction partials and the reduced M_t of every column
+  float* hd_part;
+  float* hd_m;
 };
 void matvec_plan_free(MatvecPlan* pl);
 // releases a plan's sub-plans on every exit path of the function that owns it
@@ -193,6 +196,11 @@ int matvec_run_pupdate(const MatvecPlan* pl, float* p, const float* z, const flo
 size_t ski_plan_bytes(const lo_op_desc* op, int64_t c);
 int ski_plan_init(MatvecPlan* pl, const lo_op_desc* op, int64_t c, Arena* ar, hipStream_t st);
 int ski_matvec_run(const MatvecPlan* pl, const float* v, float* y, const int* stop, hipStream_t st);
+
+// ---- Hadamard product of two roots (lo_hadamard.hip) ---------------------------------------------------------------
+size_t hadamard_plan_bytes(const lo_op_desc* op, int64_t c);
+int hadamard_plan_init(MatvecPlan* pl, const lo_op_desc* op, int64_t c, Arena* ar);
+int hadamard_matvec_run(const MatvecPlan* pl, const float* v, float* y, const int* stop, hipStream_t st);
 
 // dense / kron kernels
 int dense_matvec(const float* K, const float* d, int dd_mode, const float* v, float* y, float* dot_part, int64_t B,

@@ -42,6 +42,8 @@ size_t matvec_plan_bytes(const lo_op_desc* op, int64_t c, Split sp) {
     if (ks > 1) ar.take<float>((size_t)ks * op->B * op->N * c);
   } else if (op->kind == LO_OP_SKI_DIAG || op->kind == LO_OP_TOEPLITZ_DIAG) {
     return ski_plan_bytes(op, c) + 256;
+  } else if (op->kind == LO_OP_HADAMARD_DIAG) {
+    return hadamard_plan_bytes(op, c) + 256;
   }
   return ar.off + 256;
 }
@@ -66,6 +68,7 @@ int matvec_plan_init(MatvecPlan* pl, const lo_op_desc* op, lo_matvec_cb cb, void
   pl->ski = lo_interp_desc{};
   pl->csr_ptr = pl->csr_ids = nullptr;
   pl->ski_u = pl->ski_t = pl->tz_part = nullptr;
+  pl->hd_part = pl->hd_m = nullptr;
   if (op->B < 1 || op->N < 1 || c < 1) return LO_ERR_BADARG;
   if (op->diag_mode != LO_DIAG_NONE && !op->d) return LO_ERR_BADARG;
   switch (op->kind) {
@@ -106,6 +109,11 @@ int matvec_plan_init(MatvecPlan* pl, const lo_op_desc* op, lo_matvec_cb cb, void
     case LO_OP_SKI_DIAG:
     case LO_OP_TOEPLITZ_DIAG: {
       const int rc = ski_plan_init(pl, op, c, ar, st);
+      if (rc) return rc;
+      break;
+    }
+    case LO_OP_HADAMARD_DIAG: {
+      const int rc = hadamard_plan_init(pl, op, c, ar);
       if (rc) return rc;
       break;
     }
@@ -185,6 +193,10 @@ int matvec_run(const MatvecPlan* pl, const float* v, float* y, float* dot_part, 
       rc = ski_matvec_run(pl, v, y, stop, st);
       if (!rc && dot_part) rc = vec_dot_part(v, y, pl->c, dot_part, op.B, op.N, pl->sp, stop, st);
       return rc;
+    case LO_OP_HADAMARD_DIAG:  // (F F^T o G G^T) v + d o v: contraction M_t = F^T diag(v_t) G, expansion rowdot(F, G M_t^T)
+      rc = hadamard_matvec_run(pl, v, y, stop, st);
+      if (!rc && dot_part) rc = vec_dot_part(v, y, pl->c, dot_part, op.B, op.N, pl->sp, stop, st);
+      return rc;
     case LO_OP_CALLBACK:
       rc = pl->cb(pl->cb_user, v, y, op.B, op.N, pl->c, (void*)st);
       if (rc) return LO_ERR_LAUNCH;
@@ -221,7 +233,7 @@ using namespace lo;
 
 extern "C" {
 
-int lo_abi_version(void) { return 16; }
+int lo_abi_version(void) { return 17; }
 const char* lo_target_arch(void) { return "gfx950"; }
 
 size_t lo_matvec_workspace_bytes(const lo_op_desc* op, int64_t c) {

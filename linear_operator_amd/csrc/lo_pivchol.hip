@@ -5,6 +5,7 @@
 //   Root/LowRankRoot: row[i] = sum_r C[p,r] C[i,r]          (root_linear_operator.py:37-50, diag :22-28)
 //   Dense:            row[i] = K[p,i]                        (dense_linear_operator.py:47-50, diag :37-40)
 //   Kron:             row[i] = K1[p1,i1] K2[p2,i2]           (kronecker_product_linear_operator.py:198-216)
+//   Hadamard:         row[i] = (F_p . F_i)(G_p . G_i)        (mul_linear_operator.py:49-52, diag |F_i|^2 |G_i|^2 :43-47)
 //   Toeplitz:         row[i] = t[|p - i|]                    (toeplitz_linear_operator.py:38-40, diag :25-31)
 //   SKI:              row[i] = sum_b sum_a t[|li[p,a] - ri[i,b]|] (lv[p,a] rv[i,b])
 //                                                            (interpolated_linear_operator.py:130-144); the diagonal
@@ -117,6 +118,10 @@ __device__ __forceinline__ T src_diag(const PcDevT<T>& d, const lo_op_desc& op, 
     return A0[((size_t)b * d.N + i) * d.N + i];
   } else if (op.kind == LO_OP_CALLBACK) {  // generic operator: A1 = matrix._diagonal(), A0 = the fetched pivot rows
     return A1[(size_t)b * d.N + i];
+  } else if (op.kind == LO_OP_HADAMARD_DIAG) {
+    const T* fi = A0 + ((size_t)b * d.N + i) * op.R;
+    const T* gi = A1 + ((size_t)b * d.N + i) * op.n2;
+    return seq_dot(fi, fi, (int)op.R) * seq_dot(gi, gi, (int)op.n2);
   } else if (op.kind == LO_OP_TOEPLITZ_DIAG) {
     return A0[(size_t)b * op.R];
   } else if (op.kind == LO_OP_SKI_DIAG) {  // (left_interp(li, lv, sqrt t0) * left_interp(ri, rv, sqrt t0)), :94-101
@@ -394,6 +399,11 @@ __global__ __launch_bounds__(kThreads) void k_pc_update(PcDevT<T> d, int m) {
           tv = pc_ptr<T>(tm.A0)[((size_t)b * N + pim) * N + i];
         } else if (tm.kind == LO_OP_CALLBACK) {
           tv = pc_ptr<T>(tm.A0)[(size_t)b * N + i];  // row pi_m of this member, fetched by the host callback for this pivot
+        } else if (tm.kind == LO_OP_HADAMARD_DIAG) {
+          const int p = (int)tm.R, q = (int)tm.n2;
+          const T* F = pc_ptr<T>(tm.A0) + (size_t)b * N * p;
+          const T* G = pc_ptr<T>(tm.A1) + (size_t)b * N * q;
+          tv = seq_dot(F + (size_t)pim * p, F + (size_t)i * p, p) * seq_dot(G + (size_t)pim * q, G + (size_t)i * q, q);
         } else if (tm.kind == LO_OP_TOEPLITZ_DIAG) {
           const int lag = pim > i ? pim - i : i - pim;
           tv = pc_ptr<T>(tm.A0)[(size_t)b * tm.R + lag];
@@ -575,6 +585,8 @@ static int pc_check_desc(const lo_op_desc* op) {
           t.N != op->N)
         return LO_ERR_BADARG;
     }
+  } else if (op->kind == LO_OP_HADAMARD_DIAG) {
+    if (!op->A0 || !op->A1 || op->R < 1 || op->n2 < 1) return LO_ERR_BADARG;
   } else if (op->kind == LO_OP_TOEPLITZ_DIAG) {
     if (!op->A0 || op->R != op->N) return LO_ERR_BADARG;
   } else if (op->kind == LO_OP_SKI_DIAG) {
@@ -649,7 +661,8 @@ size_t lo_pivoted_cholesky_f64_workspace_bytes(const lo_op_desc* op, int32_t max
 int lo_pivoted_cholesky_f64(const lo_op_desc* op, int32_t max_rank, double error_tol, double* L_rows, int64_t* perm,
                             int32_t* rank_out, void* ws, size_t ws_bytes, void* stream) {
   if (!op || !L_rows || !perm || !rank_out || !ws || max_rank < 1) return LO_ERR_BADARG;
-  if (op->kind == LO_OP_SKI_DIAG || op->kind == LO_OP_TOEPLITZ_DIAG) return LO_ERR_UNSUPPORTED;  // (fp32 kinds)
+  if (op->kind == LO_OP_SKI_DIAG || op->kind == LO_OP_TOEPLITZ_DIAG || op->kind == LO_OP_HADAMARD_DIAG)
+    return LO_ERR_UNSUPPORTED;  // (fp32 kinds)
   if (const int rc = pc_check_desc(op)) return rc;
   return pc_stream_t<double>(op, nullptr, nullptr, nullptr, max_rank, error_tol, L_rows, perm, rank_out, ws, ws_bytes,
                              (hipStream_t)stream);

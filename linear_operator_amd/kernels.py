@@ -24,7 +24,7 @@ class OperatorDescriptor:
     B: int
     N: int
     A0: Optional[torch.Tensor] = None  # C [B,N,R] | K [B,N,N] | K1 [B,n1,n1]
-    A1: Optional[torch.Tensor] = None  # K2 [B,n2,n2]
+    A1: Optional[torch.Tensor] = None  # K2 [B,n2,n2] | G [B,N,q] (Hadamard: A0 = F [B,N,p])
     d: Optional[torch.Tensor] = None  # [B,N] (FULL) or [B] (CONST)
     diag_mode: int = _hip.LO_DIAG_NONE
     R: int = 0
@@ -153,6 +153,44 @@ def ski_diag_descriptor(column: torch.Tensor, left_idx: torch.Tensor, left_vals:
     ri, rv = (li, lv) if shared else (flat(right_idx), flat(right_vals))
     return _with_diag(OperatorDescriptor(_hip.LO_OP_SKI_DIAG, B, N, A0=col, R=M, n2=J, batch_shape=batch,
                                          interp=(li, lv, ri, rv), interp_plan=right_plan), d, const_diag)
+
+
+def hadamard_diag_descriptor(F: torch.Tensor, G: torch.Tensor, d: Optional[torch.Tensor], const_diag: bool = False):
+    """AddedDiag(Mul(Root(F), Root(G)), Diag(d)) (or the product alone): y = (F F^T o G G^T) v + d o v
+    (mul_linear_operator.py:54-80).  F [*batch, N, p], G [*batch, N, q] of one batch shape.  None when a rank exceeds
+    LO_HADAMARD_MAX_RANK (the caller takes the torch composition)."""
+    _hip.require_hip(F, G, d)
+    if F.shape[-1] > _hip.LO_HADAMARD_MAX_RANK or G.shape[-1] > _hip.LO_HADAMARD_MAX_RANK:
+        return None
+    batch = F.shape[:-2]
+    N, p = F.shape[-2:]
+    F3, G3 = _flat(F, 2), _flat(G, 2)
+    return _with_diag(OperatorDescriptor(_hip.LO_OP_HADAMARD_DIAG, F3.shape[0], N, A0=F3, A1=G3, R=p, n2=G.shape[-1],
+                                         batch_shape=batch), d, const_diag)
+
+
+def bilinear_hadamard(F: torch.Tensor, G: torch.Tensor, left_vecs: torch.Tensor, right_vecs: torch.Tensor):
+    """lo_hadamard_bilinear_f32: (dF, dG) of sum_s u_s^T (F F^T o G G^T) v_s, F [*b, N, p], G [*b, N, q]
+    (mul_linear_operator.py:91-126 summed over both roots).  Returned at the broadcast batch of the operands."""
+    lib = _hip.load()
+    bs0 = torch.broadcast_shapes(F.shape[:-2], G.shape[:-2])
+    U, V, bs = _uv(left_vecs, right_vecs, bs0)
+    B, N, S = U.shape
+    p, q = F.shape[-1], G.shape[-1]
+    F3 = F.expand(*bs, N, p).contiguous().reshape(B, N, p)
+    G3 = G.expand(*bs, N, q).contiguous().reshape(B, N, q)
+    _hip.require_hip(F3, G3)
+    dev = U.device
+    dF = torch.empty(B, N, p, dtype=torch.float32, device=dev)
+    dG = torch.empty(B, N, q, dtype=torch.float32, device=dev)
+    ws_bytes = lib.lo_hadamard_bilinear_workspace_bytes(B, N, p, q, S)
+    if ws_bytes == 0:
+        raise _hip.HipExtensionError(f"lo_hadamard_bilinear_f32 does not take B={B} N={N} p={p} q={q} S={S}")
+    ws = _hip.workspace(ws_bytes, dev)
+    _hip.check(lib.lo_hadamard_bilinear_f32(_hip.ptr(F3), _hip.ptr(G3), _hip.ptr(U), _hip.ptr(V), B, N, p, q, S,
+                                            _hip.ptr(dF), _hip.ptr(dG), _hip.ptr(ws), ws.numel(), _hip.stream_ptr(dev)),
+               "lo_hadamard_bilinear_f32")
+    return dF.reshape(*bs, N, p), dG.reshape(*bs, N, q)
 
 
 def interp_plan_build(idx: torch.Tensor, M: int) -> torch.Tensor:

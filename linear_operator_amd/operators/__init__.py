@@ -1,6 +1,7 @@
 """The operator classes that feed the iterative solve / logdet path."""
 from ._linear_operator import LinearOperator, to_dense
 from .added_diag_linear_operator import AddedDiagLinearOperator
+from .constant_mul_linear_operator import ConstantMulLinearOperator
 from .dense_linear_operator import DenseLinearOperator, to_linear_operator
 from .diag_linear_operator import ConstantDiagLinearOperator, DiagLinearOperator
 from .identity_linear_operator import IdentityLinearOperator
@@ -10,6 +11,7 @@ from .kronecker_product_added_diag_linear_operator import KroneckerProductAddedD
 from .linear_operator_representation_tree import LinearOperatorRepresentationTree
 from .low_rank_root_added_diag_linear_operator import LowRankRootAddedDiagLinearOperator
 from .matmul_linear_operator import MatmulLinearOperator
+from .mul_linear_operator import MulLinearOperator
 from .root_linear_operator import LowRankRootLinearOperator, RootLinearOperator
 from .sum_linear_operator import PsdSumLinearOperator, SumLinearOperator
 from .toeplitz_linear_operator import ToeplitzLinearOperator
@@ -21,5 +23,5 @@ __all__ = [
     "DiagLinearOperator", "ConstantDiagLinearOperator", "IdentityLinearOperator", "KroneckerProductLinearOperator", "KroneckerProductDiagLinearOperator",
     "LinearOperatorRepresentationTree", "RootLinearOperator", "LowRankRootLinearOperator", "SumLinearOperator",
     "PsdSumLinearOperator", "TriangularLinearOperator", "MatmulLinearOperator", "InterpolatedLinearOperator",
-    "ToeplitzLinearOperator",
+    "ToeplitzLinearOperator", "ConstantMulLinearOperator", "MulLinearOperator",
 ]

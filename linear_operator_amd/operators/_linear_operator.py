@@ -11,6 +11,7 @@ Kept seams: operator protocol (_matmul/_size/_transpose_nonbatch), `_solve` / `_
 from __future__ import annotations
 
 import itertools
+import math
 import numbers
 from collections import OrderedDict
 from typing import Callable, Optional
@@ -456,6 +457,100 @@ class LinearOperator(object):
 
     def __radd__(self, other):
         return self + other
+
+    @_implements_symmetric(torch.mul)
+    def mul(self, other):
+        """Elementwise product with a scalar, a batch of scalars ([*batch, 1, 1] or one element: `_mul_constant`), or a
+        matrix / operator of a broadcastable shape (`_mul_matrix`)."""
+        from .dense_linear_operator import to_linear_operator
+
+        if isinstance(other, LinearOperator) or torch.is_tensor(other):
+            factor = other
+        else:
+            factor = torch.tensor(other, dtype=self.dtype, device=self.device)
+        try:
+            shape = torch.broadcast_shapes(self.shape, factor.shape)
+        except RuntimeError:
+            raise RuntimeError(
+                "Cannot multiply LinearOperator of size {} by an object of size {}".format(self.shape, factor.shape)
+            )
+        if torch.is_tensor(factor):
+            if factor.numel() == 1:
+                return self._mul_constant(factor.reshape(()))
+            per_member = factor.shape[-2:] == (1, 1) and shape[:-2] == self.batch_shape
+            if per_member:
+                return self._mul_constant(factor[..., 0, 0])
+        return self._mul_matrix(to_linear_operator(factor))
+
+    def __mul__(self, other):
+        return self.mul(other)
+
+    def __rmul__(self, other):
+        return self.mul(other)
+
+    def div(self, other):
+        return self.mul(1.0 / other)
+
+    def __truediv__(self, other):
+        return self.div(other)
+
+    def _mul_constant(self, other):
+        """c A for a scalar / per-member constant; classes with a cheaper form override this."""
+        from .constant_mul_linear_operator import ConstantMulLinearOperator
+
+        return ConstantMulLinearOperator(self, other)
+
+    def _mul_matrix(self, other):
+        """A o B: evaluated densely when either side is dense, else a MulLinearOperator over the two roots."""
+        from .dense_linear_operator import DenseLinearOperator
+        from .mul_linear_operator import MulLinearOperator
+
+        a, b = self.evaluate_kernel(), other.evaluate_kernel()
+        if isinstance(a, DenseLinearOperator) or isinstance(b, DenseLinearOperator):
+            return DenseLinearOperator(a.to_dense() * b.to_dense())
+        return MulLinearOperator(a, b)
+
+    @_implements(torch.prod)
+    def prod(self, dim: int):
+        """Elementwise product of the matrices along the batch dimension `dim` (SKIP's product of 1-D kernels)."""
+        if dim is None:
+            raise ValueError("At the moment, LinearOperator.prod requires a dim argument (got None)")
+        pos = dim + self.dim() if dim < 0 else dim
+        if pos >= len(self.batch_shape):
+            raise ValueError(
+                "At the moment, LinearOperator.prod only works on batch dimensions. "
+                "Got dim={} for LinearOperator of shape {}".format(dim, self.shape)
+            )
+        return self._prod_batch(pos)
+
+    def _prod_batch(self, dim: int):
+        """Product over batch dimension `dim` (non-negative) through root decompositions: the roots of the first half of
+        the members are paired with those of the second half as MulLinearOperator(Root, Root), whose root decomposition
+        is the next level, until one pair is left.  An odd level gains the constant root 1/sqrt(N) (R R^T is the all-ones
+        matrix, the identity of the elementwise product)."""
+        from .mul_linear_operator import MulLinearOperator
+        from .root_linear_operator import RootLinearOperator
+
+        count = self.size(dim)
+        if count == 1:
+            return self[(slice(None),) * dim + (0,)]
+        roots = self.root_decomposition().root.to_dense()
+        n = self.size(-2)
+        while True:
+            if count % 2 == 1:
+                pad_shape = list(roots.shape)
+                pad_shape[dim] = 1
+                pad = torch.full(pad_shape, 1.0 / math.sqrt(n), dtype=self.dtype, device=self.device)
+                roots = torch.cat((roots, pad), dim)
+                count += 1
+            half = count // 2
+            first, second = roots.split(half, dim)
+            if half == 1:
+                return MulLinearOperator(RootLinearOperator(first.squeeze(dim).contiguous()),
+                                         RootLinearOperator(second.squeeze(dim).contiguous()))
+            level = MulLinearOperator(RootLinearOperator(first.contiguous()), RootLinearOperator(second.contiguous()))
+            roots = level.root_decomposition().root.to_dense()
+            count = half
 
     # ------------------------------------------------------------------ solves / quadratic forms / logdet
     @_implements(torch.linalg.solve)

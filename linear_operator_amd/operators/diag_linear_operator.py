@@ -56,6 +56,15 @@ class DiagLinearOperator(TriangularLinearOperator):
     def _t_matmul(self, rhs):
         return self._matmul(rhs)
 
+    def _mul_constant(self, other):
+        return DiagLinearOperator(self._diag * other[..., None])
+
+    def _mul_matrix(self, other):  # D o A keeps only A's diagonal
+        return DiagLinearOperator(self._diag * other._diagonal())
+
+    def _prod_batch(self, dim: int):  # a product of diagonal matrices is the diagonal of the products
+        return DiagLinearOperator(self._diag.prod(dim))
+
     def _size(self) -> torch.Size:
         return self._diag.shape + self._diag.shape[-1:]
 
@@ -146,6 +155,22 @@ class ConstantDiagLinearOperator(DiagLinearOperator):
 
     def _expand_batch(self, batch_shape):
         return self.__class__(self.diag_values.expand(*batch_shape, 1), diag_shape=self.diag_shape)
+
+    def _mul_constant(self, other):
+        return ConstantDiagLinearOperator(self.diag_values * other, diag_shape=self.diag_shape)
+
+    def _prod_batch(self, dim: int):
+        return ConstantDiagLinearOperator(self.diag_values.prod(dim), diag_shape=self.diag_shape)
+
+    def _mul_matrix(self, other):
+        if not isinstance(other, ConstantDiagLinearOperator):
+            return super()._mul_matrix(other)
+        if other.diag_shape != self.diag_shape:
+            raise ValueError(
+                "Dimension Mismatch: Must have same diag_shape, but got "
+                f"{self.diag_shape} and {other.diag_shape}"
+            )
+        return ConstantDiagLinearOperator(self.diag_values * other.diag_values, diag_shape=self.diag_shape)
 
     def _size(self) -> torch.Size:
         return torch.Size((*self.diag_values.shape[:-1], self.diag_shape, self.diag_shape))

@@ -31,6 +31,9 @@ class IdentityLinearOperator(ConstantDiagLinearOperator):
     def _matmul(self, rhs: Tensor) -> Tensor:
         return rhs
 
+    def _mul_matrix(self, other):  # I o A is A only for a diagonal A; as in the reference, A itself is returned
+        return other
+
     def _size(self) -> torch.Size:
         return torch.Size((*self._batch_shape, self.diag_shape, self.diag_shape))
 

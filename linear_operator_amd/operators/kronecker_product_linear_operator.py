@@ -275,6 +275,9 @@ class KroneckerProductDiagLinearOperator(DiagLinearOperator):
     def _expand_batch(self, batch_shape):
         return self.__class__(*[op._expand_batch(batch_shape) for op in self.linear_ops])
 
+    def _mul_constant(self, other):  # (the product structure is not kept: one plain diagonal)
+        return DiagLinearOperator(self._diag * other[..., None])
+
     def _bilinear_derivative(self, left_vecs: Tensor, right_vecs: Tensor):
         """sum_cols u o v is the gradient of the full diagonal [*batch, N]; factor i receives its contraction with the
         other factors' diagonals, handed to the factor's own rule (full / constant diagonal)."""

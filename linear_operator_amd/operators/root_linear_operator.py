@@ -11,6 +11,24 @@ from ._linear_operator import LinearOperator
 from .dense_linear_operator import DenseLinearOperator, to_linear_operator
 
 
+def _root_pullback(root_op, grad_root: Tensor):
+    """Derivatives with respect to root_op.representation(), given the derivative with respect to its dense root."""
+    r = root_op.root
+    if isinstance(r, DenseLinearOperator):
+        t = r.tensor
+        if not t.requires_grad:
+            return (None,)
+        return (grad_root if grad_root.shape == t.shape else grad_root.sum_to_size(*t.shape),)
+    leaves = [t.detach().requires_grad_(t.requires_grad) for t in root_op.representation()]
+    wanted = [t for t in leaves if t.requires_grad]
+    if not wanted:
+        return tuple(None for _ in leaves)
+    with torch.enable_grad():
+        dense = root_op.representation_tree()(*leaves).root.to_dense()
+        grads = iter(torch.autograd.grad(dense, wanted, grad_root.expand(dense.shape), allow_unused=True))
+    return tuple(next(grads) if t.requires_grad else None for t in leaves)
+
+
 class RootLinearOperator(LinearOperator):
     def __init__(self, root):
         root = to_linear_operator(root)
@@ -34,7 +52,12 @@ class RootLinearOperator(LinearOperator):
         (:68-72)."""
         r = self._dense_root()
         if r is None:
-            return super()._bilinear_derivative(left_vecs, right_vecs)
+            if not (left_vecs.is_cuda and self.root.size(-1) > 0):
+                return super()._bilinear_derivative(left_vecs, right_vecs)
+            # a structured root (e.g. a constant times a dense one): the derivative with respect to the dense root,
+            # pulled back through root.to_dense() by autograd
+            dense = self.root.to_dense().detach()
+            return _root_pullback(self, K.bilinear_root(dense, left_vecs, right_vecs))
         if not r.requires_grad:
             return (None,)
         res = K.bilinear_root(r, left_vecs, right_vecs)
@@ -67,6 +90,12 @@ class RootLinearOperator(LinearOperator):
 
     def _t_matmul(self, rhs):
         return self._matmul(rhs)
+
+    def _mul_constant(self, other):
+        """c R R^T = (sqrt(c) R)(sqrt(c) R)^T for c > 0; otherwise a ConstantMulLinearOperator."""
+        if not bool((other > 0).all()):
+            return super()._mul_constant(other)
+        return type(self)(self.root._mul_constant(other.sqrt()))
 
     def root_decomposition(self, method=None):
         return self

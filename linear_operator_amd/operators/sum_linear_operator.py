@@ -92,6 +92,9 @@ class SumLinearOperator(LinearOperator):
     def _t_matmul(self, rhs):
         return sum(op._t_matmul(rhs) for op in self.linear_ops)
 
+    def _mul_constant(self, other):  # c (A + B) = c A + c B, each term scaled its own way
+        return type(self)(*(op._mul_constant(other) for op in self.linear_ops))
+
     def _size(self) -> torch.Size:
         return _common_shape([op.shape for op in self.linear_ops])
 
