@@ -358,6 +358,14 @@ typedef struct lo_resident_status {
 } lo_resident_status;
 int lo_resident_status_get(lo_resident_status* out);
 int lo_resident_inject_timeouts(int32_t n);
+/* The headline solve (one column, diagonal R-space form: k_cg_rspace3) keeps what its workgroups share -- error word,
+ * member and close counters, exchange and close granules -- in ONE buffer per device that the library allocates and zeroes
+ * on first use; launches are told apart by a host-assigned tag base and epoch, so no clearing launch runs in front of a
+ * solve.  The buffer is cleared again when a counter would wrap and after any launch the host did not see closing clean.
+ * Test / debug access for the current device: force_clear != 0 makes the next such launch clear the buffer first;
+ * set_next_tag / set_next_epoch >= 0 replace the counters (to reach the wrap-around); out (or NULL) receives
+ * {next tag base, next epoch, clears so far, launches so far}.                                                        */
+int lo_resident_handoff_debug(int32_t force_clear, int64_t set_next_tag, int64_t set_next_epoch, uint32_t* out);
 
 /* ---- PivotedCholesky.forward (linear_operator/functions/_pivoted_cholesky.py:14-105) ---------- */
 /* Greedy partial pivoted Cholesky of the NON-diagonal part of `op` (op->d is ignored, as

@@ -33,7 +33,7 @@ EXPORTS = [
     "lo_abi_version", "lo_target_arch",
     "lo_matvec_workspace_bytes", "lo_matvec_f32",
     "lo_cg_workspace_bytes", "lo_cg_solve_f32", "lo_cg_set_onchip", "lo_cg_plan_f32", "lo_cg_last_executed",
-    "lo_resident_status_get", "lo_resident_inject_timeouts",
+    "lo_resident_status_get", "lo_resident_inject_timeouts", "lo_resident_handoff_debug",
     "lo_solve_fused_supported", "lo_solve_fused_workspace_bytes", "lo_solve_fused_f32", "lo_solve_fused_perm",
     "lo_cg_f64_workspace_bytes", "lo_cg_solve_f64", "lo_minres_f64_workspace_bytes", "lo_minres_f64",
     "lo_pivoted_cholesky_workspace_bytes", "lo_pivoted_cholesky_f32",
@@ -320,6 +320,8 @@ def load():
     lib.lo_resident_status_get.argtypes = [P(ResidentStatus)]
     lib.lo_resident_inject_timeouts.restype = C.c_int
     lib.lo_resident_inject_timeouts.argtypes = [C.c_int32]
+    lib.lo_resident_handoff_debug.restype = C.c_int
+    lib.lo_resident_handoff_debug.argtypes = [C.c_int32, C.c_int64, C.c_int64, P(C.c_uint32)]
     lib.lo_prof_enable.restype = C.c_int
     lib.lo_prof_enable.argtypes = [C.c_int]
     lib.lo_prof_report.restype = C.c_int

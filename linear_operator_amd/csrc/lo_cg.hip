@@ -557,6 +557,8 @@ struct CgSwitches {
   bool no_lockstep, gw8, keep_state, no_rspace_cols, no_rspace, no_wrec, no_kron_root;  // engine selection (cg_plan)
   bool no_fused_ctrl;     // the fused apply / column step leave the control step to k_cg_scal / k_cg_ctrl
   bool oc_test_fallback;  // the resident kernels start with the error word set, as if a hand-off had timed out
+  bool rs_no_diag;        // no diagonal form of the R-space iteration (rspace_launch reads it too)
+  bool clear_handoff;     // the headline solve on the caller's workspace behind a clearing launch, as every other plan
   int sc_test_fallback;   // the error word set behind the fused column step of iteration k (-1: never)
 };
 
@@ -564,7 +566,8 @@ static CgSwitches cg_switches() {
   auto on = [](const char* name) { return getenv(name) != nullptr; };
   const char* sc = getenv("LO_SC_TEST_FALLBACK");
   return {on("LO_OC_NO_LOCKSTEP"), on("LO_OC_GW8"), on("LO_OC_KEEP_STATE"), on("LO_NO_RSPACE_COLS"), on("LO_OC_NO_RSPACE"),
-          on("LO_OC_NO_WREC"), on("LO_NO_KRON_ROOT"), on("LO_NO_FUSED_CTRL"), on("LO_OC_TEST_FALLBACK"), sc ? atoi(sc) : -1};
+          on("LO_OC_NO_WREC"), on("LO_NO_KRON_ROOT"), on("LO_NO_FUSED_CTRL"), on("LO_OC_TEST_FALLBACK"), on("LO_RS_NO_DIAG"),
+          on("LO_OC_CLEAR_HANDOFF"), sc ? atoi(sc) : -1};
 }
 
 // The serial resident kernel of the columns [c - ncols, c) and its group size: the root form when it fits and the
@@ -833,8 +836,24 @@ struct CgSolve {
   int k_start = 0, launched = 0;  // iterations the resident phase completed / iterations enqueued in all
   int matvecs = 0;                // operator applications outside the iterations (x0)
   bool x_written = false;         // the resident kernels already wrote result * rhs_norm
+  bool ws_cleared = false;        // control block + granules of the workspace are zero (cg_clear_ws)
+  unsigned owned_launch = 0;      // the resident launch ran on the library's hand-off block: its id (handoff_launch_confirm)
   dim3 gridv, block;
 };
+
+// Control block and hand-off granules of the workspace as every engine but the owned launch of k_cg_rspace3 expects them:
+// ONE launch clears both.  (No-op once done; the retry loop of the resident phase clears again on its own.)
+static int cg_clear_ws(CgSolve& s) {
+  if (s.ws_cleared) return LO_OK;
+  CgDev& d = s.d;
+  const bool oc_possible = s.op->kind == LO_OP_LOWRANK_DIAG && !resident_off();
+  const size_t span = oc_possible ? (size_t)(reinterpret_cast<char*>(d.oc_close + s.B + 2) - reinterpret_cast<char*>(d.ctrl))
+                                  : sizeof(CgCtrl);
+  const int rc = zero_span(d.ctrl, span, s.st);
+  if (rc) return rc;
+  s.ws_cleared = true;
+  return LO_OK;
+}
 
 static int cg_setup(CgSolve& s, lo_matvec_cb matvec, void* matvec_user, float* t_mat, void* ws, size_t ws_bytes) {
   const lo_op_desc* op = s.op; const lo_precond_desc* pre = s.pre; const lo_cg_params* prm = s.prm;
@@ -857,13 +876,6 @@ static int cg_setup(CgSolve& s, lo_matvec_cb matvec, void* matvec_user, float* t
   s.preR4 = pre ? padded_rank(pre->k) : 0;
   s.oc_nopre = !pre && !s.precond_cb && d.oc_zero_q != nullptr;
   s.gridv = dim3(s.sp.S, (unsigned)s.B); s.block = dim3(kThreads);
-  {  // control block (+ the granule buffer behind it when a resident kernel may run)
-    const bool oc_possible = op->kind == LO_OP_LOWRANK_DIAG && !resident_off();
-    const size_t span = oc_possible ? (size_t)(reinterpret_cast<char*>(d.oc_close + s.B + 2) - reinterpret_cast<char*>(d.ctrl))
-                                    : sizeof(CgCtrl);
-    rc = zero_span(d.ctrl, span, s.st);
-    if (rc) return rc;
-  }
   if (prm->n_tridiag)
     LO_HIP_CHECK(hipMemsetAsync(t_mat, 0, sizeof(float) * (size_t)prm->n_tridiag * s.B * d.T * d.T, s.st));
   memset(&s.h, 0, sizeof(s.h));
@@ -874,7 +886,11 @@ static int cg_setup(CgSolve& s, lo_matvec_cb matvec, void* matvec_user, float* t
   s.exec = s.plan;
   s.exec.resident = 0;
   s.exec.rspace = 0;
-  return LO_OK;
+  // The control block (+ the granule buffer behind it when a resident kernel may run) is cleared here for every plan but
+  // the single column inside one resident launch: k_cg_rspace3 takes that one on the hand-off block the library owns and
+  // needs nothing of the workspace cleared (rspace3_launch_owned); whatever runs instead clears first (cg_clear_ws).
+  if (s.plan.rspace == 2 && !s.sw.clear_handoff) return LO_OK;
+  return cg_clear_ws(s);
 }
 
 // linear_cg.py:302-308 on the statistic of ALL ranks; called exactly once per completed iteration k >= first stop
@@ -938,6 +954,8 @@ static int resident_close(CgSolve& s, const OnchipArgs& a, bool lean, bool dense
   }
   int rc = LO_OK;
   if (h.oc_err == 0) {
+    // (closed without a lost hand-off: the library's block is as the next launch expects it)
+    if (s.owned_launch) handoff_launch_confirm(s.owned_launch);
     rc = cg_global_check(s);
     if (rc) return rc;
   }
@@ -964,7 +982,7 @@ static int resident_close(CgSolve& s, const OnchipArgs& a, bool lean, bool dense
   } else {  // a group hand-off timed out: redo everything with the streaming engine
     fprintf(stderr, "liblo_amd: operator-resident CG timed out, falling back to the streaming engine\n");
     onchip_note_timeout();
-    LO_HIP_CHECK(hipMemsetAsync(d.ctrl, 0, sizeof(CgCtrl), st));
+    if (s.ws_cleared) LO_HIP_CHECK(hipMemsetAsync(d.ctrl, 0, sizeof(CgCtrl), st));  // (else: cg_clear_ws before the streaming phase)
     memset(&h, 0, sizeof(h));
     *next = OcNext::kStream;
   }
@@ -993,6 +1011,7 @@ static int resident_attempt(CgSolve& s, int attempt, bool lean, bool dense, OcNe
   a.F = nullptr; a.EF = nullptr; a.E = nullptr; a.RS = nullptr; a.RSD = nullptr;
   a.close_gran = nullptr; a.close_count = nullptr; a.close_ctrl = nullptr; a.close_mirror = nullptr;
   a.close_ticket = 0; a.close_tol = 0.f; a.close_floor_ok = 0;
+  a.close_epoch = 0x80000000u; a.tag_base = 0; a.handoff_owned = 0;  // (the cleared workspace; rspace3_launch_owned replaces them)
   a.iters = s.plan.first_stop_iteration + 1; a.eps = prm->eps; a.stop_after = prm->stop_updating_after;
   a.x = d.x; a.r = d.r; a.p = d.p; a.z = d.z;
   auto lean_state = [&](bool on) {  // (kernels without the result-only mode get the state pointers back)
@@ -1007,8 +1026,10 @@ static int resident_attempt(CgSolve& s, int attempt, bool lean, bool dense, OcNe
   // LO_OC_TEST_FALLBACK: start with the error word set, as if a hand-off had timed out (exercises the host fallback)
   // (error word and member counters live in the control block: cleared with it, copied back with it)
   // lo_resident_inject_timeouts(n): the same through the real bookkeeping (cool-down, re-arm) -- the multi-rank tests
-  if (s.sw.oc_test_fallback || (attempt == 0 && resident_take_injection()))
-    LO_HIP_CHECK(hipMemsetAsync(d.oc_err, 1, 1, st));
+  // (a workspace that is not cleared yet: the error word is set behind the clearing, or in the library's own block)
+  const bool inject = s.sw.oc_test_fallback || (attempt == 0 && resident_take_injection());
+  s.owned_launch = 0;
+  if (inject && s.ws_cleared) LO_HIP_CHECK(hipMemsetAsync(d.oc_err, 1, 1, st));
   if (s.dbg.oc || s.dbg.ls) LO_HIP_CHECK(hipMemsetAsync(d.oc_dbg, 0, 16 * sizeof(long long), st));
   int rc = LO_OK; int ls = ex.lockstep_cols;
   bool rs_cols_ran = false;  // all columns are done on R + 1 coordinates
@@ -1074,7 +1095,29 @@ static int resident_attempt(CgSolve& s, int attempt, bool lean, bool dense, OcNe
       a.close_tol = d.tol;
       a.close_floor_ok = (a.iters - 1 >= std::min(10, d.max_iter - 1)) ? 1 : 0;
     }
-    rc = onchip5_launch(RC, a, s.oc_nwg, st);  // (d.oc_gbuf was cleared together with the control block)
+    // The headline plan -- diagonal form, one column, in-kernel close -- launches nothing but k_cg_rspace3: hand-off state
+    // in the library's own block, no clearing launch.  Anything else (the kernel does not take the shape, stream capture,
+    // no block) runs behind the clearing launch as before.
+    rc = LO_ERR_UNSUPPORTED;
+    if (!s.ws_cleared && close_ticket && lean && a.RSD && !s.sw.rs_no_diag && rspace_eligible(RC, N, c)) {
+      unsigned id = 0;
+      rc = rspace3_launch_owned(RC, a, s.oc_nwg, inject, &id, st);
+      if (rc == LO_OK) {
+        s.owned_launch = id;
+        tls_rspace_resident_ran = true;
+        tls_rspace_diag_ran = true;
+      } else if (rc != LO_ERR_UNSUPPORTED) {
+        return rc;
+      }
+    }
+    if (rc == LO_ERR_UNSUPPORTED) {
+      if (!s.ws_cleared) {
+        rc = cg_clear_ws(s);
+        if (rc) return rc;
+        if (inject) LO_HIP_CHECK(hipMemsetAsync(d.oc_err, 1, 1, st));
+      }
+      rc = onchip5_launch(RC, a, s.oc_nwg, st);  // (d.oc_gbuf was cleared together with the control block)
+    }
     if (rc == LO_ERR_UNSUPPORTED) {  // (does not fit this device: the Q form, after a repeat with the state if lean)
       close_ticket = 0; a.close_gran = nullptr;
       if (pre && !pre->Q) return LO_OK;  // (root form only)
@@ -1133,6 +1176,7 @@ static int cg_resident(CgSolve& s) {
     rc = zero_span(s.d.ctrl, (size_t)(reinterpret_cast<char*>(s.d.oc_close + s.B + 2) - reinterpret_cast<char*>(s.d.ctrl)),
                    s.st);
     if (rc) return rc;
+    s.ws_cleared = true;
     memset(&s.h, 0, sizeof(s.h));
   }
   return LO_OK;
@@ -1311,6 +1355,10 @@ static int cg_streaming(CgSolve& s, bool* redo) {
   *redo = false;
   int rc;
   if (s.k_start == 0) {
+    // (the owned launch of k_cg_rspace3 did not take the solve, or lost a hand-off.  When it closes a solve nothing below
+    //  reads the workspace's control block: that pass is result-only, a miss of the stop rule goes through the retry loop)
+    rc = cg_clear_ws(s);
+    if (rc) return rc;
     rc = cg_init(s);
     if (rc) return rc;
   }

@@ -1,7 +1,9 @@
 // lo_cg_close.h -- closing step of the single-column operator-resident solves (k_cg_onchip5, k_cg_rspace): the first
 // workgroup of the group that finishes LAST does what k_cg_ctrl_onchip does (stop rule linear_cg.py:302-308, NaN check
 // :199-200, "all converged before the first iteration" :207-208), mirrors the control block to pinned host memory and
-// writes the ticket.  Every member left {final residual norm | tag + flags} as one 8-byte granule in a.close_gran.
+// writes the ticket.  Every member left {final residual norm | a.close_epoch + flags} as one 8-byte granule in a.close_gran:
+// a granule has arrived when its upper 29 bits are this launch's epoch (0x80000000 over a buffer the host cleared; a
+// per-launch value in the library's own block, where the granules of earlier launches stay behind with other epochs).
 #pragma once
 #include "lo_device.h"
 #include "lo_internal.h"
@@ -26,7 +28,7 @@ __device__ __forceinline__ void cg_close_solve(const OnchipArgs& a, const int ng
       unsigned long long gr;
       for (;;) {
         gr = __hip_atomic_load(a.close_gran + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if ((unsigned)(gr >> 32) & 0x80000000u) break;
+        if (((unsigned)(gr >> 32) & ~7u) == a.close_epoch) break;
         if (++spin > R4_MAXSPIN || __hip_atomic_load(a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
           lost = true;  // a group gave up (hand-off timeout): its members never arrive -- the host redoes the solve
           break;
@@ -48,21 +50,28 @@ __device__ __forceinline__ void cg_close_solve(const OnchipArgs& a, const int ng
     const float redo = block_sum256(lredo, red_s);
     if (t == 0) {
       CgCtrl* c = a.close_ctrl;
+      // (every field the closing step owns is written: the block need not have been cleared for this launch)
+      const bool nan = anynan > 0.f;
+      const bool skip = !nan && notconv == 0.f;    // every column converged before the first iteration (:207-208)
+      const bool tol = !nan && !skip && a.close_floor_ok && mean < a.close_tol;
       c->rs_redo = redo > 0.f ? 1 : 0;
-      c->iterations = a.iters;
+      c->iterations = skip ? 0 : a.iters;
       c->mean_resid = mean;
-      if (anynan > 0.f) {
-        c->nan_detected = 1;
-        c->stop = 1;
-      } else if (notconv == 0.f) {                 // every column converged before the first iteration (:207-208)
-        c->skipped = 1;
-        c->iterations = 0;
-        c->stop = 1;
-      } else if (a.close_floor_ok && mean < a.close_tol) {
-        c->tol_reached = 1;
-        c->stop = 1;
-      }
+      c->nan_detected = nan ? 1 : 0;
+      c->skipped = skip ? 1 : 0;
+      c->tol_reached = tol ? 1 : 0;
+      c->stop = (nan || skip || tol) ? 1 : 0;
+      c->last_tridiag_iter = 0;
+      c->tri_disabled = 0;
       c->oc_err = __hip_atomic_load(a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (a.handoff_owned) {
+        // err and the counters are not words of *c here.  Every group has drawn its last member and counted itself in:
+        // the next launch (stream order) finds both counters at zero.  err stays as it is: after a lost hand-off the host
+        // clears the whole block before it is used again.
+        c->oc_next = c->oc_next_ls = c->pf_next = 0;
+        __hip_atomic_store(a.next_member, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(a.close_count, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
       if (a.close_mirror) {
         *a.close_mirror = *c;
         __threadfence_system();

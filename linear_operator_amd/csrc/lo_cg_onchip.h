@@ -46,8 +46,15 @@ struct OnchipArgs {
   // member leaves {final residual norm | tag + flags} as one 8-byte granule, the workgroup that finishes last evaluates the
   // stop rule / NaN / skip conditions of k_cg_ctrl_onchip over them and mirrors the control block to the host -- the
   // separate control launch (4 us + a dependent-launch gap) disappears.  close_gran == nullptr: the host launches it.
-  unsigned long long* close_gran;  // [B], zeroed together with the control block
-  int* close_count;                // groups that have finished, zeroed together with the control block
+  unsigned long long* close_gran;  // [B]: zeroed together with the control block, or words of the library's own hand-off
+                                   // block (handoff_owned) that earlier launches left with OTHER epochs
+  int* close_count;                // groups that have finished: zero at the start of the launch
+  unsigned close_epoch;            // upper 29 bits of an arrived close granule (the low 3 are the member's flags): 0x80000000
+                                   // over a zeroed buffer, this launch's epoch in the library's own block
+  unsigned tag_base;               // k_cg_rspace3: the tags of this launch's group exchanges start above it (0 over a zeroed
+                                   // buffer; host-assigned and larger than any earlier launch's in the library's own block)
+  int handoff_owned;               // 1: err / next_member / close_count / the granules are the library's own block, which no
+                                   // launch clears: the closing workgroup leaves the counters at zero for the next launch
   struct CgCtrl* close_ctrl;       // device control block
   struct CgCtrl* close_mirror;     // pinned host copy (or nullptr)
   unsigned close_ticket;
@@ -65,6 +72,14 @@ bool onchip5_eligible(int RC, int64_t N, int64_t c);
 int rspace_launch(int RC, const OnchipArgs& a, int nwg, hipStream_t st);
 // ... its diagonal form in the chunk-per-lane register layout (k_cg_rspace3, lo_rspace3.hip); called by rspace_launch
 int rspace3_launch(int RC, const OnchipArgs& a, int nwg, hipStream_t st);
+// ... on the hand-off block the library owns (no clearing launch in front; handoff_launch_confirm / DESIGN 4.16): `a` as for
+// rspace3_launch with the in-kernel close filled in -- gbuf, err, next_member, close_gran, close_count, tag_base and
+// close_epoch are replaced.  inject: start with the error word set (lo_resident_inject_timeouts).  *launch_id names the
+// launch for handoff_launch_confirm.  LO_ERR_UNSUPPORTED: nothing was enqueued, the caller takes the cleared workspace.
+int rspace3_launch_owned(int RC, const OnchipArgs& a, int nwg, bool inject, unsigned* launch_id, hipStream_t st);
+// the host has seen launch `launch_id` close without a lost hand-off: the block is as the next launch expects it.  Any
+// launch that is not confirmed (timeout, launch error, a result nobody waited for) makes the next one clear the block.
+void handoff_launch_confirm(unsigned launch_id);
 bool rspace_eligible(int RC, int64_t N, int64_t c);
 size_t rspace_gbuf_bytes(int nworkgroups);
 extern thread_local bool tls_rspace_diag_ran;      // ... and it ran the diagonal form (lo_precond_desc.RSD)

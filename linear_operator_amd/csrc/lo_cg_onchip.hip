@@ -48,6 +48,9 @@ ResidentLaunch::ResidentLaunch(hipStream_t st) {
 
 ResidentLaunch::~ResidentLaunch() { g_res_mu.unlock(); }
 
+ResidentLock::ResidentLock() { g_res_mu.lock(); }
+ResidentLock::~ResidentLock() { g_res_mu.unlock(); }
+
 // The same-XCD hand-off publishes granules with WORKGROUP-scope stores that other workgroups of the XCD read through the
 // shared L2: outside the HIP memory model, correct only where a CU's vector L1 is write-through into the XCD's L2.  That
 // holds on gfx950 (verified on MI355X: tools/fuzz_resident.py, the GPU test suite) -- so the path is OPT-IN per

@@ -811,7 +811,7 @@ __global__ __launch_bounds__(R4_TPB, 2 * R4_TPB / 256) void k_cg_onchip5(OnchipA
         a.has_conv[bc] = conv ? 1 : 0;
         if (!MC && a.close_gran) {  // this member's line of the closing step: one never-torn 8-byte store
           const unsigned long long gr =
-              ((unsigned long long)(0x80000000u | close_flags) << 32) | (unsigned long long)__float_as_uint(rn);
+              ((unsigned long long)(a.close_epoch | close_flags) << 32) | (unsigned long long)__float_as_uint(rn);
           __hip_atomic_store(a.close_gran + b, gr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
       }

@@ -257,6 +257,12 @@ struct ResidentLaunch {
   ResidentLaunch(const ResidentLaunch&) = delete;
   ResidentLaunch& operator=(const ResidentLaunch&) = delete;
 };
+struct ResidentLock {  // the same lock without a launch (host state that resident launches read under it)
+  ResidentLock();
+  ~ResidentLock();
+  ResidentLock(const ResidentLock&) = delete;
+  ResidentLock& operator=(const ResidentLock&) = delete;
+};
 extern bool g_onchip_disabled;  // lo_cg_set_onchip(0): streaming engines only (tests compare the two)
 extern int g_onchip_fused_timeouts;  // group exchanges of the fused solve that timed out in this process
 // A REAL hand-off timeout (co-residency lost: another process / kernel holds part of the CUs) sends the next calls to

@@ -22,6 +22,8 @@
 //
 // Numerics: fp64 sums in another order (the old kernel's results to ~1e-15 relative before the final rounding to fp32).
 #include <algorithm>
+#include <atomic>
+#include <mutex>
 #include <type_traits>
 #include <stdlib.h>
 
@@ -61,6 +63,7 @@ struct PeerOut {
   long long member_off;  // this rank's first member inside a peer's gather buffer
 };
 PeerOut g_peer_out = {{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, 0, 0};
+std::mutex g_peer_mu;  // lo_peer_gather_set against the snapshot a launch takes
 
 __host__ __device__ constexpr int r3_np(int RC) { return 2 * RC + 6; }  // w0 | u0 | s | a0 | next member | sum dinv^2 | xcc | xcc^2
 
@@ -121,7 +124,7 @@ __global__ __launch_bounds__(R3_TPB, 2) void k_cg_rspace3(OnchipArgs a, PeerOut 
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int wave_u = __builtin_amdgcn_readfirstlane(wave);
   unsigned long long* const gbase = a.gbuf + (size_t)grp * 2 * NG;  // [parity][GW][NP][2]
-  unsigned tag = 0;
+  unsigned tag = a.tag_base;  // (0 over a cleared buffer; above every earlier launch's tags in the library's own block)
   bool same_xcd = false;
   const unsigned xcc = __builtin_amdgcn_s_getreg((4 - 1) << 11 | 20) & 0xf;  // HW_REG_XCC_ID[3:0]
   bool first = true;
@@ -518,7 +521,7 @@ __global__ __launch_bounds__(R3_TPB, 2) void k_cg_rspace3(OnchipArgs a, PeerOut 
         a.has_conv[bc] = conv ? 1 : 0;
         if (a.close_gran) {
           const unsigned long long gr =
-              ((unsigned long long)(0x80000000u | close_flags) << 32) | (unsigned long long)__float_as_uint(rn);
+              ((unsigned long long)(a.close_epoch | close_flags) << 32) | (unsigned long long)__float_as_uint(rn);
           __hip_atomic_store(a.close_gran + b, gr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
       }
@@ -602,33 +605,154 @@ __global__ __launch_bounds__(R3_TPB, 2) void k_cg_rspace3(OnchipArgs a, PeerOut 
   if (a.close_gran && wig == 0) cg_close_solve(a, ngroups, t);
 }
 
+// LO_RS_PRIO: wave-priority mask of the latency-critical phases, read once per process
+int rspace3_prio() {
+  static const int prio = [] {
+    const char* e = getenv("LO_RS_PRIO");
+    return e ? atoi(e) : 3;  // iterations AND the x pass at raised priority (0.1935 -> 0.1894 ms per headline solve)
+  }();
+  return prio;
+}
+
+// ---- the hand-off block the library owns (one per device) ----
+// What a launch of k_cg_rspace3 shares between its workgroups -- the error word, the member hand-out counter, the close
+// counter, the exchange granules and the close granules -- used to be carved out of the caller's workspace, which may be
+// fresh memory on every call: one k_zero_span launch in front of every solve (2.3 us + a 4 us dependent-launch gap in front
+// of a 142 us kernel, profiles/r07).  Here they live in a buffer that is allocated and zeroed ONCE (as k_lr_mv's,
+// lo_lowrank_mv.hip) and told apart launch from launch:
+//   * exchange granules carry tags above `tag_base`, which grows by more than a workgroup can perform exchanges in a launch
+//     (one per member it takes: at most B);
+//   * close granules carry the launch's epoch in the bits above the member's three flags;
+//   * the two counters are left at zero by the closing workgroup (lo_cg_close.h), the error word stays zero while nothing
+//     is lost.
+// The block is cleared again (the old way: zero_span in front of the launch) when a counter would wrap, and when the
+// previous launch on it was not CONFIRMED clean by the host (handoff_launch_confirm): a lost hand-off, an injected one, a
+// launch error, a caller that gave up on the ticket.  Resident launches of a process never overlap (ResidentLaunch),
+// whose lock also guards this state.
+constexpr size_t HO_MAX_WGS = 2 * 320;           // two workgroups per CU, up to 320 CUs
+constexpr size_t HO_GRAN_PER_WG = 432;           // (rspace_gbuf_bytes: what a workgroup's share of a group's granules may take)
+constexpr size_t HO_MAX_MEMBERS = 65536;         // close granules; larger batches take the caller's workspace
+constexpr size_t HO_HEAD_BYTES = 256;            // err | next_member | close_count | . | (err + 4: rs_redo of the host-closed form, unused)
+constexpr unsigned HO_TAG_LIMIT = 0xfff00000u;   // tag_base + B + 2 stays below it
+constexpr unsigned HO_EPOCH_LIMIT = 0x1ffffff0u; // epochs are 29-bit and never 0
+struct HandoffBlock {
+  char* buf = nullptr;
+  size_t bytes = 0;
+  bool failed = false;
+  unsigned next_tag = 1, next_epoch = 1;
+  unsigned last_launch = 0;                 // id of the last launch on the block (0: none yet)
+  std::atomic<unsigned> confirmed{0};       // id of the last launch the host saw closing clean
+  bool force_clear = false;                 // lo_resident_handoff_debug: the next launch clears the block
+  unsigned clears = 0, launches = 0;        // (lo_resident_handoff_debug)
+};
+HandoffBlock g_handoff[16];
+std::atomic<unsigned> g_handoff_ids{0};
+
+HandoffBlock* handoff_block() {  // (called with the ResidentLaunch lock held)
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return nullptr;
+  HandoffBlock& h = g_handoff[dev];
+  if (!h.buf && !h.failed) {
+    h.bytes = HO_HEAD_BYTES + (HO_MAX_WGS * HO_GRAN_PER_WG + HO_MAX_MEMBERS) * sizeof(unsigned long long);
+    if (hipMalloc(&h.buf, h.bytes) != hipSuccess || hipMemset(h.buf, 0, h.bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      h.buf = nullptr;
+      h.failed = true;
+    }
+  }
+  return h.buf ? &h : nullptr;
+}
+
+// The counters of the next launch on the block: true when the block has to be cleared first (wrap-around).
+bool handoff_advance(unsigned* next_tag, unsigned* next_epoch, int64_t B, unsigned* tag_base, unsigned* epoch) {
+  bool wrap = false;
+  const unsigned need = (unsigned)B + 2u;  // (B <= HO_MAX_MEMBERS)
+  if (*next_tag >= HO_TAG_LIMIT - need || *next_epoch >= HO_EPOCH_LIMIT) {
+    *next_tag = 1;
+    *next_epoch = 1;
+    wrap = true;
+  }
+  *tag_base = *next_tag;
+  *epoch = *next_epoch;
+  *next_tag += need;
+  *next_epoch += 1;
+  return wrap;
+}
+
+struct OwnedLaunch {  // rspace3_go: null for a launch on the caller's (cleared) workspace
+  bool inject;
+  unsigned* launch_id;
+};
+
 template <int RC, int GW>
-int rspace3_go(const OnchipArgs& a, int nwg, hipStream_t st) {
+int rspace3_go(const OnchipArgs& a, int nwg, const OwnedLaunch* own, hipStream_t st) {
   int per_cu = 0;
   if (LO_OCCUPANCY_CACHED(per_cu, (k_cg_rspace3<RC, GW>), R3_TPB, 0) != hipSuccess || per_cu < 2) return LO_ERR_UNSUPPORTED;
   LO_PROF_BEGIN("cg_onchip", st);  // (one scope for the resident single-column kernels: lo_cg_last_executed tells them apart)
   ResidentLaunch guard(st);
   OnchipArgs a2 = a;
-  {
-    const char* e = getenv("LO_RS_PRIO");
-    a2.prefetch = e ? atoi(e) : 3;  // iterations AND the x pass at raised priority (0.1935 -> 0.1894 ms per headline solve)
+  a2.prefetch = rspace3_prio();
+  if (own) {
+    // (host-assigned tags must not be baked into a captured graph: a replay would meet its own granules)
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) {
+      (void)hipGetLastError();
+      return LO_ERR_UNSUPPORTED;
+    }
+    HandoffBlock* h = (a.B <= (int64_t)HO_MAX_MEMBERS && (size_t)2 * nwg <= HO_MAX_WGS) ? handoff_block() : nullptr;
+    if (!h) return LO_ERR_UNSUPPORTED;
+    bool clear = h->force_clear || h->last_launch != h->confirmed.load(std::memory_order_acquire);
+    h->force_clear = false;
+    clear = handoff_advance(&h->next_tag, &h->next_epoch, a.B, &a2.tag_base, &a2.close_epoch) || clear;
+    h->last_launch = g_handoff_ids.fetch_add(1, std::memory_order_relaxed) + 1;
+    if (h->last_launch == 0) h->last_launch = g_handoff_ids.fetch_add(1, std::memory_order_relaxed) + 1;
+    *own->launch_id = h->last_launch;
+    ++h->launches;
+    if (clear) {  // (ordered behind every earlier resident launch by the guard)
+      ++h->clears;
+      const int zrc = zero_span(h->buf, h->bytes, st);
+      if (zrc) return zrc;
+    }
+    a2.close_epoch <<= 3;
+    a2.handoff_owned = 1;
+    a2.err = reinterpret_cast<int*>(h->buf);
+    a2.next_member = a2.err + 1;
+    a2.close_count = a2.err + 2;
+    a2.gbuf = reinterpret_cast<unsigned long long*>(h->buf + HO_HEAD_BYTES);
+    a2.close_gran = a2.gbuf + HO_MAX_WGS * HO_GRAN_PER_WG;
+    if (own->inject) LO_HIP_CHECK(hipMemsetAsync(a2.err, 1, 1, st));
   }
-  hipLaunchKernelGGL((k_cg_rspace3<RC, GW>), dim3(2 * nwg), dim3(R3_TPB), 0, st, a2, g_peer_out);
+  PeerOut po;
+  {
+    std::lock_guard<std::mutex> lk(g_peer_mu);
+    po = g_peer_out;
+  }
+  hipLaunchKernelGGL((k_cg_rspace3<RC, GW>), dim3(2 * nwg), dim3(R3_TPB), 0, st, a2, po);
   LO_PROF_END(st);
   LO_LAUNCH_CHECK();
   return LO_OK;
 }
 
 template <int RC>
-int rspace3_gw(const OnchipArgs& a, int nwg, hipStream_t st) {
+int rspace3_gw(const OnchipArgs& a, int nwg, const OwnedLaunch* own, hipStream_t st) {
   switch (a.GW) {
-    case 1: return rspace3_go<RC, 1>(a, nwg, st);
-    case 2: return rspace3_go<RC, 2>(a, nwg, st);
-    case 4: return rspace3_go<RC, 4>(a, nwg, st);
-    case 8: return rspace3_go<RC, 8>(a, nwg, st);
-    case 16: return rspace3_go<RC, 16>(a, nwg, st);
-    case 32: return rspace3_go<RC, 32>(a, nwg, st);
+    case 1: return rspace3_go<RC, 1>(a, nwg, own, st);
+    case 2: return rspace3_go<RC, 2>(a, nwg, own, st);
+    case 4: return rspace3_go<RC, 4>(a, nwg, own, st);
+    case 8: return rspace3_go<RC, 8>(a, nwg, own, st);
+    case 16: return rspace3_go<RC, 16>(a, nwg, own, st);
+    case 32: return rspace3_go<RC, 32>(a, nwg, own, st);
   }
+  return LO_ERR_UNSUPPORTED;
+}
+
+int rspace3_dispatch(int RC, const OnchipArgs& a, int nwg, const OwnedLaunch* own, hipStream_t st) {
+  if (!a.RSD || a.x || a.c != 1 || a.ab_rec || !a.xout || a.GW > 32 || a.N < 256 || (int64_t)a.GW * R3_ROWS < a.N)
+    return LO_ERR_UNSUPPORTED;
+  // granules of a group: 2 x GW x NP x 2 -- inside what rspace_gbuf_bytes reserves per workgroup (432)
+  if (RC == 32) return rspace3_gw<32>(a, nwg, own, st);
+  if (RC == 16) return rspace3_gw<16>(a, nwg, own, st);
+  if (RC == 8) return rspace3_gw<8>(a, nwg, own, st);
   return LO_ERR_UNSUPPORTED;
 }
 
@@ -636,22 +760,46 @@ int rspace3_gw(const OnchipArgs& a, int nwg, hipStream_t st) {
 
 // The diagonal form in the chunk-per-lane layout: groups of up to 32 workgroups (N <= 32768), members of at least 256 rows,
 // rows per workgroup = 1024 (a.RW).  LO_ERR_UNSUPPORTED: rspace_launch runs k_cg_rspace<.., true>.
-int rspace3_launch(int RC, const OnchipArgs& a, int nwg, hipStream_t st) {
-  if (!a.RSD || a.x || a.c != 1 || a.ab_rec || !a.xout || a.GW > 32 || a.N < 256 || (int64_t)a.GW * R3_ROWS < a.N)
-    return LO_ERR_UNSUPPORTED;
-  // granules of a group: 2 x GW x NP x 2 -- inside what rspace_gbuf_bytes reserves per workgroup (432)
-  if (RC == 32) return rspace3_gw<32>(a, nwg, st);
-  if (RC == 16) return rspace3_gw<16>(a, nwg, st);
-  if (RC == 8) return rspace3_gw<8>(a, nwg, st);
-  return LO_ERR_UNSUPPORTED;
+int rspace3_launch(int RC, const OnchipArgs& a, int nwg, hipStream_t st) { return rspace3_dispatch(RC, a, nwg, nullptr, st); }
+
+int rspace3_launch_owned(int RC, const OnchipArgs& a, int nwg, bool inject, unsigned* launch_id, hipStream_t st) {
+  if (!a.close_gran || !a.close_ctrl || !a.close_mirror || a.dbg) return LO_ERR_UNSUPPORTED;
+  const OwnedLaunch own = {inject, launch_id};
+  return rspace3_dispatch(RC, a, nwg, &own, st);
+}
+
+void handoff_launch_confirm(unsigned launch_id) {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return;
+  g_handoff[dev].confirmed.store(launch_id, std::memory_order_release);
 }
 
 }  // namespace lo
 
 extern "C" int lo_peer_gather_set(float* const* bufs, int n, long long member_offset) {
   if (n < 0 || n > 7 || (n > 0 && !bufs)) return LO_ERR_BADARG;
+  std::lock_guard<std::mutex> lk(lo::g_peer_mu);
   for (int i = 0; i < 7; ++i) lo::g_peer_out.buf[i] = i < n ? bufs[i] : nullptr;
   lo::g_peer_out.n = n;
   lo::g_peer_out.member_off = member_offset;
+  return LO_OK;
+}
+
+// Test / debug access to the hand-off block of the current device (lo_amd.h).
+extern "C" int lo_resident_handoff_debug(int32_t force_clear, int64_t set_next_tag, int64_t set_next_epoch, uint32_t* out) {
+  lo::ResidentLock guard;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return LO_ERR_BADARG;
+  lo::HandoffBlock& h = lo::g_handoff[dev];
+  if (set_next_tag > 0xffffffffll || set_next_epoch > 0xffffffffll) return LO_ERR_BADARG;
+  if (set_next_tag >= 0) h.next_tag = (unsigned)set_next_tag;
+  if (set_next_epoch >= 0) h.next_epoch = (unsigned)set_next_epoch;
+  if (force_clear) h.force_clear = true;
+  if (out) {
+    out[0] = h.next_tag;
+    out[1] = h.next_epoch;
+    out[2] = h.clears;
+    out[3] = h.launches;
+  }
   return LO_OK;
 }

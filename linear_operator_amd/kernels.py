@@ -1530,6 +1530,16 @@ def inject_resident_timeouts(n: int):
     _hip.check(_hip.load().lo_resident_inject_timeouts(int(n)), "lo_resident_inject_timeouts")
 
 
+def resident_handoff_debug(force_clear: bool = False, next_tag: int = -1, next_epoch: int = -1) -> dict:
+    """lo_resident_handoff_debug: the hand-off buffer the library owns for the headline solve (`k_cg_rspace3`) on the
+    current device -- optionally make the next launch clear it first, or replace the tag / epoch counters (tests of the
+    wrap-around); returns the counters and how many launches / clears the buffer has seen."""
+    out = (C.c_uint32 * 4)()
+    _hip.check(_hip.load().lo_resident_handoff_debug(1 if force_clear else 0, int(next_tag), int(next_epoch), out),
+               "lo_resident_handoff_debug")
+    return {"next_tag": int(out[0]), "next_epoch": int(out[1]), "clears": int(out[2]), "launches": int(out[3])}
+
+
 def peer_gather_set(bufs=(), member_offset: int = 0) -> None:
     """lo_peer_gather_set (prototype): up to seven [B_total, N] fp32 buffers the resident single-column solve writes its
     solutions into next to its own output -- the gather of SURVEY 8(e) as peer writes.  () removes them."""
