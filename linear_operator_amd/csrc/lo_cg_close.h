@@ -27,17 +27,18 @@ __device__ __forceinline__ void cg_close_solve(const OnchipArgs& a, const int ng
     for (int64_t i = t; i < a.B && !lost; i += R4_TPB) {
       unsigned long long gr;
       for (;;) {
-        gr = __hip_atomic_load(a.close_gran + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (((unsigned)(gr >> 32) & ~7u) == a.close_epoch) break;
-        if (++spin > R4_MAXSPIN || __hip_atomic_load(a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
+        gr = granule_load(a.close_gran + i);
+        if ((granule_tag(gr) & ~7u) == a.close_epoch) break;
+        // DEVIATES from poll_give_up: the error word is read on EVERY miss, and it is set once, after the loop
+        if (++spin > kHandoffMaxSpin || __hip_atomic_load(a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
           lost = true;  // a group gave up (hand-off timeout): its members never arrive -- the host redoes the solve
           break;
         }
         __builtin_amdgcn_s_sleep(1);
       }
       if (lost) break;
-      const float rn = __uint_as_float((unsigned)(gr & 0xffffffffull));
-      const unsigned fl = (unsigned)(gr >> 32);
+      const float rn = granule_value(gr);
+      const unsigned fl = granule_tag(gr);
       lsum += rn;
       if (rn != rn || (fl & 2u)) lnan = 1.f;
       if (!(fl & 1u)) lnotconv = 1.f;

@@ -40,6 +40,7 @@
 #include "lo_device.h"
 #include "lo_internal.h"
 #include "lo_cg_onchip.h"
+#include "lo_group_reduce.h"
 
 namespace lo {
 
@@ -47,7 +48,6 @@ constexpr int LS_WROWS = 128;   // rows per wave
 constexpr int LS_NBLK = 8;      // 16-row blocks per wave
 constexpr int LS_NC = 16;       // columns advanced together
 constexpr int LS_NVP = 832;     // payload slots allocated per workgroup (>= NV of every instantiation)
-constexpr unsigned LS_MAXSPIN = 1u << 20;
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -110,11 +110,7 @@ __device__ __forceinline__ void ls_group_sum(float (*part)[LS_NVP], float* res, 
   const unsigned tag = ++g.tag;
   __syncthreads();
   unsigned long long* slot = g.gslot + (size_t)(tag & 1u) * (GW + 1) * LS_NVP;  // GW partial arrays | one totals array
-  auto publish = [&](unsigned long long* dst, float v) {
-    const unsigned long long mine = ((unsigned long long)tag << 32) | (unsigned long long)__float_as_uint(v);
-    if (g.same_xcd) __hip_atomic_store(dst, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    else __hip_atomic_store(dst, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  };
+  auto publish = [&](unsigned long long* dst, float v) { granule_store(dst, granule_pack(tag, v), g.same_xcd); };
   // sum over NW consecutive granules (stride LS_NVP) of entry e, waiting for their tags
   constexpr int NG = GW < 8 ? GW : 8;  // granules of one entry gathered at a time
   auto gather8 = [&](const unsigned long long* src, int e) -> float {
@@ -124,17 +120,12 @@ __device__ __forceinline__ void ls_group_sum(float (*part)[LS_NVP], float* res, 
       bool ok = true;
 #pragma unroll
       for (int w = 0; w < NG; ++w) {
-        const unsigned long long x =
-            __hip_atomic_load(src + (size_t)w * LS_NVP + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        ok = ok && ((unsigned)(x >> 32) == tag);
-        vals[w] = __uint_as_float((unsigned)(x & 0xffffffffull));
+        const unsigned long long x = granule_load(src + (size_t)w * LS_NVP + e);
+        ok = ok && (granule_tag(x) == tag);
+        vals[w] = granule_value(x);
       }
       if (ok) break;
-      if (++spin > LS_MAXSPIN ||
-          ((spin & 1023u) == 0 && __hip_atomic_load(g.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
-        atomicExch(g.err, 1);  // timed out, or another workgroup already did: give up at once
-        break;
-      }
+      if (poll_give_up(spin, g.err)) break;
       __builtin_amdgcn_s_sleep(1);
     }
     float tot = 0.f;
@@ -157,21 +148,7 @@ __device__ __forceinline__ void ls_group_sum(float (*part)[LS_NVP], float* res, 
     const int lo = g.wig * per, hi = min(cnt, lo + per);
     for (int e = lo + t; e < hi; e += TPB)  // (fixed order: workgroups 0-7, then 8-15)
       publish(tot + e, gather8(slot, e) + gather8(slot + (size_t)8 * LS_NVP, e));
-    for (int e = t; e < cnt; e += TPB) {
-      unsigned spin = 0;
-      unsigned long long x;
-      for (;;) {
-        x = __hip_atomic_load(tot + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if ((unsigned)(x >> 32) == tag) break;
-        if (++spin > LS_MAXSPIN ||
-            ((spin & 1023u) == 0 && __hip_atomic_load(g.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
-          atomicExch(g.err, 1);
-          break;
-        }
-        __builtin_amdgcn_s_sleep(1);
-      }
-      res[e] = __uint_as_float((unsigned)(x & 0xffffffffull));
-    }
+    for (int e = t; e < cnt; e += TPB) res[e] = granule_value(granule_wait(tot + e, tag, g.err));
   }
   __syncthreads();
 }
@@ -200,13 +177,9 @@ __global__ __launch_bounds__(NW * 64, 2) void k_cg_lockstep(OnchipArgs a) {
   __shared__ float res[LS_NVP];
   __shared__ float h_s[NH * 4 * 64];            // H = C^T Q in the A-operand order [(h, s)][lane]
 
-  const int wg = blockIdx.x;
-  const int xcd = wg % 8, jx = wg / 8;  // block b runs on XCD b % 8: keep a group behind one L2 (speed only)
-  const int groups_per_xcd = (gridDim.x / 8) / GW;
-  const int grp = xcd * groups_per_xcd + jx / GW;
-  const int wig = jx % GW;
-  const int ngroups = groups_per_xcd * 8;
-  if (jx / GW >= groups_per_xcd) return;
+  const GroupPlace gp = group_place(GW);
+  if (!gp.active) return;  // (surplus workgroup)
+  const int grp = gp.grp, wig = gp.wig, ngroups = gp.ngroups;
   const int t = threadIdx.x, lane = t & 63, w = __builtin_amdgcn_readfirstlane(t >> 6), kk = lane >> 4, n = lane & 15;
   if (t < NP) part[t][NV] = 0.f;  // the hand-out slot of the payload (first barrier: the placement check below)
   LsGroup g;
@@ -216,15 +189,14 @@ __global__ __launch_bounds__(NW * 64, 2) void k_cg_lockstep(OnchipArgs a) {
   g.err = a.err;
   g.same_xcd = false;
   {  // placement check through the agent-scope path (see lo_cg_onchip4.hip)
-    const unsigned xcc = __builtin_amdgcn_s_getreg((4 - 1) << 11 | 20) & 0xf;  // HW_REG_XCC_ID[3:0]
+    const unsigned xcc = xcc_id();
     if (t < 2) {
       part[0][t] = t == 0 ? (float)xcc : (float)(xcc * xcc);
 #pragma unroll
       for (int q = 1; q < NP; ++q) part[q][t] = 0.f;
     }
     ls_group_sum<GW, NP, LS_TPB>(part, res, 2, g);
-    const float fx = (float)xcc;
-    g.same_xcd = (res[0] == GW * fx) && (res[1] == GW * fx * fx) && (a.allow_l2_handoff != 0);
+    g.same_xcd = same_xcd_verdict(res[0], res[1], GW, xcc, a.allow_l2_handoff);
     __syncthreads();
   }
 
@@ -237,7 +209,7 @@ __global__ __launch_bounds__(NW * 64, 2) void k_cg_lockstep(OnchipArgs a) {
     __shared__ int cu_slot;
     if (t == 0) {
       const unsigned hwid = __builtin_amdgcn_s_getreg((32 - 1) << 11 | 4);   // HW_REG_HW_ID
-      const unsigned xcc = __builtin_amdgcn_s_getreg((4 - 1) << 11 | 20) & 0xf;
+      const unsigned xcc = xcc_id();
       int* counters = reinterpret_cast<int*>(a.gbuf + (size_t)ngroups_total_slots(gridDim.x, GW));
       cu_slot = atomicAdd(counters + ((xcc << 8) | ((hwid >> 8) & 0xffu)), 1);
     }

@@ -40,13 +40,9 @@ __global__ __launch_bounds__(R4_TPB, 2 * R4_TPB / 256) void k_cg_onchip4(OnchipA
   __shared__ float4 q_s[R4_ROWS * NQ];  // Q rows of this workgroup, swizzled 16-byte slots
   __shared__ float x_s[R4_ROWS], d_s[R4_ROWS], dinv_s[R4_ROWS];  // per-row x, d, 1/d (VGPR budget: 256 with 2 WGs per CU)
   constexpr int gw = GW;
-  const int wg = blockIdx.x;
-  const int xcd = wg % 8, jx = wg / 8;  // block b runs on XCD b % 8: keep a group behind one L2 (speed only)
-  const int groups_per_xcd = (gridDim.x / 8) / gw;
-  const int grp = xcd * groups_per_xcd + jx / gw;
-  const int wig = jx % gw;
-  const int ngroups = groups_per_xcd * 8;
-  if (jx / gw >= groups_per_xcd) return;
+  const GroupPlace gp = group_place(gw);
+  if (!gp.active) return;  // (surplus workgroup)
+  const int grp = gp.grp, wig = gp.wig, ngroups = gp.ngroups;
   const int t = threadIdx.x;
   R4Group g;
   g.gslot = a.gbuf + (size_t)grp * 2 * gw * R4_SLOT;
@@ -55,19 +51,7 @@ __global__ __launch_bounds__(R4_TPB, 2 * R4_TPB / 256) void k_cg_onchip4(OnchipA
   g.tag = 0;
   g.err = a.err;
   g.same_xcd = false;
-  {  // placement check through the agent-scope path: plain-store hand-off only when the whole group shares an XCD;
-     // sum and sum of squares of the XCC ids agree with gw * id and gw * id^2 only if all ids are equal
-    const unsigned xcc = __builtin_amdgcn_s_getreg((4 - 1) << 11 | 20) & 0xf;  // HW_REG_XCC_ID[3:0]
-    if (t < 64) {
-      sh.red[0][0] = (float)xcc;
-      sh.red[0][1] = (float)(xcc * xcc);
-    }
-    if (t < 2 * (R4_WAVES - 1)) sh.red[1 + t / 2][t % 2] = 0.f;
-    r4_group_sum<GW>(sh, 2, g);
-    const float fx = (float)xcc;
-    g.same_xcd = (sh.res[0] == gw * fx) && (sh.res[1] == gw * fx * fx) && (a.allow_l2_handoff != 0);
-    __syncthreads();
-  }
+  r4_placement_check<GW>(sh, g, a.allow_l2_handoff);  // plain-store hand-off only when the whole group shares an XCD
 
   const int row0 = wig * a.RW;
   const int nv = max(0, min(a.RW, a.N - row0));  // rows of this workgroup
@@ -403,13 +387,9 @@ __global__ __launch_bounds__(R4_TPB, 2 * R4_TPB / 256) void k_cg_onchip5(OnchipA
   __shared__ __attribute__((aligned(16))) float e_s[WR ? RC * FLD : 4];
   __shared__ float x_s[R4_ROWS], d_s[R4_ROWS], dinv_s[R4_ROWS];
   __shared__ float4 stage_s[R4_WAVES * 64 * (RC / 4)];  // per-wave transposition window of the member load
-  const int wg = blockIdx.x;
-  const int xcd = wg % 8, jx = wg / 8;
-  const int groups_per_xcd = (gridDim.x / 8) / GW;
-  const int grp = xcd * groups_per_xcd + jx / GW;
-  const int wig = jx % GW;
-  const int ngroups = groups_per_xcd * 8;
-  if (jx / GW >= groups_per_xcd) return;
+  const GroupPlace gp = group_place(GW);
+  if (!gp.active) return;  // (surplus workgroup)
+  const int grp = gp.grp, wig = gp.wig, ngroups = gp.ngroups;
   const int t = threadIdx.x, lane = t & 63;
   R4Group g;
   g.gslot = a.gbuf + (size_t)grp * 2 * (GW == 64 ? GW + 1 : GW) * R4_SLOT;
@@ -418,18 +398,7 @@ __global__ __launch_bounds__(R4_TPB, 2 * R4_TPB / 256) void k_cg_onchip5(OnchipA
   g.tag = 0;
   g.err = a.err;
   g.same_xcd = false;
-  {
-    const unsigned xcc = __builtin_amdgcn_s_getreg((4 - 1) << 11 | 20) & 0xf;  // HW_REG_XCC_ID[3:0]
-    if (t < 64) {
-      sh.red[0][0] = (float)xcc;
-      sh.red[0][1] = (float)(xcc * xcc);
-    }
-    if (t < 2 * (R4_WAVES - 1)) sh.red[1 + t / 2][t % 2] = 0.f;
-    r4_group_sum<GW>(sh, 2, g);
-    const float fx = (float)xcc;
-    g.same_xcd = (sh.res[0] == GW * fx) && (sh.res[1] == GW * fx * fx) && (a.allow_l2_handoff != 0);
-    __syncthreads();
-  }
+  r4_placement_check<GW>(sh, g, a.allow_l2_handoff);
   const int row0 = wig * a.RW;
   const int nv = max(0, min(a.RW, a.N - row0));
   const bool pre = a.F != nullptr;
@@ -810,9 +779,7 @@ __global__ __launch_bounds__(R4_TPB, 2 * R4_TPB / 256) void k_cg_onchip5(OnchipA
         a.resid_norm[bc] = rn;
         a.has_conv[bc] = conv ? 1 : 0;
         if (!MC && a.close_gran) {  // this member's line of the closing step: one never-torn 8-byte store
-          const unsigned long long gr =
-              ((unsigned long long)(a.close_epoch | close_flags) << 32) | (unsigned long long)__float_as_uint(rn);
-          __hip_atomic_store(a.close_gran + b, gr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          granule_store(a.close_gran + b, granule_pack(a.close_epoch | close_flags, rn), /*same_xcd=*/false);
         }
       }
       __syncthreads();

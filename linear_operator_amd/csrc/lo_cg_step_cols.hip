@@ -143,13 +143,9 @@ template <int GW, int CT, bool PRE, int RB>
 __global__ __launch_bounds__(SC_TPB, 2) void k_cg_step_cols(ScArgs a) {
   if (a.stop && *a.stop) return;
   __shared__ ScShared sh;
-  const int wg = blockIdx.x;
-  const int xcd = wg % 8, jx = wg / 8;
-  const int groups_per_xcd = (gridDim.x / 8) / GW;
-  const int grp = xcd * groups_per_xcd + jx / GW;
-  const int wig = jx % GW;
-  const int ngroups = groups_per_xcd * 8;
-  if (jx / GW >= groups_per_xcd) return;
+  const GroupPlace gp = group_place(GW);
+  if (!gp.active) return;  // (surplus workgroup)
+  const int grp = gp.grp, wig = gp.wig, ngroups = gp.ngroups;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int n = lane & 15, kk = lane >> 4;
   R4Group g;
@@ -458,10 +454,10 @@ __global__ __launch_bounds__(SC_TPB, 2) void k_cg_step_cols(ScArgs a) {
         ln += sh.pa[1][j];
         lm = fmaxf(lm, sh.pa[2][j]);
       }
-      const unsigned long long tg = (unsigned long long)(unsigned)(k_it + 1) << 32;
-      __hip_atomic_store(a.cf.gran + b, tg | __float_as_uint(ls), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(a.cf.gran + a.B + b, tg | __float_as_uint(ln), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(a.cf.gran + 2 * a.B + b, tg | __float_as_uint(lm), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const unsigned tg = (unsigned)(k_it + 1);
+      granule_store(a.cf.gran + b, granule_pack(tg, ls), /*same_xcd=*/false);
+      granule_store(a.cf.gran + a.B + b, granule_pack(tg, ln), /*same_xcd=*/false);
+      granule_store(a.cf.gran + 2 * a.B + b, granule_pack(tg, lm), /*same_xcd=*/false);
       cf_old = atomicAdd(a.cf.done, 1);
     }
     if (stamp) c4 = wall_clock64();
@@ -543,18 +539,11 @@ __global__ __launch_bounds__(SC_TPB, 2) void k_cg_step_cols(ScArgs a) {
       if (last) {  // every member of the batch is recorded: the batch-global decisions (cg_ctrl_body), fixed order
         float ls = 0.f, ln = 0.f, lm = -INFINITY;
         const unsigned want = (unsigned)(k_it + 1);
-        for (int64_t i = t; i < 3 * a.B; i += 64) {
-          unsigned long long gq;
-          unsigned spin = 0;
-          do {  // (the counter said every member was issued; its granules may still be on their way)
-            gq = __hip_atomic_load(a.cf.gran + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          } while ((unsigned)(gq >> 32) != want && ++spin < R4_MAXSPIN);
-          if ((unsigned)(gq >> 32) != want) atomicExch(a.err, 1);
-        }
+        for (int64_t i = t; i < 3 * a.B; i += 64) granule_wait_announced(a.cf.gran + i, want, a.err);
         for (int64_t i = t; i < a.B; i += 64) {
-          ls += __uint_as_float((unsigned)(__hip_atomic_load(a.cf.gran + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 0xffffffffull));
-          ln += __uint_as_float((unsigned)(__hip_atomic_load(a.cf.gran + a.B + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 0xffffffffull));
-          lm = fmaxf(lm, __uint_as_float((unsigned)(__hip_atomic_load(a.cf.gran + 2 * a.B + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 0xffffffffull)));
+          ls += granule_value(granule_load(a.cf.gran + i));
+          ln += granule_value(granule_load(a.cf.gran + a.B + i));
+          lm = fmaxf(lm, granule_value(granule_load(a.cf.gran + 2 * a.B + i)));
         }
         const float mean = wave_sum_fast(ls) / (float)(a.B * c);
         const float anynan = wave_sum_fast(ln);

@@ -1,6 +1,7 @@
-// lo_group_reduce.h -- building blocks of the operator-resident kernels that own FOUR rows per thread (256-thread
-// workgroups, groups of GW workgroups per batch member): the wave reduce-scatter and the group all-reduce through
-// tagged 8-byte granules (see lo_cg_onchip.hip / lo_cg_onchip4.hip for the design notes).
+// lo_group_reduce.h -- what the operator-resident kernels share at their edges ("The resident hand-off in
+// one place"): the mapping of a launch onto groups of GW workgroups behind one XCD's L2, the placement check, the tagged
+// 8-byte granule and its scoped store, and the rule by which a granule poll gives up.  Below that: the wave
+// reduce-scatter and the group all-reduces of the kernels that own R4_NR rows per thread (256-thread workgroups).
 #pragma once
 #include "lo_device.h"
 
@@ -12,7 +13,104 @@ constexpr int R4_WAVES = R4_TPB / 64;    // 4
 constexpr int R4_ROWS = R4_TPB * R4_NR;  // rows per workgroup
 constexpr int R4_MAXGW = 32;  // (the root-form CG kernel also takes groups of 64: lane-parallel all-reduce below)
 constexpr int R4_SLOT = 40;
-constexpr unsigned R4_MAXSPIN = 1u << 20;  // ~0.5 s of polling: co-residency was lost (never seen on a dedicated GPU)
+constexpr unsigned kHandoffMaxSpin = 1u << 20;  // ~0.5 s of polling: co-residency was lost (never seen on a dedicated GPU)
+
+// ---- group placement: workgroup wg runs on XCD wg % 8, so a group takes GW workgroups of the SAME residue (speed only:
+// the placement check below decides whether the group may rely on it).  Workgroups beyond the last whole group of
+// their XCD are surplus (active == false) and return at once.
+struct GroupPlace {
+  int grp, wig, ngroups;  // group of this workgroup, its index inside the group, groups of the launch
+  bool active;
+};
+__device__ __forceinline__ GroupPlace group_place(const int gw, const int per_xcd) {
+  const int wg = blockIdx.x;
+  const int xcd = wg % 8, jx = wg / 8;
+  const int groups_per_xcd = per_xcd / gw;
+  GroupPlace p;
+  p.grp = xcd * groups_per_xcd + jx / gw;
+  p.wig = jx % gw;
+  p.ngroups = groups_per_xcd * 8;
+  p.active = jx / gw < groups_per_xcd;
+  return p;
+}
+__device__ __forceinline__ GroupPlace group_place(const int gw) { return group_place(gw, (int)(gridDim.x / 8)); }
+
+// ---- placement check: the sum and the sum of squares of the group's XCC ids agree with gw * id and gw * id^2 only if
+// all ids are equal; plain (workgroup-scope) stores hand off through the shared L2 only then, and only if the host allows
+__device__ __forceinline__ unsigned xcc_id() {
+  return __builtin_amdgcn_s_getreg((4 - 1) << 11 | 20) & 0xf;  // HW_REG_XCC_ID[3:0]
+}
+template <class T>
+__device__ __forceinline__ bool same_xcd_verdict(T sum_id, T sum_id2, int gw, unsigned xcc, int allow_l2_handoff) {
+  const T fx = (T)xcc;
+  return (sum_id == gw * fx) && (sum_id2 == gw * fx * fx) && (allow_l2_handoff != 0);
+}
+// (kernels whose first exchange gathers raw words instead of summing: id_of(w) = the id workgroup w published)
+template <int GW, class Ids>
+__device__ __forceinline__ bool same_xcd_gathered(Ids id_of, int allow_l2_handoff) {
+  bool same = true;
+#pragma unroll
+  for (int w = 1; w < GW; ++w) same = same && (id_of(w) == id_of(0));
+  return same && (allow_l2_handoff != 0);
+}
+
+// ---- granule: {tag | 32 payload bits} in one never-torn 8-byte word.  A double travels as two granules (low word, high
+// word) with the same tag.  Stores are relaxed; polls always load at agent scope.
+__device__ __forceinline__ unsigned long long granule_pack_bits(unsigned tag, unsigned bits) {
+  return ((unsigned long long)tag << 32) | (unsigned long long)bits;
+}
+__device__ __forceinline__ unsigned long long granule_pack(unsigned tag, float v) {
+  return granule_pack_bits(tag, __float_as_uint(v));
+}
+__device__ __forceinline__ unsigned granule_tag(unsigned long long x) { return (unsigned)(x >> 32); }
+__device__ __forceinline__ unsigned granule_bits(unsigned long long x) { return (unsigned)(x & 0xffffffffull); }
+__device__ __forceinline__ float granule_value(unsigned long long x) { return __uint_as_float(granule_bits(x)); }
+__device__ __forceinline__ void granule_store(unsigned long long* dst, unsigned long long x, bool same_xcd) {
+  if (same_xcd) __hip_atomic_store(dst, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  else __hip_atomic_store(dst, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ unsigned long long granule_load(const unsigned long long* src) {
+  return __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// ---- give-up rule of a granule poll, called after every miss: true when this poll has missed kHandoffMaxSpin times, or
+// when (looked at every 1024th miss) somebody else has already given up.  `lost_elsewhere` reads the error word.
+template <class Lost>
+__device__ __forceinline__ bool poll_missed(unsigned& spin, Lost lost_elsewhere) {
+  return ++spin > kHandoffMaxSpin || ((spin & 1023u) == 0 && lost_elsewhere());
+}
+// the common form: the error word is 0 / 1 and is set right here.  Use: if (poll_give_up(spin, err)) break; s_sleep(1);
+__device__ __forceinline__ bool poll_give_up(unsigned& spin, int* err) {
+  if (poll_missed(spin, [&] { return __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0; })) {
+    atomicExch(err, 1);  // timed out, or another workgroup already did: give up at once
+    return true;
+  }
+  return false;
+}
+// one granule, polled until it carries `tag` (given up: the stale granule comes back)
+__device__ __forceinline__ unsigned long long granule_wait(const unsigned long long* src, unsigned tag, int* err) {
+  unsigned long long x;
+  unsigned spin = 0;
+  for (;;) {
+    x = granule_load(src);
+    if (granule_tag(x) == tag) break;
+    if (poll_give_up(spin, err)) break;
+    __builtin_amdgcn_s_sleep(1);
+  }
+  return x;
+}
+// DEVIATES from the rule above (kept as it was): the wait of a launch's closing step for a granule whose arrival a
+// counter has already announced neither sleeps nor looks at the error word, and it sets the word after the loop.
+__device__ __forceinline__ unsigned long long granule_wait_announced(const unsigned long long* src, unsigned want,
+                                                                      int* err) {
+  unsigned long long gq;
+  unsigned spin = 0;
+  do {  // (the counter said every member was issued; its granule may still be on its way)
+    gq = granule_load(src);
+  } while (granule_tag(gq) != want && ++spin < kHandoffMaxSpin);
+  if (granule_tag(gq) != want) atomicExch(err, 1);
+  return gq;
+}
 
 struct alignas(16) R4Shared {
   float red[R4_WAVES][R4_SLOT];
@@ -65,9 +163,7 @@ struct PfSlots {
 };
 
 __device__ __forceinline__ void pf_store(const R4Group& g, unsigned tag, unsigned long long* dst, float v) {
-  const unsigned long long mine = ((unsigned long long)tag << 32) | (unsigned long long)__float_as_uint(v);
-  if (g.same_xcd) __hip_atomic_store(dst, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  else __hip_atomic_store(dst, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  granule_store(dst, granule_pack(tag, v), g.same_xcd);
 }
 
 // every lane of the wave takes part; lanes with active == false only vote
@@ -77,18 +173,14 @@ __device__ __forceinline__ float pf_wait(const R4Group& g, unsigned tag, const u
   for (;;) {
     bool ok = true;
     if (active) {
-      x = __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      ok = (unsigned)(x >> 32) == tag;
+      x = granule_load(src);
+      ok = granule_tag(x) == tag;
     }
     if (__all(ok)) break;
-    if (++spin > R4_MAXSPIN ||
-        ((spin & 1023u) == 0 && __hip_atomic_load(g.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
-      atomicExch(g.err, 1);  // timed out, or another workgroup already did: give up at once
-      break;
-    }
+    if (poll_give_up(spin, g.err)) break;
     __builtin_amdgcn_s_sleep(1);
   }
-  return active ? __uint_as_float((unsigned)(x & 0xffffffffull)) : 0.f;
+  return active ? granule_value(x) : 0.f;
 }
 
 template <int GW>
@@ -146,11 +238,7 @@ __device__ __forceinline__ void r4_group_sum_t(R4Shared& sh, int cnt, R4Group& g
 #pragma unroll
     for (int w = 0; w < R4_WAVES; ++w) s += sh.red[w][t];
     unsigned long long* slot = g.gslot + (size_t)(tag & 1u) * GW * R4_SLOT;
-    const unsigned long long mine = ((unsigned long long)tag << 32) | (unsigned long long)__float_as_uint(s);
-    if (g.same_xcd)
-      __hip_atomic_store(slot + (size_t)g.wig * R4_SLOT + t, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    else
-      __hip_atomic_store(slot + (size_t)g.wig * R4_SLOT + t, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    pf_store(g, tag, slot + (size_t)g.wig * R4_SLOT + t, s);
     if (stamp) c2 = wall_clock64();
     float tot = 0.f;
     unsigned spin = 0;
@@ -162,17 +250,12 @@ __device__ __forceinline__ void r4_group_sum_t(R4Shared& sh, int cnt, R4Group& g
         bool ok = true;
 #pragma unroll
         for (int w = 0; w < GW; ++w) {
-          const unsigned long long x =
-              __hip_atomic_load(slot + (size_t)w * R4_SLOT + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          ok = ok && ((unsigned)(x >> 32) == tag);
-          vals[w] = __uint_as_float((unsigned)(x & 0xffffffffull));
+          const unsigned long long x = granule_load(slot + (size_t)w * R4_SLOT + t);
+          ok = ok && (granule_tag(x) == tag);
+          vals[w] = granule_value(x);
         }
         if (ok) break;
-        if (++spin > R4_MAXSPIN ||
-            ((spin & 1023u) == 0 && __hip_atomic_load(g.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
-          atomicExch(g.err, 1);  // timed out, or another workgroup already did: give up at once
-          break;
-        }
+        if (poll_give_up(spin, g.err)) break;
         __builtin_amdgcn_s_sleep(1);
       }
 #pragma unroll
@@ -190,11 +273,7 @@ __device__ __forceinline__ void r4_group_sum_t(R4Shared& sh, int cnt, R4Group& g
           bad |= __hip_atomic_load(words + 2 * ((size_t)w * R4_SLOT + t) + 1, __ATOMIC_RELAXED,
                                    __HIP_MEMORY_SCOPE_AGENT) ^ tag;
         if (bad == 0) break;
-        if (++spin > R4_MAXSPIN ||
-            ((spin & 1023u) == 0 && __hip_atomic_load(g.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
-          atomicExch(g.err, 1);
-          break;
-        }
+        if (poll_give_up(spin, g.err)) break;
         __builtin_amdgcn_s_sleep(1);
       }
 #pragma unroll
@@ -222,6 +301,28 @@ __device__ __forceinline__ void r4_group_sum_t(R4Shared& sh, int cnt, R4Group& g
 template <int GW>
 __device__ __forceinline__ void r4_group_sum(R4Shared& sh, int cnt, R4Group& g) {
   r4_group_sum_t<GW>(sh, cnt, g, (int)threadIdx.x);
+}
+
+// The placement check as an exchange of its own (agent-scope path: g.same_xcd is false on entry): seeds sh.red with the
+// XCC id and its square, sums them over the group and sets g.same_xcd.  OWNERS: through pf_publish / pf_collect (the
+// kernels whose granule layout is [2][GW + 1][R4_SLOT] at every GW).  Ends with a barrier (sh.res is free again).
+template <int GW, bool OWNERS = false>
+__device__ __forceinline__ void r4_placement_check(R4Shared& sh, R4Group& g, int allow_l2_handoff) {
+  const int t = threadIdx.x;
+  const unsigned xcc = xcc_id();
+  if (t < 64) {
+    sh.red[0][0] = (float)xcc;
+    sh.red[0][1] = (float)(xcc * xcc);
+  }
+  if (t < 2 * (R4_WAVES - 1)) sh.red[1 + t / 2][t % 2] = 0.f;
+  if constexpr (OWNERS) {
+    const PfSlots ps = pf_publish<GW>(sh, 2, g);
+    pf_collect<GW>(sh, 2, g, ps);
+  } else {
+    r4_group_sum<GW>(sh, 2, g);
+  }
+  g.same_xcd = same_xcd_verdict(sh.res[0], sh.res[1], GW, xcc, allow_l2_handoff);
+  __syncthreads();
 }
 
 // all-reduce of n generated components + ns scalars over the whole group -> sh.res[0 .. n + ns)

@@ -137,14 +137,10 @@ __global__ __launch_bounds__(MV_TPB, WPS) void k_lr_mv(LrMvArgs a) {
   // (the sticky stop word of a CG solve and the launch's error word are REQUESTED here and looked at behind the first
   //  member's loads: two dependent round trips less in front of the first byte from HBM)
   const int stop0 = a.stop ? *a.stop : 0;
-  const int wg = blockIdx.x;
-  const int xcd = wg % 8, jx = wg / 8;  // (workgroups go round-robin to the XCDs: checked below, not assumed)
-  const int per_xcd = (int)gridDim.x / 8;
-  const int groups_per_xcd = per_xcd / GW;
-  const int gix = jx / GW, wig = jx % GW;
-  if (gix >= groups_per_xcd) return;
-  const int grp = xcd * groups_per_xcd + gix;
-  const int ngroups = groups_per_xcd * 8;
+  const int jx = blockIdx.x / 8, per_xcd = (int)gridDim.x / 8;  // (both again for the CU slot below)
+  const GroupPlace gp = group_place(GW, per_xcd);  // (workgroups go round-robin to the XCDs: checked below, not assumed)
+  if (!gp.active) return;
+  const int grp = gp.grp, wig = gp.wig, ngroups = gp.ngroups;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int k = lane & (CH - 1), g = lane / CH;
   unsigned long long* const gbase = a.gran + (size_t)grp * 2 * GW * NPS;
@@ -171,9 +167,7 @@ __global__ __launch_bounds__(MV_TPB, WPS) void k_lr_mv(LrMvArgs a) {
       unsigned long long* slot = gbase + (size_t)(tag & 1u) * GW * NPS;
       if (t < cnt) {
         const float s = (red[0][t] + red[1][t]) + (red[2][t] + red[3][t]);
-        const unsigned long long mine = ((unsigned long long)tag << 32) | (unsigned long long)__float_as_uint(s);
-        if (same_xcd) __hip_atomic_store(slot + (size_t)wig * NPS + t, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        else __hip_atomic_store(slot + (size_t)wig * NPS + t, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        granule_store(slot + (size_t)wig * NPS + t, granule_pack(tag, s), same_xcd);
       }
       unsigned spin = 0;
       bool lost = false;
@@ -182,10 +176,13 @@ __global__ __launch_bounds__(MV_TPB, WPS) void k_lr_mv(LrMvArgs a) {
         const int w = idx / cnt, e = idx - w * cnt;
         unsigned long long x;
         for (;;) {
-          x = __hip_atomic_load(slot + (size_t)w * NPS + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          if ((unsigned)(x >> 32) == tag) break;
-          if (++spin > R4_MAXSPIN ||
-              ((spin & 1023u) == 0 && __hip_atomic_load(a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == a.tag_base)) {
+          x = granule_load(slot + (size_t)w * NPS + e);
+          if (granule_tag(x) == tag) break;
+          // DEVIATES from poll_give_up: the error word of this kernel carries the launch's tag_base (it is never cleared
+          // between launches), and the first workgroup to give up also tells the host through err_host
+          if (poll_missed(spin, [&] {
+                return __hip_atomic_load(a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == a.tag_base;
+              })) {
             if (atomicExch(a.err, a.tag_base) != a.tag_base)
               __hip_atomic_store(a.err_host, a.tag_base, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             lost = true;
@@ -193,7 +190,7 @@ __global__ __launch_bounds__(MV_TPB, WPS) void k_lr_mv(LrMvArgs a) {
           }
           __builtin_amdgcn_s_sleep(1);
         }
-        pol[idx] = __uint_as_float((unsigned)(x & 0xffffffffull));
+        pol[idx] = granule_value(x);
       }
       if (lost) lost_s = 1;
       __syncthreads();
@@ -209,7 +206,7 @@ __global__ __launch_bounds__(MV_TPB, WPS) void k_lr_mv(LrMvArgs a) {
   };
   // placement check (see k_cg_onchip4): the group's FIRST exchange goes through agent-scope stores and carries the XCC id;
   // plain same-XCD stores (hand-off at L2 latency) only from the second member on, and only if the whole group shares an XCD
-  const unsigned xcc = __builtin_amdgcn_s_getreg((4 - 1) << 11 | 20) & 0xf;  // HW_REG_XCC_ID[3:0]
+  const unsigned xcc = xcc_id();
   bool first = true, lost = false;
   if (a.dbg && wig == 0 && t == 0) a.dbg[8 + 2 * grp] = wall_clock64();  // (LO_MV_DEBUG: when each group starts / ends)
 
@@ -336,8 +333,7 @@ __global__ __launch_bounds__(MV_TPB, WPS) void k_lr_mv(LrMvArgs a) {
       if (GW > 1 && first) {
         if (t < 8) red[t >> 1][NP + (t & 1)] = t == 0 ? (float)xcc : (t == 1 ? (float)(xcc * xcc) : 0.f);
         have_t = group_sum(NPS);
-        const float fx = (float)xcc;
-        same_xcd = have_t && (res[NP] == GW * fx) && (res[NP + 1] == GW * fx * fx) && (a.allow_l2_handoff != 0);
+        same_xcd = have_t && same_xcd_verdict(res[NP], res[NP + 1], GW, xcc, a.allow_l2_handoff);
         first = false;
       } else {
         have_t = group_sum(NP);

@@ -37,6 +37,7 @@
 
 #include "lo_device.h"
 #include "lo_internal.h"
+#include "lo_group_reduce.h"
 
 namespace lo {
 
@@ -46,7 +47,6 @@ constexpr int PO_SLOT = 72;   // granules per workgroup and parity (header + 32 
 constexpr int PO_MAXR = 16;   // up to here: 4 slots of 16 bytes per row (64 KB of L rows, two workgroups per CU)
 constexpr int P4_MAXR = 32;   // above 16: 8 slots of 16 bytes per row (128 KB, one workgroup per CU)
 constexpr int PO_HDR = 4;     // value, position, (k_pc_onchip4, in LDS only: the candidate's row inside its workgroup), error partial
-constexpr unsigned PO_MAXSPIN = 1u << 20;  // ~0.5 s of polling: co-residency was lost (never seen on a dedicated GPU)
 constexpr int PO_INVALID = 0x7fffffff;
 
 struct PoArgs {
@@ -228,11 +228,7 @@ __device__ __forceinline__ void p4_gather(P4Shared<GW>& sh, const float4* l_s, i
     } else {
       myval = sh.part[t];
     }
-    const unsigned long long mine = ((unsigned long long)tag << 32) | (unsigned long long)myval;
-    if (same_xcd)
-      __hip_atomic_store(slot + (size_t)wig * PO_SLOT + t, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    else
-      __hip_atomic_store(slot + (size_t)wig * PO_SLOT + t, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    granule_store(slot + (size_t)wig * PO_SLOT + t, granule_pack_bits(tag, myval), same_xcd);
     unsigned spin = 0;
     if constexpr (GW <= 16) {
       unsigned vals[GW];
@@ -240,17 +236,11 @@ __device__ __forceinline__ void p4_gather(P4Shared<GW>& sh, const float4* l_s, i
         bool ok = true;
 #pragma unroll
         for (int w = 0; w < GW; ++w) {
-          const unsigned long long x =
-              __hip_atomic_load(slot + (size_t)w * PO_SLOT + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          ok = ok && ((unsigned)(x >> 32) == tag);
-          vals[w] = (unsigned)(x & 0xffffffffull);
+          const unsigned long long x = granule_load(slot + (size_t)w * PO_SLOT + t);
+          ok = ok && (granule_tag(x) == tag);
+          vals[w] = granule_bits(x);
         }
-        if (ok) break;
-        if (++spin > PO_MAXSPIN ||
-            ((spin & 1023u) == 0 && __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
-          atomicExch(err, 1);  // timed out, or another workgroup already did: give up at once
-          break;
-        }
+        if (ok || poll_give_up(spin, err)) break;
         __builtin_amdgcn_s_sleep(1);
       }
 #pragma unroll
@@ -265,12 +255,7 @@ __device__ __forceinline__ void p4_gather(P4Shared<GW>& sh, const float4* l_s, i
         for (int w = 0; w < GW; ++w)
           bad |= __hip_atomic_load(words + 2 * ((size_t)w * PO_SLOT + t) + 1, __ATOMIC_RELAXED,
                                    __HIP_MEMORY_SCOPE_AGENT) ^ tag;
-        if (bad == 0) break;
-        if (++spin > PO_MAXSPIN ||
-            ((spin & 1023u) == 0 && __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
-          atomicExch(err, 1);
-          break;
-        }
+        if (bad == 0 || poll_give_up(spin, err)) break;
         __builtin_amdgcn_s_sleep(1);
       }
 #pragma unroll
@@ -327,25 +312,18 @@ __global__ __launch_bounds__(P4_TPB, 2) void k_pc_onchip4(PoArgs a) {
   __shared__ float4 l_static[LQ == 4 ? P4_ROWS * 4 : 1];
   extern __shared__ float4 l_dynamic[];
   float4* const l_s = (LQ == 4) ? l_static : l_dynamic;
-  const int wg = blockIdx.x;
-  const int xcd = wg % 8, jx = wg / 8;
-  const int groups_per_xcd = (gridDim.x / 8) / GW;
-  const int grp = xcd * groups_per_xcd + jx / GW;
-  const int wig = jx % GW;
-  const int ngroups = groups_per_xcd * 8;
-  if (jx / GW >= groups_per_xcd) return;
+  const GroupPlace gp = group_place(GW);
+  if (!gp.active) return;  // (surplus workgroup)
+  const int grp = gp.grp, wig = gp.wig, ngroups = gp.ngroups;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   unsigned long long* gslot = a.gbuf + (size_t)grp * 2 * GW * PO_SLOT;
   unsigned tag = 0;
   bool same_xcd = false;
   {
-    const unsigned xcc = __builtin_amdgcn_s_getreg((4 - 1) << 11 | 20) & 0xf;  // HW_REG_XCC_ID[3:0]
-    if (t == 0) sh.part[0] = xcc;
+    // placement check: this kernel's exchange is a gather of raw words, so the XCC ids themselves are compared
+    if (t == 0) sh.part[0] = xcc_id();
     p4_gather<GW, NS, RC, false>(sh, l_s, 1, gslot, wig, ++tag, a.err, false);
-    bool same = true;
-#pragma unroll
-    for (int w = 1; w < GW; ++w) same = same && (sh.gath[w][0] == sh.gath[0][0]);
-    same_xcd = same && (a.allow_l2_handoff != 0);
+    same_xcd = same_xcd_gathered<GW>([&](int w) { return sh.gath[w][0]; }, a.allow_l2_handoff);
     __syncthreads();
   }
   const int row0 = wig * a.RW;
@@ -719,19 +697,7 @@ struct alignas(16) PrShared {
 // threads, one load each.  Phase 2, after the winner is known: threads 0 .. m-1 fetch the WINNER's L entries only (the
 // loads of the winner's row of the operator are issued first: their latency hides behind this poll).
 __device__ __forceinline__ unsigned pr_poll(const unsigned long long* src, unsigned tag, int* err) {
-  unsigned long long g = 0;
-  unsigned spin = 0;
-  for (;;) {
-    g = __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if ((unsigned)(g >> 32) == tag) break;
-    if (++spin > PO_MAXSPIN ||
-        ((spin & 1023u) == 0 && __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
-      atomicExch(err, 1);  // timed out, or another workgroup already did: give up at once
-      break;
-    }
-    __builtin_amdgcn_s_sleep(1);
-  }
-  return (unsigned)(g & 0xffffffffull);
+  return granule_bits(granule_wait(src, tag, err));
 }
 
 template <int GW>
@@ -743,8 +709,7 @@ __device__ __forceinline__ void pr_headers(PrShared<GW>& sh, int cnt, unsigned l
     if (t < cnt) sh.gath[0][t] = sh.part[t];
   } else {
     if (t < cnt)
-      __hip_atomic_store(slot + (size_t)wig * PR_SLOT + t, ((unsigned long long)tag << 32) | (unsigned long long)sh.part[t],
-                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      granule_store(slot + (size_t)wig * PR_SLOT + t, granule_pack_bits(tag, sh.part[t]), /*same_xcd=*/false);
     if (t < 4 * GW) {
       const int w = t >> 2, fld = t & 3;
       sh.gath[w][fld] = pr_poll(slot + (size_t)w * PR_SLOT + fld, tag, err);
@@ -769,13 +734,9 @@ __global__ __launch_bounds__(P4_TPB, 2) void k_pc_onchip_rows(PrArgs a) {
   __shared__ float4 l_static[LQ == 4 ? P4_ROWS * 4 : 1];
   extern __shared__ float4 l_dynamic[];
   float4* const l_s = (LQ == 4) ? l_static : l_dynamic;
-  const int wg = blockIdx.x;
-  const int xcd = wg % 8, jx = wg / 8;
-  const int groups_per_xcd = (gridDim.x / 8) / GW;
-  const int grp = xcd * groups_per_xcd + jx / GW;
-  const int wig = jx % GW;
-  const int ngroups = groups_per_xcd * 8;
-  if (jx / GW >= groups_per_xcd) return;
+  const GroupPlace gp = group_place(GW);
+  if (!gp.active) return;  // (surplus workgroup)
+  const int grp = gp.grp, wig = gp.wig, ngroups = gp.ngroups;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   unsigned long long* gslot = a.gbuf + (size_t)grp * 2 * GW * PR_SLOT;
   unsigned tag = 0;

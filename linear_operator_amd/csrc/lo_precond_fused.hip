@@ -88,13 +88,9 @@ __global__ __launch_bounds__(R4_TPB, OCC) void k_precond_fused(PfArgs a) {
   if (a.stop && *a.stop) return;
   __shared__ R4Shared sh;
   __shared__ float alpha_s, rzo_s;
-  const int wg = blockIdx.x;
-  const int xcd = wg % 8, jx = wg / 8;
-  const int groups_per_xcd = (gridDim.x / 8) / GW;
-  const int grp = xcd * groups_per_xcd + jx / GW;
-  const int wig = jx % GW;
-  const int ngroups = groups_per_xcd * 8;
-  if (jx / GW >= groups_per_xcd) return;
+  const GroupPlace gp = group_place(GW);
+  if (!gp.active) return;  // (surplus workgroup)
+  const int grp = gp.grp, wig = gp.wig, ngroups = gp.ngroups;
   const int t = threadIdx.x;
   R4Group g;
   g.gslot = a.gbuf + (size_t)grp * 2 * (GW + 1) * R4_SLOT;
@@ -110,19 +106,7 @@ __global__ __launch_bounds__(R4_TPB, OCC) void k_precond_fused(PfArgs a) {
   g.tag = a.tag_base;
   g.err = a.err;
   g.same_xcd = false;
-  {
-    const unsigned xcc = __builtin_amdgcn_s_getreg((4 - 1) << 11 | 20) & 0xf;  // HW_REG_XCC_ID[3:0]
-    if (t < 64) {
-      sh.red[0][0] = (float)xcc;
-      sh.red[0][1] = (float)(xcc * xcc);
-    }
-    if (t < 2 * (R4_WAVES - 1)) sh.red[1 + t / 2][t % 2] = 0.f;
-    const PfSlots ps = pf_publish<GW>(sh, 2, g);
-    pf_collect<GW>(sh, 2, g, ps);
-    const float fx = (float)xcc;
-    g.same_xcd = (sh.res[0] == GW * fx) && (sh.res[1] == GW * fx * fx) && (a.allow_l2_handoff != 0);
-    __syncthreads();
-  }
+  r4_placement_check<GW, true>(sh, g, a.allow_l2_handoff);
   const int row0 = wig * a.RW;
   const int nv = max(0, min(a.RW, a.N - row0));
   // Ownership of Q: thread t holds the 16-byte piece (row = 64 i + (t >> 2), columns 4 (t & 3) .. + 3) for i = 0 .. 15:
@@ -242,8 +226,7 @@ __global__ __launch_bounds__(R4_TPB, OCC) void k_precond_fused(PfArgs a) {
       // No fence (a device-scope release writes the XCD's L2 back: +13 us per launch): the norm travels to the group
       // that closes the launch inside a tagged 8-byte granule, like the hand-offs; the plain stores above are for the
       // NEXT launch.
-      __hip_atomic_store(a.cf.gran + b, ((unsigned long long)(unsigned)(a.launch + 1) << 32) | __float_as_uint(rn),
-                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      granule_store(a.cf.gran + b, granule_pack((unsigned)(a.launch + 1), rn), /*same_xcd=*/false);
       cf_old = atomicAdd(a.cf.done, 1);
     }
     float zv[NV];
@@ -274,13 +257,7 @@ __global__ __launch_bounds__(R4_TPB, OCC) void k_precond_fused(PfArgs a) {
         float ls = 0.f;
         const unsigned want = (unsigned)(a.launch + 1);
         for (int64_t i = t; i < a.B; i += 64) {
-          unsigned long long gq;
-          unsigned spin = 0;
-          do {  // (the counter said every member was issued; its granule may still be on its way)
-            gq = __hip_atomic_load(a.cf.gran + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          } while ((unsigned)(gq >> 32) != want && ++spin < R4_MAXSPIN);
-          if ((unsigned)(gq >> 32) != want) atomicExch(a.err, 1);
-          ls += __uint_as_float((unsigned)(gq & 0xffffffffull));
+          ls += granule_value(granule_wait_announced(a.cf.gran + i, want, a.err));
         }
         const float mean = wave_sum_fast(ls) / (float)a.B;
         if (t == 0) {
@@ -316,13 +293,9 @@ __global__ __launch_bounds__(R4_TPB, OCC) void k_precond_fused_kron(PfArgs a) {
   __shared__ R4Shared sh;
   __shared__ float alpha_s, rzo_s;
   __shared__ __attribute__((aligned(16))) float kf_s[256];
-  const int wg = blockIdx.x;
-  const int xcd = wg % 8, jx = wg / 8;
-  const int groups_per_xcd = (gridDim.x / 8) / GW;
-  const int grp = xcd * groups_per_xcd + jx / GW;
-  const int wig = jx % GW;
-  const int ngroups = groups_per_xcd * 8;
-  if (jx / GW >= groups_per_xcd) return;
+  const GroupPlace gp = group_place(GW);
+  if (!gp.active) return;  // (surplus workgroup)
+  const int grp = gp.grp, wig = gp.wig, ngroups = gp.ngroups;
   const int t = threadIdx.x;
   R4Group g;
   g.gslot = a.gbuf + (size_t)grp * 2 * (GW + 1) * R4_SLOT;
@@ -338,19 +311,7 @@ __global__ __launch_bounds__(R4_TPB, OCC) void k_precond_fused_kron(PfArgs a) {
   g.tag = a.tag_base;
   g.err = a.err;
   g.same_xcd = false;
-  {
-    const unsigned xcc = __builtin_amdgcn_s_getreg((4 - 1) << 11 | 20) & 0xf;  // HW_REG_XCC_ID[3:0]
-    if (t < 64) {
-      sh.red[0][0] = (float)xcc;
-      sh.red[0][1] = (float)(xcc * xcc);
-    }
-    if (t < 2 * (R4_WAVES - 1)) sh.red[1 + t / 2][t % 2] = 0.f;
-    const PfSlots ps = pf_publish<GW>(sh, 2, g);
-    pf_collect<GW>(sh, 2, g, ps);
-    const float fx = (float)xcc;
-    g.same_xcd = (sh.res[0] == GW * fx) && (sh.res[1] == GW * fx * fx) && (a.allow_l2_handoff != 0);
-    __syncthreads();
-  }
+  r4_placement_check<GW, true>(sh, g, a.allow_l2_handoff);
   const int row0 = wig * a.RW;  // multiple of 256 (precond_fused_rupdate)
   const int nv = max(0, min(a.RW, a.N - row0));
   const int lane = t & 63, wave = t >> 6;
@@ -463,8 +424,7 @@ __global__ __launch_bounds__(R4_TPB, OCC) void k_precond_fused_kron(PfArgs a) {
       a.cf.beta[b] = beta;
       a.cf.resid_norm[b] = rn;
       a.cf.has_conv[b] = rn < a.cf.stop_after;
-      __hip_atomic_store(a.cf.gran + b, ((unsigned long long)(unsigned)(a.launch + 1) << 32) | __float_as_uint(rn),
-                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      granule_store(a.cf.gran + b, granule_pack((unsigned)(a.launch + 1), rn), /*same_xcd=*/false);
       cf_old = atomicAdd(a.cf.done, 1);
     }
 #pragma unroll
@@ -487,13 +447,7 @@ __global__ __launch_bounds__(R4_TPB, OCC) void k_precond_fused_kron(PfArgs a) {
         float ls = 0.f;
         const unsigned want = (unsigned)(a.launch + 1);
         for (int64_t i = t; i < a.B; i += 64) {
-          unsigned long long gq;
-          unsigned spin = 0;
-          do {
-            gq = __hip_atomic_load(a.cf.gran + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          } while ((unsigned)(gq >> 32) != want && ++spin < R4_MAXSPIN);
-          if ((unsigned)(gq >> 32) != want) atomicExch(a.err, 1);
-          ls += __uint_as_float((unsigned)(gq & 0xffffffffull));
+          ls += granule_value(granule_wait_announced(a.cf.gran + i, want, a.err));
         }
         const float mean = wave_sum_fast(ls) / (float)a.B;
         if (t == 0) {

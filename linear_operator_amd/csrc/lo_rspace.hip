@@ -192,13 +192,9 @@ __global__ __launch_bounds__(R4_TPB, 2 * R4_TPB / 256) void k_cg_rspace(OnchipAr
   __shared__ RsShared<RC> rs;
   __shared__ __attribute__((aligned(16))) double mat_s[4 * RC * MLD];  // E | F E | E F E | G2
   __shared__ float4 stage_s[R4_WAVES * 64 * (RC / 4)];                 // per-wave transposition window of the member load
-  const int wg = blockIdx.x;
-  const int xcd = wg % 8, jx = wg / 8;
-  const int groups_per_xcd = (gridDim.x / 8) / GW;
-  const int grp = xcd * groups_per_xcd + jx / GW;
-  const int wig = jx % GW;
-  const int ngroups = groups_per_xcd * 8;
-  if (jx / GW >= groups_per_xcd) return;
+  const GroupPlace gp = group_place(GW);
+  if (!gp.active) return;  // (surplus workgroup)
+  const int grp = gp.grp, wig = gp.wig, ngroups = gp.ngroups;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   R4Group g;
   // granules of the group: [placement check: 2 x (GW + 1) x R4_SLOT] [the members' all-reduces: 2 x GW x RS_SLOT]
@@ -209,18 +205,7 @@ __global__ __launch_bounds__(R4_TPB, 2 * R4_TPB / 256) void k_cg_rspace(OnchipAr
   g.tag = 0;
   g.err = a.err;
   g.same_xcd = false;
-  {  // placement check (see k_cg_onchip4): plain-store hand-off only when the whole group shares an XCD
-    const unsigned xcc = __builtin_amdgcn_s_getreg((4 - 1) << 11 | 20) & 0xf;  // HW_REG_XCC_ID[3:0]
-    if (t < 64) {
-      sh.red[0][0] = (float)xcc;
-      sh.red[0][1] = (float)(xcc * xcc);
-    }
-    if (t < 2 * (R4_WAVES - 1)) sh.red[1 + t / 2][t % 2] = 0.f;
-    r4_group_sum<GW>(sh, 2, g);
-    const float fx = (float)xcc;
-    g.same_xcd = (sh.res[0] == GW * fx) && (sh.res[1] == GW * fx * fx) && (a.allow_l2_handoff != 0);
-    __syncthreads();
-  }
+  r4_placement_check<GW>(sh, g, a.allow_l2_handoff);  // plain-store hand-off only when the whole group shares an XCD
   const int row0 = wig * a.RW;
   const int nv = max(0, min(a.RW, a.N - row0));
   const bool di_full = a.dinv_mode == LO_DIAG_FULL;
@@ -370,15 +355,8 @@ __global__ __launch_bounds__(R4_TPB, 2 * R4_TPB / 256) void k_cg_rspace(OnchipAr
         if constexpr (GW > 1) {
           unsigned long long* slot = rs_slot + (size_t)(tag & 1u) * GW * RS_SLOT;
           unsigned long long* mine = slot + (size_t)wig * RS_SLOT + 2 * t;
-          const unsigned long long g0 = ((unsigned long long)tag << 32) | (unsigned long long)lo_w(v);
-          const unsigned long long g1 = ((unsigned long long)tag << 32) | (unsigned long long)hi_w(v);
-          if (g.same_xcd) {
-            __hip_atomic_store(mine, g0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            __hip_atomic_store(mine + 1, g1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-          } else {
-            __hip_atomic_store(mine, g0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(mine + 1, g1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          }
+          granule_store(mine, granule_pack_bits(tag, lo_w(v)), g.same_xcd);
+          granule_store(mine + 1, granule_pack_bits(tag, hi_w(v)), g.same_xcd);
           tot = 0.0;
           unsigned spin = 0;
           constexpr int CK = (GW < 8) ? GW : 8;  // workgroups polled together (2 CK loads in flight)
@@ -390,21 +368,19 @@ __global__ __launch_bounds__(R4_TPB, 2 * R4_TPB / 256) void k_cg_rspace(OnchipAr
 #pragma unroll
               for (int w = 0; w < CK; ++w) {
                 const unsigned long long* src = slot + (size_t)(w0_ + w) * RS_SLOT + 2 * t;
-                x0[w] = __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                x1[w] = __hip_atomic_load(src + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                ok = ok && ((unsigned)(x0[w] >> 32) == tag) && ((unsigned)(x1[w] >> 32) == tag);
+                x0[w] = granule_load(src);
+                x1[w] = granule_load(src + 1);
+                ok = ok && (granule_tag(x0[w]) == tag) && (granule_tag(x1[w]) == tag);
               }
               if (ok) break;
-              if (++spin > R4_MAXSPIN ||
-                  ((spin & 1023u) == 0 && __hip_atomic_load(g.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
-                atomicExch(g.err, 1);  // timed out, or another workgroup already did: give up at once
+              if (poll_give_up(spin, g.err)) {
                 lost = true;
                 break;
               }
               __builtin_amdgcn_s_sleep(1);
             }
 #pragma unroll
-            for (int w = 0; w < CK; ++w) tot += mk_d((unsigned)(x0[w] & 0xffffffffull), (unsigned)(x1[w] & 0xffffffffull));
+            for (int w = 0; w < CK; ++w) tot += mk_d(granule_bits(x0[w]), granule_bits(x1[w]));
           }
         }
         rs.res[t] = tot;
@@ -590,9 +566,7 @@ __global__ __launch_bounds__(R4_TPB, 2 * R4_TPB / 256) void k_cg_rspace(OnchipAr
         a.resid_norm[bc] = rn;
         a.has_conv[bc] = conv ? 1 : 0;
         if (a.close_gran) {
-          const unsigned long long gr =
-              ((unsigned long long)(a.close_epoch | close_flags) << 32) | (unsigned long long)__float_as_uint(rn);
-          __hip_atomic_store(a.close_gran + b, gr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          granule_store(a.close_gran + b, granule_pack(a.close_epoch | close_flags, rn), /*same_xcd=*/false);
         }
       }
       // y = Tin (eta - xi g0): lane i walks column i of TinT (its half of the eigen-indices; consecutive lanes read
@@ -770,9 +744,7 @@ __global__ __launch_bounds__(R4_TPB, 2 * R4_TPB / 256) void k_cg_rspace(OnchipAr
         a.resid_norm[bc] = rn;
         a.has_conv[bc] = conv ? 1 : 0;
         if (a.close_gran) {  // this member's line of the closing step: one never-torn 8-byte store
-          const unsigned long long gr =
-              ((unsigned long long)(a.close_epoch | close_flags) << 32) | (unsigned long long)__float_as_uint(rn);
-          __hip_atomic_store(a.close_gran + b, gr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          granule_store(a.close_gran + b, granule_pack(a.close_epoch | close_flags, rn), /*same_xcd=*/false);
         }
       }
     }

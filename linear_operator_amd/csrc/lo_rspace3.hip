@@ -114,19 +114,15 @@ __global__ __launch_bounds__(R3_TPB, 2) void k_cg_rspace3(OnchipArgs a, PeerOut 
   __shared__ __attribute__((aligned(16))) double res[NP];
   __shared__ __attribute__((aligned(16))) double gv[4][32];
   __shared__ unsigned polw[GW > 1 ? NG : 2];
-  const int wg = blockIdx.x;
-  const int xcd = wg % 8, jx = wg / 8;
-  const int groups_per_xcd = ((int)gridDim.x / 8) / GW;
-  const int grp = xcd * groups_per_xcd + jx / GW;
-  const int wig = jx % GW;
-  const int ngroups = groups_per_xcd * 8;
-  if (jx / GW >= groups_per_xcd) return;
+  const GroupPlace gp = group_place(GW, (int)gridDim.x / 8);
+  if (!gp.active) return;  // (surplus workgroup)
+  const int grp = gp.grp, wig = gp.wig, ngroups = gp.ngroups;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int wave_u = __builtin_amdgcn_readfirstlane(wave);
   unsigned long long* const gbase = a.gbuf + (size_t)grp * 2 * NG;  // [parity][GW][NP][2]
   unsigned tag = a.tag_base;  // (0 over a cleared buffer; above every earlier launch's tags in the library's own block)
   bool same_xcd = false;
-  const unsigned xcc = __builtin_amdgcn_s_getreg((4 - 1) << 11 | 20) & 0xf;  // HW_REG_XCC_ID[3:0]
+  const unsigned xcc = xcc_id();
   bool first = true;
   // rows: a wave owns [row0, row0 + 256); it loads from row0c = min(row0, N - 256) on (no per-row clamp: lo_lowrank_mv.hip),
   // rows below row0 belong to the previous wave and enter with b = 0 and 1/d = 0, as do rows >= N
@@ -299,15 +295,8 @@ __global__ __launch_bounds__(R3_TPB, 2) void k_cg_rspace3(OnchipArgs a, PeerOut 
         if (tt < NP) {
           const double v = (red[0][tt] + red[1][tt]) + (red[2][tt] + red[3][tt]);
           unsigned long long* mine = slot + ((size_t)wig * NP + tt) * 2;
-          const unsigned long long g0 = ((unsigned long long)tag << 32) | (unsigned long long)lo_w(v);
-          const unsigned long long g1 = ((unsigned long long)tag << 32) | (unsigned long long)hi_w(v);
-          if (same_xcd) {
-            __hip_atomic_store(mine, g0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            __hip_atomic_store(mine + 1, g1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-          } else {
-            __hip_atomic_store(mine, g0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(mine + 1, g1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          }
+          granule_store(mine, granule_pack_bits(tag, lo_w(v)), same_xcd);
+          granule_store(mine + 1, granule_pack_bits(tag, hi_w(v)), same_xcd);
         }
         constexpr int PER = (NG + R3_TPB - 1) / R3_TPB;  // granules per thread
         constexpr int CKQ = PER < 8 ? PER : 8;            // ... polled together
@@ -321,13 +310,11 @@ __global__ __launch_bounds__(R3_TPB, 2) void k_cg_rspace3(OnchipArgs a, PeerOut 
 #pragma unroll
             for (int q = 0; q < CKQ; ++q) {
               const int idx = tt + R3_TPB * (q0 + q);
-              x[q] = __hip_atomic_load(slot + min(idx, NG - 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-              ok = ok && ((unsigned)(x[q] >> 32) == tag);
+              x[q] = granule_load(slot + min(idx, NG - 1));
+              ok = ok && (granule_tag(x[q]) == tag);
             }
             if (ok) break;
-            if (++spin > R4_MAXSPIN ||
-                ((spin & 1023u) == 0 && __hip_atomic_load(a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
-              atomicExch(a.err, 1);  // timed out, or another workgroup already did: give up at once
+            if (poll_give_up(spin, a.err)) {
               lost = true;
               break;
             }
@@ -336,7 +323,7 @@ __global__ __launch_bounds__(R3_TPB, 2) void k_cg_rspace3(OnchipArgs a, PeerOut 
 #pragma unroll
           for (int q = 0; q < CKQ; ++q) {
             const int idx = tt + R3_TPB * (q0 + q);
-            if (idx < NG) polw[idx] = (unsigned)(x[q] & 0xffffffffull);
+            if (idx < NG) polw[idx] = granule_bits(x[q]);
           }
         }
         __syncthreads();
@@ -352,8 +339,7 @@ __global__ __launch_bounds__(R3_TPB, 2) void k_cg_rspace3(OnchipArgs a, PeerOut 
     if (GW > 1 && first) {  // placement check (see k_cg_onchip4): plain-store hand-off only when the group shares an XCD
       unsigned xc = xcc;
       asm volatile("" : "+s"(xc));
-      const double fx = (double)xc;
-      same_xcd = (res[2 * RC + 4] == GW * fx) && (res[2 * RC + 5] == GW * fx * fx) && (a.allow_l2_handoff != 0);
+      same_xcd = same_xcd_verdict(res[2 * RC + 4], res[2 * RC + 5], GW, xc, a.allow_l2_handoff);
     }
     first = false;
     if (stamp) a.dbg[2] = wall_clock64();
@@ -520,9 +506,7 @@ __global__ __launch_bounds__(R3_TPB, 2) void k_cg_rspace3(OnchipArgs a, PeerOut 
         a.resid_norm[bc] = rn;
         a.has_conv[bc] = conv ? 1 : 0;
         if (a.close_gran) {
-          const unsigned long long gr =
-              ((unsigned long long)(a.close_epoch | close_flags) << 32) | (unsigned long long)__float_as_uint(rn);
-          __hip_atomic_store(a.close_gran + b, gr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          granule_store(a.close_gran + b, granule_pack(a.close_epoch | close_flags, rn), /*same_xcd=*/false);
         }
       }
       // y = Tin (eta - xi g0): lane i walks column i of TinT (its half of the eigen-indices)

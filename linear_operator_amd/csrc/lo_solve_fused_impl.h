@@ -108,20 +108,6 @@ struct alignas(16) FuPShared {
 
 __device__ __forceinline__ int fu_l_slot(int r, int q) { return r * 4 + (q ^ ((r >> 2) & 3)); }
 
-struct FuWait {
-  int* err;
-  unsigned spin;
-  __device__ __forceinline__ bool give_up() {
-    if (++spin > R4_MAXSPIN ||
-        ((spin & 1023u) == 0 && __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
-      atomicExch(err, 1);  // timed out, or another workgroup already did: give up at once
-      return true;
-    }
-    __builtin_amdgcn_s_sleep(1);
-    return false;
-  }
-};
-
 // thread t < cnt publishes sh.part[t] and fetches component t of every workgroup of the group into sh.gath
 template <int GW>
 __device__ __forceinline__ void fu_gather(FuPShared<GW>& sh, int cnt, unsigned long long* gslot_base, int wig,
@@ -129,24 +115,20 @@ __device__ __forceinline__ void fu_gather(FuPShared<GW>& sh, int cnt, unsigned l
   __syncthreads();  // sh.part complete
   if (t < cnt) {
     unsigned long long* slot = gslot_base + (size_t)(tag & 1u) * GW * FU_SLOT;
-    const unsigned long long mine = ((unsigned long long)tag << 32) | (unsigned long long)sh.part[t];
-    if (same_xcd)
-      __hip_atomic_store(slot + (size_t)wig * FU_SLOT + t, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    else
-      __hip_atomic_store(slot + (size_t)wig * FU_SLOT + t, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    FuWait wt{err, 0};
+    granule_store(slot + (size_t)wig * FU_SLOT + t, granule_pack_bits(tag, sh.part[t]), same_xcd);
+    unsigned spin = 0;
     if constexpr (GW <= 16) {
       unsigned vals[GW];
       for (;;) {
         bool ok = true;
 #pragma unroll
         for (int w = 0; w < GW; ++w) {
-          const unsigned long long x =
-              __hip_atomic_load(slot + (size_t)w * FU_SLOT + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          ok = ok && ((unsigned)(x >> 32) == tag);
-          vals[w] = (unsigned)(x & 0xffffffffull);
+          const unsigned long long x = granule_load(slot + (size_t)w * FU_SLOT + t);
+          ok = ok && (granule_tag(x) == tag);
+          vals[w] = granule_bits(x);
         }
-        if (ok || wt.give_up()) break;
+        if (ok || poll_give_up(spin, err)) break;
+        __builtin_amdgcn_s_sleep(1);
       }
 #pragma unroll
       for (int w = 0; w < GW; ++w) sh.gath[w][t] = vals[w];
@@ -160,7 +142,8 @@ __device__ __forceinline__ void fu_gather(FuPShared<GW>& sh, int cnt, unsigned l
         for (int w = 0; w < GW; ++w)
           bad |= __hip_atomic_load(words + 2 * ((size_t)w * FU_SLOT + t) + 1, __ATOMIC_RELAXED,
                                    __HIP_MEMORY_SCOPE_AGENT) ^ tag;
-        if (bad == 0 || wt.give_up()) break;
+        if (bad == 0 || poll_give_up(spin, err)) break;
+        __builtin_amdgcn_s_sleep(1);
       }
 #pragma unroll
       for (int h = 0; h < GW; h += 16) {
@@ -245,13 +228,9 @@ __global__ __launch_bounds__(R4_TPB, 2) void k_solve_fused(FusedArgs a) {
   float* const e_s = ef_s + RC * FLD;
   constexpr bool WR = !MC;  // one column: w by recurrence, exactly as k_cg_onchip5 MODE 2 (same bits)
 
-  const int wg = blockIdx.x;
-  const int xcd = wg % 8, jx = wg / 8;  // block b runs on XCD b % 8: keep a group behind one L2 (speed only)
-  const int groups_per_xcd = (gridDim.x / 8) / GW;
-  const int grp = xcd * groups_per_xcd + jx / GW;
-  const int wig = jx % GW;
-  const int ngroups = groups_per_xcd * 8;
-  if (jx / GW >= groups_per_xcd) return;
+  const GroupPlace gp = group_place(GW);
+  if (!gp.active) return;  // (surplus workgroup)
+  const int grp = gp.grp, wig = gp.wig, ngroups = gp.ngroups;
   const int t0 = threadIdx.x;  // (phase code takes its own opaque copy: see the pivot phase)
   unsigned long long* const pslot = a.pgbuf + (size_t)grp * 2 * GW * FU_SLOT;
   unsigned long long* const eslot = a.egbuf + (size_t)grp * GW * FU_ESLOT;
@@ -264,13 +243,10 @@ __global__ __launch_bounds__(R4_TPB, 2) void k_solve_fused(FusedArgs a) {
   g.err = a.err;
   g.same_xcd = false;
   {  // placement check through the agent-scope path: plain-store hand-off only when the whole group shares an XCD
-    const unsigned xcc = __builtin_amdgcn_s_getreg((4 - 1) << 11 | 20) & 0xf;  // HW_REG_XCC_ID[3:0]
-    if (t0 == 0) shp.part[0] = xcc;
+     // (this kernel's first exchange is the pivot phase's gather of raw words: the ids themselves are compared)
+    if (t0 == 0) shp.part[0] = xcc_id();
     fu_gather<GW>(shp, 1, pslot, wig, ++ptag, a.err, false, t0);
-    bool same = true;
-#pragma unroll
-    for (int w = 1; w < GW; ++w) same = same && (shp.gath[w][0] == shp.gath[0][0]);
-    g.same_xcd = same && (a.allow_l2_handoff != 0);
+    g.same_xcd = same_xcd_gathered<GW>([&](int w) { return shp.gath[w][0]; }, a.allow_l2_handoff);
     __syncthreads();
   }
   const bool same_xcd = g.same_xcd;
@@ -437,17 +413,15 @@ __global__ __launch_bounds__(R4_TPB, 2) void k_solve_fused(FusedArgs a) {
         const double v = (red[e] + red[NE + e]) + (red[2 * NE + e] + red[3 * NE + e]);
         const bool used = (NB == 3) || ((e % 12) < 4);
         if (used) {
-          const unsigned long long mine = ((unsigned long long)tg << 32) | (unsigned long long)__float_as_uint((float)v);
-          __hip_atomic_store(eslot + (size_t)wig * FU_ESLOT + e, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          granule_store(eslot + (size_t)wig * FU_ESLOT + e, granule_pack(tg, (float)v), /*same_xcd=*/false);
         }
       }
       if (te < 2) {  // sum log d of the workgroup as a (hi, lo) pair of floats
         const double ls = (red[4 * NE] + red[4 * NE + 1]) + (red[4 * NE + 2] + red[4 * NE + 3]);
         const float hi = (float)ls;
         const float lo = (float)(ls - (double)hi);
-        const unsigned long long mine =
-            ((unsigned long long)tg << 32) | (unsigned long long)__float_as_uint(te == 0 ? hi : lo);
-        __hip_atomic_store(eslot + (size_t)wig * FU_ESLOT + NE + te, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        granule_store(eslot + (size_t)wig * FU_ESLOT + NE + te, granule_pack(tg, te == 0 ? hi : lo),
+                      /*same_xcd=*/false);
       }
     }
     __syncthreads();  // tile / red are dead: the L rows can be cleared
@@ -651,7 +625,7 @@ __global__ __launch_bounds__(R4_TPB, 2) void k_solve_fused(FusedArgs a) {
       }
       auto fetch_sum = [&](int e) -> double {
         double s = 0.0;
-        FuWait wt{a.err, 0};
+        unsigned spin = 0;
         for (int w0 = 0; w0 < GW; w0 += 8) {
           constexpr int W = GW < 8 ? GW : 8;
           unsigned long long x[W];
@@ -659,14 +633,14 @@ __global__ __launch_bounds__(R4_TPB, 2) void k_solve_fused(FusedArgs a) {
             bool ok = true;
 #pragma unroll
             for (int w = 0; w < W; ++w) {
-              x[w] = __hip_atomic_load(eslot + (size_t)(w0 + w) * FU_ESLOT + e, __ATOMIC_RELAXED,
-                                       __HIP_MEMORY_SCOPE_AGENT);
-              ok = ok && ((unsigned)(x[w] >> 32) == tg);
+              x[w] = granule_load(eslot + (size_t)(w0 + w) * FU_ESLOT + e);
+              ok = ok && (granule_tag(x[w]) == tg);
             }
-            if (ok || wt.give_up()) break;
+            if (ok || poll_give_up(spin, a.err)) break;
+            __builtin_amdgcn_s_sleep(1);
           }
 #pragma unroll
-          for (int w = 0; w < W; ++w) s += (double)__uint_as_float((unsigned)(x[w] & 0xffffffffull));
+          for (int w = 0; w < W; ++w) s += (double)granule_value(x[w]);
         }
         return s;
       };
