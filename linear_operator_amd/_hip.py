@@ -29,38 +29,6 @@ LO_ERR_UNSUPPORTED = -4
 LO_FUSED_OK, LO_FUSED_EARLY_STOP, LO_FUSED_CONTINUE, LO_FUSED_TIMEOUT = 0, 1, 2, 3
 _ERR = {-1: "bad argument", -2: "HIP launch/runtime failure", -3: "workspace too small", -4: "unsupported shape"}
 
-EXPORTS = [
-    "lo_abi_version", "lo_target_arch",
-    "lo_matvec_workspace_bytes", "lo_matvec_f32",
-    "lo_cg_workspace_bytes", "lo_cg_solve_f32", "lo_cg_set_onchip", "lo_cg_plan_f32", "lo_cg_last_executed",
-    "lo_resident_status_get", "lo_resident_inject_timeouts", "lo_resident_handoff_debug",
-    "lo_solve_fused_supported", "lo_solve_fused_workspace_bytes", "lo_solve_fused_f32", "lo_solve_fused_perm",
-    "lo_cg_f64_workspace_bytes", "lo_cg_solve_f64", "lo_minres_f64_workspace_bytes", "lo_minres_f64",
-    "lo_pivoted_cholesky_workspace_bytes", "lo_pivoted_cholesky_f32",
-    "lo_pivoted_cholesky_cb_workspace_bytes", "lo_pivoted_cholesky_cb_f32",
-    "lo_pivoted_cholesky_f64_workspace_bytes", "lo_pivoted_cholesky_f64",
-    "lo_pivoted_cholesky_cb_f64_workspace_bytes", "lo_pivoted_cholesky_cb_f64",
-    "lo_precond_build_workspace_bytes", "lo_precond_build_f32", "lo_precond_build_strided_f32",
-    "lo_precond_apply_workspace_bytes", "lo_precond_apply_f32",
-    "lo_precond_root_form_workspace_bytes", "lo_precond_root_form_f32",
-    "lo_precond_root_form_rs_workspace_bytes", "lo_precond_root_form_rs_f32", "lo_precond_eigform_f32",
-    "lo_precond_kron_root_workspace_bytes", "lo_precond_kron_root_f32",
-    "lo_lanczos_workspace_bytes", "lo_lanczos_tridiag_f32", "lo_lanczos_permute_f32",
-    "lo_root_from_lanczos_f32", "lo_root_from_lanczos_native_f32",
-    "lo_lanczos_f64_workspace_bytes", "lo_lanczos_tridiag_f64",
-    "lo_tridiag_eigh_slq_workspace_bytes", "lo_tridiag_eigh_slq_f32",
-    "lo_bilinear_dense_f32", "lo_bilinear_diag_f32", "lo_bilinear_root_workspace_bytes", "lo_bilinear_root_f32",
-    "lo_bilinear_kron_workspace_bytes", "lo_bilinear_kron_f32", "lo_root_apply_add_f32",
-    "lo_minres_workspace_bytes", "lo_minres_f32",
-    "lo_probe_vectors_workspace_bytes", "lo_probe_vectors_f32", "lo_iql_backward_factors_f32",
-    "lo_interp_f32", "lo_interp_t_workspace_bytes", "lo_interp_t_f32", "lo_interp_plan_bytes", "lo_interp_plan_build",
-    "lo_interp_t_planned_f32", "lo_toeplitz_workspace_bytes", "lo_toeplitz_mv_f32",
-    "lo_toeplitz_bilinear_f32", "lo_interp_values_grad_f32",
-    "lo_hadamard_bilinear_workspace_bytes", "lo_hadamard_bilinear_f32",
-    "lo_prof_enable", "lo_prof_report", "lo_hbm_triad_f32", "lo_hbm_copy_f32", "lo_hbm_stream_dev", "lo_peer_gather_set",
-]
-
-
 class HipExtensionError(RuntimeError):
     pass
 
@@ -164,6 +132,100 @@ class MinresInfo(C.Structure):
 ROWFETCH_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p)
 MATVEC_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p)
 
+# The C ABI of include/lo_amd.h, one line per entry point: name -> (restype, argtypes).  load() applies it; pointers to
+# device memory and opaque handles (workspaces, streams, callback user data) are void*.
+ci, i32, i64, f32, f64, sz, vp, P = C.c_int, C.c_int32, C.c_int64, C.c_float, C.c_double, C.c_size_t, C.c_void_p, C.POINTER
+_PROTOTYPES = {
+    "lo_abi_version": (ci, []),
+    "lo_target_arch": (C.c_char_p, []),
+    "lo_matvec_workspace_bytes": (sz, [P(OpDesc), i64]),
+    "lo_matvec_f32": (ci, [P(OpDesc), vp, vp, i64, vp, sz, vp]),
+    "lo_cg_workspace_bytes": (sz, [P(OpDesc), P(PrecondDesc), P(CgParams)]),
+    "lo_cg_solve_f32": (ci, [P(OpDesc), MATVEC_CB, vp, P(PrecondDesc), MATVEC_CB, vp, P(CgParams), vp, vp, vp, vp, vp,
+                              sz, P(CgInfo), vp]),
+    "lo_cg_set_onchip": (ci, [ci]),
+    "lo_cg_plan_f32": (ci, [P(OpDesc), P(PrecondDesc), ci, ci, P(CgParams), ci, P(CgPlan)]),
+    "lo_cg_last_executed": (ci, [P(CgPlan)]),
+    "lo_resident_status_get": (ci, [P(ResidentStatus)]),
+    "lo_resident_inject_timeouts": (ci, [i32]),
+    "lo_resident_handoff_debug": (ci, [i32, i64, i64, P(C.c_uint32)]),
+    "lo_solve_fused_supported": (ci, [P(OpDesc), i32, P(CgParams)]),
+    "lo_solve_fused_workspace_bytes": (sz, [P(OpDesc), i32, P(CgParams)]),
+    "lo_solve_fused_f32": (ci, [P(OpDesc), i32, f32, P(CgParams), vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, P(FusedInfo),
+                                 vp]),
+    "lo_solve_fused_perm": (ci, [vp, i64, i64, i32, vp, vp]),
+    "lo_cg_f64_workspace_bytes": (sz, [i64, i64, P(CgParamsF64)]),
+    "lo_cg_solve_f64": (ci, [vp, vp, MATVEC_CB, vp, MATVEC_CB, vp, P(CgParamsF64), i64, i64, vp, vp, vp, vp, vp, sz,
+                              P(CgInfoF64), vp]),
+    "lo_minres_f64_workspace_bytes": (sz, [i64, i64, P(MinresParamsF64)]),
+    "lo_minres_f64": (ci, [vp, vp, MATVEC_CB, vp, MATVEC_CB, vp, P(MinresParamsF64), i64, i64, vp, vp, vp, vp, sz,
+                            P(MinresInfoF64), vp]),
+    "lo_pivoted_cholesky_workspace_bytes": (sz, [P(OpDesc), i32]),
+    "lo_pivoted_cholesky_f32": (ci, [P(OpDesc), i32, f32, vp, vp, P(i32), vp, sz, vp]),
+    "lo_pivoted_cholesky_cb_workspace_bytes": (sz, [i64, i64, i32]),
+    "lo_pivoted_cholesky_cb_f32": (ci, [i64, i64, vp, ROWFETCH_CB, vp, i32, f32, vp, vp, P(i32), vp, sz, vp]),
+    "lo_pivoted_cholesky_f64_workspace_bytes": (sz, [P(OpDesc), i32]),
+    "lo_pivoted_cholesky_f64": (ci, [P(OpDesc), i32, f64, vp, vp, P(i32), vp, sz, vp]),
+    "lo_pivoted_cholesky_cb_f64_workspace_bytes": (sz, [i64, i64, i32]),
+    "lo_pivoted_cholesky_cb_f64": (ci, [i64, i64, vp, ROWFETCH_CB, vp, i32, f64, vp, vp, P(i32), vp, sz, vp]),
+    "lo_precond_build_workspace_bytes": (sz, [i64, i64, i32]),
+    "lo_precond_build_f32": (ci, [vp, vp, i32, i64, i64, i32, vp, vp, vp, vp, sz, vp]),
+    "lo_precond_build_strided_f32": (ci, [vp, i64, i64, i64, vp, i32, i64, i64, i32, vp, vp, vp, vp, sz, vp]),
+    "lo_precond_apply_workspace_bytes": (sz, [i64, i64, i32, i64]),
+    "lo_precond_apply_f32": (ci, [P(PrecondDesc), vp, vp, i64, i64, i64, vp, sz, vp]),
+    "lo_precond_root_form_workspace_bytes": (sz, [i64, i64, i32]),
+    "lo_precond_root_form_f32": (ci, [vp, i32, vp, i32, vp, i64, i64, i64, vp, i64, i64, i32, i32, vp, vp, vp, vp, vp,
+                                       vp, sz, vp]),
+    "lo_precond_root_form_rs_workspace_bytes": (sz, [i64, i64, i32]),
+    "lo_precond_root_form_rs_f32": (ci, [vp, i32, vp, i32, vp, i64, i64, i64, vp, i64, i64, i32, i32, vp, vp, vp, vp,
+                                          vp, vp, vp, sz, vp]),
+    "lo_precond_eigform_f32": (ci, [vp, i64, i32, i32, vp, vp]),
+    "lo_precond_kron_root_workspace_bytes": (sz, [i64]),
+    "lo_precond_kron_root_f32": (ci, [P(OpDesc), vp, i64, i64, i64, vp, i32, vp, vp, vp, vp, vp, sz, vp]),
+    "lo_lanczos_workspace_bytes": (sz, [P(OpDesc), i64, i32]),
+    "lo_lanczos_tridiag_f32": (ci, [P(OpDesc), MATVEC_CB, vp, vp, i64, i32, f32, vp, vp, P(i32), vp, sz, vp]),
+    "lo_lanczos_permute_f32": (ci, [vp, i32, i64, i64, i64, vp, vp]),
+    "lo_root_from_lanczos_f32": (ci, [vp, vp, vp, i64, i64, i32, vp, vp, vp, vp]),
+    "lo_root_from_lanczos_native_f32": (ci, [vp, vp, vp, i64, i64, i64, i32, vp, vp, vp, vp]),
+    "lo_lanczos_f64_workspace_bytes": (sz, [i64, i64, i64, i32]),
+    "lo_lanczos_tridiag_f64": (ci, [vp, vp, MATVEC_CB, vp, vp, i64, i64, i64, i32, f64, vp, vp, P(i32), vp, sz, vp]),
+    "lo_tridiag_eigh_slq_workspace_bytes": (sz, [i64, i64]),
+    "lo_tridiag_eigh_slq_f32": (ci, [vp, i64, i64, i32, i64, vp, vp, vp, vp, sz, vp]),
+    "lo_bilinear_dense_f32": (ci, [vp, vp, i64, i64, i64, vp, vp]),
+    "lo_bilinear_diag_f32": (ci, [vp, vp, i64, i64, i64, i32, vp, vp, sz, vp]),
+    "lo_bilinear_root_workspace_bytes": (sz, [i64, i64, i64, i64]),
+    "lo_bilinear_root_f32": (ci, [vp, vp, vp, i64, i64, i64, i64, vp, vp, vp, sz, vp]),
+    "lo_bilinear_kron_workspace_bytes": (sz, [i64, i64, i64, i64]),
+    "lo_bilinear_kron_f32": (ci, [vp, vp, vp, vp, i64, i64, i64, i64, vp, vp, vp, sz, vp]),
+    "lo_root_apply_add_f32": (ci, [vp, vp, i64, i64, i64, i64, vp, vp]),
+    "lo_minres_workspace_bytes": (sz, [P(OpDesc), P(PrecondDesc), P(MinresParams)]),
+    "lo_minres_f32": (ci, [P(OpDesc), MATVEC_CB, vp, P(PrecondDesc), MATVEC_CB, vp, P(MinresParams), vp, vp, vp, vp, sz,
+                            P(MinresInfo), vp]),
+    "lo_probe_vectors_workspace_bytes": (sz, [i64, i64, i64]),
+    "lo_probe_vectors_f32": (ci, [vp, i64, i64, i64, i32, vp, i32, vp, vp, vp, i64, i64, i64, i64, vp, vp, vp, sz, vp]),
+    "lo_iql_backward_factors_f32": (ci, [vp, vp, i64, vp, vp, vp, f32, i64, i64, i64, i64, vp, vp, vp, vp, vp]),
+    "lo_interp_f32": (ci, [vp, vp, i64, i64, i64, i64, vp, i64, vp, vp]),
+    "lo_interp_t_workspace_bytes": (sz, [i64, i64, i64, i64]),
+    "lo_interp_t_f32": (ci, [vp, vp, i64, i64, i64, i64, vp, i64, vp, vp, sz, vp]),
+    "lo_interp_plan_bytes": (sz, [i64, i64, i64, i64]),
+    "lo_interp_plan_build": (ci, [vp, i64, i64, i64, i64, vp, sz, vp]),
+    "lo_interp_t_planned_f32": (ci, [vp, vp, i64, i64, i64, i64, vp, i64, vp, vp]),
+    "lo_toeplitz_workspace_bytes": (sz, [i64, i64, i64]),
+    "lo_toeplitz_mv_f32": (ci, [vp, i64, i64, vp, i64, vp, vp, sz, vp]),
+    "lo_toeplitz_bilinear_f32": (ci, [vp, vp, i64, i64, i64, vp, vp, sz, vp]),
+    "lo_interp_values_grad_f32": (ci, [vp, i64, i64, i64, i64, vp, vp, i64, vp, vp]),
+    "lo_hadamard_bilinear_workspace_bytes": (sz, [i64, i64, i64, i64, i64]),
+    "lo_hadamard_bilinear_f32": (ci, [vp, vp, vp, vp, i64, i64, i64, i64, i64, vp, vp, vp, sz, vp]),
+    "lo_prof_enable": (ci, [ci]),
+    "lo_prof_report": (ci, [C.c_char_p, sz]),
+    "lo_hbm_triad_f32": (ci, [vp, vp, vp, f32, sz, vp]),
+    "lo_hbm_copy_f32": (ci, [vp, vp, sz, vp]),
+    "lo_hbm_stream_dev": (ci, [ci, ci, ci, vp, vp, vp, f32, sz, vp]),
+    "lo_peer_gather_set": (ci, [P(vp), ci, C.c_longlong]),
+}
+del ci, i32, i64, f32, f64, sz, vp, P
+EXPORTS = list(_PROTOTYPES)
+
 
 def lib_path() -> str:
     return _LIB_PATH
@@ -180,219 +242,18 @@ def load():
             "g.build()'` (or `make -C linear_operator_amd/csrc`). linear_operator_amd has no CPU fallback."
         )
     lib = C.CDLL(_LIB_PATH, mode=C.RTLD_GLOBAL)
-    lib.lo_abi_version.restype = C.c_int
-    lib.lo_target_arch.restype = C.c_char_p
-    if lib.lo_abi_version() != ABI_VERSION:
+    missing = []
+    for name, (restype, argtypes) in _PROTOTYPES.items():
+        fn = getattr(lib, name, None)
+        if fn is None:
+            missing.append(name)
+            continue
+        fn.restype = restype
+        fn.argtypes = argtypes
+    if "lo_abi_version" not in missing and lib.lo_abi_version() != ABI_VERSION:
         raise HipExtensionError(f"liblo_amd.so ABI {lib.lo_abi_version()} != binding {ABI_VERSION}; rebuild")
-    missing = [name for name in EXPORTS if not hasattr(lib, name)]
     if missing:
         raise HipExtensionError(f"liblo_amd.so does not export {missing}; rebuild it")
-    sz = C.c_size_t
-    P = C.POINTER
-    lib.lo_matvec_workspace_bytes.restype = sz
-    lib.lo_matvec_workspace_bytes.argtypes = [P(OpDesc), C.c_int64]
-    lib.lo_matvec_f32.restype = C.c_int
-    lib.lo_matvec_f32.argtypes = [P(OpDesc), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, sz, C.c_void_p]
-    lib.lo_cg_workspace_bytes.restype = sz
-    lib.lo_cg_workspace_bytes.argtypes = [P(OpDesc), P(PrecondDesc), P(CgParams)]
-    lib.lo_cg_solve_f32.restype = C.c_int
-    lib.lo_cg_solve_f32.argtypes = [P(OpDesc), MATVEC_CB, C.c_void_p, P(PrecondDesc), MATVEC_CB, C.c_void_p,
-                                    P(CgParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, sz,
-                                    P(CgInfo), C.c_void_p]
-    lib.lo_root_from_lanczos_native_f32.restype = C.c_int
-    lib.lo_root_from_lanczos_native_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
-                                                    C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.lo_pivoted_cholesky_f64_workspace_bytes.restype = sz
-    lib.lo_pivoted_cholesky_f64_workspace_bytes.argtypes = [P(OpDesc), C.c_int32]
-    lib.lo_pivoted_cholesky_f64.restype = C.c_int
-    lib.lo_pivoted_cholesky_f64.argtypes = [P(OpDesc), C.c_int32, C.c_double, C.c_void_p, C.c_void_p, P(C.c_int32),
-                                            C.c_void_p, sz, C.c_void_p]
-    lib.lo_pivoted_cholesky_cb_f64_workspace_bytes.restype = sz
-    lib.lo_pivoted_cholesky_cb_f64_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int32]
-    lib.lo_pivoted_cholesky_cb_f64.restype = C.c_int
-    lib.lo_pivoted_cholesky_cb_f64.argtypes = [C.c_int64, C.c_int64, C.c_void_p, ROWFETCH_CB, C.c_void_p, C.c_int32,
-                                               C.c_double, C.c_void_p, C.c_void_p, P(C.c_int32), C.c_void_p, sz,
-                                               C.c_void_p]
-    lib.lo_cg_plan_f32.restype = C.c_int
-    lib.lo_cg_plan_f32.argtypes = [P(OpDesc), P(PrecondDesc), C.c_int, C.c_int, P(CgParams), C.c_int, P(CgPlan)]
-    lib.lo_cg_last_executed.restype = C.c_int
-    lib.lo_cg_last_executed.argtypes = [P(CgPlan)]
-    lib.lo_solve_fused_supported.restype = C.c_int
-    lib.lo_solve_fused_supported.argtypes = [P(OpDesc), C.c_int32, P(CgParams)]
-    lib.lo_solve_fused_workspace_bytes.restype = sz
-    lib.lo_solve_fused_workspace_bytes.argtypes = [P(OpDesc), C.c_int32, P(CgParams)]
-    lib.lo_solve_fused_f32.restype = C.c_int
-    lib.lo_solve_fused_f32.argtypes = [P(OpDesc), C.c_int32, C.c_float, P(CgParams), C.c_void_p, C.c_void_p, C.c_void_p,
-                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, sz,
-                                       P(FusedInfo), C.c_void_p]
-    lib.lo_solve_fused_perm.restype = C.c_int
-    lib.lo_solve_fused_perm.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]
-    lib.lo_cg_f64_workspace_bytes.restype = sz
-    lib.lo_cg_f64_workspace_bytes.argtypes = [C.c_int64, C.c_int64, P(CgParamsF64)]
-    lib.lo_cg_solve_f64.restype = C.c_int
-    lib.lo_cg_solve_f64.argtypes = [C.c_void_p, C.c_void_p, MATVEC_CB, C.c_void_p, MATVEC_CB, C.c_void_p,
-                                    P(CgParamsF64), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
-                                    C.c_void_p, C.c_void_p, sz, P(CgInfoF64), C.c_void_p]
-    lib.lo_lanczos_f64_workspace_bytes.restype = sz
-    lib.lo_lanczos_f64_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int32]
-    lib.lo_lanczos_tridiag_f64.restype = C.c_int
-    lib.lo_lanczos_tridiag_f64.argtypes = [C.c_void_p, C.c_void_p, MATVEC_CB, C.c_void_p, C.c_void_p, C.c_int64,
-                                           C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_void_p, C.c_void_p,
-                                           P(C.c_int32), C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.lo_minres_f64_workspace_bytes.restype = sz
-    lib.lo_minres_f64_workspace_bytes.argtypes = [C.c_int64, C.c_int64, P(MinresParamsF64)]
-    lib.lo_minres_f64.restype = C.c_int
-    lib.lo_minres_f64.argtypes = [C.c_void_p, C.c_void_p, MATVEC_CB, C.c_void_p, MATVEC_CB, C.c_void_p,
-                                  P(MinresParamsF64), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
-                                  C.c_void_p, sz, P(MinresInfoF64), C.c_void_p]
-    lib.lo_minres_workspace_bytes.restype = sz
-    lib.lo_minres_workspace_bytes.argtypes = [P(OpDesc), P(PrecondDesc), P(MinresParams)]
-    lib.lo_minres_f32.restype = C.c_int
-    lib.lo_minres_f32.argtypes = [P(OpDesc), MATVEC_CB, C.c_void_p, P(PrecondDesc), MATVEC_CB, C.c_void_p,
-                                  P(MinresParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, sz, P(MinresInfo),
-                                  C.c_void_p]
-    lib.lo_pivoted_cholesky_workspace_bytes.restype = sz
-    lib.lo_pivoted_cholesky_workspace_bytes.argtypes = [P(OpDesc), C.c_int32]
-    lib.lo_pivoted_cholesky_f32.restype = C.c_int
-    lib.lo_pivoted_cholesky_f32.argtypes = [P(OpDesc), C.c_int32, C.c_float, C.c_void_p, C.c_void_p,
-                                            P(C.c_int32), C.c_void_p, sz, C.c_void_p]
-    lib.lo_pivoted_cholesky_cb_workspace_bytes.restype = sz
-    lib.lo_pivoted_cholesky_cb_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int32]
-    lib.lo_pivoted_cholesky_cb_f32.restype = C.c_int
-    lib.lo_pivoted_cholesky_cb_f32.argtypes = [C.c_int64, C.c_int64, C.c_void_p, ROWFETCH_CB, C.c_void_p, C.c_int32,
-                                               C.c_float, C.c_void_p, C.c_void_p, P(C.c_int32), C.c_void_p, sz,
-                                               C.c_void_p]
-    lib.lo_precond_build_workspace_bytes.restype = sz
-    lib.lo_precond_build_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int32]
-    lib.lo_precond_build_f32.restype = C.c_int
-    lib.lo_precond_build_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32,
-                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, sz, C.c_void_p]
-    lib.lo_precond_build_strided_f32.restype = C.c_int
-    lib.lo_precond_build_strided_f32.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int32,
-                                                 C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                 C.c_void_p, sz, C.c_void_p]
-    lib.lo_precond_root_form_workspace_bytes.restype = sz
-    lib.lo_precond_root_form_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int32]
-    lib.lo_precond_root_form_f32.restype = C.c_int
-    lib.lo_precond_root_form_f32.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64,
-                                             C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int32,
-                                             C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                             C.c_void_p, sz, C.c_void_p]
-    lib.lo_precond_root_form_rs_workspace_bytes.restype = sz
-    lib.lo_precond_root_form_rs_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int32]
-    lib.lo_precond_eigform_f32.restype = C.c_int
-    lib.lo_precond_eigform_f32.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
-    lib.lo_precond_root_form_rs_f32.restype = C.c_int
-    lib.lo_precond_root_form_rs_f32.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64,
-                                                C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int32,
-                                                C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                C.c_void_p, C.c_void_p, sz, C.c_void_p]
-    lib.lo_precond_kron_root_workspace_bytes.restype = sz
-    lib.lo_precond_kron_root_workspace_bytes.argtypes = [C.c_int64]
-    lib.lo_precond_kron_root_f32.restype = C.c_int
-    lib.lo_precond_kron_root_f32.argtypes = [P(OpDesc), C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
-                                             C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, sz,
-                                             C.c_void_p]
-    lib.lo_precond_apply_workspace_bytes.restype = sz
-    lib.lo_precond_apply_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int32, C.c_int64]
-    lib.lo_precond_apply_f32.restype = C.c_int
-    lib.lo_precond_apply_f32.argtypes = [P(PrecondDesc), C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
-                                         C.c_void_p, sz, C.c_void_p]
-    lib.lo_root_from_lanczos_f32.restype = C.c_int
-    lib.lo_root_from_lanczos_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32,
-                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.lo_lanczos_permute_f32.restype = C.c_int
-    lib.lo_lanczos_permute_f32.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
-    lib.lo_lanczos_workspace_bytes.restype = sz
-    lib.lo_lanczos_workspace_bytes.argtypes = [P(OpDesc), C.c_int64, C.c_int32]
-    lib.lo_lanczos_tridiag_f32.restype = C.c_int
-    lib.lo_lanczos_tridiag_f32.argtypes = [P(OpDesc), MATVEC_CB, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
-                                           C.c_float, C.c_void_p, C.c_void_p, P(C.c_int32), C.c_void_p, sz,
-                                           C.c_void_p]
-    lib.lo_tridiag_eigh_slq_f32.restype = C.c_int
-    lib.lo_tridiag_eigh_slq_workspace_bytes.restype = sz
-    lib.lo_tridiag_eigh_slq_workspace_bytes.argtypes = [C.c_int64, C.c_int64]
-    lib.lo_tridiag_eigh_slq_f32.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_void_p,
-                                            C.c_void_p, C.c_void_p, C.c_void_p, sz, C.c_void_p]
-    lib.lo_cg_set_onchip.restype = C.c_int
-    lib.lo_cg_set_onchip.argtypes = [C.c_int]
-    lib.lo_resident_status_get.restype = C.c_int
-    lib.lo_resident_status_get.argtypes = [P(ResidentStatus)]
-    lib.lo_resident_inject_timeouts.restype = C.c_int
-    lib.lo_resident_inject_timeouts.argtypes = [C.c_int32]
-    lib.lo_resident_handoff_debug.restype = C.c_int
-    lib.lo_resident_handoff_debug.argtypes = [C.c_int32, C.c_int64, C.c_int64, P(C.c_uint32)]
-    lib.lo_prof_enable.restype = C.c_int
-    lib.lo_prof_enable.argtypes = [C.c_int]
-    lib.lo_prof_report.restype = C.c_int
-    lib.lo_prof_report.argtypes = [C.c_char_p, sz]
-    lib.lo_bilinear_dense_f32.restype = C.c_int
-    lib.lo_bilinear_dense_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
-    lib.lo_bilinear_diag_f32.restype = C.c_int
-    lib.lo_bilinear_diag_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_void_p,
-                                         C.c_void_p, sz, C.c_void_p]
-    lib.lo_bilinear_root_workspace_bytes.restype = sz
-    lib.lo_bilinear_root_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int64]
-    lib.lo_bilinear_root_f32.restype = C.c_int
-    lib.lo_bilinear_root_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
-                                         C.c_void_p, C.c_void_p, C.c_void_p, sz, C.c_void_p]
-    lib.lo_bilinear_kron_workspace_bytes.restype = sz
-    lib.lo_bilinear_kron_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int64]
-    lib.lo_bilinear_kron_f32.restype = C.c_int
-    lib.lo_bilinear_kron_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
-                                         C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, sz, C.c_void_p]
-    lib.lo_root_apply_add_f32.restype = C.c_int
-    lib.lo_root_apply_add_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
-                                          C.c_void_p]
-    lib.lo_probe_vectors_workspace_bytes.restype = sz
-    lib.lo_probe_vectors_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int64]
-    lib.lo_probe_vectors_f32.restype = C.c_int
-    lib.lo_probe_vectors_f32.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int32,
-                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
-                                         C.c_void_p, C.c_void_p, C.c_void_p, sz, C.c_void_p]
-    lib.lo_iql_backward_factors_f32.restype = C.c_int
-    lib.lo_iql_backward_factors_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                C.c_float, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
-                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    i64 = C.c_int64
-    lib.lo_interp_f32.restype = C.c_int
-    lib.lo_interp_f32.argtypes = [C.c_void_p, C.c_void_p, i64, i64, i64, i64, C.c_void_p, i64, C.c_void_p, C.c_void_p]
-    lib.lo_interp_t_workspace_bytes.restype = sz
-    lib.lo_interp_t_workspace_bytes.argtypes = [i64, i64, i64, i64]
-    lib.lo_interp_t_f32.restype = C.c_int
-    lib.lo_interp_t_f32.argtypes = [C.c_void_p, C.c_void_p, i64, i64, i64, i64, C.c_void_p, i64, C.c_void_p, C.c_void_p,
-                                    sz, C.c_void_p]
-    lib.lo_interp_plan_bytes.restype = sz
-    lib.lo_interp_plan_bytes.argtypes = [i64, i64, i64, i64]
-    lib.lo_interp_plan_build.restype = C.c_int
-    lib.lo_interp_plan_build.argtypes = [C.c_void_p, i64, i64, i64, i64, C.c_void_p, sz, C.c_void_p]
-    lib.lo_interp_t_planned_f32.restype = C.c_int
-    lib.lo_interp_t_planned_f32.argtypes = [C.c_void_p, C.c_void_p, i64, i64, i64, i64, C.c_void_p, i64, C.c_void_p,
-                                            C.c_void_p]
-    lib.lo_toeplitz_workspace_bytes.restype = sz
-    lib.lo_toeplitz_workspace_bytes.argtypes = [i64, i64, i64]
-    lib.lo_toeplitz_mv_f32.restype = C.c_int
-    lib.lo_toeplitz_mv_f32.argtypes = [C.c_void_p, i64, i64, C.c_void_p, i64, C.c_void_p, C.c_void_p, sz, C.c_void_p]
-    lib.lo_toeplitz_bilinear_f32.restype = C.c_int
-    lib.lo_toeplitz_bilinear_f32.argtypes = [C.c_void_p, C.c_void_p, i64, i64, i64, C.c_void_p, C.c_void_p, sz,
-                                             C.c_void_p]
-    lib.lo_interp_values_grad_f32.restype = C.c_int
-    lib.lo_interp_values_grad_f32.argtypes = [C.c_void_p, i64, i64, i64, i64, C.c_void_p, C.c_void_p, i64, C.c_void_p,
-                                              C.c_void_p]
-    lib.lo_hadamard_bilinear_workspace_bytes.restype = sz
-    lib.lo_hadamard_bilinear_workspace_bytes.argtypes = [i64, i64, i64, i64, i64]
-    lib.lo_hadamard_bilinear_f32.restype = C.c_int
-    lib.lo_hadamard_bilinear_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, i64, i64, i64, i64, i64,
-                                             C.c_void_p, C.c_void_p, C.c_void_p, sz, C.c_void_p]
-    lib.lo_hbm_triad_f32.restype = C.c_int
-    lib.lo_hbm_triad_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, sz, C.c_void_p]
-    lib.lo_hbm_copy_f32.restype = C.c_int
-    lib.lo_hbm_copy_f32.argtypes = [C.c_void_p, C.c_void_p, sz, C.c_void_p]
-    lib.lo_peer_gather_set.restype = C.c_int
-    lib.lo_peer_gather_set.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_longlong]
-    lib.lo_hbm_stream_dev.restype = C.c_int
-    lib.lo_hbm_stream_dev.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, sz,
-                                      C.c_void_p]
     _lib = lib
     return lib
 
@@ -416,7 +277,6 @@ def hbm_stream_gbs(device, mode: str = "triad", n_floats: int = 1 << 28, reps: i
     """Achievable HBM rate of this box in GB/s: `triad` a = b + s c (12 bytes per element), `copy` a = b (8 bytes),
     `read` (8 bytes), over n-float arrays (1 GiB each by default: far beyond the 256 MiB Infinity Cache).  `unroll` /
     `nt` select a variant of the sweep aid instead of the library's default shape."""
-    import torch
     lib = load()
     a, b, c = (torch.empty(n_floats, dtype=torch.float32, device=device) for _ in range(3))
     b.fill_(1.0)
@@ -451,6 +311,12 @@ def hbm_triad_gbs(device, n_floats: int = 1 << 28, reps: int = 10) -> float:
 def check(rc: int, what: str):
     if rc != 0:
         raise HipExtensionError(f"liblo_amd {what} failed: {_ERR.get(rc, rc)}")
+
+
+def call(name: str, *args):
+    """Call the entry point `name`; a non-zero return raises through check() under that name.  Entry points whose
+    non-zero return is a decision of the library (LO_ERR_UNSUPPORTED: take the other path) are called directly."""
+    check(getattr(load(), name)(*args), name)
 
 
 def require_hip(*tensors: Optional[torch.Tensor], dtype=torch.float32):

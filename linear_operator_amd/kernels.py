@@ -18,7 +18,7 @@ from . import _hip
 
 @dataclass
 class OperatorDescriptor:
-    """Lowered form of an operator tree (see operators/_lowering.py): what the kernels need."""
+    """Lowered form of an operator tree (the operators' `_kernel_descriptor()`): what the kernels need."""
 
     kind: int
     B: int
@@ -86,6 +86,91 @@ def _flat(t: torch.Tensor, keep: int) -> torch.Tensor:
     """[*batch, <keep trailing dims>] -> contiguous [B, ...]."""
     t = t.contiguous()
     return t.reshape(-1, *t.shape[t.dim() - keep:])
+
+
+def _byref(s):
+    return None if s is None else C.byref(s)
+
+
+def _launch(name: str, dev, *args, ws_bytes: Optional[int] = None, info=None, errors=()):
+    """Enqueue the entry point `name` on the current stream of `dev`: tensors go as device pointers, `ws_bytes` adds the
+    (workspace, its size) pair and `info` the result struct of a solver, which the entry points take in this order
+    before the stream.  `errors`: what the Python callbacks of this call caught (_wrap_closure); such an exception is
+    raised in place of the library's return code."""
+    args = [_hip.ptr(a) if isinstance(a, torch.Tensor) else a for a in args]
+    if ws_bytes is not None:
+        ws = _hip.workspace(ws_bytes, dev)
+        args += [_hip.ptr(ws), ws.numel()]
+    if info is not None:
+        args.append(C.byref(info))
+    try:
+        _hip.call(name, *args, _hip.stream_ptr(dev))
+    finally:
+        _reraise(*errors)
+
+
+_NO_CLOSURE = (_hip.MATVEC_CB(), ())  # the NULL callback and the exceptions it caught
+
+
+def _wrap_closure(fn: Callable, device, batch_shape, typestr: str = "<f4"):
+    """Python closure (tensor [*batch_shape, N, c] -> tensor) as an lo_matvec_cb (`typestr` "<f8": lo_matvec_cb_f64)
+    and the list its exceptions are kept in for _reraise."""
+    err = []
+
+    def cb(user, v_ptr, y_ptr, B, N, c, stream):
+        try:
+            v = _hip.as_tensor(v_ptr, (B, N, c), device, typestr)
+            y = _hip.as_tensor(y_ptr, (B, N, c), device, typestr)
+            y.copy_(fn(v.reshape(*batch_shape, N, c)).reshape(B, N, c))
+            return 0
+        except BaseException as e:  # noqa: BLE001 -- must not unwind through C
+            err.append(e)
+            return 1
+
+    return _hip.MATVEC_CB(cb), err
+
+
+def _reraise(*error_lists):
+    """After a call that took Python callbacks: raise the first exception one of them caught."""
+    for err in error_lists:
+        for e in err:
+            raise e
+
+
+def _callback_desc(B: int, N: int) -> _hip.OpDesc:
+    """The descriptor of an operator that is only a matvec callback."""
+    s = _hip.OpDesc()
+    s.kind, s.diag_mode, s.B, s.N, s.R, s.n2 = _hip.LO_OP_CALLBACK, _hip.LO_DIAG_NONE, B, N, 0, 0
+    return s
+
+
+def _dense_f64(A, diag, matvec_closure, batch_shape, B: int, N: int):
+    """The dense operand (A [B, N, N], diag [B, N] or None) of the fp64 entry points; (None, None): the closure."""
+    if A is not None:
+        return (A.expand(*batch_shape, N, N).reshape(B, N, N).contiguous(),
+                None if diag is None else diag.expand(*batch_shape, N).reshape(B, N).contiguous())
+    if matvec_closure is None:
+        raise ValueError("need a dense fp64 operator or a matvec closure")
+    return None, None
+
+
+def _diag_operand(d: torch.Tensor, B: int, N: int, const_diag: bool, want_dinv: bool = False):
+    """(d flattened to [B] (constant) or [B, N], its LO_DIAG_* mode, an empty buffer of that shape for 1 / d or None)."""
+    if const_diag:
+        d2, mode = d.contiguous().reshape(-1), _hip.LO_DIAG_CONST
+        assert d2.numel() == B, "constant diagonal must hold one value per batch member"
+    else:
+        d2, mode = _flat(d, 1), _hip.LO_DIAG_FULL
+        assert d2.shape == (B, N)
+    return d2, mode, (torch.empty_like(d2, dtype=torch.float32) if want_dinv else None)
+
+
+def _row_strides(L3: torch.Tensor):
+    """(member, row, column) strides of the factor L3 [B, N, k]; one member has no member stride."""
+    sm, sr, sc = L3.stride()
+    if L3.shape[0] == 1:
+        sm = 0
+    return sm, sr, sc
 
 
 def lowrank_diag_descriptor(Croot: torch.Tensor, d: Optional[torch.Tensor], const_diag: bool = False):
@@ -186,10 +271,7 @@ def bilinear_hadamard(F: torch.Tensor, G: torch.Tensor, left_vecs: torch.Tensor,
     ws_bytes = lib.lo_hadamard_bilinear_workspace_bytes(B, N, p, q, S)
     if ws_bytes == 0:
         raise _hip.HipExtensionError(f"lo_hadamard_bilinear_f32 does not take B={B} N={N} p={p} q={q} S={S}")
-    ws = _hip.workspace(ws_bytes, dev)
-    _hip.check(lib.lo_hadamard_bilinear_f32(_hip.ptr(F3), _hip.ptr(G3), _hip.ptr(U), _hip.ptr(V), B, N, p, q, S,
-                                            _hip.ptr(dF), _hip.ptr(dG), _hip.ptr(ws), ws.numel(), _hip.stream_ptr(dev)),
-               "lo_hadamard_bilinear_f32")
+    _launch("lo_hadamard_bilinear_f32", dev, F3, G3, U, V, B, N, p, q, S, dF, dG, ws_bytes=ws_bytes)
     return dF.reshape(*bs, N, p), dG.reshape(*bs, N, q)
 
 
@@ -199,8 +281,7 @@ def interp_plan_build(idx: torch.Tensor, M: int) -> torch.Tensor:
     idx = idx.contiguous()
     B, N, J = idx.shape
     plan = _hip.workspace(lib.lo_interp_plan_bytes(B, N, J, M), idx.device)
-    _hip.check(lib.lo_interp_plan_build(_hip.ptr(idx), B, N, J, M, _hip.ptr(plan), plan.numel(),
-                                        _hip.stream_ptr(idx.device)), "lo_interp_plan_build")
+    _launch("lo_interp_plan_build", idx.device, idx, B, N, J, M, plan, plan.numel())
     return plan
 
 
@@ -233,27 +314,23 @@ def clear_interp_plan_memo():
 
 def interp_t_planned(plan: torch.Tensor, vals: torch.Tensor, v: torch.Tensor, M: int) -> torch.Tensor:
     """W^T v from a kept grid-major copy (interp_plan): vals [B, N, J], v [B, N, c] -> [B, M, c]."""
-    lib = _hip.load()
     _hip.require_hip(vals, v)
     B, N, J = vals.shape
     c = v.shape[-1]
     vals, v = vals.contiguous(), v.contiguous()
     out = torch.empty(B, M, c, dtype=torch.float32, device=v.device)
-    _hip.check(lib.lo_interp_t_planned_f32(_hip.ptr(plan), _hip.ptr(vals), B, N, J, M, _hip.ptr(v), c, _hip.ptr(out),
-                                           _hip.stream_ptr(v.device)), "lo_interp_t_planned_f32")
+    _launch("lo_interp_t_planned_f32", v.device, plan, vals, B, N, J, M, v, c, out)
     return out
 
 
 def interp(idx: torch.Tensor, vals: torch.Tensor, u: torch.Tensor) -> torch.Tensor:
     """W u: idx int64 / vals fp32 [B, N, J], u [B, M, c] -> [B, N, c] (lo_interp_f32)."""
-    lib = _hip.load()
     _hip.require_hip(vals, u)
     B, N, J = idx.shape
     M, c = u.shape[-2:]
     idx, vals, u = idx.contiguous(), vals.contiguous(), u.contiguous()
     y = torch.empty(B, N, c, dtype=torch.float32, device=u.device)
-    _hip.check(lib.lo_interp_f32(_hip.ptr(idx), _hip.ptr(vals), B, N, J, M, _hip.ptr(u), c, _hip.ptr(y),
-                                 _hip.stream_ptr(u.device)), "lo_interp_f32")
+    _launch("lo_interp_f32", u.device, idx, vals, B, N, J, M, u, c, y)
     return y
 
 
@@ -265,9 +342,8 @@ def interp_t(idx: torch.Tensor, vals: torch.Tensor, v: torch.Tensor, M: int) -> 
     c = v.shape[-1]
     idx, vals, v = idx.contiguous(), vals.contiguous(), v.contiguous()
     out = torch.empty(B, M, c, dtype=torch.float32, device=v.device)
-    ws = _hip.workspace(lib.lo_interp_t_workspace_bytes(B, N, J, M), v.device)
-    _hip.check(lib.lo_interp_t_f32(_hip.ptr(idx), _hip.ptr(vals), B, N, J, M, _hip.ptr(v), c, _hip.ptr(out),
-                                   _hip.ptr(ws), ws.numel(), _hip.stream_ptr(v.device)), "lo_interp_t_f32")
+    _launch("lo_interp_t_f32", v.device, idx, vals, B, N, J, M, v, c, out,
+            ws_bytes=lib.lo_interp_t_workspace_bytes(B, N, J, M))
     return out
 
 
@@ -279,9 +355,7 @@ def toeplitz_mv(column: torch.Tensor, u: torch.Tensor) -> torch.Tensor:
     c = u.shape[-1]
     column, u = column.contiguous(), u.contiguous()
     y = torch.empty(B, M, c, dtype=torch.float32, device=u.device)
-    ws = _hip.workspace(lib.lo_toeplitz_workspace_bytes(B, M, c), u.device)
-    _hip.check(lib.lo_toeplitz_mv_f32(_hip.ptr(column), B, M, _hip.ptr(u), c, _hip.ptr(y), _hip.ptr(ws), ws.numel(),
-                                      _hip.stream_ptr(u.device)), "lo_toeplitz_mv_f32")
+    _launch("lo_toeplitz_mv_f32", u.device, column, B, M, u, c, y, ws_bytes=lib.lo_toeplitz_workspace_bytes(B, M, c))
     return y
 
 
@@ -292,36 +366,24 @@ def toeplitz_bilinear(u: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
     B, M, S = u.shape
     u, v = u.contiguous(), v.contiguous()
     g = torch.empty(B, M, dtype=torch.float32, device=u.device)
-    ws = _hip.workspace(lib.lo_toeplitz_workspace_bytes(B, M, 1), u.device)
-    _hip.check(lib.lo_toeplitz_bilinear_f32(_hip.ptr(u), _hip.ptr(v), B, M, S, _hip.ptr(g), _hip.ptr(ws), ws.numel(),
-                                            _hip.stream_ptr(u.device)), "lo_toeplitz_bilinear_f32")
+    _launch("lo_toeplitz_bilinear_f32", u.device, u, v, B, M, S, g, ws_bytes=lib.lo_toeplitz_workspace_bytes(B, M, 1))
     return g
 
 
 def interp_values_grad(idx: torch.Tensor, lv: torch.Tensor, R: torch.Tensor) -> torch.Tensor:
     """g [B, N, J]: g[n, j] = sum_s lv[n, s] R[idx[n, j], s]; idx [B, N, J], lv [B, N, S], R [B, M, S]."""
-    lib = _hip.load()
     _hip.require_hip(lv, R)
     B, N, J = idx.shape
     M, S = R.shape[-2:]
     idx, lv, R = idx.contiguous(), lv.contiguous(), R.contiguous()
     g = torch.empty(B, N, J, dtype=torch.float32, device=R.device)
-    _hip.check(lib.lo_interp_values_grad_f32(_hip.ptr(idx), B, N, J, M, _hip.ptr(lv), _hip.ptr(R), S, _hip.ptr(g),
-                                             _hip.stream_ptr(R.device)), "lo_interp_values_grad_f32")
+    _launch("lo_interp_values_grad_f32", R.device, idx, B, N, J, M, lv, R, S, g)
     return g
 
 
 def _with_diag(desc: OperatorDescriptor, d, const_diag):
-    if d is None:
-        return desc
-    if const_diag:
-        desc.d = d.contiguous().reshape(-1)
-        assert desc.d.numel() == desc.B, "constant diagonal must hold one value per batch member"
-        desc.diag_mode = _hip.LO_DIAG_CONST
-    else:
-        desc.d = _flat(d, 1)
-        assert desc.d.shape == (desc.B, desc.N)
-        desc.diag_mode = _hip.LO_DIAG_FULL
+    if d is not None:
+        desc.d, desc.diag_mode, _ = _diag_operand(d, desc.B, desc.N, const_diag)
     return desc
 
 
@@ -405,11 +467,9 @@ class WoodburyPreconditioner:
             if self.rs_rank < 2 or self.rs_rank % 2:
                 self.rsd_refused = "root rank"
                 return self
-            lib = _hip.load()
             B, ld = self.RS.shape[0], self.RS.shape[-1]
             RSD = torch.empty_like(self.RS)
-            _hip.check(lib.lo_precond_eigform_f32(_hip.ptr(self.RS), B, self.rs_rank, ld, _hip.ptr(RSD),
-                                                  _hip.stream_ptr(self.RS.device)), "lo_precond_eigform_f32")
+            _launch("lo_precond_eigform_f32", self.RS.device, self.RS, B, self.rs_rank, ld, RSD)
             worst = float(RSD[:, 5, 1, 0].amin().item())
             if worst > 0:
                 self.RSD = RSD
@@ -446,24 +506,6 @@ class CGResult:
     mean_residual: float
 
 
-def _wrap_closure(fn: Callable, device):
-    """Python closure (tensor -> tensor) as an lo_matvec_cb."""
-    err = []
-
-    def cb(user, v_ptr, y_ptr, B, N, c, stream):
-        try:
-            v = _hip.as_tensor(v_ptr, (B, N, c), device)
-            y = _hip.as_tensor(y_ptr, (B, N, c), device)
-            out = fn(v)
-            y.copy_(out.reshape(B, N, c))
-            return 0
-        except BaseException as e:  # noqa: BLE001 -- must not unwind through C
-            err.append(e)
-            return 1
-
-    return _hip.MATVEC_CB(cb), err
-
-
 @dataclass
 class MinresResult:
     x: torch.Tensor  # [n_shifts, *batch, N, c]
@@ -471,6 +513,26 @@ class MinresResult:
     matvecs: int
     converged: bool
     conv: float
+
+
+def _minres_operands(rhs, shifts, value, max_iter, tolerance, eps, prm_cls):
+    """What the two MINRES entry points share: (rhs [B, N, c], shifts [Q] | [Q, B], the parameter struct, x [Q, B, N, c])."""
+    rhs3 = _flat(rhs, 2)
+    B = rhs3.shape[0]
+    Q = shifts.shape[0]
+    per_member = shifts.dim() > 1
+    sh = shifts.to(device=rhs.device, dtype=rhs.dtype)
+    sh = (sh.expand(Q, *rhs.shape[:-2]).reshape(Q, B) if per_member else sh.reshape(Q)).contiguous()
+    prm = prm_cls()
+    prm.c, prm.n_shifts, prm.max_iter = rhs.shape[-1], Q, max_iter
+    prm.has_value, prm.value = (0, 1.0) if value is None else (1, float(value))
+    prm.shifts_per_member, prm.tolerance, prm.eps = int(per_member), tolerance, eps
+    return rhs3, sh, prm, torch.empty(Q, *rhs3.shape, dtype=rhs.dtype, device=rhs.device)
+
+
+def _minres_result(x, rhs, info) -> MinresResult:
+    return MinresResult(x.reshape(x.shape[0], *rhs.shape), info.iterations, info.matvecs, bool(info.converged),
+                        float(info.conv))
 
 
 def minres_solve(desc: Optional[OperatorDescriptor], rhs: torch.Tensor, shifts: torch.Tensor, *,
@@ -482,47 +544,27 @@ def minres_solve(desc: Optional[OperatorDescriptor], rhs: torch.Tensor, shifts: 
     rhs [*batch, N, c]; shifts [Q] or [Q, *batch]; returns x [Q, *batch, N, c] (scaled back by the rhs norms)."""
     lib = _hip.load()
     _hip.require_hip(rhs, shifts)
-    N, c = rhs.shape[-2:]
-    rhs3 = _flat(rhs, 2)
-    B = rhs3.shape[0]
+    N = rhs.shape[-2]
     dev = rhs.device
-    Q = shifts.shape[0]
-    per_member = shifts.dim() > 1
-    sh = shifts.to(torch.float32)
-    sh = (sh.expand(Q, *rhs.shape[:-2]).reshape(Q, B) if per_member else sh.reshape(Q)).contiguous()
+    rhs3, sh, prm, x = _minres_operands(rhs, shifts, value, max_iter, tolerance, eps, _hip.MinresParams)
+    B = rhs3.shape[0]
     if desc is None:
         if matvec_closure is None:
             raise ValueError("need an operator descriptor or a matvec closure")
-        s = _hip.OpDesc()
-        s.kind, s.diag_mode, s.B, s.N, s.R, s.n2 = _hip.LO_OP_CALLBACK, _hip.LO_DIAG_NONE, B, N, 0, 0
-        bshape = tuple(closure_batch_shape) if closure_batch_shape is not None else tuple(rhs.shape[:-2])
-        mv_cb, mv_err = _wrap_closure(lambda v: matvec_closure(v.reshape(*bshape, N, c)), dev)
+        s = _callback_desc(B, N)
     else:
         if desc.B != B or desc.N != N:
             raise RuntimeError(f"minres: rhs {tuple(rhs.shape)} does not match operator batch {desc.B}, N {desc.N}")
         s = desc.c_struct()
-        mv_cb, mv_err = _hip.MATVEC_CB(), []
-    if precond_closure is not None:
-        bshape_p = tuple(closure_batch_shape) if closure_batch_shape is not None else tuple(rhs.shape[:-2])
-        pc_cb, pc_err = _wrap_closure(lambda v: precond_closure(v.reshape(*bshape_p, N, c)), dev)
-    else:
-        pc_cb, pc_err = _hip.MATVEC_CB(), []
+    bshape = tuple(closure_batch_shape) if closure_batch_shape is not None else tuple(rhs.shape[:-2])
+    mv_cb, mv_err = _wrap_closure(matvec_closure, dev, bshape) if desc is None else _NO_CLOSURE
+    pc_cb, pc_err = _wrap_closure(precond_closure, dev, bshape) if precond_closure is not None else _NO_CLOSURE
     pre_s = precond.ensure_q().c_struct() if precond is not None else None  # (MINRES applies the Q form)
-    pre_p = C.byref(pre_s) if pre_s is not None else None
-    prm = _hip.MinresParams()
-    prm.c, prm.n_shifts, prm.max_iter = c, Q, max_iter
-    prm.has_value, prm.value = (0, 1.0) if value is None else (1, float(value))
-    prm.shifts_per_member, prm.tolerance, prm.eps = int(per_member), tolerance, eps
-    ws = _hip.workspace(lib.lo_minres_workspace_bytes(C.byref(s), pre_p, C.byref(prm)), dev)
-    x = torch.empty(Q, *rhs3.shape, dtype=torch.float32, device=dev)
     info = _hip.MinresInfo()
-    rc = lib.lo_minres_f32(C.byref(s), mv_cb, None, pre_p, pc_cb, None, C.byref(prm), _hip.ptr(rhs3), _hip.ptr(sh),
-                           _hip.ptr(x), _hip.ptr(ws), ws.numel(), C.byref(info), _hip.stream_ptr(dev))
-    for e in (mv_err + pc_err):
-        raise e
-    _hip.check(rc, "lo_minres_f32")
-    return MinresResult(x.reshape(Q, *rhs.shape), info.iterations, info.matvecs, bool(info.converged),
-                        float(info.conv))
+    _launch("lo_minres_f32", dev, C.byref(s), mv_cb, None, _byref(pre_s), pc_cb, None, C.byref(prm), rhs3, sh, x,
+            ws_bytes=lib.lo_minres_workspace_bytes(C.byref(s), _byref(pre_s), C.byref(prm)), info=info,
+            errors=(mv_err, pc_err))
+    return _minres_result(x, rhs, info)
 
 
 def minres_solve_f64(A: Optional[torch.Tensor], rhs: torch.Tensor, shifts: torch.Tensor, *,
@@ -534,52 +576,18 @@ def minres_solve_f64(A: Optional[torch.Tensor], rhs: torch.Tensor, shifts: torch
     other operator is called back once per product; `precond_closure`: any callable or None."""
     lib = _hip.load()
     _hip.require_hip(rhs, A, dtype=torch.float64)
-    N, c = rhs.shape[-2:]
-    rhs3 = _flat(rhs, 2)
-    B = rhs3.shape[0]
+    N = rhs.shape[-2]
     dev = rhs.device
     bshape = tuple(rhs.shape[:-2])
-    Q = shifts.shape[0]
-    per_member = shifts.dim() > 1
-    sh = shifts.to(device=dev, dtype=torch.float64)
-    sh = (sh.expand(Q, *bshape).reshape(Q, B) if per_member else sh.reshape(Q)).contiguous()
-    A3 = None
-    if A is not None:
-        A3 = A.expand(*bshape, N, N).reshape(B, N, N).contiguous()
-    elif matvec_closure is None:
-        raise ValueError("need a dense fp64 operator or a matvec closure")
-
-    def wrap(fn):
-        err = []
-
-        def cb(user, v_ptr, y_ptr, B_, N_, c_, stream):
-            try:
-                v = _hip.as_tensor(v_ptr, (B_, N_, c_), dev, "<f8")
-                y = _hip.as_tensor(y_ptr, (B_, N_, c_), dev, "<f8")
-                y.copy_(fn(v.reshape(*bshape, N_, c_)).reshape(B_, N_, c_))
-                return 0
-            except BaseException as e:  # noqa: BLE001 -- must not unwind through C
-                err.append(e)
-                return 1
-
-        return _hip.MATVEC_CB(cb), err
-
-    mv_cb, mv_err = wrap(matvec_closure) if A3 is None else (_hip.MATVEC_CB(), [])
-    pc_cb, pc_err = wrap(precond_closure) if precond_closure is not None else (_hip.MATVEC_CB(), [])
-    prm = _hip.MinresParamsF64()
-    prm.c, prm.n_shifts, prm.max_iter = c, Q, max_iter
-    prm.has_value, prm.value = (0, 1.0) if value is None else (1, float(value))
-    prm.shifts_per_member, prm.tolerance, prm.eps = int(per_member), tolerance, eps
-    ws = _hip.workspace(lib.lo_minres_f64_workspace_bytes(B, N, C.byref(prm)), dev)
-    x = torch.empty(Q, *rhs3.shape, dtype=torch.float64, device=dev)
+    rhs3, sh, prm, x = _minres_operands(rhs, shifts, value, max_iter, tolerance, eps, _hip.MinresParamsF64)
+    B = rhs3.shape[0]
+    A3, _ = _dense_f64(A, None, matvec_closure, bshape, B, N)
+    mv_cb, mv_err = _wrap_closure(matvec_closure, dev, bshape, "<f8") if A3 is None else _NO_CLOSURE
+    pc_cb, pc_err = _wrap_closure(precond_closure, dev, bshape, "<f8") if precond_closure is not None else _NO_CLOSURE
     info = _hip.MinresInfoF64()
-    rc = lib.lo_minres_f64(_hip.ptr(A3), None, mv_cb, None, pc_cb, None, C.byref(prm), B, N, _hip.ptr(rhs3),
-                           _hip.ptr(sh), _hip.ptr(x), _hip.ptr(ws), ws.numel(), C.byref(info), _hip.stream_ptr(dev))
-    for e in (mv_err + pc_err):
-        raise e
-    _hip.check(rc, "lo_minres_f64")
-    return MinresResult(x.reshape(Q, *rhs.shape), info.iterations, info.matvecs, bool(info.converged),
-                        float(info.conv))
+    _launch("lo_minres_f64", dev, A3, None, mv_cb, None, pc_cb, None, C.byref(prm), B, N, rhs3, sh, x,
+            ws_bytes=lib.lo_minres_f64_workspace_bytes(B, N, C.byref(prm)), info=info, errors=(mv_err, pc_err))
+    return _minres_result(x, rhs, info)
 
 
 # The diagonal form of the R-space iteration (csrc/lo_eigform.hip) is a cache-lifetime investment: two R x R Jacobi
@@ -601,6 +609,31 @@ def _eigform_due(uses: int, B: int) -> bool:
     return uses * gain_us >= build_us
 
 
+def _cg_params(c, n_tridiag, max_iter, max_tridiag_iter, tolerance, eps, stop_updating_after, floor_max_iter,
+               cls=_hip.CgParams):
+    """lo_cg_params (or, cls=_hip.CgParamsF64, lo_cg_params_f64) of one solve."""
+    prm = cls()
+    prm.c, prm.n_tridiag, prm.max_iter, prm.max_tridiag_iter = c, n_tridiag, max_iter, max_tridiag_iter
+    prm.floor_max_iter = floor_max_iter  # the reference's stop-rule floors use the unclipped max_iter (:303-305)
+    prm.tolerance, prm.eps, prm.stop_updating_after = tolerance, eps, stop_updating_after
+    return prm
+
+
+def _tridiag_buffer(n_tridiag: int, B: int, max_tridiag_iter: int, like: torch.Tensor):
+    if not n_tridiag:
+        return None
+    return torch.empty(n_tridiag, B, max_tridiag_iter, max_tridiag_iter, dtype=like.dtype, device=like.device)
+
+
+def _cg_result(x: torch.Tensor, t_mat: Optional[torch.Tensor], info) -> CGResult:
+    """CGResult from lo_cg_info / lo_cg_info_f64 / lo_fused_info; t_mat cropped to the iterations that filled it."""
+    if t_mat is not None:
+        m = info.last_tridiag_iter + 1
+        t_mat = t_mat[:, :, :m, :m].contiguous()
+    return CGResult(x, t_mat, info.iterations, info.matvecs, bool(info.tolerance_reached), bool(info.nan_detected),
+                    bool(info.skipped), float(info.mean_residual))
+
+
 def cg_solve(desc: Optional[OperatorDescriptor], rhs: torch.Tensor, *, x0: Optional[torch.Tensor] = None,
              precond: Optional[WoodburyPreconditioner] = None, matvec_closure: Optional[Callable] = None,
              precond_closure: Optional[Callable] = None, closure_batch_shape=None, n_tridiag: int = 0,
@@ -619,33 +652,17 @@ def cg_solve(desc: Optional[OperatorDescriptor], rhs: torch.Tensor, *, x0: Optio
     B = rhs3.shape[0]
     x03 = None if x0 is None else _flat(x0.expand_as(rhs), 2)
     dev = rhs.device
-    keep = []
     if desc is None:
         if matvec_closure is None:
             raise ValueError("need an operator descriptor or a matvec closure")
-        s = _hip.OpDesc()
-        s.kind, s.diag_mode, s.B, s.N, s.R, s.n2 = _hip.LO_OP_CALLBACK, _hip.LO_DIAG_NONE, B, N, 0, 0
-        bshape = tuple(closure_batch_shape) if closure_batch_shape is not None else tuple(rhs.shape[:-2])
-
-        def mv(v):
-            return matvec_closure(v.reshape(*bshape, N, c))
-
-        mv_cb, mv_err = _wrap_closure(mv, dev)
+        s = _callback_desc(B, N)
     else:
         if desc.B != B or desc.N != N:
             raise RuntimeError(f"cg_solve: rhs {tuple(rhs.shape)} does not match operator batch {desc.B}, N {desc.N}")
         s = desc.c_struct()
-        mv_cb, mv_err = _hip.MATVEC_CB(), []
-    if precond_closure is not None:
-        bshape_p = tuple(closure_batch_shape) if closure_batch_shape is not None else tuple(rhs.shape[:-2])
-
-        def pc(v):
-            return precond_closure(v.reshape(*bshape_p, N, c))
-
-        pc_cb, pc_err = _wrap_closure(pc, dev)
-    else:
-        pc_cb, pc_err = _hip.MATVEC_CB(), []
-    keep += [mv_cb, pc_cb]
+    bshape = tuple(closure_batch_shape) if closure_batch_shape is not None else tuple(rhs.shape[:-2])
+    mv_cb, mv_err = _wrap_closure(matvec_closure, dev, bshape) if desc is None else _NO_CLOSURE
+    pc_cb, pc_err = _wrap_closure(precond_closure, dev, bshape) if precond_closure is not None else _NO_CLOSURE
     # The diagonal form (0.5 - 0.7 ms of Jacobi work, 25 MB at 512 x 32, one blocking read-back) is built once the cache has
     # served enough solves ON THE RESIDENT R-SPACE KERNEL to pay for it: solves that kernel does not take (members beyond its
     # range, the batch-global stop rule, a cool-down of the resident kernels, LO_OC_NO_RSPACE) are not counted -- they are
@@ -660,10 +677,8 @@ def cg_solve(desc: Optional[OperatorDescriptor], rhs: torch.Tensor, *, x0: Optio
         # -> start over" retry below while another rank continues -- the collective counts would diverge.  Q up front.
         precond.ensure_q()
     pre_s = precond.c_struct() if precond is not None else None
-    prm = _hip.CgParams()
-    prm.c, prm.n_tridiag, prm.max_iter, prm.max_tridiag_iter = c, n_tridiag, max_iter, max_tridiag_iter
-    prm.floor_max_iter = floor_max_iter  # the reference's stop-rule floors use the unclipped max_iter (:303-305)
-    prm.tolerance, prm.eps, prm.stop_updating_after = tolerance, eps, stop_updating_after
+    pre_p = _byref(pre_s)
+    prm = _cg_params(c, n_tridiag, max_iter, max_tridiag_iter, tolerance, eps, stop_updating_after, floor_max_iter)
     sr_err = []
     if stop_reduce is not None:  # batch-global stopping rule over the ranks of a process group (distributed.py)
         def _sr(user, vals):
@@ -675,20 +690,17 @@ def cg_solve(desc: Optional[OperatorDescriptor], rhs: torch.Tensor, *, x0: Optio
                 sr_err.append(e)
                 return 1
 
-        prm.stop_reduce = _hip.STOP_REDUCE_CB(_sr)
-        keep.append(prm.stop_reduce)
-    ws_bytes = lib.lo_cg_workspace_bytes(C.byref(s), C.byref(pre_s) if pre_s is not None else None, C.byref(prm))
-    ws = _hip.workspace(ws_bytes, dev)
+        sr_cb = _hip.STOP_REDUCE_CB(_sr)  # (held here for the call: the struct stores its address)
+        prm.stop_reduce = sr_cb
+    ws = _hip.workspace(lib.lo_cg_workspace_bytes(C.byref(s), pre_p, C.byref(prm)), dev)
     x = torch.empty_like(rhs3)
-    t_mat = None
-    if n_tridiag:
-        t_mat = torch.empty(n_tridiag, B, max_tridiag_iter, max_tridiag_iter, dtype=torch.float32, device=dev)
+    t_mat = _tridiag_buffer(n_tridiag, B, max_tridiag_iter, rhs3)
     info = _hip.CgInfo()
-    rc = lib.lo_cg_solve_f32(C.byref(s), mv_cb, None, C.byref(pre_s) if pre_s is not None else None, pc_cb, None,
-                             C.byref(prm), _hip.ptr(rhs3), _hip.ptr(x03), _hip.ptr(x), _hip.ptr(t_mat), _hip.ptr(ws),
-                             ws.numel(), C.byref(info), _hip.stream_ptr(dev))
-    for e in (mv_err + pc_err + sr_err):
-        raise e
+    # (called directly, not through _launch: LO_ERR_UNSUPPORTED is a decision, and this is the headline solve's path)
+    rc = lib.lo_cg_solve_f32(C.byref(s), mv_cb, None, pre_p, pc_cb, None, C.byref(prm), _hip.ptr(rhs3), _hip.ptr(x03),
+                             _hip.ptr(x), _hip.ptr(t_mat), _hip.ptr(ws), ws.numel(), C.byref(info),
+                             _hip.stream_ptr(dev))
+    _reraise(mv_err, pc_err, sr_err)
     if rc == _hip.LO_ERR_UNSUPPORTED and precond is not None and precond.Q is None:
         # root-form-only preconditioner and the operator-resident kernels could not take the solve (shape outside
         # their range, or a group hand-off timed out): build the generic Q form and run again
@@ -703,11 +715,7 @@ def cg_solve(desc: Optional[OperatorDescriptor], rhs: torch.Tensor, *, x0: Optio
         ex = _hip.CgPlan()
         if lib.lo_cg_last_executed(C.byref(ex)) == 0 and ex.rspace == 2:
             precond.rs_uses += 1
-    if t_mat is not None:
-        m = info.last_tridiag_iter + 1
-        t_mat = t_mat[:, :, :m, :m].contiguous()
-    return CGResult(x.reshape(rhs.shape), t_mat, info.iterations, info.matvecs, bool(info.tolerance_reached),
-                    bool(info.nan_detected), bool(info.skipped), float(info.mean_residual))
+    return _cg_result(x.reshape(rhs.shape), t_mat, info)
 
 
 def _plan_dict(pl) -> dict:
@@ -724,24 +732,21 @@ def cg_plan(desc: OperatorDescriptor, c: int, *, precond: Optional[WoodburyPreco
             floor_max_iter: int = 0, global_rule: bool = False, cus: int = 0) -> dict:
     """lo_cg_plan_f32: which engines `cg_solve` will run for these arguments (pure; nothing is launched).  cus = 0:
     this device."""
-    lib = _hip.load()
     s = desc.c_struct()
     pre_s = precond.c_struct() if precond is not None else None
-    prm = _hip.CgParams()
-    prm.c, prm.n_tridiag, prm.max_iter, prm.max_tridiag_iter, prm.floor_max_iter = c, n_tridiag, max_iter, max_tridiag_iter, floor_max_iter
-    prm.tolerance, prm.eps, prm.stop_updating_after = 1.0, 1e-10, 1e-10
+    prm = _cg_params(c, n_tridiag, max_iter, max_tridiag_iter, 1.0, 1e-10, 1e-10, floor_max_iter)
     if global_rule:
         prm.stop_reduce = _hip.STOP_REDUCE_CB(lambda user, vals: 0)
     out = _hip.CgPlan()
-    _hip.check(lib.lo_cg_plan_f32(C.byref(s), C.byref(pre_s) if pre_s is not None else None, int(has_precond_closure),
-                                  int(has_x0), C.byref(prm), int(cus), C.byref(out)), "lo_cg_plan_f32")
+    _hip.call("lo_cg_plan_f32", C.byref(s), _byref(pre_s), int(has_precond_closure), int(has_x0), C.byref(prm),
+              int(cus), C.byref(out))
     return _plan_dict(out)
 
 
 def cg_last_executed() -> dict:
     """lo_cg_last_executed: the plan the calling thread's last `cg_solve` actually ran (after run-time fall-backs)."""
     out = _hip.CgPlan()
-    _hip.check(_hip.load().lo_cg_last_executed(C.byref(out)), "lo_cg_last_executed")
+    _hip.call("lo_cg_last_executed", C.byref(out))
     return _plan_dict(out)
 
 
@@ -757,20 +762,10 @@ class FusedSolveResult:
 
     def permutation(self, N: int) -> torch.Tensor:
         """The reference's permutation [B, N] int64 (_pivoted_cholesky.py:47-48, :67-70) from the recorded exchanges."""
-        lib = _hip.load()
         B = self.swaps.shape[0]
         perm = torch.empty(B, N, dtype=torch.int64, device=self.swaps.device)
-        _hip.check(lib.lo_solve_fused_perm(_hip.ptr(self.swaps), B, N, self.rank, _hip.ptr(perm),
-                                           _hip.stream_ptr(perm.device)), "lo_solve_fused_perm")
+        _launch("lo_solve_fused_perm", perm.device, self.swaps, B, N, self.rank, perm)
         return perm
-
-
-def _cg_params(c, n_tridiag, max_iter, max_tridiag_iter, tolerance, eps, stop_updating_after, floor_max_iter):
-    prm = _hip.CgParams()
-    prm.c, prm.n_tridiag, prm.max_iter, prm.max_tridiag_iter = c, n_tridiag, max_iter, max_tridiag_iter
-    prm.floor_max_iter = floor_max_iter
-    prm.tolerance, prm.eps, prm.stop_updating_after = tolerance, eps, stop_updating_after
-    return prm
 
 
 _fused_ws_bytes: dict = {}  # workspace size of lo_solve_fused_f32 per (B, rank, c, max_iter, floor): a pure function
@@ -828,9 +823,7 @@ def solve_fused(desc: OperatorDescriptor, rhs: torch.Tensor, rank: int, error_to
         return None
     pre = WoodburyPreconditioner(None, dinv, rank, const, logdet.reshape(desc.batch_shape) if desc.batch_shape else logdet,
                                  F, EF, E)
-    cg = CGResult(x.reshape(rhs.shape), None, info.iterations, info.matvecs, bool(info.tolerance_reached),
-                  bool(info.nan_detected), bool(info.skipped), float(info.mean_residual))
-    return FusedSolveResult(cg, pre, swaps, rank)
+    return FusedSolveResult(_cg_result(x.reshape(rhs.shape), None, info), pre, swaps, rank)
 
 
 def cg_solve_f64(A: Optional[torch.Tensor], diag: Optional[torch.Tensor], rhs: torch.Tensor, *,
@@ -850,51 +843,17 @@ def cg_solve_f64(A: Optional[torch.Tensor], diag: Optional[torch.Tensor], rhs: t
     dev = rhs.device
     bshape = tuple(rhs.shape[:-2])
     x03 = None if x0 is None else _flat(x0.expand_as(rhs), 2)
-    A3 = d2 = None
-    if A is not None:
-        A3 = A.expand(*bshape, N, N).reshape(B, N, N).contiguous()
-        d2 = None if diag is None else diag.expand(*bshape, N).reshape(B, N).contiguous()
-    elif matvec_closure is None:
-        raise ValueError("need a dense fp64 operator or a matvec closure")
-
-    def wrap(fn):
-        err = []
-
-        def cb(user, v_ptr, y_ptr, B_, N_, c_, stream):
-            try:
-                v = _hip.as_tensor(v_ptr, (B_, N_, c_), dev, "<f8")
-                y = _hip.as_tensor(y_ptr, (B_, N_, c_), dev, "<f8")
-                y.copy_(fn(v.reshape(*bshape, N_, c_)).reshape(B_, N_, c_))
-                return 0
-            except BaseException as e:  # noqa: BLE001 -- must not unwind through C
-                err.append(e)
-                return 1
-
-        return _hip.MATVEC_CB(cb), err
-
-    mv_cb, mv_err = wrap(matvec_closure) if A3 is None else (_hip.MATVEC_CB(), [])
-    pc_cb, pc_err = wrap(precond_closure) if precond_closure is not None else (_hip.MATVEC_CB(), [])
-    prm = _hip.CgParamsF64()
-    prm.c, prm.n_tridiag, prm.max_iter, prm.max_tridiag_iter = c, n_tridiag, max_iter, max_tridiag_iter
-    prm.floor_max_iter = floor_max_iter
-    prm.tolerance, prm.eps, prm.stop_updating_after = tolerance, eps, stop_updating_after
-    ws = _hip.workspace(lib.lo_cg_f64_workspace_bytes(B, N, C.byref(prm)), dev)
+    A3, d2 = _dense_f64(A, diag, matvec_closure, bshape, B, N)
+    mv_cb, mv_err = _wrap_closure(matvec_closure, dev, bshape, "<f8") if A3 is None else _NO_CLOSURE
+    pc_cb, pc_err = _wrap_closure(precond_closure, dev, bshape, "<f8") if precond_closure is not None else _NO_CLOSURE
+    prm = _cg_params(c, n_tridiag, max_iter, max_tridiag_iter, tolerance, eps, stop_updating_after, floor_max_iter,
+                     _hip.CgParamsF64)
     x = torch.empty_like(rhs3)
-    t_mat = None
-    if n_tridiag:
-        t_mat = torch.empty(n_tridiag, B, max_tridiag_iter, max_tridiag_iter, dtype=torch.float64, device=dev)
+    t_mat = _tridiag_buffer(n_tridiag, B, max_tridiag_iter, rhs3)
     info = _hip.CgInfoF64()
-    rc = lib.lo_cg_solve_f64(_hip.ptr(A3), _hip.ptr(d2), mv_cb, None, pc_cb, None, C.byref(prm), B, N, _hip.ptr(rhs3),
-                             _hip.ptr(x03), _hip.ptr(x), _hip.ptr(t_mat), _hip.ptr(ws), ws.numel(), C.byref(info),
-                             _hip.stream_ptr(dev))
-    for e in (mv_err + pc_err):
-        raise e
-    _hip.check(rc, "lo_cg_solve_f64")
-    if t_mat is not None:
-        m = info.last_tridiag_iter + 1
-        t_mat = t_mat[:, :, :m, :m].contiguous()
-    return CGResult(x.reshape(rhs.shape), t_mat, info.iterations, info.matvecs, bool(info.tolerance_reached),
-                    bool(info.nan_detected), bool(info.skipped), float(info.mean_residual))
+    _launch("lo_cg_solve_f64", dev, A3, d2, mv_cb, None, pc_cb, None, C.byref(prm), B, N, rhs3, x03, x, t_mat,
+            ws_bytes=lib.lo_cg_f64_workspace_bytes(B, N, C.byref(prm)), info=info, errors=(mv_err, pc_err))
+    return _cg_result(x.reshape(rhs.shape), t_mat, info)
 
 
 def precond_apply(pre: WoodburyPreconditioner, r: torch.Tensor) -> torch.Tensor:
@@ -905,9 +864,8 @@ def precond_apply(pre: WoodburyPreconditioner, r: torch.Tensor) -> torch.Tensor:
     B = r3.shape[0]
     z = torch.empty_like(r3)
     s = pre.ensure_q().c_struct()
-    ws = _hip.workspace(lib.lo_precond_apply_workspace_bytes(B, N, pre.k, c), r.device)
-    _hip.check(lib.lo_precond_apply_f32(C.byref(s), _hip.ptr(r3), _hip.ptr(z), B, N, c, _hip.ptr(ws), ws.numel(),
-                                        _hip.stream_ptr(r.device)), "lo_precond_apply_f32")
+    _launch("lo_precond_apply_f32", r.device, C.byref(s), r3, z, B, N, c,
+            ws_bytes=lib.lo_precond_apply_workspace_bytes(B, N, pre.k, c))
     return z.reshape(r.shape)
 
 
@@ -936,12 +894,9 @@ def probe_vectors(L: torch.Tensor, d: torch.Tensor, e1: torch.Tensor, e2: torch.
     dev = e2.device
     out = torch.empty(B, N, P + q, dtype=torch.float32, device=dev)
     norms = torch.empty(B, P, dtype=torch.float32, device=dev)
-    ws = _hip.workspace(lib.lo_probe_vectors_workspace_bytes(B, N, P), dev)
-    rc = lib.lo_probe_vectors_f32(_hip.ptr(Lx), Lx.stride(0), Lx.stride(1), Lx.stride(2), k, _hip.ptr(d2),
-                                  _hip.LO_DIAG_CONST if const else _hip.LO_DIAG_FULL, _hip.ptr(e13), _hip.ptr(e23),
-                                  _hip.ptr(iq3), q, B, N, P, _hip.ptr(out), _hip.ptr(norms), _hip.ptr(ws), ws.numel(),
-                                  _hip.stream_ptr(dev))
-    _hip.check(rc, "lo_probe_vectors_f32")
+    _launch("lo_probe_vectors_f32", dev, Lx, Lx.stride(0), Lx.stride(1), Lx.stride(2), k, d2,
+            _hip.LO_DIAG_CONST if const else _hip.LO_DIAG_FULL, e13, e23, iq3, q, B, N, P, out, norms,
+            ws_bytes=lib.lo_probe_vectors_workspace_bytes(B, N, P))
     return out.reshape(*bs, N, P + q), norms.reshape(*bs, 1, P)
 
 
@@ -951,7 +906,6 @@ def iql_backward_factors(solves: torch.Tensor, pp: torch.Tensor, norms: torch.Te
     in one pass.  solves [*batch, N, P + q]; pp [*batch, N, >= P] the preconditioner applied to the NORMALISED probes;
     norms [*batch, 1, P]; g_ld [*batch]; g_iq [*batch, q] or None.  Returns (left, right [*batch, N, P + q], pre_left,
     pre_right [*batch, N, P])."""
-    lib = _hip.load()
     bs = solves.shape[:-2]
     N, c = solves.shape[-2:]
     q = c - P
@@ -964,14 +918,21 @@ def iql_backward_factors(solves: torch.Tensor, pp: torch.Tensor, norms: torch.Te
     left, right = torch.empty_like(s3), torch.empty_like(s3)
     pre_left = torch.empty(B, N, P, dtype=torch.float32, device=s3.device)
     pre_right = torch.empty_like(pre_left)
-    rc = lib.lo_iql_backward_factors_f32(_hip.ptr(s3), _hip.ptr(p3), p3.shape[-1], _hip.ptr(n2), _hip.ptr(gl), _hip.ptr(gq),
-                                         1.0 / P, B, N, P, q, _hip.ptr(left), _hip.ptr(right), _hip.ptr(pre_left),
-                                         _hip.ptr(pre_right), _hip.stream_ptr(s3.device))
-    _hip.check(rc, "lo_iql_backward_factors_f32")
+    _launch("lo_iql_backward_factors_f32", s3.device, s3, p3, p3.shape[-1], n2, gl, gq, 1.0 / P, B, N, P, q, left, right,
+            pre_left, pre_right)
     return (left.reshape(*bs, N, c), right.reshape(*bs, N, c), pre_left.reshape(*bs, N, P), pre_right.reshape(*bs, N, P))
 
 
 # ------------------------------------------------------------------------------------------------
+def _pivchol_out(L_rows: torch.Tensor, perm: torch.Tensor, m: int, batch_shape, contiguous: bool):
+    """(L [*batch, N, m], permutation [*batch, N]) from the [B, max_rank, N] rows the kernels wrote and the m pivots taken."""
+    N = L_rows.shape[-1]
+    L = L_rows[:, :m, :].mT  # _pivoted_cholesky.py:105
+    if contiguous:
+        L = L.contiguous()
+    return L.reshape(*batch_shape, N, m), perm.reshape(*batch_shape, N)
+
+
 def pivoted_cholesky(desc: OperatorDescriptor, rank: int, error_tol: float = 1e-3, contiguous: bool = True):
     """lo_pivoted_cholesky_f32: PivotedCholesky.forward (functions/_pivoted_cholesky.py:14-105) of the
     NON-diagonal part of `desc`.  Returns (L [*batch, N, m], permutation [*batch, N] int64).
@@ -984,16 +945,10 @@ def pivoted_cholesky(desc: OperatorDescriptor, rank: int, error_tol: float = 1e-
     L_rows = torch.empty(B, max_rank, N, dtype=torch.float32, device=dev)
     perm = torch.empty(B, N, dtype=torch.int64, device=dev)
     s = desc.without_diag().c_struct()
-    ws = _hip.workspace(lib.lo_pivoted_cholesky_workspace_bytes(C.byref(s), max_rank), dev)
     m = C.c_int32(0)
-    _hip.check(lib.lo_pivoted_cholesky_f32(C.byref(s), max_rank, float(error_tol), _hip.ptr(L_rows), _hip.ptr(perm),
-                                           C.byref(m), _hip.ptr(ws), ws.numel(), _hip.stream_ptr(dev)),
-               "lo_pivoted_cholesky_f32")
-    L = L_rows[:, : m.value, :].mT  # _pivoted_cholesky.py:105
-    if contiguous:
-        L = L.contiguous()
-    bs = tuple(desc.batch_shape)
-    return L.reshape(*bs, N, m.value), perm.reshape(*bs, N)
+    _launch("lo_pivoted_cholesky_f32", dev, C.byref(s), max_rank, float(error_tol), L_rows, perm, C.byref(m),
+            ws_bytes=lib.lo_pivoted_cholesky_workspace_bytes(C.byref(s), max_rank))
+    return _pivchol_out(L_rows, perm, m.value, tuple(desc.batch_shape), contiguous)
 
 
 def pivoted_cholesky_generic(diag: torch.Tensor, row_fetch: Callable, rank: int, error_tol: float = 1e-3,
@@ -1026,23 +981,11 @@ def pivoted_cholesky_generic(diag: torch.Tensor, row_fetch: Callable, rank: int,
             err.append(e)
             return 1
 
-    c_cb = _hip.ROWFETCH_CB(cb)
     m = C.c_int32(0)
-    if f64:
-        ws = _hip.workspace(lib.lo_pivoted_cholesky_cb_f64_workspace_bytes(B, N, max_rank), dev)
-        rc = lib.lo_pivoted_cholesky_cb_f64(B, N, _hip.ptr(d2), c_cb, None, max_rank, float(error_tol), _hip.ptr(L_rows),
-                                            _hip.ptr(perm), C.byref(m), _hip.ptr(ws), ws.numel(), _hip.stream_ptr(dev))
-    else:
-        ws = _hip.workspace(lib.lo_pivoted_cholesky_cb_workspace_bytes(B, N, max_rank), dev)
-        rc = lib.lo_pivoted_cholesky_cb_f32(B, N, _hip.ptr(d2), c_cb, None, max_rank, float(error_tol), _hip.ptr(L_rows),
-                                            _hip.ptr(perm), C.byref(m), _hip.ptr(ws), ws.numel(), _hip.stream_ptr(dev))
-    if err:
-        raise err[0]
-    _hip.check(rc, "lo_pivoted_cholesky_cb_f64" if f64 else "lo_pivoted_cholesky_cb_f32")
-    L = L_rows[:, : m.value, :].mT
-    if contiguous:
-        L = L.contiguous()
-    return L.reshape(*bs, N, m.value), perm.reshape(*bs, N)
+    ws_bytes = (lib.lo_pivoted_cholesky_cb_f64_workspace_bytes if f64 else lib.lo_pivoted_cholesky_cb_workspace_bytes)
+    _launch("lo_pivoted_cholesky_cb_f64" if f64 else "lo_pivoted_cholesky_cb_f32", dev, B, N, d2, _hip.ROWFETCH_CB(cb),
+            None, max_rank, float(error_tol), L_rows, perm, C.byref(m), ws_bytes=ws_bytes(B, N, max_rank), errors=(err,))
+    return _pivchol_out(L_rows, perm, m.value, bs, contiguous)
 
 
 def _root_form(lib, root, perm, L3, d, constant_diag, B, N, k, dev) -> WoodburyPreconditioner:
@@ -1053,32 +996,16 @@ def _root_form(lib, root, perm, L3, d, constant_diag, B, N, k, dev) -> WoodburyP
     F = torch.empty(B, ld, ld, dtype=torch.float32, device=dev)
     EF = torch.empty_like(F)
     E = torch.empty_like(F)
-    if constant_diag:
-        d2 = d.contiguous().reshape(-1)
-        dinv = torch.empty(B, dtype=torch.float32, device=dev)
-        mode = _hip.LO_DIAG_CONST
-    else:
-        d2 = _flat(d, 1)
-        dinv = torch.empty(B, N, dtype=torch.float32, device=dev)
-        mode = _hip.LO_DIAG_FULL
+    d2, mode, dinv = _diag_operand(d, B, N, constant_diag, want_dinv=True)
     logdet = torch.empty(B, dtype=torch.float32, device=dev)
-    sm, sr, sc = L3.stride()
-    if B == 1:
-        sm = 0
     if R % 4 == 0 and C3.data_ptr() % 16 == 0 and not os.environ.get("LO_NO_RSPACE_FORM"):
         # with the R-space form: E and C^T C on the fp64 matrix cores (the fp32 F / EF / E are roundings of the same)
         RS = torch.empty(B, 6, ld, ld, dtype=torch.float64, device=dev)
-        ws = _hip.workspace(lib.lo_precond_root_form_rs_workspace_bytes(B, N, R), dev)
-        _hip.check(lib.lo_precond_root_form_rs_f32(_hip.ptr(C3), R, _hip.ptr(d2), mode, _hip.ptr(L3), sm, sr, sc,
-                                                   _hip.ptr(p2), B, N, k, ld, _hip.ptr(F), _hip.ptr(EF), _hip.ptr(E),
-                                                   _hip.ptr(dinv), _hip.ptr(logdet), _hip.ptr(RS), _hip.ptr(ws),
-                                                   ws.numel(), _hip.stream_ptr(dev)), "lo_precond_root_form_rs_f32")
+        _launch("lo_precond_root_form_rs_f32", dev, C3, R, d2, mode, L3, *_row_strides(L3), p2, B, N, k, ld, F, EF, E,
+                dinv, logdet, RS, ws_bytes=lib.lo_precond_root_form_rs_workspace_bytes(B, N, R))
         return WoodburyPreconditioner(None, dinv, k, constant_diag, logdet, F, EF, E, RS, rs_rank=R)
-    ws = _hip.workspace(lib.lo_precond_root_form_workspace_bytes(B, N, R), dev)
-    _hip.check(lib.lo_precond_root_form_f32(_hip.ptr(C3), R, _hip.ptr(d2), mode, _hip.ptr(L3), sm, sr, sc, _hip.ptr(p2),
-                                            B, N, k, ld, _hip.ptr(F), _hip.ptr(EF), _hip.ptr(E), _hip.ptr(dinv),
-                                            _hip.ptr(logdet), _hip.ptr(ws), ws.numel(), _hip.stream_ptr(dev)),
-               "lo_precond_root_form_f32")
+    _launch("lo_precond_root_form_f32", dev, C3, R, d2, mode, L3, *_row_strides(L3), p2, B, N, k, ld, F, EF, E, dinv,
+            logdet, ws_bytes=lib.lo_precond_root_form_workspace_bytes(B, N, R))
     return WoodburyPreconditioner(None, dinv, k, constant_diag, logdet, F, EF, E)
 
 
@@ -1097,14 +1024,9 @@ def _kron_root(lib, desc: "OperatorDescriptor", perm, L3, k, dev):
     kF = torch.empty(B, 16, 16, dtype=torch.float32, device=dev)
     kappa = torch.empty(B, dtype=torch.float32, device=dev)
     p2 = _flat(perm, 1)
-    ws = _hip.workspace(lib.lo_precond_kron_root_workspace_bytes(B), dev)
-    sm, sr, sc = L3.stride()
-    if B == 1:
-        sm = 0
     s = desc.c_struct()
-    _hip.check(lib.lo_precond_kron_root_f32(C.byref(s), _hip.ptr(L3), sm, sr, sc, _hip.ptr(p2), k, _hip.ptr(ka),
-                                            _hip.ptr(kb), _hip.ptr(kF), _hip.ptr(kappa), _hip.ptr(ws), ws.numel(),
-                                            _hip.stream_ptr(dev)), "lo_precond_kron_root_f32")
+    _launch("lo_precond_kron_root_f32", dev, C.byref(s), L3, *_row_strides(L3), p2, k, ka, kb, kF, kappa,
+            ws_bytes=lib.lo_precond_kron_root_workspace_bytes(B))
     worst = float(kappa.max())
     if not (worst < KRON_ROOT_MAX_KAPPA):  # (also NaN)
         return None, worst
@@ -1147,25 +1069,10 @@ def precond_build(L: torch.Tensor, d: torch.Tensor, constant_diag: bool, root: O
         return full
     ldq = padded_rank(k)
     Q = torch.empty(B, N, ldq, dtype=torch.float32, device=dev)
-    if constant_diag:
-        d2 = d.contiguous().reshape(-1)
-        assert d2.numel() == B
-        dinv = torch.empty(B, dtype=torch.float32, device=dev)
-        mode = _hip.LO_DIAG_CONST
-    else:
-        d2 = _flat(d, 1)
-        assert d2.shape == (B, N)
-        dinv = torch.empty(B, N, dtype=torch.float32, device=dev)
-        mode = _hip.LO_DIAG_FULL
+    d2, mode, dinv = _diag_operand(d, B, N, constant_diag, want_dinv=True)
     logdet = torch.empty(B, dtype=torch.float32, device=dev)
-    ws = _hip.workspace(lib.lo_precond_build_workspace_bytes(B, N, k), dev)
-    sm, sr, sc = L3.stride()
-    if B == 1:
-        sm = 0
-    _hip.check(lib.lo_precond_build_strided_f32(_hip.ptr(L3), sm, sr, sc, _hip.ptr(d2), mode, B, N, k, _hip.ptr(Q),
-                                                _hip.ptr(dinv), _hip.ptr(logdet), _hip.ptr(ws), ws.numel(),
-                                                _hip.stream_ptr(dev)),
-               "lo_precond_build_strided_f32")
+    _launch("lo_precond_build_strided_f32", dev, L3, *_row_strides(L3), d2, mode, B, N, k, Q, dinv, logdet,
+            ws_bytes=lib.lo_precond_build_workspace_bytes(B, N, k))
     out = WoodburyPreconditioner(Q, dinv, k, constant_diag, logdet.reshape(L.shape[:-2]))
     if (kron is not None and perm is not None and constant_diag and kron.kind == _hip.LO_OP_KRON_DIAG
             and kron.diag_mode == _hip.LO_DIAG_CONST and kron.B == B and kron.N == N and 1 <= k <= 16
@@ -1187,10 +1094,8 @@ def tridiag_eigh_slq(t_mat: torch.Tensor, n: int, want_evecs: bool = False, want
     evals = torch.empty(P * B, T, dtype=torch.float32, device=dev)
     evecs = torch.empty(P * B, T, T, dtype=torch.float32, device=dev) if want_evecs else None
     logdet = torch.empty(B, dtype=torch.float32, device=dev) if want_logdet else None
-    ws = _hip.workspace(lib.lo_tridiag_eigh_slq_workspace_bytes(P, B), dev)
-    _hip.check(lib.lo_tridiag_eigh_slq_f32(_hip.ptr(t3), P, B, T, int(n), _hip.ptr(evals), _hip.ptr(evecs),
-                                           _hip.ptr(logdet), _hip.ptr(ws), ws.numel(), _hip.stream_ptr(dev)),
-               "lo_tridiag_eigh_slq_f32")
+    _launch("lo_tridiag_eigh_slq_f32", dev, t3, P, B, T, int(n), evals, evecs, logdet,
+            ws_bytes=lib.lo_tridiag_eigh_slq_workspace_bytes(P, B))
     return (evals.reshape(P, *batch, T), None if evecs is None else evecs.reshape(P, *batch, T, T),
             None if logdet is None else logdet.reshape(batch))
 
@@ -1208,38 +1113,40 @@ def lanczos_tridiag(desc: Optional[OperatorDescriptor], init_vecs: torch.Tensor,
     v3 = _flat(init_vecs, 2)
     B = v3.shape[0]
     dev = init_vecs.device
-    if desc is None:
-        s = _hip.OpDesc()
-        s.kind, s.diag_mode, s.B, s.N, s.R, s.n2 = _hip.LO_OP_CALLBACK, _hip.LO_DIAG_NONE, B, N, 0, 0
-
-        def mv(v):
-            return matvec_closure(v.reshape(*batch, N, P))
-
-        cb, err = _wrap_closure(mv, dev)
-    else:
-        s = desc.c_struct()
-        cb, err = _hip.MATVEC_CB(), []
+    if desc is None and matvec_closure is None:
+        raise ValueError("need an operator descriptor or a matvec closure")
+    s = _callback_desc(B, N) if desc is None else desc.c_struct()
+    cb, err = _wrap_closure(matvec_closure, dev, batch) if desc is None else _NO_CLOSURE
     max_iter = int(max_iter)
-    q = torch.empty(max_iter, B, N, P, dtype=torch.float32, device=dev)
-    t = torch.empty(max_iter, max_iter, B, P, dtype=torch.float32, device=dev)
-    ws = _hip.workspace(lib.lo_lanczos_workspace_bytes(C.byref(s), P, max_iter), dev)
+    q, t = _lanczos_buffers(max_iter, v3)
     iters = C.c_int32(0)
-    rc = lib.lo_lanczos_tridiag_f32(C.byref(s), cb, None, _hip.ptr(v3), P, max_iter, float(tol), _hip.ptr(q),
-                                    _hip.ptr(t), C.byref(iters), _hip.ptr(ws), ws.numel(), _hip.stream_ptr(dev))
-    for e in err:
-        raise e
-    _hip.check(rc, "lo_lanczos_tridiag_f32")
+    _launch("lo_lanczos_tridiag_f32", dev, C.byref(s), cb, None, v3, P, max_iter, float(tol), q, t, C.byref(iters),
+            ws_bytes=lib.lo_lanczos_workspace_bytes(C.byref(s), P, max_iter), errors=(err,))
     k = iters.value
-    nb = len(batch)
-    t = t[:k, :k].reshape(k, k, *batch, P)
+    q_out = None
     if contiguous:
         q_out = torch.empty(P, *batch, N, k, dtype=torch.float32, device=dev)
         rc = lib.lo_lanczos_permute_f32(_hip.ptr(q), k, B, N, P, _hip.ptr(q_out), _hip.stream_ptr(dev))  # lanczos.py:154
         if rc == _hip.LO_ERR_UNSUPPORTED:
-            q_out = q[:k].reshape(k, *batch, N, P).permute(-1, *range(1, 1 + nb), -2, 0).contiguous()
+            q_out = q[:k].reshape(k, *batch, N, P).permute(-1, *range(1, 1 + len(batch)), -2, 0).contiguous()
         else:
             _hip.check(rc, "lo_lanczos_permute_f32")
-    else:
+    return _lanczos_out(q, t, k, batch, q_out)
+
+
+def _lanczos_buffers(max_iter: int, v3: torch.Tensor):
+    """The basis [max_iter, B, N, P] and the tridiagonals [max_iter, max_iter, B, P] as the step kernels write them."""
+    B, N, P = v3.shape
+    return (torch.empty(max_iter, B, N, P, dtype=v3.dtype, device=v3.device),
+            torch.empty(max_iter, max_iter, B, P, dtype=v3.dtype, device=v3.device))
+
+
+def _lanczos_out(q: torch.Tensor, t: torch.Tensor, k: int, batch, q_out: Optional[torch.Tensor] = None):
+    """(q_mat [P, *batch, N, k], t_mat [P, *batch, k, k]) of the reference (lanczos.py:151-161) from the buffers after k
+    steps; q_out: the basis already in the reference's memory layout."""
+    nb = len(batch)
+    N, P = q.shape[-2:]
+    if q_out is None:
         # the reference's q_mat [P, *batch, N, k] (lanczos.py:154) as a VIEW of the basis in the layout the step kernels
         # write it ([k, B, N, P]): same shape, same values, no 5 GB copy at the cfg3 shape.  The consumers on the path
         # (root_from_lanczos below) read this layout directly; anything else sees an ordinary strided tensor.
@@ -1247,7 +1154,7 @@ def lanczos_tridiag(desc: Optional[OperatorDescriptor], init_vecs: torch.Tensor,
         #  ADVICE r4)
         qk = q[:k] if k == q.shape[0] else q[:k].clone()
         q_out = qk.reshape(k, *batch, N, P).permute(-1, *range(1, 1 + nb), -2, 0)
-    t_out = t.permute(-1, *range(2, 2 + nb), 0, 1).contiguous()  # :156
+    t_out = t[:k, :k].reshape(k, k, *batch, P).permute(-1, *range(2, 2 + nb), 0, 1).contiguous()  # :156
     if P == 1:  # squeeze_(0) (:159-161) only acts on a size-1 leading dim
         q_out, t_out = q_out[0], t_out[0]
     return q_out, t_out
@@ -1265,44 +1172,14 @@ def lanczos_tridiag_f64(A: Optional[torch.Tensor], diag: Optional[torch.Tensor],
     v3 = _flat(init_vecs, 2)
     B = v3.shape[0]
     dev = init_vecs.device
-    A3 = d2 = None
-    err = []
-    cb = _hip.MATVEC_CB()
-    if A is not None:
-        A3 = A.expand(*batch, N, N).reshape(B, N, N).contiguous()
-        d2 = None if diag is None else diag.expand(*batch, N).reshape(B, N).contiguous()
-    elif matvec_closure is None:
-        raise ValueError("need a dense fp64 operator or a matvec closure")
-    else:
-        def _cb(user, v_ptr, y_ptr, B_, N_, c_, stream):
-            try:
-                v = _hip.as_tensor(v_ptr, (B_, N_, c_), dev, "<f8")
-                y = _hip.as_tensor(y_ptr, (B_, N_, c_), dev, "<f8")
-                y.copy_(matvec_closure(v.reshape(*batch, N_, c_)).reshape(B_, N_, c_))
-                return 0
-            except BaseException as e:  # noqa: BLE001 -- must not unwind through C
-                err.append(e)
-                return 1
-
-        cb = _hip.MATVEC_CB(_cb)
+    A3, d2 = _dense_f64(A, diag, matvec_closure, batch, B, N)
+    cb, err = _wrap_closure(matvec_closure, dev, batch, "<f8") if A3 is None else _NO_CLOSURE
     max_iter = int(max_iter)
-    q = torch.empty(max_iter, B, N, P, dtype=torch.float64, device=dev)
-    t = torch.empty(max_iter, max_iter, B, P, dtype=torch.float64, device=dev)
-    ws = _hip.workspace(lib.lo_lanczos_f64_workspace_bytes(B, N, P, max_iter), dev)
+    q, t = _lanczos_buffers(max_iter, v3)
     iters = C.c_int32(0)
-    rc = lib.lo_lanczos_tridiag_f64(_hip.ptr(A3), _hip.ptr(d2), cb, None, _hip.ptr(v3), B, N, P, max_iter, float(tol),
-                                    _hip.ptr(q), _hip.ptr(t), C.byref(iters), _hip.ptr(ws), ws.numel(),
-                                    _hip.stream_ptr(dev))
-    for e in err:
-        raise e
-    _hip.check(rc, "lo_lanczos_tridiag_f64")
-    k = iters.value
-    nb = len(batch)
-    q_out = (q[:k] if k == q.shape[0] else q[:k].clone()).reshape(k, *batch, N, P).permute(-1, *range(1, 1 + nb), -2, 0)
-    t_out = t[:k, :k].reshape(k, k, *batch, P).permute(-1, *range(2, 2 + nb), 0, 1).contiguous()
-    if P == 1:
-        q_out, t_out = q_out[0], t_out[0]
-    return q_out, t_out
+    _launch("lo_lanczos_tridiag_f64", dev, A3, d2, cb, None, v3, B, N, P, max_iter, float(tol), q, t, C.byref(iters),
+            ws_bytes=lib.lo_lanczos_f64_workspace_bytes(B, N, P, max_iter), errors=(err,))
+    return _lanczos_out(q, t, iters.value, batch)
 
 
 def _native_lanczos_layout(q_mat: torch.Tensor):
@@ -1367,9 +1244,7 @@ def root_from_lanczos(q_mat: torch.Tensor, evecs: torch.Tensor, evals: torch.Ten
     qv = torch.empty_like(q3)
     root = torch.empty_like(q3) if want_root else None
     inv = torch.empty_like(q3) if want_inverse else None
-    _hip.check(lib.lo_root_from_lanczos_f32(_hip.ptr(q3), _hip.ptr(v3), _hip.ptr(e3), PB, N, k, _hip.ptr(qv),
-                                            _hip.ptr(root), _hip.ptr(inv), _hip.stream_ptr(dev)),
-               "lo_root_from_lanczos_f32")
+    _launch("lo_root_from_lanczos_f32", dev, q3, v3, e3, PB, N, k, qv, root, inv)
     shp = (*lead, N, k)
     return qv.reshape(shp), (None if root is None else root.reshape(shp)), (None if inv is None else inv.reshape(shp))
 
@@ -1394,21 +1269,18 @@ def _is_f64(*ts):
 
 def bilinear_dense(left_vecs: torch.Tensor, right_vecs: torch.Tensor, batch_shape=()):
     """lo_bilinear_dense_f32: U V^T [*batch, N, N] (dense_linear_operator.py:69-71)."""
-    lib = _hip.load()
     U, V, bs = _uv(left_vecs, right_vecs, batch_shape)
     B, N, D = U.shape
     if _is_f64(U, V):
         return torch.matmul(U, V.mT).reshape(*bs, N, N)
     out = torch.empty(B, N, N, dtype=torch.float32, device=U.device)
-    _hip.check(lib.lo_bilinear_dense_f32(_hip.ptr(U), _hip.ptr(V), B, N, D, _hip.ptr(out), _hip.stream_ptr(U.device)),
-               "lo_bilinear_dense_f32")
+    _launch("lo_bilinear_dense_f32", U.device, U, V, B, N, D, out)
     return out.reshape(*bs, N, N)
 
 
 def bilinear_diag(left_vecs: torch.Tensor, right_vecs: torch.Tensor, batch_shape=(), constant: bool = False):
     """lo_bilinear_diag_f32: sum_d U o V [*batch, N], or its sum over N as [*batch, 1] for a constant diagonal
     (diag_linear_operator.py:37-45, :337-344)."""
-    lib = _hip.load()
     U, V, bs = _uv(left_vecs, right_vecs, batch_shape)
     B, N, D = U.shape
     dev = U.device
@@ -1417,9 +1289,7 @@ def bilinear_diag(left_vecs: torch.Tensor, right_vecs: torch.Tensor, batch_shape
         return rd.sum(-1).reshape(*bs, 1) if constant else rd.reshape(*bs, N)
     out = torch.empty(B if constant else B * N, dtype=torch.float32, device=dev)
     ws = _hip.workspace(4 * B * N + 256, dev) if constant else None
-    _hip.check(lib.lo_bilinear_diag_f32(_hip.ptr(U), _hip.ptr(V), B, N, D, 1 if constant else 0, _hip.ptr(out),
-                                        _hip.ptr(ws), 0 if ws is None else ws.numel(), _hip.stream_ptr(dev)),
-               "lo_bilinear_diag_f32")
+    _launch("lo_bilinear_diag_f32", dev, U, V, B, N, D, 1 if constant else 0, out, ws, 0 if ws is None else ws.numel())
     return out.reshape(*bs, 1) if constant else out.reshape(*bs, N)
 
 
@@ -1449,10 +1319,8 @@ def bilinear_root(root: torch.Tensor, left_vecs: torch.Tensor, right_vecs: torch
         Dc = Uc.shape[-1]
         o = torch.empty(B, N, R, dtype=torch.float32, device=dev)
         rd = torch.empty(B, N, dtype=torch.float32, device=dev) if with_rowdot else None
-        ws = _hip.workspace(lib.lo_bilinear_root_workspace_bytes(B, N, R, Dc), dev)
-        _hip.check(lib.lo_bilinear_root_f32(_hip.ptr(Cm), _hip.ptr(Uc), _hip.ptr(Vc), B, N, R, Dc, _hip.ptr(o),
-                                            _hip.ptr(rd), _hip.ptr(ws), ws.numel(), _hip.stream_ptr(dev)),
-                   "lo_bilinear_root_f32")
+        _launch("lo_bilinear_root_f32", dev, Cm, Uc, Vc, B, N, R, Dc, o, rd,
+                ws_bytes=lib.lo_bilinear_root_workspace_bytes(B, N, R, Dc))
         out = o if out is None else out.add_(o)
         if with_rowdot:
             rowdot = rd if rowdot is None else rowdot.add_(rd)
@@ -1503,10 +1371,8 @@ def bilinear_kron(K1: torch.Tensor, K2: torch.Tensor, left_vecs: torch.Tensor, r
     dev = U.device
     d1 = torch.empty(B, n1, n1, dtype=torch.float32, device=dev)
     d2 = torch.empty(B, n2, n2, dtype=torch.float32, device=dev)
-    ws = _hip.workspace(lib.lo_bilinear_kron_workspace_bytes(B, n1, n2, D), dev)
-    _hip.check(lib.lo_bilinear_kron_f32(_hip.ptr(A1), _hip.ptr(A2), _hip.ptr(U), _hip.ptr(V), B, n1, n2, D, _hip.ptr(d1),
-                                        _hip.ptr(d2), _hip.ptr(ws), ws.numel(), _hip.stream_ptr(dev)),
-               "lo_bilinear_kron_f32")
+    _launch("lo_bilinear_kron_f32", dev, A1, A2, U, V, B, n1, n2, D, d1, d2,
+            ws_bytes=lib.lo_bilinear_kron_workspace_bytes(B, n1, n2, D))
     return d1.reshape(*bs, n1, n1), d2.reshape(*bs, n2, n2)
 
 
@@ -1520,14 +1386,14 @@ def resident_status() -> dict:
     """lo_resident_status_get: the gate of the resident kernels -- hand-off timeouts seen by this process, calls still
     to be served by the streaming engines (cool-down), length of the next cool-down, re-arms so far."""
     out = _hip.ResidentStatus()
-    _hip.check(_hip.load().lo_resident_status_get(C.byref(out)), "lo_resident_status_get")
+    _hip.call("lo_resident_status_get", C.byref(out))
     return {n: int(getattr(out, n)) for n, _ in _hip.ResidentStatus._fields_}
 
 
 def inject_resident_timeouts(n: int):
     """lo_resident_inject_timeouts: the next n resident CG launches are treated as timed out (the solve is redone on
     the streaming engine and a cool-down starts) -- tests and `bench.py --inject-timeouts`."""
-    _hip.check(_hip.load().lo_resident_inject_timeouts(int(n)), "lo_resident_inject_timeouts")
+    _hip.call("lo_resident_inject_timeouts", int(n))
 
 
 def resident_handoff_debug(force_clear: bool = False, next_tag: int = -1, next_epoch: int = -1) -> dict:
@@ -1535,15 +1401,13 @@ def resident_handoff_debug(force_clear: bool = False, next_tag: int = -1, next_e
     current device -- optionally make the next launch clear it first, or replace the tag / epoch counters (tests of the
     wrap-around); returns the counters and how many launches / clears the buffer has seen."""
     out = (C.c_uint32 * 4)()
-    _hip.check(_hip.load().lo_resident_handoff_debug(1 if force_clear else 0, int(next_tag), int(next_epoch), out),
-               "lo_resident_handoff_debug")
+    _hip.call("lo_resident_handoff_debug", 1 if force_clear else 0, int(next_tag), int(next_epoch), out)
     return {"next_tag": int(out[0]), "next_epoch": int(out[1]), "clears": int(out[2]), "launches": int(out[3])}
 
 
 def peer_gather_set(bufs=(), member_offset: int = 0) -> None:
     """lo_peer_gather_set (prototype): up to seven [B_total, N] fp32 buffers the resident single-column solve writes its
     solutions into next to its own output -- the gather of SURVEY 8(e) as peer writes.  () removes them."""
-    lib = _hip.load()
     n = len(bufs)
     arr = (C.c_void_p * max(n, 1))(*[b.data_ptr() for b in bufs])
-    _hip.check(lib.lo_peer_gather_set(arr, n, int(member_offset)), "lo_peer_gather_set")
+    _hip.call("lo_peer_gather_set", arr, n, int(member_offset))

@@ -63,6 +63,69 @@ def test_abi_library_loads_and_exports_every_declared_symbol():
     assert set(_hip.EXPORTS) == set(declared)
 
 
+STRUCT_MIRRORS = {  # struct of include/lo_amd.h -> its ctypes mirror
+    "lo_op_desc": _hip.OpDesc, "lo_interp_desc": _hip.InterpDesc, "lo_precond_desc": _hip.PrecondDesc,
+    "lo_cg_params": _hip.CgParams, "lo_cg_info": _hip.CgInfo, "lo_cg_plan": _hip.CgPlan,
+    "lo_fused_info": _hip.FusedInfo, "lo_resident_status": _hip.ResidentStatus,
+    "lo_minres_params": _hip.MinresParams, "lo_minres_info": _hip.MinresInfo,
+    "lo_cg_params_f64": _hip.CgParamsF64, "lo_cg_info_f64": _hip.CgInfoF64,
+    "lo_minres_params_f64": _hip.MinresParamsF64, "lo_minres_info_f64": _hip.MinresInfoF64,
+}
+# binding field -> the header's member(s) where the names differ: the binding has one slot for the anonymous union
+FIELD_NAMES = {("lo_op_desc", "terms"): ("terms", "interp")}
+
+
+def test_binding_mirrors_the_constants_and_struct_layouts_of_the_header(tmp_path):
+    """The ctypes side of the ABI is written by hand: every LO_* constant it carries has the header's value, the engine /
+    stream name tables have one key per header value, and every mirrored struct has the size, field offsets and field
+    sizes the host C compiler gives include/lo_amd.h (a probe program generated here)."""
+    import shutil
+    import subprocess
+
+    inc = os.path.join(ROOT, "include")
+    hdr = open(os.path.join(inc, "lo_amd.h")).read()
+    defines = {m.group(1): int(m.group(2)) for m in re.finditer(r"^#define (LO_[A-Z0-9_]+)\s+\(?(-?\d+)\)?", hdr, re.M)}
+    mirrored = {n: v for n, v in vars(_hip).items() if n.startswith("LO_") and isinstance(v, int)}
+    assert len(mirrored) >= 19
+    assert {n: defines.get(n) for n in mirrored} == mirrored
+    for n in defines:  # the families the binding dispatches on are mirrored completely
+        if n.startswith(("LO_OP_", "LO_DIAG_", "LO_FUSED_")):
+            assert n in mirrored, f"{n} of include/lo_amd.h has no mirror in _hip.py"
+    errors = {v for n, v in defines.items() if n.startswith("LO_ERR_")}
+    assert set(_hip._ERR) == errors and len(errors) == 4 and _hip.LO_ERR_UNSUPPORTED in errors
+    for prefix, names in (("LO_ENGINE_", _hip.ENGINE_NAMES), ("LO_STREAM_", _hip.STREAM_PRE_NAMES)):
+        values = [v for n, v in defines.items() if n.startswith(prefix)]
+        assert len(values) >= 4 and len(set(values)) == len(values)
+        assert sorted(names) == sorted(values), f"{prefix}* of the header: {sorted(values)}, binding: {sorted(names)}"
+
+    assert set(re.findall(r"typedef struct (lo_[a-z0-9_]+)", hdr)) == set(STRUCT_MIRRORS)
+    lines, want = [], {}
+    for cname, cls in STRUCT_MIRRORS.items():
+        lines.append(f'  printf("{cname} %zu\\n", sizeof({cname}));')
+        want[cname] = ctypes.sizeof(cls)
+        assert len({f[0] for f in cls._fields_}) == len(cls._fields_)
+        for field, _ in cls._fields_:
+            for member in FIELD_NAMES.get((cname, field), (field,)):
+                lines.append(f'  printf("{cname}.{member} %zu %zu\\n", offsetof({cname}, {member}), '
+                             f'sizeof((({cname}*)0)->{member}));')
+                want[f"{cname}.{member}"] = (getattr(cls, field).offset, getattr(cls, field).size)
+    src = tmp_path / "layout_probe.c"
+    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "lo_amd.h"\nint main(void) {\n'
+                   + "\n".join(lines) + "\n  return 0;\n}\n")
+    exe = tmp_path / "layout_probe"
+    cc = shutil.which("gcc") or shutil.which("cc")
+    assert cc, "the layout probe needs the host C compiler (the one the oracle build uses)"
+    p = subprocess.run([cc, "-std=c11", "-Wall", "-I", inc, str(src), "-o", str(exe)], capture_output=True, text=True)
+    assert p.returncode == 0, p.stderr[-3000:]
+    got = {}
+    for line in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.splitlines():
+        key, *nums = line.split()
+        got[key] = int(nums[0]) if len(nums) == 1 else (int(nums[0]), int(nums[1]))
+    assert got["lo_op_desc"] == 80 and got["lo_precond_desc"] == 104 and got["lo_cg_params"] == 56
+    bad = {k: (got.get(k), v) for k, v in want.items() if got.get(k) != v}
+    assert not bad, f"(header, binding) size or (offset, size) differ: {bad}"
+
+
 def test_class_relationships_and_add_routing():
     # isinstance relations are part of the contract (SURVEY 8(b))
     assert issubclass(AddedDiagLinearOperator, SumLinearOperator)
