@@ -680,6 +680,25 @@ int lo_hadamard_bilinear_f32(const float* F, const float* G, const float* U, con
                              int64_t p, int64_t q, int64_t S, float* dF, float* dG, void* ws, size_t ws_bytes,
                              void* stream);
 
+/* ---- exact small-N path: batched Cholesky and triangular solves (ABI 18; csrc/lo_chol.hip) -------------------------
+ * fp32, contiguous row-major, N <= 1024 (larger: LO_ERR_UNSUPPORTED), stream-ordered; fixed-order sums, no atomics: a
+ * member's result does not depend on the batch around it and repeats bit for bit.
+ *   lo_cholesky_f32        A [B, N, N] (lower triangle read) -> L [B, N, N] with A = L L^T, strict upper triangle
+ *                          zeroed; info [B] int32: 0, or the 1-based order of the first leading minor whose pivot is
+ *                          not > 0 (NaN included; that member's L is unspecified, the others are untouched);
+ *                          logdet [B] double = 2 sum log L_ii, or NULL.
+ *   lo_tri_solve_f32       out [B, N, c] = M^-1 rhs, M = T or T^T (transpose) of the lower (upper = 0: the lower
+ *                          triangle of T is read) or upper factor T [B, N, N]; sumsq [B, c] = sum_i out_ic^2, or NULL.
+ *   lo_cholesky_solve_f32  out = (T T^T)^-1 rhs for a lower factor, (T^T T)^-1 rhs for an upper one, one launch.
+ * out may alias rhs.                                                                                                  */
+size_t lo_cholesky_workspace_bytes(int64_t B, int64_t N);
+int lo_cholesky_f32(const float* A, float* L, int32_t* info, double* logdet, int64_t B, int64_t N, void* ws,
+                    size_t ws_bytes, void* stream);
+int lo_tri_solve_f32(const float* T, const float* rhs, float* out, float* sumsq, int64_t B, int64_t N, int64_t c,
+                     int32_t upper, int32_t transpose, void* stream);
+int lo_cholesky_solve_f32(const float* T, const float* rhs, float* out, int64_t B, int64_t N, int64_t c, int32_t upper,
+                          void* stream);
+
 /* ---- measurement aid (no reference counterpart) ------------------------------------------------ */
 /* Opt-in HIP-event timing of every kernel launch of the library, recorded on the launch stream.
  * lo_prof_report writes "name count total_ms" lines into buf (returns the byte count) and resets.

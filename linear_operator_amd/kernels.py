@@ -1411,3 +1411,69 @@ def peer_gather_set(bufs=(), member_offset: int = 0) -> None:
     n = len(bufs)
     arr = (C.c_void_p * max(n, 1))(*[b.data_ptr() for b in bufs])
     _hip.call("lo_peer_gather_set", arr, n, int(member_offset))
+
+
+# ---------------------------------------------------------------- exact small-N path (csrc/lo_chol.hip)
+CHOLESKY_MAX_N = 1024  # what lo_cholesky_f32 / lo_tri_solve_f32 / lo_cholesky_solve_f32 take
+
+
+def _factor_and_rhs(L: torch.Tensor, rhs: torch.Tensor):
+    """A factor [*b, N, N] and right-hand sides [*b', N, c] (or [N]) broadcast to one batch and flattened."""
+    if L.dim() < 2 or L.shape[-1] != L.shape[-2]:
+        raise ValueError(f"expected square factors [..., N, N], got {tuple(L.shape)}")
+    is_vec = rhs.dim() == 1
+    cols = rhs.unsqueeze(-1) if is_vec else rhs
+    N, c = L.shape[-1], cols.shape[-1]
+    if cols.shape[-2] != N:
+        raise ValueError(f"right-hand side of {cols.shape[-2]} rows against a factor of {N}")
+    _hip.require_hip(L, cols)
+    bs = torch.broadcast_shapes(L.shape[:-2], cols.shape[:-2])
+    L3 = _flat(L.expand(*bs, N, N), 2)
+    R3 = _flat(cols.expand(*bs, N, c), 2)
+    return L3, R3, bs, is_vec
+
+
+def cholesky(A: torch.Tensor, want_logdet: bool = False):
+    """lo_cholesky_f32: (L, info[, logdet]) of A [*batch, N, N] = L L^T, N <= 1024; only the lower triangle of A is
+    read, the strict upper triangle of L is zero, info [*batch] int32 is 0 or the 1-based order of the first leading
+    minor whose pivot is not > 0 (that member's L is unspecified), logdet [*batch] float64 = 2 sum log L_ii."""
+    if A.dim() < 2 or A.shape[-1] != A.shape[-2]:
+        raise ValueError(f"expected square matrices [..., N, N], got {tuple(A.shape)}")
+    _hip.require_hip(A)
+    bs, N = A.shape[:-2], A.shape[-1]
+    A3 = _flat(A, 2)
+    B, dev = A3.shape[0], A.device
+    L = torch.empty_like(A3)
+    info = torch.empty(B, dtype=torch.int32, device=dev)
+    logdet = torch.empty(B, dtype=torch.float64, device=dev) if want_logdet else None
+    if B > 0 and N > 0:
+        _launch("lo_cholesky_f32", dev, A3, L, info, logdet, B, N,
+                ws_bytes=_hip.load().lo_cholesky_workspace_bytes(B, N))
+    out = (L.reshape(*bs, N, N), info.reshape(bs))
+    return out + (logdet.reshape(bs),) if want_logdet else out
+
+
+def triangular_solve(L: torch.Tensor, rhs: torch.Tensor, transpose: bool = False, want_sumsq: bool = False,
+                     upper: bool = False):
+    """lo_tri_solve_f32: L^-1 rhs, or L^-T rhs (`transpose`), for a lower (or `upper`) factor [*b, N, N], N <= 1024;
+    with `want_sumsq` also sum_i out_ic^2 [*batch, c] from the same launch (the inv_quad of a Cholesky factor)."""
+    L3, R3, bs, is_vec = _factor_and_rhs(L, rhs)
+    B, N, c = R3.shape
+    out = torch.empty_like(R3)
+    sumsq = torch.empty(B, c, dtype=torch.float32, device=R3.device) if want_sumsq else None
+    if out.numel():
+        _launch("lo_tri_solve_f32", R3.device, L3, R3, out, sumsq, B, N, c, int(bool(upper)), int(bool(transpose)))
+    out = out.reshape(*bs, N) if is_vec else out.reshape(*bs, N, c)
+    if not want_sumsq:
+        return out
+    return out, (sumsq.reshape(bs) if is_vec else sumsq.reshape(*bs, c))
+
+
+def cholesky_solve(L: torch.Tensor, rhs: torch.Tensor, upper: bool = False) -> torch.Tensor:
+    """lo_cholesky_solve_f32: (L L^T)^-1 rhs for a lower factor, (U^T U)^-1 rhs for an `upper` one, in one launch."""
+    L3, R3, bs, is_vec = _factor_and_rhs(L, rhs)
+    B, N, c = R3.shape
+    out = torch.empty_like(R3)
+    if out.numel():
+        _launch("lo_cholesky_solve_f32", R3.device, L3, R3, out, B, N, c, int(bool(upper)))
+    return out.reshape(*bs, N) if is_vec else out.reshape(*bs, N, c)

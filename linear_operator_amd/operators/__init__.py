@@ -16,6 +16,7 @@ from .root_linear_operator import LowRankRootLinearOperator, RootLinearOperator
 from .sum_linear_operator import PsdSumLinearOperator, SumLinearOperator
 from .toeplitz_linear_operator import ToeplitzLinearOperator
 from .triangular_linear_operator import TriangularLinearOperator
+from .chol_linear_operator import CholLinearOperator
 
 __all__ = [
     "LowRankRootAddedDiagLinearOperator", "KroneckerProductAddedDiagLinearOperator",
@@ -23,5 +24,5 @@ __all__ = [
     "DiagLinearOperator", "ConstantDiagLinearOperator", "IdentityLinearOperator", "KroneckerProductLinearOperator", "KroneckerProductDiagLinearOperator",
     "LinearOperatorRepresentationTree", "RootLinearOperator", "LowRankRootLinearOperator", "SumLinearOperator",
     "PsdSumLinearOperator", "TriangularLinearOperator", "MatmulLinearOperator", "InterpolatedLinearOperator",
-    "ToeplitzLinearOperator", "ConstantMulLinearOperator", "MulLinearOperator",
+    "ToeplitzLinearOperator", "ConstantMulLinearOperator", "MulLinearOperator", "CholLinearOperator",
 ]

@@ -784,7 +784,9 @@ class LinearOperator(object):
         if method == "cholesky":
             L = self.cholesky().to_dense()
             eye = torch.eye(L.shape[-2], device=L.device, dtype=L.dtype)
-            return RootLinearOperator(torch.linalg.solve_triangular(L, eye, upper=False).mT)
+            from ..functions._cholesky import substitute
+
+            return RootLinearOperator(substitute(L, eye, upper=False).mT)
         if method == "lanczos":
             if initial_vectors is not None:
                 if self.dim() == 2 and initial_vectors.dim() == 1:
@@ -862,7 +864,9 @@ class LinearOperator(object):
 class _TriangularFactor:
     """Minimal stand-in for CholLinearOperator(TriangularLinearOperator(L)) on the N <= max_cholesky_size
     branch (reference: chol_linear_operator.py:121, triangular_linear_operator.py:72-91): exact solves and
-    logdet through ATen.  Plumbing for cfg1, not part of the HIP hot path."""
+    logdet through the routed helpers of utils/cholesky.py and functions/_cholesky.py -- the native kernels of
+    csrc/lo_chol.hip for float32 HIP factors of at most 1024 rows, ATen otherwise.  The public class of the same algebra
+    is operators/chol_linear_operator.py; this one keeps the return conventions `LinearOperator.cholesky()` has had."""
 
     def __init__(self, factor: Tensor, upper: bool = False):
         self.factor = factor
@@ -883,8 +887,9 @@ class _TriangularFactor:
         if inv_quad_rhs is not None:
             is_vec = inv_quad_rhs.dim() == 1
             r = inv_quad_rhs.unsqueeze(-1) if is_vec else inv_quad_rhs
-            L = self.factor.mT if self.upper else self.factor
-            half = torch.linalg.solve_triangular(L, r, upper=False)
+            from ..functions._cholesky import substitute
+
+            half = substitute(self.factor, r, upper=self.upper, transpose=self.upper)  # L^-1 r, L = U^T for an upper factor
             inv_quad_term = (half ** 2).sum(-2)
             if reduce_inv_quad:
                 inv_quad_term = inv_quad_term.sum(-1)

@@ -3,9 +3,10 @@
 `DiagLinearOperator` derives from it, diag_linear_operator.py:16, and GPyTorch tests `isinstance(op,
 TriangularLinearOperator)`).
 
-Not on the iterative hot path: products and solves of a dense triangular factor are plain ATen calls
-(`torch.linalg.solve_triangular`), as in the reference.  Diagonal operators override everything with elementwise forms
-and never call this constructor with a dense tensor.
+Solves with a dense float32 HIP factor of at most 1024 rows are the native blocked substitution
+(lo_tri_solve_f32 / lo_cholesky_solve_f32 through functions/_cholesky.py; an upper factor or a transposed view goes
+through the kernel's flags, not a copy); CPU, float64 and larger factors take `torch.linalg.solve_triangular`.  Diagonal
+operators override everything with elementwise forms and never call this constructor with a dense tensor.
 """
 from __future__ import annotations
 
@@ -13,6 +14,13 @@ import torch
 from torch import Tensor
 
 from ._linear_operator import LinearOperator
+
+
+def _routed():
+    """functions/_cholesky.py (imported late: the functions package imports the operators)."""
+    from ..functions import _cholesky
+
+    return _cholesky
 
 
 class _TriangularLinearOperatorBase:
@@ -59,7 +67,7 @@ class TriangularLinearOperator(LinearOperator, _TriangularLinearOperatorBase):
         """T^-1 R by substitution (reference :160-191)."""
         is_vec = right_tensor.dim() == 1
         cols = right_tensor.unsqueeze(-1) if is_vec else right_tensor
-        res = torch.linalg.solve_triangular(self._tensor, cols, upper=self.upper)
+        res = _routed().substitute(self._tensor, cols, upper=self.upper)
         if is_vec:
             res = res.squeeze(-1)
         return res if left_tensor is None else left_tensor @ res
@@ -73,12 +81,13 @@ class TriangularLinearOperator(LinearOperator, _TriangularLinearOperatorBase):
         is_vec = rhs.dim() == 1
         cols = rhs.unsqueeze(-1) if is_vec else rhs
         t, t_is_upper = self._tensor, self.upper
-        if upper:  # (T^H T)^-1 = T^-1 T^-H
-            w = torch.linalg.solve_triangular(t.mT, cols, upper=not t_is_upper)
-            res = torch.linalg.solve_triangular(t, w, upper=t_is_upper)
+        chol_solve, native_ok, substitute = _routed().chol_solve, _routed().native_ok, _routed().substitute
+        if native_ok(t, cols, solve=True) and bool(upper) == t_is_upper and (t.is_contiguous() or not t.mT.is_contiguous()):
+            res = chol_solve(t, cols, upper=t_is_upper)  # both substitutions in one launch
+        elif upper:  # (T^H T)^-1 = T^-1 T^-H
+            res = substitute(t, substitute(t, cols, upper=t_is_upper, transpose=True), upper=t_is_upper)
         else:  # (T T^H)^-1 = T^-H T^-1
-            w = torch.linalg.solve_triangular(t, cols, upper=t_is_upper)
-            res = torch.linalg.solve_triangular(t.mT, w, upper=not t_is_upper)
+            res = substitute(t, substitute(t, cols, upper=t_is_upper), upper=t_is_upper, transpose=True)
         return res.squeeze(-1) if is_vec else res
 
     def inverse(self) -> "TriangularLinearOperator":
@@ -95,7 +104,7 @@ class TriangularLinearOperator(LinearOperator, _TriangularLinearOperatorBase):
         inv_quad_term = empty
         if inv_quad_rhs is not None:
             cols = inv_quad_rhs.unsqueeze(-1) if inv_quad_rhs.dim() == 1 else inv_quad_rhs
-            inv_quad_term = (cols * self.solve(cols)).sum(-2)
+            inv_quad_term = (cols * self.solve(cols)).sum(-2)  # (solve: the native substitution on the device)
             if reduce_inv_quad or inv_quad_rhs.dim() == 1:
                 inv_quad_term = inv_quad_term.sum(-1)
         logdet_term = empty

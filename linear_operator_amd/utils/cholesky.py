@@ -1,6 +1,7 @@
-"""psd_safe_cholesky: cholesky_ex with escalating jitter (reference: linear_operator/utils/cholesky.py:13-74).
-Plumbing for the N <= max_cholesky_size dispatch branch; runs on whatever device the tensor lives on through
-ATen (this is the reference's own exact path, not part of the HIP hot path)."""
+"""psd_safe_cholesky: cholesky_ex with escalating jitter (reference: linear_operator/utils/cholesky.py:13-74), the
+factorisation of the N <= max_cholesky_size dispatch branch.  float32 HIP tensors of at most 1024 rows go to the
+native batched kernels (csrc/lo_chol.hip through functions/_cholesky.py); CPU tensors, float64 and larger matrices
+take ATen, with the two workarounds below."""
 from __future__ import annotations
 
 import warnings
@@ -18,6 +19,10 @@ def _cholesky_ex(A):
     fine, so are one matrix and float64; tools/probe/chol_batched.py) and takes the context with it.  Those shapes are
     factorised as blockdiag(A, I) of 384 rows -- chol(blockdiag(A, I)) = blockdiag(chol(A), I), differentiable -- and
     the leading block is returned."""
+    from ..functions._cholesky import NativeCholesky, native_ok
+
+    if native_ok(A):
+        return NativeCholesky.apply(A)
     n = A.shape[-1]
     if A.is_cuda and A.dtype == torch.float32 and A.dim() > 2 and A.shape[:-2].numel() > 1 and 256 < n < 384:
         pad = 384 - n
@@ -33,7 +38,11 @@ def cholesky_solve(rhs, factor, upper=False):
     """torch.cholesky_solve.  Same stack, second hole: the BATCHED solve of ONE right-hand-side column against factors of
     more than 512 rows (float32 and float64; two or more columns, one matrix, and n <= 512 are fine --
     tools/probe/chol_solve_batched.py) ends in `unspecified launch failure`.  Such a column is solved twice side by side
-    and the first copy returned."""
+    and the first copy returned.  float32 HIP operands of at most 1024 rows take lo_cholesky_solve_f32 instead."""
+    from ..functions._cholesky import chol_solve, native_ok
+
+    if rhs.dim() >= 2 and native_ok(factor, rhs, solve=True):
+        return chol_solve(factor, rhs, upper=upper)
     if (rhs.is_cuda and rhs.dim() >= 2 and rhs.shape[-1] == 1 and factor.shape[-1] > 512
             and torch.broadcast_shapes(rhs.shape[:-2], factor.shape[:-2]).numel() > 1):
         return torch.cholesky_solve(rhs.expand(*rhs.shape[:-1], 2).contiguous(), factor, upper=upper)[..., :1]
