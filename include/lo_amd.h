@@ -699,6 +699,23 @@ int lo_tri_solve_f32(const float* T, const float* rhs, float* out, float* sumsq,
 int lo_cholesky_solve_f32(const float* T, const float* rhs, float* out, int64_t B, int64_t N, int64_t c, int32_t upper,
                           void* stream);
 
+/* ---- block operators over a batch of members (ABI 19; csrc/lo_block.hip) ---------------------------------------------
+ * `base` describes B = G * T members of size n x n, the block index fastest (member g * T + t); kind LO_OP_DENSE_DIAG
+ * or LO_OP_LOWRANK_DIAG with any diagonal mode (the + d o v term serves Block(AddedDiag(base, Diag))); other kinds
+ * return LO_ERR_UNSUPPORTED (the caller composes the product from the base operator's own), B % T != 0 LO_ERR_BADARG.
+ * The vectors are read and written in the layout of the block operator, c columns innermost, any c, n, T >= 1:
+ *   LO_BLOCK_DIAG         BlockDiagLinearOperator: the plain batched product (lo_matvec_f32 of the same arguments)
+ *   LO_BLOCK_INTERLEAVED  BlockInterleavedLinearOperator: no transposed copy of the vectors is made
+ *   LO_BLOCK_SUM          SumBatchLinearOperator: the sum over t runs inside the workgroup that owns the output rows,
+ *                         no [T, n, c] intermediate
+ * Plain launches, fixed-order sums, no float atomics: results repeat bit for bit.  y must not alias v.                 */
+#define LO_BLOCK_DIAG 0        /* v, y: [G, T*n, c], row t*n + i belongs to block t       */
+#define LO_BLOCK_INTERLEAVED 1 /* v, y: [G, n*T, c], row i*T + t belongs to block t       */
+#define LO_BLOCK_SUM 2         /* v, y: [G, n, c];  y = sum_t A_{g,t} v_g                 */
+size_t lo_block_mv_workspace_bytes(const lo_op_desc* base, int32_t layout, int64_t T, int64_t c);
+int lo_block_mv_f32(const lo_op_desc* base, int32_t layout, int64_t T, const float* v, float* y, int64_t c,
+                    void* ws, size_t ws_bytes, void* stream);
+
 /* ---- measurement aid (no reference counterpart) ------------------------------------------------ */
 /* Opt-in HIP-event timing of every kernel launch of the library, recorded on the launch stream.
  * lo_prof_report writes "name count total_ms" lines into buf (returns the byte count) and resets.

@@ -23,7 +23,8 @@ LO_TOEPLITZ_MAX_M = 16384
 LO_OP_HADAMARD_DIAG = 7
 LO_HADAMARD_MAX_RANK = 128
 LO_DIAG_NONE, LO_DIAG_FULL, LO_DIAG_CONST = 0, 1, 2
-ABI_VERSION = 18
+LO_BLOCK_DIAG, LO_BLOCK_INTERLEAVED, LO_BLOCK_SUM = 0, 1, 2
+ABI_VERSION = 19
 
 LO_ERR_UNSUPPORTED = -4
 LO_FUSED_OK, LO_FUSED_EARLY_STOP, LO_FUSED_CONTINUE, LO_FUSED_TIMEOUT = 0, 1, 2, 3
@@ -220,6 +221,8 @@ _PROTOTYPES = {
     "lo_cholesky_f32": (ci, [vp, vp, vp, vp, i64, i64, vp, sz, vp]),
     "lo_tri_solve_f32": (ci, [vp, vp, vp, vp, i64, i64, i64, i32, i32, vp]),
     "lo_cholesky_solve_f32": (ci, [vp, vp, vp, i64, i64, i64, i32, vp]),
+    "lo_block_mv_workspace_bytes": (sz, [P(OpDesc), i32, i64, i64]),
+    "lo_block_mv_f32": (ci, [P(OpDesc), i32, i64, vp, vp, i64, vp, sz, vp]),
     "lo_prof_enable": (ci, [ci]),
     "lo_prof_report": (ci, [C.c_char_p, sz]),
     "lo_hbm_triad_f32": (ci, [vp, vp, vp, f32, sz, vp]),

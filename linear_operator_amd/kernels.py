@@ -405,6 +405,30 @@ def matvec(desc: OperatorDescriptor, v: torch.Tensor) -> torch.Tensor:
     return y.reshape(v.shape)
 
 
+def block_matvec(desc: OperatorDescriptor, layout: int, T: int, v: torch.Tensor) -> Optional[torch.Tensor]:
+    """y = Block(A) v for the block operator over the B = G T members of `desc`, the block index fastest
+    (lo_block_mv_f32): `layout` LO_BLOCK_DIAG / LO_BLOCK_INTERLEAVED with v [*batch, T N, c] in that row order, or
+    LO_BLOCK_SUM with v [*batch, N, c].  None for a descriptor the kernels leave to the caller's composition
+    (LO_ERR_UNSUPPORTED)."""
+    lib = _hip.load()
+    _hip.require_hip(v)
+    c = v.shape[-1]
+    v3 = _flat(v, 2)
+    rows = desc.N if layout == _hip.LO_BLOCK_SUM else T * desc.N
+    if T < 1 or desc.B % T or v3.shape[0] != desc.B // T or v3.shape[1] != rows:
+        raise RuntimeError(f"block_matvec: rhs of shape {tuple(v.shape)} does not match {desc.B} members of size "
+                           f"{desc.N} in groups of {T} blocks (layout {layout})")
+    y = torch.empty_like(v3)
+    s = desc.c_struct()
+    ws = _hip.workspace(lib.lo_block_mv_workspace_bytes(C.byref(s), layout, T, c), v.device)
+    rc = lib.lo_block_mv_f32(C.byref(s), layout, T, _hip.ptr(v3), _hip.ptr(y), c, _hip.ptr(ws), ws.numel(),
+                             _hip.stream_ptr(v.device))
+    if rc == _hip.LO_ERR_UNSUPPORTED:
+        return None
+    _hip.check(rc, "lo_block_mv_f32")
+    return y.reshape(v.shape)
+
+
 _CACHE_GENERATIONS = itertools.count(1)
 
 

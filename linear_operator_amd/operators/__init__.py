@@ -17,6 +17,10 @@ from .sum_linear_operator import PsdSumLinearOperator, SumLinearOperator
 from .toeplitz_linear_operator import ToeplitzLinearOperator
 from .triangular_linear_operator import TriangularLinearOperator
 from .chol_linear_operator import CholLinearOperator
+from .block_linear_operator import BlockLinearOperator
+from .block_diag_linear_operator import BlockDiagLinearOperator
+from .block_interleaved_linear_operator import BlockInterleavedLinearOperator
+from .sum_batch_linear_operator import SumBatchLinearOperator
 
 __all__ = [
     "LowRankRootAddedDiagLinearOperator", "KroneckerProductAddedDiagLinearOperator",
@@ -25,4 +29,5 @@ __all__ = [
     "LinearOperatorRepresentationTree", "RootLinearOperator", "LowRankRootLinearOperator", "SumLinearOperator",
     "PsdSumLinearOperator", "TriangularLinearOperator", "MatmulLinearOperator", "InterpolatedLinearOperator",
     "ToeplitzLinearOperator", "ConstantMulLinearOperator", "MulLinearOperator", "CholLinearOperator",
+    "BlockLinearOperator", "BlockDiagLinearOperator", "BlockInterleavedLinearOperator", "SumBatchLinearOperator",
 ]

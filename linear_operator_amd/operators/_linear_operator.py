@@ -108,6 +108,33 @@ class LinearOperator(object):
     def _t_matmul(self, rhs: Tensor) -> Tensor:
         return self.mT._matmul(rhs)
 
+    def _map_batch(self, on_tensor: Callable, on_operator: Callable) -> "LinearOperator":
+        """The operator rebuilt from its components with their batch dimensions transformed."""
+        def conv(a):
+            if torch.is_tensor(a):
+                return on_tensor(a)
+            return on_operator(a) if isinstance(a, LinearOperator) else a
+
+        return self.__class__(*[conv(a) for a in self._args],
+                              **{k: conv(v) for k, v in self._differentiable_kwargs.items()},
+                              **self._nondifferentiable_kwargs)
+
+    def _permute_batch(self, *dims: int) -> "LinearOperator":
+        """Batch dimensions permuted to the order `dims` (reference :640-668): every tensor of the representation carries
+        the batch dimensions in front; classes whose tensors do not override this."""
+        return self._map_batch(lambda t: t.permute(*dims, *range(len(dims), t.dim())),
+                               lambda op: op._permute_batch(*dims))
+
+    def _unsqueeze_batch(self, dim: int) -> "LinearOperator":
+        """A batch dimension of size one inserted at the (non-negative) position `dim` (reference :848-861)."""
+        return self._map_batch(lambda t: t.unsqueeze(dim), lambda op: op._unsqueeze_batch(dim))
+
+    def _sum_batch(self, dim: int) -> "LinearOperator":
+        """The sum over the batch dimension `dim`, kept lazy (reference :765-779)."""
+        from .sum_batch_linear_operator import SumBatchLinearOperator
+
+        return SumBatchLinearOperator(self, block_dim=dim)
+
     def _preconditioner(self):  # reference :618-627
         """(closure P^-1(.), LinearOperator P, log|P|) or (None, None, None)."""
         return None, None, None
@@ -509,6 +536,24 @@ class LinearOperator(object):
         if isinstance(a, DenseLinearOperator) or isinstance(b, DenseLinearOperator):
             return DenseLinearOperator(a.to_dense() * b.to_dense())
         return MulLinearOperator(a, b)
+
+    @_implements(torch.sum)
+    def sum(self, dim: Optional[int] = None):
+        """Sum over a dimension (reference :2468-2521): a batch dimension gives a SumBatchLinearOperator, the row or the
+        column dimension a product with a vector of ones, no dimension the sum of all entries."""
+        if dim is None:
+            ones = torch.ones(self.size(-1), 1, dtype=self.dtype, device=self.device)
+            return (self @ ones).sum()
+        pos = dim + self.dim() if dim < 0 else dim
+        if pos == self.dim() - 1:
+            ones = torch.ones(self.size(-1), 1, dtype=self.dtype, device=self.device)
+            return (self @ ones).squeeze(-1)
+        if pos == self.dim() - 2:
+            ones = torch.ones(self.size(-2), 1, dtype=self.dtype, device=self.device)
+            return (self.mT @ ones).squeeze(-1)
+        if 0 <= pos < self.dim():
+            return self._sum_batch(pos)
+        raise ValueError("Invalid dim ({}) for LinearOperator of size {}".format(dim, self.shape))
 
     @_implements(torch.prod)
     def prod(self, dim: int):

@@ -69,6 +69,14 @@ class ConstantMulLinearOperator(LinearOperator):
         c = self._constant.expand(*batch_shape) if len(batch_shape) else self._constant
         return type(self)(self.base_linear_op._expand_batch(batch_shape), c)
 
+    def _permute_batch(self, *dims: int):  # (the constant holds batch dimensions only, and perhaps not all of them)
+        c = self._constant.expand(self.batch_shape).permute(*dims) if self._constant.dim() else self._constant
+        return type(self)(self.base_linear_op._permute_batch(*dims), c)
+
+    def _unsqueeze_batch(self, dim: int):
+        c = self._constant.expand(self.batch_shape).unsqueeze(dim) if self._constant.dim() else self._constant
+        return type(self)(self.base_linear_op._unsqueeze_batch(dim), c)
+
     def _get_indices(self, row_index, col_index, *batch_indices) -> Tensor:
         per_member = self._constant.expand(self.batch_shape)[batch_indices]
         return self.base_linear_op._get_indices(row_index, col_index, *batch_indices) * per_member

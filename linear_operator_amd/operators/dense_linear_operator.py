@@ -66,6 +66,9 @@ class DenseLinearOperator(LinearOperator):
     def _size(self) -> torch.Size:
         return self.tensor.size()
 
+    def _sum_batch(self, dim: int):  # reference :89-90
+        return self.__class__(self.tensor.sum(dim))
+
     def _transpose_nonbatch(self):
         return DenseLinearOperator(self.tensor.mT)
 
