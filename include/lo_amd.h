@@ -367,6 +367,33 @@ int lo_resident_inject_timeouts(int32_t n);
  * {next tag base, next epoch, clears so far, launches so far}.                                                        */
 int lo_resident_handoff_debug(int32_t force_clear, int64_t set_next_tag, int64_t set_next_epoch, uint32_t* out);
 
+/* ---- solve sessions: the headline solve without its per-call set-up (ABI 20) ---------------------------------------- */
+/* A preconditioner cache serves many solves of one operator; what lo_cg_solve_f32 does before and after its one launch
+ * for the headline plan (validation, the LO_* switches, the engine selection, the workspace carve) does not depend on the
+ * right-hand side.  A session holds all of it: created once per (operator, cache, parameters), it takes one
+ * right-hand side per call.
+ *   create   copies the three structs; LO_ERR_UNSUPPORTED unless the plan is the single column inside ONE launch of
+ *            k_cg_rspace3 on the library's hand-off buffer: lo_cg_plan.rspace == 2 and lean, c == 1, no tridiagonals,
+ *            no x0, no callbacks, no stop_reduce, pre->RSD present, R and pre->ldq already padded, no debug or A/B
+ *            switch set.  `workspace` (lo_cg_session_workspace_bytes: a control block and a few scalars per member, no
+ *            N-vector) belongs to the session until it is destroyed; the tensors the structs point to must stay alive.
+ *   solve    x [B,N,1] = A^-1 rhs as lo_cg_solve_f32 computes it, bit for bit; fills `info` and `executed` (what
+ *            lo_cg_last_executed would report, which it also updates).  Returns LO_ERR_UNSUPPORTED -- the caller then
+ *            runs lo_cg_solve_f32 with the same arguments on the same thread, where all of that logic lives -- when a
+ *            LO_* switch or lo_cg_set_onchip differs from creation, during a cool-down, after a lost or injected
+ *            hand-off time-out (counted once), for a right-hand side the diagonal form hands to the dense one, when the
+ *            stop rule does not hold at the floor, on NaN, and under stream capture.  That rerun counts as the same
+ *            entry-point call of a cool-down.  One solve at a time per session; synchronisation as lo_cg_solve_f32.
+ *   destroy  frees the host state (NULL is allowed).  lo_cg_session_debug_live: sessions alive in this process.      */
+struct lo_cg_session;
+size_t lo_cg_session_workspace_bytes(const lo_op_desc* op, const lo_cg_params* prm);
+int lo_cg_session_create_f32(const lo_op_desc* op, const lo_precond_desc* pre, const lo_cg_params* prm, void* workspace,
+                             size_t workspace_bytes, struct lo_cg_session** out);
+int lo_cg_session_solve_f32(struct lo_cg_session* s, const float* rhs, float* x, lo_cg_info* info, lo_cg_plan* executed,
+                            void* stream);
+void lo_cg_session_destroy(struct lo_cg_session* s);
+int lo_cg_session_debug_live(void);
+
 /* ---- PivotedCholesky.forward (linear_operator/functions/_pivoted_cholesky.py:14-105) ---------- */
 /* Greedy partial pivoted Cholesky of the NON-diagonal part of `op` (op->d is ignored, as
  * added_diag_linear_operator.py:125 calls self._linear_op.pivoted_cholesky).

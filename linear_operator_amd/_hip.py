@@ -24,7 +24,7 @@ LO_OP_HADAMARD_DIAG = 7
 LO_HADAMARD_MAX_RANK = 128
 LO_DIAG_NONE, LO_DIAG_FULL, LO_DIAG_CONST = 0, 1, 2
 LO_BLOCK_DIAG, LO_BLOCK_INTERLEAVED, LO_BLOCK_SUM = 0, 1, 2
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 LO_ERR_UNSUPPORTED = -4
 LO_FUSED_OK, LO_FUSED_EARLY_STOP, LO_FUSED_CONTINUE, LO_FUSED_TIMEOUT = 0, 1, 2, 3
@@ -144,6 +144,11 @@ _PROTOTYPES = {
     "lo_cg_workspace_bytes": (sz, [P(OpDesc), P(PrecondDesc), P(CgParams)]),
     "lo_cg_solve_f32": (ci, [P(OpDesc), MATVEC_CB, vp, P(PrecondDesc), MATVEC_CB, vp, P(CgParams), vp, vp, vp, vp, vp,
                               sz, P(CgInfo), vp]),
+    "lo_cg_session_workspace_bytes": (sz, [P(OpDesc), P(CgParams)]),
+    "lo_cg_session_create_f32": (ci, [P(OpDesc), P(PrecondDesc), P(CgParams), vp, sz, P(vp)]),
+    "lo_cg_session_solve_f32": (ci, [vp, vp, vp, P(CgInfo), P(CgPlan), vp]),
+    "lo_cg_session_destroy": (None, [vp]),
+    "lo_cg_session_debug_live": (ci, []),
     "lo_cg_set_onchip": (ci, [ci]),
     "lo_cg_plan_f32": (ci, [P(OpDesc), P(PrecondDesc), ci, ci, P(CgParams), ci, P(CgPlan)]),
     "lo_cg_last_executed": (ci, [P(CgPlan)]),
@@ -265,8 +270,10 @@ def load():
     return lib
 
 
-def prof_enable(on: bool):
-    load().lo_prof_enable(1 if on else 0)
+def prof_enable(on):
+    """True / 1: HIP-event scopes around the launches; 2: host intervals of the entry points only ("host:<name>" lines of
+    prof_report, no events inside them); 3: both; False / 0: off."""
+    load().lo_prof_enable(int(on))
 
 
 def prof_report() -> dict:

@@ -20,6 +20,7 @@
 #include <atomic>
 #include <cstdlib>
 #include <cstring>
+#include <new>
 
 #include "lo_device.h"
 #include "lo_internal.h"
@@ -47,6 +48,16 @@ void resident_tick() {  // once per entry-point call that could use a resident k
     fprintf(stderr, "liblo_amd: resident kernels re-armed after their cool-down\n");
   }
 }
+// A session solve that has ticked and launched hands its call to lo_cg_solve_f32, which ticks again for what is the SAME
+// entry-point call: a cool-down that is running (the launch lost its hand-off) gets that call back.
+static void resident_untick() {
+  int c = g_res_cooldown.load(std::memory_order_relaxed);
+  while (c > 0 && !g_res_cooldown.compare_exchange_weak(c, c + 1, std::memory_order_relaxed)) {
+  }
+}
+// resident_off() as the call will see it behind its resident_tick()
+static bool resident_off_after_tick() { return g_onchip_disabled || g_res_cooldown.load(std::memory_order_relaxed) > 1; }
+static void resident_return_injection() { g_res_inject.fetch_add(1, std::memory_order_relaxed); }
 void resident_note_ok() { g_res_backoff.store(kResidentBackoff0, std::memory_order_relaxed); }
 bool resident_take_injection() {
   int n = g_res_inject.load(std::memory_order_relaxed);
@@ -85,7 +96,7 @@ static int wait_ticket(volatile unsigned* word, unsigned ticket, hipStream_t st)
   return (*word == ticket) ? LO_OK : LO_ERR_LAUNCH;
 }
 void onchip_note_timeout() {
-  if (getenv("LO_OC_TEST_FALLBACK")) return;
+  if (cg_env().sw.oc_test_fallback) return;
   g_res_timeouts.fetch_add(1, std::memory_order_relaxed);
   const int bo = g_res_backoff.load(std::memory_order_relaxed);
   g_res_cooldown.store(bo, std::memory_order_relaxed);
@@ -124,6 +135,27 @@ static void lean_miss_note(const lo_op_desc* op, const lo_cg_params* prm, int ge
 }
 static thread_local lo_cg_plan tls_last_exec = {};    // what the last lo_cg_solve_f32 of this thread actually launched
 static thread_local bool tls_no_fused_precond = false;  // set while a solve is redone after a timed-out hand-off
+// lo_prof_enable(2): when the owned launch of k_cg_rspace3 returned / when the host saw its ticket (HostMarks)
+static thread_local std::chrono::steady_clock::time_point tls_host_launched, tls_host_ticket;
+// entry -> launch returned ("<what>_entry_to_launch") and ticket seen -> return ("<what>_ticket_to_return") of one headline
+// solve, in microseconds, when the call launched k_cg_rspace3 on the library's block and waited for its ticket
+struct HostMarks {
+  const char* what;
+  std::chrono::steady_clock::time_point t0;
+  bool on;
+  explicit HostMarks(const char* w) : what(w), on(g_prof_host) {
+    if (on) t0 = tls_host_launched = tls_host_ticket = std::chrono::steady_clock::now();
+  }
+  ~HostMarks() {
+    if (!on || tls_host_launched == t0 || tls_host_ticket == t0) return;
+    const auto t1 = std::chrono::steady_clock::now();
+    char name[64];
+    snprintf(name, sizeof(name), "%s_entry_to_launch", what);
+    prof_host(name, std::chrono::duration<double, std::micro>(tls_host_launched - t0).count());
+    snprintf(name, sizeof(name), "%s_ticket_to_return", what);
+    prof_host(name, std::chrono::duration<double, std::micro>(t1 - tls_host_ticket).count());
+  }
+};
 
 // A chunk of columns goes to the column-lockstep kernel (16 at a time on the matrix cores) when it has at least this
 // many live columns; fewer are cheaper one after the other on the second-generation kernel.
@@ -552,23 +584,8 @@ static CgShape cg_shape(const lo_op_desc* op, const lo_precond_desc* pre, bool p
   return s;
 }
 
-// The LO_* switches of the CG driver, read once per solve.
-struct CgSwitches {
-  bool no_lockstep, gw8, keep_state, no_rspace_cols, no_rspace, no_wrec, no_kron_root;  // engine selection (cg_plan)
-  bool no_fused_ctrl;     // the fused apply / column step leave the control step to k_cg_scal / k_cg_ctrl
-  bool oc_test_fallback;  // the resident kernels start with the error word set, as if a hand-off had timed out
-  bool rs_no_diag;        // no diagonal form of the R-space iteration (rspace_launch reads it too)
-  bool clear_handoff;     // the headline solve on the caller's workspace behind a clearing launch, as every other plan
-  int sc_test_fallback;   // the error word set behind the fused column step of iteration k (-1: never)
-};
-
-static CgSwitches cg_switches() {
-  auto on = [](const char* name) { return getenv(name) != nullptr; };
-  const char* sc = getenv("LO_SC_TEST_FALLBACK");
-  return {on("LO_OC_NO_LOCKSTEP"), on("LO_OC_GW8"), on("LO_OC_KEEP_STATE"), on("LO_NO_RSPACE_COLS"), on("LO_OC_NO_RSPACE"),
-          on("LO_OC_NO_WREC"), on("LO_NO_KRON_ROOT"), on("LO_NO_FUSED_CTRL"), on("LO_OC_TEST_FALLBACK"), on("LO_RS_NO_DIAG"),
-          on("LO_OC_CLEAR_HANDOFF"), sc ? atoi(sc) : -1};
-}
+// (CgSwitches / CgEnv / cg_env: lo_internal.h, lo_cg_onchip.hip -- every LO_* switch of the resident kernels in one pass)
+static CgSwitches cg_switches() { return cg_env().sw; }
 
 // The serial resident kernel of the columns [c - ncols, c) and its group size: the root form when it fits and the
 // preconditioner's root is the operator's own (or there is none), else the Q form (second generation), else none.
@@ -660,6 +677,14 @@ static void cg_plan(const lo_op_desc* op, const lo_precond_desc* pre, bool pre_c
 }
 
 
+// iterations the resident kernels record residual norms (and alpha / beta) for: up to the first possible stop
+static int oc_record_iters(const lo_cg_params* prm) {
+  const int fmi0 = prm->floor_max_iter > 0 ? prm->floor_max_iter : prm->max_iter;
+  int oc_iters = std::min(10, fmi0 - 1);
+  if (prm->n_tridiag) oc_iters = std::max(oc_iters, std::min(prm->max_tridiag_iter, fmi0 - 1));
+  return std::max(1, oc_iters + 1);
+}
+
 static size_t cg_layout(const lo_op_desc* op, const lo_precond_desc* pre, bool pre_cb, const lo_cg_params* prm,
                         void* ws, size_t ws_bytes, CgDev* d, MatvecPlan* pl, lo_matvec_cb mv_cb, void* mv_user,
                         const float** Qpad, float** upart, hipStream_t st, int* rc_out, bool init) {
@@ -706,10 +731,7 @@ static size_t cg_layout(const lo_op_desc* op, const lo_precond_desc* pre, bool p
   dd.ctrl_part = ar.take<float>(3 * 256);
   // operator-resident fast path scratch (c == 1): granule buffer, error word, per-iteration residuals
   dd.oc_err = reinterpret_cast<int*>(reinterpret_cast<char*>(dd.ctrl) + offsetof(CgCtrl, oc_err));  // (+ oc_next)
-  const int fmi0 = prm->floor_max_iter > 0 ? prm->floor_max_iter : prm->max_iter;
-  int oc_iters = std::min(10, fmi0 - 1);
-  if (prm->n_tridiag) oc_iters = std::max(oc_iters, std::min(prm->max_tridiag_iter, fmi0 - 1));
-  oc_iters = std::max(1, oc_iters + 1);
+  const int oc_iters = oc_record_iters(prm);
   const CgShape shp = cg_shape(op, pre, pre_cb, prm);  // (the predicates cg_plan decides on)
   const bool oc_shape = shp.oc_shape;
   const size_t oc_n = oc_shape ? (size_t)B * c : 1;
@@ -773,10 +795,9 @@ static size_t cg_layout(const lo_op_desc* op, const lo_precond_desc* pre, bool p
 struct CgDebug {
   bool ls = false, oc = false, sc = false;
   int member = 0;
-  static CgDebug read(int64_t B) {  // (sc: only where the fused column step runs, see cg_streaming)
-    const char *els = getenv("LO_LS_DEBUG"), *eoc = getenv("LO_OC_DEBUG");
-    const bool ls = els && B >= 8, oc = !ls && eoc && B >= 8;
-    return {ls, oc, getenv("LO_SC_DEBUG") != nullptr, oc ? atoi(eoc) : (ls ? atoi(els) : 0)};
+  static CgDebug read(const CgEnv& env, int64_t B) {  // (sc: only where the fused column step runs, see cg_streaming)
+    const bool ls = env.ls_debug && B >= 8, oc = !ls && env.oc_debug && B >= 8;
+    return {ls, oc, env.sc_debug, oc ? env.oc_member : (ls ? env.ls_member : 0)};
   }
   int report_resident(const long long* dev) const {
     long long ts[12];
@@ -838,6 +859,7 @@ struct CgSolve {
   bool x_written = false;         // the resident kernels already wrote result * rhs_norm
   bool ws_cleared = false;        // control block + granules of the workspace are zero (cg_clear_ws)
   unsigned owned_launch = 0;      // the resident launch ran on the library's hand-off block: its id (handoff_launch_confirm)
+  bool session = false;           // a solve session (lo_cg_session): its workspace holds no granules -- only the owned launch
   dim3 gridv, block;
 };
 
@@ -855,16 +877,9 @@ static int cg_clear_ws(CgSolve& s) {
   return LO_OK;
 }
 
-static int cg_setup(CgSolve& s, lo_matvec_cb matvec, void* matvec_user, float* t_mat, void* ws, size_t ws_bytes) {
-  const lo_op_desc* op = s.op; const lo_precond_desc* pre = s.pre; const lo_cg_params* prm = s.prm;
-  s.sw = cg_switches();
-  s.dbg = CgDebug::read(s.B);
-  int rc = LO_OK;
-  cg_layout(op, pre, s.precond_cb != nullptr, prm, ws, ws_bytes, &s.d, &s.pl, matvec, matvec_user, &s.Qp, &s.upart, s.st,
-            &rc, true);
-  if (rc) return rc;
-  CgDev& d = s.d;
-  s.sp = s.pl.sp;
+// What the set-up derives from the parameters alone, behind the carve of s.d (cg_setup, and a session's one set-up).
+static void cg_setup_scalars(CgSolve& s, float* t_mat) {
+  const lo_precond_desc* pre = s.pre; const lo_cg_params* prm = s.prm; CgDev& d = s.d;
   s.fmi = prm->floor_max_iter > 0 ? prm->floor_max_iter : prm->max_iter;  // (linear_cg.py:303-305)
   d.n_tridiag = prm->n_tridiag; d.max_iter = s.fmi; d.n_tridiag_iter = d.T = prm->max_tridiag_iter;
   // batch-global stopping rule over several ranks (lo_stop_reduce_cb): the device never decides the tolerance stop
@@ -875,17 +890,39 @@ static int cg_setup(CgSolve& s, lo_matvec_cb matvec, void* matvec_user, float* t
   s.precond = (pre != nullptr) || (s.precond_cb != nullptr);
   s.preR4 = pre ? padded_rank(pre->k) : 0;
   s.oc_nopre = !pre && !s.precond_cb && d.oc_zero_q != nullptr;
-  s.gridv = dim3(s.sp.S, (unsigned)s.B); s.block = dim3(kThreads);
-  if (prm->n_tridiag)
-    LO_HIP_CHECK(hipMemsetAsync(t_mat, 0, sizeof(float) * (size_t)prm->n_tridiag * s.B * d.T * d.T, s.st));
+  s.block = dim3(kThreads);
+}
+// The state of one run, as at the start of a solve: nothing executed yet.
+static void cg_reset_run(CgSolve& s) {
   memset(&s.h, 0, sizeof(s.h));
-  s.oc_nwg = onchip_num_workgroups();
-  // ---- the plan (pure: cg_plan above; lo_cg_plan_f32 reports the same decisions to the tests) ----
-  cg_plan(op, pre, s.precond_cb != nullptr, s.x0 != nullptr, prm, s.oc_nwg, s.sw, &s.plan);
+  s.k_start = s.launched = s.matvecs = 0;
+  s.x_written = s.ws_cleared = false;
+  s.owned_launch = 0;
   tls_rspace_resident_ran = false;
   s.exec = s.plan;
   s.exec.resident = 0;
   s.exec.rspace = 0;
+}
+
+static int cg_setup(CgSolve& s, lo_matvec_cb matvec, void* matvec_user, float* t_mat, void* ws, size_t ws_bytes) {
+  const lo_op_desc* op = s.op; const lo_precond_desc* pre = s.pre; const lo_cg_params* prm = s.prm;
+  const CgEnv env = cg_env();
+  s.sw = env.sw;
+  s.dbg = CgDebug::read(env, s.B);
+  int rc = LO_OK;
+  cg_layout(op, pre, s.precond_cb != nullptr, prm, ws, ws_bytes, &s.d, &s.pl, matvec, matvec_user, &s.Qp, &s.upart, s.st,
+            &rc, true);
+  if (rc) return rc;
+  CgDev& d = s.d;
+  s.sp = s.pl.sp;
+  cg_setup_scalars(s, t_mat);
+  s.gridv = dim3(s.sp.S, (unsigned)s.B);
+  if (prm->n_tridiag)
+    LO_HIP_CHECK(hipMemsetAsync(t_mat, 0, sizeof(float) * (size_t)prm->n_tridiag * s.B * d.T * d.T, s.st));
+  s.oc_nwg = onchip_num_workgroups();
+  // ---- the plan (pure: cg_plan above; lo_cg_plan_f32 reports the same decisions to the tests) ----
+  cg_plan(op, pre, s.precond_cb != nullptr, s.x0 != nullptr, prm, s.oc_nwg, s.sw, &s.plan);
+  cg_reset_run(s);
   // The control block (+ the granule buffer behind it when a resident kernel may run) is cleared here for every plan but
   // the single column inside one resident launch: k_cg_rspace3 takes that one on the hand-off block the library owns and
   // needs nothing of the workspace cleared (rspace3_launch_owned); whatever runs instead clears first (cg_clear_ws).
@@ -947,6 +984,7 @@ static int resident_close(CgSolve& s, const OnchipArgs& a, bool lean, bool dense
     // (with tridiagonals k_oc_tridiag is still queued behind the control kernel: drain the stream as before)
     if (ktri) LO_HIP_CHECK(hipStreamSynchronize(st));
     else if (wait_ticket(reinterpret_cast<volatile unsigned*>(mirror) + 63, ticket, st)) return LO_ERR_LAUNCH;
+    if (g_prof_host) tls_host_ticket = std::chrono::steady_clock::now();
     memcpy(&h, mirror, sizeof(CgCtrl));
   } else {
     LO_HIP_CHECK(hipMemcpyAsync(&h, d.ctrl, sizeof(CgCtrl), hipMemcpyDeviceToHost, st));
@@ -1027,7 +1065,8 @@ static int resident_attempt(CgSolve& s, int attempt, bool lean, bool dense, OcNe
   // (error word and member counters live in the control block: cleared with it, copied back with it)
   // lo_resident_inject_timeouts(n): the same through the real bookkeeping (cool-down, re-arm) -- the multi-rank tests
   // (a workspace that is not cleared yet: the error word is set behind the clearing, or in the library's own block)
-  const bool inject = s.sw.oc_test_fallback || (attempt == 0 && resident_take_injection());
+  const bool injected = attempt == 0 && resident_take_injection();
+  const bool inject = s.sw.oc_test_fallback || injected;
   s.owned_launch = 0;
   if (inject && s.ws_cleared) LO_HIP_CHECK(hipMemsetAsync(d.oc_err, 1, 1, st));
   if (s.dbg.oc || s.dbg.ls) LO_HIP_CHECK(hipMemsetAsync(d.oc_dbg, 0, 16 * sizeof(long long), st));
@@ -1106,9 +1145,14 @@ static int resident_attempt(CgSolve& s, int attempt, bool lean, bool dense, OcNe
         s.owned_launch = id;
         tls_rspace_resident_ran = true;
         tls_rspace_diag_ran = true;
+        if (g_prof_host) tls_host_launched = std::chrono::steady_clock::now();
       } else if (rc != LO_ERR_UNSUPPORTED) {
         return rc;
       }
+    }
+    if (rc == LO_ERR_UNSUPPORTED && s.session) {  // (nothing was enqueued: the general path takes the solve,
+      if (injected) resident_return_injection();    //  and the injected time-out with it)
+      return rc;
     }
     if (rc == LO_ERR_UNSUPPORTED) {
       if (!s.ws_cleared) {
@@ -1441,11 +1485,151 @@ static int cg_close(CgSolve& s, lo_cg_info* info) {
   return LO_OK;
 }
 
+// ---- solve sessions ---------------------------------------------------------------------------------
+// What the headline plan -- one column, diagonal R-space form, result only, closed inside the one launch of k_cg_rspace3 on
+// the library's own hand-off block -- touches of a workspace: the control block, the per-member scalars, the residual
+// record and the close granules a.close_gran names before rspace3_launch_owned replaces them.  No N-vector, no granules.
+// (The same members, sized as cg_layout sizes them for c == 1 without tridiagonals: a member added there for this plan
+//  belongs here too -- tests/test_gpu_cg_session.py compares the two paths bit for bit.)
+static size_t session_layout(const lo_op_desc* op, const lo_cg_params* prm, void* ws, size_t ws_bytes, CgDev* d) {
+  const int64_t B = op->B;
+  Arena ar(ws, ws_bytes);
+  CgDev dd;
+  memset(&dd, 0, sizeof(dd));
+  dd.B = B; dd.N = op->N; dd.c = 1;
+  dd.ctrl = ar.take<CgCtrl>(1);
+  dd.oc_close = ar.take<unsigned long long>((size_t)B + 2);
+  dd.rhs_norm = ar.take<float>(B);
+  dd.rz = ar.take<float>(B);
+  dd.alpha = ar.take<float>(B);
+  dd.beta = ar.take<float>(B);
+  dd.resid_norm = ar.take<float>(B);
+  dd.rhs_is_zero = ar.take<int>(B);
+  dd.has_conv = ar.take<int>(B);
+  dd.oc_err = reinterpret_cast<int*>(reinterpret_cast<char*>(dd.ctrl) + offsetof(CgCtrl, oc_err));
+  dd.oc_resid = ar.take<float>((size_t)B * oc_record_iters(prm));
+  dd.oc_init_conv = ar.take<int>(B);
+  if (d) *d = dd;
+  return (ws && !ar.ok) ? 0 : ar.off + 256;
+}
+
+static std::atomic<int> g_sessions_live{0};
+
 }  // namespace lo
 
 using namespace lo;
 
+// Everything of a resident single-column solve that does not depend on the right-hand side: the three descriptors, the
+// switches it was planned under, the plan, the carved workspace -- a CgSolve set up once.  One solve at a time per session.
+struct lo_cg_session {
+  lo_op_desc op;
+  lo_precond_desc pre;
+  lo_cg_params prm;
+  CgEnv env;
+  CgSolve s;
+  bool refused = false;  // the owned launch does not take this shape on this device: every solve goes to the general path
+};
+
 extern "C" {
+
+size_t lo_cg_session_workspace_bytes(const lo_op_desc* op, const lo_cg_params* prm) {
+  if (!op || !prm || op->B < 1) return 0;
+  return session_layout(op, prm, nullptr, 0, nullptr);
+}
+
+int lo_cg_session_create_f32(const lo_op_desc* op, const lo_precond_desc* pre, const lo_cg_params* prm, void* ws,
+                             size_t ws_bytes, struct lo_cg_session** out) {
+  if (!op || !pre || !prm || !ws || !out) return LO_ERR_BADARG;
+  EnvScope env_scope;
+  *out = nullptr;
+  if (prm->c != 1 || prm->n_tridiag != 0 || prm->stop_reduce) return LO_ERR_UNSUPPORTED;
+  const bool pre_root = pre->F && pre->EF && pre->rf_ld > 0;
+  if (pre->k < 1 || pre->k > kMaxRank || !pre->dinv || (!pre->Q && !pre_root)) return LO_ERR_BADARG;
+  if (op->kind != LO_OP_LOWRANK_DIAG || op->B < 1 || op->N < 1 || op->R < 1 || !op->A0) return LO_ERR_UNSUPPORTED;
+  if (op->diag_mode != LO_DIAG_NONE && !op->d) return LO_ERR_BADARG;
+  // (operands the general path pads into its workspace on every call stay with it)
+  if (padded_rank(op->R) != op->R || (pre->Q && pre->ldq != padded_rank(pre->k))) return LO_ERR_UNSUPPORTED;
+  const CgEnv env = cg_env();
+  if (env.ls_debug || env.oc_debug || env.sc_debug || env.sw.clear_handoff || env.sw.oc_test_fallback ||
+      env.sw.rs_no_diag || !pre->RSD || pinned_status_block() == nullptr)
+    return LO_ERR_UNSUPPORTED;
+  lo_cg_plan plan;
+  const int nwg = onchip_num_workgroups();
+  cg_plan(op, pre, false, false, prm, nwg, env.sw, &plan);
+  if (!plan.resident || plan.rspace != 2 || !plan.lean || !rspace_eligible(padded_rank(op->R), op->N, 1))
+    return LO_ERR_UNSUPPORTED;
+  lo_cg_session* ss = new (std::nothrow) lo_cg_session();
+  if (!ss) return LO_ERR_LAUNCH;
+  ss->op = *op; ss->pre = *pre; ss->prm = *prm; ss->env = env;
+  CgSolve& s = ss->s;
+  s = CgSolve{&ss->op, &ss->pre, nullptr, nullptr, &ss->prm, nullptr, nullptr, nullptr, nullptr, op->B, op->N, 1};
+  if (session_layout(op, prm, ws, ws_bytes, &s.d) == 0) {
+    delete ss;
+    return LO_ERR_WORKSPACE;
+  }
+  // (the part of cg_setup this plan needs; the operands are used where they are)
+  memset(&s.pl, 0, sizeof(s.pl));
+  s.pl.op = *op; s.pl.c = 1; s.pl.Apad = op->A0; s.pl.lda = s.pl.R4 = padded_rank(op->R);
+  s.Qp = pre->Q;
+  s.sw = env.sw;
+  s.dbg = CgDebug::read(env, s.B);
+  cg_setup_scalars(s, nullptr);
+  s.oc_nwg = nwg;
+  s.plan = plan;
+  s.session = true;
+  g_sessions_live.fetch_add(1, std::memory_order_relaxed);
+  *out = ss;
+  return LO_OK;
+}
+
+int lo_cg_session_solve_f32(struct lo_cg_session* ss, const float* rhs, float* x, lo_cg_info* info, lo_cg_plan* executed,
+                            void* stream) {
+  if (!ss || !rhs || !x || !info || !executed) return LO_ERR_BADARG;
+  HostMarks marks("cg_session");
+  EnvScope env_scope;
+  CgSolve& s = ss->s;
+  // Whatever is not this plan running clean is lo_cg_solve_f32's (LO_ERR_UNSUPPORTED).  Before the launch nothing has been
+  // touched, not even the cool-down's count: the general path serves the call from its start.
+  if (ss->refused || resident_off_after_tick() || !(cg_env() == ss->env)) return LO_ERR_UNSUPPORTED;
+  if (lean_miss_find(s.op, s.prm, s.pre->generation) >= 0) return LO_ERR_UNSUPPORTED;
+  hipStream_t st = (hipStream_t)stream;
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(st, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) {
+    (void)hipGetLastError();
+    return LO_ERR_UNSUPPORTED;
+  }
+  resident_tick();
+  // Behind the launch the general path finds the library as a failed first attempt of its own would have left it; its
+  // resident_tick() is this call's second and is given back first.
+  auto general = [&]() {
+    resident_untick();
+    return LO_ERR_UNSUPPORTED;
+  };
+  s.rhs = rhs; s.x = x; s.st = st;
+  cg_reset_run(s);
+  OcNext next = OcNext::kStream;
+  const int rc = resident_attempt(s, 0, true, false, &next);
+  if (rc == LO_ERR_UNSUPPORTED) {
+    if (!s.owned_launch) ss->refused = true;  // (else: the stop rule missed at the floor and the cache carries no Q form)
+    return general();
+  }
+  if (rc) return rc;
+  // a lost hand-off (noted once, in resident_close), a delicate right-hand side, a miss of the stop rule, NaN
+  if (next != OcNext::kDone || !s.x_written || !s.h.stop || s.h.nan_detected) return general();
+  s.launched = s.k_start;
+  const int crc = cg_close(s, info);
+  if (crc) return crc;
+  *executed = s.exec;
+  return LO_OK;
+}
+
+void lo_cg_session_destroy(struct lo_cg_session* ss) {
+  if (!ss) return;
+  g_sessions_live.fetch_sub(1, std::memory_order_relaxed);
+  delete ss;
+}
+
+int lo_cg_session_debug_live(void) { return g_sessions_live.load(std::memory_order_relaxed); }
 
 size_t lo_cg_workspace_bytes(const lo_op_desc* op, const lo_precond_desc* pre, const lo_cg_params* prm) {
   if (!op || !prm) return 0;
@@ -1475,6 +1659,8 @@ int lo_cg_solve_f32(const lo_op_desc* op, lo_matvec_cb matvec, void* matvec_user
   if (pre && precond_cb) return LO_ERR_BADARG;
   const bool pre_root = pre && pre->F && pre->EF && pre->rf_ld > 0;  // root form of the preconditioner available
   if (pre && (pre->k < 1 || pre->k > kMaxRank || !pre->dinv || (!pre->Q && !pre_root))) return LO_ERR_BADARG;
+  HostMarks marks("cg_solve");
+  EnvScope env_scope;
   resident_tick();
 
   CgSolve s{op, pre, precond_cb, precond_user, prm, rhs, x0, x, (hipStream_t)stream, op->B, op->N, (int)prm->c};
@@ -1507,6 +1693,7 @@ int lo_cg_plan_f32(const lo_op_desc* op, const lo_precond_desc* pre, int has_pre
   if (!op || !prm || !plan) return LO_ERR_BADARG;
   if (prm->c < 1 || prm->c > kMaxCols) return LO_ERR_UNSUPPORTED;
   if (pre && has_precond_cb) return LO_ERR_BADARG;
+  EnvScope env_scope;
   const int nwg = cus > 0 ? (cus / 32) * 32 : onchip_num_workgroups();
   cg_plan(op, pre, has_precond_cb != 0, has_x0 != 0, prm, nwg, cg_switches(), plan);
   return LO_OK;

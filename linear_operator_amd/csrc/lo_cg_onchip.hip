@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <mutex>
 #include <stdlib.h>
+#include <unistd.h>  // environ
 
 #include "lo_device.h"
 #include <string.h>
@@ -29,11 +30,57 @@ bool g_res_have = false;
 hipEvent_t g_res_ev[16] = {};
 }  // namespace
 
+// ---- the LO_* switches (lo_internal.h) ----
+static CgEnv env_pass() {
+  enum { kNoLockstep, kGw8, kKeepState, kNoRspaceCols, kNoRspace, kNoWrec, kNoKronRoot, kNoFusedCtrl, kTestFallback,
+         kRsNoDiag, kClearHandoff, kScTestFallback, kLsDebug, kOcDebug, kScDebug, kNoL2Handoff, kReserveCus,
+         kNoResidentOrder, kCount };
+  static const char* const names[kCount] = {
+      "OC_NO_LOCKSTEP", "OC_GW8", "OC_KEEP_STATE", "NO_RSPACE_COLS", "OC_NO_RSPACE", "OC_NO_WREC", "NO_KRON_ROOT",
+      "NO_FUSED_CTRL", "OC_TEST_FALLBACK", "RS_NO_DIAG", "OC_CLEAR_HANDOFF", "SC_TEST_FALLBACK", "LS_DEBUG", "OC_DEBUG",
+      "SC_DEBUG", "OC_NO_L2_HANDOFF", "OC_RESERVE_CUS", "NO_RESIDENT_ORDER"};
+  const char* val[kCount] = {};
+  for (char** e = environ; e && *e; ++e) {
+    const char* v = *e;
+    if (v[0] != 'L' || v[1] != 'O' || v[2] != '_') continue;
+    const char* eq = strchr(v + 3, '=');
+    if (!eq) continue;
+    const size_t len = (size_t)(eq - (v + 3));
+    for (int i = 0; i < kCount; ++i)
+      if (!val[i] && strlen(names[i]) == len && memcmp(names[i], v + 3, len) == 0) {  // (the first match, as getenv)
+        val[i] = eq + 1;
+        break;
+      }
+  }
+  CgEnv env;
+  auto on = [&](int i) { return val[i] != nullptr; };
+  env.sw.no_lockstep = on(kNoLockstep); env.sw.gw8 = on(kGw8); env.sw.keep_state = on(kKeepState);
+  env.sw.no_rspace_cols = on(kNoRspaceCols); env.sw.no_rspace = on(kNoRspace); env.sw.no_wrec = on(kNoWrec);
+  env.sw.no_kron_root = on(kNoKronRoot); env.sw.no_fused_ctrl = on(kNoFusedCtrl);
+  env.sw.oc_test_fallback = on(kTestFallback); env.sw.rs_no_diag = on(kRsNoDiag); env.sw.clear_handoff = on(kClearHandoff);
+  env.sw.sc_test_fallback = val[kScTestFallback] ? atoi(val[kScTestFallback]) : -1;
+  env.ls_debug = on(kLsDebug); env.oc_debug = on(kOcDebug); env.sc_debug = on(kScDebug);
+  env.ls_member = env.ls_debug ? atoi(val[kLsDebug]) : 0;
+  env.oc_member = env.oc_debug ? atoi(val[kOcDebug]) : 0;
+  env.no_l2_handoff = on(kNoL2Handoff);
+  env.has_reserve = on(kReserveCus);
+  env.reserve_cus = env.has_reserve ? atoi(val[kReserveCus]) : 0;
+  env.no_resident_order = on(kNoResidentOrder);
+  return env;
+}
+static thread_local CgEnv tls_env;
+static thread_local int tls_env_depth = 0;
+CgEnv cg_env() { return tls_env_depth > 0 ? tls_env : env_pass(); }
+EnvScope::EnvScope() {
+  if (tls_env_depth++ == 0) tls_env = env_pass();
+}
+EnvScope::~EnvScope() { --tls_env_depth; }
+
 ResidentLaunch::ResidentLaunch(hipStream_t st) {
   g_res_mu.lock();
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return;
-  if (g_res_have && g_res_last_dev == dev && g_res_last != st && !getenv("LO_NO_RESIDENT_ORDER")) {
+  if (g_res_have && g_res_last_dev == dev && g_res_last != st && !cg_env().no_resident_order) {
     if (!g_res_ev[dev] && hipEventCreateWithFlags(&g_res_ev[dev], hipEventDisableTiming) != hipSuccess) g_res_ev[dev] = nullptr;
     // (a stream the caller has destroyed in the meantime makes the record fail: nothing left to wait for)
     if (g_res_ev[dev] && hipEventRecord(g_res_ev[dev], g_res_last) == hipSuccess)
@@ -57,7 +104,7 @@ ResidentLock::~ResidentLock() { g_res_mu.unlock(); }
 // verified architecture string; anywhere else (and with LO_OC_NO_L2_HANDOFF) every granule is an agent-scope store.
 // Cost of the agent-scope stores on MI355X: profiles/r04/l2_handoff_cost.txt.
 int onchip_l2_handoff_allowed() {
-  if (getenv("LO_OC_NO_L2_HANDOFF")) return 0;
+  if (cg_env().no_l2_handoff) return 0;
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
   static int verified[64] = {0};  // 0 unknown, 1 yes, 2 no
@@ -85,7 +132,8 @@ int onchip_num_workgroups() {
   // (RCCL's all-gather kernel on its own stream) finds room WITHOUT displacing workgroups of a resident group -- a
   // displaced workgroup stalls its whole group until the other kernel ends.  The spare slots end up scattered over the
   // CUs (the dispatcher balances), each big enough for a 256-thread workgroup of <= 256 VGPRs.
-  if (const char* e = getenv("LO_OC_RESERVE_CUS")) cus = std::max(64, cus - std::max(0, atoi(e)));
+  const CgEnv env = cg_env();
+  if (env.has_reserve) cus = std::max(64, cus - std::max(0, env.reserve_cus));
   return (cus / 32) * 32;  // 2 workgroups per CU: a multiple of 8 XCDs x 8 workgroups per group
 }
 

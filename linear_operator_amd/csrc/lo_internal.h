@@ -36,6 +36,12 @@ void prof_stop(hipStream_t st);
     if (lo::g_prof_on) lo::prof_stop(st); \
   } while (0)
 
+// host-side intervals of an entry point (steady_clock), reported by lo_prof_report as "host:<name>" lines next to the
+// event scopes.  lo_prof_enable(2) turns them on WITHOUT the event scopes, whose two hipEventRecord calls per launch would
+// sit inside the intervals (tools/mb_step_gap.py).
+extern bool g_prof_host;
+void prof_host(const char* name, double us);
+
 // Row split of one batch member over S workgroups (rows multiple of 4 except the tail).
 struct Split {
   int S;
@@ -236,6 +242,46 @@ int lowrank_mv_run(const float* C, int R4, const float* d, int d_mode, const flo
                    int64_t c, const int* stop, hipStream_t st);
 
 // ---- operator-resident CG (lo_cg_onchip.hip) -----------------------------------------------------
+// The LO_* switches of the CG driver and of the resident launch helpers.
+struct CgSwitches {
+  bool no_lockstep, gw8, keep_state, no_rspace_cols, no_rspace, no_wrec, no_kron_root;  // engine selection (cg_plan)
+  bool no_fused_ctrl;     // the fused apply / column step leave the control step to k_cg_scal / k_cg_ctrl
+  bool oc_test_fallback;  // the resident kernels start with the error word set, as if a hand-off had timed out
+  bool rs_no_diag;        // no diagonal form of the R-space iteration (rspace_launch reads it too)
+  bool clear_handoff;     // the headline solve on the caller's workspace behind a clearing launch, as every other plan
+  int sc_test_fallback;   // the error word set behind the fused column step of iteration k (-1: never)
+  bool operator==(const CgSwitches& o) const {
+    return no_lockstep == o.no_lockstep && gw8 == o.gw8 && keep_state == o.keep_state && no_rspace_cols == o.no_rspace_cols &&
+           no_rspace == o.no_rspace && no_wrec == o.no_wrec && no_kron_root == o.no_kron_root &&
+           no_fused_ctrl == o.no_fused_ctrl && oc_test_fallback == o.oc_test_fallback && rs_no_diag == o.rs_no_diag &&
+           clear_handoff == o.clear_handoff && sc_test_fallback == o.sc_test_fallback;
+  }
+};
+// Every one of them, taken in ONE pass over the process environment (a getenv per switch walked it some twenty times per
+// solve).  cg_env() is the one reader: inside an EnvScope -- the CG entry points open one -- it returns the pass made when
+// the scope opened, so a call reads the environment once; outside, every cg_env() is a pass of its own.  The general
+// path therefore still sees a switch flipped between two calls (bench.py and the tests do that), and a solve session
+// compares the call's pass with the one it was created under.
+struct CgEnv {
+  CgSwitches sw;
+  bool ls_debug, oc_debug, sc_debug;  // LO_LS_DEBUG / LO_OC_DEBUG / LO_SC_DEBUG (CgDebug)
+  int ls_member, oc_member;
+  bool no_l2_handoff;                 // LO_OC_NO_L2_HANDOFF (onchip_l2_handoff_allowed)
+  bool has_reserve; int reserve_cus;  // LO_OC_RESERVE_CUS (onchip_num_workgroups)
+  bool no_resident_order;             // LO_NO_RESIDENT_ORDER (ResidentLaunch)
+  bool operator==(const CgEnv& o) const {
+    return sw == o.sw && ls_debug == o.ls_debug && oc_debug == o.oc_debug && sc_debug == o.sc_debug &&
+           ls_member == o.ls_member && oc_member == o.oc_member && no_l2_handoff == o.no_l2_handoff &&
+           has_reserve == o.has_reserve && reserve_cus == o.reserve_cus && no_resident_order == o.no_resident_order;
+  }
+};
+CgEnv cg_env();
+struct EnvScope {
+  EnvScope();
+  ~EnvScope();
+  EnvScope(const EnvScope&) = delete;
+  EnvScope& operator=(const EnvScope&) = delete;
+};
 struct OnchipArgs;
 size_t onchip_gbuf_bytes(int ngroups);
 // fp64 Gram partials of a root on the fp64 matrix cores (lo_rspace.hip): E = C^T diag(dinv) C (dinv_full != nullptr) and C^T C

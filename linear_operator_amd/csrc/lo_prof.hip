@@ -9,6 +9,7 @@
 namespace lo {
 
 bool g_prof_on = false;
+bool g_prof_host = false;
 
 namespace {
 struct Rec {
@@ -17,6 +18,7 @@ struct Rec {
 };
 std::vector<Rec> g_recs;
 std::vector<hipEvent_t> g_pool;
+std::map<std::string, std::pair<long, double>> g_host;  // host intervals: count, total ms
 hipEvent_t take_event() {
   if (!g_pool.empty()) {
     hipEvent_t e = g_pool.back();
@@ -38,6 +40,11 @@ void prof_start(const char* name, hipStream_t st) {
   g_recs.push_back(r);
 }
 void prof_stop(hipStream_t st) { (void)hipEventRecord(g_recs.back().b, st); }
+void prof_host(const char* name, double us) {
+  auto& e = g_host[std::string("host:") + name];
+  e.first += 1;
+  e.second += us * 1e-3;
+}
 
 // BabelStream-style kernels over n floats: the achievable HBM rate of this box, reported next to the 8 TB/s spec peak
 // (SURVEY 8(d)).  Every thread moves U float4 that lie one workgroup-width apart (a wave instruction touches 1 KiB of
@@ -143,7 +150,8 @@ int lo_hbm_stream_dev(int mode, int unroll, int nt, float* a, const float* b, co
 }
 
 int lo_prof_enable(int on) {
-  g_prof_on = on != 0;
+  g_prof_on = (on & 1) != 0;   // event scopes around the launches
+  g_prof_host = (on & 2) != 0;  // host intervals of the entry points (no events)
   return LO_OK;
 }
 
@@ -162,6 +170,8 @@ int lo_prof_report(char* buf, size_t buflen) {
     g_pool.push_back(r.b);
   }
   g_recs.clear();
+  for (auto& kv : g_host) agg[kv.first] = kv.second;
+  g_host.clear();
   std::string out;
   for (auto& kv : agg) {
     char line[256];

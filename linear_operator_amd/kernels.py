@@ -8,6 +8,8 @@ from __future__ import annotations
 import ctypes as C
 import itertools
 import os
+import threading
+from collections import OrderedDict
 from dataclasses import dataclass, field
 from typing import Callable, Optional
 
@@ -465,10 +467,26 @@ class WoodburyPreconditioner:
     # lo_precond_desc.generation: one number per cache OBJECT (never 0), part of the key of the library's "this solve missed
     # the stop rule in its result-only pass" memo -- a tensor address the allocator hands out again does not inherit it
     generation: int = field(default_factory=lambda: next(_CACHE_GENERATIONS))
+    # native solve sessions (lo_cg_session) of the single-column solves this cache serves, by operator and parameters
+    # (_session_solve): a small LRU, dropped by whatever changes the cache and destroyed with it
+    _sessions: OrderedDict = field(default_factory=OrderedDict, repr=False, compare=False)
 
     @property
     def rf_ld(self) -> int:
         return 0 if self.F is None else int(self.F.shape[-1])
+
+    def drop_sessions(self) -> None:
+        """Destroy the native solve sessions of this cache (their structs hold pointers into its tensors)."""
+        sessions = self.__dict__.get("_sessions")
+        while sessions:
+            _, ent = sessions.popitem()
+            ent.close()
+
+    def __del__(self):
+        try:
+            self.drop_sessions()
+        except Exception:  # noqa: BLE001 -- interpreter shutdown: the library may be gone already
+            pass
 
     def ensure_q(self) -> "WoodburyPreconditioner":
         """Build the generic (Q, dinv) form if this preconditioner only carries the root form."""
@@ -480,6 +498,7 @@ class WoodburyPreconditioner:
                 full = self.rebuild().ensure_q()
             else:
                 raise _hip.HipExtensionError("root-form-only preconditioner without its factor: Q cannot be built")
+            self.drop_sessions()
             self.Q, self.dinv, self.k = full.Q, full.dinv, full.k
         return self
 
@@ -496,6 +515,7 @@ class WoodburyPreconditioner:
             _launch("lo_precond_eigform_f32", self.RS.device, self.RS, B, self.rs_rank, ld, RSD)
             worst = float(RSD[:, 5, 1, 0].amin().item())
             if worst > 0:
+                self.drop_sessions()
                 self.RSD = RSD
             else:
                 self.rsd_refused = "ill-conditioned basis" if worst == -2.0 else "eigenvalue not positive"
@@ -658,6 +678,86 @@ def _cg_result(x: torch.Tensor, t_mat: Optional[torch.Tensor], info) -> CGResult
                     bool(info.skipped), float(info.mean_residual))
 
 
+_SESSIONS_PER_CACHE = 4    # (a cache serves one operator; a second entry is another tolerance or max_iter)
+_SESSION_RETRY_AFTER = 32  # solves after which a refused creation is tried again (a cool-down ends, a switch is removed)
+
+
+class _CgSession:
+    """One lo_cg_session with what it needs kept alive: its workspace, the tensors its structs point to, and the result
+    structs every solve fills.  handle None: the library refused the plan (LO_ERR_UNSUPPORTED) -- the general path."""
+
+    __slots__ = ("handle", "ws", "keep", "info", "plan", "info_ref", "plan_ref", "retry", "busy", "_destroy")
+
+    def __init__(self, lib, desc: "OperatorDescriptor", pre: "WoodburyPreconditioner", prm, dev):
+        s, ps = desc.c_struct(), pre.c_struct()
+        self.ws = _hip.workspace(lib.lo_cg_session_workspace_bytes(C.byref(s), C.byref(prm)), dev)
+        self.keep = (desc.A0, desc.d, pre.Q, pre.dinv, pre.F, pre.EF, pre.E, pre.RS, pre.RSD)
+        self.info, self.plan = _hip.CgInfo(), _hip.CgPlan()
+        self.info_ref, self.plan_ref = C.byref(self.info), C.byref(self.plan)
+        self.retry = _SESSION_RETRY_AFTER
+        self.busy = threading.Lock()  # one solve at a time per session: a second thread takes the general path
+        self._destroy = lib.lo_cg_session_destroy
+        out = C.c_void_p()
+        rc = lib.lo_cg_session_create_f32(C.byref(s), C.byref(ps), C.byref(prm), _hip.ptr(self.ws), self.ws.numel(),
+                                          C.byref(out))
+        if rc != _hip.LO_ERR_UNSUPPORTED:
+            _hip.check(rc, "lo_cg_session_create_f32")
+        self.handle = out.value if rc == 0 else None
+
+    def close(self):
+        if self.handle is not None:
+            self._destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        self.close()
+
+
+def cg_sessions_live() -> int:
+    """lo_cg_session_debug_live: native solve sessions alive in this process (tests)."""
+    return int(_hip.load().lo_cg_session_debug_live())
+
+
+def _session_solve(lib, desc: "OperatorDescriptor", pre: "WoodburyPreconditioner", rhs: torch.Tensor, rhs3: torch.Tensor,
+                   params: tuple) -> Optional["CGResult"]:
+    """The solve through the native session of (operator, cache, parameters), created on first use; None: the general path
+    takes it (no session for this plan, or lo_cg_session_solve_f32 handed the call over)."""
+    # (the operator by its POINTERS: the operator classes lower themselves to a fresh descriptor, with fresh views of the
+    #  same storage, on every solve; the entry keeps the tensors it was made from alive, so no address is handed out again
+    #  while it exists.  The cache's own tensors by identity: they are attributes of `pre`, replaced only by assignment.)
+    key = (desc.A0.data_ptr(), 0 if desc.d is None else desc.d.data_ptr(), desc.kind, desc.diag_mode, desc.B, desc.N,
+           desc.R, params, pre.generation, id(pre.Q), id(pre.dinv), id(pre.RSD))
+    sessions = pre._sessions
+    ent = sessions.get(key)
+    if ent is None:
+        max_iter, max_tridiag_iter, tolerance, eps, stop_updating_after, floor_max_iter = params
+        prm = _cg_params(1, 0, max_iter, max_tridiag_iter, tolerance, eps, stop_updating_after, floor_max_iter)
+        ent = sessions[key] = _CgSession(lib, desc, pre, prm, rhs.device)
+        while len(sessions) > _SESSIONS_PER_CACHE:
+            sessions.popitem(last=False)[1].close()
+    else:
+        sessions.move_to_end(key)
+    if ent.handle is None:
+        ent.retry -= 1
+        if ent.retry <= 0:
+            del sessions[key]
+        return None
+    if not ent.busy.acquire(False):
+        return None
+    try:
+        x = torch.empty_like(rhs3)
+        rc = lib.lo_cg_session_solve_f32(ent.handle, rhs3.data_ptr(), x.data_ptr(), ent.info_ref, ent.plan_ref,
+                                         _hip.stream_ptr(rhs.device))
+        if rc == _hip.LO_ERR_UNSUPPORTED:
+            return None
+        _hip.check(rc, "lo_cg_session_solve_f32")
+        if ent.plan.rspace == 2:
+            pre.rs_uses += 1
+        return _cg_result(x.reshape(rhs.shape), None, ent.info)
+    finally:
+        ent.busy.release()
+
+
 def cg_solve(desc: Optional[OperatorDescriptor], rhs: torch.Tensor, *, x0: Optional[torch.Tensor] = None,
              precond: Optional[WoodburyPreconditioner] = None, matvec_closure: Optional[Callable] = None,
              precond_closure: Optional[Callable] = None, closure_batch_shape=None, n_tridiag: int = 0,
@@ -683,6 +783,16 @@ def cg_solve(desc: Optional[OperatorDescriptor], rhs: torch.Tensor, *, x0: Optio
     else:
         if desc.B != B or desc.N != N:
             raise RuntimeError(f"cg_solve: rhs {tuple(rhs.shape)} does not match operator batch {desc.B}, N {desc.N}")
+        # The headline solve -- one column on a cache that carries the diagonal form -- through its native session: nothing
+        # below depends on the right-hand side, and the session did it once.  LO_CG_NO_SESSION: everything below, always.
+        if (precond is not None and precond.RSD is not None and precond.RS is not None and c == 1 and not n_tridiag
+                and desc.kind == _hip.LO_OP_LOWRANK_DIAG and desc.A0 is not None
+                and x0 is None and stop_reduce is None and precond_closure is None and not _retry
+                and "LO_CG_NO_SESSION" not in os.environ):
+            res = _session_solve(lib, desc, precond, rhs, rhs3,
+                                 (max_iter, max_tridiag_iter, tolerance, eps, stop_updating_after, floor_max_iter))
+            if res is not None:
+                return res
         s = desc.c_struct()
     bshape = tuple(closure_batch_shape) if closure_batch_shape is not None else tuple(rhs.shape[:-2])
     mv_cb, mv_err = _wrap_closure(matvec_closure, dev, bshape) if desc is None else _NO_CLOSURE
