@@ -57,6 +57,8 @@ extern "C" {
 #define LO_OP_HADAMARD_DIAG 7 /* AddedDiag(Mul(Root(F), Root(G)), Diag(d)):  y = (F F^T o G G^T) v + d o v
                                * (mul_linear_operator.py:54-80); A0 = F [B, N, p], R = p, A1 = G [B, N, q], n2 = q     */
 #define LO_HADAMARD_MAX_RANK 128 /* p, q the native Hadamard kernels take (larger: LO_ERR_UNSUPPORTED); any column count */
+#define LO_OP_MASKED 8 /* AddedDiag(Masked(base, mask, mask), Diag(d)):  y = S (base) S^T v + d o v, S the selected rows
+                        * (masked_linear_operator.py:52-60); `mask` below, N = M, B = base->B                          */
 
 /* diagonal storage */
 #define LO_DIAG_NONE 0  /* no diagonal term (plain Root / Dense / Kron operator)                    */
@@ -64,6 +66,7 @@ extern "C" {
 #define LO_DIAG_CONST 2 /* ConstantDiagLinearOperator.diag_values [B] (diag_linear_operator.py:313)  */
 
 struct lo_interp_desc;
+struct lo_mask_desc;
 
 /* Operator descriptor ("op-tree lowering" of an AddedDiag/Sum tree). */
 typedef struct lo_op_desc {
@@ -83,14 +86,30 @@ typedef struct lo_op_desc {
                       * diag_mode LO_DIAG_NONE and the same B, N (summed left to right, like the reference's
                       * Python sum()); the SUM's own (diag_mode, d) is the one diagonal of the tree */
     const struct lo_interp_desc* interp; /* SKI (ABI 16): HOST pointer to the two interpolation matrices      */
+    const struct lo_mask_desc* mask;     /* MASKED (ABI 21): HOST pointer to the base descriptor and the index list */
   };
   /* ABI 16 kinds.  TOEPLITZ: A0 = first column t [B, M] of the symmetric Toeplitz matrix, R = M = N.
    * SKI: A0 = t [B, M], R = M (grid size), n2 = J (interpolation points per row), `interp` as below.
    * (The kinds reuse the existing fields: the size and layout of lo_op_desc are those of ABI 15.)
    * ABI 17 kind.  HADAMARD: A0 = F [B, N, p], R = p, A1 = G [B, N, q], n2 = q (same layout again).  Lowered for
    * lo_matvec_f32, the streaming CG, Lanczos, fp32 MINRES and the fp32 pivoted Cholesky; fp64 entry points return
+   * LO_ERR_UNSUPPORTED; not a term kind of LO_OP_SUM.
+   * ABI 21 kind.  MASKED: `mask` as below, N = mask->M, B = mask->base->B; its own (diag_mode, d) with d of length M is
+   * the diagonal OUTSIDE the mask, the base's own diagonal the one inside (same layout again).  Lowered for
+   * lo_matvec_f32, the streaming CG, Lanczos and fp32 MINRES; lo_pivoted_cholesky_f32 and the fp64 entry points return
    * LO_ERR_UNSUPPORTED; not a term kind of LO_OP_SUM.                                                              */
 } lo_op_desc;
+
+/* The base operator and the selected rows of an LO_OP_MASKED descriptor (masked_linear_operator.py:17-35 with
+ * row_mask == col_mask): y = S (base) S^T v + d o v, S selecting the rows idx of the base.  base: HOST descriptor of
+ * kind LOWRANK_DIAG, DENSE_DIAG, KRON_DIAG or SUM with any diagonal mode of its own (CALLBACK, MASKED, SKI, TOEPLITZ,
+ * HADAMARD: LO_ERR_UNSUPPORTED).  idx: DEVICE pointer, int64 [M], strictly increasing, one list for all members; an
+ * entry outside [0, base->N) contributes nothing and is never dereferenced (the convention of lo_interp_desc).      */
+struct lo_mask_desc { /* (a plain struct tag: C callers write `struct lo_mask_desc`) */
+  const struct lo_op_desc* base;
+  const int64_t* idx; /* [M] */
+  int64_t M;
+};
 
 /* The interpolation matrices of an LO_OP_SKI_DIAG descriptor (interpolated_linear_operator.py:43-92): row n of W_l
  * holds left_vals[b, n, :] at grid points left_idx[b, n, :] (int64, exactly as the operator stores them), W_r likewise.
@@ -725,6 +744,14 @@ int lo_tri_solve_f32(const float* T, const float* rhs, float* out, float* sumsq,
                      int32_t upper, int32_t transpose, void* stream);
 int lo_cholesky_solve_f32(const float* T, const float* rhs, float* out, int64_t B, int64_t N, int64_t c, int32_t upper,
                           void* stream);
+
+/* ---- masked operators (ABI 21; csrc/lo_masked.hip) ---------------------------------------------------------------------
+ * The kind LO_OP_MASKED is served by lo_matvec_f32 and the solvers above.  lo_mask_expand_f32 is its first step alone:
+ * u [B, N0, c] = S^T v for v [B, M, c] (zero rows where the mask is false), one coalesced write of u; idx as in
+ * lo_mask_desc.  The operator's derivative expands both vector blocks with it before the base's own contraction.   */
+size_t lo_mask_expand_workspace_bytes(int64_t N0);
+int lo_mask_expand_f32(const int64_t* idx, int64_t M, int64_t N0, const float* v, float* u, int64_t B, int64_t c,
+                       void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- block operators over a batch of members (ABI 19; csrc/lo_block.hip) ---------------------------------------------
  * `base` describes B = G * T members of size n x n, the block index fastest (member g * T + t); kind LO_OP_DENSE_DIAG

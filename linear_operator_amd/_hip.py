@@ -22,9 +22,10 @@ LO_OP_SKI_DIAG, LO_OP_TOEPLITZ_DIAG = 5, 6
 LO_TOEPLITZ_MAX_M = 16384
 LO_OP_HADAMARD_DIAG = 7
 LO_HADAMARD_MAX_RANK = 128
+LO_OP_MASKED = 8
 LO_DIAG_NONE, LO_DIAG_FULL, LO_DIAG_CONST = 0, 1, 2
 LO_BLOCK_DIAG, LO_BLOCK_INTERLEAVED, LO_BLOCK_SUM = 0, 1, 2
-ABI_VERSION = 20
+ABI_VERSION = 21
 
 LO_ERR_UNSUPPORTED = -4
 LO_FUSED_OK, LO_FUSED_EARLY_STOP, LO_FUSED_CONTINUE, LO_FUSED_TIMEOUT = 0, 1, 2, 3
@@ -51,6 +52,12 @@ class InterpDesc(C.Structure):
     descriptor's `terms` slot (a union in C)."""
     _fields_ = [("left_idx", C.c_void_p), ("left_vals", C.c_void_p), ("right_idx", C.c_void_p),
                 ("right_vals", C.c_void_p), ("right_plan", C.c_void_p)]
+
+
+class MaskDesc(C.Structure):
+    """lo_mask_desc (include/lo_amd.h): the base descriptor and the selected rows of an LO_OP_MASKED descriptor, reached
+    through the descriptor's `terms` slot (a union in C)."""
+    _fields_ = [("base", C.POINTER(OpDesc)), ("idx", C.c_void_p), ("M", C.c_int64)]
 
 
 class PrecondDesc(C.Structure):
@@ -226,6 +233,8 @@ _PROTOTYPES = {
     "lo_cholesky_f32": (ci, [vp, vp, vp, vp, i64, i64, vp, sz, vp]),
     "lo_tri_solve_f32": (ci, [vp, vp, vp, vp, i64, i64, i64, i32, i32, vp]),
     "lo_cholesky_solve_f32": (ci, [vp, vp, vp, i64, i64, i64, i32, vp]),
+    "lo_mask_expand_workspace_bytes": (sz, [i64]),
+    "lo_mask_expand_f32": (ci, [vp, i64, i64, vp, vp, i64, i64, vp, sz, vp]),
     "lo_block_mv_workspace_bytes": (sz, [P(OpDesc), i32, i64, i64]),
     "lo_block_mv_f32": (ci, [P(OpDesc), i32, i64, vp, vp, i64, vp, sz, vp]),
     "lo_prof_enable": (ci, [ci]),

@@ -172,6 +172,14 @@ struct MatvecPlan {
   // LO_OP_HADAMARD_DIAG (lo_hadamard.hip): the contraction partials and the reduced M_t of every column
   float* hd_part;
   float* hd_m;
+  // LO_OP_MASKED (lo_masked.hip): the index list, its inverse map built by matvec_plan_init, the expanded vector
+  // u = S^T v and the base's result w (nullptr on the dense route); the base's plan is sub[0] (nterms == 1)
+  const int64_t* mask_idx;  // [M]
+  int64_t mask_N0;
+  int* mask_inv;            // [N0], -1 where masked out
+  float* mask_u;            // [B, N0, c]
+  float* mask_w;            // [B, N0, c]
+  bool mask_dense;
 };
 void matvec_plan_free(MatvecPlan* pl);
 // releases a plan's sub-plans on every exit path of the function that owns it
@@ -207,6 +215,11 @@ int ski_matvec_run(const MatvecPlan* pl, const float* v, float* y, const int* st
 size_t hadamard_plan_bytes(const lo_op_desc* op, int64_t c);
 int hadamard_plan_init(MatvecPlan* pl, const lo_op_desc* op, int64_t c, Arena* ar);
 int hadamard_matvec_run(const MatvecPlan* pl, const float* v, float* y, const int* stop, hipStream_t st);
+
+// ---- masked operator (lo_masked.hip) ---------------------------------------------------------------------------------
+size_t masked_plan_bytes(const lo_op_desc* op, int64_t c);
+int masked_plan_init(MatvecPlan* pl, const lo_op_desc* op, int64_t c, Arena* ar, hipStream_t st);
+int masked_matvec_run(const MatvecPlan* pl, const float* v, float* y, const int* stop, hipStream_t st);
 
 // dense / kron kernels
 int dense_matvec(const float* K, const float* d, int dd_mode, const float* v, float* y, float* dot_part, int64_t B,

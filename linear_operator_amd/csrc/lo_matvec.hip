@@ -44,6 +44,8 @@ size_t matvec_plan_bytes(const lo_op_desc* op, int64_t c, Split sp) {
     return ski_plan_bytes(op, c) + 256;
   } else if (op->kind == LO_OP_HADAMARD_DIAG) {
     return hadamard_plan_bytes(op, c) + 256;
+  } else if (op->kind == LO_OP_MASKED) {
+    return masked_plan_bytes(op, c) + 256;
   }
   return ar.off + 256;
 }
@@ -69,6 +71,11 @@ int matvec_plan_init(MatvecPlan* pl, const lo_op_desc* op, lo_matvec_cb cb, void
   pl->csr_ptr = pl->csr_ids = nullptr;
   pl->ski_u = pl->ski_t = pl->tz_part = nullptr;
   pl->hd_part = pl->hd_m = nullptr;
+  pl->mask_idx = nullptr;
+  pl->mask_N0 = 0;
+  pl->mask_inv = nullptr;
+  pl->mask_u = pl->mask_w = nullptr;
+  pl->mask_dense = false;
   if (op->B < 1 || op->N < 1 || c < 1) return LO_ERR_BADARG;
   if (op->diag_mode != LO_DIAG_NONE && !op->d) return LO_ERR_BADARG;
   switch (op->kind) {
@@ -114,6 +121,11 @@ int matvec_plan_init(MatvecPlan* pl, const lo_op_desc* op, lo_matvec_cb cb, void
     }
     case LO_OP_HADAMARD_DIAG: {
       const int rc = hadamard_plan_init(pl, op, c, ar);
+      if (rc) return rc;
+      break;
+    }
+    case LO_OP_MASKED: {
+      const int rc = masked_plan_init(pl, op, c, ar, st);
       if (rc) return rc;
       break;
     }
@@ -197,6 +209,10 @@ int matvec_run(const MatvecPlan* pl, const float* v, float* y, float* dot_part, 
       rc = hadamard_matvec_run(pl, v, y, stop, st);
       if (!rc && dot_part) rc = vec_dot_part(v, y, pl->c, dot_part, op.B, op.N, pl->sp, stop, st);
       return rc;
+    case LO_OP_MASKED:  // S (base) S^T v + d o v: expand, the base's product (or the selected rows of a dense base), gather
+      rc = masked_matvec_run(pl, v, y, stop, st);
+      if (!rc && dot_part) rc = vec_dot_part(v, y, pl->c, dot_part, op.B, op.N, pl->sp, stop, st);
+      return rc;
     case LO_OP_CALLBACK:
       rc = pl->cb(pl->cb_user, v, y, op.B, op.N, pl->c, (void*)st);
       if (rc) return LO_ERR_LAUNCH;
@@ -233,7 +249,7 @@ using namespace lo;
 
 extern "C" {
 
-int lo_abi_version(void) { return 20; }
+int lo_abi_version(void) { return 21; }
 const char* lo_target_arch(void) { return "gfx950"; }
 
 size_t lo_matvec_workspace_bytes(const lo_op_desc* op, int64_t c) {
@@ -249,6 +265,8 @@ int lo_matvec_f32(const lo_op_desc* op, const float* v, float* y, int64_t c, voi
   Arena ar(ws, ws_bytes);
   if (op->kind == LO_OP_LOWRANK_DIAG) resident_tick();  // (an entry point that may run a resident kernel: serves the cool-down)
   if (matvec_plan_bytes(op, c, sp) > 256 && !ws) return LO_ERR_WORKSPACE;
+  // (the masked plan launches its inverse-map kernel while it is built: a short workspace is refused before that)
+  if (op->kind == LO_OP_MASKED && ws_bytes < matvec_plan_bytes(op, c, sp)) return LO_ERR_WORKSPACE;
   MatvecPlan pl;
   int rc = matvec_plan_init(&pl, op, nullptr, nullptr, c, sp, &ar, st);
   if (rc) return rc;

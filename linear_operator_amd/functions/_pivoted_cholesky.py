@@ -22,8 +22,10 @@ class PivotedCholesky(Function):
                 f"Running Pivoted Cholesky on a {matrix.shape} RHS for {max_iter} iterations."
             )
         desc = matrix._kernel_descriptor()
-        if desc is not None and desc.diag_mode != 0:
-            desc = None  # the kernels factor a descriptor WITHOUT its diagonal; a genuine A + D takes the generic path
+        if desc is not None and (desc.diag_mode != 0 or desc.kind == K._hip.LO_OP_MASKED):
+            # the kernels factor a descriptor WITHOUT its diagonal; a genuine A + D takes the generic path, and so does a
+            # masked operator, whose rows come from the base's through `_get_rows`
+            desc = None
         if desc is not None:
             L, perm = K.pivoted_cholesky(desc, max_iter, float(error_tol))
         else:

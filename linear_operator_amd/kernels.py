@@ -35,6 +35,7 @@ class OperatorDescriptor:
     terms: tuple = ()  # LO_OP_SUM: the summed structured terms (descriptors without a diagonal), left to right
     interp: tuple = ()  # LO_OP_SKI_DIAG: (left_idx, left_vals, right_idx, right_vals), [B, N, J] int64 / fp32
     interp_plan: Optional[torch.Tensor] = None  # LO_OP_SKI_DIAG: grid-major copy of W_r kept across calls (interp_plan)
+    mask: tuple = ()  # LO_OP_MASKED: (descriptor of the base operator, idx int64 [M] of the selected rows)
 
     @property
     def device(self):
@@ -45,6 +46,8 @@ class OperatorDescriptor:
             return term.device
         for t in self.interp:
             return t.device
+        if self.mask:
+            return self.mask[1].device
         raise ValueError("empty descriptor")
 
     def c_struct(self) -> _hip.OpDesc:
@@ -63,11 +66,16 @@ class OperatorDescriptor:
                                 None if self.interp_plan is None else self.interp_plan.data_ptr())
             s.terms = C.cast(C.pointer(w), C.POINTER(_hip.OpDesc))
             s._interp_keepalive = w
+        if self.mask:  # the union slot `mask`: a host struct of the base's host descriptor and the device index list
+            base = self.mask[0].c_struct()
+            m = _hip.MaskDesc(C.pointer(base), self.mask[1].data_ptr(), self.mask[1].numel())
+            s.terms = C.cast(C.pointer(m), C.POINTER(_hip.OpDesc))
+            s._mask_keepalive = (base, m)
         return s
 
     def without_diag(self) -> "OperatorDescriptor":
         return OperatorDescriptor(self.kind, self.B, self.N, self.A0, self.A1, None, _hip.LO_DIAG_NONE, self.R,
-                                  self.n2, self.batch_shape, self.terms, self.interp, self.interp_plan)
+                                  self.n2, self.batch_shape, self.terms, self.interp, self.interp_plan, self.mask)
 
 
 def sum_descriptor(terms, d: Optional[torch.Tensor] = None, const_diag: bool = False):
@@ -254,6 +262,39 @@ def hadamard_diag_descriptor(F: torch.Tensor, G: torch.Tensor, d: Optional[torch
     F3, G3 = _flat(F, 2), _flat(G, 2)
     return _with_diag(OperatorDescriptor(_hip.LO_OP_HADAMARD_DIAG, F3.shape[0], N, A0=F3, A1=G3, R=p, n2=G.shape[-1],
                                          batch_shape=batch), d, const_diag)
+
+
+_MASK_BASE_KINDS = (_hip.LO_OP_LOWRANK_DIAG, _hip.LO_OP_DENSE_DIAG, _hip.LO_OP_KRON_DIAG, _hip.LO_OP_SUM)
+
+
+def masked_descriptor(base_desc: OperatorDescriptor, idx: torch.Tensor, d: Optional[torch.Tensor] = None,
+                      const_diag: bool = False):
+    """AddedDiag(Masked(base, mask, mask), Diag(d)) (or the masked operator alone): y = S (base) S^T v + d o v with S
+    selecting the rows `idx` (int64 [M] on the device, strictly increasing) of the base -- whose own diagonal, if any,
+    sits inside the mask.  d [*batch, M] (or one value per member) is the diagonal outside it.  None for a base kind
+    the C side does not take (the caller composes the product)."""
+    if base_desc is None or base_desc.kind not in _MASK_BASE_KINDS:
+        return None
+    if idx.dtype != torch.int64 or not idx.is_cuda or idx.dim() != 1 or idx.numel() < 1:
+        return None
+    _hip.require_hip(d)
+    return _with_diag(OperatorDescriptor(_hip.LO_OP_MASKED, base_desc.B, idx.numel(), batch_shape=base_desc.batch_shape,
+                                         mask=(base_desc, idx.contiguous())), d, const_diag)
+
+
+def mask_expand(idx: torch.Tensor, n0: int, v: torch.Tensor) -> torch.Tensor:
+    """u = S^T v: v [*batch, M, c] -> [*batch, n0, c] with the rows idx (int64 [M], strictly increasing) filled and zeros
+    elsewhere (lo_mask_expand_f32: one coalesced write of u, no clearing pass)."""
+    lib = _hip.load()
+    _hip.require_hip(v)
+    M, c = v.shape[-2:]
+    if idx.numel() != M or idx.dtype != torch.int64 or not idx.is_cuda:
+        raise RuntimeError(f"mask_expand: {idx.numel()} indices for vectors of shape {tuple(v.shape)}")
+    v3 = _flat(v, 2)
+    u = torch.empty(v3.shape[0], n0, c, dtype=torch.float32, device=v.device)
+    _launch("lo_mask_expand_f32", v.device, idx.contiguous(), M, n0, v3, u, v3.shape[0], c,
+            ws_bytes=lib.lo_mask_expand_workspace_bytes(n0))
+    return u.reshape(*v.shape[:-2], n0, c)
 
 
 def bilinear_hadamard(F: torch.Tensor, G: torch.Tensor, left_vecs: torch.Tensor, right_vecs: torch.Tensor):

@@ -21,6 +21,7 @@ from .block_linear_operator import BlockLinearOperator
 from .block_diag_linear_operator import BlockDiagLinearOperator
 from .block_interleaved_linear_operator import BlockInterleavedLinearOperator
 from .sum_batch_linear_operator import SumBatchLinearOperator
+from .masked_linear_operator import MaskedLinearOperator
 
 __all__ = [
     "LowRankRootAddedDiagLinearOperator", "KroneckerProductAddedDiagLinearOperator",
@@ -30,4 +31,5 @@ __all__ = [
     "PsdSumLinearOperator", "TriangularLinearOperator", "MatmulLinearOperator", "InterpolatedLinearOperator",
     "ToeplitzLinearOperator", "ConstantMulLinearOperator", "MulLinearOperator", "CholLinearOperator",
     "BlockLinearOperator", "BlockDiagLinearOperator", "BlockInterleavedLinearOperator", "SumBatchLinearOperator",
+    "MaskedLinearOperator",
 ]

@@ -319,7 +319,8 @@ class AddedDiagLinearOperator(SumLinearOperator):
         the factor stays in the [B, m, N] row layout the HIP kernels write (a strided [.., N, m] view): the
         preconditioner build reads it in place and the transposed copy of _pivoted_cholesky.py:105 is skipped."""
         desc = self._linear_op._kernel_descriptor()
-        if desc is None or desc.diag_mode != 0 or self.device.type != "cuda" or self.dtype != torch.float32:
+        if (desc is None or desc.diag_mode != 0 or desc.kind == K._hip.LO_OP_MASKED or self.device.type != "cuda"
+                or self.dtype != torch.float32):  # (a masked operator: the generic row access, as PivotedCholesky.forward)
             L, perm = self._linear_op.pivoted_cholesky(rank=max_iter, return_pivots=True)
             from .. import distributed
 
