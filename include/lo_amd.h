@@ -677,6 +677,51 @@ int lo_lanczos_tridiag_f64(const double* A, const double* diag, lo_matvec_cb_f64
                            const double* init_vecs, int64_t B, int64_t N, int64_t P, int32_t max_iter, double tol,
                            double* q_mat, double* t_mat, int32_t* iters_out, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- float64 structured operators (ABI 22; csrc/lo_matvec_f64.hip) -------------------------------------------------
+ * y [B, N, c] = A v for a descriptor whose A0 / A1 / d point to DOUBLES (the convention of lo_pivoted_cholesky_f64; the
+ * size and layout of lo_op_desc are unchanged, and nothing in the struct records the element type: the caller keeps
+ * float64 descriptors away from the fp32 entry points).
+ *   kinds     LO_OP_LOWRANK_DIAG, LO_OP_DENSE_DIAG, LO_OP_KRON_DIAG and LO_OP_SUM of up to LO_MAX_TERMS of those (summed
+ *             left to right, the sum's own diagonal added last); every other kind: LO_ERR_UNSUPPORTED
+ *   diagonal  LO_DIAG_NONE / FULL / CONST;  any N, R, n1, n2, c >= 1, 1 <= B <= 65535;  y must not alias v (LO_ERR_BADARG)
+ * Plain launches, fixed-order sums, no float64 atomics: the same inputs give the same bits, and a member's result does
+ * not depend on the batch around it, nor on the alignment of the operands (row chunks, tiles and the thread layout are
+ * functions of the member's own shape).
+ *   low-rank   C^T v as per-workgroup partials in the workspace added in chunk order, then a second pass over C
+ *   dense      the kernel of lo_cg_solve_f64;  Kronecker: two small-GEMM passes, the [n1, n2, c] intermediate in the
+ *              workspace
+ * Asynchronous on `stream`.  Replaces the same `_matmul`s as lo_matvec_f32 for float64 operands.                    */
+size_t lo_matvec_f64_workspace_bytes(const lo_op_desc* op, int64_t c);
+int lo_matvec_f64(const lo_op_desc* op, const double* v, double* y, int64_t c, void* ws, size_t ws_bytes, void* stream);
+
+/* Library-side callbacks for the `matvec` / `precond_cb` arguments of lo_cg_solve_f64, lo_minres_f64 and
+ * lo_lanczos_tridiag_f64: the host passes these exported functions themselves with a context struct as `user`, and the
+ * solver runs a lowered operator / the Woodbury preconditioner with no call into the host language per product.  The
+ * structs and what they point to must stay alive for the solver call; the workspaces belong to the call.
+ *   lo_matvec_desc_cb_f64   y = A v by lo_matvec_f64; ws of lo_matvec_f64_workspace_bytes(op, c).  op->B, op->N must equal
+ *                           the solver's B, N.
+ *   lo_precond_desc_cb_f64  the precondition_closure of added_diag_linear_operator.py:135-140 from the cached pair
+ *                           (Q [B, N, k], noise):  z = r / d - Q (Q^T r)  (LO_DIAG_FULL, noise [B, N])
+ *                                                  z = (r - Q Q^T r) / sigma  (LO_DIAG_CONST, noise [B])
+ *                           -- the low-rank kernels of lo_matvec_f64 with another epilogue; ws of
+ *                           lo_precond_f64_workspace_bytes(B, N, k, c).  z must not alias r.                          */
+struct lo_f64_op_ctx { /* (plain struct tags, as lo_mask_desc: C callers write `struct lo_f64_op_ctx`) */
+  const lo_op_desc* op;
+  void* ws;
+  size_t ws_bytes;
+};
+struct lo_f64_precond_ctx {
+  const double* Q;     /* [B, N, k] */
+  const double* noise; /* [B, N] (LO_DIAG_FULL) or [B] (LO_DIAG_CONST) */
+  int32_t diag_mode;
+  int32_t k;
+  void* ws;
+  size_t ws_bytes;
+};
+int lo_matvec_desc_cb_f64(void* user, const double* v, double* y, int64_t B, int64_t N, int64_t c, void* stream);
+int lo_precond_desc_cb_f64(void* user, const double* r, double* z, int64_t B, int64_t N, int64_t c, void* stream);
+size_t lo_precond_f64_workspace_bytes(int64_t B, int64_t N, int32_t k, int64_t c);
+
 /* ---- Toeplitz / interpolation building blocks (ABI 16; csrc/lo_ski.hip) ------------------------------------------
  * Symmetric Toeplitz T = toeplitz(t), t [B, M]; interpolation W [B, N, M] stored as idx int64 [B, N, J] and vals fp32
  * [B, N, J] (utils/interpolation.py, utils/toeplitz.py).  Vectors [B, rows, c], c innermost.  Deterministic: the same

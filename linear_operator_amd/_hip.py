@@ -25,7 +25,7 @@ LO_HADAMARD_MAX_RANK = 128
 LO_OP_MASKED = 8
 LO_DIAG_NONE, LO_DIAG_FULL, LO_DIAG_CONST = 0, 1, 2
 LO_BLOCK_DIAG, LO_BLOCK_INTERLEAVED, LO_BLOCK_SUM = 0, 1, 2
-ABI_VERSION = 21
+ABI_VERSION = 22
 
 LO_ERR_UNSUPPORTED = -4
 LO_FUSED_OK, LO_FUSED_EARLY_STOP, LO_FUSED_CONTINUE, LO_FUSED_TIMEOUT = 0, 1, 2, 3
@@ -117,6 +117,17 @@ class CgInfoF64(C.Structure):
                 ("mean_residual", C.c_double)]
 
 
+class F64OpCtx(C.Structure):
+    """lo_f64_op_ctx: the `user` of lo_matvec_desc_cb_f64."""
+    _fields_ = [("op", C.POINTER(OpDesc)), ("ws", C.c_void_p), ("ws_bytes", C.c_size_t)]
+
+
+class F64PrecondCtx(C.Structure):
+    """lo_f64_precond_ctx: the `user` of lo_precond_desc_cb_f64."""
+    _fields_ = [("Q", C.c_void_p), ("noise", C.c_void_p), ("diag_mode", C.c_int32), ("k", C.c_int32),
+                ("ws", C.c_void_p), ("ws_bytes", C.c_size_t)]
+
+
 class MinresParamsF64(C.Structure):
     _fields_ = [("c", C.c_int64), ("n_shifts", C.c_int32), ("max_iter", C.c_int32), ("has_value", C.c_int32),
                 ("shifts_per_member", C.c_int32), ("value", C.c_double), ("tolerance", C.c_double), ("eps", C.c_double)]
@@ -173,6 +184,11 @@ _PROTOTYPES = {
     "lo_minres_f64_workspace_bytes": (sz, [i64, i64, P(MinresParamsF64)]),
     "lo_minres_f64": (ci, [vp, vp, MATVEC_CB, vp, MATVEC_CB, vp, P(MinresParamsF64), i64, i64, vp, vp, vp, vp, sz,
                             P(MinresInfoF64), vp]),
+    "lo_matvec_f64_workspace_bytes": (sz, [P(OpDesc), i64]),
+    "lo_matvec_f64": (ci, [P(OpDesc), vp, vp, i64, vp, sz, vp]),
+    "lo_matvec_desc_cb_f64": (ci, [vp, vp, vp, i64, i64, i64, vp]),
+    "lo_precond_f64_workspace_bytes": (sz, [i64, i64, i32, i64]),
+    "lo_precond_desc_cb_f64": (ci, [vp, vp, vp, i64, i64, i64, vp]),
     "lo_pivoted_cholesky_workspace_bytes": (sz, [P(OpDesc), i32]),
     "lo_pivoted_cholesky_f32": (ci, [P(OpDesc), i32, f32, vp, vp, P(i32), vp, sz, vp]),
     "lo_pivoted_cholesky_cb_workspace_bytes": (sz, [i64, i64, i32]),

@@ -56,10 +56,12 @@ __global__ __launch_bounds__(kThreads) void k64_dots(const double* __restrict__ 
   }
 }
 
-// y[b, i, j] = sum_k A[b, i, k] v[b, k, j] (+ d[b, i] v[b, i, j]); one wave per row, 8 columns per pass
+// y[b, i, j] = sum_k A[b, i, k] v[b, k, j] (+ d[b, i] v[b, i, j]); one wave per row, 8 columns per pass.
+// dmode: LO_DIAG_FULL d [B, N], LO_DIAG_CONST d [B] (d == nullptr: none); accumulate: the product is added onto y first
+// (a later term of a sum, lo_matvec_f64.hip)
 __global__ __launch_bounds__(kThreads) void k64_dense_mv(const double* __restrict__ A, const double* __restrict__ d,
-                                                          const double* __restrict__ v, double* __restrict__ y, int N,
-                                                          int c) {
+                                                          int dmode, int accumulate, const double* __restrict__ v,
+                                                          double* __restrict__ y, int N, int c) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6);
   if (row >= N) return;
@@ -86,7 +88,8 @@ __global__ __launch_bounds__(kThreads) void k64_dense_mv(const double* __restric
     if (lane == 0) {
       for (int j = 0; j < nj; ++j) {
         double r = acc[j];
-        if (d) r += d[b * N + row] * vb[(size_t)row * c + j0 + j];
+        if (accumulate) r = y[(b * N + row) * (size_t)c + j0 + j] + r;
+        if (d) r += d[dmode == LO_DIAG_CONST ? b : b * N + row] * vb[(size_t)row * c + j0 + j];
         y[(b * N + row) * (size_t)c + j0 + j] = r;
       }
     }
@@ -299,12 +302,16 @@ int f64_dots(const double* a, const double* b1, double* out1, const double* a2, 
   LO_LAUNCH_CHECK();
   return LO_OK;
 }
-int f64_dense_mv(const double* A, const double* d, const double* v, double* y, int64_t B, int64_t N, int64_t c,
-                 hipStream_t st) {
-  hipLaunchKernelGGL(k64_dense_mv, dim3((unsigned)((N + 3) / 4), (unsigned)B), dim3(kThreads), 0, st, A, d, v, y, (int)N,
-                     (int)c);
+int f64_dense_mv_ex(const double* A, const double* d, int dmode, int accumulate, const double* v, double* y, int64_t B,
+                    int64_t N, int64_t c, hipStream_t st) {
+  hipLaunchKernelGGL(k64_dense_mv, dim3((unsigned)((N + 3) / 4), (unsigned)B), dim3(kThreads), 0, st, A,
+                     dmode == LO_DIAG_NONE ? nullptr : d, dmode, accumulate, v, y, (int)N, (int)c);
   LO_LAUNCH_CHECK();
   return LO_OK;
+}
+int f64_dense_mv(const double* A, const double* d, const double* v, double* y, int64_t B, int64_t N, int64_t c,
+                 hipStream_t st) {
+  return f64_dense_mv_ex(A, d, d ? LO_DIAG_FULL : LO_DIAG_NONE, 0, v, y, B, N, c, st);
 }
 int f64_copy(const double* a, double* o, size_t total, hipStream_t st) {
   hipLaunchKernelGGL(k64_copy, dim3((unsigned)((total + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, a, o, total);
@@ -377,10 +384,7 @@ extern "C" int lo_cg_solve_f64(const double* A, const double* diag, lo_matvec_cb
 
   auto apply_op = [&](const double* v, double* y) -> int {
     if (A) {
-      hipLaunchKernelGGL(k64_dense_mv, dim3((unsigned)((N + 3) / 4), (unsigned)B), dim3(kThreads), 0, st, A, diag, v, y,
-                         (int)N, (int)c);
-      LO_LAUNCH_CHECK();
-      return LO_OK;
+      return f64_dense_mv(A, diag, v, y, B, N, c, st);
     }
     return matvec(matvec_user, v, y, B, N, c, stream) ? LO_ERR_LAUNCH : LO_OK;
   };

@@ -358,6 +358,9 @@ int f64_dots(const double* a, const double* b1, double* out1, const double* a2, 
              int64_t B, int64_t N, int64_t c, hipStream_t st);
 int f64_dense_mv(const double* A, const double* d, const double* v, double* y, int64_t B, int64_t N, int64_t c,
                  hipStream_t st);
+// the same kernel with the diagonal as (d, LO_DIAG_*) and, accumulate != 0, the product added onto y (lo_matvec_f64.hip)
+int f64_dense_mv_ex(const double* A, const double* d, int dmode, int accumulate, const double* v, double* y, int64_t B,
+                    int64_t N, int64_t c, hipStream_t st);
 int f64_copy(const double* a, double* o, size_t total, hipStream_t st);
 
 // ---- single-pass Woodbury apply fused with the CG r / x update (lo_precond_fused.hip) --------------

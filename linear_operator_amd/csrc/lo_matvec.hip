@@ -249,7 +249,7 @@ using namespace lo;
 
 extern "C" {
 
-int lo_abi_version(void) { return 21; }
+int lo_abi_version(void) { return 22; }
 const char* lo_target_arch(void) { return "gfx950"; }
 
 size_t lo_matvec_workspace_bytes(const lo_op_desc* op, int64_t c) {

@@ -22,9 +22,11 @@ class PivotedCholesky(Function):
                 f"Running Pivoted Cholesky on a {matrix.shape} RHS for {max_iter} iterations."
             )
         desc = matrix._kernel_descriptor()
-        if desc is not None and (desc.diag_mode != 0 or desc.kind == K._hip.LO_OP_MASKED):
+        if desc is not None and (desc.diag_mode != 0 or desc.kind == K._hip.LO_OP_MASKED
+                                 or desc.dtype != torch.float32):
             # the kernels factor a descriptor WITHOUT its diagonal; a genuine A + D takes the generic path, and so does a
-            # masked operator, whose rows come from the base's through `_get_rows`
+            # masked operator, whose rows come from the base's through `_get_rows`.  A float64 descriptor stays on the
+            # row-callback route as well (lo_pivoted_cholesky_cb_f64, whose pivots the reference golden pins)
             desc = None
         if desc is not None:
             L, perm = K.pivoted_cholesky(desc, max_iter, float(error_tol))

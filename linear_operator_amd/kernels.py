@@ -36,6 +36,10 @@ class OperatorDescriptor:
     interp: tuple = ()  # LO_OP_SKI_DIAG: (left_idx, left_vals, right_idx, right_vals), [B, N, J] int64 / fp32
     interp_plan: Optional[torch.Tensor] = None  # LO_OP_SKI_DIAG: grid-major copy of W_r kept across calls (interp_plan)
     mask: tuple = ()  # LO_OP_MASKED: (descriptor of the base operator, idx int64 [M] of the selected rows)
+    # element type of A0 / A1 / d.  The C struct does not record it: float64 descriptors (low-rank / dense / Kronecker /
+    # sums of those) go to lo_matvec_f64 and the float64 solvers only, and c_struct() refuses to hand one to an entry
+    # point that reads `float*`
+    dtype: torch.dtype = torch.float32
 
     @property
     def device(self):
@@ -50,7 +54,12 @@ class OperatorDescriptor:
             return self.mask[1].device
         raise ValueError("empty descriptor")
 
-    def c_struct(self) -> _hip.OpDesc:
+    def c_struct(self, dtype: torch.dtype = torch.float32) -> _hip.OpDesc:
+        """The lo_op_desc for an entry point that reads the operands as `dtype`; any other descriptor is refused."""
+        if self.dtype != dtype:
+            raise _hip.HipExtensionError(
+                f"a {self.dtype} operator descriptor was handed to a {dtype} entry point of liblo_amd (float64 "
+                "descriptors are taken by matvec and the float64 solvers only)")
         s = _hip.OpDesc()
         s.kind, s.diag_mode, s.B, s.N, s.R, s.n2 = self.kind, self.diag_mode, self.B, self.N, self.R, self.n2
         s.A0 = None if self.A0 is None else self.A0.data_ptr()
@@ -58,7 +67,7 @@ class OperatorDescriptor:
         s.d = None if self.d is None else self.d.data_ptr()
         s.nterms = len(self.terms)
         if self.terms:  # host array of term descriptors; kept alive by the returned struct
-            arr = (_hip.OpDesc * len(self.terms))(*[t.c_struct() for t in self.terms])
+            arr = (_hip.OpDesc * len(self.terms))(*[t.c_struct(dtype) for t in self.terms])
             s.terms = C.cast(arr, C.POINTER(_hip.OpDesc))
             s._terms_keepalive = arr
         if self.interp:  # the union slot `interp`: a host struct of the four device pointers
@@ -75,21 +84,38 @@ class OperatorDescriptor:
 
     def without_diag(self) -> "OperatorDescriptor":
         return OperatorDescriptor(self.kind, self.B, self.N, self.A0, self.A1, None, _hip.LO_DIAG_NONE, self.R,
-                                  self.n2, self.batch_shape, self.terms, self.interp, self.interp_plan, self.mask)
+                                  self.n2, self.batch_shape, self.terms, self.interp, self.interp_plan, self.mask,
+                                  self.dtype)
 
 
-def sum_descriptor(terms, d: Optional[torch.Tensor] = None, const_diag: bool = False):
+def _check_dtype(dtype, *tensors):
+    """The descriptor builders' element type: float32 (every engine) or, on request, float64 (matvec and the float64
+    solvers); all tensors of one descriptor share it."""
+    if dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"operator descriptors are float32 or float64, not {dtype}")
+    if dtype == torch.float64:
+        for t in tensors:
+            if t is not None and t.dtype != dtype:
+                raise _hip.HipExtensionError(f"a float64 operator descriptor takes float64 tensors only; got {t.dtype}")
+
+
+def sum_descriptor(terms, d: Optional[torch.Tensor] = None, const_diag: bool = False, dtype=torch.float32):
     """SumLinearOperator(A_1, ..., A_n) (+ one diagonal): y = sum_i A_i v + d o v (sum_linear_operator.py:47-51).
-    `terms`: 2 .. LO_MAX_TERMS descriptors of kind low-rank / dense / Kronecker WITHOUT a diagonal, same batch and N."""
+    `terms`: 2 .. LO_MAX_TERMS descriptors of kind low-rank / dense / Kronecker WITHOUT a diagonal, same batch and N,
+    all of the element type `dtype`."""
     terms = tuple(terms)
+    for t in terms:
+        if t.dtype != dtype:
+            raise _hip.HipExtensionError(f"a {dtype} sum descriptor takes {dtype} terms only; got {t.dtype}")
+    _check_dtype(dtype, d)
     if not 2 <= len(terms) <= _hip.LO_MAX_TERMS:
         raise ValueError(f"a lowered sum holds 2 .. {_hip.LO_MAX_TERMS} terms, got {len(terms)}")
     t0 = terms[0]
     for t in terms:
         if t.kind == _hip.LO_OP_SUM or t.diag_mode != _hip.LO_DIAG_NONE or (t.B, t.N) != (t0.B, t0.N):
             raise ValueError("sum terms must be plain structured operators of one batch and size")
-    return _with_diag(OperatorDescriptor(_hip.LO_OP_SUM, t0.B, t0.N, batch_shape=t0.batch_shape, terms=terms), d,
-                      const_diag)
+    return _with_diag(OperatorDescriptor(_hip.LO_OP_SUM, t0.B, t0.N, batch_shape=t0.batch_shape, terms=terms,
+                                         dtype=dtype), d, const_diag)
 
 
 def _flat(t: torch.Tensor, keep: int) -> torch.Tensor:
@@ -164,6 +190,51 @@ def _dense_f64(A, diag, matvec_closure, batch_shape, B: int, N: int):
     return None, None
 
 
+def _f64_operator(lib, desc: "OperatorDescriptor", B: int, N: int, c: int, dev):
+    """A float64 descriptor as the `matvec` of a float64 solver: (lo_matvec_desc_cb_f64 itself, its lo_f64_op_ctx as the
+    user pointer, what has to stay alive for the call).  No Python runs per product."""
+    if desc.B != B or desc.N != N:
+        raise RuntimeError(f"the right-hand side (batch {B}, N {N}) does not match operator batch {desc.B}, N {desc.N}")
+    s = desc.c_struct(torch.float64)
+    ws = _hip.workspace(lib.lo_matvec_f64_workspace_bytes(C.byref(s), c), dev)
+    ctx = _hip.F64OpCtx(C.pointer(s), ws.data_ptr(), ws.numel())
+    return C.cast(lib.lo_matvec_desc_cb_f64, _hip.MATVEC_CB), C.cast(C.pointer(ctx), C.c_void_p), (s, ws, ctx)
+
+
+def _f64_precond(lib, precond, batch_shape, B: int, N: int, c: int, dev):
+    """The cached pair (Q [*b, N, k], noise [*b, N] | [*b, 1] | [*b], constant_diag) of the float64 Woodbury
+    preconditioner as the `precond_cb` of a float64 solver (lo_precond_desc_cb_f64 and its lo_f64_precond_ctx)."""
+    Q, noise, constant = precond
+    _hip.require_hip(Q, noise, dtype=torch.float64)
+    k = Q.shape[-1]
+    Q3 = Q.expand(*batch_shape, N, k).reshape(B, N, k).contiguous()
+    if constant:
+        n2 = noise.reshape(*noise.shape, 1) if noise.dim() == len(Q.shape) - 2 else noise
+        n2 = n2.expand(*batch_shape, 1).reshape(B).contiguous()
+    else:
+        n2 = noise.expand(*batch_shape, N).reshape(B, N).contiguous()
+    ws = _hip.workspace(lib.lo_precond_f64_workspace_bytes(B, N, k, c), dev)
+    ctx = _hip.F64PrecondCtx(Q3.data_ptr(), n2.data_ptr(), _hip.LO_DIAG_CONST if constant else _hip.LO_DIAG_FULL, k,
+                             ws.data_ptr(), ws.numel())
+    return C.cast(lib.lo_precond_desc_cb_f64, _hip.MATVEC_CB), C.cast(C.pointer(ctx), C.c_void_p), (Q3, n2, ws, ctx)
+
+
+def precond_apply_f64(Q: torch.Tensor, noise: torch.Tensor, constant_diag: bool, r: torch.Tensor) -> torch.Tensor:
+    """z = r / d - Q (Q^T r) (or (r - Q Q^T r) / sigma, constant_diag) in float64: one call of lo_precond_desc_cb_f64, the
+    function the float64 solvers call per iteration.  r [*batch, N, c]."""
+    lib = _hip.load()
+    _hip.require_hip(r, dtype=torch.float64)
+    N, c = r.shape[-2:]
+    r3 = _flat(r, 2)
+    B = r3.shape[0]
+    cb, user, keep = _f64_precond(lib, (Q, noise, constant_diag), tuple(r.shape[:-2]), B, N, c, r.device)
+    z = torch.empty_like(r3)
+    _hip.check(lib.lo_precond_desc_cb_f64(user, _hip.ptr(r3), _hip.ptr(z), B, N, c, _hip.stream_ptr(r.device)),
+               "lo_precond_desc_cb_f64")
+    del keep
+    return z.reshape(r.shape)
+
+
 def _diag_operand(d: torch.Tensor, B: int, N: int, const_diag: bool, want_dinv: bool = False):
     """(d flattened to [B] (constant) or [B, N], its LO_DIAG_* mode, an empty buffer of that shape for 1 / d or None)."""
     if const_diag:
@@ -183,32 +254,37 @@ def _row_strides(L3: torch.Tensor):
     return sm, sr, sc
 
 
-def lowrank_diag_descriptor(Croot: torch.Tensor, d: Optional[torch.Tensor], const_diag: bool = False):
-    _hip.require_hip(Croot, d)
+def lowrank_diag_descriptor(Croot: torch.Tensor, d: Optional[torch.Tensor], const_diag: bool = False,
+                            dtype=torch.float32):
+    _check_dtype(dtype, Croot, d)
+    _hip.require_hip(Croot, d, dtype=dtype)
     batch = Croot.shape[:-2]
     N, R = Croot.shape[-2:]
     C3 = _flat(Croot, 2)
-    return _with_diag(OperatorDescriptor(_hip.LO_OP_LOWRANK_DIAG, C3.shape[0], N, A0=C3, R=R, batch_shape=batch), d,
-                      const_diag)
+    return _with_diag(OperatorDescriptor(_hip.LO_OP_LOWRANK_DIAG, C3.shape[0], N, A0=C3, R=R, batch_shape=batch,
+                                         dtype=dtype), d, const_diag)
 
 
-def dense_diag_descriptor(K: torch.Tensor, d: Optional[torch.Tensor], const_diag: bool = False):
-    _hip.require_hip(K, d)
+def dense_diag_descriptor(K: torch.Tensor, d: Optional[torch.Tensor], const_diag: bool = False, dtype=torch.float32):
+    _check_dtype(dtype, K, d)
+    _hip.require_hip(K, d, dtype=dtype)
     batch = K.shape[:-2]
     N = K.shape[-1]
     K3 = _flat(K, 2)
-    return _with_diag(OperatorDescriptor(_hip.LO_OP_DENSE_DIAG, K3.shape[0], N, A0=K3, batch_shape=batch), d,
-                      const_diag)
+    return _with_diag(OperatorDescriptor(_hip.LO_OP_DENSE_DIAG, K3.shape[0], N, A0=K3, batch_shape=batch, dtype=dtype),
+                      d, const_diag)
 
 
-def kron_diag_descriptor(K1: torch.Tensor, K2: torch.Tensor, d: Optional[torch.Tensor], const_diag: bool = False):
-    _hip.require_hip(K1, K2, d)
+def kron_diag_descriptor(K1: torch.Tensor, K2: torch.Tensor, d: Optional[torch.Tensor], const_diag: bool = False,
+                         dtype=torch.float32):
+    _check_dtype(dtype, K1, K2, d)
+    _hip.require_hip(K1, K2, d, dtype=dtype)
     batch = K1.shape[:-2]
     n1, n2 = K1.shape[-1], K2.shape[-1]
     A = _flat(K1, 2)
     Bm = _flat(K2, 2)
     return _with_diag(OperatorDescriptor(_hip.LO_OP_KRON_DIAG, A.shape[0], n1 * n2, A0=A, A1=Bm, R=n1, n2=n2,
-                                         batch_shape=batch), d, const_diag)
+                                         batch_shape=batch, dtype=dtype), d, const_diag)
 
 
 def toeplitz_diag_descriptor(column: torch.Tensor, d: Optional[torch.Tensor], const_diag: bool = False):
@@ -273,8 +349,8 @@ def masked_descriptor(base_desc: OperatorDescriptor, idx: torch.Tensor, d: Optio
     selecting the rows `idx` (int64 [M] on the device, strictly increasing) of the base -- whose own diagonal, if any,
     sits inside the mask.  d [*batch, M] (or one value per member) is the diagonal outside it.  None for a base kind
     the C side does not take (the caller composes the product)."""
-    if base_desc is None or base_desc.kind not in _MASK_BASE_KINDS:
-        return None
+    if base_desc is None or base_desc.kind not in _MASK_BASE_KINDS or base_desc.dtype != torch.float32:
+        return None  # (float64 bases: the masked kernels are fp32)
     if idx.dtype != torch.int64 or not idx.is_cuda or idx.dim() != 1 or idx.numel() < 1:
         return None
     _hip.require_hip(d)
@@ -426,6 +502,8 @@ def interp_values_grad(idx: torch.Tensor, lv: torch.Tensor, R: torch.Tensor) -> 
 
 def _with_diag(desc: OperatorDescriptor, d, const_diag):
     if d is not None:
+        if d.dtype != desc.dtype:
+            raise _hip.HipExtensionError(f"a {d.dtype} diagonal cannot be attached to a {desc.dtype} operator descriptor")
         desc.d, desc.diag_mode, _ = _diag_operand(d, desc.B, desc.N, const_diag)
     return desc
 
@@ -434,18 +512,82 @@ def _with_diag(desc: OperatorDescriptor, d, const_diag):
 def matvec(desc: OperatorDescriptor, v: torch.Tensor) -> torch.Tensor:
     """y = A v for v [*batch, N, c] (LinearOperator._matmul of the lowered operator)."""
     lib = _hip.load()
-    _hip.require_hip(v)
+    _hip.require_hip(v, dtype=desc.dtype)
     c = v.shape[-1]
     v3 = _flat(v, 2)
     if v3.shape[0] != desc.B or v3.shape[1] != desc.N:
         raise RuntimeError(f"matvec: rhs of shape {tuple(v.shape)} does not match operator batch {desc.B} x N {desc.N}")
     y = torch.empty_like(v3)
-    s = desc.c_struct()
-    ws_bytes = lib.lo_matvec_workspace_bytes(C.byref(s), c)
+    s = desc.c_struct(desc.dtype)
+    f64 = desc.dtype == torch.float64
+    ws_bytes = (lib.lo_matvec_f64_workspace_bytes if f64 else lib.lo_matvec_workspace_bytes)(C.byref(s), c)
     ws = _hip.workspace(ws_bytes, v.device)
-    _hip.check(lib.lo_matvec_f32(C.byref(s), _hip.ptr(v3), _hip.ptr(y), c, _hip.ptr(ws), ws.numel(),
-                                 _hip.stream_ptr(v.device)), "lo_matvec_f32")
+    name = "lo_matvec_f64" if f64 else "lo_matvec_f32"
+    _hip.check(getattr(lib, name)(C.byref(s), _hip.ptr(v3), _hip.ptr(y), c, _hip.ptr(ws), ws.numel(),
+                                  _hip.stream_ptr(v.device)), name)
     return y.reshape(v.shape)
+
+
+# Which float64 products the operators' `_matmul` hands to lo_matvec_f64, by (kind, one column / more columns): True only
+# where tools/mb_f64.py measured the native product at least as fast as the ATen composition `_matmul` otherwise runs
+# (DESIGN.md section 6g).  A combination that is absent keeps the composition; the descriptor still serves the float64
+# CG, MINRES and Lanczos, where it replaces a Python call per product.  Measured (native / ATen, microseconds):
+#   low-rank 64 x 8192 x 32        1 column  76 / 161     17 columns   392 / 428
+#   Kronecker 16 x (128 (x) 128)   1 column  31 /  60     17 columns   172 / 117   (stays with ATen)
+#   sum low-rank + dense, N 4096   1 column 155 / 212     17 columns  3489 / 402   (stays with ATen)
+# A dense operator alone was not timed and keeps torch.matmul.
+_NATIVE_MATMUL_F64: dict = {("lowrank", 1): True, ("lowrank", 2): True, ("kron", 1): True, ("sum", 1): True}
+_F64_KIND_NAMES = {_hip.LO_OP_LOWRANK_DIAG: "lowrank", _hip.LO_OP_DENSE_DIAG: "dense", _hip.LO_OP_KRON_DIAG: "kron",
+                   _hip.LO_OP_SUM: "sum"}
+
+
+def _f64_route_kind(op) -> Optional[str]:
+    """The routing-table kind of an operator from its classes alone (nothing is lowered, no tensor is touched): the
+    kind its descriptor would have, or None for an operator the float64 kernels do not take."""
+    from . import operators as ops
+
+    if isinstance(op, ops.ConstantMulLinearOperator):
+        return _f64_route_kind(op.base_linear_op)
+    if isinstance(op, ops.SumLinearOperator):  # (AddedDiag included: a sum of its operator and its diagonal)
+        flat, stack = [], list(op.linear_ops)
+        while stack:
+            t = stack.pop()
+            if isinstance(t, ops.SumLinearOperator):
+                stack.extend(t.linear_ops)
+            elif not isinstance(t, ops.DiagLinearOperator):
+                flat.append(t)
+        if len(flat) == 1:
+            return _f64_route_kind(flat[0])
+        return "sum" if flat else None
+    if isinstance(op, ops.RootLinearOperator):
+        return "lowrank"
+    if isinstance(op, ops.KroneckerProductLinearOperator):
+        return "kron"
+    if isinstance(op, ops.DenseLinearOperator):
+        return "dense"
+    return None
+
+
+def native_matmul_candidate(op, rhs: torch.Tensor) -> bool:
+    """Whether an operator's `_matmul` should lower itself for this right-hand side at all: fp32 device blocks always;
+    float64 ones only when the routing table sends the product of THIS operator's kind and column class to
+    lo_matvec_f64 -- decided before anything is lowered, so a product that stays with ATen pays nothing for the table."""
+    if rhs.dim() < 2 or not rhs.is_cuda:
+        return False
+    if rhs.dtype == torch.float32:
+        return True
+    if rhs.dtype != torch.float64 or op.dtype != torch.float64:
+        return False
+    return bool(_NATIVE_MATMUL_F64.get((_f64_route_kind(op), 1 if rhs.shape[-1] == 1 else 2), False))
+
+
+def native_matmul(desc: Optional[OperatorDescriptor], rhs: torch.Tensor) -> bool:
+    """Whether `_matmul` hands the product of the lowered operator `desc` with `rhs` to `matvec`."""
+    if desc is None or desc.dtype != rhs.dtype:
+        return False
+    if desc.dtype == torch.float32:
+        return True
+    return bool(_NATIVE_MATMUL_F64.get((_F64_KIND_NAMES.get(desc.kind), 1 if rhs.shape[-1] == 1 else 2), False))
 
 
 def block_matvec(desc: OperatorDescriptor, layout: int, T: int, v: torch.Tensor) -> Optional[torch.Tensor]:
@@ -454,6 +596,8 @@ def block_matvec(desc: OperatorDescriptor, layout: int, T: int, v: torch.Tensor)
     LO_BLOCK_SUM with v [*batch, N, c].  None for a descriptor the kernels leave to the caller's composition
     (LO_ERR_UNSUPPORTED)."""
     lib = _hip.load()
+    if desc.dtype != torch.float32:
+        return None  # (the block kernels are fp32)
     _hip.require_hip(v)
     c = v.shape[-1]
     v3 = _flat(v, 2)
@@ -655,10 +799,13 @@ def minres_solve(desc: Optional[OperatorDescriptor], rhs: torch.Tensor, shifts: 
 def minres_solve_f64(A: Optional[torch.Tensor], rhs: torch.Tensor, shifts: torch.Tensor, *,
                      value: Optional[float] = None, matvec_closure: Optional[Callable] = None,
                      precond_closure: Optional[Callable] = None, max_iter: int = 1000, tolerance: float = 1e-4,
-                     eps: float = 1e-25) -> MinresResult:
+                     eps: float = 1e-25, desc: Optional[OperatorDescriptor] = None,
+                     precond: Optional[tuple] = None) -> MinresResult:
     """lo_minres_f64: the reference's shifted MINRES (utils/minres.py:10-207) with float64 operands -- what the
-    reference's test/utils/test_minres.py runs.  `A` [*batch, N, N] is multiplied by the library's fp64 kernel, any
-    other operator is called back once per product; `precond_closure`: any callable or None."""
+    reference's test/utils/test_minres.py runs.  `A` [*batch, N, N] is multiplied by the library's fp64 kernel, a
+    float64 descriptor `desc` by lo_matvec_f64 inside the library, any other operator is called back once per product;
+    `precond`: the cached pair (Q, noise, constant_diag) of the float64 Woodbury preconditioner, applied inside the
+    library (in place of `precond_closure`: any callable or None)."""
     lib = _hip.load()
     _hip.require_hip(rhs, A, dtype=torch.float64)
     N = rhs.shape[-2]
@@ -666,12 +813,22 @@ def minres_solve_f64(A: Optional[torch.Tensor], rhs: torch.Tensor, shifts: torch
     bshape = tuple(rhs.shape[:-2])
     rhs3, sh, prm, x = _minres_operands(rhs, shifts, value, max_iter, tolerance, eps, _hip.MinresParamsF64)
     B = rhs3.shape[0]
-    A3, _ = _dense_f64(A, None, matvec_closure, bshape, B, N)
-    mv_cb, mv_err = _wrap_closure(matvec_closure, dev, bshape, "<f8") if A3 is None else _NO_CLOSURE
-    pc_cb, pc_err = _wrap_closure(precond_closure, dev, bshape, "<f8") if precond_closure is not None else _NO_CLOSURE
+    mv_user, keep = None, None
+    if desc is not None:
+        A3, (mv_cb, mv_user, keep), mv_err = None, _f64_operator(lib, desc, B, N, rhs.shape[-1], dev), ()
+    else:
+        A3, _ = _dense_f64(A, None, matvec_closure, bshape, B, N)
+        mv_cb, mv_err = _wrap_closure(matvec_closure, dev, bshape, "<f8") if A3 is None else _NO_CLOSURE
+    pc_user, pc_keep = None, None
+    if precond is not None:
+        (pc_cb, pc_user, pc_keep), pc_err = _f64_precond(lib, precond, bshape, B, N, rhs.shape[-1], dev), ()
+    else:
+        pc_cb, pc_err = (_wrap_closure(precond_closure, dev, bshape, "<f8") if precond_closure is not None
+                         else _NO_CLOSURE)
     info = _hip.MinresInfoF64()
-    _launch("lo_minres_f64", dev, A3, None, mv_cb, None, pc_cb, None, C.byref(prm), B, N, rhs3, sh, x,
+    _launch("lo_minres_f64", dev, A3, None, mv_cb, mv_user, pc_cb, pc_user, C.byref(prm), B, N, rhs3, sh, x,
             ws_bytes=lib.lo_minres_f64_workspace_bytes(B, N, C.byref(prm)), info=info, errors=(mv_err, pc_err))
+    del keep, pc_keep
     return _minres_result(x, rhs, info)
 
 
@@ -746,7 +903,7 @@ class _CgSession:
         self.handle = out.value if rc == 0 else None
 
     def close(self):
-        if self.handle is not None:
+        if getattr(self, "handle", None) is not None:  # (absent: the constructor refused the descriptor)
             self._destroy(self.handle)
             self.handle = None
 
@@ -949,7 +1106,8 @@ _fused_ws_bytes: dict = {}  # workspace size of lo_solve_fused_f32 per (B, rank,
 def solve_fused_supported(desc: Optional[OperatorDescriptor], c: int, rank: int, max_iter: int = 1000,
                           floor_max_iter: int = 0) -> bool:
     """True if lo_solve_fused_f32 takes this operator / right-hand side shape (see include/lo_amd.h)."""
-    if desc is None or desc.kind != _hip.LO_OP_LOWRANK_DIAG or desc.A0 is None or not desc.A0.is_cuda:
+    if (desc is None or desc.kind != _hip.LO_OP_LOWRANK_DIAG or desc.A0 is None or not desc.A0.is_cuda
+            or desc.dtype != torch.float32):
         return False
     prm = _cg_params(c, 0, max_iter, min(20, max_iter), 1.0, 1e-10, 1e-10, floor_max_iter)
     s = desc.c_struct()
@@ -1005,11 +1163,14 @@ def cg_solve_f64(A: Optional[torch.Tensor], diag: Optional[torch.Tensor], rhs: t
                  x0: Optional[torch.Tensor] = None, matvec_closure: Optional[Callable] = None,
                  precond_closure: Optional[Callable] = None, n_tridiag: int = 0, max_iter: int = 1000,
                  max_tridiag_iter: int = 20, tolerance: float = 1.0, eps: float = 1e-10,
-                 stop_updating_after: float = 1e-10, floor_max_iter: int = 0) -> CGResult:
+                 stop_updating_after: float = 1e-10, floor_max_iter: int = 0,
+                 desc: Optional[OperatorDescriptor] = None, precond: Optional[tuple] = None) -> CGResult:
     """lo_cg_solve_f64: the reference's linear_cg (utils/linear_cg.py:98-359) with float64 operands -- what every case
     of the reference's test/utils/test_linear_cg.py runs.  `A` [*batch, N, N] (+ `diag` [*batch, N]) is multiplied by
-    the library's fp64 kernel; otherwise `matvec_closure` is called back once per product.  `precond_closure`: any
-    callable or None."""
+    the library's fp64 kernel, a float64 descriptor `desc` (in place of `A` / `matvec_closure`) by lo_matvec_f64 inside
+    the library; otherwise `matvec_closure` is called back once per product.  `precond`: the cached pair (Q, noise,
+    constant_diag) of the float64 Woodbury preconditioner, applied inside the library (in place of `precond_closure`:
+    any callable or None)."""
     lib = _hip.load()
     _hip.require_hip(rhs, x0, A, diag, dtype=torch.float64)
     N, c = rhs.shape[-2:]
@@ -1018,16 +1179,29 @@ def cg_solve_f64(A: Optional[torch.Tensor], diag: Optional[torch.Tensor], rhs: t
     dev = rhs.device
     bshape = tuple(rhs.shape[:-2])
     x03 = None if x0 is None else _flat(x0.expand_as(rhs), 2)
-    A3, d2 = _dense_f64(A, diag, matvec_closure, bshape, B, N)
-    mv_cb, mv_err = _wrap_closure(matvec_closure, dev, bshape, "<f8") if A3 is None else _NO_CLOSURE
-    pc_cb, pc_err = _wrap_closure(precond_closure, dev, bshape, "<f8") if precond_closure is not None else _NO_CLOSURE
+    mv_user, pc_user, keep = None, None, []
+    if desc is not None:
+        A3, d2, mv_err = None, None, ()
+        mv_cb, mv_user, alive = _f64_operator(lib, desc, B, N, c, dev)
+        keep.append(alive)
+    else:
+        A3, d2 = _dense_f64(A, diag, matvec_closure, bshape, B, N)
+        mv_cb, mv_err = _wrap_closure(matvec_closure, dev, bshape, "<f8") if A3 is None else _NO_CLOSURE
+    if precond is not None:
+        pc_cb, pc_user, alive = _f64_precond(lib, precond, bshape, B, N, c, dev)
+        pc_err = ()
+        keep.append(alive)
+    else:
+        pc_cb, pc_err = (_wrap_closure(precond_closure, dev, bshape, "<f8") if precond_closure is not None
+                         else _NO_CLOSURE)
     prm = _cg_params(c, n_tridiag, max_iter, max_tridiag_iter, tolerance, eps, stop_updating_after, floor_max_iter,
                      _hip.CgParamsF64)
     x = torch.empty_like(rhs3)
     t_mat = _tridiag_buffer(n_tridiag, B, max_tridiag_iter, rhs3)
     info = _hip.CgInfoF64()
-    _launch("lo_cg_solve_f64", dev, A3, d2, mv_cb, None, pc_cb, None, C.byref(prm), B, N, rhs3, x03, x, t_mat,
+    _launch("lo_cg_solve_f64", dev, A3, d2, mv_cb, mv_user, pc_cb, pc_user, C.byref(prm), B, N, rhs3, x03, x, t_mat,
             ws_bytes=lib.lo_cg_f64_workspace_bytes(B, N, C.byref(prm)), info=info, errors=(mv_err, pc_err))
+    del keep  # (the solver is synchronous: the contexts and workspaces of the callbacks were needed until here)
     return _cg_result(x.reshape(rhs.shape), t_mat, info)
 
 
@@ -1336,10 +1510,12 @@ def _lanczos_out(q: torch.Tensor, t: torch.Tensor, k: int, batch, q_out: Optiona
 
 
 def lanczos_tridiag_f64(A: Optional[torch.Tensor], diag: Optional[torch.Tensor], init_vecs: torch.Tensor,
-                        max_iter: int, tol: float = 1e-5, matvec_closure: Optional[Callable] = None):
+                        max_iter: int, tol: float = 1e-5, matvec_closure: Optional[Callable] = None,
+                        desc: Optional[OperatorDescriptor] = None):
     """lo_lanczos_tridiag_f64: utils/lanczos.py:9-164 with float64 operands (the reference is dtype-generic).  `A`
-    [*batch, N, N] (+ `diag` [*batch, N]) is multiplied by the library's fp64 kernel, otherwise `matvec_closure` is
-    called back once per step.  Same return shapes as `lanczos_tridiag`; q_mat is the permuted view of the basis."""
+    [*batch, N, N] (+ `diag` [*batch, N]) is multiplied by the library's fp64 kernel, a float64 descriptor `desc` by
+    lo_matvec_f64 inside the library, otherwise `matvec_closure` is called back once per step.  Same return shapes as
+    `lanczos_tridiag`; q_mat is the permuted view of the basis."""
     lib = _hip.load()
     _hip.require_hip(init_vecs, A, diag, dtype=torch.float64)
     N, P = init_vecs.shape[-2:]
@@ -1347,13 +1523,19 @@ def lanczos_tridiag_f64(A: Optional[torch.Tensor], diag: Optional[torch.Tensor],
     v3 = _flat(init_vecs, 2)
     B = v3.shape[0]
     dev = init_vecs.device
-    A3, d2 = _dense_f64(A, diag, matvec_closure, batch, B, N)
-    cb, err = _wrap_closure(matvec_closure, dev, batch, "<f8") if A3 is None else _NO_CLOSURE
+    user, keep = None, None
+    if desc is not None:
+        A3, d2, err = None, None, ()
+        cb, user, keep = _f64_operator(lib, desc, B, N, P, dev)
+    else:
+        A3, d2 = _dense_f64(A, diag, matvec_closure, batch, B, N)
+        cb, err = _wrap_closure(matvec_closure, dev, batch, "<f8") if A3 is None else _NO_CLOSURE
     max_iter = int(max_iter)
     q, t = _lanczos_buffers(max_iter, v3)
     iters = C.c_int32(0)
-    _launch("lo_lanczos_tridiag_f64", dev, A3, d2, cb, None, v3, B, N, P, max_iter, float(tol), q, t, C.byref(iters),
+    _launch("lo_lanczos_tridiag_f64", dev, A3, d2, cb, user, v3, B, N, P, max_iter, float(tol), q, t, C.byref(iters),
             ws_bytes=lib.lo_lanczos_f64_workspace_bytes(B, N, P, max_iter), errors=(err,))
+    del keep
     return _lanczos_out(q, t, iters.value, batch)
 
 

@@ -40,14 +40,20 @@ class WoodburyPreconditionClosure:
 
 class DensePreconditionClosure:
     """The same closure for float64 operators, evaluated as the reference does (two GEMMs and an elementwise scaling on
-    the device, :135-140): Q [*batch, N, k] and the noise are float64 tensors; `woodbury` is None, so `linear_cg`
-    (lo_cg_solve_f64) calls it back per iteration."""
+    the device, :135-140): Q [*batch, N, k] and the noise are float64 tensors; `woodbury` is None.  The float64
+    `linear_cg` recognises the class and applies it natively (`native_operands`); float32 preconditioners of rank > 128
+    take the same class and are called back per iteration."""
 
     woodbury = None
 
     def __init__(self, q, noise, constant_diag):
         self.q, self.constant_diag = q, bool(constant_diag)
         self.noise = noise.unsqueeze(-1)  # [*batch, N | 1, 1]
+
+    def native_operands(self):
+        """(Q, noise [*batch, N | 1], constant_diag): what `linear_cg` hands to K.cg_solve_f64(precond=...), which then
+        applies this closure inside the library (lo_precond_desc_cb_f64) instead of calling it back per iteration."""
+        return self.q, self.noise[..., 0], self.constant_diag
 
     def __call__(self, tensor: Tensor) -> Tensor:
         is_vec = tensor.dim() == 1
@@ -202,9 +208,9 @@ class AddedDiagLinearOperator(SumLinearOperator):
                             torch.Size(self.batch_shape if batch_shape is None else batch_shape))
 
     def _matmul(self, rhs: Tensor) -> Tensor:
-        if rhs.dim() >= 2 and rhs.is_cuda and rhs.dtype == torch.float32:
+        if K.native_matmul_candidate(self, rhs):
             desc = self._kernel_descriptor(torch.broadcast_shapes(self.batch_shape, rhs.shape[:-2]))
-            if desc is not None:
+            if K.native_matmul(desc, rhs):
                 return K.matvec(desc, rhs.expand(*desc.batch_shape, *rhs.shape[-2:]))
         return torch.addcmul(self._linear_op._matmul(rhs), self._diag_tensor._diag.unsqueeze(-1), rhs)
 
@@ -260,7 +266,8 @@ class AddedDiagLinearOperator(SumLinearOperator):
                     return WoodburyPreconditionClosure(entry[2], self.batch_shape)
         desc = self._kernel_descriptor()
         rank = min(settings.max_preconditioner_size.value(), self.size(-1))
-        if desc is None or not K.solve_fused_supported(desc, 1, rank, settings.max_cg_iterations.value()):
+        if (desc is None or desc.dtype != torch.float32
+                or not K.solve_fused_supported(desc, 1, rank, settings.max_cg_iterations.value())):
             return super()._solve_preconditioner()
         return LazyWoodburyPreconditionClosure(self, desc, rank, settings.preconditioner_tolerance.value(), key, tensors)
 
@@ -320,7 +327,8 @@ class AddedDiagLinearOperator(SumLinearOperator):
         preconditioner build reads it in place and the transposed copy of _pivoted_cholesky.py:105 is skipped."""
         desc = self._linear_op._kernel_descriptor()
         if (desc is None or desc.diag_mode != 0 or desc.kind == K._hip.LO_OP_MASKED or self.device.type != "cuda"
-                or self.dtype != torch.float32):  # (a masked operator: the generic row access, as PivotedCholesky.forward)
+                or self.dtype != torch.float32 or desc.dtype != torch.float32):
+            # (a masked operator: the generic row access, as PivotedCholesky.forward; float64: the row-callback route)
             L, perm = self._linear_op.pivoted_cholesky(rank=max_iter, return_pivots=True)
             from .. import distributed
 
@@ -415,7 +423,7 @@ class AddedDiagLinearOperator(SumLinearOperator):
             if self._constant_diag and perm is not None:
                 base = self._linear_op._kernel_descriptor()
                 if (base is not None and base.kind == K._hip.LO_OP_KRON_DIAG and base.diag_mode == K._hip.LO_DIAG_NONE
-                        and tuple(base.batch_shape) == tuple(batch_shape)):
+                        and base.dtype == torch.float32 and tuple(base.batch_shape) == tuple(batch_shape)):
                     kron = K._with_diag(base, d_arg.to(torch.float32), True)
             self._woodbury = K.precond_build(L, d_arg.to(torch.float32), self._constant_diag, perm=perm, kron=kron)
         # (`_q_cache is not None` = "the cache is built", as in the reference :63-70; the tensor itself is only read on the

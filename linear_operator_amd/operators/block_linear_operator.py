@@ -53,7 +53,8 @@ class BlockLinearOperator(LinearOperator):
         from .. import kernels as K
 
         desc = self.base_linear_op._kernel_descriptor(torch.Size((*batch_shape, self.num_blocks)))
-        if desc is None or desc.kind not in (K._hip.LO_OP_DENSE_DIAG, K._hip.LO_OP_LOWRANK_DIAG):
+        if (desc is None or desc.kind not in (K._hip.LO_OP_DENSE_DIAG, K._hip.LO_OP_LOWRANK_DIAG)
+                or desc.dtype != torch.float32):  # (lo_block_mv_f32: float64 bases take the composition)
             return None
         return desc
 

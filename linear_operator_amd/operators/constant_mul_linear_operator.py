@@ -44,11 +44,11 @@ class ConstantMulLinearOperator(LinearOperator):
         from .. import kernels as K
 
         c = self._constant
-        if not (c.is_cuda and c.dtype == torch.float32) or self.size(-1) != self.size(-2):
+        if not (c.is_cuda and c.dtype in (torch.float32, torch.float64)) or self.size(-1) != self.size(-2):
             return None
         bs = torch.Size(self.batch_shape if batch_shape is None else batch_shape)
         desc = self.base_linear_op._kernel_descriptor(bs)
-        if desc is None or desc.diag_mode != K._hip.LO_DIAG_NONE:
+        if desc is None or desc.diag_mode != K._hip.LO_DIAG_NONE or desc.dtype != c.dtype:
             return None
         scale = c.expand(bs).reshape(-1, 1, 1) if c.dim() else c  # one factor per flattened member
         if desc.kind in (K._hip.LO_OP_LOWRANK_DIAG, K._hip.LO_OP_HADAMARD_DIAG):
@@ -82,11 +82,11 @@ class ConstantMulLinearOperator(LinearOperator):
         return self.base_linear_op._get_indices(row_index, col_index, *batch_indices) * per_member
 
     def _matmul(self, rhs: Tensor) -> Tensor:
-        if rhs.dim() >= 2 and rhs.is_cuda and rhs.dtype == torch.float32:
-            from .. import kernels as K
+        from .. import kernels as K
 
+        if K.native_matmul_candidate(self, rhs):
             desc = self._kernel_descriptor(torch.broadcast_shapes(self.batch_shape, rhs.shape[:-2]))
-            if desc is not None:
+            if K.native_matmul(desc, rhs):
                 return K.matvec(desc, rhs.expand(*desc.batch_shape, *rhs.shape[-2:]))
         return self.expanded_constant * self.base_linear_op._matmul(rhs)
 

@@ -30,11 +30,11 @@ class DenseLinearOperator(LinearOperator):
 
     def _kernel_descriptor(self, batch_shape=None):
         t = self.tensor
-        if not (t.is_cuda and t.dtype == torch.float32 and t.shape[-1] == t.shape[-2]):
+        if not (t.is_cuda and t.dtype in (torch.float32, torch.float64) and t.shape[-1] == t.shape[-2]):
             return None
         if batch_shape is not None and tuple(batch_shape) != tuple(t.shape[:-2]):
             t = t.expand(*batch_shape, *t.shape[-2:])
-        return K.dense_diag_descriptor(t, None)
+        return K.dense_diag_descriptor(t, None, dtype=t.dtype)  # (float64: lo_matvec_f64 and the float64 solvers)
 
     def _cholesky_solve(self, rhs, upper: bool = False):
         return cholesky_solve(rhs, self.to_dense(), upper=upper)

@@ -98,8 +98,10 @@ class KroneckerProductLinearOperator(LinearOperator):
         if len(ops) < 2 or not all(isinstance(op, DenseLinearOperator) for op in ops):
             return None
         ts = [op.tensor for op in ops]
-        if not all(t.is_cuda and t.dtype == torch.float32 and t.shape[-1] == t.shape[-2] for t in ts):
+        if not all(t.is_cuda and t.dtype == ts[0].dtype and t.shape[-1] == t.shape[-2] for t in ts):
             return None
+        if ts[0].dtype != torch.float32 and not (ts[0].dtype == torch.float64 and len(ts) == 2):
+            return None  # (float64: two dense factors, for lo_matvec_f64 and the float64 solvers)
         if len(ts) == 2:
             return ts[0], ts[1], 1
         sizes = [t.shape[-1] for t in ts]
@@ -130,7 +132,7 @@ class KroneckerProductLinearOperator(LinearOperator):
         bs = torch.Size(batch_shape) if batch_shape is not None else self.batch_shape
         k1 = k1.expand(*bs, *k1.shape[-2:])
         k2 = k2.expand(*bs, *k2.shape[-2:])
-        return K.kron_diag_descriptor(k1, k2, None)
+        return K.kron_diag_descriptor(k1, k2, None, dtype=k1.dtype)
 
     def _bilinear_derivative(self, left_vecs: Tensor, right_vecs: Tensor):
         """(dK1, dK2) = (sum_d U_d K2 V_d^T, sum_d U_d^T K1 V_d): the reference's generic autograd version
@@ -222,9 +224,9 @@ class KroneckerProductLinearOperator(LinearOperator):
         if is_vec:
             rhs = rhs.unsqueeze(-1)
         desc = None
-        if rhs.is_cuda and rhs.dtype == torch.float32:
+        if K.native_matmul_candidate(self, rhs):
             desc = self._kernel_descriptor(torch.broadcast_shapes(self.batch_shape, rhs.shape[:-2]))
-        if desc is not None:
+        if K.native_matmul(desc, rhs):
             res = K.matvec(desc, rhs.expand(*desc.batch_shape, *rhs.shape[-2:]))
         else:
             res = _kron_matmul(self.linear_ops, self.shape, rhs.contiguous())

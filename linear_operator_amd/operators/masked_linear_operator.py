@@ -88,7 +88,7 @@ class MaskedLinearOperator(LinearOperator):
 
         bs = torch.Size(self.batch_shape if batch_shape is None else batch_shape)
         desc = self.base._kernel_descriptor(bs)
-        if desc is None:
+        if desc is None or desc.dtype != torch.float32:
             return None
         if desc.kind == K._hip.LO_OP_LOWRANK_DIAG:
             return self._gathered_lowrank(desc)

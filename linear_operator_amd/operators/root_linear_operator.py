@@ -40,11 +40,11 @@ class RootLinearOperator(LinearOperator):
 
     def _kernel_descriptor(self, batch_shape=None):
         r = self._dense_root()
-        if r is None or not (r.is_cuda and r.dtype == torch.float32):
+        if r is None or not (r.is_cuda and r.dtype in (torch.float32, torch.float64)):
             return None
         if batch_shape is not None and tuple(batch_shape) != tuple(r.shape[:-2]):
             r = r.expand(*batch_shape, *r.shape[-2:])
-        return K.lowrank_diag_descriptor(r, None)
+        return K.lowrank_diag_descriptor(r, None, dtype=r.dtype)  # (float64: lo_matvec_f64 and the float64 solvers)
 
     def _bilinear_derivative(self, left_vecs: Tensor, right_vecs: Tensor):
         """Derivative w.r.t. the root tensor of sum_d u_d^T R R^T v_d = U (V^T R) + V (U^T R): what the reference's
@@ -82,9 +82,9 @@ class RootLinearOperator(LinearOperator):
 
     def _matmul(self, rhs: Tensor) -> Tensor:  # reference :68-72
         desc = None
-        if rhs.dim() >= 2 and rhs.is_cuda and rhs.dtype == torch.float32:
+        if K.native_matmul_candidate(self, rhs):
             desc = self._kernel_descriptor(torch.broadcast_shapes(self.batch_shape, rhs.shape[:-2]))
-        if desc is not None:
+        if K.native_matmul(desc, rhs):
             return K.matvec(desc, rhs.expand(*desc.batch_shape, *rhs.shape[-2:]))
         return self.root._matmul(self.root._t_matmul(rhs))
 

@@ -64,9 +64,9 @@ class SumLinearOperator(LinearOperator):
                     K._hip.LO_OP_LOWRANK_DIAG, K._hip.LO_OP_DENSE_DIAG, K._hip.LO_OP_KRON_DIAG):
                 return None  # (a sum's terms: low-rank / dense / Kronecker; SKI and Toeplitz terms take the closure)
             terms.append(desc)
-        if len({(t.B, t.N) for t in terms}) != 1:
+        if len({(t.B, t.N, t.dtype) for t in terms}) != 1:
             return None
-        return _sum_with_diag(K.sum_descriptor(terms), diags[0] if diags else None, batch_shape)
+        return _sum_with_diag(K.sum_descriptor(terms, dtype=terms[0].dtype), diags[0] if diags else None, batch_shape)
 
     def _diagonal(self) -> Tensor:
         return sum(op._diagonal() for op in self.linear_ops)
@@ -78,11 +78,11 @@ class SumLinearOperator(LinearOperator):
         return sum(op._get_indices(row_index, col_index, *batch_indices) for op in self.linear_ops)
 
     def _matmul(self, rhs: Tensor) -> Tensor:  # reference :47-51
-        if rhs.dim() >= 2 and rhs.is_cuda and rhs.dtype == torch.float32:
-            desc = self._kernel_descriptor(torch.broadcast_shapes(self.batch_shape, rhs.shape[:-2]))
-            if desc is not None:
-                from .. import kernels as K
+        from .. import kernels as K
 
+        if K.native_matmul_candidate(self, rhs):
+            desc = self._kernel_descriptor(torch.broadcast_shapes(self.batch_shape, rhs.shape[:-2]))
+            if K.native_matmul(desc, rhs):
                 return K.matvec(desc, rhs.expand(*desc.batch_shape, *rhs.shape[-2:]))
         return sum(op._matmul(rhs) for op in self.linear_ops)
 
@@ -146,11 +146,11 @@ def _sum_with_diag(desc, diag_op, batch_shape):
 
     if isinstance(diag_op, ConstantDiagLinearOperator):
         vals = diag_op.diag_values
-        if not (vals.is_cuda and vals.dtype == torch.float32):
+        if not (vals.is_cuda and vals.dtype == desc.dtype):
             return None
         return K._with_diag(desc, vals.expand(*batch_shape, 1)[..., 0], True)
     d = diag_op._diag
-    if not (d.is_cuda and d.dtype == torch.float32):
+    if not (d.is_cuda and d.dtype == desc.dtype):
         return None
     return K._with_diag(desc, d.expand(*batch_shape, d.shape[-1]), False)
 

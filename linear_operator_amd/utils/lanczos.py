@@ -6,7 +6,7 @@ import torch
 
 from .. import settings
 from .. import kernels as K
-from .linear_cg import _lower_matmul_closure
+from .linear_cg import _lower_f64, _lower_matmul_closure
 
 
 def lanczos_tridiag(
@@ -45,8 +45,9 @@ def lanczos_tridiag(
     if init_vecs.dtype == torch.float64:  # the reference is dtype-generic; fp64 runs csrc/lo_lanczos_f64.hip
         if torch.is_tensor(matmul_closure):
             return K.lanczos_tridiag_f64(matmul_closure, None, init_vecs.contiguous(), num_iter, tol=tol)
-        return K.lanczos_tridiag_f64(None, None, init_vecs.contiguous(), num_iter, tol=tol,
-                                     matvec_closure=matmul_closure)
+        desc = _lower_f64(matmul_closure, init_vecs.shape[:-2], init_vecs.shape[-1]) if init_vecs.is_cuda else None
+        return K.lanczos_tridiag_f64(None, None, init_vecs.contiguous(), num_iter, tol=tol, desc=desc,
+                                     matvec_closure=None if desc is not None else matmul_closure)
     desc = _lower_matmul_closure(matmul_closure, init_vecs.shape[:-2])
     closure = None
     if desc is None:

@@ -78,8 +78,9 @@ def _fused_note(key, hit: bool):
         _FUSED_MISSES[key] = _FUSED_SKIP_AFTER_MISS
 
 
-def _lower_matmul_closure(matmul_closure, batch_shape):
-    """Return an OperatorDescriptor for closures we can run natively, else None."""
+def _lower_matmul_closure(matmul_closure, batch_shape, dtype=torch.float32):
+    """Return an OperatorDescriptor of element type `dtype` (the right-hand side's) for closures we can run natively,
+    else None: an operator of another element type is declined, never reinterpreted."""
     if torch.is_tensor(matmul_closure):
         M = matmul_closure
         if M.dim() < 2 or M.shape[-1] != M.shape[-2]:
@@ -89,8 +90,39 @@ def _lower_matmul_closure(matmul_closure, batch_shape):
     if owner is not None and getattr(matmul_closure, "__name__", "") == "_matmul" and hasattr(owner, "_kernel_descriptor"):
         if type(owner)._matmul is not getattr(matmul_closure, "__func__", None):
             return None  # instance-level override / mock
-        return owner._kernel_descriptor(batch_shape)
+        desc = owner._kernel_descriptor(batch_shape)
+        return desc if desc is not None and desc.dtype == dtype else None
     return None
+
+
+def _native_precond_f64(preconditioner):
+    """(Q, noise, constant_diag) of a DensePreconditionClosure over float64 device tensors -- applied inside the library
+    by the float64 solvers (lo_precond_desc_cb_f64) -- else None: the callable is called back."""
+    operands = getattr(preconditioner, "native_operands", None)
+    if operands is None:
+        return None
+    q, noise, constant = operands()
+    if q.is_cuda and q.dtype == torch.float64 and noise.is_cuda and noise.dtype == torch.float64:
+        return q, noise, constant
+    return None
+
+
+_F64_KINDS = (K._hip.LO_OP_LOWRANK_DIAG, K._hip.LO_OP_DENSE_DIAG, K._hip.LO_OP_KRON_DIAG, K._hip.LO_OP_SUM)
+
+
+def _lower_f64(matmul_closure, batch_shape, cols: int = 1):
+    """The float64 descriptor of a bound `_matmul` whose operator lo_matvec_f64 takes, else None (plain tensors keep the
+    dense path of the float64 engines, any other callable is called back once per product).  An operator with a dense
+    term is lowered for a single column only: with 17 columns the dense float64 kernel (one wave per row) took 3.5 ms
+    where the called-back library GEMM took 0.4 ms (tools/mb_f64.py)."""
+    if torch.is_tensor(matmul_closure):
+        return None
+    desc = _lower_matmul_closure(matmul_closure, batch_shape, torch.float64)
+    if desc is None or desc.kind not in _F64_KINDS:
+        return None
+    if cols > 1 and any(t.kind == K._hip.LO_OP_DENSE_DIAG for t in (desc.terms or (desc,))):
+        return None
+    return desc
 
 
 def linear_cg(
@@ -156,15 +188,20 @@ def linear_cg(
 
     if rhs.dtype == torch.float64:
         # the reference's fp64 recipes (test/utils/test_linear_cg.py): a dense tensor is multiplied by the library's
-        # fp64 kernel, any other closure (and any preconditioner) is called back; no Woodbury / resident engines
+        # fp64 kernel, the bound `_matmul` of an operator that lowers to a float64 descriptor by lo_matvec_f64, and the
+        # dense Woodbury closure of AddedDiagLinearOperator is applied inside the library too; any other closure or
+        # preconditioner is called back.  No resident engines.
         if _active_stop_reduce() is not None:
             raise NotImplementedError("the batch-global stopping rule over ranks is fp32 only")
         dense = matmul_closure if torch.is_tensor(matmul_closure) and matmul_closure.dim() >= 2 else None
+        desc = _lower_f64(matmul_closure, batch_shape, rhs.shape[-1]) if rhs.is_cuda else None
+        native_pre = _native_precond_f64(preconditioner) if rhs.is_cuda else None
         res = K.cg_solve_f64(
-            dense, None, rhs, x0=initial_guess,
-            matvec_closure=None if dense is not None else (
+            dense, None, rhs, x0=initial_guess, desc=desc, precond=native_pre,
+            matvec_closure=None if dense is not None or desc is not None else (
                 matmul_closure.matmul if torch.is_tensor(matmul_closure) else matmul_closure),
-            precond_closure=preconditioner, n_tridiag=n_tridiag, max_iter=n_iter, max_tridiag_iter=n_tridiag_iter,
+            precond_closure=None if native_pre is not None else preconditioner,
+            n_tridiag=n_tridiag, max_iter=n_iter, max_tridiag_iter=n_tridiag_iter,
             tolerance=float(tolerance), eps=float(eps), stop_updating_after=float(stop_updating_after),
             floor_max_iter=max_iter,
         )

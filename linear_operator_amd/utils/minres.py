@@ -9,7 +9,7 @@ import torch
 
 from .. import kernels as K
 from .. import settings
-from .linear_cg import _lower_matmul_closure
+from .linear_cg import _lower_f64, _lower_matmul_closure, _native_precond_f64
 
 
 def minres(matmul_closure, rhs, eps=1e-25, shifts=None, value=None, max_iter=None, preconditioner=None):
@@ -39,15 +39,18 @@ def minres(matmul_closure, rhs, eps=1e-25, shifts=None, value=None, max_iter=Non
 
     sh = shifts.reshape(1) if shifts.dim() == 0 else shifts
     if rhs.dtype == torch.float64:
-        # the reference's fp64 recipes (test/utils/test_minres.py): dense tensors on the library's fp64 kernel, any
-        # other closure / preconditioner called back (csrc/lo_minres_f64.hip)
+        # the reference's fp64 recipes (test/utils/test_minres.py): dense tensors on the library's fp64 kernel, the
+        # bound `_matmul` of an operator with a float64 descriptor on lo_matvec_f64, any other closure / preconditioner
+        # called back (csrc/lo_minres_f64.hip)
         dense = matmul_closure if torch.is_tensor(matmul_closure) and matmul_closure.dim() >= 2 else None
+        desc = _lower_f64(matmul_closure, batch_shape, rhs_b.shape[-1]) if rhs_b.is_cuda else None
+        native_pre = _native_precond_f64(preconditioner) if rhs_b.is_cuda else None
         res = K.minres_solve_f64(
-            dense, rhs_b, sh, value=value,
-            matvec_closure=None if dense is not None else (
+            dense, rhs_b, sh, value=value, desc=desc, precond=native_pre,
+            matvec_closure=None if dense is not None or desc is not None else (
                 matmul_closure.matmul if torch.is_tensor(matmul_closure) else matmul_closure),
-            precond_closure=preconditioner, max_iter=max_iter, tolerance=float(settings.minres_tolerance.value()),
-            eps=float(eps),
+            precond_closure=None if native_pre is not None else preconditioner, max_iter=max_iter,
+            tolerance=float(settings.minres_tolerance.value()), eps=float(eps),
         )
         solution = res.x
         if squeeze:
