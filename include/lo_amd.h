@@ -65,6 +65,11 @@ extern "C" {
 #define LO_DIAG_FULL 1  /* DiagLinearOperator._diag [B, N]         (diag_linear_operator.py:25)      */
 #define LO_DIAG_CONST 2 /* ConstantDiagLinearOperator.diag_values [B] (diag_linear_operator.py:313)  */
 
+#define LO_OP_SKI_GRID_DIAG 9 /* AddedDiag(Interpolated(Kron(Toeplitz(t_1), .., Toeplitz(t_D)), W_l, W_r), Diag(d)), D = 2 or 3:
+                               *   y = W_l (T_1 (x) .. (x) T_D) W_r^T v + d o v   (SKI on a 2-D / 3-D grid)             */
+#define LO_SKI_GRID_MAX_AXIS 1024 /* grid points per axis the native grid product takes (larger: LO_ERR_UNSUPPORTED)    */
+#define LO_SKI_GRID_MAX_M 4194304 /* grid points in all, 2^22 (larger: LO_ERR_UNSUPPORTED)                              */
+
 struct lo_interp_desc;
 struct lo_mask_desc;
 
@@ -97,13 +102,19 @@ typedef struct lo_op_desc {
    * ABI 21 kind.  MASKED: `mask` as below, N = mask->M, B = mask->base->B; its own (diag_mode, d) with d of length M is
    * the diagonal OUTSIDE the mask, the base's own diagonal the one inside (same layout again).  Lowered for
    * lo_matvec_f32, the streaming CG, Lanczos and fp32 MINRES; lo_pivoted_cholesky_f32 and the fp64 entry points return
-   * LO_ERR_UNSUPPORTED; not a term kind of LO_OP_SUM.                                                              */
+   * LO_ERR_UNSUPPORTED; not a term kind of LO_OP_SUM.
+   * ABI 23 kind.  SKI_GRID: A0 = the first columns of the D Toeplitz factors concatenated per member
+   * [B, M_1 + .. + M_D], R = M = M_1 * .. * M_D (grid points, grid index g = (g_1 M_2 + g_2) M_3 + g_3), n2 = J,
+   * `interp` as for SKI with the grid shape in its grid_ndim / grid_m (same layout again).  Lowered for lo_matvec_f32,
+   * the streaming CG, Lanczos, fp32 MINRES and the fp32 pivoted Cholesky; the fp64 entry points, the resident / fused
+   * engines and the solve sessions return LO_ERR_UNSUPPORTED; not a term kind of LO_OP_SUM, not a base kind of
+   * LO_OP_MASKED.                                                                                                    */
 } lo_op_desc;
 
 /* The base operator and the selected rows of an LO_OP_MASKED descriptor (masked_linear_operator.py:17-35 with
  * row_mask == col_mask): y = S (base) S^T v + d o v, S selecting the rows idx of the base.  base: HOST descriptor of
- * kind LOWRANK_DIAG, DENSE_DIAG, KRON_DIAG or SUM with any diagonal mode of its own (CALLBACK, MASKED, SKI, TOEPLITZ,
- * HADAMARD: LO_ERR_UNSUPPORTED).  idx: DEVICE pointer, int64 [M], strictly increasing, one list for all members; an
+ * kind LOWRANK_DIAG, DENSE_DIAG, KRON_DIAG or SUM with any diagonal mode of its own (CALLBACK, MASKED, SKI, SKI_GRID,
+ * TOEPLITZ, HADAMARD: LO_ERR_UNSUPPORTED).  idx: DEVICE pointer, int64 [M], strictly increasing, one list for all members; an
  * entry outside [0, base->N) contributes nothing and is never dereferenced (the convention of lo_interp_desc).      */
 struct lo_mask_desc { /* (a plain struct tag: C callers write `struct lo_mask_desc`) */
   const struct lo_op_desc* base;
@@ -123,6 +134,10 @@ typedef struct lo_interp_desc {
   const int64_t* right_idx;  /* [B, N, J] */
   const float* right_vals;   /* [B, N, J] */
   const void* right_plan;    /* optional, see above */
+  /* ABI 23, LO_OP_SKI_GRID_DIAG only (LO_OP_SKI_DIAG ignores them; 0 = the ABI-16 meaning, a 1-D grid): the grid shape */
+  int32_t grid_ndim;         /* D: 2 or 3 */
+  int32_t grid_reserved;
+  int64_t grid_m[3];         /* M_1 .. M_D (grid_m[2] unused when D == 2), each <= LO_SKI_GRID_MAX_AXIS */
 } lo_interp_desc;
 
 /* Callbacks for LO_OP_CALLBACK and for a user preconditioner closure.
@@ -757,6 +772,19 @@ int lo_toeplitz_bilinear_f32(const float* u, const float* v, int64_t B, int64_t 
                              size_t ws_bytes, void* stream);
 int lo_interp_values_grad_f32(const int64_t* idx, int64_t B, int64_t N, int64_t J, int64_t M, const float* lv,
                               const float* R, int64_t S, float* g, void* stream);
+
+/* ---- SKI on a 2-D / 3-D grid (ABI 23; csrc/lo_ski_grid.hip) -------------------------------------------------------
+ * The grid product y = (T_1 (x) .. (x) T_D) u of D = ndim in {2, 3} symmetric Toeplitz factors, one axis per pass and no
+ * M_k x M_k matrix anywhere (kronecker_product_linear_operator.py:272-284 over toeplitz_linear_operator.py:42-53).
+ *   t   [B, M_1 + .. + M_D]: the factors' first columns, concatenated per member;  m [ndim]: HOST array M_1 .. M_D
+ *   u   [B, M_1, .., M_D, c] row-major, columns fastest (= [B, M, c] with the grid index g = (g_1 M_2 + g_2) M_3 + g_3)
+ *   y   the same shape; must not alias u.  ws: one grid vector (the _workspace_bytes query).
+ * Fixed-order sums (ascending along every axis), no float atomics: the same inputs give the same bits.
+ * LO_ERR_UNSUPPORTED: ndim outside {2, 3}, an axis beyond LO_SKI_GRID_MAX_AXIS, M beyond LO_SKI_GRID_MAX_M;
+ * LO_ERR_BADARG: null pointers, non-positive sizes.  The kind LO_OP_SKI_GRID_DIAG wraps it between W_r^T and W_l. */
+size_t lo_toeplitz_kron_workspace_bytes(const int64_t* m, int ndim, int64_t B, int64_t c);
+int lo_toeplitz_kron_mv_f32(const float* t, const int64_t* m, int ndim, int64_t B, const float* u, int64_t c, float* y,
+                            void* ws, size_t ws_bytes, void* stream);
 
 /* ---- Hadamard product of two roots (ABI 17; csrc/lo_hadamard.hip) -------------------------------------------------
  * K = (F F^T) o (G G^T), F [B, N, p], G [B, N, q], p, q <= LO_HADAMARD_MAX_RANK; U, V [B, N, S], S columns innermost.

@@ -161,7 +161,8 @@ struct MatvecPlan {
   int nterms;
   MatvecPlan* sub;
   float* ytmp;        // [B,N,c]
-  // LO_OP_SKI_DIAG / LO_OP_TOEPLITZ_DIAG (lo_ski.hip): the interpolation matrices, the grid-major copy of W_r built by
+  // LO_OP_SKI_DIAG / LO_OP_TOEPLITZ_DIAG (lo_ski.hip), LO_OP_SKI_GRID_DIAG (lo_ski_grid.hip; no tz_part, the grid shape
+  // rides in `ski`): the interpolation matrices, the grid-major copy of W_r built by
   // matvec_plan_init, the grid-sized intermediates u = W_r^T v and T u, and the split-k partials of the Toeplitz product
   lo_interp_desc ski;
   int* csr_ptr;       // [B, M+1]
@@ -210,6 +211,21 @@ int matvec_run_pupdate(const MatvecPlan* pl, float* p, const float* z, const flo
 size_t ski_plan_bytes(const lo_op_desc* op, int64_t c);
 int ski_plan_init(MatvecPlan* pl, const lo_op_desc* op, int64_t c, Arena* ar, hipStream_t st);
 int ski_matvec_run(const MatvecPlan* pl, const float* v, float* y, const int* stop, hipStream_t st);
+// the interpolation kernels and the grid-major copy of W, shared with the grid kind (lo_ski_grid.hip)
+bool interp_shape_ok(int64_t B, int64_t N, int64_t J, int64_t M);
+int interp_gather(const int64_t* idx, const float* vals, int64_t B, int64_t N, int64_t J, int64_t M, const float* u,
+                  int64_t c, const float* dd, int dd_mode, const float* v, float* y, const int* stop, hipStream_t st);
+int interp_scatter(const int* ptr, const int* ids, const float* vals, int64_t B, int64_t N, int64_t J, int64_t M,
+                   const float* v, int64_t c, float* out, const int* stop, hipStream_t st);
+size_t csr_bytes(int64_t B, int64_t N, int64_t J, int64_t M);
+int csr_build(const int64_t* idx, int64_t B, int64_t N, int64_t J, int64_t M, Arena* ar, int** ptr_out, int** ids_out,
+              hipStream_t st);
+void csr_view(const void* plan, int64_t B, int64_t N, int64_t J, int64_t M, int** ptr_out, int** ids_out);
+
+// ---- SKI on a 2-D / 3-D grid (lo_ski_grid.hip): LO_OP_SKI_GRID_DIAG, the plan fields of the SKI kind ----------------
+size_t ski_grid_plan_bytes(const lo_op_desc* op, int64_t c);
+int ski_grid_plan_init(MatvecPlan* pl, const lo_op_desc* op, int64_t c, Arena* ar, hipStream_t st);
+int ski_grid_matvec_run(const MatvecPlan* pl, const float* v, float* y, const int* stop, hipStream_t st);
 
 // ---- Hadamard product of two roots (lo_hadamard.hip) ---------------------------------------------------------------
 size_t hadamard_plan_bytes(const lo_op_desc* op, int64_t c);

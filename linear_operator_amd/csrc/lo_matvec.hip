@@ -42,6 +42,8 @@ size_t matvec_plan_bytes(const lo_op_desc* op, int64_t c, Split sp) {
     if (ks > 1) ar.take<float>((size_t)ks * op->B * op->N * c);
   } else if (op->kind == LO_OP_SKI_DIAG || op->kind == LO_OP_TOEPLITZ_DIAG) {
     return ski_plan_bytes(op, c) + 256;
+  } else if (op->kind == LO_OP_SKI_GRID_DIAG) {
+    return ski_grid_plan_bytes(op, c) + 256;
   } else if (op->kind == LO_OP_HADAMARD_DIAG) {
     return hadamard_plan_bytes(op, c) + 256;
   } else if (op->kind == LO_OP_MASKED) {
@@ -116,6 +118,11 @@ int matvec_plan_init(MatvecPlan* pl, const lo_op_desc* op, lo_matvec_cb cb, void
     case LO_OP_SKI_DIAG:
     case LO_OP_TOEPLITZ_DIAG: {
       const int rc = ski_plan_init(pl, op, c, ar, st);
+      if (rc) return rc;
+      break;
+    }
+    case LO_OP_SKI_GRID_DIAG: {
+      const int rc = ski_grid_plan_init(pl, op, c, ar, st);
       if (rc) return rc;
       break;
     }
@@ -205,6 +212,10 @@ int matvec_run(const MatvecPlan* pl, const float* v, float* y, float* dot_part, 
       rc = ski_matvec_run(pl, v, y, stop, st);
       if (!rc && dot_part) rc = vec_dot_part(v, y, pl->c, dot_part, op.B, op.N, pl->sp, stop, st);
       return rc;
+    case LO_OP_SKI_GRID_DIAG:  // W_l (T_1 (x) .. (x) T_D) W_r^T v + d o v: the same with one pass per grid axis
+      rc = ski_grid_matvec_run(pl, v, y, stop, st);
+      if (!rc && dot_part) rc = vec_dot_part(v, y, pl->c, dot_part, op.B, op.N, pl->sp, stop, st);
+      return rc;
     case LO_OP_HADAMARD_DIAG:  // (F F^T o G G^T) v + d o v: contraction M_t = F^T diag(v_t) G, expansion rowdot(F, G M_t^T)
       rc = hadamard_matvec_run(pl, v, y, stop, st);
       if (!rc && dot_part) rc = vec_dot_part(v, y, pl->c, dot_part, op.B, op.N, pl->sp, stop, st);
@@ -249,7 +260,7 @@ using namespace lo;
 
 extern "C" {
 
-int lo_abi_version(void) { return 22; }
+int lo_abi_version(void) { return 23; }
 const char* lo_target_arch(void) { return "gfx950"; }
 
 size_t lo_matvec_workspace_bytes(const lo_op_desc* op, int64_t c) {

@@ -141,6 +141,33 @@ __device__ __forceinline__ T src_diag(const PcDevT<T>& d, const lo_op_desc& op, 
       r = (j == 0) ? rt : r + rt;
     }
     return l * r;
+  } else if (op.kind == LO_OP_SKI_GRID_DIAG) {
+    // the same over the constant base diagonal t0 = prod_k t_k[0] (the Kronecker diagonal of the reference multiplies
+    // the trailing factors first, kronecker_product_linear_operator.py:22-28)
+    const int J = (int)op.n2;
+    const int64_t M = op.R;
+    const int D = d.ski.grid_ndim;
+    int64_t sumM = 0;
+    for (int k = 0; k < D; ++k) sumM += d.ski.grid_m[k];
+    const T* col = A0 + (size_t)b * sumM;
+    T t0 = col[sumM - d.ski.grid_m[D - 1]];
+    for (int64_t k = D - 2, o = sumM - d.ski.grid_m[D - 1]; k >= 0; --k) {
+      o -= d.ski.grid_m[k];
+      t0 = col[o] * t0;
+    }
+    const T s = pc_sqrt<T>(t0);
+    const int64_t* li = d.ski.left_idx + ((size_t)b * d.N + i) * J;
+    const int64_t* ri = d.ski.right_idx + ((size_t)b * d.N + i) * J;
+    const T* lv = pc_ptr<T>(d.ski.left_vals) + ((size_t)b * d.N + i) * J;
+    const T* rv = pc_ptr<T>(d.ski.right_vals) + ((size_t)b * d.N + i) * J;
+    T l = T(0), r = T(0);
+    for (int j = 0; j < J; ++j) {
+      const T lt = (li[j] >= 0 && li[j] < M) ? s * lv[j] : T(0);
+      const T rt = (ri[j] >= 0 && ri[j] < M) ? s * rv[j] : T(0);
+      l = (j == 0) ? lt : l + lt;
+      r = (j == 0) ? rt : r + rt;
+    }
+    return l * r;
   } else {
     const int n1 = (int)op.R, n2 = (int)op.n2;
     const int i1 = i / n2, i2 = i % n2;
@@ -425,6 +452,39 @@ __global__ __launch_bounds__(kThreads) void k_pc_update(PcDevT<T> d, int m) {
               tv = (bb == 0 && a == 0) ? base * (lv[a] * rv[bb]) : tv + base * (lv[a] * rv[bb]);
             }
           }
+        } else if (tm.kind == LO_OP_SKI_GRID_DIAG) {
+          // the same sum in the same order with base[g, h] = prod_k t_k[|g_k - h_k|], factors multiplied left to right
+          // (kronecker_product_linear_operator.py:198-216), g and h decomposed by the grid shape
+          const int J = (int)tm.n2;
+          const int M = (int)tm.R;  // (<= LO_SKI_GRID_MAX_M: 32-bit index arithmetic)
+          const int D = d.ski.grid_ndim;
+          const int m1 = (int)d.ski.grid_m[D - 2], m2 = (int)d.ski.grid_m[D - 1];  // the two trailing axes
+          const int m0 = D == 3 ? (int)d.ski.grid_m[0] : 0;
+          const T* c0 = pc_ptr<T>(tm.A0) + (size_t)b * (m0 + m1 + m2);  // (D == 2: no leading axis)
+          const T* c1 = c0 + m0;
+          const T* c2 = c1 + m1;
+          const int64_t* li = d.ski.left_idx + ((size_t)b * N + pim) * J;
+          const T* lv = pc_ptr<T>(d.ski.left_vals) + ((size_t)b * N + pim) * J;
+          const int64_t* ri = d.ski.right_idx + ((size_t)b * N + i) * J;
+          const T* rv = pc_ptr<T>(d.ski.right_vals) + ((size_t)b * N + i) * J;
+          for (int bb = 0; bb < J; ++bb) {
+            const int64_t q64 = ri[bb];
+            const bool q_ok = q64 >= 0 && q64 < M;
+            const int q = q_ok ? (int)q64 : 0;
+            const int q2 = q % m2, q1 = (q / m2) % m1, q0 = q / (m2 * m1);
+            for (int a = 0; a < J; ++a) {
+              const int64_t p64 = li[a];
+              const bool p_ok = p64 >= 0 && p64 < M;
+              const int p = p_ok ? (int)p64 : 0;
+              const int p2 = p % m2, p1 = (p / m2) % m1, p0 = p / (m2 * m1);
+              T base = T(0);
+              if (p_ok && q_ok) {
+                const T f1 = c1[p1 > q1 ? p1 - q1 : q1 - p1], f2 = c2[p2 > q2 ? p2 - q2 : q2 - p2];
+                base = D == 3 ? (c0[p0 > q0 ? p0 - q0 : q0 - p0] * f1) * f2 : f1 * f2;
+              }
+              tv = (bb == 0 && a == 0) ? base * (lv[a] * rv[bb]) : tv + base * (lv[a] * rv[bb]);
+            }
+          }
         } else {
           const int n1 = (int)tm.R, n2 = (int)tm.n2;
           const int p1 = pim / n2, p2 = pim % n2, i1 = i / n2, i2 = i % n2;
@@ -477,7 +537,8 @@ static void pc_layout(const lo_op_desc* op, int max_rank, Arena& ar, PcDevT<T>* 
     d->nterms = 1;
     d->terms[0] = *op;
   }
-  d->ski = (op->kind == LO_OP_SKI_DIAG && op->interp) ? *op->interp : lo_interp_desc{};
+  d->ski = ((op->kind == LO_OP_SKI_DIAG || op->kind == LO_OP_SKI_GRID_DIAG) && op->interp) ? *op->interp
+                                                                                            : lo_interp_desc{};
   d->B = B; d->N = N; d->S = sp.S; d->rows = sp.rows; d->max_rank = max_rank;
   d->ctrl = ar.take<PcCtrl>(1);
   d->diag = ar.take<T>((size_t)B * N);
@@ -593,6 +654,18 @@ static int pc_check_desc(const lo_op_desc* op) {
     const lo_interp_desc* w = op->interp;
     if (!op->A0 || op->R < 1 || op->n2 < 1 || !w || !w->left_idx || !w->left_vals || !w->right_idx || !w->right_vals)
       return LO_ERR_BADARG;
+  } else if (op->kind == LO_OP_SKI_GRID_DIAG) {
+    const lo_interp_desc* w = op->interp;
+    if (!op->A0 || op->R < 1 || op->n2 < 1 || !w || !w->left_idx || !w->left_vals || !w->right_idx || !w->right_vals)
+      return LO_ERR_BADARG;
+    if (w->grid_ndim != 2 && w->grid_ndim != 3) return LO_ERR_UNSUPPORTED;
+    int64_t M = 1;
+    for (int k = 0; k < w->grid_ndim; ++k) {
+      if (w->grid_m[k] < 1 || w->grid_m[k] > LO_SKI_GRID_MAX_AXIS) return LO_ERR_UNSUPPORTED;
+      M *= w->grid_m[k];
+    }
+    if (M > LO_SKI_GRID_MAX_M) return LO_ERR_UNSUPPORTED;
+    if (M != op->R) return LO_ERR_BADARG;
   } else if (op->kind != LO_OP_LOWRANK_DIAG && op->kind != LO_OP_DENSE_DIAG && op->kind != LO_OP_KRON_DIAG) {
     return LO_ERR_UNSUPPORTED;
   }
@@ -661,7 +734,8 @@ size_t lo_pivoted_cholesky_f64_workspace_bytes(const lo_op_desc* op, int32_t max
 int lo_pivoted_cholesky_f64(const lo_op_desc* op, int32_t max_rank, double error_tol, double* L_rows, int64_t* perm,
                             int32_t* rank_out, void* ws, size_t ws_bytes, void* stream) {
   if (!op || !L_rows || !perm || !rank_out || !ws || max_rank < 1) return LO_ERR_BADARG;
-  if (op->kind == LO_OP_SKI_DIAG || op->kind == LO_OP_TOEPLITZ_DIAG || op->kind == LO_OP_HADAMARD_DIAG)
+  if (op->kind == LO_OP_SKI_DIAG || op->kind == LO_OP_TOEPLITZ_DIAG || op->kind == LO_OP_HADAMARD_DIAG ||
+      op->kind == LO_OP_SKI_GRID_DIAG)
     return LO_ERR_UNSUPPORTED;  // (fp32 kinds)
   if (const int rc = pc_check_desc(op)) return rc;
   return pc_stream_t<double>(op, nullptr, nullptr, nullptr, max_rank, error_tol, L_rows, perm, rank_out, ws, ws_bytes,

@@ -64,7 +64,7 @@ static unsigned grid_for(size_t total) {
   return (unsigned)std::max<size_t>(1, std::min<size_t>(g, 8192));
 }
 
-static bool interp_shape_ok(int64_t B, int64_t N, int64_t J, int64_t M) {
+bool interp_shape_ok(int64_t B, int64_t N, int64_t J, int64_t M) {
   return B >= 1 && N >= 1 && J >= 1 && M >= 1 && N * J <= INT_MAX - 1 && M <= INT_MAX - 2;
 }
 
@@ -189,7 +189,7 @@ int csr_build(const int64_t* idx, int64_t B, int64_t N, int64_t J, int64_t M, Ar
 }
 
 // (ptr, ids) of a grid-major copy built by csr_build into `plan` (the layout of csr_bytes)
-static void csr_view(const void* plan, int64_t B, int64_t N, int64_t J, int64_t M, int** ptr_out, int** ids_out) {
+void csr_view(const void* plan, int64_t B, int64_t N, int64_t J, int64_t M, int** ptr_out, int** ids_out) {
   Arena ar(const_cast<void*>(plan), csr_bytes(B, N, J, M));
   *ptr_out = ar.take<int>((size_t)B * (M + 1));
   ar.take<int>((size_t)B * (M + 1));

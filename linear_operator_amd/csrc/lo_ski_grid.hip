@@ -1,0 +1,303 @@
+// lo_ski_grid.hip -- SKI on a 2-D / 3-D grid: the base of the interpolated operator is a Kronecker product of D symmetric
+// Toeplitz matrices, one per grid axis (GridInterpolationKernel on multi-dimensional inputs).
+//   KroneckerProductLinearOperator._matmul (kronecker_product_linear_operator.py:272-284) over
+//   ToeplitzLinearOperator._matmul         (toeplitz_linear_operator.py:42-53)
+//
+// The grid vector is u [B, M_1, .., M_D, c], row-major, columns fastest: the [B, M, c] layout of the interpolation
+// kernels of lo_ski.hip with the grid index g = (g_1 M_2 + g_2) M_3 + g_3.  (T_1 (x) .. (x) T_D) u is applied one axis
+// per pass.  For axis k the vector is viewed as [lines = B * outer, M_k, inner], inner = (prod_{j > k} M_j) c, and
+//   y[l, i, s] = sum_j t_k[|i - j|] u[l, j, s],   j ascending.
+// No M_k x M_k matrix exists: the lags of a member are staged in LDS as the mirrored window win[x] = t_k[|x - off|], so
+// that the lag of (i, j) is read at win[i - j + off] without an absolute value in the loop.  One workgroup owns the whole
+// sum of its outputs (M_k <= LO_SKI_GRID_MAX_AXIS: no split over j, no partials), sums run in ascending j: the same
+// inputs give the same bits.
+//
+// Two lane mappings, chosen from the shape alone:
+//   k_grid_axis_inner  inner >= 64: the 64 lanes of a wave run along `inner` (coalesced rows of u and y), the four waves
+//                      of a workgroup take different output rows i, RI rows per thread.  A [64 j x 64 s] tile of u is
+//                      staged in LDS and shared by the four waves; the lags of a wave are wave-uniform (LDS broadcast
+//                      reads), 2 RI - 1 of them serve RI x RI products.
+//   k_grid_axis_line   inner < 64 (the last axis with few columns): a thread per output element of a line [M_k, inner],
+//                      consecutive threads on consecutive elements (i, s) -- lanes run along i -- with the line staged
+//                      in LDS in chunks of j.  The reads of the line are broadcasts of at most `inner` consecutive
+//                      addresses, the reads of the window consecutive addresses: no bank conflicts.  Lines shorter than
+//                      a workgroup share one.
+#include <algorithm>
+#include <climits>
+
+#include "lo_device.h"
+#include "lo_internal.h"
+
+namespace lo {
+
+constexpr int kGridMaxAxis = LO_SKI_GRID_MAX_AXIS;
+constexpr int kGridPad = 64;                                // j runs to the next multiple of 64 in k_grid_axis_inner
+constexpr int kGridWin = 2 * kGridMaxAxis + 2 * kGridPad;   // mirrored lag window (+ the rows / j beyond M_k)
+constexpr int kGridTile = 64;                               // j tile and s tile of k_grid_axis_inner
+constexpr int kGridStage = 4096;                            // floats of a line chunk in k_grid_axis_line
+
+// win[x] = t[|x - off|] where that lag exists, else 0
+__device__ __forceinline__ void grid_stage_window(const float* __restrict__ t, int M, int off, int n, float* win) {
+  for (int x = threadIdx.x; x < n; x += kThreads) {
+    const int d = x - off;
+    const int ad = d < 0 ? -d : d;
+    win[x] = ad < M ? t[ad] : 0.f;
+  }
+}
+
+// blockIdx.x = (line, i tile, s tile), s tile fastest
+template <int RI>
+__global__ __launch_bounds__(kThreads) void k_grid_axis_inner(const float* __restrict__ t, int64_t tstride, int M,
+                                                               int64_t outer, int64_t inner, int stiles, int itiles,
+                                                               const float* __restrict__ u, float* __restrict__ y,
+                                                               const int* __restrict__ stop) {
+  if (stop && *stop) return;
+  __shared__ float us[kGridTile * kGridTile];
+  __shared__ float win[kGridWin];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const size_t blk = blockIdx.x;
+  const int st = (int)(blk % stiles);
+  const int it = (int)((blk / stiles) % itiles);
+  const size_t line = blk / ((size_t)stiles * itiles);
+  const size_t b = line / outer;
+  const int64_t s = (int64_t)st * kGridTile + lane;
+  const bool s_ok = s < inner;
+  const int i0 = (it * 4 + wave) * RI;  // first output row of this wave
+  const int off = M - 1 + kGridPad;
+  const float* ul = u + line * (size_t)M * inner;
+  float* yl = y + line * (size_t)M * inner;
+  grid_stage_window(t + b * tstride, M, off, 2 * M - 1 + 2 * kGridPad, win);
+  float acc[RI];
+#pragma unroll
+  for (int r = 0; r < RI; ++r) acc[r] = 0.f;
+  for (int j0 = 0; j0 < M; j0 += kGridTile) {
+    __syncthreads();
+#pragma unroll 4
+    for (int jj = wave; jj < kGridTile; jj += 4) {
+      const int j = j0 + jj;
+      us[jj * kGridTile + lane] = (j < M && s_ok) ? ul[(size_t)j * inner + s] : 0.f;
+    }
+    __syncthreads();
+    // lag of (row i0 + r, column j0 + jb + q) at w[r - q]; per block of RI columns the 2 RI - 1 lags wl[x] = w[x - (RI - 1)]
+    for (int jb = 0; jb < kGridTile; jb += RI) {
+      const float* w = win + (i0 - (j0 + jb) + off);
+      float wl[2 * RI - 1];
+#pragma unroll
+      for (int x = 0; x < 2 * RI - 1; ++x) wl[x] = w[x - (RI - 1)];
+#pragma unroll
+      for (int q = 0; q < RI; ++q) {
+        const float uv = us[(jb + q) * kGridTile + lane];
+#pragma unroll
+        for (int r = 0; r < RI; ++r) acc[r] = fmaf(wl[r - q + RI - 1], uv, acc[r]);
+      }
+    }
+  }
+  if (s_ok) {
+#pragma unroll
+    for (int r = 0; r < RI; ++r)
+      if (i0 + r < M) yl[(size_t)(i0 + r) * inner + s] = acc[r];
+  }
+}
+
+// blockIdx.x = (line group, block of the line), block of the line fastest; lpb lines per workgroup (LS < 256) or
+// bpl workgroups per line
+__global__ __launch_bounds__(kThreads) void k_grid_axis_line(const float* __restrict__ t, int64_t tstride, int M,
+                                                              int64_t outer, int inner, int64_t lines, int lpb, int bpl,
+                                                              int jc, const float* __restrict__ u,
+                                                              float* __restrict__ y, const int* __restrict__ stop) {
+  if (stop && *stop) return;
+  __shared__ float ls[kGridStage];
+  __shared__ float win[kGridWin];
+  const int LS = M * inner;  // floats of a line (<= 1024 * 63)
+  const size_t grp = blockIdx.x / bpl;
+  const int lb = (int)(blockIdx.x % bpl);
+  const size_t line0 = grp * lpb;
+  const int nl = (int)std::min<int64_t>(lpb, lines - (int64_t)line0);  // lines of this workgroup
+  // (the window is per member: the host keeps the lines of a workgroup inside one member -- lpb divides outer)
+  const size_t b = line0 / outer;
+  const int off = M - 1;
+  grid_stage_window(t + b * tstride, M, off, 2 * M - 1, win);
+  const int e = lb * kThreads + threadIdx.x;  // element of the workgroup's lines
+  const int ll = e / LS;                     // line within the group
+  const int el = e - ll * LS;
+  const int i = el / inner, s = el - i * inner;
+  const bool live = ll < nl;
+  const float* ug = u + line0 * (size_t)LS;
+  float acc = 0.f;
+  for (int j0 = 0; j0 < M; j0 += jc) {
+    const int nj = min(jc, M - j0);
+    __syncthreads();
+    // rows j0 .. j0 + nj of every line of the group: [nl][nj * inner], contiguous per line
+    const int per = nj * inner;
+    for (int x = threadIdx.x; x < nl * per; x += kThreads) {
+      const int l = x / per, r = x - l * per;
+      ls[x] = ug[(size_t)l * LS + (size_t)j0 * inner + r];
+    }
+    __syncthreads();
+    if (live) {
+      const float* lp = ls + ll * per + s;
+      const float* w = win + (i - j0 + off);
+#pragma unroll 4
+      for (int jj = 0; jj < nj; ++jj) acc = fmaf(w[-jj], lp[jj * inner], acc);
+    }
+  }
+  if (live) y[line0 * (size_t)LS + e] = acc;
+}
+
+static bool grid_shape_ok(const int64_t* m, int ndim, int64_t* M_out) {
+  if (ndim != 2 && ndim != 3) return false;
+  int64_t M = 1;
+  for (int k = 0; k < ndim; ++k) {
+    if (m[k] < 1 || m[k] > kGridMaxAxis) return false;
+    M *= m[k];
+  }
+  if (M > LO_SKI_GRID_MAX_M) return false;
+  *M_out = M;
+  return true;
+}
+
+// one axis: y = (I (x) T_k (x) I) u on [B * outer, Mk, inner]
+static int grid_axis(const float* t, int64_t tstride, int64_t B, int64_t outer, int64_t Mk, int64_t inner, const float* u,
+                     float* y, const int* stop, hipStream_t st) {
+  const int64_t lines = B * outer;
+  if (inner >= 64) {
+    const int64_t stiles = (inner + kGridTile - 1) / kGridTile;
+    // 8 rows per thread when that still fills the device, else 2 (a function of the shape only)
+    const bool big = lines * stiles * ((Mk + 31) / 32) >= 512;
+    const int rows = big ? 32 : 8;
+    const int64_t itiles = (Mk + rows - 1) / rows;
+    const int64_t nblk = lines * stiles * itiles;
+    if (stiles > INT_MAX || nblk > INT_MAX) return LO_ERR_UNSUPPORTED;
+    if (big)
+      hipLaunchKernelGGL((k_grid_axis_inner<8>), dim3((unsigned)nblk), dim3(kThreads), 0, st, t, tstride, (int)Mk, outer,
+                         inner, (int)stiles, (int)itiles, u, y, stop);
+    else
+      hipLaunchKernelGGL((k_grid_axis_inner<2>), dim3((unsigned)nblk), dim3(kThreads), 0, st, t, tstride, (int)Mk, outer,
+                         inner, (int)stiles, (int)itiles, u, y, stop);
+  } else {
+    const int64_t LS = Mk * inner;
+    int lpb = 1, bpl = 1, jc = (int)Mk;
+    if (LS >= kThreads) {
+      bpl = (int)((LS + kThreads - 1) / kThreads);
+      jc = (int)std::min<int64_t>(Mk, kGridStage / inner);
+    } else {
+      // several lines per workgroup, all of one member: the largest divisor of `outer` not above 256 / LS
+      lpb = (int)std::min<int64_t>(kThreads / LS, outer);
+      while (outer % lpb) --lpb;
+    }
+    const int64_t nblk = (lines + lpb - 1) / lpb * bpl;
+    if (nblk > INT_MAX) return LO_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(k_grid_axis_line, dim3((unsigned)nblk), dim3(kThreads), 0, st, t, tstride, (int)Mk, outer,
+                       (int)inner, lines, lpb, bpl, jc, u, y, stop);
+  }
+  return LO_OK;
+}
+
+size_t toeplitz_kron_ws_bytes(int64_t B, int64_t M, int64_t c) {
+  return align_up((size_t)B * M * c * sizeof(float), 256) + 256;
+}
+
+// D passes, axis 1 first, ping-pong between the two grid vectors buf0 / buf1: the passes read src, buf1, buf0 and write
+// buf1, buf0, buf1, so the result is in buf0 (D = 2) or buf1 (D = 3), returned through *out.  src may be buf0 itself
+// (it is consumed by the first pass before the second overwrites it) or a read-only input.
+int toeplitz_kron_passes(const float* t, const int64_t* m, int ndim, int64_t B, int64_t c, const float* src, float* buf0,
+                         float* buf1, float** out, const int* stop, hipStream_t st) {
+  int64_t M = 1, sumM = 0;
+  for (int k = 0; k < ndim; ++k) {
+    M *= m[k];
+    sumM += m[k];
+  }
+  const float* in = src;
+  float* bufs[2] = {buf1, buf0};
+  int64_t outer = 1, toff = 0;
+  LO_PROF_BEGIN("ski_grid_mv", st);
+  for (int k = 0; k < ndim; ++k) {
+    const int64_t inner = M / (outer * m[k]) * c;
+    float* dst = bufs[k & 1];
+    const int rc = grid_axis(t + toff, sumM, B, outer, m[k], inner, in, dst, stop, st);
+    if (rc) {
+      LO_PROF_END(st);
+      return rc;
+    }
+    in = dst;
+    outer *= m[k];
+    toff += m[k];
+  }
+  LO_PROF_END(st);
+  LO_LAUNCH_CHECK();
+  *out = bufs[(ndim - 1) & 1];
+  return LO_OK;
+}
+
+// ---- pieces of the matvec plan (lo_matvec.hip): the plan of lo_ski.hip with the Toeplitz product replaced ------------
+size_t ski_grid_plan_bytes(const lo_op_desc* op, int64_t c) {
+  const int64_t M = op->R;
+  size_t total = 2 * (align_up((size_t)op->B * M * c * sizeof(float), 256) + 256);
+  if (!op->interp || !op->interp->right_plan) total += csr_bytes(op->B, op->N, op->n2, M);
+  return total;
+}
+
+int ski_grid_plan_init(MatvecPlan* pl, const lo_op_desc* op, int64_t c, Arena* ar, hipStream_t st) {
+  const lo_interp_desc* w = op->interp;
+  if (!op->A0 || !w || !w->left_idx || !w->left_vals || !w->right_idx || !w->right_vals) return LO_ERR_BADARG;
+  int64_t M = 0;
+  if (!grid_shape_ok(w->grid_m, w->grid_ndim, &M)) return LO_ERR_UNSUPPORTED;
+  if (M != op->R) return LO_ERR_BADARG;
+  if (!interp_shape_ok(op->B, op->N, op->n2, M) || c > INT_MAX / 64) return LO_ERR_BADARG;
+  pl->ski = *w;
+  pl->ski_u = ar->take<float>((size_t)op->B * M * c);
+  pl->ski_t = ar->take<float>((size_t)op->B * M * c);
+  if (!ar->ok) return LO_ERR_WORKSPACE;
+  if (w->right_plan) {
+    csr_view(w->right_plan, op->B, op->N, op->n2, M, &pl->csr_ptr, &pl->csr_ids);
+  } else {
+    const int rc = csr_build(w->right_idx, op->B, op->N, op->n2, M, ar, &pl->csr_ptr, &pl->csr_ids, st);
+    if (rc) return rc;
+  }
+  return ar->ok ? LO_OK : LO_ERR_WORKSPACE;
+}
+
+int ski_grid_matvec_run(const MatvecPlan* pl, const float* v, float* y, const int* stop, hipStream_t st) {
+  const lo_op_desc& op = pl->op;
+  const int64_t M = op.R;
+  int rc = interp_scatter(pl->csr_ptr, pl->csr_ids, pl->ski.right_vals, op.B, op.N, op.n2, M, v, pl->c, pl->ski_u, stop,
+                          st);
+  float* g = nullptr;  // the passes write ski_t, ski_u, ski_t: the result is in ski_u (D = 2) or ski_t (D = 3)
+  if (!rc) rc = toeplitz_kron_passes(op.A0, pl->ski.grid_m, pl->ski.grid_ndim, op.B, pl->c, pl->ski_u, pl->ski_u,
+                                     pl->ski_t, &g, stop, st);
+  if (!rc) rc = interp_gather(pl->ski.left_idx, pl->ski.left_vals, op.B, op.N, op.n2, M, g, pl->c, op.d, op.diag_mode, v,
+                              y, stop, st);
+  return rc;
+}
+
+}  // namespace lo
+
+using namespace lo;
+
+extern "C" {
+
+size_t lo_toeplitz_kron_workspace_bytes(const int64_t* m, int ndim, int64_t B, int64_t c) {
+  int64_t M = 0;
+  if (!m || B < 1 || c < 1 || !grid_shape_ok(m, ndim, &M)) return 0;
+  return toeplitz_kron_ws_bytes(B, M, c);
+}
+
+int lo_toeplitz_kron_mv_f32(const float* t, const int64_t* m, int ndim, int64_t B, const float* u, int64_t c, float* y,
+                            void* ws, size_t ws_bytes, void* stream) {
+  if (!t || !m || !u || !y || !ws || B < 1 || c < 1 || u == y) return LO_ERR_BADARG;
+  if (ndim != 2 && ndim != 3) return LO_ERR_UNSUPPORTED;
+  for (int k = 0; k < ndim; ++k)
+    if (m[k] < 1) return LO_ERR_BADARG;
+  int64_t M = 0;
+  if (!grid_shape_ok(m, ndim, &M)) return LO_ERR_UNSUPPORTED;
+  if (c > INT_MAX / 64 || (size_t)B * M * c > (size_t)1 << 40) return LO_ERR_UNSUPPORTED;
+  if (ws_bytes < toeplitz_kron_ws_bytes(B, M, c) - 256) return LO_ERR_WORKSPACE;
+  // u -> ws -> y (D = 2), u -> y -> ws -> y (D = 3): the last pass writes y
+  float* out = nullptr;
+  float* w = (float*)ws;
+  const int rc = ndim == 2 ? toeplitz_kron_passes(t, m, ndim, B, c, u, y, w, &out, nullptr, (hipStream_t)stream)
+                           : toeplitz_kron_passes(t, m, ndim, B, c, u, w, y, &out, nullptr, (hipStream_t)stream);
+  return rc;
+}
+
+}  // extern "C"

@@ -130,9 +130,14 @@ def pivoted_cholesky_vjp(linear_op, full_permutation, grad_L, generic=False, fac
         return [_dense_root_vjp(reps[0].detach(), perm, grad_L, m, factor=factor, accumulate_into=acc,
                                 consume_grad=consume_grad)]
     inv_perm = inverse_permutation(perm)
+    # (when some tensors of the representation ask for a gradient only those become leaves: an operator that cannot
+    #  differentiate with respect to one of the others -- the Toeplitz columns of a Kronecker base under an
+    #  InterpolatedLinearOperator -- still gets theirs; a caller whose tensors ask for none gets all, as before)
+    selective = any(t.requires_grad for t in reps)
     leaves = []
-    for t in linear_op.representation():
-        leaves.append(t.detach().requires_grad_(True) if t.dtype.is_floating_point else t.detach())
+    for t in reps:
+        wanted = t.dtype.is_floating_point and (t.requires_grad or not selective)
+        leaves.append(t.detach().requires_grad_(True) if wanted else t.detach())
     with torch.enable_grad():
         op = linear_op.representation_tree()(*leaves)
         if isinstance(op, RootLinearOperator) and op._dense_root() is not None:

@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 import itertools
+import math
 import os
 import threading
 from collections import OrderedDict
@@ -36,6 +37,7 @@ class OperatorDescriptor:
     interp: tuple = ()  # LO_OP_SKI_DIAG: (left_idx, left_vals, right_idx, right_vals), [B, N, J] int64 / fp32
     interp_plan: Optional[torch.Tensor] = None  # LO_OP_SKI_DIAG: grid-major copy of W_r kept across calls (interp_plan)
     mask: tuple = ()  # LO_OP_MASKED: (descriptor of the base operator, idx int64 [M] of the selected rows)
+    grid: tuple = ()  # LO_OP_SKI_GRID_DIAG: the grid shape (M_1, .., M_D); A0 = the factors' columns [B, M_1 + .. + M_D]
     # element type of A0 / A1 / d.  The C struct does not record it: float64 descriptors (low-rank / dense / Kronecker /
     # sums of those) go to lo_matvec_f64 and the float64 solvers only, and c_struct() refuses to hand one to an entry
     # point that reads `float*`
@@ -73,6 +75,9 @@ class OperatorDescriptor:
         if self.interp:  # the union slot `interp`: a host struct of the four device pointers
             w = _hip.InterpDesc(*[t.data_ptr() for t in self.interp],
                                 None if self.interp_plan is None else self.interp_plan.data_ptr())
+            if self.grid:
+                w.grid_ndim = len(self.grid)
+                w.grid_m = (C.c_int64 * 3)(*self.grid)
             s.terms = C.cast(C.pointer(w), C.POINTER(_hip.OpDesc))
             s._interp_keepalive = w
         if self.mask:  # the union slot `mask`: a host struct of the base's host descriptor and the device index list
@@ -85,7 +90,7 @@ class OperatorDescriptor:
     def without_diag(self) -> "OperatorDescriptor":
         return OperatorDescriptor(self.kind, self.B, self.N, self.A0, self.A1, None, _hip.LO_DIAG_NONE, self.R,
                                   self.n2, self.batch_shape, self.terms, self.interp, self.interp_plan, self.mask,
-                                  self.dtype)
+                                  self.grid, self.dtype)
 
 
 def _check_dtype(dtype, *tensors):
@@ -324,6 +329,94 @@ def ski_diag_descriptor(column: torch.Tensor, left_idx: torch.Tensor, left_vals:
     ri, rv = (li, lv) if shared else (flat(right_idx), flat(right_vals))
     return _with_diag(OperatorDescriptor(_hip.LO_OP_SKI_DIAG, B, N, A0=col, R=M, n2=J, batch_shape=batch,
                                          interp=(li, lv, ri, rv), interp_plan=right_plan), d, const_diag)
+
+
+# Memo of the concatenated columns of a Kronecker-of-Toeplitz base, keyed on the factors' column tensors (address, version
+# counter, layout) and the batch they were expanded to: every lowering of one operator then hands the kernels the SAME
+# tensor (the preconditioner cache recognises its operator by that address), and the small copy is made once.  The entry
+# keeps the columns alive, so no address is reused while it exists; an in-place update bumps the version counter.
+SKI_GRID_COLS_MEMO_SIZE = 4
+_ski_grid_cols_memo: "list[tuple]" = []
+
+
+def _ski_grid_columns(cols, batch) -> torch.Tensor:
+    """[B, M_1 + .. + M_D] fp32: the factors' first columns [*b_k, M_k] expanded to `batch` and concatenated per member."""
+    keyed = not any(t.is_inference() for t in cols)
+    key = None
+    if keyed:
+        key = (tuple((t.data_ptr(), t._version, tuple(t.shape), tuple(t.stride())) for t in cols), tuple(batch))
+    if keyed:
+        for entry in _ski_grid_cols_memo:
+            if entry[0] == key:
+                return entry[2]
+    with torch.no_grad():
+        cat = torch.cat([t.detach().expand(*batch, t.shape[-1]).reshape(-1, t.shape[-1]) for t in cols], -1).contiguous()
+    if keyed:
+        _ski_grid_cols_memo.insert(0, (key, tuple(cols), cat))
+        del _ski_grid_cols_memo[SKI_GRID_COLS_MEMO_SIZE:]
+    return cat
+
+
+def clear_ski_grid_memo():
+    _ski_grid_cols_memo.clear()
+
+
+def ski_grid_shape_ok(grid) -> bool:
+    """Whether the native grid product takes a grid of this shape: 2 or 3 axes of at most LO_SKI_GRID_MAX_AXIS points,
+    at most LO_SKI_GRID_MAX_M points in all."""
+    return (len(grid) in (2, 3) and all(1 <= m <= _hip.LO_SKI_GRID_MAX_AXIS for m in grid)
+            and math.prod(grid) <= _hip.LO_SKI_GRID_MAX_M)
+
+
+def ski_grid_diag_descriptor(cols, left_idx: torch.Tensor, left_vals: torch.Tensor, right_idx: torch.Tensor,
+                             right_vals: torch.Tensor, d: Optional[torch.Tensor], const_diag: bool = False,
+                             right_plan: Optional[torch.Tensor] = None):
+    """AddedDiag(Interpolated(Kron(Toeplitz(cols[0]), .., Toeplitz(cols[D-1])), W_l, W_r), Diag(d)), D = 2 or 3:
+    y = W_l (T_1 (x) .. (x) T_D) W_r^T v + d o v.  cols[k] [*b_k, M_k] (batch shapes that broadcast to the indices'),
+    indices int64 / values fp32 [*batch, N, J] into the grid of M = prod M_k points, g = (g_1 M_2 + g_2) M_3 + g_3.  The
+    columns are concatenated once per (columns, batch) and memoised.  None when the shapes are outside what the kind
+    takes."""
+    cols = list(cols)
+    _hip.require_hip(*cols, left_vals, right_vals, d)
+    grid = tuple(int(t.shape[-1]) for t in cols)
+    batch = left_idx.shape[:-2]
+    N, J = left_idx.shape[-2:]
+    if (not ski_grid_shape_ok(grid) or right_idx.shape[-2:] != (N, J) or right_idx.shape[:-2] != batch
+            or left_idx.dtype != torch.int64 or right_idx.dtype != torch.int64 or not left_idx.is_cuda
+            or not right_idx.is_cuda):
+        return None
+    col = _ski_grid_columns(cols, batch)
+    B = col.shape[0]
+
+    def flat(t):
+        return t.expand(*batch, N, J).contiguous().reshape(B, N, J)
+
+    li, lv = flat(left_idx), flat(left_vals)
+    shared = right_idx is left_idx and right_vals is left_vals
+    ri, rv = (li, lv) if shared else (flat(right_idx), flat(right_vals))
+    return _with_diag(OperatorDescriptor(_hip.LO_OP_SKI_GRID_DIAG, B, N, A0=col, R=math.prod(grid), n2=J,
+                                         batch_shape=batch, interp=(li, lv, ri, rv), interp_plan=right_plan, grid=grid),
+                      d, const_diag)
+
+
+def toeplitz_kron_mv(cols, u: torch.Tensor) -> torch.Tensor:
+    """(T_1 (x) .. (x) T_D) u for the symmetric Toeplitz matrices of cols[k] [B, M_k], D = 2 or 3; u [B, M, c] with
+    M = prod M_k and the grid index g = (g_1 M_2 + g_2) M_3 + g_3 (lo_toeplitz_kron_mv_f32).  A shape the kernel does
+    not take raises."""
+    lib = _hip.load()
+    cols = [t.contiguous() for t in cols]
+    _hip.require_hip(*cols, u)
+    grid = [int(t.shape[-1]) for t in cols]
+    B, M, c = u.shape
+    if any(t.dim() != 2 or t.shape[0] != B for t in cols) or math.prod(grid) != M:
+        raise RuntimeError(f"toeplitz_kron_mv: columns of sizes {[tuple(t.shape) for t in cols]} for u {tuple(u.shape)}")
+    t = torch.cat(cols, -1).contiguous()
+    u = u.contiguous()
+    y = torch.empty_like(u)
+    m = (C.c_int64 * len(grid))(*grid)
+    _launch("lo_toeplitz_kron_mv_f32", u.device, t, m, len(grid), B, u, c, y,
+            ws_bytes=lib.lo_toeplitz_kron_workspace_bytes(m, len(grid), B, c))
+    return y
 
 
 def hadamard_diag_descriptor(F: torch.Tensor, G: torch.Tensor, d: Optional[torch.Tensor], const_diag: bool = False):

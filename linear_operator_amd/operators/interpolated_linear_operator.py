@@ -5,8 +5,9 @@ sparse interpolation matrices with J nonzeros per row, stored as int64 indices a
 
 With a symmetric Toeplitz base and fp32 HIP tensors, a square operator lowers to LO_OP_SKI_DIAG (csrc/lo_ski.hip):
 `_matmul`, CG, Lanczos, MINRES and the pivoted Cholesky run on the device, W_r^T v from a grid-major copy of W_r built
-once per plan.  Other bases (a Kronecker product of Toeplitz factors on a 2-D grid, dense bases) and rectangular
-operators compose the interpolation kernels (utils/interpolation.py) with the base's own `_matmul`.
+once per plan.  A Kronecker product of 2 or 3 Toeplitz factors (SKI on a 2-D / 3-D grid) lowers to LO_OP_SKI_GRID_DIAG
+(csrc/lo_ski_grid.hip) the same way.  Other bases (dense bases, more factors) and rectangular operators compose the
+interpolation kernels (utils/interpolation.py) with the base's own `_matmul`.
 """
 from __future__ import annotations
 
@@ -33,6 +34,28 @@ def _to_helper(*args, **kwargs):
         elif torch.is_tensor(arg):
             device, dtype = arg.device, arg.dtype
     return device, dtype
+
+
+# Which products of the grid kind `_matmul` hands to the kernels, by (grid axes, one column / more columns): True only
+# where tools/mb_ski_grid.py measured the native product at least as fast as the composition `_matmul` otherwise runs
+# (DESIGN.md section 6h holds both times of every cell).  A cell that is absent keeps the composition; the descriptor
+# still serves CG, Lanczos, MINRES and the pivoted Cholesky, where it replaces a Python call per product.  Measured
+# (native / composition, microseconds; 1 column, 17 columns):
+#   2-D  1 x 65536 on 128 (x) 128, J 16            40 /   382     112 /  4288
+#   2-D  16 x 16384 on 64 (x) 64, J 16            153 /   533     275 /  2397
+#   3-D  1 x 65536 on 32 (x) 32 (x) 32, J 64      121 /  2939     308 / 41478
+_NATIVE_MATMUL: dict = {(2, 1): True, (2, 2): True, (3, 1): True, (3, 2): True}
+
+
+def _toeplitz_kron_columns(base):
+    """The factors' first columns when `base` is a Kronecker product of 2 or 3 symmetric Toeplitz operators, else None."""
+    from .kronecker_product_linear_operator import KroneckerProductLinearOperator
+
+    if not isinstance(base, KroneckerProductLinearOperator) or len(base.linear_ops) not in (2, 3):
+        return None
+    if not all(isinstance(op, ToeplitzLinearOperator) for op in base.linear_ops):
+        return None
+    return [op.column for op in base.linear_ops]
 
 
 class InterpolatedLinearOperator(LinearOperator):
@@ -86,10 +109,11 @@ class InterpolatedLinearOperator(LinearOperator):
 
     # ------------------------------------------------------------------ lowering
     def _kernel_descriptor(self, batch_shape=None):
-        """LO_OP_SKI_DIAG for a square operator over a symmetric Toeplitz base, fp32 HIP tensors; else None."""
+        """LO_OP_SKI_DIAG for a square operator over a symmetric Toeplitz base, LO_OP_SKI_GRID_DIAG over a Kronecker
+        product of 2 or 3 of them (axes and grid within the kernel's limits), fp32 HIP tensors; else None."""
         base = self.base_linear_op
         if not isinstance(base, ToeplitzLinearOperator):
-            return None
+            return self._grid_descriptor(batch_shape)
         col = base.column
         li, lv, ri, rv = (self.left_interp_indices, self.left_interp_values, self.right_interp_indices,
                           self.right_interp_values)
@@ -110,6 +134,33 @@ class InterpolatedLinearOperator(LinearOperator):
         # the grid-major copy of W_r is kept across calls (memo keyed on the index tensor): a matvec or a solve on the
         # same indices does not rebuild it
         desc = K.ski_diag_descriptor(col.expand(*bs, M), li_e, lv_e, ri_e, rv_e, None)
+        if desc is not None:
+            desc.interp_plan = K.interp_plan(ri, bs, M)
+        return desc
+
+    def _grid_descriptor(self, batch_shape=None):
+        cols = _toeplitz_kron_columns(self.base_linear_op)
+        if cols is None:
+            return None
+        li, lv, ri, rv = (self.left_interp_indices, self.left_interp_values, self.right_interp_indices,
+                          self.right_interp_values)
+        if not all(t.is_cuda and t.dtype == torch.float32 for t in (*cols, lv, rv)) or not (li.is_cuda and ri.is_cuda):
+            return None
+        if li.shape[-2:] != ri.shape[-2:]:
+            return None
+        from .. import kernels as K
+
+        grid = tuple(int(t.shape[-1]) for t in cols)
+        if not K.ski_grid_shape_ok(grid):
+            return None
+        bs = torch.Size(self.batch_shape if batch_shape is None else batch_shape)
+        M = self.base_linear_op.size(-1)
+        N, J = li.shape[-2:]
+        shared = li is ri and lv is rv
+        ex = lambda t: t.expand(*bs, N, J)  # noqa: E731
+        li_e, lv_e = ex(li), ex(lv)
+        ri_e, rv_e = (li_e, lv_e) if shared else (ex(ri), ex(rv))
+        desc = K.ski_grid_diag_descriptor(cols, li_e, lv_e, ri_e, rv_e, None)
         if desc is not None:
             desc.interp_plan = K.interp_plan(ri, bs, M)
         return desc
@@ -168,6 +219,9 @@ class InterpolatedLinearOperator(LinearOperator):
             rhs = rhs.unsqueeze(-1)
         if rhs.is_cuda and rhs.dtype == torch.float32 and self.size(-1) == self.size(-2):
             desc = self._kernel_descriptor(torch.broadcast_shapes(self.batch_shape, rhs.shape[:-2]))
+            if desc is not None and desc.grid and not _NATIVE_MATMUL.get(
+                    (len(desc.grid), 1 if rhs.shape[-1] == 1 else 2), False):
+                desc = None  # (a cell of the routing table where the composition measured faster)
             if desc is not None:
                 from .. import kernels as K
 
@@ -227,8 +281,20 @@ class InterpolatedLinearOperator(LinearOperator):
         right_res = left_t_interp(ri, rv, right_vecs, base.size(-1))
         base_grads = op._base_grads(left_res, right_res)
         # interpolation-value gradients: gather-dot of the vectors with the base's products on the grid
-        rr = op.base_linear_op._matmul(right_res).contiguous()
-        ll = op.base_linear_op._t_matmul(left_res).contiguous()
+        cols = _toeplitz_kron_columns(op.base_linear_op)
+        grid_native = False
+        if cols is not None and right_res.is_cuda and right_res.dtype == torch.float32 and all(
+                t.is_cuda and t.dtype == torch.float32 for t in cols):
+            from .. import kernels as K
+
+            grid_native = K.ski_grid_shape_ok(tuple(int(t.shape[-1]) for t in cols))
+        if grid_native:  # the two grid products through the native Kronecker-of-Toeplitz kernel (symmetric: T^T = T)
+            flat_cols = [t.detach().expand(*batch, t.shape[-1]).reshape(-1, t.shape[-1]) for t in cols]
+            gp = lambda g: K.toeplitz_kron_mv(flat_cols, g.reshape(-1, *g.shape[-2:])).reshape(g.shape)  # noqa: E731
+            rr, ll = gp(right_res), gp(left_res)
+        else:
+            rr = op.base_linear_op._matmul(right_res).contiguous()
+            ll = op.base_linear_op._t_matmul(left_res).contiguous()
         native = (rr.is_cuda and rr.dtype == torch.float32 and li.is_cuda and li.dtype == torch.int64
                   and left_vecs.dtype == torch.float32)
         if native:
