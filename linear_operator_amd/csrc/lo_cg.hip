@@ -557,12 +557,6 @@ __global__ __launch_bounds__(kThreads) void k_cg_final(CgDev d, float* __restric
 // workgroup slots (no device memory is read, nothing is launched).  lo_cg_solve_f32 executes this plan; the only
 // decisions left to run time are the fall-backs after an occupancy query refuses a kernel or a hand-off times out.
 // Exported as lo_cg_plan_f32 so that the selection matrix has a table-driven test (tests/test_host_api.py).
-static int padded_rank(int64_t R) {  // floats per row of a rank-R factor (C, Q) as the skinny kernels read it
-  int64_t rq = (R + 3) / 4, p = 1;
-  while (p < rq) p <<= 1;
-  return (int)(4 * p);
-}
-
 struct CgShape {  // what cg_layout allocates for the resident paths (it sizes the workspace from the same predicates)
   bool oc_shape, has_ab, has_ls_gbuf, has_zero_q, pf_shape, sc_shape, sc_alloc, rs_cols;
 };
@@ -687,10 +681,10 @@ static int oc_record_iters(const lo_cg_params* prm) {
 
 static size_t cg_layout(const lo_op_desc* op, const lo_precond_desc* pre, bool pre_cb, const lo_cg_params* prm,
                         void* ws, size_t ws_bytes, CgDev* d, MatvecPlan* pl, lo_matvec_cb mv_cb, void* mv_user,
-                        const float** Qpad, float** upart, hipStream_t st, int* rc_out, bool init) {
+                        const float** Qpad, float** upart, hipStream_t st, int* rc_out) {
   const int64_t B = op->B, N = op->N, c = prm->c;
   Split sp = choose_split(B, N, 256);
-  Arena ar(ws, ws_bytes);
+  Arena ar(ws, ws_bytes);  // (ws == nullptr: the sizing pass -- the same takes, nothing staged)
   const size_t nv = (size_t)B * N * c;
   const bool precond = pre != nullptr || pre_cb;
   CgDev dd;
@@ -730,7 +724,7 @@ static size_t cg_layout(const lo_op_desc* op, const lo_precond_desc* pre, bool p
   dd.prev_beta = ar.take<float>(nt);
   dd.ctrl_part = ar.take<float>(3 * 256);
   // operator-resident fast path scratch (c == 1): granule buffer, error word, per-iteration residuals
-  dd.oc_err = reinterpret_cast<int*>(reinterpret_cast<char*>(dd.ctrl) + offsetof(CgCtrl, oc_err));  // (+ oc_next)
+  dd.oc_err = dd.ctrl ? &dd.ctrl->oc_err : nullptr;  // (+ oc_next; nullptr in the sizing pass)
   const int oc_iters = oc_record_iters(prm);
   const CgShape shp = cg_shape(op, pre, pre_cb, prm);  // (the predicates cg_plan decides on)
   const bool oc_shape = shp.oc_shape;
@@ -765,7 +759,7 @@ static size_t cg_layout(const lo_op_desc* op, const lo_precond_desc* pre, bool p
     if (upart) *upart = up;
     if (pre->Q && pre->ldq != R4) {
       float* qp = ar.take<float>((size_t)B * N * R4);
-      if (init && ar.ok && ws) {
+      if (!ar.measuring() && ar.ok) {
         if (pre->ldq != pre->k) { if (rc_out) *rc_out = LO_ERR_BADARG; }
         else {
           int rc = pad_rows(pre->Q, pre->k, qp, R4, B * N, st);
@@ -777,15 +771,12 @@ static size_t cg_layout(const lo_op_desc* op, const lo_precond_desc* pre, bool p
       *Qpad = pre->Q;
     }
   }
-  // matvec plan
-  if (init) {
-    int rc = matvec_plan_init(pl, op, mv_cb, mv_user, c, sp, &ar, st);
-    if (rc && rc_out) *rc_out = rc;
-  } else {
-    ar.off += matvec_plan_bytes(op, c, sp);
-  }
+  // matvec plan (laid out by the same call in both passes; the sizing pass keeps none)
+  MatvecPlan scratch;
+  const int rc = matvec_plan_init(pl ? pl : &scratch, op, mv_cb, mv_user, c, sp, &ar, st);
+  if (rc && rc_out) *rc_out = rc;
   if (d) *d = dd;
-  if (init && !ar.ok && rc_out && *rc_out == LO_OK) *rc_out = LO_ERR_WORKSPACE;
+  if (!ar.ok && rc_out && *rc_out == LO_OK) *rc_out = LO_ERR_WORKSPACE;
   return ar.off + 1024;
 }
 
@@ -911,7 +902,7 @@ static int cg_setup(CgSolve& s, lo_matvec_cb matvec, void* matvec_user, float* t
   s.dbg = CgDebug::read(env, s.B);
   int rc = LO_OK;
   cg_layout(op, pre, s.precond_cb != nullptr, prm, ws, ws_bytes, &s.d, &s.pl, matvec, matvec_user, &s.Qp, &s.upart, s.st,
-            &rc, true);
+            &rc);
   if (rc) return rc;
   CgDev& d = s.d;
   s.sp = s.pl.sp;
@@ -1030,11 +1021,11 @@ static int resident_close(CgSolve& s, const OnchipArgs& a, bool lean, bool dense
 // One attempt of the resident phase: lean = result-only pass, dense = the dense form of the R-space iteration.
 static int resident_attempt(CgSolve& s, int attempt, bool lean, bool dense, OcNext* next) {
   CgDev& d = s.d; const lo_precond_desc* pre = s.pre; const lo_cg_params* prm = s.prm; lo_cg_plan& ex = s.exec;
-  const int64_t B = s.B, N = s.N; const int c = s.c, RC = s.pl.R4, ocR4 = s.oc_nopre ? 4 : s.preR4;
+  const int64_t B = s.B, N = s.N; const int c = s.c, RC = s.pl.lr.R4, ocR4 = s.oc_nopre ? 4 : s.preR4;
   hipStream_t st = s.st;
   *next = OcNext::kStream;
   OnchipArgs a;
-  a.C = s.pl.Apad; a.d = s.op->d; a.d_mode = s.op->diag_mode;
+  a.C = s.pl.lr.Apad; a.d = s.op->d; a.d_mode = s.op->diag_mode;
   if (s.oc_nopre) {
     if (ex.lockstep_cols < c && ex.serial_engine == LO_ENGINE_RESIDENT_GEN2) {  // (the root form needs no Q)
       LO_HIP_CHECK(hipMemsetAsync(d.oc_zero_q, 0, sizeof(float) * (size_t)B * N * 4, st));
@@ -1568,8 +1559,8 @@ int lo_cg_session_create_f32(const lo_op_desc* op, const lo_precond_desc* pre, c
     return LO_ERR_WORKSPACE;
   }
   // (the part of cg_setup this plan needs; the operands are used where they are)
-  memset(&s.pl, 0, sizeof(s.pl));
-  s.pl.op = *op; s.pl.c = 1; s.pl.Apad = op->A0; s.pl.lda = s.pl.R4 = padded_rank(op->R);
+  s.pl = MatvecPlan();
+  s.pl.op = *op; s.pl.c = 1; s.pl.lr.Apad = op->A0; s.pl.lr.lda = s.pl.lr.R4 = padded_rank(op->R);
   s.Qp = pre->Q;
   s.sw = env.sw;
   s.dbg = CgDebug::read(env, s.B);
@@ -1641,10 +1632,10 @@ size_t lo_cg_workspace_bytes(const lo_op_desc* op, const lo_precond_desc* pre, c
     p = &dummy;
   }
   size_t need = cg_layout(op, p, true, prm, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                          nullptr, false);
+                          nullptr);
   if (!pre)  // the unpreconditioned resident path stages an all-zero Q instead of z
     need = std::max(need, cg_layout(op, nullptr, false, prm, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                    nullptr, nullptr, nullptr, false));
+                                    nullptr, nullptr, nullptr));
   return need;
 }
 

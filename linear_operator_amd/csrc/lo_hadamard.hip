@@ -340,33 +340,28 @@ static int hd_contract(const HdShape& s, const float* F, const float* G, const f
   return LO_OK;
 }
 
-size_t hadamard_plan_bytes(const lo_op_desc* op, int64_t c) {
+int hadamard_plan(MatvecPlan* pl, Arena* ar, hipStream_t) {
+  const lo_op_desc& op = pl->op;
   HdShape s;
-  if (!hd_shape(op->B, op->N, op->R, op->n2, c, &s)) return 256;
-  return align_up(s.part_floats * sizeof(float), 256) + align_up(s.m_floats * sizeof(float), 256) + 512;
-}
-
-int hadamard_plan_init(MatvecPlan* pl, const lo_op_desc* op, int64_t c, Arena* ar) {
-  HdShape s;
-  if (!op->A0 || !op->A1 || op->R < 1 || op->n2 < 1) return LO_ERR_BADARG;
-  if (!hd_shape(op->B, op->N, op->R, op->n2, c, &s)) return LO_ERR_UNSUPPORTED;
-  pl->hd_part = ar->take<float>(s.part_floats);
-  pl->hd_m = ar->take<float>(s.m_floats);
-  return ar->ok ? LO_OK : LO_ERR_WORKSPACE;
+  if (!op.A0 || !op.A1 || op.R < 1 || op.n2 < 1) return LO_ERR_BADARG;
+  if (!hd_shape(op.B, op.N, op.R, op.n2, pl->c, &s)) return LO_ERR_UNSUPPORTED;
+  pl->hd.part = ar->take<float>(s.part_floats);
+  pl->hd.m = ar->take<float>(s.m_floats);
+  return LO_OK;
 }
 
 int hadamard_matvec_run(const MatvecPlan* pl, const float* v, float* y, const int* stop, hipStream_t st) {
   const lo_op_desc& op = pl->op;
   HdShape s;
   if (!hd_shape(op.B, op.N, op.R, op.n2, pl->c, &s)) return LO_ERR_UNSUPPORTED;
-  int rc = hd_contract(s, op.A0, op.A1, v, (int)pl->c, nullptr, pl->hd_part, pl->hd_m, nullptr, stop, st);
+  int rc = hd_contract(s, op.A0, op.A1, v, (int)pl->c, nullptr, pl->hd.part, pl->hd.m, nullptr, stop, st);
   if (rc) return rc;
   const size_t lds = hd_rows_lds(s, true);
   static bool lds_set = false;
   if ((rc = hd_set_lds(reinterpret_cast<const void*>(k_hd_expand), &lds_set))) return rc;
   LO_PROF_BEGIN("k_hd_expand", st);
   hipLaunchKernelGGL(k_hd_expand, dim3((unsigned)((s.N + kHdRB - 1) / kHdRB), (unsigned)s.B), dim3(kThreads), lds, st,
-                     op.A0, op.A1, pl->hd_m, op.d, op.diag_mode, v, (int)s.N, s.p, s.q, s.PT, s.QT, (int)s.T, y, stop);
+                     op.A0, op.A1, pl->hd.m, op.d, op.diag_mode, v, (int)s.N, s.p, s.q, s.PT, s.QT, (int)s.T, y, stop);
   LO_PROF_END(st);
   LO_LAUNCH_CHECK();
   return LO_OK;

@@ -52,12 +52,14 @@ Split choose_split(int64_t B, int64_t N, int min_rows, int max_split = 256);
 
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
-// Bump allocator over the caller's workspace.
+// Bump allocator over the caller's workspace.  Over no workspace (base == nullptr) it MEASURES: take() returns nullptr and
+// only `off` advances, so the function that lays a workspace out is also the one that sizes it.
 struct Arena {
   char* base;
   size_t cap, off;
   bool ok;
   Arena(void* p, size_t bytes) : base((char*)p), cap(bytes), off(0), ok(true) {}
+  bool measuring() const { return !base; }
   template <typename T>
   T* take(size_t n) {
     off = align_up(off, 256);
@@ -68,6 +70,13 @@ struct Arena {
     return r;
   }
 };
+
+// floats per row of a rank-R factor (C, Q) as the skinny kernels read it: 4 * (R / 4 rounded up to a power of two)
+inline int padded_rank(int64_t R) {
+  int64_t rq = (R + 3) / 4, p = 1;
+  while (p < rq) p <<= 1;
+  return (int)(4 * p);
+}
 
 // ---------------------------------------------------------------------------------------------
 // device control block of one CG solve (lives in the workspace; host polls it)
@@ -142,45 +151,104 @@ int vec_dot_part(const float* a, const float* b, int64_t c, float* part, int64_t
 int vec_add_diag(const float* dd, int dd_mode, const float* v, float* y, int64_t c, int64_t B, int64_t N, Split sp,
                  const int* stop, hipStream_t st);
 
-// ---- operator matvec dispatch (lo_matvec.hip) ---------------------------------------------------
-struct MatvecPlan {
-  lo_op_desc op;
-  int64_t c;
-  Split sp;           // row split used by the skinny kernels / dot partials
-  int S_dot;          // number of partials per (b,col) the plan writes into dot_part
+// ---- operator matvec plan (lo_matvec.hip) ----------------------------------------------------
+// A kind is a state struct, a plan function and a run function.  The plan function validates the descriptor, takes the
+// kind's buffers from the arena in a fixed order and fills the state; on a measuring arena it makes the same takes and
+// launches nothing, which is how the workspace is sized (matvec_plan_bytes).
+struct MatvecPlan;
+// low-rank, dense, Kronecker, sum: planned and run in lo_matvec.hip
+struct LowrankPlan {
   const float* Apad;  // padded copy of C when R % 4 != 0 (else op.A0)
   int lda, R4;
   float* tpart;       // [B,S,R4,c]
   bool mv_resident;   // shape the one-pass resident matvec takes (lo_lowrank_mv.hip); else the two-pass kernels
-  float* kron_tmp;    // [B,N,c]
-  float* dense_part;  // split-K partials of the dense matvec (small batches) or nullptr
+};
+struct DensePlan {
+  float* part;  // split-K partials of the dense matvec (small batches) or nullptr
+};
+struct KronPlan {
+  float* tmp;  // [B,N,c], twice that on the matrix-core route of c > 1 columns
+};
+struct SumPlan {
+  float* ytmp;  // [B,N,c]: a term beyond the first is computed into it before it is added onto y (terms: MatvecPlan::sub)
+};
+
+// ---- SKI / Toeplitz (lo_ski.hip) ------------------------------------------------------------------------------------
+// LO_OP_SKI_DIAG, LO_OP_TOEPLITZ_DIAG (lo_ski.hip) and LO_OP_SKI_GRID_DIAG (lo_ski_grid.hip) share one state: the
+// interpolation matrices (with the grid shape of the grid kind), the grid-major copy of W_r, the grid-sized
+// intermediates u = W_r^T v and T u, and the split-k partials of the 1-D Toeplitz product (nullptr for the grid kind)
+struct CsrBufs {
+  int* ptr;  // [B, M+1] offsets of the grid points' entries
+  int* cur;  // [B, M+1] fill cursors of the build
+  int* tmp;  // [B, N*J] entry ids by grid point, unsorted
+  int* ids;  // [B, N*J] the same in ascending order within a grid point
+};
+struct SkiPlan {
+  lo_interp_desc w;
+  CsrBufs csr;
+  float *u, *t;  // [B, M, c]
+  float* tz_part;
+};
+int ski_plan(MatvecPlan* pl, Arena* ar, hipStream_t st);
+int ski_matvec_run(const MatvecPlan* pl, const float* v, float* y, const int* stop, hipStream_t st);
+// the interpolation kernels and the grid-major copy of W, shared with the grid kind (lo_ski_grid.hip)
+bool interp_shape_ok(int64_t B, int64_t N, int64_t J, int64_t M);
+int interp_gather(const int64_t* idx, const float* vals, int64_t B, int64_t N, int64_t J, int64_t M, const float* u,
+                  int64_t c, const float* dd, int dd_mode, const float* v, float* y, const int* stop, hipStream_t st);
+int interp_scatter(const int* ptr, const int* ids, const float* vals, int64_t B, int64_t N, int64_t J, int64_t M,
+                   const float* v, int64_t c, float* out, const int* stop, hipStream_t st);
+// the one layout of the grid-major copy; csr_bytes measures it, csr_build fills it (a measuring arena: takes only),
+// csr_view finds the buffers of a copy built earlier into `plan`
+void csr_layout(Arena& ar, int64_t B, int64_t N, int64_t J, int64_t M, CsrBufs* b);
+size_t csr_bytes(int64_t B, int64_t N, int64_t J, int64_t M);
+int csr_build(const int64_t* idx, int64_t B, int64_t N, int64_t J, int64_t M, Arena* ar, CsrBufs* b, hipStream_t st);
+CsrBufs csr_view(const void* plan, int64_t B, int64_t N, int64_t J, int64_t M);
+// the part of the plan the SKI kinds share: u, t and the copy of W_r (built here, or the caller's right_plan)
+int ski_interp_plan(MatvecPlan* pl, int64_t M, Arena* ar, hipStream_t st);
+
+// ---- SKI on a 2-D / 3-D grid (lo_ski_grid.hip): LO_OP_SKI_GRID_DIAG, on SkiPlan ---------------------------------------
+int ski_grid_plan(MatvecPlan* pl, Arena* ar, hipStream_t st);
+int ski_grid_matvec_run(const MatvecPlan* pl, const float* v, float* y, const int* stop, hipStream_t st);
+
+// ---- Hadamard product of two roots (lo_hadamard.hip) ---------------------------------------------------------------
+struct HadamardPlan {
+  float *part, *m;  // the contraction partials and the reduced M_t of every column (lo_hadamard.hip)
+};
+int hadamard_plan(MatvecPlan* pl, Arena* ar, hipStream_t st);
+int hadamard_matvec_run(const MatvecPlan* pl, const float* v, float* y, const int* stop, hipStream_t st);
+
+// ---- masked operator (lo_masked.hip) ---------------------------------------------------------------------------------
+struct MaskedPlan {      // (the base's plan is MatvecPlan::sub[0])
+  const int64_t* idx;    // [M]
+  int64_t N0;
+  int* inv;              // [N0], -1 where masked out
+  float *u, *w;          // [B, N0, c]: u = S^T v and the base's result (w == nullptr on the dense route)
+  bool dense;
+};
+int masked_plan(MatvecPlan* pl, Arena* ar, hipStream_t st);
+int masked_matvec_run(const MatvecPlan* pl, const float* v, float* y, const int* stop, hipStream_t st);
+
+// ---- the plan and its dispatch (lo_matvec.hip) -----------------------------------------------------------------------
+struct MatvecPlan {
+  lo_op_desc op;
+  int64_t c;
+  Split sp;    // row split used by the skinny kernels / dot partials
+  int S_dot;   // number of partials per (b,col) the plan writes into dot_part
   lo_matvec_cb cb;
   void* cb_user;
-  // LO_OP_SUM: one sub-plan per term (host heap, released by matvec_plan_free) and the buffer a term beyond the
-  // first is computed into before it is added onto y
+  // LO_OP_SUM: one sub-plan per term; LO_OP_MASKED: the base's plan.  Host heap, released by matvec_plan_free; a
+  // measuring pass keeps none.
   int nterms;
   MatvecPlan* sub;
-  float* ytmp;        // [B,N,c]
-  // LO_OP_SKI_DIAG / LO_OP_TOEPLITZ_DIAG (lo_ski.hip), LO_OP_SKI_GRID_DIAG (lo_ski_grid.hip; no tz_part, the grid shape
-  // rides in `ski`): the interpolation matrices, the grid-major copy of W_r built by
-  // matvec_plan_init, the grid-sized intermediates u = W_r^T v and T u, and the split-k partials of the Toeplitz product
-  lo_interp_desc ski;
-  int* csr_ptr;       // [B, M+1]
-  int* csr_ids;       // [B, N*J]
-  float* ski_u;       // [B, M, c]
-  float* ski_t;       // [B, M, c]
-  float* tz_part;
-  // LO_OP_HADAMARD_DIAG (lo_hadamard.hip): the contraction partials and the reduced M_t of every column
-  float* hd_part;
-  float* hd_m;
-  // LO_OP_MASKED (lo_masked.hip): the index list, its inverse map built by matvec_plan_init, the expanded vector
-  // u = S^T v and the base's result w (nullptr on the dense route); the base's plan is sub[0] (nterms == 1)
-  const int64_t* mask_idx;  // [M]
-  int64_t mask_N0;
-  int* mask_inv;            // [N0], -1 where masked out
-  float* mask_u;            // [B, N0, c]
-  float* mask_w;            // [B, N0, c]
-  bool mask_dense;
+  union {  // the state of op.kind
+    LowrankPlan lr;
+    DensePlan dense;
+    KronPlan kron;
+    SumPlan sum;
+    SkiPlan ski;
+    HadamardPlan hd;
+    MaskedPlan mask;
+  };
 };
 void matvec_plan_free(MatvecPlan* pl);
 // releases a plan's sub-plans on every exit path of the function that owns it
@@ -196,9 +264,15 @@ struct PlanGuard {
 int vec_axpy1(float* y, const float* a, size_t n, const int* stop, hipStream_t st);
 // clears `bytes` at p (16-byte aligned) with one kernel launch (control blocks / hand-off granules of a resident launch)
 int zero_span(void* p, size_t bytes, hipStream_t st);
-size_t matvec_plan_bytes(const lo_op_desc* op, int64_t c, Split sp);
+// Lays the plan of `op` out in the arena: validates, takes the buffers, stages what the kernels need (the padded copy
+// of C, the grid-major copy of W_r, the inverse map of a mask).  A failed call holds no sub-plans.  On a measuring
+// arena nothing is launched or kept and the return code only says whether the descriptor is valid: ar->off is the
+// size.  A caller that lays out more than the plan calls it in both modes, with a scratch plan when it measures.
 int matvec_plan_init(MatvecPlan* pl, const lo_op_desc* op, lo_matvec_cb cb, void* cb_user, int64_t c, Split sp,
                      Arena* ar, hipStream_t st);
+// what matvec_plan_init takes from an empty arena, plus kPlanTail
+constexpr size_t kPlanTail = 256;  // every size reported for a plan alone ends with it: never zero bytes to allocate
+size_t matvec_plan_bytes(const lo_op_desc* op, int64_t c, Split sp);
 // y = A v (+ optional dot partials sum_rows v o y, S_dot per (b,col))
 int matvec_run(const MatvecPlan* pl, const float* v, float* y, float* dot_part, const int* stop, hipStream_t st);
 // true if the plan can fuse the CG search-direction update into its first pass (low-rank operators)
@@ -206,36 +280,10 @@ bool matvec_can_fuse_pupdate(const MatvecPlan* pl);
 // p = z + beta p (first: p = z); y = A p; dot partials
 int matvec_run_pupdate(const MatvecPlan* pl, float* p, const float* z, const float* beta, int first, float* y,
                        float* dot_part, const int* stop, hipStream_t st);
-
-// ---- SKI / Toeplitz (lo_ski.hip) ------------------------------------------------------------------------------------
-size_t ski_plan_bytes(const lo_op_desc* op, int64_t c);
-int ski_plan_init(MatvecPlan* pl, const lo_op_desc* op, int64_t c, Arena* ar, hipStream_t st);
-int ski_matvec_run(const MatvecPlan* pl, const float* v, float* y, const int* stop, hipStream_t st);
-// the interpolation kernels and the grid-major copy of W, shared with the grid kind (lo_ski_grid.hip)
-bool interp_shape_ok(int64_t B, int64_t N, int64_t J, int64_t M);
-int interp_gather(const int64_t* idx, const float* vals, int64_t B, int64_t N, int64_t J, int64_t M, const float* u,
-                  int64_t c, const float* dd, int dd_mode, const float* v, float* y, const int* stop, hipStream_t st);
-int interp_scatter(const int* ptr, const int* ids, const float* vals, int64_t B, int64_t N, int64_t J, int64_t M,
-                   const float* v, int64_t c, float* out, const int* stop, hipStream_t st);
-size_t csr_bytes(int64_t B, int64_t N, int64_t J, int64_t M);
-int csr_build(const int64_t* idx, int64_t B, int64_t N, int64_t J, int64_t M, Arena* ar, int** ptr_out, int** ids_out,
-              hipStream_t st);
-void csr_view(const void* plan, int64_t B, int64_t N, int64_t J, int64_t M, int** ptr_out, int** ids_out);
-
-// ---- SKI on a 2-D / 3-D grid (lo_ski_grid.hip): LO_OP_SKI_GRID_DIAG, the plan fields of the SKI kind ----------------
-size_t ski_grid_plan_bytes(const lo_op_desc* op, int64_t c);
-int ski_grid_plan_init(MatvecPlan* pl, const lo_op_desc* op, int64_t c, Arena* ar, hipStream_t st);
-int ski_grid_matvec_run(const MatvecPlan* pl, const float* v, float* y, const int* stop, hipStream_t st);
-
-// ---- Hadamard product of two roots (lo_hadamard.hip) ---------------------------------------------------------------
-size_t hadamard_plan_bytes(const lo_op_desc* op, int64_t c);
-int hadamard_plan_init(MatvecPlan* pl, const lo_op_desc* op, int64_t c, Arena* ar);
-int hadamard_matvec_run(const MatvecPlan* pl, const float* v, float* y, const int* stop, hipStream_t st);
-
-// ---- masked operator (lo_masked.hip) ---------------------------------------------------------------------------------
-size_t masked_plan_bytes(const lo_op_desc* op, int64_t c);
-int masked_plan_init(MatvecPlan* pl, const lo_op_desc* op, int64_t c, Arena* ar, hipStream_t st);
-int masked_matvec_run(const MatvecPlan* pl, const float* v, float* y, const int* stop, hipStream_t st);
+// kinds a sum may hold and a mask may cover directly: the plain structured operators
+inline bool plain_term_kind(int kind) {
+  return kind == LO_OP_LOWRANK_DIAG || kind == LO_OP_DENSE_DIAG || kind == LO_OP_KRON_DIAG;
+}
 
 // dense / kron kernels
 int dense_matvec(const float* K, const float* d, int dd_mode, const float* v, float* y, float* dot_part, int64_t B,

@@ -857,7 +857,9 @@ size_t lo_lanczos_workspace_bytes(const lo_op_desc* op, int64_t P, int32_t max_i
   LzDev d;
   Split sp;
   lz_layout(op, P, max_iter, ar, &d, &sp);
-  return ar.off + matvec_plan_bytes(op, P, sp) + 1024;
+  MatvecPlan scratch;  // (measured by the call that lays it out in lo_lanczos_tridiag_f32)
+  matvec_plan_init(&scratch, op, nullptr, nullptr, P, sp, &ar, nullptr);
+  return ar.off + 1024;
 }
 
 int lo_root_from_lanczos_f32(const float* q, const float* evecs, const float* evals, int64_t PB, int64_t N, int32_t k,

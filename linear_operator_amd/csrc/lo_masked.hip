@@ -199,8 +199,7 @@ __global__ __launch_bounds__(kThreads) void k_masked_dense_mv(
 }
 
 static bool mask_base_ok(const lo_op_desc* base) {
-  return base->kind == LO_OP_LOWRANK_DIAG || base->kind == LO_OP_DENSE_DIAG || base->kind == LO_OP_KRON_DIAG ||
-         base->kind == LO_OP_SUM;
+  return plain_term_kind(base->kind) || base->kind == LO_OP_SUM;
 }
 
 // the dense route: a dense base at the column counts the vector-ALU k_dense_mv takes (the matrix-core engine of wider
@@ -220,40 +219,33 @@ static int mask_check(const lo_op_desc* op) {
 
 static Split mask_base_split(const lo_op_desc* base) { return choose_split(base->B, base->N, 256); }
 
-size_t masked_plan_bytes(const lo_op_desc* op, int64_t c) {
-  if (mask_check(op)) return 0;
-  const lo_op_desc* base = op->mask->base;
-  Arena ar(nullptr, 0);
-  ar.take<int>((size_t)base->N);
-  ar.take<float>((size_t)base->B * base->N * c);
-  if (!mask_dense_route(base, c)) ar.take<float>((size_t)base->B * base->N * c);
-  return align_up(ar.off, 256) + matvec_plan_bytes(base, c, mask_base_split(base));
-}
-
-int masked_plan_init(MatvecPlan* pl, const lo_op_desc* op, int64_t c, Arena* ar, hipStream_t st) {
-  int rc = mask_check(op);
+int masked_plan(MatvecPlan* pl, Arena* ar, hipStream_t st) {
+  const lo_op_desc& op = pl->op;
+  int rc = mask_check(&op);
   if (rc) return rc;
-  const lo_mask_desc* m = op->mask;
+  const lo_mask_desc* m = op.mask;
   const lo_op_desc* base = m->base;
-  pl->mask_idx = m->idx;
-  pl->mask_N0 = base->N;
-  pl->mask_dense = mask_dense_route(base, c);
-  pl->mask_inv = ar->take<int>((size_t)base->N);
-  pl->mask_u = ar->take<float>((size_t)base->B * base->N * c);
-  pl->mask_w = pl->mask_dense ? nullptr : ar->take<float>((size_t)base->B * base->N * c);
-  pl->nterms = 1;
-  pl->sub = new MatvecPlan[1];
-  pl->sub[0].sub = nullptr;
-  pl->sub[0].nterms = 0;
-  rc = matvec_plan_init(&pl->sub[0], base, nullptr, nullptr, c, mask_base_split(base), ar, st);
-  if (!rc && !ar->ok) rc = LO_ERR_WORKSPACE;
-  if (rc) {
-    matvec_plan_free(pl);
-    return rc;
+  MaskedPlan& k = pl->mask;
+  k.idx = m->idx;
+  k.N0 = base->N;
+  k.dense = mask_dense_route(base, pl->c);
+  k.inv = ar->take<int>((size_t)base->N);
+  k.u = ar->take<float>((size_t)base->B * base->N * pl->c);
+  k.w = k.dense ? nullptr : ar->take<float>((size_t)base->B * base->N * pl->c);
+  MatvecPlan scratch;  // (a measuring pass keeps no sub-plan)
+  MatvecPlan* sub = &scratch;
+  if (!ar->measuring()) {
+    sub = pl->sub = new MatvecPlan[1]();
+    pl->nterms = 1;
   }
-  pl->sub[0].mv_resident = false;  // streaming kernels only inside the mask (the one-pass low-rank product is a resident launch)
+  rc = matvec_plan_init(sub, base, nullptr, nullptr, pl->c, mask_base_split(base), ar, st);
+  if (rc || ar->measuring()) return rc;
+  if (!ar->ok) return LO_ERR_WORKSPACE;
+  // streaming kernels only for a low-rank base (its one-pass product is a resident launch); the terms of a sum base keep
+  // their own choice
+  if (base->kind == LO_OP_LOWRANK_DIAG) sub->lr.mv_resident = false;
   hipLaunchKernelGGL(k_mask_inv, dim3((unsigned)((base->N + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, m->idx,
-                     (int)m->M, pl->mask_inv, (int)base->N);
+                     (int)m->M, k.inv, (int)base->N);
   LO_LAUNCH_CHECK();
   return LO_OK;
 }
@@ -261,22 +253,23 @@ int masked_plan_init(MatvecPlan* pl, const lo_op_desc* op, int64_t c, Arena* ar,
 int masked_matvec_run(const MatvecPlan* pl, const float* v, float* y, const int* stop, hipStream_t st) {
   const lo_op_desc& op = pl->op;
   const lo_op_desc& base = pl->sub[0].op;
-  const int M = (int)op.N, N0 = (int)pl->mask_N0, c = (int)pl->c;
+  const MaskedPlan& k = pl->mask;
+  const int M = (int)op.N, N0 = (int)k.N0, c = (int)pl->c;
   const dim3 block(kThreads);
   const size_t per = (size_t)4 * kThreads;
   LO_PROF_BEGIN("mask_expand", st);
   hipLaunchKernelGGL(k_mask_expand, dim3((unsigned)(((size_t)N0 * c + per - 1) / per), (unsigned)op.B), block, 0, st,
-                     pl->mask_inv, v, pl->mask_u, M, N0, c, stop);
+                     k.inv, v, k.u, M, N0, c, stop);
   LO_PROF_END(st);
   LO_LAUNCH_CHECK();
-  if (pl->mask_dense) {
+  if (k.dense) {
     const int rows_per_wg = dense_rows_per_wg(op.B, M);
     const dim3 grid((unsigned)((M + rows_per_wg - 1) / rows_per_wg), (unsigned)op.B);
     for (int c0 = 0; c0 < c; c0 += 4) {
       const int cn = std::min(4, c - c0);
 #define LO_MDM(CT)                                                                                                  \
-  hipLaunchKernelGGL((k_masked_dense_mv<CT>), grid, block, 0, st, base.A0, pl->mask_idx, base.d, base.diag_mode, op.d, \
-                     op.diag_mode, pl->mask_u + c0, v + c0, c, cn, y + c0, M, N0, rows_per_wg, stop)
+  hipLaunchKernelGGL((k_masked_dense_mv<CT>), grid, block, 0, st, base.A0, k.idx, base.d, base.diag_mode, op.d, \
+                     op.diag_mode, k.u + c0, v + c0, c, cn, y + c0, M, N0, rows_per_wg, stop)
       LO_PROF_BEGIN("masked_dense_mv", st);
       if (cn == 1) LO_MDM(1);
       else if (cn == 2) LO_MDM(2);
@@ -287,11 +280,11 @@ int masked_matvec_run(const MatvecPlan* pl, const float* v, float* y, const int*
     }
     return LO_OK;
   }
-  const int rc = matvec_run(&pl->sub[0], pl->mask_u, pl->mask_w, nullptr, stop, st);
+  const int rc = matvec_run(&pl->sub[0], k.u, k.w, nullptr, stop, st);
   if (rc) return rc;
   LO_PROF_BEGIN("mask_gather", st);
   hipLaunchKernelGGL(k_mask_gather, dim3((unsigned)(((size_t)M * c + per - 1) / per), (unsigned)op.B), block, 0, st,
-                     pl->mask_idx, pl->mask_w, op.d, op.diag_mode, v, y, M, N0, c, stop);
+                     k.idx, k.w, op.d, op.diag_mode, v, y, M, N0, c, stop);
   LO_PROF_END(st);
   LO_LAUNCH_CHECK();
   return LO_OK;

@@ -280,12 +280,6 @@ __global__ __launch_bounds__(kThreads) void k_mr_final(MrDev d, int rows_per) {
     }
 }
 
-static int mr_padded_rank_k(int k) {
-  int rq = (k + 3) / 4, p = 1;
-  while (p < rq) p <<= 1;
-  return 4 * p;
-}
-
 struct MrHost {
   Split sp;
   int preR4;
@@ -295,11 +289,11 @@ struct MrHost {
 
 static size_t mr_layout(const lo_op_desc* op, const lo_precond_desc* pre, bool pre_cb, const lo_minres_params* prm,
                         void* ws, size_t ws_bytes, MrDev* dout, MatvecPlan* pl, lo_matvec_cb cb, void* cb_user,
-                        MrHost* h, hipStream_t st, int* rc_out, bool init) {
+                        MrHost* h, hipStream_t st, int* rc_out) {
   const int64_t B = op->B, N = op->N, c = prm->c;
   const int Q = prm->n_shifts;
   Split sp = choose_split(B, N, 256);
-  Arena ar(ws, ws_bytes);
+  Arena ar(ws, ws_bytes);  // (ws == nullptr: the sizing pass -- the same takes, nothing staged)
   const size_t nv = (size_t)B * N * c, ns = (size_t)B * c;
   const bool precond = pre != nullptr || pre_cb;
   MrDev d;
@@ -333,12 +327,12 @@ static size_t mr_layout(const lo_op_desc* op, const lo_precond_desc* pre, bool p
     h->upart = nullptr;
   }
   if (pre) {
-    const int R4 = mr_padded_rank_k(pre->k);
+    const int R4 = padded_rank(pre->k);
     float* up = ar.take<float>((size_t)B * sp.S * R4 * c);
     const float* qp = pre->Q;
     if (pre->ldq != R4) {
       float* pad = ar.take<float>((size_t)B * N * R4);
-      if (init && ar.ok && ws) {
+      if (!ar.measuring() && ar.ok) {
         if (pre->ldq != pre->k) { if (rc_out) *rc_out = LO_ERR_BADARG; }
         else {
           int rc = pad_rows(pre->Q, pre->k, pad, R4, B * N, st);
@@ -349,14 +343,11 @@ static size_t mr_layout(const lo_op_desc* op, const lo_precond_desc* pre, bool p
     }
     if (h) { h->preR4 = R4; h->Qp = qp; h->upart = up; }
   }
-  if (init) {
-    int rc = matvec_plan_init(pl, op, cb, cb_user, c, sp, &ar, st);
-    if (rc && rc_out && *rc_out == LO_OK) *rc_out = rc;
-  } else {
-    ar.off += matvec_plan_bytes(op, c, sp);
-  }
+  MatvecPlan scratch;  // (the sizing pass keeps no plan)
+  const int rc = matvec_plan_init(pl ? pl : &scratch, op, cb, cb_user, c, sp, &ar, st);
+  if (rc && rc_out && *rc_out == LO_OK) *rc_out = rc;
   if (dout) *dout = d;
-  if (init && !ar.ok && rc_out && *rc_out == LO_OK) *rc_out = LO_ERR_WORKSPACE;
+  if (!ar.ok && rc_out && *rc_out == LO_OK) *rc_out = LO_ERR_WORKSPACE;
   return ar.off + 1024;
 }
 
@@ -374,7 +365,7 @@ size_t lo_minres_workspace_bytes(const lo_op_desc* op, const lo_precond_desc* pr
     dummy.k = 4; dummy.ldq = 4; dummy.constant_diag = 0; dummy.reserved = 0; dummy.Q = nullptr; dummy.dinv = nullptr;
     p = &dummy;
   }
-  return mr_layout(op, p, true, prm, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false);
+  return mr_layout(op, p, true, prm, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
 }
 
 int lo_minres_f32(const lo_op_desc* op, lo_matvec_cb matvec, void* matvec_user, const lo_precond_desc* pre,
@@ -392,7 +383,7 @@ int lo_minres_f32(const lo_op_desc* op, lo_matvec_cb matvec, void* matvec_user, 
   PlanGuard pl_guard(&pl);
   MrHost h;
   int rc = LO_OK;
-  mr_layout(op, pre, precond_cb != nullptr, prm, ws, ws_bytes, &d, &pl, matvec, matvec_user, &h, st, &rc, true);
+  mr_layout(op, pre, precond_cb != nullptr, prm, ws, ws_bytes, &d, &pl, matvec, matvec_user, &h, st, &rc);
   if (rc) return rc;
   const Split sp = h.sp;
   const bool precond = pre != nullptr || precond_cb != nullptr;

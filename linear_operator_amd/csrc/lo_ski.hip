@@ -155,46 +155,44 @@ __global__ __launch_bounds__(kThreads) void k_csr_sort(const int* __restrict__ p
   }
 }
 
-size_t csr_bytes(int64_t B, int64_t N, int64_t J, int64_t M) {
-  Arena ar(nullptr, 0);
-  ar.take<int>((size_t)B * (M + 1));
-  ar.take<int>((size_t)B * (M + 1));
-  ar.take<int>((size_t)B * N * J);
-  ar.take<int>((size_t)B * N * J);
-  return ar.off + 256;
+void csr_layout(Arena& ar, int64_t B, int64_t N, int64_t J, int64_t M, CsrBufs* b) {
+  b->ptr = ar.take<int>((size_t)B * (M + 1));
+  b->cur = ar.take<int>((size_t)B * (M + 1));
+  b->tmp = ar.take<int>((size_t)B * N * J);
+  b->ids = ar.take<int>((size_t)B * N * J);
 }
 
-int csr_build(const int64_t* idx, int64_t B, int64_t N, int64_t J, int64_t M, Arena* ar, int** ptr_out, int** ids_out,
-              hipStream_t st) {
+size_t csr_bytes(int64_t B, int64_t N, int64_t J, int64_t M) {
+  Arena ar(nullptr, 0);
+  CsrBufs b;
+  csr_layout(ar, B, N, J, M, &b);
+  return ar.off + kPlanTail;
+}
+
+int csr_build(const int64_t* idx, int64_t B, int64_t N, int64_t J, int64_t M, Arena* ar, CsrBufs* b, hipStream_t st) {
   if (!interp_shape_ok(B, N, J, M)) return LO_ERR_BADARG;
-  const int NJ = (int)(N * J);
-  int* ptr = ar->take<int>((size_t)B * (M + 1));
-  int* cur = ar->take<int>((size_t)B * (M + 1));
-  int* tmp = ar->take<int>((size_t)B * NJ);
-  int* ids = ar->take<int>((size_t)B * NJ);
+  csr_layout(*ar, B, N, J, M, b);
+  if (ar->measuring()) return LO_OK;
   if (!ar->ok) return LO_ERR_WORKSPACE;
-  LO_HIP_CHECK(hipMemsetAsync(ptr, 0, sizeof(int) * (size_t)B * (M + 1), st));
+  const int NJ = (int)(N * J);
+  LO_HIP_CHECK(hipMemsetAsync(b->ptr, 0, sizeof(int) * (size_t)B * (M + 1), st));
   const size_t total = (size_t)B * NJ;
   LO_PROF_BEGIN("ski_csr_build", st);
-  hipLaunchKernelGGL(k_csr_count, dim3(grid_for(total)), dim3(kThreads), 0, st, idx, B, NJ, M, ptr);
-  hipLaunchKernelGGL(k_csr_scan, dim3((unsigned)B), dim3(kThreads), 0, st, ptr, cur, M);
-  hipLaunchKernelGGL(k_csr_fill, dim3(grid_for(total)), dim3(kThreads), 0, st, idx, B, NJ, M, cur, tmp);
+  hipLaunchKernelGGL(k_csr_count, dim3(grid_for(total)), dim3(kThreads), 0, st, idx, B, NJ, M, b->ptr);
+  hipLaunchKernelGGL(k_csr_scan, dim3((unsigned)B), dim3(kThreads), 0, st, b->ptr, b->cur, M);
+  hipLaunchKernelGGL(k_csr_fill, dim3(grid_for(total)), dim3(kThreads), 0, st, idx, B, NJ, M, b->cur, b->tmp);
   const unsigned sgrid = (unsigned)std::max<size_t>(1, std::min<size_t>(((size_t)B * M + 3) / 4, 32768));
-  hipLaunchKernelGGL(k_csr_sort, dim3(sgrid), dim3(kThreads), 0, st, ptr, B, NJ, M, tmp, ids);
+  hipLaunchKernelGGL(k_csr_sort, dim3(sgrid), dim3(kThreads), 0, st, b->ptr, B, NJ, M, b->tmp, b->ids);
   LO_PROF_END(st);
   LO_LAUNCH_CHECK();
-  *ptr_out = ptr;
-  *ids_out = ids;
   return LO_OK;
 }
 
-// (ptr, ids) of a grid-major copy built by csr_build into `plan` (the layout of csr_bytes)
-void csr_view(const void* plan, int64_t B, int64_t N, int64_t J, int64_t M, int** ptr_out, int** ids_out) {
-  Arena ar(const_cast<void*>(plan), csr_bytes(B, N, J, M));
-  *ptr_out = ar.take<int>((size_t)B * (M + 1));
-  ar.take<int>((size_t)B * (M + 1));
-  ar.take<int>((size_t)B * N * J);
-  *ids_out = ar.take<int>((size_t)B * N * J);
+CsrBufs csr_view(const void* plan, int64_t B, int64_t N, int64_t J, int64_t M) {
+  Arena ar(const_cast<void*>(plan), SIZE_MAX);
+  CsrBufs b;
+  csr_layout(ar, B, N, J, M, &b);
+  return b;
 }
 
 // ---- interpolation, scatter side: out[b, m, col] = sum over the entries (n, j) at grid point m of vals * v[n, col] --
@@ -464,51 +462,48 @@ __global__ __launch_bounds__(kThreads) void k_interp_vgrad(const int64_t* __rest
 }
 
 // ---- pieces of the matvec plan (lo_matvec.hip) --------------------------------------------------------------------------
-size_t ski_plan_bytes(const lo_op_desc* op, int64_t c) {
-  const int64_t M = op->R;
-  size_t total = toeplitz_part_bytes(op->B, M, c);
-  if (op->kind == LO_OP_SKI_DIAG) {
-    if (!op->interp || !op->interp->right_plan) total += csr_bytes(op->B, op->N, op->n2, M);
-    total += 2 * (align_up((size_t)op->B * M * c * sizeof(float), 256) + 256);
+int ski_interp_plan(MatvecPlan* pl, int64_t M, Arena* ar, hipStream_t st) {
+  const lo_op_desc& op = pl->op;
+  SkiPlan& k = pl->ski;
+  k.w = *op.interp;
+  k.u = ar->take<float>((size_t)op.B * M * pl->c);
+  k.t = ar->take<float>((size_t)op.B * M * pl->c);
+  if (!ar->ok) return LO_ERR_WORKSPACE;
+  if (k.w.right_plan) {  // the caller keeps the grid-major copy of W_r across calls (lo_interp_plan_build)
+    k.csr = csr_view(k.w.right_plan, op.B, op.N, op.n2, M);
+    return LO_OK;
   }
-  return total;
+  return csr_build(k.w.right_idx, op.B, op.N, op.n2, M, ar, &k.csr, st);
 }
 
-int ski_plan_init(MatvecPlan* pl, const lo_op_desc* op, int64_t c, Arena* ar, hipStream_t st) {
-  const int64_t M = op->R;
-  if (!op->A0 || M < 1) return LO_ERR_BADARG;
+int ski_plan(MatvecPlan* pl, Arena* ar, hipStream_t st) {
+  const lo_op_desc& op = pl->op;
+  const int64_t M = op.R;
+  if (!op.A0 || M < 1) return LO_ERR_BADARG;
   if (M > LO_TOEPLITZ_MAX_M) return LO_ERR_UNSUPPORTED;
-  if (op->kind == LO_OP_TOEPLITZ_DIAG) {
-    if (M != op->N) return LO_ERR_BADARG;
+  if (op.kind == LO_OP_TOEPLITZ_DIAG) {
+    if (M != op.N) return LO_ERR_BADARG;
   } else {
-    const lo_interp_desc* w = op->interp;
+    const lo_interp_desc* w = op.interp;
     if (!w || !w->left_idx || !w->left_vals || !w->right_idx || !w->right_vals) return LO_ERR_BADARG;
-    if (!interp_shape_ok(op->B, op->N, op->n2, M)) return LO_ERR_BADARG;
-    pl->ski = *w;
-    pl->ski_u = ar->take<float>((size_t)op->B * M * c);
-    pl->ski_t = ar->take<float>((size_t)op->B * M * c);
-    if (!ar->ok) return LO_ERR_WORKSPACE;
-    if (w->right_plan) {  // the caller keeps the grid-major copy of W_r across calls (lo_interp_plan_build)
-      csr_view(w->right_plan, op->B, op->N, op->n2, M, &pl->csr_ptr, &pl->csr_ids);
-    } else {
-      const int rc = csr_build(w->right_idx, op->B, op->N, op->n2, M, ar, &pl->csr_ptr, &pl->csr_ids, st);
-      if (rc) return rc;
-    }
+    if (!interp_shape_ok(op.B, op.N, op.n2, M)) return LO_ERR_BADARG;
+    const int rc = ski_interp_plan(pl, M, ar, st);
+    if (rc) return rc;
   }
-  pl->tz_part = ar->take<float>((size_t)tz_split(op->B, M).KS * op->B * M * c);
-  return ar->ok ? LO_OK : LO_ERR_WORKSPACE;
+  pl->ski.tz_part = ar->take<float>((size_t)tz_split(op.B, M).KS * op.B * M * pl->c);
+  return LO_OK;
 }
 
 int ski_matvec_run(const MatvecPlan* pl, const float* v, float* y, const int* stop, hipStream_t st) {
   const lo_op_desc& op = pl->op;
+  const SkiPlan& k = pl->ski;
   const int64_t M = op.R;
   if (op.kind == LO_OP_TOEPLITZ_DIAG)
-    return toeplitz_mv(op.A0, op.B, M, v, pl->c, op.d, op.diag_mode, v, y, pl->tz_part, stop, st);
-  int rc = interp_scatter(pl->csr_ptr, pl->csr_ids, pl->ski.right_vals, op.B, op.N, op.n2, M, v, pl->c, pl->ski_u, stop,
-                          st);
-  if (!rc) rc = toeplitz_mv(op.A0, op.B, M, pl->ski_u, pl->c, nullptr, LO_DIAG_NONE, nullptr, pl->ski_t, pl->tz_part, stop, st);
-  if (!rc) rc = interp_gather(pl->ski.left_idx, pl->ski.left_vals, op.B, op.N, op.n2, M, pl->ski_t, pl->c, op.d,
-                              op.diag_mode, v, y, stop, st);
+    return toeplitz_mv(op.A0, op.B, M, v, pl->c, op.d, op.diag_mode, v, y, k.tz_part, stop, st);
+  int rc = interp_scatter(k.csr.ptr, k.csr.ids, k.w.right_vals, op.B, op.N, op.n2, M, v, pl->c, k.u, stop, st);
+  if (!rc) rc = toeplitz_mv(op.A0, op.B, M, k.u, pl->c, nullptr, LO_DIAG_NONE, nullptr, k.t, k.tz_part, stop, st);
+  if (!rc) rc = interp_gather(k.w.left_idx, k.w.left_vals, op.B, op.N, op.n2, M, k.t, pl->c, op.d, op.diag_mode, v, y,
+                              stop, st);
   return rc;
 }
 
@@ -535,10 +530,10 @@ int lo_interp_t_f32(const int64_t* idx, const float* vals, int64_t B, int64_t N,
   if (!interp_shape_ok(B, N, J, M)) return LO_ERR_BADARG;
   hipStream_t st = (hipStream_t)stream;
   Arena ar(ws, ws_bytes);
-  int *ptr = nullptr, *ids = nullptr;
-  const int rc = csr_build(idx, B, N, J, M, &ar, &ptr, &ids, st);
+  CsrBufs b;
+  const int rc = csr_build(idx, B, N, J, M, &ar, &b, st);
   if (rc) return rc;
-  return interp_scatter(ptr, ids, vals, B, N, J, M, v, c, out, nullptr, st);
+  return interp_scatter(b.ptr, b.ids, vals, B, N, J, M, v, c, out, nullptr, st);
 }
 
 size_t lo_interp_plan_bytes(int64_t B, int64_t N, int64_t J, int64_t M) {
@@ -551,16 +546,15 @@ int lo_interp_plan_build(const int64_t* idx, int64_t B, int64_t N, int64_t J, in
   if (!idx || !plan || !interp_shape_ok(B, N, J, M)) return LO_ERR_BADARG;
   if (plan_bytes < csr_bytes(B, N, J, M)) return LO_ERR_WORKSPACE;
   Arena ar(plan, plan_bytes);
-  int *ptr = nullptr, *ids = nullptr;
-  return csr_build(idx, B, N, J, M, &ar, &ptr, &ids, (hipStream_t)stream);
+  CsrBufs b;
+  return csr_build(idx, B, N, J, M, &ar, &b, (hipStream_t)stream);
 }
 
 int lo_interp_t_planned_f32(const void* plan, const float* vals, int64_t B, int64_t N, int64_t J, int64_t M,
                             const float* v, int64_t c, float* out, void* stream) {
   if (!plan || !vals || !v || !out || !interp_shape_ok(B, N, J, M)) return LO_ERR_BADARG;
-  int *ptr = nullptr, *ids = nullptr;
-  csr_view(plan, B, N, J, M, &ptr, &ids);
-  return interp_scatter(ptr, ids, vals, B, N, J, M, v, c, out, nullptr, (hipStream_t)stream);
+  const CsrBufs b = csr_view(plan, B, N, J, M);
+  return interp_scatter(b.ptr, b.ids, vals, B, N, J, M, v, c, out, nullptr, (hipStream_t)stream);
 }
 
 size_t lo_toeplitz_workspace_bytes(int64_t B, int64_t M, int64_t c) {

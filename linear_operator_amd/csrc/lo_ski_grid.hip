@@ -229,44 +229,27 @@ int toeplitz_kron_passes(const float* t, const int64_t* m, int ndim, int64_t B, 
   return LO_OK;
 }
 
-// ---- pieces of the matvec plan (lo_matvec.hip): the plan of lo_ski.hip with the Toeplitz product replaced ------------
-size_t ski_grid_plan_bytes(const lo_op_desc* op, int64_t c) {
-  const int64_t M = op->R;
-  size_t total = 2 * (align_up((size_t)op->B * M * c * sizeof(float), 256) + 256);
-  if (!op->interp || !op->interp->right_plan) total += csr_bytes(op->B, op->N, op->n2, M);
-  return total;
-}
-
-int ski_grid_plan_init(MatvecPlan* pl, const lo_op_desc* op, int64_t c, Arena* ar, hipStream_t st) {
-  const lo_interp_desc* w = op->interp;
-  if (!op->A0 || !w || !w->left_idx || !w->left_vals || !w->right_idx || !w->right_vals) return LO_ERR_BADARG;
+// ---- the kind's plan and run functions (lo_matvec.hip): those of lo_ski.hip with the Toeplitz product replaced ------
+int ski_grid_plan(MatvecPlan* pl, Arena* ar, hipStream_t st) {
+  const lo_op_desc& op = pl->op;
+  const lo_interp_desc* w = op.interp;
+  if (!op.A0 || !w || !w->left_idx || !w->left_vals || !w->right_idx || !w->right_vals) return LO_ERR_BADARG;
   int64_t M = 0;
   if (!grid_shape_ok(w->grid_m, w->grid_ndim, &M)) return LO_ERR_UNSUPPORTED;
-  if (M != op->R) return LO_ERR_BADARG;
-  if (!interp_shape_ok(op->B, op->N, op->n2, M) || c > INT_MAX / 64) return LO_ERR_BADARG;
-  pl->ski = *w;
-  pl->ski_u = ar->take<float>((size_t)op->B * M * c);
-  pl->ski_t = ar->take<float>((size_t)op->B * M * c);
-  if (!ar->ok) return LO_ERR_WORKSPACE;
-  if (w->right_plan) {
-    csr_view(w->right_plan, op->B, op->N, op->n2, M, &pl->csr_ptr, &pl->csr_ids);
-  } else {
-    const int rc = csr_build(w->right_idx, op->B, op->N, op->n2, M, ar, &pl->csr_ptr, &pl->csr_ids, st);
-    if (rc) return rc;
-  }
-  return ar->ok ? LO_OK : LO_ERR_WORKSPACE;
+  if (M != op.R) return LO_ERR_BADARG;
+  if (!interp_shape_ok(op.B, op.N, op.n2, M) || pl->c > INT_MAX / 64) return LO_ERR_BADARG;
+  return ski_interp_plan(pl, M, ar, st);
 }
 
 int ski_grid_matvec_run(const MatvecPlan* pl, const float* v, float* y, const int* stop, hipStream_t st) {
   const lo_op_desc& op = pl->op;
+  const SkiPlan& k = pl->ski;
   const int64_t M = op.R;
-  int rc = interp_scatter(pl->csr_ptr, pl->csr_ids, pl->ski.right_vals, op.B, op.N, op.n2, M, v, pl->c, pl->ski_u, stop,
-                          st);
-  float* g = nullptr;  // the passes write ski_t, ski_u, ski_t: the result is in ski_u (D = 2) or ski_t (D = 3)
-  if (!rc) rc = toeplitz_kron_passes(op.A0, pl->ski.grid_m, pl->ski.grid_ndim, op.B, pl->c, pl->ski_u, pl->ski_u,
-                                     pl->ski_t, &g, stop, st);
-  if (!rc) rc = interp_gather(pl->ski.left_idx, pl->ski.left_vals, op.B, op.N, op.n2, M, g, pl->c, op.d, op.diag_mode, v,
-                              y, stop, st);
+  int rc = interp_scatter(k.csr.ptr, k.csr.ids, k.w.right_vals, op.B, op.N, op.n2, M, v, pl->c, k.u, stop, st);
+  float* g = nullptr;  // the passes write t, u, t: the result is in u (D = 2) or t (D = 3)
+  if (!rc) rc = toeplitz_kron_passes(op.A0, k.w.grid_m, k.w.grid_ndim, op.B, pl->c, k.u, k.u, k.t, &g, stop, st);
+  if (!rc) rc = interp_gather(k.w.left_idx, k.w.left_vals, op.B, op.N, op.n2, M, g, pl->c, op.d, op.diag_mode, v, y,
+                              stop, st);
   return rc;
 }
 

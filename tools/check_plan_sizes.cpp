@@ -1,0 +1,142 @@
+// check_plan_sizes.cpp -- host-only walk of the matvec plan layer's sizing paths for a sanitizer build.
+//
+// The descriptor table of tests/matvec_plan_cases.py (every kind, one and three columns) and one refused descriptor per
+// kind go through lo_matvec_workspace_bytes, lo_cg_workspace_bytes, lo_minres_workspace_bytes and
+// lo_lanczos_workspace_bytes.  The sizing passes run the plan functions on a measuring arena: they must read no device
+// pointer (the ones here are dummy addresses), keep no sub-plan (a leak report) and touch nothing out of bounds.  No GPU.
+//
+//   cd linear_operator_amd/csrc && mkdir -p build_asan
+//   for f in *.hip; do hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -fPIC -Xarch_host -fsanitize=address,undefined \
+//       -c $f -o build_asan/${f%.hip}.o; done
+//   hipcc --offload-arch=gfx950 -fsanitize=address,undefined ../../tools/check_plan_sizes.cpp build_asan/*.o \
+//       -o build_asan/check_plan_sizes && build_asan/check_plan_sizes
+#include <cstdio>
+#include <cstring>
+#include <vector>
+
+#include "../include/lo_amd.h"
+
+static const float* F(uintptr_t a) { return reinterpret_cast<const float*>(a); }
+static const int64_t* I(uintptr_t a) { return reinterpret_cast<const int64_t*>(a); }
+
+static lo_op_desc desc(int kind, int64_t B, int64_t N, int64_t R, int64_t n2, bool a1, int diag_mode) {
+  lo_op_desc d;
+  memset(&d, 0, sizeof(d));
+  d.kind = kind; d.diag_mode = diag_mode; d.B = B; d.N = N; d.R = R; d.n2 = n2;
+  d.A0 = F(0x10000);
+  d.A1 = a1 ? F(0x20000) : nullptr;
+  d.d = diag_mode != LO_DIAG_NONE ? F(0x30000) : nullptr;
+  return d;
+}
+
+struct Entry {
+  const char* name;
+  lo_op_desc op;
+  bool valid;
+};
+
+static int walk(const std::vector<Entry>& table) {
+  int bad = 0;
+  for (const Entry& e : table) {
+    for (int64_t c : {1, 3}) {
+      lo_cg_params cg;
+      memset(&cg, 0, sizeof(cg));
+      cg.c = c; cg.max_iter = 5; cg.max_tridiag_iter = 20; cg.tolerance = 1e-4f; cg.eps = 1e-10f;
+      lo_minres_params mr;
+      memset(&mr, 0, sizeof(mr));
+      mr.c = c; mr.n_shifts = 2; mr.max_iter = 3;
+      const size_t mv = lo_matvec_workspace_bytes(&e.op, c);
+      const size_t a = lo_cg_workspace_bytes(&e.op, nullptr, &cg);
+      const size_t b = lo_minres_workspace_bytes(&e.op, nullptr, &mr);
+      const size_t l = lo_lanczos_workspace_bytes(&e.op, c, 4);
+      printf("%-22s c=%lld matvec %zu cg %zu minres %zu lanczos %zu\n", e.name, (long long)c, mv, a, b, l);
+      if (!e.valid && mv > 256) {
+        printf("  a refused descriptor took buffers\n");
+        ++bad;
+      }
+      if (mv < 256 || a < mv || b < mv || l < mv) {
+        printf("  a size does not cover the plan\n");
+        ++bad;
+      }
+    }
+  }
+  return bad;
+}
+
+int main() {
+  std::vector<Entry> t;
+  t.push_back({"lowrank_r5", desc(LO_OP_LOWRANK_DIAG, 2, 300, 5, 0, false, LO_DIAG_FULL), true});
+  t.push_back({"lowrank_r8", desc(LO_OP_LOWRANK_DIAG, 2, 300, 8, 0, false, LO_DIAG_CONST), true});
+  t.push_back({"dense_splitk", desc(LO_OP_DENSE_DIAG, 1, 1024, 0, 0, false, LO_DIAG_FULL), true});
+  t.push_back({"dense_plain", desc(LO_OP_DENSE_DIAG, 2, 100, 0, 0, false, LO_DIAG_FULL), true});
+  t.push_back({"kron_3x5", desc(LO_OP_KRON_DIAG, 2, 15, 3, 5, true, LO_DIAG_FULL), true});
+  t.push_back({"kron_128", desc(LO_OP_KRON_DIAG, 1, 16384, 128, 128, true, LO_DIAG_FULL), true});
+  t.push_back({"toeplitz_33", desc(LO_OP_TOEPLITZ_DIAG, 2, 33, 33, 0, false, LO_DIAG_FULL), true});
+
+  lo_interp_desc w, wp, g2, g3;
+  memset(&w, 0, sizeof(w));
+  w.left_idx = w.right_idx = I(0x40000);
+  w.left_vals = w.right_vals = F(0x50000);
+  wp = g2 = g3 = w;
+  wp.right_plan = F(0x60000);
+  g2.grid_ndim = 2; g2.grid_m[0] = 5; g2.grid_m[1] = 7;
+  g3.grid_ndim = 3; g3.grid_m[0] = 3; g3.grid_m[1] = 4; g3.grid_m[2] = 5;
+  lo_op_desc ski = desc(LO_OP_SKI_DIAG, 2, 50, 20, 4, false, LO_DIAG_FULL), ski_p = ski;
+  ski.interp = &w;
+  ski_p.interp = &wp;
+  lo_op_desc grid2 = desc(LO_OP_SKI_GRID_DIAG, 2, 50, 35, 4, false, LO_DIAG_FULL);
+  grid2.interp = &g2;
+  lo_op_desc grid3 = desc(LO_OP_SKI_GRID_DIAG, 2, 50, 60, 8, false, LO_DIAG_FULL);
+  grid3.interp = &g3;
+  t.push_back({"ski", ski, true});
+  t.push_back({"ski_plan", ski_p, true});
+  t.push_back({"ski_grid_2d", grid2, true});
+  t.push_back({"ski_grid_3d", grid3, true});
+  t.push_back({"hadamard", desc(LO_OP_HADAMARD_DIAG, 2, 70, 3, 2, true, LO_DIAG_FULL), true});
+
+  lo_op_desc terms2[2] = {desc(LO_OP_LOWRANK_DIAG, 2, 80, 5, 0, false, LO_DIAG_NONE),
+                          desc(LO_OP_DENSE_DIAG, 2, 80, 0, 0, false, LO_DIAG_NONE)};
+  lo_op_desc terms3[3] = {terms2[0], terms2[1], desc(LO_OP_KRON_DIAG, 2, 80, 8, 10, true, LO_DIAG_NONE)};
+  lo_op_desc sum2 = desc(LO_OP_SUM, 2, 80, 0, 0, false, LO_DIAG_FULL), sum3 = sum2;
+  sum2.A0 = sum3.A0 = nullptr;
+  sum2.nterms = 2; sum2.terms = terms2;
+  sum3.nterms = 3; sum3.terms = terms3;
+  lo_op_desc base_dense = desc(LO_OP_DENSE_DIAG, 2, 90, 0, 0, false, LO_DIAG_FULL);
+  lo_op_desc base_kron = desc(LO_OP_KRON_DIAG, 2, 42, 6, 7, true, LO_DIAG_NONE);
+  lo_mask_desc md = {&base_dense, I(0x70000), 61}, mk = {&base_kron, I(0x70000), 29}, ms = {&sum2, I(0x70000), 57};
+  lo_op_desc m_dense = desc(LO_OP_MASKED, 2, 61, 0, 0, false, LO_DIAG_FULL);
+  m_dense.A0 = nullptr;
+  lo_op_desc m_kron = m_dense, m_sum = m_dense;
+  m_dense.mask = &md;
+  m_kron.N = 29; m_kron.mask = &mk;
+  m_sum.N = 57; m_sum.mask = &ms;
+  t.push_back({"masked_dense", m_dense, true});
+  t.push_back({"masked_kron", m_kron, true});
+  t.push_back({"masked_sum", m_sum, true});
+  t.push_back({"sum3", sum3, true});
+
+  // one refused descriptor per kind (and a sum whose LATER term is refused: the earlier terms' plans must not stay)
+  auto refuse = [&](const char* name, lo_op_desc d) { t.push_back({name, d, false}); };
+  lo_op_desc x = t[0].op; x.R = 0; refuse("bad lowrank", x);
+  x = t[3].op; x.A0 = nullptr; refuse("bad dense", x);
+  x = t[4].op; x.n2 = 4; refuse("bad kron", x);
+  x = t[6].op; x.R = 32; refuse("bad toeplitz", x);
+  x = ski; x.interp = nullptr; refuse("bad ski", x);
+  x = grid2; x.R = 34; refuse("bad ski grid", x);
+  x = t[11].op; x.n2 = 0; refuse("bad hadamard", x);
+  x = m_dense; x.N = 5; refuse("bad masked", x);
+  const lo_op_desc had = t[11].op;  // (a copy: the table grows)
+  lo_mask_desc mh = {&had, I(0x70000), 61};
+  x = m_dense; x.mask = &mh; refuse("masked over hadamard", x);
+  x = sum3; x.nterms = 1; refuse("bad sum", x);
+  lo_op_desc x_cb = desc(LO_OP_CALLBACK, 2, 64, 0, 0, false, LO_DIAG_NONE); refuse("callback without one", x_cb);
+  int bad = walk(t);
+
+  lo_op_desc late[3] = {terms3[0], terms3[1], terms3[2]};
+  late[2].n2 = 9;  // 8 * 9 != 80: refused after the first two terms were planned
+  lo_op_desc sum_late = sum3;
+  sum_late.terms = late;
+  bad += walk({{"sum, bad last term", sum_late, true}});  // (its first terms do take buffers)
+  printf(bad ? "FAILED: %d\n" : "ok\n", bad);
+  return bad ? 1 : 0;
+}
