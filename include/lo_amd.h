@@ -70,8 +70,12 @@ extern "C" {
 #define LO_SKI_GRID_MAX_AXIS 1024 /* grid points per axis the native grid product takes (larger: LO_ERR_UNSUPPORTED)    */
 #define LO_SKI_GRID_MAX_M 4194304 /* grid points in all, 2^22 (larger: LO_ERR_UNSUPPORTED)                              */
 
+#define LO_OP_TOEPLITZ_KRON_DIAG 10 /* AddedDiag(Kron(Toeplitz(t_1), .., Toeplitz(t_D)), Diag(d)), D = 2 or 3:
+                                    *   y = (T_1 (x) .. (x) T_D) v + d o v   (a GP on a regular 2-D / 3-D grid)         */
+
 struct lo_interp_desc;
 struct lo_mask_desc;
+struct lo_grid_desc;
 
 /* Operator descriptor ("op-tree lowering" of an AddedDiag/Sum tree). */
 typedef struct lo_op_desc {
@@ -92,6 +96,7 @@ typedef struct lo_op_desc {
                       * Python sum()); the SUM's own (diag_mode, d) is the one diagonal of the tree */
     const struct lo_interp_desc* interp; /* SKI (ABI 16): HOST pointer to the two interpolation matrices      */
     const struct lo_mask_desc* mask;     /* MASKED (ABI 21): HOST pointer to the base descriptor and the index list */
+    const struct lo_grid_desc* grid;     /* TOEPLITZ_KRON (ABI 24): HOST pointer to the grid shape                  */
   };
   /* ABI 16 kinds.  TOEPLITZ: A0 = first column t [B, M] of the symmetric Toeplitz matrix, R = M = N.
    * SKI: A0 = t [B, M], R = M (grid size), n2 = J (interpolation points per row), `interp` as below.
@@ -108,13 +113,26 @@ typedef struct lo_op_desc {
    * `interp` as for SKI with the grid shape in its grid_ndim / grid_m (same layout again).  Lowered for lo_matvec_f32,
    * the streaming CG, Lanczos, fp32 MINRES and the fp32 pivoted Cholesky; the fp64 entry points, the resident / fused
    * engines and the solve sessions return LO_ERR_UNSUPPORTED; not a term kind of LO_OP_SUM, not a base kind of
-   * LO_OP_MASKED.                                                                                                    */
+   * LO_OP_MASKED.
+   * ABI 24 kind.  TOEPLITZ_KRON: the base of SKI_GRID on its own.  A0 = the first columns of the D Toeplitz factors
+   * concatenated per member [B, M_1 + .. + M_D], N = R = M_1 * .. * M_D (same grid index), `grid` as below (same layout
+   * again); shape limits LO_SKI_GRID_MAX_AXIS / LO_SKI_GRID_MAX_M.  Lowered for lo_matvec_f32, the streaming CG,
+   * Lanczos, fp32 MINRES and the fp32 pivoted Cholesky (diagonal prod_k t_k[0], row[j] = prod_k t_k[|i_k - j_k|]); the
+   * fp64 entry points, the resident / fused engines and the solve sessions return LO_ERR_UNSUPPORTED; not a term kind of
+   * LO_OP_SUM, not a base kind of LO_OP_MASKED.                                                                       */
 } lo_op_desc;
+
+/* The grid shape of an LO_OP_TOEPLITZ_KRON_DIAG descriptor (host struct). */
+struct lo_grid_desc { /* (a plain struct tag, as lo_mask_desc) */
+  int32_t ndim;      /* D: 2 or 3 */
+  int32_t reserved;
+  int64_t m[3];      /* M_1 .. M_D (m[2] unused when D == 2), each <= LO_SKI_GRID_MAX_AXIS */
+};
 
 /* The base operator and the selected rows of an LO_OP_MASKED descriptor (masked_linear_operator.py:17-35 with
  * row_mask == col_mask): y = S (base) S^T v + d o v, S selecting the rows idx of the base.  base: HOST descriptor of
  * kind LOWRANK_DIAG, DENSE_DIAG, KRON_DIAG or SUM with any diagonal mode of its own (CALLBACK, MASKED, SKI, SKI_GRID,
- * TOEPLITZ, HADAMARD: LO_ERR_UNSUPPORTED).  idx: DEVICE pointer, int64 [M], strictly increasing, one list for all members; an
+ * TOEPLITZ, TOEPLITZ_KRON, HADAMARD: LO_ERR_UNSUPPORTED).  idx: DEVICE pointer, int64 [M], strictly increasing, one list for all members; an
  * entry outside [0, base->N) contributes nothing and is never dereferenced (the convention of lo_interp_desc).      */
 struct lo_mask_desc { /* (a plain struct tag: C callers write `struct lo_mask_desc`) */
   const struct lo_op_desc* base;
@@ -785,6 +803,20 @@ int lo_interp_values_grad_f32(const int64_t* idx, int64_t B, int64_t N, int64_t 
 size_t lo_toeplitz_kron_workspace_bytes(const int64_t* m, int ndim, int64_t B, int64_t c);
 int lo_toeplitz_kron_mv_f32(const float* t, const int64_t* m, int ndim, int64_t B, const float* u, int64_t c, float* y,
                             void* ws, size_t ws_bytes, void* stream);
+/* Gradients of sum_s u_s^T (T_1 (x) .. (x) T_D) v_s with respect to the factors' first columns (ABI 24):
+ *   g [B, M_1 + .. + M_D], g_k[b, l] = sum_s u_s^T (dK / dt_k[l]) v_s;  t, m as above;  u, v [B, M, S].
+ * With W_k = v with every factor but T_k applied, viewed as [lines = B * outer, M_k, inner], inner = (prod_{j > k} M_j) S:
+ *   g_k[b, l] = sum_{lines of b} sum_s sum_i (u[i, s] W_k[i + l, s] + [l > 0] u[i + l, s] W_k[i, s]).
+ * The partial products are single-axis passes of the grid product, shared between the axes and, the factors being
+ * symmetric, applied to u where that saves one (2 passes for D = 2, 4 for D = 3); an axis lag-correlation kernel writes
+ * one partial [M_k] per (member, chunk of lines) and a second kernel adds the partials in ascending order.
+ * Deterministic (fixed-order sums, no float atomics).  LO_ERR_UNSUPPORTED outside the shape limits of
+ * lo_toeplitz_kron_mv_f32; LO_ERR_BADARG: null pointers, non-positive sizes.  ws: the _workspace_bytes query (0: a shape
+ * that is not taken).  (sym_toeplitz_derivative_quadratic_form per axis; the reference obtains these by autograd of
+ * KroneckerProductLinearOperator._matmul.)                                                                           */
+size_t lo_toeplitz_kron_bilinear_workspace_bytes(const int64_t* m, int ndim, int64_t B, int64_t S);
+int lo_toeplitz_kron_bilinear_f32(const float* t, const int64_t* m, int ndim, int64_t B, const float* u, const float* v,
+                                  int64_t S, float* g, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- Hadamard product of two roots (ABI 17; csrc/lo_hadamard.hip) -------------------------------------------------
  * K = (F F^T) o (G G^T), F [B, N, p], G [B, N, q], p, q <= LO_HADAMARD_MAX_RANK; U, V [B, N, S], S columns innermost.

@@ -26,9 +26,10 @@ LO_OP_MASKED = 8
 LO_OP_SKI_GRID_DIAG = 9
 LO_SKI_GRID_MAX_AXIS = 1024
 LO_SKI_GRID_MAX_M = 4194304
+LO_OP_TOEPLITZ_KRON_DIAG = 10
 LO_DIAG_NONE, LO_DIAG_FULL, LO_DIAG_CONST = 0, 1, 2
 LO_BLOCK_DIAG, LO_BLOCK_INTERLEAVED, LO_BLOCK_SUM = 0, 1, 2
-ABI_VERSION = 23
+ABI_VERSION = 24
 
 LO_ERR_UNSUPPORTED = -4
 LO_FUSED_OK, LO_FUSED_EARLY_STOP, LO_FUSED_CONTINUE, LO_FUSED_TIMEOUT = 0, 1, 2, 3
@@ -57,6 +58,12 @@ class InterpDesc(C.Structure):
     _fields_ = [("left_idx", C.c_void_p), ("left_vals", C.c_void_p), ("right_idx", C.c_void_p),
                 ("right_vals", C.c_void_p), ("right_plan", C.c_void_p), ("grid_ndim", C.c_int32),
                 ("grid_reserved", C.c_int32), ("grid_m", C.c_int64 * 3)]
+
+
+class GridDesc(C.Structure):
+    """lo_grid_desc (include/lo_amd.h): the grid shape of an LO_OP_TOEPLITZ_KRON_DIAG descriptor, reached through the
+    descriptor's `terms` slot (a union in C)."""
+    _fields_ = [("ndim", C.c_int32), ("reserved", C.c_int32), ("m", C.c_int64 * 3)]
 
 
 class MaskDesc(C.Structure):
@@ -250,6 +257,8 @@ _PROTOTYPES = {
     "lo_interp_values_grad_f32": (ci, [vp, i64, i64, i64, i64, vp, vp, i64, vp, vp]),
     "lo_toeplitz_kron_workspace_bytes": (sz, [P(i64), ci, i64, i64]),
     "lo_toeplitz_kron_mv_f32": (ci, [vp, P(i64), ci, i64, vp, i64, vp, vp, sz, vp]),
+    "lo_toeplitz_kron_bilinear_workspace_bytes": (sz, [P(i64), ci, i64, i64]),
+    "lo_toeplitz_kron_bilinear_f32": (ci, [vp, P(i64), ci, i64, vp, vp, i64, vp, vp, sz, vp]),
     "lo_hadamard_bilinear_workspace_bytes": (sz, [i64, i64, i64, i64, i64]),
     "lo_hadamard_bilinear_f32": (ci, [vp, vp, vp, vp, i64, i64, i64, i64, i64, vp, vp, vp, sz, vp]),
     "lo_cholesky_workspace_bytes": (sz, [i64, i64]),

@@ -210,6 +210,15 @@ int ski_interp_plan(MatvecPlan* pl, int64_t M, Arena* ar, hipStream_t st);
 int ski_grid_plan(MatvecPlan* pl, Arena* ar, hipStream_t st);
 int ski_grid_matvec_run(const MatvecPlan* pl, const float* v, float* y, const int* stop, hipStream_t st);
 
+// ---- Kronecker product of 2 / 3 symmetric Toeplitz factors (lo_ski_grid.hip): LO_OP_TOEPLITZ_KRON_DIAG -----------------
+struct ToeplitzKronPlan {
+  lo_grid_desc g;   // a copy of the host struct op.grid
+  float* tmp;       // [B, M, c]: the grid vector between the passes (the last pass writes y)
+  bool epilogue;    // the diagonal term as a kernel of its own behind the passes (A/B switch; default: in the last pass)
+};
+int toeplitz_kron_plan(MatvecPlan* pl, Arena* ar, hipStream_t st);
+int toeplitz_kron_matvec_run(const MatvecPlan* pl, const float* v, float* y, const int* stop, hipStream_t st);
+
 // ---- Hadamard product of two roots (lo_hadamard.hip) ---------------------------------------------------------------
 struct HadamardPlan {
   float *part, *m;  // the contraction partials and the reduced M_t of every column (lo_hadamard.hip)
@@ -246,6 +255,7 @@ struct MatvecPlan {
     KronPlan kron;
     SumPlan sum;
     SkiPlan ski;
+    ToeplitzKronPlan tk;
     HadamardPlan hd;
     MaskedPlan mask;
   };

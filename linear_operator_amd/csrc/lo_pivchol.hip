@@ -7,6 +7,8 @@
 //   Kron:             row[i] = K1[p1,i1] K2[p2,i2]           (kronecker_product_linear_operator.py:198-216)
 //   Hadamard:         row[i] = (F_p . F_i)(G_p . G_i)        (mul_linear_operator.py:49-52, diag |F_i|^2 |G_i|^2 :43-47)
 //   Toeplitz:         row[i] = t[|p - i|]                    (toeplitz_linear_operator.py:38-40, diag :25-31)
+//   Toeplitz Kron:    row[i] = prod_k t_k[|p_k - i_k|]       (kronecker_product_linear_operator.py:198-216 over the
+//                                                            Toeplitz rows), the diagonal prod_k t_k[0] is constant
 //   SKI:              row[i] = sum_b sum_a t[|li[p,a] - ri[i,b]|] (lv[p,a] rv[i,b])
 //                                                            (interpolated_linear_operator.py:130-144); the diagonal
 //                     is the reference's APPROXIMATE one, (W_l sqrt(t0)) o (W_r sqrt(t0)) (:94-101,
@@ -45,7 +47,8 @@ struct PcDevT {
   // reference, sum_linear_operator.py:31-45): one entry for a plain operator
   int nterms;
   lo_op_desc terms[LO_MAX_TERMS];
-  lo_interp_desc ski;  // LO_OP_SKI_DIAG: the interpolation matrices (a device-side copy of the host struct op.interp)
+  lo_interp_desc ski;  // LO_OP_SKI_DIAG: the interpolation matrices (a device-side copy of the host struct op.interp);
+                       // LO_OP_TOEPLITZ_KRON_DIAG: only grid_ndim / grid_m, copied from the host struct op.grid
   int64_t B, N;
   int S, rows;     // position split
   int max_rank;
@@ -124,6 +127,19 @@ __device__ __forceinline__ T src_diag(const PcDevT<T>& d, const lo_op_desc& op, 
     return seq_dot(fi, fi, (int)op.R) * seq_dot(gi, gi, (int)op.n2);
   } else if (op.kind == LO_OP_TOEPLITZ_DIAG) {
     return A0[(size_t)b * op.R];
+  } else if (op.kind == LO_OP_TOEPLITZ_KRON_DIAG) {
+    // prod_k t_k[0], the trailing factors multiplied first (kronecker_product_linear_operator.py:22-28)
+    const int D = d.ski.grid_ndim;
+    int64_t sumM = 0;
+    for (int k = 0; k < D; ++k) sumM += d.ski.grid_m[k];
+    const T* col = A0 + (size_t)b * sumM;
+    int64_t o = sumM - d.ski.grid_m[D - 1];
+    T t0 = col[o];
+    for (int k = D - 2; k >= 0; --k) {
+      o -= d.ski.grid_m[k];
+      t0 = col[o] * t0;
+    }
+    return t0;
   } else if (op.kind == LO_OP_SKI_DIAG) {  // (left_interp(li, lv, sqrt t0) * left_interp(ri, rv, sqrt t0)), :94-101
     // (an index outside [0, M) contributes nothing, as in the rows below)
     const int J = (int)op.n2;
@@ -434,6 +450,19 @@ __global__ __launch_bounds__(kThreads) void k_pc_update(PcDevT<T> d, int m) {
         } else if (tm.kind == LO_OP_TOEPLITZ_DIAG) {
           const int lag = pim > i ? pim - i : i - pim;
           tv = pc_ptr<T>(tm.A0)[(size_t)b * tm.R + lag];
+        } else if (tm.kind == LO_OP_TOEPLITZ_KRON_DIAG) {
+          // prod_k t_k[|p_k - i_k|], factors multiplied left to right (kronecker_product_linear_operator.py:198-216);
+          // consecutive threads hold consecutive positions j: the gathers from the (small) columns stay in cache
+          const int D = d.ski.grid_ndim;
+          const int m1 = (int)d.ski.grid_m[D - 2], m2 = (int)d.ski.grid_m[D - 1];  // the two trailing axes
+          const int m0 = D == 3 ? (int)d.ski.grid_m[0] : 0;
+          const T* c0 = pc_ptr<T>(tm.A0) + (size_t)b * (m0 + m1 + m2);  // (D == 2: no leading axis)
+          const T* c1 = c0 + m0;
+          const T* c2 = c1 + m1;
+          const int p2 = pim % m2, p1 = (pim / m2) % m1, p0 = pim / (m2 * m1);
+          const int q2 = i % m2, q1 = (i / m2) % m1, q0 = i / (m2 * m1);
+          const T f1 = c1[p1 > q1 ? p1 - q1 : q1 - p1], f2 = c2[p2 > q2 ? p2 - q2 : q2 - p2];
+          tv = D == 3 ? (c0[p0 > q0 ? p0 - q0 : q0 - p0] * f1) * f2 : f1 * f2;
         } else if (tm.kind == LO_OP_SKI_DIAG) {
           // base_vals[b', a] * (lv[p, a] rv[i, b']) summed over both (:139-144); out-of-grid entries contribute nothing
           const int J = (int)tm.n2;
@@ -539,6 +568,10 @@ static void pc_layout(const lo_op_desc* op, int max_rank, Arena& ar, PcDevT<T>* 
   }
   d->ski = ((op->kind == LO_OP_SKI_DIAG || op->kind == LO_OP_SKI_GRID_DIAG) && op->interp) ? *op->interp
                                                                                             : lo_interp_desc{};
+  if (op->kind == LO_OP_TOEPLITZ_KRON_DIAG && op->grid) {
+    d->ski.grid_ndim = op->grid->ndim;
+    for (int k = 0; k < 3; ++k) d->ski.grid_m[k] = op->grid->m[k];
+  }
   d->B = B; d->N = N; d->S = sp.S; d->rows = sp.rows; d->max_rank = max_rank;
   d->ctrl = ar.take<PcCtrl>(1);
   d->diag = ar.take<T>((size_t)B * N);
@@ -666,6 +699,17 @@ static int pc_check_desc(const lo_op_desc* op) {
     }
     if (M > LO_SKI_GRID_MAX_M) return LO_ERR_UNSUPPORTED;
     if (M != op->R) return LO_ERR_BADARG;
+  } else if (op->kind == LO_OP_TOEPLITZ_KRON_DIAG) {
+    const lo_grid_desc* g = op->grid;
+    if (!op->A0 || !g) return LO_ERR_BADARG;
+    if (g->ndim != 2 && g->ndim != 3) return LO_ERR_UNSUPPORTED;
+    int64_t M = 1;
+    for (int k = 0; k < g->ndim; ++k) {
+      if (g->m[k] < 1 || g->m[k] > LO_SKI_GRID_MAX_AXIS) return LO_ERR_UNSUPPORTED;
+      M *= g->m[k];
+    }
+    if (M > LO_SKI_GRID_MAX_M) return LO_ERR_UNSUPPORTED;
+    if (M != op->R || M != op->N) return LO_ERR_BADARG;
   } else if (op->kind != LO_OP_LOWRANK_DIAG && op->kind != LO_OP_DENSE_DIAG && op->kind != LO_OP_KRON_DIAG) {
     return LO_ERR_UNSUPPORTED;
   }
@@ -735,7 +779,7 @@ int lo_pivoted_cholesky_f64(const lo_op_desc* op, int32_t max_rank, double error
                             int32_t* rank_out, void* ws, size_t ws_bytes, void* stream) {
   if (!op || !L_rows || !perm || !rank_out || !ws || max_rank < 1) return LO_ERR_BADARG;
   if (op->kind == LO_OP_SKI_DIAG || op->kind == LO_OP_TOEPLITZ_DIAG || op->kind == LO_OP_HADAMARD_DIAG ||
-      op->kind == LO_OP_SKI_GRID_DIAG)
+      op->kind == LO_OP_SKI_GRID_DIAG || op->kind == LO_OP_TOEPLITZ_KRON_DIAG)
     return LO_ERR_UNSUPPORTED;  // (fp32 kinds)
   if (const int rc = pc_check_desc(op)) return rc;
   return pc_stream_t<double>(op, nullptr, nullptr, nullptr, max_rank, error_tol, L_rows, perm, rank_out, ws, ws_bytes,

@@ -37,7 +37,9 @@ class OperatorDescriptor:
     interp: tuple = ()  # LO_OP_SKI_DIAG: (left_idx, left_vals, right_idx, right_vals), [B, N, J] int64 / fp32
     interp_plan: Optional[torch.Tensor] = None  # LO_OP_SKI_DIAG: grid-major copy of W_r kept across calls (interp_plan)
     mask: tuple = ()  # LO_OP_MASKED: (descriptor of the base operator, idx int64 [M] of the selected rows)
-    grid: tuple = ()  # LO_OP_SKI_GRID_DIAG: the grid shape (M_1, .., M_D); A0 = the factors' columns [B, M_1 + .. + M_D]
+    # LO_OP_SKI_GRID_DIAG, LO_OP_TOEPLITZ_KRON_DIAG: the grid shape (M_1, .., M_D); A0 = the factors' columns
+    # [B, M_1 + .. + M_D]
+    grid: tuple = ()
     # element type of A0 / A1 / d.  The C struct does not record it: float64 descriptors (low-rank / dense / Kronecker /
     # sums of those) go to lo_matvec_f64 and the float64 solvers only, and c_struct() refuses to hand one to an entry
     # point that reads `float*`
@@ -80,6 +82,10 @@ class OperatorDescriptor:
                 w.grid_m = (C.c_int64 * 3)(*self.grid)
             s.terms = C.cast(C.pointer(w), C.POINTER(_hip.OpDesc))
             s._interp_keepalive = w
+        if self.kind == _hip.LO_OP_TOEPLITZ_KRON_DIAG:  # the union slot `grid`: a host struct of the grid shape
+            g = _hip.GridDesc(len(self.grid), 0, (C.c_int64 * 3)(*self.grid))
+            s.terms = C.cast(C.pointer(g), C.POINTER(_hip.OpDesc))
+            s._grid_keepalive = g
         if self.mask:  # the union slot `mask`: a host struct of the base's host descriptor and the device index list
             base = self.mask[0].c_struct()
             m = _hip.MaskDesc(C.pointer(base), self.mask[1].data_ptr(), self.mask[1].numel())
@@ -397,6 +403,42 @@ def ski_grid_diag_descriptor(cols, left_idx: torch.Tensor, left_vals: torch.Tens
     return _with_diag(OperatorDescriptor(_hip.LO_OP_SKI_GRID_DIAG, B, N, A0=col, R=math.prod(grid), n2=J,
                                          batch_shape=batch, interp=(li, lv, ri, rv), interp_plan=right_plan, grid=grid),
                       d, const_diag)
+
+
+def toeplitz_kron_diag_descriptor(cols, d: Optional[torch.Tensor], const_diag: bool = False):
+    """AddedDiag(Kron(Toeplitz(cols[0]), .., Toeplitz(cols[D-1])), Diag(d)) (or the product alone), D = 2 or 3:
+    y = (T_1 (x) .. (x) T_D) v + d o v.  cols[k] [*b_k, M_k] of batch shapes that broadcast; the columns are concatenated
+    once per (columns, batch) and memoised (_ski_grid_columns).  None when the grid is outside what the kind takes."""
+    cols = list(cols)
+    _hip.require_hip(*cols, d)
+    grid = tuple(int(t.shape[-1]) for t in cols)
+    if not ski_grid_shape_ok(grid):
+        return None
+    batch = torch.broadcast_shapes(*(t.shape[:-1] for t in cols))
+    col = _ski_grid_columns(cols, batch)
+    M = math.prod(grid)
+    return _with_diag(OperatorDescriptor(_hip.LO_OP_TOEPLITZ_KRON_DIAG, col.shape[0], M, A0=col, R=M,
+                                         batch_shape=torch.Size(batch), grid=grid), d, const_diag)
+
+
+def toeplitz_kron_bilinear(cols, u: torch.Tensor, v: torch.Tensor):
+    """Per-factor column gradients of sum_s u_s^T (T_1 (x) .. (x) T_D) v_s (lo_toeplitz_kron_bilinear_f32): cols[k]
+    [B, M_k], D = 2 or 3; u, v [B, M, S].  Returns the list of g_k [B, M_k].  A shape the kernels do not take raises."""
+    lib = _hip.load()
+    cols = [t.contiguous() for t in cols]
+    _hip.require_hip(*cols, u, v)
+    grid = [int(t.shape[-1]) for t in cols]
+    B, M, S = u.shape
+    if any(t.dim() != 2 or t.shape[0] != B for t in cols) or math.prod(grid) != M or v.shape != u.shape:
+        raise RuntimeError(f"toeplitz_kron_bilinear: columns of sizes {[tuple(t.shape) for t in cols]} for u "
+                           f"{tuple(u.shape)}, v {tuple(v.shape)}")
+    t = torch.cat(cols, -1).contiguous()
+    u, v = u.contiguous(), v.contiguous()
+    g = torch.empty(B, sum(grid), dtype=torch.float32, device=u.device)
+    m = (C.c_int64 * len(grid))(*grid)
+    _launch("lo_toeplitz_kron_bilinear_f32", u.device, t, m, len(grid), B, u, v, S, g,
+            ws_bytes=lib.lo_toeplitz_kron_bilinear_workspace_bytes(m, len(grid), B, S))
+    return list(g.split(grid, -1))
 
 
 def toeplitz_kron_mv(cols, u: torch.Tensor) -> torch.Tensor:

@@ -1,7 +1,10 @@
 """KroneckerProductLinearOperator K1 (x) ... (x) KP -- `_matmul`, `_diagonal`, `_get_indices` only
 (reference: operators/kronecker_product_linear_operator.py:20-45, 62-96, 188-216, 272-284).  Two dense factors
 lower to the batched-GEMM kernel pair in csrc/lo_kron.hip; products of more dense factors are regrouped into two
-dense groups (`_two_groups`) and lower the same way.  `+ Diag` / `add_diagonal` build the
+dense groups (`_two_groups`) and lower the same way.  A product of 2 or 3 symmetric Toeplitz factors (the covariance of
+a GP on a regular 2-D / 3-D grid) lowers to LO_OP_TOEPLITZ_KRON_DIAG (csrc/lo_ski_grid.hip), and the gradients with
+respect to the factors' columns come from lo_toeplitz_kron_bilinear_f32 or, outside its limits, from the same closed
+form in torch.  `+ Diag` / `add_diagonal` build the
 KroneckerProductAddedDiagLinearOperator like the reference (:98-145): eigendecomposition closed forms for a
 constant diagonal, the CG path otherwise (an explicit AddedDiagLinearOperator(kron, diag) is always the CG path)."""
 from __future__ import annotations
@@ -14,9 +17,21 @@ from torch import Tensor
 from .. import kernels as K
 from .. import settings
 from ..utils.broadcasting import _matmul_broadcast_shape
+from ..utils.toeplitz import sym_toeplitz_derivative_quadratic_form, sym_toeplitz_matmul
 from ._linear_operator import LinearOperator
 from .dense_linear_operator import DenseLinearOperator, to_linear_operator
 from .diag_linear_operator import DiagLinearOperator
+from .toeplitz_linear_operator import ToeplitzLinearOperator
+
+# Which products of a Kronecker product of Toeplitz factors `_matmul` hands to the kernels, by (axes, one column / more
+# columns): True only where tools/mb_toeplitz_kron.py measured the native product at least as fast as the per-factor
+# composition `_matmul` otherwise runs (DESIGN.md section 6j holds both times of every cell).  A cell that is absent
+# keeps the composition; the descriptor still serves CG, Lanczos, MINRES and the pivoted Cholesky, where it replaces a
+# Python call per product.  Measured (native / composition, microseconds; 1 column, 17 columns):
+#   2-D  1 x 128 (x) 128            19 /   236      24 /  3885
+#   2-D  16 x 64 (x) 64             17 /   118      34 /  1883
+#   3-D  1 x 32 (x) 32 (x) 32       21 /  2382      31 / 40654
+_NATIVE_MATMUL_TOEPLITZ: dict = {(2, 1): True, (2, 2): True, (3, 1): True, (3, 2): True}
 
 
 def _kron_diag(*ops) -> Tensor:
@@ -65,6 +80,27 @@ def _group_pullback(dG: Tensor, ts):
         expr = f"...{rows}{cols},{others}->...{rows[i]}{cols[i]}"
         out.append(torch.einsum(expr, dG, *[ts[j] for j in range(p) if j != i]))
     return out
+
+
+def _toeplitz_kron_bilinear_torch(cols, u: Tensor, v: Tensor):
+    """The column gradients of sum_s u_s^T (T_1 (x) .. (x) T_D) v_s in torch, any number of factors: cols[k]
+    [*batch, M_k], u, v [*batch, N, S] of one batch shape.  Returns [g_k [*batch, M_k]]."""
+    batch, (N, S) = u.shape[:-2], u.shape[-2:]
+    sizes = [int(t.shape[-1]) for t in cols]
+
+    def axis_view(x, k):  # [*batch, outer, M_k, inner]
+        outer = math.prod(sizes[:k])
+        return x.reshape(*batch, outer, sizes[k], N // (outer * sizes[k]) * S)
+
+    grads = []
+    for k in range(len(cols)):
+        w = v
+        for j in range(len(cols)):
+            if j != k:
+                w = sym_toeplitz_matmul(cols[j].unsqueeze(-2), axis_view(w, j).contiguous()).reshape(*batch, N, S)
+        g = sym_toeplitz_derivative_quadratic_form(axis_view(u, k).contiguous(), axis_view(w, k).contiguous())
+        grads.append(g.sum(-2))
+    return grads
 
 
 class KroneckerProductLinearOperator(LinearOperator):
@@ -124,7 +160,24 @@ class KroneckerProductLinearOperator(LinearOperator):
             self._groups_cache = cache
         return cache[1]
 
+    def _toeplitz_columns(self):
+        """The factors' first columns when every factor is a symmetric Toeplitz operator, else None."""
+        if len(self.linear_ops) < 2 or not all(isinstance(op, ToeplitzLinearOperator) for op in self.linear_ops):
+            return None
+        return [op.column for op in self.linear_ops]
+
+    def _toeplitz_native(self, cols) -> bool:
+        """Whether the kernels of csrc/lo_ski_grid.hip take these columns: 2 or 3 fp32 HIP columns within the limits."""
+        return (all(t.is_cuda and t.dtype == torch.float32 for t in cols)
+                and K.ski_grid_shape_ok(tuple(int(t.shape[-1]) for t in cols)))
+
     def _kernel_descriptor(self, batch_shape=None):
+        cols = self._toeplitz_columns()
+        if cols is not None:
+            if not self._toeplitz_native(cols):
+                return None
+            bs = torch.Size(batch_shape) if batch_shape is not None else self.batch_shape
+            return K.toeplitz_kron_diag_descriptor([t.expand(*bs, t.shape[-1]) for t in cols], None)
         groups = self._two_groups()
         if groups is None:
             return None
@@ -137,6 +190,9 @@ class KroneckerProductLinearOperator(LinearOperator):
     def _bilinear_derivative(self, left_vecs: Tensor, right_vecs: Tensor):
         """(dK1, dK2) = (sum_d U_d K2 V_d^T, sum_d U_d^T K1 V_d): the reference's generic autograd version
         (_linear_operator.py:336-393) applied to the Kronecker matvec (:34-45); two dense factors on this path."""
+        cols = self._toeplitz_columns()
+        if cols is not None:
+            return self._toeplitz_bilinear_derivative(cols, left_vecs, right_vecs)
         groups = self._two_groups()
         if groups is None:
             return super()._bilinear_derivative(left_vecs, right_vecs)
@@ -145,6 +201,30 @@ class KroneckerProductLinearOperator(LinearOperator):
         ts = [op.tensor for op in self.linear_ops]
         grads = _group_pullback(d1, ts[:j]) + _group_pullback(d2, ts[j:])
         return tuple(g if tuple(g.shape) == tuple(t.shape) else g.sum_to_size(*t.shape) for g, t in zip(grads, ts))
+
+    def _toeplitz_bilinear_derivative(self, cols, left_vecs: Tensor, right_vecs: Tensor):
+        """One gradient per factor column.  With W_k = v with every factor but T_k applied, u and W_k viewed as
+        [*batch, outer, M_k, inner] (inner = (prod_{j > k} M_j) S):
+            g_k[l] = sum_{outer} sum_s sum_i (u[i, s] W_k[i + l, s] + [l > 0] u[i + l, s] W_k[i, s])
+        -- the Toeplitz lag correlation along axis k, summed over the lines of the other axes (the reference obtains the
+        same by autograd of `_matmul`).  Native for 2 or 3 fp32 HIP columns within the kernel's limits; CPU, float64, more
+        factors and larger grids take the same formula in torch."""
+        if left_vecs.ndimension() == 1:
+            left_vecs, right_vecs = left_vecs.unsqueeze(-1), right_vecs.unsqueeze(-1)
+        batch = torch.broadcast_shapes(self.batch_shape, left_vecs.shape[:-2], right_vecs.shape[:-2])
+        sizes = [int(t.shape[-1]) for t in cols]
+        N, S = math.prod(sizes), left_vecs.shape[-1]
+        u = left_vecs.expand(*batch, N, S)
+        v = right_vecs.expand(*batch, N, S)
+        ecols = [t.detach().expand(*batch, t.shape[-1]) for t in cols]
+        if (self._toeplitz_native(cols) and u.is_cuda and u.dtype == torch.float32 and v.is_cuda
+                and v.dtype == torch.float32):
+            grads = K.toeplitz_kron_bilinear([t.reshape(-1, t.shape[-1]) for t in ecols], u.reshape(-1, N, S),
+                                             v.reshape(-1, N, S))
+            grads = [g.reshape(*batch, g.shape[-1]) for g in grads]
+        else:
+            grads = _toeplitz_kron_bilinear_torch(ecols, u, v)
+        return tuple(g if tuple(g.shape) == tuple(t.shape) else g.sum_to_size(*t.shape) for g, t in zip(grads, cols))
 
     def __add__(self, other):  # reference :98-114
         from .diag_linear_operator import ConstantDiagLinearOperator, DiagLinearOperator
@@ -224,7 +304,9 @@ class KroneckerProductLinearOperator(LinearOperator):
         if is_vec:
             rhs = rhs.unsqueeze(-1)
         desc = None
-        if K.native_matmul_candidate(self, rhs):
+        if K.native_matmul_candidate(self, rhs) and (
+                self._toeplitz_columns() is None
+                or _NATIVE_MATMUL_TOEPLITZ.get((len(self.linear_ops), 1 if rhs.shape[-1] == 1 else 2), False)):
             desc = self._kernel_descriptor(torch.broadcast_shapes(self.batch_shape, rhs.shape[:-2]))
         if K.native_matmul(desc, rhs):
             res = K.matvec(desc, rhs.expand(*desc.batch_shape, *rhs.shape[-2:]))
