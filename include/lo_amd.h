@@ -68,6 +68,8 @@ extern "C" {
 #define LO_OP_SKI_GRID_DIAG 9 /* AddedDiag(Interpolated(Kron(Toeplitz(t_1), .., Toeplitz(t_D)), W_l, W_r), Diag(d)), D = 2 or 3:
                                *   y = W_l (T_1 (x) .. (x) T_D) W_r^T v + d o v   (SKI on a 2-D / 3-D grid)             */
 #define LO_SKI_GRID_MAX_AXIS 1024 /* grid points per axis the native grid product takes (larger: LO_ERR_UNSUPPORTED)    */
+#define LO_KRON_EIG_MAX_SMALL 16  /* task-factor sizes n2 the fused kernel of lo_kron_eig_apply_f32 takes                */
+#define LO_KRON_EIG_MAX_COLS 256  /* right-hand-side columns it takes (more: LO_ERR_UNSUPPORTED, the caller composes)    */
 #define LO_SKI_GRID_MAX_M 4194304 /* grid points in all, 2^22 (larger: LO_ERR_UNSUPPORTED)                              */
 
 #define LO_OP_TOEPLITZ_KRON_DIAG 10 /* AddedDiag(Kron(Toeplitz(t_1), .., Toeplitz(t_D)), Diag(d)), D = 2 or 3:
@@ -817,6 +819,24 @@ int lo_toeplitz_kron_mv_f32(const float* t, const int64_t* m, int ndim, int64_t 
 size_t lo_toeplitz_kron_bilinear_workspace_bytes(const int64_t* m, int ndim, int64_t B, int64_t S);
 int lo_toeplitz_kron_bilinear_f32(const float* t, const int64_t* m, int ndim, int64_t B, const float* u, const float* v,
                                   int64_t S, float* g, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- eigenbasis apply of a sum of two Kronecker products (ABI 25; csrc/lo_kron_eigsolve.hip) ----------------------------
+ * y = scale o ((M1 (x) S2^T) z): with Z_col the [n1, n2] view of a column of z (row index i1 n2 + i2, as everywhere),
+ *   Y_col = scale o (M1 (Z_col S2)).    M1 [B, n1, n1], S2 [B, n2, n2], scale [B, n1 n2] or NULL, z, y [B, n1 n2, c].
+ * The closed-form solve of A (x) B + C (x) D (sum_kronecker_linear_operator.py:42-66) is two calls,
+ *   (P_1^T, P_2, w) and (P_1, P_2^T, NULL),   w = 1 / (lambda_1 (x) lambda_2 + 1),
+ * with P_i, lambda_i from the per-factor generalised eigenproblems (set-up is the caller's).
+ *   n2 <= LO_KRON_EIG_MAX_SMALL   ONE fused launch for any n1 >= 1 and c <= LO_KRON_EIG_MAX_COLS: Z S2 is formed while the
+ *                                 slab of Z is staged to LDS, M1 is streamed once per 8 of the n2 c columns, scale rides in
+ *                                 the epilogue; more columns: LO_ERR_UNSUPPORTED (the caller composes)
+ *   n2 >  LO_KRON_EIG_MAX_SMALL   S2 transposed into ws, the Kronecker matvec engines of lo_matvec_f32, one scale kernel:
+ *                                 every shape the Kronecker matvec takes
+ * (LO_KRON_EIG_NO_FUSED in the environment sends every shape to the second route: measurement aid.)
+ * Fixed-order sums, no float atomics.  y must not alias z.  LO_ERR_BADARG: null pointers, non-positive sizes.
+ * ws: the _workspace_bytes query (0: a shape that is not taken).                                                       */
+size_t lo_kron_eig_apply_workspace_bytes(int64_t B, int64_t n1, int64_t n2, int64_t c);
+int lo_kron_eig_apply_f32(const float* M1, const float* S2, const float* scale, const float* z, float* y, int64_t B,
+                          int64_t n1, int64_t n2, int64_t c, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- Hadamard product of two roots (ABI 17; csrc/lo_hadamard.hip) -------------------------------------------------
  * K = (F F^T) o (G G^T), F [B, N, p], G [B, N, q], p, q <= LO_HADAMARD_MAX_RANK; U, V [B, N, S], S columns innermost.

@@ -1868,6 +1868,63 @@ def bilinear_kron(K1: torch.Tensor, K2: torch.Tensor, left_vecs: torch.Tensor, r
     return d1.reshape(*bs, n1, n1), d2.reshape(*bs, n2, n2)
 
 
+# Which shapes `kron_eig_apply` hands to the fused kernel of lo_kron_eig_apply_f32, by (n2 class, one column / more
+# columns): True only where tools/mb_sum_kron.py measured the fused launch at least as fast as the composition (the
+# Kronecker matvec kernels on (M1, S2^T) and one scale pass).  A cell that is absent keeps the
+# composition.  The n2 classes are the measured task-factor sizes; a size between two of them takes the next one above.
+# Measured (fused / composition, microseconds; 1 column, 17 columns):
+#   n2  4   1 x (4096 (x) 4)      35 /  595      533 /  696
+#   n2  8   64 x (512 (x) 8)      78 /  116     1442 /  215   (17 columns stay with the composition)
+#   n2 16   16 x (1024 (x) 16)   237 /  189     5025 /  338   (both stay with the composition)
+_KRON_EIG_SIZES = (4, 8, 16)
+_NATIVE_KRON_EIG: dict = {(4, 1): True, (4, 2): True, (8, 1): True}
+
+
+def kron_eig_routed(n2: int, c: int) -> bool:
+    """Whether the routing table sends (n2, c) to the fused kernel."""
+    if n2 > _hip.LO_KRON_EIG_MAX_SMALL or c > _hip.LO_KRON_EIG_MAX_COLS:
+        return False
+    cell = next(s for s in _KRON_EIG_SIZES if n2 <= s)
+    return bool(_NATIVE_KRON_EIG.get((cell, 1 if c == 1 else 2), False))
+
+
+def kron_eig_apply(M1: torch.Tensor, S2: torch.Tensor, scale: Optional[torch.Tensor], z: torch.Tensor,
+                   fused: Optional[bool] = None) -> Optional[torch.Tensor]:
+    """y = scale o ((M1 (x) S2^T) z), lo_kron_eig_apply_f32: M1 [*batch, n1, n1], S2 [*batch, n2, n2], scale
+    [*batch, n1 n2] or None, z [*batch, n1 n2, c] of batch shapes that broadcast.  Per column, with Z its [n1, n2] view,
+    Y = scale o (M1 (Z S2)).  n2 <= LO_KRON_EIG_MAX_SMALL: `fused` True is the one-launch kernel, False the composition
+    of the Kronecker matvec kernels with one scale pass, None what `kron_eig_routed` measured to be the faster of the
+    two; larger n2 compose inside the entry point.  None when the library does not take the shape (LO_ERR_UNSUPPORTED)."""
+    lib = _hip.load()
+    if M1.dim() < 2 or S2.dim() < 2 or z.dim() < 2 or M1.shape[-1] != M1.shape[-2] or S2.shape[-1] != S2.shape[-2]:
+        raise ValueError(f"kron_eig_apply: square factors and a matrix of columns expected, got {tuple(M1.shape)}, "
+                         f"{tuple(S2.shape)}, {tuple(z.shape)}")
+    n1, n2, (N, c) = M1.shape[-1], S2.shape[-1], z.shape[-2:]
+    if n1 * n2 != N or (scale is not None and scale.shape[-1] != N):
+        raise RuntimeError(f"kron_eig_apply: factors of {n1} and {n2} rows, scale "
+                           f"{None if scale is None else tuple(scale.shape)} against {N} rows of z")
+    _hip.require_hip(M1, S2, scale, z)
+    bs = torch.broadcast_shapes(M1.shape[:-2], S2.shape[:-2], z.shape[:-2], *([] if scale is None else [scale.shape[:-1]]))
+    if n2 <= _hip.LO_KRON_EIG_MAX_SMALL and not (kron_eig_routed(n2, c) if fused is None else fused):
+        # the composition on the Kronecker matvec kernels (what the entry point runs for larger n2)
+        desc = kron_diag_descriptor(M1.expand(*bs, n1, n1), S2.mT.expand(*bs, n2, n2), None)
+        y = matvec(desc, z.expand(*bs, N, c))
+        return y if scale is None else y.mul_(scale.unsqueeze(-1))
+    A1, A2, z3 = _flat(M1.expand(*bs, n1, n1), 2), _flat(S2.expand(*bs, n2, n2), 2), _flat(z.expand(*bs, N, c), 2)
+    sc = None if scale is None else _flat(scale.expand(*bs, N), 1)
+    B = z3.shape[0]
+    y = torch.empty_like(z3)
+    if y.numel() == 0:
+        return y.reshape(*bs, N, c)
+    ws = _hip.workspace(lib.lo_kron_eig_apply_workspace_bytes(B, n1, n2, c), z.device)
+    rc = lib.lo_kron_eig_apply_f32(_hip.ptr(A1), _hip.ptr(A2), _hip.ptr(sc), _hip.ptr(z3), _hip.ptr(y), B, n1, n2, c,
+                                   _hip.ptr(ws), ws.numel(), _hip.stream_ptr(z.device))
+    if rc == _hip.LO_ERR_UNSUPPORTED:
+        return None
+    _hip.check(rc, "lo_kron_eig_apply_f32")
+    return y.reshape(*bs, N, c)
+
+
 def set_onchip_cg(enable: bool):
     """Allow (default) or forbid the operator-resident CG fast path (csrc/lo_cg_onchip.hip); test / A-B switch.
     Enabling also ends a cool-down of the resident kernels (`resident_status`)."""

@@ -14,6 +14,7 @@ from .matmul_linear_operator import MatmulLinearOperator
 from .mul_linear_operator import MulLinearOperator
 from .root_linear_operator import LowRankRootLinearOperator, RootLinearOperator
 from .sum_linear_operator import PsdSumLinearOperator, SumLinearOperator
+from .sum_kronecker_linear_operator import SumKroneckerLinearOperator
 from .toeplitz_linear_operator import ToeplitzLinearOperator
 from .triangular_linear_operator import TriangularLinearOperator
 from .chol_linear_operator import CholLinearOperator
@@ -31,5 +32,5 @@ __all__ = [
     "PsdSumLinearOperator", "TriangularLinearOperator", "MatmulLinearOperator", "InterpolatedLinearOperator",
     "ToeplitzLinearOperator", "ConstantMulLinearOperator", "MulLinearOperator", "CholLinearOperator",
     "BlockLinearOperator", "BlockDiagLinearOperator", "BlockInterleavedLinearOperator", "SumBatchLinearOperator",
-    "MaskedLinearOperator",
+    "MaskedLinearOperator", "SumKroneckerLinearOperator",
 ]

@@ -234,6 +234,12 @@ class KroneckerProductLinearOperator(LinearOperator):
             return KroneckerProductAddedDiagLinearOperator(self, other)
         if isinstance(other, DiagLinearOperator):
             return self.add_diagonal(other._diagonal())
+        if (isinstance(other, KroneckerProductLinearOperator) and len(other.linear_ops) == len(self.linear_ops)
+                and all(a.shape[-2:] == b.shape[-2:] and a.shape[-1] == a.shape[-2]
+                        for a, b in zip(self.linear_ops, other.linear_ops))):
+            from .sum_kronecker_linear_operator import SumKroneckerLinearOperator
+
+            return SumKroneckerLinearOperator(self, other)  # reference :107-111: the eigenbasis closed forms
         return super().__add__(other)
 
     def add_diagonal(self, diag: Tensor):  # reference :116-145
