@@ -383,6 +383,17 @@ __global__ __launch_bounds__(kThreads) void k_root_apply_add(const float* __rest
   }
 }
 
+// ---- workspaces: one layout each, run by the entry point on its workspace and by the sizer on a measuring arena -------
+constexpr size_t kBilTail = 256;  // what the sizers report beyond the layout
+// t = C^T [U V] partials [B, S, 2 D, R]
+static float* bil_root_layout(Arena& ar, int64_t B, int64_t R, int64_t D, Split sp) {
+  return ar.take<float>((size_t)B * sp.S * 2 * D * R);
+}
+// the intermediate [B, n1, n2, D] of kron_bilinear
+static float* bil_kron_layout(Arena& ar, int64_t B, int64_t n1, int64_t n2, int64_t D) {
+  return ar.take<float>((size_t)B * n1 * n2 * D);
+}
+
 }  // namespace lo
 
 using namespace lo;
@@ -409,9 +420,10 @@ int lo_bilinear_diag_f32(const float* U, const float* V, int64_t B, int64_t N, i
   hipStream_t st = (hipStream_t)stream;
   const int64_t rows = B * N;
   float* rowdot = out;
-  if (constant) {
-    if (!ws || ws_bytes < sizeof(float) * (size_t)rows) return LO_ERR_WORKSPACE;
-    rowdot = (float*)ws;
+  if (constant) {  // (no sizer: the caller gives a float per row)
+    Arena ar(ws, ws_bytes);
+    rowdot = ar.take<float>((size_t)rows);
+    if (!ws || !ar.ok) return LO_ERR_WORKSPACE;
   }
   if (D > kBdiagLds) return LO_ERR_UNSUPPORTED;
   const int rb = (int)std::min<int64_t>(kThreads, kBdiagLds / D);
@@ -425,8 +437,7 @@ int lo_bilinear_diag_f32(const float* U, const float* V, int64_t B, int64_t N, i
 }
 
 size_t lo_bilinear_root_workspace_bytes(int64_t B, int64_t N, int64_t R, int64_t D) {
-  Split sp = choose_split(B, N, 256);
-  return sizeof(float) * (size_t)B * sp.S * 2 * D * R + 256;
+  return measured(kBilTail, [&](Arena& ar) { bil_root_layout(ar, B, R, D, choose_split(B, N, 256)); });
 }
 
 int lo_bilinear_root_f32(const float* C, const float* U, const float* V, int64_t B, int64_t N, int64_t R, int64_t D,
@@ -437,8 +448,9 @@ int lo_bilinear_root_f32(const float* C, const float* U, const float* V, int64_t
   if (lds_a > 64 * 1024 || lds_b > 64 * 1024) return LO_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   Split sp = choose_split(B, N, 256);
-  if (ws_bytes < sizeof(float) * (size_t)B * sp.S * 2 * D * R) return LO_ERR_WORKSPACE;
-  float* tpart = (float*)ws;
+  Arena ar(ws, ws_bytes, kBilTail);
+  float* tpart = bil_root_layout(ar, B, R, D, sp);
+  if (!ar.ok) return LO_ERR_WORKSPACE;
   LO_PROF_BEGIN("bil_root_t", st);
   if (R <= 32 && D <= 32)
     hipLaunchKernelGGL(k_bil_root_t_mfma<1>, dim3(sp.S, (unsigned)B), dim3(kThreads), 0, st, C, U, V, (int)N, (int)R,
@@ -491,14 +503,16 @@ int lo_root_apply_add_f32(const float* U, const float* T, int64_t B, int64_t N, 
 }
 
 size_t lo_bilinear_kron_workspace_bytes(int64_t B, int64_t n1, int64_t n2, int64_t D) {
-  return sizeof(float) * (size_t)B * n1 * n2 * D + 256;
+  return measured(kBilTail, [&](Arena& ar) { bil_kron_layout(ar, B, n1, n2, D); });
 }
 
 int lo_bilinear_kron_f32(const float* K1, const float* K2, const float* U, const float* V, int64_t B, int64_t n1,
                          int64_t n2, int64_t D, float* dK1, float* dK2, void* ws, size_t ws_bytes, void* stream) {
   if (!K1 || !K2 || !U || !V || !dK1 || !dK2 || !ws || B < 1 || n1 < 1 || n2 < 1 || D < 1) return LO_ERR_BADARG;
-  if (ws_bytes < sizeof(float) * (size_t)B * n1 * n2 * D) return LO_ERR_WORKSPACE;
-  return kron_bilinear(K1, K2, U, V, (float*)ws, dK1, dK2, B, (int)n1, (int)n2, D, (hipStream_t)stream);
+  Arena ar(ws, ws_bytes, kBilTail);
+  float* tmp = bil_kron_layout(ar, B, n1, n2, D);
+  if (!ar.ok) return LO_ERR_WORKSPACE;
+  return kron_bilinear(K1, K2, U, V, tmp, dK1, dK2, B, (int)n1, (int)n2, D, (hipStream_t)stream);
 }
 
 }  // extern "C"

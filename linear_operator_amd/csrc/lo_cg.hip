@@ -679,15 +679,15 @@ static int oc_record_iters(const lo_cg_params* prm) {
   return std::max(1, oc_iters + 1);
 }
 
-static size_t cg_layout(const lo_op_desc* op, const lo_precond_desc* pre, bool pre_cb, const lo_cg_params* prm,
-                        void* ws, size_t ws_bytes, CgDev* d, MatvecPlan* pl, lo_matvec_cb mv_cb, void* mv_user,
-                        const float** Qpad, float** upart, hipStream_t st, int* rc_out) {
+constexpr size_t kCgTail = 1024;  // what lo_cg_workspace_bytes reports beyond the layout
+// (on a measuring arena: the sizing pass -- the same takes, nothing staged)
+static int cg_layout(Arena& ar, const lo_op_desc* op, const lo_precond_desc* pre, bool pre_cb, const lo_cg_params* prm,
+                     CgDev* d, MatvecPlan* pl, lo_matvec_cb mv_cb, void* mv_user, PrecondPlan* pp, hipStream_t st) {
   const int64_t B = op->B, N = op->N, c = prm->c;
   Split sp = choose_split(B, N, 256);
-  Arena ar(ws, ws_bytes);  // (ws == nullptr: the sizing pass -- the same takes, nothing staged)
   const size_t nv = (size_t)B * N * c;
   const bool precond = pre != nullptr || pre_cb;
-  CgDev dd;
+  CgDev& dd = *d;
   dd.B = B; dd.N = N; dd.c = (int)c; dd.S = sp.S;
   dd.ctrl = ar.take<CgCtrl>(1);
   // (granule buffer of the serial resident kernels right behind the control block: ONE memset clears both)
@@ -700,14 +700,8 @@ static size_t cg_layout(const lo_op_desc* op, const lo_precond_desc* pre, bool p
   dd.p = ar.take<float>(nv);
   dd.Ap = ar.take<float>(nv);
   dd.z = precond ? ar.take<float>(nv) : nullptr;
-  int S_dot = sp.S;
-  if (op->kind == LO_OP_DENSE_DIAG) {
-    S_dot = dense_S_dot(B, N, c);
-  } else if (op->kind == LO_OP_KRON_DIAG) {
-    S_dot = kron_S_dot((int)op->R, (int)op->n2, c, sp.S);
-  }
-  dd.S_dot = S_dot;
-  dd.pAp_part = ar.take<float>((size_t)B * std::max(S_dot, sp.S) * c);
+  dd.S_dot = matvec_S_dot(op, c, sp);
+  dd.pAp_part = ar.take<float>((size_t)B * std::max(dd.S_dot, sp.S) * c);
   dd.rr_part = ar.take<float>((size_t)B * sp.S * c);
   dd.rz_part = precond ? ar.take<float>((size_t)B * sp.S * c) : dd.rr_part;
   dd.S_rz = sp.S;
@@ -752,32 +746,12 @@ static size_t cg_layout(const lo_op_desc* op, const lo_precond_desc* pre, bool p
     dd.oc_zero_q = ar.take<float>((size_t)B * N * 4);
     dd.oc_ones = ar.take<float>((size_t)B);
   }
-  // preconditioner staging
-  if (pre) {
-    const int R4 = padded_rank(pre->k);
-    float* up = ar.take<float>((size_t)B * sp.S * R4 * c);
-    if (upart) *upart = up;
-    if (pre->Q && pre->ldq != R4) {
-      float* qp = ar.take<float>((size_t)B * N * R4);
-      if (!ar.measuring() && ar.ok) {
-        if (pre->ldq != pre->k) { if (rc_out) *rc_out = LO_ERR_BADARG; }
-        else {
-          int rc = pad_rows(pre->Q, pre->k, qp, R4, B * N, st);
-          if (rc && rc_out) *rc_out = rc;
-        }
-      }
-      if (Qpad) *Qpad = qp;
-    } else if (Qpad) {
-      *Qpad = pre->Q;
-    }
-  }
-  // matvec plan (laid out by the same call in both passes; the sizing pass keeps none)
-  MatvecPlan scratch;
-  const int rc = matvec_plan_init(pl ? pl : &scratch, op, mv_cb, mv_user, c, sp, &ar, st);
-  if (rc && rc_out) *rc_out = rc;
-  if (d) *d = dd;
-  if (!ar.ok && rc_out && *rc_out == LO_OK) *rc_out = LO_ERR_WORKSPACE;
-  return ar.off + 1024;
+  // preconditioner and matvec plans (laid out by the same calls in both passes; a measuring pass keeps no sub-plans)
+  int rc = pre ? precond_plan_init(pp, pre, B, N, c, sp, &ar, st) : LO_OK;
+  const int rc_mv = matvec_plan_init(pl, op, mv_cb, mv_user, c, sp, &ar, st);
+  if (!rc) rc = rc_mv;
+  if (!rc && pl->S_dot != dd.S_dot) rc = LO_ERR_LAUNCH;  // (pAp_part was sized for another count: never)
+  return (rc || ar.ok) ? rc : LO_ERR_WORKSPACE;
 }
 
 // Phase timers of the resident and fused-column kernels, printed to stderr after the launches that wrote them
@@ -836,10 +810,9 @@ struct CgSolve {
   int c;
   CgDev d;
   MatvecPlan pl;
-  const float* Qp = nullptr;  // Q padded to preR4 floats per row
-  float* upart = nullptr;
+  PrecondPlan pp = {};  // the Q form staged (pre); R4 == 0 without one
   Split sp;
-  int preR4, fmi, oc_nwg;
+  int fmi, oc_nwg;
   bool precond, global_rule, oc_nopre;
   CgSwitches sw;
   CgDebug dbg;
@@ -879,7 +852,6 @@ static void cg_setup_scalars(CgSolve& s, float* t_mat) {
   d.tol = s.global_rule ? -1.0f : prm->tolerance;
   d.eps = prm->eps; d.stop_after = prm->stop_updating_after; d.check_nan_first = (s.x0 == nullptr); d.t_mat = t_mat;
   s.precond = (pre != nullptr) || (s.precond_cb != nullptr);
-  s.preR4 = pre ? padded_rank(pre->k) : 0;
   s.oc_nopre = !pre && !s.precond_cb && d.oc_zero_q != nullptr;
   s.block = dim3(kThreads);
 }
@@ -900,9 +872,8 @@ static int cg_setup(CgSolve& s, lo_matvec_cb matvec, void* matvec_user, float* t
   const CgEnv env = cg_env();
   s.sw = env.sw;
   s.dbg = CgDebug::read(env, s.B);
-  int rc = LO_OK;
-  cg_layout(op, pre, s.precond_cb != nullptr, prm, ws, ws_bytes, &s.d, &s.pl, matvec, matvec_user, &s.Qp, &s.upart, s.st,
-            &rc);
+  Arena ar(ws, ws_bytes, kCgTail);
+  int rc = cg_layout(ar, op, pre, s.precond_cb != nullptr, prm, &s.d, &s.pl, matvec, matvec_user, &s.pp, s.st);
   if (rc) return rc;
   CgDev& d = s.d;
   s.sp = s.pl.sp;
@@ -1021,7 +992,7 @@ static int resident_close(CgSolve& s, const OnchipArgs& a, bool lean, bool dense
 // One attempt of the resident phase: lean = result-only pass, dense = the dense form of the R-space iteration.
 static int resident_attempt(CgSolve& s, int attempt, bool lean, bool dense, OcNext* next) {
   CgDev& d = s.d; const lo_precond_desc* pre = s.pre; const lo_cg_params* prm = s.prm; lo_cg_plan& ex = s.exec;
-  const int64_t B = s.B, N = s.N; const int c = s.c, RC = s.pl.lr.R4, ocR4 = s.oc_nopre ? 4 : s.preR4;
+  const int64_t B = s.B, N = s.N; const int c = s.c, RC = s.pl.lr.R4, ocR4 = s.oc_nopre ? 4 : s.pp.R4;
   hipStream_t st = s.st;
   *next = OcNext::kStream;
   OnchipArgs a;
@@ -1033,10 +1004,10 @@ static int resident_attempt(CgSolve& s, int attempt, bool lean, bool dense, OcNe
     }
     a.Q = d.oc_zero_q; a.dinv = d.oc_ones; a.dinv_mode = LO_DIAG_CONST;
   } else {
-    a.Q = s.Qp; a.dinv = pre->dinv; a.dinv_mode = pre->constant_diag ? LO_DIAG_CONST : LO_DIAG_FULL;
+    a.Q = s.pp.Qp; a.dinv = pre->dinv; a.dinv_mode = pre->constant_diag ? LO_DIAG_CONST : LO_DIAG_FULL;
   }
   a.rhs = s.rhs; a.B = B; a.N = (int)N; a.c = c; a.ab_rec = prm->n_tridiag ? d.oc_ab : nullptr;
-  a.col0 = 0; a.ncols = c; a.RK = pre ? s.preR4 : 0; a.RCg = RC;
+  a.col0 = 0; a.ncols = c; a.RK = s.pp.R4; a.RCg = RC;
   a.F = nullptr; a.EF = nullptr; a.E = nullptr; a.RS = nullptr; a.RSD = nullptr;
   a.close_gran = nullptr; a.close_count = nullptr; a.close_ctrl = nullptr; a.close_mirror = nullptr;
   a.close_ticket = 0; a.close_tol = 0.f; a.close_floor_ok = 0;
@@ -1220,12 +1191,7 @@ static int cg_resident(CgSolve& s) {
 // ---- streaming phase ---------------------------------------------------------------------------------
 static int cg_apply_precond(CgSolve& s, const float* r, float* z, float* dotp) {
   const int* stop = &s.d.ctrl->stop;
-  if (s.pre) {
-    int e = skinny_tn(s.Qp, s.preR4, s.preR4, r, s.c, s.upart, s.B, s.N, s.sp, stop, s.st);
-    if (e) return e;
-    return skinny_nn(s.Qp, s.preR4, s.preR4, s.upart, s.pre->dinv, s.pre->constant_diag ? LO_DIAG_CONST : LO_DIAG_FULL,
-                     -1.0f, r, s.c, z, dotp, s.B, s.N, s.sp, stop, s.st);
-  }
+  if (s.pre) return precond_plan_run(&s.pp, r, z, dotp, stop, s.st);
   int e = s.precond_cb(s.precond_user, r, z, s.B, s.N, s.c, (void*)s.st);
   if (e) return LO_ERR_LAUNCH;
   return vec_dot_part(r, z, s.c, dotp, s.B, s.N, s.sp, stop, s.st);
@@ -1310,7 +1276,7 @@ static int cg_issue(CgSolve& s, CgIter& it, int k) {
     cf.ctrl = d.ctrl;
     cf.gran = d.pf_gran;
     // single pass over Q: r / x update, Q^T r, group all-reduce, z = r/d - Q u, p = z + beta p (lo_precond_fused.hip)
-    rc = precond_fused_rupdate(s.Qp, pre->dinv, pre->constant_diag ? LO_DIAG_CONST : LO_DIAG_FULL, d.r, d.Ap, d.p, d.x,
+    rc = precond_fused_rupdate(s.pp.Qp, pre->dinv, pre->constant_diag ? LO_DIAG_CONST : LO_DIAG_FULL, d.r, d.Ap, d.p, d.x,
                                d.z, d.pAp_part, d.S_dot, d.rz, d.has_conv, d.eps, d.alpha, d.rr_part, d.rz_part, s.sp.S,
                                B, N, d.pf_gbuf, d.oc_err, d.pf_ctr, k, nullptr, (int)prm->max_iter, stop, s.oc_nwg, &cf,
                                it.pf_kron ? &it.kron : nullptr, st);
@@ -1334,7 +1300,7 @@ static int cg_issue(CgSolve& s, CgIter& it, int k) {
     cf.done = d.sc_ctr + (std::max(1, (int)prm->max_iter) + 1);
     cf.gran = d.sc_gran;
     cf.ctrl = d.ctrl;
-    rc = cg_step_cols(pre ? s.Qp : nullptr, s.preR4, pre ? pre->dinv : nullptr,
+    rc = cg_step_cols(s.pp.Qp, s.pp.R4, pre ? pre->dinv : nullptr,
                       (pre && pre->constant_diag) ? LO_DIAG_CONST : LO_DIAG_FULL, d.r, d.Ap, d.p, d.x, s.c, d.pAp_part,
                       d.S_dot, d.rz, d.has_conv, d.eps, d.alpha, d.rr_part, d.rz_part, s.sp.S, B, N, d.sc_gbuf, d.oc_err,
                       d.sc_ctr, k, (int)prm->max_iter, stop, s.oc_nwg, &cf, s.dbg.sc ? d.oc_dbg : nullptr, st);
@@ -1354,11 +1320,12 @@ static int cg_issue(CgSolve& s, CgIter& it, int k) {
   if (pre_done) {
   } else if (pre) {
     // r-update, x-update and the residual norm ride on the first pass over Q
-    rc = skinny_tn_rupdate(s.Qp, s.preR4, s.preR4, d.r, d.Ap, d.p, d.x, d.pAp_part, d.S_dot, d.rz, d.has_conv, d.eps,
-                           d.alpha, d.rr_part, s.c, s.upart, B, N, s.sp, stop, st);
+    const PrecondPlan& pp = s.pp;
+    rc = skinny_tn_rupdate(pp.Qp, pp.R4, pp.R4, d.r, d.Ap, d.p, d.x, d.pAp_part, d.S_dot, d.rz, d.has_conv, d.eps,
+                           d.alpha, d.rr_part, s.c, pp.upart, B, N, s.sp, stop, st);
     if (rc) return rc;
-    rc = skinny_nn(s.Qp, s.preR4, s.preR4, s.upart, pre->dinv, pre->constant_diag ? LO_DIAG_CONST : LO_DIAG_FULL, -1.0f,
-                   d.r, s.c, d.z, d.rz_part, B, N, s.sp, stop, st);
+    rc = skinny_nn(pp.Qp, pp.R4, pp.R4, pp.upart, pp.dinv, pp.dinv_mode, -1.0f, d.r, s.c, d.z, d.rz_part, B, N, s.sp,
+                   stop, st);
     if (rc) return rc;
   } else {
     LO_PROF_BEGIN("cg_update_xr", st);
@@ -1538,8 +1505,11 @@ int lo_cg_session_create_f32(const lo_op_desc* op, const lo_precond_desc* pre, c
   if (pre->k < 1 || pre->k > kMaxRank || !pre->dinv || (!pre->Q && !pre_root)) return LO_ERR_BADARG;
   if (op->kind != LO_OP_LOWRANK_DIAG || op->B < 1 || op->N < 1 || op->R < 1 || !op->A0) return LO_ERR_UNSUPPORTED;
   if (op->diag_mode != LO_DIAG_NONE && !op->d) return LO_ERR_BADARG;
-  // (operands the general path pads into its workspace on every call stay with it)
-  if (padded_rank(op->R) != op->R || (pre->Q && pre->ldq != padded_rank(pre->k))) return LO_ERR_UNSUPPORTED;
+  // (operands the general path pads into its workspace on every call stay with it; the measuring pass of the plan
+  //  gives R4 and stages nothing: the session uses Q where it is)
+  PrecondPlan pp;
+  measured(0, [&](Arena& ar) { precond_plan_init(&pp, pre, op->B, op->N, 1, Split{}, &ar, nullptr); });
+  if (padded_rank(op->R) != op->R || (pre->Q && pre->ldq != pp.R4)) return LO_ERR_UNSUPPORTED;
   const CgEnv env = cg_env();
   if (env.ls_debug || env.oc_debug || env.sc_debug || env.sw.clear_handoff || env.sw.oc_test_fallback ||
       env.sw.rs_no_diag || !pre->RSD || pinned_status_block() == nullptr)
@@ -1561,7 +1531,7 @@ int lo_cg_session_create_f32(const lo_op_desc* op, const lo_precond_desc* pre, c
   // (the part of cg_setup this plan needs; the operands are used where they are)
   s.pl = MatvecPlan();
   s.pl.op = *op; s.pl.c = 1; s.pl.lr.Apad = op->A0; s.pl.lr.lda = s.pl.lr.R4 = padded_rank(op->R);
-  s.Qp = pre->Q;
+  s.pp = pp;
   s.sw = env.sw;
   s.dbg = CgDebug::read(env, s.B);
   cg_setup_scalars(s, nullptr);
@@ -1624,19 +1594,17 @@ int lo_cg_session_debug_live(void) { return g_sessions_live.load(std::memory_ord
 
 size_t lo_cg_workspace_bytes(const lo_op_desc* op, const lo_precond_desc* pre, const lo_cg_params* prm) {
   if (!op || !prm) return 0;
+  auto need = [&](const lo_precond_desc* p, bool pre_cb) {
+    CgDev d;
+    MatvecPlan pl;
+    PrecondPlan pp;
+    return measured(kCgTail, [&](Arena& ar) { cg_layout(ar, op, p, pre_cb, prm, &d, &pl, nullptr, nullptr, &pp, nullptr); });
+  };
   // worst case: assume an opaque preconditioner closure may be used as well (needs z)
-  lo_precond_desc dummy;
-  const lo_precond_desc* p = pre;
-  if (!p) {
-    dummy.k = 4; dummy.ldq = 4; dummy.constant_diag = 0; dummy.reserved = 0; dummy.Q = nullptr; dummy.dinv = nullptr;
-    p = &dummy;
-  }
-  size_t need = cg_layout(op, p, true, prm, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                          nullptr);
-  if (!pre)  // the unpreconditioned resident path stages an all-zero Q instead of z
-    need = std::max(need, cg_layout(op, nullptr, false, prm, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                    nullptr, nullptr, nullptr));
-  return need;
+  const lo_precond_desc worst = worst_case_precond();
+  const size_t with_closure = need(pre ? pre : &worst, true);
+  // (the unpreconditioned resident path stages an all-zero Q instead of z)
+  return pre ? with_closure : std::max(with_closure, need(nullptr, false));
 }
 
 int lo_cg_solve_f32(const lo_op_desc* op, lo_matvec_cb matvec, void* matvec_user, const lo_precond_desc* pre,
@@ -1724,36 +1692,26 @@ int lo_resident_inject_timeouts(int32_t n) {
   return LO_OK;
 }
 
+constexpr size_t kPrecondApplyTail = 1024;
 // z = P^{-1} r as a standalone call (precondition_closure, added_diag_linear_operator.py:135-140)
 size_t lo_precond_apply_workspace_bytes(int64_t B, int64_t N, int32_t k, int64_t c) {
-  Split sp = choose_split(B, N, 256);
-  const int R4 = padded_rank(k);
-  return align_up((size_t)B * sp.S * R4 * c * sizeof(float), 256) + align_up((size_t)B * N * R4 * sizeof(float), 256) +
-         1024;
+  // all the sizer knows: Q [B,N,k] with k floats per row (any address: a measuring pass only asks whether there is a Q)
+  const float q_form = 0.f;
+  const lo_precond_desc pre = {k, /*ldq*/ k, 0, 0, &q_form};
+  PrecondPlan pp;
+  return measured(kPrecondApplyTail,
+                  [&](Arena& ar) { precond_plan_init(&pp, &pre, B, N, c, choose_split(B, N, 256), &ar, nullptr); });
 }
 
 int lo_precond_apply_f32(const lo_precond_desc* pre, const float* r, float* z, int64_t B, int64_t N, int64_t c, void* ws,
                          size_t ws_bytes, void* stream) {
-  if (!pre || !r || !z || !ws) return LO_ERR_BADARG;
+  if (!pre || !r || !z || !ws || !pre->Q || !pre->dinv) return LO_ERR_BADARG;
   hipStream_t st = (hipStream_t)stream;
-  Split sp = choose_split(B, N, 256);
-  const int R4 = padded_rank(pre->k);
-  Arena ar(ws, ws_bytes);
-  float* upart = ar.take<float>((size_t)B * sp.S * R4 * c);
-  const float* Qp = pre->Q;
-  if (pre->ldq != R4) {
-    if (pre->ldq != pre->k) return LO_ERR_BADARG;
-    float* qp = ar.take<float>((size_t)B * N * R4);
-    if (!ar.ok) return LO_ERR_WORKSPACE;
-    int rc = pad_rows(pre->Q, pre->k, qp, R4, B * N, st);
-    if (rc) return rc;
-    Qp = qp;
-  }
-  if (!ar.ok) return LO_ERR_WORKSPACE;
-  int rc = skinny_tn(Qp, R4, R4, r, c, upart, B, N, sp, nullptr, st);
+  PrecondPlan pp;  // (a short workspace is refused before the padded copy is written: it is the plan's last take)
+  Arena ar(ws, ws_bytes, kPrecondApplyTail);
+  const int rc = precond_plan_init(&pp, pre, B, N, c, choose_split(B, N, 256), &ar, st);
   if (rc) return rc;
-  return skinny_nn(Qp, R4, R4, upart, pre->dinv, pre->constant_diag ? LO_DIAG_CONST : LO_DIAG_FULL, -1.0f, r, c, z,
-                   nullptr, B, N, sp, nullptr, st);
+  return precond_plan_run(&pp, r, z, nullptr, nullptr, st);
 }
 
 }  // extern "C"

@@ -339,6 +339,14 @@ int ts_dispatch(const float* T, const float* rhs, float* out, float* sumsq, int6
   return ts_launch<16>(T, rhs, out, sumsq, B, (int)N, (int)c, mode, upper, trans, st);
 }
 
+// the workspace of lo_cholesky_f32 (Np: N rounded up to whole panels)
+constexpr size_t kCholTail = 512;  // what the sizer reports beyond the layout
+struct CholBufs { float* W; double* dsum; };  // the factor's working copy [B, Np, Np], fp64 row sums [B, Np]
+CholBufs chol_layout(Arena& ar, int64_t B, int64_t Np) {
+  return {ar.take<float>((size_t)B * Np * Np), ar.take<double>((size_t)B * Np)};
+}
+int chol_padded(int64_t N) { return (int)((N + CH_NB - 1) / CH_NB * CH_NB); }
+
 }  // namespace
 }  // namespace lo
 
@@ -348,8 +356,7 @@ extern "C" {
 
 size_t lo_cholesky_workspace_bytes(int64_t B, int64_t N) {
   if (B < 1 || N < 1 || N > kCholMaxN) return 0;
-  const size_t Np = (size_t)(N + CH_NB - 1) / CH_NB * CH_NB;
-  return 512 + sizeof(float) * (size_t)B * Np * Np + sizeof(double) * (size_t)B * Np;
+  return measured(kCholTail, [&](Arena& ar) { chol_layout(ar, B, chol_padded(N)); });
 }
 
 int lo_cholesky_f32(const float* A, float* L, int32_t* info, double* logdet, int64_t B, int64_t N, void* ws,
@@ -357,10 +364,9 @@ int lo_cholesky_f32(const float* A, float* L, int32_t* info, double* logdet, int
   if (!A || !L || !info || B < 0 || N < 1) return LO_ERR_BADARG;
   if (N > kCholMaxN || B > 0x7fffffff) return LO_ERR_UNSUPPORTED;
   if (B == 0) return LO_OK;
-  const int Np = (int)((N + CH_NB - 1) / CH_NB * CH_NB);
-  Arena ar(ws, ws_bytes);
-  float* W = ar.take<float>((size_t)B * Np * Np);
-  double* dsum = ar.take<double>((size_t)B * Np);
+  const int Np = chol_padded(N);
+  Arena ar(ws, ws_bytes, kCholTail);
+  auto [W, dsum] = chol_layout(ar, B, Np);
   if (!ws || !ar.ok) return LO_ERR_WORKSPACE;
   const int ldb = Np - CH_NB + 4;
   const size_t lds = sizeof(float) * (size_t)CH_NB * ldb;  // + 4352 bytes static

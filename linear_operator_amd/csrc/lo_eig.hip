@@ -126,13 +126,20 @@ __global__ void k_slq_reduce(const double* __restrict__ term, int64_t P, int64_t
   logdet[b] = (float)acc;
 }
 
+// the workspace of lo_tridiag_eigh_slq_f32
+constexpr size_t kEigTail = 256;  // what the sizer reports beyond the layout
+struct EigBufs { int* fail; double* term; };  // one flag; the SLQ terms [P * B]
+static EigBufs eig_layout(Arena& ar, int64_t M) { return {ar.take<int>(1), ar.take<double>((size_t)M)}; }
+
 }  // namespace lo
 
 using namespace lo;
 
 extern "C" {
 
-size_t lo_tridiag_eigh_slq_workspace_bytes(int64_t P, int64_t B) { return (size_t)P * B * sizeof(double) + 512; }
+size_t lo_tridiag_eigh_slq_workspace_bytes(int64_t P, int64_t B) {
+  return measured(kEigTail, [&](Arena& ar) { eig_layout(ar, P * B); });
+}
 
 int lo_tridiag_eigh_slq_f32(const float* t_mat, int64_t P, int64_t B, int32_t T, int64_t n, float* evals, float* evecs,
                             float* logdet, void* ws, size_t ws_bytes, void* stream) {
@@ -140,9 +147,8 @@ int lo_tridiag_eigh_slq_f32(const float* t_mat, int64_t P, int64_t B, int32_t T,
   if (T > kEigMaxT) return LO_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   const int64_t M = P * B;
-  Arena ar(ws, ws_bytes);
-  int* fail = ar.take<int>(1);
-  double* term = ar.take<double>((size_t)M);
+  Arena ar(ws, ws_bytes, kEigTail);
+  auto [fail, term] = eig_layout(ar, M);
   if (!ar.ok) return LO_ERR_WORKSPACE;
   LO_HIP_CHECK(hipMemsetAsync(fail, 0, sizeof(int), st));
   const unsigned grid = (unsigned)((M + 63) / 64);

@@ -367,6 +367,13 @@ int hadamard_matvec_run(const MatvecPlan* pl, const float* v, float* y, const in
   return LO_OK;
 }
 
+// the workspace of lo_hadamard_bilinear_f32: the contraction partials, M_t of the 2 S columns and its transpose
+constexpr size_t kHdBilTail = 512;  // what the sizer reports beyond the layout
+struct HdBilBufs { float *part, *M, *Mt; };
+static HdBilBufs hd_bil_layout(Arena& ar, const HdShape& s) {  // (a braced list: the takes in this order)
+  return {ar.take<float>(s.part_floats), ar.take<float>(s.m_floats), ar.take<float>(s.m_floats)};
+}
+
 }  // namespace lo
 
 using namespace lo;
@@ -376,7 +383,7 @@ extern "C" {
 size_t lo_hadamard_bilinear_workspace_bytes(int64_t B, int64_t N, int64_t p, int64_t q, int64_t S) {
   HdShape s;
   if (!hd_shape(B, N, p, q, 2 * S, &s)) return 0;
-  return align_up(s.part_floats * sizeof(float), 256) + 2 * align_up(s.m_floats * sizeof(float), 256) + 512;
+  return measured(kHdBilTail, [&](Arena& ar) { hd_bil_layout(ar, s); });
 }
 
 int lo_hadamard_bilinear_f32(const float* F, const float* G, const float* U, const float* V, int64_t B, int64_t N,
@@ -386,10 +393,8 @@ int lo_hadamard_bilinear_f32(const float* F, const float* G, const float* U, con
   HdShape s;
   if (!hd_shape(B, N, p, q, 2 * S, &s)) return LO_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
-  Arena ar(ws, ws_bytes);
-  float* part = ar.take<float>(s.part_floats);
-  float* M = ar.take<float>(s.m_floats);
-  float* Mt = ar.take<float>(s.m_floats);
+  Arena ar(ws, ws_bytes, kHdBilTail);
+  auto [part, M, Mt] = hd_bil_layout(ar, s);
   if (!ws || !ar.ok) return LO_ERR_WORKSPACE;
   int rc = hd_contract(s, F, G, V, (int)S, U, part, M, Mt, nullptr, st);
   if (rc) return rc;

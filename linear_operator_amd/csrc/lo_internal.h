@@ -53,12 +53,14 @@ Split choose_split(int64_t B, int64_t N, int min_rows, int max_split = 256);
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 // Bump allocator over the caller's workspace.  Over no workspace (base == nullptr) it MEASURES: take() returns nullptr and
-// only `off` advances, so the function that lays a workspace out is also the one that sizes it.
+// only `off` advances, so the function that lays a workspace out is also the one that sizes it.  `tail`: bytes kept free
+// behind the takes, what the entry point's sizer adds to its layout -- a workspace smaller than the reported size is not ok.
 struct Arena {
   char* base;
   size_t cap, off;
   bool ok;
-  Arena(void* p, size_t bytes) : base((char*)p), cap(bytes), off(0), ok(true) {}
+  Arena(void* p, size_t bytes, size_t tail = 0)
+      : base((char*)p), cap(bytes >= tail ? bytes - tail : 0), off(0), ok(!p || bytes >= tail) {}
   bool measuring() const { return !base; }
   template <typename T>
   T* take(size_t n) {
@@ -70,6 +72,13 @@ struct Arena {
     return r;
   }
 };
+// the body of a sizer: what `layout` takes from a measuring arena, plus the entry point's tail
+template <typename F>
+size_t measured(size_t tail, F layout) {
+  Arena ar(nullptr, 0);
+  layout(ar);
+  return ar.off + tail;
+}
 
 // floats per row of a rank-R factor (C, Q) as the skinny kernels read it: 4 * (R / 4 rounded up to a power of two)
 inline int padded_rank(int64_t R) {
@@ -238,6 +247,9 @@ int masked_plan(MatvecPlan* pl, Arena* ar, hipStream_t st);
 int masked_matvec_run(const MatvecPlan* pl, const float* v, float* y, const int* stop, hipStream_t st);
 
 // ---- the plan and its dispatch (lo_matvec.hip) -----------------------------------------------------------------------
+// Partials per (member, column) the kind's matvec writes into dot_part.  The one source: the plan functions store it in
+// MatvecPlan::S_dot and the solvers size their partial buffers by it before the plan is laid out.
+int matvec_S_dot(const lo_op_desc* op, int64_t c, Split sp);
 struct MatvecPlan {
   lo_op_desc op;
   int64_t c;
@@ -294,6 +306,27 @@ int matvec_run_pupdate(const MatvecPlan* pl, float* p, const float* z, const flo
 inline bool plain_term_kind(int kind) {
   return kind == LO_OP_LOWRANK_DIAG || kind == LO_OP_DENSE_DIAG || kind == LO_OP_KRON_DIAG;
 }
+
+// ---- the Q-form Woodbury apply z = dinv o r - Q (Q^T r) as a plan (lo_skinny.hip): staged and run
+// through these two functions by the streaming CG and MINRES engines and by lo_precond_apply_f32 ----------------------
+struct PrecondPlan {
+  const float* Qp;  // Q with R4 floats per row: the caller's (ldq == R4) or the padded copy; nullptr: root form only
+  int R4;           // padded_rank(k)
+  float* upart;     // [B,S,R4,c] partials of Q^T r
+  const float* dinv;
+  int dinv_mode;
+  int64_t B, N, c;
+  Split sp;
+};
+// Takes upart, then (Q given, ldq != R4) the padded copy of Q, and pads; ldq must then be k, else LO_ERR_BADARG.  On a
+// measuring arena it makes the same takes and nothing else: the return code only says whether the descriptor is valid.
+int precond_plan_init(PrecondPlan* pp, const lo_precond_desc* pre, int64_t B, int64_t N, int64_t c, Split sp, Arena* ar,
+                      hipStream_t st);
+// z = dinv o r - Qp (Qp^T r); optional dot_part[B,S,c] = sum_rows r o z
+int precond_plan_run(const PrecondPlan* pp, const float* r, float* z, float* dot_part, const int* stop, hipStream_t st);
+// The descriptor the solver sizers lay out when they are given none: a closure preconditioner may be used with the
+// workspace, which needs z (CG) / the q vectors (MINRES) and no more staging than the smallest Q form.
+inline lo_precond_desc worst_case_precond() { return lo_precond_desc{/*k*/ 4, /*ldq*/ 4}; }
 
 // dense / kron kernels
 int dense_matvec(const float* K, const float* d, int dd_mode, const float* v, float* y, float* dot_part, int64_t B,

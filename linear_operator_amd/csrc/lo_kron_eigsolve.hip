@@ -201,10 +201,8 @@ size_t lo_kron_eig_apply_workspace_bytes(int64_t B, int64_t n1, int64_t n2, int6
   if (ke_fused_shape(n2, c)) return (B <= 65535 && n1 * n2 * c < ((int64_t)1 << 31)) ? kPlanTail : 0;
   if (n2 <= LO_KRON_EIG_MAX_SMALL && !getenv("LO_KRON_EIG_NO_FUSED")) return 0;  // (too many columns: the caller composes)
   if (!ke_general_shape(B, n1, n2, c)) return 0;
-  Arena ar(nullptr, 0);
   KeGeneral g;
-  ke_general_layout(ar, B, n1, n2, c, &g);
-  return ar.off + kPlanTail;
+  return measured(kPlanTail, [&](Arena& ar) { ke_general_layout(ar, B, n1, n2, c, &g); });
 }
 
 int lo_kron_eig_apply_f32(const float* M1, const float* S2, const float* scale, const float* z, float* y, int64_t B,

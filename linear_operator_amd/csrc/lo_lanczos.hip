@@ -839,8 +839,11 @@ int lo_root_from_lanczos_native_f32(const float* q_native, const float* evecs, c
   return LO_OK;
 }
 
+// dot partials per (member, column) the workspace holds: caps the row split; a matvec that writes more runs the plain step
+constexpr int kLzDotSlots = 64;
+
 static void lz_layout(const lo_op_desc* op, int64_t P, int max_iter, Arena& ar, LzDev* d, Split* spo) {
-  Split sp = choose_split(op->B, op->N, 256, 64);  // (the fused step keeps a member's dot partials in 64 slots)
+  Split sp = choose_split(op->B, op->N, 256, kLzDotSlots);
   *spo = sp;
   d->B = op->B; d->N = op->N; d->P = (int)P; d->S = sp.S; d->rows = sp.rows; d->max_iter = max_iter;
   d->ctrl = ar.take<LzCtrl>(1);
@@ -848,7 +851,7 @@ static void lz_layout(const lo_op_desc* op, int64_t P, int max_iter, Arena& ar, 
   d->part = ar.take<float>((size_t)op->B * sp.S * (max_iter + 1) * P);
   d->coef = ar.take<float>((size_t)op->B * (max_iter + 1) * P);
   d->scal = ar.take<float>((size_t)op->B * P * 2);  // [B, P] scalars of the step | [B, P] predicted norms
-  d->dot_part = ar.take<float>((size_t)op->B * 64 * P);  // matvec dot partials [B, S_dot <= 64, P]
+  d->dot_part = ar.take<float>((size_t)op->B * kLzDotSlots * P);  // matvec dot partials [B, S_dot, P]
 }
 
 size_t lo_lanczos_workspace_bytes(const lo_op_desc* op, int64_t P, int32_t max_iter) {
@@ -982,7 +985,7 @@ int lo_lanczos_tridiag_f32(const lo_op_desc* op, lo_matvec_cb matvec, void* matv
     LO_LAUNCH_CHECK();
     // fused path: float4 / float2 kernels, all basis vectors of a step in registers, matvec dot partials fit
     // (kLzFusedQ accumulators keep pass 1 under 128 VGPRs: four waves per SIMD)
-    const bool fused = vec4 && num_iter <= kLzFusedQ + 1 && pl.S_dot <= 64 && !getenv("LO_LZ_UNFUSED");
+    const bool fused = vec4 && num_iter <= kLzFusedQ + 1 && pl.S_dot <= kLzDotSlots && !getenv("LO_LZ_UNFUSED");
     for (k = 1; fused && k < num_iter; ++k) {
       rc = matvec_run(&pl, q(k), d.r, d.dot_part, nullptr, st);  // r = A q_k (:108) + partials of q_k . r
       if (rc) return rc;

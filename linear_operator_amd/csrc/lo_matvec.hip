@@ -48,7 +48,6 @@ static int lowrank_run(const MatvecPlan* pl, const float* v, float* y, float* do
 static int dense_plan(MatvecPlan* pl, Arena* ar, hipStream_t) {
   const lo_op_desc& op = pl->op;
   if (!op.A0) return LO_ERR_BADARG;
-  pl->S_dot = dense_S_dot(op.B, op.N, pl->c);
   const int ks = dense_mfma_slices(op.B, op.N, pl->c);
   if (ks > 1) pl->dense.part = ar->take<float>((size_t)ks * op.B * op.N * pl->c);
   return LO_OK;
@@ -66,7 +65,6 @@ static int kron_plan(MatvecPlan* pl, Arena* ar, hipStream_t) {
   if (!op.A0 || !op.A1 || op.R * op.n2 != op.N) return LO_ERR_BADARG;
   const bool cols = kron_mfma_cols_ok((int)op.R, (int)op.n2, pl->c);
   pl->kron.tmp = ar->take<float>((size_t)op.B * op.N * pl->c * (cols ? 2 : 1));
-  pl->S_dot = kron_S_dot((int)op.R, (int)op.n2, pl->c, pl->sp.S);
   return LO_OK;
 }
 
@@ -124,17 +122,24 @@ static int sum_run(const MatvecPlan* pl, const float* v, float* y, const int* st
 }
 
 // ---- the plan of any kind -------------------------------------------------------------------------------------------------
+// (the dense and Kronecker kernels write one partial per tile of their own; every other kind one per row block)
+int matvec_S_dot(const lo_op_desc* op, int64_t c, Split sp) {
+  if (op->kind == LO_OP_DENSE_DIAG) return dense_S_dot(op->B, op->N, c);
+  if (op->kind == LO_OP_KRON_DIAG) return kron_S_dot((int)op->R, (int)op->n2, c, sp.S);
+  return sp.S;
+}
+
 int matvec_plan_init(MatvecPlan* pl, const lo_op_desc* op, lo_matvec_cb cb, void* cb_user, int64_t c, Split sp,
                      Arena* ar, hipStream_t st) {
   *pl = MatvecPlan();
   pl->op = *op;
   pl->c = c;
   pl->sp = sp;
-  pl->S_dot = sp.S;
   pl->cb = cb;
   pl->cb_user = cb_user;
   if (op->B < 1 || op->N < 1 || c < 1) return LO_ERR_BADARG;
   if (op->diag_mode != LO_DIAG_NONE && !op->d) return LO_ERR_BADARG;
+  pl->S_dot = matvec_S_dot(op, c, sp);
   int rc = LO_ERR_BADARG;
   switch (op->kind) {
     case LO_OP_LOWRANK_DIAG: rc = lowrank_plan(pl, ar, st); break;
@@ -155,10 +160,8 @@ int matvec_plan_init(MatvecPlan* pl, const lo_op_desc* op, lo_matvec_cb cb, void
 }
 
 size_t matvec_plan_bytes(const lo_op_desc* op, int64_t c, Split sp) {
-  Arena ar(nullptr, 0);
-  MatvecPlan scratch;
-  matvec_plan_init(&scratch, op, nullptr, nullptr, c, sp, &ar, nullptr);  // (an invalid descriptor: what it took before it was refused)
-  return ar.off + kPlanTail;
+  MatvecPlan scratch;  // (an invalid descriptor: what it took before it was refused)
+  return measured(kPlanTail, [&](Arena& ar) { matvec_plan_init(&scratch, op, nullptr, nullptr, c, sp, &ar, nullptr); });
 }
 
 void matvec_plan_free(MatvecPlan* pl) {

@@ -280,23 +280,17 @@ __global__ __launch_bounds__(kThreads) void k_mr_final(MrDev d, int rows_per) {
     }
 }
 
-struct MrHost {
-  Split sp;
-  int preR4;
-  const float* Qp;
-  float* upart;
-};
-
-static size_t mr_layout(const lo_op_desc* op, const lo_precond_desc* pre, bool pre_cb, const lo_minres_params* prm,
-                        void* ws, size_t ws_bytes, MrDev* dout, MatvecPlan* pl, lo_matvec_cb cb, void* cb_user,
-                        MrHost* h, hipStream_t st, int* rc_out) {
+constexpr size_t kMrTail = 1024;  // what lo_minres_workspace_bytes reports beyond the layout
+// (on a measuring arena: the sizing pass -- the same takes, nothing staged)
+static int mr_layout(Arena& ar, const lo_op_desc* op, const lo_precond_desc* pre, bool pre_cb,
+                     const lo_minres_params* prm, MrDev* dout, MatvecPlan* pl, lo_matvec_cb cb, void* cb_user,
+                     PrecondPlan* pp, hipStream_t st) {
   const int64_t B = op->B, N = op->N, c = prm->c;
   const int Q = prm->n_shifts;
   Split sp = choose_split(B, N, 256);
-  Arena ar(ws, ws_bytes);  // (ws == nullptr: the sizing pass -- the same takes, nothing staged)
   const size_t nv = (size_t)B * N * c, ns = (size_t)B * c;
   const bool precond = pre != nullptr || pre_cb;
-  MrDev d;
+  MrDev& d = *dout;
   memset(&d, 0, sizeof(d));
   d.B = B; d.N = N; d.c = (int)c; d.Q = Q; d.S = sp.S;
   d.ctrl = ar.take<MrCtrl>(1);
@@ -304,12 +298,9 @@ static size_t mr_layout(const lo_op_desc* op, const lo_precond_desc* pre, bool p
   for (int i = 0; i < 2; ++i) d.q[i] = precond ? ar.take<float>(nv) : nullptr;
   d.sA = ar.take<float>(nv * Q);
   d.sB = ar.take<float>(nv * Q);
-  int S_dot = sp.S;
-  if (op->kind == LO_OP_DENSE_DIAG) S_dot = dense_S_dot(B, N, c);
-  else if (op->kind == LO_OP_KRON_DIAG) S_dot = kron_S_dot((int)op->R, (int)op->n2, c, sp.S);
-  d.S_dot = S_dot;
+  d.S_dot = matvec_S_dot(op, c, sp);
   d.S_b = sp.S;
-  d.dot_part = ar.take<float>((size_t)B * std::max(S_dot, sp.S) * c);
+  d.dot_part = ar.take<float>((size_t)B * std::max(d.S_dot, sp.S) * c);
   d.b_part = ar.take<float>((size_t)B * sp.S * c);
   d.upd_part = ar.take<float>((size_t)Q * B * sp.S * c);
   d.sol_part = ar.take<float>((size_t)Q * B * sp.S * c);
@@ -320,35 +311,11 @@ static size_t mr_layout(const lo_op_desc* op, const lo_precond_desc* pre, bool p
   d.rhs_zero = ar.take<int>(ns);
   float** per_q[] = {&d.cos1, &d.sin1, &d.cos2, &d.sin2, &d.scale_prev, &d.sub, &d.subsub, &d.diag, &d.scale_upd};
   for (float** p : per_q) *p = ar.take<float>(ns * Q);
-  if (h) {
-    h->sp = sp;
-    h->preR4 = 0;
-    h->Qp = nullptr;
-    h->upart = nullptr;
-  }
-  if (pre) {
-    const int R4 = padded_rank(pre->k);
-    float* up = ar.take<float>((size_t)B * sp.S * R4 * c);
-    const float* qp = pre->Q;
-    if (pre->ldq != R4) {
-      float* pad = ar.take<float>((size_t)B * N * R4);
-      if (!ar.measuring() && ar.ok) {
-        if (pre->ldq != pre->k) { if (rc_out) *rc_out = LO_ERR_BADARG; }
-        else {
-          int rc = pad_rows(pre->Q, pre->k, pad, R4, B * N, st);
-          if (rc && rc_out) *rc_out = rc;
-        }
-      }
-      qp = pad;
-    }
-    if (h) { h->preR4 = R4; h->Qp = qp; h->upart = up; }
-  }
-  MatvecPlan scratch;  // (the sizing pass keeps no plan)
-  const int rc = matvec_plan_init(pl ? pl : &scratch, op, cb, cb_user, c, sp, &ar, st);
-  if (rc && rc_out && *rc_out == LO_OK) *rc_out = rc;
-  if (dout) *dout = d;
-  if (!ar.ok && rc_out && *rc_out == LO_OK) *rc_out = LO_ERR_WORKSPACE;
-  return ar.off + 1024;
+  int rc = pre ? precond_plan_init(pp, pre, B, N, c, sp, &ar, st) : LO_OK;
+  const int rc_mv = matvec_plan_init(pl, op, cb, cb_user, c, sp, &ar, st);  // (a measuring pass keeps no sub-plans)
+  if (!rc) rc = rc_mv;
+  if (!rc && pl->S_dot != d.S_dot) rc = LO_ERR_LAUNCH;  // (dot_part was sized for another count: never)
+  return (rc || ar.ok) ? rc : LO_ERR_WORKSPACE;
 }
 
 }  // namespace lo
@@ -359,13 +326,13 @@ extern "C" {
 
 size_t lo_minres_workspace_bytes(const lo_op_desc* op, const lo_precond_desc* pre, const lo_minres_params* prm) {
   if (!op || !prm || prm->n_shifts < 1 || prm->c < 1) return 0;
-  lo_precond_desc dummy;
-  const lo_precond_desc* p = pre;
-  if (!p) {  // worst case: a closure preconditioner needs the q vectors as well
-    dummy.k = 4; dummy.ldq = 4; dummy.constant_diag = 0; dummy.reserved = 0; dummy.Q = nullptr; dummy.dinv = nullptr;
-    p = &dummy;
-  }
-  return mr_layout(op, p, true, prm, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+  const lo_precond_desc worst = worst_case_precond();  // (a closure preconditioner needs the q vectors as well)
+  MrDev d;
+  MatvecPlan pl;
+  PrecondPlan pp;
+  return measured(kMrTail, [&](Arena& ar) {
+    mr_layout(ar, op, pre ? pre : &worst, true, prm, &d, &pl, nullptr, nullptr, &pp, nullptr);
+  });
 }
 
 int lo_minres_f32(const lo_op_desc* op, lo_matvec_cb matvec, void* matvec_user, const lo_precond_desc* pre,
@@ -381,11 +348,11 @@ int lo_minres_f32(const lo_op_desc* op, lo_matvec_cb matvec, void* matvec_user, 
   MrDev d;
   MatvecPlan pl;
   PlanGuard pl_guard(&pl);
-  MrHost h;
-  int rc = LO_OK;
-  mr_layout(op, pre, precond_cb != nullptr, prm, ws, ws_bytes, &d, &pl, matvec, matvec_user, &h, st, &rc);
+  PrecondPlan pp;
+  Arena ar(ws, ws_bytes, kMrTail);
+  int rc = mr_layout(ar, op, pre, precond_cb != nullptr, prm, &d, &pl, matvec, matvec_user, &pp, st);
   if (rc) return rc;
-  const Split sp = h.sp;
+  const Split sp = pl.sp;
   const bool precond = pre != nullptr || precond_cb != nullptr;
   d.value = prm->has_value ? prm->value : 1.0f;
   d.eps = prm->eps;
@@ -393,18 +360,12 @@ int lo_minres_f32(const lo_op_desc* op, lo_matvec_cb matvec, void* matvec_user, 
   d.shifts = shifts;
   d.shifts_per_member = prm->shifts_per_member;
   d.sol = x;
-  d.S_dot = pl.S_dot;
   dim3 gridv(sp.S, (unsigned)B), block(kThreads);
   const unsigned gscal = (unsigned)std::min<int64_t>(256, ((int64_t)B * c + kThreads - 1) / kThreads);
   const size_t nv = (size_t)B * N * c;
 
   auto apply_precond = [&](const float* r, float* z, float* dotp) -> int {
-    if (pre) {
-      int e = skinny_tn(h.Qp, h.preR4, h.preR4, r, c, h.upart, B, N, sp, nullptr, st);
-      if (e) return e;
-      return skinny_nn(h.Qp, h.preR4, h.preR4, h.upart, pre->dinv, pre->constant_diag ? LO_DIAG_CONST : LO_DIAG_FULL,
-                       -1.0f, r, c, z, dotp, B, N, sp, nullptr, st);
-    }
+    if (pre) return precond_plan_run(&pp, r, z, dotp, nullptr, st);
     int e = precond_cb(precond_user, r, z, B, N, c, (void*)st);
     if (e) return LO_ERR_LAUNCH;
     return vec_dot_part(r, z, c, dotp, B, N, sp, nullptr, st);

@@ -663,11 +663,11 @@ int pc_stream(const lo_op_desc* op, const float* diag0, lo_rowfetch_cb row_cb, v
 
 template <typename T>
 static size_t pc_ws_bytes(const lo_op_desc* op, int32_t max_rank, bool cb) {
-  Arena ar(nullptr, 0);
   PcDevT<T> d;
-  pc_layout(op, max_rank, ar, &d);
-  if (cb) ar.take<T>((size_t)op->B * op->N);  // the fetched rows
-  return ar.off + 1024;
+  return measured(1024, [&](Arena& ar) {
+    pc_layout(op, max_rank, ar, &d);
+    if (cb) ar.take<T>((size_t)op->B * op->N);  // the fetched rows
+  });
 }
 
 static int pc_check_desc(const lo_op_desc* op) {

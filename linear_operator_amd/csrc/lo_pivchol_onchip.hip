@@ -1019,10 +1019,8 @@ static void po_layout(const lo_op_desc* op, int max_rank, Arena& ar, PoLayout* l
 }
 
 size_t pc_onchip_workspace_bytes(const lo_op_desc* op, int max_rank) {
-  Arena ar(nullptr, 0);
   PoLayout l;
-  po_layout(op, max_rank, ar, &l);
-  return ar.off + 1024;
+  return measured(1024, [&](Arena& ar) { po_layout(op, max_rank, ar, &l); });
 }
 
 int pc_onchip_run(const lo_op_desc* op, int rank, int max_rank, float tol, float* L_rows, long long* perm,
@@ -1188,10 +1186,8 @@ static void pr_layout(const lo_op_desc* op, int max_rank, Arena& ar, PrLayout* l
 }
 
 size_t pc_onchip_rows_workspace_bytes(const lo_op_desc* op, int max_rank) {
-  Arena ar(nullptr, 0);
   PrLayout l;
-  pr_layout(op, max_rank, ar, &l);
-  return ar.off + 1024;
+  return measured(1024, [&](Arena& ar) { pr_layout(op, max_rank, ar, &l); });
 }
 
 template <int SRC, int GW>

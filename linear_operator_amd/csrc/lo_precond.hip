@@ -1066,6 +1066,37 @@ static int precond_build_wide(const float* L, LStride ls, const float* d, int di
   return LO_OK;
 }
 
+// ---- workspaces of the build entry points: one layout each, run by the entry point on its workspace and by the sizer
+// on a measuring arena.  A braced list is evaluated left to right: takes in the order of the members.
+constexpr size_t kPbTail = 1024;  // what the sizers report beyond the layout
+struct PbBufs {
+  Split sp;
+  double* gpart;  // [B, S, k, k] Gram partials
+  double* logd;   // [B, S] log d partials
+  double* Minv;   // [B, k, k]; the wide path (precond_build_wide) keeps the fp32 k x k operand of its Q kernel in this storage
+  float* scale;   // [B, N] per-row 1 / sqrt(d) of the matrix-core paths
+};
+static PbBufs pb_layout(Arena& ar, int64_t B, int64_t N, int k) {
+  const Split sp = choose_split(B, N, 256);
+  return {sp, ar.take<double>((size_t)B * sp.S * k * k), ar.take<double>((size_t)B * sp.S),
+          ar.take<double>((size_t)B * k * k), ar.take<float>((size_t)B * N)};
+}
+// partials [B, S, R, R] of E = C^T D^-1 C and (R-space form only, else nullptr) of C^T C; log d [B, S]; scale [B, N]
+struct RfBufs { Split sp; double *gpartE, *gpart2, *logd; float* scale; };
+static RfBufs rf_layout(Arena& ar, int64_t B, int64_t N, int R, bool rs) {
+  const Split sp = choose_split(B, N, 256);
+  const size_t g = (size_t)B * sp.S * R * R;
+  return {sp, ar.take<double>(g), rs ? ar.take<double>(g) : nullptr, ar.take<double>((size_t)B * sp.S),
+          ar.take<float>((size_t)B * N)};
+}
+// Gram matrix [B, 16, 16]; log d [B]; pivot rows of KP, EF, E [3, B, 256]; logdet, 1 / sigma [2, B] (both already known
+// from the Q form)
+struct KrBufs { double *gpart, *logd; float *scratch, *small; };
+static KrBufs kr_layout(Arena& ar, int64_t B) {
+  return {ar.take<double>((size_t)B * 256), ar.take<double>((size_t)B), ar.take<float>((size_t)B * 256 * 3),
+          ar.take<float>((size_t)B * 2)};
+}
+
 }  // namespace lo
 
 using namespace lo;
@@ -1073,13 +1104,7 @@ using namespace lo;
 extern "C" {
 
 size_t lo_precond_build_workspace_bytes(int64_t B, int64_t N, int32_t k) {
-  Split sp = choose_split(B, N, 256);
-  Arena ar(nullptr, 0);
-  ar.take<double>((size_t)B * sp.S * k * k);
-  ar.take<double>((size_t)B * sp.S);
-  ar.take<double>((size_t)B * k * k);
-  ar.take<float>((size_t)B * N);  // per-row 1/sqrt(d) of the matrix-core path
-  return ar.off + 1024;
+  return measured(kPbTail, [&](Arena& ar) { pb_layout(ar, B, N, k); });
 }
 
 // Q must hold [B, N, ldq] floats with ldq = 4 * pow2ceil(ceil(k/4)); dinv [B,N] (FULL) or [B] (CONST).
@@ -1096,16 +1121,12 @@ int lo_precond_build_strided_f32(const float* L, int64_t ld_member, int64_t ld_r
   if (diag_mode != LO_DIAG_FULL && diag_mode != LO_DIAG_CONST) return LO_ERR_BADARG;
   if (k < 1 || k > kPbWideMaxK) return LO_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
-  Split sp = choose_split(B, N, 256);
-  Arena ar(ws, ws_bytes);
-  double* gpart = ar.take<double>((size_t)B * sp.S * k * k);
-  double* logd = ar.take<double>((size_t)B * sp.S);
-  double* Minv = ar.take<double>((size_t)B * k * k);
-  float* scale = ar.take<float>((size_t)B * N);
+  Arena ar(ws, ws_bytes, kPbTail);
+  auto [sp, gpart, logd, Minv, scale] = pb_layout(ar, B, N, k);
   if (!ar.ok) return LO_ERR_WORKSPACE;
   // wide path: k > 32, and 16 < k <= 32 in the rows layout [B, m, N] the pivoted-Cholesky kernels write (the fp64
   // matrix-core kernels of that layout take 16 columns; the per-row VALU kernels that used to serve this case need
-  // 6.4 ms at 512 x 8192 x 17 against ~1 ms here)   (Minv's storage holds the fp32 k x k operand of the Q kernel)
+  // 6.4 ms at 512 x 8192 x 17 against ~1 ms here)
   if (k > kPbMaxK || (k > 16 && ld_col != 1))
     return precond_build_wide(L, ls, d, diag_mode, B, N, k, Q, dinv, logdet_p, gpart, logd,
                               reinterpret_cast<float*>(Minv), scale, sp, st);
@@ -1160,12 +1181,7 @@ int lo_precond_build_strided_f32(const float* L, int64_t ld_member, int64_t ld_r
 }
 
 size_t lo_precond_root_form_workspace_bytes(int64_t B, int64_t N, int32_t R) {
-  Split sp = choose_split(B, N, 256);
-  Arena ar(nullptr, 0);
-  ar.take<double>((size_t)B * sp.S * R * R);
-  ar.take<double>((size_t)B * sp.S);
-  ar.take<float>((size_t)B * N);
-  return ar.off + 1024;
+  return measured(kPbTail, [&](Arena& ar) { rf_layout(ar, B, N, R, false); });
 }
 
 int lo_precond_root_form_f32(const float* C, int32_t R, const float* d, int32_t diag_mode, const float* L,
@@ -1176,11 +1192,8 @@ int lo_precond_root_form_f32(const float* C, int32_t R, const float* d, int32_t 
   if (diag_mode != LO_DIAG_FULL && diag_mode != LO_DIAG_CONST) return LO_ERR_BADARG;
   if (R < 1 || R > kPbMaxK || k < 1 || k > kPbMaxK || rf_ld < R || rf_ld > kPbMaxK) return LO_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
-  Split sp = choose_split(B, N, 256);
-  Arena ar(ws, ws_bytes);
-  double* gpart = ar.take<double>((size_t)B * sp.S * R * R);
-  double* logd = ar.take<double>((size_t)B * sp.S);
-  float* scale = ar.take<float>((size_t)B * N);
+  Arena ar(ws, ws_bytes, kPbTail);
+  auto [sp, gpart, gpart2, logd, scale] = rf_layout(ar, B, N, R, false);
   if (!ar.ok) return LO_ERR_WORKSPACE;
   dim3 grid(sp.S, (unsigned)B), block(kThreads);
   const float* sc = nullptr;
@@ -1211,13 +1224,7 @@ int lo_precond_root_form_f32(const float* C, int32_t R, const float* d, int32_t 
 }
 
 size_t lo_precond_root_form_rs_workspace_bytes(int64_t B, int64_t N, int32_t R) {
-  Split sp = choose_split(B, N, 256);
-  Arena ar(nullptr, 0);
-  ar.take<double>((size_t)B * sp.S * R * R);
-  ar.take<double>((size_t)B * sp.S * R * R);
-  ar.take<double>((size_t)B * sp.S);
-  ar.take<float>((size_t)B * N);
-  return ar.off + 1024;
+  return measured(kPbTail, [&](Arena& ar) { rf_layout(ar, B, N, R, true); });
 }
 
 int lo_precond_root_form_rs_f32(const float* C, int32_t R, const float* d, int32_t diag_mode, const float* L,
@@ -1229,12 +1236,8 @@ int lo_precond_root_form_rs_f32(const float* C, int32_t R, const float* d, int32
   if (R < 1 || R > kPbMaxK || k < 1 || k > kPbMaxK || rf_ld < R || rf_ld > kPbMaxK) return LO_ERR_UNSUPPORTED;
   if ((R % 4) != 0 || ((uintptr_t)C % 16) != 0) return LO_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
-  Split sp = choose_split(B, N, 256);
-  Arena ar(ws, ws_bytes);
-  double* gpartE = ar.take<double>((size_t)B * sp.S * R * R);
-  double* gpart2 = ar.take<double>((size_t)B * sp.S * R * R);
-  double* logd = ar.take<double>((size_t)B * sp.S);
-  float* scale = ar.take<float>((size_t)B * N);
+  Arena ar(ws, ws_bytes, kPbTail);
+  auto [sp, gpartE, gpart2, logd, scale] = rf_layout(ar, B, N, R, true);
   if (!ar.ok) return LO_ERR_WORKSPACE;
   dim3 grid(sp.S, (unsigned)B), block(kThreads);
   if (diag_mode == LO_DIAG_FULL) {  // dinv = fp32(1 / d): THE D^-1 of the R-space iteration (and log d partials)
@@ -1258,12 +1261,7 @@ int lo_precond_root_form_rs_f32(const float* C, int32_t R, const float* d, int32
 }
 
 size_t lo_precond_kron_root_workspace_bytes(int64_t B) {
-  Arena ar(nullptr, 0);
-  ar.take<double>((size_t)B * 256);
-  ar.take<double>((size_t)B);
-  ar.take<float>((size_t)B * 256 * 3);
-  ar.take<float>((size_t)B * 2);
-  return ar.off + 1024;
+  return measured(kPbTail, [&](Arena& ar) { kr_layout(ar, B); });
 }
 
 int lo_precond_kron_root_f32(const lo_op_desc* op, const float* L, int64_t ld_member, int64_t ld_row, int64_t ld_col,
@@ -1276,11 +1274,8 @@ int lo_precond_kron_root_f32(const lo_op_desc* op, const float* L, int64_t ld_me
   static_assert(kThreads == 256, "k_pb_kron_gather: one (m, n) pair per thread");
   hipStream_t st = (hipStream_t)stream;
   const int64_t B = op->B;
-  Arena ar(ws, ws_bytes);
-  double* gpart = ar.take<double>((size_t)B * 256);
-  double* logd = ar.take<double>((size_t)B);
-  float* scratch = ar.take<float>((size_t)B * 256 * 3);  // pivot rows of KP, EF, E
-  float* small = ar.take<float>((size_t)B * 2);          // logdet, 1 / sigma (both already known from the Q form)
+  Arena ar(ws, ws_bytes, kPbTail);
+  auto [gpart, logd, scratch, small] = kr_layout(ar, B);
   if (!ar.ok) return LO_ERR_WORKSPACE;
   float* Cpiv = scratch;
   LO_PROF_BEGIN("pb_kron_root", st);

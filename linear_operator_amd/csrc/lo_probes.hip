@@ -215,6 +215,11 @@ __global__ __launch_bounds__(kThreads) void k_iql_factors(const float* __restric
   }
 }
 
+// the workspace of lo_probe_vectors_f32: squared-norm partials [B, S, P], one per block of PV_ROWS rows
+constexpr size_t kPvTail = 256;  // what the sizer reports beyond the layout
+static float* pv_layout(Arena& ar, int64_t B, int S, int64_t P) { return ar.take<float>((size_t)B * S * P); }
+static int pv_blocks(int64_t N) { return (int)((N + PV_ROWS - 1) / PV_ROWS); }
+
 }  // namespace lo
 
 using namespace lo;
@@ -222,8 +227,7 @@ using namespace lo;
 extern "C" {
 
 size_t lo_probe_vectors_workspace_bytes(int64_t B, int64_t N, int64_t P) {
-  const int64_t S = (N + PV_ROWS - 1) / PV_ROWS;
-  return (size_t)B * S * P * sizeof(float) + 256;
+  return measured(kPvTail, [&](Arena& ar) { pv_layout(ar, B, pv_blocks(N), P); });
 }
 
 int lo_probe_vectors_f32(const float* L, int64_t l_sb, int64_t l_sn, int64_t l_sk, int32_t k, const float* d,
@@ -234,10 +238,11 @@ int lo_probe_vectors_f32(const float* L, int64_t l_sb, int64_t l_sn, int64_t l_s
     return LO_ERR_BADARG;
   if (k < 1 || k > 32 || P < 1 || P > 64 || q > 64 || B > 65535 || N >= (1 << 30) / (P + q)) return LO_ERR_UNSUPPORTED;
   if (diag_mode != LO_DIAG_FULL && diag_mode != LO_DIAG_CONST) return LO_ERR_BADARG;
-  if (ws_bytes < lo_probe_vectors_workspace_bytes(B, N, P)) return LO_ERR_WORKSPACE;
+  Arena ar(ws, ws_bytes, kPvTail);
+  const int S = pv_blocks(N);
+  float* part = pv_layout(ar, B, S, P);
+  if (!ar.ok) return LO_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  const int S = (int)((N + PV_ROWS - 1) / PV_ROWS);
-  float* part = reinterpret_cast<float*>(ws);
   dim3 grid(S, (unsigned)B), block(kThreads);
   LO_PROF_BEGIN("probe_form", st);
   const size_t lds = (size_t)((((int)k * (int)P + 3) & ~3) + PV_ROWS * ((int)P + 1)) * sizeof(float);

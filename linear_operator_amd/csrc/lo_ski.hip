@@ -163,10 +163,8 @@ void csr_layout(Arena& ar, int64_t B, int64_t N, int64_t J, int64_t M, CsrBufs* 
 }
 
 size_t csr_bytes(int64_t B, int64_t N, int64_t J, int64_t M) {
-  Arena ar(nullptr, 0);
   CsrBufs b;
-  csr_layout(ar, B, N, J, M, &b);
-  return ar.off + kPlanTail;
+  return measured(kPlanTail, [&](Arena& ar) { csr_layout(ar, B, N, J, M, &b); });
 }
 
 int csr_build(const int64_t* idx, int64_t B, int64_t N, int64_t J, int64_t M, Arena* ar, CsrBufs* b, hipStream_t st) {

@@ -467,10 +467,8 @@ int lo_toeplitz_kron_mv_f32(const float* t, const int64_t* m, int ndim, int64_t 
 size_t lo_toeplitz_kron_bilinear_workspace_bytes(const int64_t* m, int ndim, int64_t B, int64_t S) {
   int64_t M = 0;
   if (!m || B < 1 || S < 1 || !grid_shape_ok(m, ndim, &M)) return 0;
-  Arena ar(nullptr, 0);
   BilBufs b;
-  bil_layout(ar, m, ndim, B, M, S, &b);
-  return ar.off + 256;
+  return measured(256, [&](Arena& ar) { bil_layout(ar, m, ndim, B, M, S, &b); });
 }
 
 int lo_toeplitz_kron_bilinear_f32(const float* t, const int64_t* m, int ndim, int64_t B, const float* u, const float* v,

@@ -456,4 +456,26 @@ int skinny_nn(const float* A, int lda, int R4, const float* tpart, const float* 
   return LO_OK;
 }
 
+// ---- the Q-form Woodbury apply as a plan (lo_internal.h) ---------------------------------------------------------------
+int precond_plan_init(PrecondPlan* pp, const lo_precond_desc* pre, int64_t B, int64_t N, int64_t c, Split sp, Arena* ar,
+                      hipStream_t st) {
+  const int R4 = padded_rank(pre->k);
+  *pp = PrecondPlan{pre->Q, R4, ar->take<float>((size_t)B * sp.S * R4 * c), pre->dinv,
+                    pre->constant_diag ? LO_DIAG_CONST : LO_DIAG_FULL, B, N, c, sp};
+  if (!pre->Q || pre->ldq == R4) return ar->measuring() || ar->ok ? LO_OK : LO_ERR_WORKSPACE;
+  float* qp = ar->take<float>((size_t)B * N * R4);
+  if (pre->ldq != pre->k) return LO_ERR_BADARG;
+  if (ar->measuring()) return LO_OK;
+  if (!ar->ok) return LO_ERR_WORKSPACE;
+  pp->Qp = qp;
+  return pad_rows(pre->Q, pre->k, qp, R4, B * N, st);
+}
+
+int precond_plan_run(const PrecondPlan* pp, const float* r, float* z, float* dot_part, const int* stop, hipStream_t st) {
+  const int rc = skinny_tn(pp->Qp, pp->R4, pp->R4, r, pp->c, pp->upart, pp->B, pp->N, pp->sp, stop, st);
+  if (rc) return rc;
+  return skinny_nn(pp->Qp, pp->R4, pp->R4, pp->upart, pp->dinv, pp->dinv_mode, -1.0f, r, pp->c, z, dot_part, pp->B, pp->N,
+                   pp->sp, stop, st);
+}
+
 }  // namespace lo

@@ -148,10 +148,8 @@ int lo_solve_fused_supported(const lo_op_desc* op, int32_t rank, const lo_cg_par
 
 size_t lo_solve_fused_workspace_bytes(const lo_op_desc* op, int32_t rank, const lo_cg_params* prm) {
   if (!op || !prm) return 0;
-  Arena ar(nullptr, 0);
   FuLayout l;
-  fu_layout(op->B, rank, fused_iters(prm), prm->c, kFuMaxWgs, ar, &l);
-  return ar.off + 1024;
+  return measured(1024, [&](Arena& ar) { fu_layout(op->B, rank, fused_iters(prm), prm->c, kFuMaxWgs, ar, &l); });
 }
 
 int lo_solve_fused_f32(const lo_op_desc* op, int32_t rank, float error_tol, const lo_cg_params* prm, const float* rhs,

@@ -4,12 +4,17 @@
 // kind go through lo_matvec_workspace_bytes, lo_cg_workspace_bytes, lo_minres_workspace_bytes and
 // lo_lanczos_workspace_bytes.  The sizing passes run the plan functions on a measuring arena: they must read no device
 // pointer (the ones here are dummy addresses), keep no sub-plan (a leak report) and touch nothing out of bounds.  No GPU.
+// The solver sizers are also walked with Woodbury preconditioners (the padded copy of Q taken and not taken, the root
+// form alone), and the sizers of the other entry points with shapes of tests/workspace_cases.py.
 //
 //   cd linear_operator_amd/csrc && mkdir -p build_asan
 //   for f in *.hip; do hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -fPIC -Xarch_host -fsanitize=address,undefined \
 //       -c $f -o build_asan/${f%.hip}.o; done
-//   hipcc --offload-arch=gfx950 -fsanitize=address,undefined ../../tools/check_plan_sizes.cpp build_asan/*.o \
-//       -o build_asan/check_plan_sizes && build_asan/check_plan_sizes
+//   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined \
+//       -c ../../tools/check_plan_sizes.cpp -o build_asan/check_plan_sizes.o
+//   hipcc --offload-arch=gfx950 -fsanitize=address,undefined build_asan/*.o -o build_asan/check_plan_sizes \
+//       && build_asan/check_plan_sizes
+// (the program is compiled to an object of its own: on one line with the objects, hipcc reads them as HIP source)
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -59,6 +64,69 @@ static int walk(const std::vector<Entry>& table) {
         ++bad;
       }
     }
+  }
+  return bad;
+}
+
+// lo_precond_apply_workspace_bytes and the CG / MINRES sizers over the same descriptors: PrecondPlan on a measuring arena
+static int walk_precond(const lo_op_desc& op) {
+  int bad = 0;
+  const int64_t shapes[2][3] = {{1, 37, 1}, {3, 300, 3}};
+  for (const auto& sh : shapes)
+    for (int k : {4, 5, 8, 33}) {
+      int R4 = 4;
+      while (R4 < k) R4 *= 2;
+      const size_t got = lo_precond_apply_workspace_bytes(sh[0], sh[1], k, sh[2]);
+      const size_t copy = k != R4 ? sizeof(float) * sh[0] * sh[1] * R4 : 0, upart = sizeof(float) * sh[0] * R4 * sh[2];
+      printf("precond_apply B=%lld N=%lld k=%d c=%lld: %zu\n", (long long)sh[0], (long long)sh[1], k, (long long)sh[2], got);
+      if (got < copy + upart || got > copy + upart * 256 + 2048) {  // (at most 256 row blocks, two alignments, the tail)
+        printf("  the size does not match the plan's takes\n");
+        ++bad;
+      }
+    }
+  lo_cg_params cg;
+  memset(&cg, 0, sizeof(cg));
+  cg.c = 3; cg.max_iter = 5; cg.max_tridiag_iter = 20; cg.tolerance = 1e-4f; cg.eps = 1e-10f;
+  lo_minres_params mr;
+  memset(&mr, 0, sizeof(mr));
+  mr.c = 3; mr.n_shifts = 2; mr.max_iter = 3;
+  lo_precond_desc pre;
+  memset(&pre, 0, sizeof(pre));
+  pre.k = 5; pre.dinv = F(0x80000);
+  const size_t none_cg = lo_cg_workspace_bytes(&op, nullptr, &cg), none_mr = lo_minres_workspace_bytes(&op, nullptr, &mr);
+  const size_t copy = sizeof(float) * op.B * op.N * 8;
+  pre.ldq = 8; pre.Q = F(0x90000);  // rows padded already: upart only
+  const size_t a8 = lo_cg_workspace_bytes(&op, &pre, &cg), b8 = lo_minres_workspace_bytes(&op, &pre, &mr);
+  pre.ldq = 5;                      // unpadded rows: the copy as well
+  const size_t a5 = lo_cg_workspace_bytes(&op, &pre, &cg), b5 = lo_minres_workspace_bytes(&op, &pre, &mr);
+  pre.Q = nullptr; pre.F = pre.EF = F(0xa0000); pre.rf_ld = 8;  // root form only: no copy
+  const size_t ar = lo_cg_workspace_bytes(&op, &pre, &cg);
+  printf("woodbury k=5: cg %zu / %zu / root only %zu (none %zu), minres %zu / %zu (none %zu)\n", a8, a5, ar, none_cg, b8, b5,
+         none_mr);
+  if (a5 < a8 + copy || b5 < b8 + copy || ar >= a8 + copy) {
+    printf("  the padded copy of Q is not counted where it is taken\n");
+    ++bad;
+  }
+  return bad;
+}
+
+// the sizers of the entry points that lay their own workspace out (rows of tests/workspace_cases.py; 0 = refused)
+static int walk_entries() {
+  const size_t got[] = {
+      lo_precond_build_workspace_bytes(2, 37, 5),           lo_precond_build_workspace_bytes(3, 300, 33),
+      lo_precond_root_form_workspace_bytes(2, 37, 5),       lo_precond_root_form_rs_workspace_bytes(2, 37, 8),
+      lo_precond_kron_root_workspace_bytes(3),              lo_bilinear_root_workspace_bytes(2, 37, 5, 3),
+      lo_bilinear_kron_workspace_bytes(2, 3, 5, 3),         lo_probe_vectors_workspace_bytes(3, 300, 4),
+      lo_hadamard_bilinear_workspace_bytes(2, 37, 3, 2, 1), lo_cholesky_workspace_bytes(2, 37),
+      lo_tridiag_eigh_slq_workspace_bytes(3, 2)};
+  int bad = 0;
+  for (size_t g : got) {
+    printf("entry sizer: %zu\n", g);
+    if (g < 256) ++bad;
+  }
+  if (lo_hadamard_bilinear_workspace_bytes(2, 37, 0, 2, 1) != 0 || lo_cholesky_workspace_bytes(2, 1025) != 0) {
+    printf("  a refused shape was sized\n");
+    ++bad;
   }
   return bad;
 }
@@ -137,6 +205,7 @@ int main() {
   lo_op_desc sum_late = sum3;
   sum_late.terms = late;
   bad += walk({{"sum, bad last term", sum_late, true}});  // (its first terms do take buffers)
+  bad += walk_precond(t[0].op) + walk_entries();
   printf(bad ? "FAILED: %d\n" : "ok\n", bad);
   return bad ? 1 : 0;
 }
