@@ -75,6 +75,15 @@ extern "C" {
 #define LO_OP_TOEPLITZ_KRON_DIAG 10 /* AddedDiag(Kron(Toeplitz(t_1), .., Toeplitz(t_D)), Diag(d)), D = 2 or 3:
                                     *   y = (T_1 (x) .. (x) T_D) v + d o v   (a GP on a regular 2-D / 3-D grid)         */
 
+#define LO_OP_KERNEL_DIAG 11 /* AddedDiag(Kernel(X, X, family, lengthscale, outputscale), Diag(d)):  y = K(X, X) v + d o v with
+                              *   K_ij = outputscale^2 g(|(x_i - x_j) / lengthscale|) formed tile by tile from X, never stored
+                              * (kernel_linear_operator.py:379-383 evaluates covar_func densely)                           */
+#define LO_KERNEL_MAX_DIM 32 /* input dimensions D the on-the-fly kernels take (larger: LO_ERR_UNSUPPORTED)                 */
+#define LO_KERNEL_RBF 0      /* g(r) = exp(-r^2 / 2)                                    */
+#define LO_KERNEL_MATERN12 1 /* g(r) = exp(-r)                                          */
+#define LO_KERNEL_MATERN32 2 /* g(r) = (1 + sqrt(3) r) exp(-sqrt(3) r)                  */
+#define LO_KERNEL_MATERN52 3 /* g(r) = (1 + sqrt(5) r + 5 r^2 / 3) exp(-sqrt(5) r)      */
+
 struct lo_interp_desc;
 struct lo_mask_desc;
 struct lo_grid_desc;
@@ -121,7 +130,12 @@ typedef struct lo_op_desc {
    * again); shape limits LO_SKI_GRID_MAX_AXIS / LO_SKI_GRID_MAX_M.  Lowered for lo_matvec_f32, the streaming CG,
    * Lanczos, fp32 MINRES and the fp32 pivoted Cholesky (diagonal prod_k t_k[0], row[j] = prod_k t_k[|i_k - j_k|]); the
    * fp64 entry points, the resident / fused engines and the solve sessions return LO_ERR_UNSUPPORTED; not a term kind of
-   * LO_OP_SUM, not a base kind of LO_OP_MASKED.                                                                       */
+   * LO_OP_SUM, not a base kind of LO_OP_MASKED.
+   * ABI 26 kind.  KERNEL: A0 = X [B, N, D], R = D <= LO_KERNEL_MAX_DIM, A1 = theta [B, D + 1] = the D INVERSE lengthscales,
+   * then outputscale^2 (a shared lengthscale is replicated by the host), n2 = the family code LO_KERNEL_* (same layout
+   * again).  Lowered for lo_matvec_f32, the streaming CG, Lanczos, fp32 MINRES and the fp32 pivoted Cholesky (constant
+   * diagonal theta[D], row[j] = theta[D] g(r_ij)); the fp64 entry points, the resident / fused engines and the solve
+   * sessions return LO_ERR_UNSUPPORTED; not a term kind of LO_OP_SUM, not a base kind of LO_OP_MASKED.                  */
 } lo_op_desc;
 
 /* The grid shape of an LO_OP_TOEPLITZ_KRON_DIAG descriptor (host struct). */
@@ -134,7 +148,7 @@ struct lo_grid_desc { /* (a plain struct tag, as lo_mask_desc) */
 /* The base operator and the selected rows of an LO_OP_MASKED descriptor (masked_linear_operator.py:17-35 with
  * row_mask == col_mask): y = S (base) S^T v + d o v, S selecting the rows idx of the base.  base: HOST descriptor of
  * kind LOWRANK_DIAG, DENSE_DIAG, KRON_DIAG or SUM with any diagonal mode of its own (CALLBACK, MASKED, SKI, SKI_GRID,
- * TOEPLITZ, TOEPLITZ_KRON, HADAMARD: LO_ERR_UNSUPPORTED).  idx: DEVICE pointer, int64 [M], strictly increasing, one list for all members; an
+ * TOEPLITZ, TOEPLITZ_KRON, HADAMARD, KERNEL: LO_ERR_UNSUPPORTED).  idx: DEVICE pointer, int64 [M], strictly increasing, one list for all members; an
  * entry outside [0, base->N) contributes nothing and is never dereferenced (the convention of lo_interp_desc).      */
 struct lo_mask_desc { /* (a plain struct tag: C callers write `struct lo_mask_desc`) */
   const struct lo_op_desc* base;
@@ -850,6 +864,31 @@ size_t lo_hadamard_bilinear_workspace_bytes(int64_t B, int64_t N, int64_t p, int
 int lo_hadamard_bilinear_f32(const float* F, const float* G, const float* U, const float* V, int64_t B, int64_t N,
                              int64_t p, int64_t q, int64_t S, float* dF, float* dG, void* ws, size_t ws_bytes,
                              void* stream);
+
+/* ---- matrix-free kernel operator (ABI 26; csrc/lo_kernel_op.hip) ---------------------------------------------------------
+ * K(x1, x2)_ij = theta[D] g(r_ij), r_ij^2 = sum_d (theta[d] (x1[i, d] - x2[j, d]))^2 by direct differences, g one of
+ * LO_KERNEL_*; x1 [B, M, D], x2 [B, N, D], theta [B, D + 1] = D inverse lengthscales, then outputscale^2.  K is never in
+ * memory: a workgroup owns 256 rows (scaled once, kept in registers with their accumulators) and streams tiles of the
+ * scaled x2 and of v through LDS (kernel_linear_operator.py:379-383 evaluates covar_func densely before the product).
+ *   lo_kernel_mv_f32        y [B, M, c] = K v for v [B, N, c]; + d o v (d, diag_mode as in lo_op_desc) only when M == N
+ *                           and diag_mode != LO_DIAG_NONE.  The kind LO_OP_KERNEL_DIAG runs the same kernel with x1 = x2.
+ *                           Few rows (B M small): the columns j are split over workgroups, the partials go to ws and a
+ *                           second kernel adds them in ascending order.
+ *   lo_kernel_bilinear_f32  g_theta [B, D + 1] = d / d theta of sum_ij (sum_s U[i, s] V[j, s]) K_ij, U [B, M, t],
+ *                           V [B, N, t]: for d < D  sum_ij W_ij theta[D] (g'(r) / r) (theta[d] delta_d)^2 / theta[d], last
+ *                           entry sum_ij W_ij g(r).  A pair with r = 0 adds nothing to the first D entries for every
+ *                           family (no division by r).  One partial per workgroup, added in ascending order.
+ * Fixed-order sums, no float atomics: the same inputs give the same bits.  LO_ERR_BADARG: null pointers, non-positive
+ * sizes, an unknown family; LO_ERR_UNSUPPORTED: D > LO_KERNEL_MAX_DIM; LO_ERR_WORKSPACE (before any launch): ws smaller
+ * than the _workspace_bytes query (0: arguments that are not taken).  y must not alias v.                               */
+size_t lo_kernel_mv_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t D, int64_t c);
+int lo_kernel_mv_f32(const float* x1, const float* x2, const float* theta, int32_t family, int64_t B, int64_t M,
+                     int64_t N, int64_t D, const float* v, int64_t c, const float* d, int32_t diag_mode, float* y,
+                     void* ws, size_t ws_bytes, void* stream);
+size_t lo_kernel_bilinear_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t D, int64_t t);
+int lo_kernel_bilinear_f32(const float* x1, const float* x2, const float* theta, int32_t family, int64_t B, int64_t M,
+                           int64_t N, int64_t D, const float* U, const float* V, int64_t t, float* g_theta, void* ws,
+                           size_t ws_bytes, void* stream);
 
 /* ---- exact small-N path: batched Cholesky and triangular solves (ABI 18; csrc/lo_chol.hip) -------------------------
  * fp32, contiguous row-major, N <= 1024 (larger: LO_ERR_UNSUPPORTED), stream-ordered; fixed-order sums, no atomics: a

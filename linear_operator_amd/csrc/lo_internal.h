@@ -235,6 +235,13 @@ struct HadamardPlan {
 int hadamard_plan(MatvecPlan* pl, Arena* ar, hipStream_t st);
 int hadamard_matvec_run(const MatvecPlan* pl, const float* v, float* y, const int* stop, hipStream_t st);
 
+// ---- matrix-free kernel operator (lo_kernel_op.hip): LO_OP_KERNEL_DIAG ------------------------------------------------
+struct KernelOpPlan {
+  float* part;  // [js, B, N, c] partial products when the columns j of a member are split over js workgroups, else nullptr
+};
+int kernel_op_plan(MatvecPlan* pl, Arena* ar, hipStream_t st);
+int kernel_op_matvec_run(const MatvecPlan* pl, const float* v, float* y, const int* stop, hipStream_t st);
+
 // ---- masked operator (lo_masked.hip) ---------------------------------------------------------------------------------
 struct MaskedPlan {      // (the base's plan is MatvecPlan::sub[0])
   const int64_t* idx;    // [M]
@@ -269,6 +276,7 @@ struct MatvecPlan {
     SkiPlan ski;
     ToeplitzKronPlan tk;
     HadamardPlan hd;
+    KernelOpPlan ko;
     MaskedPlan mask;
   };
 };

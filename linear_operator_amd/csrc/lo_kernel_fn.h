@@ -1,0 +1,74 @@
+// lo_kernel_fn.h -- the covariance families of LO_OP_KERNEL_DIAG as functions of r^2 (lo_amd.h LO_KERNEL_*), shared by
+// the on-the-fly product (lo_kernel_op.hip) and the row source of the pivoted Cholesky (lo_pivchol.hip).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "../../include/lo_amd.h"
+
+namespace lo {
+
+constexpr float kKfLog2e = 1.44269504088896340736f;
+constexpr float kKfSqrt3 = 1.73205080756887729353f;
+constexpr float kKfSqrt5 = 2.23606797749978969641f;
+// beyond this r^2 every family is 0 in fp32 (exp(-sqrt(1e30)) underflows); the clamp keeps polynomial x exp finite
+constexpr float kKfMaxR2 = 1e30f;
+
+// exp(x) for x <= 0 as one v_exp_f32 on the argument multiplied by log2(e) beforehand: `xl` = x log2(e)
+__device__ __forceinline__ float kf_exp2(float xl) { return __builtin_amdgcn_exp2f(xl); }
+
+// g(r) from r^2 (FAMILY a compile-time constant in the hot loops): sqrt only for the Matern families
+template <int FAMILY>
+__device__ __forceinline__ float kf_g(float r2) {
+  if constexpr (FAMILY == LO_KERNEL_RBF) {
+    return kf_exp2(r2 * (-0.5f * kKfLog2e));
+  } else {
+    const float r = __builtin_amdgcn_sqrtf(fminf(r2, kKfMaxR2));
+    if constexpr (FAMILY == LO_KERNEL_MATERN12) {
+      return kf_exp2(r * -kKfLog2e);
+    } else if constexpr (FAMILY == LO_KERNEL_MATERN32) {
+      return fmaf(kKfSqrt3, r, 1.0f) * kf_exp2(r * (-kKfSqrt3 * kKfLog2e));
+    } else {
+      const float poly = fmaf(5.0f / 3.0f, fminf(r2, kKfMaxR2), fmaf(kKfSqrt5, r, 1.0f));
+      return poly * kf_exp2(r * (-kKfSqrt5 * kKfLog2e));
+    }
+  }
+}
+
+// g(r) and h(r) = g'(r) / r, the factor of d r^2 / 2 in the derivative of g: dg = h (d r^2) / 2.  Finite at r = 0 for
+// every family but Matern-1/2, whose h = -g / r is taken as 0 there (the pair adds nothing; no division by r).
+template <int FAMILY>
+__device__ __forceinline__ void kf_gh(float r2, float* g, float* h) {
+  if constexpr (FAMILY == LO_KERNEL_RBF) {
+    const float e = kf_exp2(r2 * (-0.5f * kKfLog2e));
+    *g = e;
+    *h = -e;
+  } else {
+    const float r2c = fminf(r2, kKfMaxR2);
+    const float r = __builtin_amdgcn_sqrtf(r2c);
+    if constexpr (FAMILY == LO_KERNEL_MATERN12) {
+      const float e = kf_exp2(r * -kKfLog2e);
+      *g = e;
+      *h = r2c > 1e-30f ? -e * __builtin_amdgcn_rsqf(r2c) : 0.0f;  // (below: h r^2 < 1e-15, and rsq of a denormal is inf)
+    } else if constexpr (FAMILY == LO_KERNEL_MATERN32) {
+      const float e = kf_exp2(r * (-kKfSqrt3 * kKfLog2e));
+      *g = fmaf(kKfSqrt3, r, 1.0f) * e;
+      *h = -3.0f * e;
+    } else {
+      const float e = kf_exp2(r * (-kKfSqrt5 * kKfLog2e));
+      *g = fmaf(5.0f / 3.0f, r2c, fmaf(kKfSqrt5, r, 1.0f)) * e;
+      *h = (-5.0f / 3.0f) * fmaf(kKfSqrt5, r, 1.0f) * e;
+    }
+  }
+}
+
+// the same with the family as a run-time value (row source of the pivoted Cholesky: one entry per thread)
+__device__ __forceinline__ float kf_g_rt(int family, float r2) {
+  switch (family) {
+    case LO_KERNEL_RBF: return kf_g<LO_KERNEL_RBF>(r2);
+    case LO_KERNEL_MATERN12: return kf_g<LO_KERNEL_MATERN12>(r2);
+    case LO_KERNEL_MATERN32: return kf_g<LO_KERNEL_MATERN32>(r2);
+    default: return kf_g<LO_KERNEL_MATERN52>(r2);
+  }
+}
+
+}  // namespace lo

@@ -150,6 +150,7 @@ int matvec_plan_init(MatvecPlan* pl, const lo_op_desc* op, lo_matvec_cb cb, void
     case LO_OP_SKI_GRID_DIAG: rc = ski_grid_plan(pl, ar, st); break;
     case LO_OP_TOEPLITZ_KRON_DIAG: rc = toeplitz_kron_plan(pl, ar, st); break;
     case LO_OP_HADAMARD_DIAG: rc = hadamard_plan(pl, ar, st); break;
+    case LO_OP_KERNEL_DIAG: rc = kernel_op_plan(pl, ar, st); break;
     case LO_OP_MASKED: rc = masked_plan(pl, ar, st); break;
     case LO_OP_CALLBACK: rc = cb ? LO_OK : LO_ERR_BADARG; break;
     case LO_OP_SUM: rc = sum_plan(pl, ar, st); break;
@@ -188,6 +189,8 @@ int matvec_run(const MatvecPlan* pl, const float* v, float* y, float* dot_part, 
       rc = toeplitz_kron_matvec_run(pl, v, y, stop, st); break;
     case LO_OP_HADAMARD_DIAG:  // (F F^T o G G^T) v + d o v: contraction M_t = F^T diag(v_t) G, expansion rowdot(F, G M_t^T)
       rc = hadamard_matvec_run(pl, v, y, stop, st); break;
+    case LO_OP_KERNEL_DIAG:  // K(X, X) v + d o v, K formed tile by tile from X (lo_kernel_op.hip)
+      rc = kernel_op_matvec_run(pl, v, y, stop, st); break;
     case LO_OP_MASKED:  // S (base) S^T v + d o v: expand, the base's product (or the selected rows of a dense base), gather
       rc = masked_matvec_run(pl, v, y, stop, st); break;
     case LO_OP_CALLBACK: rc = pl->cb(pl->cb_user, v, y, op.B, op.N, pl->c, (void*)st) ? LO_ERR_LAUNCH : LO_OK; break;
@@ -217,7 +220,7 @@ using namespace lo;
 
 extern "C" {
 
-int lo_abi_version(void) { return 25; }
+int lo_abi_version(void) { return 26; }
 const char* lo_target_arch(void) { return "gfx950"; }
 
 size_t lo_matvec_workspace_bytes(const lo_op_desc* op, int64_t c) {

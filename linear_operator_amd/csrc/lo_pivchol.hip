@@ -9,6 +9,8 @@
 //   Toeplitz:         row[i] = t[|p - i|]                    (toeplitz_linear_operator.py:38-40, diag :25-31)
 //   Toeplitz Kron:    row[i] = prod_k t_k[|p_k - i_k|]       (kronecker_product_linear_operator.py:198-216 over the
 //                                                            Toeplitz rows), the diagonal prod_k t_k[0] is constant
+//   Kernel:           row[i] = os2 g(|theta o (x_p - x_i)|), r^2 summed over d in ascending order; the diagonal os2 is
+//                                                            constant (kernel_linear_operator.py:230-246, :263-279)
 //   SKI:              row[i] = sum_b sum_a t[|li[p,a] - ri[i,b]|] (lv[p,a] rv[i,b])
 //                                                            (interpolated_linear_operator.py:130-144); the diagonal
 //                     is the reference's APPROXIMATE one, (W_l sqrt(t0)) o (W_r sqrt(t0)) (:94-101,
@@ -32,6 +34,7 @@
 #include <string.h>
 
 #include "lo_internal.h"
+#include "lo_kernel_fn.h"
 
 namespace lo {
 
@@ -127,6 +130,8 @@ __device__ __forceinline__ T src_diag(const PcDevT<T>& d, const lo_op_desc& op, 
     return seq_dot(fi, fi, (int)op.R) * seq_dot(gi, gi, (int)op.n2);
   } else if (op.kind == LO_OP_TOEPLITZ_DIAG) {
     return A0[(size_t)b * op.R];
+  } else if (op.kind == LO_OP_KERNEL_DIAG) {  // os2 g(0) = os2 (an fp32 kind: the operands are read as float)
+    return (T)op.A1[(size_t)b * (op.R + 1) + op.R];
   } else if (op.kind == LO_OP_TOEPLITZ_KRON_DIAG) {
     // prod_k t_k[0], the trailing factors multiplied first (kronecker_product_linear_operator.py:22-28)
     const int D = d.ski.grid_ndim;
@@ -450,6 +455,17 @@ __global__ __launch_bounds__(kThreads) void k_pc_update(PcDevT<T> d, int m) {
         } else if (tm.kind == LO_OP_TOEPLITZ_DIAG) {
           const int lag = pim > i ? pim - i : i - pim;
           tv = pc_ptr<T>(tm.A0)[(size_t)b * tm.R + lag];
+        } else if (tm.kind == LO_OP_KERNEL_DIAG) {  // (an fp32 kind: the operands are read as float)
+          const int D = (int)tm.R;
+          const float* th = tm.A1 + (size_t)b * (D + 1);
+          const float* xp = tm.A0 + ((size_t)b * N + pim) * D;
+          const float* xi = tm.A0 + ((size_t)b * N + i) * D;
+          float r2 = 0.0f;
+          for (int k = 0; k < D; ++k) {
+            const float df = xp[k] * th[k] - xi[k] * th[k];
+            r2 = r2 + df * df;
+          }
+          tv = (T)(th[D] * kf_g_rt((int)tm.n2, r2));
         } else if (tm.kind == LO_OP_TOEPLITZ_KRON_DIAG) {
           // prod_k t_k[|p_k - i_k|], factors multiplied left to right (kronecker_product_linear_operator.py:198-216);
           // consecutive threads hold consecutive positions j: the gathers from the (small) columns stay in cache
@@ -683,6 +699,9 @@ static int pc_check_desc(const lo_op_desc* op) {
     if (!op->A0 || !op->A1 || op->R < 1 || op->n2 < 1) return LO_ERR_BADARG;
   } else if (op->kind == LO_OP_TOEPLITZ_DIAG) {
     if (!op->A0 || op->R != op->N) return LO_ERR_BADARG;
+  } else if (op->kind == LO_OP_KERNEL_DIAG) {
+    if (!op->A0 || !op->A1 || op->R < 1 || op->n2 < LO_KERNEL_RBF || op->n2 > LO_KERNEL_MATERN52) return LO_ERR_BADARG;
+    if (op->R > LO_KERNEL_MAX_DIM) return LO_ERR_UNSUPPORTED;
   } else if (op->kind == LO_OP_SKI_DIAG) {
     const lo_interp_desc* w = op->interp;
     if (!op->A0 || op->R < 1 || op->n2 < 1 || !w || !w->left_idx || !w->left_vals || !w->right_idx || !w->right_vals)
@@ -779,7 +798,7 @@ int lo_pivoted_cholesky_f64(const lo_op_desc* op, int32_t max_rank, double error
                             int32_t* rank_out, void* ws, size_t ws_bytes, void* stream) {
   if (!op || !L_rows || !perm || !rank_out || !ws || max_rank < 1) return LO_ERR_BADARG;
   if (op->kind == LO_OP_SKI_DIAG || op->kind == LO_OP_TOEPLITZ_DIAG || op->kind == LO_OP_HADAMARD_DIAG ||
-      op->kind == LO_OP_SKI_GRID_DIAG || op->kind == LO_OP_TOEPLITZ_KRON_DIAG)
+      op->kind == LO_OP_SKI_GRID_DIAG || op->kind == LO_OP_TOEPLITZ_KRON_DIAG || op->kind == LO_OP_KERNEL_DIAG)
     return LO_ERR_UNSUPPORTED;  // (fp32 kinds)
   if (const int rc = pc_check_desc(op)) return rc;
   return pc_stream_t<double>(op, nullptr, nullptr, nullptr, max_rank, error_tol, L_rows, perm, rank_out, ws, ws_bytes,

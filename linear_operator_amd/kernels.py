@@ -27,7 +27,8 @@ class OperatorDescriptor:
     B: int
     N: int
     A0: Optional[torch.Tensor] = None  # C [B,N,R] | K [B,N,N] | K1 [B,n1,n1]
-    A1: Optional[torch.Tensor] = None  # K2 [B,n2,n2] | G [B,N,q] (Hadamard: A0 = F [B,N,p])
+    # K2 [B,n2,n2] | G [B,N,q] (Hadamard: A0 = F [B,N,p]) | theta [B,D+1] (Kernel: A0 = X [B,N,D], R = D, n2 = family)
+    A1: Optional[torch.Tensor] = None
     d: Optional[torch.Tensor] = None  # [B,N] (FULL) or [B] (CONST)
     diag_mode: int = _hip.LO_DIAG_NONE
     R: int = 0
@@ -473,6 +474,70 @@ def hadamard_diag_descriptor(F: torch.Tensor, G: torch.Tensor, d: Optional[torch
     F3, G3 = _flat(F, 2), _flat(G, 2)
     return _with_diag(OperatorDescriptor(_hip.LO_OP_HADAMARD_DIAG, F3.shape[0], N, A0=F3, A1=G3, R=p, n2=G.shape[-1],
                                          batch_shape=batch), d, const_diag)
+
+
+def kernel_theta(lengthscale: torch.Tensor, outputscale: torch.Tensor, batch, D: int) -> torch.Tensor:
+    """theta [B, D + 1] of the kernel entry points: the D inverse lengthscales (a shared one replicated), then
+    outputscale^2.  lengthscale [*b, 1, D] or [*b, 1, 1], outputscale [*b], both broadcast to `batch`."""
+    with torch.no_grad():
+        inv = (1.0 / lengthscale.detach()).expand(*batch, 1, D).reshape(-1, D)
+        os2 = torch.broadcast_to(outputscale.detach().square(), tuple(batch)).reshape(-1, 1)
+        return torch.cat((inv, os2), -1).to(torch.float32).contiguous()
+
+
+def kernel_diag_descriptor(X: torch.Tensor, theta: torch.Tensor, family: int, d: Optional[torch.Tensor] = None,
+                           const_diag: bool = False):
+    """AddedDiag(Kernel(X, X, family), Diag(d)) (or the kernel matrix alone): y = K(X, X) v + d o v with K formed on the
+    fly (csrc/lo_kernel_op.hip).  X [*batch, N, D], theta [B, D + 1] from kernel_theta.  None when D exceeds
+    LO_KERNEL_MAX_DIM (the caller evaluates covar_func)."""
+    _hip.require_hip(X, theta, d)
+    N, D = X.shape[-2:]
+    if D > _hip.LO_KERNEL_MAX_DIM or D < 1:
+        return None
+    X3 = _flat(X.detach(), 2)
+    if theta.shape != (X3.shape[0], D + 1):
+        raise RuntimeError(f"kernel_diag_descriptor: theta of shape {tuple(theta.shape)} for X {tuple(X.shape)}")
+    return _with_diag(OperatorDescriptor(_hip.LO_OP_KERNEL_DIAG, X3.shape[0], N, A0=X3, A1=theta, R=D, n2=int(family),
+                                         batch_shape=X.shape[:-2]), d, const_diag)
+
+
+def kernel_mv(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, family: int, v: torch.Tensor,
+              d: Optional[torch.Tensor] = None, const_diag: bool = False) -> torch.Tensor:
+    """lo_kernel_mv_f32: y [B, M, c] = K(x1, x2) v (+ d o v when M == N and d is given), x1 [B, M, D], x2 [B, N, D],
+    theta [B, D + 1], v [B, N, c].  A shape the kernel does not take raises."""
+    lib = _hip.load()
+    x1, x2, theta, v = x1.contiguous(), x2.contiguous(), theta.contiguous(), v.contiguous()
+    _hip.require_hip(x1, x2, theta, v, d)
+    B, M, D = x1.shape
+    N, c = v.shape[-2:]
+    if x2.shape != (B, N, D) or theta.shape != (B, D + 1) or v.shape[0] != B:
+        raise RuntimeError(f"kernel_mv: x1 {tuple(x1.shape)}, x2 {tuple(x2.shape)}, theta {tuple(theta.shape)}, "
+                           f"v {tuple(v.shape)}")
+    mode = _hip.LO_DIAG_NONE
+    if d is not None:
+        d, mode, _ = _diag_operand(d, B, N, const_diag)
+    y = torch.empty(B, M, c, dtype=torch.float32, device=v.device)
+    _launch("lo_kernel_mv_f32", v.device, x1, x2, theta, int(family), B, M, N, D, v, c, d, mode, y,
+            ws_bytes=lib.lo_kernel_mv_workspace_bytes(B, M, N, D, c))
+    return y
+
+
+def kernel_bilinear(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, family: int, U: torch.Tensor,
+                    V: torch.Tensor) -> torch.Tensor:
+    """lo_kernel_bilinear_f32: g_theta [B, D + 1], the derivative of sum_s u_s^T K(x1, x2) v_s with respect to theta
+    (the inverse lengthscales, then outputscale^2).  x1 [B, M, D], x2 [B, N, D], U [B, M, t], V [B, N, t]."""
+    lib = _hip.load()
+    x1, x2, theta, U, V = (t.contiguous() for t in (x1, x2, theta, U, V))
+    _hip.require_hip(x1, x2, theta, U, V)
+    B, M, D = x1.shape
+    N, t = V.shape[-2:]
+    if x2.shape != (B, N, D) or theta.shape != (B, D + 1) or U.shape != (B, M, t) or V.shape[0] != B:
+        raise RuntimeError(f"kernel_bilinear: x1 {tuple(x1.shape)}, x2 {tuple(x2.shape)}, theta {tuple(theta.shape)}, "
+                           f"U {tuple(U.shape)}, V {tuple(V.shape)}")
+    g = torch.empty(B, D + 1, dtype=torch.float32, device=U.device)
+    _launch("lo_kernel_bilinear_f32", U.device, x1, x2, theta, int(family), B, M, N, D, U, V, t, g,
+            ws_bytes=lib.lo_kernel_bilinear_workspace_bytes(B, M, N, D, t))
+    return g
 
 
 _MASK_BASE_KINDS = (_hip.LO_OP_LOWRANK_DIAG, _hip.LO_OP_DENSE_DIAG, _hip.LO_OP_KRON_DIAG, _hip.LO_OP_SUM)

@@ -23,6 +23,7 @@ from .block_diag_linear_operator import BlockDiagLinearOperator
 from .block_interleaved_linear_operator import BlockInterleavedLinearOperator
 from .sum_batch_linear_operator import SumBatchLinearOperator
 from .masked_linear_operator import MaskedLinearOperator
+from .kernel_linear_operator import KernelLinearOperator
 
 __all__ = [
     "LowRankRootAddedDiagLinearOperator", "KroneckerProductAddedDiagLinearOperator",
@@ -32,5 +33,5 @@ __all__ = [
     "PsdSumLinearOperator", "TriangularLinearOperator", "MatmulLinearOperator", "InterpolatedLinearOperator",
     "ToeplitzLinearOperator", "ConstantMulLinearOperator", "MulLinearOperator", "CholLinearOperator",
     "BlockLinearOperator", "BlockDiagLinearOperator", "BlockInterleavedLinearOperator", "SumBatchLinearOperator",
-    "MaskedLinearOperator", "SumKroneckerLinearOperator",
+    "MaskedLinearOperator", "SumKroneckerLinearOperator", "KernelLinearOperator",
 ]

@@ -1,0 +1,332 @@
+"""KernelLinearOperator: the covariance matrix K(x1, x2) of a kernel function held as its inputs -- the points and the
+hyperparameters, N D numbers instead of N^2 (the reference's operators/kernel_linear_operator.py, same constructor and
+results).  `covar_func(x1, x2, **params)` may be any callable; it is evaluated densely whenever the matrix itself is
+needed (the general path, as in the reference, on any device and in any dtype).
+
+Native path.  When `covar_func` carries a `native_family` (linear_operator_amd.covariance: rbf, matern12, matern32,
+matern52), there is one output per input, the tensors are float32 on the device, D <= LO_KERNEL_MAX_DIM and the
+parameters are exactly `lengthscale` [*b, 1, D] or [*b, 1, 1] and `outputscale` [*b], the matrix is NEVER formed:
+
+  _matmul / _t_matmul   the on-the-fly product lo_kernel_mv_f32 (csrc/lo_kernel_op.hip), rectangular x1 / x2 included
+  _kernel_descriptor    x1 and x2 the same points: the kind LO_OP_KERNEL_DIAG, so that AddedDiag(Kernel, Diag) runs CG,
+                        Lanczos, MINRES and the pivoted Cholesky on the device with no Python call per iteration
+  _diagonal             outputscale^2, no launch;  _get_indices / _get_rows evaluate only the requested entries
+  _bilinear_derivative  lengthscale and outputscale from lo_kernel_bilinear_f32; the points' gradients, when asked for, by
+                        autograd through covar_func on row chunks of at most MAX_DENSE_CHUNK_BYTES
+
+Anything outside that gate (D > 32, float64, CPU, several outputs per input, other parameters) takes the general path.
+"""
+from __future__ import annotations
+
+from collections import defaultdict
+from typing import Callable, Optional
+
+import torch
+from torch import Tensor
+
+from ._linear_operator import LinearOperator, to_dense
+
+# The points' gradients on the native path differentiate covar_func on blocks of rows; a block's [rows, N, D] differences
+# (the largest intermediate of the covariance functions) stay below this many bytes, so the whole of K never exists.
+MAX_DENSE_CHUNK_BYTES = 64 * 1024 * 1024
+
+_NOOP = slice(None, None, None)
+
+
+def _two():
+    return 2
+
+
+def _same_tensor(a: Tensor, b: Tensor) -> bool:
+    return a is b or (a.data_ptr() == b.data_ptr() and a.shape == b.shape and a.stride() == b.stride()
+                      and a.dtype == b.dtype and a.device == b.device)
+
+
+class KernelLinearOperator(LinearOperator):
+    def __init__(self, x1: Tensor, x2: Tensor, covar_func: Callable, num_outputs_per_input=(1, 1),
+                 num_nonbatch_dimensions: Optional[dict] = None, **params):
+        nonbatch = defaultdict(_two)
+        if num_nonbatch_dimensions is not None:
+            nonbatch.update(num_nonbatch_dimensions)
+        tensor_params = {k: v for k, v in params.items() if torch.is_tensor(v)}
+        other_params = {k: v for k, v in params.items() if not torch.is_tensor(v)}
+        batch_of, tail_of = {}, {}
+        for name, val in tensor_params.items():
+            nb = nonbatch[name]
+            batch_of[name] = val.shape[: val.dim() - nb] if nb else val.shape
+            tail_of[name] = val.shape[val.dim() - nb:] if nb else torch.Size([])
+        try:
+            batch = torch.broadcast_shapes(x1.shape[:-2], x2.shape[:-2], *batch_of.values())
+        except RuntimeError:
+            try:  # the data alone: batch dimensions and the number of input dimensions
+                torch.broadcast_shapes(torch.Size([*x1.shape[:-2], 1, x1.shape[-1]]),
+                                       torch.Size([*x2.shape[:-2], 1, x2.shape[-1]]))
+            except RuntimeError:
+                raise RuntimeError(
+                    "Incompatible data shapes for a kernel matrix: "
+                    f"x1.shape={tuple(x1.shape)}, x2.shape={tuple(x2.shape)}."
+                )
+            raise RuntimeError(
+                "Shape of kernel parameters "
+                f"({', '.join([str(tuple(param.shape)) for param in tensor_params.values()])}) "
+                f"is incompatible with data shapes x1.shape={tuple(x1.shape)}, x2.shape={tuple(x2.shape)}.\n"
+                "Recall that parameters passed to KernelLinearOperator should have dimensionality compatible "
+                "with the data (see documentation)."
+            )
+        if len(batch):  # every tensor carries the whole batch shape from here on
+            same = _same_tensor(x1, x2)
+            if x1.shape[:-2] != batch:
+                x1 = x1.expand(*batch, *x1.shape[-2:]).contiguous()
+            x2 = x1 if same else (x2 if x2.shape[:-2] == batch else x2.expand(*batch, *x2.shape[-2:]).contiguous())
+            tensor_params = {name: (val if batch_of[name] == batch else val.expand(*batch, *tail_of[name]))
+                             for name, val in tensor_params.items()}
+        super().__init__(x1, x2, covar_func=covar_func, num_outputs_per_input=num_outputs_per_input,
+                         num_nonbatch_dimensions=nonbatch, **tensor_params, **other_params)
+        self.batch_broadcast_shape = torch.Size(batch)
+        self.x1, self.x2 = x1, x2
+        self.tensor_params, self.nontensor_params = tensor_params, other_params
+        self.covar_func = covar_func
+        self.num_outputs_per_input = tuple(num_outputs_per_input)
+        self.num_nonbatch_dimensions = nonbatch
+
+    def _rebuild(self, x1, x2, tensor_params):
+        return self.__class__(x1, x2, covar_func=self.covar_func, num_outputs_per_input=self.num_outputs_per_input,
+                              num_nonbatch_dimensions=self.num_nonbatch_dimensions, **tensor_params,
+                              **self.nontensor_params)
+
+    # ------------------------------------------------------------------ the gate of the native path
+    def _native_refusal(self, check_device: bool = True) -> Optional[str]:
+        """None when the native kernels take this operator, else the reason they do not.  `check_device=False` leaves
+        out the float32-on-the-device condition (what the rest of the gate decides can then be asked on any machine)."""
+        from .. import _hip
+
+        if getattr(self.covar_func, "native_family", None) is None:
+            return "covar_func has no native_family"
+        if self.num_outputs_per_input != (1, 1):
+            return "more than one output per input"
+        if self.nontensor_params or set(self.tensor_params) != {"lengthscale", "outputscale"}:
+            return "parameters other than lengthscale and outputscale"
+        D = self.x1.shape[-1]
+        if D > _hip.LO_KERNEL_MAX_DIM or D < 1 or self.x2.shape[-1] != D:
+            return f"D = {D} beyond LO_KERNEL_MAX_DIM"
+        ls, os_ = self.tensor_params["lengthscale"], self.tensor_params["outputscale"]
+        batch = self.batch_broadcast_shape
+        if self.num_nonbatch_dimensions["lengthscale"] != 2 or ls.shape not in ((*batch, 1, D), (*batch, 1, 1)):
+            return f"lengthscale of shape {tuple(ls.shape)}"
+        if self.num_nonbatch_dimensions["outputscale"] != 0 or os_.shape != batch:
+            return f"outputscale of shape {tuple(os_.shape)}"
+        tensors = (self.x1, self.x2, ls, os_)
+        if any(t.dtype != torch.float32 for t in tensors):
+            return "not float32"
+        if check_device and not all(t.is_cuda for t in tensors):
+            return "not on the device"
+        return None
+
+    def _is_native(self) -> bool:
+        return self._native_refusal() is None
+
+    def _same_points(self) -> bool:
+        return _same_tensor(self.x1, self.x2)
+
+    def _theta(self, batch):
+        from .. import kernels as K
+
+        return K.kernel_theta(self.tensor_params["lengthscale"], self.tensor_params["outputscale"], batch,
+                              self.x1.shape[-1])
+
+    def _kernel_descriptor(self, batch_shape=None):
+        if not (self._is_native() and self._same_points()):
+            return None
+        from .. import kernels as K
+
+        bs = torch.Size(self.batch_shape if batch_shape is None else batch_shape)
+        X = self.x1.detach()
+        X = X if X.shape[:-2] == bs else X.expand(*bs, *X.shape[-2:])
+        return K.kernel_diag_descriptor(X, self._theta(bs), self.covar_func.native_family)
+
+    # ------------------------------------------------------------------ dense evaluation (the general path)
+    def _dense_covar(self):
+        """covar_func on all of x1 and x2: the [*batch, M, N] matrix (or operator).  The native path never calls it."""
+        return self.covar_func(self.x1, self.x2, **self.tensor_params, **self.nontensor_params)
+
+    @property
+    def covar_mat(self):
+        return self._dense_covar()
+
+    def to_dense(self) -> Tensor:
+        return to_dense(self._dense_covar())
+
+    # ------------------------------------------------------------------ operator protocol
+    def _size(self) -> torch.Size:
+        p, q = self.num_outputs_per_input
+        return torch.Size([*self.batch_broadcast_shape, self.x1.shape[-2] * p, self.x2.shape[-2] * q])
+
+    def _transpose_nonbatch(self):
+        return self._rebuild(self.x2, self.x1, self.tensor_params)
+
+    def _matmul(self, rhs: Tensor) -> Tensor:
+        vec = rhs.dim() == 1
+        cols = rhs.unsqueeze(-1) if vec else rhs
+        if cols.is_cuda and cols.dtype == torch.float32 and self._is_native():
+            from .. import kernels as K
+
+            M, D = self.x1.shape[-2:]
+            N, c = cols.shape[-2:]
+            bs = torch.broadcast_shapes(self.batch_shape, cols.shape[:-2])
+            x1 = self.x1.detach().expand(*bs, M, D).reshape(-1, M, D)
+            x2 = x1 if self._same_points() else self.x2.detach().expand(*bs, N, D).reshape(-1, N, D)
+            y = K.kernel_mv(x1, x2, self._theta(bs), self.covar_func.native_family,
+                            cols.detach().expand(*bs, N, c).reshape(-1, N, c))
+            y = y.reshape(*bs, M, c)
+        else:
+            y = self._dense_covar() @ cols.contiguous()
+        return y[..., 0] if vec else y
+
+    def _expand_batch(self, batch_shape):
+        batch_shape = torch.Size(batch_shape)
+        x1 = self.x1.expand(*batch_shape, *self.x1.shape[-2:])
+        x2 = x1 if self._same_points() else self.x2.expand(*batch_shape, *self.x2.shape[-2:])
+        params = {}
+        for name, val in self.tensor_params.items():
+            nb = self.num_nonbatch_dimensions[name]
+            params[name] = val.expand(*batch_shape, *(val.shape[val.dim() - nb:] if nb else ()))
+        return self._rebuild(x1, x2, params)
+
+    def _permute_batch(self, *dims: int):
+        x1 = self.x1.permute(*dims, -2, -1)
+        x2 = x1 if self._same_points() else self.x2.permute(*dims, -2, -1)
+        params = {name: val.permute(*dims, *range(len(dims), val.dim())) for name, val in self.tensor_params.items()}
+        return self._rebuild(x1, x2, params)
+
+    def _unsqueeze_batch(self, dim: int):
+        x1 = self.x1.unsqueeze(dim)
+        x2 = x1 if self._same_points() else self.x2.unsqueeze(dim)
+        return self._rebuild(x1, x2, {name: val.unsqueeze(dim) for name, val in self.tensor_params.items()})
+
+    # ------------------------------------------------------------------ entries
+    def _diagonal(self) -> Tensor:
+        p, q = self.num_outputs_per_input
+        n = self.x1.shape[-2]
+        if self._native_refusal(check_device=False) is None and self._same_points():
+            # g(0) = 1 for every native family: the diagonal is outputscale^2, no kernel launch
+            return self.tensor_params["outputscale"].square().unsqueeze(-1).expand(*self.batch_broadcast_shape, n)
+        # the pairs (x1_i, x2_i) as a leading batch dimension of 1 x 1 (or p x q) kernel matrices
+        a = self.x1.movedim(-2, 0).unsqueeze(-2)
+        b = self.x2.movedim(-2, 0).unsqueeze(-2)
+        params = {name: val.unsqueeze(0) for name, val in self.tensor_params.items()}
+        blocks = to_dense(self.covar_func(a, b, **params, **self.nontensor_params)).movedim(0, -3)  # [*b, n, p, q]
+        assert blocks.shape[-2:] == torch.Size((p, q))
+        if (p, q) == (1, 1):
+            return blocks[..., 0, 0]
+        return blocks.diagonal(dim1=-2, dim2=-1).reshape(*blocks.shape[:-3], -1)
+
+    def _get_indices(self, row_index: Tensor, col_index: Tensor, *batch_indices: Tensor) -> Tensor:
+        p, q = self.num_outputs_per_input
+        shape = torch.broadcast_shapes(row_index.shape, col_index.shape, *(i.shape for i in batch_indices))
+        row = row_index.expand(shape).reshape(-1)
+        col = col_index.expand(shape).reshape(-1)
+        bidx = tuple(i.expand(shape).reshape(-1) for i in batch_indices)
+        # one 1 x 1 (or p x q) kernel matrix per requested entry: only those entries are evaluated
+        a = self.x1[(*bidx, row.div(p, rounding_mode="floor"))].unsqueeze(-2)
+        b = self.x2[(*bidx, col.div(q, rounding_mode="floor"))].unsqueeze(-2)
+        params = {name: val[bidx] for name, val in self.tensor_params.items()}
+        blocks = to_dense(self.covar_func(a, b, **params, **self.nontensor_params))
+        assert blocks.shape[-2:] == torch.Size((p, q))
+        if (p, q) == (1, 1):
+            return blocks[..., 0, 0].reshape(shape)
+        lead = blocks.reshape(-1, p, q)
+        pick = torch.arange(lead.shape[0], device=lead.device)
+        return lead[pick, (row % p).expand(lead.shape[0]), (col % q).expand(lead.shape[0])].reshape(shape)
+
+    def _getitem(self, row_index, col_index, *batch_indices):
+        if self.num_outputs_per_input != (1, 1):
+            return super()._getitem(row_index, col_index, *batch_indices)  # (indexed densely)
+        x1 = self.x1[(*batch_indices, row_index, _NOOP)]
+        same = self._same_points() and isinstance(row_index, slice) and row_index == col_index
+        x2 = x1 if same else self.x2[(*batch_indices, col_index, _NOOP)]
+        params = {name: val[(*batch_indices, *([_NOOP] * self.num_nonbatch_dimensions[name]))]
+                  for name, val in self.tensor_params.items()}
+        return self._rebuild(x1, x2, params)
+
+    # ------------------------------------------------------------------ derivatives
+    def _bilinear_derivative(self, left_vecs: Tensor, right_vecs: Tensor):
+        """d / d(x1, x2, parameters in sorted order) of sum_s u_s^T K v_s; None for a tensor that asks for no gradient."""
+        if left_vecs.dim() == 1:
+            left_vecs, right_vecs = left_vecs.unsqueeze(-1), right_vecs.unsqueeze(-1)
+        names = list(self._differentiable_kwargs)
+        if left_vecs.is_cuda and left_vecs.dtype == torch.float32 and self._is_native():
+            return self._bilinear_derivative_native(left_vecs, right_vecs, names)
+        tensors = [self.x1, self.x2] + [self.tensor_params[n] for n in names]
+        leaves = [t.detach().requires_grad_(True) if t.requires_grad and t.dtype.is_floating_point else t.detach()
+                  for t in tensors]
+        need = [t for t in leaves if t.requires_grad]
+        if not need:
+            return (None,) * len(tensors)
+        with torch.enable_grad():
+            dense = to_dense(self.covar_func(leaves[0], leaves[1], **dict(zip(names, leaves[2:])),
+                                             **self.nontensor_params))
+            loss = (left_vecs * (dense @ right_vecs)).sum()
+            grads = list(torch.autograd.grad(loss, need, allow_unused=True))
+        return tuple(grads.pop(0) if t.requires_grad else None for t in leaves)
+
+    def _bilinear_derivative_native(self, left_vecs: Tensor, right_vecs: Tensor, names):
+        from .. import kernels as K
+
+        ls, os_ = self.tensor_params["lengthscale"], self.tensor_params["outputscale"]
+        M, D = self.x1.shape[-2:]
+        N, t = right_vecs.shape[-2:]
+        bs = torch.broadcast_shapes(self.batch_shape, left_vecs.shape[:-2], right_vecs.shape[:-2])
+        out = {"x1": None, "x2": None, "lengthscale": None, "outputscale": None}
+        if ls.requires_grad or os_.requires_grad:
+            x1 = self.x1.detach().expand(*bs, M, D).reshape(-1, M, D)
+            x2 = x1 if self._same_points() else self.x2.detach().expand(*bs, N, D).reshape(-1, N, D)
+            theta = self._theta(bs)
+            U = left_vecs.detach().expand(*bs, M, t).reshape(-1, M, t)
+            V = right_vecs.detach().expand(*bs, N, t).reshape(-1, N, t)
+            g = K.kernel_bilinear(x1, x2, theta, self.covar_func.native_family, U, V)  # [B, D + 1], d / d theta
+            if ls.requires_grad:  # theta_d = 1 / l_d: d / d l_d = -theta_d^2 d / d theta_d; a shared l sums over d
+                d_ls = (-(theta[:, :D] ** 2) * g[:, :D]).reshape(*bs, 1, D)
+                if ls.shape[-1] == 1 and D > 1:
+                    d_ls = d_ls.sum(-1, keepdim=True)
+                out["lengthscale"] = d_ls.sum_to_size(ls.shape)
+            if os_.requires_grad:  # theta_D = os^2: d / d os = 2 os d / d theta_D
+                out["outputscale"] = (2.0 * torch.broadcast_to(os_.detach(), tuple(bs)) * g[:, D].reshape(tuple(bs))).sum_to_size(os_.shape)
+        if self.x1.requires_grad or self.x2.requires_grad:
+            out["x1"], out["x2"] = self._points_derivative_chunked(left_vecs, right_vecs, bs)
+        return (out["x1"], out["x2"]) + tuple(out[n] for n in names)
+
+    def _points_derivative_chunked(self, left_vecs: Tensor, right_vecs: Tensor, bs):
+        """Gradients of sum_s u_s^T K v_s with respect to x1 and x2 by autograd through covar_func on blocks of rows of
+        at most MAX_DENSE_CHUNK_BYTES (the native kernels do not differentiate the points)."""
+        M, D = self.x1.shape[-2:]
+        N = self.x2.shape[-2]
+        want1, want2 = self.x1.requires_grad, self.x2.requires_grad
+        x1 = self.x1.detach().expand(*bs, M, D)
+        x2 = self.x2.detach().expand(*bs, N, D)
+        params = {n: v.detach() for n, v in self.tensor_params.items()}
+        per_row = max(1, bs.numel()) * N * max(D, 1) * x1.element_size()
+        rows = max(1, min(M, MAX_DENSE_CHUNK_BYTES // per_row))
+        g1 = torch.zeros_like(x1) if want1 else None
+        g2 = torch.zeros_like(x2) if want2 else None
+        U = left_vecs.detach().expand(*bs, M, left_vecs.shape[-1])
+        V = right_vecs.detach().expand(*bs, N, right_vecs.shape[-1])
+        for lo in range(0, M, rows):
+            hi = min(M, lo + rows)
+            with torch.enable_grad():
+                a = x1[..., lo:hi, :].clone().requires_grad_(want1)
+                b = x2.clone().requires_grad_(want2)
+                block = to_dense(self.covar_func(a, b, **params, **self.nontensor_params))  # [*bs, hi - lo, N]
+                loss = (U[..., lo:hi, :] * (block @ V)).sum()
+                grads = list(torch.autograd.grad(loss, [t for t in (a, b) if t.requires_grad]))
+            if want1:
+                g1[..., lo:hi, :] = grads.pop(0)
+            if want2:
+                g2 += grads.pop(0)
+        if want1:
+            g1 = g1.sum_to_size(self.x1.shape)
+        if want2:
+            g2 = g2.sum_to_size(self.x2.shape)
+        return g1, g2
+
+
+__all__ = ["KernelLinearOperator", "MAX_DENSE_CHUNK_BYTES"]
