@@ -865,7 +865,7 @@ int lo_hadamard_bilinear_f32(const float* F, const float* G, const float* U, con
                              int64_t p, int64_t q, int64_t S, float* dF, float* dG, void* ws, size_t ws_bytes,
                              void* stream);
 
-/* ---- matrix-free kernel operator (ABI 26; csrc/lo_kernel_op.hip) ---------------------------------------------------------
+/* ---- matrix-free kernel operator (ABI 26, 27; csrc/lo_kernel_op.hip) -------------------------------------------------
  * K(x1, x2)_ij = theta[D] g(r_ij), r_ij^2 = sum_d (theta[d] (x1[i, d] - x2[j, d]))^2 by direct differences, g one of
  * LO_KERNEL_*; x1 [B, M, D], x2 [B, N, D], theta [B, D + 1] = D inverse lengthscales, then outputscale^2.  K is never in
  * memory: a workgroup owns 256 rows (scaled once, kept in registers with their accumulators) and streams tiles of the
@@ -878,6 +878,12 @@ int lo_hadamard_bilinear_f32(const float* F, const float* G, const float* U, con
  *                           V [B, N, t]: for d < D  sum_ij W_ij theta[D] (g'(r) / r) (theta[d] delta_d)^2 / theta[d], last
  *                           entry sum_ij W_ij g(r).  A pair with r = 0 adds nothing to the first D entries for every
  *                           family (no division by r).  One partial per workgroup, added in ascending order.
+ *   lo_kernel_points_grad_f32 (ABI 27)  g_x1 [B, M, D] = d / d x1 of the same sum with x2 held fixed:
+ *                           g_x1[i, d] = theta[D] theta[d] sum_j W_ij (g'(r_ij) / r_ij) theta[d] (x1[i, d] - x2[j, d]).
+ *                           A thread owns a row i and sums over j in the product's order (tile, then running); a pair
+ *                           with r = 0 adds nothing.  The x2 side is the same call with the roles swapped (x1 <-> x2,
+ *                           U <-> V, M <-> N); when x1 and x2 are one tensor the caller adds the two.  Few rows: the
+ *                           columns j are split as in the product, partials [js, B, M, D] in ws, added in ascending order.
  * Fixed-order sums, no float atomics: the same inputs give the same bits.  LO_ERR_BADARG: null pointers, non-positive
  * sizes, an unknown family; LO_ERR_UNSUPPORTED: D > LO_KERNEL_MAX_DIM; LO_ERR_WORKSPACE (before any launch): ws smaller
  * than the _workspace_bytes query (0: arguments that are not taken).  y must not alias v.                               */
@@ -889,6 +895,10 @@ size_t lo_kernel_bilinear_workspace_bytes(int64_t B, int64_t M, int64_t N, int64
 int lo_kernel_bilinear_f32(const float* x1, const float* x2, const float* theta, int32_t family, int64_t B, int64_t M,
                            int64_t N, int64_t D, const float* U, const float* V, int64_t t, float* g_theta, void* ws,
                            size_t ws_bytes, void* stream);
+size_t lo_kernel_points_grad_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t D, int64_t t);
+int lo_kernel_points_grad_f32(const float* x1, const float* x2, const float* theta, int32_t family, int64_t B, int64_t M,
+                              int64_t N, int64_t D, const float* U, const float* V, int64_t t, float* g_x1, void* ws,
+                              size_t ws_bytes, void* stream);
 
 /* ---- exact small-N path: batched Cholesky and triangular solves (ABI 18; csrc/lo_chol.hip) -------------------------
  * fp32, contiguous row-major, N <= 1024 (larger: LO_ERR_UNSUPPORTED), stream-ordered; fixed-order sums, no atomics: a

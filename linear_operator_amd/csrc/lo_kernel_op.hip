@@ -1,5 +1,5 @@
 // lo_kernel_op.hip -- the matrix-free kernel operator K(x1, x2)_ij = os2 g(|(x1_i - x2_j) / l|), LO_OP_KERNEL_DIAG and the
-// entry points lo_kernel_mv_f32 / lo_kernel_bilinear_f32 of lo_amd.h (kernel_linear_operator.py:379-383 of the reference
+// entry points lo_kernel_mv_f32 / lo_kernel_bilinear_f32 / lo_kernel_points_grad_f32 of lo_amd.h (kernel_linear_operator.py:379-383 of the reference
 // evaluates covar_func densely inside _matmul; here K is never in memory).
 //
 // Product (k_kernel_mv): a workgroup owns 256 rows i of one member, one per thread.  The thread scales its point once,
@@ -15,6 +15,9 @@
 // Derivative (k_kernel_bil): the same sweep with W_ij = sum_s U[i, s] V[j, s] (8 columns s per sweep) in place of v, the
 //   thread accumulating sum_j W_ij h(r) (a_d - b_d)^2 per dimension and sum_j W_ij g(r); one partial per workgroup by a
 //   fixed-order block sum, k_kernel_bil_reduce adds them in ascending order.  No float atomics anywhere.
+// Points (k_kernel_pgrad, lo_kernel_points_grad_f32): the same sweep once more, the thread accumulating
+//   sum_j W_ij h(r) (a_d - b_d) per dimension for ITS row -- d / d x1[i, d] up to the factor theta_D theta_d; no sum across
+//   threads.  The x2 side is the same kernel with the roles of x1 / x2 and U / V swapped.  Split columns as in the product.
 #include <algorithm>
 
 #include "lo_device.h"
@@ -249,6 +252,78 @@ __global__ __launch_bounds__(64) void k_kernel_bil_reduce(const float* __restric
   g_theta[b * (D + 1) + q] = s;
 }
 
+// Gradient of the points x1: grid (row blocks, B, js), the sweep of k_kernel_bil with the accumulation
+//   g[b, i, k] = theta_D theta_k sum_j W_ij h(r_ij) s_k,  s = theta o (x1_i - x2_j)
+// A thread owns row i: nothing is reduced across threads.  `out` is g_x1 [B, M, D] when gridDim.z == 1, else the
+// partials [js, B, M, D] of the column splits (the scale is applied here; k_kernel_mv_reduce only adds).
+template <int FAMILY, int DP>
+__global__ __launch_bounds__(kThreads) void k_kernel_pgrad(const float* __restrict__ x1, const float* __restrict__ x2,
+                                                           const float* __restrict__ theta, int M, int N, int D,
+                                                           const float* __restrict__ U, const float* __restrict__ V,
+                                                           int t, float* __restrict__ out, int jchunk) {
+  __shared__ __align__(16) float xs[kKoTJ * DP];
+  __shared__ __align__(16) float vs[kKoTJ * kKoTS];
+  __shared__ float th[DP];
+  const int64_t b = blockIdx.y;
+  const int i = blockIdx.x * kThreads + threadIdx.x;
+  const bool live = i < M;
+  if (threadIdx.x < DP) th[threadIdx.x] = (int)threadIdx.x < D ? theta[b * (D + 1) + threadIdx.x] : 0.0f;
+  __syncthreads();
+  float a[DP], acc[DP];
+#pragma unroll
+  for (int k = 0; k < DP; ++k) {
+    a[k] = (live && k < D) ? x1[((size_t)b * M + i) * D + k] * th[k] : 0.0f;
+    acc[k] = 0.0f;
+  }
+  const float os2 = theta[b * (D + 1) + D];
+  const float* x2b = x2 + (size_t)b * N * D;
+  const float* Vb = V + (size_t)b * N * t;
+  const int j0 = blockIdx.z * jchunk, j1 = min(N, j0 + jchunk);
+  for (int s0 = 0; s0 < t; s0 += kKoTS) {
+    float u[kKoTS];
+#pragma unroll
+    for (int ss = 0; ss < kKoTS; ++ss) u[ss] = (live && s0 + ss < t) ? U[((size_t)b * M + i) * t + s0 + ss] : 0.0f;
+    for (int jt = j0; jt < j1; jt += kKoTJ) {
+      const int nj = min(kKoTJ, j1 - jt);
+      __syncthreads();  // (the previous tile has been read)
+      ko_stage_points<DP>(x2b, th, D, jt, nj, xs);
+      for (int e = threadIdx.x; e < nj * kKoTS; e += kThreads) {
+        const int j = e / kKoTS, ss = e - j * kKoTS;
+        vs[e] = s0 + ss < t ? Vb[(size_t)(jt + j) * t + s0 + ss] : 0.0f;
+      }
+      __syncthreads();
+      float tacc[DP];  // (a tile's sums on their own, then added to the running ones, as in the product)
+#pragma unroll
+      for (int k = 0; k < DP; ++k) tacc[k] = 0.0f;
+      for (int j = 0; j < nj; ++j) {
+        float sd[DP];
+        float r2 = 0.0f;
+#pragma unroll
+        for (int k = 0; k < DP; ++k) {
+          sd[k] = a[k] - xs[j * DP + k];
+          r2 = fmaf(sd[k], sd[k], r2);
+        }
+        float g, h;
+        kf_gh<FAMILY>(r2, &g, &h);
+        float w = 0.0f;
+#pragma unroll
+        for (int ss = 0; ss < kKoTS; ++ss) w = fmaf(u[ss], vs[j * kKoTS + ss], w);
+        const float wh = w * h;
+#pragma unroll
+        for (int k = 0; k < DP; ++k) tacc[k] = fmaf(wh, sd[k], tacc[k]);
+      }
+#pragma unroll
+      for (int k = 0; k < DP; ++k) acc[k] += tacc[k];
+    }
+  }
+  if (live) {
+    float* o = out + ((size_t)blockIdx.z * gridDim.y * M + (size_t)b * M + i) * D;
+#pragma unroll
+    for (int k = 0; k < DP; ++k)
+      if (k < D) o[k] = os2 * th[k] * acc[k];
+  }
+}
+
 static int ko_padded_dim(int64_t D) { return D <= 4 ? 4 : (D <= 8 ? 8 : (D <= 16 ? 16 : 32)); }
 static int ko_col_chunk(int64_t c) { return c == 1 ? 1 : (c <= 4 ? 4 : 16); }
 
@@ -298,6 +373,20 @@ static void ko_bil_launch_dp(int DP, dim3 grid, hipStream_t st, const float* x1,
     default: KO_BIL(32); break;
   }
 #undef KO_BIL
+}
+
+template <int FAMILY>
+static void ko_pgrad_launch_dp(int DP, dim3 grid, hipStream_t st, const float* x1, const float* x2, const float* theta,
+                               int M, int N, int D, const float* U, const float* V, int t, float* out, int jchunk) {
+#define KO_PG(DP_) \
+  hipLaunchKernelGGL((k_kernel_pgrad<FAMILY, DP_>), grid, dim3(kThreads), 0, st, x1, x2, theta, M, N, D, U, V, t, out, jchunk)
+  switch (DP) {
+    case 4: KO_PG(4); break;
+    case 8: KO_PG(8); break;
+    case 16: KO_PG(16); break;
+    default: KO_PG(32); break;
+  }
+#undef KO_PG
 }
 
 // the product on validated arguments; part: [js, B, M, c] floats when ko_shape(B, M, N).js > 1 (else unused)
@@ -360,6 +449,12 @@ static float* ko_bil_layout(Arena& ar, int64_t B, int64_t M, int64_t N, int64_t 
   return ar.take<float>((size_t)B * s.rb * s.js * (ko_padded_dim(D) + 1));
 }
 
+// the one layout of the points' gradient: the partials [js, B, M, D] of a split member
+static float* ko_pgrad_layout(Arena& ar, int64_t B, int64_t M, int64_t N, int64_t D) {
+  const KoShape s = ko_shape(B, M, N);
+  return s.js > 1 ? ar.take<float>((size_t)s.js * B * M * D) : nullptr;
+}
+
 }  // namespace lo
 
 using namespace lo;
@@ -416,6 +511,48 @@ int lo_kernel_bilinear_f32(const float* x1, const float* x2, const float* theta,
   hipLaunchKernelGGL(k_kernel_bil_reduce, dim3((unsigned)B), dim3(64), 0, st, part, s.rb * s.js, DP, (int)D, theta,
                      g_theta);
   LO_LAUNCH_CHECK();
+  return LO_OK;
+}
+
+size_t lo_kernel_points_grad_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t D, int64_t t) {
+  if (!ko_args_ok(B, M, N, D, t) || !ko_shape_ok(B, M, N, D) || t > 0x7fffffff) return 0;
+  return measured(kKoTail, [&](Arena& ar) { ko_pgrad_layout(ar, B, M, N, D); });
+}
+
+int lo_kernel_points_grad_f32(const float* x1, const float* x2, const float* theta, int32_t family, int64_t B, int64_t M,
+                              int64_t N, int64_t D, const float* U, const float* V, int64_t t, float* g_x1, void* ws,
+                              size_t ws_bytes, void* stream) {
+  if (!x1 || !x2 || !theta || !U || !V || !g_x1 || !ko_args_ok(B, M, N, D, t) || !ko_family_ok(family))
+    return LO_ERR_BADARG;
+  if (!ko_shape_ok(B, M, N, D) || t > 0x7fffffff) return LO_ERR_UNSUPPORTED;
+  hipStream_t st = (hipStream_t)stream;
+  Arena ar(ws, ws_bytes, kKoTail);
+  float* part = ko_pgrad_layout(ar, B, M, N, D);
+  if (!ws || !ar.ok) return LO_ERR_WORKSPACE;
+  const KoShape s = ko_shape(B, M, N);
+  const int DP = ko_padded_dim(D);
+  const dim3 grid((unsigned)s.rb, (unsigned)B, (unsigned)s.js);
+  float* out = s.js > 1 ? part : g_x1;
+  LO_PROF_BEGIN("k_kernel_pgrad", st);
+#define KO_FAM(F_) ko_pgrad_launch_dp<F_>(DP, grid, st, x1, x2, theta, (int)M, (int)N, (int)D, U, V, (int)t, out, s.jchunk)
+  switch (family) {
+    case LO_KERNEL_RBF: KO_FAM(LO_KERNEL_RBF); break;
+    case LO_KERNEL_MATERN12: KO_FAM(LO_KERNEL_MATERN12); break;
+    case LO_KERNEL_MATERN32: KO_FAM(LO_KERNEL_MATERN32); break;
+    default: KO_FAM(LO_KERNEL_MATERN52); break;
+  }
+#undef KO_FAM
+  LO_PROF_END(st);
+  LO_LAUNCH_CHECK();
+  if (s.js > 1) {  // the splits in ascending order (the reduction of the product with D as its columns and no diagonal)
+    const size_t total = (size_t)B * M * D;
+    LO_PROF_BEGIN("k_kernel_pgrad_reduce", st);
+    hipLaunchKernelGGL(k_kernel_mv_reduce, dim3((unsigned)((total + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, part,
+                       s.js, (size_t)M * D, total, (int)D, (const float*)nullptr, LO_DIAG_NONE, (const float*)nullptr, g_x1,
+                       (const int*)nullptr);
+    LO_PROF_END(st);
+    LO_LAUNCH_CHECK();
+  }
   return LO_OK;
 }
 

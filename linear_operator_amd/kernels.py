@@ -540,6 +540,25 @@ def kernel_bilinear(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, fam
     return g
 
 
+def kernel_points_grad(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, family: int, U: torch.Tensor,
+                       V: torch.Tensor) -> torch.Tensor:
+    """lo_kernel_points_grad_f32: g_x1 [B, M, D], the derivative of sum_s u_s^T K(x1, x2) v_s with respect to x1, x2 held
+    fixed.  x1 [B, M, D], x2 [B, N, D], theta [B, D + 1], U [B, M, t], V [B, N, t].  The derivative with respect to x2 is
+    kernel_points_grad(x2, x1, theta, family, V, U)."""
+    lib = _hip.load()
+    x1, x2, theta, U, V = (t.contiguous() for t in (x1, x2, theta, U, V))
+    _hip.require_hip(x1, x2, theta, U, V)
+    B, M, D = x1.shape
+    N, t = V.shape[-2:]
+    if x2.shape != (B, N, D) or theta.shape != (B, D + 1) or U.shape != (B, M, t) or V.shape[0] != B:
+        raise RuntimeError(f"kernel_points_grad: x1 {tuple(x1.shape)}, x2 {tuple(x2.shape)}, "
+                           f"theta {tuple(theta.shape)}, U {tuple(U.shape)}, V {tuple(V.shape)}")
+    g = torch.empty(B, M, D, dtype=torch.float32, device=U.device)
+    _launch("lo_kernel_points_grad_f32", U.device, x1, x2, theta, int(family), B, M, N, D, U, V, t, g,
+            ws_bytes=lib.lo_kernel_points_grad_workspace_bytes(B, M, N, D, t))
+    return g
+
+
 _MASK_BASE_KINDS = (_hip.LO_OP_LOWRANK_DIAG, _hip.LO_OP_DENSE_DIAG, _hip.LO_OP_KRON_DIAG, _hip.LO_OP_SUM)
 
 

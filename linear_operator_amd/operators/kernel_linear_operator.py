@@ -11,8 +11,9 @@ parameters are exactly `lengthscale` [*b, 1, D] or [*b, 1, 1] and `outputscale` 
   _kernel_descriptor    x1 and x2 the same points: the kind LO_OP_KERNEL_DIAG, so that AddedDiag(Kernel, Diag) runs CG,
                         Lanczos, MINRES and the pivoted Cholesky on the device with no Python call per iteration
   _diagonal             outputscale^2, no launch;  _get_indices / _get_rows evaluate only the requested entries
-  _bilinear_derivative  lengthscale and outputscale from lo_kernel_bilinear_f32; the points' gradients, when asked for, by
-                        autograd through covar_func on row chunks of at most MAX_DENSE_CHUNK_BYTES
+  _bilinear_derivative  lengthscale and outputscale from lo_kernel_bilinear_f32; the points' gradients, when asked for,
+                        from lo_kernel_points_grad_f32: one call per side that needs one, the x2 side as the x1 side of
+                        the transposed problem.  covar_func is not called and nothing of size M N is allocated
 
 Anything outside that gate (D > 32, float64, CPU, several outputs per input, other parameters) takes the general path.
 """
@@ -25,10 +26,6 @@ import torch
 from torch import Tensor
 
 from ._linear_operator import LinearOperator, to_dense
-
-# The points' gradients on the native path differentiate covar_func on blocks of rows; a block's [rows, N, D] differences
-# (the largest intermediate of the covariance functions) stay below this many bytes, so the whole of K never exists.
-MAX_DENSE_CHUNK_BYTES = 64 * 1024 * 1024
 
 _NOOP = slice(None, None, None)
 
@@ -277,13 +274,16 @@ class KernelLinearOperator(LinearOperator):
         N, t = right_vecs.shape[-2:]
         bs = torch.broadcast_shapes(self.batch_shape, left_vecs.shape[:-2], right_vecs.shape[:-2])
         out = {"x1": None, "x2": None, "lengthscale": None, "outputscale": None}
+        if not any(p.requires_grad for p in (self.x1, self.x2, ls, os_)):
+            return (None, None) + (None,) * len(names)
+        family = self.covar_func.native_family
+        x1 = self.x1.detach().expand(*bs, M, D).reshape(-1, M, D)
+        x2 = x1 if self._same_points() else self.x2.detach().expand(*bs, N, D).reshape(-1, N, D)
+        theta = self._theta(bs)
+        U = left_vecs.detach().expand(*bs, M, t).reshape(-1, M, t)
+        V = right_vecs.detach().expand(*bs, N, t).reshape(-1, N, t)
         if ls.requires_grad or os_.requires_grad:
-            x1 = self.x1.detach().expand(*bs, M, D).reshape(-1, M, D)
-            x2 = x1 if self._same_points() else self.x2.detach().expand(*bs, N, D).reshape(-1, N, D)
-            theta = self._theta(bs)
-            U = left_vecs.detach().expand(*bs, M, t).reshape(-1, M, t)
-            V = right_vecs.detach().expand(*bs, N, t).reshape(-1, N, t)
-            g = K.kernel_bilinear(x1, x2, theta, self.covar_func.native_family, U, V)  # [B, D + 1], d / d theta
+            g = K.kernel_bilinear(x1, x2, theta, family, U, V)  # [B, D + 1], d / d theta
             if ls.requires_grad:  # theta_d = 1 / l_d: d / d l_d = -theta_d^2 d / d theta_d; a shared l sums over d
                 d_ls = (-(theta[:, :D] ** 2) * g[:, :D]).reshape(*bs, 1, D)
                 if ls.shape[-1] == 1 and D > 1:
@@ -291,42 +291,13 @@ class KernelLinearOperator(LinearOperator):
                 out["lengthscale"] = d_ls.sum_to_size(ls.shape)
             if os_.requires_grad:  # theta_D = os^2: d / d os = 2 os d / d theta_D
                 out["outputscale"] = (2.0 * torch.broadcast_to(os_.detach(), tuple(bs)) * g[:, D].reshape(tuple(bs))).sum_to_size(os_.shape)
-        if self.x1.requires_grad or self.x2.requires_grad:
-            out["x1"], out["x2"] = self._points_derivative_chunked(left_vecs, right_vecs, bs)
+        # each side with the other held fixed; x1 and x2 the same leaf: autograd adds the two.  The x2 side is the x1 side
+        # of the transposed problem (x1 <-> x2, U <-> V).
+        if self.x1.requires_grad:
+            out["x1"] = K.kernel_points_grad(x1, x2, theta, family, U, V).reshape(*bs, M, D).sum_to_size(self.x1.shape)
+        if self.x2.requires_grad:
+            out["x2"] = K.kernel_points_grad(x2, x1, theta, family, V, U).reshape(*bs, N, D).sum_to_size(self.x2.shape)
         return (out["x1"], out["x2"]) + tuple(out[n] for n in names)
 
-    def _points_derivative_chunked(self, left_vecs: Tensor, right_vecs: Tensor, bs):
-        """Gradients of sum_s u_s^T K v_s with respect to x1 and x2 by autograd through covar_func on blocks of rows of
-        at most MAX_DENSE_CHUNK_BYTES (the native kernels do not differentiate the points)."""
-        M, D = self.x1.shape[-2:]
-        N = self.x2.shape[-2]
-        want1, want2 = self.x1.requires_grad, self.x2.requires_grad
-        x1 = self.x1.detach().expand(*bs, M, D)
-        x2 = self.x2.detach().expand(*bs, N, D)
-        params = {n: v.detach() for n, v in self.tensor_params.items()}
-        per_row = max(1, bs.numel()) * N * max(D, 1) * x1.element_size()
-        rows = max(1, min(M, MAX_DENSE_CHUNK_BYTES // per_row))
-        g1 = torch.zeros_like(x1) if want1 else None
-        g2 = torch.zeros_like(x2) if want2 else None
-        U = left_vecs.detach().expand(*bs, M, left_vecs.shape[-1])
-        V = right_vecs.detach().expand(*bs, N, right_vecs.shape[-1])
-        for lo in range(0, M, rows):
-            hi = min(M, lo + rows)
-            with torch.enable_grad():
-                a = x1[..., lo:hi, :].clone().requires_grad_(want1)
-                b = x2.clone().requires_grad_(want2)
-                block = to_dense(self.covar_func(a, b, **params, **self.nontensor_params))  # [*bs, hi - lo, N]
-                loss = (U[..., lo:hi, :] * (block @ V)).sum()
-                grads = list(torch.autograd.grad(loss, [t for t in (a, b) if t.requires_grad]))
-            if want1:
-                g1[..., lo:hi, :] = grads.pop(0)
-            if want2:
-                g2 += grads.pop(0)
-        if want1:
-            g1 = g1.sum_to_size(self.x1.shape)
-        if want2:
-            g2 = g2.sum_to_size(self.x2.shape)
-        return g1, g2
 
-
-__all__ = ["KernelLinearOperator", "MAX_DENSE_CHUNK_BYTES"]
+__all__ = ["KernelLinearOperator"]
