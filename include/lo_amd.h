@@ -83,6 +83,9 @@ extern "C" {
 #define LO_KERNEL_MATERN12 1 /* g(r) = exp(-r)                                          */
 #define LO_KERNEL_MATERN32 2 /* g(r) = (1 + sqrt(3) r) exp(-sqrt(3) r)                  */
 #define LO_KERNEL_MATERN52 3 /* g(r) = (1 + sqrt(5) r + 5 r^2 / 3) exp(-sqrt(5) r)      */
+#define LO_OP_KERNEL_SUM_DIAG 12 /* AddedDiag(Kernel_1(X, X) + .. + Kernel_T(X, X), Diag(d)) over ONE point tensor X:
+                                  *   y = (sum_t K_t(X, X)) v + d o v, every K_t formed tile by tile in the same pass      */
+#define LO_KERNEL_MAX_TERMS 4    /* kernel terms T one LO_OP_KERNEL_SUM_DIAG descriptor / lo_kernel_sum_* call fuses      */
 
 struct lo_interp_desc;
 struct lo_mask_desc;
@@ -135,7 +138,16 @@ typedef struct lo_op_desc {
    * then outputscale^2 (a shared lengthscale is replicated by the host), n2 = the family code LO_KERNEL_* (same layout
    * again).  Lowered for lo_matvec_f32, the streaming CG, Lanczos, fp32 MINRES and the fp32 pivoted Cholesky (constant
    * diagonal theta[D], row[j] = theta[D] g(r_ij)); the fp64 entry points, the resident / fused engines and the solve
-   * sessions return LO_ERR_UNSUPPORTED; not a term kind of LO_OP_SUM, not a base kind of LO_OP_MASKED.                  */
+   * sessions return LO_ERR_UNSUPPORTED; a term kind of LO_OP_SUM from ABI 28 on; not a base kind of LO_OP_MASKED.
+   * ABI 28 kind.  KERNEL_SUM: A0 = X [B, N, D], R = D <= LO_KERNEL_MAX_DIM, A1 = theta [B, T, D + 1] (per term the D inverse
+   * lengthscales, then outputscale^2), nterms = T in 1 .. LO_KERNEL_MAX_TERMS (`terms` unused), n2 = the T family codes, four
+   * bits per term, term 0 lowest (same layout again).  Lowered for lo_matvec_f32, the streaming CG, Lanczos, fp32 MINRES
+   * and the fp32 pivoted Cholesky (diagonal sum_t theta[t][D], row[j] = sum_t theta[t][D] g_t(r_t,ij) in term order); the
+   * fp64 entry points, the resident / fused engines and the solve sessions return LO_ERR_UNSUPPORTED; not a base kind of
+   * LO_OP_MASKED.
+   * ABI 28: KERNEL and KERNEL_SUM are term kinds of LO_OP_SUM next to LOWRANK / DENSE / KRON for lo_matvec_f32, the
+   * streaming CG, Lanczos, fp32 MINRES and the fp32 pivoted Cholesky (operators over different point tensors, a kernel
+   * plus a low-rank root); a sum that holds one is refused by the fp64 entry points and as the base of LO_OP_MASKED.   */
 } lo_op_desc;
 
 /* The grid shape of an LO_OP_TOEPLITZ_KRON_DIAG descriptor (host struct). */
@@ -899,6 +911,34 @@ size_t lo_kernel_points_grad_workspace_bytes(int64_t B, int64_t M, int64_t N, in
 int lo_kernel_points_grad_f32(const float* x1, const float* x2, const float* theta, int32_t family, int64_t B, int64_t M,
                               int64_t N, int64_t D, const float* U, const float* V, int64_t t, float* g_x1, void* ws,
                               size_t ws_bytes, void* stream);
+
+/* ---- sums of matrix-free kernel operators over the same points (ABI 28; csrc/lo_kernel_sum.hip) ------------------------
+ * K_ij = sum_t theta[t][D] g_{f_t}(r_t,ij), r_t,ij^2 = sum_d (theta[t][d] (x1[i, d] - x2[j, d]))^2 for T terms,
+ * 1 <= T <= LO_KERNEL_MAX_TERMS; theta [B, T, D + 1], `families` a HOST array of T codes LO_KERNEL_* (terms may mix
+ * families).  One pass over the pairs for all terms: the tile of x2 is staged scaled once per term, the tile of v once;
+ * the T kernel values of a pair are added before its column FMAs run.  The term loop runs outside sub-tiles of 8 pairs,
+ * so a term's family is switched on once per 8 pairs.  Launch shape, column splits and the sums' order as in the
+ * single-term kernels above; every argument and error code as there, plus LO_ERR_BADARG for T outside the range or a
+ * null `families`.
+ *   lo_kernel_sum_mv_f32           y [B, M, c] = K v (+ d o v when M == N), the kind LO_OP_KERNEL_SUM_DIAG with x1 = x2.
+ *                                  Fused for T > 1 and c > 4; narrower right-hand sides run the single-term kernel once
+ *                                  per term inside the call, added in term order (measured faster: DESIGN.md 6m); the
+ *                                  workspace then holds one more [B, M, c] vector
+ *   lo_kernel_sum_bilinear_f32     g_theta [B, T, D + 1]: every term's d / d theta of sum_ij W_ij K_ij, W_ij formed once per
+ *                                  pair; one sweep (two when 16 < D and T > 2: a thread holds the running sums of 2 terms)
+ *   lo_kernel_sum_points_grad_f32  g_x1 [B, M, D], the gradient of the points summed over the terms, one sweep           */
+size_t lo_kernel_sum_mv_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t D, int64_t T, int64_t c);
+int lo_kernel_sum_mv_f32(const float* x1, const float* x2, const float* theta, const int32_t* families, int64_t T,
+                         int64_t B, int64_t M, int64_t N, int64_t D, const float* v, int64_t c, const float* d,
+                         int32_t diag_mode, float* y, void* ws, size_t ws_bytes, void* stream);
+size_t lo_kernel_sum_bilinear_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t D, int64_t T, int64_t t);
+int lo_kernel_sum_bilinear_f32(const float* x1, const float* x2, const float* theta, const int32_t* families, int64_t T,
+                               int64_t B, int64_t M, int64_t N, int64_t D, const float* U, const float* V, int64_t t,
+                               float* g_theta, void* ws, size_t ws_bytes, void* stream);
+size_t lo_kernel_sum_points_grad_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t D, int64_t T, int64_t t);
+int lo_kernel_sum_points_grad_f32(const float* x1, const float* x2, const float* theta, const int32_t* families, int64_t T,
+                                  int64_t B, int64_t M, int64_t N, int64_t D, const float* U, const float* V, int64_t t,
+                                  float* g_x1, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- exact small-N path: batched Cholesky and triangular solves (ABI 18; csrc/lo_chol.hip) -------------------------
  * fp32, contiguous row-major, N <= 1024 (larger: LO_ERR_UNSUPPORTED), stream-ordered; fixed-order sums, no atomics: a

@@ -238,9 +238,16 @@ int hadamard_matvec_run(const MatvecPlan* pl, const float* v, float* y, const in
 // ---- matrix-free kernel operator (lo_kernel_op.hip): LO_OP_KERNEL_DIAG ------------------------------------------------
 struct KernelOpPlan {
   float* part;  // [js, B, N, c] partial products when the columns j of a member are split over js workgroups, else nullptr
+  float* ytmp;  // LO_OP_KERNEL_SUM_DIAG on its per-term route: [B, N, c], a term beyond the first before it is added onto y
 };
 int kernel_op_plan(MatvecPlan* pl, Arena* ar, hipStream_t st);
 int kernel_op_matvec_run(const MatvecPlan* pl, const float* v, float* y, const int* stop, hipStream_t st);
+
+// ---- sum of matrix-free kernel operators over the same points (lo_kernel_sum.hip): LO_OP_KERNEL_SUM_DIAG, on KernelOpPlan
+int kernel_sum_plan(MatvecPlan* pl, Arena* ar, hipStream_t st);
+int kernel_sum_matvec_run(const MatvecPlan* pl, const float* v, float* y, const int* stop, hipStream_t st);
+// LO_OK, or why the descriptor of that kind is refused (the pivoted Cholesky validates it without a plan)
+int kernel_sum_desc_check(const lo_op_desc* op);
 
 // ---- masked operator (lo_masked.hip) ---------------------------------------------------------------------------------
 struct MaskedPlan {      // (the base's plan is MatvecPlan::sub[0])
@@ -314,6 +321,8 @@ int matvec_run_pupdate(const MatvecPlan* pl, float* p, const float* z, const flo
 inline bool plain_term_kind(int kind) {
   return kind == LO_OP_LOWRANK_DIAG || kind == LO_OP_DENSE_DIAG || kind == LO_OP_KRON_DIAG;
 }
+// the matrix-free kernel kinds: terms of a sum next to the plain ones (fp32 engines only; not under a mask)
+inline bool kernel_term_kind(int kind) { return kind == LO_OP_KERNEL_DIAG || kind == LO_OP_KERNEL_SUM_DIAG; }
 
 // ---- the Q-form Woodbury apply z = dinv o r - Q (Q^T r) as a plan (lo_skinny.hip): staged and run
 // through these two functions by the streaming CG and MINRES engines and by lo_precond_apply_f32 ----------------------

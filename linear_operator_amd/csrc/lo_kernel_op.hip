@@ -23,38 +23,9 @@
 #include "lo_device.h"
 #include "lo_internal.h"
 #include "lo_kernel_fn.h"
+#include "lo_kernel_shape.h"
 
 namespace lo {
-
-constexpr int kKoTJ = 128;  // points of x2 per LDS tile
-constexpr int kKoTS = 8;    // columns s of U / V per sweep of the derivative
-constexpr int kKoMaxSplit = 64;
-
-struct KoShape {
-  int rb;       // row blocks of 256
-  int js;       // workgroups a member's columns j are split over
-  int jchunk;   // columns per split (a multiple of kKoTJ)
-};
-
-static bool ko_args_ok(int64_t B, int64_t M, int64_t N, int64_t D, int64_t c) {
-  return B >= 1 && M >= 1 && N >= 1 && D >= 1 && c >= 1;
-}
-static bool ko_shape_ok(int64_t B, int64_t M, int64_t N, int64_t D) {
-  return D <= LO_KERNEL_MAX_DIM && B <= 65535 && M <= 0x7ffffe00 && N <= 0x7ffffe00;
-}
-
-static KoShape ko_shape(int64_t B, int64_t M, int64_t N) {
-  KoShape s;
-  s.rb = (int)((M + kThreads - 1) / kThreads);
-  const int64_t wgs = (int64_t)s.rb * B;
-  const int64_t tiles = (N + kKoTJ - 1) / kKoTJ;
-  int64_t js = 1;
-  if (wgs < 512) js = std::min<int64_t>(std::min<int64_t>(tiles, (512 + wgs - 1) / wgs), kKoMaxSplit);
-  const int64_t per = (tiles + js - 1) / js;
-  s.jchunk = (int)(per * kKoTJ);
-  s.js = (int)((N + s.jchunk - 1) / s.jchunk);
-  return s;
-}
 
 // stage the tile [jt, jt + nj) of x2, scaled by the inverse lengthscales, as xs[j][DP] (coordinates >= D are 0)
 template <int DP>
@@ -66,10 +37,11 @@ __device__ __forceinline__ void ko_stage_points(const float* __restrict__ x2b, c
   }
 }
 
-// grid (row blocks, B, js); part == nullptr: y is written with the diagonal term, else partial products [js, B, M, c]
+// grid (row blocks, B, js); part == nullptr: y is written with the diagonal term, else partial products [js, B, M, c].
+// tstride: floats between the thetas of two members (D + 1; T (D + 1) for one term of a [B, T, D + 1] array)
 template <int FAMILY, int DP, int CC>
 __global__ __launch_bounds__(kThreads) void k_kernel_mv(const float* __restrict__ x1, const float* __restrict__ x2,
-                                                        const float* __restrict__ theta, int M, int N, int D,
+                                                        const float* __restrict__ theta, int tstride, int M, int N, int D,
                                                         const float* __restrict__ v, int c,
                                                         const float* __restrict__ dd_ptr, int dd_mode,
                                                         float* __restrict__ y, float* __restrict__ part, int jchunk,
@@ -81,12 +53,12 @@ __global__ __launch_bounds__(kThreads) void k_kernel_mv(const float* __restrict_
   const int64_t b = blockIdx.y;
   const int i = blockIdx.x * kThreads + threadIdx.x;
   const bool live = i < M;
-  if (threadIdx.x < DP) th[threadIdx.x] = (int)threadIdx.x < D ? theta[b * (D + 1) + threadIdx.x] : 0.0f;
+  if (threadIdx.x < DP) th[threadIdx.x] = (int)threadIdx.x < D ? theta[b * tstride + threadIdx.x] : 0.0f;
   __syncthreads();
   float a[DP];
 #pragma unroll
   for (int k = 0; k < DP; ++k) a[k] = (live && k < D) ? x1[((size_t)b * M + i) * D + k] * th[k] : 0.0f;
-  const float os2 = theta[b * (D + 1) + D];
+  const float os2 = theta[b * tstride + D];
   const float* x2b = x2 + (size_t)b * N * D;
   const float* vb = v + (size_t)b * N * c;
   const int j0 = blockIdx.z * jchunk, j1 = min(N, j0 + jchunk);
@@ -324,34 +296,42 @@ __global__ __launch_bounds__(kThreads) void k_kernel_pgrad(const float* __restri
   }
 }
 
-static int ko_padded_dim(int64_t D) { return D <= 4 ? 4 : (D <= 8 ? 8 : (D <= 16 ? 16 : 32)); }
-static int ko_col_chunk(int64_t c) { return c == 1 ? 1 : (c <= 4 ? 4 : 16); }
+int ko_reduce_splits(const char* prof_name, const float* part, int js, size_t per_member, size_t total, int c,
+                     const float* d, int dmode, const float* v, float* y, const int* stop, hipStream_t st) {
+  LO_PROF_BEGIN(prof_name, st);
+  hipLaunchKernelGGL(k_kernel_mv_reduce, dim3((unsigned)((total + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, part,
+                     js, per_member, total, c, d, dmode, v, y, stop);
+  LO_PROF_END(st);
+  LO_LAUNCH_CHECK();
+  return LO_OK;
+}
 
 template <int FAMILY, int DP>
-static void ko_mv_launch_cc(int CC, dim3 grid, hipStream_t st, const float* x1, const float* x2, const float* theta, int M,
-                            int N, int D, const float* v, int c, const float* d, int dmode, float* y, float* part,
-                            int jchunk, const int* stop) {
+static void ko_mv_launch_cc(int CC, dim3 grid, hipStream_t st, const float* x1, const float* x2, const float* theta,
+                            int tstride, int M, int N, int D, const float* v, int c, const float* d, int dmode, float* y,
+                            float* part, int jchunk, const int* stop) {
   switch (CC) {
     case 1:
-      hipLaunchKernelGGL((k_kernel_mv<FAMILY, DP, 1>), grid, dim3(kThreads), 0, st, x1, x2, theta, M, N, D, v, c, d, dmode,
-                         y, part, jchunk, stop);
+      hipLaunchKernelGGL((k_kernel_mv<FAMILY, DP, 1>), grid, dim3(kThreads), 0, st, x1, x2, theta, tstride, M, N, D, v, c,
+                         d, dmode, y, part, jchunk, stop);
       break;
     case 4:
-      hipLaunchKernelGGL((k_kernel_mv<FAMILY, DP, 4>), grid, dim3(kThreads), 0, st, x1, x2, theta, M, N, D, v, c, d, dmode,
-                         y, part, jchunk, stop);
+      hipLaunchKernelGGL((k_kernel_mv<FAMILY, DP, 4>), grid, dim3(kThreads), 0, st, x1, x2, theta, tstride, M, N, D, v, c,
+                         d, dmode, y, part, jchunk, stop);
       break;
     default:
-      hipLaunchKernelGGL((k_kernel_mv<FAMILY, DP, 16>), grid, dim3(kThreads), 0, st, x1, x2, theta, M, N, D, v, c, d,
-                         dmode, y, part, jchunk, stop);
+      hipLaunchKernelGGL((k_kernel_mv<FAMILY, DP, 16>), grid, dim3(kThreads), 0, st, x1, x2, theta, tstride, M, N, D, v, c,
+                         d, dmode, y, part, jchunk, stop);
       break;
   }
 }
 
 template <int FAMILY>
 static void ko_mv_launch_dp(int DP, int CC, dim3 grid, hipStream_t st, const float* x1, const float* x2,
-                            const float* theta, int M, int N, int D, const float* v, int c, const float* d, int dmode,
-                            float* y, float* part, int jchunk, const int* stop) {
-#define KO_MV(DP_) ko_mv_launch_cc<FAMILY, DP_>(CC, grid, st, x1, x2, theta, M, N, D, v, c, d, dmode, y, part, jchunk, stop)
+                            const float* theta, int tstride, int M, int N, int D, const float* v, int c, const float* d,
+                            int dmode, float* y, float* part, int jchunk, const int* stop) {
+#define KO_MV(DP_) \
+  ko_mv_launch_cc<FAMILY, DP_>(CC, grid, st, x1, x2, theta, tstride, M, N, D, v, c, d, dmode, y, part, jchunk, stop)
   switch (DP) {
     case 4: KO_MV(4); break;
     case 8: KO_MV(8); break;
@@ -390,16 +370,18 @@ static void ko_pgrad_launch_dp(int DP, dim3 grid, hipStream_t st, const float* x
 }
 
 // the product on validated arguments; part: [js, B, M, c] floats when ko_shape(B, M, N).js > 1 (else unused)
-static int kernel_mv_run(const float* x1, const float* x2, const float* theta, int family, int64_t B, int64_t M, int64_t N,
-                         int64_t D, const float* v, int64_t c, const float* d, int dmode, float* y, float* part,
-                         const int* stop, hipStream_t st) {
+int kernel_mv_run(const float* x1, const float* x2, const float* theta, int64_t tstride, int family, int64_t B, int64_t M,
+                  int64_t N, int64_t D, const float* v, int64_t c, const float* d, int dmode, float* y, float* part,
+                  const int* stop, hipStream_t st) {
   const KoShape s = ko_shape(B, M, N);
   const int DP = ko_padded_dim(D), CC = ko_col_chunk(c);
   const dim3 grid((unsigned)s.rb, (unsigned)B, (unsigned)s.js);
   float* p = s.js > 1 ? part : nullptr;
   if (M != N) dmode = LO_DIAG_NONE;
   LO_PROF_BEGIN("k_kernel_mv", st);
-#define KO_FAM(F_) ko_mv_launch_dp<F_>(DP, CC, grid, st, x1, x2, theta, (int)M, (int)N, (int)D, v, (int)c, d, dmode, y, p, s.jchunk, stop)
+#define KO_FAM(F_)                                                                                                    \
+  ko_mv_launch_dp<F_>(DP, CC, grid, st, x1, x2, theta, (int)tstride, (int)M, (int)N, (int)D, v, (int)c, d, dmode, y, p, \
+                      s.jchunk, stop)
   switch (family) {
     case LO_KERNEL_RBF: KO_FAM(LO_KERNEL_RBF); break;
     case LO_KERNEL_MATERN12: KO_FAM(LO_KERNEL_MATERN12); break;
@@ -409,18 +391,11 @@ static int kernel_mv_run(const float* x1, const float* x2, const float* theta, i
 #undef KO_FAM
   LO_PROF_END(st);
   LO_LAUNCH_CHECK();
-  if (p) {
-    const size_t total = (size_t)B * M * c;
-    LO_PROF_BEGIN("k_kernel_mv_reduce", st);
-    hipLaunchKernelGGL(k_kernel_mv_reduce, dim3((unsigned)((total + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, p,
-                       s.js, (size_t)M * c, total, (int)c, d, dmode, v, y, stop);
-    LO_PROF_END(st);
-    LO_LAUNCH_CHECK();
-  }
+  if (p)
+    return ko_reduce_splits("k_kernel_mv_reduce", p, s.js, (size_t)M * c, (size_t)B * M * c, (int)c, d, dmode, v, y, stop,
+                            st);
   return LO_OK;
 }
-
-static bool ko_family_ok(int64_t family) { return family >= LO_KERNEL_RBF && family <= LO_KERNEL_MATERN52; }
 
 // the one layout of the product's workspace: the partials of a split member
 static float* ko_mv_layout(Arena& ar, int64_t B, int64_t M, int64_t N, int64_t c) {
@@ -438,11 +413,9 @@ int kernel_op_plan(MatvecPlan* pl, Arena* ar, hipStream_t) {
 
 int kernel_op_matvec_run(const MatvecPlan* pl, const float* v, float* y, const int* stop, hipStream_t st) {
   const lo_op_desc& op = pl->op;
-  return kernel_mv_run(op.A0, op.A0, op.A1, (int)op.n2, op.B, op.N, op.N, op.R, v, pl->c, op.d, op.diag_mode, y,
+  return kernel_mv_run(op.A0, op.A0, op.A1, op.R + 1, (int)op.n2, op.B, op.N, op.N, op.R, v, pl->c, op.d, op.diag_mode, y,
                        pl->ko.part, stop, st);
 }
-
-constexpr size_t kKoTail = 256;  // what the sizers report beyond the layout
 
 static float* ko_bil_layout(Arena& ar, int64_t B, int64_t M, int64_t N, int64_t D) {
   const KoShape s = ko_shape(B, M, N);
@@ -476,7 +449,8 @@ int lo_kernel_mv_f32(const float* x1, const float* x2, const float* theta, int32
   Arena ar(ws, ws_bytes, kKoTail);
   float* part = ko_mv_layout(ar, B, M, N, c);
   if (!ws || !ar.ok) return LO_ERR_WORKSPACE;
-  return kernel_mv_run(x1, x2, theta, family, B, M, N, D, v, c, d, diag_mode, y, part, nullptr, (hipStream_t)stream);
+  return kernel_mv_run(x1, x2, theta, D + 1, family, B, M, N, D, v, c, d, diag_mode, y, part, nullptr,
+                       (hipStream_t)stream);
 }
 
 size_t lo_kernel_bilinear_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t D, int64_t t) {
@@ -544,15 +518,9 @@ int lo_kernel_points_grad_f32(const float* x1, const float* x2, const float* the
 #undef KO_FAM
   LO_PROF_END(st);
   LO_LAUNCH_CHECK();
-  if (s.js > 1) {  // the splits in ascending order (the reduction of the product with D as its columns and no diagonal)
-    const size_t total = (size_t)B * M * D;
-    LO_PROF_BEGIN("k_kernel_pgrad_reduce", st);
-    hipLaunchKernelGGL(k_kernel_mv_reduce, dim3((unsigned)((total + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, part,
-                       s.js, (size_t)M * D, total, (int)D, (const float*)nullptr, LO_DIAG_NONE, (const float*)nullptr, g_x1,
-                       (const int*)nullptr);
-    LO_PROF_END(st);
-    LO_LAUNCH_CHECK();
-  }
+  if (s.js > 1)  // the splits in ascending order (the reduction of the product with D as its columns and no diagonal)
+    return ko_reduce_splits("k_kernel_pgrad_reduce", part, s.js, (size_t)M * D, (size_t)B * M * D, (int)D, nullptr,
+                            LO_DIAG_NONE, nullptr, g_x1, nullptr, st);
   return LO_OK;
 }
 

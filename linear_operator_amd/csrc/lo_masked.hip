@@ -199,6 +199,9 @@ __global__ __launch_bounds__(kThreads) void k_masked_dense_mv(
 }
 
 static bool mask_base_ok(const lo_op_desc* base) {
+  if (base->kind == LO_OP_SUM && base->terms)  // (a sum's kernel terms are not taken under a mask)
+    for (int i = 0; i < base->nterms && i < LO_MAX_TERMS; ++i)
+      if (kernel_term_kind(base->terms[i].kind)) return false;
   return plain_term_kind(base->kind) || base->kind == LO_OP_SUM;
 }
 

@@ -92,7 +92,7 @@ static int sum_plan(MatvecPlan* pl, Arena* ar, hipStream_t st) {
   if (op.nterms < 2 || op.nterms > LO_MAX_TERMS || !op.terms) return LO_ERR_BADARG;
   for (int i = 0; i < op.nterms; ++i) {
     const lo_op_desc& t = op.terms[i];
-    if (!plain_term_kind(t.kind) || t.diag_mode != LO_DIAG_NONE || t.B != op.B || t.N != op.N) return LO_ERR_BADARG;
+    if (!(plain_term_kind(t.kind) || kernel_term_kind(t.kind)) || t.diag_mode != LO_DIAG_NONE || t.B != op.B || t.N != op.N) return LO_ERR_BADARG;
   }
   pl->sum.ytmp = ar->take<float>((size_t)op.B * op.N * pl->c);
   MatvecPlan scratch;  // (a measuring pass keeps no sub-plans)
@@ -151,6 +151,7 @@ int matvec_plan_init(MatvecPlan* pl, const lo_op_desc* op, lo_matvec_cb cb, void
     case LO_OP_TOEPLITZ_KRON_DIAG: rc = toeplitz_kron_plan(pl, ar, st); break;
     case LO_OP_HADAMARD_DIAG: rc = hadamard_plan(pl, ar, st); break;
     case LO_OP_KERNEL_DIAG: rc = kernel_op_plan(pl, ar, st); break;
+    case LO_OP_KERNEL_SUM_DIAG: rc = kernel_sum_plan(pl, ar, st); break;
     case LO_OP_MASKED: rc = masked_plan(pl, ar, st); break;
     case LO_OP_CALLBACK: rc = cb ? LO_OK : LO_ERR_BADARG; break;
     case LO_OP_SUM: rc = sum_plan(pl, ar, st); break;
@@ -191,6 +192,8 @@ int matvec_run(const MatvecPlan* pl, const float* v, float* y, float* dot_part, 
       rc = hadamard_matvec_run(pl, v, y, stop, st); break;
     case LO_OP_KERNEL_DIAG:  // K(X, X) v + d o v, K formed tile by tile from X (lo_kernel_op.hip)
       rc = kernel_op_matvec_run(pl, v, y, stop, st); break;
+    case LO_OP_KERNEL_SUM_DIAG:  // (sum_t K_t(X, X)) v + d o v in one pass over the pairs (lo_kernel_sum.hip)
+      rc = kernel_sum_matvec_run(pl, v, y, stop, st); break;
     case LO_OP_MASKED:  // S (base) S^T v + d o v: expand, the base's product (or the selected rows of a dense base), gather
       rc = masked_matvec_run(pl, v, y, stop, st); break;
     case LO_OP_CALLBACK: rc = pl->cb(pl->cb_user, v, y, op.B, op.N, pl->c, (void*)st) ? LO_ERR_LAUNCH : LO_OK; break;
@@ -220,7 +223,7 @@ using namespace lo;
 
 extern "C" {
 
-int lo_abi_version(void) { return 27; }
+int lo_abi_version(void) { return 28; }
 const char* lo_target_arch(void) { return "gfx950"; }
 
 size_t lo_matvec_workspace_bytes(const lo_op_desc* op, int64_t c) {

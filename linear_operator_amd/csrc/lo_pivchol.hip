@@ -132,6 +132,11 @@ __device__ __forceinline__ T src_diag(const PcDevT<T>& d, const lo_op_desc& op, 
     return A0[(size_t)b * op.R];
   } else if (op.kind == LO_OP_KERNEL_DIAG) {  // os2 g(0) = os2 (an fp32 kind: the operands are read as float)
     return (T)op.A1[(size_t)b * (op.R + 1) + op.R];
+  } else if (op.kind == LO_OP_KERNEL_SUM_DIAG) {  // sum_t os2_t, in term order
+    const float* th = op.A1 + (size_t)b * op.nterms * (op.R + 1);
+    float s = th[op.R];
+    for (int t = 1; t < op.nterms; ++t) s = s + th[(size_t)t * (op.R + 1) + op.R];
+    return (T)s;
   } else if (op.kind == LO_OP_TOEPLITZ_KRON_DIAG) {
     // prod_k t_k[0], the trailing factors multiplied first (kronecker_product_linear_operator.py:22-28)
     const int D = d.ski.grid_ndim;
@@ -466,6 +471,22 @@ __global__ __launch_bounds__(kThreads) void k_pc_update(PcDevT<T> d, int m) {
             r2 = r2 + df * df;
           }
           tv = (T)(th[D] * kf_g_rt((int)tm.n2, r2));
+        } else if (tm.kind == LO_OP_KERNEL_SUM_DIAG) {  // the same row source per term, summed in term order
+          const int D = (int)tm.R;
+          const float* xp = tm.A0 + ((size_t)b * N + pim) * D;
+          const float* xi = tm.A0 + ((size_t)b * N + i) * D;
+          float s = 0.0f;
+          for (int t = 0; t < tm.nterms; ++t) {
+            const float* th = tm.A1 + ((size_t)b * tm.nterms + t) * (D + 1);
+            float r2 = 0.0f;
+            for (int k = 0; k < D; ++k) {
+              const float df = xp[k] * th[k] - xi[k] * th[k];
+              r2 = r2 + df * df;
+            }
+            const float kt = th[D] * kf_g_rt((int)((tm.n2 >> (4 * t)) & 15), r2);
+            s = t == 0 ? kt : s + kt;
+          }
+          tv = (T)s;
         } else if (tm.kind == LO_OP_TOEPLITZ_KRON_DIAG) {
           // prod_k t_k[|p_k - i_k|], factors multiplied left to right (kronecker_product_linear_operator.py:198-216);
           // consecutive threads hold consecutive positions j: the gathers from the (small) columns stay in cache
@@ -686,22 +707,32 @@ static size_t pc_ws_bytes(const lo_op_desc* op, int32_t max_rank, bool cb) {
   });
 }
 
-static int pc_check_desc(const lo_op_desc* op) {
+static int pc_check_kernel(const lo_op_desc* op) {
+  if (!op->A0 || !op->A1 || op->R < 1 || op->n2 < LO_KERNEL_RBF || op->n2 > LO_KERNEL_MATERN52) return LO_ERR_BADARG;
+  if (op->R > LO_KERNEL_MAX_DIM) return LO_ERR_UNSUPPORTED;
+  return LO_OK;
+}
+
+// fp32_kinds: the caller reads the operands as float (the float64 engine takes the plain kinds and sums of them only)
+static int pc_check_desc(const lo_op_desc* op, bool fp32_kinds = true) {
   if (op->kind == LO_OP_SUM) {
     if (op->nterms < 2 || op->nterms > LO_MAX_TERMS || !op->terms) return LO_ERR_BADARG;
     for (int i = 0; i < op->nterms; ++i) {
       const lo_op_desc& t = op->terms[i];
-      if ((t.kind != LO_OP_LOWRANK_DIAG && t.kind != LO_OP_DENSE_DIAG && t.kind != LO_OP_KRON_DIAG) || t.B != op->B ||
-          t.N != op->N)
-        return LO_ERR_BADARG;
+      if (!(plain_term_kind(t.kind) || kernel_term_kind(t.kind)) || t.B != op->B || t.N != op->N) return LO_ERR_BADARG;
+      if (kernel_term_kind(t.kind)) {  // (a term is validated as the kind on its own is)
+        if (!fp32_kinds) return LO_ERR_UNSUPPORTED;
+        if (const int rc = t.kind == LO_OP_KERNEL_DIAG ? pc_check_kernel(&t) : kernel_sum_desc_check(&t)) return rc;
+      }
     }
   } else if (op->kind == LO_OP_HADAMARD_DIAG) {
     if (!op->A0 || !op->A1 || op->R < 1 || op->n2 < 1) return LO_ERR_BADARG;
   } else if (op->kind == LO_OP_TOEPLITZ_DIAG) {
     if (!op->A0 || op->R != op->N) return LO_ERR_BADARG;
   } else if (op->kind == LO_OP_KERNEL_DIAG) {
-    if (!op->A0 || !op->A1 || op->R < 1 || op->n2 < LO_KERNEL_RBF || op->n2 > LO_KERNEL_MATERN52) return LO_ERR_BADARG;
-    if (op->R > LO_KERNEL_MAX_DIM) return LO_ERR_UNSUPPORTED;
+    if (const int rc = pc_check_kernel(op)) return rc;
+  } else if (op->kind == LO_OP_KERNEL_SUM_DIAG) {
+    if (const int rc = kernel_sum_desc_check(op)) return rc;
   } else if (op->kind == LO_OP_SKI_DIAG) {
     const lo_interp_desc* w = op->interp;
     if (!op->A0 || op->R < 1 || op->n2 < 1 || !w || !w->left_idx || !w->left_vals || !w->right_idx || !w->right_vals)
@@ -798,9 +829,9 @@ int lo_pivoted_cholesky_f64(const lo_op_desc* op, int32_t max_rank, double error
                             int32_t* rank_out, void* ws, size_t ws_bytes, void* stream) {
   if (!op || !L_rows || !perm || !rank_out || !ws || max_rank < 1) return LO_ERR_BADARG;
   if (op->kind == LO_OP_SKI_DIAG || op->kind == LO_OP_TOEPLITZ_DIAG || op->kind == LO_OP_HADAMARD_DIAG ||
-      op->kind == LO_OP_SKI_GRID_DIAG || op->kind == LO_OP_TOEPLITZ_KRON_DIAG || op->kind == LO_OP_KERNEL_DIAG)
+      op->kind == LO_OP_SKI_GRID_DIAG || op->kind == LO_OP_TOEPLITZ_KRON_DIAG || kernel_term_kind(op->kind))
     return LO_ERR_UNSUPPORTED;  // (fp32 kinds)
-  if (const int rc = pc_check_desc(op)) return rc;
+  if (const int rc = pc_check_desc(op, false)) return rc;
   return pc_stream_t<double>(op, nullptr, nullptr, nullptr, max_rank, error_tol, L_rows, perm, rank_out, ws, ws_bytes,
                              (hipStream_t)stream);
 }

@@ -28,6 +28,7 @@ class OperatorDescriptor:
     N: int
     A0: Optional[torch.Tensor] = None  # C [B,N,R] | K [B,N,N] | K1 [B,n1,n1]
     # K2 [B,n2,n2] | G [B,N,q] (Hadamard: A0 = F [B,N,p]) | theta [B,D+1] (Kernel: A0 = X [B,N,D], R = D, n2 = family)
+    # | theta [B,T,D+1] (KernelSum: A0 = X, R = D, n2 = the packed families, kernel_terms = T)
     A1: Optional[torch.Tensor] = None
     d: Optional[torch.Tensor] = None  # [B,N] (FULL) or [B] (CONST)
     diag_mode: int = _hip.LO_DIAG_NONE
@@ -45,6 +46,7 @@ class OperatorDescriptor:
     # sums of those) go to lo_matvec_f64 and the float64 solvers only, and c_struct() refuses to hand one to an entry
     # point that reads `float*`
     dtype: torch.dtype = torch.float32
+    kernel_terms: int = 0  # LO_OP_KERNEL_SUM_DIAG: T, the struct's `nterms` (the kind has no `terms`)
 
     @property
     def device(self):
@@ -70,7 +72,7 @@ class OperatorDescriptor:
         s.A0 = None if self.A0 is None else self.A0.data_ptr()
         s.A1 = None if self.A1 is None else self.A1.data_ptr()
         s.d = None if self.d is None else self.d.data_ptr()
-        s.nterms = len(self.terms)
+        s.nterms = len(self.terms) or self.kernel_terms
         if self.terms:  # host array of term descriptors; kept alive by the returned struct
             arr = (_hip.OpDesc * len(self.terms))(*[t.c_struct(dtype) for t in self.terms])
             s.terms = C.cast(arr, C.POINTER(_hip.OpDesc))
@@ -97,7 +99,7 @@ class OperatorDescriptor:
     def without_diag(self) -> "OperatorDescriptor":
         return OperatorDescriptor(self.kind, self.B, self.N, self.A0, self.A1, None, _hip.LO_DIAG_NONE, self.R,
                                   self.n2, self.batch_shape, self.terms, self.interp, self.interp_plan, self.mask,
-                                  self.grid, self.dtype)
+                                  self.grid, self.dtype, self.kernel_terms)
 
 
 def _check_dtype(dtype, *tensors):
@@ -113,8 +115,9 @@ def _check_dtype(dtype, *tensors):
 
 def sum_descriptor(terms, d: Optional[torch.Tensor] = None, const_diag: bool = False, dtype=torch.float32):
     """SumLinearOperator(A_1, ..., A_n) (+ one diagonal): y = sum_i A_i v + d o v (sum_linear_operator.py:47-51).
-    `terms`: 2 .. LO_MAX_TERMS descriptors of kind low-rank / dense / Kronecker WITHOUT a diagonal, same batch and N,
-    all of the element type `dtype`."""
+    `terms`: 2 .. LO_MAX_TERMS descriptors of kind low-rank / dense / Kronecker -- float32 sums also matrix-free kernel
+    terms (LO_OP_KERNEL_DIAG, LO_OP_KERNEL_SUM_DIAG) -- WITHOUT a diagonal, same batch and N, all of the element type
+    `dtype`."""
     terms = tuple(terms)
     for t in terms:
         if t.dtype != dtype:
@@ -559,6 +562,121 @@ def kernel_points_grad(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, 
     return g
 
 
+def kernel_sum_theta(lengthscales, outputscales, batch, D: int) -> torch.Tensor:
+    """theta [B, T, D + 1] of the fused kernel-sum entry points: per term the D inverse lengthscales (a shared one
+    replicated), then outputscale^2 -- kernel_theta of every term, stacked in term order."""
+    return torch.stack([kernel_theta(ls, os_, batch, D) for ls, os_ in zip(lengthscales, outputscales)], 1).contiguous()
+
+
+def kernel_sum_pack_families(families) -> int:
+    """The family codes as the descriptor's n2: four bits per term, term 0 lowest."""
+    families = [int(f) for f in families]
+    if not 1 <= len(families) <= _hip.LO_KERNEL_MAX_TERMS:
+        raise ValueError(f"a fused kernel sum holds 1 .. {_hip.LO_KERNEL_MAX_TERMS} terms, got {len(families)}")
+    if any(not _hip.LO_KERNEL_RBF <= f <= _hip.LO_KERNEL_MATERN52 for f in families):
+        raise ValueError(f"unknown kernel family among {families}")
+    return sum(f << (4 * t) for t, f in enumerate(families))
+
+
+# Which derivative calls of a sum of kernel operators over one pair of point tensors are fused, from tools/mb_kernel_sum.py
+# on the MI355X (DESIGN.md section 6m; fused / per-term time, T = 2 and 3, t = 1 and 17):
+#   theta   D 4: 0.86 - 0.97   D 16: 1.09 - 1.12      points   D 4, T 3: 0.96 - 0.98   D 4, T 2: 1.04 - 1.05   D 16: 1.13 - 1.21
+# The fused sweep forms W_ij once for all terms; beyond D = 4 the distances outweigh that and the term loop costs more
+# than it saves.  A cell that was not measured (4 < D < 16, T = 4) takes the side of its nearest measured neighbour.
+def kernel_sum_fused_bilinear(D: int, T: int) -> bool:
+    return T >= 2 and D <= 4
+
+
+def kernel_sum_fused_points_grad(D: int, T: int) -> bool:
+    return T >= 3 and D <= 4
+
+
+def kernel_sum_diag_descriptor(X: torch.Tensor, theta: torch.Tensor, families, d: Optional[torch.Tensor] = None,
+                               const_diag: bool = False):
+    """AddedDiag(Kernel_1(X, X) + .. + Kernel_T(X, X), Diag(d)) (or the sum alone) over ONE point tensor:
+    y = (sum_t K_t) v + d o v, all terms formed in one pass (csrc/lo_kernel_sum.hip).  X [*batch, N, D],
+    theta [B, T, D + 1] from kernel_sum_theta, `families` the T codes.  None when D exceeds LO_KERNEL_MAX_DIM."""
+    _hip.require_hip(X, theta, d)
+    N, D = X.shape[-2:]
+    if D > _hip.LO_KERNEL_MAX_DIM or D < 1:
+        return None
+    packed = kernel_sum_pack_families(families)
+    T = len(families)
+    X3 = _flat(X.detach(), 2)
+    if theta.shape != (X3.shape[0], T, D + 1):
+        raise RuntimeError(f"kernel_sum_diag_descriptor: theta of shape {tuple(theta.shape)} for X {tuple(X.shape)}, "
+                           f"{T} terms")
+    return _with_diag(OperatorDescriptor(_hip.LO_OP_KERNEL_SUM_DIAG, X3.shape[0], N, A0=X3, A1=theta.contiguous(), R=D,
+                                         n2=packed, batch_shape=X.shape[:-2], kernel_terms=T), d, const_diag)
+
+
+def _kernel_sum_args(what, x1, x2, theta, families, W):
+    x1, x2, theta, W = x1.contiguous(), x2.contiguous(), theta.contiguous(), W.contiguous()
+    _hip.require_hip(x1, x2, theta, W)
+    kernel_sum_pack_families(families)
+    T = len(families)
+    B, M, D = x1.shape
+    N = W.shape[-2]
+    if x2.shape != (B, N, D) or theta.shape != (B, T, D + 1) or W.shape[0] != B or W.dim() != 3:
+        raise RuntimeError(f"{what}: x1 {tuple(x1.shape)}, x2 {tuple(x2.shape)}, theta {tuple(theta.shape)} for {T} "
+                           f"terms, right operand {tuple(W.shape)}")
+    return x1, x2, theta, W, (C.c_int32 * T)(*[int(f) for f in families]), T
+
+
+def kernel_sum_mv(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, families, v: torch.Tensor,
+                  d: Optional[torch.Tensor] = None, const_diag: bool = False) -> torch.Tensor:
+    """lo_kernel_sum_mv_f32: y [B, M, c] = (sum_t K_t(x1, x2)) v (+ d o v when M == N and d is given), x1 [B, M, D],
+    x2 [B, N, D], theta [B, T, D + 1], `families` the T codes, v [B, N, c].  A shape the kernel does not take raises."""
+    lib = _hip.load()
+    x1, x2, theta, v, fams, T = _kernel_sum_args("kernel_sum_mv", x1, x2, theta, families, v)
+    _hip.require_hip(d)
+    B, M, D = x1.shape
+    N, c = v.shape[-2:]
+    mode = _hip.LO_DIAG_NONE
+    if d is not None:
+        d, mode, _ = _diag_operand(d, B, N, const_diag)
+    y = torch.empty(B, M, c, dtype=torch.float32, device=v.device)
+    _launch("lo_kernel_sum_mv_f32", v.device, x1, x2, theta, fams, T, B, M, N, D, v, c, d, mode, y,
+            ws_bytes=lib.lo_kernel_sum_mv_workspace_bytes(B, M, N, D, T, c))
+    return y
+
+
+def kernel_sum_bilinear(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, families, U: torch.Tensor,
+                        V: torch.Tensor) -> torch.Tensor:
+    """lo_kernel_sum_bilinear_f32: g_theta [B, T, D + 1], every term's derivative of sum_s u_s^T K(x1, x2) v_s with
+    respect to its theta, W_ij = sum_s U[i, s] V[j, s] formed once per pair.  U [B, M, t], V [B, N, t]."""
+    lib = _hip.load()
+    x1, x2, theta, V, fams, T = _kernel_sum_args("kernel_sum_bilinear", x1, x2, theta, families, V)
+    U = U.contiguous()
+    _hip.require_hip(U)
+    B, M, D = x1.shape
+    N, t = V.shape[-2:]
+    if U.shape != (B, M, t):
+        raise RuntimeError(f"kernel_sum_bilinear: U {tuple(U.shape)} for x1 {tuple(x1.shape)}, V {tuple(V.shape)}")
+    g = torch.empty(B, T, D + 1, dtype=torch.float32, device=U.device)
+    _launch("lo_kernel_sum_bilinear_f32", U.device, x1, x2, theta, fams, T, B, M, N, D, U, V, t, g,
+            ws_bytes=lib.lo_kernel_sum_bilinear_workspace_bytes(B, M, N, D, T, t))
+    return g
+
+
+def kernel_sum_points_grad(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, families, U: torch.Tensor,
+                           V: torch.Tensor) -> torch.Tensor:
+    """lo_kernel_sum_points_grad_f32: g_x1 [B, M, D], the derivative of sum_s u_s^T (sum_t K_t(x1, x2)) v_s with respect
+    to x1, x2 held fixed, in one sweep.  The x2 side is kernel_sum_points_grad(x2, x1, theta, families, V, U)."""
+    lib = _hip.load()
+    x1, x2, theta, V, fams, T = _kernel_sum_args("kernel_sum_points_grad", x1, x2, theta, families, V)
+    U = U.contiguous()
+    _hip.require_hip(U)
+    B, M, D = x1.shape
+    N, t = V.shape[-2:]
+    if U.shape != (B, M, t):
+        raise RuntimeError(f"kernel_sum_points_grad: U {tuple(U.shape)} for x1 {tuple(x1.shape)}, V {tuple(V.shape)}")
+    g = torch.empty(B, M, D, dtype=torch.float32, device=U.device)
+    _launch("lo_kernel_sum_points_grad_f32", U.device, x1, x2, theta, fams, T, B, M, N, D, U, V, t, g,
+            ws_bytes=lib.lo_kernel_sum_points_grad_workspace_bytes(B, M, N, D, T, t))
+    return g
+
+
 _MASK_BASE_KINDS = (_hip.LO_OP_LOWRANK_DIAG, _hip.LO_OP_DENSE_DIAG, _hip.LO_OP_KRON_DIAG, _hip.LO_OP_SUM)
 
 
@@ -570,6 +688,8 @@ def masked_descriptor(base_desc: OperatorDescriptor, idx: torch.Tensor, d: Optio
     the C side does not take (the caller composes the product)."""
     if base_desc is None or base_desc.kind not in _MASK_BASE_KINDS or base_desc.dtype != torch.float32:
         return None  # (float64 bases: the masked kernels are fp32)
+    if any(t.kind in (_hip.LO_OP_KERNEL_DIAG, _hip.LO_OP_KERNEL_SUM_DIAG) for t in base_desc.terms):
+        return None  # (a sum's matrix-free kernel terms are not taken under a mask)
     if idx.dtype != torch.int64 or not idx.is_cuda or idx.dim() != 1 or idx.numel() < 1:
         return None
     _hip.require_hip(d)
