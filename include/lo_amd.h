@@ -86,6 +86,10 @@ extern "C" {
 #define LO_OP_KERNEL_SUM_DIAG 12 /* AddedDiag(Kernel_1(X, X) + .. + Kernel_T(X, X), Diag(d)) over ONE point tensor X:
                                   *   y = (sum_t K_t(X, X)) v + d o v, every K_t formed tile by tile in the same pass      */
 #define LO_KERNEL_MAX_TERMS 4    /* kernel terms T one LO_OP_KERNEL_SUM_DIAG descriptor / lo_kernel_sum_* call fuses      */
+#define LO_OP_KERNEL_KRON_DIAG 13 /* AddedDiag(Kron(Kernel(X, X), Bt), Diag(d)), the multitask (coregionalisation) covariance:
+                                   *   y[(i,t)] = sum_j theta_D g(r_ij) sum_s Bt[t,s] v[(j,s)] + d o v, index i T + t (data
+                                   * index slowest, kronecker_product_linear_operator.py:34-45); K never stored            */
+#define LO_KERNEL_KRON_MAX_TASKS 8 /* tasks T (Bt is T x T) the kind and lo_kernel_kron_mv_f32 take (more: LO_ERR_UNSUPPORTED) */
 
 struct lo_interp_desc;
 struct lo_mask_desc;
@@ -111,6 +115,7 @@ typedef struct lo_op_desc {
     const struct lo_interp_desc* interp; /* SKI (ABI 16): HOST pointer to the two interpolation matrices      */
     const struct lo_mask_desc* mask;     /* MASKED (ABI 21): HOST pointer to the base descriptor and the index list */
     const struct lo_grid_desc* grid;     /* TOEPLITZ_KRON (ABI 24): HOST pointer to the grid shape                  */
+    const float* task;                   /* KERNEL_KRON (ABI 29): DEVICE pointer to Bt [B, T, T], used exactly as given */
   };
   /* ABI 16 kinds.  TOEPLITZ: A0 = first column t [B, M] of the symmetric Toeplitz matrix, R = M = N.
    * SKI: A0 = t [B, M], R = M (grid size), n2 = J (interpolation points per row), `interp` as below.
@@ -147,7 +152,14 @@ typedef struct lo_op_desc {
    * LO_OP_MASKED.
    * ABI 28: KERNEL and KERNEL_SUM are term kinds of LO_OP_SUM next to LOWRANK / DENSE / KRON for lo_matvec_f32, the
    * streaming CG, Lanczos, fp32 MINRES and the fp32 pivoted Cholesky (operators over different point tensors, a kernel
-   * plus a low-rank root); a sum that holds one is refused by the fp64 entry points and as the base of LO_OP_MASKED.   */
+   * plus a low-rank root); a sum that holds one is refused by the fp64 entry points and as the base of LO_OP_MASKED.
+   * ABI 29 kind.  KERNEL_KRON: A0 = X [B, n, D], R = D <= LO_KERNEL_MAX_DIM, A1 = theta [B, D + 1] exactly as for KERNEL,
+   * n2 = one family code LO_KERNEL_*, nterms = T in 1 .. LO_KERNEL_KRON_MAX_TASKS, N = n T, `task` = Bt [B, T, T] on the
+   * DEVICE (same layout again: `task` is one more member of the union).  Bt is used as given, symmetric or not.  Lowered
+   * for lo_matvec_f32, the streaming CG, Lanczos, fp32 MINRES and the fp32 pivoted Cholesky (diagonal theta[D] Bt[t,t],
+   * row (p, tau): row[j T + s] = (theta[D] g(r_pj)) Bt[tau, s]); the fp64 entry points, the resident / fused engines and
+   * the solve sessions return LO_ERR_UNSUPPORTED; not a term kind of LO_OP_SUM, not a base kind of LO_OP_MASKED.
+   * LO_ERR_BADARG: a null A0 / A1 / task, R < 1, a family outside 0 .. 3, T < 1, N % T != 0.                          */
 } lo_op_desc;
 
 /* The grid shape of an LO_OP_TOEPLITZ_KRON_DIAG descriptor (host struct). */
@@ -939,6 +951,20 @@ size_t lo_kernel_sum_points_grad_workspace_bytes(int64_t B, int64_t M, int64_t N
 int lo_kernel_sum_points_grad_f32(const float* x1, const float* x2, const float* theta, const int32_t* families, int64_t T,
                                   int64_t B, int64_t M, int64_t N, int64_t D, const float* U, const float* V, int64_t t,
                                   float* g_x1, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- matrix-free multitask operator Kernel(X, X) (x) Bt (ABI 29; csrc/lo_kernel_kron.hip) -------------------------------
+ * y [B, n T, c] = (K(X, X) (x) Bt) v (+ d o v), row and column index i T + t:
+ *   y[(i,t), col] = sum_j theta[D] g(r_ij) sum_s Bt[t,s] v[(j,s), col] + d[(i,t)] v[(i,t), col]
+ * x [B, n, D], theta [B, D + 1] and `family` as for lo_kernel_mv_f32, task = Bt [B, T, T] (not required symmetric),
+ * v [B, n T, c], d per diag_mode over the n T rows.  One sweep of the pairs carries up to 32 of the T c "wide" columns;
+ * Bt is applied while the tile of v is staged.  Launch shape, splits of the points j and the order of the sums as in
+ * lo_kernel_mv_f32: fixed-order sums, no atomics, two calls give equal bits.
+ * LO_ERR_BADARG: a null pointer, a non-positive size, family outside 0 .. 3, T < 1, an unknown diag_mode or one without d;
+ * LO_ERR_UNSUPPORTED: D > LO_KERNEL_MAX_DIM, T > LO_KERNEL_KRON_MAX_TASKS; LO_ERR_WORKSPACE before any launch.           */
+size_t lo_kernel_kron_mv_workspace_bytes(int64_t B, int64_t n, int64_t D, int64_t T, int64_t c);
+int lo_kernel_kron_mv_f32(const float* x, const float* theta, const float* task, int32_t family, int64_t B, int64_t n,
+                          int64_t D, int64_t T, const float* v, int64_t c, const float* d, int32_t diag_mode, float* y,
+                          void* ws, size_t ws_bytes, void* stream);
 
 /* ---- exact small-N path: batched Cholesky and triangular solves (ABI 18; csrc/lo_chol.hip) -------------------------
  * fp32, contiguous row-major, N <= 1024 (larger: LO_ERR_UNSUPPORTED), stream-ordered; fixed-order sums, no atomics: a

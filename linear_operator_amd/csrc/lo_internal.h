@@ -249,6 +249,15 @@ int kernel_sum_matvec_run(const MatvecPlan* pl, const float* v, float* y, const 
 // LO_OK, or why the descriptor of that kind is refused (the pivoted Cholesky validates it without a plan)
 int kernel_sum_desc_check(const lo_op_desc* op);
 
+// ---- matrix-free multitask operator Kernel(X, X) (x) Bt (lo_kernel_kron.hip): LO_OP_KERNEL_KRON_DIAG -------------------
+struct KernelKronPlan {
+  float* part;  // [js, B, n, T c] partial products when the points j of a member are split over js workgroups, else nullptr
+};
+int kernel_kron_plan(MatvecPlan* pl, Arena* ar, hipStream_t st);
+int kernel_kron_matvec_run(const MatvecPlan* pl, const float* v, float* y, const int* stop, hipStream_t st);
+// LO_OK, or why the descriptor of that kind is refused (the pivoted Cholesky validates it without a plan)
+int kernel_kron_desc_check(const lo_op_desc* op);
+
 // ---- masked operator (lo_masked.hip) ---------------------------------------------------------------------------------
 struct MaskedPlan {      // (the base's plan is MatvecPlan::sub[0])
   const int64_t* idx;    // [M]
@@ -284,6 +293,7 @@ struct MatvecPlan {
     ToeplitzKronPlan tk;
     HadamardPlan hd;
     KernelOpPlan ko;
+    KernelKronPlan kk;
     MaskedPlan mask;
   };
 };

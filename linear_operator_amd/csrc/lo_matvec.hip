@@ -152,6 +152,7 @@ int matvec_plan_init(MatvecPlan* pl, const lo_op_desc* op, lo_matvec_cb cb, void
     case LO_OP_HADAMARD_DIAG: rc = hadamard_plan(pl, ar, st); break;
     case LO_OP_KERNEL_DIAG: rc = kernel_op_plan(pl, ar, st); break;
     case LO_OP_KERNEL_SUM_DIAG: rc = kernel_sum_plan(pl, ar, st); break;
+    case LO_OP_KERNEL_KRON_DIAG: rc = kernel_kron_plan(pl, ar, st); break;
     case LO_OP_MASKED: rc = masked_plan(pl, ar, st); break;
     case LO_OP_CALLBACK: rc = cb ? LO_OK : LO_ERR_BADARG; break;
     case LO_OP_SUM: rc = sum_plan(pl, ar, st); break;
@@ -194,6 +195,8 @@ int matvec_run(const MatvecPlan* pl, const float* v, float* y, float* dot_part, 
       rc = kernel_op_matvec_run(pl, v, y, stop, st); break;
     case LO_OP_KERNEL_SUM_DIAG:  // (sum_t K_t(X, X)) v + d o v in one pass over the pairs (lo_kernel_sum.hip)
       rc = kernel_sum_matvec_run(pl, v, y, stop, st); break;
+    case LO_OP_KERNEL_KRON_DIAG:  // (K(X, X) (x) Bt) v + d o v, Bt applied while the tile of v is staged (lo_kernel_kron.hip)
+      rc = kernel_kron_matvec_run(pl, v, y, stop, st); break;
     case LO_OP_MASKED:  // S (base) S^T v + d o v: expand, the base's product (or the selected rows of a dense base), gather
       rc = masked_matvec_run(pl, v, y, stop, st); break;
     case LO_OP_CALLBACK: rc = pl->cb(pl->cb_user, v, y, op.B, op.N, pl->c, (void*)st) ? LO_ERR_LAUNCH : LO_OK; break;
@@ -223,7 +226,7 @@ using namespace lo;
 
 extern "C" {
 
-int lo_abi_version(void) { return 28; }
+int lo_abi_version(void) { return 29; }
 const char* lo_target_arch(void) { return "gfx950"; }
 
 size_t lo_matvec_workspace_bytes(const lo_op_desc* op, int64_t c) {

@@ -137,6 +137,9 @@ __device__ __forceinline__ T src_diag(const PcDevT<T>& d, const lo_op_desc& op, 
     float s = th[op.R];
     for (int t = 1; t < op.nterms; ++t) s = s + th[(size_t)t * (op.R + 1) + op.R];
     return (T)s;
+  } else if (op.kind == LO_OP_KERNEL_KRON_DIAG) {  // row i = (p, tau): os2 g(0) Bt[tau, tau] = os2 Bt[tau, tau]
+    const int nt = op.nterms, tau = i % nt;
+    return (T)(op.A1[(size_t)b * (op.R + 1) + op.R] * op.task[((size_t)b * nt + tau) * nt + tau]);
   } else if (op.kind == LO_OP_TOEPLITZ_KRON_DIAG) {
     // prod_k t_k[0], the trailing factors multiplied first (kronecker_product_linear_operator.py:22-28)
     const int D = d.ski.grid_ndim;
@@ -487,6 +490,18 @@ __global__ __launch_bounds__(kThreads) void k_pc_update(PcDevT<T> d, int m) {
             s = t == 0 ? kt : s + kt;
           }
           tv = (T)s;
+        } else if (tm.kind == LO_OP_KERNEL_KRON_DIAG) {  // pivot (p, tau), entry (j, s): (os2 g(r_pj)) Bt[tau, s]
+          const int D = (int)tm.R, nt = tm.nterms;
+          const int n = N / nt, pp = pim / nt, tau = pim - pp * nt, jj = i / nt, ss = i - jj * nt;
+          const float* th = tm.A1 + (size_t)b * (D + 1);
+          const float* xp = tm.A0 + ((size_t)b * n + pp) * D;
+          const float* xi = tm.A0 + ((size_t)b * n + jj) * D;
+          float r2 = 0.0f;
+          for (int k = 0; k < D; ++k) {
+            const float df = xp[k] * th[k] - xi[k] * th[k];
+            r2 = r2 + df * df;
+          }
+          tv = (T)((th[D] * kf_g_rt((int)tm.n2, r2)) * tm.task[((size_t)b * nt + tau) * nt + ss]);
         } else if (tm.kind == LO_OP_TOEPLITZ_KRON_DIAG) {
           // prod_k t_k[|p_k - i_k|], factors multiplied left to right (kronecker_product_linear_operator.py:198-216);
           // consecutive threads hold consecutive positions j: the gathers from the (small) columns stay in cache
@@ -733,6 +748,8 @@ static int pc_check_desc(const lo_op_desc* op, bool fp32_kinds = true) {
     if (const int rc = pc_check_kernel(op)) return rc;
   } else if (op->kind == LO_OP_KERNEL_SUM_DIAG) {
     if (const int rc = kernel_sum_desc_check(op)) return rc;
+  } else if (op->kind == LO_OP_KERNEL_KRON_DIAG) {
+    if (const int rc = kernel_kron_desc_check(op)) return rc;
   } else if (op->kind == LO_OP_SKI_DIAG) {
     const lo_interp_desc* w = op->interp;
     if (!op->A0 || op->R < 1 || op->n2 < 1 || !w || !w->left_idx || !w->left_vals || !w->right_idx || !w->right_vals)
@@ -829,7 +846,8 @@ int lo_pivoted_cholesky_f64(const lo_op_desc* op, int32_t max_rank, double error
                             int32_t* rank_out, void* ws, size_t ws_bytes, void* stream) {
   if (!op || !L_rows || !perm || !rank_out || !ws || max_rank < 1) return LO_ERR_BADARG;
   if (op->kind == LO_OP_SKI_DIAG || op->kind == LO_OP_TOEPLITZ_DIAG || op->kind == LO_OP_HADAMARD_DIAG ||
-      op->kind == LO_OP_SKI_GRID_DIAG || op->kind == LO_OP_TOEPLITZ_KRON_DIAG || kernel_term_kind(op->kind))
+      op->kind == LO_OP_SKI_GRID_DIAG || op->kind == LO_OP_TOEPLITZ_KRON_DIAG || kernel_term_kind(op->kind) ||
+      op->kind == LO_OP_KERNEL_KRON_DIAG)
     return LO_ERR_UNSUPPORTED;  // (fp32 kinds)
   if (const int rc = pc_check_desc(op, false)) return rc;
   return pc_stream_t<double>(op, nullptr, nullptr, nullptr, max_rank, error_tol, L_rows, perm, rank_out, ws, ws_bytes,

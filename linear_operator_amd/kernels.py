@@ -29,6 +29,7 @@ class OperatorDescriptor:
     A0: Optional[torch.Tensor] = None  # C [B,N,R] | K [B,N,N] | K1 [B,n1,n1]
     # K2 [B,n2,n2] | G [B,N,q] (Hadamard: A0 = F [B,N,p]) | theta [B,D+1] (Kernel: A0 = X [B,N,D], R = D, n2 = family)
     # | theta [B,T,D+1] (KernelSum: A0 = X, R = D, n2 = the packed families, kernel_terms = T)
+    # | theta [B,D+1] (KernelKron: A0 = X [B,n,D], R = D, n2 = family, kernel_terms = T, task = Bt, N = n T)
     A1: Optional[torch.Tensor] = None
     d: Optional[torch.Tensor] = None  # [B,N] (FULL) or [B] (CONST)
     diag_mode: int = _hip.LO_DIAG_NONE
@@ -46,7 +47,9 @@ class OperatorDescriptor:
     # sums of those) go to lo_matvec_f64 and the float64 solvers only, and c_struct() refuses to hand one to an entry
     # point that reads `float*`
     dtype: torch.dtype = torch.float32
-    kernel_terms: int = 0  # LO_OP_KERNEL_SUM_DIAG: T, the struct's `nterms` (the kind has no `terms`)
+    # LO_OP_KERNEL_SUM_DIAG: T, the struct's `nterms` (the kind has no `terms`); LO_OP_KERNEL_KRON_DIAG: the tasks T
+    kernel_terms: int = 0
+    task: Optional[torch.Tensor] = None  # LO_OP_KERNEL_KRON_DIAG: Bt [B, T, T], the union slot `task` (a DEVICE pointer)
 
     @property
     def device(self):
@@ -89,6 +92,8 @@ class OperatorDescriptor:
             g = _hip.GridDesc(len(self.grid), 0, (C.c_int64 * 3)(*self.grid))
             s.terms = C.cast(C.pointer(g), C.POINTER(_hip.OpDesc))
             s._grid_keepalive = g
+        if self.task is not None:  # the union slot `task`: the device pointer itself
+            s.terms = C.cast(C.c_void_p(self.task.data_ptr()), C.POINTER(_hip.OpDesc))
         if self.mask:  # the union slot `mask`: a host struct of the base's host descriptor and the device index list
             base = self.mask[0].c_struct()
             m = _hip.MaskDesc(C.pointer(base), self.mask[1].data_ptr(), self.mask[1].numel())
@@ -99,7 +104,7 @@ class OperatorDescriptor:
     def without_diag(self) -> "OperatorDescriptor":
         return OperatorDescriptor(self.kind, self.B, self.N, self.A0, self.A1, None, _hip.LO_DIAG_NONE, self.R,
                                   self.n2, self.batch_shape, self.terms, self.interp, self.interp_plan, self.mask,
-                                  self.grid, self.dtype, self.kernel_terms)
+                                  self.grid, self.dtype, self.kernel_terms, self.task)
 
 
 def _check_dtype(dtype, *tensors):
@@ -675,6 +680,48 @@ def kernel_sum_points_grad(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tens
     _launch("lo_kernel_sum_points_grad_f32", U.device, x1, x2, theta, fams, T, B, M, N, D, U, V, t, g,
             ws_bytes=lib.lo_kernel_sum_points_grad_workspace_bytes(B, M, N, D, T, t))
     return g
+
+
+def kernel_kron_diag_descriptor(X: torch.Tensor, theta: torch.Tensor, family: int, task: torch.Tensor,
+                                d: Optional[torch.Tensor] = None, const_diag: bool = False):
+    """AddedDiag(Kron(Kernel(X, X, family), Bt), Diag(d)) (or the product alone), the multitask covariance with row index
+    i T + t: y = (K (x) Bt) v + d o v, K formed on the fly and Bt applied while v is staged (csrc/lo_kernel_kron.hip).
+    X [*batch, n, D], theta [B, D + 1] from kernel_theta, task = Bt [*batch, T, T].  None when D exceeds LO_KERNEL_MAX_DIM
+    or T exceeds LO_KERNEL_KRON_MAX_TASKS (the caller composes the factors)."""
+    _hip.require_hip(X, theta, task, d)
+    n, D = X.shape[-2:]
+    T = task.shape[-1]
+    if D > _hip.LO_KERNEL_MAX_DIM or D < 1 or not 1 <= T <= _hip.LO_KERNEL_KRON_MAX_TASKS:
+        return None
+    X3, Bt = _flat(X.detach(), 2), _flat(task.detach(), 2)
+    if theta.shape != (X3.shape[0], D + 1) or Bt.shape != (X3.shape[0], T, T):
+        raise RuntimeError(f"kernel_kron_diag_descriptor: theta {tuple(theta.shape)}, task {tuple(task.shape)} for X "
+                           f"{tuple(X.shape)}")
+    return _with_diag(OperatorDescriptor(_hip.LO_OP_KERNEL_KRON_DIAG, X3.shape[0], n * T, A0=X3, A1=theta, R=D,
+                                         n2=int(family), batch_shape=X.shape[:-2], kernel_terms=T, task=Bt), d, const_diag)
+
+
+def kernel_kron_mv(x: torch.Tensor, theta: torch.Tensor, task: torch.Tensor, family: int, v: torch.Tensor,
+                   d: Optional[torch.Tensor] = None, const_diag: bool = False) -> torch.Tensor:
+    """lo_kernel_kron_mv_f32: y [B, n T, c] = (K(x, x) (x) Bt) v (+ d o v), x [B, n, D], theta [B, D + 1], task = Bt
+    [B, T, T] (used as given, symmetric or not), v [B, n T, c], row index i T + t.  A shape the kernel does not take
+    raises."""
+    lib = _hip.load()
+    x, theta, task, v = x.contiguous(), theta.contiguous(), task.contiguous(), v.contiguous()
+    _hip.require_hip(x, theta, task, v, d)
+    B, n, D = x.shape
+    T = task.shape[-1]
+    N, c = v.shape[-2:]
+    if theta.shape != (B, D + 1) or task.shape != (B, T, T) or v.shape[0] != B or N != n * T:
+        raise RuntimeError(f"kernel_kron_mv: x {tuple(x.shape)}, theta {tuple(theta.shape)}, task {tuple(task.shape)}, "
+                           f"v {tuple(v.shape)}")
+    mode = _hip.LO_DIAG_NONE
+    if d is not None:
+        d, mode, _ = _diag_operand(d, B, N, const_diag)
+    y = torch.empty(B, N, c, dtype=torch.float32, device=v.device)
+    _launch("lo_kernel_kron_mv_f32", v.device, x, theta, task, int(family), B, n, D, T, v, c, d, mode, y,
+            ws_bytes=lib.lo_kernel_kron_mv_workspace_bytes(B, n, D, T, c))
+    return y
 
 
 _MASK_BASE_KINDS = (_hip.LO_OP_LOWRANK_DIAG, _hip.LO_OP_DENSE_DIAG, _hip.LO_OP_KRON_DIAG, _hip.LO_OP_SUM)

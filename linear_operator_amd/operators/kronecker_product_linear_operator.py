@@ -4,12 +4,26 @@ lower to the batched-GEMM kernel pair in csrc/lo_kron.hip; products of more dens
 dense groups (`_two_groups`) and lower the same way.  A product of 2 or 3 symmetric Toeplitz factors (the covariance of
 a GP on a regular 2-D / 3-D grid) lowers to LO_OP_TOEPLITZ_KRON_DIAG (csrc/lo_ski_grid.hip), and the gradients with
 respect to the factors' columns come from lo_toeplitz_kron_bilinear_f32 or, outside its limits, from the same closed
-form in torch.  `+ Diag` / `add_diagonal` build the
+form in torch.
+
+Multitask covariance, matrix-free.  Kron(KernelLinearOperator(X, X), Dense(Bt)) with a native kernel factor over one
+points tensor and a float32 device task factor Bt [*b, T, T], T <= LO_KERNEL_KRON_MAX_TASKS (`_kernel_kron_refusal`),
+lowers to LO_OP_KERNEL_KRON_DIAG (csrc/lo_kernel_kron.hip): CG, Lanczos, MINRES and the pivoted Cholesky run on the
+device without a Python call per product and without K (x) Bt or K in memory.  `_matmul` itself goes to the fused
+product only for the (T, columns) cells of `_NATIVE_MATMUL_KERNEL_KRON`; elsewhere it keeps the per-factor composition,
+whose kernel factor is matrix-free already.  `_bilinear_derivative` composes the kernel factor's native derivatives
+with one on-the-fly product for Bt; no autograd, nothing of size n^2.  The matrix-free route to a solve is the explicit
+AddedDiagLinearOperator(kron, DiagLinearOperator(d)), or KroneckerProductAddedDiag with a general diagonal: `+` and
+`add_diagonal` are routed as before, so a constant or Kronecker-structured diagonal keeps the reference's
+eigendecomposition forms (which take the dense n x n data kernel).
+
+`+ Diag` / `add_diagonal` build the
 KroneckerProductAddedDiagLinearOperator like the reference (:98-145): eigendecomposition closed forms for a
 constant diagonal, the CG path otherwise (an explicit AddedDiagLinearOperator(kron, diag) is always the CG path)."""
 from __future__ import annotations
 
 import math
+from typing import Optional
 
 import torch
 from torch import Tensor
@@ -21,6 +35,7 @@ from ..utils.toeplitz import sym_toeplitz_derivative_quadratic_form, sym_toeplit
 from ._linear_operator import LinearOperator
 from .dense_linear_operator import DenseLinearOperator, to_linear_operator
 from .diag_linear_operator import DiagLinearOperator
+from .kernel_linear_operator import KernelLinearOperator
 from .toeplitz_linear_operator import ToeplitzLinearOperator
 
 # Which products of a Kronecker product of Toeplitz factors `_matmul` hands to the kernels, by (axes, one column / more
@@ -32,6 +47,18 @@ from .toeplitz_linear_operator import ToeplitzLinearOperator
 #   2-D  16 x 64 (x) 64             17 /   118      34 /  1883
 #   3-D  1 x 32 (x) 32 (x) 32       21 /  2382      31 / 40654
 _NATIVE_MATMUL_TOEPLITZ: dict = {(2, 1): True, (2, 2): True, (3, 1): True, (3, 2): True}
+
+
+# Which products of Kron(Kernel, Dense(Bt)) `_matmul` hands to the fused kernel lo_kernel_kron_mv_f32, by (T, one column /
+# more columns): True only where tools/mb_kernel_kron.py measured it at least as fast, beyond the spread of the rounds, as
+# the per-factor composition (`_kron_matmul`: lo_kernel_mv_f32 with T c columns, then Bt) at BOTH measured shapes.  An
+# absent cell keeps the composition; the descriptor lowers always.  Measured on the MI355X (fused / composition,
+# microseconds; 1 x 16384, D 4 and 8 x 4096, D 16):
+#   T 2   1 column  145 /  161,  203 /  224     17 columns   754 /  795 (ranges overlap),   681 /  940
+#   T 4   1 column  143 /  160,  205 /  229     17 columns  1358 / 1314,                   1120 / 1534
+#   T 8   1 column  290 /  262,  306 /  314     17 columns  3146 / 2347,                   2264 / 2703
+# T = 3 was not measured and takes the side its two neighbours share.
+_NATIVE_MATMUL_KERNEL_KRON: dict = {(2, 1): True, (3, 1): True, (4, 1): True}
 
 
 def _kron_diag(*ops) -> Tensor:
@@ -171,7 +198,45 @@ class KroneckerProductLinearOperator(LinearOperator):
         return (all(t.is_cuda and t.dtype == torch.float32 for t in cols)
                 and K.ski_grid_shape_ok(tuple(int(t.shape[-1]) for t in cols)))
 
+    def _kernel_kron_refusal(self, check_device: bool = True) -> Optional[str]:
+        """None when this product is the matrix-free multitask operator the kind LO_OP_KERNEL_KRON_DIAG takes, else the
+        reason it is not.  `check_device=False` leaves out the on-the-device conditions, as KernelLinearOperator's
+        `_native_refusal` does (the rest of the gate can then be asked on any machine)."""
+        ops = self.linear_ops
+        if len(ops) != 2:
+            return f"{len(ops)} factors"
+        kern, task = ops
+        if not isinstance(kern, KernelLinearOperator):
+            return "the first factor is not a KernelLinearOperator"
+        why = kern._native_refusal(check_device)
+        if why is not None:
+            return f"kernel factor: {why}"
+        if not kern._same_points():
+            return "kernel factor over two different point tensors"
+        if not isinstance(task, DenseLinearOperator):
+            return "the task factor is not a DenseLinearOperator"
+        Bt = task.tensor
+        if Bt.dim() < 2 or Bt.shape[-1] != Bt.shape[-2]:
+            return f"task factor of shape {tuple(Bt.shape)}"
+        if Bt.shape[-1] > K._hip.LO_KERNEL_KRON_MAX_TASKS:
+            return f"T = {Bt.shape[-1]} beyond LO_KERNEL_KRON_MAX_TASKS"
+        if Bt.dtype != torch.float32:
+            return "task factor not float32"
+        if check_device and not Bt.is_cuda:
+            return "task factor not on the device"
+        return None
+
+    def _kernel_kron_descriptor(self, bs):
+        kern, task = self.linear_ops
+        X = kern.x1.detach()
+        X = X if X.shape[:-2] == bs else X.expand(*bs, *X.shape[-2:])
+        Bt = task.tensor.detach()
+        Bt = Bt if Bt.shape[:-2] == bs else Bt.expand(*bs, *Bt.shape[-2:])
+        return K.kernel_kron_diag_descriptor(X, kern._theta(bs), kern.covar_func.native_family, Bt)
+
     def _kernel_descriptor(self, batch_shape=None):
+        if self._kernel_kron_refusal() is None:
+            return self._kernel_kron_descriptor(torch.Size(self.batch_shape if batch_shape is None else batch_shape))
         cols = self._toeplitz_columns()
         if cols is not None:
             if not self._toeplitz_native(cols):
@@ -193,6 +258,9 @@ class KroneckerProductLinearOperator(LinearOperator):
         cols = self._toeplitz_columns()
         if cols is not None:
             return self._toeplitz_bilinear_derivative(cols, left_vecs, right_vecs)
+        if (len(self.linear_ops) == 2 and isinstance(self.linear_ops[0], KernelLinearOperator)
+                and isinstance(self.linear_ops[1], DenseLinearOperator)):
+            return self._kernel_kron_bilinear_derivative(left_vecs, right_vecs)
         groups = self._two_groups()
         if groups is None:
             return super()._bilinear_derivative(left_vecs, right_vecs)
@@ -201,6 +269,30 @@ class KroneckerProductLinearOperator(LinearOperator):
         ts = [op.tensor for op in self.linear_ops]
         grads = _group_pullback(d1, ts[:j]) + _group_pullback(d2, ts[j:])
         return tuple(g if tuple(g.shape) == tuple(t.shape) else g.sum_to_size(*t.shape) for g, t in zip(grads, ts))
+
+    def _kernel_kron_bilinear_derivative(self, left_vecs: Tensor, right_vecs: Tensor):
+        """Kron(Kernel, Dense(Bt)), row index i T + t, by composition -- no autograd of the product, nothing of size
+        n^2.  With U3 = U viewed as [*b, m, T s] and VB3 the same view of V with Bt applied to the task index of every row,
+        sum_col u^T (K (x) Bt) v = sum_col' U3^T K VB3: the kernel factor's own derivative (lo_kernel_bilinear_f32 and
+        lo_kernel_points_grad_f32 on the native path).  dBt[tau, s] = sum_{i, col} U[(i, tau), col] (K V3)[(i, s), col]:
+        one product of the kernel factor with T s columns (lo_kernel_mv_f32) and a contraction."""
+        kern, task = self.linear_ops
+        if left_vecs.ndimension() == 1:
+            left_vecs, right_vecs = left_vecs.unsqueeze(-1), right_vecs.unsqueeze(-1)
+        Bt = task.tensor
+        T, S = Bt.shape[-1], left_vecs.shape[-1]
+        m, n = kern.shape[-2:]
+        bs = torch.broadcast_shapes(self.batch_shape, left_vecs.shape[:-2], right_vecs.shape[:-2])
+        U4 = left_vecs.detach().expand(*bs, m * T, S).reshape(*bs, m, T, S)
+        V4 = right_vecs.detach().expand(*bs, n * T, S).reshape(*bs, n, T, S)
+        VB4 = torch.einsum("...ts,...jsc->...jtc", Bt.detach(), V4)
+        g_kern = kern._bilinear_derivative(U4.reshape(*bs, m, T * S), VB4.reshape(*bs, n, T * S))
+        g_task = None
+        if Bt.requires_grad:
+            KV4 = kern._matmul(V4.reshape(*bs, n, T * S)).reshape(*bs, m, T, S)
+            g_task = torch.einsum("...itc,...isc->...ts", U4, KV4)
+            g_task = g_task if tuple(g_task.shape) == tuple(Bt.shape) else g_task.sum_to_size(*Bt.shape)
+        return tuple(g_kern) + (g_task,)
 
     def _toeplitz_bilinear_derivative(self, cols, left_vecs: Tensor, right_vecs: Tensor):
         """One gradient per factor column.  With W_k = v with every factor but T_k applied, u and W_k viewed as
@@ -309,6 +401,17 @@ class KroneckerProductLinearOperator(LinearOperator):
         is_vec = rhs.ndimension() == 1
         if is_vec:
             rhs = rhs.unsqueeze(-1)
+        if rhs.is_cuda and rhs.dtype == torch.float32 and self._kernel_kron_refusal() is None:
+            T = self.linear_ops[1].shape[-1]
+            if _NATIVE_MATMUL_KERNEL_KRON.get((T, 1 if rhs.shape[-1] == 1 else 2), False):
+                bs = torch.broadcast_shapes(self.batch_shape, rhs.shape[:-2])
+                desc = self._kernel_kron_descriptor(bs)
+                res = K.kernel_kron_mv(desc.A0, desc.A1, desc.task, desc.n2,
+                                       rhs.detach().expand(*bs, *rhs.shape[-2:]).reshape(-1, *rhs.shape[-2:]))
+                res = res.reshape(*bs, *res.shape[-2:])
+            else:  # (the per-factor composition; its kernel factor is matrix-free)
+                res = _kron_matmul(self.linear_ops, self.shape, rhs.contiguous())
+            return res.squeeze(-1) if is_vec else res
         desc = None
         if K.native_matmul_candidate(self, rhs) and (
                 self._toeplitz_columns() is None
