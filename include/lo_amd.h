@@ -317,7 +317,13 @@ int lo_matvec_f32(const lo_op_desc* op, const float* v, float* y, int64_t c, voi
  * ends inside the resident launches, the status block arrives through pinned host memory (a ticket the control kernel
  * writes last) and the call returns without a hipStreamSynchronize: work the caller queued on `stream` BEFORE the call
  * is complete, but the stream's tail event may not have retired yet -- order later work by the stream, not by the
- * host.  Otherwise polls the device stop flag between launch chunks.                                       */
+ * host.  Otherwise polls the device stop flag between launch chunks.
+ * Resident single-column solve (k_cg_rspace3; lo_cg_session_solve_f32 too): when the call returns, `info` is FINAL and x
+ * is complete IN STREAM ORDER -- work on `stream`, or on a stream that waits for it, sees all of x; a reader that
+ * bypasses stream order (a host read of mapped memory, another stream without an event) does not.  This has always
+ * been so: the ticket was written by one workgroup of the last group behind its own x pass while the group's other
+ * workgroups could still be storing x.  The kernel now sends it in front of that pass (nothing the ticket reports
+ * depends on x); with peer buffers installed (lo_peer_gather_set) it still leaves behind the pass.            */
 size_t lo_cg_workspace_bytes(const lo_op_desc* op, const lo_precond_desc* pre, const lo_cg_params* prm);
 int lo_cg_solve_f32(const lo_op_desc* op, lo_matvec_cb matvec, void* matvec_user, const lo_precond_desc* pre,
                     lo_matvec_cb precond_cb, void* precond_user, const lo_cg_params* prm, const float* rhs,

@@ -151,6 +151,7 @@ __global__ __launch_bounds__(R3_TPB, 2) void k_cg_rspace3(OnchipArgs a, PeerOut 
       for (int i = 0; i < 8; ++i) dst[8 * q + i] = *(g_cf4*)(bq + loff + (i - 4) * 1024);
     }
   };
+  int closed = 0;  // workgroup-uniform: this workgroup has run the closing step (inside the loop, below)
   int64_t b = grp;
   {
     int tl0 = t;
@@ -538,6 +539,29 @@ __global__ __launch_bounds__(R3_TPB, 2) void k_cg_rspace3(OnchipArgs a, PeerOut 
       if (hf == 0) myv[j] = yj * (double)nrm;
       __builtin_amdgcn_wave_barrier();
     }
+    // ---- the group's final member: close the solve HERE, in front of the x pass (lo_cg_close.h) ----
+    // The closing step reads the members' close granules, the error word and the counters, nothing of x: the host's
+    // ticket need not wait for this pass (2.3 - 2.5 us), and x was complete in stream order only before as well (the
+    // ticket used to leave after workgroup 0's own x pass, with the group's other workgroups still storing).  Why the
+    // helper's conditions hold at this point:
+    //   (1) b_next = ngroups + the value this member's draw returned, and it is >= B: the group's LAST draw from
+    //       next_member has returned (the loop ends with this member, nobody of the group draws again);
+    //   (2) the exchange above was the group's last, and workgroup 0 saw the granules of all GW workgroups in it: a
+    //       sibling that is still polling them can only find them, so nobody of this group sets the error word any more;
+    //   (3) the member's state and close granule were stored behind the chain above, those of the group's earlier members
+    //       before.  (The call sits behind y, not behind those stores: here only C, xi and the stage pointers are live.)
+    // Uniform over the workgroup (res[] is LDS, wig and po.n are scalars): the barriers inside the helper are legal.
+    // With peer buffers the close stays behind the x pass: a rank that has seen its solve return has issued its peer stores.
+    if (a.close_gran && wig == 0 && po.n == 0 && __builtin_amdgcn_readfirstlane((int)(b_next >= a.B))) {
+      int tc = (int)threadIdx.x;  // (opaque: what the helper derives from it is formed here, not kept around the loop)
+      asm volatile("" : "+v"(tc));
+      cg_close_solve(a, ngroups, tc);
+      closed = 1;
+      // (no next member: pre[] holds zeros.  Defined again behind the call, its 32 registers are dead across it and
+      //  the closing step needs none that C or the x pass occupy: 0 spills)
+#pragma unroll
+      for (int i = 0; i < NPF; ++i) pre[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
     if (!(a.prefetch & 2)) __builtin_amdgcn_s_setprio(0);
     if (stamp) a.dbg[3] = wall_clock64();
     // ---- x = nrm D^-1 (xi r0 + C y) = D^-1 (xi b + C (nrm y)), fp64 (for small diagonals the two terms cancel) ----
@@ -586,7 +610,12 @@ __global__ __launch_bounds__(R3_TPB, 2) void k_cg_rspace3(OnchipArgs a, PeerOut 
     __syncthreads();  // the next member's matrices / stages may replace these from here on
     b = b_next;
   }
-  if (a.close_gran && wig == 0) cg_close_solve(a, ngroups, t);
+  // (not closed yet: a group that never entered the loop -- fewer members than groups --, or peer buffers installed)
+  if (a.close_gran && wig == 0 && !closed) {
+    int te = (int)threadIdx.x;
+    asm volatile("" : "+v"(te));
+    cg_close_solve(a, ngroups, te);
+  }
 }
 
 // LO_RS_PRIO: wave-priority mask of the latency-critical phases, read once per process
