@@ -90,6 +90,11 @@ extern "C" {
                                    *   y[(i,t)] = sum_j theta_D g(r_ij) sum_s Bt[t,s] v[(j,s)] + d o v, index i T + t (data
                                    * index slowest, kronecker_product_linear_operator.py:34-45); K never stored            */
 #define LO_KERNEL_KRON_MAX_TASKS 8 /* tasks T (Bt is T x T) the kind and lo_kernel_kron_mv_f32 take (more: LO_ERR_UNSUPPORTED) */
+#define LO_OP_KERNEL_GRAD_DIAG 14 /* AddedDiag(GradKernel(X, X), Diag(d)): the covariance of the values AND the D partial
+                                   * derivatives of a GP at n points (a GP with derivative observations), D + 1 outputs per
+                                   * input, index i (D + 1) + a (data index slowest, a = 0 the value, a = 1 .. D the
+                                   * derivative in coordinate a - 1); the n (D + 1) x n (D + 1) matrix is never stored    */
+#define LO_KERNEL_GRAD_MAX_DIM 16 /* input dimensions D the kind and lo_kernel_grad_* take (more: LO_ERR_UNSUPPORTED)      */
 
 struct lo_interp_desc;
 struct lo_mask_desc;
@@ -159,7 +164,16 @@ typedef struct lo_op_desc {
    * for lo_matvec_f32, the streaming CG, Lanczos, fp32 MINRES and the fp32 pivoted Cholesky (diagonal theta[D] Bt[t,t],
    * row (p, tau): row[j T + s] = (theta[D] g(r_pj)) Bt[tau, s]); the fp64 entry points, the resident / fused engines and
    * the solve sessions return LO_ERR_UNSUPPORTED; not a term kind of LO_OP_SUM, not a base kind of LO_OP_MASKED.
-   * LO_ERR_BADARG: a null A0 / A1 / task, R < 1, a family outside 0 .. 3, T < 1, N % T != 0.                          */
+   * LO_ERR_BADARG: a null A0 / A1 / task, R < 1, a family outside 0 .. 3, T < 1, N % T != 0.
+   * ABI 30 kind.  KERNEL_GRAD: A0 = X [B, n, D], R = D <= LO_KERNEL_GRAD_MAX_DIM, A1 = theta [B, D + 1] exactly as for
+   * KERNEL, n2 = the family code (LO_KERNEL_RBF only), N = n (D + 1), nterms = 0, no new member.  With t_k = theta[k],
+   * u_k = t_k (x_i[k] - x_j[k]), e = exp(-|u|^2 / 2), the block of the pair (i, j) is (a, b = 1 .. D)
+   *   K[0,0] = os2 e,  K[0,b] = os2 t_b u_b e,  K[a,0] = -os2 t_a u_a e,  K[a,b] = os2 t_a t_b (delta_ab - u_a u_b) e
+   * Lowered for lo_matvec_f32, the streaming CG, Lanczos, fp32 MINRES and the fp32 pivoted Cholesky (diagonal os2 for
+   * a = 0, os2 t_a^2 else); the fp64 entry points, the resident / fused engines and the solve sessions return
+   * LO_ERR_UNSUPPORTED; not a term kind of LO_OP_SUM, not a base kind of LO_OP_MASKED.
+   * LO_ERR_BADARG: a null A0 / A1, R < 1, N % (R + 1) != 0, a family outside 0 .. 3; LO_ERR_UNSUPPORTED: D > 16, a
+   * family other than RBF.                                                                                             */
 } lo_op_desc;
 
 /* The grid shape of an LO_OP_TOEPLITZ_KRON_DIAG descriptor (host struct). */
@@ -971,6 +985,29 @@ size_t lo_kernel_kron_mv_workspace_bytes(int64_t B, int64_t n, int64_t D, int64_
 int lo_kernel_kron_mv_f32(const float* x, const float* theta, const float* task, int32_t family, int64_t B, int64_t n,
                           int64_t D, int64_t T, const float* v, int64_t c, const float* d, int32_t diag_mode, float* y,
                           void* ws, size_t ws_bytes, void* stream);
+
+/* ---- matrix-free derivative GP: the RBF gradient kernel (ABI 30; csrc/lo_kernel_grad.hip) ------------------------------
+ * y [B, M (D + 1), c] = K(x1, x2) v (+ d o v) for the block matrix of LO_OP_KERNEL_GRAD_DIAG, rows i (D + 1) + a over
+ * the M points of x1 [B, M, D], columns j (D + 1) + b over the N points of x2 [B, N, D] (M, N count POINTS; rectangular
+ * x1 != x2 is the prediction case), theta [B, D + 1] and `family` as for lo_kernel_mv_f32, v [B, N (D + 1), c].  With
+ * w[j,0] = v[j,0], w[j,b] = t_b v[j,b] (applied while the tile of v is staged) and s = w[j,0] + sum_b u_b w[j,b]:
+ *   y[i,0] = os2 sum_j e s,   y[i,a] = os2 t_a sum_j e (w[j,a] - u_a s)
+ * so a pair costs D FMAs for s and 2 D + 1 for the accumulators per column; nothing of size D^2 is formed.  d per
+ * diag_mode over the M (D + 1) rows, allowed only when M == N.  Launch shape, splits of the points j and the order of
+ * the sums as in lo_kernel_mv_f32: fixed-order sums, no atomics, two calls give equal bits.
+ * lo_kernel_grad_bilinear_f32: g_theta [B, D + 1] = d / d theta of S = sum_s U[:, s]^T K(x1, x2) V[:, s], U [B, M (D + 1),
+ * t], V [B, N (D + 1), t], in the meaning lo_kernel_bilinear_f32 gives its output (inverse lengthscales, then os2).
+ * LO_ERR_BADARG: a null pointer, a non-positive size, family outside 0 .. 3, an unknown diag_mode, one without d or one
+ * with M != N; LO_ERR_UNSUPPORTED: D > LO_KERNEL_GRAD_MAX_DIM, a family other than LO_KERNEL_RBF; LO_ERR_WORKSPACE before
+ * any launch.                                                                                                          */
+size_t lo_kernel_grad_mv_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t D, int64_t c);
+int lo_kernel_grad_mv_f32(const float* x1, const float* x2, const float* theta, int32_t family, int64_t B, int64_t M,
+                          int64_t N, int64_t D, const float* v, int64_t c, const float* d, int32_t diag_mode, float* y,
+                          void* ws, size_t ws_bytes, void* stream);
+size_t lo_kernel_grad_bilinear_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t D, int64_t t);
+int lo_kernel_grad_bilinear_f32(const float* x1, const float* x2, const float* theta, int32_t family, int64_t B, int64_t M,
+                                int64_t N, int64_t D, const float* U, const float* V, int64_t t, float* g_theta, void* ws,
+                                size_t ws_bytes, void* stream);
 
 /* ---- exact small-N path: batched Cholesky and triangular solves (ABI 18; csrc/lo_chol.hip) -------------------------
  * fp32, contiguous row-major, N <= 1024 (larger: LO_ERR_UNSUPPORTED), stream-ordered; fixed-order sums, no atomics: a

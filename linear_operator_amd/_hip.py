@@ -35,9 +35,11 @@ LO_OP_KERNEL_SUM_DIAG = 12
 LO_KERNEL_MAX_TERMS = 4
 LO_OP_KERNEL_KRON_DIAG = 13
 LO_KERNEL_KRON_MAX_TASKS = 8
+LO_OP_KERNEL_GRAD_DIAG = 14
+LO_KERNEL_GRAD_MAX_DIM = 16
 LO_DIAG_NONE, LO_DIAG_FULL, LO_DIAG_CONST = 0, 1, 2
 LO_BLOCK_DIAG, LO_BLOCK_INTERLEAVED, LO_BLOCK_SUM = 0, 1, 2
-ABI_VERSION = 29
+ABI_VERSION = 30
 
 LO_ERR_UNSUPPORTED = -4
 LO_FUSED_OK, LO_FUSED_EARLY_STOP, LO_FUSED_CONTINUE, LO_FUSED_TIMEOUT = 0, 1, 2, 3
@@ -285,6 +287,10 @@ _PROTOTYPES = {
     "lo_kernel_sum_points_grad_f32": (ci, [vp, vp, vp, P(i32), i64, i64, i64, i64, i64, vp, vp, i64, vp, vp, sz, vp]),
     "lo_kernel_kron_mv_workspace_bytes": (sz, [i64, i64, i64, i64, i64]),
     "lo_kernel_kron_mv_f32": (ci, [vp, vp, vp, i32, i64, i64, i64, i64, vp, i64, vp, i32, vp, vp, sz, vp]),
+    "lo_kernel_grad_mv_workspace_bytes": (sz, [i64, i64, i64, i64, i64]),
+    "lo_kernel_grad_mv_f32": (ci, [vp, vp, vp, i32, i64, i64, i64, i64, vp, i64, vp, i32, vp, vp, sz, vp]),
+    "lo_kernel_grad_bilinear_workspace_bytes": (sz, [i64, i64, i64, i64, i64]),
+    "lo_kernel_grad_bilinear_f32": (ci, [vp, vp, vp, i32, i64, i64, i64, i64, vp, vp, i64, vp, vp, sz, vp]),
     "lo_cholesky_workspace_bytes": (sz, [i64, i64]),
     "lo_cholesky_f32": (ci, [vp, vp, vp, vp, i64, i64, vp, sz, vp]),
     "lo_tri_solve_f32": (ci, [vp, vp, vp, vp, i64, i64, i64, i32, i32, vp]),

@@ -11,9 +11,18 @@ convention `f(x1, x2, lengthscale, outputscale)` (the `covar_func` of the refere
     matern32  g(r) = (1 + sqrt(3) r) exp(-sqrt(3) r)
     matern52  g(r) = (1 + sqrt(5) r + 5 r^2 / 3) exp(-sqrt(5) r)
 
+    rbf_grad  the covariance of the values AND the D partial derivatives of an RBF GP (a GP with derivative
+              observations; GPyTorch's RBFKernelGrad): D + 1 outputs per input, [..., M (D + 1), N (D + 1)], row index
+              i (D + 1) + a with a = 0 the value and a = 1 .. D the derivative in coordinate a - 1.  With
+              t = 1 / lengthscale, u = t (x1_i - x2_j), e = exp(-|u|^2 / 2) the block of the pair (i, j) is
+                  K[0,0] = os^2 e            K[0,b] = os^2 t_b u_b e
+                  K[a,0] = -os^2 t_a u_a e   K[a,b] = os^2 t_a t_b (delta_ab - u_a u_b) e
+              (pass num_outputs_per_input=(D + 1, D + 1) to the operator)
+
 r^2 is the sum of squared direct differences of the scaled points (no |a|^2 + |b|^2 - 2 a.b, which cancels for near
 points).  Each function carries `native_family`, the LO_KERNEL_* code under which csrc/lo_kernel_op.hip evaluates the
-same formula tile by tile; on that path the [..., M, N] matrix these functions return is never formed.
+same formula tile by tile; on that path the [..., M, N] matrix these functions return is never formed.  rbf_grad
+carries `native_outputs = "grad"` besides: csrc/lo_kernel_grad.hip forms its blocks pair by pair.
 """
 from __future__ import annotations
 
@@ -63,11 +72,29 @@ def matern52(x1: Tensor, x2: Tensor, lengthscale: Tensor, outputscale: Tensor) -
     return _scale(outputscale) * ((1.0 + s + (5.0 / 3.0) * r2) * torch.exp(-s))
 
 
+def rbf_grad(x1: Tensor, x2: Tensor, lengthscale: Tensor, outputscale: Tensor) -> Tensor:
+    D = x1.shape[-1]
+    u = (x1 / lengthscale).unsqueeze(-2) - (x2 / lengthscale).unsqueeze(-3)  # [..., M, N, D], scaled, then differenced
+    e = _scale(outputscale) * torch.exp(-0.5 * u.square().sum(-1))  # [..., M, N]
+    theta = (1.0 / lengthscale).expand(*lengthscale.shape[:-1], D)  # [..., 1, D]
+    tu = theta.unsqueeze(-3) * u  # t_b u_b
+    inner = torch.diag_embed(theta.square()).unsqueeze(-3) - tu.unsqueeze(-1) * tu.unsqueeze(-2)  # [..., M, N, D, D]
+    top = torch.cat((torch.ones_like(tu[..., :1]), tu), -1).unsqueeze(-2)  # [..., M, N, 1, D + 1]
+    block = torch.cat((top, torch.cat((-tu.unsqueeze(-1), inner.expand(*tu.shape, D)), -1)), -2)
+    K = e[..., None, None] * block  # [..., M, N, D + 1, D + 1]
+    M, N = K.shape[-4:-2]
+    return K.transpose(-3, -2).reshape(*K.shape[:-4], M * (D + 1), N * (D + 1))
+
+
 rbf.native_family = _hip.LO_KERNEL_RBF
+rbf_grad.native_family = _hip.LO_KERNEL_RBF
+rbf_grad.native_outputs = "grad"
 matern12.native_family = _hip.LO_KERNEL_MATERN12
 matern32.native_family = _hip.LO_KERNEL_MATERN32
 matern52.native_family = _hip.LO_KERNEL_MATERN52
 
 FAMILIES = {"rbf": rbf, "matern12": matern12, "matern32": matern32, "matern52": matern52}
+# gradient kernels (D + 1 outputs per input): kept apart, FAMILIES holds the one-output families only
+GRAD_FAMILIES = {"rbf_grad": rbf_grad}
 
-__all__ = ["rbf", "matern12", "matern32", "matern52", "scaled_sq_dist", "FAMILIES"]
+__all__ = ["rbf", "matern12", "matern32", "matern52", "rbf_grad", "scaled_sq_dist", "FAMILIES", "GRAD_FAMILIES"]

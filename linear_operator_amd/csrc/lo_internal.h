@@ -258,6 +258,15 @@ int kernel_kron_matvec_run(const MatvecPlan* pl, const float* v, float* y, const
 // LO_OK, or why the descriptor of that kind is refused (the pivoted Cholesky validates it without a plan)
 int kernel_kron_desc_check(const lo_op_desc* op);
 
+// ---- matrix-free RBF gradient kernel, D + 1 outputs per input (lo_kernel_grad.hip): LO_OP_KERNEL_GRAD_DIAG -------------
+struct KernelGradPlan {
+  float* part;  // [js, B, n, (D + 1) c] partial products when the points j of a member are split over js workgroups, else nullptr
+};
+int kernel_grad_plan(MatvecPlan* pl, Arena* ar, hipStream_t st);
+int kernel_grad_matvec_run(const MatvecPlan* pl, const float* v, float* y, const int* stop, hipStream_t st);
+// LO_OK, or why the descriptor of that kind is refused (the pivoted Cholesky validates it without a plan)
+int kernel_grad_desc_check(const lo_op_desc* op);
+
 // ---- masked operator (lo_masked.hip) ---------------------------------------------------------------------------------
 struct MaskedPlan {      // (the base's plan is MatvecPlan::sub[0])
   const int64_t* idx;    // [M]
@@ -294,6 +303,7 @@ struct MatvecPlan {
     HadamardPlan hd;
     KernelOpPlan ko;
     KernelKronPlan kk;
+    KernelGradPlan kg;
     MaskedPlan mask;
   };
 };

@@ -61,6 +61,16 @@ __device__ __forceinline__ void kf_gh(float r2, float* g, float* h) {
   }
 }
 
+// The pair function of the gradient kernel (LO_OP_KERNEL_GRAD_DIAG): for k = os2 g with g a function of r^2 and u the
+// scaled difference, the block of a pair is g0, t_b u_b g1, -t_a u_a g1, t_a t_b (delta_ab g1 - u_a u_b g2) with
+// g0 = g, g1 = -2 dg / d(r^2), g2 = 4 d^2 g / d(r^2)^2.  RBF: g0 = g1 = g2 = exp(-r^2 / 2), ONE factor, which is all
+// the callers use today; a twice differentiable family (Matern-5/2) adds its case here and the callers take three.
+template <int FAMILY>
+__device__ __forceinline__ float kf_grad_pair(float r2) {
+  static_assert(FAMILY == LO_KERNEL_RBF, "the gradient kernel is built for RBF only");
+  return kf_g<LO_KERNEL_RBF>(r2);
+}
+
 // the same with the family as a run-time value (row source of the pivoted Cholesky: one entry per thread)
 __device__ __forceinline__ float kf_g_rt(int family, float r2) {
   switch (family) {

@@ -306,6 +306,13 @@ int ko_reduce_splits(const char* prof_name, const float* part, int js, size_t pe
   return LO_OK;
 }
 
+int ko_bil_reduce(const float* part, int nblk, int DP, int64_t B, int64_t D, const float* theta, float* g_theta,
+                  hipStream_t st) {
+  hipLaunchKernelGGL(k_kernel_bil_reduce, dim3((unsigned)B), dim3(64), 0, st, part, nblk, DP, (int)D, theta, g_theta);
+  LO_LAUNCH_CHECK();
+  return LO_OK;
+}
+
 template <int FAMILY, int DP>
 static void ko_mv_launch_cc(int CC, dim3 grid, hipStream_t st, const float* x1, const float* x2, const float* theta,
                             int tstride, int M, int N, int D, const float* v, int c, const float* d, int dmode, float* y,
@@ -482,10 +489,7 @@ int lo_kernel_bilinear_f32(const float* x1, const float* x2, const float* theta,
 #undef KO_FAM
   LO_PROF_END(st);
   LO_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_kernel_bil_reduce, dim3((unsigned)B), dim3(64), 0, st, part, s.rb * s.js, DP, (int)D, theta,
-                     g_theta);
-  LO_LAUNCH_CHECK();
-  return LO_OK;
+  return ko_bil_reduce(part, s.rb * s.js, DP, B, D, theta, g_theta, st);
 }
 
 size_t lo_kernel_points_grad_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t D, int64_t t) {

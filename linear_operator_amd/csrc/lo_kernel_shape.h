@@ -53,4 +53,10 @@ int kernel_mv_run(const float* x1, const float* x2, const float* theta, int64_t 
 int ko_reduce_splits(const char* prof_name, const float* part, int js, size_t per_member, size_t total, int c,
                      const float* d, int dmode, const float* v, float* y, const int* stop, hipStream_t st);
 
+
+// g_theta [B, D + 1] from the per-workgroup partials [B, nblk, DP + 1] of a bilinear sweep, in ascending order
+// (lo_kernel_op.hip): slot q < D times os2 / theta[q], slot DP (the sum for os2) as it is
+int ko_bil_reduce(const float* part, int nblk, int DP, int64_t B, int64_t D, const float* theta, float* g_theta,
+                  hipStream_t st);
+
 }  // namespace lo

@@ -140,6 +140,10 @@ __device__ __forceinline__ T src_diag(const PcDevT<T>& d, const lo_op_desc& op, 
   } else if (op.kind == LO_OP_KERNEL_KRON_DIAG) {  // row i = (p, tau): os2 g(0) Bt[tau, tau] = os2 Bt[tau, tau]
     const int nt = op.nterms, tau = i % nt;
     return (T)(op.A1[(size_t)b * (op.R + 1) + op.R] * op.task[((size_t)b * nt + tau) * nt + tau]);
+  } else if (op.kind == LO_OP_KERNEL_GRAD_DIAG) {  // row i = (p, a): os2 for the value, os2 t_a^2 for a derivative
+    const int D = (int)op.R, a = i % (D + 1);
+    const float* th = op.A1 + (size_t)b * (D + 1);
+    return (T)(a == 0 ? th[D] : th[D] * (th[a - 1] * th[a - 1]));
   } else if (op.kind == LO_OP_TOEPLITZ_KRON_DIAG) {
     // prod_k t_k[0], the trailing factors multiplied first (kronecker_product_linear_operator.py:22-28)
     const int D = d.ski.grid_ndim;
@@ -502,6 +506,25 @@ __global__ __launch_bounds__(kThreads) void k_pc_update(PcDevT<T> d, int m) {
             r2 = r2 + df * df;
           }
           tv = (T)((th[D] * kf_g_rt((int)tm.n2, r2)) * tm.task[((size_t)b * nt + tau) * nt + ss]);
+        } else if (tm.kind == LO_OP_KERNEL_GRAD_DIAG) {  // pivot (p, al), entry (j, be): the block formula of lo_amd.h
+          const int D = (int)tm.R, nt = D + 1;
+          const int n = N / nt, pp = pim / nt, al = pim - pp * nt, jj = i / nt, be = i - jj * nt;
+          const float* th = tm.A1 + (size_t)b * nt;
+          const float* xp = tm.A0 + ((size_t)b * n + pp) * D;
+          const float* xi = tm.A0 + ((size_t)b * n + jj) * D;
+          float r2 = 0.0f, ua = 0.0f, ub = 0.0f;  // u = the separately rounded scaled coordinates differenced
+          for (int k = 0; k < D; ++k) {
+            const float df = xp[k] * th[k] - xi[k] * th[k];
+            r2 = r2 + df * df;
+            if (k + 1 == al) ua = df;
+            if (k + 1 == be) ub = df;
+          }
+          const float e = th[D] * kf_g_rt(LO_KERNEL_RBF, r2);
+          float f;
+          if (al == 0) f = be == 0 ? 1.0f : th[be - 1] * ub;
+          else if (be == 0) f = -(th[al - 1] * ua);
+          else f = (th[al - 1] * th[be - 1]) * ((al == be ? 1.0f : 0.0f) - ua * ub);
+          tv = (T)(e * f);
         } else if (tm.kind == LO_OP_TOEPLITZ_KRON_DIAG) {
           // prod_k t_k[|p_k - i_k|], factors multiplied left to right (kronecker_product_linear_operator.py:198-216);
           // consecutive threads hold consecutive positions j: the gathers from the (small) columns stay in cache
@@ -750,6 +773,8 @@ static int pc_check_desc(const lo_op_desc* op, bool fp32_kinds = true) {
     if (const int rc = kernel_sum_desc_check(op)) return rc;
   } else if (op->kind == LO_OP_KERNEL_KRON_DIAG) {
     if (const int rc = kernel_kron_desc_check(op)) return rc;
+  } else if (op->kind == LO_OP_KERNEL_GRAD_DIAG) {
+    if (const int rc = kernel_grad_desc_check(op)) return rc;
   } else if (op->kind == LO_OP_SKI_DIAG) {
     const lo_interp_desc* w = op->interp;
     if (!op->A0 || op->R < 1 || op->n2 < 1 || !w || !w->left_idx || !w->left_vals || !w->right_idx || !w->right_vals)
@@ -847,7 +872,7 @@ int lo_pivoted_cholesky_f64(const lo_op_desc* op, int32_t max_rank, double error
   if (!op || !L_rows || !perm || !rank_out || !ws || max_rank < 1) return LO_ERR_BADARG;
   if (op->kind == LO_OP_SKI_DIAG || op->kind == LO_OP_TOEPLITZ_DIAG || op->kind == LO_OP_HADAMARD_DIAG ||
       op->kind == LO_OP_SKI_GRID_DIAG || op->kind == LO_OP_TOEPLITZ_KRON_DIAG || kernel_term_kind(op->kind) ||
-      op->kind == LO_OP_KERNEL_KRON_DIAG)
+      op->kind == LO_OP_KERNEL_KRON_DIAG || op->kind == LO_OP_KERNEL_GRAD_DIAG)
     return LO_ERR_UNSUPPORTED;  // (fp32 kinds)
   if (const int rc = pc_check_desc(op, false)) return rc;
   return pc_stream_t<double>(op, nullptr, nullptr, nullptr, max_rank, error_tol, L_rows, perm, rank_out, ws, ws_bytes,

@@ -724,6 +724,67 @@ def kernel_kron_mv(x: torch.Tensor, theta: torch.Tensor, task: torch.Tensor, fam
     return y
 
 
+def kernel_grad_diag_descriptor(X: torch.Tensor, theta: torch.Tensor, family: int, d: Optional[torch.Tensor] = None,
+                                const_diag: bool = False):
+    """AddedDiag(GradKernel(X, X), Diag(d)) (or the operator alone): the covariance of the values and the D partial
+    derivatives at the n points, row index i (D + 1) + a, formed pair by pair (csrc/lo_kernel_grad.hip).  X [*batch, n, D],
+    theta [B, D + 1] from kernel_theta, d over the n (D + 1) rows.  None when D exceeds LO_KERNEL_GRAD_MAX_DIM or the
+    family is not RBF (the caller evaluates covar_func)."""
+    _hip.require_hip(X, theta, d)
+    n, D = X.shape[-2:]
+    if D > _hip.LO_KERNEL_GRAD_MAX_DIM or D < 1 or int(family) != _hip.LO_KERNEL_RBF:
+        return None
+    X3 = _flat(X.detach(), 2)
+    if theta.shape != (X3.shape[0], D + 1):
+        raise RuntimeError(f"kernel_grad_diag_descriptor: theta of shape {tuple(theta.shape)} for X {tuple(X.shape)}")
+    return _with_diag(OperatorDescriptor(_hip.LO_OP_KERNEL_GRAD_DIAG, X3.shape[0], n * (D + 1), A0=X3, A1=theta, R=D,
+                                         n2=int(family), batch_shape=X.shape[:-2]), d, const_diag)
+
+
+def kernel_grad_mv(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, family: int, v: torch.Tensor,
+                   d: Optional[torch.Tensor] = None, const_diag: bool = False) -> torch.Tensor:
+    """lo_kernel_grad_mv_f32: y [B, M (D + 1), c] = K(x1, x2) v (+ d o v, only when M == N) for the gradient kernel's
+    block matrix, x1 [B, M, D], x2 [B, N, D], theta [B, D + 1], v [B, N (D + 1), c].  A shape the kernel does not take
+    raises."""
+    lib = _hip.load()
+    x1, x2, theta, v = x1.contiguous(), x2.contiguous(), theta.contiguous(), v.contiguous()
+    _hip.require_hip(x1, x2, theta, v, d)
+    B, M, D = x1.shape
+    N = x2.shape[-2]
+    c = v.shape[-1]
+    if x2.shape != (B, N, D) or theta.shape != (B, D + 1) or v.shape != (B, N * (D + 1), c):
+        raise RuntimeError(f"kernel_grad_mv: x1 {tuple(x1.shape)}, x2 {tuple(x2.shape)}, theta {tuple(theta.shape)}, "
+                           f"v {tuple(v.shape)}")
+    mode = _hip.LO_DIAG_NONE
+    if d is not None:
+        d, mode, _ = _diag_operand(d, B, M * (D + 1), const_diag)
+    y = torch.empty(B, M * (D + 1), c, dtype=torch.float32, device=v.device)
+    _launch("lo_kernel_grad_mv_f32", v.device, x1, x2, theta, int(family), B, M, N, D, v, c, d, mode, y,
+            ws_bytes=lib.lo_kernel_grad_mv_workspace_bytes(B, M, N, D, c))
+    return y
+
+
+def kernel_grad_bilinear(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, family: int, U: torch.Tensor,
+                         V: torch.Tensor) -> torch.Tensor:
+    """lo_kernel_grad_bilinear_f32: g_theta [B, D + 1], the derivative of sum_s u_s^T K(x1, x2) v_s with respect to theta
+    (the inverse lengthscales, then outputscale^2) for the gradient kernel's block matrix.  x1 [B, M, D], x2 [B, N, D],
+    U [B, M (D + 1), t], V [B, N (D + 1), t]."""
+    lib = _hip.load()
+    x1, x2, theta, U, V = (t.contiguous() for t in (x1, x2, theta, U, V))
+    _hip.require_hip(x1, x2, theta, U, V)
+    B, M, D = x1.shape
+    N = x2.shape[-2]
+    t = V.shape[-1]
+    if (x2.shape != (B, N, D) or theta.shape != (B, D + 1) or U.shape != (B, M * (D + 1), t)
+            or V.shape != (B, N * (D + 1), t)):
+        raise RuntimeError(f"kernel_grad_bilinear: x1 {tuple(x1.shape)}, x2 {tuple(x2.shape)}, "
+                           f"theta {tuple(theta.shape)}, U {tuple(U.shape)}, V {tuple(V.shape)}")
+    g = torch.empty(B, D + 1, dtype=torch.float32, device=U.device)
+    _launch("lo_kernel_grad_bilinear_f32", U.device, x1, x2, theta, int(family), B, M, N, D, U, V, t, g,
+            ws_bytes=lib.lo_kernel_grad_bilinear_workspace_bytes(B, M, N, D, t))
+    return g
+
+
 _MASK_BASE_KINDS = (_hip.LO_OP_LOWRANK_DIAG, _hip.LO_OP_DENSE_DIAG, _hip.LO_OP_KRON_DIAG, _hip.LO_OP_SUM)
 
 

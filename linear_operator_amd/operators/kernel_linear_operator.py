@@ -15,7 +15,18 @@ parameters are exactly `lengthscale` [*b, 1, D] or [*b, 1, 1] and `outputscale` 
                         from lo_kernel_points_grad_f32: one call per side that needs one, the x2 side as the x1 side of
                         the transposed problem.  covar_func is not called and nothing of size M N is allocated
 
-Anything outside that gate (D > 32, float64, CPU, several outputs per input, other parameters) takes the general path.
+Gradient kernels.  `covariance.rbf_grad` (`native_outputs == "grad"`) with num_outputs_per_input = (D + 1, D + 1), D <=
+LO_KERNEL_GRAD_MAX_DIM and the same parameters has a gate of its own, `_native_grad_refusal`; `_native_refusal` keeps
+answering "more than one output per input", so every caller that assumes one output per input stays out.  Inside it:
+
+  _matmul / _t_matmul   lo_kernel_grad_mv_f32 (csrc/lo_kernel_grad.hip), always: its purpose is memory
+  _kernel_descriptor    x1 and x2 the same points: the kind LO_OP_KERNEL_GRAD_DIAG
+  _diagonal             outputscale^2 (1, 1 / l_1^2, .., 1 / l_D^2) per point, no launch, no covar_func
+  _bilinear_derivative  lo_kernel_grad_bilinear_f32 when neither points tensor asks for a gradient (else the general path)
+  _getitem              slices of whole points rebuild the operator over the sliced points; anything else indexes densely
+
+Anything outside the gates (D > 32, float64, CPU, several outputs per input of another kind, other parameters) takes the
+general path.
 """
 from __future__ import annotations
 
@@ -122,6 +133,38 @@ class KernelLinearOperator(LinearOperator):
     def _is_native(self) -> bool:
         return self._native_refusal() is None
 
+    def _native_grad_refusal(self, check_device: bool = True) -> Optional[str]:
+        """The gate of the gradient kernel (D + 1 outputs per input, csrc/lo_kernel_grad.hip): None when the native
+        kernels take this operator, else the reason they do not.  `check_device=False` leaves out the device condition."""
+        from .. import _hip
+
+        if getattr(self.covar_func, "native_outputs", None) != "grad":
+            return "covar_func has no native_outputs == 'grad'"
+        if getattr(self.covar_func, "native_family", None) != _hip.LO_KERNEL_RBF:
+            return "a gradient kernel of a family other than RBF"
+        D = self.x1.shape[-1]
+        if D < 1 or self.x2.shape[-1] != D or D > _hip.LO_KERNEL_GRAD_MAX_DIM:
+            return f"D = {D} beyond LO_KERNEL_GRAD_MAX_DIM"
+        if self.num_outputs_per_input != (D + 1, D + 1):
+            return f"num_outputs_per_input is not ({D + 1}, {D + 1})"
+        if self.nontensor_params or set(self.tensor_params) != {"lengthscale", "outputscale"}:
+            return "parameters other than lengthscale and outputscale"
+        ls, os_ = self.tensor_params["lengthscale"], self.tensor_params["outputscale"]
+        batch = self.batch_broadcast_shape
+        if self.num_nonbatch_dimensions["lengthscale"] != 2 or ls.shape not in ((*batch, 1, D), (*batch, 1, 1)):
+            return f"lengthscale of shape {tuple(ls.shape)}"
+        if self.num_nonbatch_dimensions["outputscale"] != 0 or os_.shape != batch:
+            return f"outputscale of shape {tuple(os_.shape)}"
+        tensors = (self.x1, self.x2, ls, os_)
+        if any(t.dtype != torch.float32 for t in tensors):
+            return "not float32"
+        if check_device and not all(t.is_cuda for t in tensors):
+            return "not on the device"
+        return None
+
+    def _is_native_grad(self) -> bool:
+        return self._native_grad_refusal() is None
+
     def _same_points(self) -> bool:
         return _same_tensor(self.x1, self.x2)
 
@@ -132,14 +175,16 @@ class KernelLinearOperator(LinearOperator):
                               self.x1.shape[-1])
 
     def _kernel_descriptor(self, batch_shape=None):
-        if not (self._is_native() and self._same_points()):
+        grad = self._is_native_grad()
+        if not ((grad or self._is_native()) and self._same_points()):
             return None
         from .. import kernels as K
 
         bs = torch.Size(self.batch_shape if batch_shape is None else batch_shape)
         X = self.x1.detach()
         X = X if X.shape[:-2] == bs else X.expand(*bs, *X.shape[-2:])
-        return K.kernel_diag_descriptor(X, self._theta(bs), self.covar_func.native_family)
+        build = K.kernel_grad_diag_descriptor if grad else K.kernel_diag_descriptor
+        return build(X, self._theta(bs), self.covar_func.native_family)
 
     # ------------------------------------------------------------------ dense evaluation (the general path)
     def _dense_covar(self):
@@ -164,7 +209,18 @@ class KernelLinearOperator(LinearOperator):
     def _matmul(self, rhs: Tensor) -> Tensor:
         vec = rhs.dim() == 1
         cols = rhs.unsqueeze(-1) if vec else rhs
-        if cols.is_cuda and cols.dtype == torch.float32 and self._is_native():
+        if cols.is_cuda and cols.dtype == torch.float32 and self._is_native_grad():
+            from .. import kernels as K
+
+            M, D = self.x1.shape[-2:]
+            N, c = self.x2.shape[-2], cols.shape[-1]
+            bs = torch.broadcast_shapes(self.batch_shape, cols.shape[:-2])
+            x1 = self.x1.detach().expand(*bs, M, D).reshape(-1, M, D)
+            x2 = x1 if self._same_points() else self.x2.detach().expand(*bs, N, D).reshape(-1, N, D)
+            y = K.kernel_grad_mv(x1, x2, self._theta(bs), self.covar_func.native_family,
+                                 cols.detach().expand(*bs, N * (D + 1), c).reshape(-1, N * (D + 1), c))
+            y = y.reshape(*bs, M * (D + 1), c)
+        elif cols.is_cuda and cols.dtype == torch.float32 and self._is_native():
             from .. import kernels as K
 
             M, D = self.x1.shape[-2:]
@@ -207,6 +263,14 @@ class KernelLinearOperator(LinearOperator):
         if self._native_refusal(check_device=False) is None and self._same_points():
             # g(0) = 1 for every native family: the diagonal is outputscale^2, no kernel launch
             return self.tensor_params["outputscale"].square().unsqueeze(-1).expand(*self.batch_broadcast_shape, n)
+        if self._native_grad_refusal(check_device=False) is None and self._same_points():
+            # the block of a point with itself is outputscale^2 diag(1, 1 / l_1^2, .., 1 / l_D^2): no launch, no covar_func
+            D = self.x1.shape[-1]
+            batch = self.batch_broadcast_shape
+            inv2 = (1.0 / self.tensor_params["lengthscale"]).square().expand(*batch, 1, D)[..., 0, :]
+            os2 = self.tensor_params["outputscale"].square().unsqueeze(-1)
+            per = torch.cat((torch.ones_like(inv2[..., :1]), inv2), -1) * os2
+            return per.unsqueeze(-2).expand(*batch, n, D + 1).reshape(*batch, n * (D + 1))
         # the pairs (x1_i, x2_i) as a leading batch dimension of 1 x 1 (or p x q) kernel matrices
         a = self.x1.movedim(-2, 0).unsqueeze(-2)
         b = self.x2.movedim(-2, 0).unsqueeze(-2)
@@ -237,13 +301,32 @@ class KernelLinearOperator(LinearOperator):
 
     def _getitem(self, row_index, col_index, *batch_indices):
         if self.num_outputs_per_input != (1, 1):
-            return super()._getitem(row_index, col_index, *batch_indices)  # (indexed densely)
+            points = self._whole_point_slices(row_index, col_index)
+            if points is None:
+                return super()._getitem(row_index, col_index, *batch_indices)  # (indexed densely)
+            row_index, col_index = points
         x1 = self.x1[(*batch_indices, row_index, _NOOP)]
         same = self._same_points() and isinstance(row_index, slice) and row_index == col_index
         x2 = x1 if same else self.x2[(*batch_indices, col_index, _NOOP)]
         params = {name: val[(*batch_indices, *([_NOOP] * self.num_nonbatch_dimensions[name]))]
                   for name, val in self.tensor_params.items()}
         return self._rebuild(x1, x2, params)
+
+    def _whole_point_slices(self, row_index, col_index):
+        """Inside the gradient gate: the slices over the POINTS that two step-free slices of whole points select
+        (kernel_linear_operator.py:300-340 of the reference divides such slices by the outputs per input); None for
+        anything else, which is indexed densely."""
+        if self._native_grad_refusal(check_device=False) is not None:
+            return None
+        out = []
+        for index, size, per in zip((row_index, col_index), self.shape[-2:], self.num_outputs_per_input):
+            if not isinstance(index, slice):
+                return None
+            start, stop, step = index.indices(size)
+            if step != 1 or start % per or stop % per or stop <= start:
+                return None
+            out.append(slice(start // per, stop // per, None))
+        return tuple(out)
 
     # ------------------------------------------------------------------ derivatives
     def _bilinear_derivative(self, left_vecs: Tensor, right_vecs: Tensor):
@@ -253,6 +336,10 @@ class KernelLinearOperator(LinearOperator):
         names = list(self._differentiable_kwargs)
         if left_vecs.is_cuda and left_vecs.dtype == torch.float32 and self._is_native():
             return self._bilinear_derivative_native(left_vecs, right_vecs, names)
+        if (left_vecs.is_cuda and left_vecs.dtype == torch.float32 and self._is_native_grad()
+                and not (self.x1.requires_grad or self.x2.requires_grad)):
+            # (native gradients of the points are not built for this kind: such a call takes the general path whole)
+            return self._bilinear_derivative_native(left_vecs, right_vecs, names, grad=True)
         tensors = [self.x1, self.x2] + [self.tensor_params[n] for n in names]
         leaves = [t.detach().requires_grad_(True) if t.requires_grad and t.dtype.is_floating_point else t.detach()
                   for t in tensors]
@@ -266,12 +353,15 @@ class KernelLinearOperator(LinearOperator):
             grads = list(torch.autograd.grad(loss, need, allow_unused=True))
         return tuple(grads.pop(0) if t.requires_grad else None for t in leaves)
 
-    def _bilinear_derivative_native(self, left_vecs: Tensor, right_vecs: Tensor, names):
+    def _bilinear_derivative_native(self, left_vecs: Tensor, right_vecs: Tensor, names, grad: bool = False):
+        """grad: the gradient kernel (the vectors have D + 1 rows per point; the caller saw that no points tensor asks
+        for a gradient)."""
         from .. import kernels as K
 
         ls, os_ = self.tensor_params["lengthscale"], self.tensor_params["outputscale"]
         M, D = self.x1.shape[-2:]
-        N, t = right_vecs.shape[-2:]
+        N, t = self.x2.shape[-2], right_vecs.shape[-1]
+        p = D + 1 if grad else 1
         bs = torch.broadcast_shapes(self.batch_shape, left_vecs.shape[:-2], right_vecs.shape[:-2])
         out = {"x1": None, "x2": None, "lengthscale": None, "outputscale": None}
         if not any(p.requires_grad for p in (self.x1, self.x2, ls, os_)):
@@ -280,10 +370,11 @@ class KernelLinearOperator(LinearOperator):
         x1 = self.x1.detach().expand(*bs, M, D).reshape(-1, M, D)
         x2 = x1 if self._same_points() else self.x2.detach().expand(*bs, N, D).reshape(-1, N, D)
         theta = self._theta(bs)
-        U = left_vecs.detach().expand(*bs, M, t).reshape(-1, M, t)
-        V = right_vecs.detach().expand(*bs, N, t).reshape(-1, N, t)
+        U = left_vecs.detach().expand(*bs, M * p, t).reshape(-1, M * p, t)
+        V = right_vecs.detach().expand(*bs, N * p, t).reshape(-1, N * p, t)
         if ls.requires_grad or os_.requires_grad:
-            g = K.kernel_bilinear(x1, x2, theta, family, U, V)  # [B, D + 1], d / d theta
+            bilinear = K.kernel_grad_bilinear if grad else K.kernel_bilinear
+            g = bilinear(x1, x2, theta, family, U, V)  # [B, D + 1], d / d theta
             if ls.requires_grad:  # theta_d = 1 / l_d: d / d l_d = -theta_d^2 d / d theta_d; a shared l sums over d
                 d_ls = (-(theta[:, :D] ** 2) * g[:, :D]).reshape(*bs, 1, D)
                 if ls.shape[-1] == 1 and D > 1:
