@@ -774,12 +774,19 @@ int lo_lanczos_tridiag_f64(const double* A, const double* diag, lo_matvec_cb_f64
  * y [B, N, c] = A v for a descriptor whose A0 / A1 / d point to DOUBLES (the convention of lo_pivoted_cholesky_f64; the
  * size and layout of lo_op_desc are unchanged, and nothing in the struct records the element type: the caller keeps
  * float64 descriptors away from the fp32 entry points).
- *   kinds     LO_OP_LOWRANK_DIAG, LO_OP_DENSE_DIAG, LO_OP_KRON_DIAG and LO_OP_SUM of up to LO_MAX_TERMS of those (summed
- *             left to right, the sum's own diagonal added last); every other kind: LO_ERR_UNSUPPORTED
+ *   kinds     LO_OP_LOWRANK_DIAG, LO_OP_DENSE_DIAG, LO_OP_KRON_DIAG, (ABI 31) LO_OP_KERNEL_DIAG with A0 = X [B, N, D],
+ *             A1 = theta [B, D + 1] as doubles, R = D, n2 = the family, and LO_OP_SUM of up to LO_MAX_TERMS of those in
+ *             any order (summed left to right, the sum's own diagonal added last); every other kind -- the sum-, Kron-
+ *             and gradient-kernel kinds included: LO_ERR_UNSUPPORTED
  *   diagonal  LO_DIAG_NONE / FULL / CONST;  any N, R, n1, n2, c >= 1, 1 <= B <= 65535;  y must not alias v (LO_ERR_BADARG)
+ *   kernel    a null A0 / A1, R < 1 or a family outside LO_KERNEL_RBF .. LO_KERNEL_MATERN52: LO_ERR_BADARG;
+ *             R > LO_KERNEL_MAX_DIM: LO_ERR_UNSUPPORTED; both, and a workspace that is too small, before any launch of the
+ *             call, whatever the term's position in a sum
  * Plain launches, fixed-order sums, no float64 atomics: the same inputs give the same bits, and a member's result does
  * not depend on the batch around it, nor on the alignment of the operands (row chunks, tiles and the thread layout are
- * functions of the member's own shape).
+ * functions of the member's own shape).  EXCEPTION: for the kernel kind the order of the partial sums follows
+ * ko_shape(B, M, N) exactly as in lo_kernel_mv_f32 (few row blocks: the columns j are split over workgroups), so a
+ * member's bits may depend on B; two calls on the same inputs still give equal bits.
  *   low-rank   C^T v as per-workgroup partials in the workspace added in chunk order, then a second pass over C
  *   dense      the kernel of lo_cg_solve_f64;  Kronecker: two small-GEMM passes, the [n1, n2, c] intermediate in the
  *              workspace
@@ -943,6 +950,30 @@ size_t lo_kernel_points_grad_workspace_bytes(int64_t B, int64_t M, int64_t N, in
 int lo_kernel_points_grad_f32(const float* x1, const float* x2, const float* theta, int32_t family, int64_t B, int64_t M,
                               int64_t N, int64_t D, const float* U, const float* V, int64_t t, float* g_x1, void* ws,
                               size_t ws_bytes, void* stream);
+
+/* ---- the same operator in float64 (ABI 31; csrc/lo_kernel_op_f64.hip) --------------------------------------------------
+ * The three entry points above with `double` in place of `float`: same formulas, same argument meanings, same error
+ * codes in the same order of precedence (lo_kernel_mv_f64 checks the aliasing it forbids: y == v is LO_ERR_BADARG),
+ * LO_ERR_WORKSPACE before any launch, sizers of their own.  K is never in memory.  The sweeps keep the structure of the fp32
+ * kernels (256 rows per workgroup, x2 scaled while staged in LDS tiles of 128, r^2 by direct differences in ascending k, a
+ * tile's sum on its own and then added to the running one, the column split of few-row shapes with an ascending reduce);
+ * exp and sqrt are the device math library's, there is no hardware double-precision exponential.  The Matern families
+ * take r = sqrt(min(r^2, 1e300)), so every family stays finite (and is 0) when r^2 overflows.  A pair with r^2 <= 1e-30
+ * adds nothing to the Matern-1/2 lengthscale and points sums; g'(r) / r of the other families is finite at 0.
+ * Fixed-order sums, no atomics: the same inputs give the same bits.  The kind LO_OP_KERNEL_DIAG of lo_matvec_f64 runs
+ * lo_kernel_mv_f64's kernel with x1 = x2.                                                                               */
+size_t lo_kernel_mv_f64_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t D, int64_t c);
+int lo_kernel_mv_f64(const double* x1, const double* x2, const double* theta, int32_t family, int64_t B, int64_t M,
+                     int64_t N, int64_t D, const double* v, int64_t c, const double* d, int32_t diag_mode, double* y,
+                     void* ws, size_t ws_bytes, void* stream);
+size_t lo_kernel_bilinear_f64_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t D, int64_t t);
+int lo_kernel_bilinear_f64(const double* x1, const double* x2, const double* theta, int32_t family, int64_t B, int64_t M,
+                           int64_t N, int64_t D, const double* U, const double* V, int64_t t, double* g_theta, void* ws,
+                           size_t ws_bytes, void* stream);
+size_t lo_kernel_points_grad_f64_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t D, int64_t t);
+int lo_kernel_points_grad_f64(const double* x1, const double* x2, const double* theta, int32_t family, int64_t B,
+                              int64_t M, int64_t N, int64_t D, const double* U, const double* V, int64_t t, double* g_x1,
+                              void* ws, size_t ws_bytes, void* stream);
 
 /* ---- sums of matrix-free kernel operators over the same points (ABI 28; csrc/lo_kernel_sum.hip) ------------------------
  * K_ij = sum_t theta[t][D] g_{f_t}(r_t,ij), r_t,ij^2 = sum_d (theta[t][d] (x1[i, d] - x2[j, d]))^2 for T terms,

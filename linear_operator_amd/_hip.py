@@ -39,7 +39,7 @@ LO_OP_KERNEL_GRAD_DIAG = 14
 LO_KERNEL_GRAD_MAX_DIM = 16
 LO_DIAG_NONE, LO_DIAG_FULL, LO_DIAG_CONST = 0, 1, 2
 LO_BLOCK_DIAG, LO_BLOCK_INTERLEAVED, LO_BLOCK_SUM = 0, 1, 2
-ABI_VERSION = 30
+ABI_VERSION = 31
 
 LO_ERR_UNSUPPORTED = -4
 LO_FUSED_OK, LO_FUSED_EARLY_STOP, LO_FUSED_CONTINUE, LO_FUSED_TIMEOUT = 0, 1, 2, 3
@@ -279,6 +279,12 @@ _PROTOTYPES = {
     "lo_kernel_bilinear_f32": (ci, [vp, vp, vp, i32, i64, i64, i64, i64, vp, vp, i64, vp, vp, sz, vp]),
     "lo_kernel_points_grad_workspace_bytes": (sz, [i64, i64, i64, i64, i64]),
     "lo_kernel_points_grad_f32": (ci, [vp, vp, vp, i32, i64, i64, i64, i64, vp, vp, i64, vp, vp, sz, vp]),
+    "lo_kernel_mv_f64_workspace_bytes": (sz, [i64, i64, i64, i64, i64]),
+    "lo_kernel_mv_f64": (ci, [vp, vp, vp, i32, i64, i64, i64, i64, vp, i64, vp, i32, vp, vp, sz, vp]),
+    "lo_kernel_bilinear_f64_workspace_bytes": (sz, [i64, i64, i64, i64, i64]),
+    "lo_kernel_bilinear_f64": (ci, [vp, vp, vp, i32, i64, i64, i64, i64, vp, vp, i64, vp, vp, sz, vp]),
+    "lo_kernel_points_grad_f64_workspace_bytes": (sz, [i64, i64, i64, i64, i64]),
+    "lo_kernel_points_grad_f64": (ci, [vp, vp, vp, i32, i64, i64, i64, i64, vp, vp, i64, vp, vp, sz, vp]),
     "lo_kernel_sum_mv_workspace_bytes": (sz, [i64, i64, i64, i64, i64, i64]),
     "lo_kernel_sum_mv_f32": (ci, [vp, vp, vp, P(i32), i64, i64, i64, i64, i64, vp, i64, vp, i32, vp, vp, sz, vp]),
     "lo_kernel_sum_bilinear_workspace_bytes": (sz, [i64, i64, i64, i64, i64, i64]),

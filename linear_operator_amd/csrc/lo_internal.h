@@ -506,6 +506,14 @@ int f64_dense_mv(const double* A, const double* d, const double* v, double* y, i
 int f64_dense_mv_ex(const double* A, const double* d, int dmode, int accumulate, const double* v, double* y, int64_t B,
                     int64_t N, int64_t c, hipStream_t st);
 int f64_copy(const double* a, double* o, size_t total, hipStream_t st);
+// the float64 matrix-free kernel product (lo_kernel_op_f64.hip) for lo_matvec_f64: the check of an LO_OP_KERNEL_DIAG
+// descriptor whose A0 / A1 point to doubles, the one layout of the product's workspace (the partials [js, B, M, c] of a
+// split member, else nullptr) and the product itself on validated arguments ([y +] K v + d o v)
+int kernel_desc_check_f64(const lo_op_desc* op, int64_t c);
+double* kernel_mv_layout_f64(Arena& ar, int64_t B, int64_t M, int64_t N, int64_t c);
+int kernel_mv_run_f64(const double* x1, const double* x2, const double* theta, int family, int64_t B, int64_t M,
+                      int64_t N, int64_t D, const double* v, int64_t c, const double* d, int dmode, int accumulate,
+                      double* y, double* part, hipStream_t st);
 
 // ---- single-pass Woodbury apply fused with the CG r / x update (lo_precond_fused.hip) --------------
 bool precond_fused_eligible(int64_t B, int64_t N, int64_t c, int ldq, int S);

@@ -61,6 +61,57 @@ __device__ __forceinline__ void kf_gh(float r2, float* g, float* h) {
   }
 }
 
+// The float64 pair functions (lo_kernel_op_f64.hip).  There is no hardware double-precision exponential: exp and sqrt are
+// the device math library's.  The Matern families clamp r^2 at kKfMaxR2D, so that polynomial x exp stays finite (and is
+// 0) when r^2 overflows; RBF needs no clamp, exp(-inf) is 0.
+constexpr double kKfSqrt3D = 1.7320508075688772935274463415058723669428;
+constexpr double kKfSqrt5D = 2.2360679774997896964091736687312762354406;
+constexpr double kKfMaxR2D = 1e300;
+constexpr double kKfR2FloorD = 1e-30;  // covariance._R2_FLOOR: a closer pair adds nothing to the Matern-1/2 derivatives
+
+template <int FAMILY>
+__device__ __forceinline__ double kf_g64(double r2) {
+  if constexpr (FAMILY == LO_KERNEL_RBF) {
+    return exp(-0.5 * r2);
+  } else {
+    const double r2c = fmin(r2, kKfMaxR2D);
+    const double r = sqrt(r2c);
+    if constexpr (FAMILY == LO_KERNEL_MATERN12) {
+      return exp(-r);
+    } else if constexpr (FAMILY == LO_KERNEL_MATERN32) {
+      return fma(kKfSqrt3D, r, 1.0) * exp(-kKfSqrt3D * r);
+    } else {
+      return fma(5.0 / 3.0, r2c, fma(kKfSqrt5D, r, 1.0)) * exp(-kKfSqrt5D * r);
+    }
+  }
+}
+
+// g(r) and h(r) = g'(r) / r in float64, as kf_gh: h of Matern-1/2 is taken as 0 for r^2 <= kKfR2FloorD
+template <int FAMILY>
+__device__ __forceinline__ void kf_gh64(double r2, double* g, double* h) {
+  if constexpr (FAMILY == LO_KERNEL_RBF) {
+    const double e = exp(-0.5 * r2);
+    *g = e;
+    *h = -e;
+  } else {
+    const double r2c = fmin(r2, kKfMaxR2D);
+    const double r = sqrt(r2c);
+    if constexpr (FAMILY == LO_KERNEL_MATERN12) {
+      const double e = exp(-r);
+      *g = e;
+      *h = r2c > kKfR2FloorD ? -e / r : 0.0;
+    } else if constexpr (FAMILY == LO_KERNEL_MATERN32) {
+      const double e = exp(-kKfSqrt3D * r);
+      *g = fma(kKfSqrt3D, r, 1.0) * e;
+      *h = -3.0 * e;
+    } else {
+      const double e = exp(-kKfSqrt5D * r);
+      *g = fma(5.0 / 3.0, r2c, fma(kKfSqrt5D, r, 1.0)) * e;
+      *h = (-5.0 / 3.0) * fma(kKfSqrt5D, r, 1.0) * e;
+    }
+  }
+}
+
 // The pair function of the gradient kernel (LO_OP_KERNEL_GRAD_DIAG): for k = os2 g with g a function of r^2 and u the
 // scaled difference, the block of a pair is g0, t_b u_b g1, -t_a u_a g1, t_a t_b (delta_ab g1 - u_a u_b g2) with
 // g0 = g, g1 = -2 dg / d(r^2), g2 = 4 d^2 g / d(r^2)^2.  RBF: g0 = g1 = g2 = exp(-r^2 / 2), ONE factor, which is all

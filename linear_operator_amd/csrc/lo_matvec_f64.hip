@@ -11,10 +11,14 @@
 //   dense      k64_dense_mv of lo_cg_f64.hip (f64_dense_mv_ex).
 //   Kronecker  two passes of one tiled VALU small-GEMM kernel (k64_kron_gemm), the [n1, n2, c] intermediate in the
 //              workspace.  (A v_mfma_f64_16x16x4 variant has not been written)
+//   kernel     (ABI 31) LO_OP_KERNEL_DIAG with A0 = X, A1 = theta as doubles: k64_kernel_mv of lo_kernel_op_f64.hip, K never
+//              in memory; validated, and its workspace checked, before the first launch of the call.
 //   sum        the first term writes y, later terms accumulate into it in their epilogue, the sum's own diagonal goes
 //              into the last term's epilogue.
 // Every sum runs in a fixed order that depends on the member's own shape only (the row chunks are a function of N, the
 // tiles of n1, n2, c): the same inputs give the same bits and a member's result does not depend on the batch around it.
+// The kernel kind is the exception to the second half: its column split follows ko_shape(B, M, N), as in
+// lo_kernel_mv_f32, so the order of its partial sums depends on B; two calls on the same inputs still give equal bits.
 // No float64 atomics.
 #include "lo_internal.h"
 
@@ -378,7 +382,9 @@ static int kron_run(const double* K1, const double* K2, int64_t B, int64_t n1, i
   return LO_OK;
 }
 
-static bool plain_kind(int kind) { return kind == LO_OP_LOWRANK_DIAG || kind == LO_OP_DENSE_DIAG || kind == LO_OP_KRON_DIAG; }
+static bool plain_kind(int kind) {
+  return kind == LO_OP_LOWRANK_DIAG || kind == LO_OP_DENSE_DIAG || kind == LO_OP_KRON_DIAG || kind == LO_OP_KERNEL_DIAG;
+}
 
 // bytes of one plain term (lay out with a null arena)
 static size_t term_bytes(const lo_op_desc* op, int64_t c) {
@@ -388,6 +394,8 @@ static size_t term_bytes(const lo_op_desc* op, int64_t c) {
     lr_layout(op->B, op->N, op->R, c, ar, &a, &b);
   } else if (op->kind == LO_OP_KRON_DIAG) {
     ar.take<double>((size_t)op->B * op->N * c);
+  } else if (op->kind == LO_OP_KERNEL_DIAG) {
+    if (kernel_desc_check_f64(op, c) == LO_OK) kernel_mv_layout_f64(ar, op->B, op->N, op->N, c);
   }
   return ar.off;
 }
@@ -405,9 +413,24 @@ static int term_run(const lo_op_desc* op, const double* dd, int dmode, int accum
     case LO_OP_KRON_DIAG:
       if (!op->A1 || op->R < 1 || op->n2 < 1 || op->R * op->n2 != op->N) return LO_ERR_BADARG;
       return kron_run(A0, (const double*)op->A1, op->B, op->R, op->n2, c, dd, dmode, accumulate, v, y, ar, st);
+    case LO_OP_KERNEL_DIAG: {  // (checked by the caller before the first launch: kernel_terms_check)
+      double* part = kernel_mv_layout_f64(ar, op->B, op->N, op->N, c);
+      if (!ar.ok) return LO_ERR_WORKSPACE;
+      return kernel_mv_run_f64(A0, A0, (const double*)op->A1, (int)op->n2, op->B, op->N, op->N, op->R, v, c, dd, dmode,
+                               accumulate, y, part, st);
+    }
     default:
       return LO_ERR_UNSUPPORTED;
   }
+}
+
+// a kernel term is validated, and its workspace measured against what the caller gave, before anything is launched
+static int kernel_term_check(const lo_op_desc* op, int64_t c, size_t ws_bytes, const void* ws) {
+  if (op->kind != LO_OP_KERNEL_DIAG) return LO_OK;
+  const int rc = kernel_desc_check_f64(op, c);
+  if (rc) return rc;
+  const size_t need = term_bytes(op, c);
+  return (need > ws_bytes || (need && !ws)) ? LO_ERR_WORKSPACE : LO_OK;
 }
 
 static int diag_ok(const lo_op_desc* op) {
@@ -440,6 +463,7 @@ extern "C" int lo_matvec_f64(const lo_op_desc* op, const double* v, double* y, i
   hipStream_t st = (hipStream_t)stream;
   const double* dd = (const double*)op->d;
   if (op->kind != LO_OP_SUM) {
+    if (const int rc = kernel_term_check(op, c, ws_bytes, ws)) return rc;
     Arena ar(ws, ws_bytes);
     return term_run(op, dd, op->diag_mode, 0, v, y, c, ar, st);
   }
@@ -448,6 +472,7 @@ extern "C" int lo_matvec_f64(const lo_op_desc* op, const double* v, double* y, i
     const lo_op_desc* t = &op->terms[i];
     if (!plain_kind(t->kind)) return LO_ERR_UNSUPPORTED;
     if (t->diag_mode != LO_DIAG_NONE || t->B != op->B || t->N != op->N) return LO_ERR_BADARG;
+    if (const int rc = kernel_term_check(t, c, ws_bytes, ws)) return rc;
   }
   for (int i = 0; i < op->nterms; ++i) {
     const bool last = i == op->nterms - 1;

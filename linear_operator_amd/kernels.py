@@ -120,9 +120,8 @@ def _check_dtype(dtype, *tensors):
 
 def sum_descriptor(terms, d: Optional[torch.Tensor] = None, const_diag: bool = False, dtype=torch.float32):
     """SumLinearOperator(A_1, ..., A_n) (+ one diagonal): y = sum_i A_i v + d o v (sum_linear_operator.py:47-51).
-    `terms`: 2 .. LO_MAX_TERMS descriptors of kind low-rank / dense / Kronecker -- float32 sums also matrix-free kernel
-    terms (LO_OP_KERNEL_DIAG, LO_OP_KERNEL_SUM_DIAG) -- WITHOUT a diagonal, same batch and N, all of the element type
-    `dtype`."""
+    `terms`: 2 .. LO_MAX_TERMS descriptors of kind low-rank / dense / Kronecker / matrix-free kernel (LO_OP_KERNEL_DIAG;
+    float32 sums also LO_OP_KERNEL_SUM_DIAG) WITHOUT a diagonal, same batch and N, all of the element type `dtype`."""
     terms = tuple(terms)
     for t in terms:
         if t.dtype != dtype:
@@ -484,21 +483,34 @@ def hadamard_diag_descriptor(F: torch.Tensor, G: torch.Tensor, d: Optional[torch
                                          batch_shape=batch), d, const_diag)
 
 
-def kernel_theta(lengthscale: torch.Tensor, outputscale: torch.Tensor, batch, D: int) -> torch.Tensor:
-    """theta [B, D + 1] of the kernel entry points: the D inverse lengthscales (a shared one replicated), then
-    outputscale^2.  lengthscale [*b, 1, D] or [*b, 1, 1], outputscale [*b], both broadcast to `batch`."""
+def kernel_theta(lengthscale: torch.Tensor, outputscale: torch.Tensor, batch, D: int,
+                 dtype=torch.float32) -> torch.Tensor:
+    """theta [B, D + 1] of the kernel entry points, of element type `dtype`: the D inverse lengthscales (a shared one
+    replicated), then outputscale^2.  lengthscale [*b, 1, D] or [*b, 1, 1], outputscale [*b], both broadcast to `batch`."""
     with torch.no_grad():
         inv = (1.0 / lengthscale.detach()).expand(*batch, 1, D).reshape(-1, D)
         os2 = torch.broadcast_to(outputscale.detach().square(), tuple(batch)).reshape(-1, 1)
-        return torch.cat((inv, os2), -1).to(torch.float32).contiguous()
+        return torch.cat((inv, os2), -1).to(dtype).contiguous()
+
+
+def _kernel_dtype(what: str, *tensors):
+    """The one element type of a kernel entry point's operands (float32: the _f32 entry point, float64: its _f64 twin);
+    mixed types raise."""
+    dtypes = {t.dtype for t in tensors if t is not None}
+    if len(dtypes) != 1 or next(iter(dtypes)) not in (torch.float32, torch.float64):
+        raise _hip.HipExtensionError(f"{what}: the operands must all be float32 or all be float64, got "
+                                     f"{sorted(str(d) for d in dtypes)}")
+    return next(iter(dtypes))
 
 
 def kernel_diag_descriptor(X: torch.Tensor, theta: torch.Tensor, family: int, d: Optional[torch.Tensor] = None,
-                           const_diag: bool = False):
+                           const_diag: bool = False, dtype=torch.float32):
     """AddedDiag(Kernel(X, X, family), Diag(d)) (or the kernel matrix alone): y = K(X, X) v + d o v with K formed on the
-    fly (csrc/lo_kernel_op.hip).  X [*batch, N, D], theta [B, D + 1] from kernel_theta.  None when D exceeds
-    LO_KERNEL_MAX_DIM (the caller evaluates covar_func)."""
-    _hip.require_hip(X, theta, d)
+    fly (csrc/lo_kernel_op.hip; dtype=torch.float64: csrc/lo_kernel_op_f64.hip through lo_matvec_f64 and the float64
+    solvers).  X [*batch, N, D], theta [B, D + 1] from kernel_theta.  None when D exceeds LO_KERNEL_MAX_DIM (the caller
+    evaluates covar_func)."""
+    _check_dtype(dtype, X, theta, d)
+    _hip.require_hip(X, theta, d, dtype=dtype)
     N, D = X.shape[-2:]
     if D > _hip.LO_KERNEL_MAX_DIM or D < 1:
         return None
@@ -506,16 +518,18 @@ def kernel_diag_descriptor(X: torch.Tensor, theta: torch.Tensor, family: int, d:
     if theta.shape != (X3.shape[0], D + 1):
         raise RuntimeError(f"kernel_diag_descriptor: theta of shape {tuple(theta.shape)} for X {tuple(X.shape)}")
     return _with_diag(OperatorDescriptor(_hip.LO_OP_KERNEL_DIAG, X3.shape[0], N, A0=X3, A1=theta, R=D, n2=int(family),
-                                         batch_shape=X.shape[:-2]), d, const_diag)
+                                         batch_shape=X.shape[:-2], dtype=dtype), d, const_diag)
 
 
 def kernel_mv(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, family: int, v: torch.Tensor,
               d: Optional[torch.Tensor] = None, const_diag: bool = False) -> torch.Tensor:
-    """lo_kernel_mv_f32: y [B, M, c] = K(x1, x2) v (+ d o v when M == N and d is given), x1 [B, M, D], x2 [B, N, D],
-    theta [B, D + 1], v [B, N, c].  A shape the kernel does not take raises."""
+    """lo_kernel_mv_f32 (all operands float64: lo_kernel_mv_f64): y [B, M, c] = K(x1, x2) v (+ d o v when M == N and d is
+    given), x1 [B, M, D], x2 [B, N, D], theta [B, D + 1], v [B, N, c].  A shape the kernel does not take raises."""
     lib = _hip.load()
     x1, x2, theta, v = x1.contiguous(), x2.contiguous(), theta.contiguous(), v.contiguous()
-    _hip.require_hip(x1, x2, theta, v, d)
+    dtype = _kernel_dtype("kernel_mv", x1, x2, theta, v, d)
+    f64 = dtype == torch.float64
+    _hip.require_hip(x1, x2, theta, v, d, dtype=dtype)
     B, M, D = x1.shape
     N, c = v.shape[-2:]
     if x2.shape != (B, N, D) or theta.shape != (B, D + 1) or v.shape[0] != B:
@@ -524,46 +538,54 @@ def kernel_mv(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, family: i
     mode = _hip.LO_DIAG_NONE
     if d is not None:
         d, mode, _ = _diag_operand(d, B, N, const_diag)
-    y = torch.empty(B, M, c, dtype=torch.float32, device=v.device)
-    _launch("lo_kernel_mv_f32", v.device, x1, x2, theta, int(family), B, M, N, D, v, c, d, mode, y,
-            ws_bytes=lib.lo_kernel_mv_workspace_bytes(B, M, N, D, c))
+    y = torch.empty(B, M, c, dtype=dtype, device=v.device)
+    sizer = lib.lo_kernel_mv_f64_workspace_bytes if f64 else lib.lo_kernel_mv_workspace_bytes
+    _launch("lo_kernel_mv_f64" if f64 else "lo_kernel_mv_f32", v.device, x1, x2, theta, int(family), B, M, N, D, v, c, d,
+            mode, y, ws_bytes=sizer(B, M, N, D, c))
     return y
 
 
 def kernel_bilinear(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, family: int, U: torch.Tensor,
                     V: torch.Tensor) -> torch.Tensor:
-    """lo_kernel_bilinear_f32: g_theta [B, D + 1], the derivative of sum_s u_s^T K(x1, x2) v_s with respect to theta
-    (the inverse lengthscales, then outputscale^2).  x1 [B, M, D], x2 [B, N, D], U [B, M, t], V [B, N, t]."""
+    """lo_kernel_bilinear_f32 (all operands float64: lo_kernel_bilinear_f64): g_theta [B, D + 1], the derivative of
+    sum_s u_s^T K(x1, x2) v_s with respect to theta (the inverse lengthscales, then outputscale^2).  x1 [B, M, D],
+    x2 [B, N, D], U [B, M, t], V [B, N, t]."""
     lib = _hip.load()
     x1, x2, theta, U, V = (t.contiguous() for t in (x1, x2, theta, U, V))
-    _hip.require_hip(x1, x2, theta, U, V)
+    dtype = _kernel_dtype("kernel_bilinear", x1, x2, theta, U, V)
+    f64 = dtype == torch.float64
+    _hip.require_hip(x1, x2, theta, U, V, dtype=dtype)
     B, M, D = x1.shape
     N, t = V.shape[-2:]
     if x2.shape != (B, N, D) or theta.shape != (B, D + 1) or U.shape != (B, M, t) or V.shape[0] != B:
         raise RuntimeError(f"kernel_bilinear: x1 {tuple(x1.shape)}, x2 {tuple(x2.shape)}, theta {tuple(theta.shape)}, "
                            f"U {tuple(U.shape)}, V {tuple(V.shape)}")
-    g = torch.empty(B, D + 1, dtype=torch.float32, device=U.device)
-    _launch("lo_kernel_bilinear_f32", U.device, x1, x2, theta, int(family), B, M, N, D, U, V, t, g,
-            ws_bytes=lib.lo_kernel_bilinear_workspace_bytes(B, M, N, D, t))
+    g = torch.empty(B, D + 1, dtype=dtype, device=U.device)
+    sizer = lib.lo_kernel_bilinear_f64_workspace_bytes if f64 else lib.lo_kernel_bilinear_workspace_bytes
+    _launch("lo_kernel_bilinear_f64" if f64 else "lo_kernel_bilinear_f32", U.device, x1, x2, theta, int(family), B, M, N,
+            D, U, V, t, g, ws_bytes=sizer(B, M, N, D, t))
     return g
 
 
 def kernel_points_grad(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, family: int, U: torch.Tensor,
                        V: torch.Tensor) -> torch.Tensor:
-    """lo_kernel_points_grad_f32: g_x1 [B, M, D], the derivative of sum_s u_s^T K(x1, x2) v_s with respect to x1, x2 held
-    fixed.  x1 [B, M, D], x2 [B, N, D], theta [B, D + 1], U [B, M, t], V [B, N, t].  The derivative with respect to x2 is
-    kernel_points_grad(x2, x1, theta, family, V, U)."""
+    """lo_kernel_points_grad_f32 (all operands float64: lo_kernel_points_grad_f64): g_x1 [B, M, D], the derivative of
+    sum_s u_s^T K(x1, x2) v_s with respect to x1, x2 held fixed.  x1 [B, M, D], x2 [B, N, D], theta [B, D + 1],
+    U [B, M, t], V [B, N, t].  The derivative with respect to x2 is kernel_points_grad(x2, x1, theta, family, V, U)."""
     lib = _hip.load()
     x1, x2, theta, U, V = (t.contiguous() for t in (x1, x2, theta, U, V))
-    _hip.require_hip(x1, x2, theta, U, V)
+    dtype = _kernel_dtype("kernel_points_grad", x1, x2, theta, U, V)
+    f64 = dtype == torch.float64
+    _hip.require_hip(x1, x2, theta, U, V, dtype=dtype)
     B, M, D = x1.shape
     N, t = V.shape[-2:]
     if x2.shape != (B, N, D) or theta.shape != (B, D + 1) or U.shape != (B, M, t) or V.shape[0] != B:
         raise RuntimeError(f"kernel_points_grad: x1 {tuple(x1.shape)}, x2 {tuple(x2.shape)}, "
                            f"theta {tuple(theta.shape)}, U {tuple(U.shape)}, V {tuple(V.shape)}")
-    g = torch.empty(B, M, D, dtype=torch.float32, device=U.device)
-    _launch("lo_kernel_points_grad_f32", U.device, x1, x2, theta, int(family), B, M, N, D, U, V, t, g,
-            ws_bytes=lib.lo_kernel_points_grad_workspace_bytes(B, M, N, D, t))
+    g = torch.empty(B, M, D, dtype=dtype, device=U.device)
+    sizer = lib.lo_kernel_points_grad_f64_workspace_bytes if f64 else lib.lo_kernel_points_grad_workspace_bytes
+    _launch("lo_kernel_points_grad_f64" if f64 else "lo_kernel_points_grad_f32", U.device, x1, x2, theta, int(family), B,
+            M, N, D, U, V, t, g, ws_bytes=sizer(B, M, N, D, t))
     return g
 
 
@@ -983,9 +1005,12 @@ def matvec(desc: OperatorDescriptor, v: torch.Tensor) -> torch.Tensor:
 #   Kronecker 16 x (128 (x) 128)   1 column  31 /  60     17 columns   172 / 117   (stays with ATen)
 #   sum low-rank + dense, N 4096   1 column 155 / 212     17 columns  3489 / 402   (stays with ATen)
 # A dense operator alone was not timed and keeps torch.matmul.
-_NATIVE_MATMUL_F64: dict = {("lowrank", 1): True, ("lowrank", 2): True, ("kron", 1): True, ("sum", 1): True}
+# The matrix-free kernel kind (csrc/lo_kernel_op_f64.hip) is in the table unconditionally: its purpose is memory (the
+# composition stores the [B, N, N] matrix), not a timing (DESIGN.md sections 6l, 6p).
+_NATIVE_MATMUL_F64: dict = {("lowrank", 1): True, ("lowrank", 2): True, ("kron", 1): True, ("sum", 1): True,
+                            ("kernel", 1): True, ("kernel", 2): True}
 _F64_KIND_NAMES = {_hip.LO_OP_LOWRANK_DIAG: "lowrank", _hip.LO_OP_DENSE_DIAG: "dense", _hip.LO_OP_KRON_DIAG: "kron",
-                   _hip.LO_OP_SUM: "sum"}
+                   _hip.LO_OP_SUM: "sum", _hip.LO_OP_KERNEL_DIAG: "kernel"}
 
 
 def _f64_route_kind(op) -> Optional[str]:
@@ -1012,6 +1037,8 @@ def _f64_route_kind(op) -> Optional[str]:
         return "kron"
     if isinstance(op, ops.DenseLinearOperator):
         return "dense"
+    if isinstance(op, ops.KernelLinearOperator) and op._native_f64_refusal(check_device=False) is None:
+        return "kernel"
     return None
 
 

@@ -25,8 +25,22 @@ answering "more than one output per input", so every caller that assumes one out
   _bilinear_derivative  lo_kernel_grad_bilinear_f32 when neither points tensor asks for a gradient (else the general path)
   _getitem              slices of whole points rebuild the operator over the sliced points; anything else indexes densely
 
-Anything outside the gates (D > 32, float64, CPU, several outputs per input of another kind, other parameters) takes the
-general path.
+Float64.  The four one-output families with every tensor float64 on the device have a gate of their own,
+`_native_f64_refusal` (the conditions of `_native_refusal` with float64 in place of float32); `_native_refusal` keeps
+answering "not float32", so the fp32 fusion gates of the Sum and Kronecker operators never see such an operator.  Inside it,
+with a float64 device right-hand side:
+
+  _matmul / _t_matmul   lo_kernel_mv_f64 (csrc/lo_kernel_op_f64.hip), always, rectangular x1 / x2 included
+  _kernel_descriptor_f64  x1 and x2 the same points: the float64 LO_OP_KERNEL_DIAG descriptor, which AddedDiag and Sum
+                        lower through (_attach_diag, utils.linear_cg._lower_f64), so that the float64 CG, MINRES and
+                        Lanczos multiply by lo_matvec_f64 with no Python call per product.  `_kernel_descriptor()` of the
+                        operator on its own stays None for float64, as it always was
+  _diagonal             outputscale^2, no launch
+  _bilinear_derivative  lo_kernel_bilinear_f64 and lo_kernel_points_grad_f64, the same theta -> lengthscale / outputscale
+                        mapping as in float32
+
+Anything outside the gates (D > 32, mixed element types, CPU, several outputs per input of another kind, other
+parameters) takes the general path, and so does a float32 right-hand side against a float64 operator or the reverse.
 """
 from __future__ import annotations
 
@@ -165,14 +179,57 @@ class KernelLinearOperator(LinearOperator):
     def _is_native_grad(self) -> bool:
         return self._native_grad_refusal() is None
 
+    def _native_f64_refusal(self, check_device: bool = True) -> Optional[str]:
+        """The gate of the float64 kernels (csrc/lo_kernel_op_f64.hip): None when they take this operator, else the
+        reason they do not -- the conditions of `_native_refusal` with every tensor float64.  `check_device=False`
+        leaves out the device condition."""
+        from .. import _hip
+
+        if getattr(self.covar_func, "native_family", None) is None:
+            return "covar_func has no native_family"
+        if self.num_outputs_per_input != (1, 1):
+            return "more than one output per input"
+        if self.nontensor_params or set(self.tensor_params) != {"lengthscale", "outputscale"}:
+            return "parameters other than lengthscale and outputscale"
+        D = self.x1.shape[-1]
+        if D > _hip.LO_KERNEL_MAX_DIM or D < 1 or self.x2.shape[-1] != D:
+            return f"D = {D} beyond LO_KERNEL_MAX_DIM"
+        ls, os_ = self.tensor_params["lengthscale"], self.tensor_params["outputscale"]
+        batch = self.batch_broadcast_shape
+        if self.num_nonbatch_dimensions["lengthscale"] != 2 or ls.shape not in ((*batch, 1, D), (*batch, 1, 1)):
+            return f"lengthscale of shape {tuple(ls.shape)}"
+        if self.num_nonbatch_dimensions["outputscale"] != 0 or os_.shape != batch:
+            return f"outputscale of shape {tuple(os_.shape)}"
+        tensors = (self.x1, self.x2, ls, os_)
+        if any(t.dtype != torch.float64 for t in tensors):
+            return "not float64"
+        if check_device and not all(t.is_cuda for t in tensors):
+            return "not on the device"
+        return None
+
+    def _is_native_f64(self) -> bool:
+        return self._native_f64_refusal() is None
+
     def _same_points(self) -> bool:
         return _same_tensor(self.x1, self.x2)
 
-    def _theta(self, batch):
+    def _theta(self, batch, dtype=torch.float32):
         from .. import kernels as K
 
         return K.kernel_theta(self.tensor_params["lengthscale"], self.tensor_params["outputscale"], batch,
-                              self.x1.shape[-1])
+                              self.x1.shape[-1], dtype=dtype)
+
+    def _kernel_descriptor_f64(self, batch_shape=None):
+        """The float64 LO_OP_KERNEL_DIAG descriptor inside the float64 gate when x1 and x2 are one tensor, else None."""
+        if not (self._is_native_f64() and self._same_points()):
+            return None
+        from .. import kernels as K
+
+        bs = torch.Size(self.batch_shape if batch_shape is None else batch_shape)
+        X = self.x1.detach()
+        X = X if X.shape[:-2] == bs else X.expand(*bs, *X.shape[-2:])
+        return K.kernel_diag_descriptor(X, self._theta(bs, torch.float64), self.covar_func.native_family,
+                                        dtype=torch.float64)
 
     def _kernel_descriptor(self, batch_shape=None):
         grad = self._is_native_grad()
@@ -220,7 +277,8 @@ class KernelLinearOperator(LinearOperator):
             y = K.kernel_grad_mv(x1, x2, self._theta(bs), self.covar_func.native_family,
                                  cols.detach().expand(*bs, N * (D + 1), c).reshape(-1, N * (D + 1), c))
             y = y.reshape(*bs, M * (D + 1), c)
-        elif cols.is_cuda and cols.dtype == torch.float32 and self._is_native():
+        elif cols.is_cuda and ((cols.dtype == torch.float32 and self._is_native())
+                               or (cols.dtype == torch.float64 and self._is_native_f64())):
             from .. import kernels as K
 
             M, D = self.x1.shape[-2:]
@@ -228,7 +286,7 @@ class KernelLinearOperator(LinearOperator):
             bs = torch.broadcast_shapes(self.batch_shape, cols.shape[:-2])
             x1 = self.x1.detach().expand(*bs, M, D).reshape(-1, M, D)
             x2 = x1 if self._same_points() else self.x2.detach().expand(*bs, N, D).reshape(-1, N, D)
-            y = K.kernel_mv(x1, x2, self._theta(bs), self.covar_func.native_family,
+            y = K.kernel_mv(x1, x2, self._theta(bs, cols.dtype), self.covar_func.native_family,
                             cols.detach().expand(*bs, N, c).reshape(-1, N, c))
             y = y.reshape(*bs, M, c)
         else:
@@ -260,7 +318,8 @@ class KernelLinearOperator(LinearOperator):
     def _diagonal(self) -> Tensor:
         p, q = self.num_outputs_per_input
         n = self.x1.shape[-2]
-        if self._native_refusal(check_device=False) is None and self._same_points():
+        if ((self._native_refusal(check_device=False) is None or self._native_f64_refusal(check_device=False) is None)
+                and self._same_points()):
             # g(0) = 1 for every native family: the diagonal is outputscale^2, no kernel launch
             return self.tensor_params["outputscale"].square().unsqueeze(-1).expand(*self.batch_broadcast_shape, n)
         if self._native_grad_refusal(check_device=False) is None and self._same_points():
@@ -336,6 +395,9 @@ class KernelLinearOperator(LinearOperator):
         names = list(self._differentiable_kwargs)
         if left_vecs.is_cuda and left_vecs.dtype == torch.float32 and self._is_native():
             return self._bilinear_derivative_native(left_vecs, right_vecs, names)
+        if (left_vecs.is_cuda and left_vecs.dtype == torch.float64 and right_vecs.dtype == torch.float64
+                and self._is_native_f64()):
+            return self._bilinear_derivative_native(left_vecs, right_vecs, names)
         if (left_vecs.is_cuda and left_vecs.dtype == torch.float32 and self._is_native_grad()
                 and not (self.x1.requires_grad or self.x2.requires_grad)):
             # (native gradients of the points are not built for this kind: such a call takes the general path whole)
@@ -369,7 +431,7 @@ class KernelLinearOperator(LinearOperator):
         family = self.covar_func.native_family
         x1 = self.x1.detach().expand(*bs, M, D).reshape(-1, M, D)
         x2 = x1 if self._same_points() else self.x2.detach().expand(*bs, N, D).reshape(-1, N, D)
-        theta = self._theta(bs)
+        theta = self._theta(bs, left_vecs.dtype)
         U = left_vecs.detach().expand(*bs, M * p, t).reshape(-1, M * p, t)
         V = right_vecs.detach().expand(*bs, N * p, t).reshape(-1, N * p, t)
         if ls.requires_grad or os_.requires_grad:

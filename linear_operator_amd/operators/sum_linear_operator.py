@@ -54,6 +54,15 @@ def _kernel_groups(ops, check_device: bool = True):
     return items
 
 
+def _term_descriptor(op, batch_shape):
+    """The descriptor of one operator as a term of a lowering: its `_kernel_descriptor`, or -- a float64
+    KernelLinearOperator, whose own `_kernel_descriptor()` stays None -- its `_kernel_descriptor_f64`."""
+    desc = op._kernel_descriptor(batch_shape)
+    if desc is None and hasattr(op, "_kernel_descriptor_f64"):
+        desc = op._kernel_descriptor_f64(batch_shape)
+    return desc
+
+
 def _kernel_group_pair(ops):
     """The operators themselves when ALL of `ops` (two or more, at most LO_KERNEL_MAX_TERMS) are native
     KernelLinearOperators over one (x1, x2) pair -- square or rectangular: one fused product or derivative serves the whole
@@ -127,7 +136,7 @@ class SumLinearOperator(LinearOperator):
             return None
         terms = []
         for item in items:
-            desc = _group_descriptor(item, batch_shape) if isinstance(item, list) else item._kernel_descriptor(batch_shape)
+            desc = _group_descriptor(item, batch_shape) if isinstance(item, list) else _term_descriptor(item, batch_shape)
             if desc is None or desc.diag_mode != 0 or desc.kind not in (
                     K._hip.LO_OP_LOWRANK_DIAG, K._hip.LO_OP_DENSE_DIAG, K._hip.LO_OP_KRON_DIAG, K._hip.LO_OP_KERNEL_DIAG,
                     K._hip.LO_OP_KERNEL_SUM_DIAG):
@@ -294,7 +303,7 @@ def _group_bilinear_derivative(group, left_vecs: Tensor, right_vecs: Tensor):
 
 def _attach_diag(base_op, diag_op, batch_shape):
     """Descriptor of `base_op (+ diag_op)` expanded to batch_shape, or None."""
-    desc = base_op._kernel_descriptor(batch_shape)
+    desc = _term_descriptor(base_op, batch_shape)
     if desc is None or desc.diag_mode != 0:
         return None
     return _sum_with_diag(desc, diag_op, batch_shape)

@@ -91,6 +91,8 @@ def _lower_matmul_closure(matmul_closure, batch_shape, dtype=torch.float32):
         if type(owner)._matmul is not getattr(matmul_closure, "__func__", None):
             return None  # instance-level override / mock
         desc = owner._kernel_descriptor(batch_shape)
+        if desc is None and dtype == torch.float64 and hasattr(owner, "_kernel_descriptor_f64"):
+            desc = owner._kernel_descriptor_f64(batch_shape)  # (a float64 KernelLinearOperator on its own)
         return desc if desc is not None and desc.dtype == dtype else None
     return None
 
@@ -107,7 +109,8 @@ def _native_precond_f64(preconditioner):
     return None
 
 
-_F64_KINDS = (K._hip.LO_OP_LOWRANK_DIAG, K._hip.LO_OP_DENSE_DIAG, K._hip.LO_OP_KRON_DIAG, K._hip.LO_OP_SUM)
+_F64_KINDS = (K._hip.LO_OP_LOWRANK_DIAG, K._hip.LO_OP_DENSE_DIAG, K._hip.LO_OP_KRON_DIAG, K._hip.LO_OP_SUM,
+              K._hip.LO_OP_KERNEL_DIAG)
 
 
 def _lower_f64(matmul_closure, batch_shape, cols: int = 1):
