@@ -18,7 +18,12 @@
 //   * x = D^-1 (xi b + C (nrm y)) in fp64 from the same registers: row sums reduce-scattered over the CH lanes of a row, a
 //     wave store covers 64 consecutive rows;
 //   * (second pass) a member starts with all of its rows already requested: a quarter during the previous member's
-//     iterations, the rest inside its x pass (168 -> 152 us per launch on one box, 142.5 us in the committed profile).
+//     iterations, the rest inside its x pass (168 -> 152 us per launch on one box, 142.5 us in the committed profile);
+//   * (third pass, profiles/r12) work the result does not need is off the member's serial path: the last iteration's
+//     residual norm is formed by workgroup 0 only and, but for a group's final member, at the NEXT member's top while
+//     its loads travel; the member draw no longer waits for its own round trip in front of the top's requests; one
+//     poll round per exchange up to 9 granules a thread; the exit product's LDS reads are in flight together
+//     (143.6 -> 139.9 us per launch).
 //
 // Numerics: fp64 sums in another order (the old kernel's results to ~1e-15 relative before the final rounding to fp32).
 #include <algorithm>
@@ -98,6 +103,58 @@ __device__ __forceinline__ double rows_reduce_d(double (&p)[CH], int lane) {
   }
 }
 
+// ---- pieces of the iteration chain that the member loop uses at two places (the chain, and the next member's top) ----
+__device__ __forceinline__ double pick_d(double v, int ln_) {
+  return mk_d((unsigned)__builtin_amdgcn_readlane((int)lo_w(v), ln_), (unsigned)__builtin_amdgcn_readlane((int)hi_w(v), ln_));
+}
+// (M v)_j for the lane pair (j, j + 32): each half-wave takes NH columns of row j, the halves are added lower + upper
+template <int NH>
+__device__ __forceinline__ double own_row_dot(const double* mrow, const double* vec) {
+  double a0_ = 0.0, a1_ = 0.0;
+#pragma unroll
+  for (int q = 0; q < NH; q += 2) {
+    const double2 xa = *reinterpret_cast<const double2*>(mrow + q);
+    const double2 xx = *reinterpret_cast<const double2*>(vec + q);
+    a0_ = fma(xa.x, xx.x, a0_);
+    a1_ = fma(xa.y, xx.y, a1_);
+  }
+  double lo_, up_;
+  halves_d(a0_ + a1_, lo_, up_);
+  return lo_ + up_;
+}
+// Residual norm in the coordinates of C, as the dense form: r = c' r0 + C g with g = Tu del, del = c - c' c0, and
+// r^T r = c'^2 a0 + 2 c' g.u0 + g^T G2 g.  `vec` is a 32-double LDS vector of the calling wave (overwritten); tucol is
+// this half's part of column j of TuT, nrow this half's part of row j of G2.
+template <int NH, int MLD>
+__device__ __forceinline__ float resid_norm_c(double dl, double cp, double a0, double u0, bool live, int j, int hf, int lane,
+                                              double* vec, const double* tucol, const double* nrow) {
+  __builtin_amdgcn_wave_barrier();
+  if (hf == 0) vec[j] = dl;
+  __builtin_amdgcn_wave_barrier();
+  double gj_;
+  {
+    double a0_ = 0.0, a1_ = 0.0;
+#pragma unroll
+    for (int q = 0; q < NH; q += 2) {
+      const double2 dd = *reinterpret_cast<const double2*>(vec + hf * NH + q);
+      a0_ = fma(tucol[(size_t)q * MLD], dd.x, a0_);
+      a1_ = fma(tucol[(size_t)(q + 1) * MLD], dd.y, a1_);
+    }
+    double lo_, up_;
+    halves_d(a0_ + a1_, lo_, up_);
+    gj_ = live ? lo_ + up_ : 0.0;
+  }
+  __builtin_amdgcn_wave_barrier();
+  if (hf == 0) vec[j] = gj_;
+  __builtin_amdgcn_wave_barrier();
+  const double nd = own_row_dot<NH>(nrow, vec + hf * NH);      // (G2 g)_j
+  const double r2 = row16_sum_d(halve_pair_d<16>(gj_ * nd, gj_ * u0, lane));
+  const double dnd = pick_d(r2, 0), dm = pick_d(r2, 16);
+  const double s1 = fma(cp, fma(cp, a0, 2.0 * dm), dnd);       // r^T r
+  const float s1f = (float)s1;
+  return __builtin_amdgcn_sqrtf(s1f < 0.f ? 0.f : s1f);
+}
+
 template <int RC, int GW>
 __global__ __launch_bounds__(R3_TPB, 2) void k_cg_rspace3(OnchipArgs a, PeerOut po) {
   constexpr int CH = RC / 4;     // 16-byte chunks per row
@@ -114,6 +171,9 @@ __global__ __launch_bounds__(R3_TPB, 2) void k_cg_rspace3(OnchipArgs a, PeerOut 
   __shared__ __attribute__((aligned(16))) double res[NP];
   __shared__ __attribute__((aligned(16))) double gv[4][32];
   __shared__ unsigned polw[GW > 1 ? NG : 2];
+  // what the last residual norm of a member needs when it is formed at the next member's top (below): del | c' | close
+  // flags | member.  Its own vector: gv[wave] holds nrm * y for the x pass by then.
+  __shared__ __attribute__((aligned(16))) double late_v[32 + 4];
   const GroupPlace gp = group_place(GW, (int)gridDim.x / 8);
   if (!gp.active) return;  // (surplus workgroup)
   const int grp = gp.grp, wig = gp.wig, ngroups = gp.ngroups;
@@ -152,6 +212,7 @@ __global__ __launch_bounds__(R3_TPB, 2) void k_cg_rspace3(OnchipArgs a, PeerOut 
     }
   };
   int closed = 0;  // workgroup-uniform: this workgroup has run the closing step (inside the loop, below)
+  bool late_pending = false;  // workgroup-uniform: the previous member's last residual norm is still to be formed
   int64_t b = grp;
   {
     int tl0 = t;
@@ -168,7 +229,10 @@ __global__ __launch_bounds__(R3_TPB, 2) void k_cg_rspace3(OnchipArgs a, PeerOut 
     const bool stamp = a.dbg && b == a.dbg_member && wig == 0 && t == 0;
     if (stamp) a.dbg[0] = wall_clock64();
     int drawn = 0;
-    if (wig == 0 && t == 0) drawn = atomicAdd(a.next_member, 1);  // (its round trip hides behind the member load)
+    // (its round trip hides behind the member load -- through a pointer whose address space the compiler cannot see: on a
+    //  global pointer the wave-level combining of atomics reads the result back with v_readfirstlane right here, behind
+    //  an s_waitcnt vmcnt(0) that also waits for every row still in flight, and the requests below start only then)
+    if (wig == 0 && t == 0) drawn = atomicAdd(opaque_uniform(a.next_member), 1);
     int tl = t;
     asm volatile("" : "+v"(tl));
     const int ln = tl & 63, k = ln & (CH - 1), g = ln / CH;
@@ -207,6 +271,50 @@ __global__ __launch_bounds__(R3_TPB, 2) void k_cg_rspace3(OnchipArgs a, PeerOut 
       }
     }
     const double lam_mine = a.RSD[((size_t)b * 6 + 5) * RC * RC + min(ln & 31, RC - 1)];  // this lane's eigenvalue
+    // ---- the last residual norm of the PREVIOUS member, when that was not the group's final one (see `late` below) ----
+    // Every request of this member is in flight and nothing has arrived: the wave that owes the norm forms it here, from
+    // what it left in late_v, while all four waves wait for their loads anyway.  mat_s (TuT, G2) and res[] are still the
+    // previous member's: the barrier that releases them to this member stands BEHIND this block, not at the end of the
+    // previous member's x pass (between the two places nothing touches LDS that another wave reads: the stages bst / dst
+    // and gv are per wave).  u0, a0 and nrm are formed from res[] as the chain's entry forms them.  The records and the
+    // close granule leave in front of the barrier, so the closing step of the group's final member -- behind at least
+    // this barrier -- finds them issued (lo_cg_close.h (3)).
+    if (late_pending && wave_u == ((a.iters - 1) & 3)) {
+      int l3 = lane;
+      asm volatile("" : "+v"(l3));
+      const int j = l3 & 31, hf = l3 >> 5;
+      const bool live = j < RC;
+      const int jr = live ? j : RC - 1;
+      double a0 = res[2 * RC + 1];
+      float nrm = sqrtf((float)a0);
+      const bool rhs_zero = nrm < a.eps;
+      if (rhs_zero) nrm = 1.0f;
+      const double inv = 1.0 / (double)nrm;
+      const double u0 = live ? res[RC + jr] * inv : 0.0;
+      a0 *= inv * inv;
+      const double* tucol = mat_s + (size_t)(1 * RC + hf * NH) * MLD + jr;
+      const double* nrow = mat_s + (size_t)(2 * RC + jr) * MLD + hf * NH;
+      const double dl = late_v[j], cp = late_v[32];
+      const unsigned flags0 = (unsigned)late_v[33];
+      const size_t bp = (size_t)late_v[34];  // the previous member (exact: members are counted in fp64 by the exchange too)
+      float rn = resid_norm_c<NH, MLD>(dl, cp, a0, u0, live, j, hf, l3, late_v, tucol, nrow);
+      if (rhs_zero) rn = 0.f;
+      if (l3 == 0) {
+        // (opaque copies: formed here.  As invariants of the member loop the record's offset is kept in vector registers
+        //  from the kernel's entry on, and spilled)
+        int it = a.iters;
+        long long nb = a.B;
+        asm volatile("" : "+s"(it), "+s"(nb));
+        const unsigned close_flags = flags0 | ((it == 1 && rn != rn) ? 2u : 0u);  // (NaN after the first product)
+        a.resid_rec[(size_t)(it - 1) * (size_t)nb + bp] = rn;
+        a.resid_norm[bp] = rn;
+        a.has_conv[bp] = (rn < a.stop_after) ? 1 : 0;
+        if (a.close_gran) {
+          granule_store(a.close_gran + bp, granule_pack(a.close_epoch | close_flags, rn), /*same_xcd=*/false);
+        }
+      }
+    }
+    __syncthreads();  // the previous member's matrices and res[] may be replaced from here on
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
       bw[ln + 64 * m] = bq4[m];
@@ -300,7 +408,11 @@ __global__ __launch_bounds__(R3_TPB, 2) void k_cg_rspace3(OnchipArgs a, PeerOut 
           granule_store(mine + 1, granule_pack_bits(tag, hi_w(v)), same_xcd);
         }
         constexpr int PER = (NG + R3_TPB - 1) / R3_TPB;  // granules per thread
-        constexpr int CKQ = PER < 8 ? PER : 8;            // ... polled together
+        // ... polled together: all of them up to 9 (<32, 8>: ONE round of 9, where a round of 8 was followed by a dependent
+        // round for one granule and seven clamped duplicates), two equal rounds up to 18 (<32, 16>: 9 + 9), rounds of 8
+        // in groups of 32 workgroups
+        constexpr int CKQ = GW == 32 ? 8 : PER <= 9 ? PER : (PER + 1) / 2;
+        static_assert(CKQ <= 9 && 2 * CKQ >= (GW == 32 ? 16 : PER), "poll rounds");
         unsigned spin = 0;
         bool lost = false;
 #pragma unroll 1
@@ -377,26 +489,13 @@ __global__ __launch_bounds__(R3_TPB, 2) void k_cg_rspace3(OnchipArgs a, PeerOut 
       float sa = a.stop_after;
       asm volatile("" : "+s"(sa));
       const double sure_rz = 2.0 * (double)sa * (double)sa * sqrt(d2);
-      auto own_row_dot = [&](const double* mrow, const double* vec) {
-        double a0_ = 0.0, a1_ = 0.0;
-#pragma unroll
-        for (int q = 0; q < NH; q += 2) {
-          const double2 xa = *reinterpret_cast<const double2*>(mrow + q);
-          const double2 xx = *reinterpret_cast<const double2*>(vec + q);
-          a0_ = fma(xa.x, xx.x, a0_);
-          a1_ = fma(xa.y, xx.y, a1_);
-        }
-        double lo_, up_;
-        halves_d(a0_ + a1_, lo_, up_);
-        return lo_ + up_;
-      };
       double* myv = gv[wave];
       if (hf == 0) myv[j] = w0;
       __builtin_amdgcn_wave_barrier();
       const double* row0m = mat_s + (size_t)jr * MLD + hf * NH;                    // row j of TinT (this half)
       // c0 = TinT w0 = W^T beta0, g0 = TuT w0 = W^-1 beta0 (beta0 = U^T b^): |beta0|^2 = c0 . g0 and V S^-1 beta0 = Tin g0
-      double c0 = own_row_dot(row0m, myv + hf * NH);                               // TinT w0
-      double e0 = own_row_dot(row0m + (size_t)1 * RC * MLD, myv + hf * NH);        // g0 = TuT w0
+      double c0 = own_row_dot<NH>(row0m, myv + hf * NH);                           // TinT w0
+      double e0 = own_row_dot<NH>(row0m + (size_t)1 * RC * MLD, myv + hf * NH);    // g0 = TuT w0
       const double* nrow = row0m + (size_t)2 * RC * MLD;                           // row j of G2 = C^T C
       const double* tucol = mat_s + (size_t)(1 * RC + hf * NH) * MLD + jr;         // column j of TuT (this half of its rows)
       c0 = live ? c0 : 0.0;
@@ -417,6 +516,15 @@ __global__ __launch_bounds__(R3_TPB, 2) void k_cg_rspace3(OnchipArgs a, PeerOut 
       const size_t bc = (size_t)b;
       const bool rec = wig == 0 && lane == 0;
       const int last_owner = (a.iters - 1) & 3;  // the wave that forms the last residual norm writes the member's state
+      // The last iteration's residual norm enters nothing but the member's records (resid_rec, resid_norm, has_conv, the
+      // close granule): x took its last update at the top of that iteration, the alpha its `conv` would zero is never
+      // applied.  It is 150 instructions with eight serialized LDS round trips on the path to y, so
+      //   * only workgroup 0 of a group, which stores the records, forms it at all;
+      //   * for a member that is not the group's final one, the owning wave leaves del and c' in late_v and forms the
+      //     norm at the next member's top, behind that member's requests, where all waves wait for loads (the group's
+      //     final member keeps the order norm, records, closing step, x pass: the closing step reads the granule).
+      const bool late = wig == 0 && a.iters > 0 && wave_u == last_owner &&
+                        __builtin_amdgcn_readfirstlane((int)(b_next < a.B)) != 0;  // (wave-uniform)
       for (int kk = -1; kk < a.iters; ++kk) {
         if (kk >= 0) {  // x += alpha p (:31);  r -= alpha A p (:264)
           last_alpha = (float)alpha;
@@ -430,54 +538,34 @@ __global__ __launch_bounds__(R3_TPB, 2) void k_cg_rspace3(OnchipArgs a, PeerOut 
         const bool lo_h = hf == 0;
         const float inv_rz = __builtin_amdgcn_rcpf((float)rz);       // (off the chain: rz is the previous iteration's)
         const double red2 = row16_sum_d(halve_pair_d<16>(lo_h ? cj * cj : lc * qj, lo_h ? lc * cj : 0.0, lane));
-        const auto pick = [&](double v, int ln_) {
-          return mk_d((unsigned)__builtin_amdgcn_readlane((int)lo_w(v), ln_),
-                      (unsigned)__builtin_amdgcn_readlane((int)hi_w(v), ln_));
-        };
-        const double cc = pick(red2, 0), clc = pick(red2, 16), clq = pick(red2, 32);
+        const double cc = pick_d(red2, 0), clc = pick_d(red2, 16), clq = pick_d(red2, 32);
         const double rzn = fma(cp * cp, tau2, cc);                     // residual_inner_prod :215 / :35-36
         const bool sure = rzn > sure_rz;
         const bool rec_first = kk == 0 && a.close_gran == nullptr && wave == 0;
-        const bool rec_last = kk == a.iters - 1 && wave == last_owner;
+        const bool rec_last = kk == a.iters - 1 && wave == last_owner && wig == 0;
+        const bool late_now = late && kk == a.iters - 1;               // (this wave's rec_last, formed at the next member's top)
         const bool own = rec_first || rec_last || !sure;
         float rnn = 0.f;
         if (kk < 0) {
           const float s1f = (float)a0;
           rnn = __builtin_amdgcn_sqrtf(s1f < 0.f ? 0.f : s1f);
-        } else if (own) {
-          // in the coordinates of C, as the dense form: r = c' r0 + C g with g = Tu (c - c' c0), r^T r = c'^2 a0 + 2 c' g.u0 + g^T G2 g
+        } else if (late_now) {
           const double dl = fma(-cp, c0, cj);                          // del = c - c' c0
-          __builtin_amdgcn_wave_barrier();
-          if (hf == 0) myv[j] = dl;
-          __builtin_amdgcn_wave_barrier();
-          double gj_;
-          {
-            double a0_ = 0.0, a1_ = 0.0;
-#pragma unroll
-            for (int q = 0; q < NH; q += 2) {
-              const double2 dd = *reinterpret_cast<const double2*>(myv + hf * NH + q);
-              a0_ = fma(tucol[(size_t)q * MLD], dd.x, a0_);
-              a1_ = fma(tucol[(size_t)(q + 1) * MLD], dd.y, a1_);
-            }
-            double lo_, up_;
-            halves_d(a0_ + a1_, lo_, up_);
-            gj_ = live ? lo_ + up_ : 0.0;
-          }
-          __builtin_amdgcn_wave_barrier();
-          if (hf == 0) myv[j] = gj_;
-          __builtin_amdgcn_wave_barrier();
-          const double nd = own_row_dot(nrow, myv + hf * NH);          // (G2 g)_j
-          const double r2 = row16_sum_d(halve_pair_d<16>(gj_ * nd, gj_ * u0, lane));
-          const double dnd = pick(r2, 0), dm = pick(r2, 16);
-          const double s1 = fma(cp, fma(cp, a0, 2.0 * dm), dnd);       // r^T r
-          const float s1f = (float)s1;
-          rnn = __builtin_amdgcn_sqrtf(s1f < 0.f ? 0.f : s1f);
+          if (hf == 0) late_v[j] = dl;
+          if (lane == 0) late_v[32] = cp;
+        } else if (own) {
+          const double dl = fma(-cp, c0, cj);                          // del = c - c' c0
+          rnn = resid_norm_c<NH, MLD>(dl, cp, a0, u0, live, j, hf, lane, myv, tucol, nrow);
         }
         if (kk >= 0) {                                               // closes iteration kk: beta, residual norm, records
           beta = ((float)rz < a.eps) ? 0.0 : (double)((float)rzn * inv_rz);  // :39-42
           if (rhs_zero) rnn = 0.f;                                   // :299
           rn = rnn;
-          if (rec && (rec_first || rec_last)) a.resid_rec[(size_t)kk * a.B + bc] = rn;
+          if (rec && (rec_first || rec_last) && !late_now) {
+            long long nb = a.B;  // (opaque: the record's offset is formed here, not kept -- and spilled -- around the loops)
+            asm volatile("" : "+s"(nb));
+            a.resid_rec[(size_t)kk * (size_t)nb + bc] = rn;
+          }
         } else {
           beta = 0.0;
           rn = rnn;
@@ -504,10 +592,15 @@ __global__ __launch_bounds__(R3_TPB, 2) void k_cg_rspace3(OnchipArgs a, PeerOut 
         a.rz[bc] = (float)rz;
         a.alpha[bc] = last_alpha;
         a.beta[bc] = (float)beta;
-        a.resid_norm[bc] = rn;
-        a.has_conv[bc] = conv ? 1 : 0;
-        if (a.close_gran) {
-          granule_store(a.close_gran + b, granule_pack(a.close_epoch | close_flags, rn), /*same_xcd=*/false);
+        if (late) {  // (residual norm, has_conv and the close granule: at the next member's top)
+          late_v[33] = (double)close_flags;
+          late_v[34] = (double)b;
+        } else {
+          a.resid_norm[bc] = rn;
+          a.has_conv[bc] = conv ? 1 : 0;
+          if (a.close_gran) {
+            granule_store(a.close_gran + b, granule_pack(a.close_epoch | close_flags, rn), /*same_xcd=*/false);
+          }
         }
       }
       // y = Tin (eta - xi g0): lane i walks column i of TinT (its half of the eigen-indices)
@@ -517,12 +610,22 @@ __global__ __launch_bounds__(R3_TPB, 2) void k_cg_rspace3(OnchipArgs a, PeerOut 
       xi = etap;
       {
         const double* col = mat_s + (size_t)(hf * NH) * MLD + jr;
-        double a0_ = 0.0, a1_ = 0.0;
+        // (every LDS read of the walk in flight before the first FMA: the chain's state is dead, its registers hold them.
+        //  Read as they were needed, each ds_read2_b64 had its own s_waitcnt: NH / 2 LDS round trips in a row)
+        double cv[NH];
+        double2 ee[NH / 2];
 #pragma unroll
         for (int q = 0; q < NH; q += 2) {
-          const double2 ee = *reinterpret_cast<const double2*>(myv + hf * NH + q);
-          a0_ = fma(col[(size_t)q * MLD], ee.x, a0_);
-          a1_ = fma(col[(size_t)(q + 1) * MLD], ee.y, a1_);
+          ee[q / 2] = *reinterpret_cast<const double2*>(myv + hf * NH + q);
+          cv[q] = col[(size_t)q * MLD];
+          cv[q + 1] = col[(size_t)(q + 1) * MLD];
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        double a0_ = 0.0, a1_ = 0.0;
+#pragma unroll
+        for (int q = 0; q < NH; q += 2) {  // (the same FMAs in the same order)
+          a0_ = fma(cv[q], ee[q / 2].x, a0_);
+          a1_ = fma(cv[q + 1], ee[q / 2].y, a1_);
         }
         double lo_, up_;
         halves_d(a0_ + a1_, lo_, up_);
@@ -548,8 +651,10 @@ __global__ __launch_bounds__(R3_TPB, 2) void k_cg_rspace3(OnchipArgs a, PeerOut 
     //       next_member has returned (the loop ends with this member, nobody of the group draws again);
     //   (2) the exchange above was the group's last, and workgroup 0 saw the granules of all GW workgroups in it: a
     //       sibling that is still polling them can only find them, so nobody of this group sets the error word any more;
-    //   (3) the member's state and close granule were stored behind the chain above, those of the group's earlier members
-    //       before.  (The call sits behind y, not behind those stores: here only C, xi and the stage pointers are live.)
+    //   (3) the member's state and close granule were stored behind the chain above (a final member never defers them).
+    //       Those of the group's earlier members were issued at the top of the member that followed each, in front of
+    //       that member's barrier: every wave of this workgroup has passed those barriers.  (The call sits behind y, not behind
+    //       the stores: here only C, xi and the stage pointers are live.)
     // Uniform over the workgroup (res[] is LDS, wig and po.n are scalars): the barriers inside the helper are legal.
     // With peer buffers the close stays behind the x pass: a rank that has seen its solve return has issued its peer stores.
     if (a.close_gran && wig == 0 && po.n == 0 && __builtin_amdgcn_readfirstlane((int)(b_next >= a.B))) {
@@ -607,7 +712,8 @@ __global__ __launch_bounds__(R3_TPB, 2) void k_cg_rspace3(OnchipArgs a, PeerOut 
     }
     __builtin_amdgcn_s_setprio(0);
     if (stamp) a.dbg[4] = wall_clock64();
-    __syncthreads();  // the next member's matrices / stages may replace these from here on
+    // (no barrier here: the one that releases mat_s and res[] to the next member stands behind its requests, above)
+    late_pending = wig == 0 && a.iters > 0 && __builtin_amdgcn_readfirstlane((int)(b_next < a.B)) != 0;
     b = b_next;
   }
   // (not closed yet: a group that never entered the loop -- fewer members than groups --, or peer buffers installed)
