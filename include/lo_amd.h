@@ -478,6 +478,14 @@ int lo_resident_inject_timeouts(int32_t n);
  * set_next_tag / set_next_epoch >= 0 replace the counters (to reach the wrap-around); out (or NULL) receives
  * {next tag base, next epoch, clears so far, launches so far}.                                                        */
 int lo_resident_handoff_debug(int32_t force_clear, int64_t set_next_tag, int64_t set_next_epoch, uint32_t* out);
+/* The order in which k_cg_rspace3 walks the members of a batch is UNSPECIFIED: x, `info` and every record are the same
+ * bit for bit in any order.  The library uses the freedom: a solve on the operator (C, B, N, padded rank) of the
+ * previous solve on the library's buffer, when that one closed clean, walks the members from B - 1 down, so that it
+ * starts with what the previous solve left in the memory-side cache; every other solve walks from 0 up (ABI 32).
+ * Test / debug access for the current device: mode -1 leaves the rule as it is, 0 automatic (the rule above), 1 always
+ * from 0 up, 2 always from B - 1 down (forced modes hold for launches on the caller's workspace too, e.g. under
+ * LO_OC_DEBUG); out (or NULL) receives {direction of the last launch: 0 up, 1 down; launches that walked down so far}. */
+int lo_resident_order_debug(int32_t mode, uint32_t* out);
 
 /* ---- solve sessions: the headline solve without its per-call set-up (ABI 20) ---------------------------------------- */
 /* A preconditioner cache serves many solves of one operator; what lo_cg_solve_f32 does before and after its one launch

@@ -39,7 +39,7 @@ LO_OP_KERNEL_GRAD_DIAG = 14
 LO_KERNEL_GRAD_MAX_DIM = 16
 LO_DIAG_NONE, LO_DIAG_FULL, LO_DIAG_CONST = 0, 1, 2
 LO_BLOCK_DIAG, LO_BLOCK_INTERLEAVED, LO_BLOCK_SUM = 0, 1, 2
-ABI_VERSION = 31
+ABI_VERSION = 32
 
 LO_ERR_UNSUPPORTED = -4
 LO_FUSED_OK, LO_FUSED_EARLY_STOP, LO_FUSED_CONTINUE, LO_FUSED_TIMEOUT = 0, 1, 2, 3
@@ -195,6 +195,7 @@ _PROTOTYPES = {
     "lo_resident_status_get": (ci, [P(ResidentStatus)]),
     "lo_resident_inject_timeouts": (ci, [i32]),
     "lo_resident_handoff_debug": (ci, [i32, i64, i64, P(C.c_uint32)]),
+    "lo_resident_order_debug": (ci, [i32, P(C.c_uint32)]),
     "lo_solve_fused_supported": (ci, [P(OpDesc), i32, P(CgParams)]),
     "lo_solve_fused_workspace_bytes": (sz, [P(OpDesc), i32, P(CgParams)]),
     "lo_solve_fused_f32": (ci, [P(OpDesc), i32, f32, P(CgParams), vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, P(FusedInfo),

@@ -779,6 +779,8 @@ struct CgDebug {
                 ts[8], ts[9], ts[10]);
       fprintf(stderr, "onchip member0 (100 MHz ticks): load %lld init %lld iters %lld store %lld | wg-wait %lld publish %lld poll %lld\n",
               ts[1] - ts[0], ts[2] - ts[1], ts[3] - ts[2], ts[4] - ts[3], ts[5], ts[6], ts[7]);
+      if (ts[11] && ts[0])  // (k_cg_rspace3: where the member's top lies behind the launch's first workgroup)
+        fprintf(stderr, "  top at %lld ticks behind the entry of group 0\n", ts[0] - ts[11]);
     }
     return LO_OK;
   }
@@ -1012,6 +1014,7 @@ static int resident_attempt(CgSolve& s, int attempt, bool lean, bool dense, OcNe
   a.close_gran = nullptr; a.close_count = nullptr; a.close_ctrl = nullptr; a.close_mirror = nullptr;
   a.close_ticket = 0; a.close_tol = 0.f; a.close_floor_ok = 0;
   a.close_epoch = 0x80000000u; a.tag_base = 0; a.handoff_owned = 0;  // (the cleared workspace; rspace3_launch_owned replaces them)
+  a.member_flip = 0;  // (the walk order of k_cg_rspace3: rspace3_go decides it for every launch)
   a.iters = s.plan.first_stop_iteration + 1; a.eps = prm->eps; a.stop_after = prm->stop_updating_after;
   a.x = d.x; a.r = d.r; a.p = d.p; a.z = d.z;
   auto lean_state = [&](bool on) {  // (kernels without the result-only mode get the state pointers back)

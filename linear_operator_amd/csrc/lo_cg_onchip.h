@@ -60,6 +60,8 @@ struct OnchipArgs {
   unsigned close_ticket;
   float close_tol;                 // tolerance (< 0: the host decides -- batch-global rule over ranks)
   int close_floor_ok;              // iters - 1 >= min(10, max_iter - 1)
+  int member_flip;                 // k_cg_rspace3: 1 walks the members from B - 1 down (physical member = B - 1 - drawn index);
+                                   // set by rspace3_go for every launch, read by no other kernel.  Results do not depend on it
   long long* dbg;  // optional timestamps (wall_clock64) of member dbg_member / its workgroup 0, or nullptr
   int dbg_member;
 };

@@ -23,7 +23,10 @@
 //     residual norm is formed by workgroup 0 only and, but for a group's final member, at the NEXT member's top while
 //     its loads travel; the member draw no longer waits for its own round trip in front of the top's requests; one
 //     poll round per exchange up to 9 granules a thread; the exit product's LDS reads are in flight together
-//     (143.6 -> 139.9 us per launch).
+//     (143.6 -> 139.9 us per launch);
+//   * (fourth pass, profiles/r13) consecutive solves of one operator walk the members in opposite directions
+//     (OnchipArgs::member_flip, decided in rspace3_go): a solve starts with the members the previous one left in the
+//     256 MiB memory-side cache instead of the ones it evicted first (139.2 -> 131.1 us per launch).
 //
 // Numerics: fp64 sums in another order (the old kernel's results to ~1e-15 relative before the final rounding to fp32).
 #include <algorithm>
@@ -213,20 +216,31 @@ __global__ __launch_bounds__(R3_TPB, 2) void k_cg_rspace3(OnchipArgs a, PeerOut 
   };
   int closed = 0;  // workgroup-uniform: this workgroup has run the closing step (inside the loop, below)
   bool late_pending = false;  // workgroup-uniform: the previous member's last residual norm is still to be formed
+  // Members are DRAWN by logical index b (grp first, then ngroups + the hand-out counter, as ever) and ADDRESSED by the
+  // physical index m = flip ? B - 1 - b : b: a launch that follows one on the same operator walks the batch the other way
+  // round and finds the members the previous launch read last still in the memory-side cache (rspace3_go).
+  // Everything a member owns in memory -- operator, right-hand side, matrices, x, records, close granule -- goes by m; a
+  // member's arithmetic does not depend on when it runs, so results are the same bit for bit in either direction.
+  const bool flip = a.member_flip != 0;
+  // (debug stamps: the launch's origin on the time axis of the stamped member -- group 0 enters with the first wave of
+  //  workgroups; kept in memory, not in a register around the member loop)
+  if (a.dbg && grp == 0 && wig == 0 && t == 0) a.dbg[11] = wall_clock64();
   int64_t b = grp;
   {
     int tl0 = t;
     asm volatile("" : "+v"(tl0));
     if (b < a.B) {
-      request(b, tl0, 0, std::integral_constant<int, NPF>{}, pre);
-      request(b, tl0, NPF, std::integral_constant<int, NXT>{}, nxt);
+      const int64_t m0 = flip ? a.B - 1 - b : b;
+      request(m0, tl0, 0, std::integral_constant<int, NPF>{}, pre);
+      request(m0, tl0, NPF, std::integral_constant<int, NXT>{}, nxt);
     } else {
 #pragma unroll
       for (int i = 0; i < NPF; ++i) pre[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
     }
   }
   while (b < a.B) {
-    const bool stamp = a.dbg && b == a.dbg_member && wig == 0 && t == 0;
+    const int64_t m = flip ? a.B - 1 - b : b;  // (workgroup-uniform: scalar registers only)
+    const bool stamp = a.dbg && m == a.dbg_member && wig == 0 && t == 0;
     if (stamp) a.dbg[0] = wall_clock64();
     int drawn = 0;
     // (its round trip hides behind the member load -- through a pointer whose address space the compiler cannot see: on a
@@ -244,8 +258,8 @@ __global__ __launch_bounds__(R3_TPB, 2) void k_cg_rspace3(OnchipArgs a, PeerOut 
     for (int i = 0; i < NXT; ++i) Cr[NPF + i] = nxt[i];
     float bq4[4], dq4[4];
     {
-      g_cf* bb_ = opaque_uniform((g_cf*)(a.rhs + (size_t)b * a.N + row0c));
-      g_cf* dd_ = opaque_uniform((g_cf*)(di_full ? a.dinv + (size_t)b * a.N + row0c : a.dinv + b));
+      g_cf* bb_ = opaque_uniform((g_cf*)(a.rhs + (size_t)m * a.N + row0c));
+      g_cf* dd_ = opaque_uniform((g_cf*)(di_full ? a.dinv + (size_t)m * a.N + row0c : a.dinv + m));
       const int lo_e = row0 - row0c, hi_e = max(0, min(256, a.N - row0c));
       const int dstride = di_full ? 1 : 0;
 #pragma unroll
@@ -261,7 +275,7 @@ __global__ __launch_bounds__(R3_TPB, 2) void k_cg_rspace3(OnchipArgs a, PeerOut 
     f32x4 mv[NM];
     {
       typedef __attribute__((address_space(1))) const f32x4 g_m4;
-      const g_m4* src = (const g_m4*)(a.RSD + (size_t)b * 6 * RC * RC);
+      const g_m4* src = (const g_m4*)(a.RSD + (size_t)m * 6 * RC * RC);
 #pragma unroll
       for (int u = 0; u < NM; ++u) {
         const int e = min(tl + R3_TPB * u, 3 * RC * RC / 2 - 1);  // piece e of the three matrices in LDS order
@@ -270,7 +284,7 @@ __global__ __launch_bounds__(R3_TPB, 2) void k_cg_rspace3(OnchipArgs a, PeerOut 
         mv[u] = src[(size_t)mg * (RC * RC / 2) + (e - ms * (RC * RC / 2))];
       }
     }
-    const double lam_mine = a.RSD[((size_t)b * 6 + 5) * RC * RC + min(ln & 31, RC - 1)];  // this lane's eigenvalue
+    const double lam_mine = a.RSD[((size_t)m * 6 + 5) * RC * RC + min(ln & 31, RC - 1)];  // this lane's eigenvalue
     // ---- the last residual norm of the PREVIOUS member, when that was not the group's final one (see `late` below) ----
     // Every request of this member is in flight and nothing has arrived: the wave that owes the norm forms it here, from
     // what it left in late_v, while all four waves wait for their loads anyway.  mat_s (TuT, G2) and res[] are still the
@@ -461,7 +475,7 @@ __global__ __launch_bounds__(R3_TPB, 2) void k_cg_rspace3(OnchipArgs a, PeerOut 
       int tp = t;
       asm volatile("" : "+v"(tp));
       if (b_next < a.B) {
-        request(b_next, tp, 0, std::integral_constant<int, NPF>{}, pre);
+        request(flip ? a.B - 1 - b_next : b_next, tp, 0, std::integral_constant<int, NPF>{}, pre);
       } else {  // (defined on both paths: no value of the finished members stays live)
 #pragma unroll
         for (int i = 0; i < NPF; ++i) pre[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -513,7 +527,7 @@ __global__ __launch_bounds__(R3_TPB, 2) void k_cg_rspace3(OnchipArgs a, PeerOut 
       float rn = 0.f, last_alpha = 0.f;
       bool conv = false;
       unsigned close_flags = 0u;
-      const size_t bc = (size_t)b;
+      const size_t bc = (size_t)m;
       const bool rec = wig == 0 && lane == 0;
       const int last_owner = (a.iters - 1) & 3;  // the wave that forms the last residual norm writes the member's state
       // The last iteration's residual norm enters nothing but the member's records (resid_rec, resid_norm, has_conv, the
@@ -594,12 +608,12 @@ __global__ __launch_bounds__(R3_TPB, 2) void k_cg_rspace3(OnchipArgs a, PeerOut 
         a.beta[bc] = (float)beta;
         if (late) {  // (residual norm, has_conv and the close granule: at the next member's top)
           late_v[33] = (double)close_flags;
-          late_v[34] = (double)b;
+          late_v[34] = (double)m;
         } else {
           a.resid_norm[bc] = rn;
           a.has_conv[bc] = conv ? 1 : 0;
           if (a.close_gran) {
-            granule_store(a.close_gran + b, granule_pack(a.close_epoch | close_flags, rn), /*same_xcd=*/false);
+            granule_store(a.close_gran + m, granule_pack(a.close_epoch | close_flags, rn), /*same_xcd=*/false);
           }
         }
       }
@@ -677,9 +691,10 @@ __global__ __launch_bounds__(R3_TPB, 2) void k_cg_rspace3(OnchipArgs a, PeerOut 
       const double* myv = gv[wave];
       const double2 ya = *reinterpret_cast<const double2*>(&myv[4 * k2]);
       const double2 yb = *reinterpret_cast<const double2*>(&myv[4 * k2 + 2]);
-      g_f* const xb = opaque_uniform((g_f*)(a.xout + (size_t)b * a.N + row0c));
+      g_f* const xb = opaque_uniform((g_f*)(a.xout + (size_t)m * a.N + row0c));
       const bool more = b_next < a.B;
-      g_cc* const Cn = (g_cc*)(a.C + ((size_t)(more ? b_next : b) * a.N + row0c) * RC);
+      const int64_t m_next = flip ? a.B - 1 - b_next : b_next;
+      g_cc* const Cn = (g_cc*)(a.C + ((size_t)(more ? m_next : m) * a.N + row0c) * RC);
       const unsigned loffn = (unsigned)((g2 * RC + 4 * k2) * sizeof(float));
 #pragma unroll
       for (int js = 0; js < 4; ++js) {
@@ -699,7 +714,7 @@ __global__ __launch_bounds__(R3_TPB, 2) void k_cg_rspace3(OnchipArgs a, PeerOut 
           const float xval = (float)(acc * (double)dw[rw]);  // :335
           xb[rw] = xval;
           for (int pp = 0; pp < po.n; ++pp)  // (prototype: the gather as peer writes)
-            ((g_f*)po.buf[pp])[((size_t)(b + po.member_off)) * a.N + row] = xval;
+            ((g_f*)po.buf[pp])[((size_t)(m + po.member_off)) * a.N + row] = xval;
         }
         if (CH * jj >= NPF) {  // the registers of this group are free: the next member's rows of the same instructions
           g_cc* bqn = opaque_uniform(Cn + (CH * jj + 4) * 1024);
@@ -763,6 +778,18 @@ struct HandoffBlock {
   std::atomic<unsigned> confirmed{0};       // id of the last launch the host saw closing clean
   bool force_clear = false;                 // lo_resident_handoff_debug: the next launch clears the block
   unsigned clears = 0, launches = 0;        // (lo_resident_handoff_debug)
+  // The walk order of the members (OnchipArgs::member_flip).  A solve streams its whole operator, 1.05 MB a member at
+  // the headline shape, and the memory-side cache (256 MiB, allocates on streamed reads) keeps roughly the bytes read
+  // last.  Walked the same way every time, a solve starts with the members the previous one read longest ago: all
+  // evicted.  So an owned launch on the operator of the last owned launch -- same C, B, N and RC -- runs in the opposite
+  // direction when that launch was confirmed clean, and every other launch runs forward.  The order never enters a
+  // result: a record that is stale or matches by accident costs nothing but the hits.
+  const float* ord_C = nullptr;             // operator of the last owned launch (null: none)
+  int64_t ord_B = 0;
+  int ord_N = 0, ord_RC = 0;
+  bool ord_flip = false;                    // its direction
+  int ord_mode = 0;                         // lo_resident_order_debug: 0 automatic, 1 always forward, 2 always reverse
+  unsigned ord_last = 0, ord_reversed = 0;  // direction of the last k_cg_rspace3 launch (owned or not), reversed launches
 };
 HandoffBlock g_handoff[16];
 std::atomic<unsigned> g_handoff_ids{0};
@@ -811,6 +838,9 @@ int rspace3_go(const OnchipArgs& a, int nwg, const OwnedLaunch* own, hipStream_t
   ResidentLaunch guard(st);
   OnchipArgs a2 = a;
   a2.prefetch = rspace3_prio();
+  a2.member_flip = 0;
+  int dev = 0;  // (the order state of a launch on the caller's workspace: the device's block record, without its buffer)
+  HandoffBlock* const ho = (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 16) ? &g_handoff[dev] : nullptr;
   if (own) {
     // (host-assigned tags must not be baked into a captured graph: a replay would meet its own granules)
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
@@ -820,8 +850,13 @@ int rspace3_go(const OnchipArgs& a, int nwg, const OwnedLaunch* own, hipStream_t
     }
     HandoffBlock* h = (a.B <= (int64_t)HO_MAX_MEMBERS && (size_t)2 * nwg <= HO_MAX_WGS) ? handoff_block() : nullptr;
     if (!h) return LO_ERR_UNSUPPORTED;
+    const bool prev_clean = h->last_launch != 0 && h->last_launch == h->confirmed.load(std::memory_order_acquire);
     bool clear = h->force_clear || h->last_launch != h->confirmed.load(std::memory_order_acquire);
     h->force_clear = false;
+    // (see HandoffBlock: the opposite direction on the operator of a clean predecessor, forward otherwise)
+    const bool same_op = h->ord_C == a.C && h->ord_B == a.B && h->ord_N == a.N && h->ord_RC == RC;
+    a2.member_flip = (same_op && prev_clean && !h->ord_flip) ? 1 : 0;
+    h->ord_C = a.C; h->ord_B = a.B; h->ord_N = a.N; h->ord_RC = RC;
     clear = handoff_advance(&h->next_tag, &h->next_epoch, a.B, &a2.tag_base, &a2.close_epoch) || clear;
     h->last_launch = g_handoff_ids.fetch_add(1, std::memory_order_relaxed) + 1;
     if (h->last_launch == 0) h->last_launch = g_handoff_ids.fetch_add(1, std::memory_order_relaxed) + 1;
@@ -840,6 +875,12 @@ int rspace3_go(const OnchipArgs& a, int nwg, const OwnedLaunch* own, hipStream_t
     a2.gbuf = reinterpret_cast<unsigned long long*>(h->buf + HO_HEAD_BYTES);
     a2.close_gran = a2.gbuf + HO_MAX_WGS * HO_GRAN_PER_WG;
     if (own->inject) LO_HIP_CHECK(hipMemsetAsync(a2.err, 1, 1, st));
+  }
+  if (ho) {
+    if (ho->ord_mode) a2.member_flip = ho->ord_mode == 2 ? 1 : 0;  // (forced: owned and other launches alike)
+    if (own) ho->ord_flip = a2.member_flip != 0;
+    ho->ord_last = (unsigned)a2.member_flip;
+    ho->ord_reversed += (unsigned)a2.member_flip;
   }
   PeerOut po;
   {
@@ -919,6 +960,21 @@ extern "C" int lo_resident_handoff_debug(int32_t force_clear, int64_t set_next_t
     out[1] = h.next_epoch;
     out[2] = h.clears;
     out[3] = h.launches;
+  }
+  return LO_OK;
+}
+
+// Test / debug access to the walk order of k_cg_rspace3 on the current device (lo_amd.h).
+extern "C" int lo_resident_order_debug(int32_t mode, uint32_t* out) {
+  lo::ResidentLock guard;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return LO_ERR_BADARG;
+  if (mode < -1 || mode > 2) return LO_ERR_BADARG;
+  lo::HandoffBlock& h = lo::g_handoff[dev];
+  if (mode >= 0) h.ord_mode = mode;
+  if (out) {
+    out[0] = h.ord_last;
+    out[1] = h.ord_reversed;
   }
   return LO_OK;
 }

@@ -2293,6 +2293,15 @@ def resident_handoff_debug(force_clear: bool = False, next_tag: int = -1, next_e
     return {"next_tag": int(out[0]), "next_epoch": int(out[1]), "clears": int(out[2]), "launches": int(out[3])}
 
 
+def resident_order_debug(mode: int = -1) -> dict:
+    """lo_resident_order_debug: the order in which the headline solve (`k_cg_rspace3`) walks its members on the current
+    device -- mode 0 automatic (opposite to a clean predecessor on the same operator), 1 always forward, 2 always
+    reverse, -1 leave; returns the direction of the last launch and how many launches ran in reverse."""
+    out = (C.c_uint32 * 2)()
+    _hip.call("lo_resident_order_debug", int(mode), out)
+    return {"last": "reverse" if out[0] else "forward", "reversed": int(out[1])}
+
+
 def peer_gather_set(bufs=(), member_offset: int = 0) -> None:
     """lo_peer_gather_set (prototype): up to seven [B_total, N] fp32 buffers the resident single-column solve writes its
     solutions into next to its own output -- the gather of SURVEY 8(e) as peer writes.  () removes them."""
