@@ -1067,6 +1067,18 @@ int lo_tri_solve_f32(const float* T, const float* rhs, float* out, float* sumsq,
 int lo_cholesky_solve_f32(const float* T, const float* rhs, float* out, int64_t B, int64_t N, int64_t c, int32_t upper,
                           void* stream);
 
+/* ---- the same path in fp64 (ABI 33; csrc/lo_chol_f64.hip) ------------------------------------------------------------
+ * Argument order, refusals, info / logdet / sumsq semantics and determinism as the fp32 calls above; every operand and
+ * every sum is float64 (sumsq included), the panel update runs on v_mfma_f64_16x16x4_f64.  N <= 1024; the sizer returns 0
+ * for a shape the factorisation refuses.  out may alias rhs.                                                         */
+size_t lo_cholesky_f64_workspace_bytes(int64_t B, int64_t N);
+int lo_cholesky_f64(const double* A, double* L, int32_t* info, double* logdet, int64_t B, int64_t N, void* ws,
+                    size_t ws_bytes, void* stream);
+int lo_tri_solve_f64(const double* T, const double* rhs, double* out, double* sumsq, int64_t B, int64_t N, int64_t c,
+                     int32_t upper, int32_t transpose, void* stream);
+int lo_cholesky_solve_f64(const double* T, const double* rhs, double* out, int64_t B, int64_t N, int64_t c,
+                          int32_t upper, void* stream);
+
 /* ---- masked operators (ABI 21; csrc/lo_masked.hip) ---------------------------------------------------------------------
  * The kind LO_OP_MASKED is served by lo_matvec_f32 and the solvers above.  lo_mask_expand_f32 is its first step alone:
  * u [B, N0, c] = S^T v for v [B, M, c] (zero rows where the mask is false), one coalesced write of u; idx as in

@@ -1,5 +1,6 @@
 """Autograd Functions of the exact small-N path: the native batched Cholesky, triangular solve and Cholesky solve
-(csrc/lo_chol.hip through kernels.cholesky / triangular_solve / cholesky_solve) with their pull-backs.  The ATen calls
+(csrc/lo_chol.hip, float64: csrc/lo_chol_f64.hip, through kernels.cholesky / triangular_solve / cholesky_solve) with
+their pull-backs, which run on the kernels of the same dtype.  The ATen calls
 they replace (torch.linalg.cholesky_ex, torch.linalg.solve_triangular, torch.cholesky_solve) are differentiable, so
 these are too.
 
@@ -96,20 +97,26 @@ class NativeTriSolve(torch.autograd.Function):
 
 # 1 x 800^2: the two sweeps take about 1040 us against about 500 us for ATen, the only single-matrix solve measured
 SINGLE_SOLVE_MAX_N = 0
+# float64, 1 x 800^2 (tools/mb_chol.py --dtype float64): factor + one-column solve takes about
+# 4140 us with the native substitution against about 3360 us with ATen's, so ATen keeps the unbatched float64 solve
+SINGLE_SOLVE_MAX_N_F64 = 0
+_NATIVE_DTYPES = (torch.float32, torch.float64)
 
 
 def native_ok(factor: torch.Tensor, *others: torch.Tensor, solve: bool = False) -> bool:
-    """The routing predicate of the exact path: float32 HIP tensors with 1 <= N <= 1024 go to the native kernels,
-    everything else (CPU, float64, larger N) keeps the ATen calls.  `solve`: the call is a substitution, not a
-    factorisation -- one workgroup per member and column block leaves a single matrix on a few compute units, and
-    above SINGLE_SOLVE_MAX_N rows ATen's whole-device substitution is faster (measured), so an
-    unbatched solve of that size stays there.  Batched calls are always native: they win at every measured shape,
-    and they include the two shapes at which the ATen routines fault."""
-    if not (factor.is_cuda and factor.dtype == torch.float32 and factor.dim() >= 2
+    """The routing predicate of the exact path: float32 or float64 HIP tensors, all of one dtype, with 1 <= N <= 1024
+    go to the native kernels (csrc/lo_chol.hip, csrc/lo_chol_f64.hip), everything else (CPU, other or mixed dtypes,
+    larger N) keeps the ATen calls.  `solve`: the call is a substitution, not a factorisation -- one workgroup per member
+    and column block leaves a single matrix on a few compute units, and above SINGLE_SOLVE_MAX_N (float64:
+    SINGLE_SOLVE_MAX_N_F64) rows ATen's whole-device substitution is faster (measured, DESIGN sections 6d and 6d-64),
+    so an unbatched solve of that size stays there.  Batched calls are always native: they win at every measured
+    shape, and they include the shapes at which the ATen routines fault."""
+    if not (factor.is_cuda and factor.dtype in _NATIVE_DTYPES and factor.dim() >= 2
             and 1 <= factor.shape[-1] <= K.CHOLESKY_MAX_N and factor.shape[-1] == factor.shape[-2]
-            and all(o.is_cuda and o.dtype == torch.float32 for o in others)):
+            and all(o.is_cuda and o.dtype == factor.dtype for o in others)):
         return False
-    if solve and factor.shape[-1] > SINGLE_SOLVE_MAX_N:
+    single_max = SINGLE_SOLVE_MAX_N if factor.dtype == torch.float32 else SINGLE_SOLVE_MAX_N_F64
+    if solve and factor.shape[-1] > single_max:
         batch = torch.broadcast_shapes(factor.shape[:-2], *(o.shape[:-2] for o in others if o.dim() >= 2))
         return batch.numel() > 1
     return True
@@ -135,7 +142,7 @@ def chol_solve(factor, rhs, upper=False):
 
 def substitute(factor, rhs, upper=False, transpose=False):
     """M^-1 rhs for M = factor or factor^T (`transpose`) of a lower / upper triangular tensor: the native kernel for
-    float32 HIP factors of at most 1024 rows, torch.linalg.solve_triangular otherwise.  A transposed view of a
+    float32 or float64 HIP factors of at most 1024 rows, torch.linalg.solve_triangular otherwise.  A transposed view of a
     contiguous factor is handed over as that factor with both flags flipped, never copied."""
     if native_ok(factor, rhs, solve=True):
         if not factor.is_contiguous() and factor.mT.is_contiguous():

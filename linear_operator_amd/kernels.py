@@ -2310,12 +2310,25 @@ def peer_gather_set(bufs=(), member_offset: int = 0) -> None:
     _hip.call("lo_peer_gather_set", arr, n, int(member_offset))
 
 
-# ---------------------------------------------------------------- exact small-N path (csrc/lo_chol.hip)
-CHOLESKY_MAX_N = 1024  # what lo_cholesky_f32 / lo_tri_solve_f32 / lo_cholesky_solve_f32 take
+# ------------------------------------------- exact small-N path (csrc/lo_chol.hip, float64: csrc/lo_chol_f64.hip)
+CHOLESKY_MAX_N = 1024  # what lo_cholesky_* / lo_tri_solve_* / lo_cholesky_solve_* take, _f32 and _f64 alike
+_CHOL_SUFFIX = {torch.float32: "f32", torch.float64: "f64"}
+
+
+def _chol_suffix(*tensors: torch.Tensor) -> str:
+    """The entry-point suffix of the operands' common dtype, float32 or float64; mixed dtypes are an error."""
+    dtype = tensors[0].dtype
+    if dtype not in _CHOL_SUFFIX:
+        raise ValueError(f"the exact path takes float32 or float64 tensors, got {dtype}")
+    if any(t.dtype != dtype for t in tensors):
+        raise ValueError(f"factor and right-hand side must share one dtype, got {[t.dtype for t in tensors]}")
+    _hip.require_hip(*tensors, dtype=dtype)
+    return _CHOL_SUFFIX[dtype]
 
 
 def _factor_and_rhs(L: torch.Tensor, rhs: torch.Tensor):
-    """A factor [*b, N, N] and right-hand sides [*b', N, c] (or [N]) broadcast to one batch and flattened."""
+    """A factor [*b, N, N] and right-hand sides [*b', N, c] (or [N]) of one dtype, broadcast to one batch and flattened;
+    last the suffix of the entry points for that dtype."""
     if L.dim() < 2 or L.shape[-1] != L.shape[-2]:
         raise ValueError(f"expected square factors [..., N, N], got {tuple(L.shape)}")
     is_vec = rhs.dim() == 1
@@ -2323,20 +2336,21 @@ def _factor_and_rhs(L: torch.Tensor, rhs: torch.Tensor):
     N, c = L.shape[-1], cols.shape[-1]
     if cols.shape[-2] != N:
         raise ValueError(f"right-hand side of {cols.shape[-2]} rows against a factor of {N}")
-    _hip.require_hip(L, cols)
+    sfx = _chol_suffix(L, cols)
     bs = torch.broadcast_shapes(L.shape[:-2], cols.shape[:-2])
     L3 = _flat(L.expand(*bs, N, N), 2)
     R3 = _flat(cols.expand(*bs, N, c), 2)
-    return L3, R3, bs, is_vec
+    return L3, R3, bs, is_vec, sfx
 
 
 def cholesky(A: torch.Tensor, want_logdet: bool = False):
-    """lo_cholesky_f32: (L, info[, logdet]) of A [*batch, N, N] = L L^T, N <= 1024; only the lower triangle of A is
-    read, the strict upper triangle of L is zero, info [*batch] int32 is 0 or the 1-based order of the first leading
-    minor whose pivot is not > 0 (that member's L is unspecified), logdet [*batch] float64 = 2 sum log L_ii."""
+    """lo_cholesky_f32 / lo_cholesky_f64 by dtype: (L, info[, logdet]) of A [*batch, N, N] = L L^T, N <= 1024; only the
+    lower triangle of A is read, the strict upper triangle of L is zero, info [*batch] int32 is 0 or the 1-based order of
+    the first leading minor whose pivot is not > 0 (that member's L is unspecified), logdet [*batch] float64 =
+    2 sum log L_ii."""
     if A.dim() < 2 or A.shape[-1] != A.shape[-2]:
         raise ValueError(f"expected square matrices [..., N, N], got {tuple(A.shape)}")
-    _hip.require_hip(A)
+    sfx = _chol_suffix(A)
     bs, N = A.shape[:-2], A.shape[-1]
     A3 = _flat(A, 2)
     B, dev = A3.shape[0], A.device
@@ -2344,22 +2358,23 @@ def cholesky(A: torch.Tensor, want_logdet: bool = False):
     info = torch.empty(B, dtype=torch.int32, device=dev)
     logdet = torch.empty(B, dtype=torch.float64, device=dev) if want_logdet else None
     if B > 0 and N > 0:
-        _launch("lo_cholesky_f32", dev, A3, L, info, logdet, B, N,
-                ws_bytes=_hip.load().lo_cholesky_workspace_bytes(B, N))
+        sizer = "lo_cholesky_workspace_bytes" if sfx == "f32" else "lo_cholesky_f64_workspace_bytes"
+        _launch(f"lo_cholesky_{sfx}", dev, A3, L, info, logdet, B, N, ws_bytes=getattr(_hip.load(), sizer)(B, N))
     out = (L.reshape(*bs, N, N), info.reshape(bs))
     return out + (logdet.reshape(bs),) if want_logdet else out
 
 
 def triangular_solve(L: torch.Tensor, rhs: torch.Tensor, transpose: bool = False, want_sumsq: bool = False,
                      upper: bool = False):
-    """lo_tri_solve_f32: L^-1 rhs, or L^-T rhs (`transpose`), for a lower (or `upper`) factor [*b, N, N], N <= 1024;
-    with `want_sumsq` also sum_i out_ic^2 [*batch, c] from the same launch (the inv_quad of a Cholesky factor)."""
-    L3, R3, bs, is_vec = _factor_and_rhs(L, rhs)
+    """lo_tri_solve_f32 / lo_tri_solve_f64 by dtype: L^-1 rhs, or L^-T rhs (`transpose`), for a lower (or `upper`) factor
+    [*b, N, N], N <= 1024; with `want_sumsq` also sum_i out_ic^2 [*batch, c], of the operands' dtype, from the same
+    launch (the inv_quad of a Cholesky factor)."""
+    L3, R3, bs, is_vec, sfx = _factor_and_rhs(L, rhs)
     B, N, c = R3.shape
     out = torch.empty_like(R3)
-    sumsq = torch.empty(B, c, dtype=torch.float32, device=R3.device) if want_sumsq else None
+    sumsq = torch.empty(B, c, dtype=R3.dtype, device=R3.device) if want_sumsq else None
     if out.numel():
-        _launch("lo_tri_solve_f32", R3.device, L3, R3, out, sumsq, B, N, c, int(bool(upper)), int(bool(transpose)))
+        _launch(f"lo_tri_solve_{sfx}", R3.device, L3, R3, out, sumsq, B, N, c, int(bool(upper)), int(bool(transpose)))
     out = out.reshape(*bs, N) if is_vec else out.reshape(*bs, N, c)
     if not want_sumsq:
         return out
@@ -2367,10 +2382,11 @@ def triangular_solve(L: torch.Tensor, rhs: torch.Tensor, transpose: bool = False
 
 
 def cholesky_solve(L: torch.Tensor, rhs: torch.Tensor, upper: bool = False) -> torch.Tensor:
-    """lo_cholesky_solve_f32: (L L^T)^-1 rhs for a lower factor, (U^T U)^-1 rhs for an `upper` one, in one launch."""
-    L3, R3, bs, is_vec = _factor_and_rhs(L, rhs)
+    """lo_cholesky_solve_f32 / lo_cholesky_solve_f64 by dtype: (L L^T)^-1 rhs for a lower factor, (U^T U)^-1 rhs for an
+    `upper` one, in one launch."""
+    L3, R3, bs, is_vec, sfx = _factor_and_rhs(L, rhs)
     B, N, c = R3.shape
     out = torch.empty_like(R3)
     if out.numel():
-        _launch("lo_cholesky_solve_f32", R3.device, L3, R3, out, B, N, c, int(bool(upper)))
+        _launch(f"lo_cholesky_solve_{sfx}", R3.device, L3, R3, out, B, N, c, int(bool(upper)))
     return out.reshape(*bs, N) if is_vec else out.reshape(*bs, N, c)

@@ -910,7 +910,8 @@ class _TriangularFactor:
     """Minimal stand-in for CholLinearOperator(TriangularLinearOperator(L)) on the N <= max_cholesky_size
     branch (reference: chol_linear_operator.py:121, triangular_linear_operator.py:72-91): exact solves and
     logdet through the routed helpers of utils/cholesky.py and functions/_cholesky.py -- the native kernels of
-    csrc/lo_chol.hip for float32 HIP factors of at most 1024 rows, ATen otherwise.  The public class of the same algebra
+    csrc/lo_chol.hip and csrc/lo_chol_f64.hip for float32 and float64 HIP factors of at most 1024 rows, ATen otherwise.
+    The public class of the same algebra
     is operators/chol_linear_operator.py; this one keeps the return conventions `LinearOperator.cholesky()` has had."""
 
     def __init__(self, factor: Tensor, upper: bool = False):

@@ -2,8 +2,8 @@
 an upper one (reference: linear_operator/operators/chol_linear_operator.py:18-189; GPyTorch constructs it and tests
 `isinstance` against it).  A RootLinearOperator whose root is a TriangularLinearOperator: solves are the two
 substitutions of that root, the quadratic form is one substitution and a column sum of squares, the log-determinant
-comes off the stored diagonal.  With a float32 HIP factor of at most 1024 rows all of these are the native kernels of
-csrc/lo_chol.hip; CPU and float64 factors take ATen."""
+comes off the stored diagonal.  With a float32 or float64 HIP factor of at most 1024 rows all of these are the
+native kernels of csrc/lo_chol.hip and csrc/lo_chol_f64.hip; CPU factors take ATen."""
 from __future__ import annotations
 
 import warnings

@@ -3,9 +3,10 @@
 `DiagLinearOperator` derives from it, diag_linear_operator.py:16, and GPyTorch tests `isinstance(op,
 TriangularLinearOperator)`).
 
-Solves with a dense float32 HIP factor of at most 1024 rows are the native blocked substitution
-(lo_tri_solve_f32 / lo_cholesky_solve_f32 through functions/_cholesky.py; an upper factor or a transposed view goes
-through the kernel's flags, not a copy); CPU, float64 and larger factors take `torch.linalg.solve_triangular`.  Diagonal
+Solves with a dense float32 or float64 HIP factor of at most 1024 rows are the native blocked substitution
+(lo_tri_solve_f32 / lo_cholesky_solve_f32 and their _f64 twins through functions/_cholesky.py; an upper factor or a
+transposed view goes through the kernel's flags, not a copy); CPU and larger factors take
+`torch.linalg.solve_triangular`.  Diagonal
 operators override everything with elementwise forms and never call this constructor with a dense tensor.
 """
 from __future__ import annotations

@@ -1,7 +1,7 @@
 """psd_safe_cholesky: cholesky_ex with escalating jitter (reference: linear_operator/utils/cholesky.py:13-74), the
-factorisation of the N <= max_cholesky_size dispatch branch.  float32 HIP tensors of at most 1024 rows go to the
-native batched kernels (csrc/lo_chol.hip through functions/_cholesky.py); CPU tensors, float64 and larger matrices
-take ATen, with the two workarounds below."""
+factorisation of the N <= max_cholesky_size dispatch branch.  float32 and float64 HIP tensors of at most 1024 rows go to
+the native batched kernels (csrc/lo_chol.hip, csrc/lo_chol_f64.hip through functions/_cholesky.py); CPU tensors and
+larger matrices take ATen, with the two workarounds below."""
 from __future__ import annotations
 
 import warnings
@@ -38,7 +38,8 @@ def cholesky_solve(rhs, factor, upper=False):
     """torch.cholesky_solve.  Same stack, second hole: the BATCHED solve of ONE right-hand-side column against factors of
     more than 512 rows (float32 and float64; two or more columns, one matrix, and n <= 512 are fine --
     tools/probe/chol_solve_batched.py) ends in `unspecified launch failure`.  Such a column is solved twice side by side
-    and the first copy returned.  float32 HIP operands of at most 1024 rows take lo_cholesky_solve_f32 instead."""
+    and the first copy returned.  float32 and float64 HIP operands of at most 1024 rows take lo_cholesky_solve_f32 /
+    lo_cholesky_solve_f64 instead."""
     from ..functions._cholesky import chol_solve, native_ok
 
     if rhs.dim() >= 2 and native_ok(factor, rhs, solve=True):
