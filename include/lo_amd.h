@@ -95,6 +95,11 @@ extern "C" {
                                    * input, index i (D + 1) + a (data index slowest, a = 0 the value, a = 1 .. D the
                                    * derivative in coordinate a - 1); the n (D + 1) x n (D + 1) matrix is never stored    */
 #define LO_KERNEL_GRAD_MAX_DIM 16 /* input dimensions D the kind and lo_kernel_grad_* take (more: LO_ERR_UNSUPPORTED)      */
+#define LO_OP_KERNEL_TASK_DIAG 15 /* AddedDiag(TaskKernel(X, X), Diag(d)), the task-indexed ("Hadamard") multitask covariance:
+                                   * every observation carries its own task id t_i in the LAST column of X [B, N, D + 1]:
+                                   *   y[i] = sum_j theta_D g(r_ij) Bt[t_i, t_j] v[j] + d o v, r over columns 0 .. D - 1;
+                                   * tasks need not be observed at the same points; K never stored                        */
+#define LO_KERNEL_TASK_MAX_TASKS 8 /* tasks T (Bt is T x T) the kind and lo_kernel_task_* take (more: LO_ERR_UNSUPPORTED)   */
 
 struct lo_interp_desc;
 struct lo_mask_desc;
@@ -120,7 +125,8 @@ typedef struct lo_op_desc {
     const struct lo_interp_desc* interp; /* SKI (ABI 16): HOST pointer to the two interpolation matrices      */
     const struct lo_mask_desc* mask;     /* MASKED (ABI 21): HOST pointer to the base descriptor and the index list */
     const struct lo_grid_desc* grid;     /* TOEPLITZ_KRON (ABI 24): HOST pointer to the grid shape                  */
-    const float* task;                   /* KERNEL_KRON (ABI 29): DEVICE pointer to Bt [B, T, T], used exactly as given */
+    const float* task;                   /* KERNEL_KRON (ABI 29), KERNEL_TASK (ABI 34): DEVICE pointer to Bt [B, T, T], used
+                                          * exactly as given                                                           */
   };
   /* ABI 16 kinds.  TOEPLITZ: A0 = first column t [B, M] of the symmetric Toeplitz matrix, R = M = N.
    * SKI: A0 = t [B, M], R = M (grid size), n2 = J (interpolation points per row), `interp` as below.
@@ -173,7 +179,19 @@ typedef struct lo_op_desc {
    * a = 0, os2 t_a^2 else); the fp64 entry points, the resident / fused engines and the solve sessions return
    * LO_ERR_UNSUPPORTED; not a term kind of LO_OP_SUM, not a base kind of LO_OP_MASKED.
    * LO_ERR_BADARG: a null A0 / A1, R < 1, N % (R + 1) != 0, a family outside 0 .. 3; LO_ERR_UNSUPPORTED: D > 16, a
-   * family other than RBF.                                                                                             */
+   * family other than RBF.
+   * ABI 34 kind.  KERNEL_TASK: A0 = X [B, N, D + 1], the D coordinates and then the task id of the observation (an integer
+   * 0 .. T - 1 stored as a float), R = D (the coordinates: 1 <= D <= LO_KERNEL_MAX_DIM - 1), A1 = theta [B, D + 1] exactly
+   * as for KERNEL, n2 = one family code LO_KERNEL_*, nterms = T in 1 .. LO_KERNEL_TASK_MAX_TASKS, `task` = Bt [B, T, T] on
+   * the DEVICE (same layout again, no new member), used as given, symmetric or not:
+   *   K_ij = theta[D] g(r_ij) Bt[t_i, t_j],  r_ij^2 = sum_{k < D} (theta[k] (x_i[k] - x_j[k]))^2
+   * An id is rounded to the nearest integer and clamped into [0, T - 1] (NaN reads as 0): no id indexes outside Bt; ids
+   * outside the range are the caller's error.  Lowered for lo_matvec_f32, the streaming CG, Lanczos, fp32 MINRES and the
+   * fp32 pivoted Cholesky (diagonal theta[D] Bt[t_i, t_i], row of pivot p: row[j] = (theta[D] g(r_pj)) Bt[t_p, t_j]); the
+   * fp64 entry points, the resident / fused engines and the solve sessions return LO_ERR_UNSUPPORTED; not a term kind of
+   * LO_OP_SUM, not a base kind of LO_OP_MASKED.
+   * LO_ERR_BADARG: a null A0 / A1 / task, R < 1, a family outside 0 .. 3, T < 1; LO_ERR_UNSUPPORTED: R + 1 >
+   * LO_KERNEL_MAX_DIM, T > LO_KERNEL_TASK_MAX_TASKS.                                                                     */
 } lo_op_desc;
 
 /* The grid shape of an LO_OP_TOEPLITZ_KRON_DIAG descriptor (host struct). */
@@ -1047,6 +1065,39 @@ size_t lo_kernel_grad_bilinear_workspace_bytes(int64_t B, int64_t M, int64_t N, 
 int lo_kernel_grad_bilinear_f32(const float* x1, const float* x2, const float* theta, int32_t family, int64_t B, int64_t M,
                                 int64_t N, int64_t D, const float* U, const float* V, int64_t t, float* g_theta, void* ws,
                                 size_t ws_bytes, void* stream);
+
+/* ---- matrix-free task-indexed multitask operator (ABI 34; csrc/lo_kernel_task.hip) --------------------------------------
+ * K(x1, x2)_ij = theta[D] g(r_ij) Bt[t_i, t_j] for x1 [B, M, D + 1], x2 [B, N, D + 1]: columns 0 .. D - 1 the coordinates,
+ * column D the task id (rounded to nearest, clamped into [0, T - 1]); theta [B, D + 1] and `family` as for
+ * lo_kernel_mv_f32, task = Bt [B, T, T] (not required symmetric).  D counts the COORDINATES; rectangular x1 != x2 is the
+ * prediction case.  The sweeps are those of lo_kernel_mv_f32 / lo_kernel_bilinear_f32 / lo_kernel_points_grad_f32 (256
+ * rows per workgroup, x2 scaled while staged in LDS tiles of 128 together with its task ids, r^2 by direct differences,
+ * a tile's sums on their own and then added to the running ones, the column split of few-row shapes with an ascending
+ * reduce); Bt sits in LDS transposed and a pair reads one word of it.  Fixed-order sums, no atomics: two calls give
+ * equal bits.
+ *   lo_kernel_task_mv_f32           y [B, M, c] = K(x1, x2) v (+ d o v when M == N), v [B, N, c], d per diag_mode; the kind
+ *                                   LO_OP_KERNEL_TASK_DIAG with x1 = x2
+ *   lo_kernel_task_bilinear_f32     for W_ij = sum_s U[i, s] V[j, s], U [B, M, t], V [B, N, t]: g_theta [B, D + 1] =
+ *                                   d / d theta of sum_ij W_ij K_ij in the meaning lo_kernel_bilinear_f32 gives it, and
+ *                                   g_task [B, T, T], g_task[a, b] = theta[D] sum_{i: t_i = a} sum_{j: t_j = b} W_ij g(r_ij)
+ *                                   = d / d Bt[a, b] (not symmetrised; exact zeros for a task without a point)
+ *   lo_kernel_task_points_grad_f32  g_x1 [B, M, D + 1] = d / d x1 of the same sum, the task column written as 0.  The x2
+ *                                   side is the same call with x1 / x2 and U / V swapped and Bt transposed by the caller
+ * LO_ERR_BADARG: a null pointer, a non-positive size, family outside 0 .. 3, T < 1, an unknown diag_mode or (M == N) one
+ * without d; LO_ERR_UNSUPPORTED: D + 1 > LO_KERNEL_MAX_DIM, T > LO_KERNEL_TASK_MAX_TASKS; LO_ERR_WORKSPACE before any
+ * launch.  The sizers return 0 for arguments the call would refuse.                                                    */
+size_t lo_kernel_task_mv_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t D, int64_t T, int64_t c);
+int lo_kernel_task_mv_f32(const float* x1, const float* x2, const float* theta, const float* task, int32_t family,
+                          int64_t B, int64_t M, int64_t N, int64_t D, int64_t T, const float* v, int64_t c, const float* d,
+                          int32_t diag_mode, float* y, void* ws, size_t ws_bytes, void* stream);
+size_t lo_kernel_task_bilinear_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t D, int64_t T, int64_t t);
+int lo_kernel_task_bilinear_f32(const float* x1, const float* x2, const float* theta, const float* task, int32_t family,
+                                int64_t B, int64_t M, int64_t N, int64_t D, int64_t T, const float* U, const float* V,
+                                int64_t t, float* g_theta, float* g_task, void* ws, size_t ws_bytes, void* stream);
+size_t lo_kernel_task_points_grad_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t D, int64_t T, int64_t t);
+int lo_kernel_task_points_grad_f32(const float* x1, const float* x2, const float* theta, const float* task, int32_t family,
+                                   int64_t B, int64_t M, int64_t N, int64_t D, int64_t T, const float* U, const float* V,
+                                   int64_t t, float* g_x1, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- exact small-N path: batched Cholesky and triangular solves (ABI 18; csrc/lo_chol.hip) -------------------------
  * fp32, contiguous row-major, N <= 1024 (larger: LO_ERR_UNSUPPORTED), stream-ordered; fixed-order sums, no atomics: a

@@ -37,9 +37,11 @@ LO_OP_KERNEL_KRON_DIAG = 13
 LO_KERNEL_KRON_MAX_TASKS = 8
 LO_OP_KERNEL_GRAD_DIAG = 14
 LO_KERNEL_GRAD_MAX_DIM = 16
+LO_OP_KERNEL_TASK_DIAG = 15
+LO_KERNEL_TASK_MAX_TASKS = 8
 LO_DIAG_NONE, LO_DIAG_FULL, LO_DIAG_CONST = 0, 1, 2
 LO_BLOCK_DIAG, LO_BLOCK_INTERLEAVED, LO_BLOCK_SUM = 0, 1, 2
-ABI_VERSION = 33
+ABI_VERSION = 34
 
 LO_ERR_UNSUPPORTED = -4
 LO_FUSED_OK, LO_FUSED_EARLY_STOP, LO_FUSED_CONTINUE, LO_FUSED_TIMEOUT = 0, 1, 2, 3
@@ -298,6 +300,12 @@ _PROTOTYPES = {
     "lo_kernel_grad_mv_f32": (ci, [vp, vp, vp, i32, i64, i64, i64, i64, vp, i64, vp, i32, vp, vp, sz, vp]),
     "lo_kernel_grad_bilinear_workspace_bytes": (sz, [i64, i64, i64, i64, i64]),
     "lo_kernel_grad_bilinear_f32": (ci, [vp, vp, vp, i32, i64, i64, i64, i64, vp, vp, i64, vp, vp, sz, vp]),
+    "lo_kernel_task_mv_workspace_bytes": (sz, [i64, i64, i64, i64, i64, i64]),
+    "lo_kernel_task_mv_f32": (ci, [vp, vp, vp, vp, i32, i64, i64, i64, i64, i64, vp, i64, vp, i32, vp, vp, sz, vp]),
+    "lo_kernel_task_bilinear_workspace_bytes": (sz, [i64, i64, i64, i64, i64, i64]),
+    "lo_kernel_task_bilinear_f32": (ci, [vp, vp, vp, vp, i32, i64, i64, i64, i64, i64, vp, vp, i64, vp, vp, vp, sz, vp]),
+    "lo_kernel_task_points_grad_workspace_bytes": (sz, [i64, i64, i64, i64, i64, i64]),
+    "lo_kernel_task_points_grad_f32": (ci, [vp, vp, vp, vp, i32, i64, i64, i64, i64, i64, vp, vp, i64, vp, vp, sz, vp]),
     "lo_cholesky_workspace_bytes": (sz, [i64, i64]),
     "lo_cholesky_f32": (ci, [vp, vp, vp, vp, i64, i64, vp, sz, vp]),
     "lo_tri_solve_f32": (ci, [vp, vp, vp, vp, i64, i64, i64, i32, i32, vp]),

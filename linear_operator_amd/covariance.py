@@ -19,10 +19,19 @@ convention `f(x1, x2, lengthscale, outputscale)` (the `covar_func` of the refere
                   K[a,0] = -os^2 t_a u_a e   K[a,b] = os^2 t_a t_b (delta_ab - u_a u_b) e
               (pass num_outputs_per_input=(D + 1, D + 1) to the operator)
 
+    *_task    rbf_task, matern12_task, matern32_task, matern52_task: the task-indexed ("Hadamard") multitask kernel,
+              `f(x1, x2, lengthscale, outputscale, task_covar)`.  x [..., N, D + 1]: columns 0 .. D - 1 the coordinates,
+              column D the task id of the observation, an integer 0 .. T - 1 stored as a float; lengthscale [..., 1, D]
+              or [..., 1, 1] over the coordinates; task_covar [..., T, T]:
+                  k(x1_i, x2_j) = outputscale^2 g(r_ij) task_covar[t_i, t_j]
+              One output per input; the gradient with respect to the task column is zero, as autograd gives it.
+
 r^2 is the sum of squared direct differences of the scaled points (no |a|^2 + |b|^2 - 2 a.b, which cancels for near
 points).  Each function carries `native_family`, the LO_KERNEL_* code under which csrc/lo_kernel_op.hip evaluates the
 same formula tile by tile; on that path the [..., M, N] matrix these functions return is never formed.  rbf_grad
 carries `native_outputs = "grad"` besides: csrc/lo_kernel_grad.hip forms its blocks pair by pair.
+The *_task functions carry the base family's code and `native_outputs = "task"`: csrc/lo_kernel_task.hip stages the ids
+with the points and reads one word of task_covar per pair.
 """
 from __future__ import annotations
 
@@ -86,6 +95,32 @@ def rbf_grad(x1: Tensor, x2: Tensor, lengthscale: Tensor, outputscale: Tensor) -
     return K.transpose(-3, -2).reshape(*K.shape[:-4], M * (D + 1), N * (D + 1))
 
 
+def _task_gather(x1: Tensor, x2: Tensor, task_covar: Tensor) -> Tensor:
+    """task_covar[t_i, t_j] [..., M, N] for the ids in the last columns of x1 and x2."""
+    t1, t2 = x1[..., -1].long(), x2[..., -1].long()
+    T = task_covar.shape[-1]
+    batch = torch.broadcast_shapes(t1.shape[:-1], t2.shape[:-1], task_covar.shape[:-2])
+    M, N = t1.shape[-1], t2.shape[-1]
+    rows = task_covar.expand(*batch, T, T).gather(-2, t1.expand(*batch, M).unsqueeze(-1).expand(*batch, M, T))
+    return rows.gather(-1, t2.expand(*batch, N).unsqueeze(-2).expand(*batch, M, N))
+
+
+def rbf_task(x1: Tensor, x2: Tensor, lengthscale: Tensor, outputscale: Tensor, task_covar: Tensor) -> Tensor:
+    return rbf(x1[..., :-1], x2[..., :-1], lengthscale, outputscale) * _task_gather(x1, x2, task_covar)
+
+
+def matern12_task(x1: Tensor, x2: Tensor, lengthscale: Tensor, outputscale: Tensor, task_covar: Tensor) -> Tensor:
+    return matern12(x1[..., :-1], x2[..., :-1], lengthscale, outputscale) * _task_gather(x1, x2, task_covar)
+
+
+def matern32_task(x1: Tensor, x2: Tensor, lengthscale: Tensor, outputscale: Tensor, task_covar: Tensor) -> Tensor:
+    return matern32(x1[..., :-1], x2[..., :-1], lengthscale, outputscale) * _task_gather(x1, x2, task_covar)
+
+
+def matern52_task(x1: Tensor, x2: Tensor, lengthscale: Tensor, outputscale: Tensor, task_covar: Tensor) -> Tensor:
+    return matern52(x1[..., :-1], x2[..., :-1], lengthscale, outputscale) * _task_gather(x1, x2, task_covar)
+
+
 rbf.native_family = _hip.LO_KERNEL_RBF
 rbf_grad.native_family = _hip.LO_KERNEL_RBF
 rbf_grad.native_outputs = "grad"
@@ -93,8 +128,17 @@ matern12.native_family = _hip.LO_KERNEL_MATERN12
 matern32.native_family = _hip.LO_KERNEL_MATERN32
 matern52.native_family = _hip.LO_KERNEL_MATERN52
 
+for _f, _base in ((rbf_task, rbf), (matern12_task, matern12), (matern32_task, matern32), (matern52_task, matern52)):
+    _f.native_family = _base.native_family
+    _f.native_outputs = "task"
+
 FAMILIES = {"rbf": rbf, "matern12": matern12, "matern32": matern32, "matern52": matern52}
 # gradient kernels (D + 1 outputs per input): kept apart, FAMILIES holds the one-output families only
 GRAD_FAMILIES = {"rbf_grad": rbf_grad}
 
-__all__ = ["rbf", "matern12", "matern32", "matern52", "rbf_grad", "scaled_sq_dist", "FAMILIES", "GRAD_FAMILIES"]
+# task-indexed multitask kernels (one more parameter, task_covar): kept apart as well
+TASK_FAMILIES = {"rbf_task": rbf_task, "matern12_task": matern12_task, "matern32_task": matern32_task,
+                 "matern52_task": matern52_task}
+
+__all__ = ["rbf", "matern12", "matern32", "matern52", "rbf_grad", "rbf_task", "matern12_task", "matern32_task",
+           "matern52_task", "scaled_sq_dist", "FAMILIES", "GRAD_FAMILIES", "TASK_FAMILIES"]

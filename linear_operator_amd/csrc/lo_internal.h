@@ -267,6 +267,15 @@ int kernel_grad_matvec_run(const MatvecPlan* pl, const float* v, float* y, const
 // LO_OK, or why the descriptor of that kind is refused (the pivoted Cholesky validates it without a plan)
 int kernel_grad_desc_check(const lo_op_desc* op);
 
+// ---- matrix-free task-indexed multitask operator (lo_kernel_task.hip): LO_OP_KERNEL_TASK_DIAG ----------------------------
+struct KernelTaskPlan {
+  float* part;  // [js, B, N, c] partial products when the columns j of a member are split over js workgroups, else nullptr
+};
+int kernel_task_plan(MatvecPlan* pl, Arena* ar, hipStream_t st);
+int kernel_task_matvec_run(const MatvecPlan* pl, const float* v, float* y, const int* stop, hipStream_t st);
+// LO_OK, or why the descriptor of that kind is refused (the pivoted Cholesky validates it without a plan)
+int kernel_task_desc_check(const lo_op_desc* op);
+
 // ---- masked operator (lo_masked.hip) ---------------------------------------------------------------------------------
 struct MaskedPlan {      // (the base's plan is MatvecPlan::sub[0])
   const int64_t* idx;    // [M]
@@ -304,6 +313,7 @@ struct MatvecPlan {
     KernelOpPlan ko;
     KernelKronPlan kk;
     KernelGradPlan kg;
+    KernelTaskPlan kt;
     MaskedPlan mask;
   };
 };

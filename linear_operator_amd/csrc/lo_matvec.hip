@@ -154,6 +154,7 @@ int matvec_plan_init(MatvecPlan* pl, const lo_op_desc* op, lo_matvec_cb cb, void
     case LO_OP_KERNEL_SUM_DIAG: rc = kernel_sum_plan(pl, ar, st); break;
     case LO_OP_KERNEL_KRON_DIAG: rc = kernel_kron_plan(pl, ar, st); break;
     case LO_OP_KERNEL_GRAD_DIAG: rc = kernel_grad_plan(pl, ar, st); break;
+    case LO_OP_KERNEL_TASK_DIAG: rc = kernel_task_plan(pl, ar, st); break;
     case LO_OP_MASKED: rc = masked_plan(pl, ar, st); break;
     case LO_OP_CALLBACK: rc = cb ? LO_OK : LO_ERR_BADARG; break;
     case LO_OP_SUM: rc = sum_plan(pl, ar, st); break;
@@ -200,6 +201,8 @@ int matvec_run(const MatvecPlan* pl, const float* v, float* y, float* dot_part, 
       rc = kernel_kron_matvec_run(pl, v, y, stop, st); break;
     case LO_OP_KERNEL_GRAD_DIAG:  // the RBF gradient kernel's blocks formed pair by pair, D + 1 outputs per point (lo_kernel_grad.hip)
       rc = kernel_grad_matvec_run(pl, v, y, stop, st); break;
+    case LO_OP_KERNEL_TASK_DIAG:  // K_ij = os2 g(r_ij) Bt[t_i, t_j], the task ids staged with the points (lo_kernel_task.hip)
+      rc = kernel_task_matvec_run(pl, v, y, stop, st); break;
     case LO_OP_MASKED:  // S (base) S^T v + d o v: expand, the base's product (or the selected rows of a dense base), gather
       rc = masked_matvec_run(pl, v, y, stop, st); break;
     case LO_OP_CALLBACK: rc = pl->cb(pl->cb_user, v, y, op.B, op.N, pl->c, (void*)st) ? LO_ERR_LAUNCH : LO_OK; break;
@@ -229,7 +232,7 @@ using namespace lo;
 
 extern "C" {
 
-int lo_abi_version(void) { return 33; }
+int lo_abi_version(void) { return 34; }
 const char* lo_target_arch(void) { return "gfx950"; }
 
 size_t lo_matvec_workspace_bytes(const lo_op_desc* op, int64_t c) {

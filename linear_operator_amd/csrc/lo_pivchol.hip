@@ -35,6 +35,7 @@
 
 #include "lo_internal.h"
 #include "lo_kernel_fn.h"
+#include "lo_kernel_task.h"
 
 namespace lo {
 
@@ -140,6 +141,10 @@ __device__ __forceinline__ T src_diag(const PcDevT<T>& d, const lo_op_desc& op, 
   } else if (op.kind == LO_OP_KERNEL_KRON_DIAG) {  // row i = (p, tau): os2 g(0) Bt[tau, tau] = os2 Bt[tau, tau]
     const int nt = op.nterms, tau = i % nt;
     return (T)(op.A1[(size_t)b * (op.R + 1) + op.R] * op.task[((size_t)b * nt + tau) * nt + tau]);
+  } else if (op.kind == LO_OP_KERNEL_TASK_DIAG) {  // os2 g(0) Bt[t_i, t_i], t_i the (clamped) id in the points' last column
+    const int D = (int)op.R, nt = op.nterms;
+    const int ti = tk_task_id(op.A0[((size_t)b * d.N + i) * (D + 1) + D], nt);
+    return (T)(op.A1[(size_t)b * (D + 1) + D] * op.task[((size_t)b * nt + ti) * nt + ti]);
   } else if (op.kind == LO_OP_KERNEL_GRAD_DIAG) {  // row i = (p, a): os2 for the value, os2 t_a^2 for a derivative
     const int D = (int)op.R, a = i % (D + 1);
     const float* th = op.A1 + (size_t)b * (D + 1);
@@ -506,6 +511,18 @@ __global__ __launch_bounds__(kThreads) void k_pc_update(PcDevT<T> d, int m) {
             r2 = r2 + df * df;
           }
           tv = (T)((th[D] * kf_g_rt((int)tm.n2, r2)) * tm.task[((size_t)b * nt + tau) * nt + ss]);
+        } else if (tm.kind == LO_OP_KERNEL_TASK_DIAG) {  // pivot p, entry j: (os2 g(r_pj)) Bt[t_p, t_j]
+          const int D = (int)tm.R, nt = tm.nterms;
+          const float* th = tm.A1 + (size_t)b * (D + 1);
+          const float* xp = tm.A0 + ((size_t)b * N + pim) * (D + 1);
+          const float* xi = tm.A0 + ((size_t)b * N + i) * (D + 1);
+          float r2 = 0.0f;
+          for (int k = 0; k < D; ++k) {
+            const float df = xp[k] * th[k] - xi[k] * th[k];
+            r2 = r2 + df * df;
+          }
+          const int tp = tk_task_id(xp[D], nt), tj = tk_task_id(xi[D], nt);
+          tv = (T)((th[D] * kf_g_rt((int)tm.n2, r2)) * tm.task[((size_t)b * nt + tp) * nt + tj]);
         } else if (tm.kind == LO_OP_KERNEL_GRAD_DIAG) {  // pivot (p, al), entry (j, be): the block formula of lo_amd.h
           const int D = (int)tm.R, nt = D + 1;
           const int n = N / nt, pp = pim / nt, al = pim - pp * nt, jj = i / nt, be = i - jj * nt;
@@ -775,6 +792,8 @@ static int pc_check_desc(const lo_op_desc* op, bool fp32_kinds = true) {
     if (const int rc = kernel_kron_desc_check(op)) return rc;
   } else if (op->kind == LO_OP_KERNEL_GRAD_DIAG) {
     if (const int rc = kernel_grad_desc_check(op)) return rc;
+  } else if (op->kind == LO_OP_KERNEL_TASK_DIAG) {
+    if (const int rc = kernel_task_desc_check(op)) return rc;
   } else if (op->kind == LO_OP_SKI_DIAG) {
     const lo_interp_desc* w = op->interp;
     if (!op->A0 || op->R < 1 || op->n2 < 1 || !w || !w->left_idx || !w->left_vals || !w->right_idx || !w->right_vals)
@@ -872,7 +891,7 @@ int lo_pivoted_cholesky_f64(const lo_op_desc* op, int32_t max_rank, double error
   if (!op || !L_rows || !perm || !rank_out || !ws || max_rank < 1) return LO_ERR_BADARG;
   if (op->kind == LO_OP_SKI_DIAG || op->kind == LO_OP_TOEPLITZ_DIAG || op->kind == LO_OP_HADAMARD_DIAG ||
       op->kind == LO_OP_SKI_GRID_DIAG || op->kind == LO_OP_TOEPLITZ_KRON_DIAG || kernel_term_kind(op->kind) ||
-      op->kind == LO_OP_KERNEL_KRON_DIAG || op->kind == LO_OP_KERNEL_GRAD_DIAG)
+      op->kind == LO_OP_KERNEL_KRON_DIAG || op->kind == LO_OP_KERNEL_GRAD_DIAG || op->kind == LO_OP_KERNEL_TASK_DIAG)
     return LO_ERR_UNSUPPORTED;  // (fp32 kinds)
   if (const int rc = pc_check_desc(op, false)) return rc;
   return pc_stream_t<double>(op, nullptr, nullptr, nullptr, max_rank, error_tol, L_rows, perm, rank_out, ws, ws_bytes,

@@ -30,6 +30,7 @@ class OperatorDescriptor:
     # K2 [B,n2,n2] | G [B,N,q] (Hadamard: A0 = F [B,N,p]) | theta [B,D+1] (Kernel: A0 = X [B,N,D], R = D, n2 = family)
     # | theta [B,T,D+1] (KernelSum: A0 = X, R = D, n2 = the packed families, kernel_terms = T)
     # | theta [B,D+1] (KernelKron: A0 = X [B,n,D], R = D, n2 = family, kernel_terms = T, task = Bt, N = n T)
+    # | theta [B,D+1] (KernelTask: A0 = X [B,N,D+1] with the task id last, R = D, n2 = family, kernel_terms = T, task = Bt)
     A1: Optional[torch.Tensor] = None
     d: Optional[torch.Tensor] = None  # [B,N] (FULL) or [B] (CONST)
     diag_mode: int = _hip.LO_DIAG_NONE
@@ -47,9 +48,11 @@ class OperatorDescriptor:
     # sums of those) go to lo_matvec_f64 and the float64 solvers only, and c_struct() refuses to hand one to an entry
     # point that reads `float*`
     dtype: torch.dtype = torch.float32
-    # LO_OP_KERNEL_SUM_DIAG: T, the struct's `nterms` (the kind has no `terms`); LO_OP_KERNEL_KRON_DIAG: the tasks T
+    # LO_OP_KERNEL_SUM_DIAG: T, the struct's `nterms` (the kind has no `terms`); LO_OP_KERNEL_KRON_DIAG,
+    # LO_OP_KERNEL_TASK_DIAG: the tasks T
     kernel_terms: int = 0
-    task: Optional[torch.Tensor] = None  # LO_OP_KERNEL_KRON_DIAG: Bt [B, T, T], the union slot `task` (a DEVICE pointer)
+    # LO_OP_KERNEL_KRON_DIAG, LO_OP_KERNEL_TASK_DIAG: Bt [B, T, T], the union slot `task` (a DEVICE pointer)
+    task: Optional[torch.Tensor] = None
 
     @property
     def device(self):
@@ -804,6 +807,93 @@ def kernel_grad_bilinear(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor
     g = torch.empty(B, D + 1, dtype=torch.float32, device=U.device)
     _launch("lo_kernel_grad_bilinear_f32", U.device, x1, x2, theta, int(family), B, M, N, D, U, V, t, g,
             ws_bytes=lib.lo_kernel_grad_bilinear_workspace_bytes(B, M, N, D, t))
+    return g
+
+
+def kernel_task_diag_descriptor(X: torch.Tensor, theta: torch.Tensor, family: int, task: torch.Tensor,
+                                d: Optional[torch.Tensor] = None, const_diag: bool = False):
+    """AddedDiag(TaskKernel(X, X, family), Diag(d)) (or the operator alone), the task-indexed multitask covariance
+    K_ij = os2 g(r_ij) Bt[t_i, t_j] formed on the fly (csrc/lo_kernel_task.hip).  X [*batch, N, D + 1]: D coordinates and
+    then the task id of the observation; theta [B, D + 1] from kernel_theta over the D coordinates, task = Bt
+    [*batch, T, T].  None when D + 1 exceeds LO_KERNEL_MAX_DIM or T exceeds LO_KERNEL_TASK_MAX_TASKS (the caller
+    evaluates covar_func)."""
+    _hip.require_hip(X, theta, task, d)
+    N, D = X.shape[-2], X.shape[-1] - 1
+    T = task.shape[-1]
+    if D + 1 > _hip.LO_KERNEL_MAX_DIM or D < 1 or not 1 <= T <= _hip.LO_KERNEL_TASK_MAX_TASKS:
+        return None
+    X3, Bt = _flat(X.detach(), 2), _flat(task.detach(), 2)
+    if theta.shape != (X3.shape[0], D + 1) or Bt.shape != (X3.shape[0], T, T):
+        raise RuntimeError(f"kernel_task_diag_descriptor: theta {tuple(theta.shape)}, task {tuple(task.shape)} for X "
+                           f"{tuple(X.shape)}")
+    return _with_diag(OperatorDescriptor(_hip.LO_OP_KERNEL_TASK_DIAG, X3.shape[0], N, A0=X3, A1=theta.contiguous(), R=D,
+                                         n2=int(family), batch_shape=X.shape[:-2], kernel_terms=T, task=Bt), d, const_diag)
+
+
+def _kernel_task_args(what, x1, x2, theta, task, W):
+    x1, x2, theta, task, W = (t.contiguous() for t in (x1, x2, theta, task, W))
+    _hip.require_hip(x1, x2, theta, task, W)
+    B, M, D = x1.shape[0], x1.shape[1], x1.shape[2] - 1
+    T = task.shape[-1]
+    N = W.shape[-2]
+    if (x1.dim() != 3 or x2.shape != (B, N, D + 1) or theta.shape != (B, D + 1) or task.shape != (B, T, T)
+            or W.dim() != 3 or W.shape[0] != B):
+        raise RuntimeError(f"{what}: x1 {tuple(x1.shape)}, x2 {tuple(x2.shape)}, theta {tuple(theta.shape)}, "
+                           f"task {tuple(task.shape)}, right operand {tuple(W.shape)}")
+    return x1, x2, theta, task, W, (B, M, N, D, T)
+
+
+def kernel_task_mv(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, task: torch.Tensor, family: int,
+                   v: torch.Tensor, d: Optional[torch.Tensor] = None, const_diag: bool = False) -> torch.Tensor:
+    """lo_kernel_task_mv_f32: y [B, M, c] = K(x1, x2) v (+ d o v when M == N and d is given), K_ij = os2 g(r_ij)
+    Bt[t_i, t_j]; x1 [B, M, D + 1], x2 [B, N, D + 1] with the task id in the last column, theta [B, D + 1], task = Bt
+    [B, T, T] (used as given, symmetric or not), v [B, N, c].  A shape the kernel does not take raises."""
+    lib = _hip.load()
+    x1, x2, theta, task, v, (B, M, N, D, T) = _kernel_task_args("kernel_task_mv", x1, x2, theta, task, v)
+    _hip.require_hip(d)
+    c = v.shape[-1]
+    mode = _hip.LO_DIAG_NONE
+    if d is not None:
+        d, mode, _ = _diag_operand(d, B, N, const_diag)
+    y = torch.empty(B, M, c, dtype=torch.float32, device=v.device)
+    _launch("lo_kernel_task_mv_f32", v.device, x1, x2, theta, task, int(family), B, M, N, D, T, v, c, d, mode, y,
+            ws_bytes=lib.lo_kernel_task_mv_workspace_bytes(B, M, N, D, T, c))
+    return y
+
+
+def kernel_task_bilinear(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, task: torch.Tensor, family: int,
+                         U: torch.Tensor, V: torch.Tensor):
+    """lo_kernel_task_bilinear_f32: (g_theta [B, D + 1], g_task [B, T, T]), the derivatives of sum_s u_s^T K(x1, x2) v_s
+    with respect to theta (the inverse lengthscales, then outputscale^2) and to Bt (entry by entry, not symmetrised).
+    U [B, M, t], V [B, N, t]."""
+    lib = _hip.load()
+    x1, x2, theta, task, V, (B, M, N, D, T) = _kernel_task_args("kernel_task_bilinear", x1, x2, theta, task, V)
+    U = U.contiguous()
+    _hip.require_hip(U)
+    t = V.shape[-1]
+    if U.shape != (B, M, t):
+        raise RuntimeError(f"kernel_task_bilinear: U {tuple(U.shape)} for x1 {tuple(x1.shape)}, V {tuple(V.shape)}")
+    g = torch.empty(B, D + 1, dtype=torch.float32, device=U.device)
+    gB = torch.empty(B, T, T, dtype=torch.float32, device=U.device)
+    _launch("lo_kernel_task_bilinear_f32", U.device, x1, x2, theta, task, int(family), B, M, N, D, T, U, V, t, g, gB,
+            ws_bytes=lib.lo_kernel_task_bilinear_workspace_bytes(B, M, N, D, T, t))
+    return g, gB
+
+
+def kernel_task_points_grad(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, task: torch.Tensor, family: int,
+                            U: torch.Tensor, V: torch.Tensor) -> torch.Tensor:
+    """lo_kernel_task_points_grad_f32: g_x1 [B, M, D + 1], the derivative of sum_s u_s^T K(x1, x2) v_s with respect to
+    x1, x2 held fixed; the task column is 0.  The x2 side is kernel_task_points_grad(x2, x1, theta, task.mT, family, V, U)."""
+    lib = _hip.load()
+    x1, x2, theta, task, V, (B, M, N, D, T) = _kernel_task_args("kernel_task_points_grad", x1, x2, theta, task, V)
+    U = U.contiguous()
+    _hip.require_hip(U)
+    t = V.shape[-1]
+    if U.shape != (B, M, t):
+        raise RuntimeError(f"kernel_task_points_grad: U {tuple(U.shape)} for x1 {tuple(x1.shape)}, V {tuple(V.shape)}")
+    g = torch.empty(B, M, D + 1, dtype=torch.float32, device=U.device)
+    _launch("lo_kernel_task_points_grad_f32", U.device, x1, x2, theta, task, int(family), B, M, N, D, T, U, V, t, g,
+            ws_bytes=lib.lo_kernel_task_points_grad_workspace_bytes(B, M, N, D, T, t))
     return g
 
 

@@ -25,6 +25,21 @@ answering "more than one output per input", so every caller that assumes one out
   _bilinear_derivative  lo_kernel_grad_bilinear_f32 when neither points tensor asks for a gradient (else the general path)
   _getitem              slices of whole points rebuild the operator over the sliced points; anything else indexes densely
 
+Task-indexed multitask kernels.  `covariance.rbf_task` .. `matern52_task` (`native_outputs == "task"`): the points carry
+the task id of the observation in their last column, the parameters are `lengthscale`, `outputscale` and `task_covar`
+[*b, T, T], T <= LO_KERNEL_TASK_MAX_TASKS, and K_ij = outputscale^2 g(r_ij) task_covar[t_i, t_j].  The gate is
+`_native_task_refusal`; `_native_refusal` keeps answering "parameters other than lengthscale and outputscale", so the
+Sum and Kronecker fusion gates never take such an operator.  Inside it:
+
+  _matmul / _t_matmul   lo_kernel_task_mv_f32 (csrc/lo_kernel_task.hip), always, rectangular included: its purpose is memory
+  _kernel_descriptor    x1 and x2 the same points: the kind LO_OP_KERNEL_TASK_DIAG
+  _diagonal             outputscale^2 task_covar[t_i, t_i] by a gather, no covar_func
+  _bilinear_derivative  lengthscale, outputscale and task_covar from lo_kernel_task_bilinear_f32, the points' gradients
+                        from lo_kernel_task_points_grad_f32 (the task column's gradient is 0)
+
+The operator treats task_covar as symmetric: `_transpose_nonbatch` swaps the points and keeps the parameters, as it does
+for any covar_func.  Ids outside [0, T) are the caller's error: the gate does not synchronise to look, the kernels clamp.
+
 Float64.  The four one-output families with every tensor float64 on the device have a gate of their own,
 `_native_f64_refusal` (the conditions of `_native_refusal` with float64 in place of float32); `_native_refusal` keeps
 answering "not float32", so the fp32 fusion gates of the Sum and Kronecker operators never see such an operator.  Inside it,
@@ -179,6 +194,43 @@ class KernelLinearOperator(LinearOperator):
     def _is_native_grad(self) -> bool:
         return self._native_grad_refusal() is None
 
+    def _native_task_refusal(self, check_device: bool = True) -> Optional[str]:
+        """The gate of the task-indexed multitask kernels (csrc/lo_kernel_task.hip): None when the native kernels take
+        this operator, else the reason they do not.  `check_device=False` leaves out the device condition."""
+        from .. import _hip
+
+        if getattr(self.covar_func, "native_outputs", None) != "task":
+            return "covar_func has no native_outputs == 'task'"
+        if getattr(self.covar_func, "native_family", None) is None:
+            return "covar_func has no native_family"
+        if self.num_outputs_per_input != (1, 1):
+            return "more than one output per input"
+        if self.nontensor_params or set(self.tensor_params) != {"lengthscale", "outputscale", "task_covar"}:
+            return "parameters other than lengthscale, outputscale and task_covar"
+        D = self.x1.shape[-1] - 1
+        if D < 1 or self.x2.shape[-1] != D + 1 or D + 1 > _hip.LO_KERNEL_MAX_DIM:
+            return f"D = {D} outside 1 .. LO_KERNEL_MAX_DIM - 1"
+        ls, os_, Bt = (self.tensor_params[k] for k in ("lengthscale", "outputscale", "task_covar"))
+        batch = self.batch_broadcast_shape
+        if self.num_nonbatch_dimensions["lengthscale"] != 2 or ls.shape not in ((*batch, 1, D), (*batch, 1, 1)):
+            return f"lengthscale of shape {tuple(ls.shape)}"
+        if self.num_nonbatch_dimensions["outputscale"] != 0 or os_.shape != batch:
+            return f"outputscale of shape {tuple(os_.shape)}"
+        T = Bt.shape[-1]
+        if self.num_nonbatch_dimensions["task_covar"] != 2 or Bt.shape != (*batch, T, T) or T < 1:
+            return f"task_covar of shape {tuple(Bt.shape)}"
+        if T > _hip.LO_KERNEL_TASK_MAX_TASKS:
+            return f"T = {T} beyond LO_KERNEL_TASK_MAX_TASKS"
+        tensors = (self.x1, self.x2, ls, os_, Bt)
+        if any(t.dtype != torch.float32 for t in tensors):
+            return "not float32"
+        if check_device and not all(t.is_cuda for t in tensors):
+            return "not on the device"
+        return None
+
+    def _is_native_task(self) -> bool:
+        return self._native_task_refusal() is None
+
     def _native_f64_refusal(self, check_device: bool = True) -> Optional[str]:
         """The gate of the float64 kernels (csrc/lo_kernel_op_f64.hip): None when they take this operator, else the
         reason they do not -- the conditions of `_native_refusal` with every tensor float64.  `check_device=False`
@@ -219,6 +271,16 @@ class KernelLinearOperator(LinearOperator):
         return K.kernel_theta(self.tensor_params["lengthscale"], self.tensor_params["outputscale"], batch,
                               self.x1.shape[-1], dtype=dtype)
 
+    def _task_operands(self, batch):
+        """Inside the task gate: theta [B, D + 1] over the D coordinates and task_covar as Bt [B, T, T], for `batch`."""
+        from .. import kernels as K
+
+        Bt = self.tensor_params["task_covar"].detach()
+        T = Bt.shape[-1]
+        theta = K.kernel_theta(self.tensor_params["lengthscale"], self.tensor_params["outputscale"], batch,
+                               self.x1.shape[-1] - 1)
+        return theta, Bt.expand(*batch, T, T).reshape(-1, T, T)
+
     def _kernel_descriptor_f64(self, batch_shape=None):
         """The float64 LO_OP_KERNEL_DIAG descriptor inside the float64 gate when x1 and x2 are one tensor, else None."""
         if not (self._is_native_f64() and self._same_points()):
@@ -232,14 +294,17 @@ class KernelLinearOperator(LinearOperator):
                                         dtype=torch.float64)
 
     def _kernel_descriptor(self, batch_shape=None):
-        grad = self._is_native_grad()
-        if not ((grad or self._is_native()) and self._same_points()):
+        grad, task = self._is_native_grad(), self._is_native_task()
+        if not ((grad or task or self._is_native()) and self._same_points()):
             return None
         from .. import kernels as K
 
         bs = torch.Size(self.batch_shape if batch_shape is None else batch_shape)
         X = self.x1.detach()
         X = X if X.shape[:-2] == bs else X.expand(*bs, *X.shape[-2:])
+        if task:
+            theta, Bt = self._task_operands(bs)
+            return K.kernel_task_diag_descriptor(X, theta, self.covar_func.native_family, Bt.reshape(*bs, *Bt.shape[-2:]))
         build = K.kernel_grad_diag_descriptor if grad else K.kernel_diag_descriptor
         return build(X, self._theta(bs), self.covar_func.native_family)
 
@@ -277,6 +342,18 @@ class KernelLinearOperator(LinearOperator):
             y = K.kernel_grad_mv(x1, x2, self._theta(bs), self.covar_func.native_family,
                                  cols.detach().expand(*bs, N * (D + 1), c).reshape(-1, N * (D + 1), c))
             y = y.reshape(*bs, M * (D + 1), c)
+        elif cols.is_cuda and cols.dtype == torch.float32 and self._is_native_task():
+            from .. import kernels as K
+
+            M, DX = self.x1.shape[-2:]
+            N, c = cols.shape[-2:]
+            bs = torch.broadcast_shapes(self.batch_shape, cols.shape[:-2])
+            x1 = self.x1.detach().expand(*bs, M, DX).reshape(-1, M, DX)
+            x2 = x1 if self._same_points() else self.x2.detach().expand(*bs, N, DX).reshape(-1, N, DX)
+            theta, Bt = self._task_operands(bs)
+            y = K.kernel_task_mv(x1, x2, theta, Bt, self.covar_func.native_family,
+                                 cols.detach().expand(*bs, N, c).reshape(-1, N, c))
+            y = y.reshape(*bs, M, c)
         elif cols.is_cuda and ((cols.dtype == torch.float32 and self._is_native())
                                or (cols.dtype == torch.float64 and self._is_native_f64())):
             from .. import kernels as K
@@ -322,6 +399,12 @@ class KernelLinearOperator(LinearOperator):
                 and self._same_points()):
             # g(0) = 1 for every native family: the diagonal is outputscale^2, no kernel launch
             return self.tensor_params["outputscale"].square().unsqueeze(-1).expand(*self.batch_broadcast_shape, n)
+        if self._native_task_refusal(check_device=False) is None and self._same_points():
+            # g(0) = 1: outputscale^2 task_covar[t_i, t_i], the table's diagonal gathered at the ids; no covar_func
+            batch = self.batch_broadcast_shape
+            ids = self.x1[..., -1].long().expand(*batch, n)
+            own = self.tensor_params["task_covar"].diagonal(dim1=-2, dim2=-1).expand(*batch, -1).gather(-1, ids)
+            return self.tensor_params["outputscale"].square().unsqueeze(-1) * own
         if self._native_grad_refusal(check_device=False) is None and self._same_points():
             # the block of a point with itself is outputscale^2 diag(1, 1 / l_1^2, .., 1 / l_D^2): no launch, no covar_func
             D = self.x1.shape[-1]
@@ -398,6 +481,8 @@ class KernelLinearOperator(LinearOperator):
         if (left_vecs.is_cuda and left_vecs.dtype == torch.float64 and right_vecs.dtype == torch.float64
                 and self._is_native_f64()):
             return self._bilinear_derivative_native(left_vecs, right_vecs, names)
+        if left_vecs.is_cuda and left_vecs.dtype == torch.float32 and self._is_native_task():
+            return self._bilinear_derivative_task(left_vecs, right_vecs, names)
         if (left_vecs.is_cuda and left_vecs.dtype == torch.float32 and self._is_native_grad()
                 and not (self.x1.requires_grad or self.x2.requires_grad)):
             # (native gradients of the points are not built for this kind: such a call takes the general path whole)
@@ -414,6 +499,47 @@ class KernelLinearOperator(LinearOperator):
             loss = (left_vecs * (dense @ right_vecs)).sum()
             grads = list(torch.autograd.grad(loss, need, allow_unused=True))
         return tuple(grads.pop(0) if t.requires_grad else None for t in leaves)
+
+    def _theta_to_params(self, g: Tensor, theta: Tensor, D: int, bs, out: dict) -> None:
+        """d / d theta [B, D + 1] as the gradients of the lengthscale and outputscale tensors, where they ask for one."""
+        ls, os_ = self.tensor_params["lengthscale"], self.tensor_params["outputscale"]
+        if ls.requires_grad:  # theta_d = 1 / l_d: d / d l_d = -theta_d^2 d / d theta_d; a shared l sums over d
+            d_ls = (-(theta[:, :D] ** 2) * g[:, :D]).reshape(*bs, 1, D)
+            if ls.shape[-1] == 1 and D > 1:
+                d_ls = d_ls.sum(-1, keepdim=True)
+            out["lengthscale"] = d_ls.sum_to_size(ls.shape)
+        if os_.requires_grad:  # theta_D = os^2: d / d os = 2 os d / d theta_D
+            out["outputscale"] = (2.0 * torch.broadcast_to(os_.detach(), tuple(bs)) * g[:, D].reshape(tuple(bs))).sum_to_size(os_.shape)
+
+    def _bilinear_derivative_task(self, left_vecs: Tensor, right_vecs: Tensor, names):
+        """Inside the task gate: every gradient from the native kernels, nothing of size M N allocated."""
+        from .. import kernels as K
+
+        ls, os_, Bt = (self.tensor_params[k] for k in ("lengthscale", "outputscale", "task_covar"))
+        M, DX = self.x1.shape[-2:]
+        N, t = self.x2.shape[-2], right_vecs.shape[-1]
+        T = Bt.shape[-1]
+        bs = torch.broadcast_shapes(self.batch_shape, left_vecs.shape[:-2], right_vecs.shape[:-2])
+        out = {"x1": None, "x2": None, "lengthscale": None, "outputscale": None, "task_covar": None}
+        if not any(p.requires_grad for p in (self.x1, self.x2, ls, os_, Bt)):
+            return (None, None) + (None,) * len(names)
+        family = self.covar_func.native_family
+        x1 = self.x1.detach().expand(*bs, M, DX).reshape(-1, M, DX)
+        x2 = x1 if self._same_points() else self.x2.detach().expand(*bs, N, DX).reshape(-1, N, DX)
+        theta, task = self._task_operands(bs)
+        U = left_vecs.detach().expand(*bs, M, t).reshape(-1, M, t)
+        V = right_vecs.detach().expand(*bs, N, t).reshape(-1, N, t)
+        if ls.requires_grad or os_.requires_grad or Bt.requires_grad:
+            g, g_task = K.kernel_task_bilinear(x1, x2, theta, task, family, U, V)
+            self._theta_to_params(g, theta, DX - 1, bs, out)
+            if Bt.requires_grad:
+                out["task_covar"] = g_task.reshape(*bs, T, T).sum_to_size(Bt.shape)
+        # the x2 side is the x1 side of the transposed problem: x1 <-> x2, U <-> V, Bt transposed
+        if self.x1.requires_grad:
+            out["x1"] = K.kernel_task_points_grad(x1, x2, theta, task, family, U, V).reshape(*bs, M, DX).sum_to_size(self.x1.shape)
+        if self.x2.requires_grad:
+            out["x2"] = K.kernel_task_points_grad(x2, x1, theta, task.mT, family, V, U).reshape(*bs, N, DX).sum_to_size(self.x2.shape)
+        return (out["x1"], out["x2"]) + tuple(out[n] for n in names)
 
     def _bilinear_derivative_native(self, left_vecs: Tensor, right_vecs: Tensor, names, grad: bool = False):
         """grad: the gradient kernel (the vectors have D + 1 rows per point; the caller saw that no points tensor asks
@@ -437,13 +563,7 @@ class KernelLinearOperator(LinearOperator):
         if ls.requires_grad or os_.requires_grad:
             bilinear = K.kernel_grad_bilinear if grad else K.kernel_bilinear
             g = bilinear(x1, x2, theta, family, U, V)  # [B, D + 1], d / d theta
-            if ls.requires_grad:  # theta_d = 1 / l_d: d / d l_d = -theta_d^2 d / d theta_d; a shared l sums over d
-                d_ls = (-(theta[:, :D] ** 2) * g[:, :D]).reshape(*bs, 1, D)
-                if ls.shape[-1] == 1 and D > 1:
-                    d_ls = d_ls.sum(-1, keepdim=True)
-                out["lengthscale"] = d_ls.sum_to_size(ls.shape)
-            if os_.requires_grad:  # theta_D = os^2: d / d os = 2 os d / d theta_D
-                out["outputscale"] = (2.0 * torch.broadcast_to(os_.detach(), tuple(bs)) * g[:, D].reshape(tuple(bs))).sum_to_size(os_.shape)
+            self._theta_to_params(g, theta, D, bs, out)
         # each side with the other held fixed; x1 and x2 the same leaf: autograd adds the two.  The x2 side is the x1 side
         # of the transposed problem (x1 <-> x2, U <-> V).
         if self.x1.requires_grad:
