@@ -504,6 +504,22 @@ int lo_resident_handoff_debug(int32_t force_clear, int64_t set_next_tag, int64_t
  * from 0 up, 2 always from B - 1 down (forced modes hold for launches on the caller's workspace too, e.g. under
  * LO_OC_DEBUG); out (or NULL) receives {direction of the last launch: 0 up, 1 down; launches that walked down so far}. */
 int lo_resident_order_debug(int32_t mode, uint32_t* out);
+/* The ordered start of k_cg_rspace3 (ABI 35).  The dispatcher hands an XCD its workgroups in order and fills the first
+ * slot of every compute unit before the second, so the groups of an XCD enter in two waves -- the lower and the upper
+ * half of their local indices -- about 4 us apart.  In a launch of six rounds or more (rounds = members / groups,
+ * rounded up) every workgroup of a group with a first member waits, at the kernel's entry and before it requests
+ * anything, (the group's index inside its wave) x 200 ticks of the 100 MHz clock, provided no group of the layout would
+ * wait more than three steps (groups of 8 workgroups or more on a whole device).  Groups that share compute units then
+ * stay out of phase round after round.  The wait reads the clock and nothing else, never exceeds 800 ticks (8 us), and
+ * enters no result.
+ * Test / debug access for the current device: mode -1 leaves the rule as it is, 0 automatic (the rule above), 1 never,
+ * 2 delta = 200 whatever the rounds and the layout, 3 delta_ticks (0 .. 800) -- forced modes hold for launches on the
+ * caller's workspace too; out (or NULL) receives {mode in force; delta the last launch used, 0 = it did not wait; the
+ * groups it was laid out in; launches that waited so far}.
+ * lo_resident_start_delay evaluates the rule without a device: the ticks group `grp` of a launch of B members in
+ * `ngroups` groups (a multiple of 8) waits under (mode, delta_ticks) as above, or -1 for arguments out of range.      */
+int lo_resident_start_debug(int32_t mode, int32_t delta_ticks, uint32_t* out);
+int lo_resident_start_delay(int32_t mode, int32_t delta_ticks, int64_t B, int32_t ngroups, int32_t grp);
 
 /* ---- solve sessions: the headline solve without its per-call set-up (ABI 20) ---------------------------------------- */
 /* A preconditioner cache serves many solves of one operator; what lo_cg_solve_f32 does before and after its one launch

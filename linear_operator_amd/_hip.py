@@ -41,7 +41,7 @@ LO_OP_KERNEL_TASK_DIAG = 15
 LO_KERNEL_TASK_MAX_TASKS = 8
 LO_DIAG_NONE, LO_DIAG_FULL, LO_DIAG_CONST = 0, 1, 2
 LO_BLOCK_DIAG, LO_BLOCK_INTERLEAVED, LO_BLOCK_SUM = 0, 1, 2
-ABI_VERSION = 34
+ABI_VERSION = 35
 
 LO_ERR_UNSUPPORTED = -4
 LO_FUSED_OK, LO_FUSED_EARLY_STOP, LO_FUSED_CONTINUE, LO_FUSED_TIMEOUT = 0, 1, 2, 3
@@ -198,6 +198,8 @@ _PROTOTYPES = {
     "lo_resident_inject_timeouts": (ci, [i32]),
     "lo_resident_handoff_debug": (ci, [i32, i64, i64, P(C.c_uint32)]),
     "lo_resident_order_debug": (ci, [i32, P(C.c_uint32)]),
+    "lo_resident_start_debug": (ci, [i32, i32, P(C.c_uint32)]),
+    "lo_resident_start_delay": (ci, [i32, i32, i64, i32, i32]),
     "lo_solve_fused_supported": (ci, [P(OpDesc), i32, P(CgParams)]),
     "lo_solve_fused_workspace_bytes": (sz, [P(OpDesc), i32, P(CgParams)]),
     "lo_solve_fused_f32": (ci, [P(OpDesc), i32, f32, P(CgParams), vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, P(FusedInfo),

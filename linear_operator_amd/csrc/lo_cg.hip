@@ -1015,6 +1015,7 @@ static int resident_attempt(CgSolve& s, int attempt, bool lean, bool dense, OcNe
   a.close_ticket = 0; a.close_tol = 0.f; a.close_floor_ok = 0;
   a.close_epoch = 0x80000000u; a.tag_base = 0; a.handoff_owned = 0;  // (the cleared workspace; rspace3_launch_owned replaces them)
   a.member_flip = 0;  // (the walk order of k_cg_rspace3: rspace3_go decides it for every launch)
+  a.start_delay = 0;  // (its ordered start: rspace3_go as well)
   a.iters = s.plan.first_stop_iteration + 1; a.eps = prm->eps; a.stop_after = prm->stop_updating_after;
   a.x = d.x; a.r = d.r; a.p = d.p; a.z = d.z;
   auto lean_state = [&](bool on) {  // (kernels without the result-only mode get the state pointers back)

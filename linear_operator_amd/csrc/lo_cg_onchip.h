@@ -62,6 +62,8 @@ struct OnchipArgs {
   int close_floor_ok;              // iters - 1 >= min(10, max_iter - 1)
   int member_flip;                 // k_cg_rspace3: 1 walks the members from B - 1 down (physical member = B - 1 - drawn index);
                                    // set by rspace3_go for every launch, read by no other kernel.  Results do not depend on it
+  int start_delay;                 // k_cg_rspace3: the ordered start (lo_rs3_start.h: delta in clock ticks, 0 = none); set
+                                   // by rspace3_go for every launch, read by no other kernel.  Results do not depend on it
   long long* dbg;  // optional timestamps (wall_clock64) of member dbg_member / its workgroup 0, or nullptr
   int dbg_member;
 };

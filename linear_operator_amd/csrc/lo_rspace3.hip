@@ -26,7 +26,10 @@
 //     (143.6 -> 139.9 us per launch);
 //   * (fourth pass, profiles/r13) consecutive solves of one operator walk the members in opposite directions
 //     (OnchipArgs::member_flip, decided in rspace3_go): a solve starts with the members the previous one left in the
-//     256 MiB memory-side cache instead of the ones it evicted first (139.2 -> 131.1 us per launch).
+//     256 MiB memory-side cache instead of the ones it evicted first (139.2 -> 131.1 us per launch);
+//   * (fifth pass, profiles/r14) the ordered start: in a launch of six rounds or more the groups that the dispatcher
+//     starts together wait 0, 1, 2, 3 steps of a delay at the kernel's entry (OnchipArgs::start_delay, lo_rs3_start.h)
+//     and stay out of phase from then on (132.9 -> 129.9 us per launch in the tool's timing).
 //
 // Numerics: fp64 sums in another order (the old kernel's results to ~1e-15 relative before the final rounding to fp32).
 #include <algorithm>
@@ -41,6 +44,7 @@
 #include "lo_group_reduce.h"
 #include "lo_cg_close.h"
 #include "lo_f64_lanes.h"
+#include "lo_rs3_start.h"
 
 namespace lo {
 
@@ -179,6 +183,23 @@ __global__ __launch_bounds__(R3_TPB, 2) void k_cg_rspace3(OnchipArgs a, PeerOut 
   __shared__ __attribute__((aligned(16))) double late_v[32 + 4];
   const GroupPlace gp = group_place(GW, (int)gridDim.x / 8);
   if (!gp.active) return;  // (surplus workgroup)
+  // The ordered start (lo_rs3_start.h): a group's FIRST member asks for its rows start_delay(group) ticks behind this
+  // wave's entry -- the same wait in every workgroup of the group -- so that the groups the dispatcher starts
+  // together do not load, reduce and iterate in phase.  The wait reads the clock and nothing else, ends at the cap
+  // whatever the argument holds, and stands here, in front of everything the member loop keeps in registers: scalar
+  // registers only, from opaque copies (behind the first request it cost a vector-register spill at 32 columns).  A
+  // group without a member (grp >= B) never waits; no later member does.
+  {
+    int sd = a.start_delay, g0 = gp.grp, li = (int)(blockIdx.x / 8) / GW;  // (li: the group's local index inside its XCD)
+    asm volatile("" : "+s"(sd), "+s"(g0), "+s"(li));
+    const unsigned wait = (sd != 0 && g0 < a.B) ? (unsigned)r3_start_delay_local(sd, li, (int)gridDim.x / 8 / GW) : 0u;
+    if (wait > 0) {  // (<= R3_START_CAP_TICKS)
+      const unsigned t_in = (unsigned)wall_clock64();  // (low words: the differences below are exact modulo 2^32)
+#pragma unroll 1
+      for (int n = 0; n < 4 * R3_START_CAP_TICKS && (unsigned)wall_clock64() - t_in < wait; ++n)
+        __builtin_amdgcn_s_sleep(1);
+    }
+  }
   const int grp = gp.grp, wig = gp.wig, ngroups = gp.ngroups;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int wave_u = __builtin_amdgcn_readfirstlane(wave);
@@ -790,6 +811,11 @@ struct HandoffBlock {
   bool ord_flip = false;                    // its direction
   int ord_mode = 0;                         // lo_resident_order_debug: 0 automatic, 1 always forward, 2 always reverse
   unsigned ord_last = 0, ord_reversed = 0;  // direction of the last k_cg_rspace3 launch (owned or not), reversed launches
+  // The ordered start (OnchipArgs::start_delay, lo_rs3_start.h): lo_resident_start_debug sets mode and delta, every launch
+  // of k_cg_rspace3 -- owned or not -- records the argument it ran with and the groups it was laid out in.
+  int start_mode = R3_START_AUTO, start_delta = 0;
+  int start_last = 0, start_last_ngroups = 0;
+  unsigned start_waited = 0;                // launches that ran with a wait
 };
 HandoffBlock g_handoff[16];
 std::atomic<unsigned> g_handoff_ids{0};
@@ -881,6 +907,14 @@ int rspace3_go(const OnchipArgs& a, int nwg, const OwnedLaunch* own, hipStream_t
     if (own) ho->ord_flip = a2.member_flip != 0;
     ho->ord_last = (unsigned)a2.member_flip;
     ho->ord_reversed += (unsigned)a2.member_flip;
+  }
+  // (the ordered start: by the rounds of this launch, or as lo_resident_start_debug forces it)
+  const int ngroups = (2 * nwg / 8 / GW) * 8;
+  a2.start_delay = r3_start_arg(ho ? ho->start_mode : R3_START_AUTO, ho ? ho->start_delta : 0, a.B, ngroups);
+  if (ho) {
+    ho->start_last = a2.start_delay;
+    ho->start_last_ngroups = ngroups;
+    ho->start_waited += a2.start_delay != 0 ? 1u : 0u;
   }
   PeerOut po;
   {
@@ -977,4 +1011,32 @@ extern "C" int lo_resident_order_debug(int32_t mode, uint32_t* out) {
     out[1] = h.ord_reversed;
   }
   return LO_OK;
+}
+
+// Test / debug access to the ordered start of k_cg_rspace3 on the current device (lo_amd.h).
+extern "C" int lo_resident_start_debug(int32_t mode, int32_t delta_ticks, uint32_t* out) {
+  lo::ResidentLock guard;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return LO_ERR_BADARG;
+  if (mode < -1 || mode > lo::R3_START_GIVEN) return LO_ERR_BADARG;
+  const bool given = mode == lo::R3_START_GIVEN;
+  if (given && (delta_ticks < 0 || delta_ticks > lo::R3_START_CAP_TICKS)) return LO_ERR_BADARG;
+  lo::HandoffBlock& h = lo::g_handoff[dev];
+  if (mode >= 0) {
+    h.start_mode = mode;
+    h.start_delta = given ? delta_ticks : 0;
+  }
+  if (out) {
+    out[0] = (uint32_t)h.start_mode;
+    out[1] = (uint32_t)h.start_last;
+    out[2] = (uint32_t)h.start_last_ngroups;
+    out[3] = h.start_waited;
+  }
+  return LO_OK;
+}
+
+// The rule of the ordered start without a device: the ticks group `grp` of a launch of B members in `ngroups` groups waits.
+extern "C" int lo_resident_start_delay(int32_t mode, int32_t delta_ticks, int64_t B, int32_t ngroups, int32_t grp) {
+  if (mode < 0 || mode > lo::R3_START_GIVEN || B < 0 || ngroups < 8 || ngroups % 8 || grp < 0 || grp >= ngroups) return -1;
+  return lo::r3_start_delay(lo::r3_start_arg(mode, delta_ticks, B, ngroups), grp, ngroups / 8);
 }

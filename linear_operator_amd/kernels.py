@@ -2392,6 +2392,25 @@ def resident_order_debug(mode: int = -1) -> dict:
     return {"last": "reverse" if out[0] else "forward", "reversed": int(out[1])}
 
 
+RESIDENT_START_CAP_TICKS = 800  # (csrc/lo_rs3_start.h: no workgroup waits longer, 8 us of the 100 MHz clock)
+
+
+def resident_start_debug(mode: int = -1, delta_ticks: int = 0) -> dict:
+    """lo_resident_start_debug: the ordered start of the headline solve (`k_cg_rspace3`) on the current device -- mode 0
+    automatic (the committed delay in launches of six rounds or more, in the layouts it was measured in), 1 never, 2
+    the committed delay always, 3 `delta_ticks`, -1 leave; returns the mode in force and what the last launch used:
+    its delta (0: no wait), its groups, and how many launches waited."""
+    out = (C.c_uint32 * 4)()
+    _hip.call("lo_resident_start_debug", int(mode), int(delta_ticks), out)
+    return {"mode": int(out[0]), "delta": int(out[1]), "ngroups": int(out[2]), "waited": int(out[3])}
+
+
+def resident_start_delay(mode: int, delta_ticks: int, B: int, ngroups: int, grp: int) -> int:
+    """lo_resident_start_delay: the ticks group `grp` of a launch of B members in `ngroups` groups waits under
+    (mode, delta_ticks) -- the rule of the ordered start, evaluated on the host (no device needed)."""
+    return int(_hip.load().lo_resident_start_delay(int(mode), int(delta_ticks), int(B), int(ngroups), int(grp)))
+
+
 def peer_gather_set(bufs=(), member_offset: int = 0) -> None:
     """lo_peer_gather_set (prototype): up to seven [B_total, N] fp32 buffers the resident single-column solve writes its
     solutions into next to its own output -- the gather of SURVEY 8(e) as peer writes.  () removes them."""
