@@ -27,13 +27,7 @@
 
 namespace lo {
 
-// columns of v one sweep carries, by the padded dimension: a thread holds (DP + 1) CC running sums and as many tile sums,
-// and every instantiation stays at 3 waves per SIMD (<= 168 VGPRs) without scratch -- 4 columns at DP 4, 2 at DP 8, 1 at
-// DP 16 (one more column at DP 8 / 16 spills: 200 / 249 VGPRs unconstrained)
-inline int kg_col_chunk(int DP, int64_t c) {
-  const int most = DP <= 4 ? 4 : (DP <= 8 ? 2 : 1);
-  return c == 1 ? 1 : (c == 2 ? std::min(most, 2) : most);
-}
+// (the column chunks kg_col_chunk / kg_cols / kg_bil_cols by the padded dimension: lo_kernel_shape.h)
 
 // grid (row blocks, B, js); part == nullptr: y is written with the diagonal term, else partial products [js, B, M T, c]
 template <int FAMILY, int DP, int CC>
@@ -265,64 +259,32 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(3))) v
   if (threadIdx.x == 0) out[DP] = sum;
 }
 
-template <int DP>
-static void kg_mv_launch_cc(int CC, dim3 grid, hipStream_t st, const float* x1, const float* x2, const float* theta, int M,
-                            int N, int D, const float* v, int c, const float* d, int dmode, float* y, float* part,
-                            int jchunk, const int* stop) {
-#define KG_MV(CC_)                                                                                                    \
-  hipLaunchKernelGGL((k_kernel_grad_mv<LO_KERNEL_RBF, DP, CC_>), grid, dim3(kThreads), 0, st, x1, x2, theta, M, N, D, v, \
-                     c, d, dmode, y, part, jchunk, stop)
-  if constexpr (DP <= 4) {
-    if (CC == 4) {
-      KG_MV(4);
-      return;
-    }
-  }
-  if constexpr (DP <= 8) {
-    if (CC == 2) {
-      KG_MV(2);
-      return;
-    }
-  }
-  KG_MV(1);
-#undef KG_MV
-}
-
 // arguments both entry points and the descriptor are held to (all sizes already positive); cols = c or t
 static bool kg_shape_ok(int64_t B, int64_t M, int64_t N, int64_t D, int64_t cols) {
   return D <= LO_KERNEL_GRAD_MAX_DIM && B <= 65535 && M * (D + 1) <= 0x7ffffe00 && N * (D + 1) <= 0x7ffffe00 &&
          cols <= 0x7fffffff / (D + 1);
 }
 
-// the one layout of the product's workspace: the partials [js, B, M (D + 1), c] of a split member
-static float* kg_mv_layout(Arena& ar, int64_t B, int64_t M, int64_t N, int64_t D, int64_t c) {
-  const KoShape s = ko_shape(B, M, N);
-  return s.js > 1 ? ar.take<float>((size_t)s.js * B * M * (D + 1) * c) : nullptr;
-}
-
-// the product on validated arguments (family RBF)
+// the product on validated arguments (family RBF); part: the partials [js, B, M, (D + 1) c] of a split member
 static int kg_mv_run(const float* x1, const float* x2, const float* theta, int64_t B, int64_t M, int64_t N, int64_t D,
                      const float* v, int64_t c, const float* d, int dmode, float* y, float* part, const int* stop,
                      hipStream_t st) {
-  const KoShape s = ko_shape(B, M, N);
-  const int DP = ko_padded_dim(D), CC = kg_col_chunk(DP, c);
+  const KoSweep w(B, M, N, D);
+  const int CC = kg_col_chunk(w.DP, c);
   const int64_t T = D + 1;
-  const dim3 grid((unsigned)s.rb, (unsigned)B, (unsigned)s.js);
-  float* p = s.js > 1 ? part : nullptr;
+  float* p = w.s.js > 1 ? part : nullptr;
   LO_PROF_BEGIN("k_kernel_grad_mv", st);
-#define KG_MV(DP_) \
-  kg_mv_launch_cc<DP_>(CC, grid, st, x1, x2, theta, (int)M, (int)N, (int)D, v, (int)c, d, dmode, y, p, s.jchunk, stop)
-  switch (DP) {
-    case 4: KG_MV(4); break;
-    case 8: KG_MV(8); break;
-    default: KG_MV(16); break;
-  }
-#undef KG_MV
+  ko_pick(kg_dims{}, w.DP, [&](auto P) {  // (the column list depends on the padded dimension)
+    ko_pick(kg_cols<P()>{}, CC, [&](auto C) {
+      hipLaunchKernelGGL((k_kernel_grad_mv<LO_KERNEL_RBF, P(), C()>), w.grid, dim3(kThreads), 0, st, x1, x2, theta, (int)M,
+                         (int)N, (int)D, v, (int)c, d, dmode, y, p, w.s.jchunk, stop);
+    });
+  });
   LO_PROF_END(st);
   LO_LAUNCH_CHECK();
   if (p)  // (rows of c elements: the full diagonal of the reduction is indexed by o / c = the full row i T + a)
-    return ko_reduce_splits("k_kernel_grad_mv_reduce", p, s.js, (size_t)M * T * c, (size_t)B * M * T * c, (int)c, d, dmode,
-                            v, y, stop, st);
+    return ko_reduce_splits("k_kernel_grad_mv_reduce", p, w.s.js, (size_t)M * T * c, (size_t)B * M * T * c, (int)c, d,
+                            dmode, v, y, stop, st);
   return LO_OK;
 }
 
@@ -338,7 +300,7 @@ int kernel_grad_plan(MatvecPlan* pl, Arena* ar, hipStream_t) {
   if (const int rc = kernel_grad_desc_check(&op)) return rc;
   const int64_t n = op.N / (op.R + 1);
   if (!kg_shape_ok(op.B, n, n, op.R, pl->c)) return LO_ERR_UNSUPPORTED;
-  pl->kg.part = kg_mv_layout(*ar, op.B, n, n, op.R, pl->c);
+  pl->kg.part = ko_split_layout<float>(*ar, op.B, n, n, (op.R + 1) * pl->c);
   return LO_OK;
 }
 
@@ -346,11 +308,6 @@ int kernel_grad_matvec_run(const MatvecPlan* pl, const float* v, float* y, const
   const lo_op_desc& op = pl->op;
   const int64_t n = op.N / (op.R + 1);
   return kg_mv_run(op.A0, op.A0, op.A1, op.B, n, n, op.R, v, pl->c, op.d, op.diag_mode, y, pl->kg.part, stop, st);
-}
-
-static float* kg_bil_layout(Arena& ar, int64_t B, int64_t M, int64_t N, int64_t D) {
-  const KoShape s = ko_shape(B, M, N);
-  return ar.take<float>((size_t)B * s.rb * s.js * (ko_padded_dim(D) + 1));
 }
 
 }  // namespace lo
@@ -361,25 +318,25 @@ extern "C" {
 
 size_t lo_kernel_grad_mv_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t D, int64_t c) {
   if (!ko_args_ok(B, M, N, D, c) || !kg_shape_ok(B, M, N, D, c)) return 0;
-  return measured(kKoTail, [&](Arena& ar) { kg_mv_layout(ar, B, M, N, D, c); });
+  return measured(kKoTail, [&](Arena& ar) { ko_split_layout<float>(ar, B, M, N, (D + 1) * c); });
 }
 
 int lo_kernel_grad_mv_f32(const float* x1, const float* x2, const float* theta, int32_t family, int64_t B, int64_t M,
                           int64_t N, int64_t D, const float* v, int64_t c, const float* d, int32_t diag_mode, float* y,
                           void* ws, size_t ws_bytes, void* stream) {
   if (!x1 || !x2 || !theta || !v || !y || !ko_args_ok(B, M, N, D, c) || !ko_family_ok(family)) return LO_ERR_BADARG;
-  if (diag_mode != LO_DIAG_NONE && diag_mode != LO_DIAG_FULL && diag_mode != LO_DIAG_CONST) return LO_ERR_BADARG;
-  if (diag_mode != LO_DIAG_NONE && (!d || M != N)) return LO_ERR_BADARG;
+  // (a diagonal term only on a square operator, and then with its operand)
+  if (!ko_diag_ok(diag_mode, d, true) || (diag_mode != LO_DIAG_NONE && M != N)) return LO_ERR_BADARG;
   if (family != LO_KERNEL_RBF || !kg_shape_ok(B, M, N, D, c)) return LO_ERR_UNSUPPORTED;
   Arena ar(ws, ws_bytes, kKoTail);
-  float* part = kg_mv_layout(ar, B, M, N, D, c);
+  float* part = ko_split_layout<float>(ar, B, M, N, (D + 1) * c);
   if (!ws || !ar.ok) return LO_ERR_WORKSPACE;
   return kg_mv_run(x1, x2, theta, B, M, N, D, v, c, d, diag_mode, y, part, nullptr, (hipStream_t)stream);
 }
 
 size_t lo_kernel_grad_bilinear_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t D, int64_t t) {
   if (!ko_args_ok(B, M, N, D, t) || !kg_shape_ok(B, M, N, D, t)) return 0;
-  return measured(kKoTail, [&](Arena& ar) { kg_bil_layout(ar, B, M, N, D); });
+  return measured(kKoTail, [&](Arena& ar) { ko_bil_layout<float>(ar, B, M, N, D); });
 }
 
 int lo_kernel_grad_bilinear_f32(const float* x1, const float* x2, const float* theta, int32_t family, int64_t B, int64_t M,
@@ -390,24 +347,18 @@ int lo_kernel_grad_bilinear_f32(const float* x1, const float* x2, const float* t
   if (family != LO_KERNEL_RBF || !kg_shape_ok(B, M, N, D, t)) return LO_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   Arena ar(ws, ws_bytes, kKoTail);
-  float* part = kg_bil_layout(ar, B, M, N, D);
+  float* part = ko_bil_layout<float>(ar, B, M, N, D);
   if (!ws || !ar.ok) return LO_ERR_WORKSPACE;
-  const KoShape s = ko_shape(B, M, N);
-  const int DP = ko_padded_dim(D);
-  const dim3 grid((unsigned)s.rb, (unsigned)B, (unsigned)s.js);
+  const KoSweep w(B, M, N, D);
   LO_PROF_BEGIN("k_kernel_grad_bilinear", st);
-#define KG_BIL(DP_, TS_)                                                                                               \
-  hipLaunchKernelGGL((k_kernel_grad_bilinear<LO_KERNEL_RBF, DP_, TS_>), grid, dim3(kThreads), 0, st, x1, x2, theta, (int)M, \
-                     (int)N, (int)D, U, V, (int)t, part, s.jchunk)
-  switch (DP) {  // columns of U / V per sweep: the thread keeps DP + 1 scaled entries of U per column in registers
-    case 4: KG_BIL(4, kKoTS); break;
-    case 8: KG_BIL(8, 4); break;
-    default: KG_BIL(16, 2); break;
-  }
-#undef KG_BIL
+  ko_pick(kg_dims{}, w.DP, [&](auto P) {
+    hipLaunchKernelGGL((k_kernel_grad_bilinear<LO_KERNEL_RBF, P(), kg_bil_cols(P())>), w.grid, dim3(kThreads), 0, st, x1, x2,
+                       theta, (int)M, (int)N, (int)D, U, V, (int)t, part, w.s.jchunk);
+  });
   LO_PROF_END(st);
   LO_LAUNCH_CHECK();
-  return ko_bil_reduce(part, s.rb * s.js, DP, B, D, theta, g_theta, st);
+  return ko_bil_reduce(part, w.s.rb * w.s.js, w.DP, B, D, theta, g_theta, st);
 }
 
 }  // extern "C"
+

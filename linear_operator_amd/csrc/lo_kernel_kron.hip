@@ -22,7 +22,7 @@
 namespace lo {
 
 inline bool kk_tasks_ok(int64_t T) { return T >= 1 && T <= LO_KERNEL_KRON_MAX_TASKS; }
-inline int kk_col_chunk(int64_t W) { return W <= 4 ? 4 : (W <= 16 ? 16 : 32); }
+// (the wide column chunk of a sweep, kk_col_chunk / kk_cols: lo_kernel_shape.h)
 
 // grid (row blocks, B, js); part == nullptr: y is written with the diagonal term, else partial products [js, B, n, T c]
 template <int FAMILY, int DP, int CCW>
@@ -111,69 +111,27 @@ __global__ __launch_bounds__(kThreads) void k_kernel_kron_mv(const float* __rest
   }
 }
 
-template <int FAMILY, int DP>
-static void kk_mv_launch_cc(int CCW, dim3 grid, hipStream_t st, const float* x, const float* theta, const float* task,
-                            int n, int D, int T, const float* v, int c, const float* d, int dmode, float* y, float* part,
-                            int jchunk, const int* stop) {
-#define KK_MV(CCW_)                                                                                                     \
-  hipLaunchKernelGGL((k_kernel_kron_mv<FAMILY, DP, CCW_>), grid, dim3(kThreads), 0, st, x, theta, task, n, D, T, v, c, d, \
-                     dmode, y, part, jchunk, stop)
-  switch (CCW) {
-    case 4: KK_MV(4); break;
-    case 16: KK_MV(16); break;
-    default: KK_MV(32); break;
-  }
-#undef KK_MV
-}
-
-template <int FAMILY>
-static void kk_mv_launch_dp(int DP, int CCW, dim3 grid, hipStream_t st, const float* x, const float* theta,
-                            const float* task, int n, int D, int T, const float* v, int c, const float* d, int dmode,
-                            float* y, float* part, int jchunk, const int* stop) {
-#define KK_MV(DP_) kk_mv_launch_cc<FAMILY, DP_>(CCW, grid, st, x, theta, task, n, D, T, v, c, d, dmode, y, part, jchunk, stop)
-  switch (DP) {
-    case 4: KK_MV(4); break;
-    case 8: KK_MV(8); break;
-    case 16: KK_MV(16); break;
-    default: KK_MV(32); break;
-  }
-#undef KK_MV
-}
-
 // arguments both the entry point and the descriptor are held to (B, n, D, T, c already positive)
 static bool kk_shape_ok(int64_t B, int64_t n, int64_t D, int64_t T, int64_t c) {
   return ko_shape_ok(B, n, n, D) && n * T <= 0x7ffffe00 && T * c <= 0x7fffffff;
 }
 
-// the one layout of the product's workspace: the partials [js, B, n, T c] of a split member
-static float* kk_mv_layout(Arena& ar, int64_t B, int64_t n, int64_t T, int64_t c) {
-  const KoShape s = ko_shape(B, n, n);
-  return s.js > 1 ? ar.take<float>((size_t)s.js * B * n * T * c) : nullptr;
-}
-
-// the product on validated arguments
+// the product on validated arguments; part: the partials [js, B, n, T c] of a split member (ko_split_layout)
 static int kk_mv_run(const float* x, const float* theta, const float* task, int family, int64_t B, int64_t n, int64_t D,
                      int64_t T, const float* v, int64_t c, const float* d, int dmode, float* y, float* part,
                      const int* stop, hipStream_t st) {
-  const KoShape s = ko_shape(B, n, n);
+  const KoSweep w(B, n, n, D);
   const int64_t W = T * c;
-  const int DP = ko_padded_dim(D), CCW = kk_col_chunk(W);
-  const dim3 grid((unsigned)s.rb, (unsigned)B, (unsigned)s.js);
-  float* p = s.js > 1 ? part : nullptr;
+  float* p = w.s.js > 1 ? part : nullptr;
   LO_PROF_BEGIN("k_kernel_kron_mv", st);
-#define KK_FAM(F_) \
-  kk_mv_launch_dp<F_>(DP, CCW, grid, st, x, theta, task, (int)n, (int)D, (int)T, v, (int)c, d, dmode, y, p, s.jchunk, stop)
-  switch (family) {
-    case LO_KERNEL_RBF: KK_FAM(LO_KERNEL_RBF); break;
-    case LO_KERNEL_MATERN12: KK_FAM(LO_KERNEL_MATERN12); break;
-    case LO_KERNEL_MATERN32: KK_FAM(LO_KERNEL_MATERN32); break;
-    default: KK_FAM(LO_KERNEL_MATERN52); break;
-  }
-#undef KK_FAM
+  ko_dispatch(family, w.DP, kk_cols{}, kk_col_chunk(W), [&](auto F, auto P, auto C) {
+    hipLaunchKernelGGL((k_kernel_kron_mv<F(), P(), C()>), w.grid, dim3(kThreads), 0, st, x, theta, task, (int)n, (int)D,
+                       (int)T, v, (int)c, d, dmode, y, p, w.s.jchunk, stop);
+  });
   LO_PROF_END(st);
   LO_LAUNCH_CHECK();
   if (p)  // (rows of c elements: the full diagonal of the reduction is indexed by o / c = the full row i T + t)
-    return ko_reduce_splits("k_kernel_kron_mv_reduce", p, s.js, (size_t)n * W, (size_t)B * n * W, (int)c, d, dmode, v, y,
+    return ko_reduce_splits("k_kernel_kron_mv_reduce", p, w.s.js, (size_t)n * W, (size_t)B * n * W, (int)c, d, dmode, v, y,
                             stop, st);
   return LO_OK;
 }
@@ -190,7 +148,7 @@ int kernel_kron_plan(MatvecPlan* pl, Arena* ar, hipStream_t) {
   if (const int rc = kernel_kron_desc_check(&op)) return rc;
   const int64_t n = op.N / op.nterms;
   if (!kk_shape_ok(op.B, n, op.R, op.nterms, pl->c)) return LO_ERR_UNSUPPORTED;
-  pl->kk.part = kk_mv_layout(*ar, op.B, n, op.nterms, pl->c);
+  pl->kk.part = ko_split_layout<float>(*ar, op.B, n, n, op.nterms * pl->c);
   return LO_OK;
 }
 
@@ -208,7 +166,7 @@ extern "C" {
 
 size_t lo_kernel_kron_mv_workspace_bytes(int64_t B, int64_t n, int64_t D, int64_t T, int64_t c) {
   if (!ko_args_ok(B, n, n, D, c) || !kk_tasks_ok(T) || !kk_shape_ok(B, n, D, T, c)) return 0;
-  return measured(kKoTail, [&](Arena& ar) { kk_mv_layout(ar, B, n, T, c); });
+  return measured(kKoTail, [&](Arena& ar) { ko_split_layout<float>(ar, B, n, n, T * c); });
 }
 
 int lo_kernel_kron_mv_f32(const float* x, const float* theta, const float* task, int32_t family, int64_t B, int64_t n,
@@ -216,13 +174,13 @@ int lo_kernel_kron_mv_f32(const float* x, const float* theta, const float* task,
                           void* ws, size_t ws_bytes, void* stream) {
   if (!x || !theta || !task || !v || !y || !ko_args_ok(B, n, n, D, c) || !ko_family_ok(family) || T < 1)
     return LO_ERR_BADARG;
-  if (diag_mode != LO_DIAG_NONE && diag_mode != LO_DIAG_FULL && diag_mode != LO_DIAG_CONST) return LO_ERR_BADARG;
-  if (diag_mode != LO_DIAG_NONE && !d) return LO_ERR_BADARG;
+  if (!ko_diag_ok(diag_mode, d, true)) return LO_ERR_BADARG;  // (the operator is square: d whenever a mode is given)
   if (!kk_tasks_ok(T) || !kk_shape_ok(B, n, D, T, c)) return LO_ERR_UNSUPPORTED;
   Arena ar(ws, ws_bytes, kKoTail);
-  float* part = kk_mv_layout(ar, B, n, T, c);
+  float* part = ko_split_layout<float>(ar, B, n, n, T * c);
   if (!ws || !ar.ok) return LO_ERR_WORKSPACE;
   return kk_mv_run(x, theta, task, family, B, n, D, T, v, c, d, diag_mode, y, part, nullptr, (hipStream_t)stream);
 }
 
 }  // extern "C"
+

@@ -313,108 +313,31 @@ int ko_bil_reduce(const float* part, int nblk, int DP, int64_t B, int64_t D, con
   return LO_OK;
 }
 
-template <int FAMILY, int DP>
-static void ko_mv_launch_cc(int CC, dim3 grid, hipStream_t st, const float* x1, const float* x2, const float* theta,
-                            int tstride, int M, int N, int D, const float* v, int c, const float* d, int dmode, float* y,
-                            float* part, int jchunk, const int* stop) {
-  switch (CC) {
-    case 1:
-      hipLaunchKernelGGL((k_kernel_mv<FAMILY, DP, 1>), grid, dim3(kThreads), 0, st, x1, x2, theta, tstride, M, N, D, v, c,
-                         d, dmode, y, part, jchunk, stop);
-      break;
-    case 4:
-      hipLaunchKernelGGL((k_kernel_mv<FAMILY, DP, 4>), grid, dim3(kThreads), 0, st, x1, x2, theta, tstride, M, N, D, v, c,
-                         d, dmode, y, part, jchunk, stop);
-      break;
-    default:
-      hipLaunchKernelGGL((k_kernel_mv<FAMILY, DP, 16>), grid, dim3(kThreads), 0, st, x1, x2, theta, tstride, M, N, D, v, c,
-                         d, dmode, y, part, jchunk, stop);
-      break;
-  }
-}
-
-template <int FAMILY>
-static void ko_mv_launch_dp(int DP, int CC, dim3 grid, hipStream_t st, const float* x1, const float* x2,
-                            const float* theta, int tstride, int M, int N, int D, const float* v, int c, const float* d,
-                            int dmode, float* y, float* part, int jchunk, const int* stop) {
-#define KO_MV(DP_) \
-  ko_mv_launch_cc<FAMILY, DP_>(CC, grid, st, x1, x2, theta, tstride, M, N, D, v, c, d, dmode, y, part, jchunk, stop)
-  switch (DP) {
-    case 4: KO_MV(4); break;
-    case 8: KO_MV(8); break;
-    case 16: KO_MV(16); break;
-    default: KO_MV(32); break;
-  }
-#undef KO_MV
-}
-
-template <int FAMILY>
-static void ko_bil_launch_dp(int DP, dim3 grid, hipStream_t st, const float* x1, const float* x2, const float* theta, int M,
-                             int N, int D, const float* U, const float* V, int t, float* part, int jchunk) {
-#define KO_BIL(DP_) \
-  hipLaunchKernelGGL((k_kernel_bil<FAMILY, DP_>), grid, dim3(kThreads), 0, st, x1, x2, theta, M, N, D, U, V, t, part, jchunk)
-  switch (DP) {
-    case 4: KO_BIL(4); break;
-    case 8: KO_BIL(8); break;
-    case 16: KO_BIL(16); break;
-    default: KO_BIL(32); break;
-  }
-#undef KO_BIL
-}
-
-template <int FAMILY>
-static void ko_pgrad_launch_dp(int DP, dim3 grid, hipStream_t st, const float* x1, const float* x2, const float* theta,
-                               int M, int N, int D, const float* U, const float* V, int t, float* out, int jchunk) {
-#define KO_PG(DP_) \
-  hipLaunchKernelGGL((k_kernel_pgrad<FAMILY, DP_>), grid, dim3(kThreads), 0, st, x1, x2, theta, M, N, D, U, V, t, out, jchunk)
-  switch (DP) {
-    case 4: KO_PG(4); break;
-    case 8: KO_PG(8); break;
-    case 16: KO_PG(16); break;
-    default: KO_PG(32); break;
-  }
-#undef KO_PG
-}
-
 // the product on validated arguments; part: [js, B, M, c] floats when ko_shape(B, M, N).js > 1 (else unused)
 int kernel_mv_run(const float* x1, const float* x2, const float* theta, int64_t tstride, int family, int64_t B, int64_t M,
                   int64_t N, int64_t D, const float* v, int64_t c, const float* d, int dmode, float* y, float* part,
                   const int* stop, hipStream_t st) {
-  const KoShape s = ko_shape(B, M, N);
-  const int DP = ko_padded_dim(D), CC = ko_col_chunk(c);
-  const dim3 grid((unsigned)s.rb, (unsigned)B, (unsigned)s.js);
-  float* p = s.js > 1 ? part : nullptr;
+  const KoSweep w(B, M, N, D);
+  float* p = w.s.js > 1 ? part : nullptr;
   if (M != N) dmode = LO_DIAG_NONE;
   LO_PROF_BEGIN("k_kernel_mv", st);
-#define KO_FAM(F_)                                                                                                    \
-  ko_mv_launch_dp<F_>(DP, CC, grid, st, x1, x2, theta, (int)tstride, (int)M, (int)N, (int)D, v, (int)c, d, dmode, y, p, \
-                      s.jchunk, stop)
-  switch (family) {
-    case LO_KERNEL_RBF: KO_FAM(LO_KERNEL_RBF); break;
-    case LO_KERNEL_MATERN12: KO_FAM(LO_KERNEL_MATERN12); break;
-    case LO_KERNEL_MATERN32: KO_FAM(LO_KERNEL_MATERN32); break;
-    default: KO_FAM(LO_KERNEL_MATERN52); break;
-  }
-#undef KO_FAM
+  ko_dispatch(family, w.DP, ko_cols{}, ko_col_chunk(c), [&](auto F, auto P, auto C) {
+    hipLaunchKernelGGL((k_kernel_mv<F(), P(), C()>), w.grid, dim3(kThreads), 0, st, x1, x2, theta, (int)tstride, (int)M,
+                       (int)N, (int)D, v, (int)c, d, dmode, y, p, w.s.jchunk, stop);
+  });
   LO_PROF_END(st);
   LO_LAUNCH_CHECK();
   if (p)
-    return ko_reduce_splits("k_kernel_mv_reduce", p, s.js, (size_t)M * c, (size_t)B * M * c, (int)c, d, dmode, v, y, stop,
-                            st);
+    return ko_reduce_splits("k_kernel_mv_reduce", p, w.s.js, (size_t)M * c, (size_t)B * M * c, (int)c, d, dmode, v, y,
+                            stop, st);
   return LO_OK;
-}
-
-// the one layout of the product's workspace: the partials of a split member
-static float* ko_mv_layout(Arena& ar, int64_t B, int64_t M, int64_t N, int64_t c) {
-  const KoShape s = ko_shape(B, M, N);
-  return s.js > 1 ? ar.take<float>((size_t)s.js * B * M * c) : nullptr;
 }
 
 int kernel_op_plan(MatvecPlan* pl, Arena* ar, hipStream_t) {
   const lo_op_desc& op = pl->op;
   if (!op.A0 || !op.A1 || op.R < 1 || !ko_family_ok(op.n2)) return LO_ERR_BADARG;
   if (!ko_shape_ok(op.B, op.N, op.N, op.R) || pl->c > 0x7fffffff) return LO_ERR_UNSUPPORTED;
-  pl->ko.part = ko_mv_layout(*ar, op.B, op.N, op.N, pl->c);
+  pl->ko.part = ko_split_layout<float>(*ar, op.B, op.N, op.N, pl->c);
   return LO_OK;
 }
 
@@ -422,17 +345,6 @@ int kernel_op_matvec_run(const MatvecPlan* pl, const float* v, float* y, const i
   const lo_op_desc& op = pl->op;
   return kernel_mv_run(op.A0, op.A0, op.A1, op.R + 1, (int)op.n2, op.B, op.N, op.N, op.R, v, pl->c, op.d, op.diag_mode, y,
                        pl->ko.part, stop, st);
-}
-
-static float* ko_bil_layout(Arena& ar, int64_t B, int64_t M, int64_t N, int64_t D) {
-  const KoShape s = ko_shape(B, M, N);
-  return ar.take<float>((size_t)B * s.rb * s.js * (ko_padded_dim(D) + 1));
-}
-
-// the one layout of the points' gradient: the partials [js, B, M, D] of a split member
-static float* ko_pgrad_layout(Arena& ar, int64_t B, int64_t M, int64_t N, int64_t D) {
-  const KoShape s = ko_shape(B, M, N);
-  return s.js > 1 ? ar.take<float>((size_t)s.js * B * M * D) : nullptr;
 }
 
 }  // namespace lo
@@ -443,18 +355,17 @@ extern "C" {
 
 size_t lo_kernel_mv_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t D, int64_t c) {
   if (!ko_args_ok(B, M, N, D, c) || !ko_shape_ok(B, M, N, D) || c > 0x7fffffff) return 0;
-  return measured(kKoTail, [&](Arena& ar) { ko_mv_layout(ar, B, M, N, c); });
+  return measured(kKoTail, [&](Arena& ar) { ko_split_layout<float>(ar, B, M, N, c); });
 }
 
 int lo_kernel_mv_f32(const float* x1, const float* x2, const float* theta, int32_t family, int64_t B, int64_t M,
                      int64_t N, int64_t D, const float* v, int64_t c, const float* d, int32_t diag_mode, float* y,
                      void* ws, size_t ws_bytes, void* stream) {
   if (!x1 || !x2 || !theta || !v || !y || !ko_args_ok(B, M, N, D, c) || !ko_family_ok(family)) return LO_ERR_BADARG;
-  if (diag_mode != LO_DIAG_NONE && diag_mode != LO_DIAG_FULL && diag_mode != LO_DIAG_CONST) return LO_ERR_BADARG;
-  if (diag_mode != LO_DIAG_NONE && M == N && !d) return LO_ERR_BADARG;
+  if (!ko_diag_ok(diag_mode, d, M == N)) return LO_ERR_BADARG;
   if (!ko_shape_ok(B, M, N, D) || c > 0x7fffffff) return LO_ERR_UNSUPPORTED;
   Arena ar(ws, ws_bytes, kKoTail);
-  float* part = ko_mv_layout(ar, B, M, N, c);
+  float* part = ko_split_layout<float>(ar, B, M, N, c);
   if (!ws || !ar.ok) return LO_ERR_WORKSPACE;
   return kernel_mv_run(x1, x2, theta, D + 1, family, B, M, N, D, v, c, d, diag_mode, y, part, nullptr,
                        (hipStream_t)stream);
@@ -462,7 +373,7 @@ int lo_kernel_mv_f32(const float* x1, const float* x2, const float* theta, int32
 
 size_t lo_kernel_bilinear_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t D, int64_t t) {
   if (!ko_args_ok(B, M, N, D, t) || !ko_shape_ok(B, M, N, D) || t > 0x7fffffff) return 0;
-  return measured(kKoTail, [&](Arena& ar) { ko_bil_layout(ar, B, M, N, D); });
+  return measured(kKoTail, [&](Arena& ar) { ko_bil_layout<float>(ar, B, M, N, D); });
 }
 
 int lo_kernel_bilinear_f32(const float* x1, const float* x2, const float* theta, int32_t family, int64_t B, int64_t M,
@@ -473,28 +384,22 @@ int lo_kernel_bilinear_f32(const float* x1, const float* x2, const float* theta,
   if (!ko_shape_ok(B, M, N, D) || t > 0x7fffffff) return LO_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   Arena ar(ws, ws_bytes, kKoTail);
-  float* part = ko_bil_layout(ar, B, M, N, D);
+  float* part = ko_bil_layout<float>(ar, B, M, N, D);
   if (!ws || !ar.ok) return LO_ERR_WORKSPACE;
-  const KoShape s = ko_shape(B, M, N);
-  const int DP = ko_padded_dim(D);
-  const dim3 grid((unsigned)s.rb, (unsigned)B, (unsigned)s.js);
+  const KoSweep w(B, M, N, D);
   LO_PROF_BEGIN("k_kernel_bil", st);
-#define KO_FAM(F_) ko_bil_launch_dp<F_>(DP, grid, st, x1, x2, theta, (int)M, (int)N, (int)D, U, V, (int)t, part, s.jchunk)
-  switch (family) {
-    case LO_KERNEL_RBF: KO_FAM(LO_KERNEL_RBF); break;
-    case LO_KERNEL_MATERN12: KO_FAM(LO_KERNEL_MATERN12); break;
-    case LO_KERNEL_MATERN32: KO_FAM(LO_KERNEL_MATERN32); break;
-    default: KO_FAM(LO_KERNEL_MATERN52); break;
-  }
-#undef KO_FAM
+  ko_dispatch(family, w.DP, [&](auto F, auto P) {
+    hipLaunchKernelGGL((k_kernel_bil<F(), P()>), w.grid, dim3(kThreads), 0, st, x1, x2, theta, (int)M, (int)N, (int)D, U, V,
+                       (int)t, part, w.s.jchunk);
+  });
   LO_PROF_END(st);
   LO_LAUNCH_CHECK();
-  return ko_bil_reduce(part, s.rb * s.js, DP, B, D, theta, g_theta, st);
+  return ko_bil_reduce(part, w.s.rb * w.s.js, w.DP, B, D, theta, g_theta, st);
 }
 
 size_t lo_kernel_points_grad_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t D, int64_t t) {
   if (!ko_args_ok(B, M, N, D, t) || !ko_shape_ok(B, M, N, D) || t > 0x7fffffff) return 0;
-  return measured(kKoTail, [&](Arena& ar) { ko_pgrad_layout(ar, B, M, N, D); });
+  return measured(kKoTail, [&](Arena& ar) { ko_split_layout<float>(ar, B, M, N, D); });
 }
 
 int lo_kernel_points_grad_f32(const float* x1, const float* x2, const float* theta, int32_t family, int64_t B, int64_t M,
@@ -505,27 +410,22 @@ int lo_kernel_points_grad_f32(const float* x1, const float* x2, const float* the
   if (!ko_shape_ok(B, M, N, D) || t > 0x7fffffff) return LO_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   Arena ar(ws, ws_bytes, kKoTail);
-  float* part = ko_pgrad_layout(ar, B, M, N, D);
+  float* part = ko_split_layout<float>(ar, B, M, N, D);  // [js, B, M, D]
   if (!ws || !ar.ok) return LO_ERR_WORKSPACE;
-  const KoShape s = ko_shape(B, M, N);
-  const int DP = ko_padded_dim(D);
-  const dim3 grid((unsigned)s.rb, (unsigned)B, (unsigned)s.js);
-  float* out = s.js > 1 ? part : g_x1;
+  const KoSweep w(B, M, N, D);
+  float* out = w.s.js > 1 ? part : g_x1;
   LO_PROF_BEGIN("k_kernel_pgrad", st);
-#define KO_FAM(F_) ko_pgrad_launch_dp<F_>(DP, grid, st, x1, x2, theta, (int)M, (int)N, (int)D, U, V, (int)t, out, s.jchunk)
-  switch (family) {
-    case LO_KERNEL_RBF: KO_FAM(LO_KERNEL_RBF); break;
-    case LO_KERNEL_MATERN12: KO_FAM(LO_KERNEL_MATERN12); break;
-    case LO_KERNEL_MATERN32: KO_FAM(LO_KERNEL_MATERN32); break;
-    default: KO_FAM(LO_KERNEL_MATERN52); break;
-  }
-#undef KO_FAM
+  ko_dispatch(family, w.DP, [&](auto F, auto P) {
+    hipLaunchKernelGGL((k_kernel_pgrad<F(), P()>), w.grid, dim3(kThreads), 0, st, x1, x2, theta, (int)M, (int)N, (int)D, U,
+                       V, (int)t, out, w.s.jchunk);
+  });
   LO_PROF_END(st);
   LO_LAUNCH_CHECK();
-  if (s.js > 1)  // the splits in ascending order (the reduction of the product with D as its columns and no diagonal)
-    return ko_reduce_splits("k_kernel_pgrad_reduce", part, s.js, (size_t)M * D, (size_t)B * M * D, (int)D, nullptr,
+  if (w.s.js > 1)  // the splits in ascending order (the reduction of the product with D as its columns and no diagonal)
+    return ko_reduce_splits("k_kernel_pgrad_reduce", part, w.s.js, (size_t)M * D, (size_t)B * M * D, (int)D, nullptr,
                             LO_DIAG_NONE, nullptr, g_x1, nullptr, st);
   return LO_OK;
 }
 
 }  // extern "C"
+

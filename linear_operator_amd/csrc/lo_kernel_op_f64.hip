@@ -21,8 +21,8 @@
 
 namespace lo {
 
-// columns of v per sweep: 1 / 4 / 8 (DP = 32: 1 / 4 -- the point alone is 64 VGPRs there)
-inline int ko64_col_chunk(int64_t c, int DP) { return c == 1 ? 1 : ((c <= 4 || DP == 32) ? 4 : 8); }
+// (columns of v per sweep: ko64_col_chunk / ko64_cols of lo_kernel_shape.h)
+
 // columns s of U / V per sweep of the derivatives
 template <int DP>
 constexpr int ko64_ts() {
@@ -322,96 +322,32 @@ static int ko64_reduce_splits(const char* prof_name, const double* part, int js,
   return LO_OK;
 }
 
-#define KO64_MV_ARGS x1, x2, theta, M, N, D, v, c, d, dmode, accumulate, y, part, jchunk
-template <int FAMILY, int DP>
-static void ko64_mv_launch_cc(int CC, dim3 grid, hipStream_t st, const double* x1, const double* x2, const double* theta,
-                              int M, int N, int D, const double* v, int c, const double* d, int dmode, int accumulate,
-                              double* y, double* part, int jchunk) {
-  if (CC == 1) {
-    hipLaunchKernelGGL((k64_kernel_mv<FAMILY, DP, 1>), grid, dim3(kThreads), 0, st, KO64_MV_ARGS);
-  } else if (CC == 4) {
-    hipLaunchKernelGGL((k64_kernel_mv<FAMILY, DP, 4>), grid, dim3(kThreads), 0, st, KO64_MV_ARGS);
-  } else {
-    if constexpr (DP < 32) hipLaunchKernelGGL((k64_kernel_mv<FAMILY, DP, 8>), grid, dim3(kThreads), 0, st, KO64_MV_ARGS);
-  }
-}
-
-template <int FAMILY>
-static void ko64_mv_launch_dp(int DP, int CC, dim3 grid, hipStream_t st, const double* x1, const double* x2,
-                              const double* theta, int M, int N, int D, const double* v, int c, const double* d,
-                              int dmode, int accumulate, double* y, double* part, int jchunk) {
-#define KO64_MV(DP_) ko64_mv_launch_cc<FAMILY, DP_>(CC, grid, st, KO64_MV_ARGS)
-  switch (DP) {
-    case 4: KO64_MV(4); break;
-    case 8: KO64_MV(8); break;
-    case 16: KO64_MV(16); break;
-    default: KO64_MV(32); break;
-  }
-#undef KO64_MV
-}
-#undef KO64_MV_ARGS
-
-template <int FAMILY>
-static void ko64_bil_launch_dp(int DP, dim3 grid, hipStream_t st, const double* x1, const double* x2,
-                               const double* theta, int M, int N, int D, const double* U, const double* V, int t,
-                               double* part, int jchunk) {
-#define KO64_BIL(DP_) \
-  hipLaunchKernelGGL((k64_kernel_bil<FAMILY, DP_>), grid, dim3(kThreads), 0, st, x1, x2, theta, M, N, D, U, V, t, part, jchunk)
-  switch (DP) {
-    case 4: KO64_BIL(4); break;
-    case 8: KO64_BIL(8); break;
-    case 16: KO64_BIL(16); break;
-    default: KO64_BIL(32); break;
-  }
-#undef KO64_BIL
-}
-
-template <int FAMILY>
-static void ko64_pgrad_launch_dp(int DP, dim3 grid, hipStream_t st, const double* x1, const double* x2,
-                                 const double* theta, int M, int N, int D, const double* U, const double* V, int t,
-                                 double* out, int jchunk) {
-#define KO64_PG(DP_) \
-  hipLaunchKernelGGL((k64_kernel_pgrad<FAMILY, DP_>), grid, dim3(kThreads), 0, st, x1, x2, theta, M, N, D, U, V, t, out, jchunk)
-  switch (DP) {
-    case 4: KO64_PG(4); break;
-    case 8: KO64_PG(8); break;
-    case 16: KO64_PG(16); break;
-    default: KO64_PG(32); break;
-  }
-#undef KO64_PG
-}
-
 // the product on validated arguments; part: [js, B, M, c] doubles when ko_shape(B, M, N).js > 1 (else unused)
 int kernel_mv_run_f64(const double* x1, const double* x2, const double* theta, int family, int64_t B, int64_t M,
                       int64_t N, int64_t D, const double* v, int64_t c, const double* d, int dmode, int accumulate,
                       double* y, double* part, hipStream_t st) {
-  const KoShape s = ko_shape(B, M, N);
-  const int DP = ko_padded_dim(D), CC = ko64_col_chunk(c, DP);
-  const dim3 grid((unsigned)s.rb, (unsigned)B, (unsigned)s.js);
-  double* p = s.js > 1 ? part : nullptr;
+  const KoSweep w(B, M, N, D);
+  const int CC = ko64_col_chunk(c, w.DP);
+  double* p = w.s.js > 1 ? part : nullptr;
   if (M != N) dmode = LO_DIAG_NONE;
   LO_PROF_BEGIN("k64_kernel_mv", st);
-#define KO64_FAM(F_) \
-  ko64_mv_launch_dp<F_>(DP, CC, grid, st, x1, x2, theta, (int)M, (int)N, (int)D, v, (int)c, d, dmode, accumulate, y, p, s.jchunk)
-  switch (family) {
-    case LO_KERNEL_RBF: KO64_FAM(LO_KERNEL_RBF); break;
-    case LO_KERNEL_MATERN12: KO64_FAM(LO_KERNEL_MATERN12); break;
-    case LO_KERNEL_MATERN32: KO64_FAM(LO_KERNEL_MATERN32); break;
-    default: KO64_FAM(LO_KERNEL_MATERN52); break;
-  }
-#undef KO64_FAM
+  ko_dispatch(family, w.DP, [&](auto F, auto P) {  // (the column list depends on the padded dimension)
+    ko_pick(ko64_cols<P()>{}, CC, [&](auto C) {
+      hipLaunchKernelGGL((k64_kernel_mv<F(), P(), C()>), w.grid, dim3(kThreads), 0, st, x1, x2, theta, (int)M, (int)N,
+                         (int)D, v, (int)c, d, dmode, accumulate, y, p, w.s.jchunk);
+    });
+  });
   LO_PROF_END(st);
   LO_LAUNCH_CHECK();
   if (p)
-    return ko64_reduce_splits("k64_kernel_mv_reduce", p, s.js, (size_t)M * c, (size_t)B * M * c, (int)c, d, dmode,
+    return ko64_reduce_splits("k64_kernel_mv_reduce", p, w.s.js, (size_t)M * c, (size_t)B * M * c, (int)c, d, dmode,
                               accumulate, v, y, st);
   return LO_OK;
 }
 
 // the one layout of the product's workspace: the partials of a split member
 double* kernel_mv_layout_f64(Arena& ar, int64_t B, int64_t M, int64_t N, int64_t c) {
-  const KoShape s = ko_shape(B, M, N);
-  return s.js > 1 ? ar.take<double>((size_t)s.js * B * M * c) : nullptr;
+  return ko_split_layout<double>(ar, B, M, N, c);
 }
 
 // LO_OP_KERNEL_DIAG of lo_matvec_f64 (A0 = X, A1 = theta: doubles), validated as the fp32 plan validates it
@@ -419,17 +355,6 @@ int kernel_desc_check_f64(const lo_op_desc* op, int64_t c) {
   if (!op->A0 || !op->A1 || op->R < 1 || !ko_family_ok(op->n2)) return LO_ERR_BADARG;
   if (!ko_shape_ok(op->B, op->N, op->N, op->R) || c > 0x7fffffff) return LO_ERR_UNSUPPORTED;
   return LO_OK;
-}
-
-static double* ko64_bil_layout(Arena& ar, int64_t B, int64_t M, int64_t N, int64_t D) {
-  const KoShape s = ko_shape(B, M, N);
-  return ar.take<double>((size_t)B * s.rb * s.js * (ko_padded_dim(D) + 1));
-}
-
-// the one layout of the points' gradient: the partials [js, B, M, D] of a split member
-static double* ko64_pgrad_layout(Arena& ar, int64_t B, int64_t M, int64_t N, int64_t D) {
-  const KoShape s = ko_shape(B, M, N);
-  return s.js > 1 ? ar.take<double>((size_t)s.js * B * M * D) : nullptr;
 }
 
 }  // namespace lo
@@ -448,8 +373,7 @@ int lo_kernel_mv_f64(const double* x1, const double* x2, const double* theta, in
                      void* ws, size_t ws_bytes, void* stream) {
   if (!x1 || !x2 || !theta || !v || !y || v == y || !ko_args_ok(B, M, N, D, c) || !ko_family_ok(family))
     return LO_ERR_BADARG;
-  if (diag_mode != LO_DIAG_NONE && diag_mode != LO_DIAG_FULL && diag_mode != LO_DIAG_CONST) return LO_ERR_BADARG;
-  if (diag_mode != LO_DIAG_NONE && M == N && !d) return LO_ERR_BADARG;
+  if (!ko_diag_ok(diag_mode, d, M == N)) return LO_ERR_BADARG;
   if (!ko_shape_ok(B, M, N, D) || c > 0x7fffffff) return LO_ERR_UNSUPPORTED;
   Arena ar(ws, ws_bytes, kKoTail);
   double* part = kernel_mv_layout_f64(ar, B, M, N, c);
@@ -459,7 +383,7 @@ int lo_kernel_mv_f64(const double* x1, const double* x2, const double* theta, in
 
 size_t lo_kernel_bilinear_f64_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t D, int64_t t) {
   if (!ko_args_ok(B, M, N, D, t) || !ko_shape_ok(B, M, N, D) || t > 0x7fffffff) return 0;
-  return measured(kKoTail, [&](Arena& ar) { ko64_bil_layout(ar, B, M, N, D); });
+  return measured(kKoTail, [&](Arena& ar) { ko_bil_layout<double>(ar, B, M, N, D); });
 }
 
 int lo_kernel_bilinear_f64(const double* x1, const double* x2, const double* theta, int32_t family, int64_t B, int64_t M,
@@ -470,23 +394,17 @@ int lo_kernel_bilinear_f64(const double* x1, const double* x2, const double* the
   if (!ko_shape_ok(B, M, N, D) || t > 0x7fffffff) return LO_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   Arena ar(ws, ws_bytes, kKoTail);
-  double* part = ko64_bil_layout(ar, B, M, N, D);
+  double* part = ko_bil_layout<double>(ar, B, M, N, D);
   if (!ws || !ar.ok) return LO_ERR_WORKSPACE;
-  const KoShape s = ko_shape(B, M, N);
-  const int DP = ko_padded_dim(D);
-  const dim3 grid((unsigned)s.rb, (unsigned)B, (unsigned)s.js);
+  const KoSweep w(B, M, N, D);
   LO_PROF_BEGIN("k64_kernel_bil", st);
-#define KO64_FAM(F_) ko64_bil_launch_dp<F_>(DP, grid, st, x1, x2, theta, (int)M, (int)N, (int)D, U, V, (int)t, part, s.jchunk)
-  switch (family) {
-    case LO_KERNEL_RBF: KO64_FAM(LO_KERNEL_RBF); break;
-    case LO_KERNEL_MATERN12: KO64_FAM(LO_KERNEL_MATERN12); break;
-    case LO_KERNEL_MATERN32: KO64_FAM(LO_KERNEL_MATERN32); break;
-    default: KO64_FAM(LO_KERNEL_MATERN52); break;
-  }
-#undef KO64_FAM
+  ko_dispatch(family, w.DP, [&](auto F, auto P) {
+    hipLaunchKernelGGL((k64_kernel_bil<F(), P()>), w.grid, dim3(kThreads), 0, st, x1, x2, theta, (int)M, (int)N, (int)D, U,
+                       V, (int)t, part, w.s.jchunk);
+  });
   LO_PROF_END(st);
   LO_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k64_kernel_bil_reduce, dim3((unsigned)B), dim3(64), 0, st, part, s.rb * s.js, DP, (int)D, theta,
+  hipLaunchKernelGGL(k64_kernel_bil_reduce, dim3((unsigned)B), dim3(64), 0, st, part, w.s.rb * w.s.js, w.DP, (int)D, theta,
                      g_theta);
   LO_LAUNCH_CHECK();
   return LO_OK;
@@ -494,7 +412,7 @@ int lo_kernel_bilinear_f64(const double* x1, const double* x2, const double* the
 
 size_t lo_kernel_points_grad_f64_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t D, int64_t t) {
   if (!ko_args_ok(B, M, N, D, t) || !ko_shape_ok(B, M, N, D) || t > 0x7fffffff) return 0;
-  return measured(kKoTail, [&](Arena& ar) { ko64_pgrad_layout(ar, B, M, N, D); });
+  return measured(kKoTail, [&](Arena& ar) { ko_split_layout<double>(ar, B, M, N, D); });
 }
 
 int lo_kernel_points_grad_f64(const double* x1, const double* x2, const double* theta, int32_t family, int64_t B,
@@ -505,27 +423,22 @@ int lo_kernel_points_grad_f64(const double* x1, const double* x2, const double* 
   if (!ko_shape_ok(B, M, N, D) || t > 0x7fffffff) return LO_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   Arena ar(ws, ws_bytes, kKoTail);
-  double* part = ko64_pgrad_layout(ar, B, M, N, D);
+  double* part = ko_split_layout<double>(ar, B, M, N, D);  // [js, B, M, D]
   if (!ws || !ar.ok) return LO_ERR_WORKSPACE;
-  const KoShape s = ko_shape(B, M, N);
-  const int DP = ko_padded_dim(D);
-  const dim3 grid((unsigned)s.rb, (unsigned)B, (unsigned)s.js);
-  double* out = s.js > 1 ? part : g_x1;
+  const KoSweep w(B, M, N, D);
+  double* out = w.s.js > 1 ? part : g_x1;
   LO_PROF_BEGIN("k64_kernel_pgrad", st);
-#define KO64_FAM(F_) ko64_pgrad_launch_dp<F_>(DP, grid, st, x1, x2, theta, (int)M, (int)N, (int)D, U, V, (int)t, out, s.jchunk)
-  switch (family) {
-    case LO_KERNEL_RBF: KO64_FAM(LO_KERNEL_RBF); break;
-    case LO_KERNEL_MATERN12: KO64_FAM(LO_KERNEL_MATERN12); break;
-    case LO_KERNEL_MATERN32: KO64_FAM(LO_KERNEL_MATERN32); break;
-    default: KO64_FAM(LO_KERNEL_MATERN52); break;
-  }
-#undef KO64_FAM
+  ko_dispatch(family, w.DP, [&](auto F, auto P) {
+    hipLaunchKernelGGL((k64_kernel_pgrad<F(), P()>), w.grid, dim3(kThreads), 0, st, x1, x2, theta, (int)M, (int)N, (int)D,
+                       U, V, (int)t, out, w.s.jchunk);
+  });
   LO_PROF_END(st);
   LO_LAUNCH_CHECK();
-  if (s.js > 1)  // the splits in ascending order (the reduction of the product with D as its columns and no diagonal)
-    return ko64_reduce_splits("k64_kernel_pgrad_reduce", part, s.js, (size_t)M * D, (size_t)B * M * D, (int)D, nullptr,
+  if (w.s.js > 1)  // the splits in ascending order (the reduction of the product with D as its columns and no diagonal)
+    return ko64_reduce_splits("k64_kernel_pgrad_reduce", part, w.s.js, (size_t)M * D, (size_t)B * M * D, (int)D, nullptr,
                               LO_DIAG_NONE, 0, nullptr, g_x1, st);
   return LO_OK;
 }
 
 }  // extern "C"
+

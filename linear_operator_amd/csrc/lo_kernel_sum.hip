@@ -463,9 +463,8 @@ struct KsMvBufs {
 
 // the one layout of the product's workspace
 static KsMvBufs ks_mv_layout(Arena& ar, int64_t B, int64_t M, int64_t N, int64_t T, int64_t c) {
-  const KoShape s = ko_shape(B, M, N);
   KsMvBufs b;
-  b.part = s.js > 1 ? ar.take<float>((size_t)s.js * B * M * c) : nullptr;
+  b.part = ko_split_layout<float>(ar, B, M, N, c);
   b.ytmp = (T > 1 && !ks_mv_fused(T, c)) ? ar.take<float>((size_t)B * M * c) : nullptr;
   return b;
 }
@@ -484,37 +483,26 @@ static int ksum_mv_run(const float* x1, const float* x2, const float* theta, uns
     }
     return LO_OK;
   }
-  const KoShape s = ko_shape(B, M, N);
-  const int DP = ko_padded_dim(D);
-  const dim3 grid((unsigned)s.rb, (unsigned)B, (unsigned)s.js);
-  const size_t lds = ks_lds_bytes(T, DP, kKsCC);
-  float* p = s.js > 1 ? bufs.part : nullptr;
+  const KoSweep w(B, M, N, D);
+  const size_t lds = ks_lds_bytes(T, w.DP, kKsCC);
+  float* p = w.s.js > 1 ? bufs.part : nullptr;
   LO_PROF_BEGIN("k_ksum_mv", st);
-#define KS_MV(DP_)                                                                                                     \
-  hipLaunchKernelGGL((k_ksum_mv<DP_, kKsCC>), grid, dim3(kThreads), lds, st, x1, x2, theta, fams, T, (int)M, (int)N, (int)D, \
-                     v, (int)c, d, dmode, y, p, s.jchunk, stop)
-  switch (DP) {
-    case 4: KS_MV(4); break;
-    case 8: KS_MV(8); break;
-    case 16: KS_MV(16); break;
-    default: KS_MV(32); break;
-  }
-#undef KS_MV
+  ko_pick(ko_dims{}, w.DP, [&](auto P) {
+    hipLaunchKernelGGL((k_ksum_mv<P(), kKsCC>), w.grid, dim3(kThreads), lds, st, x1, x2, theta, fams, T, (int)M, (int)N,
+                       (int)D, v, (int)c, d, dmode, y, p, w.s.jchunk, stop);
+  });
   LO_PROF_END(st);
   LO_LAUNCH_CHECK();
   if (p)
-    return ko_reduce_splits("k_ksum_mv_reduce", p, s.js, (size_t)M * c, (size_t)B * M * c, (int)c, d, dmode, v, y, stop, st);
+    return ko_reduce_splits("k_ksum_mv_reduce", p, w.s.js, (size_t)M * c, (size_t)B * M * c, (int)c, d, dmode, v, y, stop,
+                            st);
   return LO_OK;
 }
 
-// the layouts of the other two workspaces: the partials of every workgroup (derivative) and of a split member (points)
+// the layout of the derivative's workspace: the partials [T, DP + 1] of every workgroup
 static float* ks_bil_layout(Arena& ar, int64_t B, int64_t M, int64_t N, int64_t D, int64_t T) {
   const KoShape s = ko_shape(B, M, N);
   return ar.take<float>((size_t)B * s.rb * s.js * T * (ko_padded_dim(D) + 1));
-}
-static float* ks_pgrad_layout(Arena& ar, int64_t B, int64_t M, int64_t N, int64_t D) {
-  const KoShape s = ko_shape(B, M, N);
-  return s.js > 1 ? ar.take<float>((size_t)s.js * B * M * D) : nullptr;
 }
 
 int kernel_sum_plan(MatvecPlan* pl, Arena* ar, hipStream_t) {
@@ -556,8 +544,7 @@ int lo_kernel_sum_mv_f32(const float* x1, const float* x2, const float* theta, c
   if (!x1 || !x2 || !theta || !families || !v || !y || !ko_args_ok(B, M, N, D, c) || !ks_terms_ok(T)) return LO_ERR_BADARG;
   const int64_t fams = ks_pack(families, T);
   if (fams < 0) return LO_ERR_BADARG;
-  if (diag_mode != LO_DIAG_NONE && diag_mode != LO_DIAG_FULL && diag_mode != LO_DIAG_CONST) return LO_ERR_BADARG;
-  if (diag_mode != LO_DIAG_NONE && M == N && !d) return LO_ERR_BADARG;
+  if (!ko_diag_ok(diag_mode, d, M == N)) return LO_ERR_BADARG;
   if (!ko_shape_ok(B, M, N, D) || c > 0x7fffffff) return LO_ERR_UNSUPPORTED;
   Arena ar(ws, ws_bytes, kKoTail);
   const KsMvBufs bufs = ks_mv_layout(ar, B, M, N, T, c);
@@ -583,36 +570,28 @@ int lo_kernel_sum_bilinear_f32(const float* x1, const float* x2, const float* th
   Arena ar(ws, ws_bytes, kKoTail);
   float* part = ks_bil_layout(ar, B, M, N, D, T);
   if (!ws || !ar.ok) return LO_ERR_WORKSPACE;
-  const KoShape s = ko_shape(B, M, N);
-  const int DP = ko_padded_dim(D);
-  const int TT = DP == 32 ? 2 : 4;  // (ks_bil_terms<DP>())
-  const dim3 grid((unsigned)s.rb, (unsigned)B, (unsigned)s.js);
+  const KoSweep w(B, M, N, D);
+  const int TT = w.DP == 32 ? 2 : 4;  // (ks_bil_terms<DP>())
   for (int t0 = 0; t0 < (int)T; t0 += TT) {  // (one sweep unless 16 < D and T > 2)
     const int nt = std::min<int>(TT, (int)T - t0);
-    const size_t lds = ks_lds_bytes(nt, DP, kKoTS);
+    const size_t lds = ks_lds_bytes(nt, w.DP, kKoTS);
     LO_PROF_BEGIN("k_ksum_bil", st);
-#define KS_BIL(DP_)                                                                                                        \
-  hipLaunchKernelGGL((k_ksum_bil<DP_>), grid, dim3(kThreads), lds, st, x1, x2, theta, (unsigned)fams, (int)T, t0, nt, (int)M, \
-                     (int)N, (int)D, U, V, (int)t, part, s.jchunk)
-    switch (DP) {
-      case 4: KS_BIL(4); break;
-      case 8: KS_BIL(8); break;
-      case 16: KS_BIL(16); break;
-      default: KS_BIL(32); break;
-    }
-#undef KS_BIL
+    ko_pick(ko_dims{}, w.DP, [&](auto P) {
+      hipLaunchKernelGGL((k_ksum_bil<P()>), w.grid, dim3(kThreads), lds, st, x1, x2, theta, (unsigned)fams, (int)T, t0, nt,
+                         (int)M, (int)N, (int)D, U, V, (int)t, part, w.s.jchunk);
+    });
     LO_PROF_END(st);
     LO_LAUNCH_CHECK();
   }
-  hipLaunchKernelGGL(k_ksum_bil_reduce, dim3((unsigned)B), dim3(kThreads), 0, st, part, s.rb * s.js, DP, (int)D, (int)T,
-                     theta, g_theta);
+  hipLaunchKernelGGL(k_ksum_bil_reduce, dim3((unsigned)B), dim3(kThreads), 0, st, part, w.s.rb * w.s.js, w.DP, (int)D,
+                     (int)T, theta, g_theta);
   LO_LAUNCH_CHECK();
   return LO_OK;
 }
 
 size_t lo_kernel_sum_points_grad_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t D, int64_t T, int64_t t) {
   if (!ko_args_ok(B, M, N, D, t) || !ks_terms_ok(T) || !ko_shape_ok(B, M, N, D) || t > 0x7fffffff) return 0;
-  return measured(kKoTail, [&](Arena& ar) { ks_pgrad_layout(ar, B, M, N, D); });
+  return measured(kKoTail, [&](Arena& ar) { ko_split_layout<float>(ar, B, M, N, D); });
 }
 
 int lo_kernel_sum_points_grad_f32(const float* x1, const float* x2, const float* theta, const int32_t* families, int64_t T,
@@ -625,28 +604,20 @@ int lo_kernel_sum_points_grad_f32(const float* x1, const float* x2, const float*
   if (!ko_shape_ok(B, M, N, D) || t > 0x7fffffff) return LO_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   Arena ar(ws, ws_bytes, kKoTail);
-  float* part = ks_pgrad_layout(ar, B, M, N, D);
+  float* part = ko_split_layout<float>(ar, B, M, N, D);  // [js, B, M, D]
   if (!ws || !ar.ok) return LO_ERR_WORKSPACE;
-  const KoShape s = ko_shape(B, M, N);
-  const int DP = ko_padded_dim(D);
-  const dim3 grid((unsigned)s.rb, (unsigned)B, (unsigned)s.js);
-  const size_t lds = ks_lds_bytes((int)T, DP, kKoTS);
-  float* out = s.js > 1 ? part : g_x1;
+  const KoSweep w(B, M, N, D);
+  const size_t lds = ks_lds_bytes((int)T, w.DP, kKoTS);
+  float* out = w.s.js > 1 ? part : g_x1;
   LO_PROF_BEGIN("k_ksum_pgrad", st);
-#define KS_PG(DP_)                                                                                                     \
-  hipLaunchKernelGGL((k_ksum_pgrad<DP_>), grid, dim3(kThreads), lds, st, x1, x2, theta, (unsigned)fams, (int)T, (int)M, \
-                     (int)N, (int)D, U, V, (int)t, out, s.jchunk)
-  switch (DP) {
-    case 4: KS_PG(4); break;
-    case 8: KS_PG(8); break;
-    case 16: KS_PG(16); break;
-    default: KS_PG(32); break;
-  }
-#undef KS_PG
+  ko_pick(ko_dims{}, w.DP, [&](auto P) {
+    hipLaunchKernelGGL((k_ksum_pgrad<P()>), w.grid, dim3(kThreads), lds, st, x1, x2, theta, (unsigned)fams, (int)T, (int)M,
+                       (int)N, (int)D, U, V, (int)t, out, w.s.jchunk);
+  });
   LO_PROF_END(st);
   LO_LAUNCH_CHECK();
-  if (s.js > 1)  // the splits in ascending order
-    return ko_reduce_splits("k_ksum_pgrad_reduce", part, s.js, (size_t)M * D, (size_t)B * M * D, (int)D, nullptr,
+  if (w.s.js > 1)  // the splits in ascending order
+    return ko_reduce_splits("k_ksum_pgrad_reduce", part, w.s.js, (size_t)M * D, (size_t)B * M * D, (int)D, nullptr,
                             LO_DIAG_NONE, nullptr, g_x1, nullptr, st);
   return LO_OK;
 }

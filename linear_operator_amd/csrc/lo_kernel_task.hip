@@ -368,107 +368,30 @@ __global__ __launch_bounds__(kThreads) void k_kernel_task_pgrad(const float* __r
   }
 }
 
-#define TK_DP_SWITCH(DP_VAR, CALL) \
-  switch (DP_VAR) {                \
-    case 4: CALL(4); break;        \
-    case 8: CALL(8); break;        \
-    case 16: CALL(16); break;      \
-    default: CALL(32); break;      \
-  }
-#define TK_FAMILY_SWITCH(FAMILY_VAR, CALL)                      \
-  switch (FAMILY_VAR) {                                         \
-    case LO_KERNEL_RBF: CALL(LO_KERNEL_RBF); break;             \
-    case LO_KERNEL_MATERN12: CALL(LO_KERNEL_MATERN12); break;   \
-    case LO_KERNEL_MATERN32: CALL(LO_KERNEL_MATERN32); break;   \
-    default: CALL(LO_KERNEL_MATERN52); break;                   \
-  }
-
-template <int FAMILY, int DP>
-static void tk_mv_launch_cc(int CC, dim3 grid, hipStream_t st, const float* x1, const float* x2, const float* theta,
-                            const float* task, int M, int N, int D, int T, const float* v, int c, const float* d,
-                            int dmode, float* y, float* part, int jchunk, const int* stop) {
-#define TK_MV(CC_)                                                                                                     \
-  hipLaunchKernelGGL((k_kernel_task_mv<FAMILY, DP, CC_>), grid, dim3(kThreads), 0, st, x1, x2, theta, task, M, N, D, T, \
-                     v, c, d, dmode, y, part, jchunk, stop)
-  switch (CC) {
-    case 1: TK_MV(1); break;
-    case 4: TK_MV(4); break;
-    default: TK_MV(16); break;
-  }
-#undef TK_MV
-}
-
-template <int FAMILY>
-static void tk_mv_launch_dp(int DP, int CC, dim3 grid, hipStream_t st, const float* x1, const float* x2,
-                            const float* theta, const float* task, int M, int N, int D, int T, const float* v, int c,
-                            const float* d, int dmode, float* y, float* part, int jchunk, const int* stop) {
-#define TK_MV(DP_) \
-  tk_mv_launch_cc<FAMILY, DP_>(CC, grid, st, x1, x2, theta, task, M, N, D, T, v, c, d, dmode, y, part, jchunk, stop)
-  TK_DP_SWITCH(DP, TK_MV)
-#undef TK_MV
-}
-
-template <int FAMILY>
-static void tk_bil_launch_dp(int DP, dim3 grid, hipStream_t st, const float* x1, const float* x2, const float* theta,
-                             const float* task, int M, int N, int D, int T, const float* U, const float* V, int t,
-                             float* part, int jchunk) {
-#define TK_BIL(DP_)                                                                                                     \
-  hipLaunchKernelGGL((k_kernel_task_bil<FAMILY, DP_>), grid, dim3(kThreads), 0, st, x1, x2, theta, task, M, N, D, T, U, \
-                     V, t, part, jchunk)
-  TK_DP_SWITCH(DP, TK_BIL)
-#undef TK_BIL
-}
-
-template <int FAMILY>
-static void tk_pgrad_launch_dp(int DP, dim3 grid, hipStream_t st, const float* x1, const float* x2, const float* theta,
-                               const float* task, int M, int N, int D, int T, const float* U, const float* V, int t,
-                               float* out, int jchunk) {
-#define TK_PG(DP_)                                                                                                        \
-  hipLaunchKernelGGL((k_kernel_task_pgrad<FAMILY, DP_>), grid, dim3(kThreads), 0, st, x1, x2, theta, task, M, N, D, T, U, \
-                     V, t, out, jchunk)
-  TK_DP_SWITCH(DP, TK_PG)
-#undef TK_PG
-}
-
 // the product on validated arguments; part: [js, B, M, c] floats when ko_shape(B, M, N).js > 1 (else unused)
 static int tk_mv_run(const float* x1, const float* x2, const float* theta, const float* task, int family, int64_t B,
                      int64_t M, int64_t N, int64_t D, int64_t T, const float* v, int64_t c, const float* d, int dmode,
                      float* y, float* part, const int* stop, hipStream_t st) {
-  const KoShape s = ko_shape(B, M, N);
-  const int DP = ko_padded_dim(D), CC = ko_col_chunk(c);
-  const dim3 grid((unsigned)s.rb, (unsigned)B, (unsigned)s.js);
-  float* p = s.js > 1 ? part : nullptr;
+  const KoSweep w(B, M, N, D);
+  float* p = w.s.js > 1 ? part : nullptr;
   if (M != N) dmode = LO_DIAG_NONE;
   LO_PROF_BEGIN("k_kernel_task_mv", st);
-#define TK_FAM(F_)                                                                                                      \
-  tk_mv_launch_dp<F_>(DP, CC, grid, st, x1, x2, theta, task, (int)M, (int)N, (int)D, (int)T, v, (int)c, d, dmode, y, p, \
-                      s.jchunk, stop)
-  TK_FAMILY_SWITCH(family, TK_FAM)
-#undef TK_FAM
+  ko_dispatch(family, w.DP, ko_cols{}, ko_col_chunk(c), [&](auto F, auto P, auto C) {
+    hipLaunchKernelGGL((k_kernel_task_mv<F(), P(), C()>), w.grid, dim3(kThreads), 0, st, x1, x2, theta, task, (int)M,
+                       (int)N, (int)D, (int)T, v, (int)c, d, dmode, y, p, w.s.jchunk, stop);
+  });
   LO_PROF_END(st);
   LO_LAUNCH_CHECK();
   if (p)
-    return ko_reduce_splits("k_kernel_task_mv_reduce", p, s.js, (size_t)M * c, (size_t)B * M * c, (int)c, d, dmode, v, y,
+    return ko_reduce_splits("k_kernel_task_mv_reduce", p, w.s.js, (size_t)M * c, (size_t)B * M * c, (int)c, d, dmode, v, y,
                             stop, st);
   return LO_OK;
-}
-
-// the one layout of the product's workspace: the partials of a split member
-static float* tk_mv_layout(Arena& ar, int64_t B, int64_t M, int64_t N, int64_t c) {
-  const KoShape s = ko_shape(B, M, N);
-  return s.js > 1 ? ar.take<float>((size_t)s.js * B * M * c) : nullptr;
 }
 
 // the workgroups' partials [B, rb js, DP + T T] of the derivative
 static float* tk_bil_layout(Arena& ar, int64_t B, int64_t M, int64_t N, int64_t D, int64_t T) {
   const KoShape s = ko_shape(B, M, N);
   return ar.take<float>((size_t)B * s.rb * s.js * (ko_padded_dim(D) + T * T));
-}
-
-// the one layout of the points' gradient: the partials [js, B, M, D + 1] of a split member
-static float* tk_pgrad_layout(Arena& ar, int64_t B, int64_t M, int64_t N, int64_t D) {
-  const KoShape s = ko_shape(B, M, N);
-  return s.js > 1 ? ar.take<float>((size_t)s.js * B * M * (D + 1)) : nullptr;
 }
 
 int kernel_task_desc_check(const lo_op_desc* op) {
@@ -481,7 +404,7 @@ int kernel_task_plan(MatvecPlan* pl, Arena* ar, hipStream_t) {
   const lo_op_desc& op = pl->op;
   if (const int rc = kernel_task_desc_check(&op)) return rc;
   if (!tk_shape_ok(op.B, op.N, op.N, op.R) || pl->c > 0x7fffffff) return LO_ERR_UNSUPPORTED;
-  pl->kt.part = tk_mv_layout(*ar, op.B, op.N, op.N, pl->c);
+  pl->kt.part = ko_split_layout<float>(*ar, op.B, op.N, op.N, pl->c);
   return LO_OK;
 }
 
@@ -504,7 +427,7 @@ extern "C" {
 
 size_t lo_kernel_task_mv_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t D, int64_t T, int64_t c) {
   if (!tk_sizes_ok(B, M, N, D, T, c)) return 0;
-  return measured(kKoTail, [&](Arena& ar) { tk_mv_layout(ar, B, M, N, c); });
+  return measured(kKoTail, [&](Arena& ar) { ko_split_layout<float>(ar, B, M, N, c); });
 }
 
 int lo_kernel_task_mv_f32(const float* x1, const float* x2, const float* theta, const float* task, int32_t family,
@@ -512,11 +435,10 @@ int lo_kernel_task_mv_f32(const float* x1, const float* x2, const float* theta, 
                           int32_t diag_mode, float* y, void* ws, size_t ws_bytes, void* stream) {
   if (!x1 || !x2 || !theta || !task || !v || !y || !ko_args_ok(B, M, N, D, c) || !ko_family_ok(family) || T < 1)
     return LO_ERR_BADARG;
-  if (diag_mode != LO_DIAG_NONE && diag_mode != LO_DIAG_FULL && diag_mode != LO_DIAG_CONST) return LO_ERR_BADARG;
-  if (diag_mode != LO_DIAG_NONE && M == N && !d) return LO_ERR_BADARG;
+  if (!ko_diag_ok(diag_mode, d, M == N)) return LO_ERR_BADARG;
   if (!tk_sizes_ok(B, M, N, D, T, c)) return LO_ERR_UNSUPPORTED;
   Arena ar(ws, ws_bytes, kKoTail);
-  float* part = tk_mv_layout(ar, B, M, N, c);
+  float* part = ko_split_layout<float>(ar, B, M, N, c);
   if (!ws || !ar.ok) return LO_ERR_WORKSPACE;
   return tk_mv_run(x1, x2, theta, task, family, B, M, N, D, T, v, c, d, diag_mode, y, part, nullptr, (hipStream_t)stream);
 }
@@ -537,25 +459,23 @@ int lo_kernel_task_bilinear_f32(const float* x1, const float* x2, const float* t
   Arena ar(ws, ws_bytes, kKoTail);
   float* part = tk_bil_layout(ar, B, M, N, D, T);
   if (!ws || !ar.ok) return LO_ERR_WORKSPACE;
-  const KoShape s = ko_shape(B, M, N);
-  const int DP = ko_padded_dim(D);
-  const dim3 grid((unsigned)s.rb, (unsigned)B, (unsigned)s.js);
+  const KoSweep w(B, M, N, D);
   LO_PROF_BEGIN("k_kernel_task_bil", st);
-#define TK_FAM(F_) \
-  tk_bil_launch_dp<F_>(DP, grid, st, x1, x2, theta, task, (int)M, (int)N, (int)D, (int)T, U, V, (int)t, part, s.jchunk)
-  TK_FAMILY_SWITCH(family, TK_FAM)
-#undef TK_FAM
+  ko_dispatch(family, w.DP, [&](auto F, auto P) {
+    hipLaunchKernelGGL((k_kernel_task_bil<F(), P()>), w.grid, dim3(kThreads), 0, st, x1, x2, theta, task, (int)M, (int)N,
+                       (int)D, (int)T, U, V, (int)t, part, w.s.jchunk);
+  });
   LO_PROF_END(st);
   LO_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_kernel_task_bil_reduce, dim3((unsigned)B), dim3(128), 0, st, part, s.rb * s.js, DP, (int)D, (int)T,
-                     theta, task, g_theta, g_task);
+  hipLaunchKernelGGL(k_kernel_task_bil_reduce, dim3((unsigned)B), dim3(128), 0, st, part, w.s.rb * w.s.js, w.DP, (int)D,
+                     (int)T, theta, task, g_theta, g_task);
   LO_LAUNCH_CHECK();
   return LO_OK;
 }
 
 size_t lo_kernel_task_points_grad_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t D, int64_t T, int64_t t) {
   if (!tk_sizes_ok(B, M, N, D, T, t)) return 0;
-  return measured(kKoTail, [&](Arena& ar) { tk_pgrad_layout(ar, B, M, N, D); });
+  return measured(kKoTail, [&](Arena& ar) { ko_split_layout<float>(ar, B, M, N, D + 1); });
 }
 
 int lo_kernel_task_points_grad_f32(const float* x1, const float* x2, const float* theta, const float* task, int32_t family,
@@ -566,23 +486,22 @@ int lo_kernel_task_points_grad_f32(const float* x1, const float* x2, const float
   if (!tk_sizes_ok(B, M, N, D, T, t)) return LO_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   Arena ar(ws, ws_bytes, kKoTail);
-  float* part = tk_pgrad_layout(ar, B, M, N, D);
+  float* part = ko_split_layout<float>(ar, B, M, N, D + 1);  // [js, B, M, D + 1]
   if (!ws || !ar.ok) return LO_ERR_WORKSPACE;
-  const KoShape s = ko_shape(B, M, N);
-  const int DP = ko_padded_dim(D);
-  const dim3 grid((unsigned)s.rb, (unsigned)B, (unsigned)s.js);
-  float* out = s.js > 1 ? part : g_x1;
+  const KoSweep w(B, M, N, D);
+  float* out = w.s.js > 1 ? part : g_x1;
   LO_PROF_BEGIN("k_kernel_task_pgrad", st);
-#define TK_FAM(F_) \
-  tk_pgrad_launch_dp<F_>(DP, grid, st, x1, x2, theta, task, (int)M, (int)N, (int)D, (int)T, U, V, (int)t, out, s.jchunk)
-  TK_FAMILY_SWITCH(family, TK_FAM)
-#undef TK_FAM
+  ko_dispatch(family, w.DP, [&](auto F, auto P) {
+    hipLaunchKernelGGL((k_kernel_task_pgrad<F(), P()>), w.grid, dim3(kThreads), 0, st, x1, x2, theta, task, (int)M, (int)N,
+                       (int)D, (int)T, U, V, (int)t, out, w.s.jchunk);
+  });
   LO_PROF_END(st);
   LO_LAUNCH_CHECK();
-  if (s.js > 1)  // the splits in ascending order (the reduction of the product with D + 1 as its columns and no diagonal)
-    return ko_reduce_splits("k_kernel_task_pgrad_reduce", part, s.js, (size_t)M * (D + 1), (size_t)B * M * (D + 1),
+  if (w.s.js > 1)  // the splits in ascending order (the reduction of the product with D + 1 as its columns and no diagonal)
+    return ko_reduce_splits("k_kernel_task_pgrad_reduce", part, w.s.js, (size_t)M * (D + 1), (size_t)B * M * (D + 1),
                             (int)(D + 1), nullptr, LO_DIAG_NONE, nullptr, g_x1, nullptr, st);
   return LO_OK;
 }
 
 }  // extern "C"
+

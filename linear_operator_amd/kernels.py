@@ -6,6 +6,7 @@ current stream; there is no other implementation behind these functions.
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import itertools
 import math
 import os
@@ -499,11 +500,63 @@ def kernel_theta(lengthscale: torch.Tensor, outputscale: torch.Tensor, batch, D:
 def _kernel_dtype(what: str, *tensors):
     """The one element type of a kernel entry point's operands (float32: the _f32 entry point, float64: its _f64 twin);
     mixed types raise."""
-    dtypes = {t.dtype for t in tensors if t is not None}
-    if len(dtypes) != 1 or next(iter(dtypes)) not in (torch.float32, torch.float64):
+    dtype = tensors[0].dtype
+    for t in tensors:
+        if t is not None and t.dtype != dtype:
+            dtype = None
+    if dtype != torch.float32 and dtype != torch.float64:
         raise _hip.HipExtensionError(f"{what}: the operands must all be float32 or all be float64, got "
-                                     f"{sorted(str(d) for d in dtypes)}")
-    return next(iter(dtypes))
+                                     f"{sorted({str(t.dtype) for t in tensors if t is not None})}")
+    return dtype
+
+
+def _kernel_args(what, x1, x2, theta, right, left=None, d=None, task=None, families=None, ids=0, block=1, twin=False):
+    """The checked operands of an entry point of the matrix-free kernel family: the points x1 [B, M, D] and x2 [B, N, D]
+    (`ids` = 1: one more column, the task id), theta [B, D + 1] (with `families`, the T codes of a sum: [B, T, D + 1]),
+    `task` = Bt [B, T, T] or None, the right operand [B, N block, cols] and, for the derivatives, the left one
+    [B, M block, cols] (`block` rows per point: T of the Kronecker kind, D + 1 of the gradient kind).  They are made
+    contiguous and, like the diagonal `d`, must be HIP tensors of one element type: float32, or all float64 where the
+    kind has _f64 twins (`twin`).  Returns (x1, x2, theta, extra, left, right, (B, M, N, D, T, cols), dtype) with
+    extra = Bt, or the families as the int32 array the sum's entry points take, or None."""
+    x1, x2, theta, right = x1.contiguous(), x2.contiguous(), theta.contiguous(), right.contiguous()
+    if left is not None:
+        left = left.contiguous()
+    extra, T = None, 0
+    if task is not None:
+        extra = task = task.contiguous()
+        T = task.shape[-1]
+    dtype = _kernel_dtype(what, x1, x2, theta, right, left, task, d) if twin else torch.float32
+    _hip.require_hip(x1, x2, theta, right, left, task, d, dtype=dtype)
+    if families is not None:
+        kernel_sum_pack_families(families)
+        T = len(families)
+        extra = (C.c_int32 * T)(*[int(f) for f in families])
+    B, M, D = x1.shape
+    N = x2.shape[-2] if x2.dim() == 3 else -1
+    cols = right.shape[-1]
+    if (x2.shape != (B, N, D) or theta.shape != ((B, D + 1 - ids) if families is None else (B, T, D + 1))
+            or right.shape != (B, N * block, cols) or (left is not None and left.shape != (B, M * block, cols))
+            or (task is not None and task.shape != (B, T, T))):
+        raise RuntimeError(f"{what}: x1 {tuple(x1.shape)}, x2 {tuple(x2.shape)}, theta {tuple(theta.shape)}"
+                           + (f" for {T} terms" if families is not None else "")
+                           + (f", task {tuple(task.shape)}" if task is not None else "")
+                           + (f", left operand {tuple(left.shape)}" if left is not None else "")
+                           + f", right operand {tuple(right.shape)}")
+    return x1, x2, theta, extra, left, right, (B, M, N, D - ids, T, cols), dtype
+
+
+def _kernel_diag(d: Optional[torch.Tensor], B: int, rows: int, const_diag: bool):
+    """(d as a product's entry point takes it, its LO_DIAG_* mode); without d: (None, LO_DIAG_NONE)."""
+    if d is None:
+        return None, _hip.LO_DIAG_NONE
+    return _diag_operand(d, B, rows, const_diag)[:2]
+
+
+@functools.lru_cache(maxsize=None)
+def _kernel_entry(stem: str, f64: bool):
+    """(name of the entry point `stem`_f32 or, float64, `stem`_f64 of the kernel family, its workspace sizer)."""
+    sizer = getattr(_hip.load(), f"{stem}_f64_workspace_bytes" if f64 else f"{stem}_workspace_bytes")
+    return (f"{stem}_f64" if f64 else f"{stem}_f32"), sizer
 
 
 def kernel_diag_descriptor(X: torch.Tensor, theta: torch.Tensor, family: int, d: Optional[torch.Tensor] = None,
@@ -528,23 +581,11 @@ def kernel_mv(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, family: i
               d: Optional[torch.Tensor] = None, const_diag: bool = False) -> torch.Tensor:
     """lo_kernel_mv_f32 (all operands float64: lo_kernel_mv_f64): y [B, M, c] = K(x1, x2) v (+ d o v when M == N and d is
     given), x1 [B, M, D], x2 [B, N, D], theta [B, D + 1], v [B, N, c].  A shape the kernel does not take raises."""
-    lib = _hip.load()
-    x1, x2, theta, v = x1.contiguous(), x2.contiguous(), theta.contiguous(), v.contiguous()
-    dtype = _kernel_dtype("kernel_mv", x1, x2, theta, v, d)
-    f64 = dtype == torch.float64
-    _hip.require_hip(x1, x2, theta, v, d, dtype=dtype)
-    B, M, D = x1.shape
-    N, c = v.shape[-2:]
-    if x2.shape != (B, N, D) or theta.shape != (B, D + 1) or v.shape[0] != B:
-        raise RuntimeError(f"kernel_mv: x1 {tuple(x1.shape)}, x2 {tuple(x2.shape)}, theta {tuple(theta.shape)}, "
-                           f"v {tuple(v.shape)}")
-    mode = _hip.LO_DIAG_NONE
-    if d is not None:
-        d, mode, _ = _diag_operand(d, B, N, const_diag)
+    x1, x2, theta, _, _, v, (B, M, N, D, _, c), dtype = _kernel_args("kernel_mv", x1, x2, theta, v, d=d, twin=True)
+    d, mode = _kernel_diag(d, B, N, const_diag)
     y = torch.empty(B, M, c, dtype=dtype, device=v.device)
-    sizer = lib.lo_kernel_mv_f64_workspace_bytes if f64 else lib.lo_kernel_mv_workspace_bytes
-    _launch("lo_kernel_mv_f64" if f64 else "lo_kernel_mv_f32", v.device, x1, x2, theta, int(family), B, M, N, D, v, c, d,
-            mode, y, ws_bytes=sizer(B, M, N, D, c))
+    name, sizer = _kernel_entry("lo_kernel_mv", dtype == torch.float64)
+    _launch(name, v.device, x1, x2, theta, int(family), B, M, N, D, v, c, d, mode, y, ws_bytes=sizer(B, M, N, D, c))
     return y
 
 
@@ -553,20 +594,10 @@ def kernel_bilinear(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, fam
     """lo_kernel_bilinear_f32 (all operands float64: lo_kernel_bilinear_f64): g_theta [B, D + 1], the derivative of
     sum_s u_s^T K(x1, x2) v_s with respect to theta (the inverse lengthscales, then outputscale^2).  x1 [B, M, D],
     x2 [B, N, D], U [B, M, t], V [B, N, t]."""
-    lib = _hip.load()
-    x1, x2, theta, U, V = (t.contiguous() for t in (x1, x2, theta, U, V))
-    dtype = _kernel_dtype("kernel_bilinear", x1, x2, theta, U, V)
-    f64 = dtype == torch.float64
-    _hip.require_hip(x1, x2, theta, U, V, dtype=dtype)
-    B, M, D = x1.shape
-    N, t = V.shape[-2:]
-    if x2.shape != (B, N, D) or theta.shape != (B, D + 1) or U.shape != (B, M, t) or V.shape[0] != B:
-        raise RuntimeError(f"kernel_bilinear: x1 {tuple(x1.shape)}, x2 {tuple(x2.shape)}, theta {tuple(theta.shape)}, "
-                           f"U {tuple(U.shape)}, V {tuple(V.shape)}")
+    x1, x2, theta, _, U, V, (B, M, N, D, _, t), dtype = _kernel_args("kernel_bilinear", x1, x2, theta, V, U, twin=True)
     g = torch.empty(B, D + 1, dtype=dtype, device=U.device)
-    sizer = lib.lo_kernel_bilinear_f64_workspace_bytes if f64 else lib.lo_kernel_bilinear_workspace_bytes
-    _launch("lo_kernel_bilinear_f64" if f64 else "lo_kernel_bilinear_f32", U.device, x1, x2, theta, int(family), B, M, N,
-            D, U, V, t, g, ws_bytes=sizer(B, M, N, D, t))
+    name, sizer = _kernel_entry("lo_kernel_bilinear", dtype == torch.float64)
+    _launch(name, U.device, x1, x2, theta, int(family), B, M, N, D, U, V, t, g, ws_bytes=sizer(B, M, N, D, t))
     return g
 
 
@@ -575,20 +606,11 @@ def kernel_points_grad(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, 
     """lo_kernel_points_grad_f32 (all operands float64: lo_kernel_points_grad_f64): g_x1 [B, M, D], the derivative of
     sum_s u_s^T K(x1, x2) v_s with respect to x1, x2 held fixed.  x1 [B, M, D], x2 [B, N, D], theta [B, D + 1],
     U [B, M, t], V [B, N, t].  The derivative with respect to x2 is kernel_points_grad(x2, x1, theta, family, V, U)."""
-    lib = _hip.load()
-    x1, x2, theta, U, V = (t.contiguous() for t in (x1, x2, theta, U, V))
-    dtype = _kernel_dtype("kernel_points_grad", x1, x2, theta, U, V)
-    f64 = dtype == torch.float64
-    _hip.require_hip(x1, x2, theta, U, V, dtype=dtype)
-    B, M, D = x1.shape
-    N, t = V.shape[-2:]
-    if x2.shape != (B, N, D) or theta.shape != (B, D + 1) or U.shape != (B, M, t) or V.shape[0] != B:
-        raise RuntimeError(f"kernel_points_grad: x1 {tuple(x1.shape)}, x2 {tuple(x2.shape)}, "
-                           f"theta {tuple(theta.shape)}, U {tuple(U.shape)}, V {tuple(V.shape)}")
+    x1, x2, theta, _, U, V, (B, M, N, D, _, t), dtype = _kernel_args("kernel_points_grad", x1, x2, theta, V, U,
+                                                                        twin=True)
     g = torch.empty(B, M, D, dtype=dtype, device=U.device)
-    sizer = lib.lo_kernel_points_grad_f64_workspace_bytes if f64 else lib.lo_kernel_points_grad_workspace_bytes
-    _launch("lo_kernel_points_grad_f64" if f64 else "lo_kernel_points_grad_f32", U.device, x1, x2, theta, int(family), B,
-            M, N, D, U, V, t, g, ws_bytes=sizer(B, M, N, D, t))
+    name, sizer = _kernel_entry("lo_kernel_points_grad", dtype == torch.float64)
+    _launch(name, U.device, x1, x2, theta, int(family), B, M, N, D, U, V, t, g, ws_bytes=sizer(B, M, N, D, t))
     return g
 
 
@@ -640,34 +662,16 @@ def kernel_sum_diag_descriptor(X: torch.Tensor, theta: torch.Tensor, families, d
                                          n2=packed, batch_shape=X.shape[:-2], kernel_terms=T), d, const_diag)
 
 
-def _kernel_sum_args(what, x1, x2, theta, families, W):
-    x1, x2, theta, W = x1.contiguous(), x2.contiguous(), theta.contiguous(), W.contiguous()
-    _hip.require_hip(x1, x2, theta, W)
-    kernel_sum_pack_families(families)
-    T = len(families)
-    B, M, D = x1.shape
-    N = W.shape[-2]
-    if x2.shape != (B, N, D) or theta.shape != (B, T, D + 1) or W.shape[0] != B or W.dim() != 3:
-        raise RuntimeError(f"{what}: x1 {tuple(x1.shape)}, x2 {tuple(x2.shape)}, theta {tuple(theta.shape)} for {T} "
-                           f"terms, right operand {tuple(W.shape)}")
-    return x1, x2, theta, W, (C.c_int32 * T)(*[int(f) for f in families]), T
-
-
 def kernel_sum_mv(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, families, v: torch.Tensor,
                   d: Optional[torch.Tensor] = None, const_diag: bool = False) -> torch.Tensor:
     """lo_kernel_sum_mv_f32: y [B, M, c] = (sum_t K_t(x1, x2)) v (+ d o v when M == N and d is given), x1 [B, M, D],
     x2 [B, N, D], theta [B, T, D + 1], `families` the T codes, v [B, N, c].  A shape the kernel does not take raises."""
-    lib = _hip.load()
-    x1, x2, theta, v, fams, T = _kernel_sum_args("kernel_sum_mv", x1, x2, theta, families, v)
-    _hip.require_hip(d)
-    B, M, D = x1.shape
-    N, c = v.shape[-2:]
-    mode = _hip.LO_DIAG_NONE
-    if d is not None:
-        d, mode, _ = _diag_operand(d, B, N, const_diag)
-    y = torch.empty(B, M, c, dtype=torch.float32, device=v.device)
-    _launch("lo_kernel_sum_mv_f32", v.device, x1, x2, theta, fams, T, B, M, N, D, v, c, d, mode, y,
-            ws_bytes=lib.lo_kernel_sum_mv_workspace_bytes(B, M, N, D, T, c))
+    x1, x2, theta, fams, _, v, (B, M, N, D, T, c), dtype = _kernel_args("kernel_sum_mv", x1, x2, theta, v, d=d,
+                                                                         families=families)
+    d, mode = _kernel_diag(d, B, N, const_diag)
+    y = torch.empty(B, M, c, dtype=dtype, device=v.device)
+    name, sizer = _kernel_entry("lo_kernel_sum_mv", dtype == torch.float64)
+    _launch(name, v.device, x1, x2, theta, fams, T, B, M, N, D, v, c, d, mode, y, ws_bytes=sizer(B, M, N, D, T, c))
     return y
 
 
@@ -675,17 +679,11 @@ def kernel_sum_bilinear(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor,
                         V: torch.Tensor) -> torch.Tensor:
     """lo_kernel_sum_bilinear_f32: g_theta [B, T, D + 1], every term's derivative of sum_s u_s^T K(x1, x2) v_s with
     respect to its theta, W_ij = sum_s U[i, s] V[j, s] formed once per pair.  U [B, M, t], V [B, N, t]."""
-    lib = _hip.load()
-    x1, x2, theta, V, fams, T = _kernel_sum_args("kernel_sum_bilinear", x1, x2, theta, families, V)
-    U = U.contiguous()
-    _hip.require_hip(U)
-    B, M, D = x1.shape
-    N, t = V.shape[-2:]
-    if U.shape != (B, M, t):
-        raise RuntimeError(f"kernel_sum_bilinear: U {tuple(U.shape)} for x1 {tuple(x1.shape)}, V {tuple(V.shape)}")
-    g = torch.empty(B, T, D + 1, dtype=torch.float32, device=U.device)
-    _launch("lo_kernel_sum_bilinear_f32", U.device, x1, x2, theta, fams, T, B, M, N, D, U, V, t, g,
-            ws_bytes=lib.lo_kernel_sum_bilinear_workspace_bytes(B, M, N, D, T, t))
+    x1, x2, theta, fams, U, V, (B, M, N, D, T, t), dtype = _kernel_args("kernel_sum_bilinear", x1, x2, theta, V, U,
+                                                                         families=families)
+    g = torch.empty(B, T, D + 1, dtype=dtype, device=U.device)
+    name, sizer = _kernel_entry("lo_kernel_sum_bilinear", dtype == torch.float64)
+    _launch(name, U.device, x1, x2, theta, fams, T, B, M, N, D, U, V, t, g, ws_bytes=sizer(B, M, N, D, T, t))
     return g
 
 
@@ -693,17 +691,11 @@ def kernel_sum_points_grad(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tens
                            V: torch.Tensor) -> torch.Tensor:
     """lo_kernel_sum_points_grad_f32: g_x1 [B, M, D], the derivative of sum_s u_s^T (sum_t K_t(x1, x2)) v_s with respect
     to x1, x2 held fixed, in one sweep.  The x2 side is kernel_sum_points_grad(x2, x1, theta, families, V, U)."""
-    lib = _hip.load()
-    x1, x2, theta, V, fams, T = _kernel_sum_args("kernel_sum_points_grad", x1, x2, theta, families, V)
-    U = U.contiguous()
-    _hip.require_hip(U)
-    B, M, D = x1.shape
-    N, t = V.shape[-2:]
-    if U.shape != (B, M, t):
-        raise RuntimeError(f"kernel_sum_points_grad: U {tuple(U.shape)} for x1 {tuple(x1.shape)}, V {tuple(V.shape)}")
-    g = torch.empty(B, M, D, dtype=torch.float32, device=U.device)
-    _launch("lo_kernel_sum_points_grad_f32", U.device, x1, x2, theta, fams, T, B, M, N, D, U, V, t, g,
-            ws_bytes=lib.lo_kernel_sum_points_grad_workspace_bytes(B, M, N, D, T, t))
+    x1, x2, theta, fams, U, V, (B, M, N, D, T, t), dtype = _kernel_args("kernel_sum_points_grad", x1, x2, theta, V, U,
+                                                                         families=families)
+    g = torch.empty(B, M, D, dtype=dtype, device=U.device)
+    name, sizer = _kernel_entry("lo_kernel_sum_points_grad", dtype == torch.float64)
+    _launch(name, U.device, x1, x2, theta, fams, T, B, M, N, D, U, V, t, g, ws_bytes=sizer(B, M, N, D, T, t))
     return g
 
 
@@ -731,21 +723,12 @@ def kernel_kron_mv(x: torch.Tensor, theta: torch.Tensor, task: torch.Tensor, fam
     """lo_kernel_kron_mv_f32: y [B, n T, c] = (K(x, x) (x) Bt) v (+ d o v), x [B, n, D], theta [B, D + 1], task = Bt
     [B, T, T] (used as given, symmetric or not), v [B, n T, c], row index i T + t.  A shape the kernel does not take
     raises."""
-    lib = _hip.load()
-    x, theta, task, v = x.contiguous(), theta.contiguous(), task.contiguous(), v.contiguous()
-    _hip.require_hip(x, theta, task, v, d)
-    B, n, D = x.shape
-    T = task.shape[-1]
-    N, c = v.shape[-2:]
-    if theta.shape != (B, D + 1) or task.shape != (B, T, T) or v.shape[0] != B or N != n * T:
-        raise RuntimeError(f"kernel_kron_mv: x {tuple(x.shape)}, theta {tuple(theta.shape)}, task {tuple(task.shape)}, "
-                           f"v {tuple(v.shape)}")
-    mode = _hip.LO_DIAG_NONE
-    if d is not None:
-        d, mode, _ = _diag_operand(d, B, N, const_diag)
-    y = torch.empty(B, N, c, dtype=torch.float32, device=v.device)
-    _launch("lo_kernel_kron_mv_f32", v.device, x, theta, task, int(family), B, n, D, T, v, c, d, mode, y,
-            ws_bytes=lib.lo_kernel_kron_mv_workspace_bytes(B, n, D, T, c))
+    x, _, theta, task, _, v, (B, n, _, D, T, c), dtype = _kernel_args("kernel_kron_mv", x, x, theta, v, d=d, task=task,
+                                                                       block=task.shape[-1])
+    d, mode = _kernel_diag(d, B, n * T, const_diag)
+    y = torch.empty(B, n * T, c, dtype=dtype, device=v.device)
+    name, sizer = _kernel_entry("lo_kernel_kron_mv", dtype == torch.float64)
+    _launch(name, v.device, x, theta, task, int(family), B, n, D, T, v, c, d, mode, y, ws_bytes=sizer(B, n, D, T, c))
     return y
 
 
@@ -771,21 +754,12 @@ def kernel_grad_mv(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, fami
     """lo_kernel_grad_mv_f32: y [B, M (D + 1), c] = K(x1, x2) v (+ d o v, only when M == N) for the gradient kernel's
     block matrix, x1 [B, M, D], x2 [B, N, D], theta [B, D + 1], v [B, N (D + 1), c].  A shape the kernel does not take
     raises."""
-    lib = _hip.load()
-    x1, x2, theta, v = x1.contiguous(), x2.contiguous(), theta.contiguous(), v.contiguous()
-    _hip.require_hip(x1, x2, theta, v, d)
-    B, M, D = x1.shape
-    N = x2.shape[-2]
-    c = v.shape[-1]
-    if x2.shape != (B, N, D) or theta.shape != (B, D + 1) or v.shape != (B, N * (D + 1), c):
-        raise RuntimeError(f"kernel_grad_mv: x1 {tuple(x1.shape)}, x2 {tuple(x2.shape)}, theta {tuple(theta.shape)}, "
-                           f"v {tuple(v.shape)}")
-    mode = _hip.LO_DIAG_NONE
-    if d is not None:
-        d, mode, _ = _diag_operand(d, B, M * (D + 1), const_diag)
-    y = torch.empty(B, M * (D + 1), c, dtype=torch.float32, device=v.device)
-    _launch("lo_kernel_grad_mv_f32", v.device, x1, x2, theta, int(family), B, M, N, D, v, c, d, mode, y,
-            ws_bytes=lib.lo_kernel_grad_mv_workspace_bytes(B, M, N, D, c))
+    x1, x2, theta, _, _, v, (B, M, N, D, _, c), dtype = _kernel_args("kernel_grad_mv", x1, x2, theta, v, d=d,
+                                                                      block=x1.shape[-1] + 1)
+    d, mode = _kernel_diag(d, B, M * (D + 1), const_diag)
+    y = torch.empty(B, M * (D + 1), c, dtype=dtype, device=v.device)
+    name, sizer = _kernel_entry("lo_kernel_grad_mv", dtype == torch.float64)
+    _launch(name, v.device, x1, x2, theta, int(family), B, M, N, D, v, c, d, mode, y, ws_bytes=sizer(B, M, N, D, c))
     return y
 
 
@@ -794,19 +768,11 @@ def kernel_grad_bilinear(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor
     """lo_kernel_grad_bilinear_f32: g_theta [B, D + 1], the derivative of sum_s u_s^T K(x1, x2) v_s with respect to theta
     (the inverse lengthscales, then outputscale^2) for the gradient kernel's block matrix.  x1 [B, M, D], x2 [B, N, D],
     U [B, M (D + 1), t], V [B, N (D + 1), t]."""
-    lib = _hip.load()
-    x1, x2, theta, U, V = (t.contiguous() for t in (x1, x2, theta, U, V))
-    _hip.require_hip(x1, x2, theta, U, V)
-    B, M, D = x1.shape
-    N = x2.shape[-2]
-    t = V.shape[-1]
-    if (x2.shape != (B, N, D) or theta.shape != (B, D + 1) or U.shape != (B, M * (D + 1), t)
-            or V.shape != (B, N * (D + 1), t)):
-        raise RuntimeError(f"kernel_grad_bilinear: x1 {tuple(x1.shape)}, x2 {tuple(x2.shape)}, "
-                           f"theta {tuple(theta.shape)}, U {tuple(U.shape)}, V {tuple(V.shape)}")
-    g = torch.empty(B, D + 1, dtype=torch.float32, device=U.device)
-    _launch("lo_kernel_grad_bilinear_f32", U.device, x1, x2, theta, int(family), B, M, N, D, U, V, t, g,
-            ws_bytes=lib.lo_kernel_grad_bilinear_workspace_bytes(B, M, N, D, t))
+    x1, x2, theta, _, U, V, (B, M, N, D, _, t), dtype = _kernel_args("kernel_grad_bilinear", x1, x2, theta, V, U,
+                                                                      block=x1.shape[-1] + 1)
+    g = torch.empty(B, D + 1, dtype=dtype, device=U.device)
+    name, sizer = _kernel_entry("lo_kernel_grad_bilinear", dtype == torch.float64)
+    _launch(name, U.device, x1, x2, theta, int(family), B, M, N, D, U, V, t, g, ws_bytes=sizer(B, M, N, D, t))
     return g
 
 
@@ -830,34 +796,18 @@ def kernel_task_diag_descriptor(X: torch.Tensor, theta: torch.Tensor, family: in
                                          n2=int(family), batch_shape=X.shape[:-2], kernel_terms=T, task=Bt), d, const_diag)
 
 
-def _kernel_task_args(what, x1, x2, theta, task, W):
-    x1, x2, theta, task, W = (t.contiguous() for t in (x1, x2, theta, task, W))
-    _hip.require_hip(x1, x2, theta, task, W)
-    B, M, D = x1.shape[0], x1.shape[1], x1.shape[2] - 1
-    T = task.shape[-1]
-    N = W.shape[-2]
-    if (x1.dim() != 3 or x2.shape != (B, N, D + 1) or theta.shape != (B, D + 1) or task.shape != (B, T, T)
-            or W.dim() != 3 or W.shape[0] != B):
-        raise RuntimeError(f"{what}: x1 {tuple(x1.shape)}, x2 {tuple(x2.shape)}, theta {tuple(theta.shape)}, "
-                           f"task {tuple(task.shape)}, right operand {tuple(W.shape)}")
-    return x1, x2, theta, task, W, (B, M, N, D, T)
-
-
 def kernel_task_mv(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, task: torch.Tensor, family: int,
                    v: torch.Tensor, d: Optional[torch.Tensor] = None, const_diag: bool = False) -> torch.Tensor:
     """lo_kernel_task_mv_f32: y [B, M, c] = K(x1, x2) v (+ d o v when M == N and d is given), K_ij = os2 g(r_ij)
     Bt[t_i, t_j]; x1 [B, M, D + 1], x2 [B, N, D + 1] with the task id in the last column, theta [B, D + 1], task = Bt
     [B, T, T] (used as given, symmetric or not), v [B, N, c].  A shape the kernel does not take raises."""
-    lib = _hip.load()
-    x1, x2, theta, task, v, (B, M, N, D, T) = _kernel_task_args("kernel_task_mv", x1, x2, theta, task, v)
-    _hip.require_hip(d)
-    c = v.shape[-1]
-    mode = _hip.LO_DIAG_NONE
-    if d is not None:
-        d, mode, _ = _diag_operand(d, B, N, const_diag)
-    y = torch.empty(B, M, c, dtype=torch.float32, device=v.device)
-    _launch("lo_kernel_task_mv_f32", v.device, x1, x2, theta, task, int(family), B, M, N, D, T, v, c, d, mode, y,
-            ws_bytes=lib.lo_kernel_task_mv_workspace_bytes(B, M, N, D, T, c))
+    x1, x2, theta, task, _, v, (B, M, N, D, T, c), dtype = _kernel_args("kernel_task_mv", x1, x2, theta, v, d=d,
+                                                                         task=task, ids=1)
+    d, mode = _kernel_diag(d, B, N, const_diag)
+    y = torch.empty(B, M, c, dtype=dtype, device=v.device)
+    name, sizer = _kernel_entry("lo_kernel_task_mv", dtype == torch.float64)
+    _launch(name, v.device, x1, x2, theta, task, int(family), B, M, N, D, T, v, c, d, mode, y,
+            ws_bytes=sizer(B, M, N, D, T, c))
     return y
 
 
@@ -866,17 +816,13 @@ def kernel_task_bilinear(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor
     """lo_kernel_task_bilinear_f32: (g_theta [B, D + 1], g_task [B, T, T]), the derivatives of sum_s u_s^T K(x1, x2) v_s
     with respect to theta (the inverse lengthscales, then outputscale^2) and to Bt (entry by entry, not symmetrised).
     U [B, M, t], V [B, N, t]."""
-    lib = _hip.load()
-    x1, x2, theta, task, V, (B, M, N, D, T) = _kernel_task_args("kernel_task_bilinear", x1, x2, theta, task, V)
-    U = U.contiguous()
-    _hip.require_hip(U)
-    t = V.shape[-1]
-    if U.shape != (B, M, t):
-        raise RuntimeError(f"kernel_task_bilinear: U {tuple(U.shape)} for x1 {tuple(x1.shape)}, V {tuple(V.shape)}")
-    g = torch.empty(B, D + 1, dtype=torch.float32, device=U.device)
-    gB = torch.empty(B, T, T, dtype=torch.float32, device=U.device)
-    _launch("lo_kernel_task_bilinear_f32", U.device, x1, x2, theta, task, int(family), B, M, N, D, T, U, V, t, g, gB,
-            ws_bytes=lib.lo_kernel_task_bilinear_workspace_bytes(B, M, N, D, T, t))
+    x1, x2, theta, task, U, V, (B, M, N, D, T, t), dtype = _kernel_args("kernel_task_bilinear", x1, x2, theta, V, U,
+                                                                         task=task, ids=1)
+    g = torch.empty(B, D + 1, dtype=dtype, device=U.device)
+    gB = torch.empty(B, T, T, dtype=dtype, device=U.device)
+    name, sizer = _kernel_entry("lo_kernel_task_bilinear", dtype == torch.float64)
+    _launch(name, U.device, x1, x2, theta, task, int(family), B, M, N, D, T, U, V, t, g, gB,
+            ws_bytes=sizer(B, M, N, D, T, t))
     return g, gB
 
 
@@ -884,16 +830,12 @@ def kernel_task_points_grad(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Ten
                             U: torch.Tensor, V: torch.Tensor) -> torch.Tensor:
     """lo_kernel_task_points_grad_f32: g_x1 [B, M, D + 1], the derivative of sum_s u_s^T K(x1, x2) v_s with respect to
     x1, x2 held fixed; the task column is 0.  The x2 side is kernel_task_points_grad(x2, x1, theta, task.mT, family, V, U)."""
-    lib = _hip.load()
-    x1, x2, theta, task, V, (B, M, N, D, T) = _kernel_task_args("kernel_task_points_grad", x1, x2, theta, task, V)
-    U = U.contiguous()
-    _hip.require_hip(U)
-    t = V.shape[-1]
-    if U.shape != (B, M, t):
-        raise RuntimeError(f"kernel_task_points_grad: U {tuple(U.shape)} for x1 {tuple(x1.shape)}, V {tuple(V.shape)}")
-    g = torch.empty(B, M, D + 1, dtype=torch.float32, device=U.device)
-    _launch("lo_kernel_task_points_grad_f32", U.device, x1, x2, theta, task, int(family), B, M, N, D, T, U, V, t, g,
-            ws_bytes=lib.lo_kernel_task_points_grad_workspace_bytes(B, M, N, D, T, t))
+    x1, x2, theta, task, U, V, (B, M, N, D, T, t), dtype = _kernel_args("kernel_task_points_grad", x1, x2, theta, V, U,
+                                                                         task=task, ids=1)
+    g = torch.empty(B, M, D + 1, dtype=dtype, device=U.device)
+    name, sizer = _kernel_entry("lo_kernel_task_points_grad", dtype == torch.float64)
+    _launch(name, U.device, x1, x2, theta, task, int(family), B, M, N, D, T, U, V, t, g,
+            ws_bytes=sizer(B, M, N, D, T, t))
     return g
 
 

@@ -5,7 +5,8 @@
 // lo_lanczos_workspace_bytes.  The sizing passes run the plan functions on a measuring arena: they must read no device
 // pointer (the ones here are dummy addresses), keep no sub-plan (a leak report) and touch nothing out of bounds.  No GPU.
 // The solver sizers are also walked with Woodbury preconditioners (the padded copy of Q taken and not taken, the root
-// form alone), and the sizers of the other entry points with shapes of tests/workspace_cases.py.
+// form alone), and the sizers of the other entry points with shapes of tests/workspace_cases.py.  Last, the compile-time
+// pickers of the matrix-free kernel family (csrc/lo_kernel_shape.h) are held to what the switches they replaced chose.
 //
 //   cd linear_operator_amd/csrc && mkdir -p build_asan
 //   for f in *.hip; do hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -fPIC -Xarch_host -fsanitize=address,undefined \
@@ -20,6 +21,7 @@
 #include <vector>
 
 #include "../include/lo_amd.h"
+#include "../linear_operator_amd/csrc/lo_kernel_shape.h"
 
 static const float* F(uintptr_t a) { return reinterpret_cast<const float*>(a); }
 static const int64_t* I(uintptr_t a) { return reinterpret_cast<const int64_t*>(a); }
@@ -131,6 +133,90 @@ static int walk_entries() {
   return bad;
 }
 
+// The compile-time pickers of csrc/lo_kernel_shape.h, which choose a kernel instantiation of the matrix-free kernel family
+// from run-time values: for every value of a list, one below, one between (where there is one) and one above, the constant
+// that ko_pick hands on must be the one the `switch` it replaced chose -- the matching `case`, else the `default:` arm.
+// The expectations are written out.
+template <class Seq>
+static int picked(Seq seq, int v) {
+  int got = -1;
+  lo::ko_pick(seq, v, [&](auto c) { got = c(); });
+  return got;
+}
+
+static int walk_pickers() {
+  using namespace lo;
+  struct Pick {
+    const char* list;
+    int v, got, want;
+  };
+  const Pick picks[] = {
+      // family: case RBF / MATERN12 / MATERN32, default MATERN52
+      {"families", -1, picked(ko_families{}, -1), 3}, {"families", 0, picked(ko_families{}, 0), 0},
+      {"families", 1, picked(ko_families{}, 1), 1},   {"families", 2, picked(ko_families{}, 2), 2},
+      {"families", 3, picked(ko_families{}, 3), 3},   {"families", 4, picked(ko_families{}, 4), 3},
+      // padded dimension: case 4 / 8 / 16, default 32
+      {"dims", 3, picked(ko_dims{}, 3), 32},   {"dims", 4, picked(ko_dims{}, 4), 4},    {"dims", 6, picked(ko_dims{}, 6), 32},
+      {"dims", 8, picked(ko_dims{}, 8), 8},    {"dims", 12, picked(ko_dims{}, 12), 32}, {"dims", 16, picked(ko_dims{}, 16), 16},
+      {"dims", 24, picked(ko_dims{}, 24), 32}, {"dims", 32, picked(ko_dims{}, 32), 32}, {"dims", 33, picked(ko_dims{}, 33), 32},
+      // columns of the single-term and task products: case 1 / 4, default 16
+      {"cols", 0, picked(ko_cols{}, 0), 16},   {"cols", 1, picked(ko_cols{}, 1), 1},   {"cols", 2, picked(ko_cols{}, 2), 16},
+      {"cols", 4, picked(ko_cols{}, 4), 4},    {"cols", 8, picked(ko_cols{}, 8), 16},  {"cols", 16, picked(ko_cols{}, 16), 16},
+      {"cols", 17, picked(ko_cols{}, 17), 16},
+      // wide columns of the Kronecker product: case 4 / 16, default 32
+      {"kron cols", 3, picked(kk_cols{}, 3), 32},   {"kron cols", 4, picked(kk_cols{}, 4), 4},
+      {"kron cols", 8, picked(kk_cols{}, 8), 32},   {"kron cols", 16, picked(kk_cols{}, 16), 16},
+      {"kron cols", 24, picked(kk_cols{}, 24), 32}, {"kron cols", 32, picked(kk_cols{}, 32), 32},
+      {"kron cols", 33, picked(kk_cols{}, 33), 32},
+      // float64 columns: CC == 1, CC == 4, else 8 below DP 32 (at DP 32 the old code launched nothing for a third value,
+      // which ko64_col_chunk never yields there: the list ends at 4)
+      {"f64 cols", 0, picked(ko64_cols<16>{}, 0), 8},   {"f64 cols", 1, picked(ko64_cols<16>{}, 1), 1},
+      {"f64 cols", 2, picked(ko64_cols<16>{}, 2), 8},   {"f64 cols", 4, picked(ko64_cols<16>{}, 4), 4},
+      {"f64 cols", 6, picked(ko64_cols<16>{}, 6), 8},   {"f64 cols", 8, picked(ko64_cols<16>{}, 8), 8},
+      {"f64 cols", 9, picked(ko64_cols<16>{}, 9), 8},   {"f64 cols DP 32", 1, picked(ko64_cols<32>{}, 1), 1},
+      {"f64 cols DP 32", 4, picked(ko64_cols<32>{}, 4), 4},
+      // gradient kernel, padded dimension: case 4 / 8, default 16
+      {"grad dims", 3, picked(kg_dims{}, 3), 16},   {"grad dims", 4, picked(kg_dims{}, 4), 4},
+      {"grad dims", 6, picked(kg_dims{}, 6), 16},   {"grad dims", 8, picked(kg_dims{}, 8), 8},
+      {"grad dims", 12, picked(kg_dims{}, 12), 16}, {"grad dims", 16, picked(kg_dims{}, 16), 16},
+      {"grad dims", 32, picked(kg_dims{}, 32), 16},
+      // gradient kernel, columns: CC == 4 at DP 4, CC == 2 up to DP 8, else 1
+      {"grad cols DP 4", 0, picked(kg_cols<4>{}, 0), 1},   {"grad cols DP 4", 1, picked(kg_cols<4>{}, 1), 1},
+      {"grad cols DP 4", 2, picked(kg_cols<4>{}, 2), 2},   {"grad cols DP 4", 3, picked(kg_cols<4>{}, 3), 1},
+      {"grad cols DP 4", 4, picked(kg_cols<4>{}, 4), 4},   {"grad cols DP 4", 5, picked(kg_cols<4>{}, 5), 1},
+      {"grad cols DP 8", 0, picked(kg_cols<8>{}, 0), 1},   {"grad cols DP 8", 1, picked(kg_cols<8>{}, 1), 1},
+      {"grad cols DP 8", 2, picked(kg_cols<8>{}, 2), 2},   {"grad cols DP 8", 4, picked(kg_cols<8>{}, 4), 1},
+      {"grad cols DP 16", 1, picked(kg_cols<16>{}, 1), 1}, {"grad cols DP 16", 2, picked(kg_cols<16>{}, 2), 1},
+  };
+  int bad = 0;
+  for (const Pick& p : picks)
+    if (p.got != p.want) {
+      printf("picker %s: %d chose %d, the switch chose %d\n", p.list, p.v, p.got, p.want);
+      ++bad;
+    }
+  // the chunk functions yield members of their lists only, so the `default:` arm is never an unlisted width
+  for (int64_t c = 1; c <= 40; ++c) {
+    for (int DP : {4, 8, 16, 32}) {
+      if (picked(ko_cols{}, ko_col_chunk(c)) != ko_col_chunk(c) || picked(kk_cols{}, kk_col_chunk(c)) != kk_col_chunk(c)) ++bad;
+      const int c64 = ko64_col_chunk(c, DP);
+      if ((DP == 32 ? picked(ko64_cols<32>{}, c64) : picked(ko64_cols<16>{}, c64)) != c64) ++bad;
+      const int cg = kg_col_chunk(DP, c);
+      if (DP <= 16 && (DP == 4 ? picked(kg_cols<4>{}, cg) : DP == 8 ? picked(kg_cols<8>{}, cg) : picked(kg_cols<16>{}, cg)) != cg)
+        ++bad;
+    }
+  }
+  // the dispatcher hands the three constants on together
+  int seen[3] = {-1, -1, -1};
+  ko_dispatch(LO_KERNEL_MATERN32, 8, kk_cols{}, 16, [&](auto f, auto p, auto c) {
+    seen[0] = f();
+    seen[1] = p();
+    seen[2] = c();
+  });
+  if (seen[0] != LO_KERNEL_MATERN32 || seen[1] != 8 || seen[2] != 16) ++bad;
+  printf("pickers: %zu choices checked, %d wrong\n", sizeof(picks) / sizeof(picks[0]), bad);
+  return bad;
+}
+
 int main() {
   std::vector<Entry> t;
   t.push_back({"lowrank_r5", desc(LO_OP_LOWRANK_DIAG, 2, 300, 5, 0, false, LO_DIAG_FULL), true});
@@ -205,7 +291,7 @@ int main() {
   lo_op_desc sum_late = sum3;
   sum_late.terms = late;
   bad += walk({{"sum, bad last term", sum_late, true}});  // (its first terms do take buffers)
-  bad += walk_precond(t[0].op) + walk_entries();
+  bad += walk_precond(t[0].op) + walk_entries() + walk_pickers();
   printf(bad ? "FAILED: %d\n" : "ok\n", bad);
   return bad ? 1 : 0;
 }
