@@ -325,7 +325,7 @@ typedef struct lo_cg_info {
 } lo_cg_info;
 
 /* ---- library ------------------------------------------------------------------------------- */
-/* ABI version (bumped on any signature change) and the gfx arch string the code objects target. */
+/* ABI version (36; bumped on any signature change) and the gfx arch string the code objects target. */
 int lo_abi_version(void);
 const char* lo_target_arch(void);
 
@@ -1145,6 +1145,23 @@ int lo_tri_solve_f64(const double* T, const double* rhs, double* out, double* su
                      int32_t upper, int32_t transpose, void* stream);
 int lo_cholesky_solve_f64(const double* T, const double* rhs, double* out, int64_t B, int64_t N, int64_t c,
                           int32_t upper, void* stream);
+
+/* ---- batched symmetric eigendecomposition in fp64 (ABI 36; csrc/lo_eigh_f64.hip) ---------------------------------------
+ * A [B, N, N] contiguous row-major, ONLY THE LOWER TRIANGLE IS READ (the default UPLO of torch.linalg.eigh); A is not
+ * modified.  evals [B, N] ascending; evecs [B, N, N] row-major, column j the unit eigenvector of evals[j]; with
+ * want_vectors = 0 evecs may be NULL and no vector work is done (the eigenvalues are the same bits either way).
+ * info [B] int32: 0, or > 0 when the member's input holds a non-finite value (1) or its iteration did not converge
+ * within 30 N sweeps (2); such a member's evals (and evecs) are filled with NaN on the device, the other members are
+ * untouched.  One workgroup per member: Householder tridiagonalisation, implicit-shift QL, back-transformation; the
+ * member is scaled by a power of two first.  Stream-ordered, fixed-order sums, no atomics: a member's result does not
+ * depend on the batch around it and repeats bit for bit.
+ * Before any launch: LO_ERR_BADARG for a null A / evals / info, want_vectors with a null evecs, N < 1, B < 0;
+ * LO_ERR_UNSUPPORTED for N > LO_EIGH_MAX_N; LO_ERR_WORKSPACE for a short or null workspace; B == 0 is a success that
+ * launches nothing.  The sizer returns 0 for what the call refuses.                                                   */
+#define LO_EIGH_MAX_N 1024
+size_t lo_eigh_f64_workspace_bytes(int64_t B, int64_t N, int32_t want_vectors);
+int lo_eigh_f64(const double* A, double* evals, double* evecs, int32_t* info, int64_t B, int64_t N, int32_t want_vectors,
+                void* ws, size_t ws_bytes, void* stream);
 
 /* ---- masked operators (ABI 21; csrc/lo_masked.hip) ---------------------------------------------------------------------
  * The kind LO_OP_MASKED is served by lo_matvec_f32 and the solvers above.  lo_mask_expand_f32 is its first step alone:

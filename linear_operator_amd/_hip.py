@@ -41,7 +41,8 @@ LO_OP_KERNEL_TASK_DIAG = 15
 LO_KERNEL_TASK_MAX_TASKS = 8
 LO_DIAG_NONE, LO_DIAG_FULL, LO_DIAG_CONST = 0, 1, 2
 LO_BLOCK_DIAG, LO_BLOCK_INTERLEAVED, LO_BLOCK_SUM = 0, 1, 2
-ABI_VERSION = 35
+LO_EIGH_MAX_N = 1024
+ABI_VERSION = 36
 
 LO_ERR_UNSUPPORTED = -4
 LO_FUSED_OK, LO_FUSED_EARLY_STOP, LO_FUSED_CONTINUE, LO_FUSED_TIMEOUT = 0, 1, 2, 3
@@ -316,6 +317,8 @@ _PROTOTYPES = {
     "lo_cholesky_f64": (ci, [vp, vp, vp, vp, i64, i64, vp, sz, vp]),
     "lo_tri_solve_f64": (ci, [vp, vp, vp, vp, i64, i64, i64, i32, i32, vp]),
     "lo_cholesky_solve_f64": (ci, [vp, vp, vp, i64, i64, i64, i32, vp]),
+    "lo_eigh_f64_workspace_bytes": (sz, [i64, i64, i32]),
+    "lo_eigh_f64": (ci, [vp, vp, vp, vp, i64, i64, i32, vp, sz, vp]),
     "lo_mask_expand_workspace_bytes": (sz, [i64]),
     "lo_mask_expand_f32": (ci, [vp, i64, i64, vp, vp, i64, i64, vp, sz, vp]),
     "lo_block_mv_workspace_bytes": (sz, [P(OpDesc), i32, i64, i64]),

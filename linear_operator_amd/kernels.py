@@ -2441,3 +2441,28 @@ def cholesky_solve(L: torch.Tensor, rhs: torch.Tensor, upper: bool = False) -> t
     if out.numel():
         _launch(f"lo_cholesky_solve_{sfx}", R3.device, L3, R3, out, B, N, c, int(bool(upper)))
     return out.reshape(*bs, N) if is_vec else out.reshape(*bs, N, c)
+
+
+# ------------------------------------------- symmetric eigendecomposition, float64 (csrc/lo_eigh_f64.hip)
+EIGH_MAX_N = _hip.LO_EIGH_MAX_N  # what lo_eigh_f64 takes
+
+
+def eigh(A: torch.Tensor, want_vectors: bool = True):
+    """lo_eigh_f64: (evals [*batch, N] ascending, evecs [*batch, N, N] or None, info [*batch] int32) of the symmetric
+    float64 matrices A [*batch, N, N], 1 <= N <= 1024; only the lower triangle of A is read.  Column j of evecs is the
+    unit eigenvector of evals[j].  info is 0, or > 0 for a member whose input holds a non-finite value or whose iteration
+    did not converge: that member's outputs are NaN.  Without vectors the eigenvalues are the same bits."""
+    if A.dim() < 2 or A.shape[-1] != A.shape[-2]:
+        raise ValueError(f"expected square matrices [..., N, N], got {tuple(A.shape)}")
+    _hip.require_hip(A, dtype=torch.float64)
+    bs, N = A.shape[:-2], A.shape[-1]
+    A3 = _flat(A, 2)
+    B, dev = A3.shape[0], A.device
+    evals = torch.empty(B, N, dtype=torch.float64, device=dev)
+    evecs = torch.empty_like(A3) if want_vectors else None
+    info = torch.empty(B, dtype=torch.int32, device=dev)
+    if B > 0 and N > 0:
+        wv = int(bool(want_vectors))
+        _launch("lo_eigh_f64", dev, A3, evals, evecs, info, B, N, wv,
+                ws_bytes=_hip.load().lo_eigh_f64_workspace_bytes(B, N, wv))
+    return evals.reshape(*bs, N), (evecs.reshape(*bs, N, N) if want_vectors else None), info.reshape(bs)

@@ -758,15 +758,32 @@ class LinearOperator(object):
         return res if lhs is None else (res, inv_quad_res)
 
     def _symeig(self, eigenvectors: bool = False, return_evals_as_lazy: bool = False):
-        """Dense symmetric eigendecomposition in `settings._linalg_dtype_symeig` (ATen plumbing; reference :878-901)."""
+        """Dense symmetric eigendecomposition in `settings._linalg_dtype_symeig` (functions/_eigh.py: the native float64
+        eigensolver where it is routed, ATen otherwise; reference :878-901)."""
+        from ..functions import _eigh
         from .dense_linear_operator import DenseLinearOperator
 
         if settings.verbose_linalg.on():
             settings.verbose_linalg.logger.debug(f"Running symeig on a matrix of size {self.shape}.")
         dtype = self.dtype
-        evals, evecs = torch.linalg.eigh(self.to_dense().to(dtype=settings._linalg_dtype_symeig.value()))
+        evals, evecs = _eigh.eigh(self.to_dense().to(dtype=settings._linalg_dtype_symeig.value()))
         evals = evals.clamp_min(0.0).to(dtype=dtype)
         return evals, (DenseLinearOperator(evecs.to(dtype=dtype)) if eigenvectors else None)
+
+    @_implements(torch.linalg.eigh)
+    def eigh(self):
+        """(eigenvalues [*batch, N], eigenvectors as a LinearOperator [*batch, N, N]) of the symmetric operator
+        (reference :1521-1541): `_symeig` with vectors, so structured classes return structured vectors and the
+        eigenvalues are clamped at zero and cast as there.  Like the reference's, the eigenvalues of a structured
+        operator are not sorted.  The reference's look-up of a cached decomposition is not reproduced: every call
+        decomposes."""
+        return self._symeig(eigenvectors=True)
+
+    @_implements(torch.linalg.eigvalsh)
+    def eigvalsh(self):
+        """Eigenvalues [*batch, N] of the symmetric operator (reference :1543-1562): `_symeig` without vectors; no
+        cache look-up, as for `eigh`."""
+        return self._symeig(eigenvectors=False)[0]
 
     def diagonalization(self, method: Optional[str] = None):
         """(evals, evecs) of a (usually partial) diagonalization Q diag(lambda) Q^T ~= A (reference :1439-1482):

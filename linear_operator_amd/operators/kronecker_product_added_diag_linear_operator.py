@@ -72,6 +72,8 @@ class KroneckerProductAddedDiagLinearOperator(AddedDiagLinearOperator):
 
     def _symmetrized_eig(self, detach: bool):
         """(D^-1/2 as a vector [*batch, N], eigenvalues of S [*batch, N], Q) in the symeig dtype; per-factor eigh."""
+        from ..functions import _eigh
+
         dt = settings._linalg_dtype_symeig.value()
         roots, evals, evecs = [], None, []
         for k_op, d_op in zip(self.linear_op.linear_ops, self.diag_tensor.linear_ops):
@@ -79,7 +81,7 @@ class KroneckerProductAddedDiagLinearOperator(AddedDiagLinearOperator):
             if detach:
                 kd, dd = kd.detach(), dd.detach()
             ir = dd.to(dt).rsqrt()
-            ev, q = torch.linalg.eigh(ir.unsqueeze(-1) * kd.to(dt) * ir.unsqueeze(-2))
+            ev, q = _eigh.eigh(ir.unsqueeze(-1) * kd.to(dt) * ir.unsqueeze(-2))
             ev = ev.clamp_min(0.0)
             roots.append(DiagLinearOperator(ir))
             evals = ev if evals is None else (evals.unsqueeze(-1) * ev.unsqueeze(-2)).reshape(*ev.shape[:-1], -1)

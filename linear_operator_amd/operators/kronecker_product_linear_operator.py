@@ -365,10 +365,12 @@ class KroneckerProductLinearOperator(LinearOperator):
         [*batch, N], evecs = Kronecker product of the factors' eigenvector matrices.  `symeig_dtype_evals` keeps the
         eigenvalues in `settings._linalg_dtype_symeig` (the closed-form solve shifts and inverts them there, like
         the reference's fp64 solve, kronecker_product_added_diag_linear_operator.py:147-161)."""
+        from ..functions import _eigh
+
         evals, evecs = None, []
         for op in self.linear_ops:
             dense = op.to_dense()
-            ev, q = torch.linalg.eigh(dense.to(dtype=settings._linalg_dtype_symeig.value()))
+            ev, q = _eigh.eigh(dense.to(dtype=settings._linalg_dtype_symeig.value()))
             ev = ev.clamp_min(0.0)
             if not symeig_dtype_evals:
                 ev = ev.to(dtype=dense.dtype)

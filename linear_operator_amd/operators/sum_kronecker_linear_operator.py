@@ -46,10 +46,12 @@ def sum_kron_factor_setup(a: Tensor, c: Tensor):
     P^T c P = I and P^T a P = diag(lambda).  Differentiable (Cholesky, triangular solves, eigh).  (Called in the symeig
     dtype, float64 unless `settings.linalg_dtypes` says otherwise: the batched float32 Cholesky of INTEGRATION.md
     section 5d is not on this path by default.)"""
+    from ..functions import _eigh
+
     L = torch.linalg.cholesky(c)
     half = torch.linalg.solve_triangular(L, a, upper=False)  # L^-1 a
     at = torch.linalg.solve_triangular(L, half.mT, upper=False)  # L^-1 a^T L^-T
-    ev, q = torch.linalg.eigh(0.5 * (at + at.mT))
+    ev, q = _eigh.eigh(0.5 * (at + at.mT))
     p = torch.linalg.solve_triangular(L.mT, q, upper=True)  # L^-T Q
     return p, ev.clamp_min(0.0), L, q
 
