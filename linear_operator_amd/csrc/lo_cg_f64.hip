@@ -6,7 +6,7 @@
 // diagonal) multiplied by k64_dense_mv or an opaque closure called back once per iteration; the preconditioner is a
 // closure or absent.  Same masking of alpha / beta, same stopping rule and the same CG-coefficient tridiagonals as the
 // fp32 engine (lo_cg.hip); none of the operator-resident machinery.
-#include "lo_internal.h"
+#include "lo_f64_solver.h"
 
 #include <algorithm>
 #include <math.h>
@@ -314,7 +314,7 @@ int f64_dense_mv(const double* A, const double* d, const double* v, double* y, i
   return f64_dense_mv_ex(A, d, d ? LO_DIAG_FULL : LO_DIAG_NONE, 0, v, y, B, N, c, st);
 }
 int f64_copy(const double* a, double* o, size_t total, hipStream_t st) {
-  hipLaunchKernelGGL(k64_copy, dim3((unsigned)((total + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, a, o, total);
+  hipLaunchKernelGGL(k64_copy, elem_grid(total), dim3(kThreads), 0, st, a, o, total);
   LO_LAUNCH_CHECK();
   return LO_OK;
 }
@@ -326,6 +326,7 @@ struct Lay64 {
   Ctl64* ctl;
 };
 
+constexpr size_t kCg64Tail = 1024;  // what lo_cg_f64_workspace_bytes reports behind the layout
 static void lay64(int64_t B, int64_t N, const lo_cg_params_f64* prm, Arena& ar, Lay64* l) {
   const size_t V = (size_t)B * N * prm->c, S = (size_t)B * prm->c;
   l->ctl = ar.take<Ctl64>(1);
@@ -354,18 +355,18 @@ static void lay64(int64_t B, int64_t N, const lo_cg_params_f64* prm, Arena& ar, 
 using namespace lo;
 
 extern "C" size_t lo_cg_f64_workspace_bytes(int64_t B, int64_t N, const lo_cg_params_f64* prm) {
-  Arena ar(nullptr, 0);
   Lay64 l;
-  lay64(B, N, prm, ar, &l);
-  return ar.off + 1024;
+  return measured(kCg64Tail, [&](Arena& ar) { lay64(B, N, prm, ar, &l); });
 }
 
 extern "C" int lo_cg_solve_f64(const double* A, const double* diag, lo_matvec_cb_f64 matvec, void* matvec_user,
                                lo_matvec_cb_f64 precond_cb, void* precond_user, const lo_cg_params_f64* prm,
                                int64_t B, int64_t N, const double* rhs, const double* x0, double* x, double* t_mat,
                                void* ws, size_t ws_bytes, lo_cg_info_f64* info, void* stream) {
-  if (!prm || !rhs || !x || !info || (!A && !matvec)) return LO_ERR_BADARG;
+  if (!prm || !rhs || !x || !info) return LO_ERR_BADARG;
   const int64_t c = prm->c;
+  const F64Operand opd{A, diag, matvec, matvec_user, precond_cb, precond_user, B, N, c, stream};
+  if (!opd.valid()) return LO_ERR_BADARG;
   if (B < 1 || N < 1 || c < 1 || B > 65535 || c > 0x7fffffff / 2 || N > 0x7ffffff0) return LO_ERR_UNSUPPORTED;
   if (prm->n_tridiag < 0 || prm->n_tridiag > c || (prm->n_tridiag && !t_mat)) return LO_ERR_BADARG;
   if ((size_t)B * (size_t)c > (size_t)1 << 30) return LO_ERR_UNSUPPORTED;
@@ -375,48 +376,30 @@ extern "C" int lo_cg_solve_f64(const double* A, const double* diag, lo_matvec_cb
   lay64(B, N, prm, ar, &l);
   if (!ar.ok) return LO_ERR_WORKSPACE;
   const size_t total = (size_t)B * N * c;
-  const unsigned eg = (unsigned)((total + kThreads - 1) / kThreads);
+  const dim3 eg = elem_grid(total);
   const dim3 dgrid((unsigned)c, (unsigned)B);
   const int BC = (int)(B * c);
   const int floor_max = prm->floor_max_iter > 0 ? prm->floor_max_iter : prm->max_iter;
   const int T = prm->max_tridiag_iter;
   memset(info, 0, sizeof(*info));
-
-  auto apply_op = [&](const double* v, double* y) -> int {
-    if (A) {
-      return f64_dense_mv(A, diag, v, y, B, N, c, st);
-    }
-    return matvec(matvec_user, v, y, B, N, c, stream) ? LO_ERR_LAUNCH : LO_OK;
-  };
-  auto apply_pre = [&](const double* v, double* y) -> int {
-    if (precond_cb) return precond_cb(precond_user, v, y, B, N, c, stream) ? LO_ERR_LAUNCH : LO_OK;
-    hipLaunchKernelGGL(k64_copy, dim3(eg), dim3(kThreads), 0, st, v, y, total);
-    LO_LAUNCH_CHECK();
-    return LO_OK;
-  };
   Ctl64 h;
-  auto read_ctl = [&]() -> int {
-    LO_HIP_CHECK(hipMemcpyAsync(&h, l.ctl, sizeof(h), hipMemcpyDeviceToHost, st));
-    LO_HIP_CHECK(hipStreamSynchronize(st));
-    return LO_OK;
-  };
 
   LO_HIP_CHECK(hipMemsetAsync(l.ctl, 0, sizeof(Ctl64), st));
   if (prm->n_tridiag)
     LO_HIP_CHECK(hipMemsetAsync(t_mat, 0, sizeof(double) * (size_t)prm->n_tridiag * B * T * T, st));
   hipLaunchKernelGGL(k64_dots, dgrid, dim3(kThreads), 0, st, rhs, rhs, l.nsq, nullptr, nullptr, nullptr, (int)N, (int)c);
-  hipLaunchKernelGGL(k64_normalise, dim3(eg), dim3(kThreads), 0, st, rhs, x0, l.nsq, prm->eps, l.u, l.x, l.rn, l.rzero,
+  hipLaunchKernelGGL(k64_normalise, eg, dim3(kThreads), 0, st, rhs, x0, l.nsq, prm->eps, l.u, l.x, l.rn, l.rzero,
                      (int)N, (int)c, total);
   LO_LAUNCH_CHECK();
-  int rc = apply_op(l.x, l.Ap);
+  int rc = opd.op(l.x, l.Ap);
   if (rc) return rc;
   int matvecs = 1;
-  hipLaunchKernelGGL(k64_residual, dim3(eg), dim3(kThreads), 0, st, l.u, l.Ap, l.r, l.ctl, total);
+  hipLaunchKernelGGL(k64_residual, eg, dim3(kThreads), 0, st, l.u, l.Ap, l.r, l.ctl, total);
   hipLaunchKernelGGL(k64_dots, dgrid, dim3(kThreads), 0, st, l.r, l.r, l.rr, nullptr, nullptr, nullptr, (int)N, (int)c);
   hipLaunchKernelGGL(k64_ctrl_init, dim3(1), dim3(kThreads), 0, st, l.rr, prm->stop_updating_after, prm->n_tridiag,
                      l.conv, l.ctl, BC);
   LO_LAUNCH_CHECK();
-  if ((rc = read_ctl())) return rc;
+  if ((rc = f64_read_back(&h, l.ctl, st))) return rc;
   if (h.nan_detected) {
     info->nan_detected = 1;
     info->matvecs = matvecs;
@@ -425,36 +408,36 @@ extern "C" int lo_cg_solve_f64(const double* A, const double* diag, lo_matvec_cb
   double* rz_old = l.rz_a;
   double* rz_new = l.rz_b;
   if (!h.stop && prm->max_iter > 0) {
-    if ((rc = apply_pre(l.r, l.z))) return rc;
-    hipLaunchKernelGGL(k64_copy, dim3(eg), dim3(kThreads), 0, st, l.z, l.p, total);
+    if ((rc = opd.pre(l.r, l.z))) return rc;
+    hipLaunchKernelGGL(k64_copy, eg, dim3(kThreads), 0, st, l.z, l.p, total);
     hipLaunchKernelGGL(k64_dots, dgrid, dim3(kThreads), 0, st, l.z, l.r, rz_old, nullptr, nullptr, nullptr, (int)N,
                        (int)c);
     LO_LAUNCH_CHECK();
     Tri64 tri{t_mat, l.prev_arec, l.prev_beta, prm->n_tridiag, T, (int)B};
     for (int k = 0; k < prm->max_iter; ++k) {
-      if ((rc = apply_op(l.p, l.Ap))) return rc;
+      if ((rc = opd.op(l.p, l.Ap))) return rc;
       ++matvecs;
       hipLaunchKernelGGL(k64_dots, dgrid, dim3(kThreads), 0, st, l.p, l.Ap, l.pAp, nullptr, nullptr, nullptr, (int)N,
                          (int)c);
-      hipLaunchKernelGGL(k64_update_r, dim3(eg), dim3(kThreads), 0, st, l.pAp, rz_old, l.conv, prm->eps, l.Ap, l.r,
+      hipLaunchKernelGGL(k64_update_r, eg, dim3(kThreads), 0, st, l.pAp, rz_old, l.conv, prm->eps, l.Ap, l.r,
                          l.alpha, (int)N, (int)c, total);
       LO_LAUNCH_CHECK();
-      if ((rc = apply_pre(l.r, l.z))) return rc;
+      if ((rc = opd.pre(l.r, l.z))) return rc;
       hipLaunchKernelGGL(k64_dots, dgrid, dim3(kThreads), 0, st, l.r, l.z, rz_new, l.r, l.r, l.rr, (int)N, (int)c);
-      hipLaunchKernelGGL(k64_update_xp, dim3(eg), dim3(kThreads), 0, st, l.alpha, rz_old, rz_new, prm->eps, l.z, l.x,
+      hipLaunchKernelGGL(k64_update_xp, eg, dim3(kThreads), 0, st, l.alpha, rz_old, rz_new, prm->eps, l.z, l.x,
                          l.p, l.beta, (int)N, (int)c, total);
       hipLaunchKernelGGL(k64_ctrl, dim3(1), dim3(kThreads), 0, st, l.rr, l.rzero, prm->stop_updating_after,
                          prm->tolerance, k, floor_max, std::min<int>(prm->max_tridiag_iter, T), l.alpha, l.beta, tri,
                          l.conv, l.ctl, (int)B, (int)c);
       LO_LAUNCH_CHECK();
       std::swap(rz_old, rz_new);
-      if ((rc = read_ctl())) return rc;
+      if ((rc = f64_read_back(&h, l.ctl, st))) return rc;
       if (h.stop) break;
     }
   }
-  hipLaunchKernelGGL(k64_final, dim3(eg), dim3(kThreads), 0, st, l.x, l.rn, x, (int)N, (int)c, total);
+  hipLaunchKernelGGL(k64_final, eg, dim3(kThreads), 0, st, l.x, l.rn, x, (int)N, (int)c, total);
   LO_LAUNCH_CHECK();
-  if ((rc = read_ctl())) return rc;
+  if ((rc = f64_read_back(&h, l.ctl, st))) return rc;
   info->iterations = h.iterations;
   info->matvecs = matvecs;
   info->tolerance_reached = h.tol_reached;

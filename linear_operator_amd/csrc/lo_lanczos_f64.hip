@@ -6,7 +6,7 @@
 // opaque closure.  Full re-orthogonalisation against every stored vector, the reference's signed `inner > tol` test with
 // up to ten extra passes (:131-142) and its batch-global stopping rule (:147) -- the two decisions are read back to the
 // host once per step, as the reference's own `.item()`-style tests do.
-#include "lo_internal.h"
+#include "lo_f64_solver.h"
 
 #include <math.h>
 #include <string.h>
@@ -101,6 +101,7 @@ struct LzLay64 {
   double *r, *tmp, *coef, *sq, *nrm;
   int* flags;
 };
+constexpr size_t kLz64Tail = 1024;  // what lo_lanczos_f64_workspace_bytes reports behind the layout
 void lz_lay64(int64_t B, int64_t N, int64_t P, int max_iter, Arena& ar, LzLay64* l) {
   const size_t V = (size_t)B * N * P, S = (size_t)B * P;
   l->r = ar.take<double>(V);
@@ -117,17 +118,16 @@ void lz_lay64(int64_t B, int64_t N, int64_t P, int max_iter, Arena& ar, LzLay64*
 using namespace lo;
 
 extern "C" size_t lo_lanczos_f64_workspace_bytes(int64_t B, int64_t N, int64_t P, int32_t max_iter) {
-  Arena ar(nullptr, 0);
   LzLay64 l;
-  lz_lay64(B, N, P, max_iter, ar, &l);
-  return ar.off + 1024;
+  return measured(kLz64Tail, [&](Arena& ar) { lz_lay64(B, N, P, max_iter, ar, &l); });
 }
 
 extern "C" int lo_lanczos_tridiag_f64(const double* A, const double* diag, lo_matvec_cb_f64 matvec, void* matvec_user,
                                       const double* init_vecs, int64_t B, int64_t N, int64_t P, int32_t max_iter,
                                       double tol, double* q_mat, double* t_mat, int32_t* iters_out, void* ws,
                                       size_t ws_bytes, void* stream) {
-  if (!init_vecs || !q_mat || !t_mat || !iters_out || (!A && !matvec)) return LO_ERR_BADARG;
+  const F64Operand opd{A, diag, matvec, matvec_user, nullptr, nullptr, B, N, P, stream};
+  if (!init_vecs || !q_mat || !t_mat || !iters_out || !opd.valid()) return LO_ERR_BADARG;
   if (B < 1 || N < 1 || P < 1 || max_iter < 1) return LO_ERR_BADARG;
   if (B > 65535 || P > 0x7fffffff / 2 || N > 0x7ffffff0 || max_iter > 65535) return LO_ERR_UNSUPPORTED;
   const int K = (int)std::min<int64_t>(max_iter, N);  // lanczos.py:57
@@ -137,14 +137,10 @@ extern "C" int lo_lanczos_tridiag_f64(const double* A, const double* diag, lo_ma
   lz_lay64(B, N, P, max_iter, ar, &l);
   if (!ar.ok) return LO_ERR_WORKSPACE;
   const size_t V = (size_t)B * N * P, S = (size_t)B * P;
-  const unsigned eg = (unsigned)((V + kThreads - 1) / kThreads);
+  const dim3 eg = elem_grid(V);
   const int iB = (int)B, iN = (int)N, iP = (int)P;
   auto qv = [&](int j) { return q_mat + (size_t)j * V; };
   auto tm = [&](int i, int j) { return t_mat + ((size_t)i * max_iter + j) * S; };
-  auto apply_op = [&](const double* v, double* y) -> int {
-    if (A) return f64_dense_mv(A, diag, v, y, B, N, P, st);
-    return matvec(matvec_user, v, y, B, N, P, stream) ? LO_ERR_LAUNCH : LO_OK;
-  };
   auto dots = [&](const double* Q, int m, const double* r, double* out) {
     hipLaunchKernelGGL(k64l_dots, dim3((unsigned)P, (unsigned)B, (unsigned)m), dim3(kThreads), 0, st, Q, r, out, iB, iN,
                        iP);
@@ -153,7 +149,7 @@ extern "C" int lo_lanczos_tridiag_f64(const double* A, const double* diag, lo_ma
   auto normalise = [&](const double* a, double* out) {
     dots(a, 1, a, l.sq);
     hipLaunchKernelGGL(k64l_sqrt, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, st, l.sq, l.nrm, (int)S);
-    hipLaunchKernelGGL(k64l_divide, dim3(eg), dim3(kThreads), 0, st, a, l.nrm, out, iN, iP, V);
+    hipLaunchKernelGGL(k64l_divide, eg, dim3(kThreads), 0, st, a, l.nrm, out, iN, iP, V);
   };
   auto copy_small = [&](double* dst, const double* src) -> int {
     LO_HIP_CHECK(hipMemcpyAsync(dst, src, sizeof(double) * S, hipMemcpyDeviceToDevice, st));
@@ -163,10 +159,10 @@ extern "C" int lo_lanczos_tridiag_f64(const double* A, const double* diag, lo_ma
   LO_HIP_CHECK(hipMemsetAsync(t_mat, 0, sizeof(double) * (size_t)max_iter * max_iter * S, st));
 
   normalise(init_vecs, qv(0));  // :81
-  if ((rc = apply_op(qv(0), l.r))) return rc;  // :85
+  if ((rc = opd.op(qv(0), l.r))) return rc;  // :85
   dots(qv(0), 1, l.r, l.coef);  // alpha_0
   if ((rc = copy_small(tm(0, 0), l.coef))) return rc;
-  hipLaunchKernelGGL(k64l_sub_scaled, dim3(eg), dim3(kThreads), 0, st, l.r, qv(0), l.coef, l.r, iN, iP, V);  // :89
+  hipLaunchKernelGGL(k64l_sub_scaled, eg, dim3(kThreads), 0, st, l.r, qv(0), l.coef, l.r, iN, iP, V);  // :89
   LO_LAUNCH_CHECK();
   if (K > 1) {
     normalise(l.r, qv(1));  // :98
@@ -174,16 +170,16 @@ extern "C" int lo_lanczos_tridiag_f64(const double* A, const double* diag, lo_ma
   }
   int k = 0;
   for (k = 1; k < K; ++k) {  // :101
-    if ((rc = apply_op(qv(k), l.tmp))) return rc;
-    hipLaunchKernelGGL(k64l_sub_scaled, dim3(eg), dim3(kThreads), 0, st, l.tmp, qv(k - 1), tm(k, k - 1), l.r, iN, iP,
+    if ((rc = opd.op(qv(k), l.tmp))) return rc;
+    hipLaunchKernelGGL(k64l_sub_scaled, eg, dim3(kThreads), 0, st, l.tmp, qv(k - 1), tm(k, k - 1), l.r, iN, iP,
                        V);  // :108
     dots(qv(k), 1, l.r, l.coef);  // alpha_k
     if ((rc = copy_small(tm(k, k), l.coef))) return rc;
     if (k + 1 >= K) break;  // :114
-    hipLaunchKernelGGL(k64l_sub_scaled, dim3(eg), dim3(kThreads), 0, st, l.r, qv(k), l.coef, l.r, iN, iP, V);
+    hipLaunchKernelGGL(k64l_sub_scaled, eg, dim3(kThreads), 0, st, l.r, qv(k), l.coef, l.r, iN, iP, V);
     const int m = k + 1;
     dots(q_mat, m, l.r, l.coef);  // :118
-    hipLaunchKernelGGL(k64l_project_out, dim3(eg), dim3(kThreads), 0, st, l.r, q_mat, l.coef, m, iB, iN, iP, V);
+    hipLaunchKernelGGL(k64l_project_out, eg, dim3(kThreads), 0, st, l.r, q_mat, l.coef, m, iB, iN, iP, V);
     normalise(l.r, l.r);
     if ((rc = copy_small(tm(k, k + 1), l.nrm)) || (rc = copy_small(tm(k + 1, k), l.nrm))) return rc;
     LO_LAUNCH_CHECK();
@@ -194,16 +190,15 @@ extern "C" int lo_lanczos_tridiag_f64(const double* A, const double* diag, lo_ma
       hipLaunchKernelGGL(k64l_flags, dim3(1), dim3(kThreads), 0, st, l.coef, (int)((size_t)m * S), tol, tm(k, k + 1),
                          (int)S, l.flags);
       LO_LAUNCH_CHECK();
-      LO_HIP_CHECK(hipMemcpyAsync(h, l.flags, sizeof(h), hipMemcpyDeviceToHost, st));
-      LO_HIP_CHECK(hipStreamSynchronize(st));
+      if ((rc = f64_read_back(h, l.flags, st, 2))) return rc;
       if (!h[0]) {
         could = true;
         break;
       }
-      hipLaunchKernelGGL(k64l_project_out, dim3(eg), dim3(kThreads), 0, st, l.r, q_mat, l.coef, m, iB, iN, iP, V);
+      hipLaunchKernelGGL(k64l_project_out, eg, dim3(kThreads), 0, st, l.r, q_mat, l.coef, m, iB, iN, iP, V);
       normalise(l.r, l.r);
     }
-    hipLaunchKernelGGL(k64l_sub_scaled, dim3(eg), dim3(kThreads), 0, st, l.r, (const double*)nullptr,
+    hipLaunchKernelGGL(k64l_sub_scaled, eg, dim3(kThreads), 0, st, l.r, (const double*)nullptr,
                        (const double*)nullptr, qv(k + 1), iN, iP, V);  // :145
     LO_LAUNCH_CHECK();
     if (h[1] == 0 || !could) break;  // :147

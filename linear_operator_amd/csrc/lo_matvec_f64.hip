@@ -20,7 +20,7 @@
 // The kernel kind is the exception to the second half: its column split follows ko_shape(B, M, N), as in
 // lo_kernel_mv_f32, so the order of its partial sums depends on B; two calls on the same inputs still give equal bits.
 // No float64 atomics.
-#include "lo_internal.h"
+#include "lo_f64_solver.h"
 
 #include <algorithm>
 
@@ -336,8 +336,7 @@ static int lr_run(const double* C, int64_t B, int64_t N, int64_t R, int64_t c, c
     hipLaunchKernelGGL(k64_lr_tn<1>, grid, dim3(kThreads), 0, st, C, v, tpart, (int)N, (int)R, (int)c, g.S, g.RLc, g.RPP,
                        g.aligned);
   LO_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k64_lr_finish, dim3((unsigned)((total + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, tpart, t,
-                     g.S, (int)(R * c), total);
+  hipLaunchKernelGGL(k64_lr_finish, elem_grid(total), dim3(kThreads), 0, st, tpart, t, g.S, (int)(R * c), total);
   LO_LAUNCH_CHECK();
   if (g.VEC == 2)
     hipLaunchKernelGGL(k64_lr_nn<2>, grid, dim3(kThreads), 0, st, C, t, dd, dmode, v, y, (int)N, (int)R, (int)c, g.S,
@@ -354,11 +353,13 @@ static bool kron_shape_ok(int64_t B, int64_t n1, int64_t n2, int64_t c) {
          n2 * c <= 0x7ffffff0 && (n1 + kGT - 1) / kGT <= 65535 && (n2 + kGT - 1) / kGT <= 65535;
 }
 
+static double* kron_layout(int64_t B, int64_t N, int64_t c, Arena& ar) { return ar.take<double>((size_t)B * N * c); }
+
 static int kron_run(const double* K1, const double* K2, int64_t B, int64_t n1, int64_t n2, int64_t c, const double* dd,
                     int dmode, int accumulate, const double* v, double* y, Arena& ar, hipStream_t st) {
   if (!kron_shape_ok(B, n1, n2, c)) return LO_ERR_UNSUPPORTED;
   const int64_t N = n1 * n2;
-  double* tmp = ar.take<double>((size_t)B * N * c);
+  double* tmp = kron_layout(B, N, c, ar);
   if (!ar.ok) return LO_ERR_WORKSPACE;
   KronGemm a{};  // tmp[i1, k2, j] = sum_i2 K2[k2, i2] v[i1, i2, j]
   a.A = K2, a.X = v, a.out = tmp;
@@ -386,18 +387,19 @@ static bool plain_kind(int kind) {
   return kind == LO_OP_LOWRANK_DIAG || kind == LO_OP_DENSE_DIAG || kind == LO_OP_KRON_DIAG || kind == LO_OP_KERNEL_DIAG;
 }
 
-// bytes of one plain term (lay out with a null arena)
-static size_t term_bytes(const lo_op_desc* op, int64_t c) {
-  Arena ar(nullptr, 0);
+constexpr size_t kMv64Tail = 1024, kPre64Tail = 1024;  // what the matvec / preconditioner sizer reports behind its layout
+
+// What term_run takes for one term, through the layout function of the term's kind: nothing for the dense kind, for a
+// kind lo_matvec_f64 refuses and for a kernel term its check refuses.
+static void term_layout(const lo_op_desc* op, int64_t c, Arena& ar) {
   if (op->kind == LO_OP_LOWRANK_DIAG) {
     double *a, *b;
     lr_layout(op->B, op->N, op->R, c, ar, &a, &b);
   } else if (op->kind == LO_OP_KRON_DIAG) {
-    ar.take<double>((size_t)op->B * op->N * c);
+    kron_layout(op->B, op->N, c, ar);
   } else if (op->kind == LO_OP_KERNEL_DIAG) {
     if (kernel_desc_check_f64(op, c) == LO_OK) kernel_mv_layout_f64(ar, op->B, op->N, op->N, c);
   }
-  return ar.off;
 }
 
 static int term_run(const lo_op_desc* op, const double* dd, int dmode, int accumulate, const double* v, double* y,
@@ -429,7 +431,7 @@ static int kernel_term_check(const lo_op_desc* op, int64_t c, size_t ws_bytes, c
   if (op->kind != LO_OP_KERNEL_DIAG) return LO_OK;
   const int rc = kernel_desc_check_f64(op, c);
   if (rc) return rc;
-  const size_t need = term_bytes(op, c);
+  const size_t need = measured(0, [&](Arena& ar) { term_layout(op, c, ar); });
   return (need > ws_bytes || (need && !ws)) ? LO_ERR_WORKSPACE : LO_OK;
 }
 
@@ -444,15 +446,15 @@ using namespace lo;
 
 extern "C" size_t lo_matvec_f64_workspace_bytes(const lo_op_desc* op, int64_t c) {
   if (!op || c < 1 || op->B < 1 || op->N < 1) return 0;
-  size_t need = 0;
-  if (op->kind == LO_OP_SUM) {
-    if (!op->terms || op->nterms < 2 || op->nterms > LO_MAX_TERMS) return 0;
-    for (int i = 0; i < op->nterms; ++i)
-      if (plain_kind(op->terms[i].kind)) need = std::max(need, term_bytes(&op->terms[i], c));
-  } else if (plain_kind(op->kind)) {
-    need = term_bytes(op, c);
-  }
-  return need + 1024;
+  if (op->kind != LO_OP_SUM) return measured(kMv64Tail, [&](Arena& ar) { term_layout(op, c, ar); });
+  if (!op->terms || op->nterms < 2 || op->nterms > LO_MAX_TERMS) return 0;
+  return measured(kMv64Tail, [&](Arena& ar) {  // (the terms share the workspace: the largest of them)
+    for (int i = 0; i < op->nterms; ++i) {
+      Arena term(nullptr, 0);
+      term_layout(&op->terms[i], c, term);
+      ar.off = std::max(ar.off, term.off);
+    }
+  });
 }
 
 extern "C" int lo_matvec_f64(const lo_op_desc* op, const double* v, double* y, int64_t c, void* ws, size_t ws_bytes,
@@ -492,10 +494,8 @@ extern "C" int lo_matvec_desc_cb_f64(void* user, const double* v, double* y, int
 
 extern "C" size_t lo_precond_f64_workspace_bytes(int64_t B, int64_t N, int32_t k, int64_t c) {
   if (B < 1 || N < 1 || k < 1 || c < 1) return 0;
-  Arena ar(nullptr, 0);
   double *a, *b;
-  lr_layout(B, N, k, c, ar, &a, &b);
-  return ar.off + 1024;
+  return measured(kPre64Tail, [&](Arena& ar) { lr_layout(B, N, k, c, ar, &a, &b); });
 }
 
 extern "C" int lo_precond_desc_cb_f64(void* user, const double* r, double* z, int64_t B, int64_t N, int64_t c,

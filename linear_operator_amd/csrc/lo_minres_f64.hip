@@ -6,7 +6,7 @@
 // formulation: one preconditioned Lanczos recurrence (z, q, alpha, beta) shared by the Q shifts, the Givens recurrences
 // of every shift as scalars [Q, B, c], two search vectors and the solution per shift [Q, B, N, c]; a dense fp64 operator
 // (k64_dense_mv) or a closure called back once per iteration; the preconditioner is a closure or absent.
-#include "lo_internal.h"
+#include "lo_f64_solver.h"
 
 #include <algorithm>
 #include <math.h>
@@ -182,6 +182,7 @@ struct LayM64 {
   double *ss_sc, *ss_sol;  // [Q, B, c]
 };
 
+constexpr size_t kMr64Tail = 1024;  // what lo_minres_f64_workspace_bytes reports behind the layout
 static void lay_m64(int64_t B, int64_t N, const lo_minres_params_f64* prm, Arena& ar, LayM64* l) {
   const size_t V = (size_t)B * N * prm->c, S = (size_t)B * prm->c, Q = (size_t)prm->n_shifts;
   l->ctl = ar.take<Mr64Ctl>(1);
@@ -201,18 +202,18 @@ static void lay_m64(int64_t B, int64_t N, const lo_minres_params_f64* prm, Arena
 using namespace lo;
 
 extern "C" size_t lo_minres_f64_workspace_bytes(int64_t B, int64_t N, const lo_minres_params_f64* prm) {
-  Arena ar(nullptr, 0);
   LayM64 l;
-  lay_m64(B, N, prm, ar, &l);
-  return ar.off + 1024;
+  return measured(kMr64Tail, [&](Arena& ar) { lay_m64(B, N, prm, ar, &l); });
 }
 
 extern "C" int lo_minres_f64(const double* A, const double* diag, lo_matvec_cb_f64 matvec, void* matvec_user,
                              lo_matvec_cb_f64 precond_cb, void* precond_user, const lo_minres_params_f64* prm,
                              int64_t B, int64_t N, const double* rhs, const double* shifts, double* x, void* ws,
                              size_t ws_bytes, lo_minres_info_f64* info, void* stream) {
-  if (!prm || !rhs || !x || !info || !shifts || (!A && !matvec)) return LO_ERR_BADARG;
+  if (!prm || !rhs || !x || !info || !shifts) return LO_ERR_BADARG;
   const int64_t c = prm->c;
+  const F64Operand opd{A, diag, matvec, matvec_user, precond_cb, precond_user, B, N, c, stream};
+  if (!opd.valid()) return LO_ERR_BADARG;
   const int Q = prm->n_shifts;
   if (B < 1 || N < 1 || c < 1 || Q < 1 || N > 0x7ffffff0 || (int64_t)Q * B > 65535 || (int64_t)Q * B * c > (1 << 30))
     return LO_ERR_UNSUPPORTED;
@@ -224,43 +225,34 @@ extern "C" int lo_minres_f64(const double* A, const double* diag, lo_matvec_cb_f
   const size_t V = (size_t)B * N * c, QV = (size_t)Q * V;
   const int S = (int)(B * c), QS = Q * S;
   const double value = prm->has_value ? prm->value : 1.0;
-  auto eg = [](size_t n) { return dim3((unsigned)((n + kThreads - 1) / kThreads)); };
-  const dim3 blk(kThreads);
+  const dim3 blk(kThreads), gV = elem_grid(V), gS = elem_grid(S), gQS = elem_grid(QS), gQV = elem_grid(QV);
   memset(info, 0, sizeof(*info));
 
-  auto apply_op = [&](const double* v, double* y) -> int {
-    if (A) return f64_dense_mv(A, diag, v, y, B, N, c, st);
-    return matvec(matvec_user, v, y, B, N, c, stream) ? LO_ERR_LAUNCH : LO_OK;
-  };
-  auto apply_pre = [&](const double* v, double* y) -> int {
-    if (precond_cb) return precond_cb(precond_user, v, y, B, N, c, stream) ? LO_ERR_LAUNCH : LO_OK;
-    return f64_copy(v, y, V, st);
-  };
   int rc;
   LO_HIP_CHECK(hipMemsetAsync(l.ctl, 0, sizeof(Mr64Ctl), st));
   // rhs norms and the zero mask (:52-56); z1 = rhs / norm
   if ((rc = f64_dots(rhs, rhs, l.nsq, nullptr, nullptr, nullptr, B, N, c, st))) return rc;
-  hipLaunchKernelGGL(k64m_normalise, eg(V), blk, 0, st, rhs, l.nsq, l.z1, l.rn, l.rz, (int)N, (int)c, V);
+  hipLaunchKernelGGL(k64m_normalise, gV, blk, 0, st, rhs, l.nsq, l.z1, l.rn, l.rz, (int)N, (int)c, V);
   LO_LAUNCH_CHECK();
   int matvecs = 0;
   // the reference spends one product on the shapes (:66-68): a closure sees the same number of calls here
   if (!A) {
-    if ((rc = apply_op(l.z1, l.prod))) return rc;
+    if ((rc = opd.op(l.z1, l.prod))) return rc;
   }
   ++matvecs;
   LO_HIP_CHECK(hipMemsetAsync(l.z2, 0, sizeof(double) * V, st));
   LO_HIP_CHECK(hipMemsetAsync(l.s1, 0, sizeof(double) * QV, st));
   LO_HIP_CHECK(hipMemsetAsync(l.s2, 0, sizeof(double) * QV, st));
   LO_HIP_CHECK(hipMemsetAsync(l.sol, 0, sizeof(double) * QV, st));
-  if ((rc = apply_pre(l.z1, l.q1))) return rc;                                              // :76-79
+  if ((rc = opd.pre(l.z1, l.q1))) return rc;                                              // :76-79
   if ((rc = f64_dots(l.z1, l.q1, l.dot, nullptr, nullptr, nullptr, B, N, c, st))) return rc;  // :80
-  hipLaunchKernelGGL(k64m_sqrt, eg(S), blk, 0, st, l.dot, -1.0, l.beta_prev, S);
-  hipLaunchKernelGGL(k64m_div2, eg(V), blk, 0, st, l.z1, l.q1, l.beta_prev, (int)N, (int)c, V);  // :81-83
-  hipLaunchKernelGGL(k64m_fill, eg(QS), blk, 0, st, l.rot.cos1, 1.0, (size_t)QS);               // :96-111
-  hipLaunchKernelGGL(k64m_fill, eg(QS), blk, 0, st, l.rot.cos2, 1.0, (size_t)QS);
+  hipLaunchKernelGGL(k64m_sqrt, gS, blk, 0, st, l.dot, -1.0, l.beta_prev, S);
+  hipLaunchKernelGGL(k64m_div2, gV, blk, 0, st, l.z1, l.q1, l.beta_prev, (int)N, (int)c, V);  // :81-83
+  hipLaunchKernelGGL(k64m_fill, gQS, blk, 0, st, l.rot.cos1, 1.0, (size_t)QS);               // :96-111
+  hipLaunchKernelGGL(k64m_fill, gQS, blk, 0, st, l.rot.cos2, 1.0, (size_t)QS);
   LO_HIP_CHECK(hipMemsetAsync(l.rot.sin1, 0, sizeof(double) * QS, st));
   LO_HIP_CHECK(hipMemsetAsync(l.rot.sin2, 0, sizeof(double) * QS, st));
-  hipLaunchKernelGGL(k64m_bcast, eg(QS), blk, 0, st, l.beta_prev, l.rot.scale_prev, S, QS);      // :113
+  hipLaunchKernelGGL(k64m_bcast, gQS, blk, 0, st, l.beta_prev, l.rot.scale_prev, S, QS);      // :113
   LO_LAUNCH_CHECK();
 
   double *z1 = l.z1, *z2 = l.z2, *zc = l.zc, *q1 = l.q1, *qc = l.qc, *s1 = l.s1, *s2 = l.s2;
@@ -270,18 +262,18 @@ extern "C" int lo_minres_f64(const double* A, const double* diag, lo_matvec_cb_f
   const int n_loop = prm->max_iter + 2;  // :134
   int it = 0;
   for (; it < n_loop; ++it) {
-    if ((rc = apply_op(q1, l.prod))) return rc;  // :137-139
+    if ((rc = opd.op(q1, l.prod))) return rc;  // :137-139
     ++matvecs;
     if ((rc = f64_dots(l.prod, q1, l.dot, nullptr, nullptr, nullptr, B, N, c, st))) return rc;
-    hipLaunchKernelGGL(k64m_zc, eg(V), blk, 0, st, l.prod, z1, z2, l.dot, beta_prev, value, zc, l.alpha, (int)N, (int)c, V);
+    hipLaunchKernelGGL(k64m_zc, gV, blk, 0, st, l.prod, z1, z2, l.dot, beta_prev, value, zc, l.alpha, (int)N, (int)c, V);
     LO_LAUNCH_CHECK();
-    if ((rc = apply_pre(zc, qc))) return rc;     // :145-146
+    if ((rc = opd.pre(zc, qc))) return rc;     // :145-146
     if ((rc = f64_dots(zc, qc, l.dot, nullptr, nullptr, nullptr, B, N, c, st))) return rc;
-    hipLaunchKernelGGL(k64m_sqrt, eg(S), blk, 0, st, l.dot, prm->eps, beta, S);              // :147-150
-    hipLaunchKernelGGL(k64m_div2, eg(V), blk, 0, st, zc, qc, beta, (int)N, (int)c, V);        // :151-152
-    hipLaunchKernelGGL(k64m_givens, eg(QS), blk, 0, st, l.rot, l.alpha, beta, beta_prev, shifts,
+    hipLaunchKernelGGL(k64m_sqrt, gS, blk, 0, st, l.dot, prm->eps, beta, S);              // :147-150
+    hipLaunchKernelGGL(k64m_div2, gV, blk, 0, st, zc, qc, beta, (int)N, (int)c, V);        // :151-152
+    hipLaunchKernelGGL(k64m_givens, gQS, blk, 0, st, l.rot, l.alpha, beta, beta_prev, shifts,
                        prm->shifts_per_member, Q, (int)B, (int)c);
-    hipLaunchKernelGGL(k64m_update, eg(QV), blk, 0, st, q1, s1, s2, l.sol, l.rot, (int)N, (int)c, V, QV);
+    hipLaunchKernelGGL(k64m_update, gQV, blk, 0, st, q1, s1, s2, l.sol, l.rot, (int)N, (int)c, V, QV);
     LO_LAUNCH_CHECK();
     std::swap(s1, s2);  // the new search vector (written over s2) is s1 from now on, the old s1 becomes s2
     if ((it + 1) % 10 == 0) {  // :178-183
@@ -289,8 +281,7 @@ extern "C" int lo_minres_f64(const double* A, const double* diag, lo_matvec_cb_f
       hipLaunchKernelGGL(k64m_conv, dim3(1), blk, 0, st, l.ss_sc, l.ss_sol, l.rot.scale_now, prm->tolerance, it, QS,
                          l.ctl);
       LO_LAUNCH_CHECK();
-      LO_HIP_CHECK(hipMemcpyAsync(&h, l.ctl, sizeof(h), hipMemcpyDeviceToHost, st));
-      LO_HIP_CHECK(hipStreamSynchronize(st));
+      if ((rc = f64_read_back(&h, l.ctl, st))) return rc;
       if (h.stop) {
         ++it;
         break;
@@ -302,7 +293,7 @@ extern "C" int lo_minres_f64(const double* A, const double* diag, lo_matvec_cb_f
     std::swap(q1, qc);
     std::swap(beta, beta_prev);
   }
-  hipLaunchKernelGGL(k64m_final, eg(QV), blk, 0, st, l.sol, l.rn, l.rz, x, (int)N, (int)c, V, QV);
+  hipLaunchKernelGGL(k64m_final, gQV, blk, 0, st, l.sol, l.rn, l.rz, x, (int)N, (int)c, V, QV);
   LO_LAUNCH_CHECK();
   LO_HIP_CHECK(hipStreamSynchronize(st));
   info->iterations = it;

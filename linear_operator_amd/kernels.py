@@ -242,6 +242,36 @@ def _f64_precond(lib, precond, batch_shape, B: int, N: int, c: int, dev):
     return C.cast(lib.lo_precond_desc_cb_f64, _hip.MATVEC_CB), C.cast(C.pointer(ctx), C.c_void_p), (Q3, n2, ws, ctx)
 
 
+def _f64_operands(lib, A, diag, desc, matvec_closure, precond, precond_closure, bshape, B: int, N: int, c: int, dev):
+    """The operator and the preconditioner of a float64 solver call, the one rule of cg_solve_f64, minres_solve_f64 and
+    lanczos_tridiag_f64.  Operator: the float64 descriptor `desc` (lo_matvec_desc_cb_f64, inside the library), else the
+    dense `A` (+ `diag`), else `matvec_closure`.  Preconditioner: the native pair `precond` (lo_precond_desc_cb_f64),
+    else `precond_closure`, else none.  Returns (A3, d2, mv_cb, mv_user, pc_cb, pc_user, the error lists for _launch,
+    what has to stay alive until the solver returns)."""
+    A3 = d2 = mv_user = pc_user = mv_keep = pc_keep = None
+    mv_err, (pc_cb, pc_err) = (), _NO_CLOSURE
+    if desc is not None:
+        mv_cb, mv_user, mv_keep = _f64_operator(lib, desc, B, N, c, dev)
+    else:
+        A3, d2 = _dense_f64(A, diag, matvec_closure, bshape, B, N)
+        mv_cb, mv_err = _wrap_closure(matvec_closure, dev, bshape, "<f8") if A3 is None else _NO_CLOSURE
+    if precond is not None:
+        pc_cb, pc_user, pc_keep = _f64_precond(lib, precond, bshape, B, N, c, dev)
+    elif precond_closure is not None:
+        pc_cb, pc_err = _wrap_closure(precond_closure, dev, bshape, "<f8")
+    return A3, d2, mv_cb, mv_user, pc_cb, pc_user, (mv_err, pc_err), (mv_keep, pc_keep)
+
+
+def _f32_operator(desc: Optional["OperatorDescriptor"], matvec_closure, bshape, B: int, N: int, dev):
+    """The operator of a float32 solver that takes a descriptor or a closure (MINRES, Lanczos): (the struct of `desc`,
+    else of the callback descriptor; the closure's callback; the list its exceptions are kept in)."""
+    if desc is not None:
+        return (desc.c_struct(), *_NO_CLOSURE)
+    if matvec_closure is None:
+        raise ValueError("need an operator descriptor or a matvec closure")
+    return (_callback_desc(B, N), *_wrap_closure(matvec_closure, dev, bshape))
+
+
 def precond_apply_f64(Q: torch.Tensor, noise: torch.Tensor, constant_diag: bool, r: torch.Tensor) -> torch.Tensor:
     """z = r / d - Q (Q^T r) (or (r - Q Q^T r) / sigma, constant_diag) in float64: one call of lo_precond_desc_cb_f64, the
     function the float64 solvers call per iteration.  r [*batch, N, c]."""
@@ -1283,16 +1313,10 @@ def minres_solve(desc: Optional[OperatorDescriptor], rhs: torch.Tensor, shifts: 
     dev = rhs.device
     rhs3, sh, prm, x = _minres_operands(rhs, shifts, value, max_iter, tolerance, eps, _hip.MinresParams)
     B = rhs3.shape[0]
-    if desc is None:
-        if matvec_closure is None:
-            raise ValueError("need an operator descriptor or a matvec closure")
-        s = _callback_desc(B, N)
-    else:
-        if desc.B != B or desc.N != N:
-            raise RuntimeError(f"minres: rhs {tuple(rhs.shape)} does not match operator batch {desc.B}, N {desc.N}")
-        s = desc.c_struct()
+    if desc is not None and (desc.B != B or desc.N != N):
+        raise RuntimeError(f"minres: rhs {tuple(rhs.shape)} does not match operator batch {desc.B}, N {desc.N}")
     bshape = tuple(closure_batch_shape) if closure_batch_shape is not None else tuple(rhs.shape[:-2])
-    mv_cb, mv_err = _wrap_closure(matvec_closure, dev, bshape) if desc is None else _NO_CLOSURE
+    s, mv_cb, mv_err = _f32_operator(desc, matvec_closure, bshape, B, N, dev)
     pc_cb, pc_err = _wrap_closure(precond_closure, dev, bshape) if precond_closure is not None else _NO_CLOSURE
     pre_s = precond.ensure_q().c_struct() if precond is not None else None  # (MINRES applies the Q form)
     info = _hip.MinresInfo()
@@ -1319,22 +1343,12 @@ def minres_solve_f64(A: Optional[torch.Tensor], rhs: torch.Tensor, shifts: torch
     bshape = tuple(rhs.shape[:-2])
     rhs3, sh, prm, x = _minres_operands(rhs, shifts, value, max_iter, tolerance, eps, _hip.MinresParamsF64)
     B = rhs3.shape[0]
-    mv_user, keep = None, None
-    if desc is not None:
-        A3, (mv_cb, mv_user, keep), mv_err = None, _f64_operator(lib, desc, B, N, rhs.shape[-1], dev), ()
-    else:
-        A3, _ = _dense_f64(A, None, matvec_closure, bshape, B, N)
-        mv_cb, mv_err = _wrap_closure(matvec_closure, dev, bshape, "<f8") if A3 is None else _NO_CLOSURE
-    pc_user, pc_keep = None, None
-    if precond is not None:
-        (pc_cb, pc_user, pc_keep), pc_err = _f64_precond(lib, precond, bshape, B, N, rhs.shape[-1], dev), ()
-    else:
-        pc_cb, pc_err = (_wrap_closure(precond_closure, dev, bshape, "<f8") if precond_closure is not None
-                         else _NO_CLOSURE)
+    A3, d2, mv_cb, mv_user, pc_cb, pc_user, errors, keep = _f64_operands(
+        lib, A, None, desc, matvec_closure, precond, precond_closure, bshape, B, N, rhs.shape[-1], dev)
     info = _hip.MinresInfoF64()
-    _launch("lo_minres_f64", dev, A3, None, mv_cb, mv_user, pc_cb, pc_user, C.byref(prm), B, N, rhs3, sh, x,
-            ws_bytes=lib.lo_minres_f64_workspace_bytes(B, N, C.byref(prm)), info=info, errors=(mv_err, pc_err))
-    del keep, pc_keep
+    _launch("lo_minres_f64", dev, A3, d2, mv_cb, mv_user, pc_cb, pc_user, C.byref(prm), B, N, rhs3, sh, x,
+            ws_bytes=lib.lo_minres_f64_workspace_bytes(B, N, C.byref(prm)), info=info, errors=errors)
+    del keep  # (the solver is synchronous: the contexts and workspaces of the callbacks were needed until here)
     return _minres_result(x, rhs, info)
 
 
@@ -1685,28 +1699,15 @@ def cg_solve_f64(A: Optional[torch.Tensor], diag: Optional[torch.Tensor], rhs: t
     dev = rhs.device
     bshape = tuple(rhs.shape[:-2])
     x03 = None if x0 is None else _flat(x0.expand_as(rhs), 2)
-    mv_user, pc_user, keep = None, None, []
-    if desc is not None:
-        A3, d2, mv_err = None, None, ()
-        mv_cb, mv_user, alive = _f64_operator(lib, desc, B, N, c, dev)
-        keep.append(alive)
-    else:
-        A3, d2 = _dense_f64(A, diag, matvec_closure, bshape, B, N)
-        mv_cb, mv_err = _wrap_closure(matvec_closure, dev, bshape, "<f8") if A3 is None else _NO_CLOSURE
-    if precond is not None:
-        pc_cb, pc_user, alive = _f64_precond(lib, precond, bshape, B, N, c, dev)
-        pc_err = ()
-        keep.append(alive)
-    else:
-        pc_cb, pc_err = (_wrap_closure(precond_closure, dev, bshape, "<f8") if precond_closure is not None
-                         else _NO_CLOSURE)
+    A3, d2, mv_cb, mv_user, pc_cb, pc_user, errors, keep = _f64_operands(
+        lib, A, diag, desc, matvec_closure, precond, precond_closure, bshape, B, N, c, dev)
     prm = _cg_params(c, n_tridiag, max_iter, max_tridiag_iter, tolerance, eps, stop_updating_after, floor_max_iter,
                      _hip.CgParamsF64)
     x = torch.empty_like(rhs3)
     t_mat = _tridiag_buffer(n_tridiag, B, max_tridiag_iter, rhs3)
     info = _hip.CgInfoF64()
     _launch("lo_cg_solve_f64", dev, A3, d2, mv_cb, mv_user, pc_cb, pc_user, C.byref(prm), B, N, rhs3, x03, x, t_mat,
-            ws_bytes=lib.lo_cg_f64_workspace_bytes(B, N, C.byref(prm)), info=info, errors=(mv_err, pc_err))
+            ws_bytes=lib.lo_cg_f64_workspace_bytes(B, N, C.byref(prm)), info=info, errors=errors)
     del keep  # (the solver is synchronous: the contexts and workspaces of the callbacks were needed until here)
     return _cg_result(x.reshape(rhs.shape), t_mat, info)
 
@@ -1968,10 +1969,7 @@ def lanczos_tridiag(desc: Optional[OperatorDescriptor], init_vecs: torch.Tensor,
     v3 = _flat(init_vecs, 2)
     B = v3.shape[0]
     dev = init_vecs.device
-    if desc is None and matvec_closure is None:
-        raise ValueError("need an operator descriptor or a matvec closure")
-    s = _callback_desc(B, N) if desc is None else desc.c_struct()
-    cb, err = _wrap_closure(matvec_closure, dev, batch) if desc is None else _NO_CLOSURE
+    s, cb, err = _f32_operator(desc, matvec_closure, batch, B, N, dev)
     max_iter = int(max_iter)
     q, t = _lanczos_buffers(max_iter, v3)
     iters = C.c_int32(0)
@@ -2029,18 +2027,13 @@ def lanczos_tridiag_f64(A: Optional[torch.Tensor], diag: Optional[torch.Tensor],
     v3 = _flat(init_vecs, 2)
     B = v3.shape[0]
     dev = init_vecs.device
-    user, keep = None, None
-    if desc is not None:
-        A3, d2, err = None, None, ()
-        cb, user, keep = _f64_operator(lib, desc, B, N, P, dev)
-    else:
-        A3, d2 = _dense_f64(A, diag, matvec_closure, batch, B, N)
-        cb, err = _wrap_closure(matvec_closure, dev, batch, "<f8") if A3 is None else _NO_CLOSURE
+    A3, d2, cb, user, _, _, errors, keep = _f64_operands(lib, A, diag, desc, matvec_closure, None, None, batch, B, N, P,
+                                                         dev)
     max_iter = int(max_iter)
     q, t = _lanczos_buffers(max_iter, v3)
     iters = C.c_int32(0)
     _launch("lo_lanczos_tridiag_f64", dev, A3, d2, cb, user, v3, B, N, P, max_iter, float(tol), q, t, C.byref(iters),
-            ws_bytes=lib.lo_lanczos_f64_workspace_bytes(B, N, P, max_iter), errors=(err,))
+            ws_bytes=lib.lo_lanczos_f64_workspace_bytes(B, N, P, max_iter), errors=errors)
     del keep
     return _lanczos_out(q, t, iters.value, batch)
 

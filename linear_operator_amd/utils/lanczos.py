@@ -6,7 +6,8 @@ import torch
 
 from .. import settings
 from .. import kernels as K
-from .linear_cg import _lower_f64, _lower_matmul_closure
+# (_lower_f64: tests/test_gpu_f64_desc.py switches the lowering off in every front end)
+from .linear_cg import _f64_operands, _lower_f64, _lower_matmul_closure  # noqa: F401
 
 
 def lanczos_tridiag(
@@ -43,11 +44,9 @@ def lanczos_tridiag(
             f"Running Lanczos on a {matrix_shape} matrix with a {init_vecs.shape} RHS for {num_iter} iterations."
         )
     if init_vecs.dtype == torch.float64:  # the reference is dtype-generic; fp64 runs csrc/lo_lanczos_f64.hip
-        if torch.is_tensor(matmul_closure):
-            return K.lanczos_tridiag_f64(matmul_closure, None, init_vecs.contiguous(), num_iter, tol=tol)
-        desc = _lower_f64(matmul_closure, init_vecs.shape[:-2], init_vecs.shape[-1]) if init_vecs.is_cuda else None
-        return K.lanczos_tridiag_f64(None, None, init_vecs.contiguous(), num_iter, tol=tol, desc=desc,
-                                     matvec_closure=None if desc is not None else matmul_closure)
+        dense, operands = _f64_operands(matmul_closure, None, init_vecs.shape[:-2], init_vecs.shape[-1],
+                                        init_vecs.is_cuda)
+        return K.lanczos_tridiag_f64(dense, None, init_vecs.contiguous(), num_iter, tol=tol, **operands)
     desc = _lower_matmul_closure(matmul_closure, init_vecs.shape[:-2])
     closure = None
     if desc is None:

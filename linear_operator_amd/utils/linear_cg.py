@@ -128,6 +128,33 @@ def _lower_f64(matmul_closure, batch_shape, cols: int = 1):
     return desc
 
 
+def _f64_operands(matmul_closure, preconditioner, batch_shape, cols: int, is_cuda: bool):
+    """The one rule of linear_cg, minres and lanczos_tridiag for a float64 solve: (the dense tensor or None, the keyword
+    arguments desc= and matvec_closure= of the kernels.*_f64 wrappers, with a preconditioner precond= and
+    precond_closure= too).  A tensor is multiplied by the library's fp64 kernel, the bound `_matmul` of an operator that
+    lowers to a float64 descriptor by lo_matvec_f64, the dense Woodbury closure of AddedDiagLinearOperator is applied
+    inside the library too; any other closure or preconditioner is called back."""
+    dense = matmul_closure if torch.is_tensor(matmul_closure) and matmul_closure.dim() >= 2 else None
+    desc = _lower_f64(matmul_closure, batch_shape, cols) if is_cuda else None
+    kwargs = dict(desc=desc, matvec_closure=None if dense is not None or desc is not None else (
+        matmul_closure.matmul if torch.is_tensor(matmul_closure) else matmul_closure))
+    if preconditioner is not None:
+        native_pre = _native_precond_f64(preconditioner) if is_cuda else None
+        kwargs.update(precond=native_pre, precond_closure=None if native_pre is not None else preconditioner)
+    return dense, kwargs
+
+
+def _f32_precond(preconditioner, batch_shape):
+    """(woodbury, precond_closure) of a float32 solve: the WoodburyPreconditioner the callable carries when it was built
+    for this batch size, else the callable itself to be called back; (None, None) without a preconditioner."""
+    if preconditioner is None:
+        return None, None
+    woodbury = getattr(preconditioner, "woodbury", None)
+    if woodbury is not None and int(woodbury.dinv.shape[0]) != max(1, batch_shape.numel()):
+        woodbury = None
+    return woodbury, (preconditioner if woodbury is None else None)
+
+
 def linear_cg(
     matmul_closure,
     rhs,
@@ -190,21 +217,12 @@ def linear_cg(
         )
 
     if rhs.dtype == torch.float64:
-        # the reference's fp64 recipes (test/utils/test_linear_cg.py): a dense tensor is multiplied by the library's
-        # fp64 kernel, the bound `_matmul` of an operator that lowers to a float64 descriptor by lo_matvec_f64, and the
-        # dense Woodbury closure of AddedDiagLinearOperator is applied inside the library too; any other closure or
-        # preconditioner is called back.  No resident engines.
+        # the reference's fp64 recipes (test/utils/test_linear_cg.py), operands by _f64_operands.  No resident engines.
         if _active_stop_reduce() is not None:
             raise NotImplementedError("the batch-global stopping rule over ranks is fp32 only")
-        dense = matmul_closure if torch.is_tensor(matmul_closure) and matmul_closure.dim() >= 2 else None
-        desc = _lower_f64(matmul_closure, batch_shape, rhs.shape[-1]) if rhs.is_cuda else None
-        native_pre = _native_precond_f64(preconditioner) if rhs.is_cuda else None
+        dense, operands = _f64_operands(matmul_closure, preconditioner, batch_shape, rhs.shape[-1], rhs.is_cuda)
         res = K.cg_solve_f64(
-            dense, None, rhs, x0=initial_guess, desc=desc, precond=native_pre,
-            matvec_closure=None if dense is not None or desc is not None else (
-                matmul_closure.matmul if torch.is_tensor(matmul_closure) else matmul_closure),
-            precond_closure=None if native_pre is not None else preconditioner,
-            n_tridiag=n_tridiag, max_iter=n_iter, max_tridiag_iter=n_tridiag_iter,
+            dense, None, rhs, x0=initial_guess, **operands, n_tridiag=n_tridiag, max_iter=n_iter, max_tridiag_iter=n_tridiag_iter,
             tolerance=float(tolerance), eps=float(eps), stop_updating_after=float(stop_updating_after),
             floor_max_iter=max_iter,
         )
@@ -235,14 +253,7 @@ def linear_cg(
                         res = fused.cg
             if res is None:
                 preconditioner = lazy.materialize()  # the ordinary three-launch build (or None: NaN in the factor)
-        woodbury, precond_closure = None, None
-        if preconditioner is not None and res is None:
-            woodbury = getattr(preconditioner, "woodbury", None)
-            if woodbury is not None and int(woodbury.dinv.shape[0]) != max(1, batch_shape.numel()):
-                woodbury = None
-            if woodbury is None:
-                precond_closure = preconditioner
-
+        woodbury, precond_closure = _f32_precond(preconditioner if res is None else None, batch_shape)
         res = res if res is not None else K.cg_solve(
             desc, rhs, x0=initial_guess, precond=woodbury, matvec_closure=closure, precond_closure=precond_closure,
             n_tridiag=n_tridiag, max_iter=n_iter, max_tridiag_iter=n_tridiag_iter, tolerance=float(tolerance),

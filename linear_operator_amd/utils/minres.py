@@ -9,7 +9,8 @@ import torch
 
 from .. import kernels as K
 from .. import settings
-from .linear_cg import _lower_f64, _lower_matmul_closure, _native_precond_f64
+# (_lower_f64: tests/test_gpu_f64_desc.py switches the lowering off in every front end)
+from .linear_cg import _f32_precond, _f64_operands, _lower_f64, _lower_matmul_closure  # noqa: F401
 
 
 def minres(matmul_closure, rhs, eps=1e-25, shifts=None, value=None, max_iter=None, preconditioner=None):
@@ -39,46 +40,27 @@ def minres(matmul_closure, rhs, eps=1e-25, shifts=None, value=None, max_iter=Non
 
     sh = shifts.reshape(1) if shifts.dim() == 0 else shifts
     if rhs.dtype == torch.float64:
-        # the reference's fp64 recipes (test/utils/test_minres.py): dense tensors on the library's fp64 kernel, the
-        # bound `_matmul` of an operator with a float64 descriptor on lo_matvec_f64, any other closure / preconditioner
-        # called back (csrc/lo_minres_f64.hip)
-        dense = matmul_closure if torch.is_tensor(matmul_closure) and matmul_closure.dim() >= 2 else None
-        desc = _lower_f64(matmul_closure, batch_shape, rhs_b.shape[-1]) if rhs_b.is_cuda else None
-        native_pre = _native_precond_f64(preconditioner) if rhs_b.is_cuda else None
+        # the reference's fp64 recipes (test/utils/test_minres.py), operands by _f64_operands (csrc/lo_minres_f64.hip)
+        dense, operands = _f64_operands(matmul_closure, preconditioner, batch_shape, rhs_b.shape[-1], rhs_b.is_cuda)
         res = K.minres_solve_f64(
-            dense, rhs_b, sh, value=value, desc=desc, precond=native_pre,
-            matvec_closure=None if dense is not None or desc is not None else (
-                matmul_closure.matmul if torch.is_tensor(matmul_closure) else matmul_closure),
-            precond_closure=None if native_pre is not None else preconditioner, max_iter=max_iter,
+            dense, rhs_b, sh, value=value, **operands, max_iter=max_iter,
             tolerance=float(settings.minres_tolerance.value()), eps=float(eps),
         )
-        solution = res.x
-        if squeeze:
-            solution = solution.squeeze(-1)
-        if shifts.numel() == 1:
-            solution = solution.squeeze(0)
-        return solution
-
-    desc = _lower_matmul_closure(matmul_closure, batch_shape)
-    closure = None
-    if desc is None:
-        closure = matmul_closure.matmul if torch.is_tensor(matmul_closure) else matmul_closure
-    woodbury, precond_closure = None, None
-    if preconditioner is not None:
-        woodbury = getattr(preconditioner, "woodbury", None)
-        if woodbury is not None and int(woodbury.dinv.shape[0]) != max(1, batch_shape.numel()):
-            woodbury = None
-        if woodbury is None:
-            precond_closure = preconditioner
-    if settings.verbose_linalg.on():
-        settings.verbose_linalg.logger.debug(
-            f"Running MINRES on a {rhs.shape} RHS for {max_iter} iterations "
-            f"(tol={settings.minres_tolerance.value()}). Output: {(sh.shape[0], *rhs_b.shape)}."
+    else:
+        desc = _lower_matmul_closure(matmul_closure, batch_shape)
+        closure = None
+        if desc is None:
+            closure = matmul_closure.matmul if torch.is_tensor(matmul_closure) else matmul_closure
+        woodbury, precond_closure = _f32_precond(preconditioner, batch_shape)
+        if settings.verbose_linalg.on():
+            settings.verbose_linalg.logger.debug(
+                f"Running MINRES on a {rhs.shape} RHS for {max_iter} iterations "
+                f"(tol={settings.minres_tolerance.value()}). Output: {(sh.shape[0], *rhs_b.shape)}."
+            )
+        res = K.minres_solve(
+            desc, rhs_b, sh, value=value, precond=woodbury, matvec_closure=closure, precond_closure=precond_closure,
+            max_iter=max_iter, tolerance=float(settings.minres_tolerance.value()), eps=float(eps),
         )
-    res = K.minres_solve(
-        desc, rhs_b, sh, value=value, precond=woodbury, matvec_closure=closure, precond_closure=precond_closure,
-        max_iter=max_iter, tolerance=float(settings.minres_tolerance.value()), eps=float(eps),
-    )
     solution = res.x
     if squeeze:  # :203-206
         solution = solution.squeeze(-1)

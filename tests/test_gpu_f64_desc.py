@@ -386,3 +386,123 @@ def test_user_closures_are_still_called_once_per_product():
         warnings.simplefilter("ignore")
         x = linear_cg(closure, dev(b), max_iter=60, tolerance=1e-8)
     assert calls[0] == info.matvecs and x.dtype == torch.float64
+
+
+# ---- the operand path the three float64 solvers share (kernels._f64_operands, csrc/lo_f64_solver.h) --------------------
+# B = 2 so that a member index exists, N = 5, two columns, two shifts, five steps.  References: the oracle's restatement
+# of each solver on the same numpy operands, computed once, under the float64 bar of this file (1e-9).
+SOLVERS = ("cg", "minres", "lanczos")
+OB, ON, OC, OSTEPS = 2, 5, 2, 5
+
+
+class Operand:
+    """A + diag(d), SPD and well conditioned, with right-hand sides; `dense_desc(with_diag)`: the float64 descriptor."""
+
+    def __init__(self):
+        M = rng(81).standard_normal((OB, ON, ON))
+        self.A = M @ M.swapaxes(-1, -2) / ON + np.eye(ON)
+        self.d = rng(82).random((OB, ON)) + 0.5
+        self.rhs = rng(83).standard_normal((OB, ON, OC))
+        self.shifts = np.array([0.25, 1.5])
+        self.At, self.dt, self.rhst, self.sht = dev(self.A), dev(self.d), dev(self.rhs), dev(self.shifts)
+        self.want = {}
+
+    def dense_desc(self, with_diag):
+        return K.dense_diag_descriptor(self.At, self.dt if with_diag else None, dtype=torch.float64)
+
+    def full(self, with_diag):
+        return self.At + torch.diag_embed(self.dt) if with_diag else self.At
+
+    def reference(self, solver):
+        if solver not in self.want:
+            Ad = self.A + np.einsum("bi,ij->bij", self.d, np.eye(ON))
+            if solver == "cg":
+                x, _, info = orc.linear_cg(lambda v: Ad @ v, self.rhs, max_iter=OSTEPS, max_tridiag_iter=OSTEPS,
+                                            tolerance=1e-12)
+                self.want[solver] = ((x,), info.matvecs)
+            elif solver == "minres":
+                x, info = orc.minres(lambda v: self.A @ v, self.rhs, shifts=self.shifts, max_iter=OSTEPS)
+                self.want[solver] = ((x,), info.iterations)
+            else:
+                self.want[solver] = (orc.lanczos_tridiag(lambda v: Ad @ v, OSTEPS, self.rhs), None)
+        return self.want[solver]
+
+
+@pytest.fixture(scope="module")
+def opd():
+    return Operand()
+
+
+def run_solver(o, solver, **operand):
+    """(output tensors, the count of products (CG) or iterations (MINRES) or None) of one solver call.  `operand`: A= (and diag=), desc= or matvec_closure=
+    (and precond_closure=); CG and Lanczos solve with A + diag(d), MINRES (no diagonal argument) with A."""
+    A, diag = operand.pop("A", None), operand.pop("diag", None)
+    if solver == "cg":
+        res = K.cg_solve_f64(A, diag, o.rhst, max_iter=OSTEPS, max_tridiag_iter=OSTEPS, tolerance=1e-12, **operand)
+        return (res.x,), res.matvecs
+    if solver == "minres":
+        res = K.minres_solve_f64(A, o.rhst, o.sht, max_iter=OSTEPS, **operand)
+        return (res.x,), res.iterations
+    return K.lanczos_tridiag_f64(A, diag, o.rhst, OSTEPS, **operand), None
+
+
+def dense_operand(o, solver):
+    return dict(A=o.At) if solver == "minres" else dict(A=o.At, diag=o.dt)
+
+
+def assert_right(o, solver, got):
+    outs, count = got
+    want, want_count = o.reference(solver)
+    assert count == want_count
+    for a, b in zip(outs, want):
+        err = rel_err(host(a), b)
+        print(solver, "against the oracle", err)
+        assert a.dtype == torch.float64 and tuple(a.shape) == b.shape and err < 1e-9, (solver, err)
+
+
+class ClosureFailure(Exception):
+    pass
+
+
+@pytest.mark.parametrize("solver,which", [(s, "matvec_closure") for s in SOLVERS] +
+                         [(s, "precond_closure") for s in ("cg", "minres")])
+def test_an_exception_inside_a_closure_surfaces_as_itself(opd, solver, which):
+    raised = ClosureFailure(f"{which} of {solver}, member 1")
+
+    def failing(v):
+        raise raised
+
+    full = opd.full(solver != "minres")
+    operand = dict(matvec_closure=failing) if which == "matvec_closure" else dict(
+        matvec_closure=lambda v: full @ v, precond_closure=failing)
+    with pytest.raises(ClosureFailure) as caught:
+        run_solver(opd, solver, **operand)
+    assert caught.value is raised and str(caught.value) == f"{which} of {solver}, member 1"
+    # the device and the library are as they were: the ordinary routes give the right answer
+    assert_right(opd, solver, run_solver(opd, solver, **dense_operand(opd, solver)))
+    closure = dict(matvec_closure=lambda v: full @ v)
+    if solver != "lanczos":
+        closure["precond_closure"] = lambda v: v.clone()
+    assert_right(opd, solver, run_solver(opd, solver, **closure))
+
+
+@pytest.mark.parametrize("solver", SOLVERS)
+def test_dense_tensor_and_dense_descriptor_give_the_same_bits(opd, solver):
+    """Both routes end in k64_dense_mv with the same launch (f64_dense_mv_ex), so an operand wired to the wrong slot of
+    the shared helper -- the diagonal dropped, the descriptor's context in the preconditioner's place -- shows as a
+    different bit.  Bit-equal on the parent commit too (profiles/r16/README.md)."""
+    dense = run_solver(opd, solver, **dense_operand(opd, solver))
+    desc = run_solver(opd, solver, desc=opd.dense_desc(solver != "minres"))
+    assert_right(opd, solver, dense)
+    assert dense[1] == desc[1]
+    for a, b in zip(dense[0], desc[0]):
+        assert torch.equal(a, b), (solver, float((a - b).abs().max()))
+
+
+@pytest.mark.parametrize("solver", SOLVERS)
+def test_the_wrappers_refuse_a_missing_or_mismatched_operator_in_the_same_words(opd, solver):
+    with pytest.raises(ValueError, match="^need a dense fp64 operator or a matvec closure$"):
+        run_solver(opd, solver)
+    other = K.dense_diag_descriptor(dev(np.ones((3, 4, 4))), None, dtype=torch.float64)
+    with pytest.raises(RuntimeError, match=r"^the right-hand side \(batch 2, N 5\) does not match operator batch 3, N 4$"):
+        run_solver(opd, solver, desc=other)

@@ -16,11 +16,13 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 with open(os.path.join(HERE, "golden", "workspace_bytes.json")) as f:
     RECORDED = json.load(f)
 ROWS = [(fn, args, needed) for fn, rows in wc.CASES.items() for args, needed in rows]
+ROWS += [(fn, args, needed) for fn, rows in wc.F64_CASES.items() for args, needed in rows]
 
 
 def test_the_recording_covers_the_table():
     assert sorted(RECORDED) == sorted(wc.key(fn, args) for fn, args, _ in ROWS)
     assert len(wc.CASES) == 11 and all(len(rows) >= 2 for rows in wc.CASES.values())
+    assert len(wc.F64_CASES) == 4 and all(len(rows) >= 3 for rows in wc.F64_CASES.values())
 
 
 @pytest.mark.parametrize("fn,args,needed", ROWS, ids=[wc.key(fn, args) for fn, args, _ in ROWS])

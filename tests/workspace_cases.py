@@ -6,7 +6,14 @@ tests/golden/workspace_bytes.json) and tests/test_gpu_workspace.py.  Not a test 
 A row is (arguments of the sizer, needed): `needed` is the plain sum of the buffers the entry point provably uses, with
 every row split counted as one block (the library never splits into fewer), and 0 for a shape the sizer refuses.  Only
 lo_hadamard_bilinear_workspace_bytes and lo_cholesky_workspace_bytes refuse a shape; the other sizers report a size for
-whatever they are given and their entry points do the refusing."""
+whatever they are given and their entry points do the refusing.
+
+F64_CASES: the float64 solvers and the float64 Woodbury apply, rows of the same form.  They are a table of their own
+because their entry points take a workspace without the sizer's tail (a behaviour kept as it is), so the walk of
+tests/test_gpu_workspace.py, which expects one byte less than the reported size to be refused, does not apply to them."""
+import ctypes
+
+from linear_operator_amd import _hip
 
 
 def padded_rank(k):
@@ -67,10 +74,49 @@ CASES = {
 }
 
 
+F64_SHAPES = ((1, 1, 1), (3, 37, 3), (2, 300, 17))  # (B, N, c)
+
+
+def _cg_f64(B, N, c):  # the control block (8 ints and a double), six vectors, ten scalars and two flags per column
+    prm = _hip.CgParamsF64(c=c, max_iter=20, max_tridiag_iter=20)
+    return (B, N, prm), 40 + 8 * (6 * B * N * c + 10 * B * c) + 4 * 2 * B * c
+
+
+def _minres_f64(B, N, c, Q):
+    # the control block (4 ints and a double), six vectors and three per shift, six scalars and a flag per column, the
+    # nine Givens scalars and two squared norms per shift and column
+    prm = _hip.MinresParamsF64(c=c, n_shifts=Q, max_iter=20)
+    return (B, N, prm), 24 + 8 * ((6 + 3 * Q) * B * N * c + 6 * B * c + 11 * Q * B * c) + 4 * B * c
+
+
+def _lanczos_f64(B, N, P, max_iter):  # r and the product, the coefficients of every step, two norms, four flag words
+    return (B, N, P, max_iter), 8 * (2 * B * N * P + B * P * max_iter + 2 * B * P) + 4 * 4
+
+
+def _precond_f64(B, N, k, c):  # the partials of Q^T r, one block per chunk of 256 rows, and their sum
+    return (B, N, k, c), 8 * B * k * c * ((N + 255) // 256 + 1)
+
+
+F64_CASES = {
+    "lo_cg_f64_workspace_bytes": [_cg_f64(*s) for s in F64_SHAPES],
+    "lo_minres_f64_workspace_bytes": [_minres_f64(*s, Q) for s in F64_SHAPES for Q in (1, 3)],
+    "lo_lanczos_f64_workspace_bytes": [_lanczos_f64(*s, m) for s in F64_SHAPES for m in (1, 20)],
+    "lo_precond_f64_workspace_bytes": [_precond_f64(B, N, k, c) for (B, N, c) in F64_SHAPES for k in (4, 33)],
+}
+
+
+def _show(a):
+    """An argument in a key: a parameter struct as its non-zero fields."""
+    if isinstance(a, ctypes.Structure):
+        return "{" + " ".join(f"{n}={getattr(a, n)}" for n, _ in a._fields_ if getattr(a, n)) + "}"
+    return str(a)
+
+
 def key(fn, args):
-    return fn + "(" + ",".join(str(a) for a in args) + ")"
+    return fn + "(" + ",".join(_show(a) for a in args) + ")"
 
 
 def sizes(lib):
-    """{key: bytes} over the whole table."""
-    return {key(fn, args): int(getattr(lib, fn)(*args)) for fn, rows in CASES.items() for args, _ in rows}
+    """{key: bytes} over both tables."""
+    return {key(fn, args): int(getattr(lib, fn)(*args)) for table in (CASES, F64_CASES) for fn, rows in table.items()
+            for args, _ in rows}

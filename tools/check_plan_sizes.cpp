@@ -5,7 +5,8 @@
 // lo_lanczos_workspace_bytes.  The sizing passes run the plan functions on a measuring arena: they must read no device
 // pointer (the ones here are dummy addresses), keep no sub-plan (a leak report) and touch nothing out of bounds.  No GPU.
 // The solver sizers are also walked with Woodbury preconditioners (the padded copy of Q taken and not taken, the root
-// form alone), and the sizers of the other entry points with shapes of tests/workspace_cases.py.  Last, the compile-time
+// form alone), and the sizers of the other entry points with shapes of tests/workspace_cases.py, the five float64 sizers
+// (csrc/lo_*_f64.hip) among them.  Last, the compile-time
 // pickers of the matrix-free kernel family (csrc/lo_kernel_shape.h) are held to what the switches they replaced chose.
 //
 //   cd linear_operator_amd/csrc && mkdir -p build_asan
@@ -130,6 +131,63 @@ static int walk_entries() {
     printf("  a refused shape was sized\n");
     ++bad;
   }
+  return bad;
+}
+
+// The float64 sizers over F64_SHAPES of tests/workspace_cases.py: each covers the plain sum of its buffers and, with at most
+// 41 takes aligned to 256 bytes and the tail of 1024, no more than that plus 12 KiB; one refused or degenerate argument
+// set each.  lo_matvec_f64_workspace_bytes reads the descriptor only (dummy pointers), a sum takes its largest term.
+static int walk_f64() {
+  int bad = 0;
+  auto held = [&](const char* what, size_t got, size_t needed) {
+    printf("%s: %zu (buffers %zu)\n", what, got, needed);
+    if (got < needed || got > needed + 12288) {
+      printf("  the size does not match the layout's takes\n");
+      ++bad;
+    }
+  };
+  const int64_t shapes[3][3] = {{1, 1, 1}, {3, 37, 3}, {2, 300, 17}};
+  for (const auto& sh : shapes) {
+    const size_t B = sh[0], N = sh[1], c = sh[2], V = 8 * B * N * c, S = 8 * B * c;
+    lo_cg_params_f64 cg;
+    memset(&cg, 0, sizeof(cg));
+    cg.c = c; cg.max_iter = 20; cg.max_tridiag_iter = 20;
+    held("cg_f64", lo_cg_f64_workspace_bytes(B, N, &cg), 40 + 6 * V + 10 * S + 2 * 4 * B * c);
+    for (int Q : {1, 3}) {
+      lo_minres_params_f64 mr;
+      memset(&mr, 0, sizeof(mr));
+      mr.c = c; mr.n_shifts = Q; mr.max_iter = 20;
+      held("minres_f64", lo_minres_f64_workspace_bytes(B, N, &mr), 24 + (6 + 3 * Q) * V + (6 + 11 * Q) * S + 4 * B * c);
+    }
+    for (int m : {1, 20}) held("lanczos_f64", lo_lanczos_f64_workspace_bytes(B, N, c, m), 2 * V + (m + 2) * S + 16);
+    for (int k : {4, 33}) held("precond_f64", lo_precond_f64_workspace_bytes(B, N, k, c), k * S * ((N + 255) / 256 + 1));
+    lo_op_desc lr = desc(LO_OP_LOWRANK_DIAG, B, N, 5, 0, false, LO_DIAG_FULL);
+    lo_op_desc dn = desc(LO_OP_DENSE_DIAG, B, N, 0, 0, false, LO_DIAG_FULL);
+    lo_op_desc kr = desc(LO_OP_KRON_DIAG, B, N, 1, N, true, LO_DIAG_CONST);
+    lo_op_desc terms[3] = {lr, dn, kr};
+    for (lo_op_desc& t : terms) { t.diag_mode = LO_DIAG_NONE; t.d = nullptr; }
+    lo_op_desc sum = desc(LO_OP_SUM, B, N, 0, 0, false, LO_DIAG_FULL);
+    sum.A0 = nullptr; sum.nterms = 3; sum.terms = terms;
+    const size_t need_lr = 5 * S * ((N + 255) / 256 + 1), need_kr = V;
+    held("matvec_f64 lowrank", lo_matvec_f64_workspace_bytes(&lr, c), need_lr);
+    held("matvec_f64 dense", lo_matvec_f64_workspace_bytes(&dn, c), 0);
+    held("matvec_f64 kron", lo_matvec_f64_workspace_bytes(&kr, c), need_kr);
+    held("matvec_f64 sum", lo_matvec_f64_workspace_bytes(&sum, c), need_lr > need_kr ? need_lr : need_kr);
+    sum.nterms = 1;  // refused: no size
+    if (lo_matvec_f64_workspace_bytes(&sum, c) != 0 || lo_matvec_f64_workspace_bytes(&lr, 0) != 0 ||
+        lo_matvec_f64_workspace_bytes(nullptr, c) != 0 || lo_precond_f64_workspace_bytes(B, N, 0, c) != 0) {
+      printf("  a refused float64 argument set was sized\n");
+      ++bad;
+    }
+  }
+  // degenerate arguments the solver sizers take as they come (their entry points refuse): the tail alone, no read
+  lo_cg_params_f64 cg0;
+  memset(&cg0, 0, sizeof(cg0));
+  lo_minres_params_f64 mr0;
+  memset(&mr0, 0, sizeof(mr0));
+  held("cg_f64 B=0", lo_cg_f64_workspace_bytes(0, 37, &cg0), 40);
+  held("minres_f64 c=0", lo_minres_f64_workspace_bytes(3, 37, &mr0), 24);
+  held("lanczos_f64 N=0", lo_lanczos_f64_workspace_bytes(3, 0, 3, 20), 8 * (20 + 2) * 9 + 16);
   return bad;
 }
 
@@ -291,7 +349,7 @@ int main() {
   lo_op_desc sum_late = sum3;
   sum_late.terms = late;
   bad += walk({{"sum, bad last term", sum_late, true}});  // (its first terms do take buffers)
-  bad += walk_precond(t[0].op) + walk_entries() + walk_pickers();
+  bad += walk_precond(t[0].op) + walk_entries() + walk_f64() + walk_pickers();
   printf(bad ? "FAILED: %d\n" : "ok\n", bad);
   return bad ? 1 : 0;
 }

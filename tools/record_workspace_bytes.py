@@ -1,10 +1,12 @@
 """Records what the workspace sizers of tests/workspace_cases.py report into tests/golden/workspace_bytes.json.
 
 The recording is the upper bound of tests/test_workspace_bytes_cpu.py: a size may shrink but not grow.  It was taken
-from the library of the commit before the entry points got their layout functions; run it again only on a build whose
-sizes are meant to become the new bound.  No device call: the sizers are host arithmetic.
+from the library of the commit before the entry points got their layout functions (the float64 rows: before their sizers
+went through them); run it again only on a build whose sizes are meant to become the new bound.  No device call: the sizers are host arithmetic.
 
-    python tools/record_workspace_bytes.py [path/to/liblo_amd.so]
+    python tools/record_workspace_bytes.py [--add] [path/to/liblo_amd.so]
+
+--add records the rows the file does not hold yet and keeps the bound of every row it holds.
 """
 import ctypes
 import json
@@ -20,16 +22,21 @@ from linear_operator_amd import _hip  # noqa: E402
 
 
 def main():
-    if len(sys.argv) > 1:  # another build's library, with the prototypes of this tree
-        lib = ctypes.CDLL(sys.argv[1])
-        for fn in wc.CASES:
+    argv = [a for a in sys.argv[1:] if a != "--add"]
+    if argv:  # another build's library, with the prototypes of this tree
+        lib = ctypes.CDLL(argv[0])
+        for fn in (*wc.CASES, *wc.F64_CASES):
             restype, argtypes = _hip._PROTOTYPES[fn]
             getattr(lib, fn).restype, getattr(lib, fn).argtypes = restype, argtypes
     else:
         lib = _hip.load()
     out = os.path.join(ROOT, "tests", "golden", "workspace_bytes.json")
+    got = wc.sizes(lib)
+    if "--add" in sys.argv[1:]:
+        with open(out) as f:
+            got.update(json.load(f))
     with open(out, "w") as f:
-        json.dump(wc.sizes(lib), f, indent=1, sort_keys=True)
+        json.dump(got, f, indent=1, sort_keys=True)
         f.write("\n")
     print("wrote", out)
 
