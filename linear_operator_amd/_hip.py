@@ -365,6 +365,37 @@ def load():
     return lib
 
 
+_FAST_PATH = os.path.join(os.path.dirname(_LIB_PATH), "_lo_pyfast.so")
+_fast = False  # False: not tried yet; None: not built or not importable; else the bound module
+
+
+def _import_fast():
+    """The extension module csrc/lo_pyfast.cpp, from the file the csrc Makefile wrote beside liblo_amd.so."""
+    from importlib.machinery import ExtensionFileLoader
+    from importlib.util import module_from_spec, spec_from_file_location
+
+    spec = spec_from_file_location("_lo_pyfast", _FAST_PATH, loader=ExtensionFileLoader("_lo_pyfast", _FAST_PATH))
+    mod = module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def fast():
+    """_lo_pyfast bound to the entry points of the CDLL load() holds (it is not linked against liblo_amd.so: it calls
+    the very image ctypes loaded), or None if it is not built or does not import -- the ctypes binding serves then."""
+    global _fast
+    if _fast is False:
+        lib = load()
+        try:
+            mod = _import_fast() if os.path.exists(_FAST_PATH) else None
+            if mod is not None:
+                mod.bind(C.cast(lib.lo_cg_session_solve_f32, C.c_void_p).value)
+        except Exception:  # noqa: BLE001 -- optional: another interpreter's build, a truncated file
+            mod = None
+        _fast = mod
+    return _fast
+
+
 def prof_enable(on):
     """True / 1: HIP-event scopes around the launches; 2: host intervals of the entry points only ("host:<name>" lines of
     prof_report, no events inside them); 3: both; False / 0: off."""
@@ -449,10 +480,13 @@ def ptr(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+RAW_STREAM = getattr(torch._C, "_cuda_getCurrentRawStream", None)  # (device index) -> the current stream's handle as an int
+
+
 def stream_ptr(device=None):
     """The current HIP stream of `device` as a raw handle (torch._C._cuda_getCurrentRawStream: 0.3 us instead of the 4 us
     of building a torch.cuda.Stream object -- this sits on every solve's critical path)."""
-    raw = getattr(torch._C, "_cuda_getCurrentRawStream", None)
+    raw = RAW_STREAM
     if raw is None:
         return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
     if device is None:

@@ -1191,6 +1191,8 @@ class WoodburyPreconditioner:
     # native solve sessions (lo_cg_session) of the single-column solves this cache serves, by operator and parameters
     # (_session_solve): a small LRU, dropped by whatever changes the cache and destroyed with it
     _sessions: OrderedDict = field(default_factory=OrderedDict, repr=False, compare=False)
+    # the session of the last solve with what it was found by, in front of the LRU (_session_solve); gone with the sessions
+    _memo: Optional[tuple] = field(default=None, repr=False, compare=False)
 
     @property
     def rf_ld(self) -> int:
@@ -1198,6 +1200,7 @@ class WoodburyPreconditioner:
 
     def drop_sessions(self) -> None:
         """Destroy the native solve sessions of this cache (their structs hold pointers into its tensors)."""
+        self.__dict__["_memo"] = None
         sessions = self.__dict__.get("_sessions")
         while sessions:
             _, ent = sessions.popitem()
@@ -1436,6 +1439,34 @@ def cg_sessions_live() -> int:
     return int(_hip.load().lo_cg_session_debug_live())
 
 
+_UNSET = object()
+_fast_mode: Optional[bool] = None  # cg_fast_entry: True forced, False forbidden, None automatic
+_fast_module = _UNSET              # _hip.fast(), once asked for
+
+
+def _fast_resolve():
+    global _fast_module
+    _fast_module = _hip.fast()
+    return _fast_module
+
+
+def cg_fast_entry(mode: Optional[bool] = None) -> str:
+    """Which binding calls lo_cg_session_solve_f32 for the session solves of `cg_solve`: True forces the native entry
+    (csrc/lo_pyfast.cpp; an error where it is not built), False forbids it, None leaves it automatic (the native entry
+    where it is built and imports).  Returns what is in force from now on: "native" or "ctypes"."""
+    global _fast_mode
+    if mode is not None and not isinstance(mode, bool):
+        raise TypeError(f"cg_fast_entry takes True, False or None, not {mode!r}")
+    mod = _fast_resolve()
+    usable = mod is not None and _hip.RAW_STREAM is not None
+    if mode is True and not usable:
+        raise _hip.HipExtensionError(
+            f"the native session entry is not available ({_hip._FAST_PATH}: not built, or it does not import); "
+            "build it with `make -C linear_operator_amd/csrc`")
+    _fast_mode = mode
+    return "native" if usable and mode is not False else "ctypes"
+
+
 def _session_solve(lib, desc: "OperatorDescriptor", pre: "WoodburyPreconditioner", rhs: torch.Tensor, rhs3: torch.Tensor,
                    params: tuple) -> Optional["CGResult"]:
     """The solve through the native session of (operator, cache, parameters), created on first use; None: the general path
@@ -1443,27 +1474,51 @@ def _session_solve(lib, desc: "OperatorDescriptor", pre: "WoodburyPreconditioner
     # (the operator by its POINTERS: the operator classes lower themselves to a fresh descriptor, with fresh views of the
     #  same storage, on every solve; the entry keeps the tensors it was made from alive, so no address is handed out again
     #  while it exists.  The cache's own tensors by identity: they are attributes of `pre`, replaced only by assignment.)
-    key = (desc.A0.data_ptr(), 0 if desc.d is None else desc.d.data_ptr(), desc.kind, desc.diag_mode, desc.B, desc.N,
-           desc.R, params, pre.generation, id(pre.Q), id(pre.dinv), id(pre.RSD))
-    sessions = pre._sessions
-    ent = sessions.get(key)
-    if ent is None:
-        max_iter, max_tridiag_iter, tolerance, eps, stop_updating_after, floor_max_iter = params
-        prm = _cg_params(1, 0, max_iter, max_tridiag_iter, tolerance, eps, stop_updating_after, floor_max_iter)
-        ent = sessions[key] = _CgSession(lib, desc, pre, prm, rhs.device)
-        while len(sessions) > _SESSIONS_PER_CACHE:
-            sessions.popitem(last=False)[1].close()
+    # In front of the LRU, the session of the cache's last solve (always the LRU's newest entry): the same descriptor
+    # object over the same tensors, the same parameters, the cache's tensors unchanged -- no key, no pointer is formed.
+    m = pre._memo
+    if (m is not None and m[1] is desc and m[2] is desc.A0 and m[3] is desc.d and m[4] == params and m[5] is pre.Q
+            and m[6] is pre.dinv and m[7] is pre.RSD and m[8] == pre.generation and m[0].handle is not None):
+        ent = m[0]
     else:
-        sessions.move_to_end(key)
-    if ent.handle is None:
-        ent.retry -= 1
-        if ent.retry <= 0:
-            del sessions[key]
-        return None
+        key = (desc.A0.data_ptr(), 0 if desc.d is None else desc.d.data_ptr(), desc.kind, desc.diag_mode, desc.B, desc.N,
+               desc.R, params, pre.generation, id(pre.Q), id(pre.dinv), id(pre.RSD))
+        sessions = pre._sessions
+        ent = sessions.get(key)
+        if ent is None:
+            max_iter, max_tridiag_iter, tolerance, eps, stop_updating_after, floor_max_iter = params
+            prm = _cg_params(1, 0, max_iter, max_tridiag_iter, tolerance, eps, stop_updating_after, floor_max_iter)
+            ent = sessions[key] = _CgSession(lib, desc, pre, prm, rhs.device)
+            while len(sessions) > _SESSIONS_PER_CACHE:
+                sessions.popitem(last=False)[1].close()
+        else:
+            sessions.move_to_end(key)
+        if ent.handle is None:
+            pre._memo = None
+            ent.retry -= 1
+            if ent.retry <= 0:
+                del sessions[key]
+            return None
+        # (a descriptor rebuilt over the same storage finds its session by the key above and is remembered in its turn)
+        pre._memo = (ent, desc, desc.A0, desc.d, params, pre.Q, pre.dinv, pre.RSD, pre.generation)
     if not ent.busy.acquire(False):
         return None
     try:
         x = torch.empty_like(rhs3)
+        fast = _fast_module if _fast_mode is not False else None
+        if fast is _UNSET:
+            fast = _fast_resolve()
+        if fast is not None and _hip.RAW_STREAM is not None:
+            # csrc/lo_pyfast.cpp: the result structs on its stack, integers in, a tuple out
+            rc, iterations, matvecs, reached, nan, skipped, residual, rspace = fast.session_solve(
+                ent.handle, rhs3.data_ptr(), x.data_ptr(), _hip.RAW_STREAM(rhs3.get_device()))
+            if rc == _hip.LO_ERR_UNSUPPORTED:
+                return None
+            _hip.check(rc, "lo_cg_session_solve_f32")
+            if rspace == 2:
+                pre.rs_uses += 1
+            return CGResult(x if rhs3 is rhs else x.reshape(rhs.shape), None, iterations, matvecs, reached, nan, skipped,
+                            residual)
         rc = lib.lo_cg_session_solve_f32(ent.handle, rhs3.data_ptr(), x.data_ptr(), ent.info_ref, ent.plan_ref,
                                          _hip.stream_ptr(rhs.device))
         if rc == _hip.LO_ERR_UNSUPPORTED:
@@ -1471,7 +1526,7 @@ def _session_solve(lib, desc: "OperatorDescriptor", pre: "WoodburyPreconditioner
         _hip.check(rc, "lo_cg_session_solve_f32")
         if ent.plan.rspace == 2:
             pre.rs_uses += 1
-        return _cg_result(x.reshape(rhs.shape), None, ent.info)
+        return _cg_result(x if rhs3 is rhs else x.reshape(rhs.shape), None, ent.info)
     finally:
         ent.busy.release()
 
@@ -1489,9 +1544,13 @@ def cg_solve(desc: Optional[OperatorDescriptor], rhs: torch.Tensor, *, x0: Optio
     """
     lib = _hip.load()
     _hip.require_hip(rhs, x0)
-    N, c = rhs.shape[-2:]
-    rhs3 = _flat(rhs, 2)
-    B = rhs3.shape[0]
+    shape = rhs.shape
+    N, c = shape[-2:]
+    if len(shape) == 3 and rhs.is_contiguous():  # (no view of what is [B, N, c] already)
+        rhs3, B = rhs, shape[0]
+    else:
+        rhs3 = _flat(rhs, 2)
+        B = rhs3.shape[0]
     x03 = None if x0 is None else _flat(x0.expand_as(rhs), 2)
     dev = rhs.device
     if desc is None:

@@ -46,9 +46,11 @@ def host_marks():
 for _ in range(30): step()
 print(f"(c) python before the call   {timeit(before):7.2f} us   (general path; includes the two allocations and lo_cg_workspace_bytes)")
 print(f"(b) python after the call    {timeit(after):7.2f} us   (general path)")
-for mode in (("general", "session") if has_sessions else ("general",)):
+has_fast = has_sessions and hasattr(K, "cg_fast_entry") and K.cg_fast_entry(None) == "native"  # (csrc/lo_pyfast.cpp)
+for mode in (("general", "session", "native") if has_fast else ("general", "session") if has_sessions else ("general",)):
     if mode == "general": os.environ["LO_CG_NO_SESSION"] = "1"
     else: os.environ.pop("LO_CG_NO_SESSION", None)
+    if has_fast: K.cg_fast_entry(mode == "native")  # "session": the ctypes binding of the same entry point
     for _ in range(30): step()
     t, k = timeit(step), kernel_us()
     line = f"{mode:8s} step {t:7.2f} us   kernel {k.get('cg_onchip', float('nan')):7.2f} us   host share {t - k.get('cg_onchip', 0.0):6.2f} us"

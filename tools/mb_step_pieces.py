@@ -33,6 +33,13 @@ print(f"kernels.cg_solve      {timeit(step):7.1f} us")
 if hasattr(lib, "lo_cg_session_solve_f32"):  # the bare session call, everything prebuilt (after cg_solve above has made it)
     ent = next((e for e in pre._sessions.values() if e.handle), None)
     if ent: print(f"bare session call     {timeit(lambda: lib.lo_cg_session_solve_f32(ent.handle, rhs.data_ptr(), x.data_ptr(), ent.info_ref, ent.plan_ref, st)):7.1f} us")
+    fast = _hip.fast() if ent and hasattr(_hip, "fast") else None  # (csrc/lo_pyfast.cpp: the same entry point, no ctypes)
+    if fast:
+        print(f"bare native call      {timeit(lambda: fast.session_solve(ent.handle, rhs.data_ptr(), x.data_ptr(), st.value or 0)):7.1f} us")
+        for on in (False, True):
+            K.cg_fast_entry(on)
+            print(f"kernels.cg_solve      {timeit(step):7.1f} us   ({K.cg_fast_entry(on)} entry)")
+        K.cg_fast_entry(None)
 print(f"lo_cg_workspace_bytes {timeit(lambda: lib.lo_cg_workspace_bytes(C.byref(s), C.byref(ps), C.byref(prm))):7.1f} us")
 print(f"c_struct x2 + params  {timeit(lambda: (desc.c_struct(), pre.c_struct(), K._cg_params(1, 0, 1000, 20, 1e-4, 1e-10, 1e-10, 0))):7.1f} us")
 print(f"torch.empty x2        {timeit(lambda: (_hip.workspace(ws.numel(), rhs.device), torch.empty_like(rhs))):7.1f} us")

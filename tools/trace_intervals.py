@@ -11,7 +11,7 @@ for f in glob.glob(os.path.join(sys.argv[1], "**", "*kernel_trace.csv"), recursi
 rows.sort()
 def stats(a):
     a = np.asarray(a, dtype=np.float64) / 1e3
-    return (f"n={a.size} median={np.median(a):.2f} us mean={a.mean():.2f} p10={np.percentile(a, 10):.2f} "
+    return (f"n={a.size} median={np.median(a):.2f} us mean={a.mean():.2f} sd={a.std():.2f} p10={np.percentile(a, 10):.2f} "
             f"p90={np.percentile(a, 90):.2f} min={a.min():.2f} max={a.max():.2f}") if a.size else "none"
 rs3 = [(s, e) for s, e, n in rows if "k_cg_rspace3" in n]
 zs = sum("k_zero_span" in n for _, _, n in rows)
