@@ -23,12 +23,29 @@ __device__ __forceinline__ float wave_max(float v) {
 // ---- xor-butterfly partner fetch on the gfx950 cross-lane hardware (no LDS crossbar except M == 4) ----
 //   M = 32 / 16 : v_permlane32_swap / v_permlane16_swap     M = 8 : DPP row_ror:8
 //   M = 4       : ds_swizzle SWAP,4                         M = 2, 1 : DPP quad_perm
+// A DPP move whose control gives EVERY lane a source lane inside its own row (row_ror, quad_perm; all rows and banks
+// enabled): no lane keeps the destination's previous value, so none is supplied.  update_dpp(0, ...) made the compiler
+// zero the destination with a v_mov_b32 in front of every move, between the add that forms the source and the move that
+// waits for it.  A lane whose source lane is switched off in EXEC reads 0 (bound_ctrl), which is what the zeroed
+// destination gave it.
+template <int CTRL>
+__device__ __forceinline__ int dpp_all_i(int v) {
+  static_assert(CTRL == 0x128 || CTRL == 0x124 || (CTRL >= 0 && CTRL <= 0xff), "row_ror:8, row_ror:4 or a quad_perm");
+  return __builtin_amdgcn_mov_dpp(v, CTRL, 0xf, 0xf, true);
+}
+// xor-4 partner on the DPP path instead of the LDS-crossbar ds_swizzle with its own wait: two row shifts under
+// complementary bank masks.  As a PAIR they write every lane from a source inside its row -- what the first move leaves
+// in banks 1, 3 the second one writes -- so the first supplies no previous value either.
+__device__ __forceinline__ int xor4_dpp_i(int x) {
+  const int a = __builtin_amdgcn_mov_dpp(x, 0x104, 0xf, 0x5, true);       // row_shl:4 -> banks 0, 2 read lane + 4
+  return __builtin_amdgcn_update_dpp(a, x, 0x114, 0xf, 0xa, false);       // row_shr:4 -> banks 1, 3 read lane - 4
+}
 template <int M>
 __device__ __forceinline__ int xor_lane_i(int v) {
-  if constexpr (M == 8) return __builtin_amdgcn_update_dpp(0, v, 0x128, 0xf, 0xf, false);
+  if constexpr (M == 8) return dpp_all_i<0x128>(v);
   else if constexpr (M == 4) return __builtin_amdgcn_ds_swizzle(v, 0x101f);
-  else if constexpr (M == 2) return __builtin_amdgcn_update_dpp(0, v, 0x4e, 0xf, 0xf, false);
-  else return __builtin_amdgcn_update_dpp(0, v, 0xb1, 0xf, 0xf, false);
+  else if constexpr (M == 2) return dpp_all_i<0x4e>(v);
+  else return dpp_all_i<0xb1>(v);
 }
 // {a, b} = {own value, value of lane ^ M} in an order that depends on the lane: combine them symmetrically.
 template <int M>

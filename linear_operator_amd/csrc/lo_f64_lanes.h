@@ -37,10 +37,10 @@ __device__ __forceinline__ double lanes32_sum_d(double v) {
 __device__ __forceinline__ double wave_sum_fast_d(double v) { return bfly_add_d<32>(lanes32_sum_d(v)); }
 // sum over each row of 16 lanes, every lane ends with the total: rotations instead of the xor pattern (a plain sum needs no
 // pairing, and row_ror:4 stays on the DPP path where the xor-4 exchange is an LDS-crossbar ds_swizzle with its own wait)
+// (dpp_all_i: no `old` operand -- these rotations and quad permutations give every lane a source inside its row)
 template <int CTRL>
 __device__ __forceinline__ double dpp_add_d(double x) {
-  return x + mk_d((unsigned)__builtin_amdgcn_update_dpp(0, (int)lo_w(x), CTRL, 0xf, 0xf, false),
-                  (unsigned)__builtin_amdgcn_update_dpp(0, (int)hi_w(x), CTRL, 0xf, 0xf, false));
+  return x + mk_d((unsigned)dpp_all_i<CTRL>((int)lo_w(x)), (unsigned)dpp_all_i<CTRL>((int)hi_w(x)));
 }
 __device__ __forceinline__ double row16_sum_d(double x) {
   x = dpp_add_d<0x128>(x);  // row_ror:8

@@ -76,13 +76,8 @@ __device__ __forceinline__ T* opaque_uniform(T* p) {
   return p;
 }
 
-// xor-4 exchange on the DPP path (two row shifts under complementary bank masks) instead of the LDS-crossbar ds_swizzle
-__device__ __forceinline__ float xor4_dpp(float v) {
-  const int x = __float_as_int(v);
-  const int a = __builtin_amdgcn_update_dpp(0, x, 0x104, 0xf, 0x5, false);  // row_shl:4 -> banks 0, 2 read lane + 4
-  const int b = __builtin_amdgcn_update_dpp(a, x, 0x114, 0xf, 0xa, false);  // row_shr:4 -> banks 1, 3 read lane - 4
-  return __int_as_float(b);
-}
+// xor-4 exchange on the DPP path (xor4_dpp_i, lo_device.h) instead of the LDS-crossbar ds_swizzle
+__device__ __forceinline__ float xor4_dpp(float v) { return __int_as_float(xor4_dpp_i(__float_as_int(v))); }
 __device__ __forceinline__ float halve4(float lo, float hi, int lane) {
   const bool up = (lane & 4) != 0;
   const float keep = up ? hi : lo;

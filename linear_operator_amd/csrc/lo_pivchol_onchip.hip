@@ -138,11 +138,8 @@ __device__ __forceinline__ f2 pk_mul_bcast(f2 a, f2 b) {
 __device__ __forceinline__ f2 pk_add(f2 a, f2 b) { return a + b; }
 __device__ __forceinline__ f2 pk_mul(f2 a, f2 b) { return a * b; }
 
-// xor-4 partner on the DPP path (two row shifts under complementary bank masks) instead of the LDS-crossbar ds_swizzle
-__device__ __forceinline__ int p4_xor4(int x) {
-  const int a = __builtin_amdgcn_update_dpp(0, x, 0x104, 0xf, 0x5, false);  // row_shl:4 -> banks 0, 2 read lane + 4
-  return __builtin_amdgcn_update_dpp(a, x, 0x114, 0xf, 0xa, false);          // row_shr:4 -> banks 1, 3 read lane - 4
-}
+// xor-4 partner on the DPP path (xor4_dpp_i, lo_device.h) instead of the LDS-crossbar ds_swizzle
+__device__ __forceinline__ int p4_xor4(int x) { return xor4_dpp_i(x); }
 // wave_sum_fast (lo_device.h) with the xor-4 step on the DPP path: same operands, same order, same bits
 __device__ __forceinline__ float p4_wave_sum(float v) {
   v = bfly_add<1>(v); v = bfly_add<2>(v);

@@ -79,12 +79,8 @@ std::mutex g_peer_mu;  // lo_peer_gather_set against the snapshot a launch takes
 
 __host__ __device__ constexpr int r3_np(int RC) { return 2 * RC + 6; }  // w0 | u0 | s | a0 | next member | sum dinv^2 | xcc | xcc^2
 
-// xor-4 exchange of a double on the DPP path (two row shifts under complementary bank masks per word) instead of the
-// LDS-crossbar ds_swizzle with its own wait
-__device__ __forceinline__ unsigned xor4_dpp_u(unsigned x) {
-  const int a = __builtin_amdgcn_update_dpp(0, (int)x, 0x104, 0xf, 0x5, false);  // row_shl:4 -> banks 0, 2 read lane + 4
-  return (unsigned)__builtin_amdgcn_update_dpp(a, (int)x, 0x114, 0xf, 0xa, false);  // row_shr:4 -> banks 1, 3 read lane - 4
-}
+// xor-4 exchange of a double on the DPP path (xor4_dpp_i, lo_device.h, per word)
+__device__ __forceinline__ unsigned xor4_dpp_u(unsigned x) { return (unsigned)xor4_dpp_i((int)x); }
 __device__ __forceinline__ double halve4_d(double lo, double hi, int lane) {
   const bool up = (lane & 4) != 0;
   const double keep = up ? hi : lo;
