@@ -100,6 +100,9 @@ extern "C" {
                                    *   y[i] = sum_j theta_D g(r_ij) Bt[t_i, t_j] v[j] + d o v, r over columns 0 .. D - 1;
                                    * tasks need not be observed at the same points; K never stored                        */
 #define LO_KERNEL_TASK_MAX_TASKS 8 /* tasks T (Bt is T x T) the kind and lo_kernel_task_* take (more: LO_ERR_UNSUPPORTED)   */
+#define LO_OP_SKI_SUM_DIAG 16   /* AddedDiag(SumBatch(Interpolated(Toeplitz(t_p), W_l,p, W_r,p)), Diag(d)):
+                                 *   y = sum_{p < P} W_l,p T_p W_r,p^T v + d o v,  P 1-D grids of M points over the same N rows */
+#define LO_SKI_SUM_MAX_TERMS 64 /* terms P one LO_OP_SKI_SUM_DIAG descriptor / lo_interp_sum_f32 call takes (more: LO_ERR_UNSUPPORTED) */
 
 struct lo_interp_desc;
 struct lo_mask_desc;
@@ -191,7 +194,23 @@ typedef struct lo_op_desc {
    * fp64 entry points, the resident / fused engines and the solve sessions return LO_ERR_UNSUPPORTED; not a term kind of
    * LO_OP_SUM, not a base kind of LO_OP_MASKED.
    * LO_ERR_BADARG: a null A0 / A1 / task, R < 1, a family outside 0 .. 3, T < 1; LO_ERR_UNSUPPORTED: R + 1 >
-   * LO_KERNEL_MAX_DIM, T > LO_KERNEL_TASK_MAX_TASKS.                                                                     */
+   * LO_KERNEL_MAX_DIM, T > LO_KERNEL_TASK_MAX_TASKS.
+   * ABI 37 kind.  SKI_SUM, the additive KISS-GP model (one 1-D grid per input dimension, summed): A0 = t [B, P, M], the
+   * first columns of the P Toeplitz terms, R = M <= LO_TOEPLITZ_MAX_M, n2 = J, nterms = P in 1 .. LO_SKI_SUM_MAX_TERMS
+   * (`terms` unused), N the rows, `interp` a lo_interp_desc whose four arrays are [B, P, N, J], the term index second --
+   * exactly the tensors the base operator holds for its batch (*batch, P) -- with grid_ndim = 0 and right_plan NULL or
+   * the copy lo_interp_plan_build makes for (B P, N, J, M) (same layout again, no new member).  The kind's own
+   * (diag_mode, d) has d of [B, N] or [B].  An index outside [0, M) contributes nothing and is never dereferenced.
+   * Terms are summed in ascending order after each term's own sum over j; with P = 1 the product and the pivoted
+   * Cholesky rows have the bits of LO_OP_SKI_DIAG on the same arrays.  Lowered for lo_matvec_f32, the streaming CG,
+   * Lanczos, fp32 MINRES and the fp32 pivoted Cholesky (row of pivot q: row[i] = sum_p of the SKI row of term p; the
+   * diagonal is the EXACT one, sum_p sum_a sum_b t_p[|li[p,i,a] - ri[p,i,b]|] lv[p,i,a] rv[p,i,b], which is what the
+   * reference's SumBatch._diagonal gives its pivot search -- not the approximate one of LO_OP_SKI_DIAG); the fp64 entry
+   * points, the resident / fused engines and the solve sessions return LO_ERR_UNSUPPORTED; not a term kind of
+   * LO_OP_SUM, not a base kind of LO_OP_MASKED or of lo_block_mv_f32.
+   * LO_ERR_BADARG: a null A0 / interp / array in it, P < 1, J < 1, M < 1; LO_ERR_UNSUPPORTED: P > LO_SKI_SUM_MAX_TERMS,
+   * M > LO_TOEPLITZ_MAX_M, B P > 65535, N J or M beyond the 32-bit limits of the interpolation kernels;
+   * LO_ERR_WORKSPACE: a short workspace.  All before any launch.                                                          */
 } lo_op_desc;
 
 /* The grid shape of an LO_OP_TOEPLITZ_KRON_DIAG descriptor (host struct). */
@@ -899,6 +918,19 @@ int lo_toeplitz_bilinear_f32(const float* u, const float* v, int64_t B, int64_t 
                              size_t ws_bytes, void* stream);
 int lo_interp_values_grad_f32(const int64_t* idx, int64_t B, int64_t N, int64_t J, int64_t M, const float* lv,
                               const float* R, int64_t S, float* g, void* stream);
+
+/* ---- additive SKI building blocks (ABI 37; csrc/lo_ski_sum.hip) --------------------------------------------------------
+ * The two kernels LO_OP_SKI_SUM_DIAG adds to the ones above, over P terms per member (arrays [B, P, N, J], grid
+ * member g = b P + p).  Fixed-order sums (j ascending within a term, terms ascending), no float atomics: the same inputs
+ * give the same bits; P = 1 gives the bits of lo_interp_f32 / lo_interp_t_planned_f32.  Index entries outside [0, M)
+ * contribute nothing.  LO_ERR_BADARG: null pointers, sizes below 1, a diag_mode other than LO_DIAG_* or one without d / v;
+ * LO_ERR_UNSUPPORTED: P > LO_SKI_SUM_MAX_TERMS, B P > 65535.                                                               */
+/* y [B, N, c] = sum_{p<P} W_p u_p (+ d o v when dd_mode != LO_DIAG_NONE);  idx / vals [B, P, N, J], u [B, P, M, c] */
+int lo_interp_sum_f32(const int64_t* idx, const float* vals, int64_t B, int64_t P, int64_t N, int64_t J, int64_t M,
+                      const float* u, int64_t c, const float* d, int32_t diag_mode, const float* v, float* y, void* stream);
+/* out [B, P, M, c] = W_p^T v for every p from ONE v [B, N, c] (no [P, N, c] copy of v); plan as lo_interp_plan_build(B*P) */
+int lo_interp_t_bcast_planned_f32(const void* plan, const float* vals, int64_t B, int64_t P, int64_t N, int64_t J,
+                                  int64_t M, const float* v, int64_t c, float* out, void* stream);
 
 /* ---- SKI on a 2-D / 3-D grid (ABI 23; csrc/lo_ski_grid.hip) -------------------------------------------------------
  * The grid product y = (T_1 (x) .. (x) T_D) u of D = ndim in {2, 3} symmetric Toeplitz factors, one axis per pass and no

@@ -26,6 +26,8 @@ LO_OP_MASKED = 8
 LO_OP_SKI_GRID_DIAG = 9
 LO_SKI_GRID_MAX_AXIS = 1024
 LO_SKI_GRID_MAX_M = 4194304
+LO_OP_SKI_SUM_DIAG = 16
+LO_SKI_SUM_MAX_TERMS = 64
 LO_OP_TOEPLITZ_KRON_DIAG = 10
 LO_KRON_EIG_MAX_SMALL, LO_KRON_EIG_MAX_COLS = 16, 256
 LO_OP_KERNEL_DIAG = 11
@@ -42,7 +44,7 @@ LO_KERNEL_TASK_MAX_TASKS = 8
 LO_DIAG_NONE, LO_DIAG_FULL, LO_DIAG_CONST = 0, 1, 2
 LO_BLOCK_DIAG, LO_BLOCK_INTERLEAVED, LO_BLOCK_SUM = 0, 1, 2
 LO_EIGH_MAX_N = 1024
-ABI_VERSION = 36
+ABI_VERSION = 37
 
 LO_ERR_UNSUPPORTED = -4
 LO_FUSED_OK, LO_FUSED_EARLY_STOP, LO_FUSED_CONTINUE, LO_FUSED_TIMEOUT = 0, 1, 2, 3
@@ -267,6 +269,8 @@ _PROTOTYPES = {
     "lo_interp_plan_bytes": (sz, [i64, i64, i64, i64]),
     "lo_interp_plan_build": (ci, [vp, i64, i64, i64, i64, vp, sz, vp]),
     "lo_interp_t_planned_f32": (ci, [vp, vp, i64, i64, i64, i64, vp, i64, vp, vp]),
+    "lo_interp_sum_f32": (ci, [vp, vp, i64, i64, i64, i64, i64, vp, i64, vp, i32, vp, vp, vp]),
+    "lo_interp_t_bcast_planned_f32": (ci, [vp, vp, i64, i64, i64, i64, i64, vp, i64, vp, vp]),
     "lo_toeplitz_workspace_bytes": (sz, [i64, i64, i64]),
     "lo_toeplitz_mv_f32": (ci, [vp, i64, i64, vp, i64, vp, vp, sz, vp]),
     "lo_toeplitz_bilinear_f32": (ci, [vp, vp, i64, i64, i64, vp, vp, sz, vp]),

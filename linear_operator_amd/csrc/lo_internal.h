@@ -215,6 +215,21 @@ CsrBufs csr_view(const void* plan, int64_t B, int64_t N, int64_t J, int64_t M);
 // the part of the plan the SKI kinds share: u, t and the copy of W_r (built here, or the caller's right_plan)
 int ski_interp_plan(MatvecPlan* pl, int64_t M, Arena* ar, hipStream_t st);
 
+// ---- additive SKI, a sum of P 1-D terms over the same rows (lo_ski_sum.hip): LO_OP_SKI_SUM_DIAG, on SkiPlan ---------
+// The state of the SKI kind over the G = B * P grid members (member g = b * P + p): u, t [G, M, c], the copy of W_r and
+// the split-k partials of G Toeplitz products.
+int ski_sum_plan(MatvecPlan* pl, Arena* ar, hipStream_t st);
+int ski_sum_matvec_run(const MatvecPlan* pl, const float* v, float* y, const int* stop, hipStream_t st);
+// LO_OK, or why the descriptor of that kind is refused (the pivoted Cholesky validates it without a plan)
+int ski_sum_desc_check(const lo_op_desc* op);
+// interp_scatter with member g of W reading v[g / vdiv] (v [B / vdiv, N, c])
+int interp_scatter_bcast(const int* ptr, const int* ids, const float* vals, int64_t B, int vdiv, int64_t N, int64_t J,
+                         int64_t M, const float* v, int64_t c, float* out, const int* stop, hipStream_t st);
+// the 1-D Toeplitz product of lo_ski.hip and the floats of its split-k partials `part`
+size_t toeplitz_part_floats(int64_t B, int64_t M, int64_t c);
+int toeplitz_mv(const float* t, int64_t B, int64_t M, const float* u, int64_t c, const float* dd, int dd_mode,
+                const float* v, float* y, float* part, const int* stop, hipStream_t st);
+
 // ---- SKI on a 2-D / 3-D grid (lo_ski_grid.hip): LO_OP_SKI_GRID_DIAG, on SkiPlan ---------------------------------------
 int ski_grid_plan(MatvecPlan* pl, Arena* ar, hipStream_t st);
 int ski_grid_matvec_run(const MatvecPlan* pl, const float* v, float* y, const int* stop, hipStream_t st);

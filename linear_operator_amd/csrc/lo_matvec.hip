@@ -148,6 +148,7 @@ int matvec_plan_init(MatvecPlan* pl, const lo_op_desc* op, lo_matvec_cb cb, void
     case LO_OP_SKI_DIAG:
     case LO_OP_TOEPLITZ_DIAG: rc = ski_plan(pl, ar, st); break;
     case LO_OP_SKI_GRID_DIAG: rc = ski_grid_plan(pl, ar, st); break;
+    case LO_OP_SKI_SUM_DIAG: rc = ski_sum_plan(pl, ar, st); break;
     case LO_OP_TOEPLITZ_KRON_DIAG: rc = toeplitz_kron_plan(pl, ar, st); break;
     case LO_OP_HADAMARD_DIAG: rc = hadamard_plan(pl, ar, st); break;
     case LO_OP_KERNEL_DIAG: rc = kernel_op_plan(pl, ar, st); break;
@@ -189,6 +190,8 @@ int matvec_run(const MatvecPlan* pl, const float* v, float* y, float* dot_part, 
     case LO_OP_TOEPLITZ_DIAG: rc = ski_matvec_run(pl, v, y, stop, st); break;
     case LO_OP_SKI_GRID_DIAG:  // W_l (T_1 (x) .. (x) T_D) W_r^T v + d o v: the same with one pass per grid axis
       rc = ski_grid_matvec_run(pl, v, y, stop, st); break;
+    case LO_OP_SKI_SUM_DIAG:  // sum_p W_l,p T_p W_r,p^T v + d o v: the SKI passes over B P grid members, one summing gather
+      rc = ski_sum_matvec_run(pl, v, y, stop, st); break;
     case LO_OP_TOEPLITZ_KRON_DIAG:  // (T_1 (x) .. (x) T_D) v + d o v: one pass per grid axis, the diagonal in the last
       rc = toeplitz_kron_matvec_run(pl, v, y, stop, st); break;
     case LO_OP_HADAMARD_DIAG:  // (F F^T o G G^T) v + d o v: contraction M_t = F^T diag(v_t) G, expansion rowdot(F, G M_t^T)
@@ -232,7 +235,7 @@ using namespace lo;
 
 extern "C" {
 
-int lo_abi_version(void) { return 36; }
+int lo_abi_version(void) { return 37; }
 const char* lo_target_arch(void) { return "gfx950"; }
 
 size_t lo_matvec_workspace_bytes(const lo_op_desc* op, int64_t c) {

@@ -15,6 +15,9 @@
 //                                                            (interpolated_linear_operator.py:130-144); the diagonal
 //                     is the reference's APPROXIMATE one, (W_l sqrt(t0)) o (W_r sqrt(t0)) (:94-101,
 //                     functions/_pivoted_cholesky.py:25): pivots are chosen on it, rows come from the true matrix
+//   SKI sum:          row[i] = sum_p (the SKI row of term p), terms ascending (sum_batch_linear_operator.py:43-52); the
+//                     diagonal is the EXACT one, sum_p sum_b sum_a t_p[|li[p,i,a] - ri[p,i,b]|] (lv[p,i,a] rv[p,i,b])
+//                     (SumBatch has no approximate diagonal: _approx_diagonal is _diagonal, :37-41)
 // Integer results (pivots, permutation) must match the CPU path bit for bit, so every value that feeds
 // a pivot decision is computed per element in a FIXED order with individually rounded operations
 // (products rounded before summation, sequential in r and in j; this file is compiled with
@@ -114,6 +117,30 @@ __device__ __forceinline__ T seq_dot(const T* __restrict__ a, const T* __restric
   return acc;
 }
 
+// entry (pim, i) of W_l T W_r^T for grid member g of the interpolation arrays and of the columns: base_vals[b', a] *
+// (lv[pim, a] rv[i, b']) summed over both, b' outside (interpolated_linear_operator.py:139-144); out-of-grid entries
+// contribute nothing
+template <typename T>
+__device__ __forceinline__ T ski_entry(const lo_interp_desc& w, const float* A0, int64_t M, int J, size_t g, int64_t N,
+                                       int pim, int i) {
+  const T* col = pc_ptr<T>(A0) + g * M;
+  const int64_t* li = w.left_idx + (g * N + pim) * J;
+  const T* lv = pc_ptr<T>(w.left_vals) + (g * N + pim) * J;
+  const int64_t* ri = w.right_idx + (g * N + i) * J;
+  const T* rv = pc_ptr<T>(w.right_vals) + (g * N + i) * J;
+  T tv = T(0);
+  for (int bb = 0; bb < J; ++bb) {
+    const int64_t q = ri[bb];
+    for (int a = 0; a < J; ++a) {
+      const int64_t p = li[a];
+      const int64_t lag = p > q ? p - q : q - p;
+      const T base = (p >= 0 && p < M && q >= 0 && q < M) ? col[lag] : T(0);
+      tv = (bb == 0 && a == 0) ? base * (lv[a] * rv[bb]) : tv + base * (lv[a] * rv[bb]);
+    }
+  }
+  return tv;
+}
+
 template <typename T>
 __device__ __forceinline__ T src_diag(const PcDevT<T>& d, const lo_op_desc& op, int64_t b, int i) {
   const T* A0 = pc_ptr<T>(op.A0);
@@ -179,6 +206,13 @@ __device__ __forceinline__ T src_diag(const PcDevT<T>& d, const lo_op_desc& op, 
       r = (j == 0) ? rt : r + rt;
     }
     return l * r;
+  } else if (op.kind == LO_OP_SKI_SUM_DIAG) {  // the exact diagonal: entry (i, i) of every term, terms ascending
+    T s = T(0);
+    for (int p = 0; p < op.nterms; ++p) {
+      const T tv = ski_entry<T>(d.ski, op.A0, op.R, (int)op.n2, (size_t)b * op.nterms + p, d.N, i, i);
+      s = p == 0 ? tv : s + tv;
+    }
+    return s;
   } else if (op.kind == LO_OP_SKI_GRID_DIAG) {
     // the same over the constant base diagonal t0 = prod_k t_k[0] (the Kronecker diagonal of the reference multiplies
     // the trailing factors first, kronecker_product_linear_operator.py:22-28)
@@ -556,22 +590,11 @@ __global__ __launch_bounds__(kThreads) void k_pc_update(PcDevT<T> d, int m) {
           const T f1 = c1[p1 > q1 ? p1 - q1 : q1 - p1], f2 = c2[p2 > q2 ? p2 - q2 : q2 - p2];
           tv = D == 3 ? (c0[p0 > q0 ? p0 - q0 : q0 - p0] * f1) * f2 : f1 * f2;
         } else if (tm.kind == LO_OP_SKI_DIAG) {
-          // base_vals[b', a] * (lv[p, a] rv[i, b']) summed over both (:139-144); out-of-grid entries contribute nothing
-          const int J = (int)tm.n2;
-          const int64_t M = tm.R;
-          const T* col = pc_ptr<T>(tm.A0) + (size_t)b * M;
-          const int64_t* li = d.ski.left_idx + ((size_t)b * N + pim) * J;
-          const T* lv = pc_ptr<T>(d.ski.left_vals) + ((size_t)b * N + pim) * J;
-          const int64_t* ri = d.ski.right_idx + ((size_t)b * N + i) * J;
-          const T* rv = pc_ptr<T>(d.ski.right_vals) + ((size_t)b * N + i) * J;
-          for (int bb = 0; bb < J; ++bb) {
-            const int64_t q = ri[bb];
-            for (int a = 0; a < J; ++a) {
-              const int64_t p = li[a];
-              const int64_t lag = p > q ? p - q : q - p;
-              const T base = (p >= 0 && p < M && q >= 0 && q < M) ? col[lag] : T(0);
-              tv = (bb == 0 && a == 0) ? base * (lv[a] * rv[bb]) : tv + base * (lv[a] * rv[bb]);
-            }
+          tv = ski_entry<T>(d.ski, tm.A0, tm.R, (int)tm.n2, (size_t)b, N, pim, i);
+        } else if (tm.kind == LO_OP_SKI_SUM_DIAG) {  // the same row per term, summed in term order
+          for (int p = 0; p < tm.nterms; ++p) {
+            const T pv = ski_entry<T>(d.ski, tm.A0, tm.R, (int)tm.n2, (size_t)b * tm.nterms + p, N, pim, i);
+            tv = p == 0 ? pv : tv + pv;
           }
         } else if (tm.kind == LO_OP_SKI_GRID_DIAG) {
           // the same sum in the same order with base[g, h] = prod_k t_k[|g_k - h_k|], factors multiplied left to right
@@ -658,8 +681,8 @@ static void pc_layout(const lo_op_desc* op, int max_rank, Arena& ar, PcDevT<T>* 
     d->nterms = 1;
     d->terms[0] = *op;
   }
-  d->ski = ((op->kind == LO_OP_SKI_DIAG || op->kind == LO_OP_SKI_GRID_DIAG) && op->interp) ? *op->interp
-                                                                                            : lo_interp_desc{};
+  const bool ski = op->kind == LO_OP_SKI_DIAG || op->kind == LO_OP_SKI_GRID_DIAG || op->kind == LO_OP_SKI_SUM_DIAG;
+  d->ski = (ski && op->interp) ? *op->interp : lo_interp_desc{};
   if (op->kind == LO_OP_TOEPLITZ_KRON_DIAG && op->grid) {
     d->ski.grid_ndim = op->grid->ndim;
     for (int k = 0; k < 3; ++k) d->ski.grid_m[k] = op->grid->m[k];
@@ -798,6 +821,8 @@ static int pc_check_desc(const lo_op_desc* op, bool fp32_kinds = true) {
     const lo_interp_desc* w = op->interp;
     if (!op->A0 || op->R < 1 || op->n2 < 1 || !w || !w->left_idx || !w->left_vals || !w->right_idx || !w->right_vals)
       return LO_ERR_BADARG;
+  } else if (op->kind == LO_OP_SKI_SUM_DIAG) {
+    if (const int rc = ski_sum_desc_check(op)) return rc;
   } else if (op->kind == LO_OP_SKI_GRID_DIAG) {
     const lo_interp_desc* w = op->interp;
     if (!op->A0 || op->R < 1 || op->n2 < 1 || !w || !w->left_idx || !w->left_vals || !w->right_idx || !w->right_vals)
@@ -890,7 +915,8 @@ int lo_pivoted_cholesky_f64(const lo_op_desc* op, int32_t max_rank, double error
                             int32_t* rank_out, void* ws, size_t ws_bytes, void* stream) {
   if (!op || !L_rows || !perm || !rank_out || !ws || max_rank < 1) return LO_ERR_BADARG;
   if (op->kind == LO_OP_SKI_DIAG || op->kind == LO_OP_TOEPLITZ_DIAG || op->kind == LO_OP_HADAMARD_DIAG ||
-      op->kind == LO_OP_SKI_GRID_DIAG || op->kind == LO_OP_TOEPLITZ_KRON_DIAG || kernel_term_kind(op->kind) ||
+      op->kind == LO_OP_SKI_GRID_DIAG || op->kind == LO_OP_SKI_SUM_DIAG || op->kind == LO_OP_TOEPLITZ_KRON_DIAG ||
+      kernel_term_kind(op->kind) ||
       op->kind == LO_OP_KERNEL_KRON_DIAG || op->kind == LO_OP_KERNEL_GRAD_DIAG || op->kind == LO_OP_KERNEL_TASK_DIAG)
     return LO_ERR_UNSUPPORTED;  // (fp32 kinds)
   if (const int rc = pc_check_desc(op, false)) return rc;

@@ -199,7 +199,7 @@ CsrBufs csr_view(const void* plan, int64_t B, int64_t N, int64_t J, int64_t M) {
 // few columns: one wave per (member, grid point, column)
 __global__ __launch_bounds__(kThreads) void k_interp_t_wave(const int* __restrict__ ptr, const int* __restrict__ ids,
                                                         const float* __restrict__ vals, int64_t B, int64_t N, int J,
-                                                        int64_t M, const float* __restrict__ v, int c,
+                                                        int64_t M, const float* __restrict__ v, int vdiv, int c,
                                                         float* __restrict__ out, const int* __restrict__ stop) {
   if (stop && *stop) return;
   constexpr int kWaves = kThreads / 64;
@@ -215,7 +215,7 @@ __global__ __launch_bounds__(kThreads) void k_interp_t_wave(const int* __restric
     const int beg = pb[m], end = pb[m + 1];
     const int* ib = ids + b * NJ;
     const float* wb = vals + b * NJ;
-    const float* vb = v + b * N * c + col;
+    const float* vb = v + (vdiv > 1 ? b / vdiv : b) * N * c + col;
     float acc = 0.f;
     for (int k = beg + lane; k < end; k += 64) {
       const int id = ib[k];
@@ -229,7 +229,7 @@ __global__ __launch_bounds__(kThreads) void k_interp_t_wave(const int* __restric
 // many columns: one thread per output element, the columns of a grid point in consecutive lanes (shared index loads)
 __global__ __launch_bounds__(kThreads) void k_interp_t_lane(const int* __restrict__ ptr, const int* __restrict__ ids,
                                                              const float* __restrict__ vals, int64_t B, int64_t N, int J,
-                                                             int64_t M, const float* __restrict__ v, int c,
+                                                             int64_t M, const float* __restrict__ v, int vdiv, int c,
                                                              float* __restrict__ out, const int* __restrict__ stop) {
   if (stop && *stop) return;
   const size_t total = (size_t)B * M * c;
@@ -243,7 +243,7 @@ __global__ __launch_bounds__(kThreads) void k_interp_t_lane(const int* __restric
     const int beg = pb[m], end = pb[m + 1];
     const int* ib = ids + b * NJ;
     const float* wb = vals + b * NJ;
-    const float* vb = v + b * N * c + col;
+    const float* vb = v + (vdiv > 1 ? b / vdiv : b) * N * c + col;
     float acc = 0.f;
     for (int k = beg; k < end; ++k) {
       const int id = ib[k];
@@ -253,22 +253,29 @@ __global__ __launch_bounds__(kThreads) void k_interp_t_lane(const int* __restric
   }
 }
 
-int interp_scatter(const int* ptr, const int* ids, const float* vals, int64_t B, int64_t N, int64_t J, int64_t M,
-                   const float* v, int64_t c, float* out, const int* stop, hipStream_t st) {
-  if (!interp_shape_ok(B, N, J, M) || c < 1 || c > INT_MAX) return LO_ERR_BADARG;
+// vdiv: grid members that read one member of v (member b of W reads v[b / vdiv]): 1 for the SKI kinds, the P terms of
+// the additive kind (lo_ski_sum.hip), whose v [B / P, N, c] is never copied P times
+int interp_scatter_bcast(const int* ptr, const int* ids, const float* vals, int64_t B, int vdiv, int64_t N, int64_t J,
+                         int64_t M, const float* v, int64_t c, float* out, const int* stop, hipStream_t st) {
+  if (!interp_shape_ok(B, N, J, M) || c < 1 || c > INT_MAX || vdiv < 1) return LO_ERR_BADARG;
   const size_t total = (size_t)B * M * c;
   LO_PROF_BEGIN("ski_interp_t", st);
   if (c < 8) {  // (the mode is a function of the shape only: the same inputs give the same bits)
     const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>((total + 3) / 4, 32768));
-    hipLaunchKernelGGL(k_interp_t_wave, dim3(grid), dim3(kThreads), 0, st, ptr, ids, vals, B, N, (int)J, M, v, (int)c,
-                       out, stop);
+    hipLaunchKernelGGL(k_interp_t_wave, dim3(grid), dim3(kThreads), 0, st, ptr, ids, vals, B, N, (int)J, M, v, vdiv,
+                       (int)c, out, stop);
   } else {
     hipLaunchKernelGGL(k_interp_t_lane, dim3(grid_for(total)), dim3(kThreads), 0, st, ptr, ids, vals, B, N, (int)J, M, v,
-                       (int)c, out, stop);
+                       vdiv, (int)c, out, stop);
   }
   LO_PROF_END(st);
   LO_LAUNCH_CHECK();
   return LO_OK;
+}
+
+int interp_scatter(const int* ptr, const int* ids, const float* vals, int64_t B, int64_t N, int64_t J, int64_t M,
+                   const float* v, int64_t c, float* out, const int* stop, hipStream_t st) {
+  return interp_scatter_bcast(ptr, ids, vals, B, 1, N, J, M, v, c, out, stop, st);
 }
 
 // ---- Toeplitz product --------------------------------------------------------------------------------------------------
@@ -355,9 +362,10 @@ __global__ __launch_bounds__(kThreads) void k_tz_reduce(const float* __restrict_
   }
 }
 
+size_t toeplitz_part_floats(int64_t B, int64_t M, int64_t c) { return (size_t)tz_split(B, M).KS * B * M * c; }
+
 size_t toeplitz_part_bytes(int64_t B, int64_t M, int64_t c) {
-  const TzSplit s = tz_split(B, M);
-  return align_up((size_t)s.KS * B * M * c * sizeof(float), 256) + 256;
+  return align_up(toeplitz_part_floats(B, M, c) * sizeof(float), 256) + 256;
 }
 
 int toeplitz_mv(const float* t, int64_t B, int64_t M, const float* u, int64_t c, const float* dd, int dd_mode,
@@ -488,7 +496,7 @@ int ski_plan(MatvecPlan* pl, Arena* ar, hipStream_t st) {
     const int rc = ski_interp_plan(pl, M, ar, st);
     if (rc) return rc;
   }
-  pl->ski.tz_part = ar->take<float>((size_t)tz_split(op.B, M).KS * op.B * M * pl->c);
+  pl->ski.tz_part = ar->take<float>(toeplitz_part_floats(op.B, M, pl->c));
   return LO_OK;
 }
 

@@ -50,7 +50,7 @@ class OperatorDescriptor:
     # point that reads `float*`
     dtype: torch.dtype = torch.float32
     # LO_OP_KERNEL_SUM_DIAG: T, the struct's `nterms` (the kind has no `terms`); LO_OP_KERNEL_KRON_DIAG,
-    # LO_OP_KERNEL_TASK_DIAG: the tasks T
+    # LO_OP_KERNEL_TASK_DIAG: the tasks T; LO_OP_SKI_SUM_DIAG: the P summed terms (A0 [B, P, M], interp [B, P, N, J])
     kernel_terms: int = 0
     # LO_OP_KERNEL_KRON_DIAG, LO_OP_KERNEL_TASK_DIAG: Bt [B, T, T], the union slot `task` (a DEVICE pointer)
     task: Optional[torch.Tensor] = None
@@ -377,6 +377,35 @@ def ski_diag_descriptor(column: torch.Tensor, left_idx: torch.Tensor, left_vals:
     ri, rv = (li, lv) if shared else (flat(right_idx), flat(right_vals))
     return _with_diag(OperatorDescriptor(_hip.LO_OP_SKI_DIAG, B, N, A0=col, R=M, n2=J, batch_shape=batch,
                                          interp=(li, lv, ri, rv), interp_plan=right_plan), d, const_diag)
+
+
+def ski_sum_diag_descriptor(cols: torch.Tensor, left_idx: torch.Tensor, left_vals: torch.Tensor,
+                            right_idx: torch.Tensor, right_vals: torch.Tensor, d: Optional[torch.Tensor],
+                            const_diag: bool = False, right_plan: Optional[torch.Tensor] = None):
+    """AddedDiag(SumBatch(Interpolated(Toeplitz(cols), W_l, W_r)), Diag(d)), the additive SKI model:
+    y = sum_p W_l,p T_p W_r,p^T v + d o v.  cols [*batch, P, M], indices int64 / values fp32 [*batch, P, N, J] (the base
+    operator's own tensors: the summed dimension is its last batch dimension), d [*batch, N] or [*batch].  None when the
+    shapes are outside what the kind takes.  `right_plan`: interp_plan(right_idx, (*batch, P), M), kept by the caller
+    (else every matvec / solve builds the grid-major copy of W_r itself)."""
+    _hip.require_hip(cols, left_vals, right_vals, d)
+    batch = cols.shape[:-2]
+    P, M = cols.shape[-2:]
+    N, J = left_idx.shape[-2:]
+    B = math.prod(batch)
+    if (M > _hip.LO_TOEPLITZ_MAX_M or not 1 <= P <= _hip.LO_SKI_SUM_MAX_TERMS or B * P > 65535
+            or right_idx.shape[-2:] != (N, J) or left_idx.dtype != torch.int64 or right_idx.dtype != torch.int64
+            or not left_idx.is_cuda or not right_idx.is_cuda):
+        return None
+    col = cols.contiguous().reshape(B, P, M)
+
+    def flat(t):
+        return t.expand(*batch, P, N, J).contiguous().reshape(B, P, N, J)
+
+    li, lv = flat(left_idx), flat(left_vals)
+    shared = right_idx is left_idx and right_vals is left_vals  # (one copy: the kernels read the same arrays twice)
+    ri, rv = (li, lv) if shared else (flat(right_idx), flat(right_vals))
+    return _with_diag(OperatorDescriptor(_hip.LO_OP_SKI_SUM_DIAG, B, N, A0=col, R=M, n2=J, batch_shape=batch,
+                                         interp=(li, lv, ri, rv), interp_plan=right_plan, kernel_terms=P), d, const_diag)
 
 
 # Memo of the concatenated columns of a Kronecker-of-Toeplitz base, keyed on the factors' column tensors (address, version
@@ -984,6 +1013,34 @@ def interp(idx: torch.Tensor, vals: torch.Tensor, u: torch.Tensor) -> torch.Tens
     return y
 
 
+def interp_sum(idx: torch.Tensor, vals: torch.Tensor, u: torch.Tensor, d: Optional[torch.Tensor] = None,
+               v: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """sum_p W_p u_p (+ d o v): idx int64 / vals fp32 [B, P, N, J], u [B, P, M, c] -> [B, N, c], with d [B, N] or [B]
+    and v [B, N, c] (lo_interp_sum_f32; terms summed in ascending order, no [P, N, c] intermediate)."""
+    _hip.require_hip(vals, u, d, v)
+    B, P, N, J = idx.shape
+    M, c = u.shape[-2:]
+    idx, vals, u = idx.contiguous(), vals.contiguous(), u.contiguous()
+    mode = _hip.LO_DIAG_NONE if d is None else (_hip.LO_DIAG_FULL if d.dim() == 2 else _hip.LO_DIAG_CONST)
+    if d is not None:
+        d, v = d.contiguous(), v.contiguous()
+    y = torch.empty(B, N, c, dtype=torch.float32, device=u.device)
+    _launch("lo_interp_sum_f32", u.device, idx, vals, B, P, N, J, M, u, c, d, mode, v, y)
+    return y
+
+
+def interp_t_bcast(plan: torch.Tensor, vals: torch.Tensor, v: torch.Tensor, M: int) -> torch.Tensor:
+    """W_p^T v for every term p from one v: plan = interp_plan_build over the B P members, vals [B, P, N, J],
+    v [B, N, c] -> [B, P, M, c] (lo_interp_t_bcast_planned_f32; v is not copied P times)."""
+    _hip.require_hip(vals, v)
+    B, P, N, J = vals.shape
+    c = v.shape[-1]
+    vals, v = vals.contiguous(), v.contiguous()
+    out = torch.empty(B, P, M, c, dtype=torch.float32, device=v.device)
+    _launch("lo_interp_t_bcast_planned_f32", v.device, plan, vals, B, P, N, J, M, v, c, out)
+    return out
+
+
 def interp_t(idx: torch.Tensor, vals: torch.Tensor, v: torch.Tensor, M: int) -> torch.Tensor:
     """W^T v: idx / vals [B, N, J], v [B, N, c] -> [B, M, c] (lo_interp_t_f32, deterministic)."""
     lib = _hip.load()
@@ -1117,10 +1174,21 @@ def native_matmul_candidate(op, rhs: torch.Tensor) -> bool:
     return bool(_NATIVE_MATMUL_F64.get((_f64_route_kind(op), 1 if rhs.shape[-1] == 1 else 2), False))
 
 
+# Which products of the additive SKI kind (LO_OP_SKI_SUM_DIAG) the operators' `_matmul` hands to lo_matvec_f32, by column
+# class (one column / more columns): True only where tools/mb_ski_sum.py measured the kind faster than the composition
+# beyond the run-to-run spread.  The descriptor lowers always: CG, Lanczos, MINRES and the pivoted
+# Cholesky run on it whatever this table says.  Measured (kind / composition, microseconds, median of 5 rounds):
+#   S1: 1 x 262144, P 8, M 8192, J 4    1 column  177 / 196     17 columns  1317 / 1461
+#   S2: 16 x 16384, P 4, M 2048, J 4    1 column   96 / 107     17 columns   661 /  721
+NATIVE_MATMUL_SKI_SUM: dict = {1: True, 2: True}
+
+
 def native_matmul(desc: Optional[OperatorDescriptor], rhs: torch.Tensor) -> bool:
     """Whether `_matmul` hands the product of the lowered operator `desc` with `rhs` to `matvec`."""
     if desc is None or desc.dtype != rhs.dtype:
         return False
+    if desc.kind == _hip.LO_OP_SKI_SUM_DIAG:
+        return bool(NATIVE_MATMUL_SKI_SUM.get(1 if rhs.shape[-1] == 1 else 2, False))
     if desc.dtype == torch.float32:
         return True
     return bool(_NATIVE_MATMUL_F64.get((_F64_KIND_NAMES.get(desc.kind), 1 if rhs.shape[-1] == 1 else 2), False))
