@@ -340,10 +340,14 @@ static int hd_contract(const HdShape& s, const float* F, const float* G, const f
   return LO_OK;
 }
 
+int hadamard_desc_check(const lo_op_desc* op) {
+  return (!op->A0 || !op->A1 || op->R < 1 || op->n2 < 1) ? LO_ERR_BADARG : LO_OK;
+}
+
 int hadamard_plan(MatvecPlan* pl, Arena* ar, hipStream_t) {
   const lo_op_desc& op = pl->op;
   HdShape s;
-  if (!op.A0 || !op.A1 || op.R < 1 || op.n2 < 1) return LO_ERR_BADARG;
+  if (const int rc = hadamard_desc_check(&op)) return rc;
   if (!hd_shape(op.B, op.N, op.R, op.n2, pl->c, &s)) return LO_ERR_UNSUPPORTED;
   pl->hd.part = ar->take<float>(s.part_floats);
   pl->hd.m = ar->take<float>(s.m_floats);

@@ -200,6 +200,13 @@ struct SkiPlan {
 };
 int ski_plan(MatvecPlan* pl, Arena* ar, hipStream_t st);
 int ski_matvec_run(const MatvecPlan* pl, const float* v, float* y, const int* stop, hipStream_t st);
+// LO_OK, or why the descriptor of that kind is refused: what the plan function and the pivoted Cholesky (which validates
+// without a plan) both check; each adds the bounds of its own kernels.  One per kind, next to the kind's plan function.
+int toeplitz_desc_check(const lo_op_desc* op);
+int ski_desc_check(const lo_op_desc* op);
+inline bool interp_ptrs_ok(const lo_interp_desc* w) {
+  return w && w->left_idx && w->left_vals && w->right_idx && w->right_vals;
+}
 // the interpolation kernels and the grid-major copy of W, shared with the grid kind (lo_ski_grid.hip)
 bool interp_shape_ok(int64_t B, int64_t N, int64_t J, int64_t M);
 int interp_gather(const int64_t* idx, const float* vals, int64_t B, int64_t N, int64_t J, int64_t M, const float* u,
@@ -220,7 +227,6 @@ int ski_interp_plan(MatvecPlan* pl, int64_t M, Arena* ar, hipStream_t st);
 // the split-k partials of G Toeplitz products.
 int ski_sum_plan(MatvecPlan* pl, Arena* ar, hipStream_t st);
 int ski_sum_matvec_run(const MatvecPlan* pl, const float* v, float* y, const int* stop, hipStream_t st);
-// LO_OK, or why the descriptor of that kind is refused (the pivoted Cholesky validates it without a plan)
 int ski_sum_desc_check(const lo_op_desc* op);
 // interp_scatter with member g of W reading v[g / vdiv] (v [B / vdiv, N, c])
 int interp_scatter_bcast(const int* ptr, const int* ids, const float* vals, int64_t B, int vdiv, int64_t N, int64_t J,
@@ -233,6 +239,7 @@ int toeplitz_mv(const float* t, int64_t B, int64_t M, const float* u, int64_t c,
 // ---- SKI on a 2-D / 3-D grid (lo_ski_grid.hip): LO_OP_SKI_GRID_DIAG, on SkiPlan ---------------------------------------
 int ski_grid_plan(MatvecPlan* pl, Arena* ar, hipStream_t st);
 int ski_grid_matvec_run(const MatvecPlan* pl, const float* v, float* y, const int* stop, hipStream_t st);
+int ski_grid_desc_check(const lo_op_desc* op);
 
 // ---- Kronecker product of 2 / 3 symmetric Toeplitz factors (lo_ski_grid.hip): LO_OP_TOEPLITZ_KRON_DIAG -----------------
 struct ToeplitzKronPlan {
@@ -242,6 +249,7 @@ struct ToeplitzKronPlan {
 };
 int toeplitz_kron_plan(MatvecPlan* pl, Arena* ar, hipStream_t st);
 int toeplitz_kron_matvec_run(const MatvecPlan* pl, const float* v, float* y, const int* stop, hipStream_t st);
+int toeplitz_kron_desc_check(const lo_op_desc* op);
 
 // ---- Hadamard product of two roots (lo_hadamard.hip) ---------------------------------------------------------------
 struct HadamardPlan {
@@ -249,6 +257,7 @@ struct HadamardPlan {
 };
 int hadamard_plan(MatvecPlan* pl, Arena* ar, hipStream_t st);
 int hadamard_matvec_run(const MatvecPlan* pl, const float* v, float* y, const int* stop, hipStream_t st);
+int hadamard_desc_check(const lo_op_desc* op);
 
 // ---- matrix-free kernel operator (lo_kernel_op.hip): LO_OP_KERNEL_DIAG ------------------------------------------------
 struct KernelOpPlan {
@@ -257,11 +266,11 @@ struct KernelOpPlan {
 };
 int kernel_op_plan(MatvecPlan* pl, Arena* ar, hipStream_t st);
 int kernel_op_matvec_run(const MatvecPlan* pl, const float* v, float* y, const int* stop, hipStream_t st);
+int kernel_desc_check(const lo_op_desc* op);
 
 // ---- sum of matrix-free kernel operators over the same points (lo_kernel_sum.hip): LO_OP_KERNEL_SUM_DIAG, on KernelOpPlan
 int kernel_sum_plan(MatvecPlan* pl, Arena* ar, hipStream_t st);
 int kernel_sum_matvec_run(const MatvecPlan* pl, const float* v, float* y, const int* stop, hipStream_t st);
-// LO_OK, or why the descriptor of that kind is refused (the pivoted Cholesky validates it without a plan)
 int kernel_sum_desc_check(const lo_op_desc* op);
 
 // ---- matrix-free multitask operator Kernel(X, X) (x) Bt (lo_kernel_kron.hip): LO_OP_KERNEL_KRON_DIAG -------------------
@@ -270,7 +279,6 @@ struct KernelKronPlan {
 };
 int kernel_kron_plan(MatvecPlan* pl, Arena* ar, hipStream_t st);
 int kernel_kron_matvec_run(const MatvecPlan* pl, const float* v, float* y, const int* stop, hipStream_t st);
-// LO_OK, or why the descriptor of that kind is refused (the pivoted Cholesky validates it without a plan)
 int kernel_kron_desc_check(const lo_op_desc* op);
 
 // ---- matrix-free RBF gradient kernel, D + 1 outputs per input (lo_kernel_grad.hip): LO_OP_KERNEL_GRAD_DIAG -------------
@@ -279,7 +287,6 @@ struct KernelGradPlan {
 };
 int kernel_grad_plan(MatvecPlan* pl, Arena* ar, hipStream_t st);
 int kernel_grad_matvec_run(const MatvecPlan* pl, const float* v, float* y, const int* stop, hipStream_t st);
-// LO_OK, or why the descriptor of that kind is refused (the pivoted Cholesky validates it without a plan)
 int kernel_grad_desc_check(const lo_op_desc* op);
 
 // ---- matrix-free task-indexed multitask operator (lo_kernel_task.hip): LO_OP_KERNEL_TASK_DIAG ----------------------------
@@ -288,7 +295,6 @@ struct KernelTaskPlan {
 };
 int kernel_task_plan(MatvecPlan* pl, Arena* ar, hipStream_t st);
 int kernel_task_matvec_run(const MatvecPlan* pl, const float* v, float* y, const int* stop, hipStream_t st);
-// LO_OK, or why the descriptor of that kind is refused (the pivoted Cholesky validates it without a plan)
 int kernel_task_desc_check(const lo_op_desc* op);
 
 // ---- masked operator (lo_masked.hip) ---------------------------------------------------------------------------------

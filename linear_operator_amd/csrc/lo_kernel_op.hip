@@ -333,9 +333,15 @@ int kernel_mv_run(const float* x1, const float* x2, const float* theta, int64_t 
   return LO_OK;
 }
 
+int kernel_desc_check(const lo_op_desc* op) {
+  if (!op->A0 || !op->A1 || op->R < 1 || !ko_family_ok(op->n2)) return LO_ERR_BADARG;
+  return op->R > LO_KERNEL_MAX_DIM ? LO_ERR_UNSUPPORTED : LO_OK;
+}
+
 int kernel_op_plan(MatvecPlan* pl, Arena* ar, hipStream_t) {
   const lo_op_desc& op = pl->op;
-  if (!op.A0 || !op.A1 || op.R < 1 || !ko_family_ok(op.n2)) return LO_ERR_BADARG;
+  if (const int rc = kernel_desc_check(&op)) return rc;
+  // the launch limits of the product's kernels (batch, rows, columns): the pivoted Cholesky launches none of them
   if (!ko_shape_ok(op.B, op.N, op.N, op.R) || pl->c > 0x7fffffff) return LO_ERR_UNSUPPORTED;
   pl->ko.part = ko_split_layout<float>(*ar, op.B, op.N, op.N, pl->c);
   return LO_OK;

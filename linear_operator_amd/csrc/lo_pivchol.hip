@@ -1,23 +1,40 @@
 // lo_pivchol.hip -- greedy partial pivoted Cholesky, restating PivotedCholesky.forward
 // (linear_operator/functions/_pivoted_cholesky.py:14-105) with the row fetch
 // (utils/permutation.py:9-88 -> LinearOperator.__getitem__ -> operator _get_indices) generated on the fly
-// from the operator descriptor:
-//   Root/LowRankRoot: row[i] = sum_r C[p,r] C[i,r]          (root_linear_operator.py:37-50, diag :22-28)
-//   Dense:            row[i] = K[p,i]                        (dense_linear_operator.py:47-50, diag :37-40)
-//   Kron:             row[i] = K1[p1,i1] K2[p2,i2]           (kronecker_product_linear_operator.py:198-216)
-//   Hadamard:         row[i] = (F_p . F_i)(G_p . G_i)        (mul_linear_operator.py:49-52, diag |F_i|^2 |G_i|^2 :43-47)
-//   Toeplitz:         row[i] = t[|p - i|]                    (toeplitz_linear_operator.py:38-40, diag :25-31)
-//   Toeplitz Kron:    row[i] = prod_k t_k[|p_k - i_k|]       (kronecker_product_linear_operator.py:198-216 over the
-//                                                            Toeplitz rows), the diagonal prod_k t_k[0] is constant
-//   Kernel:           row[i] = os2 g(|theta o (x_p - x_i)|), r^2 summed over d in ascending order; the diagonal os2 is
-//                                                            constant (kernel_linear_operator.py:230-246, :263-279)
-//   SKI:              row[i] = sum_b sum_a t[|li[p,a] - ri[i,b]|] (lv[p,a] rv[i,b])
-//                                                            (interpolated_linear_operator.py:130-144); the diagonal
-//                     is the reference's APPROXIMATE one, (W_l sqrt(t0)) o (W_r sqrt(t0)) (:94-101,
-//                     functions/_pivoted_cholesky.py:25): pivots are chosen on it, rows come from the true matrix
-//   SKI sum:          row[i] = sum_p (the SKI row of term p), terms ascending (sum_batch_linear_operator.py:43-52); the
-//                     diagonal is the EXACT one, sum_p sum_b sum_a t_p[|li[p,i,a] - ri[p,i,b]|] (lv[p,i,a] rv[p,i,b])
-//                     (SumBatch has no approximate diagonal: _approx_diagonal is _diagonal, :37-41)
+// from the operator descriptor.  One line per kind: entry (p, i) of the row of pivot p, the diagonal, the reference's
+// lines where it has the operator, and the functions that hold the formula (every kind's diagonal is a branch of
+// src_diag, its row a branch of src_entry, its descriptor check a case of pc_check_desc):
+//   LOWRANK        sum_r C[p,r] C[i,r]; diag sum_r C[i,r]^2 (root_linear_operator.py:37-50, :22-28)
+//                  -- seq_dot over the LDS tile of stage_rows, in k_pc_init / k_pc_update themselves
+//   DENSE          K[p,i]; diag K[i,i] (dense_linear_operator.py:47-50, :37-40)
+//   KRON           K1[p1,i1] K2[p2,i2]; diag K1[i1,i1] K2[i2,i2] (kronecker_product_linear_operator.py:198-216, :22-28)
+//   CALLBACK       the row and the diagonal the caller's callback fetched (LinearOperator.__getitem__ / _diagonal)
+//   SUM            the terms' rows / diagonals added left to right (sum_linear_operator.py:31-45) -- the term loops
+//                  of k_pc_init / k_pc_update
+//   HADAMARD       (F_p . F_i)(G_p . G_i); diag |F_i|^2 |G_i|^2 (mul_linear_operator.py:49-52, :43-47) -- seq_dot
+//   TOEPLITZ       t[|p - i|]; diag t[0] (toeplitz_linear_operator.py:38-40, :25-31)
+//   TOEPLITZ_KRON  prod_k t_k[|p_k - i_k|], leading factor first; diag prod_k t_k[0], trailing factors first
+//                  (kronecker_product_linear_operator.py:198-216, :22-28 over the Toeplitz rows) -- grid_base, grid_t0
+//   SKI            sum_b sum_a t[|li[p,a] - ri[i,b]|] (lv[p,a] rv[i,b]) (interpolated_linear_operator.py:130-144);
+//                  diag the reference's APPROXIMATE one, (W_l sqrt t0) o (W_r sqrt t0), t0 = t[0] (:94-101,
+//                  functions/_pivoted_cholesky.py:25): pivots are chosen on it, rows come from the true matrix
+//                  -- ski_entry<T, false>, ski_approx_diag
+//   SKI_GRID       the same with t[|.|] replaced by the TOEPLITZ_KRON entry of the grid points and t0 = prod_k t_k[0]
+//                  -- ski_entry<T, true> over grid_base, ski_approx_diag over grid_t0
+//   SKI_SUM        sum over the terms of the SKI entry, terms ascending (sum_batch_linear_operator.py:43-52); diag
+//                  the EXACT one, entry (i, i) of the same sum (SumBatch has no approximate diagonal: _approx_diagonal
+//                  is _diagonal, :37-41) -- ski_entry<T, false> in both
+//   KERNEL         os2 g(r2), r2 = |theta o x_p - theta o x_i|^2 summed over the coordinates in ascending order; diag
+//                  os2 (kernel_linear_operator.py:230-246, :263-279) -- kern_r2, kf_g_rt (lo_kernel_fn.h)
+//   KERNEL_SUM     sum_t os2_t g_t(r2_t), terms ascending; diag sum_t os2_t (sum_linear_operator.py:31-45 over
+//                  KERNEL terms on one point tensor) -- kern_r2 per term
+//   KERNEL_KRON    (os2 g(r2_pj)) Bt[tau, s] for p = (p, tau), i = (j, s); diag os2 Bt[tau, tau]
+//                  (kronecker_product_linear_operator.py:198-216 over KERNEL and the task matrix) -- kern_r2
+//   KERNEL_TASK    (os2 g(r2_pi)) Bt[t_p, t_i], the task ids in the points' last column; diag os2 Bt[t_i, t_i]
+//                  (no operator of the reference: include/lo_amd.h, LO_OP_KERNEL_TASK_DIAG) -- kern_r2, tk_task_id
+//   KERNEL_GRAD    the (al, be) entry of the RBF value / derivative block of the points p, j; diag os2, os2 t_a^2
+//                  (no operator of the reference: include/lo_amd.h, lo_kernel_grad_mv_f32) -- its own loop: that of
+//                  kern_r2, which also keeps the scaled differences of the coordinates al, be
 // Integer results (pivots, permutation) must match the CPU path bit for bit, so every value that feeds
 // a pivot decision is computed per element in a FIXED order with individually rounded operations
 // (products rounded before summation, sequential in r and in j; this file is compiled with
@@ -86,28 +103,21 @@ template <typename T> __device__ __forceinline__ const T* pc_ptr(const float* p)
 // block reductions over 256 threads through `red` (256 elements of T): fixed tree order, result in every thread
 __device__ __forceinline__ float pc_block_sum(float v, float* red) { return block_sum256(v, red); }  // (round 1-3 order)
 __device__ __forceinline__ float pc_block_max(float v, float* red) { return block_max256(v, red); }
-template <typename T>
-__device__ __forceinline__ T pc_block_sum(T v, T* red) {
+template <typename T, typename Op>
+__device__ __forceinline__ T pc_block_reduce(T v, T* red, Op op) {
   __syncthreads();
   red[threadIdx.x] = v;
   __syncthreads();
   for (int h = kThreads / 2; h >= 1; h >>= 1) {
-    if ((int)threadIdx.x < h) red[threadIdx.x] = red[threadIdx.x] + red[threadIdx.x + h];
+    if ((int)threadIdx.x < h) red[threadIdx.x] = op(red[threadIdx.x], red[threadIdx.x + h]);
     __syncthreads();
   }
   return red[0];
 }
 template <typename T>
-__device__ __forceinline__ T pc_block_max(T v, T* red) {
-  __syncthreads();
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int h = kThreads / 2; h >= 1; h >>= 1) {
-    if ((int)threadIdx.x < h) red[threadIdx.x] = pc_max(red[threadIdx.x], red[threadIdx.x + h]);
-    __syncthreads();
-  }
-  return red[0];
-}
+__device__ __forceinline__ T pc_block_sum(T v, T* red) { return pc_block_reduce(v, red, [](T a, T b) { return a + b; }); }
+template <typename T>
+__device__ __forceinline__ T pc_block_max(T v, T* red) { return pc_block_reduce(v, red, [](T a, T b) { return pc_max(a, b); }); }
 
 template <typename T>
 __device__ __forceinline__ T seq_dot(const T* __restrict__ a, const T* __restrict__ b, int R) {
@@ -117,38 +127,108 @@ __device__ __forceinline__ T seq_dot(const T* __restrict__ a, const T* __restric
   return acc;
 }
 
-// entry (pim, i) of W_l T W_r^T for grid member g of the interpolation arrays and of the columns: base_vals[b', a] *
-// (lv[pim, a] rv[i, b']) summed over both, b' outside (interpolated_linear_operator.py:139-144); out-of-grid entries
-// contribute nothing
+// ---- the pieces the row sources share, each formula once ------------------------------------------------------------
+// |theta o (x_p - x_i)|^2 of two points of D coordinates: the coordinates scaled and rounded separately, then
+// differenced, the squares summed in ascending k
+__device__ __forceinline__ float kern_r2(const float* xp, const float* xi, const float* th, int D) {
+  float r2 = 0.0f;
+  for (int k = 0; k < D; ++k) {
+    const float df = xp[k] * th[k] - xi[k] * th[k];
+    r2 = r2 + df * df;
+  }
+  return r2;
+}
+
+// the first columns of member b of a Kronecker product of D = 2 / 3 Toeplitz factors (shape: d.ski.grid_*): the two
+// trailing axes c1, c2 and, D == 3, the leading one c0
 template <typename T>
-__device__ __forceinline__ T ski_entry(const lo_interp_desc& w, const float* A0, int64_t M, int J, size_t g, int64_t N,
-                                       int pim, int i) {
-  const T* col = pc_ptr<T>(A0) + g * M;
-  const int64_t* li = w.left_idx + (g * N + pim) * J;
-  const T* lv = pc_ptr<T>(w.left_vals) + (g * N + pim) * J;
-  const int64_t* ri = w.right_idx + (g * N + i) * J;
-  const T* rv = pc_ptr<T>(w.right_vals) + (g * N + i) * J;
+struct GridCols { int D, m1, m2; const T *c0, *c1, *c2; };
+template <typename T>
+__device__ __forceinline__ GridCols<T> grid_cols(const PcDevT<T>& d, const float* A0, int64_t b) {
+  const int D = d.ski.grid_ndim, m0 = D == 3 ? (int)d.ski.grid_m[0] : 0;
+  const int m1 = (int)d.ski.grid_m[D - 2], m2 = (int)d.ski.grid_m[D - 1];
+  const T* c0 = pc_ptr<T>(A0) + (size_t)b * (m0 + m1 + m2);
+  return {D, m1, m2, c0, c0 + m0, c0 + m0 + m1};
+}
+struct GridPt { int k0, k1, k2; };  // the coordinates of grid point k0 (m1 m2) + k1 m2 + k2
+template <typename T>
+__device__ __forceinline__ GridPt grid_pt(const GridCols<T>& g, int p) {
+  return {p / (g.m2 * g.m1), (p / g.m2) % g.m1, p % g.m2};
+}
+// prod_k t_k[|p_k - q_k|] of the grid points p and q, the leading factor multiplied first; consecutive threads hold
+// consecutive positions: the gathers from the (small) columns stay in cache
+template <typename T>
+__device__ __forceinline__ T grid_base(const GridCols<T>& g, const GridPt& p, const GridPt& q) {
+  const T f1 = g.c1[p.k1 > q.k1 ? p.k1 - q.k1 : q.k1 - p.k1], f2 = g.c2[p.k2 > q.k2 ? p.k2 - q.k2 : q.k2 - p.k2];
+  return g.D == 3 ? (g.c0[p.k0 > q.k0 ? p.k0 - q.k0 : q.k0 - p.k0] * f1) * f2 : f1 * f2;
+}
+// its constant diagonal prod_k t_k[0], the trailing factors multiplied first
+template <typename T>
+__device__ __forceinline__ T grid_t0(const GridCols<T>& g) {
+  const T t0 = g.c1[0] * g.c2[0];
+  return g.D == 3 ? g.c0[0] * t0 : t0;
+}
+
+// entry (pim, i) of W_l K W_r^T of term tm, member g of its interpolation arrays and columns: base[p, q] *
+// (lv[pim, a] rv[i, b']) summed over both, b' outside (interpolated_linear_operator.py:139-144).  base[p, q] is
+// t[|p - q|] of the member's column, or (GRID) grid_base; a grid point outside [0, M) contributes T(0) and reads nothing
+template <typename T, bool GRID>
+__device__ __forceinline__ T ski_entry(const PcDevT<T>& d, const lo_op_desc& tm, size_t g, int pim, int i) {
+  // (N <= 0x7ffffff0 by pc_check_desc: read as the kernels' 32-bit N; GRID: M <= LO_SKI_GRID_MAX_M, 32-bit grid points)
+  const int64_t M = tm.R, N = (int)d.N;
+  const int J = (int)tm.n2;
+  const T* col = GRID ? nullptr : pc_ptr<T>(tm.A0) + g * M;  // 1-D: the member's first column
+  GridCols<T> gc{};
+  if constexpr (GRID) gc = grid_cols(d, tm.A0, (int64_t)g);
+  const int64_t* li = d.ski.left_idx + (g * N + pim) * J;
+  const T* lv = pc_ptr<T>(d.ski.left_vals) + (g * N + pim) * J;
+  const int64_t* ri = d.ski.right_idx + (g * N + i) * J;
+  const T* rv = pc_ptr<T>(d.ski.right_vals) + (g * N + i) * J;
   T tv = T(0);
   for (int bb = 0; bb < J; ++bb) {
     const int64_t q = ri[bb];
+    const bool q_in = q >= 0 && q < M;
+    GridPt qq{};
+    if constexpr (GRID) qq = grid_pt(gc, q_in ? (int)q : 0);  // (once per b')
     for (int a = 0; a < J; ++a) {
       const int64_t p = li[a];
-      const int64_t lag = p > q ? p - q : q - p;
-      const T base = (p >= 0 && p < M && q >= 0 && q < M) ? col[lag] : T(0);
-      tv = (bb == 0 && a == 0) ? base * (lv[a] * rv[bb]) : tv + base * (lv[a] * rv[bb]);
+      const bool in = p >= 0 && p < M && q_in;
+      T bv = T(0);
+      if constexpr (GRID) {
+        if (in) bv = grid_base(gc, grid_pt(gc, (int)p), qq);
+      } else {
+        if (in) bv = col[p > q ? p - q : q - p];
+      }
+      tv = (bb == 0 && a == 0) ? bv * (lv[a] * rv[bb]) : tv + bv * (lv[a] * rv[bb]);
     }
   }
   return tv;
 }
+// the reference's approximate SKI diagonal over a constant base diagonal t0 = s^2:
+// left_interp(li, lv, s) * left_interp(ri, rv, s) at row i
+template <typename T>
+__device__ __forceinline__ T ski_approx_diag(const lo_interp_desc& w, int64_t M, int J, size_t row, T s) {
+  const int64_t *li = w.left_idx + row * J, *ri = w.right_idx + row * J;
+  const T *lv = pc_ptr<T>(w.left_vals) + row * J, *rv = pc_ptr<T>(w.right_vals) + row * J;
+  T l = T(0), r = T(0);
+  for (int j = 0; j < J; ++j) {
+    const T lt = (li[j] >= 0 && li[j] < M) ? s * lv[j] : T(0);
+    const T rt = (ri[j] >= 0 && ri[j] < M) ? s * rv[j] : T(0);
+    l = (j == 0) ? lt : l + lt;
+    r = (j == 0) ? rt : r + rt;
+  }
+  return l * r;
+}
 
+template <typename T>
+__device__ __forceinline__ T src_entry(const PcDevT<T>& d, const lo_op_desc& tm, int64_t b, int pim, int i);
+
+// entry (i, i) of one term, every kind but LO_OP_LOWRANK_DIAG (k_pc_init squares the staged rows)
 template <typename T>
 __device__ __forceinline__ T src_diag(const PcDevT<T>& d, const lo_op_desc& op, int64_t b, int i) {
   const T* A0 = pc_ptr<T>(op.A0);
   const T* A1 = pc_ptr<T>(op.A1);
-  if (op.kind == LO_OP_LOWRANK_DIAG) {
-    const T* ci = A0 + ((size_t)b * d.N + i) * op.R;
-    return seq_dot(ci, ci, (int)op.R);
-  } else if (op.kind == LO_OP_DENSE_DIAG) {
+  if (op.kind == LO_OP_DENSE_DIAG) {
     return A0[((size_t)b * d.N + i) * d.N + i];
   } else if (op.kind == LO_OP_CALLBACK) {  // generic operator: A1 = matrix._diagonal(), A0 = the fetched pivot rows
     return A1[(size_t)b * d.N + i];
@@ -165,85 +245,113 @@ __device__ __forceinline__ T src_diag(const PcDevT<T>& d, const lo_op_desc& op, 
     float s = th[op.R];
     for (int t = 1; t < op.nterms; ++t) s = s + th[(size_t)t * (op.R + 1) + op.R];
     return (T)s;
-  } else if (op.kind == LO_OP_KERNEL_KRON_DIAG) {  // row i = (p, tau): os2 g(0) Bt[tau, tau] = os2 Bt[tau, tau]
-    const int nt = op.nterms, tau = i % nt;
-    return (T)(op.A1[(size_t)b * (op.R + 1) + op.R] * op.task[((size_t)b * nt + tau) * nt + tau]);
-  } else if (op.kind == LO_OP_KERNEL_TASK_DIAG) {  // os2 g(0) Bt[t_i, t_i], t_i the (clamped) id in the points' last column
+  } else if (op.kind == LO_OP_KERNEL_KRON_DIAG || op.kind == LO_OP_KERNEL_TASK_DIAG) {
+    // os2 g(0) Bt[t_i, t_i]: KRON: row i = (point, t_i); TASK: t_i the (clamped) id in the points' last column
     const int D = (int)op.R, nt = op.nterms;
-    const int ti = tk_task_id(op.A0[((size_t)b * d.N + i) * (D + 1) + D], nt);
+    const int ti = op.kind == LO_OP_KERNEL_KRON_DIAG ? i % nt : tk_task_id(op.A0[((size_t)b * d.N + i) * (D + 1) + D], nt);
     return (T)(op.A1[(size_t)b * (D + 1) + D] * op.task[((size_t)b * nt + ti) * nt + ti]);
   } else if (op.kind == LO_OP_KERNEL_GRAD_DIAG) {  // row i = (p, a): os2 for the value, os2 t_a^2 for a derivative
     const int D = (int)op.R, a = i % (D + 1);
     const float* th = op.A1 + (size_t)b * (D + 1);
     return (T)(a == 0 ? th[D] : th[D] * (th[a - 1] * th[a - 1]));
   } else if (op.kind == LO_OP_TOEPLITZ_KRON_DIAG) {
-    // prod_k t_k[0], the trailing factors multiplied first (kronecker_product_linear_operator.py:22-28)
-    const int D = d.ski.grid_ndim;
-    int64_t sumM = 0;
-    for (int k = 0; k < D; ++k) sumM += d.ski.grid_m[k];
-    const T* col = A0 + (size_t)b * sumM;
-    int64_t o = sumM - d.ski.grid_m[D - 1];
-    T t0 = col[o];
-    for (int k = D - 2; k >= 0; --k) {
-      o -= d.ski.grid_m[k];
-      t0 = col[o] * t0;
-    }
-    return t0;
-  } else if (op.kind == LO_OP_SKI_DIAG) {  // (left_interp(li, lv, sqrt t0) * left_interp(ri, rv, sqrt t0)), :94-101
-    // (an index outside [0, M) contributes nothing, as in the rows below)
-    const int J = (int)op.n2;
-    const int64_t M = op.R;
-    const T s = pc_sqrt<T>(A0[(size_t)b * M]);
-    const int64_t* li = d.ski.left_idx + ((size_t)b * d.N + i) * J;
-    const int64_t* ri = d.ski.right_idx + ((size_t)b * d.N + i) * J;
-    const T* lv = pc_ptr<T>(d.ski.left_vals) + ((size_t)b * d.N + i) * J;
-    const T* rv = pc_ptr<T>(d.ski.right_vals) + ((size_t)b * d.N + i) * J;
-    T l = T(0), r = T(0);
-    for (int j = 0; j < J; ++j) {
-      const T lt = (li[j] >= 0 && li[j] < M) ? s * lv[j] : T(0);
-      const T rt = (ri[j] >= 0 && ri[j] < M) ? s * rv[j] : T(0);
-      l = (j == 0) ? lt : l + lt;
-      r = (j == 0) ? rt : r + rt;
-    }
-    return l * r;
-  } else if (op.kind == LO_OP_SKI_SUM_DIAG) {  // the exact diagonal: entry (i, i) of every term, terms ascending
-    T s = T(0);
-    for (int p = 0; p < op.nterms; ++p) {
-      const T tv = ski_entry<T>(d.ski, op.A0, op.R, (int)op.n2, (size_t)b * op.nterms + p, d.N, i, i);
-      s = p == 0 ? tv : s + tv;
-    }
-    return s;
-  } else if (op.kind == LO_OP_SKI_GRID_DIAG) {
-    // the same over the constant base diagonal t0 = prod_k t_k[0] (the Kronecker diagonal of the reference multiplies
-    // the trailing factors first, kronecker_product_linear_operator.py:22-28)
-    const int J = (int)op.n2;
-    const int64_t M = op.R;
-    const int D = d.ski.grid_ndim;
-    int64_t sumM = 0;
-    for (int k = 0; k < D; ++k) sumM += d.ski.grid_m[k];
-    const T* col = A0 + (size_t)b * sumM;
-    T t0 = col[sumM - d.ski.grid_m[D - 1]];
-    for (int64_t k = D - 2, o = sumM - d.ski.grid_m[D - 1]; k >= 0; --k) {
-      o -= d.ski.grid_m[k];
-      t0 = col[o] * t0;
-    }
-    const T s = pc_sqrt<T>(t0);
-    const int64_t* li = d.ski.left_idx + ((size_t)b * d.N + i) * J;
-    const int64_t* ri = d.ski.right_idx + ((size_t)b * d.N + i) * J;
-    const T* lv = pc_ptr<T>(d.ski.left_vals) + ((size_t)b * d.N + i) * J;
-    const T* rv = pc_ptr<T>(d.ski.right_vals) + ((size_t)b * d.N + i) * J;
-    T l = T(0), r = T(0);
-    for (int j = 0; j < J; ++j) {
-      const T lt = (li[j] >= 0 && li[j] < M) ? s * lv[j] : T(0);
-      const T rt = (ri[j] >= 0 && ri[j] < M) ? s * rv[j] : T(0);
-      l = (j == 0) ? lt : l + lt;
-      r = (j == 0) ? rt : r + rt;
-    }
-    return l * r;
+    return grid_t0(grid_cols(d, op.A0, b));
+  } else if (op.kind == LO_OP_SKI_DIAG || op.kind == LO_OP_SKI_GRID_DIAG) {
+    // the approximate diagonal over the base's constant diagonal t0: t[0], on a grid prod_k t_k[0]
+    const T t0 = op.kind == LO_OP_SKI_DIAG ? A0[(size_t)b * op.R] : grid_t0(grid_cols(d, op.A0, b));
+    return ski_approx_diag<T>(d.ski, op.R, (int)op.n2, (size_t)b * d.N + i, pc_sqrt<T>(t0));
+  } else if (op.kind == LO_OP_SKI_SUM_DIAG) {  // the exact diagonal: entry (i, i) of the row, terms ascending
+    return src_entry(d, op, b, i, i);
   } else {
     const int n1 = (int)op.R, n2 = (int)op.n2;
     const int i1 = i / n2, i2 = i % n2;
     return A0[((size_t)b * n1 + i1) * n1 + i1] * A1[((size_t)b * n2 + i2) * n2 + i2];
+  }
+}
+
+// entry (pim, i) of one term, every kind but LO_OP_LOWRANK_DIAG (whose rows k_pc_update stages in LDS).  The kernel
+// kinds are fp32 kinds: their operands are read as float
+template <typename T>
+__device__ __forceinline__ T src_entry(const PcDevT<T>& d, const lo_op_desc& tm, int64_t b, int pim, int i) {
+  const T* A0 = pc_ptr<T>(tm.A0);
+  const int N = (int)d.N;
+  if (tm.kind == LO_OP_DENSE_DIAG) {
+    return A0[((size_t)b * N + pim) * N + i];
+  } else if (tm.kind == LO_OP_CALLBACK) {
+    return A0[(size_t)b * N + i];  // row pi_m of this member, fetched by the host callback for this pivot
+  } else if (tm.kind == LO_OP_HADAMARD_DIAG) {
+    const int p = (int)tm.R, q = (int)tm.n2;
+    const T* F = A0 + (size_t)b * N * p;
+    const T* G = pc_ptr<T>(tm.A1) + (size_t)b * N * q;
+    return seq_dot(F + (size_t)pim * p, F + (size_t)i * p, p) * seq_dot(G + (size_t)pim * q, G + (size_t)i * q, q);
+  } else if (tm.kind == LO_OP_TOEPLITZ_DIAG) {
+    return A0[(size_t)b * tm.R + (pim > i ? pim - i : i - pim)];
+  } else if (tm.kind == LO_OP_KERNEL_DIAG) {
+    const int D = (int)tm.R;
+    const float* th = tm.A1 + (size_t)b * (D + 1);
+    const float r2 = kern_r2(tm.A0 + ((size_t)b * N + pim) * D, tm.A0 + ((size_t)b * N + i) * D, th, D);
+    return (T)(th[D] * kf_g_rt((int)tm.n2, r2));
+  } else if (tm.kind == LO_OP_KERNEL_SUM_DIAG) {  // the same per term over the same points, summed in term order
+    const int D = (int)tm.R;
+    const float* xp = tm.A0 + ((size_t)b * N + pim) * D;
+    const float* xi = tm.A0 + ((size_t)b * N + i) * D;
+    float s = 0.0f;
+    for (int t = 0; t < tm.nterms; ++t) {
+      const float* th = tm.A1 + ((size_t)b * tm.nterms + t) * (D + 1);
+      const float kt = th[D] * kf_g_rt((int)((tm.n2 >> (4 * t)) & 15), kern_r2(xp, xi, th, D));
+      s = t == 0 ? kt : s + kt;
+    }
+    return (T)s;
+  } else if (tm.kind == LO_OP_KERNEL_KRON_DIAG) {  // pivot (p, tau), entry (j, s): (os2 g(r_pj)) Bt[tau, s]
+    const int D = (int)tm.R, nt = tm.nterms;
+    const int n = N / nt, pp = pim / nt, tau = pim - pp * nt, jj = i / nt, ss = i - jj * nt;
+    const float* th = tm.A1 + (size_t)b * (D + 1);
+    const float r2 = kern_r2(tm.A0 + ((size_t)b * n + pp) * D, tm.A0 + ((size_t)b * n + jj) * D, th, D);
+    return (T)((th[D] * kf_g_rt((int)tm.n2, r2)) * tm.task[((size_t)b * nt + tau) * nt + ss]);
+  } else if (tm.kind == LO_OP_KERNEL_TASK_DIAG) {  // pivot p, entry j: (os2 g(r_pj)) Bt[t_p, t_j], ids in column D
+    const int D = (int)tm.R, nt = tm.nterms;
+    const float* th = tm.A1 + (size_t)b * (D + 1);
+    const float* xp = tm.A0 + ((size_t)b * N + pim) * (D + 1);
+    const float* xi = tm.A0 + ((size_t)b * N + i) * (D + 1);
+    const int tp = tk_task_id(xp[D], nt), tj = tk_task_id(xi[D], nt);
+    return (T)((th[D] * kf_g_rt((int)tm.n2, kern_r2(xp, xi, th, D))) * tm.task[((size_t)b * nt + tp) * nt + tj]);
+  } else if (tm.kind == LO_OP_KERNEL_GRAD_DIAG) {  // pivot (p, al), entry (j, be): the block formula of lo_amd.h
+    const int D = (int)tm.R, nt = D + 1;
+    const int n = N / nt, pp = pim / nt, al = pim - pp * nt, jj = i / nt, be = i - jj * nt;
+    const float* th = tm.A1 + (size_t)b * nt;
+    const float* xp = tm.A0 + ((size_t)b * n + pp) * D;
+    const float* xi = tm.A0 + ((size_t)b * n + jj) * D;
+    float r2 = 0.0f, ua = 0.0f, ub = 0.0f;  // the loop of kern_r2, keeping the differences u of the coordinates al, be
+    for (int k = 0; k < D; ++k) {
+      const float df = xp[k] * th[k] - xi[k] * th[k];
+      r2 = r2 + df * df;
+      if (k + 1 == al) ua = df;
+      if (k + 1 == be) ub = df;
+    }
+    const float e = th[D] * kf_g_rt(LO_KERNEL_RBF, r2);
+    float f;
+    if (al == 0) f = be == 0 ? 1.0f : th[be - 1] * ub;
+    else if (be == 0) f = -(th[al - 1] * ua);
+    else f = (th[al - 1] * th[be - 1]) * ((al == be ? 1.0f : 0.0f) - ua * ub);
+    return (T)(e * f);
+  } else if (tm.kind == LO_OP_TOEPLITZ_KRON_DIAG) {
+    const GridCols<T> g = grid_cols(d, tm.A0, b);
+    return grid_base(g, grid_pt(g, pim), grid_pt(g, i));
+  } else if (tm.kind == LO_OP_SKI_DIAG) {
+    return ski_entry<T, false>(d, tm, (size_t)b, pim, i);
+  } else if (tm.kind == LO_OP_SKI_SUM_DIAG) {  // the same row per term, summed in term order
+    T tv = T(0);
+    for (int p = 0; p < tm.nterms; ++p) {
+      const T pv = ski_entry<T, false>(d, tm, (size_t)b * tm.nterms + p, pim, i);
+      tv = p == 0 ? pv : tv + pv;
+    }
+    return tv;
+  } else if (tm.kind == LO_OP_SKI_GRID_DIAG) {
+    return ski_entry<T, true>(d, tm, (size_t)b, pim, i);
+  } else {  // LO_OP_KRON_DIAG: K1[p1, i1] K2[p2, i2]
+    const int n1 = (int)tm.R, n2 = (int)tm.n2;
+    const int p1 = pim / n2, p2 = pim % n2, i1 = i / n2, i2 = i % n2;
+    return A0[((size_t)b * n1 + p1) * n1 + i1] * pc_ptr<T>(tm.A1)[((size_t)b * n2 + p2) * n2 + i2];
   }
 }
 
@@ -254,13 +362,7 @@ template <typename T>
 __device__ __forceinline__ void stage_rows(const T* __restrict__ Cb, int R, const long long* __restrict__ perm,
                                            int j0, int np, T* __restrict__ tile) {
   const int ld = R + 1;
-  if constexpr (sizeof(T) != 4) {
-    for (int e = threadIdx.x; e < np * R; e += kThreads) {
-      const int pos = e / R, r = e % R;
-      const int i = perm ? (int)perm[j0 + pos] : j0 + pos;
-      tile[pos * ld + r] = Cb[(size_t)i * R + r];
-    }
-  } else if ((R & 3) == 0) {
+  if (sizeof(T) == 4 && (R & 3) == 0) {
     const int RQ = R >> 2;
     for (int e = threadIdx.x; e < np * RQ; e += kThreads) {
       const int pos = e / RQ, q = e % RQ;
@@ -279,10 +381,31 @@ __device__ __forceinline__ void stage_rows(const T* __restrict__ Cb, int R, cons
 }
 
 template <typename T>
-__device__ __forceinline__ int tile_positions(int R) {
+__host__ __device__ __forceinline__ int tile_positions(int R) {
   // LDS budget ~48 KiB for the tile: 256 positions for R <= 47 (float), fewer for fat roots
   const int tp = (int)(49152 / sizeof(T)) / (R + 1);
   return tp >= kThreads ? kThreads : (tp < 1 ? 1 : tp);
+}
+
+// The walk over the low-rank terms that the kernels and the host's LDS sizing share: positions are walked `tp` at a time,
+// few enough for the fattest term's tile (one tile, reused by the terms); Rtot: the pivot rows C[pi_m, :] of all terms
+// side by side; Rmax + 1: the widest tile row (-1: no low-rank term, no tile)
+struct PcTiles {
+  int tp;
+  int64_t Rtot, Rmax;
+};
+template <typename T>
+__host__ __device__ __forceinline__ PcTiles pc_tiles(const PcDevT<T>& d) {
+  PcTiles w{kThreads, 0, -1};
+  for (int it = 0; it < d.nterms; ++it)
+    if (d.terms[it].kind == LO_OP_LOWRANK_DIAG) {
+      const int64_t R = d.terms[it].R;
+      const int tp = tile_positions<T>((int)R);
+      w.tp = tp < w.tp ? tp : w.tp;
+      w.Rtot += R;
+      w.Rmax = R > w.Rmax ? R : w.Rmax;
+    }
+  return w;
 }
 
 // per-slice argmax partial: best (value, position) with the FIRST maximal position winning
@@ -321,10 +444,7 @@ __global__ __launch_bounds__(kThreads) void k_pc_init(PcDevT<T> d) {
   const int64_t b = blockIdx.y;
   const int N = (int)d.N;
   const int j0 = s * d.rows, j1 = min(N, j0 + d.rows);
-  // positions are walked in tiles small enough for the fattest low-rank term's LDS tile
-  int tp = kThreads;
-  for (int it = 0; it < d.nterms; ++it)
-    if (d.terms[it].kind == LO_OP_LOWRANK_DIAG) tp = min(tp, tile_positions<T>((int)d.terms[it].R));
+  const int tp = pc_tiles(d).tp;
   T lmax = pc_ninf<T>(), lsum = T(0);
   T bv = pc_ninf<T>();
   int bj = 0x7fffffff;
@@ -453,13 +573,9 @@ __global__ __launch_bounds__(kThreads) void k_pc_update(PcDevT<T> d, int m) {
   // shared memory: [max_rank] L[j][pi_m] | per low-rank term its row C[pi_m,:] | one row tile (reused by the terms)
   T* upd = sh;
   T* crow = sh + d.max_rank;
-  int Rtot = 0, tp = kThreads;
-  for (int it = 0; it < d.nterms; ++it)
-    if (d.terms[it].kind == LO_OP_LOWRANK_DIAG) {
-      Rtot += (int)d.terms[it].R;
-      tp = min(tp, tile_positions<T>((int)d.terms[it].R));
-    }
-  T* tile = crow + Rtot;
+  const PcTiles walk = pc_tiles(d);
+  const int tp = walk.tp;
+  T* tile = crow + (int)walk.Rtot;
   for (int j = threadIdx.x; j < m; j += kThreads) upd[j] = Lb[(size_t)j * N + pim];
   {
     int off = 0;
@@ -494,146 +610,7 @@ __global__ __launch_bounds__(kThreads) void k_pc_update(PcDevT<T> d, int m) {
         if (live) tv = seq_dot(crow + off, tile + threadIdx.x * (R + 1), R);
         off += R;
       } else if (live) {
-        if (tm.kind == LO_OP_DENSE_DIAG) {
-          tv = pc_ptr<T>(tm.A0)[((size_t)b * N + pim) * N + i];
-        } else if (tm.kind == LO_OP_CALLBACK) {
-          tv = pc_ptr<T>(tm.A0)[(size_t)b * N + i];  // row pi_m of this member, fetched by the host callback for this pivot
-        } else if (tm.kind == LO_OP_HADAMARD_DIAG) {
-          const int p = (int)tm.R, q = (int)tm.n2;
-          const T* F = pc_ptr<T>(tm.A0) + (size_t)b * N * p;
-          const T* G = pc_ptr<T>(tm.A1) + (size_t)b * N * q;
-          tv = seq_dot(F + (size_t)pim * p, F + (size_t)i * p, p) * seq_dot(G + (size_t)pim * q, G + (size_t)i * q, q);
-        } else if (tm.kind == LO_OP_TOEPLITZ_DIAG) {
-          const int lag = pim > i ? pim - i : i - pim;
-          tv = pc_ptr<T>(tm.A0)[(size_t)b * tm.R + lag];
-        } else if (tm.kind == LO_OP_KERNEL_DIAG) {  // (an fp32 kind: the operands are read as float)
-          const int D = (int)tm.R;
-          const float* th = tm.A1 + (size_t)b * (D + 1);
-          const float* xp = tm.A0 + ((size_t)b * N + pim) * D;
-          const float* xi = tm.A0 + ((size_t)b * N + i) * D;
-          float r2 = 0.0f;
-          for (int k = 0; k < D; ++k) {
-            const float df = xp[k] * th[k] - xi[k] * th[k];
-            r2 = r2 + df * df;
-          }
-          tv = (T)(th[D] * kf_g_rt((int)tm.n2, r2));
-        } else if (tm.kind == LO_OP_KERNEL_SUM_DIAG) {  // the same row source per term, summed in term order
-          const int D = (int)tm.R;
-          const float* xp = tm.A0 + ((size_t)b * N + pim) * D;
-          const float* xi = tm.A0 + ((size_t)b * N + i) * D;
-          float s = 0.0f;
-          for (int t = 0; t < tm.nterms; ++t) {
-            const float* th = tm.A1 + ((size_t)b * tm.nterms + t) * (D + 1);
-            float r2 = 0.0f;
-            for (int k = 0; k < D; ++k) {
-              const float df = xp[k] * th[k] - xi[k] * th[k];
-              r2 = r2 + df * df;
-            }
-            const float kt = th[D] * kf_g_rt((int)((tm.n2 >> (4 * t)) & 15), r2);
-            s = t == 0 ? kt : s + kt;
-          }
-          tv = (T)s;
-        } else if (tm.kind == LO_OP_KERNEL_KRON_DIAG) {  // pivot (p, tau), entry (j, s): (os2 g(r_pj)) Bt[tau, s]
-          const int D = (int)tm.R, nt = tm.nterms;
-          const int n = N / nt, pp = pim / nt, tau = pim - pp * nt, jj = i / nt, ss = i - jj * nt;
-          const float* th = tm.A1 + (size_t)b * (D + 1);
-          const float* xp = tm.A0 + ((size_t)b * n + pp) * D;
-          const float* xi = tm.A0 + ((size_t)b * n + jj) * D;
-          float r2 = 0.0f;
-          for (int k = 0; k < D; ++k) {
-            const float df = xp[k] * th[k] - xi[k] * th[k];
-            r2 = r2 + df * df;
-          }
-          tv = (T)((th[D] * kf_g_rt((int)tm.n2, r2)) * tm.task[((size_t)b * nt + tau) * nt + ss]);
-        } else if (tm.kind == LO_OP_KERNEL_TASK_DIAG) {  // pivot p, entry j: (os2 g(r_pj)) Bt[t_p, t_j]
-          const int D = (int)tm.R, nt = tm.nterms;
-          const float* th = tm.A1 + (size_t)b * (D + 1);
-          const float* xp = tm.A0 + ((size_t)b * N + pim) * (D + 1);
-          const float* xi = tm.A0 + ((size_t)b * N + i) * (D + 1);
-          float r2 = 0.0f;
-          for (int k = 0; k < D; ++k) {
-            const float df = xp[k] * th[k] - xi[k] * th[k];
-            r2 = r2 + df * df;
-          }
-          const int tp = tk_task_id(xp[D], nt), tj = tk_task_id(xi[D], nt);
-          tv = (T)((th[D] * kf_g_rt((int)tm.n2, r2)) * tm.task[((size_t)b * nt + tp) * nt + tj]);
-        } else if (tm.kind == LO_OP_KERNEL_GRAD_DIAG) {  // pivot (p, al), entry (j, be): the block formula of lo_amd.h
-          const int D = (int)tm.R, nt = D + 1;
-          const int n = N / nt, pp = pim / nt, al = pim - pp * nt, jj = i / nt, be = i - jj * nt;
-          const float* th = tm.A1 + (size_t)b * nt;
-          const float* xp = tm.A0 + ((size_t)b * n + pp) * D;
-          const float* xi = tm.A0 + ((size_t)b * n + jj) * D;
-          float r2 = 0.0f, ua = 0.0f, ub = 0.0f;  // u = the separately rounded scaled coordinates differenced
-          for (int k = 0; k < D; ++k) {
-            const float df = xp[k] * th[k] - xi[k] * th[k];
-            r2 = r2 + df * df;
-            if (k + 1 == al) ua = df;
-            if (k + 1 == be) ub = df;
-          }
-          const float e = th[D] * kf_g_rt(LO_KERNEL_RBF, r2);
-          float f;
-          if (al == 0) f = be == 0 ? 1.0f : th[be - 1] * ub;
-          else if (be == 0) f = -(th[al - 1] * ua);
-          else f = (th[al - 1] * th[be - 1]) * ((al == be ? 1.0f : 0.0f) - ua * ub);
-          tv = (T)(e * f);
-        } else if (tm.kind == LO_OP_TOEPLITZ_KRON_DIAG) {
-          // prod_k t_k[|p_k - i_k|], factors multiplied left to right (kronecker_product_linear_operator.py:198-216);
-          // consecutive threads hold consecutive positions j: the gathers from the (small) columns stay in cache
-          const int D = d.ski.grid_ndim;
-          const int m1 = (int)d.ski.grid_m[D - 2], m2 = (int)d.ski.grid_m[D - 1];  // the two trailing axes
-          const int m0 = D == 3 ? (int)d.ski.grid_m[0] : 0;
-          const T* c0 = pc_ptr<T>(tm.A0) + (size_t)b * (m0 + m1 + m2);  // (D == 2: no leading axis)
-          const T* c1 = c0 + m0;
-          const T* c2 = c1 + m1;
-          const int p2 = pim % m2, p1 = (pim / m2) % m1, p0 = pim / (m2 * m1);
-          const int q2 = i % m2, q1 = (i / m2) % m1, q0 = i / (m2 * m1);
-          const T f1 = c1[p1 > q1 ? p1 - q1 : q1 - p1], f2 = c2[p2 > q2 ? p2 - q2 : q2 - p2];
-          tv = D == 3 ? (c0[p0 > q0 ? p0 - q0 : q0 - p0] * f1) * f2 : f1 * f2;
-        } else if (tm.kind == LO_OP_SKI_DIAG) {
-          tv = ski_entry<T>(d.ski, tm.A0, tm.R, (int)tm.n2, (size_t)b, N, pim, i);
-        } else if (tm.kind == LO_OP_SKI_SUM_DIAG) {  // the same row per term, summed in term order
-          for (int p = 0; p < tm.nterms; ++p) {
-            const T pv = ski_entry<T>(d.ski, tm.A0, tm.R, (int)tm.n2, (size_t)b * tm.nterms + p, N, pim, i);
-            tv = p == 0 ? pv : tv + pv;
-          }
-        } else if (tm.kind == LO_OP_SKI_GRID_DIAG) {
-          // the same sum in the same order with base[g, h] = prod_k t_k[|g_k - h_k|], factors multiplied left to right
-          // (kronecker_product_linear_operator.py:198-216), g and h decomposed by the grid shape
-          const int J = (int)tm.n2;
-          const int M = (int)tm.R;  // (<= LO_SKI_GRID_MAX_M: 32-bit index arithmetic)
-          const int D = d.ski.grid_ndim;
-          const int m1 = (int)d.ski.grid_m[D - 2], m2 = (int)d.ski.grid_m[D - 1];  // the two trailing axes
-          const int m0 = D == 3 ? (int)d.ski.grid_m[0] : 0;
-          const T* c0 = pc_ptr<T>(tm.A0) + (size_t)b * (m0 + m1 + m2);  // (D == 2: no leading axis)
-          const T* c1 = c0 + m0;
-          const T* c2 = c1 + m1;
-          const int64_t* li = d.ski.left_idx + ((size_t)b * N + pim) * J;
-          const T* lv = pc_ptr<T>(d.ski.left_vals) + ((size_t)b * N + pim) * J;
-          const int64_t* ri = d.ski.right_idx + ((size_t)b * N + i) * J;
-          const T* rv = pc_ptr<T>(d.ski.right_vals) + ((size_t)b * N + i) * J;
-          for (int bb = 0; bb < J; ++bb) {
-            const int64_t q64 = ri[bb];
-            const bool q_ok = q64 >= 0 && q64 < M;
-            const int q = q_ok ? (int)q64 : 0;
-            const int q2 = q % m2, q1 = (q / m2) % m1, q0 = q / (m2 * m1);
-            for (int a = 0; a < J; ++a) {
-              const int64_t p64 = li[a];
-              const bool p_ok = p64 >= 0 && p64 < M;
-              const int p = p_ok ? (int)p64 : 0;
-              const int p2 = p % m2, p1 = (p / m2) % m1, p0 = p / (m2 * m1);
-              T base = T(0);
-              if (p_ok && q_ok) {
-                const T f1 = c1[p1 > q1 ? p1 - q1 : q1 - p1], f2 = c2[p2 > q2 ? p2 - q2 : q2 - p2];
-                base = D == 3 ? (c0[p0 > q0 ? p0 - q0 : q0 - p0] * f1) * f2 : f1 * f2;
-              }
-              tv = (bb == 0 && a == 0) ? base * (lv[a] * rv[bb]) : tv + base * (lv[a] * rv[bb]);
-            }
-          }
-        } else {
-          const int n1 = (int)tm.R, n2 = (int)tm.n2;
-          const int p1 = pim / n2, p2 = pim % n2, i1 = i / n2, i2 = i % n2;
-          tv = pc_ptr<T>(tm.A0)[((size_t)b * n1 + p1) * n1 + i1] * pc_ptr<T>(tm.A1)[((size_t)b * n2 + p2) * n2 + i2];
-        }
+        tv = src_entry(d, tm, b, pim, i);
       }
       rowv = (it == 0) ? tv : rowv + tv;
     }
@@ -725,22 +702,9 @@ static int pc_stream_t(const lo_op_desc* op, const T* diag0, pc_rowfetch_any row
   LO_HIP_CHECK(hipMemsetAsync(L_rows, 0, sizeof(T) * (size_t)B * max_rank * N, st));  // L = zeros :36-42
   dim3 grid(d.S, (unsigned)B), block(kThreads);
   // shared memory: the pivot rows of all low-rank terms (R elements in total) + one row tile sized for the walk of the
-  // fattest low-rank term (the kernels walk min over the terms of tile_positions(R_i) positions at a time)
-  size_t R = 0, tile_elems = 0;
-  {
-    size_t tpmin = kThreads;
-    for (int it = 0; it < d.nterms; ++it)
-      if (d.terms[it].kind == LO_OP_LOWRANK_DIAG) {
-        const size_t Ri = (size_t)d.terms[it].R;
-        R += Ri;
-        size_t tp = (49152 / sizeof(T)) / (Ri + 1);
-        tp = tp >= (size_t)kThreads ? (size_t)kThreads : (tp < 1 ? 1 : tp);
-        tpmin = std::min(tpmin, tp);
-      }
-    for (int it = 0; it < d.nterms; ++it)
-      if (d.terms[it].kind == LO_OP_LOWRANK_DIAG)
-        tile_elems = std::max(tile_elems, tpmin * ((size_t)d.terms[it].R + 1));
-  }
+  // fattest low-rank term (pc_tiles: the walk the kernels make)
+  const PcTiles walk = pc_tiles(d);
+  const size_t R = (size_t)walk.Rtot, tile_elems = (size_t)walk.tp * (size_t)(walk.Rmax + 1);
   if ((tile_elems + R + max_rank) * sizeof(T) > 60000) return LO_ERR_UNSUPPORTED;
   LO_PROF_BEGIN("pc_init", st);
   hipLaunchKernelGGL((k_pc_init<T>), grid, block, tile_elems * sizeof(T), st, d);
@@ -769,11 +733,12 @@ static int pc_stream_t(const lo_op_desc* op, const T* diag0, pc_rowfetch_any row
   return LO_OK;
 }
 
-int pc_stream(const lo_op_desc* op, const float* diag0, lo_rowfetch_cb row_cb, void* row_user, int32_t max_rank,
-              float error_tol, float* L_rows, int64_t* perm, int32_t* rank_out, void* ws, size_t ws_bytes,
-              hipStream_t st) {
-  return pc_stream_t<float>(op, diag0, reinterpret_cast<pc_rowfetch_any>(row_cb), row_user, max_rank, error_tol, L_rows,
-                            perm, rank_out, ws, ws_bytes, st);
+// the descriptor of a generic operator whose rows and diagonal arrive through callbacks
+static lo_op_desc pc_cb_desc(int64_t B, int64_t N) {
+  lo_op_desc op;
+  memset(&op, 0, sizeof(op));
+  op.kind = LO_OP_CALLBACK; op.B = B; op.N = N;
+  return op;
 }
 
 template <typename T>
@@ -785,72 +750,40 @@ static size_t pc_ws_bytes(const lo_op_desc* op, int32_t max_rank, bool cb) {
   });
 }
 
-static int pc_check_kernel(const lo_op_desc* op) {
-  if (!op->A0 || !op->A1 || op->R < 1 || op->n2 < LO_KERNEL_RBF || op->n2 > LO_KERNEL_MATERN52) return LO_ERR_BADARG;
-  if (op->R > LO_KERNEL_MAX_DIM) return LO_ERR_UNSUPPORTED;
-  return LO_OK;
-}
-
-// fp32_kinds: the caller reads the operands as float (the float64 engine takes the plain kinds and sums of them only)
+// One *_desc_check per kind (lo_internal.h), shared with the kind's plan function; the streaming engine reads single
+// entries, so it adds none of the products' shape bounds.  fp32_kinds: the caller reads the operands as float (the
+// float64 engine takes the plain kinds and sums of them only)
 static int pc_check_desc(const lo_op_desc* op, bool fp32_kinds = true) {
-  if (op->kind == LO_OP_SUM) {
-    if (op->nterms < 2 || op->nterms > LO_MAX_TERMS || !op->terms) return LO_ERR_BADARG;
-    for (int i = 0; i < op->nterms; ++i) {
-      const lo_op_desc& t = op->terms[i];
-      if (!(plain_term_kind(t.kind) || kernel_term_kind(t.kind)) || t.B != op->B || t.N != op->N) return LO_ERR_BADARG;
-      if (kernel_term_kind(t.kind)) {  // (a term is validated as the kind on its own is)
-        if (!fp32_kinds) return LO_ERR_UNSUPPORTED;
-        if (const int rc = t.kind == LO_OP_KERNEL_DIAG ? pc_check_kernel(&t) : kernel_sum_desc_check(&t)) return rc;
+  int rc = LO_OK;
+  switch (op->kind) {
+    case LO_OP_LOWRANK_DIAG: case LO_OP_DENSE_DIAG: case LO_OP_KRON_DIAG: break;
+    case LO_OP_SUM:
+      if (op->nterms < 2 || op->nterms > LO_MAX_TERMS || !op->terms) return LO_ERR_BADARG;
+      for (int i = 0; i < op->nterms; ++i) {
+        const lo_op_desc& t = op->terms[i];
+        if (!(plain_term_kind(t.kind) || kernel_term_kind(t.kind)) || t.B != op->B || t.N != op->N) return LO_ERR_BADARG;
+        if (kernel_term_kind(t.kind)) {  // (a term is validated as the kind on its own is)
+          if (!fp32_kinds) return LO_ERR_UNSUPPORTED;
+          if ((rc = t.kind == LO_OP_KERNEL_DIAG ? kernel_desc_check(&t) : kernel_sum_desc_check(&t))) return rc;
+        }
       }
-    }
-  } else if (op->kind == LO_OP_HADAMARD_DIAG) {
-    if (!op->A0 || !op->A1 || op->R < 1 || op->n2 < 1) return LO_ERR_BADARG;
-  } else if (op->kind == LO_OP_TOEPLITZ_DIAG) {
-    if (!op->A0 || op->R != op->N) return LO_ERR_BADARG;
-  } else if (op->kind == LO_OP_KERNEL_DIAG) {
-    if (const int rc = pc_check_kernel(op)) return rc;
-  } else if (op->kind == LO_OP_KERNEL_SUM_DIAG) {
-    if (const int rc = kernel_sum_desc_check(op)) return rc;
-  } else if (op->kind == LO_OP_KERNEL_KRON_DIAG) {
-    if (const int rc = kernel_kron_desc_check(op)) return rc;
-  } else if (op->kind == LO_OP_KERNEL_GRAD_DIAG) {
-    if (const int rc = kernel_grad_desc_check(op)) return rc;
-  } else if (op->kind == LO_OP_KERNEL_TASK_DIAG) {
-    if (const int rc = kernel_task_desc_check(op)) return rc;
-  } else if (op->kind == LO_OP_SKI_DIAG) {
-    const lo_interp_desc* w = op->interp;
-    if (!op->A0 || op->R < 1 || op->n2 < 1 || !w || !w->left_idx || !w->left_vals || !w->right_idx || !w->right_vals)
-      return LO_ERR_BADARG;
-  } else if (op->kind == LO_OP_SKI_SUM_DIAG) {
-    if (const int rc = ski_sum_desc_check(op)) return rc;
-  } else if (op->kind == LO_OP_SKI_GRID_DIAG) {
-    const lo_interp_desc* w = op->interp;
-    if (!op->A0 || op->R < 1 || op->n2 < 1 || !w || !w->left_idx || !w->left_vals || !w->right_idx || !w->right_vals)
-      return LO_ERR_BADARG;
-    if (w->grid_ndim != 2 && w->grid_ndim != 3) return LO_ERR_UNSUPPORTED;
-    int64_t M = 1;
-    for (int k = 0; k < w->grid_ndim; ++k) {
-      if (w->grid_m[k] < 1 || w->grid_m[k] > LO_SKI_GRID_MAX_AXIS) return LO_ERR_UNSUPPORTED;
-      M *= w->grid_m[k];
-    }
-    if (M > LO_SKI_GRID_MAX_M) return LO_ERR_UNSUPPORTED;
-    if (M != op->R) return LO_ERR_BADARG;
-  } else if (op->kind == LO_OP_TOEPLITZ_KRON_DIAG) {
-    const lo_grid_desc* g = op->grid;
-    if (!op->A0 || !g) return LO_ERR_BADARG;
-    if (g->ndim != 2 && g->ndim != 3) return LO_ERR_UNSUPPORTED;
-    int64_t M = 1;
-    for (int k = 0; k < g->ndim; ++k) {
-      if (g->m[k] < 1 || g->m[k] > LO_SKI_GRID_MAX_AXIS) return LO_ERR_UNSUPPORTED;
-      M *= g->m[k];
-    }
-    if (M > LO_SKI_GRID_MAX_M) return LO_ERR_UNSUPPORTED;
-    if (M != op->R || M != op->N) return LO_ERR_BADARG;
-  } else if (op->kind != LO_OP_LOWRANK_DIAG && op->kind != LO_OP_DENSE_DIAG && op->kind != LO_OP_KRON_DIAG) {
-    return LO_ERR_UNSUPPORTED;
+      break;
+    case LO_OP_HADAMARD_DIAG: rc = hadamard_desc_check(op); break;
+    case LO_OP_TOEPLITZ_DIAG: rc = toeplitz_desc_check(op); break;
+    case LO_OP_TOEPLITZ_KRON_DIAG: rc = toeplitz_kron_desc_check(op); break;
+    case LO_OP_KERNEL_DIAG: rc = kernel_desc_check(op); break;
+    case LO_OP_KERNEL_SUM_DIAG: rc = kernel_sum_desc_check(op); break;
+    case LO_OP_KERNEL_KRON_DIAG: rc = kernel_kron_desc_check(op); break;
+    case LO_OP_KERNEL_GRAD_DIAG: rc = kernel_grad_desc_check(op); break;
+    case LO_OP_KERNEL_TASK_DIAG: rc = kernel_task_desc_check(op); break;
+    case LO_OP_SKI_DIAG: rc = ski_desc_check(op); break;
+    case LO_OP_SKI_SUM_DIAG: rc = ski_sum_desc_check(op); break;
+    // (an empty grid or stencil is refused here ahead of the grid shape; the plan refuses it behind, as a shape)
+    case LO_OP_SKI_GRID_DIAG: rc = (op->R < 1 || op->n2 < 1) ? LO_ERR_BADARG : ski_grid_desc_check(op); break;
+    default: return LO_ERR_UNSUPPORTED;
   }
-  if (op->N > 0x7ffffff0) return LO_ERR_UNSUPPORTED;
-  return LO_OK;
+  if (rc) return rc;
+  return op->N > 0x7ffffff0 ? LO_ERR_UNSUPPORTED : LO_OK;
 }
 
 }  // namespace lo
@@ -883,13 +816,11 @@ int lo_pivoted_cholesky_f32(const lo_op_desc* op, int32_t max_rank, float error_
     if (rc != LO_ERR_LAUNCH) return rc;
     (void)hipGetLastError();
   }
-  return pc_stream(op, nullptr, nullptr, nullptr, max_rank, error_tol, L_rows, perm, rank_out, ws, ws_bytes, st);
+  return pc_stream_t<float>(op, nullptr, nullptr, nullptr, max_rank, error_tol, L_rows, perm, rank_out, ws, ws_bytes, st);
 }
 
 size_t lo_pivoted_cholesky_cb_workspace_bytes(int64_t B, int64_t N, int32_t max_rank) {
-  lo_op_desc op;
-  memset(&op, 0, sizeof(op));
-  op.kind = LO_OP_CALLBACK; op.B = B; op.N = N;
+  const lo_op_desc op = pc_cb_desc(B, N);
   return pc_ws_bytes<float>(&op, max_rank, true);
 }
 
@@ -898,11 +829,9 @@ int lo_pivoted_cholesky_cb_f32(int64_t B, int64_t N, const float* diag, lo_rowfe
                                void* ws, size_t ws_bytes, void* stream) {
   if (!diag || !row_cb || !L_rows || !perm || !rank_out || !ws || max_rank < 1 || B < 1 || N < 1) return LO_ERR_BADARG;
   if (N > 0x7ffffff0) return LO_ERR_UNSUPPORTED;
-  lo_op_desc op;
-  memset(&op, 0, sizeof(op));
-  op.kind = LO_OP_CALLBACK; op.B = B; op.N = N;
-  return pc_stream(&op, diag, row_cb, row_user, max_rank, error_tol, L_rows, perm, rank_out, ws, ws_bytes,
-                   (hipStream_t)stream);
+  const lo_op_desc op = pc_cb_desc(B, N);
+  return pc_stream_t<float>(&op, diag, reinterpret_cast<pc_rowfetch_any>(row_cb), row_user, max_rank, error_tol, L_rows,
+                            perm, rank_out, ws, ws_bytes, (hipStream_t)stream);
 }
 
 // ---- float64 (round 4): the reference's PivotedCholesky.forward is dtype-generic.  Same streaming engine, same
@@ -914,20 +843,15 @@ size_t lo_pivoted_cholesky_f64_workspace_bytes(const lo_op_desc* op, int32_t max
 int lo_pivoted_cholesky_f64(const lo_op_desc* op, int32_t max_rank, double error_tol, double* L_rows, int64_t* perm,
                             int32_t* rank_out, void* ws, size_t ws_bytes, void* stream) {
   if (!op || !L_rows || !perm || !rank_out || !ws || max_rank < 1) return LO_ERR_BADARG;
-  if (op->kind == LO_OP_SKI_DIAG || op->kind == LO_OP_TOEPLITZ_DIAG || op->kind == LO_OP_HADAMARD_DIAG ||
-      op->kind == LO_OP_SKI_GRID_DIAG || op->kind == LO_OP_SKI_SUM_DIAG || op->kind == LO_OP_TOEPLITZ_KRON_DIAG ||
-      kernel_term_kind(op->kind) ||
-      op->kind == LO_OP_KERNEL_KRON_DIAG || op->kind == LO_OP_KERNEL_GRAD_DIAG || op->kind == LO_OP_KERNEL_TASK_DIAG)
-    return LO_ERR_UNSUPPORTED;  // (fp32 kinds)
+  // the kinds whose operands may be doubles; every other kind would have its floats read as doubles
+  if (!(plain_term_kind(op->kind) || op->kind == LO_OP_SUM)) return LO_ERR_UNSUPPORTED;
   if (const int rc = pc_check_desc(op, false)) return rc;
   return pc_stream_t<double>(op, nullptr, nullptr, nullptr, max_rank, error_tol, L_rows, perm, rank_out, ws, ws_bytes,
                              (hipStream_t)stream);
 }
 
 size_t lo_pivoted_cholesky_cb_f64_workspace_bytes(int64_t B, int64_t N, int32_t max_rank) {
-  lo_op_desc op;
-  memset(&op, 0, sizeof(op));
-  op.kind = LO_OP_CALLBACK; op.B = B; op.N = N;
+  const lo_op_desc op = pc_cb_desc(B, N);
   return pc_ws_bytes<double>(&op, max_rank, true);
 }
 
@@ -936,9 +860,7 @@ int lo_pivoted_cholesky_cb_f64(int64_t B, int64_t N, const double* diag, lo_rowf
                                void* ws, size_t ws_bytes, void* stream) {
   if (!diag || !row_cb || !L_rows || !perm || !rank_out || !ws || max_rank < 1 || B < 1 || N < 1) return LO_ERR_BADARG;
   if (N > 0x7ffffff0) return LO_ERR_UNSUPPORTED;
-  lo_op_desc op;
-  memset(&op, 0, sizeof(op));
-  op.kind = LO_OP_CALLBACK; op.B = B; op.N = N;
+  const lo_op_desc op = pc_cb_desc(B, N);
   return pc_stream_t<double>(&op, diag, reinterpret_cast<pc_rowfetch_any>(row_cb), row_user, max_rank, error_tol, L_rows,
                              perm, rank_out, ws, ws_bytes, (hipStream_t)stream);
 }

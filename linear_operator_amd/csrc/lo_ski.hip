@@ -482,17 +482,24 @@ int ski_interp_plan(MatvecPlan* pl, int64_t M, Arena* ar, hipStream_t st) {
   return csr_build(k.w.right_idx, op.B, op.N, op.n2, M, ar, &k.csr, st);
 }
 
+int toeplitz_desc_check(const lo_op_desc* op) { return (!op->A0 || op->R != op->N) ? LO_ERR_BADARG : LO_OK; }
+
+int ski_desc_check(const lo_op_desc* op) {
+  return (!op->A0 || op->R < 1 || op->n2 < 1 || !interp_ptrs_ok(op->interp)) ? LO_ERR_BADARG : LO_OK;
+}
+
 int ski_plan(MatvecPlan* pl, Arena* ar, hipStream_t st) {
   const lo_op_desc& op = pl->op;
   const int64_t M = op.R;
-  if (!op.A0 || M < 1) return LO_ERR_BADARG;
-  if (M > LO_TOEPLITZ_MAX_M) return LO_ERR_UNSUPPORTED;
-  if (op.kind == LO_OP_TOEPLITZ_DIAG) {
-    if (M != op.N) return LO_ERR_BADARG;
-  } else {
-    const lo_interp_desc* w = op.interp;
-    if (!w || !w->left_idx || !w->left_vals || !w->right_idx || !w->right_vals) return LO_ERR_BADARG;
-    if (!interp_shape_ok(op.B, op.N, op.n2, M)) return LO_ERR_BADARG;
+  const bool tz = op.kind == LO_OP_TOEPLITZ_DIAG;
+  const int bad = tz ? toeplitz_desc_check(&op) : ski_desc_check(&op);
+  // The order of the refusals, kept as it always was: (1) no column: BADARG; (2) M beyond the bound of the Toeplitz
+  // product: UNSUPPORTED (the plan's own condition -- the pivoted Cholesky reads single entries and has no such bound);
+  // (3) whatever else the shared check found: BADARG; (4) the products' own shape limits: BADARG
+  if (op.A0 && M > LO_TOEPLITZ_MAX_M) return LO_ERR_UNSUPPORTED;
+  if (bad) return bad;
+  if (tz ? M < 1 : !interp_shape_ok(op.B, op.N, op.n2, M)) return LO_ERR_BADARG;  // (the 32-bit limits of the products)
+  if (!tz) {
     const int rc = ski_interp_plan(pl, M, ar, st);
     if (rc) return rc;
   }

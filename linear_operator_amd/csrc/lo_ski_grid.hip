@@ -255,15 +255,18 @@ int toeplitz_kron_passes(const float* t, const int64_t* m, int ndim, int64_t B, 
 }
 
 // ---- the kind's plan and run functions (lo_matvec.hip): those of lo_ski.hip with the Toeplitz product replaced ------
+int ski_grid_desc_check(const lo_op_desc* op) {
+  if (!op->A0 || !interp_ptrs_ok(op->interp)) return LO_ERR_BADARG;
+  int64_t M = 0;
+  if (!grid_shape_ok(op->interp->grid_m, op->interp->grid_ndim, &M)) return LO_ERR_UNSUPPORTED;
+  return M != op->R ? LO_ERR_BADARG : LO_OK;
+}
+
 int ski_grid_plan(MatvecPlan* pl, Arena* ar, hipStream_t st) {
   const lo_op_desc& op = pl->op;
-  const lo_interp_desc* w = op.interp;
-  if (!op.A0 || !w || !w->left_idx || !w->left_vals || !w->right_idx || !w->right_vals) return LO_ERR_BADARG;
-  int64_t M = 0;
-  if (!grid_shape_ok(w->grid_m, w->grid_ndim, &M)) return LO_ERR_UNSUPPORTED;
-  if (M != op.R) return LO_ERR_BADARG;
-  if (!interp_shape_ok(op.B, op.N, op.n2, M) || pl->c > INT_MAX / 64) return LO_ERR_BADARG;
-  return ski_interp_plan(pl, M, ar, st);
+  if (const int rc = ski_grid_desc_check(&op)) return rc;
+  if (!interp_shape_ok(op.B, op.N, op.n2, op.R) || pl->c > INT_MAX / 64) return LO_ERR_BADARG;  // (32-bit limits)
+  return ski_interp_plan(pl, op.R, ar, st);
 }
 
 int ski_grid_matvec_run(const MatvecPlan* pl, const float* v, float* y, const int* stop, hipStream_t st) {
@@ -279,15 +282,19 @@ int ski_grid_matvec_run(const MatvecPlan* pl, const float* v, float* y, const in
 }
 
 // ---- LO_OP_TOEPLITZ_KRON_DIAG: y = (T_1 (x) .. (x) T_D) v + d o v ---------------------------------------------------------
+int toeplitz_kron_desc_check(const lo_op_desc* op) {
+  if (!op->A0 || !op->grid) return LO_ERR_BADARG;
+  int64_t M = 0;
+  if (!grid_shape_ok(op->grid->m, op->grid->ndim, &M)) return LO_ERR_UNSUPPORTED;
+  return (M != op->N || M != op->R) ? LO_ERR_BADARG : LO_OK;
+}
+
 int toeplitz_kron_plan(MatvecPlan* pl, Arena* ar, hipStream_t) {
   const lo_op_desc& op = pl->op;
-  if (!op.A0 || !op.grid) return LO_ERR_BADARG;
-  const lo_grid_desc g = *op.grid;
-  int64_t M = 0;
-  if (!grid_shape_ok(g.m, g.ndim, &M)) return LO_ERR_UNSUPPORTED;
-  if (M != op.N || M != op.R || pl->c > INT_MAX / 64) return LO_ERR_BADARG;
-  pl->tk.g = g;
-  pl->tk.tmp = ar->take<float>((size_t)op.B * M * pl->c);
+  if (const int rc = toeplitz_kron_desc_check(&op)) return rc;
+  if (pl->c > INT_MAX / 64) return LO_ERR_BADARG;
+  pl->tk.g = *op.grid;
+  pl->tk.tmp = ar->take<float>((size_t)op.B * op.N * pl->c);
   // A/B switch of DESIGN.md section 6j: the diagonal as vec_add_diag behind the passes instead of in the last store
   pl->tk.epilogue = getenv("LO_TKRON_EPILOGUE") != nullptr;
   return LO_OK;

@@ -71,8 +71,7 @@ static int interp_sum(const int64_t* idx, const float* vals, int64_t B, int64_t 
 }
 
 int ski_sum_desc_check(const lo_op_desc* op) {
-  const lo_interp_desc* w = op->interp;
-  if (!op->A0 || !w || !w->left_idx || !w->left_vals || !w->right_idx || !w->right_vals) return LO_ERR_BADARG;
+  if (!op->A0 || !interp_ptrs_ok(op->interp)) return LO_ERR_BADARG;
   if (op->nterms < 1 || op->n2 < 1 || op->R < 1 || op->B < 1 || op->N < 1) return LO_ERR_BADARG;
   if (op->nterms > LO_SKI_SUM_MAX_TERMS || op->R > LO_TOEPLITZ_MAX_M) return LO_ERR_UNSUPPORTED;
   if (!ski_sum_shape_ok(op->B, op->nterms, op->N, op->n2, op->R)) return LO_ERR_UNSUPPORTED;

@@ -6,8 +6,10 @@
 // pointer (the ones here are dummy addresses), keep no sub-plan (a leak report) and touch nothing out of bounds.  No GPU.
 // The solver sizers are also walked with Woodbury preconditioners (the padded copy of Q taken and not taken, the root
 // form alone), and the sizers of the other entry points with shapes of tests/workspace_cases.py, the five float64 sizers
-// (csrc/lo_*_f64.hip) among them.  Last, the compile-time
+// (csrc/lo_*_f64.hip) among them.  The compile-time
 // pickers of the matrix-free kernel family (csrc/lo_kernel_shape.h) are held to what the switches they replaced chose.
+// Last, refused descriptors of every kind go through lo_pivoted_cholesky_f32 / _f64 and lo_matvec_f32, which share one
+// descriptor check per kind (the *_desc_check functions of csrc/lo_internal.h): the return codes are pinned.
 //
 //   cd linear_operator_amd/csrc && mkdir -p build_asan
 //   for f in *.hip; do hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -fPIC -Xarch_host -fsanitize=address,undefined \
@@ -275,6 +277,39 @@ static int walk_pickers() {
   return bad;
 }
 
+// The return codes of refused descriptors at the entry points that share the kinds' *_desc_check functions: the pivoted
+// Cholesky (both precisions), which validates without a plan, and lo_matvec_f32, whose measuring pass runs the plan
+// function.  Every entry returns before anything touches the device: from the descriptor check, or -- the rows marked
+// "taken", the descriptors one side accepts and the other refuses -- at the empty workspace (LO_ERR_WORKSPACE, -3), which
+// every entry tests before its first launch.  A "taken" row must be of a kind that no resident engine takes (SKI, kernel,
+// a sum: pc_onchip_eligible and pc_onchip_rows_eligible are false), never low-rank, dense or Kronecker.  `want`: the codes of the sources before the checks were shared (ABI 37).
+struct Refused {
+  const char* name;
+  lo_op_desc op;
+  int want[3];  // lo_pivoted_cholesky_f32, lo_pivoted_cholesky_f64, lo_matvec_f32
+};
+
+static int walk_refused(const std::vector<Refused>& table) {
+  int bad = 0;
+  static char ws[256];  // a non-null workspace of no bytes
+  int64_t perm[1];
+  int32_t rank = 0;
+  float Lf[1], v[1] = {0}, y[1];
+  double Ld[1];
+  for (const Refused& r : table) {
+    const int got[3] = {lo_pivoted_cholesky_f32(&r.op, 4, 1e-3f, Lf, perm, &rank, ws, 0, nullptr),
+                        lo_pivoted_cholesky_f64(&r.op, 4, 1e-3, Ld, perm, &rank, ws, 0, nullptr),
+                        lo_matvec_f32(&r.op, v, y, 1, nullptr, 0, nullptr)};
+    printf("refused %-34s pivchol_f32 %d pivchol_f64 %d matvec %d\n", r.name, got[0], got[1], got[2]);
+    for (int k = 0; k < 3; ++k)
+      if (got[k] != r.want[k] || got[k] == LO_OK) {
+        printf("  entry %d returned %d, expected %d\n", k, got[k], r.want[k]);
+        ++bad;
+      }
+  }
+  return bad;
+}
+
 int main() {
   std::vector<Entry> t;
   t.push_back({"lowrank_r5", desc(LO_OP_LOWRANK_DIAG, 2, 300, 5, 0, false, LO_DIAG_FULL), true});
@@ -350,6 +385,92 @@ int main() {
   sum_late.terms = late;
   bad += walk({{"sum, bad last term", sum_late, true}});  // (its first terms do take buffers)
   bad += walk_precond(t[0].op) + walk_entries() + walk_f64() + walk_pickers();
+
+  // ---- refused descriptors through the pivoted Cholesky and the product: per kind a missing pointer, an out-of-range
+  // family or grid axis, M != R, and the fp32 kinds at the float64 entry (its UNSUPPORTED comes before the check)
+  const int BA = LO_ERR_BADARG, UN = LO_ERR_UNSUPPORTED, WS = LO_ERR_WORKSPACE;
+  std::vector<Refused> r;
+  auto with = [](lo_op_desc d, auto edit) { edit(d); return d; };
+  const lo_op_desc tz = t[6].op;
+  r.push_back({"hadamard, no G", with(had, [](lo_op_desc& d) { d.A1 = nullptr; }), {BA, UN, BA}});
+  r.push_back({"hadamard, q = 0", with(had, [](lo_op_desc& d) { d.n2 = 0; }), {BA, UN, BA}});
+  r.push_back({"toeplitz, no column", with(tz, [](lo_op_desc& d) { d.A0 = nullptr; }), {BA, UN, BA}});
+  r.push_back({"toeplitz, M != N", with(tz, [](lo_op_desc& d) { d.R = 32; }), {BA, UN, BA}});
+  r.push_back({"toeplitz, M != N beyond the bound", with(tz, [](lo_op_desc& d) { d.R = LO_TOEPLITZ_MAX_M + 1; }), {BA, UN, UN}});
+  lo_interp_desc w_nolv = w, g_axis = g2, g_ndim = g2, g_nori = g3;
+  w_nolv.left_vals = nullptr;
+  g_axis.grid_m[1] = LO_SKI_GRID_MAX_AXIS + 1;
+  g_ndim.grid_ndim = 4;
+  g_nori.right_idx = nullptr;
+  r.push_back({"ski, no interp", with(ski, [](lo_op_desc& d) { d.interp = nullptr; }), {BA, UN, BA}});
+  r.push_back({"ski, no left values", with(ski, [&](lo_op_desc& d) { d.interp = &w_nolv; }), {BA, UN, BA}});
+  r.push_back({"ski, no column", with(ski, [](lo_op_desc& d) { d.A0 = nullptr; }), {BA, UN, BA}});
+  r.push_back({"ski, J = 0", with(ski, [](lo_op_desc& d) { d.n2 = 0; }), {BA, UN, BA}});
+  r.push_back({"ski, M = 0", with(ski, [](lo_op_desc& d) { d.R = 0; }), {BA, UN, BA}});
+  // the two sides differ: the product bounds M (before it looks at J), the pivoted Cholesky reads single entries
+  r.push_back({"ski, M beyond the bound, J = 0",
+               with(ski, [](lo_op_desc& d) { d.R = LO_TOEPLITZ_MAX_M + 1; d.n2 = 0; }), {BA, UN, UN}});
+  r.push_back({"ski, M beyond the bound (taken)", with(ski, [](lo_op_desc& d) { d.R = LO_TOEPLITZ_MAX_M + 1; }), {WS, UN, UN}});
+  r.push_back({"ski, M at the bound (taken)", with(ski, [](lo_op_desc& d) { d.R = LO_TOEPLITZ_MAX_M; }), {WS, UN, WS}});
+  r.push_back({"ski grid, no right indices", with(grid3, [&](lo_op_desc& d) { d.interp = &g_nori; }), {BA, UN, BA}});
+  r.push_back({"ski grid, axis beyond the bound", with(grid2, [&](lo_op_desc& d) { d.interp = &g_axis; }), {UN, UN, UN}});
+  r.push_back({"ski grid, four axes", with(grid2, [&](lo_op_desc& d) { d.interp = &g_ndim; }), {UN, UN, UN}});
+  r.push_back({"ski grid, M != R", with(grid2, [](lo_op_desc& d) { d.R = 34; }), {BA, UN, BA}});
+  r.push_back({"ski grid, J = 0", with(grid2, [](lo_op_desc& d) { d.n2 = 0; }), {BA, UN, BA}});
+  r.push_back({"ski grid, J = 0, four axes", with(grid2, [&](lo_op_desc& d) { d.n2 = 0; d.interp = &g_ndim; }), {BA, UN, UN}});
+  lo_grid_desc gd = {2, 0, {5, 7, 0}}, gd_axis = {2, 0, {5, LO_SKI_GRID_MAX_AXIS + 1, 0}}, gd_ndim = {1, 0, {35, 0, 0}};
+  lo_op_desc tk = desc(LO_OP_TOEPLITZ_KRON_DIAG, 2, 35, 35, 0, false, LO_DIAG_FULL);
+  tk.grid = &gd;
+  r.push_back({"toeplitz kron, no grid", with(tk, [](lo_op_desc& d) { d.grid = nullptr; }), {BA, UN, BA}});
+  r.push_back({"toeplitz kron, no columns", with(tk, [](lo_op_desc& d) { d.A0 = nullptr; }), {BA, UN, BA}});
+  r.push_back({"toeplitz kron, axis beyond the bound", with(tk, [&](lo_op_desc& d) { d.grid = &gd_axis; }), {UN, UN, UN}});
+  r.push_back({"toeplitz kron, one axis", with(tk, [&](lo_op_desc& d) { d.grid = &gd_ndim; }), {UN, UN, UN}});
+  r.push_back({"toeplitz kron, M != R", with(tk, [](lo_op_desc& d) { d.R = 34; }), {BA, UN, BA}});
+  r.push_back({"toeplitz kron, M != N", with(tk, [](lo_op_desc& d) { d.N = 36; }), {BA, UN, BA}});
+  const lo_op_desc ko = desc(LO_OP_KERNEL_DIAG, 2, 100, 3, LO_KERNEL_MATERN32, true, LO_DIAG_FULL);
+  r.push_back({"kernel, no theta", with(ko, [](lo_op_desc& d) { d.A1 = nullptr; }), {BA, UN, BA}});
+  r.push_back({"kernel, family 4", with(ko, [](lo_op_desc& d) { d.n2 = 4; }), {BA, UN, BA}});
+  r.push_back({"kernel, family -1", with(ko, [](lo_op_desc& d) { d.n2 = -1; }), {BA, UN, BA}});
+  r.push_back({"kernel, D = 0", with(ko, [](lo_op_desc& d) { d.R = 0; }), {BA, UN, BA}});
+  r.push_back({"kernel, D beyond the bound", with(ko, [](lo_op_desc& d) { d.R = LO_KERNEL_MAX_DIM + 1; }), {UN, UN, UN}});
+  // the two sides differ: the product's launch bounds the batch, the pivoted Cholesky's does not
+  r.push_back({"kernel, B = 65536 (taken)", with(ko, [](lo_op_desc& d) { d.B = 65536; }), {WS, UN, UN}});
+  r.push_back({"kernel, B = 65535 (taken)", with(ko, [](lo_op_desc& d) { d.B = 65535; }), {WS, UN, WS}});
+  lo_op_desc ks = ko, kk = ko, kg = ko, kt = ko;
+  ks.kind = LO_OP_KERNEL_SUM_DIAG; ks.nterms = 3; ks.n2 = 0x210;
+  kk.kind = LO_OP_KERNEL_KRON_DIAG; kk.nterms = 4; kk.task = F(0xb0000);
+  kg.kind = LO_OP_KERNEL_GRAD_DIAG; kg.n2 = LO_KERNEL_RBF;
+  kt.kind = LO_OP_KERNEL_TASK_DIAG; kt.nterms = 4; kt.task = F(0xb0000);
+  r.push_back({"kernel sum, no points", with(ks, [](lo_op_desc& d) { d.A0 = nullptr; }), {BA, UN, BA}});
+  r.push_back({"kernel sum, family 4 in term 1", with(ks, [](lo_op_desc& d) { d.n2 = 0x240; }), {BA, UN, BA}});
+  r.push_back({"kernel sum, D beyond the bound", with(ks, [](lo_op_desc& d) { d.R = LO_KERNEL_MAX_DIM + 1; }), {UN, UN, UN}});
+  r.push_back({"kernel kron, no task matrix", with(kk, [](lo_op_desc& d) { d.task = nullptr; }), {BA, UN, BA}});
+  r.push_back({"kernel kron, family 4", with(kk, [](lo_op_desc& d) { d.n2 = 4; }), {BA, UN, BA}});
+  r.push_back({"kernel kron, N % T != 0", with(kk, [](lo_op_desc& d) { d.nterms = 3; }), {BA, UN, BA}});
+  r.push_back({"kernel grad, no theta", with(kg, [](lo_op_desc& d) { d.A1 = nullptr; }), {BA, UN, BA}});
+  r.push_back({"kernel grad, Matern", with(kg, [](lo_op_desc& d) { d.n2 = LO_KERNEL_MATERN52; }), {UN, UN, UN}});
+  r.push_back({"kernel grad, N % (D + 1) != 0", with(kg, [](lo_op_desc& d) { d.R = 2; }), {BA, UN, BA}});
+  r.push_back({"kernel task, no task matrix", with(kt, [](lo_op_desc& d) { d.task = nullptr; }), {BA, UN, BA}});
+  r.push_back({"kernel task, family 4", with(kt, [](lo_op_desc& d) { d.n2 = 4; }), {BA, UN, BA}});
+  r.push_back({"kernel task, T beyond the bound",
+               with(kt, [](lo_op_desc& d) { d.nterms = LO_KERNEL_TASK_MAX_TASKS + 1; }), {UN, UN, UN}});
+  lo_op_desc ss = ski;
+  ss.kind = LO_OP_SKI_SUM_DIAG; ss.nterms = 2;
+  r.push_back({"ski sum, no interp", with(ss, [](lo_op_desc& d) { d.interp = nullptr; }), {BA, UN, BA}});
+  r.push_back({"ski sum, no terms", with(ss, [](lo_op_desc& d) { d.nterms = 0; }), {BA, UN, BA}});
+  r.push_back({"ski sum, M beyond the bound", with(ss, [](lo_op_desc& d) { d.R = LO_TOEPLITZ_MAX_M + 1; }), {UN, UN, UN}});
+  // sums: a kernel term is validated as the kind on its own is, and refused by the float64 entry
+  lo_op_desc kterm = with(ko, [](lo_op_desc& d) { d.N = 80; d.diag_mode = LO_DIAG_NONE; d.d = nullptr; });
+  lo_op_desc kbad = with(kterm, [](lo_op_desc& d) { d.n2 = 7; });
+  lo_op_desc sk_terms[2] = {terms2[0], kbad}, sk64_terms[2] = {terms2[0], kterm}, sh_terms[2] = {terms2[0], had};
+  r.push_back({"sum, kernel term of family 7", with(sum2, [&](lo_op_desc& d) { d.terms = sk_terms; }), {BA, UN, BA}});
+  r.push_back({"sum, kernel term (taken by fp32)", with(sum2, [&](lo_op_desc& d) { d.terms = sk64_terms; }), {WS, UN, WS}});
+  r.push_back({"sum, Hadamard term", with(sum2, [&](lo_op_desc& d) { d.terms = sh_terms; }), {BA, BA, BA}});
+  r.push_back({"sum, one term", with(sum2, [](lo_op_desc& d) { d.nterms = 1; }), {BA, BA, BA}});
+  r.push_back({"masked", m_dense, {UN, UN, WS}});
+  r.push_back({"callback", x_cb, {UN, UN, BA}});
+  r.push_back({"dense, N beyond 32 bits", with(base_dense, [](lo_op_desc& d) { d.N = 0x7ffffff1; }), {UN, UN, WS}});
+  bad += walk_refused(r);
   printf(bad ? "FAILED: %d\n" : "ok\n", bad);
   return bad ? 1 : 0;
 }
