@@ -5,11 +5,13 @@ import pytest
 import torch
 
 import cases
+import lanczos_cases as lc
 from conftest import load_golden, max_rel_err_cols
 
 pytestmark = pytest.mark.gpu
 
 from linear_operator_amd import kernels as K  # noqa: E402
+from linear_operator_amd.operators import AddedDiagLinearOperator  # noqa: E402
 from oracle import lo_oracle as orc  # noqa: E402  (the checker)
 from oracle import lo_oracle_c as occ  # noqa: E402  (the checker, C restatement)
 
@@ -61,24 +63,6 @@ def test_lanczos_at_1e4_on_the_block_where_the_reference_agrees_with_itself(case
     assert eh[..., :kq].max() <= 1e-4, eh[..., :kq].max()
 
 
-import numpy as np
-import pytest
-import torch
-
-import cases
-from conftest import load_golden, max_rel_err_cols, tridiag_block_err
-
-pytestmark = pytest.mark.gpu
-
-from linear_operator_amd import kernels as K  # noqa: E402
-from linear_operator_amd import settings  # noqa: E402
-from linear_operator_amd.operators import (  # noqa: E402
-    AddedDiagLinearOperator, ConstantDiagLinearOperator, DenseLinearOperator, DiagLinearOperator,
-    KroneckerProductLinearOperator, LowRankRootLinearOperator,
-)
-from oracle import lo_oracle as orc  # noqa: E402  (the checker)
-
-
 class ProbedAddedDiag(AddedDiagLinearOperator):
     _probes = None
 
@@ -99,6 +83,14 @@ def test_lanczos_basis_view_and_native_root_epilogue(B, N, P, k):
     q_cont, t_cont = K.lanczos_tridiag(desc, V, k, contiguous=True)
     assert q_view.shape == q_cont.shape and not q_view.is_contiguous() and q_cont.is_contiguous()
     assert torch.equal(q_view, q_cont) and torch.equal(t_view, t_cont)
+    # the values: the invariants of the recurrence under 8 x what the oracle's float32 run of the same inputs shows
+    # (tests/lanczos_cases.py); k = 32, P = 8 is the float4 plain route above 24 stored vectors at a realistic N
+    Vn = host(V)
+    qo, to = orc.lanczos_tridiag(lambda x: orc.matvec_lowrank_diag(C, d, x), k, Vn)
+    apply, normA = lc.lowrank_apply64(C, d)
+    ref = lc.check_lanczos(qo, to, apply, Vn, normA)
+    vals, bnd = lc.check_lanczos(host(q_view), host(t_view), apply, Vn, normA), lc.bounds_from(ref, "f32")
+    assert tuple(t_view.shape) == to.shape and not lc.violations(vals, bnd), lc.tag(f"B={B} N={N} P={P} k={k}", vals, ref, bnd)
     if P == 1:
         q_view, q_cont, t_view = q_view.unsqueeze(0), q_cont.unsqueeze(0), t_view.unsqueeze(0)
     assert (K._native_lanczos_layout(q_view) is not None) and K._native_lanczos_layout(q_cont) is None

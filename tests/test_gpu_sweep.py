@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import cases
+import lanczos_cases as lc
 from conftest import max_rel_err_cols
 from oracle import lo_oracle as orc
 
@@ -159,6 +160,11 @@ def test_sweep_preconditioner_and_lanczos_against_oracle():
         qh = host(q).astype(np.float64)
         gram = np.swapaxes(qh, -1, -2) @ qh
         assert np.abs(gram - np.eye(gram.shape[-1])).max() < 1e-4, tag
+        # ... with every entry of T, under 8 x what the oracle's own float32 run shows (tests/lanczos_cases.py)
+        apply, normA = lc.lowrank_apply64(C, d)
+        ref = lc.check_lanczos(qo, to, apply, V, normA)
+        vals, bnd = lc.check_lanczos(host(q), host(t), apply, V, normA), lc.bounds_from(ref, "f32")
+        assert not lc.violations(vals, bnd), lc.tag(tag, vals, ref, bnd)
 
 
 @pytest.mark.parametrize("N", [1024, 1100, 2048, 2049, 4096])
