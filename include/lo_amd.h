@@ -102,6 +102,11 @@ extern "C" {
 #define LO_KERNEL_TASK_MAX_TASKS 8 /* tasks T (Bt is T x T) the kind and lo_kernel_task_* take (more: LO_ERR_UNSUPPORTED)   */
 #define LO_OP_SKI_SUM_DIAG 16   /* AddedDiag(SumBatch(Interpolated(Toeplitz(t_p), W_l,p, W_r,p)), Diag(d)):
                                  *   y = sum_{p < P} W_l,p T_p W_r,p^T v + d o v,  P 1-D grids of M points over the same N rows */
+#define LO_OP_KERNEL_LMC_DIAG 17 /* AddedDiag(Kron(Kernel_0(X, X), B_0) + .. + Kron(Kernel_{Q-1}(X, X), B_{Q-1}), Diag(d)), the linear
+                                  * model of coregionalisation over ONE point tensor, index i T + t (data index slowest):
+                                  *   y[(i,t)] = sum_q theta_q[D] sum_j g_{f_q}(r_q,ij) sum_s B_q[t,s] v[(j,s)] + d o v,
+                                  *   r_q,ij^2 = sum_k (theta_q[k] (x_i[k] - x_j[k]))^2; no K_q and no product is ever stored;
+                                  * Q in 1 .. LO_KERNEL_MAX_TERMS, T in 1 .. LO_KERNEL_KRON_MAX_TASKS, D <= LO_KERNEL_MAX_DIM */
 #define LO_SKI_SUM_MAX_TERMS 64 /* terms P one LO_OP_SKI_SUM_DIAG descriptor / lo_interp_sum_f32 call takes (more: LO_ERR_UNSUPPORTED) */
 
 struct lo_interp_desc;
@@ -129,7 +134,7 @@ typedef struct lo_op_desc {
     const struct lo_mask_desc* mask;     /* MASKED (ABI 21): HOST pointer to the base descriptor and the index list */
     const struct lo_grid_desc* grid;     /* TOEPLITZ_KRON (ABI 24): HOST pointer to the grid shape                  */
     const float* task;                   /* KERNEL_KRON (ABI 29), KERNEL_TASK (ABI 34): DEVICE pointer to Bt [B, T, T], used
-                                          * exactly as given                                                           */
+                                          * exactly as given; KERNEL_LMC (ABI 38): Bt [B, Q, T, T]                     */
   };
   /* ABI 16 kinds.  TOEPLITZ: A0 = first column t [B, M] of the symmetric Toeplitz matrix, R = M = N.
    * SKI: A0 = t [B, M], R = M (grid size), n2 = J (interpolation points per row), `interp` as below.
@@ -210,7 +215,20 @@ typedef struct lo_op_desc {
    * LO_OP_SUM, not a base kind of LO_OP_MASKED or of lo_block_mv_f32.
    * LO_ERR_BADARG: a null A0 / interp / array in it, P < 1, J < 1, M < 1; LO_ERR_UNSUPPORTED: P > LO_SKI_SUM_MAX_TERMS,
    * M > LO_TOEPLITZ_MAX_M, B P > 65535, N J or M beyond the 32-bit limits of the interpolation kernels;
-   * LO_ERR_WORKSPACE: a short workspace.  All before any launch.                                                          */
+   * LO_ERR_WORKSPACE: a short workspace.  All before any launch.
+   * ABI 38 kind.  KERNEL_LMC, the linear model of coregionalisation: A0 = X [B, n, D], R = D <= LO_KERNEL_MAX_DIM,
+   * A1 = theta [B, Q, D + 1] exactly as for KERNEL_SUM (per term the D inverse lengthscales, then outputscale^2),
+   * nterms = T in 1 .. LO_KERNEL_KRON_MAX_TASKS, N = n T, `task` = Bt [B, Q, T, T] on the DEVICE, every B_q used as
+   * given, symmetric or not; n2 = the Q family codes, four bits per term, term 0 lowest as for KERNEL_SUM, and Q itself,
+   * 1 .. LO_KERNEL_MAX_TERMS, in bits 16 .. 19 (same layout again, no new member).  Lowered for lo_matvec_f32, the
+   * streaming CG, Lanczos, fp32 MINRES and the fp32 pivoted Cholesky (diagonal sum_q theta_q[D] B_q[t,t], row (p, tau):
+   * row[j T + s] = sum_q (theta_q[D] g_q(r_q,pj)) B_q[tau, s], both in term order); the fp64 entry points, the resident /
+   * fused engines and the solve sessions return LO_ERR_UNSUPPORTED; not a term kind of LO_OP_SUM, not a base kind of
+   * LO_OP_MASKED.
+   * LO_ERR_BADARG: a null A0 / A1 / task, R < 1, Q < 1, T < 1, N % T != 0, a family nibble outside 0 .. 3 (or set beyond
+   * the Q terms), set bits of n2 above bit 19; LO_ERR_UNSUPPORTED: Q > LO_KERNEL_MAX_TERMS, T >
+   * LO_KERNEL_KRON_MAX_TASKS, D > LO_KERNEL_MAX_DIM, sizes beyond the 32-bit limits of the sweep (B > 65535, n or n T >
+   * 0x7ffffe00, T c > 0x7fffffff); LO_ERR_WORKSPACE: a short workspace.  All before any launch.                        */
 } lo_op_desc;
 
 /* The grid shape of an LO_OP_TOEPLITZ_KRON_DIAG descriptor (host struct). */
@@ -1090,6 +1108,24 @@ size_t lo_kernel_kron_mv_workspace_bytes(int64_t B, int64_t n, int64_t D, int64_
 int lo_kernel_kron_mv_f32(const float* x, const float* theta, const float* task, int32_t family, int64_t B, int64_t n,
                           int64_t D, int64_t T, const float* v, int64_t c, const float* d, int32_t diag_mode, float* y,
                           void* ws, size_t ws_bytes, void* stream);
+
+/* ---- matrix-free LMC operator sum_q Kernel_q(X, X) (x) B_q (ABI 38; csrc/lo_kernel_lmc.hip) ----------------------------
+ * y [B, n T, c] = (sum_{q < Q} K_q(X, X) (x) B_q) v (+ d o v), row and column index i T + t:
+ *   y[(i,t), col] = sum_q theta_q[D] sum_j g_{f_q}(r_q,ij) sum_s B_q[t,s] v[(j,s), col] + d[(i,t)] v[(i,t), col]
+ * x [B, n, D], theta [B, Q, D + 1] as for lo_kernel_sum_mv_f32, task = Bt [B, Q, T, T] (not required symmetric),
+ * `families` = the Q codes LO_KERNEL_* packed four bits per term, term 0 lowest (the low 16 bits of the kind's n2),
+ * v [B, n T, c], d per diag_mode over the n T rows.  One pass over the pairs forms all Q kernel values; every B_q v is
+ * formed while the tile of v is staged; a sweep carries up to 16 of the T c "wide" columns (8 for Q > 2).  Launch shape,
+ * splits of the points j and the order of the sums as in lo_kernel_kron_mv_f32: fixed-order sums, no atomics, two calls
+ * give equal bits.  The sizer: 256 bytes, plus js copies of [B, n T, c] floats when the points are split; 0 for what the
+ * entry point refuses.
+ * LO_ERR_BADARG: a null pointer, a non-positive size, Q < 1, T < 1, a family code outside 0 .. 3 or set beyond the Q
+ * terms, an unknown diag_mode or one without d; LO_ERR_UNSUPPORTED: Q > LO_KERNEL_MAX_TERMS, T >
+ * LO_KERNEL_KRON_MAX_TASKS, D > LO_KERNEL_MAX_DIM, sizes beyond the 32-bit limits; LO_ERR_WORKSPACE before any launch.  */
+size_t lo_kernel_lmc_mv_workspace_bytes(int64_t B, int64_t n, int64_t D, int64_t Q, int64_t T, int64_t c);
+int lo_kernel_lmc_mv_f32(const float* x, const float* theta, const float* task, int32_t families, int64_t B, int64_t n,
+                         int64_t D, int64_t Q, int64_t T, const float* v, int64_t c, const float* d, int32_t diag_mode,
+                         float* y, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- matrix-free derivative GP: the RBF gradient kernel (ABI 30; csrc/lo_kernel_grad.hip) ------------------------------
  * y [B, M (D + 1), c] = K(x1, x2) v (+ d o v) for the block matrix of LO_OP_KERNEL_GRAD_DIAG, rows i (D + 1) + a over

@@ -41,10 +41,11 @@ LO_OP_KERNEL_GRAD_DIAG = 14
 LO_KERNEL_GRAD_MAX_DIM = 16
 LO_OP_KERNEL_TASK_DIAG = 15
 LO_KERNEL_TASK_MAX_TASKS = 8
+LO_OP_KERNEL_LMC_DIAG = 17
 LO_DIAG_NONE, LO_DIAG_FULL, LO_DIAG_CONST = 0, 1, 2
 LO_BLOCK_DIAG, LO_BLOCK_INTERLEAVED, LO_BLOCK_SUM = 0, 1, 2
 LO_EIGH_MAX_N = 1024
-ABI_VERSION = 37
+ABI_VERSION = 38
 
 LO_ERR_UNSUPPORTED = -4
 LO_FUSED_OK, LO_FUSED_EARLY_STOP, LO_FUSED_CONTINUE, LO_FUSED_TIMEOUT = 0, 1, 2, 3
@@ -303,6 +304,8 @@ _PROTOTYPES = {
     "lo_kernel_sum_points_grad_f32": (ci, [vp, vp, vp, P(i32), i64, i64, i64, i64, i64, vp, vp, i64, vp, vp, sz, vp]),
     "lo_kernel_kron_mv_workspace_bytes": (sz, [i64, i64, i64, i64, i64]),
     "lo_kernel_kron_mv_f32": (ci, [vp, vp, vp, i32, i64, i64, i64, i64, vp, i64, vp, i32, vp, vp, sz, vp]),
+    "lo_kernel_lmc_mv_workspace_bytes": (sz, [i64, i64, i64, i64, i64, i64]),
+    "lo_kernel_lmc_mv_f32": (ci, [vp, vp, vp, i32, i64, i64, i64, i64, i64, vp, i64, vp, i32, vp, vp, sz, vp]),
     "lo_kernel_grad_mv_workspace_bytes": (sz, [i64, i64, i64, i64, i64]),
     "lo_kernel_grad_mv_f32": (ci, [vp, vp, vp, i32, i64, i64, i64, i64, vp, i64, vp, i32, vp, vp, sz, vp]),
     "lo_kernel_grad_bilinear_workspace_bytes": (sz, [i64, i64, i64, i64, i64]),

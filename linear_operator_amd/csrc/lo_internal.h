@@ -281,6 +281,11 @@ int kernel_kron_plan(MatvecPlan* pl, Arena* ar, hipStream_t st);
 int kernel_kron_matvec_run(const MatvecPlan* pl, const float* v, float* y, const int* stop, hipStream_t st);
 int kernel_kron_desc_check(const lo_op_desc* op);
 
+// ---- matrix-free LMC operator sum_q Kernel_q(X, X) (x) B_q (lo_kernel_lmc.hip): LO_OP_KERNEL_LMC_DIAG, on KernelKronPlan
+int kernel_lmc_plan(MatvecPlan* pl, Arena* ar, hipStream_t st);
+int kernel_lmc_matvec_run(const MatvecPlan* pl, const float* v, float* y, const int* stop, hipStream_t st);
+int kernel_lmc_desc_check(const lo_op_desc* op);
+
 // ---- matrix-free RBF gradient kernel, D + 1 outputs per input (lo_kernel_grad.hip): LO_OP_KERNEL_GRAD_DIAG -------------
 struct KernelGradPlan {
   float* part;  // [js, B, n, (D + 1) c] partial products when the points j of a member are split over js workgroups, else nullptr

@@ -21,8 +21,8 @@
 
 namespace lo {
 
-inline bool kk_tasks_ok(int64_t T) { return T >= 1 && T <= LO_KERNEL_KRON_MAX_TASKS; }
-// (the wide column chunk of a sweep, kk_col_chunk / kk_cols: lo_kernel_shape.h)
+// (the task count, the shape bounds and the wide column chunk of a sweep -- kk_tasks_ok, kk_shape_ok, kk_col_chunk /
+// kk_cols: lo_kernel_shape.h)
 
 // grid (row blocks, B, js); part == nullptr: y is written with the diagonal term, else partial products [js, B, n, T c]
 template <int FAMILY, int DP, int CCW>
@@ -109,11 +109,6 @@ __global__ __launch_bounds__(kThreads) void k_kernel_kron_mv(const float* __rest
       }
     }
   }
-}
-
-// arguments both the entry point and the descriptor are held to (B, n, D, T, c already positive)
-static bool kk_shape_ok(int64_t B, int64_t n, int64_t D, int64_t T, int64_t c) {
-  return ko_shape_ok(B, n, n, D) && n * T <= 0x7ffffe00 && T * c <= 0x7fffffff;
 }
 
 // the product on validated arguments; part: the partials [js, B, n, T c] of a split member (ko_split_layout)

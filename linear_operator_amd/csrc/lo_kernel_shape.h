@@ -1,7 +1,7 @@
 // lo_kernel_shape.h -- the host side that every kind of the matrix-free kernel family shares (lo_kernel_op.hip and its
-// float64 twin, lo_kernel_sum.hip, lo_kernel_kron.hip, lo_kernel_grad.hip, lo_kernel_task.hip): argument checks, the launch
-// shape, the padded sizes, the choice of a kernel instantiation from run-time values (ko_pick / ko_dispatch), the layout of
-// a split member's partials and their reduction.  No device code lives here.
+// float64 twin, lo_kernel_sum.hip, lo_kernel_kron.hip, lo_kernel_lmc.hip, lo_kernel_grad.hip, lo_kernel_task.hip):
+// argument checks, the launch shape, the padded sizes, the choice of a kernel instantiation from run-time values
+// (ko_pick / ko_dispatch), the layout of a split member's partials and their reduction.  No device code lives here.
 #pragma once
 #include <algorithm>
 #include <type_traits>
@@ -106,6 +106,16 @@ inline void ko_dispatch(int family, int DP, Cols cols, int CC, F&& f) {
 // Kronecker (lo_kernel_kron.hip), by the wide column count W = T c
 inline int kk_col_chunk(int64_t W) { return W <= 4 ? 4 : (W <= 16 ? 16 : 32); }
 using kk_cols = std::integer_sequence<int, 4, 16, 32>;
+// the tasks and the sizes the kinds with a task factor take (lo_kernel_kron.hip, lo_kernel_lmc.hip): what both the entry
+// point and the descriptor are held to (B, n, D, T, c already positive)
+inline bool kk_tasks_ok(int64_t T) { return T >= 1 && T <= LO_KERNEL_KRON_MAX_TASKS; }
+inline bool kk_shape_ok(int64_t B, int64_t n, int64_t D, int64_t T, int64_t c) {
+  return ko_shape_ok(B, n, n, D) && n * T <= 0x7ffffe00 && T * c <= 0x7fffffff;
+}
+// LMC (lo_kernel_lmc.hip), by the terms Q and the wide column count: Q copies of the tile of B_q v sit in LDS next to Q
+// copies of the scaled points, so three and four terms carry at most 8 wide columns per sweep (64 KB per workgroup)
+inline int kl_col_chunk(int64_t Q, int64_t W) { return W <= 4 ? 4 : ((W <= 8 || Q > 2) ? 8 : 16); }
+using kl_cols = std::integer_sequence<int, 4, 8, 16>;
 
 // float64 (lo_kernel_op_f64.hip): 1 / 4 / 8 (DP = 32: 1 / 4 -- the point alone is 64 VGPRs there)
 inline int ko64_col_chunk(int64_t c, int DP) { return c == 1 ? 1 : ((c <= 4 || DP == 32) ? 4 : 8); }

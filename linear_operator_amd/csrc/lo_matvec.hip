@@ -154,6 +154,7 @@ int matvec_plan_init(MatvecPlan* pl, const lo_op_desc* op, lo_matvec_cb cb, void
     case LO_OP_KERNEL_DIAG: rc = kernel_op_plan(pl, ar, st); break;
     case LO_OP_KERNEL_SUM_DIAG: rc = kernel_sum_plan(pl, ar, st); break;
     case LO_OP_KERNEL_KRON_DIAG: rc = kernel_kron_plan(pl, ar, st); break;
+    case LO_OP_KERNEL_LMC_DIAG: rc = kernel_lmc_plan(pl, ar, st); break;
     case LO_OP_KERNEL_GRAD_DIAG: rc = kernel_grad_plan(pl, ar, st); break;
     case LO_OP_KERNEL_TASK_DIAG: rc = kernel_task_plan(pl, ar, st); break;
     case LO_OP_MASKED: rc = masked_plan(pl, ar, st); break;
@@ -202,6 +203,8 @@ int matvec_run(const MatvecPlan* pl, const float* v, float* y, float* dot_part, 
       rc = kernel_sum_matvec_run(pl, v, y, stop, st); break;
     case LO_OP_KERNEL_KRON_DIAG:  // (K(X, X) (x) Bt) v + d o v, Bt applied while the tile of v is staged (lo_kernel_kron.hip)
       rc = kernel_kron_matvec_run(pl, v, y, stop, st); break;
+    case LO_OP_KERNEL_LMC_DIAG:  // (sum_q K_q(X, X) (x) B_q) v + d o v, every B_q v formed while the tile of v is staged (lo_kernel_lmc.hip)
+      rc = kernel_lmc_matvec_run(pl, v, y, stop, st); break;
     case LO_OP_KERNEL_GRAD_DIAG:  // the RBF gradient kernel's blocks formed pair by pair, D + 1 outputs per point (lo_kernel_grad.hip)
       rc = kernel_grad_matvec_run(pl, v, y, stop, st); break;
     case LO_OP_KERNEL_TASK_DIAG:  // K_ij = os2 g(r_ij) Bt[t_i, t_j], the task ids staged with the points (lo_kernel_task.hip)
@@ -235,7 +238,7 @@ using namespace lo;
 
 extern "C" {
 
-int lo_abi_version(void) { return 37; }
+int lo_abi_version(void) { return 38; }
 const char* lo_target_arch(void) { return "gfx950"; }
 
 size_t lo_matvec_workspace_bytes(const lo_op_desc* op, int64_t c) {

@@ -30,6 +30,8 @@
 //                  KERNEL terms on one point tensor) -- kern_r2 per term
 //   KERNEL_KRON    (os2 g(r2_pj)) Bt[tau, s] for p = (p, tau), i = (j, s); diag os2 Bt[tau, tau]
 //                  (kronecker_product_linear_operator.py:198-216 over KERNEL and the task matrix) -- kern_r2
+//   KERNEL_LMC     sum_q (os2_q g_q(r2_q,pj)) B_q[tau, s], terms ascending; diag sum_q os2_q B_q[tau, tau]
+//                  (sum_linear_operator.py:31-45 over KERNEL_KRON terms on one point tensor) -- kern_r2 per term
 //   KERNEL_TASK    (os2 g(r2_pi)) Bt[t_p, t_i], the task ids in the points' last column; diag os2 Bt[t_i, t_i]
 //                  (no operator of the reference: include/lo_amd.h, LO_OP_KERNEL_TASK_DIAG) -- kern_r2, tk_task_id
 //   KERNEL_GRAD    the (al, be) entry of the RBF value / derivative block of the points p, j; diag os2, os2 t_a^2
@@ -250,6 +252,13 @@ __device__ __forceinline__ T src_diag(const PcDevT<T>& d, const lo_op_desc& op, 
     const int D = (int)op.R, nt = op.nterms;
     const int ti = op.kind == LO_OP_KERNEL_KRON_DIAG ? i % nt : tk_task_id(op.A0[((size_t)b * d.N + i) * (D + 1) + D], nt);
     return (T)(op.A1[(size_t)b * (D + 1) + D] * op.task[((size_t)b * nt + ti) * nt + ti]);
+  } else if (op.kind == LO_OP_KERNEL_LMC_DIAG) {  // sum_q os2_q B_q[t_i, t_i], in term order (row i = (point, t_i))
+    const int D = (int)op.R, nt = op.nterms, Q = (int)((op.n2 >> 16) & 15), ti = i % nt;
+    const float* th = op.A1 + (size_t)b * Q * (D + 1);
+    const float* bt = op.task + ((size_t)b * Q * nt + ti) * nt + ti;
+    float s = th[D] * bt[0];
+    for (int q = 1; q < Q; ++q) s = s + th[(size_t)q * (D + 1) + D] * bt[(size_t)q * nt * nt];
+    return (T)s;
   } else if (op.kind == LO_OP_KERNEL_GRAD_DIAG) {  // row i = (p, a): os2 for the value, os2 t_a^2 for a derivative
     const int D = (int)op.R, a = i % (D + 1);
     const float* th = op.A1 + (size_t)b * (D + 1);
@@ -308,6 +317,19 @@ __device__ __forceinline__ T src_entry(const PcDevT<T>& d, const lo_op_desc& tm,
     const float* th = tm.A1 + (size_t)b * (D + 1);
     const float r2 = kern_r2(tm.A0 + ((size_t)b * n + pp) * D, tm.A0 + ((size_t)b * n + jj) * D, th, D);
     return (T)((th[D] * kf_g_rt((int)tm.n2, r2)) * tm.task[((size_t)b * nt + tau) * nt + ss]);
+  } else if (tm.kind == LO_OP_KERNEL_LMC_DIAG) {  // the KERNEL_KRON entry per term over the same points, in term order
+    const int D = (int)tm.R, nt = tm.nterms, Q = (int)((tm.n2 >> 16) & 15);
+    const int n = N / nt, pp = pim / nt, tau = pim - pp * nt, jj = i / nt, ss = i - jj * nt;
+    const float* xp = tm.A0 + ((size_t)b * n + pp) * D;
+    const float* xi = tm.A0 + ((size_t)b * n + jj) * D;
+    float s = 0.0f;
+    for (int q = 0; q < Q; ++q) {
+      const float* th = tm.A1 + ((size_t)b * Q + q) * (D + 1);
+      const float kq = (th[D] * kf_g_rt((int)((tm.n2 >> (4 * q)) & 15), kern_r2(xp, xi, th, D)))
+                       * tm.task[(((size_t)b * Q + q) * nt + tau) * nt + ss];
+      s = q == 0 ? kq : s + kq;
+    }
+    return (T)s;
   } else if (tm.kind == LO_OP_KERNEL_TASK_DIAG) {  // pivot p, entry j: (os2 g(r_pj)) Bt[t_p, t_j], ids in column D
     const int D = (int)tm.R, nt = tm.nterms;
     const float* th = tm.A1 + (size_t)b * (D + 1);
@@ -774,6 +796,7 @@ static int pc_check_desc(const lo_op_desc* op, bool fp32_kinds = true) {
     case LO_OP_KERNEL_DIAG: rc = kernel_desc_check(op); break;
     case LO_OP_KERNEL_SUM_DIAG: rc = kernel_sum_desc_check(op); break;
     case LO_OP_KERNEL_KRON_DIAG: rc = kernel_kron_desc_check(op); break;
+    case LO_OP_KERNEL_LMC_DIAG: rc = kernel_lmc_desc_check(op); break;
     case LO_OP_KERNEL_GRAD_DIAG: rc = kernel_grad_desc_check(op); break;
     case LO_OP_KERNEL_TASK_DIAG: rc = kernel_task_desc_check(op); break;
     case LO_OP_SKI_DIAG: rc = ski_desc_check(op); break;

@@ -32,6 +32,8 @@ class OperatorDescriptor:
     # | theta [B,T,D+1] (KernelSum: A0 = X, R = D, n2 = the packed families, kernel_terms = T)
     # | theta [B,D+1] (KernelKron: A0 = X [B,n,D], R = D, n2 = family, kernel_terms = T, task = Bt, N = n T)
     # | theta [B,D+1] (KernelTask: A0 = X [B,N,D+1] with the task id last, R = D, n2 = family, kernel_terms = T, task = Bt)
+    # | theta [B,Q,D+1] (KernelLmc: A0 = X [B,n,D], R = D, n2 = the packed families with Q in bits 16 .. 19 (kernel_lmc_terms),
+    #   kernel_terms = T, task = Bt [B,Q,T,T], N = n T)
     A1: Optional[torch.Tensor] = None
     d: Optional[torch.Tensor] = None  # [B,N] (FULL) or [B] (CONST)
     diag_mode: int = _hip.LO_DIAG_NONE
@@ -50,9 +52,11 @@ class OperatorDescriptor:
     # point that reads `float*`
     dtype: torch.dtype = torch.float32
     # LO_OP_KERNEL_SUM_DIAG: T, the struct's `nterms` (the kind has no `terms`); LO_OP_KERNEL_KRON_DIAG,
-    # LO_OP_KERNEL_TASK_DIAG: the tasks T; LO_OP_SKI_SUM_DIAG: the P summed terms (A0 [B, P, M], interp [B, P, N, J])
+    # LO_OP_KERNEL_TASK_DIAG, LO_OP_KERNEL_LMC_DIAG: the tasks T; LO_OP_SKI_SUM_DIAG: the P summed terms (A0 [B, P, M],
+    # interp [B, P, N, J])
     kernel_terms: int = 0
-    # LO_OP_KERNEL_KRON_DIAG, LO_OP_KERNEL_TASK_DIAG: Bt [B, T, T], the union slot `task` (a DEVICE pointer)
+    # LO_OP_KERNEL_KRON_DIAG, LO_OP_KERNEL_TASK_DIAG: Bt [B, T, T], LO_OP_KERNEL_LMC_DIAG: Bt [B, Q, T, T]: the union slot
+    # `task` (a DEVICE pointer)
     task: Optional[torch.Tensor] = None
 
     @property
@@ -791,6 +795,56 @@ def kernel_kron_mv(x: torch.Tensor, theta: torch.Tensor, task: torch.Tensor, fam
     return y
 
 
+def kernel_lmc_terms(desc: OperatorDescriptor) -> int:
+    """Q of an LO_OP_KERNEL_LMC_DIAG descriptor: bits 16 .. 19 of its n2 (the family codes sit below)."""
+    return (desc.n2 >> 16) & 15
+
+
+def kernel_lmc_diag_descriptor(X: torch.Tensor, theta: torch.Tensor, families, Bt: torch.Tensor,
+                               d: Optional[torch.Tensor] = None, const_diag: bool = False):
+    """AddedDiag(Kron(Kernel_0(X, X), B_0) + .. + Kron(Kernel_{Q-1}(X, X), B_{Q-1}), Diag(d)) (or the sum alone), the linear
+    model of coregionalisation over ONE point tensor with row index i T + t: y = (sum_q K_q (x) B_q) v + d o v, every K_q
+    formed on the fly in one pass (csrc/lo_kernel_lmc.hip).  X [*batch, n, D], theta [B, Q, D + 1] from kernel_sum_theta,
+    `families` the Q codes, Bt [*batch, Q, T, T].  None when D exceeds LO_KERNEL_MAX_DIM, Q LO_KERNEL_MAX_TERMS or T
+    LO_KERNEL_KRON_MAX_TASKS (the caller composes the terms)."""
+    _hip.require_hip(X, theta, Bt, d)
+    n, D = X.shape[-2:]
+    families = [int(f) for f in families]
+    Q, T = len(families), Bt.shape[-1]
+    if (D > _hip.LO_KERNEL_MAX_DIM or D < 1 or not 1 <= Q <= _hip.LO_KERNEL_MAX_TERMS
+            or not 1 <= T <= _hip.LO_KERNEL_KRON_MAX_TASKS):
+        return None
+    packed = kernel_sum_pack_families(families) | (Q << 16)
+    X3, B4 = _flat(X.detach(), 2), _flat(Bt.detach(), 3)
+    if theta.shape != (X3.shape[0], Q, D + 1) or B4.shape != (X3.shape[0], Q, T, T):
+        raise RuntimeError(f"kernel_lmc_diag_descriptor: theta {tuple(theta.shape)}, task {tuple(Bt.shape)} for X "
+                           f"{tuple(X.shape)}, {Q} terms")
+    return _with_diag(OperatorDescriptor(_hip.LO_OP_KERNEL_LMC_DIAG, X3.shape[0], n * T, A0=X3, A1=theta.contiguous(), R=D,
+                                         n2=packed, batch_shape=X.shape[:-2], kernel_terms=T, task=B4), d, const_diag)
+
+
+def kernel_lmc_mv(x: torch.Tensor, theta: torch.Tensor, task: torch.Tensor, families, v: torch.Tensor,
+                  d: Optional[torch.Tensor] = None, const_diag: bool = False) -> torch.Tensor:
+    """lo_kernel_lmc_mv_f32: y [B, n T, c] = (sum_q K_q(x, x) (x) B_q) v (+ d o v), x [B, n, D], theta [B, Q, D + 1],
+    task = Bt [B, Q, T, T] (used as given, symmetric or not), `families` the Q codes, v [B, n T, c], row index i T + t.
+    A shape the kernel does not take raises."""
+    x, theta, task, v = x.contiguous(), theta.contiguous(), task.contiguous(), v.contiguous()
+    _hip.require_hip(x, theta, task, v, d)
+    packed = kernel_sum_pack_families(families)
+    Q = len(families)
+    B, n, D = x.shape
+    T, c = task.shape[-1], v.shape[-1]
+    if theta.shape != (B, Q, D + 1) or task.shape != (B, Q, T, T) or v.shape != (B, n * T, c):
+        raise RuntimeError(f"kernel_lmc_mv: x {tuple(x.shape)}, theta {tuple(theta.shape)} for {Q} terms, task "
+                           f"{tuple(task.shape)}, right operand {tuple(v.shape)}")
+    d, mode = _kernel_diag(d, B, n * T, const_diag)
+    y = torch.empty(B, n * T, c, dtype=torch.float32, device=v.device)
+    sizer = _hip.load().lo_kernel_lmc_mv_workspace_bytes
+    _launch("lo_kernel_lmc_mv_f32", v.device, x, theta, task, packed, B, n, D, Q, T, v, c, d, mode, y,
+            ws_bytes=sizer(B, n, D, Q, T, c))
+    return y
+
+
 def kernel_grad_diag_descriptor(X: torch.Tensor, theta: torch.Tensor, family: int, d: Optional[torch.Tensor] = None,
                                 const_diag: bool = False):
     """AddedDiag(GradKernel(X, X), Diag(d)) (or the operator alone): the covariance of the values and the D partial
@@ -1183,12 +1237,31 @@ def native_matmul_candidate(op, rhs: torch.Tensor) -> bool:
 NATIVE_MATMUL_SKI_SUM: dict = {1: True, 2: True}
 
 
+# Which products of the LMC kind (LO_OP_KERNEL_LMC_DIAG) the operators' `_matmul` hands to lo_matvec_f32, by (Q, T, one
+# column / more columns): True only where tools/mb_kernel_lmc.py measured the fused product faster than the per-term
+# composition (Q calls of lo_kernel_kron_mv_f32 and the adds) beyond the run-to-run spread at BOTH measured shapes.  An
+# absent cell keeps the composition; the descriptor lowers always: CG, Lanczos, MINRES and the pivoted Cholesky run on it
+# whatever this table says.  Measured on the MI355X (fused / composition, microseconds, median of 5 rounds, the ranges
+# within 1 % of the medians but for a few rounds; 1 x 16384, D 4 and 8 x 4096, D 16):
+#   Q 2  T 2   1 column  394 / 314,  454 / 427     17 columns  1920 / 1607,  1768 / 1396
+#   Q 2  T 4   1 column  401 / 320,  457 / 431     17 columns  3552 / 2826,  3128 / 2309
+#   Q 4  T 2   1 column  787 / 643,  895 / 869     17 columns  4669 / 3218,  4874 / 2823
+#   Q 4  T 4   1 column  800 / 659,  902 / 878     17 columns  9026 / 5620,  9114 / 4663
+# The fused product wins in no cell -- the single-term sweep carries up to 32 wide columns without a term loop, and the
+# pairs' work is the same either way -- so the table is empty.  What the kind buys is the solvers: one preconditioned solve
+# at 1 x 8192 (T 4, Q 2) takes 93 ms on the kind against 197 ms through the closure.
+_NATIVE_MATMUL_KERNEL_LMC: dict = {}
+
+
 def native_matmul(desc: Optional[OperatorDescriptor], rhs: torch.Tensor) -> bool:
     """Whether `_matmul` hands the product of the lowered operator `desc` with `rhs` to `matvec`."""
     if desc is None or desc.dtype != rhs.dtype:
         return False
     if desc.kind == _hip.LO_OP_SKI_SUM_DIAG:
         return bool(NATIVE_MATMUL_SKI_SUM.get(1 if rhs.shape[-1] == 1 else 2, False))
+    if desc.kind == _hip.LO_OP_KERNEL_LMC_DIAG:
+        return bool(_NATIVE_MATMUL_KERNEL_LMC.get((kernel_lmc_terms(desc), desc.kernel_terms,
+                                                   1 if rhs.shape[-1] == 1 else 2), False))
     if desc.dtype == torch.float32:
         return True
     return bool(_NATIVE_MATMUL_F64.get((_F64_KIND_NAMES.get(desc.kind), 1 if rhs.shape[-1] == 1 else 2), False))

@@ -102,6 +102,41 @@ def _group_descriptor(group, batch_shape):
     return K.kernel_sum_diag_descriptor(X, _group_theta(group, batch_shape), _group_families(group))
 
 
+def _lmc_terms(ops, check_device: bool = True):
+    """The terms themselves when ALL of `ops` (the flattened, diagonal-free terms of a sum) are 2 .. LO_KERNEL_MAX_TERMS
+    matrix-free multitask products Kron(Kernel_q(X, X), Dense(B_q)) (`_kernel_kron_refusal`) whose kernel factors are over
+    the SAME points tensor, with one T and one batch: the linear model of coregionalisation, one pass of
+    csrc/lo_kernel_lmc.hip.  Else None.  `check_device=False` leaves the on-the-device conditions out of the gate."""
+    from .. import _hip
+    from .kernel_linear_operator import _same_tensor
+    from .kronecker_product_linear_operator import KroneckerProductLinearOperator
+
+    if not 2 <= len(ops) <= _hip.LO_KERNEL_MAX_TERMS:
+        return None
+    for op in ops:
+        if not isinstance(op, KroneckerProductLinearOperator) or op._kernel_kron_refusal(check_device) is not None:
+            return None
+    kern0, task0 = ops[0].linear_ops
+    for op in ops[1:]:
+        kern, task = op.linear_ops
+        if not (_same_tensor(kern.x1, kern0.x1) and task.shape[-1] == task0.shape[-1]
+                and op.batch_shape == ops[0].batch_shape):
+            return None
+    return list(ops)
+
+
+def _lmc_descriptor(terms, batch_shape):
+    """The diagonal-free LO_OP_KERNEL_LMC_DIAG descriptor of the terms of _lmc_terms at `batch_shape`."""
+    from .. import kernels as K
+
+    kerns = [op.linear_ops[0] for op in terms]
+    X = kerns[0].x1.detach()
+    X = X if X.shape[:-2] == batch_shape else X.expand(*batch_shape, *X.shape[-2:])
+    Bt = torch.stack([op.linear_ops[1].tensor.detach().expand(*batch_shape, *op.linear_ops[1].shape[-2:])
+                      for op in terms], -3)
+    return K.kernel_lmc_diag_descriptor(X, _group_theta(kerns, batch_shape), _group_families(kerns), Bt)
+
+
 class SumLinearOperator(LinearOperator):
     def __init__(self, *linear_ops, **kwargs):
         try:
@@ -119,7 +154,8 @@ class SumLinearOperator(LinearOperator):
         + at most one diagonal lower to an LO_OP_SUM descriptor -- matvec, CG, Lanczos, MINRES and the pivoted
         Cholesky then run on the device without per-term Python calls.  Native KernelLinearOperators over the same points
         tensor count as ONE term (_kernel_groups): LO_OP_KERNEL_SUM_DIAG, the descriptor itself when they are the whole
-        sum apart from the diagonal."""
+        sum apart from the diagonal.  2 .. LO_KERNEL_MAX_TERMS matrix-free multitask products Kron(Kernel_q, Dense(B_q)) over
+        one points tensor (_lmc_terms) that are the whole sum apart from the diagonal lower to LO_OP_KERNEL_LMC_DIAG."""
         from .. import kernels as K
         from .diag_linear_operator import DiagLinearOperator
 
@@ -131,6 +167,10 @@ class SumLinearOperator(LinearOperator):
             return None
         if len(others) == 1:
             return _attach_diag(others[0], diags[0] if diags else None, batch_shape)
+        lmc = _lmc_terms(others)
+        if lmc is not None:
+            desc = _lmc_descriptor(lmc, batch_shape)
+            return None if desc is None else _sum_with_diag(desc, diags[0] if diags else None, batch_shape)
         items = _kernel_groups(others)
         if len(items) > K._hip.LO_MAX_TERMS:
             return None
