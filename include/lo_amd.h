@@ -107,6 +107,11 @@ extern "C" {
                                   *   y[(i,t)] = sum_q theta_q[D] sum_j g_{f_q}(r_q,ij) sum_s B_q[t,s] v[(j,s)] + d o v,
                                   *   r_q,ij^2 = sum_k (theta_q[k] (x_i[k] - x_j[k]))^2; no K_q and no product is ever stored;
                                   * Q in 1 .. LO_KERNEL_MAX_TERMS, T in 1 .. LO_KERNEL_KRON_MAX_TASKS, D <= LO_KERNEL_MAX_DIM */
+#define LO_OP_KERNEL_PARAM_DIAG 18 /* AddedDiag(ParamKernel(X, X), Diag(d)): the matrix-free families with a shape parameter,
+                                    *   y = K(X, X) v + d o v, K_ij = theta[D] g(x_i, x_j) formed tile by tile, never stored   */
+#define LO_KERNEL_RQ 16       /* g = (1 + r^2 / (2 alpha))^(-alpha), r as for LO_KERNEL_RBF                                */
+#define LO_KERNEL_PERIODIC 17 /* g = exp(-2 sum_k (sin(pi (x_i[k] - x_j[k]) / p_k) / l_k)^2)                               */
+#define LO_KERNEL_PARAM_MAX_DIM 32 /* input dimensions D the kind and lo_kernel_param_* take (more: LO_ERR_UNSUPPORTED)     */
 #define LO_SKI_SUM_MAX_TERMS 64 /* terms P one LO_OP_SKI_SUM_DIAG descriptor / lo_interp_sum_f32 call takes (more: LO_ERR_UNSUPPORTED) */
 
 struct lo_interp_desc;
@@ -228,7 +233,20 @@ typedef struct lo_op_desc {
    * LO_ERR_BADARG: a null A0 / A1 / task, R < 1, Q < 1, T < 1, N % T != 0, a family nibble outside 0 .. 3 (or set beyond
    * the Q terms), set bits of n2 above bit 19; LO_ERR_UNSUPPORTED: Q > LO_KERNEL_MAX_TERMS, T >
    * LO_KERNEL_KRON_MAX_TASKS, D > LO_KERNEL_MAX_DIM, sizes beyond the 32-bit limits of the sweep (B > 65535, n or n T >
-   * 0x7ffffe00, T c > 0x7fffffff); LO_ERR_WORKSPACE: a short workspace.  All before any launch.                        */
+   * 0x7ffffe00, T c > 0x7fffffff); LO_ERR_WORKSPACE: a short workspace.  All before any launch.
+   * ABI 39 kind.  KERNEL_PARAM: A0 = X [B, N, D], R = D <= LO_KERNEL_PARAM_MAX_DIM, n2 = the family code LO_KERNEL_RQ or
+   * LO_KERNEL_PERIODIC (the codes 0 .. 3 belong to KERNEL and are refused here, as 16 and 17 are refused there),
+   * A1 = theta [B, 2 D + 2], one layout for both families (same layout of lo_op_desc again, no new member):
+   *   theta[0 .. D)            the D INVERSE lengthscales (a shared one replicated by the host)
+   *   theta[D]                 outputscale^2
+   *   theta[D + 1]             alpha (RQ; PERIODIC ignores it, the host writes 0)
+   *   theta[D + 2 .. 2 D + 2)  the D INVERSE periods (PERIODIC, a shared one replicated; RQ ignores them)
+   * Lowered for lo_matvec_f32, the streaming CG, Lanczos, fp32 MINRES and the fp32 pivoted Cholesky (constant diagonal
+   * theta[D], row of pivot p: row[j] = theta[D] g(x_p, x_j)); a term kind of LO_OP_SUM next to KERNEL (its own plan, its
+   * own row source: periodic + RBF + noise is one LO_OP_SUM); the fp64 entry points, the resident / fused engines and the
+   * solve sessions return LO_ERR_UNSUPPORTED; not a base kind of LO_OP_MASKED (nor a term of a masked sum); not grouped
+   * into KERNEL_SUM.  LO_ERR_BADARG: a null A0 / A1, R < 1, a family other than 16 / 17; LO_ERR_UNSUPPORTED: D >
+   * LO_KERNEL_PARAM_MAX_DIM, B > 65535, N > 0x7ffffe00; LO_ERR_WORKSPACE: a short workspace.  All before any launch.  */
 } lo_op_desc;
 
 /* The grid shape of an LO_OP_TOEPLITZ_KRON_DIAG descriptor (host struct). */
@@ -362,7 +380,7 @@ typedef struct lo_cg_info {
 } lo_cg_info;
 
 /* ---- library ------------------------------------------------------------------------------- */
-/* ABI version (36; bumped on any signature change) and the gfx arch string the code objects target. */
+/* ABI version (39; bumped on any signature change) and the gfx arch string the code objects target. */
 int lo_abi_version(void);
 const char* lo_target_arch(void);
 
@@ -1182,6 +1200,39 @@ size_t lo_kernel_task_points_grad_workspace_bytes(int64_t B, int64_t M, int64_t 
 int lo_kernel_task_points_grad_f32(const float* x1, const float* x2, const float* theta, const float* task, int32_t family,
                                    int64_t B, int64_t M, int64_t N, int64_t D, int64_t T, const float* U, const float* V,
                                    int64_t t, float* g_x1, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- matrix-free kernels with a shape parameter: rational quadratic and periodic (ABI 39; csrc/lo_kernel_param.hip) ----
+ * K(x1, x2)_ij = theta[D] g(x1_i, x2_j) for x1 [B, M, D], x2 [B, N, D], `family` LO_KERNEL_RQ or LO_KERNEL_PERIODIC and
+ * theta [B, 2 D + 2] as LO_OP_KERNEL_PARAM_DIAG lays it out (t = inverse lengthscales, os2, alpha, nu = inverse periods):
+ *   RQ        q = r^2 / (2 alpha), r^2 = sum_k (t_k x1_i[k] - t_k x2_j[k])^2,  g = (1 + q)^(-alpha)
+ *   PERIODIC  phi_k = nu_k x1_i[k] - nu_k x2_j[k],  g = exp(-2 sum_k (t_k sin(pi phi_k))^2)
+ * The points are scaled first and then differenced.  The sweeps are those of lo_kernel_mv_f32 / lo_kernel_bilinear_f32 /
+ * lo_kernel_points_grad_f32 (256 rows per workgroup, x2 scaled while staged in LDS tiles of 128, a tile's sums on their own
+ * and then added to the running ones, the column split of few-row shapes with an ascending reduce).  Fixed-order sums, no
+ * atomics: two calls give equal bits.  Rectangular x1 != x2 is the prediction case.
+ *   lo_kernel_param_mv_f32           y [B, M, c] = K(x1, x2) v (+ d o v when M == N), v [B, N, c], d per diag_mode; the kind
+ *                                    LO_OP_KERNEL_PARAM_DIAG with x1 = x2
+ *   lo_kernel_param_bilinear_f32     for W_ij = sum_s U[i, s] V[j, s], U [B, M, t], V [B, N, t]: g_theta [B, 2 D + 2] =
+ *                                    d / d theta of sum_ij W_ij K_ij for every entry of theta; the entries the family does
+ *                                    not read (RQ: the inverse periods; PERIODIC: alpha) are written as 0
+ *   lo_kernel_param_points_grad_f32  g_x1 [B, M, D] = d / d x1 of the same sum, x2 held fixed.  The x2 side is the same
+ *                                    call with x1 / x2 and U / V swapped
+ * LO_ERR_BADARG: a null pointer, a size < 1, a family other than 16 / 17, an unknown diag_mode, (M == N) a mode without
+ * d, (M != N) any mode but LO_DIAG_NONE; LO_ERR_UNSUPPORTED: D > LO_KERNEL_PARAM_MAX_DIM, B > 65535, M or N >
+ * 0x7ffffe00, c or t > 0x7fffffff; LO_ERR_WORKSPACE: a short workspace.  In this order, all before any launch.  The
+ * sizers return 0 for arguments the call would refuse.                                                                */
+size_t lo_kernel_param_mv_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t D, int64_t c);
+int lo_kernel_param_mv_f32(const float* x1, const float* x2, const float* theta, int32_t family, int64_t B, int64_t M,
+                           int64_t N, int64_t D, const float* v, int64_t c, const float* d, int32_t diag_mode, float* y,
+                           void* ws, size_t ws_bytes, void* stream);
+size_t lo_kernel_param_bilinear_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t D, int64_t t);
+int lo_kernel_param_bilinear_f32(const float* x1, const float* x2, const float* theta, int32_t family, int64_t B,
+                                 int64_t M, int64_t N, int64_t D, const float* U, const float* V, int64_t t,
+                                 float* g_theta, void* ws, size_t ws_bytes, void* stream);
+size_t lo_kernel_param_points_grad_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t D, int64_t t);
+int lo_kernel_param_points_grad_f32(const float* x1, const float* x2, const float* theta, int32_t family, int64_t B,
+                                    int64_t M, int64_t N, int64_t D, const float* U, const float* V, int64_t t,
+                                    float* g_x1, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- exact small-N path: batched Cholesky and triangular solves (ABI 18; csrc/lo_chol.hip) -------------------------
  * fp32, contiguous row-major, N <= 1024 (larger: LO_ERR_UNSUPPORTED), stream-ordered; fixed-order sums, no atomics: a

@@ -26,6 +26,15 @@ convention `f(x1, x2, lengthscale, outputscale)` (the `covar_func` of the refere
                   k(x1_i, x2_j) = outputscale^2 g(r_ij) task_covar[t_i, t_j]
               One output per input; the gradient with respect to the task column is zero, as autograd gives it.
 
+    rq        `f(x1, x2, lengthscale, outputscale, alpha)`, alpha [...] > 0, the rational quadratic kernel
+                  k = outputscale^2 (1 + r^2 / (2 alpha))^(-alpha),  r as above (alpha -> inf: rbf)
+    periodic  `f(x1, x2, lengthscale, outputscale, period_length)`, period_length [..., 1, D] or [..., 1, 1]:
+                  phi_k = x1_k / p_k - x2_k / p_k   (scaled first, then differenced)
+                  k = outputscale^2 exp(-2 sum_k (sin(pi phi_k) / l_k)^2)
+              Both: one output per input, pass num_nonbatch_dimensions={"outputscale": 0, "alpha": 0}.  They carry
+              `native_outputs = "param"` and the codes LO_KERNEL_RQ / LO_KERNEL_PERIODIC, which lie outside the codes of
+              the families above on purpose: csrc/lo_kernel_param.hip has entry points and a kind of its own.
+
 r^2 is the sum of squared direct differences of the scaled points (no |a|^2 + |b|^2 - 2 a.b, which cancels for near
 points).  Each function carries `native_family`, the LO_KERNEL_* code under which csrc/lo_kernel_op.hip evaluates the
 same formula tile by tile; on that path the [..., M, N] matrix these functions return is never formed.  rbf_grad
@@ -121,6 +130,18 @@ def matern52_task(x1: Tensor, x2: Tensor, lengthscale: Tensor, outputscale: Tens
     return matern52(x1[..., :-1], x2[..., :-1], lengthscale, outputscale) * _task_gather(x1, x2, task_covar)
 
 
+def rq(x1: Tensor, x2: Tensor, lengthscale: Tensor, outputscale: Tensor, alpha: Tensor) -> Tensor:
+    a = alpha[..., None, None]
+    q = scaled_sq_dist(x1, x2, lengthscale) / (2.0 * a)
+    return _scale(outputscale) * (1.0 + q).pow(-a)
+
+
+def periodic(x1: Tensor, x2: Tensor, lengthscale: Tensor, outputscale: Tensor, period_length: Tensor) -> Tensor:
+    phi = (x1 / period_length).unsqueeze(-2) - (x2 / period_length).unsqueeze(-3)  # [..., M, N, D]
+    s = torch.sin(math.pi * phi) / lengthscale.unsqueeze(-3)
+    return _scale(outputscale) * torch.exp(-2.0 * s.square().sum(-1))
+
+
 rbf.native_family = _hip.LO_KERNEL_RBF
 rbf_grad.native_family = _hip.LO_KERNEL_RBF
 rbf_grad.native_outputs = "grad"
@@ -132,6 +153,10 @@ for _f, _base in ((rbf_task, rbf), (matern12_task, matern12), (matern32_task, ma
     _f.native_family = _base.native_family
     _f.native_outputs = "task"
 
+rq.native_family = _hip.LO_KERNEL_RQ
+periodic.native_family = _hip.LO_KERNEL_PERIODIC
+rq.native_outputs = periodic.native_outputs = "param"
+
 FAMILIES = {"rbf": rbf, "matern12": matern12, "matern32": matern32, "matern52": matern52}
 # gradient kernels (D + 1 outputs per input): kept apart, FAMILIES holds the one-output families only
 GRAD_FAMILIES = {"rbf_grad": rbf_grad}
@@ -140,5 +165,9 @@ GRAD_FAMILIES = {"rbf_grad": rbf_grad}
 TASK_FAMILIES = {"rbf_task": rbf_task, "matern12_task": matern12_task, "matern32_task": matern32_task,
                  "matern52_task": matern52_task}
 
+# families with a shape parameter (alpha, period_length): kept apart as well, with codes outside those of FAMILIES
+PARAM_FAMILIES = {"rq": rq, "periodic": periodic}
+
 __all__ = ["rbf", "matern12", "matern32", "matern52", "rbf_grad", "rbf_task", "matern12_task", "matern32_task",
-           "matern52_task", "scaled_sq_dist", "FAMILIES", "GRAD_FAMILIES", "TASK_FAMILIES"]
+           "matern52_task", "rq", "periodic", "scaled_sq_dist", "FAMILIES", "GRAD_FAMILIES", "TASK_FAMILIES",
+           "PARAM_FAMILIES"]

@@ -302,6 +302,12 @@ int kernel_task_plan(MatvecPlan* pl, Arena* ar, hipStream_t st);
 int kernel_task_matvec_run(const MatvecPlan* pl, const float* v, float* y, const int* stop, hipStream_t st);
 int kernel_task_desc_check(const lo_op_desc* op);
 
+// ---- matrix-free kernels with a shape parameter, RQ and periodic (lo_kernel_param.hip): LO_OP_KERNEL_PARAM_DIAG, on
+// KernelOpPlan (its `part`)
+int kernel_param_plan(MatvecPlan* pl, Arena* ar, hipStream_t st);
+int kernel_param_matvec_run(const MatvecPlan* pl, const float* v, float* y, const int* stop, hipStream_t st);
+int kernel_param_desc_check(const lo_op_desc* op);
+
 // ---- masked operator (lo_masked.hip) ---------------------------------------------------------------------------------
 struct MaskedPlan {      // (the base's plan is MatvecPlan::sub[0])
   const int64_t* idx;    // [M]
@@ -378,7 +384,9 @@ inline bool plain_term_kind(int kind) {
   return kind == LO_OP_LOWRANK_DIAG || kind == LO_OP_DENSE_DIAG || kind == LO_OP_KRON_DIAG;
 }
 // the matrix-free kernel kinds: terms of a sum next to the plain ones (fp32 engines only; not under a mask)
-inline bool kernel_term_kind(int kind) { return kind == LO_OP_KERNEL_DIAG || kind == LO_OP_KERNEL_SUM_DIAG; }
+inline bool kernel_term_kind(int kind) {
+  return kind == LO_OP_KERNEL_DIAG || kind == LO_OP_KERNEL_SUM_DIAG || kind == LO_OP_KERNEL_PARAM_DIAG;
+}
 
 // ---- the Q-form Woodbury apply z = dinv o r - Q (Q^T r) as a plan (lo_skinny.hip): staged and run
 // through these two functions by the streaming CG and MINRES engines and by lo_precond_apply_f32 ----------------------

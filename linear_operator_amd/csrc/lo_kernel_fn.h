@@ -122,6 +122,74 @@ __device__ __forceinline__ float kf_grad_pair(float r2) {
   return kf_g<LO_KERNEL_RBF>(r2);
 }
 
+// ---- the families with a shape parameter (LO_OP_KERNEL_PARAM_DIAG: lo_kernel_param.hip, lo_pivchol.hip) -----------------
+// Rational quadratic, g = (1 + q)^(-alpha) with q = r^2 / (2 alpha): one v_log_f32 and one v_exp_f32, alpha and
+// inv2a = 1 / (2 alpha) uniform over the workgroup.  The clamp keeps q / (1 + q) finite when r^2 overflows.
+constexpr float kKpLn2 = 0.69314718055994530942f;
+// d g / d alpha = g (q / (1 + q) - ln(1 + q)) cancels to -q^2 / 2 for small q.  Below this q the series -q^2 / 2 + 2 q^3 / 3 -
+// 3 q^4 / 4 is used: its truncation error 4 q^5 / 5 relative to q^2 / 2 is 1.6 q^3 = 4.9e-5 at the threshold, where the
+// direct form has 2^-23 / q^2 = 1.2e-4 (1 + q rounds by 2^-24, against q^2 / 2); the two errors cross at q = 0.038.
+constexpr float kKpSeriesQ = 0.03125f;
+
+__device__ __forceinline__ float kp_rq_g(float r2, float alpha, float inv2a) {
+  const float q = fminf(r2, kKfMaxR2) * inv2a;
+  return kf_exp2(-alpha * __builtin_amdgcn_logf(1.0f + q));
+}
+
+// g, h = g'(r) / r = -g / (1 + q) (the factor kf_gh gives) and ga = d g / d alpha
+__device__ __forceinline__ void kp_rq_gha(float r2, float alpha, float inv2a, float* g, float* h, float* ga) {
+  const float q = fminf(r2, kKfMaxR2) * inv2a;
+  const float l2 = __builtin_amdgcn_logf(1.0f + q);
+  const float rc = __builtin_amdgcn_rcpf(1.0f + q);
+  const float e = kf_exp2(-alpha * l2);
+  *g = e;
+  *h = -e * rc;
+  const float series = q * q * fmaf(q, fmaf(q, -0.75f, 2.0f / 3.0f), -0.5f);
+  *ga = e * (q < kKpSeriesQ ? series : fmaf(q, rc, -l2 * kKpLn2));
+}
+
+// Periodic: sin(pi p) and sin(2 pi p) for p = |phi| >= 0 (the callers take |phi|, so that K(x, y) and K(y, x) have equal
+// bits, and put the sign back where the function is odd).  v_sin_f32 takes revolutions and a bounded domain: fract first,
+// which is exact at any magnitude.
+#ifndef LO_KP_HW_SINE
+#define LO_KP_HW_SINE 1
+#endif
+__device__ __forceinline__ float kp_sinpi(float p) {
+#if LO_KP_HW_SINE
+  return __builtin_amdgcn_sinf(__builtin_amdgcn_fractf(0.5f * p));
+#else
+  return sinpif(p);
+#endif
+}
+__device__ __forceinline__ float kp_sin2pi(float p) {
+#if LO_KP_HW_SINE
+  return __builtin_amdgcn_sinf(__builtin_amdgcn_fractf(p));
+#else
+  return sinpif(2.0f * p);
+#endif
+}
+// g = exp(-2 rho), rho = sum_k (theta_k sin(pi phi_k))^2
+__device__ __forceinline__ float kp_per_g(float rho) { return kf_exp2(rho * (-2.0f * kKfLog2e)); }
+
+// one entry with everything a run-time value (row source of the pivoted Cholesky): theta [2 D + 2] as lo_amd.h lays it
+// out; the points scaled and rounded separately, then differenced, the sums in ascending k
+__device__ __forceinline__ float kp_g_rt(int family, const float* xp, const float* xi, const float* th, int D) {
+  float acc = 0.0f;
+  if (family == LO_KERNEL_PERIODIC) {
+    const float* nu = th + D + 2;
+    for (int k = 0; k < D; ++k) {
+      const float ts = th[k] * kp_sinpi(fabsf(xp[k] * nu[k] - xi[k] * nu[k]));
+      acc = acc + ts * ts;
+    }
+    return kp_per_g(acc);
+  }
+  for (int k = 0; k < D; ++k) {
+    const float df = xp[k] * th[k] - xi[k] * th[k];
+    acc = acc + df * df;
+  }
+  return kp_rq_g(acc, th[D + 1], 0.5f / th[D + 1]);
+}
+
 // the same with the family as a run-time value (row source of the pivoted Cholesky: one entry per thread)
 __device__ __forceinline__ float kf_g_rt(int family, float r2) {
   switch (family) {

@@ -34,6 +34,8 @@
 //                  (sum_linear_operator.py:31-45 over KERNEL_KRON terms on one point tensor) -- kern_r2 per term
 //   KERNEL_TASK    (os2 g(r2_pi)) Bt[t_p, t_i], the task ids in the points' last column; diag os2 Bt[t_i, t_i]
 //                  (no operator of the reference: include/lo_amd.h, LO_OP_KERNEL_TASK_DIAG) -- kern_r2, tk_task_id
+//   KERNEL_PARAM   os2 g(x_p, x_i), g rational quadratic or periodic; diag os2 (no operator of the reference: include/lo_amd.h,
+//                  LO_OP_KERNEL_PARAM_DIAG) -- kp_g_rt (lo_kernel_fn.h)
 //   KERNEL_GRAD    the (al, be) entry of the RBF value / derivative block of the points p, j; diag os2, os2 t_a^2
 //                  (no operator of the reference: include/lo_amd.h, lo_kernel_grad_mv_f32) -- its own loop: that of
 //                  kern_r2, which also keeps the scaled differences of the coordinates al, be
@@ -242,6 +244,8 @@ __device__ __forceinline__ T src_diag(const PcDevT<T>& d, const lo_op_desc& op, 
     return A0[(size_t)b * op.R];
   } else if (op.kind == LO_OP_KERNEL_DIAG) {  // os2 g(0) = os2 (an fp32 kind: the operands are read as float)
     return (T)op.A1[(size_t)b * (op.R + 1) + op.R];
+  } else if (op.kind == LO_OP_KERNEL_PARAM_DIAG) {  // os2 g(x, x) = os2 for both families
+    return (T)op.A1[(size_t)b * (2 * op.R + 2) + op.R];
   } else if (op.kind == LO_OP_KERNEL_SUM_DIAG) {  // sum_t os2_t, in term order
     const float* th = op.A1 + (size_t)b * op.nterms * (op.R + 1);
     float s = th[op.R];
@@ -300,6 +304,10 @@ __device__ __forceinline__ T src_entry(const PcDevT<T>& d, const lo_op_desc& tm,
     const float* th = tm.A1 + (size_t)b * (D + 1);
     const float r2 = kern_r2(tm.A0 + ((size_t)b * N + pim) * D, tm.A0 + ((size_t)b * N + i) * D, th, D);
     return (T)(th[D] * kf_g_rt((int)tm.n2, r2));
+  } else if (tm.kind == LO_OP_KERNEL_PARAM_DIAG) {
+    const int D = (int)tm.R;
+    const float* th = tm.A1 + (size_t)b * (2 * D + 2);
+    return (T)(th[D] * kp_g_rt((int)tm.n2, tm.A0 + ((size_t)b * N + pim) * D, tm.A0 + ((size_t)b * N + i) * D, th, D));
   } else if (tm.kind == LO_OP_KERNEL_SUM_DIAG) {  // the same per term over the same points, summed in term order
     const int D = (int)tm.R;
     const float* xp = tm.A0 + ((size_t)b * N + pim) * D;
@@ -786,7 +794,9 @@ static int pc_check_desc(const lo_op_desc* op, bool fp32_kinds = true) {
         if (!(plain_term_kind(t.kind) || kernel_term_kind(t.kind)) || t.B != op->B || t.N != op->N) return LO_ERR_BADARG;
         if (kernel_term_kind(t.kind)) {  // (a term is validated as the kind on its own is)
           if (!fp32_kinds) return LO_ERR_UNSUPPORTED;
-          if ((rc = t.kind == LO_OP_KERNEL_DIAG ? kernel_desc_check(&t) : kernel_sum_desc_check(&t))) return rc;
+          if (t.kind == LO_OP_KERNEL_DIAG) rc = kernel_desc_check(&t);
+          else rc = t.kind == LO_OP_KERNEL_PARAM_DIAG ? kernel_param_desc_check(&t) : kernel_sum_desc_check(&t);
+          if (rc) return rc;
         }
       }
       break;
@@ -799,6 +809,7 @@ static int pc_check_desc(const lo_op_desc* op, bool fp32_kinds = true) {
     case LO_OP_KERNEL_LMC_DIAG: rc = kernel_lmc_desc_check(op); break;
     case LO_OP_KERNEL_GRAD_DIAG: rc = kernel_grad_desc_check(op); break;
     case LO_OP_KERNEL_TASK_DIAG: rc = kernel_task_desc_check(op); break;
+    case LO_OP_KERNEL_PARAM_DIAG: rc = kernel_param_desc_check(op); break;
     case LO_OP_SKI_DIAG: rc = ski_desc_check(op); break;
     case LO_OP_SKI_SUM_DIAG: rc = ski_sum_desc_check(op); break;
     // (an empty grid or stencil is refused here ahead of the grid shape; the plan refuses it behind, as a shape)

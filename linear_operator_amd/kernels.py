@@ -34,6 +34,7 @@ class OperatorDescriptor:
     # | theta [B,D+1] (KernelTask: A0 = X [B,N,D+1] with the task id last, R = D, n2 = family, kernel_terms = T, task = Bt)
     # | theta [B,Q,D+1] (KernelLmc: A0 = X [B,n,D], R = D, n2 = the packed families with Q in bits 16 .. 19 (kernel_lmc_terms),
     #   kernel_terms = T, task = Bt [B,Q,T,T], N = n T)
+    # | theta [B,2D+2] (KernelParam: A0 = X [B,N,D], R = D, n2 = LO_KERNEL_RQ / LO_KERNEL_PERIODIC; kernel_param_theta)
     A1: Optional[torch.Tensor] = None
     d: Optional[torch.Tensor] = None  # [B,N] (FULL) or [B] (CONST)
     diag_mode: int = _hip.LO_DIAG_NONE
@@ -129,7 +130,7 @@ def _check_dtype(dtype, *tensors):
 def sum_descriptor(terms, d: Optional[torch.Tensor] = None, const_diag: bool = False, dtype=torch.float32):
     """SumLinearOperator(A_1, ..., A_n) (+ one diagonal): y = sum_i A_i v + d o v (sum_linear_operator.py:47-51).
     `terms`: 2 .. LO_MAX_TERMS descriptors of kind low-rank / dense / Kronecker / matrix-free kernel (LO_OP_KERNEL_DIAG;
-    float32 sums also LO_OP_KERNEL_SUM_DIAG) WITHOUT a diagonal, same batch and N, all of the element type `dtype`."""
+    float32 sums also LO_OP_KERNEL_SUM_DIAG and LO_OP_KERNEL_PARAM_DIAG) WITHOUT a diagonal, same batch and N, all of the element type `dtype`."""
     terms = tuple(terms)
     for t in terms:
         if t.dtype != dtype:
@@ -677,6 +678,95 @@ def kernel_points_grad(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, 
     return g
 
 
+def kernel_param_theta(lengthscale: torch.Tensor, outputscale: torch.Tensor, batch, D: int,
+                       alpha: Optional[torch.Tensor] = None, period_length: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """theta [B, 2 D + 2] of the lo_kernel_param_* entry points: the D inverse lengthscales (a shared one replicated),
+    outputscale^2, alpha (rational quadratic; else 0), the D inverse periods (periodic, a shared one replicated; else 0).
+    lengthscale, period_length [*b, 1, D] or [*b, 1, 1], outputscale, alpha [*b], all broadcast to `batch`."""
+    with torch.no_grad():
+        head = kernel_theta(lengthscale, outputscale, batch, D)
+        B = head.shape[0]
+        al = (torch.zeros(B, 1, dtype=head.dtype, device=head.device) if alpha is None
+              else torch.broadcast_to(alpha.detach(), tuple(batch)).reshape(-1, 1).to(head.dtype))
+        nu = (torch.zeros(B, D, dtype=head.dtype, device=head.device) if period_length is None
+              else (1.0 / period_length.detach()).expand(*batch, 1, D).reshape(-1, D).to(head.dtype))
+        return torch.cat((head, al, nu), -1).contiguous()
+
+
+def _kernel_param_args(what, x1, x2, theta, family, right, left=None, d=None):
+    """The checked operands of an lo_kernel_param_* entry point: contiguous float32 HIP tensors x1 [B, M, D], x2 [B, N, D],
+    theta [B, 2 D + 2], the right operand [B, N, cols] and, for the derivatives, the left one [B, M, cols]."""
+    if int(family) not in (_hip.LO_KERNEL_RQ, _hip.LO_KERNEL_PERIODIC):
+        raise ValueError(f"{what}: family {family} is neither LO_KERNEL_RQ nor LO_KERNEL_PERIODIC")
+    x1, x2, theta, right = x1.contiguous(), x2.contiguous(), theta.contiguous(), right.contiguous()
+    left = None if left is None else left.contiguous()
+    _hip.require_hip(x1, x2, theta, right, left, d)
+    B, M, D = x1.shape
+    N = x2.shape[-2] if x2.dim() == 3 else -1
+    cols = right.shape[-1]
+    if (x2.shape != (B, N, D) or theta.shape != (B, 2 * D + 2) or right.shape != (B, N, cols)
+            or (left is not None and left.shape != (B, M, cols))):
+        raise RuntimeError(f"{what}: x1 {tuple(x1.shape)}, x2 {tuple(x2.shape)}, theta {tuple(theta.shape)}"
+                           + (f", left operand {tuple(left.shape)}" if left is not None else "")
+                           + f", right operand {tuple(right.shape)}")
+    return x1, x2, theta, left, right, (B, M, N, D, cols)
+
+
+def kernel_param_diag_descriptor(X: torch.Tensor, theta: torch.Tensor, family: int, d: Optional[torch.Tensor] = None,
+                                 const_diag: bool = False):
+    """AddedDiag(ParamKernel(X, X, family), Diag(d)) (or the kernel matrix alone), family LO_KERNEL_RQ or
+    LO_KERNEL_PERIODIC: y = K(X, X) v + d o v with K formed on the fly (csrc/lo_kernel_param.hip), the kind
+    LO_OP_KERNEL_PARAM_DIAG.  X [*batch, N, D], theta [B, 2 D + 2] from kernel_param_theta.  None when D exceeds
+    LO_KERNEL_PARAM_MAX_DIM or the batch the sweep's grid (the caller evaluates covar_func)."""
+    _hip.require_hip(X, theta, d)
+    N, D = X.shape[-2:]
+    X3 = _flat(X.detach(), 2)
+    if (D > _hip.LO_KERNEL_PARAM_MAX_DIM or D < 1 or X3.shape[0] > 65535
+            or int(family) not in (_hip.LO_KERNEL_RQ, _hip.LO_KERNEL_PERIODIC)):
+        return None
+    if theta.shape != (X3.shape[0], 2 * D + 2):
+        raise RuntimeError(f"kernel_param_diag_descriptor: theta of shape {tuple(theta.shape)} for X {tuple(X.shape)}")
+    return _with_diag(OperatorDescriptor(_hip.LO_OP_KERNEL_PARAM_DIAG, X3.shape[0], N, A0=X3, A1=theta.contiguous(), R=D,
+                                         n2=int(family), batch_shape=X.shape[:-2]), d, const_diag)
+
+
+def kernel_param_mv(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, family: int, v: torch.Tensor,
+                    d: Optional[torch.Tensor] = None, const_diag: bool = False) -> torch.Tensor:
+    """lo_kernel_param_mv_f32: y [B, M, c] = K(x1, x2) v (+ d o v; d only when M == N), x1 [B, M, D], x2 [B, N, D], theta
+    [B, 2 D + 2], v [B, N, c].  A shape the kernel does not take raises."""
+    x1, x2, theta, _, v, (B, M, N, D, c) = _kernel_param_args("kernel_param_mv", x1, x2, theta, family, v, d=d)
+    d, mode = _kernel_diag(d, B, N, const_diag)
+    y = torch.empty(B, M, c, dtype=torch.float32, device=v.device)
+    sizer = _hip.load().lo_kernel_param_mv_workspace_bytes
+    _launch("lo_kernel_param_mv_f32", v.device, x1, x2, theta, int(family), B, M, N, D, v, c, d, mode, y,
+            ws_bytes=sizer(B, M, N, D, c))
+    return y
+
+
+def kernel_param_bilinear(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, family: int, U: torch.Tensor,
+                          V: torch.Tensor) -> torch.Tensor:
+    """lo_kernel_param_bilinear_f32: g_theta [B, 2 D + 2], the derivative of sum_s u_s^T K(x1, x2) v_s with respect to every
+    entry of theta (0 where the family does not read the entry).  x1 [B, M, D], x2 [B, N, D], U [B, M, t], V [B, N, t]."""
+    x1, x2, theta, U, V, (B, M, N, D, t) = _kernel_param_args("kernel_param_bilinear", x1, x2, theta, family, V, U)
+    g = torch.empty(B, 2 * D + 2, dtype=torch.float32, device=U.device)
+    sizer = _hip.load().lo_kernel_param_bilinear_workspace_bytes
+    _launch("lo_kernel_param_bilinear_f32", U.device, x1, x2, theta, int(family), B, M, N, D, U, V, t, g,
+            ws_bytes=sizer(B, M, N, D, t))
+    return g
+
+
+def kernel_param_points_grad(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, family: int, U: torch.Tensor,
+                             V: torch.Tensor) -> torch.Tensor:
+    """lo_kernel_param_points_grad_f32: g_x1 [B, M, D], the derivative of sum_s u_s^T K(x1, x2) v_s with respect to x1, x2
+    held fixed.  The derivative with respect to x2 is kernel_param_points_grad(x2, x1, theta, family, V, U)."""
+    x1, x2, theta, U, V, (B, M, N, D, t) = _kernel_param_args("kernel_param_points_grad", x1, x2, theta, family, V, U)
+    g = torch.empty(B, M, D, dtype=torch.float32, device=U.device)
+    sizer = _hip.load().lo_kernel_param_points_grad_workspace_bytes
+    _launch("lo_kernel_param_points_grad_f32", U.device, x1, x2, theta, int(family), B, M, N, D, U, V, t, g,
+            ws_bytes=sizer(B, M, N, D, t))
+    return g
+
+
 def kernel_sum_theta(lengthscales, outputscales, batch, D: int) -> torch.Tensor:
     """theta [B, T, D + 1] of the fused kernel-sum entry points: per term the D inverse lengthscales (a shared one
     replicated), then outputscale^2 -- kernel_theta of every term, stacked in term order."""
@@ -963,7 +1053,8 @@ def masked_descriptor(base_desc: OperatorDescriptor, idx: torch.Tensor, d: Optio
     the C side does not take (the caller composes the product)."""
     if base_desc is None or base_desc.kind not in _MASK_BASE_KINDS or base_desc.dtype != torch.float32:
         return None  # (float64 bases: the masked kernels are fp32)
-    if any(t.kind in (_hip.LO_OP_KERNEL_DIAG, _hip.LO_OP_KERNEL_SUM_DIAG) for t in base_desc.terms):
+    if any(t.kind in (_hip.LO_OP_KERNEL_DIAG, _hip.LO_OP_KERNEL_SUM_DIAG, _hip.LO_OP_KERNEL_PARAM_DIAG)
+           for t in base_desc.terms):
         return None  # (a sum's matrix-free kernel terms are not taken under a mask)
     if idx.dtype != torch.int64 or not idx.is_cuda or idx.dim() != 1 or idx.numel() < 1:
         return None

@@ -40,6 +40,20 @@ Sum and Kronecker fusion gates never take such an operator.  Inside it:
 The operator treats task_covar as symmetric: `_transpose_nonbatch` swaps the points and keeps the parameters, as it does
 for any covar_func.  Ids outside [0, T) are the caller's error: the gate does not synchronise to look, the kernels clamp.
 
+Families with a shape parameter.  `covariance.rq` (parameters `lengthscale`, `outputscale`, `alpha` [*b]) and
+`covariance.periodic` (`lengthscale`, `outputscale`, `period_length` [*b, 1, D] or [*b, 1, 1]) carry `native_outputs ==
+"param"` and family codes outside those of the four families above; D <= LO_KERNEL_PARAM_MAX_DIM.  The gate is
+`_native_param_refusal`; `_native_refusal` keeps answering "parameters other than lengthscale and outputscale", so the Sum,
+Kronecker and LMC fusion gates never take such an operator.  Inside it:
+
+  _matmul / _t_matmul   lo_kernel_param_mv_f32 (csrc/lo_kernel_param.hip), always, rectangular included: its purpose is memory
+  _kernel_descriptor    x1 and x2 the same points: the kind LO_OP_KERNEL_PARAM_DIAG, also a term of a lowered sum
+                        (periodic + rbf + noise is one LO_OP_SUM)
+  _diagonal             outputscale^2, no launch
+  _bilinear_derivative  lengthscale, outputscale and alpha or period_length from lo_kernel_param_bilinear_f32 (d l = -theta^2
+                        d theta, d os = 2 os d os^2, d p = -nu^2 d nu, a shared l or p summed over D), the points' gradients
+                        from lo_kernel_param_points_grad_f32.  covar_func is not called, nothing of size M N is allocated
+
 Float64.  The four one-output families with every tensor float64 on the device have a gate of their own,
 `_native_f64_refusal` (the conditions of `_native_refusal` with float64 in place of float32); `_native_refusal` keeps
 answering "not float32", so the fp32 fusion gates of the Sum and Kronecker operators never see such an operator.  Inside it,
@@ -231,6 +245,46 @@ class KernelLinearOperator(LinearOperator):
     def _is_native_task(self) -> bool:
         return self._native_task_refusal() is None
 
+    def _native_param_refusal(self, check_device: bool = True) -> Optional[str]:
+        """The gate of the families with a shape parameter, rational quadratic and periodic (csrc/lo_kernel_param.hip):
+        None when the native kernels take this operator, else the reason they do not.  `check_device=False` leaves out
+        the device condition."""
+        from .. import _hip
+
+        if getattr(self.covar_func, "native_outputs", None) != "param":
+            return "covar_func has no native_outputs == 'param'"
+        family = getattr(self.covar_func, "native_family", None)
+        extra = {_hip.LO_KERNEL_RQ: "alpha", _hip.LO_KERNEL_PERIODIC: "period_length"}.get(family)
+        if extra is None:
+            return "covar_func has no native_family among LO_KERNEL_RQ, LO_KERNEL_PERIODIC"
+        if self.num_outputs_per_input != (1, 1):
+            return "more than one output per input"
+        if self.nontensor_params or set(self.tensor_params) != {"lengthscale", "outputscale", extra}:
+            return f"parameters other than lengthscale, outputscale and {extra}"
+        D = self.x1.shape[-1]
+        if D > _hip.LO_KERNEL_PARAM_MAX_DIM or D < 1 or self.x2.shape[-1] != D:
+            return f"D = {D} beyond LO_KERNEL_PARAM_MAX_DIM"
+        ls, os_, sh = (self.tensor_params[k] for k in ("lengthscale", "outputscale", extra))
+        batch = self.batch_broadcast_shape
+        if self.num_nonbatch_dimensions["lengthscale"] != 2 or ls.shape not in ((*batch, 1, D), (*batch, 1, 1)):
+            return f"lengthscale of shape {tuple(ls.shape)}"
+        if self.num_nonbatch_dimensions["outputscale"] != 0 or os_.shape != batch:
+            return f"outputscale of shape {tuple(os_.shape)}"
+        if extra == "alpha":
+            if self.num_nonbatch_dimensions["alpha"] != 0 or sh.shape != batch:
+                return f"alpha of shape {tuple(sh.shape)}"
+        elif self.num_nonbatch_dimensions["period_length"] != 2 or sh.shape not in ((*batch, 1, D), (*batch, 1, 1)):
+            return f"period_length of shape {tuple(sh.shape)}"
+        tensors = (self.x1, self.x2, ls, os_, sh)
+        if any(t.dtype != torch.float32 for t in tensors):
+            return "not float32"
+        if check_device and not all(t.is_cuda for t in tensors):
+            return "not on the device"
+        return None
+
+    def _is_native_param(self) -> bool:
+        return self._native_param_refusal() is None
+
     def _native_f64_refusal(self, check_device: bool = True) -> Optional[str]:
         """The gate of the float64 kernels (csrc/lo_kernel_op_f64.hip): None when they take this operator, else the
         reason they do not -- the conditions of `_native_refusal` with every tensor float64.  `check_device=False`
@@ -281,6 +335,14 @@ class KernelLinearOperator(LinearOperator):
                                self.x1.shape[-1] - 1)
         return theta, Bt.expand(*batch, T, T).reshape(-1, T, T)
 
+    def _param_theta(self, batch):
+        """Inside the param gate: theta [B, 2 D + 2] for `batch` (kernels.kernel_param_theta)."""
+        from .. import kernels as K
+
+        p = self.tensor_params
+        return K.kernel_param_theta(p["lengthscale"], p["outputscale"], batch, self.x1.shape[-1], alpha=p.get("alpha"),
+                                    period_length=p.get("period_length"))
+
     def _kernel_descriptor_f64(self, batch_shape=None):
         """The float64 LO_OP_KERNEL_DIAG descriptor inside the float64 gate when x1 and x2 are one tensor, else None."""
         if not (self._is_native_f64() and self._same_points()):
@@ -294,8 +356,8 @@ class KernelLinearOperator(LinearOperator):
                                         dtype=torch.float64)
 
     def _kernel_descriptor(self, batch_shape=None):
-        grad, task = self._is_native_grad(), self._is_native_task()
-        if not ((grad or task or self._is_native()) and self._same_points()):
+        grad, task, param = self._is_native_grad(), self._is_native_task(), self._is_native_param()
+        if not ((grad or task or param or self._is_native()) and self._same_points()):
             return None
         from .. import kernels as K
 
@@ -305,6 +367,8 @@ class KernelLinearOperator(LinearOperator):
         if task:
             theta, Bt = self._task_operands(bs)
             return K.kernel_task_diag_descriptor(X, theta, self.covar_func.native_family, Bt.reshape(*bs, *Bt.shape[-2:]))
+        if param:
+            return K.kernel_param_diag_descriptor(X, self._param_theta(bs), self.covar_func.native_family)
         build = K.kernel_grad_diag_descriptor if grad else K.kernel_diag_descriptor
         return build(X, self._theta(bs), self.covar_func.native_family)
 
@@ -354,6 +418,17 @@ class KernelLinearOperator(LinearOperator):
             y = K.kernel_task_mv(x1, x2, theta, Bt, self.covar_func.native_family,
                                  cols.detach().expand(*bs, N, c).reshape(-1, N, c))
             y = y.reshape(*bs, M, c)
+        elif cols.is_cuda and cols.dtype == torch.float32 and self._is_native_param():
+            from .. import kernels as K
+
+            M, D = self.x1.shape[-2:]
+            N, c = cols.shape[-2:]
+            bs = torch.broadcast_shapes(self.batch_shape, cols.shape[:-2])
+            x1 = self.x1.detach().expand(*bs, M, D).reshape(-1, M, D)
+            x2 = x1 if self._same_points() else self.x2.detach().expand(*bs, N, D).reshape(-1, N, D)
+            y = K.kernel_param_mv(x1, x2, self._param_theta(bs), self.covar_func.native_family,
+                                  cols.detach().expand(*bs, N, c).reshape(-1, N, c))
+            y = y.reshape(*bs, M, c)
         elif cols.is_cuda and ((cols.dtype == torch.float32 and self._is_native())
                                or (cols.dtype == torch.float64 and self._is_native_f64())):
             from .. import kernels as K
@@ -395,8 +470,8 @@ class KernelLinearOperator(LinearOperator):
     def _diagonal(self) -> Tensor:
         p, q = self.num_outputs_per_input
         n = self.x1.shape[-2]
-        if ((self._native_refusal(check_device=False) is None or self._native_f64_refusal(check_device=False) is None)
-                and self._same_points()):
+        if ((self._native_refusal(check_device=False) is None or self._native_f64_refusal(check_device=False) is None
+             or self._native_param_refusal(check_device=False) is None) and self._same_points()):
             # g(0) = 1 for every native family: the diagonal is outputscale^2, no kernel launch
             return self.tensor_params["outputscale"].square().unsqueeze(-1).expand(*self.batch_broadcast_shape, n)
         if self._native_task_refusal(check_device=False) is None and self._same_points():
@@ -483,6 +558,8 @@ class KernelLinearOperator(LinearOperator):
             return self._bilinear_derivative_native(left_vecs, right_vecs, names)
         if left_vecs.is_cuda and left_vecs.dtype == torch.float32 and self._is_native_task():
             return self._bilinear_derivative_task(left_vecs, right_vecs, names)
+        if left_vecs.is_cuda and left_vecs.dtype == torch.float32 and self._is_native_param():
+            return self._bilinear_derivative_param(left_vecs, right_vecs, names)
         if (left_vecs.is_cuda and left_vecs.dtype == torch.float32 and self._is_native_grad()
                 and not (self.x1.requires_grad or self.x2.requires_grad)):
             # (native gradients of the points are not built for this kind: such a call takes the general path whole)
@@ -539,6 +616,41 @@ class KernelLinearOperator(LinearOperator):
             out["x1"] = K.kernel_task_points_grad(x1, x2, theta, task, family, U, V).reshape(*bs, M, DX).sum_to_size(self.x1.shape)
         if self.x2.requires_grad:
             out["x2"] = K.kernel_task_points_grad(x2, x1, theta, task.mT, family, V, U).reshape(*bs, N, DX).sum_to_size(self.x2.shape)
+        return (out["x1"], out["x2"]) + tuple(out[n] for n in names)
+
+    def _bilinear_derivative_param(self, left_vecs: Tensor, right_vecs: Tensor, names):
+        """Inside the param gate: every gradient from the native kernels, nothing of size M N allocated."""
+        from .. import kernels as K
+
+        extra = "alpha" if "alpha" in self.tensor_params else "period_length"
+        ls, os_, sh = (self.tensor_params[k] for k in ("lengthscale", "outputscale", extra))
+        M, D = self.x1.shape[-2:]
+        N, t = self.x2.shape[-2], right_vecs.shape[-1]
+        bs = torch.broadcast_shapes(self.batch_shape, left_vecs.shape[:-2], right_vecs.shape[:-2])
+        out = {"x1": None, "x2": None, "lengthscale": None, "outputscale": None, extra: None}
+        if not any(p.requires_grad for p in (self.x1, self.x2, ls, os_, sh)):
+            return (None, None) + (None,) * len(names)
+        family = self.covar_func.native_family
+        x1 = self.x1.detach().expand(*bs, M, D).reshape(-1, M, D)
+        x2 = x1 if self._same_points() else self.x2.detach().expand(*bs, N, D).reshape(-1, N, D)
+        theta = self._param_theta(bs)
+        U = left_vecs.detach().expand(*bs, M, t).reshape(-1, M, t)
+        V = right_vecs.detach().expand(*bs, N, t).reshape(-1, N, t)
+        if ls.requires_grad or os_.requires_grad or sh.requires_grad:
+            g = K.kernel_param_bilinear(x1, x2, theta, family, U, V)  # [B, 2 D + 2], d / d theta
+            self._theta_to_params(g, theta, D, bs, out)
+            if sh.requires_grad and extra == "alpha":
+                out[extra] = g[:, D + 1].reshape(tuple(bs)).sum_to_size(sh.shape)
+            elif sh.requires_grad:  # nu_k = 1 / p_k: d / d p_k = -nu_k^2 d / d nu_k; a shared p sums over k
+                d_p = (-(theta[:, D + 2:] ** 2) * g[:, D + 2:]).reshape(*bs, 1, D)
+                if sh.shape[-1] == 1 and D > 1:
+                    d_p = d_p.sum(-1, keepdim=True)
+                out[extra] = d_p.sum_to_size(sh.shape)
+        # the x2 side is the x1 side of the transposed problem (x1 <-> x2, U <-> V)
+        if self.x1.requires_grad:
+            out["x1"] = K.kernel_param_points_grad(x1, x2, theta, family, U, V).reshape(*bs, M, D).sum_to_size(self.x1.shape)
+        if self.x2.requires_grad:
+            out["x2"] = K.kernel_param_points_grad(x2, x1, theta, family, V, U).reshape(*bs, N, D).sum_to_size(self.x2.shape)
         return (out["x1"], out["x2"]) + tuple(out[n] for n in names)
 
     def _bilinear_derivative_native(self, left_vecs: Tensor, right_vecs: Tensor, names, grad: bool = False):
