@@ -24,18 +24,9 @@
 #include "lo_internal.h"
 #include "lo_kernel_fn.h"
 #include "lo_kernel_shape.h"
+#include "lo_kernel_tile.h"
 
 namespace lo {
-
-// stage the tile [jt, jt + nj) of x2, scaled by the inverse lengthscales, as xs[j][DP] (coordinates >= D are 0)
-template <int DP>
-__device__ __forceinline__ void ko_stage_points(const float* __restrict__ x2b, const float* __restrict__ th, int D,
-                                                int jt, int nj, float* __restrict__ xs) {
-  for (int e = threadIdx.x; e < nj * DP; e += kThreads) {
-    const int j = e / DP, dd = e - j * DP;
-    xs[e] = dd < D ? x2b[(size_t)(jt + j) * D + dd] * th[dd] : 0.0f;
-  }
-}
 
 // grid (row blocks, B, js); part == nullptr: y is written with the diagonal term, else partial products [js, B, M, c].
 // tstride: floats between the thetas of two members (D + 1; T (D + 1) for one term of a [B, T, D + 1] array)

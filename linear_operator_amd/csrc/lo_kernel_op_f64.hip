@@ -18,6 +18,7 @@
 #include "lo_internal.h"
 #include "lo_kernel_fn.h"
 #include "lo_kernel_shape.h"
+#include "lo_kernel_tile.h"
 
 namespace lo {
 
@@ -35,15 +36,6 @@ constexpr int ko64_ts() {
 template <int DP>
 constexpr int ko64_waves() {
   return DP == 32 ? 1 : 2;
-}
-
-template <int DP>
-__device__ __forceinline__ void ko64_stage_points(const double* __restrict__ x2b, const double* __restrict__ th, int D,
-                                                  int jt, int nj, double* __restrict__ xs) {
-  for (int e = threadIdx.x; e < nj * DP; e += kThreads) {
-    const int j = e / DP, dd = e - j * DP;
-    xs[e] = dd < D ? x2b[(size_t)(jt + j) * D + dd] * th[dd] : 0.0;
-  }
 }
 
 // Sum over the 256 threads in a fixed order (wave butterfly, then waves 0..3); `red` >= 4 doubles of LDS
@@ -84,7 +76,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2))) v
     for (int jt = j0; jt < j1; jt += kKoTJ) {
       const int nj = min(kKoTJ, j1 - jt);
       __syncthreads();  // (the previous tile has been read)
-      ko64_stage_points<DP>(x2b, th, D, jt, nj, xs);
+      ko_stage_points<DP>(x2b, th, D, jt, nj, xs);
       for (int e = threadIdx.x; e < nj * CC; e += kThreads) {
         const int j = e / CC, cc = e - j * CC;
         vs[e] = c0 + cc < c ? vb[(size_t)(jt + j) * c + c0 + cc] : 0.0;
@@ -176,7 +168,7 @@ __global__ __launch_bounds__(kThreads, ko64_waves<DP>()) void k64_kernel_bil(
     for (int jt = j0; jt < j1; jt += kKoTJ) {
       const int nj = min(kKoTJ, j1 - jt);
       __syncthreads();
-      ko64_stage_points<DP>(x2b, th, D, jt, nj, xs);
+      ko_stage_points<DP>(x2b, th, D, jt, nj, xs);
       for (int e = threadIdx.x; e < nj * TS; e += kThreads) {
         const int j = e / TS, ss = e - j * TS;
         vs[e] = s0 + ss < t ? Vb[(size_t)(jt + j) * t + s0 + ss] : 0.0;
@@ -275,7 +267,7 @@ __global__ __launch_bounds__(kThreads, ko64_waves<DP>()) void k64_kernel_pgrad(
     for (int jt = j0; jt < j1; jt += kKoTJ) {
       const int nj = min(kKoTJ, j1 - jt);
       __syncthreads();  // (the previous tile has been read)
-      ko64_stage_points<DP>(x2b, th, D, jt, nj, xs);
+      ko_stage_points<DP>(x2b, th, D, jt, nj, xs);
       for (int e = threadIdx.x; e < nj * TS; e += kThreads) {
         const int j = e / TS, ss = e - j * TS;
         vs[e] = s0 + ss < t ? Vb[(size_t)(jt + j) * t + s0 + ss] : 0.0;

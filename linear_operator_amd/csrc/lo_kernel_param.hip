@@ -21,6 +21,7 @@
 #include "lo_internal.h"
 #include "lo_kernel_fn.h"
 #include "lo_kernel_shape.h"
+#include "lo_kernel_tile.h"
 
 namespace lo {
 
@@ -55,27 +56,6 @@ __device__ __forceinline__ void kp_load_theta(const float* __restrict__ tb, int 
   __syncthreads();
 }
 
-// stage the tile [jt, jt + nj) of x2, scaled by sc, as xs[j][DP] (coordinates >= D are 0)
-template <int DP>
-__device__ __forceinline__ void kp_stage_points(const float* __restrict__ x2b, const float* __restrict__ sc, int D, int jt,
-                                                int nj, float* __restrict__ xs) {
-  for (int e = threadIdx.x; e < nj * DP; e += kThreads) {
-    const int j = e / DP, dd = e - j * DP;
-    xs[e] = dd < D ? x2b[(size_t)(jt + j) * D + dd] * sc[dd] : 0.0f;
-  }
-}
-
-// a compensated (Kahan) running sum: the one-number-per-member entries of the derivative, N M terms of both signs
-struct KpKahan {
-  float s = 0.0f, c = 0.0f;
-  __device__ __forceinline__ void add(float w, float x) {
-    const float term = fmaf(w, x, -c);
-    const float next = s + term;
-    c = (next - s) - term;
-    s = next;
-  }
-};
-
 // grid (row blocks, B, js); part == nullptr: y is written with the diagonal term, else partial products [js, B, M, c]
 template <int FAMILY, int DP, int CC>
 __global__ __launch_bounds__(kThreads) void k_kparam_mv(const float* __restrict__ x1, const float* __restrict__ x2,
@@ -108,7 +88,7 @@ __global__ __launch_bounds__(kThreads) void k_kparam_mv(const float* __restrict_
     for (int jt = j0; jt < j1; jt += kKoTJ) {
       const int nj = min(kKoTJ, j1 - jt);
       __syncthreads();  // (the previous tile has been read)
-      kp_stage_points<DP>(x2b, sc, D, jt, nj, xs);
+      ko_stage_points<DP>(x2b, sc, D, jt, nj, xs);
       for (int e = threadIdx.x; e < nj * CC; e += kThreads) {
         const int j = e / CC, cc = e - j * CC;
         vs[e] = c0 + cc < c ? vb[(size_t)(jt + j) * c + c0 + cc] : 0.0f;
@@ -218,7 +198,7 @@ __global__ __launch_bounds__(kThreads) void k_kparam_bil(const float* __restrict
   for (int k = 0; k < DQ; ++k) pacc[k] = 0.0f;
   const float alpha = tb[D + 1];
   const float inv2a = 0.5f / alpha;
-  KpKahan gos, gal;
+  KoKahan gos, gal;
   const float* x2b = x2 + (size_t)b * N * D;
   const float* Vb = V + (size_t)b * N * t;
   const int j0 = blockIdx.z * jchunk, j1 = min(N, j0 + jchunk);
@@ -229,7 +209,7 @@ __global__ __launch_bounds__(kThreads) void k_kparam_bil(const float* __restrict
     for (int jt = j0; jt < j1; jt += kKoTJ) {
       const int nj = min(kKoTJ, j1 - jt);
       __syncthreads();
-      kp_stage_points<DP>(x2b, sc, D, jt, nj, xs);
+      ko_stage_points<DP>(x2b, sc, D, jt, nj, xs);
       for (int e = threadIdx.x; e < nj * kKoTS; e += kThreads) {
         const int j = e / kKoTS, ss = e - j * kKoTS;
         vs[e] = s0 + ss < t ? Vb[(size_t)(jt + j) * t + s0 + ss] : 0.0f;
@@ -360,7 +340,7 @@ __global__ __launch_bounds__(kThreads) void k_kparam_pgrad(const float* __restri
     for (int jt = j0; jt < j1; jt += kKoTJ) {
       const int nj = min(kKoTJ, j1 - jt);
       __syncthreads();  // (the previous tile has been read)
-      kp_stage_points<DP>(x2b, sc, D, jt, nj, xs);
+      ko_stage_points<DP>(x2b, sc, D, jt, nj, xs);
       for (int e = threadIdx.x; e < nj * kKoTS; e += kThreads) {
         const int j = e / kKoTS, ss = e - j * kKoTS;
         vs[e] = s0 + ss < t ? Vb[(size_t)(jt + j) * t + s0 + ss] : 0.0f;

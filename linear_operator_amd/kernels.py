@@ -574,34 +574,40 @@ def _kernel_dtype(what: str, *tensors):
     return dtype
 
 
-def _kernel_args(what, x1, x2, theta, right, left=None, d=None, task=None, families=None, ids=0, block=1, twin=False):
+def _kernel_args(what, x1, x2, theta, right, left=None, d=None, task=None, families=None, ids=0, block=1, twin=False,
+                 width=None):
     """The checked operands of an entry point of the matrix-free kernel family: the points x1 [B, M, D] and x2 [B, N, D]
-    (`ids` = 1: one more column, the task id), theta [B, D + 1] (with `families`, the T codes of a sum: [B, T, D + 1]),
-    `task` = Bt [B, T, T] or None, the right operand [B, N block, cols] and, for the derivatives, the left one
-    [B, M block, cols] (`block` rows per point: T of the Kronecker kind, D + 1 of the gradient kind).  They are made
-    contiguous and, like the diagonal `d`, must be HIP tensors of one element type: float32, or all float64 where the
-    kind has _f64 twins (`twin`).  Returns (x1, x2, theta, extra, left, right, (B, M, N, D, T, cols), dtype) with
-    extra = Bt, or the families as the int32 array the sum's entry points take, or None."""
+    (`ids` = 1: one more column, the task id), theta [B, `width`] (None: D + 1; with `families`, the T codes of a sum:
+    [B, T, D + 1]), `task` = Bt [B, T, T] or None, the right operand [B, N block, cols] and, for the derivatives, the
+    left one [B, M block, cols] (`block` rows per point: T of the Kronecker kind, D + 1 of the gradient kind).  They are
+    made contiguous and, like the diagonal `d`, must be HIP tensors of one element type: float32, or all float64 where
+    the kind has _f64 twins (`twin`).  Returns (x1, x2, theta, extra, left, right, (B, M, N, D, T, cols), dtype) with
+    extra = Bt, or the families as the int32 array the sum's entry points take, or None.  `families` and `task` together
+    are the LMC kind over one point tensor: Bt [B, Q, T, T], extra the packed family codes and Q in the place of T."""
     x1, x2, theta, right = x1.contiguous(), x2.contiguous(), theta.contiguous(), right.contiguous()
     if left is not None:
         left = left.contiguous()
-    extra, T = None, 0
+    extra, T, tasks = None, 0, ()
     if task is not None:
         extra = task = task.contiguous()
         T = task.shape[-1]
+        tasks = (T, T)
     dtype = _kernel_dtype(what, x1, x2, theta, right, left, task, d) if twin else torch.float32
     _hip.require_hip(x1, x2, theta, right, left, task, d, dtype=dtype)
     if families is not None:
-        kernel_sum_pack_families(families)
+        packed = kernel_sum_pack_families(families)
         T = len(families)
-        extra = (C.c_int32 * T)(*[int(f) for f in families])
+        tasks = (T, *tasks)
+        extra = (C.c_int32 * T)(*[int(f) for f in families]) if task is None else packed
     B, M, D = x1.shape
     N = x2.shape[-2] if x2.dim() == 3 else -1
     cols = right.shape[-1]
-    if (x2.shape != (B, N, D) or theta.shape != ((B, D + 1 - ids) if families is None else (B, T, D + 1))
+    if (x2.shape != (B, N, D) or theta.shape != ((B, width or D + 1 - ids) if families is None else (B, T, D + 1))
             or right.shape != (B, N * block, cols) or (left is not None and left.shape != (B, M * block, cols))
-            or (task is not None and task.shape != (B, T, T))):
-        raise RuntimeError(f"{what}: x1 {tuple(x1.shape)}, x2 {tuple(x2.shape)}, theta {tuple(theta.shape)}"
+            or (task is not None and task.shape != (B, *tasks))):
+        points = (f"x1 {tuple(x1.shape)}, x2 {tuple(x2.shape)}" if task is None or families is None
+                  else f"x {tuple(x1.shape)}")
+        raise RuntimeError(f"{what}: {points}, theta {tuple(theta.shape)}"
                            + (f" for {T} terms" if families is not None else "")
                            + (f", task {tuple(task.shape)}" if task is not None else "")
                            + (f", left operand {tuple(left.shape)}" if left is not None else "")
@@ -693,23 +699,10 @@ def kernel_param_theta(lengthscale: torch.Tensor, outputscale: torch.Tensor, bat
         return torch.cat((head, al, nu), -1).contiguous()
 
 
-def _kernel_param_args(what, x1, x2, theta, family, right, left=None, d=None):
-    """The checked operands of an lo_kernel_param_* entry point: contiguous float32 HIP tensors x1 [B, M, D], x2 [B, N, D],
-    theta [B, 2 D + 2], the right operand [B, N, cols] and, for the derivatives, the left one [B, M, cols]."""
+def _kernel_param_family(what: str, family) -> int:
     if int(family) not in (_hip.LO_KERNEL_RQ, _hip.LO_KERNEL_PERIODIC):
         raise ValueError(f"{what}: family {family} is neither LO_KERNEL_RQ nor LO_KERNEL_PERIODIC")
-    x1, x2, theta, right = x1.contiguous(), x2.contiguous(), theta.contiguous(), right.contiguous()
-    left = None if left is None else left.contiguous()
-    _hip.require_hip(x1, x2, theta, right, left, d)
-    B, M, D = x1.shape
-    N = x2.shape[-2] if x2.dim() == 3 else -1
-    cols = right.shape[-1]
-    if (x2.shape != (B, N, D) or theta.shape != (B, 2 * D + 2) or right.shape != (B, N, cols)
-            or (left is not None and left.shape != (B, M, cols))):
-        raise RuntimeError(f"{what}: x1 {tuple(x1.shape)}, x2 {tuple(x2.shape)}, theta {tuple(theta.shape)}"
-                           + (f", left operand {tuple(left.shape)}" if left is not None else "")
-                           + f", right operand {tuple(right.shape)}")
-    return x1, x2, theta, left, right, (B, M, N, D, cols)
+    return int(family)
 
 
 def kernel_param_diag_descriptor(X: torch.Tensor, theta: torch.Tensor, family: int, d: Optional[torch.Tensor] = None,
@@ -734,12 +727,13 @@ def kernel_param_mv(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, fam
                     d: Optional[torch.Tensor] = None, const_diag: bool = False) -> torch.Tensor:
     """lo_kernel_param_mv_f32: y [B, M, c] = K(x1, x2) v (+ d o v; d only when M == N), x1 [B, M, D], x2 [B, N, D], theta
     [B, 2 D + 2], v [B, N, c].  A shape the kernel does not take raises."""
-    x1, x2, theta, _, v, (B, M, N, D, c) = _kernel_param_args("kernel_param_mv", x1, x2, theta, family, v, d=d)
+    family = _kernel_param_family("kernel_param_mv", family)
+    x1, x2, theta, _, _, v, (B, M, N, D, _, c), dtype = _kernel_args("kernel_param_mv", x1, x2, theta, v, d=d,
+                                                                      width=2 * x1.shape[-1] + 2)
     d, mode = _kernel_diag(d, B, N, const_diag)
-    y = torch.empty(B, M, c, dtype=torch.float32, device=v.device)
-    sizer = _hip.load().lo_kernel_param_mv_workspace_bytes
-    _launch("lo_kernel_param_mv_f32", v.device, x1, x2, theta, int(family), B, M, N, D, v, c, d, mode, y,
-            ws_bytes=sizer(B, M, N, D, c))
+    y = torch.empty(B, M, c, dtype=dtype, device=v.device)
+    name, sizer = _kernel_entry("lo_kernel_param_mv", False)
+    _launch(name, v.device, x1, x2, theta, family, B, M, N, D, v, c, d, mode, y, ws_bytes=sizer(B, M, N, D, c))
     return y
 
 
@@ -747,11 +741,12 @@ def kernel_param_bilinear(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tenso
                           V: torch.Tensor) -> torch.Tensor:
     """lo_kernel_param_bilinear_f32: g_theta [B, 2 D + 2], the derivative of sum_s u_s^T K(x1, x2) v_s with respect to every
     entry of theta (0 where the family does not read the entry).  x1 [B, M, D], x2 [B, N, D], U [B, M, t], V [B, N, t]."""
-    x1, x2, theta, U, V, (B, M, N, D, t) = _kernel_param_args("kernel_param_bilinear", x1, x2, theta, family, V, U)
-    g = torch.empty(B, 2 * D + 2, dtype=torch.float32, device=U.device)
-    sizer = _hip.load().lo_kernel_param_bilinear_workspace_bytes
-    _launch("lo_kernel_param_bilinear_f32", U.device, x1, x2, theta, int(family), B, M, N, D, U, V, t, g,
-            ws_bytes=sizer(B, M, N, D, t))
+    family = _kernel_param_family("kernel_param_bilinear", family)
+    x1, x2, theta, _, U, V, (B, M, N, D, _, t), dtype = _kernel_args("kernel_param_bilinear", x1, x2, theta, V, U,
+                                                                      width=2 * x1.shape[-1] + 2)
+    g = torch.empty(B, 2 * D + 2, dtype=dtype, device=U.device)
+    name, sizer = _kernel_entry("lo_kernel_param_bilinear", False)
+    _launch(name, U.device, x1, x2, theta, family, B, M, N, D, U, V, t, g, ws_bytes=sizer(B, M, N, D, t))
     return g
 
 
@@ -759,11 +754,12 @@ def kernel_param_points_grad(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Te
                              V: torch.Tensor) -> torch.Tensor:
     """lo_kernel_param_points_grad_f32: g_x1 [B, M, D], the derivative of sum_s u_s^T K(x1, x2) v_s with respect to x1, x2
     held fixed.  The derivative with respect to x2 is kernel_param_points_grad(x2, x1, theta, family, V, U)."""
-    x1, x2, theta, U, V, (B, M, N, D, t) = _kernel_param_args("kernel_param_points_grad", x1, x2, theta, family, V, U)
-    g = torch.empty(B, M, D, dtype=torch.float32, device=U.device)
-    sizer = _hip.load().lo_kernel_param_points_grad_workspace_bytes
-    _launch("lo_kernel_param_points_grad_f32", U.device, x1, x2, theta, int(family), B, M, N, D, U, V, t, g,
-            ws_bytes=sizer(B, M, N, D, t))
+    family = _kernel_param_family("kernel_param_points_grad", family)
+    x1, x2, theta, _, U, V, (B, M, N, D, _, t), dtype = _kernel_args("kernel_param_points_grad", x1, x2, theta, V, U,
+                                                                      width=2 * x1.shape[-1] + 2)
+    g = torch.empty(B, M, D, dtype=dtype, device=U.device)
+    name, sizer = _kernel_entry("lo_kernel_param_points_grad", False)
+    _launch(name, U.device, x1, x2, theta, family, B, M, N, D, U, V, t, g, ws_bytes=sizer(B, M, N, D, t))
     return g
 
 
@@ -918,20 +914,14 @@ def kernel_lmc_mv(x: torch.Tensor, theta: torch.Tensor, task: torch.Tensor, fami
     """lo_kernel_lmc_mv_f32: y [B, n T, c] = (sum_q K_q(x, x) (x) B_q) v (+ d o v), x [B, n, D], theta [B, Q, D + 1],
     task = Bt [B, Q, T, T] (used as given, symmetric or not), `families` the Q codes, v [B, n T, c], row index i T + t.
     A shape the kernel does not take raises."""
-    x, theta, task, v = x.contiguous(), theta.contiguous(), task.contiguous(), v.contiguous()
-    _hip.require_hip(x, theta, task, v, d)
-    packed = kernel_sum_pack_families(families)
-    Q = len(families)
-    B, n, D = x.shape
-    T, c = task.shape[-1], v.shape[-1]
-    if theta.shape != (B, Q, D + 1) or task.shape != (B, Q, T, T) or v.shape != (B, n * T, c):
-        raise RuntimeError(f"kernel_lmc_mv: x {tuple(x.shape)}, theta {tuple(theta.shape)} for {Q} terms, task "
-                           f"{tuple(task.shape)}, right operand {tuple(v.shape)}")
+    task = task.contiguous()
+    T = task.shape[-1]
+    x, _, theta, packed, _, v, (B, n, _, D, Q, c), dtype = _kernel_args("kernel_lmc_mv", x, x, theta, v, d=d, task=task,
+                                                                         families=families, block=T)
     d, mode = _kernel_diag(d, B, n * T, const_diag)
-    y = torch.empty(B, n * T, c, dtype=torch.float32, device=v.device)
-    sizer = _hip.load().lo_kernel_lmc_mv_workspace_bytes
-    _launch("lo_kernel_lmc_mv_f32", v.device, x, theta, task, packed, B, n, D, Q, T, v, c, d, mode, y,
-            ws_bytes=sizer(B, n, D, Q, T, c))
+    y = torch.empty(B, n * T, c, dtype=dtype, device=v.device)
+    name, sizer = _kernel_entry("lo_kernel_lmc_mv", False)
+    _launch(name, v.device, x, theta, task, packed, B, n, D, Q, T, v, c, d, mode, y, ws_bytes=sizer(B, n, D, Q, T, c))
     return y
 
 

@@ -3,85 +3,106 @@ hyperparameters, N D numbers instead of N^2 (the reference's operators/kernel_li
 results).  `covar_func(x1, x2, **params)` may be any callable; it is evaluated densely whenever the matrix itself is
 needed (the general path, as in the reference, on any device and in any dtype).
 
-Native path.  When `covar_func` carries a `native_family` (linear_operator_amd.covariance: rbf, matern12, matern32,
-matern52), there is one output per input, the tensors are float32 on the device, D <= LO_KERNEL_MAX_DIM and the
-parameters are exactly `lengthscale` [*b, 1, D] or [*b, 1, 1] and `outputscale` [*b], the matrix is NEVER formed:
+Native path.  `VARIANTS` below describes every kind of operator the HIP kernels take, one row each: what `covar_func`
+must carry (linear_operator_amd.covariance), the parameters with their shapes, the limit on D and the kernels.py
+wrappers.  One gate body (`_variant_refusal`) reads a row; `_native_refusal`, `_native_f64_refusal`,
+`_native_grad_refusal`, `_native_task_refusal` and `_native_param_refusal` are its five views, and `_native_variant`
+returns the one row whose gate passes (no operator passes two).  Inside a gate the matrix is NEVER formed and
+covar_func is not called:
 
-  _matmul / _t_matmul   the on-the-fly product lo_kernel_mv_f32 (csrc/lo_kernel_op.hip), rectangular x1 / x2 included
-  _kernel_descriptor    x1 and x2 the same points: the kind LO_OP_KERNEL_DIAG, so that AddedDiag(Kernel, Diag) runs CG,
-                        Lanczos, MINRES and the pivoted Cholesky on the device with no Python call per iteration
-  _diagonal             outputscale^2, no launch;  _get_indices / _get_rows evaluate only the requested entries
-  _bilinear_derivative  lengthscale and outputscale from lo_kernel_bilinear_f32; the points' gradients, when asked for,
-                        from lo_kernel_points_grad_f32: one call per side that needs one, the x2 side as the x1 side of
-                        the transposed problem.  covar_func is not called and nothing of size M N is allocated
+  _matmul / _t_matmul   the row's product, rectangular x1 / x2 included, for a device right-hand side of the row's dtype
+  _kernel_descriptor    x1 and x2 the same points: the row's LO_OP_KERNEL_*_DIAG kind, so that AddedDiag(Kernel, Diag)
+                        runs CG, Lanczos, MINRES and the pivoted Cholesky on the device with no Python call per iteration
+  _diagonal             from the parameters alone, no launch;  _get_indices / _get_rows evaluate only the requested entries
+  _bilinear_derivative  the parameters from the row's bilinear wrapper through theta (d l = -theta^2 d theta, d os = 2 os
+                        d os^2, a shared l summed over D), the points from its points-gradient wrapper: one call per side
+                        that needs one, the x2 side as the x1 side of the transposed problem
 
-Gradient kernels.  `covariance.rbf_grad` (`native_outputs == "grad"`) with num_outputs_per_input = (D + 1, D + 1), D <=
-LO_KERNEL_GRAD_MAX_DIM and the same parameters has a gate of its own, `_native_grad_refusal`; `_native_refusal` keeps
-answering "more than one output per input", so every caller that assumes one output per input stays out.  Inside it:
+  plain   rbf, matern12/32/52, float32: csrc/lo_kernel_op.hip, LO_OP_KERNEL_DIAG; the diagonal is outputscale^2
+  f64     the same with every tensor float64: csrc/lo_kernel_op_f64.hip.  Its descriptor comes from
+          `_kernel_descriptor_f64` (AddedDiag and Sum lower through it: _attach_diag, utils.linear_cg._lower_f64);
+          `_kernel_descriptor()` stays None for float64, as it always was
+  grad    rbf_grad with num_outputs_per_input (D + 1, D + 1): csrc/lo_kernel_grad.hip, LO_OP_KERNEL_GRAD_DIAG; the
+          diagonal is outputscale^2 (1, 1 / l_1^2, .., 1 / l_D^2) per point.  No native gradients of the points: a
+          derivative call that asks for them takes the general path whole.  `_getitem` rebuilds the operator over
+          slices of whole points and indexes anything else densely
+  task    *_task, the points carry the task id in their last column, `task_covar` [*b, T, T] (treated as symmetric:
+          `_transpose_nonbatch` swaps the points and keeps the parameters): csrc/lo_kernel_task.hip,
+          LO_OP_KERNEL_TASK_DIAG; the diagonal is outputscale^2 task_covar[t_i, t_i].  Ids outside [0, T) are the
+          caller's error: the gate does not synchronise to look, the kernels clamp
+  param   rq (`alpha` [*b]) and periodic (`period_length` [*b, 1, D] or [*b, 1, 1]): csrc/lo_kernel_param.hip,
+          LO_OP_KERNEL_PARAM_DIAG, also a term of a lowered sum; d p = -nu^2 d nu; the diagonal is outputscale^2
 
-  _matmul / _t_matmul   lo_kernel_grad_mv_f32 (csrc/lo_kernel_grad.hip), always: its purpose is memory
-  _kernel_descriptor    x1 and x2 the same points: the kind LO_OP_KERNEL_GRAD_DIAG
-  _diagonal             outputscale^2 (1, 1 / l_1^2, .., 1 / l_D^2) per point, no launch, no covar_func
-  _bilinear_derivative  lo_kernel_grad_bilinear_f32 when neither points tensor asks for a gradient (else the general path)
-  _getitem              slices of whole points rebuild the operator over the sliced points; anything else indexes densely
-
-Task-indexed multitask kernels.  `covariance.rbf_task` .. `matern52_task` (`native_outputs == "task"`): the points carry
-the task id of the observation in their last column, the parameters are `lengthscale`, `outputscale` and `task_covar`
-[*b, T, T], T <= LO_KERNEL_TASK_MAX_TASKS, and K_ij = outputscale^2 g(r_ij) task_covar[t_i, t_j].  The gate is
-`_native_task_refusal`; `_native_refusal` keeps answering "parameters other than lengthscale and outputscale", so the
-Sum and Kronecker fusion gates never take such an operator.  Inside it:
-
-  _matmul / _t_matmul   lo_kernel_task_mv_f32 (csrc/lo_kernel_task.hip), always, rectangular included: its purpose is memory
-  _kernel_descriptor    x1 and x2 the same points: the kind LO_OP_KERNEL_TASK_DIAG
-  _diagonal             outputscale^2 task_covar[t_i, t_i] by a gather, no covar_func
-  _bilinear_derivative  lengthscale, outputscale and task_covar from lo_kernel_task_bilinear_f32, the points' gradients
-                        from lo_kernel_task_points_grad_f32 (the task column's gradient is 0)
-
-The operator treats task_covar as symmetric: `_transpose_nonbatch` swaps the points and keeps the parameters, as it does
-for any covar_func.  Ids outside [0, T) are the caller's error: the gate does not synchronise to look, the kernels clamp.
-
-Families with a shape parameter.  `covariance.rq` (parameters `lengthscale`, `outputscale`, `alpha` [*b]) and
-`covariance.periodic` (`lengthscale`, `outputscale`, `period_length` [*b, 1, D] or [*b, 1, 1]) carry `native_outputs ==
-"param"` and family codes outside those of the four families above; D <= LO_KERNEL_PARAM_MAX_DIM.  The gate is
-`_native_param_refusal`; `_native_refusal` keeps answering "parameters other than lengthscale and outputscale", so the Sum,
-Kronecker and LMC fusion gates never take such an operator.  Inside it:
-
-  _matmul / _t_matmul   lo_kernel_param_mv_f32 (csrc/lo_kernel_param.hip), always, rectangular included: its purpose is memory
-  _kernel_descriptor    x1 and x2 the same points: the kind LO_OP_KERNEL_PARAM_DIAG, also a term of a lowered sum
-                        (periodic + rbf + noise is one LO_OP_SUM)
-  _diagonal             outputscale^2, no launch
-  _bilinear_derivative  lengthscale, outputscale and alpha or period_length from lo_kernel_param_bilinear_f32 (d l = -theta^2
-                        d theta, d os = 2 os d os^2, d p = -nu^2 d nu, a shared l or p summed over D), the points' gradients
-                        from lo_kernel_param_points_grad_f32.  covar_func is not called, nothing of size M N is allocated
-
-Float64.  The four one-output families with every tensor float64 on the device have a gate of their own,
-`_native_f64_refusal` (the conditions of `_native_refusal` with float64 in place of float32); `_native_refusal` keeps
-answering "not float32", so the fp32 fusion gates of the Sum and Kronecker operators never see such an operator.  Inside it,
-with a float64 device right-hand side:
-
-  _matmul / _t_matmul   lo_kernel_mv_f64 (csrc/lo_kernel_op_f64.hip), always, rectangular x1 / x2 included
-  _kernel_descriptor_f64  x1 and x2 the same points: the float64 LO_OP_KERNEL_DIAG descriptor, which AddedDiag and Sum
-                        lower through (_attach_diag, utils.linear_cg._lower_f64), so that the float64 CG, MINRES and
-                        Lanczos multiply by lo_matvec_f64 with no Python call per product.  `_kernel_descriptor()` of the
-                        operator on its own stays None for float64, as it always was
-  _diagonal             outputscale^2, no launch
-  _bilinear_derivative  lo_kernel_bilinear_f64 and lo_kernel_points_grad_f64, the same theta -> lengthscale / outputscale
-                        mapping as in float32
-
-Anything outside the gates (D > 32, mixed element types, CPU, several outputs per input of another kind, other
-parameters) takes the general path, and so does a float32 right-hand side against a float64 operator or the reverse.
+`_native_refusal` answers a grad, task, param or float64 operator with "more than one output per input", "parameters
+other than lengthscale and outputscale" or "not float32", so the fp32 fusion gates of the Sum, Kronecker and LMC
+operators never take one.  Anything outside the gates (D beyond the limit, mixed element types, CPU, other parameters)
+takes the general path, and so does a right-hand side of the other float type.
 """
 from __future__ import annotations
 
 from collections import defaultdict
-from typing import Callable, Optional
+from typing import Callable, NamedTuple, Optional
 
 import torch
 from torch import Tensor
 
+from .. import _hip
+from .. import kernels as K
 from ._linear_operator import LinearOperator, to_dense
 
 _NOOP = slice(None, None, None)
+
+
+class _Extra(NamedTuple):
+    """A variant's parameter beyond lengthscale and outputscale."""
+    name: str
+    rule: str  # its shape: "scalar" [*b], "ard" [*b, 1, D] or [*b, 1, 1], "table" [*b, T, T]
+    col: int   # theta holds it in column D + col (scalar) or, as 1 / p, in the D columns from D + col on (ard); table: unused
+
+
+class _Variant(NamedTuple):
+    """One kind of operator the native kernels take.  The wrappers are names in kernels.py, looked up per call."""
+    gate: str                   # the operator's method that answers for it
+    tag: Optional[str]          # covar_func.native_outputs it answers to
+    dtype: torch.dtype          # of every tensor, the vectors included
+    families: Optional[tuple]   # the admissible covar_func.native_family codes; None: any
+    no_family: str              # the gate's answer to another one
+    extras: dict                # native_family -> _Extra (None: every family)
+    ids: int                    # id columns of the points behind the D coordinates
+    block: bool                 # D + 1 rows per point instead of 1
+    max_dim: str                # the _hip limit on the points' columns
+    theta: str
+    mv: str
+    bilinear: str
+    points_grad: Optional[str]  # None: no native gradients of the points
+    descriptor: str
+
+
+_PLAIN = _Variant("_native_refusal", None, torch.float32, None, "covar_func has no native_family", {}, 0, False, "LO_KERNEL_MAX_DIM",
+                  "kernel_theta", "kernel_mv", "kernel_bilinear", "kernel_points_grad", "kernel_diag_descriptor")
+_F64 = _PLAIN._replace(gate="_native_f64_refusal", dtype=torch.float64)
+_GRAD = _PLAIN._replace(gate="_native_grad_refusal", tag="grad", families=(_hip.LO_KERNEL_RBF,),
+                        no_family="a gradient kernel of a family other than RBF", block=True,
+                        max_dim="LO_KERNEL_GRAD_MAX_DIM", mv="kernel_grad_mv", bilinear="kernel_grad_bilinear",
+                        points_grad=None, descriptor="kernel_grad_diag_descriptor")
+_TASK = _PLAIN._replace(gate="_native_task_refusal", tag="task", extras={None: _Extra("task_covar", "table", 0)}, ids=1,
+                        mv="kernel_task_mv", bilinear="kernel_task_bilinear", points_grad="kernel_task_points_grad",
+                        descriptor="kernel_task_diag_descriptor")
+_PARAM = _PLAIN._replace(gate="_native_param_refusal", tag="param", families=(_hip.LO_KERNEL_RQ, _hip.LO_KERNEL_PERIODIC),
+                         no_family="covar_func has no native_family among LO_KERNEL_RQ, LO_KERNEL_PERIODIC",
+                         extras={_hip.LO_KERNEL_RQ: _Extra("alpha", "scalar", 1),
+                                 _hip.LO_KERNEL_PERIODIC: _Extra("period_length", "ard", 2)},
+                         max_dim="LO_KERNEL_PARAM_MAX_DIM", theta="kernel_param_theta", mv="kernel_param_mv",
+                         bilinear="kernel_param_bilinear", points_grad="kernel_param_points_grad",
+                         descriptor="kernel_param_diag_descriptor")
+VARIANTS = (_PLAIN, _F64, _GRAD, _TASK, _PARAM)
+_TAGGED = {v.tag: v for v in VARIANTS if v.tag is not None}
+
+
+def _flat(t: Tensor, bs) -> Tensor:
+    """t [*b, R, C] detached, broadcast to the batch `bs` and flattened to [B, R, C]."""
+    R, C = t.shape[-2:]
+    return t.detach().expand(*bs, R, C).reshape(-1, R, C)
 
 
 def _two():
@@ -145,232 +166,145 @@ class KernelLinearOperator(LinearOperator):
                               num_nonbatch_dimensions=self.num_nonbatch_dimensions, **tensor_params,
                               **self.nontensor_params)
 
-    # ------------------------------------------------------------------ the gate of the native path
-    def _native_refusal(self, check_device: bool = True) -> Optional[str]:
-        """None when the native kernels take this operator, else the reason they do not.  `check_device=False` leaves
-        out the float32-on-the-device condition (what the rest of the gate decides can then be asked on any machine)."""
-        from .. import _hip
+    # ------------------------------------------------------------------ the gates of the native path
+    def _extra(self, v: _Variant) -> Optional[_Extra]:
+        return v.extras.get(self.covar_func.native_family, v.extras.get(None))
 
-        if getattr(self.covar_func, "native_family", None) is None:
-            return "covar_func has no native_family"
-        if self.num_outputs_per_input != (1, 1):
+    def _variant_refusal(self, v: _Variant, check_device: bool = True) -> Optional[str]:
+        """None when the native kernels of the variant `v` take this operator, else the reason they do not.
+        `check_device=False` leaves out the device condition (what the rest of the gate decides can then be asked on any
+        machine)."""
+        if v.tag is not None and getattr(self.covar_func, "native_outputs", None) != v.tag:
+            return f"covar_func has no native_outputs == '{v.tag}'"
+        family = getattr(self.covar_func, "native_family", None)
+        if family is None or (v.families is not None and family not in v.families):
+            return v.no_family
+        DX = self.x1.shape[-1]
+        D = DX - v.ids
+        dim = None
+        if D < 1 or self.x2.shape[-1] != DX or DX > getattr(_hip, v.max_dim):
+            dim = f"D = {D} outside 1 .. {v.max_dim} - 1" if v.ids else f"D = {D} beyond {v.max_dim}"
+        if v.block:  # (the outputs per input are stated in D)
+            if dim is not None:
+                return dim
+            if self.num_outputs_per_input != (D + 1, D + 1):
+                return f"num_outputs_per_input is not ({D + 1}, {D + 1})"
+        elif self.num_outputs_per_input != (1, 1):
             return "more than one output per input"
-        if self.nontensor_params or set(self.tensor_params) != {"lengthscale", "outputscale"}:
-            return "parameters other than lengthscale and outputscale"
-        D = self.x1.shape[-1]
-        if D > _hip.LO_KERNEL_MAX_DIM or D < 1 or self.x2.shape[-1] != D:
-            return f"D = {D} beyond LO_KERNEL_MAX_DIM"
+        extra = self._extra(v)
+        names = {"lengthscale", "outputscale"} if extra is None else {"lengthscale", "outputscale", extra.name}
+        if self.nontensor_params or set(self.tensor_params) != names:
+            return "parameters other than " + ("lengthscale and outputscale" if extra is None
+                                               else f"lengthscale, outputscale and {extra.name}")
+        if dim is not None:
+            return dim
         ls, os_ = self.tensor_params["lengthscale"], self.tensor_params["outputscale"]
-        batch = self.batch_broadcast_shape
-        if self.num_nonbatch_dimensions["lengthscale"] != 2 or ls.shape not in ((*batch, 1, D), (*batch, 1, 1)):
+        batch, nonbatch = self.batch_broadcast_shape, self.num_nonbatch_dimensions
+        ard = ((*batch, 1, D), (*batch, 1, 1))
+        if nonbatch["lengthscale"] != 2 or ls.shape not in ard:
             return f"lengthscale of shape {tuple(ls.shape)}"
-        if self.num_nonbatch_dimensions["outputscale"] != 0 or os_.shape != batch:
+        if nonbatch["outputscale"] != 0 or os_.shape != batch:
             return f"outputscale of shape {tuple(os_.shape)}"
-        tensors = (self.x1, self.x2, ls, os_)
-        if any(t.dtype != torch.float32 for t in tensors):
-            return "not float32"
+        tensors = [self.x1, self.x2, ls, os_]
+        if extra is not None:
+            p = self.tensor_params[extra.name]
+            if extra.rule == "table":
+                T = p.shape[-1]
+                fits = nonbatch[extra.name] == 2 and p.shape == (*batch, T, T) and T >= 1
+            elif extra.rule == "ard":
+                fits = nonbatch[extra.name] == 2 and p.shape in ard
+            else:
+                fits = nonbatch[extra.name] == 0 and p.shape == batch
+            if not fits:
+                return f"{extra.name} of shape {tuple(p.shape)}"
+            if extra.rule == "table" and T > _hip.LO_KERNEL_TASK_MAX_TASKS:
+                return f"T = {T} beyond LO_KERNEL_TASK_MAX_TASKS"
+            tensors.append(p)
+        if any(t.dtype != v.dtype for t in tensors):
+            return "not float32" if v.dtype == torch.float32 else "not float64"
         if check_device and not all(t.is_cuda for t in tensors):
             return "not on the device"
         return None
+
+    def _native_variant(self, check_device: bool = True) -> Optional[_Variant]:
+        """The variant whose gate passes, or None.  No operator passes two gates (grad needs D + 1 outputs per input,
+        task and param a third parameter, f64 float64), so one candidate is asked, through its public gate: the row of
+        covar_func.native_outputs, and the one-output row of the points' dtype where covar_func carries no tag or its
+        row refuses."""
+        tagged = _TAGGED.get(getattr(self.covar_func, "native_outputs", None))
+        if tagged is not None and getattr(self, tagged.gate)(check_device) is None:
+            return tagged
+        plain = _F64 if self.x1.dtype == torch.float64 else _PLAIN
+        return plain if getattr(self, plain.gate)(check_device) is None else None
+
+    def _native_refusal(self, check_device: bool = True) -> Optional[str]:
+        return self._variant_refusal(_PLAIN, check_device)
+
+    def _native_f64_refusal(self, check_device: bool = True) -> Optional[str]:
+        return self._variant_refusal(_F64, check_device)
+
+    def _native_grad_refusal(self, check_device: bool = True) -> Optional[str]:
+        return self._variant_refusal(_GRAD, check_device)
+
+    def _native_task_refusal(self, check_device: bool = True) -> Optional[str]:
+        return self._variant_refusal(_TASK, check_device)
+
+    def _native_param_refusal(self, check_device: bool = True) -> Optional[str]:
+        return self._variant_refusal(_PARAM, check_device)
 
     def _is_native(self) -> bool:
         return self._native_refusal() is None
 
-    def _native_grad_refusal(self, check_device: bool = True) -> Optional[str]:
-        """The gate of the gradient kernel (D + 1 outputs per input, csrc/lo_kernel_grad.hip): None when the native
-        kernels take this operator, else the reason they do not.  `check_device=False` leaves out the device condition."""
-        from .. import _hip
-
-        if getattr(self.covar_func, "native_outputs", None) != "grad":
-            return "covar_func has no native_outputs == 'grad'"
-        if getattr(self.covar_func, "native_family", None) != _hip.LO_KERNEL_RBF:
-            return "a gradient kernel of a family other than RBF"
-        D = self.x1.shape[-1]
-        if D < 1 or self.x2.shape[-1] != D or D > _hip.LO_KERNEL_GRAD_MAX_DIM:
-            return f"D = {D} beyond LO_KERNEL_GRAD_MAX_DIM"
-        if self.num_outputs_per_input != (D + 1, D + 1):
-            return f"num_outputs_per_input is not ({D + 1}, {D + 1})"
-        if self.nontensor_params or set(self.tensor_params) != {"lengthscale", "outputscale"}:
-            return "parameters other than lengthscale and outputscale"
-        ls, os_ = self.tensor_params["lengthscale"], self.tensor_params["outputscale"]
-        batch = self.batch_broadcast_shape
-        if self.num_nonbatch_dimensions["lengthscale"] != 2 or ls.shape not in ((*batch, 1, D), (*batch, 1, 1)):
-            return f"lengthscale of shape {tuple(ls.shape)}"
-        if self.num_nonbatch_dimensions["outputscale"] != 0 or os_.shape != batch:
-            return f"outputscale of shape {tuple(os_.shape)}"
-        tensors = (self.x1, self.x2, ls, os_)
-        if any(t.dtype != torch.float32 for t in tensors):
-            return "not float32"
-        if check_device and not all(t.is_cuda for t in tensors):
-            return "not on the device"
-        return None
+    def _is_native_f64(self) -> bool:
+        return self._native_f64_refusal() is None
 
     def _is_native_grad(self) -> bool:
         return self._native_grad_refusal() is None
 
-    def _native_task_refusal(self, check_device: bool = True) -> Optional[str]:
-        """The gate of the task-indexed multitask kernels (csrc/lo_kernel_task.hip): None when the native kernels take
-        this operator, else the reason they do not.  `check_device=False` leaves out the device condition."""
-        from .. import _hip
-
-        if getattr(self.covar_func, "native_outputs", None) != "task":
-            return "covar_func has no native_outputs == 'task'"
-        if getattr(self.covar_func, "native_family", None) is None:
-            return "covar_func has no native_family"
-        if self.num_outputs_per_input != (1, 1):
-            return "more than one output per input"
-        if self.nontensor_params or set(self.tensor_params) != {"lengthscale", "outputscale", "task_covar"}:
-            return "parameters other than lengthscale, outputscale and task_covar"
-        D = self.x1.shape[-1] - 1
-        if D < 1 or self.x2.shape[-1] != D + 1 or D + 1 > _hip.LO_KERNEL_MAX_DIM:
-            return f"D = {D} outside 1 .. LO_KERNEL_MAX_DIM - 1"
-        ls, os_, Bt = (self.tensor_params[k] for k in ("lengthscale", "outputscale", "task_covar"))
-        batch = self.batch_broadcast_shape
-        if self.num_nonbatch_dimensions["lengthscale"] != 2 or ls.shape not in ((*batch, 1, D), (*batch, 1, 1)):
-            return f"lengthscale of shape {tuple(ls.shape)}"
-        if self.num_nonbatch_dimensions["outputscale"] != 0 or os_.shape != batch:
-            return f"outputscale of shape {tuple(os_.shape)}"
-        T = Bt.shape[-1]
-        if self.num_nonbatch_dimensions["task_covar"] != 2 or Bt.shape != (*batch, T, T) or T < 1:
-            return f"task_covar of shape {tuple(Bt.shape)}"
-        if T > _hip.LO_KERNEL_TASK_MAX_TASKS:
-            return f"T = {T} beyond LO_KERNEL_TASK_MAX_TASKS"
-        tensors = (self.x1, self.x2, ls, os_, Bt)
-        if any(t.dtype != torch.float32 for t in tensors):
-            return "not float32"
-        if check_device and not all(t.is_cuda for t in tensors):
-            return "not on the device"
-        return None
-
     def _is_native_task(self) -> bool:
         return self._native_task_refusal() is None
-
-    def _native_param_refusal(self, check_device: bool = True) -> Optional[str]:
-        """The gate of the families with a shape parameter, rational quadratic and periodic (csrc/lo_kernel_param.hip):
-        None when the native kernels take this operator, else the reason they do not.  `check_device=False` leaves out
-        the device condition."""
-        from .. import _hip
-
-        if getattr(self.covar_func, "native_outputs", None) != "param":
-            return "covar_func has no native_outputs == 'param'"
-        family = getattr(self.covar_func, "native_family", None)
-        extra = {_hip.LO_KERNEL_RQ: "alpha", _hip.LO_KERNEL_PERIODIC: "period_length"}.get(family)
-        if extra is None:
-            return "covar_func has no native_family among LO_KERNEL_RQ, LO_KERNEL_PERIODIC"
-        if self.num_outputs_per_input != (1, 1):
-            return "more than one output per input"
-        if self.nontensor_params or set(self.tensor_params) != {"lengthscale", "outputscale", extra}:
-            return f"parameters other than lengthscale, outputscale and {extra}"
-        D = self.x1.shape[-1]
-        if D > _hip.LO_KERNEL_PARAM_MAX_DIM or D < 1 or self.x2.shape[-1] != D:
-            return f"D = {D} beyond LO_KERNEL_PARAM_MAX_DIM"
-        ls, os_, sh = (self.tensor_params[k] for k in ("lengthscale", "outputscale", extra))
-        batch = self.batch_broadcast_shape
-        if self.num_nonbatch_dimensions["lengthscale"] != 2 or ls.shape not in ((*batch, 1, D), (*batch, 1, 1)):
-            return f"lengthscale of shape {tuple(ls.shape)}"
-        if self.num_nonbatch_dimensions["outputscale"] != 0 or os_.shape != batch:
-            return f"outputscale of shape {tuple(os_.shape)}"
-        if extra == "alpha":
-            if self.num_nonbatch_dimensions["alpha"] != 0 or sh.shape != batch:
-                return f"alpha of shape {tuple(sh.shape)}"
-        elif self.num_nonbatch_dimensions["period_length"] != 2 or sh.shape not in ((*batch, 1, D), (*batch, 1, 1)):
-            return f"period_length of shape {tuple(sh.shape)}"
-        tensors = (self.x1, self.x2, ls, os_, sh)
-        if any(t.dtype != torch.float32 for t in tensors):
-            return "not float32"
-        if check_device and not all(t.is_cuda for t in tensors):
-            return "not on the device"
-        return None
 
     def _is_native_param(self) -> bool:
         return self._native_param_refusal() is None
 
-    def _native_f64_refusal(self, check_device: bool = True) -> Optional[str]:
-        """The gate of the float64 kernels (csrc/lo_kernel_op_f64.hip): None when they take this operator, else the
-        reason they do not -- the conditions of `_native_refusal` with every tensor float64.  `check_device=False`
-        leaves out the device condition."""
-        from .. import _hip
-
-        if getattr(self.covar_func, "native_family", None) is None:
-            return "covar_func has no native_family"
-        if self.num_outputs_per_input != (1, 1):
-            return "more than one output per input"
-        if self.nontensor_params or set(self.tensor_params) != {"lengthscale", "outputscale"}:
-            return "parameters other than lengthscale and outputscale"
-        D = self.x1.shape[-1]
-        if D > _hip.LO_KERNEL_MAX_DIM or D < 1 or self.x2.shape[-1] != D:
-            return f"D = {D} beyond LO_KERNEL_MAX_DIM"
-        ls, os_ = self.tensor_params["lengthscale"], self.tensor_params["outputscale"]
-        batch = self.batch_broadcast_shape
-        if self.num_nonbatch_dimensions["lengthscale"] != 2 or ls.shape not in ((*batch, 1, D), (*batch, 1, 1)):
-            return f"lengthscale of shape {tuple(ls.shape)}"
-        if self.num_nonbatch_dimensions["outputscale"] != 0 or os_.shape != batch:
-            return f"outputscale of shape {tuple(os_.shape)}"
-        tensors = (self.x1, self.x2, ls, os_)
-        if any(t.dtype != torch.float64 for t in tensors):
-            return "not float64"
-        if check_device and not all(t.is_cuda for t in tensors):
-            return "not on the device"
-        return None
-
-    def _is_native_f64(self) -> bool:
-        return self._native_f64_refusal() is None
-
     def _same_points(self) -> bool:
         return _same_tensor(self.x1, self.x2)
 
-    def _theta(self, batch, dtype=torch.float32):
-        from .. import kernels as K
+    def _theta(self, v: _Variant, bs):
+        """Inside the gate of `v`, for the batch `bs`: (theta of the variant's entry points, the operands between theta
+        and the family: (Bt [B, T, T],) of the task variant, else ())."""
+        p, extra = self.tensor_params, self._extra(v)
+        kw = {} if v.dtype == torch.float32 else {"dtype": v.dtype}
+        if extra is not None and extra.rule != "table":
+            kw[extra.name] = p[extra.name]
+        theta = getattr(K, v.theta)(p["lengthscale"], p["outputscale"], bs, self.x1.shape[-1] - v.ids, **kw)
+        return theta, ((_flat(p[extra.name], bs),) if extra is not None and extra.rule == "table" else ())
 
-        return K.kernel_theta(self.tensor_params["lengthscale"], self.tensor_params["outputscale"], batch,
-                              self.x1.shape[-1], dtype=dtype)
+    def _points(self, bs):
+        """(x1 [B, M, DX], x2 [B, N, DX]) for the batch `bs`; one tensor when x1 and x2 are the same points."""
+        x1 = _flat(self.x1, bs)
+        return x1, (x1 if self._same_points() else _flat(self.x2, bs))
 
-    def _task_operands(self, batch):
-        """Inside the task gate: theta [B, D + 1] over the D coordinates and task_covar as Bt [B, T, T], for `batch`."""
-        from .. import kernels as K
-
-        Bt = self.tensor_params["task_covar"].detach()
-        T = Bt.shape[-1]
-        theta = K.kernel_theta(self.tensor_params["lengthscale"], self.tensor_params["outputscale"], batch,
-                               self.x1.shape[-1] - 1)
-        return theta, Bt.expand(*batch, T, T).reshape(-1, T, T)
-
-    def _param_theta(self, batch):
-        """Inside the param gate: theta [B, 2 D + 2] for `batch` (kernels.kernel_param_theta)."""
-        from .. import kernels as K
-
-        p = self.tensor_params
-        return K.kernel_param_theta(p["lengthscale"], p["outputscale"], batch, self.x1.shape[-1], alpha=p.get("alpha"),
-                                    period_length=p.get("period_length"))
+    def _descriptor(self, v: _Variant, batch_shape):
+        bs = torch.Size(self.batch_shape if batch_shape is None else batch_shape)
+        X = self.x1.detach()
+        X = X if X.shape[:-2] == bs else X.expand(*bs, *X.shape[-2:])
+        theta, task = self._theta(v, bs)
+        kw = {} if v.dtype == torch.float32 else {"dtype": v.dtype}
+        return getattr(K, v.descriptor)(X, theta, self.covar_func.native_family,
+                                        *(t.reshape(*bs, *t.shape[-2:]) for t in task), **kw)
 
     def _kernel_descriptor_f64(self, batch_shape=None):
         """The float64 LO_OP_KERNEL_DIAG descriptor inside the float64 gate when x1 and x2 are one tensor, else None."""
         if not (self._is_native_f64() and self._same_points()):
             return None
-        from .. import kernels as K
-
-        bs = torch.Size(self.batch_shape if batch_shape is None else batch_shape)
-        X = self.x1.detach()
-        X = X if X.shape[:-2] == bs else X.expand(*bs, *X.shape[-2:])
-        return K.kernel_diag_descriptor(X, self._theta(bs, torch.float64), self.covar_func.native_family,
-                                        dtype=torch.float64)
+        return self._descriptor(_F64, batch_shape)
 
     def _kernel_descriptor(self, batch_shape=None):
-        grad, task, param = self._is_native_grad(), self._is_native_task(), self._is_native_param()
-        if not ((grad or task or param or self._is_native()) and self._same_points()):
+        v = self._native_variant()
+        if v is None or v is _F64 or not self._same_points():
             return None
-        from .. import kernels as K
-
-        bs = torch.Size(self.batch_shape if batch_shape is None else batch_shape)
-        X = self.x1.detach()
-        X = X if X.shape[:-2] == bs else X.expand(*bs, *X.shape[-2:])
-        if task:
-            theta, Bt = self._task_operands(bs)
-            return K.kernel_task_diag_descriptor(X, theta, self.covar_func.native_family, Bt.reshape(*bs, *Bt.shape[-2:]))
-        if param:
-            return K.kernel_param_diag_descriptor(X, self._param_theta(bs), self.covar_func.native_family)
-        build = K.kernel_grad_diag_descriptor if grad else K.kernel_diag_descriptor
-        return build(X, self._theta(bs), self.covar_func.native_family)
+        return self._descriptor(v, batch_shape)
 
     # ------------------------------------------------------------------ dense evaluation (the general path)
     def _dense_covar(self):
@@ -395,52 +329,12 @@ class KernelLinearOperator(LinearOperator):
     def _matmul(self, rhs: Tensor) -> Tensor:
         vec = rhs.dim() == 1
         cols = rhs.unsqueeze(-1) if vec else rhs
-        if cols.is_cuda and cols.dtype == torch.float32 and self._is_native_grad():
-            from .. import kernels as K
-
-            M, D = self.x1.shape[-2:]
-            N, c = self.x2.shape[-2], cols.shape[-1]
+        v = self._native_variant() if cols.is_cuda else None
+        if v is not None and cols.dtype == v.dtype:
             bs = torch.broadcast_shapes(self.batch_shape, cols.shape[:-2])
-            x1 = self.x1.detach().expand(*bs, M, D).reshape(-1, M, D)
-            x2 = x1 if self._same_points() else self.x2.detach().expand(*bs, N, D).reshape(-1, N, D)
-            y = K.kernel_grad_mv(x1, x2, self._theta(bs), self.covar_func.native_family,
-                                 cols.detach().expand(*bs, N * (D + 1), c).reshape(-1, N * (D + 1), c))
-            y = y.reshape(*bs, M * (D + 1), c)
-        elif cols.is_cuda and cols.dtype == torch.float32 and self._is_native_task():
-            from .. import kernels as K
-
-            M, DX = self.x1.shape[-2:]
-            N, c = cols.shape[-2:]
-            bs = torch.broadcast_shapes(self.batch_shape, cols.shape[:-2])
-            x1 = self.x1.detach().expand(*bs, M, DX).reshape(-1, M, DX)
-            x2 = x1 if self._same_points() else self.x2.detach().expand(*bs, N, DX).reshape(-1, N, DX)
-            theta, Bt = self._task_operands(bs)
-            y = K.kernel_task_mv(x1, x2, theta, Bt, self.covar_func.native_family,
-                                 cols.detach().expand(*bs, N, c).reshape(-1, N, c))
-            y = y.reshape(*bs, M, c)
-        elif cols.is_cuda and cols.dtype == torch.float32 and self._is_native_param():
-            from .. import kernels as K
-
-            M, D = self.x1.shape[-2:]
-            N, c = cols.shape[-2:]
-            bs = torch.broadcast_shapes(self.batch_shape, cols.shape[:-2])
-            x1 = self.x1.detach().expand(*bs, M, D).reshape(-1, M, D)
-            x2 = x1 if self._same_points() else self.x2.detach().expand(*bs, N, D).reshape(-1, N, D)
-            y = K.kernel_param_mv(x1, x2, self._param_theta(bs), self.covar_func.native_family,
-                                  cols.detach().expand(*bs, N, c).reshape(-1, N, c))
-            y = y.reshape(*bs, M, c)
-        elif cols.is_cuda and ((cols.dtype == torch.float32 and self._is_native())
-                               or (cols.dtype == torch.float64 and self._is_native_f64())):
-            from .. import kernels as K
-
-            M, D = self.x1.shape[-2:]
-            N, c = cols.shape[-2:]
-            bs = torch.broadcast_shapes(self.batch_shape, cols.shape[:-2])
-            x1 = self.x1.detach().expand(*bs, M, D).reshape(-1, M, D)
-            x2 = x1 if self._same_points() else self.x2.detach().expand(*bs, N, D).reshape(-1, N, D)
-            y = K.kernel_mv(x1, x2, self._theta(bs, cols.dtype), self.covar_func.native_family,
-                            cols.detach().expand(*bs, N, c).reshape(-1, N, c))
-            y = y.reshape(*bs, M, c)
+            theta, task = self._theta(v, bs)
+            y = getattr(K, v.mv)(*self._points(bs), theta, *task, self.covar_func.native_family, _flat(cols, bs))
+            y = y.reshape(*bs, *y.shape[-2:])
         else:
             y = self._dense_covar() @ cols.contiguous()
         return y[..., 0] if vec else y
@@ -470,24 +364,20 @@ class KernelLinearOperator(LinearOperator):
     def _diagonal(self) -> Tensor:
         p, q = self.num_outputs_per_input
         n = self.x1.shape[-2]
-        if ((self._native_refusal(check_device=False) is None or self._native_f64_refusal(check_device=False) is None
-             or self._native_param_refusal(check_device=False) is None) and self._same_points()):
-            # g(0) = 1 for every native family: the diagonal is outputscale^2, no kernel launch
-            return self.tensor_params["outputscale"].square().unsqueeze(-1).expand(*self.batch_broadcast_shape, n)
-        if self._native_task_refusal(check_device=False) is None and self._same_points():
-            # g(0) = 1: outputscale^2 task_covar[t_i, t_i], the table's diagonal gathered at the ids; no covar_func
+        v = self._native_variant(check_device=False) if self._same_points() else None
+        if v is not None:  # g(0) = 1 for every native family: from the parameters alone, no kernel launch, no covar_func
             batch = self.batch_broadcast_shape
-            ids = self.x1[..., -1].long().expand(*batch, n)
-            own = self.tensor_params["task_covar"].diagonal(dim1=-2, dim2=-1).expand(*batch, -1).gather(-1, ids)
-            return self.tensor_params["outputscale"].square().unsqueeze(-1) * own
-        if self._native_grad_refusal(check_device=False) is None and self._same_points():
-            # the block of a point with itself is outputscale^2 diag(1, 1 / l_1^2, .., 1 / l_D^2): no launch, no covar_func
-            D = self.x1.shape[-1]
-            batch = self.batch_broadcast_shape
-            inv2 = (1.0 / self.tensor_params["lengthscale"]).square().expand(*batch, 1, D)[..., 0, :]
             os2 = self.tensor_params["outputscale"].square().unsqueeze(-1)
-            per = torch.cat((torch.ones_like(inv2[..., :1]), inv2), -1) * os2
-            return per.unsqueeze(-2).expand(*batch, n, D + 1).reshape(*batch, n * (D + 1))
+            if v.block:  # the block of a point with itself is outputscale^2 diag(1, 1 / l_1^2, .., 1 / l_D^2)
+                D = self.x1.shape[-1]
+                inv2 = (1.0 / self.tensor_params["lengthscale"]).square().expand(*batch, 1, D)[..., 0, :]
+                per = torch.cat((torch.ones_like(inv2[..., :1]), inv2), -1) * os2
+                return per.unsqueeze(-2).expand(*batch, n, D + 1).reshape(*batch, n * (D + 1))
+            if v.ids:  # outputscale^2 task_covar[t_i, t_i], the table's diagonal gathered at the ids
+                ids = self.x1[..., -1].long().expand(*batch, n)
+                table = self.tensor_params[self._extra(v).name]
+                return os2 * table.diagonal(dim1=-2, dim2=-1).expand(*batch, -1).gather(-1, ids)
+            return os2.expand(*batch, n)
         # the pairs (x1_i, x2_i) as a leading batch dimension of 1 x 1 (or p x q) kernel matrices
         a = self.x1.movedim(-2, 0).unsqueeze(-2)
         b = self.x2.movedim(-2, 0).unsqueeze(-2)
@@ -551,19 +441,11 @@ class KernelLinearOperator(LinearOperator):
         if left_vecs.dim() == 1:
             left_vecs, right_vecs = left_vecs.unsqueeze(-1), right_vecs.unsqueeze(-1)
         names = list(self._differentiable_kwargs)
-        if left_vecs.is_cuda and left_vecs.dtype == torch.float32 and self._is_native():
-            return self._bilinear_derivative_native(left_vecs, right_vecs, names)
-        if (left_vecs.is_cuda and left_vecs.dtype == torch.float64 and right_vecs.dtype == torch.float64
-                and self._is_native_f64()):
-            return self._bilinear_derivative_native(left_vecs, right_vecs, names)
-        if left_vecs.is_cuda and left_vecs.dtype == torch.float32 and self._is_native_task():
-            return self._bilinear_derivative_task(left_vecs, right_vecs, names)
-        if left_vecs.is_cuda and left_vecs.dtype == torch.float32 and self._is_native_param():
-            return self._bilinear_derivative_param(left_vecs, right_vecs, names)
-        if (left_vecs.is_cuda and left_vecs.dtype == torch.float32 and self._is_native_grad()
-                and not (self.x1.requires_grad or self.x2.requires_grad)):
-            # (native gradients of the points are not built for this kind: such a call takes the general path whole)
-            return self._bilinear_derivative_native(left_vecs, right_vecs, names, grad=True)
+        v = self._native_variant() if left_vecs.is_cuda else None
+        # (no native gradients of the points in the grad variant: such a call takes the general path whole)
+        if (v is not None and left_vecs.dtype == v.dtype and (right_vecs.dtype == v.dtype or v.dtype == torch.float32)
+                and (v.points_grad is not None or not (self.x1.requires_grad or self.x2.requires_grad))):
+            return self._bilinear_derivative_native(left_vecs, right_vecs, names, v)
         tensors = [self.x1, self.x2] + [self.tensor_params[n] for n in names]
         leaves = [t.detach().requires_grad_(True) if t.requires_grad and t.dtype.is_floating_point else t.detach()
                   for t in tensors]
@@ -577,111 +459,58 @@ class KernelLinearOperator(LinearOperator):
             grads = list(torch.autograd.grad(loss, need, allow_unused=True))
         return tuple(grads.pop(0) if t.requires_grad else None for t in leaves)
 
-    def _theta_to_params(self, g: Tensor, theta: Tensor, D: int, bs, out: dict) -> None:
-        """d / d theta [B, D + 1] as the gradients of the lengthscale and outputscale tensors, where they ask for one."""
+    def _theta_to_params(self, v: _Variant, g, theta: Tensor, bs, out: dict) -> None:
+        """d / d theta (`g`; the task variant: with d / d Bt) as the gradients of the parameter tensors that ask for one."""
+        D = self.x1.shape[-1] - v.ids
+        extra = self._extra(v)
+        if extra is not None and extra.rule == "table":
+            g, g_table = g
+
+        def inverse(lo: int, p: Tensor) -> Tensor:
+            # theta_d = 1 / p_d: d / d p_d = -theta_d^2 d / d theta_d; a shared p sums over d
+            d_p = (-(theta[:, lo:lo + D] ** 2) * g[:, lo:lo + D]).reshape(*bs, 1, D)
+            if p.shape[-1] == 1 and D > 1:
+                d_p = d_p.sum(-1, keepdim=True)
+            return d_p.sum_to_size(p.shape)
+
         ls, os_ = self.tensor_params["lengthscale"], self.tensor_params["outputscale"]
-        if ls.requires_grad:  # theta_d = 1 / l_d: d / d l_d = -theta_d^2 d / d theta_d; a shared l sums over d
-            d_ls = (-(theta[:, :D] ** 2) * g[:, :D]).reshape(*bs, 1, D)
-            if ls.shape[-1] == 1 and D > 1:
-                d_ls = d_ls.sum(-1, keepdim=True)
-            out["lengthscale"] = d_ls.sum_to_size(ls.shape)
+        if ls.requires_grad:
+            out["lengthscale"] = inverse(0, ls)
         if os_.requires_grad:  # theta_D = os^2: d / d os = 2 os d / d theta_D
-            out["outputscale"] = (2.0 * torch.broadcast_to(os_.detach(), tuple(bs)) * g[:, D].reshape(tuple(bs))).sum_to_size(os_.shape)
+            d_os = 2.0 * torch.broadcast_to(os_.detach(), tuple(bs)) * g[:, D].reshape(tuple(bs))
+            out["outputscale"] = d_os.sum_to_size(os_.shape)
+        p = None if extra is None else self.tensor_params[extra.name]
+        if p is None or not p.requires_grad:
+            return
+        if extra.rule == "table":
+            out[extra.name] = g_table.reshape(*bs, *p.shape[-2:]).sum_to_size(p.shape)
+        elif extra.rule == "ard":
+            out[extra.name] = inverse(D + extra.col, p)
+        else:
+            out[extra.name] = g[:, D + extra.col].reshape(tuple(bs)).sum_to_size(p.shape)
 
-    def _bilinear_derivative_task(self, left_vecs: Tensor, right_vecs: Tensor, names):
-        """Inside the task gate: every gradient from the native kernels, nothing of size M N allocated."""
-        from .. import kernels as K
-
-        ls, os_, Bt = (self.tensor_params[k] for k in ("lengthscale", "outputscale", "task_covar"))
-        M, DX = self.x1.shape[-2:]
-        N, t = self.x2.shape[-2], right_vecs.shape[-1]
-        T = Bt.shape[-1]
-        bs = torch.broadcast_shapes(self.batch_shape, left_vecs.shape[:-2], right_vecs.shape[:-2])
-        out = {"x1": None, "x2": None, "lengthscale": None, "outputscale": None, "task_covar": None}
-        if not any(p.requires_grad for p in (self.x1, self.x2, ls, os_, Bt)):
+    def _bilinear_derivative_native(self, left_vecs: Tensor, right_vecs: Tensor, names, v: _Variant):
+        """Inside the gate of `v` (the grad variant: the caller saw that no points tensor asks for a gradient): every
+        gradient from the native kernels, nothing of size M N allocated."""
+        params = [self.tensor_params[n] for n in names]
+        if not any(t.requires_grad for t in (self.x1, self.x2, *params)):
             return (None, None) + (None,) * len(names)
         family = self.covar_func.native_family
-        x1 = self.x1.detach().expand(*bs, M, DX).reshape(-1, M, DX)
-        x2 = x1 if self._same_points() else self.x2.detach().expand(*bs, N, DX).reshape(-1, N, DX)
-        theta, task = self._task_operands(bs)
-        U = left_vecs.detach().expand(*bs, M, t).reshape(-1, M, t)
-        V = right_vecs.detach().expand(*bs, N, t).reshape(-1, N, t)
-        if ls.requires_grad or os_.requires_grad or Bt.requires_grad:
-            g, g_task = K.kernel_task_bilinear(x1, x2, theta, task, family, U, V)
-            self._theta_to_params(g, theta, DX - 1, bs, out)
-            if Bt.requires_grad:
-                out["task_covar"] = g_task.reshape(*bs, T, T).sum_to_size(Bt.shape)
-        # the x2 side is the x1 side of the transposed problem: x1 <-> x2, U <-> V, Bt transposed
-        if self.x1.requires_grad:
-            out["x1"] = K.kernel_task_points_grad(x1, x2, theta, task, family, U, V).reshape(*bs, M, DX).sum_to_size(self.x1.shape)
-        if self.x2.requires_grad:
-            out["x2"] = K.kernel_task_points_grad(x2, x1, theta, task.mT, family, V, U).reshape(*bs, N, DX).sum_to_size(self.x2.shape)
-        return (out["x1"], out["x2"]) + tuple(out[n] for n in names)
-
-    def _bilinear_derivative_param(self, left_vecs: Tensor, right_vecs: Tensor, names):
-        """Inside the param gate: every gradient from the native kernels, nothing of size M N allocated."""
-        from .. import kernels as K
-
-        extra = "alpha" if "alpha" in self.tensor_params else "period_length"
-        ls, os_, sh = (self.tensor_params[k] for k in ("lengthscale", "outputscale", extra))
-        M, D = self.x1.shape[-2:]
-        N, t = self.x2.shape[-2], right_vecs.shape[-1]
         bs = torch.broadcast_shapes(self.batch_shape, left_vecs.shape[:-2], right_vecs.shape[:-2])
-        out = {"x1": None, "x2": None, "lengthscale": None, "outputscale": None, extra: None}
-        if not any(p.requires_grad for p in (self.x1, self.x2, ls, os_, sh)):
-            return (None, None) + (None,) * len(names)
-        family = self.covar_func.native_family
-        x1 = self.x1.detach().expand(*bs, M, D).reshape(-1, M, D)
-        x2 = x1 if self._same_points() else self.x2.detach().expand(*bs, N, D).reshape(-1, N, D)
-        theta = self._param_theta(bs)
-        U = left_vecs.detach().expand(*bs, M, t).reshape(-1, M, t)
-        V = right_vecs.detach().expand(*bs, N, t).reshape(-1, N, t)
-        if ls.requires_grad or os_.requires_grad or sh.requires_grad:
-            g = K.kernel_param_bilinear(x1, x2, theta, family, U, V)  # [B, 2 D + 2], d / d theta
-            self._theta_to_params(g, theta, D, bs, out)
-            if sh.requires_grad and extra == "alpha":
-                out[extra] = g[:, D + 1].reshape(tuple(bs)).sum_to_size(sh.shape)
-            elif sh.requires_grad:  # nu_k = 1 / p_k: d / d p_k = -nu_k^2 d / d nu_k; a shared p sums over k
-                d_p = (-(theta[:, D + 2:] ** 2) * g[:, D + 2:]).reshape(*bs, 1, D)
-                if sh.shape[-1] == 1 and D > 1:
-                    d_p = d_p.sum(-1, keepdim=True)
-                out[extra] = d_p.sum_to_size(sh.shape)
-        # the x2 side is the x1 side of the transposed problem (x1 <-> x2, U <-> V)
-        if self.x1.requires_grad:
-            out["x1"] = K.kernel_param_points_grad(x1, x2, theta, family, U, V).reshape(*bs, M, D).sum_to_size(self.x1.shape)
-        if self.x2.requires_grad:
-            out["x2"] = K.kernel_param_points_grad(x2, x1, theta, family, V, U).reshape(*bs, N, D).sum_to_size(self.x2.shape)
-        return (out["x1"], out["x2"]) + tuple(out[n] for n in names)
-
-    def _bilinear_derivative_native(self, left_vecs: Tensor, right_vecs: Tensor, names, grad: bool = False):
-        """grad: the gradient kernel (the vectors have D + 1 rows per point; the caller saw that no points tensor asks
-        for a gradient)."""
-        from .. import kernels as K
-
-        ls, os_ = self.tensor_params["lengthscale"], self.tensor_params["outputscale"]
-        M, D = self.x1.shape[-2:]
-        N, t = self.x2.shape[-2], right_vecs.shape[-1]
-        p = D + 1 if grad else 1
-        bs = torch.broadcast_shapes(self.batch_shape, left_vecs.shape[:-2], right_vecs.shape[:-2])
-        out = {"x1": None, "x2": None, "lengthscale": None, "outputscale": None}
-        if not any(p.requires_grad for p in (self.x1, self.x2, ls, os_)):
-            return (None, None) + (None,) * len(names)
-        family = self.covar_func.native_family
-        x1 = self.x1.detach().expand(*bs, M, D).reshape(-1, M, D)
-        x2 = x1 if self._same_points() else self.x2.detach().expand(*bs, N, D).reshape(-1, N, D)
-        theta = self._theta(bs, left_vecs.dtype)
-        U = left_vecs.detach().expand(*bs, M * p, t).reshape(-1, M * p, t)
-        V = right_vecs.detach().expand(*bs, N * p, t).reshape(-1, N * p, t)
-        if ls.requires_grad or os_.requires_grad:
-            bilinear = K.kernel_grad_bilinear if grad else K.kernel_bilinear
-            g = bilinear(x1, x2, theta, family, U, V)  # [B, D + 1], d / d theta
-            self._theta_to_params(g, theta, D, bs, out)
+        x1, x2 = self._points(bs)
+        theta, task = self._theta(v, bs)
+        U, V = _flat(left_vecs, bs), _flat(right_vecs, bs)
+        out = dict.fromkeys(("x1", "x2", *names))
+        if any(t.requires_grad for t in params):
+            self._theta_to_params(v, getattr(K, v.bilinear)(x1, x2, theta, *task, family, U, V), theta, bs, out)
         # each side with the other held fixed; x1 and x2 the same leaf: autograd adds the two.  The x2 side is the x1 side
-        # of the transposed problem (x1 <-> x2, U <-> V).
+        # of the transposed problem (x1 <-> x2, U <-> V, Bt transposed).
         if self.x1.requires_grad:
-            out["x1"] = K.kernel_points_grad(x1, x2, theta, family, U, V).reshape(*bs, M, D).sum_to_size(self.x1.shape)
+            g = getattr(K, v.points_grad)(x1, x2, theta, *task, family, U, V)
+            out["x1"] = g.reshape(*bs, *g.shape[-2:]).sum_to_size(self.x1.shape)
         if self.x2.requires_grad:
-            out["x2"] = K.kernel_points_grad(x2, x1, theta, family, V, U).reshape(*bs, N, D).sum_to_size(self.x2.shape)
+            g = getattr(K, v.points_grad)(x2, x1, theta, *(t.mT for t in task), family, V, U)
+            out["x2"] = g.reshape(*bs, *g.shape[-2:]).sum_to_size(self.x2.shape)
         return (out["x1"], out["x2"]) + tuple(out[n] for n in names)
 
 

@@ -232,7 +232,8 @@ class KroneckerProductLinearOperator(LinearOperator):
         X = X if X.shape[:-2] == bs else X.expand(*bs, *X.shape[-2:])
         Bt = task.tensor.detach()
         Bt = Bt if Bt.shape[:-2] == bs else Bt.expand(*bs, *Bt.shape[-2:])
-        return K.kernel_kron_diag_descriptor(X, kern._theta(bs), kern.covar_func.native_family, Bt)
+        theta = K.kernel_theta(kern.tensor_params["lengthscale"], kern.tensor_params["outputscale"], bs, X.shape[-1])
+        return K.kernel_kron_diag_descriptor(X, theta, kern.covar_func.native_family, Bt)
 
     def _kernel_descriptor(self, batch_shape=None):
         if self._kernel_kron_refusal() is None:

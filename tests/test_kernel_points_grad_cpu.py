@@ -2,6 +2,8 @@
 sizer, which is host code), kernels.kernel_points_grad, and the removal of the chunked autograd path."""
 import inspect
 
+import torch
+
 from linear_operator_amd import _hip
 from linear_operator_amd import kernels as K
 from linear_operator_amd.operators import KernelLinearOperator, kernel_linear_operator
@@ -56,4 +58,7 @@ def test_python_layers():
     assert list(inspect.signature(K.kernel_points_grad).parameters) == ["x1", "x2", "theta", "family", "U", "V"]
     assert not hasattr(KernelLinearOperator, "_points_derivative_chunked")
     assert not hasattr(kernel_linear_operator, "MAX_DENSE_CHUNK_BYTES")
-    assert "kernel_points_grad" in inspect.getsource(KernelLinearOperator._bilinear_derivative_native)
+    # the points' gradients come from the wrapper the variant's table row names, called by _bilinear_derivative_native
+    plain = next(v for v in kernel_linear_operator.VARIANTS if v.tag is None and v.dtype == torch.float32)
+    assert plain.points_grad == "kernel_points_grad"
+    assert "getattr(K, v.points_grad)" in inspect.getsource(KernelLinearOperator._bilinear_derivative_native)
