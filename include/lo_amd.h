@@ -112,6 +112,11 @@ extern "C" {
 #define LO_KERNEL_RQ 16       /* g = (1 + r^2 / (2 alpha))^(-alpha), r as for LO_KERNEL_RBF                                */
 #define LO_KERNEL_PERIODIC 17 /* g = exp(-2 sum_k (sin(pi (x_i[k] - x_j[k]) / p_k) / l_k)^2)                               */
 #define LO_KERNEL_PARAM_MAX_DIM 32 /* input dimensions D the kind and lo_kernel_param_* take (more: LO_ERR_UNSUPPORTED)     */
+#define LO_OP_KERNEL_SM_DIAG 19 /* AddedDiag(SM(X, X), Diag(d)): the matrix-free spectral mixture kernel, y = K(X, X) v + d o v,
+                                 *   K_ij = sum_q w_q exp(-2 pi^2 sum_k (sigma_qk tau_k)^2) prod_k cos(2 pi mu_qk tau_k),
+                                 *   tau = x_i - x_j, formed tile by tile, never stored                                       */
+#define LO_KERNEL_SM_MAX_DIM 16 /* input dimensions D the kind and lo_kernel_sm_* take (more: LO_ERR_UNSUPPORTED)            */
+#define LO_KERNEL_SM_MAX_MIX 16 /* mixtures Q the kind and lo_kernel_sm_* take (more: LO_ERR_UNSUPPORTED)                    */
 #define LO_SKI_SUM_MAX_TERMS 64 /* terms P one LO_OP_SKI_SUM_DIAG descriptor / lo_interp_sum_f32 call takes (more: LO_ERR_UNSUPPORTED) */
 
 struct lo_interp_desc;
@@ -246,7 +251,18 @@ typedef struct lo_op_desc {
    * own row source: periodic + RBF + noise is one LO_OP_SUM); the fp64 entry points, the resident / fused engines and the
    * solve sessions return LO_ERR_UNSUPPORTED; not a base kind of LO_OP_MASKED (nor a term of a masked sum); not grouped
    * into KERNEL_SUM.  LO_ERR_BADARG: a null A0 / A1, R < 1, a family other than 16 / 17; LO_ERR_UNSUPPORTED: D >
-   * LO_KERNEL_PARAM_MAX_DIM, B > 65535, N > 0x7ffffe00; LO_ERR_WORKSPACE: a short workspace.  All before any launch.  */
+   * LO_KERNEL_PARAM_MAX_DIM, B > 65535, N > 0x7ffffe00; LO_ERR_WORKSPACE: a short workspace.  All before any launch.
+   * ABI 40 kind.  KERNEL_SM: A0 = X [B, N, D], R = D <= LO_KERNEL_SM_MAX_DIM, n2 = the number of mixtures Q in 1 ..
+   * LO_KERNEL_SM_MAX_MIX, A1 = theta [B, Q, 2 D + 1], per mixture the RAW values (no inverses, no outputscale):
+   *   theta[q][0]                  the weight w_q
+   *   theta[q][1 .. D + 1)         the D means mu_q (frequencies; the sign of a mean does not change K)
+   *   theta[q][D + 1 .. 2 D + 1)   the D scales sigma_q
+   * Lowered for lo_matvec_f32, the streaming CG, Lanczos, fp32 MINRES and the fp32 pivoted Cholesky (constant diagonal
+   * sum_q w_q added in ascending q, row of pivot p: row[j] = K(x_p, x_j)); a term kind of LO_OP_SUM next to KERNEL and
+   * KERNEL_PARAM (SM + RBF + noise is one LO_OP_SUM); the fp64 entry points, the resident / fused engines and the solve
+   * sessions return LO_ERR_UNSUPPORTED; not a base kind of LO_OP_MASKED (nor a term of a masked sum); not grouped into
+   * KERNEL_SUM.  LO_ERR_BADARG: a null A0 / A1, R < 1, Q < 1; LO_ERR_UNSUPPORTED: D > LO_KERNEL_SM_MAX_DIM, Q >
+   * LO_KERNEL_SM_MAX_MIX, B > 65535, N > 0x7ffffe00; LO_ERR_WORKSPACE: a short workspace.  All before any launch.     */
 } lo_op_desc;
 
 /* The grid shape of an LO_OP_TOEPLITZ_KRON_DIAG descriptor (host struct). */
@@ -380,7 +396,7 @@ typedef struct lo_cg_info {
 } lo_cg_info;
 
 /* ---- library ------------------------------------------------------------------------------- */
-/* ABI version (39; bumped on any signature change) and the gfx arch string the code objects target. */
+/* ABI version (40; bumped on any signature change) and the gfx arch string the code objects target. */
 int lo_abi_version(void);
 const char* lo_target_arch(void);
 
@@ -1233,6 +1249,40 @@ size_t lo_kernel_param_points_grad_workspace_bytes(int64_t B, int64_t M, int64_t
 int lo_kernel_param_points_grad_f32(const float* x1, const float* x2, const float* theta, int32_t family, int64_t B,
                                     int64_t M, int64_t N, int64_t D, const float* U, const float* V, int64_t t,
                                     float* g_x1, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- matrix-free spectral mixture kernel (ABI 40; csrc/lo_kernel_sm.hip) -------------------------------------------------
+ * K(x1, x2)_ij = sum_{q < Q} w_q E_q prod_k cos(2 pi mu_qk tau_k), E_q = exp(-2 pi^2 sum_k (sigma_qk tau_k)^2), tau = x1_i -
+ * x2_j, for x1 [B, M, D], x2 [B, N, D] and theta [B, Q, 2 D + 1] as LO_OP_KERNEL_SM_DIAG lays it out.  The points are
+ * differenced FIRST and then multiplied by mu or sigma (the phase error is |mu tau| eps, not |mu x| eps); |tau| is used
+ * throughout, so K(x, y) and K(y, x) have equal bits; the cosine is taken in revolutions after fract.  The sweeps are those
+ * of lo_kernel_param_*: 256 rows per workgroup, x2 staged in LDS tiles of 128, a tile's sums on their own and then added
+ * to the running ones, the column split of few-row shapes with an ascending reduce.  Fixed-order sums, no atomics: two
+ * calls give equal bits.  Rectangular x1 != x2 is the prediction case.
+ *   lo_kernel_sm_mv_f32           y [B, M, c] = K(x1, x2) v (+ d o v when M == N), v [B, N, c], d per diag_mode; the kind
+ *                                 LO_OP_KERNEL_SM_DIAG with x1 = x2
+ *   lo_kernel_sm_bilinear_f32     for W_ij = sum_s U[i, s] V[j, s], U [B, M, t], V [B, N, t]: g_theta [B, Q, 2 D + 1] =
+ *                                 d / d theta of sum_ij W_ij K_ij, in theta's own layout.  With c_k, s_k the cosine and sine
+ *                                 of 2 pi mu_qk tau_k: d/dw_q = E_q prod c, d/dsigma_qk = -4 pi^2 sigma_qk tau_k^2 w_q E_q
+ *                                 prod c, d/dmu_qk = -2 pi tau_k s_k w_q E_q prod_{l != k} c_l (no division by a cosine)
+ *   lo_kernel_sm_points_grad_f32  g_x1 [B, M, D] = d / d x1 of the same sum, x2 held fixed.  The x2 side is the same call
+ *                                 with x1 / x2 and U / V swapped
+ * Q stands where `family` stands in lo_kernel_param_*; the sizers take it as well.
+ * LO_ERR_BADARG: a null pointer, a size < 1, Q < 1, an unknown diag_mode, (M == N) a mode without d, (M != N) any mode but
+ * LO_DIAG_NONE; LO_ERR_UNSUPPORTED: D > LO_KERNEL_SM_MAX_DIM, Q > LO_KERNEL_SM_MAX_MIX, B > 65535, M or N > 0x7ffffe00,
+ * c or t > 0x7fffffff; LO_ERR_WORKSPACE: a short workspace.  In this order, all before any launch.  The sizers return 0
+ * for arguments the call would refuse.                                                                                */
+size_t lo_kernel_sm_mv_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t D, int64_t Q, int64_t c);
+int lo_kernel_sm_mv_f32(const float* x1, const float* x2, const float* theta, int32_t Q, int64_t B, int64_t M, int64_t N,
+                        int64_t D, const float* v, int64_t c, const float* d, int32_t diag_mode, float* y, void* ws,
+                        size_t ws_bytes, void* stream);
+size_t lo_kernel_sm_bilinear_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t D, int64_t Q, int64_t t);
+int lo_kernel_sm_bilinear_f32(const float* x1, const float* x2, const float* theta, int32_t Q, int64_t B, int64_t M,
+                              int64_t N, int64_t D, const float* U, const float* V, int64_t t, float* g_theta, void* ws,
+                              size_t ws_bytes, void* stream);
+size_t lo_kernel_sm_points_grad_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t D, int64_t Q, int64_t t);
+int lo_kernel_sm_points_grad_f32(const float* x1, const float* x2, const float* theta, int32_t Q, int64_t B, int64_t M,
+                                 int64_t N, int64_t D, const float* U, const float* V, int64_t t, float* g_x1, void* ws,
+                                 size_t ws_bytes, void* stream);
 
 /* ---- exact small-N path: batched Cholesky and triangular solves (ABI 18; csrc/lo_chol.hip) -------------------------
  * fp32, contiguous row-major, N <= 1024 (larger: LO_ERR_UNSUPPORTED), stream-ordered; fixed-order sums, no atomics: a

@@ -45,10 +45,12 @@ LO_OP_KERNEL_LMC_DIAG = 17
 LO_OP_KERNEL_PARAM_DIAG = 18
 LO_KERNEL_RQ, LO_KERNEL_PERIODIC = 16, 17
 LO_KERNEL_PARAM_MAX_DIM = 32
+LO_OP_KERNEL_SM_DIAG = 19
+LO_KERNEL_SM_MAX_DIM, LO_KERNEL_SM_MAX_MIX = 16, 16
 LO_DIAG_NONE, LO_DIAG_FULL, LO_DIAG_CONST = 0, 1, 2
 LO_BLOCK_DIAG, LO_BLOCK_INTERLEAVED, LO_BLOCK_SUM = 0, 1, 2
 LO_EIGH_MAX_N = 1024
-ABI_VERSION = 39
+ABI_VERSION = 40
 
 LO_ERR_UNSUPPORTED = -4
 LO_FUSED_OK, LO_FUSED_EARLY_STOP, LO_FUSED_CONTINUE, LO_FUSED_TIMEOUT = 0, 1, 2, 3
@@ -325,6 +327,12 @@ _PROTOTYPES = {
     "lo_kernel_param_bilinear_f32": (ci, [vp, vp, vp, i32, i64, i64, i64, i64, vp, vp, i64, vp, vp, sz, vp]),
     "lo_kernel_param_points_grad_workspace_bytes": (sz, [i64, i64, i64, i64, i64]),
     "lo_kernel_param_points_grad_f32": (ci, [vp, vp, vp, i32, i64, i64, i64, i64, vp, vp, i64, vp, vp, sz, vp]),
+    "lo_kernel_sm_mv_workspace_bytes": (sz, [i64, i64, i64, i64, i64, i64]),
+    "lo_kernel_sm_mv_f32": (ci, [vp, vp, vp, i32, i64, i64, i64, i64, vp, i64, vp, i32, vp, vp, sz, vp]),
+    "lo_kernel_sm_bilinear_workspace_bytes": (sz, [i64, i64, i64, i64, i64, i64]),
+    "lo_kernel_sm_bilinear_f32": (ci, [vp, vp, vp, i32, i64, i64, i64, i64, vp, vp, i64, vp, vp, sz, vp]),
+    "lo_kernel_sm_points_grad_workspace_bytes": (sz, [i64, i64, i64, i64, i64, i64]),
+    "lo_kernel_sm_points_grad_f32": (ci, [vp, vp, vp, i32, i64, i64, i64, i64, vp, vp, i64, vp, vp, sz, vp]),
     "lo_cholesky_workspace_bytes": (sz, [i64, i64]),
     "lo_cholesky_f32": (ci, [vp, vp, vp, vp, i64, i64, vp, sz, vp]),
     "lo_tri_solve_f32": (ci, [vp, vp, vp, vp, i64, i64, i64, i32, i32, vp]),

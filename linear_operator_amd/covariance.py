@@ -35,6 +35,16 @@ convention `f(x1, x2, lengthscale, outputscale)` (the `covar_func` of the refere
               `native_outputs = "param"` and the codes LO_KERNEL_RQ / LO_KERNEL_PERIODIC, which lie outside the codes of
               the families above on purpose: csrc/lo_kernel_param.hip has entry points and a kind of its own.
 
+    spectral_mixture  `f(x1, x2, mixture_weights, mixture_means, mixture_scales)`, GPyTorch's SpectralMixtureKernel:
+              mixture_weights [..., Q], mixture_means and mixture_scales [..., Q, D] (GPyTorch keeps the means and scales as
+              [Q, 1, D]: squeeze the 1), no lengthscale and no outputscale:
+                  tau = x1_i - x2_j   (differenced first, then multiplied by mu or sigma: in float32 the difference of
+                                       near points is exact and the phase error is |mu tau| eps, not |mu x| eps)
+                  k = sum_q w_q exp(-2 pi^2 sum_k (sigma_qk tau_k)^2) prod_k cos(2 pi mu_qk tau_k)
+              One output per input, pass num_nonbatch_dimensions={"mixture_weights": 1}.  It carries
+              `native_outputs = "sm"` and NO native_family: csrc/lo_kernel_sm.hip has entry points and a kind of its own,
+              and every gate that asks for a family refuses it.  The diagonal is sum_q w_q.
+
 r^2 is the sum of squared direct differences of the scaled points (no |a|^2 + |b|^2 - 2 a.b, which cancels for near
 points).  Each function carries `native_family`, the LO_KERNEL_* code under which csrc/lo_kernel_op.hip evaluates the
 same formula tile by tile; on that path the [..., M, N] matrix these functions return is never formed.  rbf_grad
@@ -142,6 +152,15 @@ def periodic(x1: Tensor, x2: Tensor, lengthscale: Tensor, outputscale: Tensor, p
     return _scale(outputscale) * torch.exp(-2.0 * s.square().sum(-1))
 
 
+def spectral_mixture(x1: Tensor, x2: Tensor, mixture_weights: Tensor, mixture_means: Tensor,
+                     mixture_scales: Tensor) -> Tensor:
+    tau = (x1.unsqueeze(-2) - x2.unsqueeze(-3)).unsqueeze(-4)  # [..., 1, M, N, D]
+    mu, sg = mixture_means[..., :, None, None, :], mixture_scales[..., :, None, None, :]  # [..., Q, 1, 1, D]
+    env = torch.exp((-2.0 * math.pi ** 2) * (sg * tau).square().sum(-1))
+    osc = torch.cos((2.0 * math.pi) * (mu * tau)).prod(-1)
+    return (mixture_weights[..., :, None, None] * env * osc).sum(-3)
+
+
 rbf.native_family = _hip.LO_KERNEL_RBF
 rbf_grad.native_family = _hip.LO_KERNEL_RBF
 rbf_grad.native_outputs = "grad"
@@ -157,6 +176,8 @@ rq.native_family = _hip.LO_KERNEL_RQ
 periodic.native_family = _hip.LO_KERNEL_PERIODIC
 rq.native_outputs = periodic.native_outputs = "param"
 
+spectral_mixture.native_outputs = "sm"  # (and no native_family)
+
 FAMILIES = {"rbf": rbf, "matern12": matern12, "matern32": matern32, "matern52": matern52}
 # gradient kernels (D + 1 outputs per input): kept apart, FAMILIES holds the one-output families only
 GRAD_FAMILIES = {"rbf_grad": rbf_grad}
@@ -168,6 +189,9 @@ TASK_FAMILIES = {"rbf_task": rbf_task, "matern12_task": matern12_task, "matern32
 # families with a shape parameter (alpha, period_length): kept apart as well, with codes outside those of FAMILIES
 PARAM_FAMILIES = {"rq": rq, "periodic": periodic}
 
+# mixtures of products over the dimensions (no lengthscale, no outputscale, no family code): kept apart as well
+MIXTURE_FAMILIES = {"spectral_mixture": spectral_mixture}
+
 __all__ = ["rbf", "matern12", "matern32", "matern52", "rbf_grad", "rbf_task", "matern12_task", "matern32_task",
-           "matern52_task", "rq", "periodic", "scaled_sq_dist", "FAMILIES", "GRAD_FAMILIES", "TASK_FAMILIES",
-           "PARAM_FAMILIES"]
+           "matern52_task", "rq", "periodic", "spectral_mixture", "scaled_sq_dist", "FAMILIES", "GRAD_FAMILIES",
+           "TASK_FAMILIES", "PARAM_FAMILIES", "MIXTURE_FAMILIES"]

@@ -308,6 +308,11 @@ int kernel_param_plan(MatvecPlan* pl, Arena* ar, hipStream_t st);
 int kernel_param_matvec_run(const MatvecPlan* pl, const float* v, float* y, const int* stop, hipStream_t st);
 int kernel_param_desc_check(const lo_op_desc* op);
 
+// ---- matrix-free spectral mixture kernel (lo_kernel_sm.hip): LO_OP_KERNEL_SM_DIAG, on KernelOpPlan (its `part`)
+int kernel_sm_plan(MatvecPlan* pl, Arena* ar, hipStream_t st);
+int kernel_sm_matvec_run(const MatvecPlan* pl, const float* v, float* y, const int* stop, hipStream_t st);
+int kernel_sm_desc_check(const lo_op_desc* op);
+
 // ---- masked operator (lo_masked.hip) ---------------------------------------------------------------------------------
 struct MaskedPlan {      // (the base's plan is MatvecPlan::sub[0])
   const int64_t* idx;    // [M]
@@ -385,7 +390,8 @@ inline bool plain_term_kind(int kind) {
 }
 // the matrix-free kernel kinds: terms of a sum next to the plain ones (fp32 engines only; not under a mask)
 inline bool kernel_term_kind(int kind) {
-  return kind == LO_OP_KERNEL_DIAG || kind == LO_OP_KERNEL_SUM_DIAG || kind == LO_OP_KERNEL_PARAM_DIAG;
+  return kind == LO_OP_KERNEL_DIAG || kind == LO_OP_KERNEL_SUM_DIAG || kind == LO_OP_KERNEL_PARAM_DIAG ||
+         kind == LO_OP_KERNEL_SM_DIAG;
 }
 
 // ---- the Q-form Woodbury apply z = dinv o r - Q (Q^T r) as a plan (lo_skinny.hip): staged and run

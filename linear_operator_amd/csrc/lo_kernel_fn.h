@@ -190,6 +190,43 @@ __device__ __forceinline__ float kp_g_rt(int family, const float* xp, const floa
   return kp_rq_g(acc, th[D + 1], 0.5f / th[D + 1]);
 }
 
+// ---- the spectral mixture kernel (LO_OP_KERNEL_SM_DIAG: lo_kernel_sm.hip, lo_pivchol.hip) -------------------------------
+// k = sum_q w_q exp(-2 pi^2 sum_k (sigma_qk tau_k)^2) prod_k cos(2 pi mu_qk tau_k), tau = x - x'.  cos(2 pi p) for
+// p = |mu tau| >= 0 in revolutions: fract first (exact at any magnitude), then v_cos_f32, as kp_sin2pi; its sine partner in
+// the derivatives is kp_sin2pi itself.
+#ifndef LO_KSM_HW_COSINE
+#define LO_KSM_HW_COSINE 1
+#endif
+__device__ __forceinline__ float ksm_cos2pi(float p) {
+#if LO_KSM_HW_COSINE
+  return __builtin_amdgcn_cosf(__builtin_amdgcn_fractf(p));
+#else
+  return cospif(2.0f * p);
+#endif
+}
+constexpr float kKsmPi = 3.14159265358979323846f;
+constexpr float kKsmExpScale = -2.0f * kKsmPi * kKsmPi * kKfLog2e;  // E = exp2(kKsmExpScale sum_k (sigma_k tau_k)^2)
+__device__ __forceinline__ float ksm_env(float s2) { return kf_exp2(s2 * kKsmExpScale); }
+
+// one entry with everything a run-time value (row source of the pivoted Cholesky): theta [Q, 2 D + 1] as lo_amd.h lays it
+// out (w, mu_1 .. mu_D, sigma_1 .. sigma_D per mixture); the points differenced first, the sums in ascending k and q
+__device__ __forceinline__ float ksm_g_rt(const float* xp, const float* xi, const float* th, int D, int Q) {
+  float acc = 0.0f;
+  for (int q = 0; q < Q; ++q) {
+    const float* t = th + (size_t)q * (2 * D + 1);
+    float s2 = 0.0f, pr = 1.0f;
+    for (int k = 0; k < D; ++k) {
+      const float tau = fabsf(xp[k] - xi[k]);
+      const float st = t[1 + D + k] * tau;
+      s2 = s2 + st * st;
+      pr = pr * ksm_cos2pi(fabsf(t[1 + k]) * tau);
+    }
+    const float term = t[0] * (ksm_env(s2) * pr);
+    acc = q == 0 ? term : acc + term;
+  }
+  return acc;
+}
+
 // the same with the family as a run-time value (row source of the pivoted Cholesky: one entry per thread)
 __device__ __forceinline__ float kf_g_rt(int family, float r2) {
   switch (family) {

@@ -158,6 +158,7 @@ int matvec_plan_init(MatvecPlan* pl, const lo_op_desc* op, lo_matvec_cb cb, void
     case LO_OP_KERNEL_GRAD_DIAG: rc = kernel_grad_plan(pl, ar, st); break;
     case LO_OP_KERNEL_TASK_DIAG: rc = kernel_task_plan(pl, ar, st); break;
     case LO_OP_KERNEL_PARAM_DIAG: rc = kernel_param_plan(pl, ar, st); break;
+    case LO_OP_KERNEL_SM_DIAG: rc = kernel_sm_plan(pl, ar, st); break;
     case LO_OP_MASKED: rc = masked_plan(pl, ar, st); break;
     case LO_OP_CALLBACK: rc = cb ? LO_OK : LO_ERR_BADARG; break;
     case LO_OP_SUM: rc = sum_plan(pl, ar, st); break;
@@ -212,6 +213,8 @@ int matvec_run(const MatvecPlan* pl, const float* v, float* y, float* dot_part, 
       rc = kernel_task_matvec_run(pl, v, y, stop, st); break;
     case LO_OP_KERNEL_PARAM_DIAG:  // K_ij = os2 g(x_i, x_j), g rational quadratic or periodic (lo_kernel_param.hip)
       rc = kernel_param_matvec_run(pl, v, y, stop, st); break;
+    case LO_OP_KERNEL_SM_DIAG:  // K_ij = sum_q w_q E_q(tau) prod_k cos(2 pi mu_qk tau_k), the spectral mixture (lo_kernel_sm.hip)
+      rc = kernel_sm_matvec_run(pl, v, y, stop, st); break;
     case LO_OP_MASKED:  // S (base) S^T v + d o v: expand, the base's product (or the selected rows of a dense base), gather
       rc = masked_matvec_run(pl, v, y, stop, st); break;
     case LO_OP_CALLBACK: rc = pl->cb(pl->cb_user, v, y, op.B, op.N, pl->c, (void*)st) ? LO_ERR_LAUNCH : LO_OK; break;
@@ -241,7 +244,7 @@ using namespace lo;
 
 extern "C" {
 
-int lo_abi_version(void) { return 39; }
+int lo_abi_version(void) { return 40; }
 const char* lo_target_arch(void) { return "gfx950"; }
 
 size_t lo_matvec_workspace_bytes(const lo_op_desc* op, int64_t c) {

@@ -36,6 +36,8 @@
 //                  (no operator of the reference: include/lo_amd.h, LO_OP_KERNEL_TASK_DIAG) -- kern_r2, tk_task_id
 //   KERNEL_PARAM   os2 g(x_p, x_i), g rational quadratic or periodic; diag os2 (no operator of the reference: include/lo_amd.h,
 //                  LO_OP_KERNEL_PARAM_DIAG) -- kp_g_rt (lo_kernel_fn.h)
+//   KERNEL_SM      sum_q w_q E_q prod_k cos(2 pi mu_qk tau_k), the spectral mixture; diag sum_q w_q in ascending q (no operator of
+//                  the reference: include/lo_amd.h, LO_OP_KERNEL_SM_DIAG) -- ksm_g_rt (lo_kernel_fn.h)
 //   KERNEL_GRAD    the (al, be) entry of the RBF value / derivative block of the points p, j; diag os2, os2 t_a^2
 //                  (no operator of the reference: include/lo_amd.h, lo_kernel_grad_mv_f32) -- its own loop: that of
 //                  kern_r2, which also keeps the scaled differences of the coordinates al, be
@@ -246,6 +248,12 @@ __device__ __forceinline__ T src_diag(const PcDevT<T>& d, const lo_op_desc& op, 
     return (T)op.A1[(size_t)b * (op.R + 1) + op.R];
   } else if (op.kind == LO_OP_KERNEL_PARAM_DIAG) {  // os2 g(x, x) = os2 for both families
     return (T)op.A1[(size_t)b * (2 * op.R + 2) + op.R];
+  } else if (op.kind == LO_OP_KERNEL_SM_DIAG) {  // sum_q w_q, in ascending q (every envelope and cosine is 1 at tau = 0)
+    const int W = 2 * (int)op.R + 1, Q = (int)op.n2;
+    const float* th = op.A1 + (size_t)b * Q * W;
+    float s = th[0];
+    for (int q = 1; q < Q; ++q) s = s + th[(size_t)q * W];
+    return (T)s;
   } else if (op.kind == LO_OP_KERNEL_SUM_DIAG) {  // sum_t os2_t, in term order
     const float* th = op.A1 + (size_t)b * op.nterms * (op.R + 1);
     float s = th[op.R];
@@ -308,6 +316,10 @@ __device__ __forceinline__ T src_entry(const PcDevT<T>& d, const lo_op_desc& tm,
     const int D = (int)tm.R;
     const float* th = tm.A1 + (size_t)b * (2 * D + 2);
     return (T)(th[D] * kp_g_rt((int)tm.n2, tm.A0 + ((size_t)b * N + pim) * D, tm.A0 + ((size_t)b * N + i) * D, th, D));
+  } else if (tm.kind == LO_OP_KERNEL_SM_DIAG) {
+    const int D = (int)tm.R, Q = (int)tm.n2;
+    const float* th = tm.A1 + (size_t)b * Q * (2 * D + 1);
+    return (T)ksm_g_rt(tm.A0 + ((size_t)b * N + pim) * D, tm.A0 + ((size_t)b * N + i) * D, th, D, Q);
   } else if (tm.kind == LO_OP_KERNEL_SUM_DIAG) {  // the same per term over the same points, summed in term order
     const int D = (int)tm.R;
     const float* xp = tm.A0 + ((size_t)b * N + pim) * D;
@@ -795,6 +807,7 @@ static int pc_check_desc(const lo_op_desc* op, bool fp32_kinds = true) {
         if (kernel_term_kind(t.kind)) {  // (a term is validated as the kind on its own is)
           if (!fp32_kinds) return LO_ERR_UNSUPPORTED;
           if (t.kind == LO_OP_KERNEL_DIAG) rc = kernel_desc_check(&t);
+          else if (t.kind == LO_OP_KERNEL_SM_DIAG) rc = kernel_sm_desc_check(&t);
           else rc = t.kind == LO_OP_KERNEL_PARAM_DIAG ? kernel_param_desc_check(&t) : kernel_sum_desc_check(&t);
           if (rc) return rc;
         }
@@ -810,6 +823,7 @@ static int pc_check_desc(const lo_op_desc* op, bool fp32_kinds = true) {
     case LO_OP_KERNEL_GRAD_DIAG: rc = kernel_grad_desc_check(op); break;
     case LO_OP_KERNEL_TASK_DIAG: rc = kernel_task_desc_check(op); break;
     case LO_OP_KERNEL_PARAM_DIAG: rc = kernel_param_desc_check(op); break;
+    case LO_OP_KERNEL_SM_DIAG: rc = kernel_sm_desc_check(op); break;
     case LO_OP_SKI_DIAG: rc = ski_desc_check(op); break;
     case LO_OP_SKI_SUM_DIAG: rc = ski_sum_desc_check(op); break;
     // (an empty grid or stencil is refused here ahead of the grid shape; the plan refuses it behind, as a shape)

@@ -35,6 +35,7 @@ class OperatorDescriptor:
     # | theta [B,Q,D+1] (KernelLmc: A0 = X [B,n,D], R = D, n2 = the packed families with Q in bits 16 .. 19 (kernel_lmc_terms),
     #   kernel_terms = T, task = Bt [B,Q,T,T], N = n T)
     # | theta [B,2D+2] (KernelParam: A0 = X [B,N,D], R = D, n2 = LO_KERNEL_RQ / LO_KERNEL_PERIODIC; kernel_param_theta)
+    # | theta [B,Q,2D+1] (KernelSm: A0 = X [B,N,D], R = D, n2 = Q; kernel_sm_theta)
     A1: Optional[torch.Tensor] = None
     d: Optional[torch.Tensor] = None  # [B,N] (FULL) or [B] (CONST)
     diag_mode: int = _hip.LO_DIAG_NONE
@@ -130,7 +131,8 @@ def _check_dtype(dtype, *tensors):
 def sum_descriptor(terms, d: Optional[torch.Tensor] = None, const_diag: bool = False, dtype=torch.float32):
     """SumLinearOperator(A_1, ..., A_n) (+ one diagonal): y = sum_i A_i v + d o v (sum_linear_operator.py:47-51).
     `terms`: 2 .. LO_MAX_TERMS descriptors of kind low-rank / dense / Kronecker / matrix-free kernel (LO_OP_KERNEL_DIAG;
-    float32 sums also LO_OP_KERNEL_SUM_DIAG and LO_OP_KERNEL_PARAM_DIAG) WITHOUT a diagonal, same batch and N, all of the element type `dtype`."""
+    float32 sums also LO_OP_KERNEL_SUM_DIAG, LO_OP_KERNEL_PARAM_DIAG and LO_OP_KERNEL_SM_DIAG) WITHOUT a diagonal, same batch
+    and N, all of the element type `dtype`."""
     terms = tuple(terms)
     for t in terms:
         if t.dtype != dtype:
@@ -763,6 +765,79 @@ def kernel_param_points_grad(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Te
     return g
 
 
+def kernel_sm_theta(weights: torch.Tensor, means: torch.Tensor, scales: torch.Tensor, batch, D: int) -> torch.Tensor:
+    """theta [B, Q, 2 D + 1] of the lo_kernel_sm_* entry points: per mixture the weight, the D means, the D scales, raw
+    values (no inverses).  weights [*b, Q], means and scales [*b, Q, D], all broadcast to `batch`."""
+    with torch.no_grad():
+        Q = weights.shape[-1]
+        w = weights.detach().expand(*batch, Q).reshape(-1, Q, 1)
+        mu = means.detach().expand(*batch, Q, D).reshape(-1, Q, D)
+        sg = scales.detach().expand(*batch, Q, D).reshape(-1, Q, D)
+        return torch.cat((w, mu, sg), -1).to(torch.float32).contiguous()
+
+
+def _kernel_sm_args(what, x1, x2, theta, right, left=None, d=None):
+    """_kernel_args for theta [B, Q, 2 D + 1]: the checked operands and (B, M, N, D, Q, cols)."""
+    if theta.dim() != 3 or theta.shape[-1] != 2 * x1.shape[-1] + 1 or theta.shape[-2] < 1:
+        raise RuntimeError(f"{what}: theta of shape {tuple(theta.shape)} for x1 {tuple(x1.shape)}")
+    Q = theta.shape[-2]
+    x1, x2, flat, _, left, right, (B, M, N, D, _, cols), _ = _kernel_args(what, x1, x2, theta.reshape(theta.shape[0], -1),
+                                                                         right, left, d=d, width=Q * theta.shape[-1])
+    return x1, x2, flat, left, right, (B, M, N, D, Q, cols)
+
+
+def kernel_sm_diag_descriptor(X: torch.Tensor, theta: torch.Tensor, d: Optional[torch.Tensor] = None,
+                              const_diag: bool = False):
+    """AddedDiag(SM(X, X), Diag(d)) (or the kernel matrix alone): y = K(X, X) v + d o v with the spectral mixture K formed
+    on the fly (csrc/lo_kernel_sm.hip), the kind LO_OP_KERNEL_SM_DIAG.  X [*batch, N, D], theta [B, Q, 2 D + 1] from
+    kernel_sm_theta.  None when D or Q exceeds LO_KERNEL_SM_MAX_DIM / LO_KERNEL_SM_MAX_MIX or the batch the sweep's grid
+    (the caller evaluates covar_func)."""
+    _hip.require_hip(X, theta, d)
+    N, D = X.shape[-2:]
+    X3 = _flat(X.detach(), 2)
+    Q = theta.shape[-2] if theta.dim() == 3 else 0
+    if (D > _hip.LO_KERNEL_SM_MAX_DIM or D < 1 or Q > _hip.LO_KERNEL_SM_MAX_MIX or X3.shape[0] > 65535):
+        return None
+    if theta.shape != (X3.shape[0], Q, 2 * D + 1) or Q < 1:
+        raise RuntimeError(f"kernel_sm_diag_descriptor: theta of shape {tuple(theta.shape)} for X {tuple(X.shape)}")
+    return _with_diag(OperatorDescriptor(_hip.LO_OP_KERNEL_SM_DIAG, X3.shape[0], N, A0=X3, A1=theta.contiguous(), R=D,
+                                         n2=Q, batch_shape=X.shape[:-2]), d, const_diag)
+
+
+def kernel_sm_mv(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, v: torch.Tensor,
+                 d: Optional[torch.Tensor] = None, const_diag: bool = False) -> torch.Tensor:
+    """lo_kernel_sm_mv_f32: y [B, M, c] = K(x1, x2) v (+ d o v; d only when M == N), x1 [B, M, D], x2 [B, N, D], theta
+    [B, Q, 2 D + 1], v [B, N, c].  A shape the kernel does not take raises."""
+    x1, x2, theta, _, v, (B, M, N, D, Q, c) = _kernel_sm_args("kernel_sm_mv", x1, x2, theta, v, d=d)
+    d, mode = _kernel_diag(d, B, N, const_diag)
+    y = torch.empty(B, M, c, dtype=torch.float32, device=v.device)
+    name, sizer = _kernel_entry("lo_kernel_sm_mv", False)
+    _launch(name, v.device, x1, x2, theta, Q, B, M, N, D, v, c, d, mode, y, ws_bytes=sizer(B, M, N, D, Q, c))
+    return y
+
+
+def kernel_sm_bilinear(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, U: torch.Tensor,
+                       V: torch.Tensor) -> torch.Tensor:
+    """lo_kernel_sm_bilinear_f32: g_theta [B, Q, 2 D + 1], the derivative of sum_s u_s^T K(x1, x2) v_s with respect to every
+    entry of theta, in theta's layout.  x1 [B, M, D], x2 [B, N, D], U [B, M, t], V [B, N, t]."""
+    x1, x2, theta, U, V, (B, M, N, D, Q, t) = _kernel_sm_args("kernel_sm_bilinear", x1, x2, theta, V, U)
+    g = torch.empty(B, Q, 2 * D + 1, dtype=torch.float32, device=U.device)
+    name, sizer = _kernel_entry("lo_kernel_sm_bilinear", False)
+    _launch(name, U.device, x1, x2, theta, Q, B, M, N, D, U, V, t, g, ws_bytes=sizer(B, M, N, D, Q, t))
+    return g
+
+
+def kernel_sm_points_grad(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, U: torch.Tensor,
+                          V: torch.Tensor) -> torch.Tensor:
+    """lo_kernel_sm_points_grad_f32: g_x1 [B, M, D], the derivative of sum_s u_s^T K(x1, x2) v_s with respect to x1, x2 held
+    fixed.  The derivative with respect to x2 is kernel_sm_points_grad(x2, x1, theta, V, U)."""
+    x1, x2, theta, U, V, (B, M, N, D, Q, t) = _kernel_sm_args("kernel_sm_points_grad", x1, x2, theta, V, U)
+    g = torch.empty(B, M, D, dtype=torch.float32, device=U.device)
+    name, sizer = _kernel_entry("lo_kernel_sm_points_grad", False)
+    _launch(name, U.device, x1, x2, theta, Q, B, M, N, D, U, V, t, g, ws_bytes=sizer(B, M, N, D, Q, t))
+    return g
+
+
 def kernel_sum_theta(lengthscales, outputscales, batch, D: int) -> torch.Tensor:
     """theta [B, T, D + 1] of the fused kernel-sum entry points: per term the D inverse lengthscales (a shared one
     replicated), then outputscale^2 -- kernel_theta of every term, stacked in term order."""
@@ -1043,7 +1118,8 @@ def masked_descriptor(base_desc: OperatorDescriptor, idx: torch.Tensor, d: Optio
     the C side does not take (the caller composes the product)."""
     if base_desc is None or base_desc.kind not in _MASK_BASE_KINDS or base_desc.dtype != torch.float32:
         return None  # (float64 bases: the masked kernels are fp32)
-    if any(t.kind in (_hip.LO_OP_KERNEL_DIAG, _hip.LO_OP_KERNEL_SUM_DIAG, _hip.LO_OP_KERNEL_PARAM_DIAG)
+    if any(t.kind in (_hip.LO_OP_KERNEL_DIAG, _hip.LO_OP_KERNEL_SUM_DIAG, _hip.LO_OP_KERNEL_PARAM_DIAG,
+                      _hip.LO_OP_KERNEL_SM_DIAG)
            for t in base_desc.terms):
         return None  # (a sum's matrix-free kernel terms are not taken under a mask)
     if idx.dtype != torch.int64 or not idx.is_cuda or idx.dim() != 1 or idx.numel() < 1:

@@ -6,7 +6,8 @@ needed (the general path, as in the reference, on any device and in any dtype).
 Native path.  `VARIANTS` below describes every kind of operator the HIP kernels take, one row each: what `covar_func`
 must carry (linear_operator_amd.covariance), the parameters with their shapes, the limit on D and the kernels.py
 wrappers.  One gate body (`_variant_refusal`) reads a row; `_native_refusal`, `_native_f64_refusal`,
-`_native_grad_refusal`, `_native_task_refusal` and `_native_param_refusal` are its five views, and `_native_variant`
+`_native_grad_refusal`, `_native_task_refusal` and `_native_param_refusal` are its five views (`_native_sm_refusal` a sixth,
+over `MIXTURE_VARIANTS`), and `_native_variant`
 returns the one row whose gate passes (no operator passes two).  Inside a gate the matrix is NEVER formed and
 covar_func is not called:
 
@@ -32,6 +33,15 @@ covar_func is not called:
           caller's error: the gate does not synchronise to look, the kernels clamp
   param   rq (`alpha` [*b]) and periodic (`period_length` [*b, 1, D] or [*b, 1, 1]): csrc/lo_kernel_param.hip,
           LO_OP_KERNEL_PARAM_DIAG, also a term of a lowered sum; d p = -nu^2 d nu; the diagonal is outputscale^2
+
+  sm      spectral_mixture, the row of `MIXTURE_VARIANTS` (kept apart: `VARIANTS` holds the rows whose covar_func carries a
+          native_family, this one carries none): `mixture_weights` [*b, Q], `mixture_means` and `mixture_scales`
+          [*b, Q, D], no lengthscale and no outputscale, D and Q at most 16: csrc/lo_kernel_sm.hip,
+          LO_OP_KERNEL_SM_DIAG, also a term of a lowered sum; the sixth gate `_native_sm_refusal`; theta holds the raw
+          values, so d / d theta IS the parameters' gradient; the diagonal is sum_q w_q.  Inside the gate the kernel is
+          always taken, no threshold: its purpose is memory (the dense function forms a [Q, M, N, D] temporary).  The
+          five gates above refuse it with "covar_func has no native_family" / "no native_outputs == '..'", so the Sum
+          fusion, Kronecker and LMC kinds never take one
 
 `_native_refusal` answers a grad, task, param or float64 operator with "more than one output per input", "parameters
 other than lengthscale and outputscale" or "not float32", so the fp32 fusion gates of the Sum, Kronecker and LMC
@@ -76,6 +86,10 @@ class _Variant(NamedTuple):
     bilinear: str
     points_grad: Optional[str]  # None: no native gradients of the points
     descriptor: str
+    # a row whose parameters are not lengthscale / outputscale (+ extras): name -> non-batch dimensions, in the order the
+    # theta builder takes them.  Such a row needs no native_family: its wrappers take (points, theta, vectors)
+    params: Optional[dict] = None
+    max_mix: Optional[str] = None  # the _hip limit on the leading non-batch dimension of the parameters (the mixtures Q)
 
 
 _PLAIN = _Variant("_native_refusal", None, torch.float32, None, "covar_func has no native_family", {}, 0, False, "LO_KERNEL_MAX_DIM",
@@ -96,7 +110,11 @@ _PARAM = _PLAIN._replace(gate="_native_param_refusal", tag="param", families=(_h
                          bilinear="kernel_param_bilinear", points_grad="kernel_param_points_grad",
                          descriptor="kernel_param_diag_descriptor")
 VARIANTS = (_PLAIN, _F64, _GRAD, _TASK, _PARAM)
-_TAGGED = {v.tag: v for v in VARIANTS if v.tag is not None}
+_SM = _Variant("_native_sm_refusal", "sm", torch.float32, None, "", {}, 0, False, "LO_KERNEL_SM_MAX_DIM", "kernel_sm_theta",
+               "kernel_sm_mv", "kernel_sm_bilinear", "kernel_sm_points_grad", "kernel_sm_diag_descriptor",
+               params={"mixture_weights": 1, "mixture_means": 2, "mixture_scales": 2}, max_mix="LO_KERNEL_SM_MAX_MIX")
+MIXTURE_VARIANTS = (_SM,)
+_TAGGED = {v.tag: v for v in (*VARIANTS, *MIXTURE_VARIANTS) if v.tag is not None}
 
 
 def _flat(t: Tensor, bs) -> Tensor:
@@ -176,6 +194,8 @@ class KernelLinearOperator(LinearOperator):
         machine)."""
         if v.tag is not None and getattr(self.covar_func, "native_outputs", None) != v.tag:
             return f"covar_func has no native_outputs == '{v.tag}'"
+        if v.params is not None:
+            return self._mixture_refusal(v, check_device)
         family = getattr(self.covar_func, "native_family", None)
         if family is None or (v.families is not None and family not in v.families):
             return v.no_family
@@ -226,6 +246,32 @@ class KernelLinearOperator(LinearOperator):
             return "not on the device"
         return None
 
+    def _mixture_refusal(self, v: _Variant, check_device: bool) -> Optional[str]:
+        """The rest of the gate of a row with parameters of its own (`v.params`): weights [*b, Q] and per-mixture tables
+        [*b, Q, D], exactly those."""
+        if self.num_outputs_per_input != (1, 1):
+            return "more than one output per input"
+        names = list(v.params)
+        if self.nontensor_params or set(self.tensor_params) != set(names):
+            return "parameters other than " + ", ".join(names[:-1]) + " and " + names[-1]
+        D = self.x1.shape[-1]
+        if D < 1 or self.x2.shape[-1] != D or D > getattr(_hip, v.max_dim):
+            return f"D = {D} beyond {v.max_dim}"
+        batch, nonbatch = self.batch_broadcast_shape, self.num_nonbatch_dimensions
+        Q = self.tensor_params[names[0]].shape[-1]
+        for name, nb in v.params.items():
+            p = self.tensor_params[name]
+            if nonbatch[name] != nb or p.shape != ((*batch, Q) if nb == 1 else (*batch, Q, D)) or Q < 1:
+                return f"{name} of shape {tuple(p.shape)}"
+        if Q > getattr(_hip, v.max_mix):
+            return f"Q = {Q} beyond {v.max_mix}"
+        tensors = [self.x1, self.x2, *(self.tensor_params[name] for name in names)]
+        if any(t.dtype != v.dtype for t in tensors):
+            return "not float32"
+        if check_device and not all(t.is_cuda for t in tensors):
+            return "not on the device"
+        return None
+
     def _native_variant(self, check_device: bool = True) -> Optional[_Variant]:
         """The variant whose gate passes, or None.  No operator passes two gates (grad needs D + 1 outputs per input,
         task and param a third parameter, f64 float64), so one candidate is asked, through its public gate: the row of
@@ -252,6 +298,9 @@ class KernelLinearOperator(LinearOperator):
     def _native_param_refusal(self, check_device: bool = True) -> Optional[str]:
         return self._variant_refusal(_PARAM, check_device)
 
+    def _native_sm_refusal(self, check_device: bool = True) -> Optional[str]:
+        return self._variant_refusal(_SM, check_device)
+
     def _is_native(self) -> bool:
         return self._native_refusal() is None
 
@@ -267,18 +316,28 @@ class KernelLinearOperator(LinearOperator):
     def _is_native_param(self) -> bool:
         return self._native_param_refusal() is None
 
+    def _is_native_sm(self) -> bool:
+        return self._native_sm_refusal() is None
+
     def _same_points(self) -> bool:
         return _same_tensor(self.x1, self.x2)
 
     def _theta(self, v: _Variant, bs):
         """Inside the gate of `v`, for the batch `bs`: (theta of the variant's entry points, the operands between theta
         and the family: (Bt [B, T, T],) of the task variant, else ())."""
+        if v.params is not None:
+            return getattr(K, v.theta)(*(self.tensor_params[name] for name in v.params), bs, self.x1.shape[-1]), ()
         p, extra = self.tensor_params, self._extra(v)
         kw = {} if v.dtype == torch.float32 else {"dtype": v.dtype}
         if extra is not None and extra.rule != "table":
             kw[extra.name] = p[extra.name]
         theta = getattr(K, v.theta)(p["lengthscale"], p["outputscale"], bs, self.x1.shape[-1] - v.ids, **kw)
         return theta, ((_flat(p[extra.name], bs),) if extra is not None and extra.rule == "table" else ())
+
+    def _lead(self, v: _Variant, theta, task=()):
+        """What the wrappers of `v` take between the points and the vectors: theta (, Bt), the family code -- theta alone
+        for a row with parameters of its own."""
+        return (theta,) if v.params is not None else (theta, *task, self.covar_func.native_family)
 
     def _points(self, bs):
         """(x1 [B, M, DX], x2 [B, N, DX]) for the batch `bs`; one tensor when x1 and x2 are the same points."""
@@ -290,6 +349,8 @@ class KernelLinearOperator(LinearOperator):
         X = self.x1.detach()
         X = X if X.shape[:-2] == bs else X.expand(*bs, *X.shape[-2:])
         theta, task = self._theta(v, bs)
+        if v.params is not None:
+            return getattr(K, v.descriptor)(X, theta)
         kw = {} if v.dtype == torch.float32 else {"dtype": v.dtype}
         return getattr(K, v.descriptor)(X, theta, self.covar_func.native_family,
                                         *(t.reshape(*bs, *t.shape[-2:]) for t in task), **kw)
@@ -333,7 +394,7 @@ class KernelLinearOperator(LinearOperator):
         if v is not None and cols.dtype == v.dtype:
             bs = torch.broadcast_shapes(self.batch_shape, cols.shape[:-2])
             theta, task = self._theta(v, bs)
-            y = getattr(K, v.mv)(*self._points(bs), theta, *task, self.covar_func.native_family, _flat(cols, bs))
+            y = getattr(K, v.mv)(*self._points(bs), *self._lead(v, theta, task), _flat(cols, bs))
             y = y.reshape(*bs, *y.shape[-2:])
         else:
             y = self._dense_covar() @ cols.contiguous()
@@ -367,6 +428,8 @@ class KernelLinearOperator(LinearOperator):
         v = self._native_variant(check_device=False) if self._same_points() else None
         if v is not None:  # g(0) = 1 for every native family: from the parameters alone, no kernel launch, no covar_func
             batch = self.batch_broadcast_shape
+            if v.params is not None:  # every mixture is its weight at tau = 0: sum_q w_q
+                return self.tensor_params[next(iter(v.params))].sum(-1, keepdim=True).expand(*batch, n)
             os2 = self.tensor_params["outputscale"].square().unsqueeze(-1)
             if v.block:  # the block of a point with itself is outputscale^2 diag(1, 1 / l_1^2, .., 1 / l_D^2)
                 D = self.x1.shape[-1]
@@ -462,6 +525,15 @@ class KernelLinearOperator(LinearOperator):
     def _theta_to_params(self, v: _Variant, g, theta: Tensor, bs, out: dict) -> None:
         """d / d theta (`g`; the task variant: with d / d Bt) as the gradients of the parameter tensors that ask for one."""
         D = self.x1.shape[-1] - v.ids
+        if v.params is not None:  # theta [B, Q, 2 D + 1] holds the raw values: column 0, then D columns per table
+            lo = 0
+            for name, nb in v.params.items():
+                p, width = self.tensor_params[name], 1 if nb == 1 else D
+                if p.requires_grad:
+                    d_p = g[:, :, lo] if nb == 1 else g[:, :, lo:lo + width]
+                    out[name] = d_p.reshape(*bs, *d_p.shape[1:]).sum_to_size(p.shape)
+                lo += width
+            return
         extra = self._extra(v)
         if extra is not None and extra.rule == "table":
             g, g_table = g
@@ -495,21 +567,20 @@ class KernelLinearOperator(LinearOperator):
         params = [self.tensor_params[n] for n in names]
         if not any(t.requires_grad for t in (self.x1, self.x2, *params)):
             return (None, None) + (None,) * len(names)
-        family = self.covar_func.native_family
         bs = torch.broadcast_shapes(self.batch_shape, left_vecs.shape[:-2], right_vecs.shape[:-2])
         x1, x2 = self._points(bs)
         theta, task = self._theta(v, bs)
         U, V = _flat(left_vecs, bs), _flat(right_vecs, bs)
         out = dict.fromkeys(("x1", "x2", *names))
         if any(t.requires_grad for t in params):
-            self._theta_to_params(v, getattr(K, v.bilinear)(x1, x2, theta, *task, family, U, V), theta, bs, out)
+            self._theta_to_params(v, getattr(K, v.bilinear)(x1, x2, *self._lead(v, theta, task), U, V), theta, bs, out)
         # each side with the other held fixed; x1 and x2 the same leaf: autograd adds the two.  The x2 side is the x1 side
         # of the transposed problem (x1 <-> x2, U <-> V, Bt transposed).
         if self.x1.requires_grad:
-            g = getattr(K, v.points_grad)(x1, x2, theta, *task, family, U, V)
+            g = getattr(K, v.points_grad)(x1, x2, *self._lead(v, theta, task), U, V)
             out["x1"] = g.reshape(*bs, *g.shape[-2:]).sum_to_size(self.x1.shape)
         if self.x2.requires_grad:
-            g = getattr(K, v.points_grad)(x2, x1, theta, *(t.mT for t in task), family, V, U)
+            g = getattr(K, v.points_grad)(x2, x1, *self._lead(v, theta, tuple(t.mT for t in task)), V, U)
             out["x2"] = g.reshape(*bs, *g.shape[-2:]).sum_to_size(self.x2.shape)
         return (out["x1"], out["x2"]) + tuple(out[n] for n in names)
 

@@ -154,8 +154,8 @@ class SumLinearOperator(LinearOperator):
         + at most one diagonal lower to an LO_OP_SUM descriptor -- matvec, CG, Lanczos, MINRES and the pivoted
         Cholesky then run on the device without per-term Python calls.  Native KernelLinearOperators over the same points
         tensor count as ONE term (_kernel_groups): LO_OP_KERNEL_SUM_DIAG, the descriptor itself when they are the whole
-        sum apart from the diagonal; a rational-quadratic or periodic KernelLinearOperator (LO_OP_KERNEL_PARAM_DIAG) is a
-        term of its own.  2 .. LO_KERNEL_MAX_TERMS matrix-free multitask products Kron(Kernel_q, Dense(B_q)) over
+        sum apart from the diagonal; a rational-quadratic or periodic KernelLinearOperator (LO_OP_KERNEL_PARAM_DIAG) and a
+        spectral-mixture one (LO_OP_KERNEL_SM_DIAG) are terms of their own.  2 .. LO_KERNEL_MAX_TERMS matrix-free multitask products Kron(Kernel_q, Dense(B_q)) over
         one points tensor (_lmc_terms) that are the whole sum apart from the diagonal lower to LO_OP_KERNEL_LMC_DIAG."""
         from .. import kernels as K
         from .diag_linear_operator import DiagLinearOperator
@@ -180,7 +180,7 @@ class SumLinearOperator(LinearOperator):
             desc = _group_descriptor(item, batch_shape) if isinstance(item, list) else _term_descriptor(item, batch_shape)
             if desc is None or desc.diag_mode != 0 or desc.kind not in (
                     K._hip.LO_OP_LOWRANK_DIAG, K._hip.LO_OP_DENSE_DIAG, K._hip.LO_OP_KRON_DIAG, K._hip.LO_OP_KERNEL_DIAG,
-                    K._hip.LO_OP_KERNEL_SUM_DIAG, K._hip.LO_OP_KERNEL_PARAM_DIAG):
+                    K._hip.LO_OP_KERNEL_SUM_DIAG, K._hip.LO_OP_KERNEL_PARAM_DIAG, K._hip.LO_OP_KERNEL_SM_DIAG):
                 return None  # (a sum's terms: low-rank / dense / Kronecker / kernel; SKI and Toeplitz terms take the closure)
             terms.append(desc)
         if len(terms) == 1:  # the kernel group is the whole sum
