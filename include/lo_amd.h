@@ -117,6 +117,9 @@ extern "C" {
                                  *   tau = x_i - x_j, formed tile by tile, never stored                                       */
 #define LO_KERNEL_SM_MAX_DIM 16 /* input dimensions D the kind and lo_kernel_sm_* take (more: LO_ERR_UNSUPPORTED)            */
 #define LO_KERNEL_SM_MAX_MIX 16 /* mixtures Q the kind and lo_kernel_sm_* take (more: LO_ERR_UNSUPPORTED)                    */
+#define LO_OP_KERNEL_MGRAD_DIAG 20 /* AddedDiag(Matern52GradKernel(X, X), Diag(d)): the covariance of the values AND the D partial
+                                    * derivatives of a Matern-5/2 GP at n points, the layout of LO_OP_KERNEL_GRAD_DIAG (index
+                                    * i (D + 1) + a), D <= LO_KERNEL_GRAD_MAX_DIM; the matrix is never stored              */
 #define LO_SKI_SUM_MAX_TERMS 64 /* terms P one LO_OP_SKI_SUM_DIAG descriptor / lo_interp_sum_f32 call takes (more: LO_ERR_UNSUPPORTED) */
 
 struct lo_interp_desc;
@@ -262,7 +265,15 @@ typedef struct lo_op_desc {
    * KERNEL_PARAM (SM + RBF + noise is one LO_OP_SUM); the fp64 entry points, the resident / fused engines and the solve
    * sessions return LO_ERR_UNSUPPORTED; not a base kind of LO_OP_MASKED (nor a term of a masked sum); not grouped into
    * KERNEL_SUM.  LO_ERR_BADARG: a null A0 / A1, R < 1, Q < 1; LO_ERR_UNSUPPORTED: D > LO_KERNEL_SM_MAX_DIM, Q >
-   * LO_KERNEL_SM_MAX_MIX, B > 65535, N > 0x7ffffe00; LO_ERR_WORKSPACE: a short workspace.  All before any launch.     */
+   * LO_KERNEL_SM_MAX_MIX, B > 65535, N > 0x7ffffe00; LO_ERR_WORKSPACE: a short workspace.  All before any launch.
+   * ABI 41 kind.  KERNEL_MGRAD: A0 = X [B, n, D], R = D <= LO_KERNEL_GRAD_MAX_DIM, A1 = theta [B, D + 1] exactly as for
+   * KERNEL (the D inverse lengthscales, then outputscale^2), N = n (D + 1); n2 is not read (the family is Matern-5/2).
+   * Lowered for lo_matvec_f32, the streaming CG, Lanczos, fp32 MINRES and the fp32 pivoted Cholesky (diagonal theta[D] in
+   * a value row and (5 / 3) theta[D] theta[a - 1]^2 in the row of derivative a; row (p, al): the block formula of
+   * lo_kernel_mgrad_mv_f32); the fp64 entry points, the resident / fused engines and the solve sessions return
+   * LO_ERR_UNSUPPORTED; not a term of LO_OP_SUM and not a base of LO_OP_MASKED.  LO_ERR_BADARG: a null A0 / A1, R < 1,
+   * N % (R + 1) != 0; LO_ERR_UNSUPPORTED: D > LO_KERNEL_GRAD_MAX_DIM, B > 65535, N > 0x7ffffe00; LO_ERR_WORKSPACE: a short
+   * workspace.  All before any launch.                                                                                */
 } lo_op_desc;
 
 /* The grid shape of an LO_OP_TOEPLITZ_KRON_DIAG descriptor (host struct). */
@@ -1282,6 +1293,33 @@ int lo_kernel_sm_bilinear_f32(const float* x1, const float* x2, const float* the
 size_t lo_kernel_sm_points_grad_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t D, int64_t Q, int64_t t);
 int lo_kernel_sm_points_grad_f32(const float* x1, const float* x2, const float* theta, int32_t Q, int64_t B, int64_t M,
                                  int64_t N, int64_t D, const float* U, const float* V, int64_t t, float* g_x1, void* ws,
+                                 size_t ws_bytes, void* stream);
+
+/* ---- matrix-free derivative GP: the Matern-5/2 gradient kernel (ABI 41; csrc/lo_kernel_mgrad.hip) ---------------------
+ * y [B, M (D + 1), c] = K(x1, x2) v (+ d o v) for the block matrix of LO_OP_KERNEL_MGRAD_DIAG, rows i (D + 1) + a over
+ * x1 [B, M, D], columns j (D + 1) + b over x2 [B, N, D], theta [B, D + 1] as for lo_kernel_mv_f32.  With t_k = theta[k],
+ * u_k = t_k x1[i,k] - t_k x2[j,k], r = |u|, s = sqrt(5) r, E = exp(-s):
+ *   g0 = (1 + s + s^2 / 3) E    g1 = (5 / 3) (1 + s) E    g2 = (25 / 3) E
+ *   K[0,0] = theta[D] g0             K[0,b] = theta[D] t_b u_b g1
+ *   K[a,0] = -theta[D] t_a u_a g1    K[a,b] = theta[D] t_a t_b (g1 delta_ab - g2 u_a u_b)
+ * one square root and one exponential per pair; finite at r = 0 (the block of a point with itself is theta[D] diag(1,
+ * (5 / 3) t_1^2, .., (5 / 3) t_D^2)).  The sweep, the split of few-row shapes and the fixed-order sums are those of
+ * lo_kernel_grad_mv_f32: two calls give equal bits.  Rectangular x1 != x2 is the prediction case; d (per diag_mode) only
+ * when M == N.
+ * lo_kernel_mgrad_bilinear_f32: g_theta [B, D + 1] = d / d theta of S = sum_s U[:, s]^T K(x1, x2) V[:, s], U [B, M (D + 1),
+ * t], V [B, N (D + 1), t], in the meaning of lo_kernel_bilinear_f32.  The third radial derivative carries 1 / r; it is
+ * taken as 0 for a pair with r^2 <= 1e-30, where it multiplies terms of order r^4.
+ * LO_ERR_BADARG: a null pointer, a size < 1, an unknown diag_mode, a mode without d, a mode other than LO_DIAG_NONE
+ * with M != N; LO_ERR_UNSUPPORTED: D > LO_KERNEL_GRAD_MAX_DIM, B > 65535, M (D + 1) or N (D + 1) > 0x7ffffe00, c or t >
+ * 0x7fffffff / (D + 1); LO_ERR_WORKSPACE: a short workspace.  In this order, all before any launch.  The sizers return 0
+ * for arguments the call would refuse.                                                                                */
+size_t lo_kernel_mgrad_mv_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t D, int64_t c);
+int lo_kernel_mgrad_mv_f32(const float* x1, const float* x2, const float* theta, int64_t B, int64_t M, int64_t N, int64_t D,
+                           const float* v, int64_t c, const float* d, int32_t diag_mode, float* y, void* ws,
+                           size_t ws_bytes, void* stream);
+size_t lo_kernel_mgrad_bilinear_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t D, int64_t t);
+int lo_kernel_mgrad_bilinear_f32(const float* x1, const float* x2, const float* theta, int64_t B, int64_t M, int64_t N,
+                                 int64_t D, const float* U, const float* V, int64_t t, float* g_theta, void* ws,
                                  size_t ws_bytes, void* stream);
 
 /* ---- exact small-N path: batched Cholesky and triangular solves (ABI 18; csrc/lo_chol.hip) -------------------------

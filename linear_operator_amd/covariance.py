@@ -19,6 +19,15 @@ convention `f(x1, x2, lengthscale, outputscale)` (the `covar_func` of the refere
                   K[a,0] = -os^2 t_a u_a e   K[a,b] = os^2 t_a t_b (delta_ab - u_a u_b) e
               (pass num_outputs_per_input=(D + 1, D + 1) to the operator)
 
+    matern52_grad  the same for a Matern-5/2 GP (GPyTorch's Matern52KernelGrad), same layout and the same call.  With
+              s = sqrt(5) r, E = exp(-s) and three radial factors where rbf_grad has one,
+                  g0 = (1 + s + s^2 / 3) E    g1 = (5 / 3) (1 + s) E    g2 = (25 / 3) E
+                  K[0,0] = os^2 g0             K[0,b] = os^2 t_b u_b g1
+                  K[a,0] = -os^2 t_a u_a g1    K[a,b] = os^2 t_a t_b (g1 delta_ab - g2 u_a u_b)
+              nothing is singular at r = 0: the block of a point with itself is os^2 diag(1, (5 / 3) t_1^2, ..).  It
+              carries `native_outputs = "mgrad"` and NO native_family: csrc/lo_kernel_mgrad.hip has entry points and a
+              kind of its own, and every gate that asks for a family refuses it.
+
     *_task    rbf_task, matern12_task, matern32_task, matern52_task: the task-indexed ("Hadamard") multitask kernel,
               `f(x1, x2, lengthscale, outputscale, task_covar)`.  x [..., N, D + 1]: columns 0 .. D - 1 the coordinates,
               column D the task id of the observation, an integer 0 .. T - 1 stored as a float; lengthscale [..., 1, D]
@@ -114,6 +123,26 @@ def rbf_grad(x1: Tensor, x2: Tensor, lengthscale: Tensor, outputscale: Tensor) -
     return K.transpose(-3, -2).reshape(*K.shape[:-4], M * (D + 1), N * (D + 1))
 
 
+def matern52_grad(x1: Tensor, x2: Tensor, lengthscale: Tensor, outputscale: Tensor) -> Tensor:
+    D = x1.shape[-1]
+    u = (x1 / lengthscale).unsqueeze(-2) - (x2 / lengthscale).unsqueeze(-3)  # [..., M, N, D], scaled, then differenced
+    r2 = u.square().sum(-1)
+    s = math.sqrt(5.0) * _dist(r2)
+    e = _scale(outputscale) * torch.exp(-s)  # [..., M, N]
+    g0 = (1.0 + s + (5.0 / 3.0) * r2) * e
+    g1 = (5.0 / 3.0) * (1.0 + s) * e
+    g2 = (25.0 / 3.0) * e
+    theta = (1.0 / lengthscale).expand(*lengthscale.shape[:-1], D)  # [..., 1, D]
+    tu = theta.unsqueeze(-3) * u  # t_b u_b
+    inner = (g1[..., None, None] * torch.diag_embed(theta.square()).unsqueeze(-3)
+             - g2[..., None, None] * (tu.unsqueeze(-1) * tu.unsqueeze(-2)))  # [..., M, N, D, D]
+    edge = g1.unsqueeze(-1) * tu  # [..., M, N, D]
+    top = torch.cat((g0.unsqueeze(-1), edge), -1).unsqueeze(-2)  # [..., M, N, 1, D + 1]
+    K = torch.cat((top, torch.cat((-edge.unsqueeze(-1), inner), -1)), -2)  # [..., M, N, D + 1, D + 1]
+    M, N = K.shape[-4:-2]
+    return K.transpose(-3, -2).reshape(*K.shape[:-4], M * (D + 1), N * (D + 1))
+
+
 def _task_gather(x1: Tensor, x2: Tensor, task_covar: Tensor) -> Tensor:
     """task_covar[t_i, t_j] [..., M, N] for the ids in the last columns of x1 and x2."""
     t1, t2 = x1[..., -1].long(), x2[..., -1].long()
@@ -177,10 +206,14 @@ periodic.native_family = _hip.LO_KERNEL_PERIODIC
 rq.native_outputs = periodic.native_outputs = "param"
 
 spectral_mixture.native_outputs = "sm"  # (and no native_family)
+matern52_grad.native_outputs = "mgrad"  # (and no native_family)
 
 FAMILIES = {"rbf": rbf, "matern12": matern12, "matern32": matern32, "matern52": matern52}
 # gradient kernels (D + 1 outputs per input): kept apart, FAMILIES holds the one-output families only
 GRAD_FAMILIES = {"rbf_grad": rbf_grad}
+
+# gradient kernels with entry points of their own (no family code): kept apart as well
+MGRAD_FAMILIES = {"matern52_grad": matern52_grad}
 
 # task-indexed multitask kernels (one more parameter, task_covar): kept apart as well
 TASK_FAMILIES = {"rbf_task": rbf_task, "matern12_task": matern12_task, "matern32_task": matern32_task,
@@ -192,6 +225,6 @@ PARAM_FAMILIES = {"rq": rq, "periodic": periodic}
 # mixtures of products over the dimensions (no lengthscale, no outputscale, no family code): kept apart as well
 MIXTURE_FAMILIES = {"spectral_mixture": spectral_mixture}
 
-__all__ = ["rbf", "matern12", "matern32", "matern52", "rbf_grad", "rbf_task", "matern12_task", "matern32_task",
+__all__ = ["rbf", "matern12", "matern32", "matern52", "rbf_grad", "matern52_grad", "rbf_task", "matern12_task", "matern32_task",
            "matern52_task", "rq", "periodic", "spectral_mixture", "scaled_sq_dist", "FAMILIES", "GRAD_FAMILIES",
-           "TASK_FAMILIES", "PARAM_FAMILIES", "MIXTURE_FAMILIES"]
+           "MGRAD_FAMILIES", "TASK_FAMILIES", "PARAM_FAMILIES", "MIXTURE_FAMILIES"]

@@ -294,6 +294,11 @@ int kernel_grad_plan(MatvecPlan* pl, Arena* ar, hipStream_t st);
 int kernel_grad_matvec_run(const MatvecPlan* pl, const float* v, float* y, const int* stop, hipStream_t st);
 int kernel_grad_desc_check(const lo_op_desc* op);
 
+// ---- matrix-free Matern-5/2 gradient kernel (lo_kernel_mgrad.hip): LO_OP_KERNEL_MGRAD_DIAG, on KernelGradPlan (its `part`)
+int kernel_mgrad_plan(MatvecPlan* pl, Arena* ar, hipStream_t st);
+int kernel_mgrad_matvec_run(const MatvecPlan* pl, const float* v, float* y, const int* stop, hipStream_t st);
+int kernel_mgrad_desc_check(const lo_op_desc* op);
+
 // ---- matrix-free task-indexed multitask operator (lo_kernel_task.hip): LO_OP_KERNEL_TASK_DIAG ----------------------------
 struct KernelTaskPlan {
   float* part;  // [js, B, N, c] partial products when the columns j of a member are split over js workgroups, else nullptr

@@ -122,6 +122,27 @@ __device__ __forceinline__ float kf_grad_pair(float r2) {
   return kf_g<LO_KERNEL_RBF>(r2);
 }
 
+// The pair function of the Matern-5/2 gradient kernel (LO_OP_KERNEL_MGRAD_DIAG: lo_kernel_mgrad.hip, lo_pivchol.hip): the
+// three radial factors of the block above for g = (1 + s + s^2 / 3) E, s = sqrt(5) r, E = exp(-s):
+//   g0 = g,  g1 = -2 dg / d(r^2) = (5 / 3) (1 + s) E,  g2 = -2 dg1 / d(r^2) = (25 / 3) E
+// from one v_sqrt_f32 and one v_exp_f32.  Nothing is singular at r = 0 (g0 = 1, g1 = 5 / 3, g2 = 25 / 3).
+__device__ __forceinline__ void kf_mgrad_pair(float r2, float* g0, float* g1, float* g2) {
+  const float r2c = fminf(r2, kKfMaxR2);
+  const float r = __builtin_amdgcn_sqrtf(r2c);
+  const float e = kf_exp2(r * (-kKfSqrt5 * kKfLog2e));
+  const float lin = fmaf(kKfSqrt5, r, 1.0f);
+  *g0 = fmaf(5.0f / 3.0f, r2c, lin) * e;
+  *g1 = (5.0f / 3.0f) * lin * e;
+  *g2 = (25.0f / 3.0f) * e;
+}
+// the same with g3 = -2 dg2 / d(r^2) = (25 sqrt(5) / 3) E / r, the one factor with 1 / r: taken as 0 for r^2 <= 1e-30
+// (covariance._R2_FLOOR: a coincident pair; the callers multiply it by terms of order r^4)
+__device__ __forceinline__ void kf_mgrad_pair3(float r2, float* g0, float* g1, float* g2, float* g3) {
+  kf_mgrad_pair(r2, g0, g1, g2);
+  const float r2c = fminf(r2, kKfMaxR2);
+  *g3 = r2c > 1e-30f ? (kKfSqrt5 * *g2) * __builtin_amdgcn_rsqf(r2c) : 0.0f;
+}
+
 // ---- the families with a shape parameter (LO_OP_KERNEL_PARAM_DIAG: lo_kernel_param.hip, lo_pivchol.hip) -----------------
 // Rational quadratic, g = (1 + q)^(-alpha) with q = r^2 / (2 alpha): one v_log_f32 and one v_exp_f32, alpha and
 // inv2a = 1 / (2 alpha) uniform over the workgroup.  The clamp keeps q / (1 + q) finite when r^2 overflows.

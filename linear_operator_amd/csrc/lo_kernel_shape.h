@@ -136,6 +136,14 @@ using kg_cols = std::conditional_t<DP <= 4, std::integer_sequence<int, 4, 2, 1>,
 // columns of U / V one sweep of its derivative carries: the thread keeps DP + 1 scaled entries of U per column in registers
 constexpr int kg_bil_cols(int DP) { return DP <= 4 ? kKoTS : (DP <= 8 ? 4 : 2); }
 
+// Matern-5/2 gradient kernel (lo_kernel_mgrad.hip), by the padded dimension (kg_dims): the sums of the RBF gradient kernel
+// plus three radial factors instead of one, and every instantiation still stays at 3 waves per SIMD without scratch
+// (product: 61 / 76 / 110 VGPRs at DP 4, 95 / 124 at DP 8, 167 at DP 16; derivative: 162 / 161 / 164)
+inline int km_col_chunk(int DP, int64_t c) { return kg_col_chunk(DP, c); }
+template <int DP>
+using km_cols = kg_cols<DP>;
+constexpr int km_bil_cols(int DP) { return DP <= 4 ? kKoTS : (DP <= 8 ? 4 : 2); }
+
 // the single-term product on validated arguments (lo_kernel_op.hip); tstride: floats between two members' thetas;
 // part: [js, B, M, c] floats when ko_shape(B, M, N).js > 1 (else unused)
 int kernel_mv_run(const float* x1, const float* x2, const float* theta, int64_t tstride, int family, int64_t B, int64_t M,

@@ -41,6 +41,8 @@
 //   KERNEL_GRAD    the (al, be) entry of the RBF value / derivative block of the points p, j; diag os2, os2 t_a^2
 //                  (no operator of the reference: include/lo_amd.h, lo_kernel_grad_mv_f32) -- its own loop: that of
 //                  kern_r2, which also keeps the scaled differences of the coordinates al, be
+//   KERNEL_MGRAD   the same entry of the Matern-5/2 block, three radial factors g0, g1, g2 (kf_mgrad_pair); diag os2,
+//                  (5 / 3) os2 t_a^2 (no operator of the reference: include/lo_amd.h, lo_kernel_mgrad_mv_f32)
 // Integer results (pivots, permutation) must match the CPU path bit for bit, so every value that feeds
 // a pivot decision is computed per element in a FIXED order with individually rounded operations
 // (products rounded before summation, sequential in r and in j; this file is compiled with
@@ -275,6 +277,10 @@ __device__ __forceinline__ T src_diag(const PcDevT<T>& d, const lo_op_desc& op, 
     const int D = (int)op.R, a = i % (D + 1);
     const float* th = op.A1 + (size_t)b * (D + 1);
     return (T)(a == 0 ? th[D] : th[D] * (th[a - 1] * th[a - 1]));
+  } else if (op.kind == LO_OP_KERNEL_MGRAD_DIAG) {  // row i = (p, a): os2 g0(0) = os2, os2 t_a^2 g1(0) = (5 / 3) os2 t_a^2
+    const int D = (int)op.R, a = i % (D + 1);
+    const float* th = op.A1 + (size_t)b * (D + 1);
+    return (T)(a == 0 ? th[D] : (th[D] * (5.0f / 3.0f)) * (th[a - 1] * th[a - 1]));
   } else if (op.kind == LO_OP_TOEPLITZ_KRON_DIAG) {
     return grid_t0(grid_cols(d, op.A0, b));
   } else if (op.kind == LO_OP_SKI_DIAG || op.kind == LO_OP_SKI_GRID_DIAG) {
@@ -376,6 +382,26 @@ __device__ __forceinline__ T src_entry(const PcDevT<T>& d, const lo_op_desc& tm,
     else if (be == 0) f = -(th[al - 1] * ua);
     else f = (th[al - 1] * th[be - 1]) * ((al == be ? 1.0f : 0.0f) - ua * ub);
     return (T)(e * f);
+  } else if (tm.kind == LO_OP_KERNEL_MGRAD_DIAG) {  // pivot (p, al), entry (j, be): the block formula of lo_amd.h
+    const int D = (int)tm.R, nt = D + 1;
+    const int n = N / nt, pp = pim / nt, al = pim - pp * nt, jj = i / nt, be = i - jj * nt;
+    const float* th = tm.A1 + (size_t)b * nt;
+    const float* xp = tm.A0 + ((size_t)b * n + pp) * D;
+    const float* xi = tm.A0 + ((size_t)b * n + jj) * D;
+    float r2 = 0.0f, ua = 0.0f, ub = 0.0f;  // the loop of kern_r2, keeping the differences u of the coordinates al, be
+    for (int k = 0; k < D; ++k) {
+      const float df = xp[k] * th[k] - xi[k] * th[k];
+      r2 = r2 + df * df;
+      if (k + 1 == al) ua = df;
+      if (k + 1 == be) ub = df;
+    }
+    float g0, g1, g2;
+    kf_mgrad_pair(r2, &g0, &g1, &g2);
+    float f;
+    if (al == 0) f = be == 0 ? g0 : (th[be - 1] * ub) * g1;
+    else if (be == 0) f = -((th[al - 1] * ua) * g1);
+    else f = (th[al - 1] * th[be - 1]) * ((al == be ? g1 : 0.0f) - g2 * (ua * ub));
+    return (T)(th[D] * f);
   } else if (tm.kind == LO_OP_TOEPLITZ_KRON_DIAG) {
     const GridCols<T> g = grid_cols(d, tm.A0, b);
     return grid_base(g, grid_pt(g, pim), grid_pt(g, i));
@@ -824,6 +850,7 @@ static int pc_check_desc(const lo_op_desc* op, bool fp32_kinds = true) {
     case LO_OP_KERNEL_TASK_DIAG: rc = kernel_task_desc_check(op); break;
     case LO_OP_KERNEL_PARAM_DIAG: rc = kernel_param_desc_check(op); break;
     case LO_OP_KERNEL_SM_DIAG: rc = kernel_sm_desc_check(op); break;
+    case LO_OP_KERNEL_MGRAD_DIAG: rc = kernel_mgrad_desc_check(op); break;
     case LO_OP_SKI_DIAG: rc = ski_desc_check(op); break;
     case LO_OP_SKI_SUM_DIAG: rc = ski_sum_desc_check(op); break;
     // (an empty grid or stencil is refused here ahead of the grid shape; the plan refuses it behind, as a shape)

@@ -1044,6 +1044,50 @@ def kernel_grad_bilinear(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor
     return g
 
 
+def kernel_mgrad_diag_descriptor(X: torch.Tensor, theta: torch.Tensor, d: Optional[torch.Tensor] = None,
+                                 const_diag: bool = False):
+    """AddedDiag(Matern52GradKernel(X, X), Diag(d)) (or the operator alone): the covariance of the values and the D partial
+    derivatives of a Matern-5/2 GP at the n points, row index i (D + 1) + a, formed pair by pair (csrc/lo_kernel_mgrad.hip).
+    X [*batch, n, D], theta [B, D + 1] from kernel_theta, d over the n (D + 1) rows.  None when D exceeds
+    LO_KERNEL_GRAD_MAX_DIM (the caller evaluates covar_func)."""
+    _hip.require_hip(X, theta, d)
+    n, D = X.shape[-2:]
+    if D > _hip.LO_KERNEL_GRAD_MAX_DIM or D < 1:
+        return None
+    X3 = _flat(X.detach(), 2)
+    if theta.shape != (X3.shape[0], D + 1):
+        raise RuntimeError(f"kernel_mgrad_diag_descriptor: theta of shape {tuple(theta.shape)} for X {tuple(X.shape)}")
+    return _with_diag(OperatorDescriptor(_hip.LO_OP_KERNEL_MGRAD_DIAG, X3.shape[0], n * (D + 1), A0=X3, A1=theta, R=D,
+                                         batch_shape=X.shape[:-2]), d, const_diag)
+
+
+def kernel_mgrad_mv(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, v: torch.Tensor,
+                    d: Optional[torch.Tensor] = None, const_diag: bool = False) -> torch.Tensor:
+    """lo_kernel_mgrad_mv_f32: y [B, M (D + 1), c] = K(x1, x2) v (+ d o v, only when M == N) for the Matern-5/2 gradient
+    kernel's block matrix, x1 [B, M, D], x2 [B, N, D], theta [B, D + 1], v [B, N (D + 1), c].  A shape the kernel does not
+    take raises."""
+    x1, x2, theta, _, _, v, (B, M, N, D, _, c), _ = _kernel_args("kernel_mgrad_mv", x1, x2, theta, v, d=d,
+                                                                  block=x1.shape[-1] + 1)
+    d, mode = _kernel_diag(d, B, M * (D + 1), const_diag)
+    y = torch.empty(B, M * (D + 1), c, dtype=torch.float32, device=v.device)
+    name, sizer = _kernel_entry("lo_kernel_mgrad_mv", False)
+    _launch(name, v.device, x1, x2, theta, B, M, N, D, v, c, d, mode, y, ws_bytes=sizer(B, M, N, D, c))
+    return y
+
+
+def kernel_mgrad_bilinear(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, U: torch.Tensor,
+                          V: torch.Tensor) -> torch.Tensor:
+    """lo_kernel_mgrad_bilinear_f32: g_theta [B, D + 1], the derivative of sum_s u_s^T K(x1, x2) v_s with respect to theta
+    (the inverse lengthscales, then outputscale^2) for the Matern-5/2 gradient kernel's block matrix.  x1 [B, M, D],
+    x2 [B, N, D], U [B, M (D + 1), t], V [B, N (D + 1), t]."""
+    x1, x2, theta, _, U, V, (B, M, N, D, _, t), _ = _kernel_args("kernel_mgrad_bilinear", x1, x2, theta, V, U,
+                                                                  block=x1.shape[-1] + 1)
+    g = torch.empty(B, D + 1, dtype=torch.float32, device=U.device)
+    name, sizer = _kernel_entry("lo_kernel_mgrad_bilinear", False)
+    _launch(name, U.device, x1, x2, theta, B, M, N, D, U, V, t, g, ws_bytes=sizer(B, M, N, D, t))
+    return g
+
+
 def kernel_task_diag_descriptor(X: torch.Tensor, theta: torch.Tensor, family: int, task: torch.Tensor,
                                 d: Optional[torch.Tensor] = None, const_diag: bool = False):
     """AddedDiag(TaskKernel(X, X, family), Diag(d)) (or the operator alone), the task-indexed multitask covariance

@@ -7,7 +7,7 @@ Native path.  `VARIANTS` below describes every kind of operator the HIP kernels 
 must carry (linear_operator_amd.covariance), the parameters with their shapes, the limit on D and the kernels.py
 wrappers.  One gate body (`_variant_refusal`) reads a row; `_native_refusal`, `_native_f64_refusal`,
 `_native_grad_refusal`, `_native_task_refusal` and `_native_param_refusal` are its five views (`_native_sm_refusal` a sixth,
-over `MIXTURE_VARIANTS`), and `_native_variant`
+over `MIXTURE_VARIANTS`, `_native_mgrad_refusal` a seventh, over `BLOCK_VARIANTS`), and `_native_variant`
 returns the one row whose gate passes (no operator passes two).  Inside a gate the matrix is NEVER formed and
 covar_func is not called:
 
@@ -42,6 +42,15 @@ covar_func is not called:
           always taken, no threshold: its purpose is memory (the dense function forms a [Q, M, N, D] temporary).  The
           five gates above refuse it with "covar_func has no native_family" / "no native_outputs == '..'", so the Sum
           fusion, Kronecker and LMC kinds never take one
+
+  mgrad   matern52_grad with num_outputs_per_input (D + 1, D + 1), the row of `BLOCK_VARIANTS` (kept apart for the reason
+          the sm row is: covar_func carries no native_family): lengthscale and outputscale as in the grad row, D at most
+          16: csrc/lo_kernel_mgrad.hip, LO_OP_KERNEL_MGRAD_DIAG (not a term of a lowered sum); the seventh gate
+          `_native_mgrad_refusal`; the diagonal is outputscale^2 (1, 5 / (3 l_1^2), .., 5 / (3 l_D^2)) per point.  The
+          parameters' gradients come from lo_kernel_mgrad_bilinear_f32; gradients with respect to the POINTS keep the
+          general path (a derivative call that asks for them takes it whole), and `_getitem` treats slices of whole
+          points as the grad row does.  Inside the gate the kernel is always taken, no threshold: its purpose is
+          memory, as for rbf_grad
 
 `_native_refusal` answers a grad, task, param or float64 operator with "more than one output per input", "parameters
 other than lengthscale and outputscale" or "not float32", so the fp32 fusion gates of the Sum, Kronecker and LMC
@@ -90,6 +99,8 @@ class _Variant(NamedTuple):
     # theta builder takes them.  Such a row needs no native_family: its wrappers take (points, theta, vectors)
     params: Optional[dict] = None
     max_mix: Optional[str] = None  # the _hip limit on the leading non-batch dimension of the parameters (the mixtures Q)
+    has_family: bool = True        # False: covar_func carries no native_family and the wrappers take no family code
+    self_slope: float = 1.0        # a block row: g1(0), the factor of outputscale^2 / l_a^2 in derivative slot a of the diagonal
 
 
 _PLAIN = _Variant("_native_refusal", None, torch.float32, None, "covar_func has no native_family", {}, 0, False, "LO_KERNEL_MAX_DIM",
@@ -114,7 +125,11 @@ _SM = _Variant("_native_sm_refusal", "sm", torch.float32, None, "", {}, 0, False
                "kernel_sm_mv", "kernel_sm_bilinear", "kernel_sm_points_grad", "kernel_sm_diag_descriptor",
                params={"mixture_weights": 1, "mixture_means": 2, "mixture_scales": 2}, max_mix="LO_KERNEL_SM_MAX_MIX")
 MIXTURE_VARIANTS = (_SM,)
-_TAGGED = {v.tag: v for v in (*VARIANTS, *MIXTURE_VARIANTS) if v.tag is not None}
+_MGRAD = _GRAD._replace(gate="_native_mgrad_refusal", tag="mgrad", families=None, no_family="", mv="kernel_mgrad_mv",
+                        bilinear="kernel_mgrad_bilinear", descriptor="kernel_mgrad_diag_descriptor", has_family=False,
+                        self_slope=5.0 / 3.0)
+BLOCK_VARIANTS = (_MGRAD,)
+_TAGGED = {v.tag: v for v in (*VARIANTS, *MIXTURE_VARIANTS, *BLOCK_VARIANTS) if v.tag is not None}
 
 
 def _flat(t: Tensor, bs) -> Tensor:
@@ -186,7 +201,7 @@ class KernelLinearOperator(LinearOperator):
 
     # ------------------------------------------------------------------ the gates of the native path
     def _extra(self, v: _Variant) -> Optional[_Extra]:
-        return v.extras.get(self.covar_func.native_family, v.extras.get(None))
+        return v.extras.get(getattr(self.covar_func, "native_family", None), v.extras.get(None))
 
     def _variant_refusal(self, v: _Variant, check_device: bool = True) -> Optional[str]:
         """None when the native kernels of the variant `v` take this operator, else the reason they do not.
@@ -197,7 +212,7 @@ class KernelLinearOperator(LinearOperator):
         if v.params is not None:
             return self._mixture_refusal(v, check_device)
         family = getattr(self.covar_func, "native_family", None)
-        if family is None or (v.families is not None and family not in v.families):
+        if v.has_family and (family is None or (v.families is not None and family not in v.families)):
             return v.no_family
         DX = self.x1.shape[-1]
         D = DX - v.ids
@@ -301,6 +316,9 @@ class KernelLinearOperator(LinearOperator):
     def _native_sm_refusal(self, check_device: bool = True) -> Optional[str]:
         return self._variant_refusal(_SM, check_device)
 
+    def _native_mgrad_refusal(self, check_device: bool = True) -> Optional[str]:
+        return self._variant_refusal(_MGRAD, check_device)
+
     def _is_native(self) -> bool:
         return self._native_refusal() is None
 
@@ -319,6 +337,9 @@ class KernelLinearOperator(LinearOperator):
     def _is_native_sm(self) -> bool:
         return self._native_sm_refusal() is None
 
+    def _is_native_mgrad(self) -> bool:
+        return self._native_mgrad_refusal() is None
+
     def _same_points(self) -> bool:
         return _same_tensor(self.x1, self.x2)
 
@@ -336,8 +357,8 @@ class KernelLinearOperator(LinearOperator):
 
     def _lead(self, v: _Variant, theta, task=()):
         """What the wrappers of `v` take between the points and the vectors: theta (, Bt), the family code -- theta alone
-        for a row with parameters of its own."""
-        return (theta,) if v.params is not None else (theta, *task, self.covar_func.native_family)
+        for a row with parameters of its own or without a family."""
+        return (theta,) if v.params is not None or not v.has_family else (theta, *task, self.covar_func.native_family)
 
     def _points(self, bs):
         """(x1 [B, M, DX], x2 [B, N, DX]) for the batch `bs`; one tensor when x1 and x2 are the same points."""
@@ -349,7 +370,7 @@ class KernelLinearOperator(LinearOperator):
         X = self.x1.detach()
         X = X if X.shape[:-2] == bs else X.expand(*bs, *X.shape[-2:])
         theta, task = self._theta(v, bs)
-        if v.params is not None:
+        if v.params is not None or not v.has_family:
             return getattr(K, v.descriptor)(X, theta)
         kw = {} if v.dtype == torch.float32 else {"dtype": v.dtype}
         return getattr(K, v.descriptor)(X, theta, self.covar_func.native_family,
@@ -431,9 +452,11 @@ class KernelLinearOperator(LinearOperator):
             if v.params is not None:  # every mixture is its weight at tau = 0: sum_q w_q
                 return self.tensor_params[next(iter(v.params))].sum(-1, keepdim=True).expand(*batch, n)
             os2 = self.tensor_params["outputscale"].square().unsqueeze(-1)
-            if v.block:  # the block of a point with itself is outputscale^2 diag(1, 1 / l_1^2, .., 1 / l_D^2)
+            if v.block:  # the block of a point with itself is outputscale^2 diag(1, g1(0) / l_1^2, .., g1(0) / l_D^2)
                 D = self.x1.shape[-1]
                 inv2 = (1.0 / self.tensor_params["lengthscale"]).square().expand(*batch, 1, D)[..., 0, :]
+                if v.self_slope != 1.0:
+                    inv2 = v.self_slope * inv2
                 per = torch.cat((torch.ones_like(inv2[..., :1]), inv2), -1) * os2
                 return per.unsqueeze(-2).expand(*batch, n, D + 1).reshape(*batch, n * (D + 1))
             if v.ids:  # outputscale^2 task_covar[t_i, t_i], the table's diagonal gathered at the ids
@@ -483,10 +506,11 @@ class KernelLinearOperator(LinearOperator):
         return self._rebuild(x1, x2, params)
 
     def _whole_point_slices(self, row_index, col_index):
-        """Inside the gradient gate: the slices over the POINTS that two step-free slices of whole points select
+        """Inside a gradient gate (grad, mgrad): the slices over the POINTS that two step-free slices of whole points select
         (kernel_linear_operator.py:300-340 of the reference divides such slices by the outputs per input); None for
         anything else, which is indexed densely."""
-        if self._native_grad_refusal(check_device=False) is not None:
+        v = self._native_variant(check_device=False)
+        if v is None or not v.block:
             return None
         out = []
         for index, size, per in zip((row_index, col_index), self.shape[-2:], self.num_outputs_per_input):
