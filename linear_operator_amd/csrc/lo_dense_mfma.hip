@@ -7,12 +7,12 @@
 // Workgroup = 64 rows x all N; loop over K in slabs of 128 columns (512 contiguous bytes per row: DRAM locality);
 // waves = 2 row tiles x 2 k-halves, the k-halves are summed through LDS at the end:
 //   global -> registers (next slab, issued before the MFMAs of the current one) -> LDS:
-//     K slab [128 rows][64 k], row stride 68 floats: float4 stores stay aligned and the ds_read_b128 of the A
+//     K slab [64 rows][128 k], row stride 132 floats: float4 stores stay aligned and the ds_read_b128 of the A
 //     operand (lane = row) is bank-conflict free (4 * row mod 64 distinct within a 16-lane group);
-//     v slab [64 k][32 cols] (columns >= c zero).
-//   wave w owns rows 32 w .. 32 w + 31: D[row][col] += sum_k K[row][k] v[k][col] with v_mfma_f32_32x32x2_f32, lane
-//   half h = lane >> 5 taking k in [32 h, 32 h + 32) of the slab.
-// Epilogue fused: + d o v, store, CG inner product partial sum_rows v o y (one per 128-row tile).
+//     v slab [128 k][32 cols] (columns >= c zero).
+//   wave w owns rows 32 (w & 1) .. + 31 and the k half w >> 1 of the slab: D[row][col] += sum_k K[row][k] v[k][col]
+//   with v_mfma_f32_32x32x2_f32, lane half h = lane >> 5 taking k in [64 (w >> 1) + 32 h, + 32) of the slab.
+// Epilogue fused: + d o v, store, CG inner product partial sum_rows v o y (one per 64-row tile).
 #include <algorithm>
 #include <stdlib.h>
 
@@ -44,7 +44,7 @@ __global__ __launch_bounds__(kThreads) void k_dense_mv_mfma(const float* __restr
   const float* Kb = K + (size_t)b * N * N;
   const size_t vbase = (size_t)b * N * ldv;
 
-  // staging map: thread t loads float4 #(t + 256 u), u = 0..7 of the [128][64] slab: row = f / 16, quad = f % 16
+  // staging map: thread t loads float4 #(t + 256 u), u = 0..7 of the [64][128] slab: row = f / 32, quad = f % 32
   float4 kreg[8];
   float vreg[16];
   const bool full_rows = ((N & 3) == 0) && (row0 + DM_ROWS <= N);  // workgroup-uniform fast path condition
