@@ -1079,6 +1079,16 @@ size_t lo_kernel_mv_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t D, 
 int lo_kernel_mv_f32(const float* x1, const float* x2, const float* theta, int32_t family, int64_t B, int64_t M,
                      int64_t N, int64_t D, const float* v, int64_t c, const float* d, int32_t diag_mode, float* y,
                      void* ws, size_t ws_bytes, void* stream);
+/* (ABI 42; csrc/lo_kernel_mv_wide.hip) lo_kernel_mv_f32 for many columns: the kernel values are formed as above, one per
+ * lane on the vector ALU by direct differences, and their product with v runs on v_mfma_f32_32x32x2_f32 (exact fp32,
+ * fp32 accumulation), 32 columns per sweep.  Arguments, checks, error codes, workspace layout and the column split are
+ * those of lo_kernel_mv_f32; this entry always runs the matrix-core kernel, for any c >= 1.  lo_kernel_mv_f32 and every
+ * caller of its product take it where ko_wide(c, DP) of csrc/lo_kernel_shape.h says so (a function of c and the padded
+ * dimension alone).  Fixed-order sums, no atomics: the same inputs give the same bits.                                  */
+size_t lo_kernel_mv_wide_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t D, int64_t c);
+int lo_kernel_mv_wide_f32(const float* x1, const float* x2, const float* theta, int32_t family, int64_t B, int64_t M,
+                          int64_t N, int64_t D, const float* v, int64_t c, const float* d, int32_t diag_mode, float* y,
+                          void* ws, size_t ws_bytes, void* stream);
 size_t lo_kernel_bilinear_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t D, int64_t t);
 int lo_kernel_bilinear_f32(const float* x1, const float* x2, const float* theta, int32_t family, int64_t B, int64_t M,
                            int64_t N, int64_t D, const float* U, const float* V, int64_t t, float* g_theta, void* ws,

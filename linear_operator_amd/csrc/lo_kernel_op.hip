@@ -8,7 +8,8 @@
 //   tiles of 128; every lane reads the same tile entry, so the LDS reads are broadcasts without bank conflicts.  Per pair:
 //   r^2 = sum_d (a_d - b_d)^2 by direct differences (never |a|^2 + |b|^2 - 2 a.b, which cancels for near points), g(r)
 //   with one v_exp_f32 on a pre-multiplied argument (and one v_sqrt_f32 for the Matern families), CC FMAs.  A tile's sum is
-//   formed on its own and then added to the running one (two-level summation).  More than CC columns: another sweep.
+//   formed on its own and then added to the running one (two-level summation).  More than CC columns: another sweep --
+//   which is why kernel_mv_run hands many columns (ko_wide) to k_kernel_mv_wide of lo_kernel_mv_wide.hip instead.
 //   Ragged M, N, D, c are predicated: padded coordinates are 0 on both sides, rows beyond M compute and store nothing.
 // Few rows (B ceil(M / 256) < 512 workgroups): the columns j are split over gridDim.z workgroups, the partials go to the
 //   workspace and k_kernel_mv_reduce adds them in ascending order and applies + d o v.  No workgroup waits for another.
@@ -309,6 +310,8 @@ int kernel_mv_run(const float* x1, const float* x2, const float* theta, int64_t 
                   int64_t N, int64_t D, const float* v, int64_t c, const float* d, int dmode, float* y, float* part,
                   const int* stop, hipStream_t st) {
   const KoSweep w(B, M, N, D);
+  if (ko_wide(c, w.DP))  // many columns: the product on the matrix cores (lo_kernel_mv_wide.hip)
+    return kernel_mv_wide_run(x1, x2, theta, tstride, family, B, M, N, D, v, c, d, dmode, y, part, stop, st);
   float* p = w.s.js > 1 ? part : nullptr;
   if (M != N) dmode = LO_DIAG_NONE;
   LO_PROF_BEGIN("k_kernel_mv", st);

@@ -150,6 +150,17 @@ int kernel_mv_run(const float* x1, const float* x2, const float* theta, int64_t 
                   int64_t N, int64_t D, const float* v, int64_t c, const float* d, int dmode, float* y, float* part,
                   const int* stop, hipStream_t st);
 
+// The many-column product on the matrix cores (lo_kernel_mv_wide.hip, k_kernel_mv_wide): same arguments, same partials.
+int kernel_mv_wide_run(const float* x1, const float* x2, const float* theta, int64_t tstride, int family, int64_t B,
+                       int64_t M, int64_t N, int64_t D, const float* v, int64_t c, const float* d, int dmode, float* y,
+                       float* part, const int* stop, hipStream_t st);
+// Which of the two kernel_mv_run launches: a function of the column count and the padded dimension alone, read by
+// kernel_mv_run and nothing else.  The cells come from the column sweep of tools/mb_kernel_op.py:
+// a cell is routed to k_kernel_mv_wide only where its median beat k_kernel_mv's by more than the measured spread.  From 17
+// columns on (a second sweep of k_kernel_mv) it won at every DP, 0.34 - 0.77 of the time; at 5 .. 16 columns it won at
+// DP 16 and 32 (0.66 - 0.83) and lost at DP 4 and 8 (1.02 - 1.14); up to 4 columns k_kernel_mv is kept everywhere.
+inline bool ko_wide(int64_t c, int DP) { return c >= 17 || (c >= 5 && DP >= 16); }
+
 // y[b, i, col] = sum_z part[z, b, i, col] (ascending z) + d o v over `total` = B rows c elements (lo_kernel_op.hip)
 int ko_reduce_splits(const char* prof_name, const float* part, int js, size_t per_member, size_t total, int c,
                      const float* d, int dmode, const float* v, float* y, const int* stop, hipStream_t st);

@@ -661,6 +661,19 @@ def kernel_mv(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, family: i
     return y
 
 
+def kernel_mv_wide(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, family: int, v: torch.Tensor,
+                   d: Optional[torch.Tensor] = None, const_diag: bool = False) -> torch.Tensor:
+    """lo_kernel_mv_wide_f32: kernel_mv on the many-column kernel (csrc/lo_kernel_mv_wide.hip: the product with v on the
+    matrix cores, 32 columns per sweep), whatever the column count; float32 only.  kernel_mv takes this kernel by itself
+    where it is the faster one."""
+    x1, x2, theta, _, _, v, (B, M, N, D, _, c), _ = _kernel_args("kernel_mv_wide", x1, x2, theta, v, d=d)
+    d, mode = _kernel_diag(d, B, N, const_diag)
+    y = torch.empty(B, M, c, dtype=torch.float32, device=v.device)
+    name, sizer = _kernel_entry("lo_kernel_mv_wide", False)
+    _launch(name, v.device, x1, x2, theta, int(family), B, M, N, D, v, c, d, mode, y, ws_bytes=sizer(B, M, N, D, c))
+    return y
+
+
 def kernel_bilinear(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, family: int, U: torch.Tensor,
                     V: torch.Tensor) -> torch.Tensor:
     """lo_kernel_bilinear_f32 (all operands float64: lo_kernel_bilinear_f64): g_theta [B, D + 1], the derivative of

@@ -12,7 +12,12 @@ Points' gradient (--what points): lo_kernel_points_grad_f32 for BOTH sides (two 
 ABI 26, restated here as chunked_autograd_points: torch autograd through the covariance function on row blocks of at
 most 64 MiB of differences.  Same inputs, the two taking turns; the slow alternative is repeated fewer times per turn
 (its count is printed), never fewer turns.
-Usage:  python tools/mb_kernel_op.py [--what product,points] [--reps 20] [--rounds 5] [--families rbf,matern52]
+
+Column sweep (--what wide): lo_kernel_mv_wide_f32 (csrc/lo_kernel_mv_wide.hip, the product with V on the matrix cores)
+against lo_kernel_mv_f32 over the column counts WIDE_COLS at the shapes WIDE_SHAPES, the two taking turns.  The rule
+ko_wide of csrc/lo_kernel_shape.h is set from this table, so the comparison is against k_kernel_mv
+only on a build whose ko_wide returns false: where the rule routes, both calls run the same kernel.
+Usage:  python tools/mb_kernel_op.py [--what product,points,wide] [--reps 20] [--rounds 5] [--families rbf,matern52]
 One JSON line per measurement.
 """
 from __future__ import annotations
@@ -38,6 +43,9 @@ from linear_operator_amd import kernels as K  # noqa: E402
 SHAPES = ((1, 16384, 4, 1, True), (1, 16384, 4, 17, True), (8, 8192, 16, 1, True), (1, 131072, 8, 1, False))
 # (B, N, D, t) of the points' gradient
 POINT_SHAPES = ((1, 16384, 4, 1), (1, 16384, 4, 17), (8, 8192, 16, 1), (1, 131072, 8, 1))
+# the column sweep of the many-column product: (B, N, D) and the column counts
+WIDE_SHAPES = ((1, 16384, 4), (1, 16384, 8), (8, 8192, 16), (1, 16384, 32))  # one per padded dimension
+WIDE_COLS = (1, 2, 4, 5, 8, 16, 17, 32, 33, 64)
 CHUNK_BYTES = 64 * 1024 * 1024  # the differences [rows, N, D] of one row block of the autograd path
 
 
@@ -111,6 +119,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--families", default="rbf,matern12,matern32,matern52")
     ap.add_argument("--what", default="product,points")
+    ap.add_argument("--dims", default="", help="the column sweep at these D only (comma separated; default: all)")
     args = ap.parse_args()
     dev = "cuda"
     if not torch.cuda.is_available():
@@ -120,6 +129,32 @@ def main():
         product(args, dev, gen)
     if "points" in args.what.split(","):
         points_gradient(args, dev, gen)
+    if "wide" in args.what.split(","):
+        wide_columns(args, dev, gen)
+
+
+def wide_columns(args, dev, gen):
+    dims = [int(d) for d in args.dims.split(",") if d]
+    for B, N, D in WIDE_SHAPES:
+        if dims and D not in dims:
+            continue
+        x = torch.rand(B, N, D, generator=gen).to(dev)
+        ls = (0.3 * D ** 0.5 * (0.7 + 0.6 * torch.rand(B, 1, D, generator=gen))).to(dev)
+        os_ = (0.8 + 0.7 * torch.rand(B, generator=gen)).to(dev)
+        theta = K.kernel_theta(ls, os_, (B,), D)
+        for name in args.families.split(","):
+            fam = covariance.FAMILIES[name].native_family
+            for c in WIDE_COLS:
+                v = torch.randn(B, N, c, generator=gen).to(dev)
+                fns = [lambda: K.kernel_mv(x, x, theta, fam, v), lambda: K.kernel_mv_wide(x, x, theta, fam, v)]
+                times = alternated(fns, args.reps, args.rounds)
+                y_n, y_w = fns[0](), fns[1]()
+                print(json.dumps(dict(
+                    what="kernel_mv_wide", family=name, B=B, N=N, D=D, c=c, mv_us=r1(times[0]), wide_us=r1(times[1]),
+                    wide_over_mv=round(times[1][0] / times[0][0], 3),
+                    # the wide kernel wins when even its slowest round beats the other's fastest one
+                    wide_wins=times[1][2] < times[0][1], rel_diff=((y_w - y_n).norm() / y_n.norm()).item())),
+                    flush=True)
 
 
 def product(args, dev, gen):
