@@ -1097,6 +1097,20 @@ size_t lo_kernel_points_grad_workspace_bytes(int64_t B, int64_t M, int64_t N, in
 int lo_kernel_points_grad_f32(const float* x1, const float* x2, const float* theta, int32_t family, int64_t B, int64_t M,
                               int64_t N, int64_t D, const float* U, const float* V, int64_t t, float* g_x1, void* ws,
                               size_t ws_bytes, void* stream);
+/* (ABI 43; csrc/lo_kernel_bil_wide.hip) lo_kernel_bilinear_f32 and lo_kernel_points_grad_f32 for many columns t:
+ * W = U V^T runs on v_mfma_f32_32x32x2_f32 (exact fp32, fp32 accumulation), up to 32 columns per sweep, and r^2, g and h
+ * of a pair are formed once per sweep, by direct differences as above.  Arguments, checks, error codes, workspace layout
+ * and the column split are those of the plain twins; these entries always run the matrix-core kernels, for any t >= 1.
+ * The plain twins take them where ko_bil_wide(t, DP) of csrc/lo_kernel_shape.h says so (a function of t and the padded
+ * dimension alone).  Fixed-order sums, no atomics: the same inputs give the same bits.                                 */
+size_t lo_kernel_bilinear_wide_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t D, int64_t t);
+int lo_kernel_bilinear_wide_f32(const float* x1, const float* x2, const float* theta, int32_t family, int64_t B,
+                                int64_t M, int64_t N, int64_t D, const float* U, const float* V, int64_t t,
+                                float* g_theta, void* ws, size_t ws_bytes, void* stream);
+size_t lo_kernel_points_grad_wide_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t D, int64_t t);
+int lo_kernel_points_grad_wide_f32(const float* x1, const float* x2, const float* theta, int32_t family, int64_t B,
+                                   int64_t M, int64_t N, int64_t D, const float* U, const float* V, int64_t t,
+                                   float* g_x1, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- the same operator in float64 (ABI 31; csrc/lo_kernel_op_f64.hip) --------------------------------------------------
  * The three entry points above with `double` in place of `float`: same formulas, same argument meanings, same error

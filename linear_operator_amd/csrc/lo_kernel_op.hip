@@ -327,6 +327,42 @@ int kernel_mv_run(const float* x1, const float* x2, const float* theta, int64_t 
   return LO_OK;
 }
 
+// the hyperparameters' derivative on validated arguments; part: the partials of ko_bil_layout
+int kernel_bil_run(const float* x1, const float* x2, const float* theta, int family, int64_t B, int64_t M, int64_t N,
+                   int64_t D, const float* U, const float* V, int64_t t, float* g_theta, float* part, hipStream_t st) {
+  const KoSweep w(B, M, N, D);
+  if (ko_bil_wide(t, w.DP))  // many columns: W = U V^T on the matrix cores (lo_kernel_bil_wide.hip)
+    return kernel_bil_wide_run(x1, x2, theta, family, B, M, N, D, U, V, t, g_theta, part, st);
+  LO_PROF_BEGIN("k_kernel_bil", st);
+  ko_dispatch(family, w.DP, [&](auto F, auto P) {
+    hipLaunchKernelGGL((k_kernel_bil<F(), P()>), w.grid, dim3(kThreads), 0, st, x1, x2, theta, (int)M, (int)N, (int)D, U, V,
+                       (int)t, part, w.s.jchunk);
+  });
+  LO_PROF_END(st);
+  LO_LAUNCH_CHECK();
+  return ko_bil_reduce(part, w.s.rb * w.s.js, w.DP, B, D, theta, g_theta, st);
+}
+
+// the derivative of the points x1 on validated arguments; part: [js, B, M, D] floats when ko_shape(B, M, N).js > 1
+int kernel_pgrad_run(const float* x1, const float* x2, const float* theta, int family, int64_t B, int64_t M, int64_t N,
+                     int64_t D, const float* U, const float* V, int64_t t, float* g_x1, float* part, hipStream_t st) {
+  const KoSweep w(B, M, N, D);
+  if (ko_bil_wide(t, w.DP))  // many columns: W = U V^T on the matrix cores (lo_kernel_bil_wide.hip)
+    return kernel_pgrad_wide_run(x1, x2, theta, family, B, M, N, D, U, V, t, g_x1, part, st);
+  float* out = w.s.js > 1 ? part : g_x1;
+  LO_PROF_BEGIN("k_kernel_pgrad", st);
+  ko_dispatch(family, w.DP, [&](auto F, auto P) {
+    hipLaunchKernelGGL((k_kernel_pgrad<F(), P()>), w.grid, dim3(kThreads), 0, st, x1, x2, theta, (int)M, (int)N, (int)D, U,
+                       V, (int)t, out, w.s.jchunk);
+  });
+  LO_PROF_END(st);
+  LO_LAUNCH_CHECK();
+  if (w.s.js > 1)  // the splits in ascending order (the reduction of the product with D as its columns and no diagonal)
+    return ko_reduce_splits("k_kernel_pgrad_reduce", part, w.s.js, (size_t)M * D, (size_t)B * M * D, (int)D, nullptr,
+                            LO_DIAG_NONE, nullptr, g_x1, nullptr, st);
+  return LO_OK;
+}
+
 int kernel_desc_check(const lo_op_desc* op) {
   if (!op->A0 || !op->A1 || op->R < 1 || !ko_family_ok(op->n2)) return LO_ERR_BADARG;
   return op->R > LO_KERNEL_MAX_DIM ? LO_ERR_UNSUPPORTED : LO_OK;
@@ -382,19 +418,10 @@ int lo_kernel_bilinear_f32(const float* x1, const float* x2, const float* theta,
   if (!x1 || !x2 || !theta || !U || !V || !g_theta || !ko_args_ok(B, M, N, D, t) || !ko_family_ok(family))
     return LO_ERR_BADARG;
   if (!ko_shape_ok(B, M, N, D) || t > 0x7fffffff) return LO_ERR_UNSUPPORTED;
-  hipStream_t st = (hipStream_t)stream;
   Arena ar(ws, ws_bytes, kKoTail);
   float* part = ko_bil_layout<float>(ar, B, M, N, D);
   if (!ws || !ar.ok) return LO_ERR_WORKSPACE;
-  const KoSweep w(B, M, N, D);
-  LO_PROF_BEGIN("k_kernel_bil", st);
-  ko_dispatch(family, w.DP, [&](auto F, auto P) {
-    hipLaunchKernelGGL((k_kernel_bil<F(), P()>), w.grid, dim3(kThreads), 0, st, x1, x2, theta, (int)M, (int)N, (int)D, U, V,
-                       (int)t, part, w.s.jchunk);
-  });
-  LO_PROF_END(st);
-  LO_LAUNCH_CHECK();
-  return ko_bil_reduce(part, w.s.rb * w.s.js, w.DP, B, D, theta, g_theta, st);
+  return kernel_bil_run(x1, x2, theta, family, B, M, N, D, U, V, t, g_theta, part, (hipStream_t)stream);
 }
 
 size_t lo_kernel_points_grad_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t D, int64_t t) {
@@ -408,23 +435,10 @@ int lo_kernel_points_grad_f32(const float* x1, const float* x2, const float* the
   if (!x1 || !x2 || !theta || !U || !V || !g_x1 || !ko_args_ok(B, M, N, D, t) || !ko_family_ok(family))
     return LO_ERR_BADARG;
   if (!ko_shape_ok(B, M, N, D) || t > 0x7fffffff) return LO_ERR_UNSUPPORTED;
-  hipStream_t st = (hipStream_t)stream;
   Arena ar(ws, ws_bytes, kKoTail);
   float* part = ko_split_layout<float>(ar, B, M, N, D);  // [js, B, M, D]
   if (!ws || !ar.ok) return LO_ERR_WORKSPACE;
-  const KoSweep w(B, M, N, D);
-  float* out = w.s.js > 1 ? part : g_x1;
-  LO_PROF_BEGIN("k_kernel_pgrad", st);
-  ko_dispatch(family, w.DP, [&](auto F, auto P) {
-    hipLaunchKernelGGL((k_kernel_pgrad<F(), P()>), w.grid, dim3(kThreads), 0, st, x1, x2, theta, (int)M, (int)N, (int)D, U,
-                       V, (int)t, out, w.s.jchunk);
-  });
-  LO_PROF_END(st);
-  LO_LAUNCH_CHECK();
-  if (w.s.js > 1)  // the splits in ascending order (the reduction of the product with D as its columns and no diagonal)
-    return ko_reduce_splits("k_kernel_pgrad_reduce", part, w.s.js, (size_t)M * D, (size_t)B * M * D, (int)D, nullptr,
-                            LO_DIAG_NONE, nullptr, g_x1, nullptr, st);
-  return LO_OK;
+  return kernel_pgrad_run(x1, x2, theta, family, B, M, N, D, U, V, t, g_x1, part, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -135,6 +135,10 @@ using kg_cols = std::conditional_t<DP <= 4, std::integer_sequence<int, 4, 2, 1>,
                                    std::conditional_t<DP <= 8, std::integer_sequence<int, 2, 1>, std::integer_sequence<int, 1>>>;
 // columns of U / V one sweep of its derivative carries: the thread keeps DP + 1 scaled entries of U per column in registers
 constexpr int kg_bil_cols(int DP) { return DP <= 4 ? kKoTS : (DP <= 8 ? 4 : 2); }
+// columns of U / V one sweep of the plain kind's wide derivatives carries (lo_kernel_bil_wide.hip): the contraction length
+// of W = U V^T on the matrix cores, half of them per lane in registers for each of two rows, beside the lane's point, its
+// DP running and DP tile sums and the 32 accumulators of W
+constexpr int ko_bil_wide_cols(int DP) { return 32; }
 
 // Matern-5/2 gradient kernel (lo_kernel_mgrad.hip), by the padded dimension (kg_dims): the sums of the RBF gradient kernel
 // plus three radial factors instead of one, and every instantiation still stays at 3 waves per SIMD without scratch
@@ -160,6 +164,27 @@ int kernel_mv_wide_run(const float* x1, const float* x2, const float* theta, int
 // columns on (a second sweep of k_kernel_mv) it won at every DP, 0.34 - 0.77 of the time; at 5 .. 16 columns it won at
 // DP 16 and 32 (0.66 - 0.83) and lost at DP 4 and 8 (1.02 - 1.14); up to 4 columns k_kernel_mv is kept everywhere.
 inline bool ko_wide(int64_t c, int DP) { return c >= 17 || (c >= 5 && DP >= 16); }
+
+// The derivatives of sum_s u_s^T K(x1, x2) v_s on validated arguments (lo_kernel_op.hip): the hyperparameters, part the
+// partials of ko_bil_layout, and the points x1, part the partials of ko_split_layout with D columns
+int kernel_bil_run(const float* x1, const float* x2, const float* theta, int family, int64_t B, int64_t M, int64_t N,
+                   int64_t D, const float* U, const float* V, int64_t t, float* g_theta, float* part, hipStream_t st);
+int kernel_pgrad_run(const float* x1, const float* x2, const float* theta, int family, int64_t B, int64_t M, int64_t N,
+                     int64_t D, const float* U, const float* V, int64_t t, float* g_x1, float* part, hipStream_t st);
+// The same with W = U V^T on the matrix cores (lo_kernel_bil_wide.hip, k_kernel_bil_wide): same arguments, same partials.
+int kernel_bil_wide_run(const float* x1, const float* x2, const float* theta, int family, int64_t B, int64_t M, int64_t N,
+                        int64_t D, const float* U, const float* V, int64_t t, float* g_theta, float* part, hipStream_t st);
+int kernel_pgrad_wide_run(const float* x1, const float* x2, const float* theta, int family, int64_t B, int64_t M,
+                          int64_t N, int64_t D, const float* U, const float* V, int64_t t, float* g_x1, float* part,
+                          hipStream_t st);
+// Which of the two kernel_bil_run and kernel_pgrad_run launch: a function of the column count and the padded dimension
+// alone, read by those two and nothing else.  The cells come from the derivative sweep of tools/mb_kernel_op.py (--what
+// bilwide): from 9 columns on (a second sweep of the old kernels) k_kernel_bil_wide's slowest round
+// beat the old kernel's fastest in every cell of both kernels, 0.43 - 0.57 of the time at 9 .. 16 columns and 0.28 - 0.45
+// from 17 on.  Up to 8 columns it also won in all cells but one (0.76 - 0.94 at DP <= 16, 0.95 - 1.01 at DP 32; the points'
+// kernel at DP 32, t = 8 lost); those cells keep the old kernels, as ko_wide keeps c <= 4: the few-column derivatives of
+// every caller stay the kernels they were, which tests/test_gpu_kernel_variants.py pins by name.
+inline bool ko_bil_wide(int64_t t, int DP) { return t >= 9; }
 
 // y[b, i, col] = sum_z part[z, b, i, col] (ascending z) + d o v over `total` = B rows c elements (lo_kernel_op.hip)
 int ko_reduce_splits(const char* prof_name, const float* part, int js, size_t per_member, size_t total, int c,

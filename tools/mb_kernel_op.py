@@ -17,7 +17,12 @@ Column sweep (--what wide): lo_kernel_mv_wide_f32 (csrc/lo_kernel_mv_wide.hip, t
 against lo_kernel_mv_f32 over the column counts WIDE_COLS at the shapes WIDE_SHAPES, the two taking turns.  The rule
 ko_wide of csrc/lo_kernel_shape.h is set from this table, so the comparison is against k_kernel_mv
 only on a build whose ko_wide returns false: where the rule routes, both calls run the same kernel.
-Usage:  python tools/mb_kernel_op.py [--what product,points,wide] [--reps 20] [--rounds 5] [--families rbf,matern52]
+
+Derivative sweep (--what bilwide): lo_kernel_bilinear_wide_f32 and lo_kernel_points_grad_wide_f32
+(csrc/lo_kernel_bil_wide.hip, W = U V^T on the matrix cores) against their plain twins over the column counts BIL_COLS at
+WIDE_SHAPES, the two taking turns.  ko_bil_wide of csrc/lo_kernel_shape.h is set from this table (DESIGN.md section 6y);
+as above, the comparison is against the old kernels only on a build whose ko_bil_wide returns false.
+Usage:  python tools/mb_kernel_op.py [--what product,points,wide,bilwide] [--reps 20] [--rounds 5] [--families rbf,matern52]
 One JSON line per measurement.
 """
 from __future__ import annotations
@@ -46,6 +51,7 @@ POINT_SHAPES = ((1, 16384, 4, 1), (1, 16384, 4, 17), (8, 8192, 16, 1), (1, 13107
 # the column sweep of the many-column product: (B, N, D) and the column counts
 WIDE_SHAPES = ((1, 16384, 4), (1, 16384, 8), (8, 8192, 16), (1, 16384, 32))  # one per padded dimension
 WIDE_COLS = (1, 2, 4, 5, 8, 16, 17, 32, 33, 64)
+BIL_COLS = (1, 2, 4, 8, 9, 11, 16, 17, 32, 33, 64)  # the columns t of the derivative sweep
 CHUNK_BYTES = 64 * 1024 * 1024  # the differences [rows, N, D] of one row block of the autograd path
 
 
@@ -131,6 +137,34 @@ def main():
         points_gradient(args, dev, gen)
     if "wide" in args.what.split(","):
         wide_columns(args, dev, gen)
+    if "bilwide" in args.what.split(","):
+        wide_derivatives(args, dev, gen)
+
+
+def wide_derivatives(args, dev, gen):
+    dims = [int(d) for d in args.dims.split(",") if d]
+    for B, N, D in WIDE_SHAPES:
+        if dims and D not in dims:
+            continue
+        x = torch.rand(B, N, D, generator=gen).to(dev)
+        ls = (0.3 * D ** 0.5 * (0.7 + 0.6 * torch.rand(B, 1, D, generator=gen))).to(dev)
+        os_ = (0.8 + 0.7 * torch.rand(B, generator=gen)).to(dev)
+        theta = K.kernel_theta(ls, os_, (B,), D)
+        for name in args.families.split(","):
+            fam = covariance.FAMILIES[name].native_family
+            for t in BIL_COLS:
+                U, V = torch.randn(B, N, t, generator=gen).to(dev), torch.randn(B, N, t, generator=gen).to(dev)
+                for what, old, new in (("kernel_bilinear_wide", K.kernel_bilinear, K.kernel_bilinear_wide),
+                                       ("kernel_points_grad_wide", K.kernel_points_grad, K.kernel_points_grad_wide)):
+                    fns = [lambda: old(x, x, theta, fam, U, V), lambda: new(x, x, theta, fam, U, V)]
+                    times = alternated(fns, args.reps, args.rounds)
+                    g_o, g_w = fns[0](), fns[1]()
+                    print(json.dumps(dict(
+                        what=what, family=name, B=B, N=N, D=D, t=t, old_us=r1(times[0]), wide_us=r1(times[1]),
+                        wide_over_old=round(times[1][0] / times[0][0], 3),
+                        # the wide kernel wins when even its slowest round beats the other's fastest one
+                        wide_wins=times[1][2] < times[0][1], rel_diff=((g_w - g_o).norm() / g_o.norm()).item())),
+                        flush=True)
 
 
 def wide_columns(args, dev, gen):
