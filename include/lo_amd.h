@@ -1127,6 +1127,18 @@ size_t lo_kernel_mv_f64_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t
 int lo_kernel_mv_f64(const double* x1, const double* x2, const double* theta, int32_t family, int64_t B, int64_t M,
                      int64_t N, int64_t D, const double* v, int64_t c, const double* d, int32_t diag_mode, double* y,
                      void* ws, size_t ws_bytes, void* stream);
+/* (ABI 44; csrc/lo_kernel_mv_wide_f64.hip) lo_kernel_mv_f64 for many columns: the kernel values are formed as above, one
+ * per lane on the vector ALU by direct differences, and their product with v runs on v_mfma_f64_16x16x4_f64, 16 to 48
+ * columns per sweep (32 at D > 16), so that a kernel value is formed once for them all.  Arguments, checks, error codes
+ * in their order, workspace bytes and layout and the column split are those of lo_kernel_mv_f64; this entry always runs
+ * the matrix-core kernel, for any c >= 1.  lo_kernel_mv_f64 and every caller of its product (LO_OP_KERNEL_DIAG of
+ * lo_matvec_f64, alone and as a term of LO_OP_SUM, and the float64 solvers through them) take it where ko64_wide(c, DP)
+ * of csrc/lo_kernel_shape.h says so (a function of c and the padded dimension alone).  Fixed-order sums, no atomics: the
+ * same inputs give the same bits.                                                                                      */
+size_t lo_kernel_mv_wide_f64_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t D, int64_t c);
+int lo_kernel_mv_wide_f64(const double* x1, const double* x2, const double* theta, int32_t family, int64_t B, int64_t M,
+                          int64_t N, int64_t D, const double* v, int64_t c, const double* d, int32_t diag_mode, double* y,
+                          void* ws, size_t ws_bytes, void* stream);
 size_t lo_kernel_bilinear_f64_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t D, int64_t t);
 int lo_kernel_bilinear_f64(const double* x1, const double* x2, const double* theta, int32_t family, int64_t B, int64_t M,
                            int64_t N, int64_t D, const double* U, const double* V, int64_t t, double* g_theta, void* ws,

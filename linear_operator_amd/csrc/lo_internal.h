@@ -569,6 +569,11 @@ double* kernel_mv_layout_f64(Arena& ar, int64_t B, int64_t M, int64_t N, int64_t
 int kernel_mv_run_f64(const double* x1, const double* x2, const double* theta, int family, int64_t B, int64_t M,
                       int64_t N, int64_t D, const double* v, int64_t c, const double* d, int dmode, int accumulate,
                       double* y, double* part, hipStream_t st);
+// The many-column product on the matrix cores (lo_kernel_mv_wide_f64.hip, k64_kernel_mv_wide): same arguments, same
+// partials; kernel_mv_run_f64 takes it where ko64_wide(c, DP) of lo_kernel_shape.h says so.
+int kernel_mv_wide_run_f64(const double* x1, const double* x2, const double* theta, int family, int64_t B, int64_t M,
+                           int64_t N, int64_t D, const double* v, int64_t c, const double* d, int dmode, int accumulate,
+                           double* y, double* part, hipStream_t st);
 
 // ---- single-pass Woodbury apply fused with the CG r / x update (lo_precond_fused.hip) --------------
 bool precond_fused_eligible(int64_t B, int64_t N, int64_t c, int ldq, int S);

@@ -304,8 +304,8 @@ __global__ __launch_bounds__(kThreads, ko64_waves<DP>()) void k64_kernel_pgrad(
   }
 }
 
-static int ko64_reduce_splits(const char* prof_name, const double* part, int js, size_t per_member, size_t total, int c,
-                              const double* d, int dmode, int accumulate, const double* v, double* y, hipStream_t st) {
+int ko64_reduce_splits(const char* prof_name, const double* part, int js, size_t per_member, size_t total, int c,
+                       const double* d, int dmode, int accumulate, const double* v, double* y, hipStream_t st) {
   LO_PROF_BEGIN(prof_name, st);
   hipLaunchKernelGGL(k64_kernel_mv_reduce, dim3((unsigned)((total + kThreads - 1) / kThreads)), dim3(kThreads), 0, st,
                      part, js, per_member, total, c, d, dmode, accumulate, v, y);
@@ -319,6 +319,8 @@ int kernel_mv_run_f64(const double* x1, const double* x2, const double* theta, i
                       int64_t N, int64_t D, const double* v, int64_t c, const double* d, int dmode, int accumulate,
                       double* y, double* part, hipStream_t st) {
   const KoSweep w(B, M, N, D);
+  if (ko64_wide(c, w.DP))
+    return kernel_mv_wide_run_f64(x1, x2, theta, family, B, M, N, D, v, c, d, dmode, accumulate, y, part, st);
   const int CC = ko64_col_chunk(c, w.DP);
   double* p = w.s.js > 1 ? part : nullptr;
   if (M != N) dmode = LO_DIAG_NONE;

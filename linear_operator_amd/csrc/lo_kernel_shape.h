@@ -121,6 +121,28 @@ using kl_cols = std::integer_sequence<int, 4, 8, 16>;
 inline int ko64_col_chunk(int64_t c, int DP) { return c == 1 ? 1 : ((c <= 4 || DP == 32) ? 4 : 8); }
 template <int DP>
 using ko64_cols = std::conditional_t<DP == 32, std::integer_sequence<int, 1, 4>, std::integer_sequence<int, 1, 4, 8>>;
+// float64, many columns (lo_kernel_mv_wide_f64.hip): 16-column tiles NT per sweep.  The tile of points (DP KB) and of v
+// (16 NT KB) are the workgroup's LDS, 64 KB at most: three tiles, two at DP = 32.  The sweeps are made even: 17 columns
+// are one sweep of two tiles, 65 two sweeps of three (three of two at DP = 32).
+constexpr int ko64_wide_max_tiles(int DP) { return DP == 32 ? 2 : 3; }
+inline int ko64_wide_tiles(int64_t c, int DP) {
+  const int64_t tiles = (c + 15) / 16, most = ko64_wide_max_tiles(DP);
+  const int64_t sweeps = (tiles + most - 1) / most;
+  return (int)((tiles + sweeps - 1) / sweeps);
+}
+template <int DP>
+using ko64_wide_nts = std::conditional_t<DP == 32, std::integer_sequence<int, 1, 2>, std::integer_sequence<int, 1, 2, 3>>;
+// Which of the two kernel_mv_run_f64 launches (lo_kernel_op_f64.hip): a function of the column count and the padded
+// dimension alone, read by kernel_mv_run_f64 and nothing else.  The cells come from the column sweep of
+// tools/mb_kernel_f64.py --what wide: a cell is routed to k64_kernel_mv_wide only where its slowest
+// round beat k64_kernel_mv's fastest.  From 9 columns on (a second sweep of k64_kernel_mv) it won in every cell, 0.48 - 0.66
+// of the time at 9 .. 16 columns, 0.14 - 0.56 from 17 on; at 5 .. 8 columns (two sweeps of four at DP 32) it won at DP 32
+// (0.59 - 0.60), lost at DP 4 and 8 (1.12 - 1.31) and split at DP 16 (0.94 - 1.20: not routed); up to 4 columns
+// k64_kernel_mv is kept everywhere (1.16 - 1.56), c = 1 included, which tests/test_gpu_kernel_variants.py pins by name.
+inline bool ko64_wide(int64_t c, int DP) { return c >= 9 || (c >= 5 && DP == 32); }
+// y[b, i, col] = [y +] sum_z part[z, b, i, col] (ascending z) + d o v over `total` = B rows c doubles (lo_kernel_op_f64.hip)
+int ko64_reduce_splits(const char* prof_name, const double* part, int js, size_t per_member, size_t total, int c,
+                       const double* d, int dmode, int accumulate, const double* v, double* y, hipStream_t st);
 
 // gradient kernel (lo_kernel_grad.hip), by the padded dimension: a thread holds (DP + 1) CC running sums and as many tile
 // sums, and every instantiation stays at 3 waves per SIMD (<= 168 VGPRs) without scratch -- 4 columns at DP 4, 2 at DP 8, 1

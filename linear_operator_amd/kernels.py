@@ -663,13 +663,14 @@ def kernel_mv(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, family: i
 
 def kernel_mv_wide(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, family: int, v: torch.Tensor,
                    d: Optional[torch.Tensor] = None, const_diag: bool = False) -> torch.Tensor:
-    """lo_kernel_mv_wide_f32: kernel_mv on the many-column kernel (csrc/lo_kernel_mv_wide.hip: the product with v on the
-    matrix cores, 32 columns per sweep), whatever the column count; float32 only.  kernel_mv takes this kernel by itself
-    where it is the faster one."""
-    x1, x2, theta, _, _, v, (B, M, N, D, _, c), _ = _kernel_args("kernel_mv_wide", x1, x2, theta, v, d=d)
+    """lo_kernel_mv_wide_f32 (all operands float64: lo_kernel_mv_wide_f64): kernel_mv on the many-column kernel
+    (csrc/lo_kernel_mv_wide.hip: the product with v on the matrix cores, 32 columns per sweep; float64:
+    csrc/lo_kernel_mv_wide_f64.hip, 16 to 48 columns per sweep), whatever the column count.  kernel_mv takes this kernel
+    by itself where it is the faster one."""
+    x1, x2, theta, _, _, v, (B, M, N, D, _, c), dtype = _kernel_args("kernel_mv_wide", x1, x2, theta, v, d=d, twin=True)
     d, mode = _kernel_diag(d, B, N, const_diag)
-    y = torch.empty(B, M, c, dtype=torch.float32, device=v.device)
-    name, sizer = _kernel_entry("lo_kernel_mv_wide", False)
+    y = torch.empty(B, M, c, dtype=dtype, device=v.device)
+    name, sizer = _kernel_entry("lo_kernel_mv_wide", dtype == torch.float64)
     _launch(name, v.device, x1, x2, theta, int(family), B, M, N, D, v, c, d, mode, y, ws_bytes=sizer(B, M, N, D, c))
     return y
 

@@ -11,11 +11,14 @@ min - max (a slow route is repeated fewer times per turn, never fewer turns; the
 shape has no stored alternative (128 GiB) and is timed alone.  --what derivs: lo_kernel_bilinear_f64 and the two
 lo_kernel_points_grad_f64 calls against float64 autograd through the dense matrix on row blocks of at most 1 GiB of
 differences.  --what solve: one preconditioned float64 solve of Kernel + Diag at 1 x 16384 on the descriptor route against
-the parent's route (the float64 gate patched shut), residuals printed.
+the parent's route (the float64 gate patched shut), residuals printed; --solve-cols right-hand sides.  --what wide: the
+column sweep behind ko64_wide (csrc/lo_kernel_shape.h): kernel_mv against kernel_mv_wide in float64, taking turns, over
+WIDE_COLS x WIDE_SHAPES; run it on a build whose ko64_wide returns false, or both sides are the same kernel.  --what iqld:
+a float64 inv_quad_logdet with 16 probes at 1 x 8192.
 
 No route depends on these numbers: the float64 gate is taken whenever it holds, because its purpose is memory (DESIGN.md
 section 6p).
-Usage:  python tools/mb_kernel_f64.py [--what product,derivs,solve] [--reps 20] [--rounds 5] [--families rbf,matern52]
+Usage:  python tools/mb_kernel_f64.py [--what product,derivs,solve,wide,iqld] [--reps 20] [--rounds 5] [--families rbf,matern52]
 One JSON line per measurement.
 """
 from __future__ import annotations
@@ -45,6 +48,8 @@ SHAPES = ((1, 16384, 4, True), (8, 8192, 16, True), (1, 131072, 8, False))
 COLS = (1, 17)
 DERIV_SHAPES = ((1, 16384, 4, 1), (1, 16384, 4, 17), (8, 8192, 16, 1))
 CHUNK_BYTES = 1 << 30
+WIDE_SHAPES = tuple((B, N, D) for B, N in ((1, 16384), (8, 8192)) for D in (4, 8, 16, 32))
+WIDE_COLS = (1, 2, 4, 5, 8, 9, 16, 17, 32, 33, 64, 65)
 
 
 def draw(B, N, D, gen, dev):
@@ -88,6 +93,59 @@ def product(args, dev, gen):
                                rel_diff=((y_n - y_d).norm() / y_d.norm()).item())
                     del dense
                 print(json.dumps(out), flush=True)
+
+
+def wide_columns(args, dev, gen):
+    dims = [int(d) for d in args.dims.split(",") if d]
+    cols = [int(c) for c in args.cols.split(",") if c] or WIDE_COLS
+    for B, N, D in WIDE_SHAPES:
+        if dims and D not in dims:
+            continue
+        x, ls, os_ = draw(B, N, D, gen, dev)
+        theta = K.kernel_theta(ls, os_, (B,), D, dtype=F64)
+        for name in args.families.split(","):
+            fam = covariance.FAMILIES[name].native_family
+            for c in cols:
+                v = torch.randn(B, N, c, generator=gen, dtype=F64).to(dev)
+                fns = [lambda: K.kernel_mv(x, x, theta, fam, v), lambda: K.kernel_mv_wide(x, x, theta, fam, v)]
+                times, per = alternated_within(fns, args.reps, args.rounds, turn_us=1e5)
+                y_n, y_w = fns[0](), fns[1]()
+                print(json.dumps(dict(
+                    what="kernel_mv_wide_f64", family=name, B=B, N=N, D=D, c=c, mv_us=r1(times[0]), wide_us=r1(times[1]),
+                    wide_over_mv=round(times[1][0] / times[0][0], 3), calls_per_turn=per,
+                    # the wide kernel wins when even its slowest round beats the other's fastest one
+                    wide_wins=times[1][2] < times[0][1], rel_diff=((y_w - y_n).norm() / y_n.norm()).item())),
+                    flush=True)
+
+
+def iqld(args, dev, gen):
+    """inv_quad_logdet of Kernel + Diag at 1 x 8192, D 4, with 16 probes (stochastic Lanczos quadrature), forward only."""
+    from linear_operator_amd.operators.added_diag_linear_operator import clear_preconditioner_memo
+
+    B, N, D = 1, 8192, 4
+    x, ls, os_ = draw(B, N, D, gen, dev)
+    noise = (0.05 + 0.1 * torch.rand(B, N, generator=gen, dtype=F64)).to(dev)
+    rhs = torch.randn(B, N, 1, generator=gen, dtype=F64).to(dev)
+    for name in args.families.split(","):
+        A = AddedDiagLinearOperator(KernelLinearOperator(x, x, covariance.FAMILIES[name],
+                                                         num_nonbatch_dimensions={"outputscale": 0}, lengthscale=ls,
+                                                         outputscale=os_), DiagLinearOperator(noise))
+        ms = []
+        with settings.max_cholesky_size(0), settings.cg_tolerance(args.cg_tolerance), settings.num_trace_samples(16), \
+                warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            for _ in range(1 + args.solve_rounds):
+                clear_preconditioner_memo()
+                torch.manual_seed(0)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                iq, ld = A.inv_quad_logdet(rhs, logdet=True)
+                torch.cuda.synchronize()
+                ms.append((time.perf_counter() - t0) * 1e3)
+        ms = sorted(ms[1:])  # (the first call warms up)
+        print(json.dumps(dict(what="kernel_iqld_f64", family=name, B=B, N=N, D=D, probes=16, inv_quad=iq.item(),
+                              logdet=ld.item(), ms=[round(ms[len(ms) // 2], 2), round(ms[0], 2), round(ms[-1], 2)])),
+              flush=True)
 
 
 def chunked_autograd(fn, x1, x2, ls, os_, U, V):
@@ -143,14 +201,14 @@ def solve(args, dev, gen):
     B, N, D = 1, 16384, 4
     x, ls, os_ = draw(B, N, D, gen, dev)
     noise = (0.05 + 0.1 * torch.rand(B, N, generator=gen, dtype=F64)).to(dev)
-    rhs = torch.randn(B, N, 1, generator=gen, dtype=F64).to(dev)
+    rhs = torch.randn(B, N, args.solve_cols, generator=gen, dtype=F64).to(dev)
     for name in args.families.split(","):
         fn = covariance.FAMILIES[name]
         A = AddedDiagLinearOperator(KernelLinearOperator(x, x, fn, num_nonbatch_dimensions={"outputscale": 0},
                                                          lengthscale=ls, outputscale=os_), DiagLinearOperator(noise))
-        out = dict(what="kernel_solve_f64", family=name, B=B, N=N, D=D, cg_tolerance=args.cg_tolerance)
+        out = dict(what="kernel_solve_f64", family=name, B=B, N=N, D=D, c=args.solve_cols, cg_tolerance=args.cg_tolerance)
         real = KernelLinearOperator._native_f64_refusal
-        for route in ("descriptor", "parent"):
+        for route in args.solve_routes.split(","):
             if route == "parent":
                 KernelLinearOperator._native_f64_refusal = lambda self, check_device=True: "shut"
             try:
@@ -182,6 +240,10 @@ def main():
     ap.add_argument("--cg-tolerance", type=float, default=1e-2)
     ap.add_argument("--families", default="rbf,matern52")
     ap.add_argument("--what", default="product,derivs,solve")
+    ap.add_argument("--solve-cols", type=int, default=1)
+    ap.add_argument("--solve-routes", default="descriptor,parent")
+    ap.add_argument("--dims", default="", help="wide: only these D")
+    ap.add_argument("--cols", default="", help="wide: only these column counts")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("mb_kernel_f64.py measures on the device; none is available")
@@ -193,6 +255,10 @@ def main():
         derivatives(args, "cuda", gen)
     if "solve" in what:
         solve(args, "cuda", gen)
+    if "wide" in what:
+        wide_columns(args, "cuda", gen)
+    if "iqld" in what:
+        iqld(args, "cuda", gen)
 
 
 if __name__ == "__main__":
