@@ -1147,6 +1147,21 @@ size_t lo_kernel_points_grad_f64_workspace_bytes(int64_t B, int64_t M, int64_t N
 int lo_kernel_points_grad_f64(const double* x1, const double* x2, const double* theta, int32_t family, int64_t B,
                               int64_t M, int64_t N, int64_t D, const double* U, const double* V, int64_t t, double* g_x1,
                               void* ws, size_t ws_bytes, void* stream);
+/* (ABI 45; csrc/lo_kernel_bil_wide_f64.hip) lo_kernel_bilinear_f64 and lo_kernel_points_grad_f64 for many columns t:
+ * W = U V^T runs on v_mfma_f64_16x16x4_f64, 52 / 48 / 16 / 28 columns per sweep at D <= 4 / 8 / 16 / 32, two lane swaps
+ * give every lane one row again, and r^2, the exp, the sqrt and the scaled differences of a pair are formed once per
+ * sweep, by direct differences as above.  Arguments, checks, error codes in their order, workspace bytes and layout and the
+ * column split are those of the two entries above; these entries always run the matrix-core kernel, for any t >= 1.
+ * lo_kernel_bilinear_f64 and lo_kernel_points_grad_f64 take it where ko64_bil_wide(t, DP) of csrc/lo_kernel_shape.h says
+ * so (a function of t and the padded dimension alone).  Fixed-order sums, no atomics: the same inputs give the same bits. */
+size_t lo_kernel_bilinear_wide_f64_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t D, int64_t t);
+int lo_kernel_bilinear_wide_f64(const double* x1, const double* x2, const double* theta, int32_t family, int64_t B,
+                                int64_t M, int64_t N, int64_t D, const double* U, const double* V, int64_t t,
+                                double* g_theta, void* ws, size_t ws_bytes, void* stream);
+size_t lo_kernel_points_grad_wide_f64_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t D, int64_t t);
+int lo_kernel_points_grad_wide_f64(const double* x1, const double* x2, const double* theta, int32_t family, int64_t B,
+                                   int64_t M, int64_t N, int64_t D, const double* U, const double* V, int64_t t,
+                                   double* g_x1, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- sums of matrix-free kernel operators over the same points (ABI 28; csrc/lo_kernel_sum.hip) ------------------------
  * K_ij = sum_t theta[t][D] g_{f_t}(r_t,ij), r_t,ij^2 = sum_d (theta[t][d] (x1[i, d] - x2[j, d]))^2 for T terms,

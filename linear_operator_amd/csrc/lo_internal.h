@@ -574,6 +574,23 @@ int kernel_mv_run_f64(const double* x1, const double* x2, const double* theta, i
 int kernel_mv_wide_run_f64(const double* x1, const double* x2, const double* theta, int family, int64_t B, int64_t M,
                            int64_t N, int64_t D, const double* v, int64_t c, const double* d, int dmode, int accumulate,
                            double* y, double* part, hipStream_t st);
+// The float64 derivatives of sum_s u_s^T K(x1, x2) v_s on validated arguments (lo_kernel_op_f64.hip), the twins of
+// kernel_bil_run / kernel_pgrad_run: part is the partials of ko_bil_layout<double> (hyperparameters) and of
+// ko_split_layout<double> with D columns (points)
+int kernel_bil_run_f64(const double* x1, const double* x2, const double* theta, int family, int64_t B, int64_t M,
+                       int64_t N, int64_t D, const double* U, const double* V, int64_t t, double* g_theta, double* part,
+                       hipStream_t st);
+int kernel_pgrad_run_f64(const double* x1, const double* x2, const double* theta, int family, int64_t B, int64_t M,
+                         int64_t N, int64_t D, const double* U, const double* V, int64_t t, double* g_x1, double* part,
+                         hipStream_t st);
+// The same with W = U V^T on the matrix cores (lo_kernel_bil_wide_f64.hip, k64_kernel_bil_wide): same arguments, same
+// partials; the two above take it where ko64_bil_wide(t, DP) of lo_kernel_shape.h says so.
+int kernel_bil_wide_run_f64(const double* x1, const double* x2, const double* theta, int family, int64_t B, int64_t M,
+                            int64_t N, int64_t D, const double* U, const double* V, int64_t t, double* g_theta,
+                            double* part, hipStream_t st);
+int kernel_pgrad_wide_run_f64(const double* x1, const double* x2, const double* theta, int family, int64_t B, int64_t M,
+                              int64_t N, int64_t D, const double* U, const double* V, int64_t t, double* g_x1,
+                              double* part, hipStream_t st);
 
 // ---- single-pass Woodbury apply fused with the CG r / x update (lo_precond_fused.hip) --------------
 bool precond_fused_eligible(int64_t B, int64_t N, int64_t c, int ldq, int S);

@@ -30,23 +30,7 @@ constexpr int ko64_ts() {
   return DP <= 8 ? 8 : (DP == 16 ? 4 : 2);
 }
 
-// waves per SIMD the derivative kernels are held to (the second argument of __launch_bounds__, i.e. amdgpu_waves_per_eu):
-// two (<= 256 VGPRs) up to DP = 16; at DP = 32 the point, the running and the tile sums are 192 VGPRs before anything
-// else, so one wave per SIMD, whose budget of 512 lets the accumulation registers hold what does not fit
-template <int DP>
-constexpr int ko64_waves() {
-  return DP == 32 ? 1 : 2;
-}
-
-// Sum over the 256 threads in a fixed order (wave butterfly, then waves 0..3); `red` >= 4 doubles of LDS
-__device__ __forceinline__ double block_sum256_d(double v, double* red) {
-  v = wave_sum_d(v);
-  const int w = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[w] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
+// (waves per SIMD of the derivative kernels: ko64_waves of lo_kernel_shape.h; block_sum256_d: lo_kernel_tile.h)
 
 // grid (row blocks, B, js); part == nullptr: y is written ([y +] K v + d o v), else the partial products [js, B, M, c]
 template <int FAMILY, int DP, int CC>
@@ -339,6 +323,51 @@ int kernel_mv_run_f64(const double* x1, const double* x2, const double* theta, i
   return LO_OK;
 }
 
+// g_theta from the partials of a bilinear sweep (k64_kernel_bil or k64_kernel_bil_wide), in ascending order
+int ko64_bil_reduce(const double* part, int nblk, int DP, int64_t B, int64_t D, const double* theta, double* g_theta,
+                    hipStream_t st) {
+  hipLaunchKernelGGL(k64_kernel_bil_reduce, dim3((unsigned)B), dim3(64), 0, st, part, nblk, DP, (int)D, theta, g_theta);
+  LO_LAUNCH_CHECK();
+  return LO_OK;
+}
+
+// the derivatives on validated arguments: the hyperparameters, part the partials of ko_bil_layout<double>, and the points
+// x1, part the partials of ko_split_layout<double> with D columns.  ko64_bil_wide (lo_kernel_shape.h) sends the
+// many-column calls to the matrix cores (lo_kernel_bil_wide_f64.hip)
+int kernel_bil_run_f64(const double* x1, const double* x2, const double* theta, int family, int64_t B, int64_t M,
+                       int64_t N, int64_t D, const double* U, const double* V, int64_t t, double* g_theta, double* part,
+                       hipStream_t st) {
+  const KoSweep w(B, M, N, D);
+  if (ko64_bil_wide(t, w.DP)) return kernel_bil_wide_run_f64(x1, x2, theta, family, B, M, N, D, U, V, t, g_theta, part, st);
+  LO_PROF_BEGIN("k64_kernel_bil", st);
+  ko_dispatch(family, w.DP, [&](auto F, auto P) {
+    hipLaunchKernelGGL((k64_kernel_bil<F(), P()>), w.grid, dim3(kThreads), 0, st, x1, x2, theta, (int)M, (int)N, (int)D, U,
+                       V, (int)t, part, w.s.jchunk);
+  });
+  LO_PROF_END(st);
+  LO_LAUNCH_CHECK();
+  return ko64_bil_reduce(part, w.s.rb * w.s.js, w.DP, B, D, theta, g_theta, st);
+}
+
+int kernel_pgrad_run_f64(const double* x1, const double* x2, const double* theta, int family, int64_t B, int64_t M,
+                         int64_t N, int64_t D, const double* U, const double* V, int64_t t, double* g_x1, double* part,
+                         hipStream_t st) {
+  const KoSweep w(B, M, N, D);
+  if (ko64_bil_wide(t, w.DP)) return kernel_pgrad_wide_run_f64(x1, x2, theta, family, B, M, N, D, U, V, t, g_x1, part, st);
+  double* out = w.s.js > 1 ? part : g_x1;
+  LO_PROF_BEGIN("k64_kernel_pgrad", st);
+  ko_dispatch(family, w.DP, [&](auto F, auto P) {
+    hipLaunchKernelGGL((k64_kernel_pgrad<F(), P()>), w.grid, dim3(kThreads), 0, st, x1, x2, theta, (int)M, (int)N, (int)D,
+                       U, V, (int)t, out, w.s.jchunk);
+  });
+  LO_PROF_END(st);
+  LO_LAUNCH_CHECK();
+  if (w.s.js > 1)  // the splits in ascending order (the reduction of the product with D as its columns and no diagonal)
+    return ko64_reduce_splits("k64_kernel_pgrad_reduce", part, w.s.js, (size_t)M * D, (size_t)B * M * D, (int)D, nullptr,
+                              LO_DIAG_NONE, 0, nullptr, g_x1, st);
+  return LO_OK;
+}
+
 // the one layout of the product's workspace: the partials of a split member
 double* kernel_mv_layout_f64(Arena& ar, int64_t B, int64_t M, int64_t N, int64_t c) {
   return ko_split_layout<double>(ar, B, M, N, c);
@@ -386,22 +415,10 @@ int lo_kernel_bilinear_f64(const double* x1, const double* x2, const double* the
   if (!x1 || !x2 || !theta || !U || !V || !g_theta || !ko_args_ok(B, M, N, D, t) || !ko_family_ok(family))
     return LO_ERR_BADARG;
   if (!ko_shape_ok(B, M, N, D) || t > 0x7fffffff) return LO_ERR_UNSUPPORTED;
-  hipStream_t st = (hipStream_t)stream;
   Arena ar(ws, ws_bytes, kKoTail);
   double* part = ko_bil_layout<double>(ar, B, M, N, D);
   if (!ws || !ar.ok) return LO_ERR_WORKSPACE;
-  const KoSweep w(B, M, N, D);
-  LO_PROF_BEGIN("k64_kernel_bil", st);
-  ko_dispatch(family, w.DP, [&](auto F, auto P) {
-    hipLaunchKernelGGL((k64_kernel_bil<F(), P()>), w.grid, dim3(kThreads), 0, st, x1, x2, theta, (int)M, (int)N, (int)D, U,
-                       V, (int)t, part, w.s.jchunk);
-  });
-  LO_PROF_END(st);
-  LO_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k64_kernel_bil_reduce, dim3((unsigned)B), dim3(64), 0, st, part, w.s.rb * w.s.js, w.DP, (int)D, theta,
-                     g_theta);
-  LO_LAUNCH_CHECK();
-  return LO_OK;
+  return kernel_bil_run_f64(x1, x2, theta, family, B, M, N, D, U, V, t, g_theta, part, (hipStream_t)stream);
 }
 
 size_t lo_kernel_points_grad_f64_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t D, int64_t t) {
@@ -415,23 +432,10 @@ int lo_kernel_points_grad_f64(const double* x1, const double* x2, const double* 
   if (!x1 || !x2 || !theta || !U || !V || !g_x1 || !ko_args_ok(B, M, N, D, t) || !ko_family_ok(family))
     return LO_ERR_BADARG;
   if (!ko_shape_ok(B, M, N, D) || t > 0x7fffffff) return LO_ERR_UNSUPPORTED;
-  hipStream_t st = (hipStream_t)stream;
   Arena ar(ws, ws_bytes, kKoTail);
   double* part = ko_split_layout<double>(ar, B, M, N, D);  // [js, B, M, D]
   if (!ws || !ar.ok) return LO_ERR_WORKSPACE;
-  const KoSweep w(B, M, N, D);
-  double* out = w.s.js > 1 ? part : g_x1;
-  LO_PROF_BEGIN("k64_kernel_pgrad", st);
-  ko_dispatch(family, w.DP, [&](auto F, auto P) {
-    hipLaunchKernelGGL((k64_kernel_pgrad<F(), P()>), w.grid, dim3(kThreads), 0, st, x1, x2, theta, (int)M, (int)N, (int)D,
-                       U, V, (int)t, out, w.s.jchunk);
-  });
-  LO_PROF_END(st);
-  LO_LAUNCH_CHECK();
-  if (w.s.js > 1)  // the splits in ascending order (the reduction of the product with D as its columns and no diagonal)
-    return ko64_reduce_splits("k64_kernel_pgrad_reduce", part, w.s.js, (size_t)M * D, (size_t)B * M * D, (int)D, nullptr,
-                              LO_DIAG_NONE, 0, nullptr, g_x1, st);
-  return LO_OK;
+  return kernel_pgrad_run_f64(x1, x2, theta, family, B, M, N, D, U, V, t, g_x1, part, (hipStream_t)stream);
 }
 
 }  // extern "C"

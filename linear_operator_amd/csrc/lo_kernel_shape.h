@@ -143,6 +143,33 @@ inline bool ko64_wide(int64_t c, int DP) { return c >= 9 || (c >= 5 && DP == 32)
 // y[b, i, col] = [y +] sum_z part[z, b, i, col] (ascending z) + d o v over `total` = B rows c doubles (lo_kernel_op_f64.hip)
 int ko64_reduce_splits(const char* prof_name, const double* part, int js, size_t per_member, size_t total, int c,
                        const double* d, int dmode, int accumulate, const double* v, double* y, hipStream_t st);
+// g_theta [B, D + 1] from the per-workgroup partials [B, nblk, DP + 1] of a float64 bilinear sweep, in ascending order
+// (lo_kernel_op_f64.hip, k64_kernel_bil_reduce): slot q < D times os2 / theta[q], slot DP as it is
+int ko64_bil_reduce(const double* part, int nblk, int DP, int64_t B, int64_t D, const double* theta, double* g_theta,
+                    hipStream_t st);
+// waves per SIMD the float64 derivative kernels are held to (the second argument of __launch_bounds__, i.e.
+// amdgpu_waves_per_eu): two (<= 256 VGPRs) up to DP = 16; at DP = 32 the point, the running and the tile sums are 192 VGPRs
+// before anything else, so one wave per SIMD, whose budget of 512 lets the accumulation registers hold what does not fit
+template <int DP>
+constexpr int ko64_waves() {
+  return DP == 32 ? 1 : 2;
+}
+// columns of U / V one sweep of the float64 wide derivatives carries (lo_kernel_bil_wide_f64.hip): the contraction length
+// of W = U V^T on v_mfma_f64_16x16x4_f64.  A lane keeps 2 cols VGPRs of B operands beside the 32 of the accumulators and
+// the 6 DP of its point, running and tile sums; the V tile is 1.125 cols KB of LDS beside DP KB of points.  The largest
+// multiple of 4 at which none of the 8 instantiations of a DP uses scratch under ko64_waves: 64 KB
+// of static LDS end DP 4, 8 and 32 (64064 / 63584 / 65312 bytes); registers end DP 16, where Matern-1/2's hyperparameter
+// kernel spills 20 bytes per lane at 20 columns (the other seven take 20, and 24 with 12 - 20 bytes in three of them)
+constexpr int ko64_bil_wide_cols(int DP) { return DP <= 4 ? 52 : (DP <= 8 ? 48 : (DP <= 16 ? 16 : 28)); }
+// Which of the two kernel_bil_run_f64 and kernel_pgrad_run_f64 launch: a function of the column count and the padded
+// dimension alone, read by those two and nothing else.  The cells come from the derivative sweep of tools/mb_kernel_f64.py
+// --what wide_derivs: a cell is routed to k64_kernel_bil_wide only where its slowest round beat the
+// plain kernel's fastest.  From 9 columns on (a second sweep of the plain kernels at DP <= 8) it won in every cell of both
+// kernels: 0.56 - 0.65 of the time at 9 .. 16 columns and 0.27 - 0.46 from 17 on at DP 4 and 8, 0.30 - 0.47 at DP 16,
+// 0.11 - 0.33 at DP 32.  At 5 .. 8 columns it won at DP 16 (0.56 - 0.60: two sweeps of four) and DP 32 (0.27 - 0.53: three
+// or four sweeps of two) and lost at DP 4 and 8 (1.05 - 1.12: one sweep either way).  t <= 4 always stays on k64_kernel_bil
+// / k64_kernel_pgrad, which tests/test_gpu_kernel_variants.py pins by name.
+inline bool ko64_bil_wide(int64_t t, int DP) { return t >= 9 || (t >= 5 && DP >= 16); }
 
 // gradient kernel (lo_kernel_grad.hip), by the padded dimension: a thread holds (DP + 1) CC running sums and as many tile
 // sums, and every instantiation stays at 3 waves per SIMD (<= 168 VGPRs) without scratch -- 4 columns at DP 4, 2 at DP 8, 1

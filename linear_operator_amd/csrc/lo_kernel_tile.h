@@ -16,6 +16,16 @@ __device__ __forceinline__ void ko_stage_points(const T* __restrict__ x2b, const
   }
 }
 
+// Sum over the 256 threads in a fixed order (wave butterfly, then waves 0..3); `red` >= 4 doubles of LDS
+__device__ __forceinline__ double block_sum256_d(double v, double* red) {
+  v = wave_sum_d(v);
+  const int w = threadIdx.x >> 6;
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[w] = v;
+  __syncthreads();
+  return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
 // a compensated (Kahan) running sum: the one-number-per-member entries of the derivatives, N M terms of both signs
 struct KoKahan {
   float s = 0.0f, c = 0.0f;

@@ -702,23 +702,27 @@ def kernel_points_grad(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, 
 
 def kernel_bilinear_wide(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, family: int, U: torch.Tensor,
                          V: torch.Tensor) -> torch.Tensor:
-    """lo_kernel_bilinear_wide_f32: kernel_bilinear on the many-column kernel (csrc/lo_kernel_bil_wide.hip: W = U V^T on
-    the matrix cores, 32 columns per sweep), whatever the column count; float32 only.  kernel_bilinear takes this kernel
-    by itself where it is the faster one."""
-    x1, x2, theta, _, U, V, (B, M, N, D, _, t), _ = _kernel_args("kernel_bilinear_wide", x1, x2, theta, V, U)
-    g = torch.empty(B, D + 1, dtype=torch.float32, device=U.device)
-    name, sizer = _kernel_entry("lo_kernel_bilinear_wide", False)
+    """lo_kernel_bilinear_wide_f32 (all operands float64: lo_kernel_bilinear_wide_f64): kernel_bilinear on the
+    many-column kernel (csrc/lo_kernel_bil_wide.hip: W = U V^T on the matrix cores, 32 columns per sweep; float64:
+    csrc/lo_kernel_bil_wide_f64.hip, 16 to 52 columns per sweep), whatever the column count.  kernel_bilinear takes this
+    kernel by itself where it is the faster one."""
+    x1, x2, theta, _, U, V, (B, M, N, D, _, t), dtype = _kernel_args("kernel_bilinear_wide", x1, x2, theta, V, U,
+                                                                        twin=True)
+    g = torch.empty(B, D + 1, dtype=dtype, device=U.device)
+    name, sizer = _kernel_entry("lo_kernel_bilinear_wide", dtype == torch.float64)
     _launch(name, U.device, x1, x2, theta, int(family), B, M, N, D, U, V, t, g, ws_bytes=sizer(B, M, N, D, t))
     return g
 
 
 def kernel_points_grad_wide(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, family: int, U: torch.Tensor,
                             V: torch.Tensor) -> torch.Tensor:
-    """lo_kernel_points_grad_wide_f32: kernel_points_grad on the many-column kernel (csrc/lo_kernel_bil_wide.hip),
-    whatever the column count; float32 only.  kernel_points_grad takes this kernel by itself where it is the faster one."""
-    x1, x2, theta, _, U, V, (B, M, N, D, _, t), _ = _kernel_args("kernel_points_grad_wide", x1, x2, theta, V, U)
-    g = torch.empty(B, M, D, dtype=torch.float32, device=U.device)
-    name, sizer = _kernel_entry("lo_kernel_points_grad_wide", False)
+    """lo_kernel_points_grad_wide_f32 (all operands float64: lo_kernel_points_grad_wide_f64): kernel_points_grad on the
+    many-column kernel (csrc/lo_kernel_bil_wide.hip; float64: csrc/lo_kernel_bil_wide_f64.hip), whatever the column
+    count.  kernel_points_grad takes this kernel by itself where it is the faster one."""
+    x1, x2, theta, _, U, V, (B, M, N, D, _, t), dtype = _kernel_args("kernel_points_grad_wide", x1, x2, theta, V, U,
+                                                                        twin=True)
+    g = torch.empty(B, M, D, dtype=dtype, device=U.device)
+    name, sizer = _kernel_entry("lo_kernel_points_grad_wide", dtype == torch.float64)
     _launch(name, U.device, x1, x2, theta, int(family), B, M, N, D, U, V, t, g, ws_bytes=sizer(B, M, N, D, t))
     return g
 

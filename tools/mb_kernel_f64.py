@@ -14,11 +14,14 @@ differences.  --what solve: one preconditioned float64 solve of Kernel + Diag at
 the parent's route (the float64 gate patched shut), residuals printed; --solve-cols right-hand sides.  --what wide: the
 column sweep behind ko64_wide (csrc/lo_kernel_shape.h): kernel_mv against kernel_mv_wide in float64, taking turns, over
 WIDE_COLS x WIDE_SHAPES; run it on a build whose ko64_wide returns false, or both sides are the same kernel.  --what iqld:
-a float64 inv_quad_logdet with 16 probes at 1 x 8192.
+a float64 inv_quad_logdet with 16 probes at 1 x 8192 (--backward: with the backward pass through both terms).  --what
+wide_derivs: the sweep behind ko64_bil_wide: kernel_bilinear / kernel_points_grad against their _wide twins
+(csrc/lo_kernel_bil_wide_f64.hip) in float64, taking turns, over WIDE_SHAPES x BIL_COLS; as with --what wide, the plain side
+is the plain kernel only on a build whose ko64_bil_wide returns false.
 
 No route depends on these numbers: the float64 gate is taken whenever it holds, because its purpose is memory (DESIGN.md
 section 6p).
-Usage:  python tools/mb_kernel_f64.py [--what product,derivs,solve,wide,iqld] [--reps 20] [--rounds 5] [--families rbf,matern52]
+Usage:  python tools/mb_kernel_f64.py [--what product,derivs,solve,wide,iqld,wide_derivs] [--reps 20] [--rounds 5] [--families rbf,matern52]
 One JSON line per measurement.
 """
 from __future__ import annotations
@@ -50,6 +53,7 @@ DERIV_SHAPES = ((1, 16384, 4, 1), (1, 16384, 4, 17), (8, 8192, 16, 1))
 CHUNK_BYTES = 1 << 30
 WIDE_SHAPES = tuple((B, N, D) for B, N in ((1, 16384), (8, 8192)) for D in (4, 8, 16, 32))
 WIDE_COLS = (1, 2, 4, 5, 8, 9, 16, 17, 32, 33, 64, 65)
+BIL_COLS = (5, 8, 9, 11, 16, 17, 33, 65)  # the columns t of the derivative sweep
 
 
 def draw(B, N, D, gen, dev):
@@ -118,15 +122,45 @@ def wide_columns(args, dev, gen):
                     flush=True)
 
 
+def wide_derivatives(args, dev, gen):
+    dims = [int(d) for d in args.dims.split(",") if d]
+    cols = [int(c) for c in args.cols.split(",") if c] or BIL_COLS
+    for B, N, D in WIDE_SHAPES:
+        if dims and D not in dims:
+            continue
+        x, ls, os_ = draw(B, N, D, gen, dev)
+        theta = K.kernel_theta(ls, os_, (B,), D, dtype=F64)
+        for name in args.families.split(","):
+            fam = covariance.FAMILIES[name].native_family
+            for t in cols:
+                U = torch.randn(B, N, t, generator=gen, dtype=F64).to(dev)
+                V = torch.randn(B, N, t, generator=gen, dtype=F64).to(dev)
+                for what, old, new in (("kernel_bilinear_wide_f64", K.kernel_bilinear, K.kernel_bilinear_wide),
+                                       ("kernel_points_grad_wide_f64", K.kernel_points_grad, K.kernel_points_grad_wide)):
+                    fns = [lambda: old(x, x, theta, fam, U, V), lambda: new(x, x, theta, fam, U, V)]
+                    times, per = alternated_within(fns, args.reps, args.rounds, turn_us=5e4)
+                    g_o, g_w = fns[0](), fns[1]()
+                    print(json.dumps(dict(
+                        what=what, family=name, B=B, N=N, D=D, t=t, plain_us=r1(times[0]), wide_us=r1(times[1]),
+                        wide_over_plain=round(times[1][0] / times[0][0], 3), calls_per_turn=per,
+                        # the wide kernel wins when even its slowest round beats the other's fastest one
+                        wide_wins=times[1][2] < times[0][1], rel_diff=((g_w - g_o).norm() / g_o.norm()).item())),
+                        flush=True)
+
+
 def iqld(args, dev, gen):
-    """inv_quad_logdet of Kernel + Diag at 1 x 8192, D 4, with 16 probes (stochastic Lanczos quadrature), forward only."""
+    """inv_quad_logdet of Kernel + Diag at 1 x 8192, D 4, with 16 probes (stochastic Lanczos quadrature); --backward: the
+    backward pass of inv_quad + logdet to the points, the lengthscale, the outputscale and the noise is timed with it."""
     from linear_operator_amd.operators.added_diag_linear_operator import clear_preconditioner_memo
 
     B, N, D = 1, 8192, 4
     x, ls, os_ = draw(B, N, D, gen, dev)
     noise = (0.05 + 0.1 * torch.rand(B, N, generator=gen, dtype=F64)).to(dev)
     rhs = torch.randn(B, N, 1, generator=gen, dtype=F64).to(dev)
+    leaves = (x, ls, os_, noise)
     for name in args.families.split(","):
+        for leaf in leaves:
+            leaf.requires_grad_(args.backward)
         A = AddedDiagLinearOperator(KernelLinearOperator(x, x, covariance.FAMILIES[name],
                                                          num_nonbatch_dimensions={"outputscale": 0}, lengthscale=ls,
                                                          outputscale=os_), DiagLinearOperator(noise))
@@ -140,10 +174,15 @@ def iqld(args, dev, gen):
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
                 iq, ld = A.inv_quad_logdet(rhs, logdet=True)
+                if args.backward:
+                    for leaf in leaves:
+                        leaf.grad = None
+                    (iq.sum() + ld.sum()).backward()
                 torch.cuda.synchronize()
                 ms.append((time.perf_counter() - t0) * 1e3)
         ms = sorted(ms[1:])  # (the first call warms up)
-        print(json.dumps(dict(what="kernel_iqld_f64", family=name, B=B, N=N, D=D, probes=16, inv_quad=iq.item(),
+        print(json.dumps(dict(what="kernel_iqld_f64", family=name, B=B, N=N, D=D, probes=16, backward=args.backward,
+                              inv_quad=iq.item(),
                               logdet=ld.item(), ms=[round(ms[len(ms) // 2], 2), round(ms[0], 2), round(ms[-1], 2)])),
               flush=True)
 
@@ -243,7 +282,8 @@ def main():
     ap.add_argument("--solve-cols", type=int, default=1)
     ap.add_argument("--solve-routes", default="descriptor,parent")
     ap.add_argument("--dims", default="", help="wide: only these D")
-    ap.add_argument("--cols", default="", help="wide: only these column counts")
+    ap.add_argument("--cols", default="", help="wide, wide_derivs: only these column counts")
+    ap.add_argument("--backward", action="store_true", help="iqld: time the backward pass too")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("mb_kernel_f64.py measures on the device; none is available")
@@ -257,6 +297,8 @@ def main():
         solve(args, "cuda", gen)
     if "wide" in what:
         wide_columns(args, "cuda", gen)
+    if "wide_derivs" in what:
+        wide_derivatives(args, "cuda", gen)
     if "iqld" in what:
         iqld(args, "cuda", gen)
 
