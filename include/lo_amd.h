@@ -1346,6 +1346,23 @@ int lo_kernel_sm_points_grad_f32(const float* x1, const float* x2, const float* 
                                  int64_t N, int64_t D, const float* U, const float* V, int64_t t, float* g_x1, void* ws,
                                  size_t ws_bytes, void* stream);
 
+/* (ABI 46; csrc/lo_kernel_kinds_wide.hip) lo_kernel_param_mv_f32 and lo_kernel_sm_mv_f32 for many columns: the kernel
+ * value is formed as above, by the same device functions in the same order, ONCE per 32 columns, and its product with v
+ * runs on v_mfma_f32_32x32x2_f32 (exact fp32 products, fp32 accumulation).  256 rows per workgroup as two 32-row tiles per
+ * wave, x2 staged in LDS tiles of 128, v as [128][32]; a tile's sums on their own and then added to the running ones, the
+ * column split with its ascending reduce.  No atomics: two calls give equal bits.  The arguments, the checks, the error
+ * codes and their order are those of the one-column twins above, the sizers equal theirs, and the kernel runs for ANY
+ * c >= 1.  lo_kernel_param_mv_f32 / lo_kernel_sm_mv_f32 and the two kinds of lo_matvec_f32 take this kernel by themselves
+ * where it measured faster (kp_wide / ksm_wide of csrc/lo_kernel_shape.h).                                              */
+size_t lo_kernel_param_mv_wide_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t D, int64_t c);
+int lo_kernel_param_mv_wide_f32(const float* x1, const float* x2, const float* theta, int32_t family, int64_t B,
+                                int64_t M, int64_t N, int64_t D, const float* v, int64_t c, const float* d,
+                                int32_t diag_mode, float* y, void* ws, size_t ws_bytes, void* stream);
+size_t lo_kernel_sm_mv_wide_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t D, int64_t Q, int64_t c);
+int lo_kernel_sm_mv_wide_f32(const float* x1, const float* x2, const float* theta, int32_t Q, int64_t B, int64_t M,
+                             int64_t N, int64_t D, const float* v, int64_t c, const float* d, int32_t diag_mode, float* y,
+                             void* ws, size_t ws_bytes, void* stream);
+
 /* ---- matrix-free derivative GP: the Matern-5/2 gradient kernel (ABI 41; csrc/lo_kernel_mgrad.hip) ---------------------
  * y [B, M (D + 1), c] = K(x1, x2) v (+ d o v) for the block matrix of LO_OP_KERNEL_MGRAD_DIAG, rows i (D + 1) + a over
  * x1 [B, M, D], columns j (D + 1) + b over x2 [B, N, D], theta [B, D + 1] as for lo_kernel_mv_f32.  With t_k = theta[k],

@@ -27,33 +27,10 @@ namespace lo {
 
 constexpr float kKpPi = 3.14159265358979323846f;
 
-inline bool kp_family_ok(int64_t family) { return family == LO_KERNEL_RQ || family == LO_KERNEL_PERIODIC; }
-inline bool kp_shape_ok(int64_t B, int64_t M, int64_t N, int64_t D) {
-  return D <= LO_KERNEL_PARAM_MAX_DIM && ko_shape_ok(B, M, N, D);
-}
-using kp_families = std::integer_sequence<int, LO_KERNEL_RQ, LO_KERNEL_PERIODIC>;
-template <class F>
-inline void kp_dispatch(int family, int DP, F&& f) {
-  ko_pick(kp_families{}, family, [&](auto fam) { ko_pick(ko_dims{}, DP, [&](auto dp) { f(fam, dp); }); });
-}
-
 // the one layout of the derivative's workspace: a partial [2 DP + 2] per workgroup, [B, rb js, 2 DP + 2]
 inline float* kp_bil_layout(Arena& ar, int64_t B, int64_t M, int64_t N, int64_t D) {
   const KoShape s = ko_shape(B, M, N);
   return ar.take<float>((size_t)B * s.rb * s.js * (2 * ko_padded_dim(D) + 2));
-}
-
-// what a workgroup reads of its member's theta: th[k] = t_k, sc[k] = the factor the points are scaled by (RQ: t_k,
-// PERIODIC: nu_k), both 0 for k >= D
-template <int FAMILY, int DP>
-__device__ __forceinline__ void kp_load_theta(const float* __restrict__ tb, int D, float* th, float* sc) {
-  if (threadIdx.x < DP) {
-    const int k = threadIdx.x;
-    const float t = k < D ? tb[k] : 0.0f;
-    th[k] = t;
-    sc[k] = FAMILY == LO_KERNEL_PERIODIC ? (k < D ? tb[D + 2 + k] : 0.0f) : t;
-  }
-  __syncthreads();
 }
 
 // grid (row blocks, B, js); part == nullptr: y is written with the diagonal term, else partial products [js, B, M, c]
@@ -377,6 +354,8 @@ static int kernel_param_mv_run(const float* x1, const float* x2, const float* th
                                int64_t N, int64_t D, const float* v, int64_t c, const float* d, int dmode, float* y,
                                float* part, const int* stop, hipStream_t st) {
   const KoSweep w(B, M, N, D);
+  if (kp_wide(family, c, w.DP))  // many columns: the product on the matrix cores (lo_kernel_kinds_wide.hip)
+    return kernel_param_mv_wide_run(x1, x2, theta, family, B, M, N, D, v, c, d, dmode, y, part, stop, st);
   float* p = w.s.js > 1 ? part : nullptr;
   if (M != N) dmode = LO_DIAG_NONE;
   LO_PROF_BEGIN("k_kparam_mv", st);
@@ -412,11 +391,6 @@ int kernel_param_matvec_run(const MatvecPlan* pl, const float* v, float* y, cons
   const lo_op_desc& op = pl->op;
   return kernel_param_mv_run(op.A0, op.A0, op.A1, (int)op.n2, op.B, op.N, op.N, op.R, v, pl->c, op.d, op.diag_mode, y,
                              pl->ko.part, stop, st);
-}
-
-// the entry points' diagonal operand: ko_diag_ok, and no mode at all on a rectangular product
-static bool kp_diag_ok(int diag_mode, const void* d, bool square) {
-  return ko_diag_ok(diag_mode, d, square) && (square || diag_mode == LO_DIAG_NONE);
 }
 
 }  // namespace lo

@@ -235,6 +235,53 @@ int kernel_pgrad_wide_run(const float* x1, const float* x2, const float* theta, 
 // every caller stay the kernels they were, which tests/test_gpu_kernel_variants.py pins by name.
 inline bool ko_bil_wide(int64_t t, int DP) { return t >= 9; }
 
+// ---- the kinds with a pair value of their own: rational quadratic / periodic (lo_kernel_param.hip) and spectral mixture
+// (lo_kernel_sm.hip); what their entry points and those of lo_kernel_kinds_wide.hip are held to ---------------------------
+inline bool kp_family_ok(int64_t family) { return family == LO_KERNEL_RQ || family == LO_KERNEL_PERIODIC; }
+inline bool kp_shape_ok(int64_t B, int64_t M, int64_t N, int64_t D) {
+  return D <= LO_KERNEL_PARAM_MAX_DIM && ko_shape_ok(B, M, N, D);
+}
+using kp_families = std::integer_sequence<int, LO_KERNEL_RQ, LO_KERNEL_PERIODIC>;
+template <class F>
+inline void kp_dispatch(int family, int DP, F&& f) {
+  ko_pick(kp_families{}, family, [&](auto fam) { ko_pick(ko_dims{}, DP, [&](auto dp) { f(fam, dp); }); });
+}
+inline bool ksm_args_ok(int64_t B, int64_t M, int64_t N, int64_t D, int64_t Q, int64_t c) {
+  return ko_args_ok(B, M, N, D, c) && Q >= 1;
+}
+inline bool ksm_shape_ok(int64_t B, int64_t M, int64_t N, int64_t D, int64_t Q, int64_t c) {
+  return D <= LO_KERNEL_SM_MAX_DIM && Q <= LO_KERNEL_SM_MAX_MIX && ko_shape_ok(B, M, N, D) && c <= 0x7fffffff;
+}
+using ksm_dims = std::integer_sequence<int, 4, 8, 16>;  // ko_padded_dim up to LO_KERNEL_SM_MAX_DIM
+// the diagonal operand of both kinds' products: ko_diag_ok, and no mode at all on a rectangular product
+inline bool kp_diag_ok(int diag_mode, const void* d, bool square) {
+  return ko_diag_ok(diag_mode, d, square) && (square || diag_mode == LO_DIAG_NONE);
+}
+inline bool ksm_diag_ok(int diag_mode, const void* d, bool square) { return kp_diag_ok(diag_mode, d, square); }
+
+// Their many-column products on the matrix cores (lo_kernel_kinds_wide.hip, k_kinds_mv_wide): the arguments and the
+// partials of kernel_param_mv_run / kernel_sm_mv_run.
+int kernel_param_mv_wide_run(const float* x1, const float* x2, const float* theta, int family, int64_t B, int64_t M,
+                             int64_t N, int64_t D, const float* v, int64_t c, const float* d, int dmode, float* y,
+                             float* part, const int* stop, hipStream_t st);
+int kernel_sm_mv_wide_run(const float* x1, const float* x2, const float* theta, int Q, int64_t B, int64_t M, int64_t N,
+                          int64_t D, const float* v, int64_t c, const float* d, int dmode, float* y, float* part,
+                          const int* stop, hipStream_t st);
+// Which of the two kernel_param_mv_run and kernel_sm_mv_run launch: functions of the family, the column count and the
+// padded dimension alone, read by those two and nothing else.  The cells come from the column sweeps of
+// tools/mb_kernel_param.py and tools/mb_kernel_sm.py (--what wide): a cell is routed to
+// k_kinds_mv_wide only where its slowest round beat the one-column kernel's fastest.  From 17 columns on (a second sweep of
+// k_kparam_mv / k_ksm_mv) it won in every cell of every family: 0.35 - 0.77 of the time.  At 5 .. 16 columns rational
+// quadratic won at DP 16 and 32 (0.68 - 0.78) and lost at DP 4 and 8 (1.03 - 1.09); periodic won at DP 32 only (0.95 -
+// 0.96; 1.08 - 1.12 below: its D sines per pair leave the ALU no room beside the matrix cores); spectral mixture won at
+// every DP and both Q (0.93 - 0.98).  Up to 4 columns the one-column kernels are kept everywhere, c = 1 included, which
+// tests/test_gpu_kernel_variants.py pins by name (the wide kernel won 8 of those 36 cells, rational quadratic at DP 32 by
+// 11 - 20 % and spectral mixture by 2 - 11 %, and lost the others by 1 - 97 %).
+inline bool kp_wide(int family, int64_t c, int DP) {
+  return c >= 17 || (c >= 5 && DP >= (family == LO_KERNEL_PERIODIC ? 32 : 16));
+}
+inline bool ksm_wide(int64_t c, int DP) { return c >= 5; }
+
 // y[b, i, col] = sum_z part[z, b, i, col] (ascending z) + d o v over `total` = B rows c elements (lo_kernel_op.hip)
 int ko_reduce_splits(const char* prof_name, const float* part, int js, size_t per_member, size_t total, int c,
                      const float* d, int dmode, const float* v, float* y, const int* stop, hipStream_t st);

@@ -31,45 +31,10 @@
 
 namespace lo {
 
-constexpr int kKsmQ = LO_KERNEL_SM_MAX_MIX;
-
-inline bool ksm_args_ok(int64_t B, int64_t M, int64_t N, int64_t D, int64_t Q, int64_t c) {
-  return ko_args_ok(B, M, N, D, c) && Q >= 1;
-}
-inline bool ksm_shape_ok(int64_t B, int64_t M, int64_t N, int64_t D, int64_t Q, int64_t c) {
-  return D <= LO_KERNEL_SM_MAX_DIM && Q <= LO_KERNEL_SM_MAX_MIX && ko_shape_ok(B, M, N, D) && c <= 0x7fffffff;
-}
-using ksm_dims = std::integer_sequence<int, 4, 8, 16>;  // ko_padded_dim up to LO_KERNEL_SM_MAX_DIM
-
 // the one layout of the derivative's workspace: a partial [2 DP + 1] per workgroup, [B, Q, rb js, 2 DP + 1]
 inline float* ksm_bil_layout(Arena& ar, int64_t B, int64_t M, int64_t N, int64_t D, int64_t Q) {
   const KoShape s = ko_shape(B, M, N);
   return ar.take<float>((size_t)B * Q * s.rb * s.js * (2 * ko_padded_dim(D) + 1));
-}
-
-// the member's theta in LDS: tw[q] = w_q, tmu[q][k] = |mu_qk|, tsg[q][k] = sigma_qk, both 0 for k >= D (Q DP <= 256 words)
-template <int DP>
-__device__ __forceinline__ void ksm_load_theta(const float* __restrict__ tb, int D, int Q, float* tw, float* tmu,
-                                               float* tsg) {
-  const int e = threadIdx.x;
-  if (e < Q * DP) {
-    const int q = e / DP, k = e - q * DP;
-    const float* t = tb + q * (2 * D + 1);
-    tmu[e] = k < D ? fabsf(t[1 + k]) : 0.0f;
-    tsg[e] = k < D ? t[1 + D + k] : 0.0f;
-  }
-  if (e < Q) tw[e] = tb[e * (2 * D + 1)];
-  __syncthreads();
-}
-
-// stage the tile [jt, jt + nj) of x2 as xs[j][DP], raw (coordinates >= D are 0)
-template <int DP>
-__device__ __forceinline__ void ksm_stage_points(const float* __restrict__ x2b, int D, int jt, int nj,
-                                                 float* __restrict__ xs) {
-  for (int e = threadIdx.x; e < nj * DP; e += kThreads) {
-    const int j = e / DP, dd = e - j * DP;
-    xs[e] = dd < D ? x2b[(size_t)(jt + j) * D + dd] : 0.0f;
-  }
 }
 
 // stage the rows [jt, jt + nj) of the right operand, columns [c0, c0 + CC) of its c, as vs[j][CC] (columns >= c are 0)
@@ -385,6 +350,8 @@ static int kernel_sm_mv_run(const float* x1, const float* x2, const float* theta
                             int64_t D, const float* v, int64_t c, const float* d, int dmode, float* y, float* part,
                             const int* stop, hipStream_t st) {
   const KoSweep w(B, M, N, D);
+  if (ksm_wide(c, w.DP))  // many columns: the product on the matrix cores (lo_kernel_kinds_wide.hip)
+    return kernel_sm_mv_wide_run(x1, x2, theta, Q, B, M, N, D, v, c, d, dmode, y, part, stop, st);
   float* p = w.s.js > 1 ? part : nullptr;
   if (M != N) dmode = LO_DIAG_NONE;
   LO_PROF_BEGIN("k_ksm_mv", st);
@@ -420,11 +387,6 @@ int kernel_sm_matvec_run(const MatvecPlan* pl, const float* v, float* y, const i
   const lo_op_desc& op = pl->op;
   return kernel_sm_mv_run(op.A0, op.A0, op.A1, (int)op.n2, op.B, op.N, op.N, op.R, v, pl->c, op.d, op.diag_mode, y,
                           pl->ko.part, stop, st);
-}
-
-// the entry points' diagonal operand: ko_diag_ok, and no mode at all on a rectangular product
-static bool ksm_diag_ok(int diag_mode, const void* d, bool square) {
-  return ko_diag_ok(diag_mode, d, square) && (square || diag_mode == LO_DIAG_NONE);
 }
 
 }  // namespace lo

@@ -1,5 +1,5 @@
 // lo_kernel_tile.h -- what the sweeps of the matrix-free kernel family share on the device (lo_kernel_op.hip,
-// lo_kernel_op_f64.hip, lo_kernel_param.hip).  Plain inlined functions: a kernel that uses one compiles to the
+// lo_kernel_op_f64.hip, lo_kernel_param.hip, lo_kernel_sm.hip, lo_kernel_kinds_wide.hip).  Plain inlined functions: a kernel that uses one compiles to the
 // instructions it had with the text written out (profiles/r19 holds the comparison, and the helpers that did not pass it).
 #pragma once
 #include "lo_internal.h"
@@ -13,6 +13,48 @@ __device__ __forceinline__ void ko_stage_points(const T* __restrict__ x2b, const
   for (int e = threadIdx.x; e < nj * DP; e += kThreads) {
     const int j = e / DP, dd = e - j * DP;
     xs[e] = dd < D ? x2b[(size_t)(jt + j) * D + dd] * sc[dd] : T(0);
+  }
+}
+
+// ---- what the kernels of the rational-quadratic / periodic kind share (lo_kernel_param.hip, lo_kernel_kinds_wide.hip) -----
+// what a workgroup reads of its member's theta: th[k] = t_k, sc[k] = the factor the points are scaled by (RQ: t_k,
+// PERIODIC: nu_k), both 0 for k >= D
+template <int FAMILY, int DP>
+__device__ __forceinline__ void kp_load_theta(const float* __restrict__ tb, int D, float* th, float* sc) {
+  if (threadIdx.x < DP) {
+    const int k = threadIdx.x;
+    const float t = k < D ? tb[k] : 0.0f;
+    th[k] = t;
+    sc[k] = FAMILY == LO_KERNEL_PERIODIC ? (k < D ? tb[D + 2 + k] : 0.0f) : t;
+  }
+  __syncthreads();
+}
+
+// ---- what the kernels of the spectral mixture kind share (lo_kernel_sm.hip, lo_kernel_kinds_wide.hip) --------------------
+constexpr int kKsmQ = LO_KERNEL_SM_MAX_MIX;
+
+// the member's theta in LDS: tw[q] = w_q, tmu[q][k] = |mu_qk|, tsg[q][k] = sigma_qk, both 0 for k >= D (Q DP <= 256 words)
+template <int DP>
+__device__ __forceinline__ void ksm_load_theta(const float* __restrict__ tb, int D, int Q, float* tw, float* tmu,
+                                               float* tsg) {
+  const int e = threadIdx.x;
+  if (e < Q * DP) {
+    const int q = e / DP, k = e - q * DP;
+    const float* t = tb + q * (2 * D + 1);
+    tmu[e] = k < D ? fabsf(t[1 + k]) : 0.0f;
+    tsg[e] = k < D ? t[1 + D + k] : 0.0f;
+  }
+  if (e < Q) tw[e] = tb[e * (2 * D + 1)];
+  __syncthreads();
+}
+
+// stage the tile [jt, jt + nj) of x2 as xs[j][DP], raw (coordinates >= D are 0)
+template <int DP>
+__device__ __forceinline__ void ksm_stage_points(const float* __restrict__ x2b, int D, int jt, int nj,
+                                                 float* __restrict__ xs) {
+  for (int e = threadIdx.x; e < nj * DP; e += kThreads) {
+    const int j = e / DP, dd = e - j * DP;
+    xs[e] = dd < D ? x2b[(size_t)(jt + j) * D + dd] : 0.0f;
   }
 }
 

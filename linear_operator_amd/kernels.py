@@ -766,18 +766,30 @@ def kernel_param_diag_descriptor(X: torch.Tensor, theta: torch.Tensor, family: i
                                          n2=int(family), batch_shape=X.shape[:-2]), d, const_diag)
 
 
+def _kernel_param_mv(what, stem, x1, x2, theta, family, v, d, const_diag):
+    family = _kernel_param_family(what, family)
+    x1, x2, theta, _, _, v, (B, M, N, D, _, c), dtype = _kernel_args(what, x1, x2, theta, v, d=d,
+                                                                      width=2 * x1.shape[-1] + 2)
+    d, mode = _kernel_diag(d, B, N, const_diag)
+    y = torch.empty(B, M, c, dtype=dtype, device=v.device)
+    name, sizer = _kernel_entry(stem, False)
+    _launch(name, v.device, x1, x2, theta, family, B, M, N, D, v, c, d, mode, y, ws_bytes=sizer(B, M, N, D, c))
+    return y
+
+
 def kernel_param_mv(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, family: int, v: torch.Tensor,
                     d: Optional[torch.Tensor] = None, const_diag: bool = False) -> torch.Tensor:
     """lo_kernel_param_mv_f32: y [B, M, c] = K(x1, x2) v (+ d o v; d only when M == N), x1 [B, M, D], x2 [B, N, D], theta
     [B, 2 D + 2], v [B, N, c].  A shape the kernel does not take raises."""
-    family = _kernel_param_family("kernel_param_mv", family)
-    x1, x2, theta, _, _, v, (B, M, N, D, _, c), dtype = _kernel_args("kernel_param_mv", x1, x2, theta, v, d=d,
-                                                                      width=2 * x1.shape[-1] + 2)
-    d, mode = _kernel_diag(d, B, N, const_diag)
-    y = torch.empty(B, M, c, dtype=dtype, device=v.device)
-    name, sizer = _kernel_entry("lo_kernel_param_mv", False)
-    _launch(name, v.device, x1, x2, theta, family, B, M, N, D, v, c, d, mode, y, ws_bytes=sizer(B, M, N, D, c))
-    return y
+    return _kernel_param_mv("kernel_param_mv", "lo_kernel_param_mv", x1, x2, theta, family, v, d, const_diag)
+
+
+def kernel_param_mv_wide(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, family: int, v: torch.Tensor,
+                         d: Optional[torch.Tensor] = None, const_diag: bool = False) -> torch.Tensor:
+    """lo_kernel_param_mv_wide_f32: kernel_param_mv on the many-column kernel (csrc/lo_kernel_kinds_wide.hip: the product
+    with v on the matrix cores, 32 columns per sweep), whatever the column count.  kernel_param_mv takes this kernel by
+    itself where it is the faster one."""
+    return _kernel_param_mv("kernel_param_mv_wide", "lo_kernel_param_mv_wide", x1, x2, theta, family, v, d, const_diag)
 
 
 def kernel_param_bilinear(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, family: int, U: torch.Tensor,
@@ -845,16 +857,28 @@ def kernel_sm_diag_descriptor(X: torch.Tensor, theta: torch.Tensor, d: Optional[
                                          n2=Q, batch_shape=X.shape[:-2]), d, const_diag)
 
 
+def _kernel_sm_mv(what, stem, x1, x2, theta, v, d, const_diag):
+    x1, x2, theta, _, v, (B, M, N, D, Q, c) = _kernel_sm_args(what, x1, x2, theta, v, d=d)
+    d, mode = _kernel_diag(d, B, N, const_diag)
+    y = torch.empty(B, M, c, dtype=torch.float32, device=v.device)
+    name, sizer = _kernel_entry(stem, False)
+    _launch(name, v.device, x1, x2, theta, Q, B, M, N, D, v, c, d, mode, y, ws_bytes=sizer(B, M, N, D, Q, c))
+    return y
+
+
 def kernel_sm_mv(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, v: torch.Tensor,
                  d: Optional[torch.Tensor] = None, const_diag: bool = False) -> torch.Tensor:
     """lo_kernel_sm_mv_f32: y [B, M, c] = K(x1, x2) v (+ d o v; d only when M == N), x1 [B, M, D], x2 [B, N, D], theta
     [B, Q, 2 D + 1], v [B, N, c].  A shape the kernel does not take raises."""
-    x1, x2, theta, _, v, (B, M, N, D, Q, c) = _kernel_sm_args("kernel_sm_mv", x1, x2, theta, v, d=d)
-    d, mode = _kernel_diag(d, B, N, const_diag)
-    y = torch.empty(B, M, c, dtype=torch.float32, device=v.device)
-    name, sizer = _kernel_entry("lo_kernel_sm_mv", False)
-    _launch(name, v.device, x1, x2, theta, Q, B, M, N, D, v, c, d, mode, y, ws_bytes=sizer(B, M, N, D, Q, c))
-    return y
+    return _kernel_sm_mv("kernel_sm_mv", "lo_kernel_sm_mv", x1, x2, theta, v, d, const_diag)
+
+
+def kernel_sm_mv_wide(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, v: torch.Tensor,
+                      d: Optional[torch.Tensor] = None, const_diag: bool = False) -> torch.Tensor:
+    """lo_kernel_sm_mv_wide_f32: kernel_sm_mv on the many-column kernel (csrc/lo_kernel_kinds_wide.hip: the product with v
+    on the matrix cores, 32 columns per sweep), whatever the column count.  kernel_sm_mv takes this kernel by itself where
+    it is the faster one."""
+    return _kernel_sm_mv("kernel_sm_mv_wide", "lo_kernel_sm_mv_wide", x1, x2, theta, v, d, const_diag)
 
 
 def kernel_sm_bilinear(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, U: torch.Tensor,

@@ -11,11 +11,19 @@ it; device events after warm-up).
   solve     one preconditioned solve of SM + D at 1 x 8192 (D 1, Q 4): the native descriptor against the dense callback
             route (the gate patched shut); a fresh operator per solve, host clock around a synchronise
 
+  wide      column sweep: lo_kernel_sm_mv_wide_f32 (csrc/lo_kernel_kinds_wide.hip, the product with V on the matrix cores)
+            against lo_kernel_sm_mv_f32 over the column counts WIDE_COLS at WIDE_SHAPES, the two taking turns.  ksm_wide of
+            csrc/lo_kernel_shape.h is set from this table, so the comparison is against k_ksm_mv
+            only on a build whose ksm_wide returns false: where the rule routes, both calls run the same kernel
+  widesolve the 17-column preconditioned solve at 1 x 16384 and the 16-probe inv_quad_logdet at 1 x 8192 (D 1, Q 4, rank-15
+            pivoted Cholesky preconditioner, cg_tolerance 1e-3), host clock around a synchronise, median of --rounds calls:
+            one build per process, run in alternated processes against the build to compare with
+
 Shapes 1 x 16384 (D 1, Q 4: the time-series shape) and 8 x 8192 (D 4, Q 4).  The dense function holds [Q, M, N, D]
 intermediates (4 GiB per tensor per member at both shapes), so every dense route runs member by member; a route that runs
 out of memory is reported as null.  No routing rests on these numbers: inside its gate the kernel is always taken, its
 purpose is memory.
-Usage:  python tools/mb_kernel_sm.py [--what product,bilinear,points,solve] [--reps 20] [--rounds 5]
+Usage:  python tools/mb_kernel_sm.py [--what product,bilinear,points,solve,wide,widesolve] [--reps 20] [--rounds 5]
 One JSON line per measurement.
 """
 from __future__ import annotations
@@ -44,6 +52,8 @@ SHAPES = ((1, 16384, 1, 4), (8, 8192, 4, 4))  # (B, n, D, Q)
 COLS = (1, 17)
 DERIV_COLS = 8
 SOLVE = (1, 8192, 1, 4)
+WIDE_SHAPES = ((1, 16384, 1, 4), (1, 16384, 4, 4), (1, 16384, 16, 4), (1, 16384, 4, 16))  # (B, n, D, Q): every padded D, both Q
+WIDE_COLS = (1, 2, 4, 5, 8, 16, 17, 32, 33, 64)
 NB = {"mixture_weights": 1}
 NAMES = ("mixture_weights", "mixture_means", "mixture_scales")
 FN = covariance.spectral_mixture
@@ -177,6 +187,46 @@ def solve(args, dev, gen):
                           native_over_callback=round(med[0] / med[1], 4), rel_diff=rel_diff(a, b))), flush=True)
 
 
+def wide_columns(args, dev, gen):
+    for B, n, D, Q in WIDE_SHAPES:
+        x, _, theta = make(B, n, D, Q, gen, dev)
+        for c in WIDE_COLS:
+            V = torch.randn(B, n, c, generator=gen).to(dev)
+            fns = [lambda: K.kernel_sm_mv(x, x, theta, V), lambda: K.kernel_sm_mv_wide(x, x, theta, V)]
+            times = alternated(fns, args.reps, args.rounds)
+            print(json.dumps(dict(
+                what="kernel_sm_mv_wide", B=B, n=n, D=D, Q=Q, c=c, mv_us=r1(times[0]), wide_us=r1(times[1]),
+                wide_over_mv=round(times[1][0] / times[0][0], 3),
+                # the wide kernel wins when even its slowest round beats the other's fastest one
+                wide_wins=times[1][2] < times[0][1], rel_diff=rel_diff(fns[1](), fns[0]()))), flush=True)
+
+
+def wide_solves(args, dev, gen):
+    def clock(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    for what, n, c in (("solve", 16384, 17), ("inv_quad_logdet", 8192, 16)):
+        x, p, _ = make(1, n, 1, 4, gen, dev)
+        noise = (0.05 + 0.1 * torch.rand(1, n, generator=gen)).to(dev)
+        rhs = torch.randn(1, n, c if what == "solve" else 1, generator=gen).to(dev)
+
+        def run():
+            A = AddedDiagLinearOperator(KernelLinearOperator(x, x, FN, num_nonbatch_dimensions=NB, **p),
+                                        DiagLinearOperator(noise))
+            return A.solve(rhs) if what == "solve" else A.inv_quad_logdet(rhs, logdet=True)
+
+        with settings.max_cholesky_size(0), settings.min_preconditioning_size(0), settings.cg_tolerance(1e-3), \
+                settings.max_preconditioner_size(15), settings.num_trace_samples(c):
+            run()  # (warm-up)
+            times = [clock(run) for _ in range(args.rounds)]
+        print(json.dumps(dict(what="wide_" + what, n=n, D=1, Q=4, columns=c,
+                              ms=[round(t, 2) for t in (statistics.median(times), min(times), max(times))])), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -191,6 +241,10 @@ def main():
             solve(args, "cuda", gen)
         elif what == "product":
             product(args, "cuda", gen)
+        elif what == "wide":
+            wide_columns(args, "cuda", gen)
+        elif what == "widesolve":
+            wide_solves(args, "cuda", gen)
         else:
             derivatives(args, "cuda", gen, what)
 
