@@ -1363,6 +1363,34 @@ int lo_kernel_sm_mv_wide_f32(const float* x1, const float* x2, const float* thet
                              int64_t N, int64_t D, const float* v, int64_t c, const float* d, int32_t diag_mode, float* y,
                              void* ws, size_t ws_bytes, void* stream);
 
+/* (ABI 47; csrc/lo_kernel_kinds_bil_wide.hip) the derivatives of both kinds for many columns: W = U V^T runs on
+ * v_mfma_f32_32x32x2_f32, up to 32 columns per sweep, v_permlane32_swap_b32 hands every row back to one lane, and every
+ * kernel value and derivative factor is formed as above, by the same device functions, ONCE per pair and sweep of 32
+ * columns instead of once per 8.  The sums per coordinate are taken in the order of the twins above; the one-number
+ * entries (os2, alpha, the mixture weight) are added in float64 per lane and per workgroup and rounded to float32 once per
+ * partial, where the twins keep a compensated float32 sum.  Split, partials, reductions and slot orders are the twins'; no
+ * atomics: two calls give equal bits.  The arguments, the checks, the error codes and their order are the twins', the
+ * sizers equal theirs, and the kernel runs for ANY t >= 1.  lo_kernel_param_bilinear_f32 / _points_grad_f32 and
+ * lo_kernel_sm_bilinear_f32 / _points_grad_f32 take this kernel by themselves from 9 columns on, where it measured faster
+ * in every cell (kp_bil_wide / ksm_bil_wide of csrc/lo_kernel_shape.h); their results there differ from ABI 46's by the
+ * order in which W is summed and by the float64 sums.                                                                     */
+size_t lo_kernel_param_bilinear_wide_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t D, int64_t t);
+int lo_kernel_param_bilinear_wide_f32(const float* x1, const float* x2, const float* theta, int32_t family, int64_t B,
+                                      int64_t M, int64_t N, int64_t D, const float* U, const float* V, int64_t t,
+                                      float* g_theta, void* ws, size_t ws_bytes, void* stream);
+size_t lo_kernel_param_points_grad_wide_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t D, int64_t t);
+int lo_kernel_param_points_grad_wide_f32(const float* x1, const float* x2, const float* theta, int32_t family, int64_t B,
+                                         int64_t M, int64_t N, int64_t D, const float* U, const float* V, int64_t t,
+                                         float* g_x1, void* ws, size_t ws_bytes, void* stream);
+size_t lo_kernel_sm_bilinear_wide_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t D, int64_t Q, int64_t t);
+int lo_kernel_sm_bilinear_wide_f32(const float* x1, const float* x2, const float* theta, int32_t Q, int64_t B, int64_t M,
+                                   int64_t N, int64_t D, const float* U, const float* V, int64_t t, float* g_theta,
+                                   void* ws, size_t ws_bytes, void* stream);
+size_t lo_kernel_sm_points_grad_wide_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t D, int64_t Q, int64_t t);
+int lo_kernel_sm_points_grad_wide_f32(const float* x1, const float* x2, const float* theta, int32_t Q, int64_t B,
+                                      int64_t M, int64_t N, int64_t D, const float* U, const float* V, int64_t t,
+                                      float* g_x1, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- matrix-free derivative GP: the Matern-5/2 gradient kernel (ABI 41; csrc/lo_kernel_mgrad.hip) ---------------------
  * y [B, M (D + 1), c] = K(x1, x2) v (+ d o v) for the block matrix of LO_OP_KERNEL_MGRAD_DIAG, rows i (D + 1) + a over
  * x1 [B, M, D], columns j (D + 1) + b over x2 [B, N, D], theta [B, D + 1] as for lo_kernel_mv_f32.  With t_k = theta[k],

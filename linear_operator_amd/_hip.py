@@ -51,7 +51,7 @@ LO_OP_KERNEL_MGRAD_DIAG = 20
 LO_DIAG_NONE, LO_DIAG_FULL, LO_DIAG_CONST = 0, 1, 2
 LO_BLOCK_DIAG, LO_BLOCK_INTERLEAVED, LO_BLOCK_SUM = 0, 1, 2
 LO_EIGH_MAX_N = 1024
-ABI_VERSION = 46
+ABI_VERSION = 47
 
 LO_ERR_UNSUPPORTED = -4
 LO_FUSED_OK, LO_FUSED_EARLY_STOP, LO_FUSED_CONTINUE, LO_FUSED_TIMEOUT = 0, 1, 2, 3
@@ -342,6 +342,10 @@ _PROTOTYPES = {
     "lo_kernel_param_bilinear_f32": (ci, [vp, vp, vp, i32, i64, i64, i64, i64, vp, vp, i64, vp, vp, sz, vp]),
     "lo_kernel_param_points_grad_workspace_bytes": (sz, [i64, i64, i64, i64, i64]),
     "lo_kernel_param_points_grad_f32": (ci, [vp, vp, vp, i32, i64, i64, i64, i64, vp, vp, i64, vp, vp, sz, vp]),
+    "lo_kernel_param_bilinear_wide_workspace_bytes": (sz, [i64, i64, i64, i64, i64]),
+    "lo_kernel_param_bilinear_wide_f32": (ci, [vp, vp, vp, i32, i64, i64, i64, i64, vp, vp, i64, vp, vp, sz, vp]),
+    "lo_kernel_param_points_grad_wide_workspace_bytes": (sz, [i64, i64, i64, i64, i64]),
+    "lo_kernel_param_points_grad_wide_f32": (ci, [vp, vp, vp, i32, i64, i64, i64, i64, vp, vp, i64, vp, vp, sz, vp]),
     "lo_kernel_mgrad_mv_workspace_bytes": (sz, [i64, i64, i64, i64, i64]),
     "lo_kernel_mgrad_mv_f32": (ci, [vp, vp, vp, i64, i64, i64, i64, vp, i64, vp, i32, vp, vp, sz, vp]),
     "lo_kernel_mgrad_bilinear_workspace_bytes": (sz, [i64, i64, i64, i64, i64]),
@@ -354,6 +358,10 @@ _PROTOTYPES = {
     "lo_kernel_sm_bilinear_f32": (ci, [vp, vp, vp, i32, i64, i64, i64, i64, vp, vp, i64, vp, vp, sz, vp]),
     "lo_kernel_sm_points_grad_workspace_bytes": (sz, [i64, i64, i64, i64, i64, i64]),
     "lo_kernel_sm_points_grad_f32": (ci, [vp, vp, vp, i32, i64, i64, i64, i64, vp, vp, i64, vp, vp, sz, vp]),
+    "lo_kernel_sm_bilinear_wide_workspace_bytes": (sz, [i64, i64, i64, i64, i64, i64]),
+    "lo_kernel_sm_bilinear_wide_f32": (ci, [vp, vp, vp, i32, i64, i64, i64, i64, vp, vp, i64, vp, vp, sz, vp]),
+    "lo_kernel_sm_points_grad_wide_workspace_bytes": (sz, [i64, i64, i64, i64, i64, i64]),
+    "lo_kernel_sm_points_grad_wide_f32": (ci, [vp, vp, vp, i32, i64, i64, i64, i64, vp, vp, i64, vp, vp, sz, vp]),
     "lo_cholesky_workspace_bytes": (sz, [i64, i64]),
     "lo_cholesky_f32": (ci, [vp, vp, vp, vp, i64, i64, vp, sz, vp]),
     "lo_tri_solve_f32": (ci, [vp, vp, vp, vp, i64, i64, i64, i32, i32, vp]),

@@ -25,14 +25,6 @@
 
 namespace lo {
 
-constexpr float kKpPi = 3.14159265358979323846f;
-
-// the one layout of the derivative's workspace: a partial [2 DP + 2] per workgroup, [B, rb js, 2 DP + 2]
-inline float* kp_bil_layout(Arena& ar, int64_t B, int64_t M, int64_t N, int64_t D) {
-  const KoShape s = ko_shape(B, M, N);
-  return ar.take<float>((size_t)B * s.rb * s.js * (2 * ko_padded_dim(D) + 2));
-}
-
 // grid (row blocks, B, js); part == nullptr: y is written with the diagonal term, else partial products [js, B, M, c]
 template <int FAMILY, int DP, int CC>
 __global__ __launch_bounds__(kThreads) void k_kparam_mv(const float* __restrict__ x1, const float* __restrict__ x2,
@@ -111,40 +103,6 @@ __global__ __launch_bounds__(kThreads) void k_kparam_mv(const float* __restrict_
         }
       }
     }
-  }
-}
-
-// The pair of the two derivative sweeps: from the thread's point a and the tile's point xs[j] the value g and per
-// coordinate what the lengthscale / period / points sums take.
-//   RQ:        g, h, ga as kp_rq_gha; e1[k] = the scaled difference s_k (lengthscale: h s_k^2, points: h s_k)
-//   PERIODIC:  g; e1[k] = (t_k s_k)^2, e2[k] = t_k^2 |phi_k| sin(2 pi |phi_k|) (even in phi), or with POINTS
-//              e2[k] = sin(2 pi phi_k) (odd: the sign put back)
-template <int FAMILY, int DP, bool POINTS>
-__device__ __forceinline__ void kp_pair(const float (&a)[DP], const float* __restrict__ xj, const float* __restrict__ th,
-                                        float alpha, float inv2a, float* g, float* h, float* ga, float (&e1)[DP],
-                                        float (&e2)[DP]) {
-  float sum = 0.0f;
-#pragma unroll
-  for (int k = 0; k < DP; ++k) {
-    const float df = a[k] - xj[k];
-    if constexpr (FAMILY == LO_KERNEL_PERIODIC) {
-      const float p = fabsf(df);
-      const float ts = th[k] * kp_sinpi(p);
-      const float s2 = kp_sin2pi(p);
-      e1[k] = ts * ts;
-      e2[k] = POINTS ? (df < 0.0f ? -s2 : s2) : th[k] * th[k] * p * s2;
-      sum += e1[k];
-    } else {
-      e1[k] = df;
-      sum = fmaf(df, df, sum);
-    }
-  }
-  if constexpr (FAMILY == LO_KERNEL_PERIODIC) {
-    *g = kp_per_g(sum);
-    *h = 0.0f;
-    *ga = 0.0f;
-  } else {
-    kp_rq_gha(sum, alpha, inv2a, g, h, ga);
   }
 }
 
@@ -373,6 +331,51 @@ static int kernel_param_mv_run(const float* x1, const float* x2, const float* th
   return LO_OK;
 }
 
+int kp_bil_reduce(const float* part, int nblk, int DP, int64_t B, int64_t D, int family, const float* theta,
+                  float* g_theta, hipStream_t st) {
+  hipLaunchKernelGGL(k_kparam_bil_reduce, dim3((unsigned)B), dim3(128), 0, st, part, nblk, DP, (int)D, family, theta,
+                     g_theta);
+  LO_LAUNCH_CHECK();
+  return LO_OK;
+}
+
+// the derivatives on validated arguments: part the partials of kp_bil_layout / of ko_split_layout with D columns
+static int kernel_param_bil_run(const float* x1, const float* x2, const float* theta, int family, int64_t B, int64_t M,
+                                int64_t N, int64_t D, const float* U, const float* V, int64_t t, float* g_theta,
+                                float* part, hipStream_t st) {
+  const KoSweep w(B, M, N, D);
+  if (kp_bil_wide(family, t, w.DP))  // many columns: W on the matrix cores (lo_kernel_kinds_bil_wide.hip)
+    return kernel_param_bil_wide_run(x1, x2, theta, family, B, M, N, D, U, V, t, g_theta, part, st);
+  LO_PROF_BEGIN("k_kparam_bil", st);
+  kp_dispatch(family, w.DP, [&](auto F, auto P) {
+    hipLaunchKernelGGL((k_kparam_bil<F(), P()>), w.grid, dim3(kThreads), 0, st, x1, x2, theta, (int)M, (int)N, (int)D, U, V,
+                       (int)t, part, w.s.jchunk);
+  });
+  LO_PROF_END(st);
+  LO_LAUNCH_CHECK();
+  return kp_bil_reduce(part, w.s.rb * w.s.js, w.DP, B, D, family, theta, g_theta, st);
+}
+
+static int kernel_param_pgrad_run(const float* x1, const float* x2, const float* theta, int family, int64_t B, int64_t M,
+                                  int64_t N, int64_t D, const float* U, const float* V, int64_t t, float* g_x1,
+                                  float* part, hipStream_t st) {
+  const KoSweep w(B, M, N, D);
+  if (kp_bil_wide(family, t, w.DP))
+    return kernel_param_pgrad_wide_run(x1, x2, theta, family, B, M, N, D, U, V, t, g_x1, part, st);
+  float* out = w.s.js > 1 ? part : g_x1;
+  LO_PROF_BEGIN("k_kparam_pgrad", st);
+  kp_dispatch(family, w.DP, [&](auto F, auto P) {
+    hipLaunchKernelGGL((k_kparam_pgrad<F(), P()>), w.grid, dim3(kThreads), 0, st, x1, x2, theta, (int)M, (int)N, (int)D, U,
+                       V, (int)t, out, w.s.jchunk);
+  });
+  LO_PROF_END(st);
+  LO_LAUNCH_CHECK();
+  if (w.s.js > 1)  // the splits in ascending order (the reduction of the product with D as its columns and no diagonal)
+    return ko_reduce_splits("k_kparam_pgrad_reduce", part, w.s.js, (size_t)M * D, (size_t)B * M * D, (int)D, nullptr,
+                            LO_DIAG_NONE, nullptr, g_x1, nullptr, st);
+  return LO_OK;
+}
+
 int kernel_param_desc_check(const lo_op_desc* op) {
   if (!op->A0 || !op->A1 || op->R < 1 || !kp_family_ok(op->n2)) return LO_ERR_BADARG;
   return op->R > LO_KERNEL_PARAM_MAX_DIM ? LO_ERR_UNSUPPORTED : LO_OK;
@@ -428,22 +431,10 @@ int lo_kernel_param_bilinear_f32(const float* x1, const float* x2, const float* 
   if (!x1 || !x2 || !theta || !U || !V || !g_theta || !ko_args_ok(B, M, N, D, t) || !kp_family_ok(family))
     return LO_ERR_BADARG;
   if (!kp_shape_ok(B, M, N, D) || t > 0x7fffffff) return LO_ERR_UNSUPPORTED;
-  hipStream_t st = (hipStream_t)stream;
   Arena ar(ws, ws_bytes, kKoTail);
   float* part = kp_bil_layout(ar, B, M, N, D);
   if (!ws || !ar.ok) return LO_ERR_WORKSPACE;
-  const KoSweep w(B, M, N, D);
-  LO_PROF_BEGIN("k_kparam_bil", st);
-  kp_dispatch(family, w.DP, [&](auto F, auto P) {
-    hipLaunchKernelGGL((k_kparam_bil<F(), P()>), w.grid, dim3(kThreads), 0, st, x1, x2, theta, (int)M, (int)N, (int)D, U, V,
-                       (int)t, part, w.s.jchunk);
-  });
-  LO_PROF_END(st);
-  LO_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_kparam_bil_reduce, dim3((unsigned)B), dim3(128), 0, st, part, w.s.rb * w.s.js, w.DP, (int)D,
-                     (int)family, theta, g_theta);
-  LO_LAUNCH_CHECK();
-  return LO_OK;
+  return kernel_param_bil_run(x1, x2, theta, family, B, M, N, D, U, V, t, g_theta, part, (hipStream_t)stream);
 }
 
 size_t lo_kernel_param_points_grad_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t D, int64_t t) {
@@ -457,23 +448,10 @@ int lo_kernel_param_points_grad_f32(const float* x1, const float* x2, const floa
   if (!x1 || !x2 || !theta || !U || !V || !g_x1 || !ko_args_ok(B, M, N, D, t) || !kp_family_ok(family))
     return LO_ERR_BADARG;
   if (!kp_shape_ok(B, M, N, D) || t > 0x7fffffff) return LO_ERR_UNSUPPORTED;
-  hipStream_t st = (hipStream_t)stream;
   Arena ar(ws, ws_bytes, kKoTail);
   float* part = ko_split_layout<float>(ar, B, M, N, D);  // [js, B, M, D]
   if (!ws || !ar.ok) return LO_ERR_WORKSPACE;
-  const KoSweep w(B, M, N, D);
-  float* out = w.s.js > 1 ? part : g_x1;
-  LO_PROF_BEGIN("k_kparam_pgrad", st);
-  kp_dispatch(family, w.DP, [&](auto F, auto P) {
-    hipLaunchKernelGGL((k_kparam_pgrad<F(), P()>), w.grid, dim3(kThreads), 0, st, x1, x2, theta, (int)M, (int)N, (int)D, U,
-                       V, (int)t, out, w.s.jchunk);
-  });
-  LO_PROF_END(st);
-  LO_LAUNCH_CHECK();
-  if (w.s.js > 1)  // the splits in ascending order (the reduction of the product with D as its columns and no diagonal)
-    return ko_reduce_splits("k_kparam_pgrad_reduce", part, w.s.js, (size_t)M * D, (size_t)B * M * D, (int)D, nullptr,
-                            LO_DIAG_NONE, nullptr, g_x1, nullptr, st);
-  return LO_OK;
+  return kernel_param_pgrad_run(x1, x2, theta, family, B, M, N, D, U, V, t, g_x1, part, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -282,6 +282,55 @@ inline bool kp_wide(int family, int64_t c, int DP) {
 }
 inline bool ksm_wide(int64_t c, int DP) { return c >= 5; }
 
+// The layouts of their derivatives' workspaces: a partial per workgroup, [B, rb js, 2 DP + 2] (k_kparam_bil_reduce) and
+// [B, Q, rb js, 2 DP + 1] (k_ksm_bil_reduce)
+inline float* kp_bil_layout(Arena& ar, int64_t B, int64_t M, int64_t N, int64_t D) {
+  const KoShape s = ko_shape(B, M, N);
+  return ar.take<float>((size_t)B * s.rb * s.js * (2 * ko_padded_dim(D) + 2));
+}
+inline float* ksm_bil_layout(Arena& ar, int64_t B, int64_t M, int64_t N, int64_t D, int64_t Q) {
+  const KoShape s = ko_shape(B, M, N);
+  return ar.take<float>((size_t)B * Q * s.rb * s.js * (2 * ko_padded_dim(D) + 1));
+}
+// g_theta from those partials in ascending order, with the factors (lo_kernel_param.hip, lo_kernel_sm.hip)
+int kp_bil_reduce(const float* part, int nblk, int DP, int64_t B, int64_t D, int family, const float* theta,
+                  float* g_theta, hipStream_t st);
+int ksm_bil_reduce(const float* part, int nblk, int DP, int64_t B, int64_t D, int64_t Q, const float* theta,
+                   float* g_theta, hipStream_t st);
+
+// Their many-column derivatives with W = U V^T on the matrix cores (lo_kernel_kinds_bil_wide.hip, k_kinds_bil_wide): the
+// arguments and the partials of kernel_param_bil_run / kernel_param_pgrad_run / kernel_sm_bil_run / kernel_sm_pgrad_run.
+int kernel_param_bil_wide_run(const float* x1, const float* x2, const float* theta, int family, int64_t B, int64_t M,
+                              int64_t N, int64_t D, const float* U, const float* V, int64_t t, float* g_theta,
+                              float* part, hipStream_t st);
+int kernel_param_pgrad_wide_run(const float* x1, const float* x2, const float* theta, int family, int64_t B, int64_t M,
+                                int64_t N, int64_t D, const float* U, const float* V, int64_t t, float* g_x1, float* part,
+                                hipStream_t st);
+int kernel_sm_bil_wide_run(const float* x1, const float* x2, const float* theta, int Q, int64_t B, int64_t M, int64_t N,
+                           int64_t D, const float* U, const float* V, int64_t t, float* g_theta, float* part,
+                           hipStream_t st);
+int kernel_sm_pgrad_wide_run(const float* x1, const float* x2, const float* theta, int Q, int64_t B, int64_t M, int64_t N,
+                             int64_t D, const float* U, const float* V, int64_t t, float* g_x1, float* part,
+                             hipStream_t st);
+// columns of U / V one sweep of those kernels carries, next to ko_bil_wide_cols: half of them per lane in registers for
+// each of two rows, beside the lane's point, its running and tile sums and the 32 accumulators of W.  32, but 16 for
+// periodic at DP 32, whose hyperparameter kernel (five arrays of 32 and two float64 sums) uses 76 bytes of scratch per
+// lane at 32 (DESIGN.md section 6zc holds the table)
+constexpr int kp_bil_wide_cols(int family, int DP) { return family == LO_KERNEL_PERIODIC && DP == 32 ? 16 : 32; }
+constexpr int ksm_bil_wide_cols(int DP) { return 32; }
+// Which of the two those four run functions launch: functions of the family, the column count and the padded dimension
+// alone, read by them and nothing else.  The cells come from the derivative sweeps of tools/mb_kernel_param.py and
+// tools/mb_kernel_sm.py (--what bilwide): a cell is routed to k_kinds_bil_wide only where its slowest
+// round beat the plain kernel's fastest.  From 9 columns on (a second sweep of the plain kernels) it won in every cell of
+// every family and both kernels: at 9 .. 16 columns 0.44 - 0.66 of the time (rational quadratic at DP 32: 0.61 - 0.84),
+// from 17 on 0.24 - 0.66 (the points of periodic at DP 32, which sweeps 16 columns: 0.65 - 0.86).  Up to 8 columns it won 45
+// of the 64 rational-quadratic / periodic cells (0.78 - 0.99) and lost the others (1.00 - 1.55, most of them at DP 32),
+// and, of spectral mixture, the points at DP 4 (0.92 - 0.98) but no hyperparameter cell (1.01 - 1.30); those cells keep
+// the plain kernels whatever the sweep says: t <= 8 stays on k_kparam_bil / k_kparam_pgrad / k_ksm_bil / k_ksm_pgrad, which
+// tests/test_gpu_kernel_variants.py pins by name.
+inline bool kp_bil_wide(int family, int64_t t, int DP) { return t >= 9; }
+inline bool ksm_bil_wide(int64_t t, int DP) { return t >= 9; }
+
 // y[b, i, col] = sum_z part[z, b, i, col] (ascending z) + d o v over `total` = B rows c elements (lo_kernel_op.hip)
 int ko_reduce_splits(const char* prof_name, const float* part, int js, size_t per_member, size_t total, int c,
                      const float* d, int dmode, const float* v, float* y, const int* stop, hipStream_t st);

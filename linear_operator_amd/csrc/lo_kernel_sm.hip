@@ -31,12 +31,6 @@
 
 namespace lo {
 
-// the one layout of the derivative's workspace: a partial [2 DP + 1] per workgroup, [B, Q, rb js, 2 DP + 1]
-inline float* ksm_bil_layout(Arena& ar, int64_t B, int64_t M, int64_t N, int64_t D, int64_t Q) {
-  const KoShape s = ko_shape(B, M, N);
-  return ar.take<float>((size_t)B * Q * s.rb * s.js * (2 * ko_padded_dim(D) + 1));
-}
-
 // stage the rows [jt, jt + nj) of the right operand, columns [c0, c0 + CC) of its c, as vs[j][CC] (columns >= c are 0)
 template <int CC>
 __device__ __forceinline__ void ksm_stage_cols(const float* __restrict__ vb, int c, int c0, int jt, int nj,
@@ -45,40 +39,6 @@ __device__ __forceinline__ void ksm_stage_cols(const float* __restrict__ vb, int
     const int j = e / CC, cc = e - j * CC;
     vs[e] = c0 + cc < c ? vb[(size_t)(jt + j) * c + c0 + cc] : 0.0f;
   }
-}
-
-// one mixture of one pair: the envelope E, the cosines c[k] and, with SINES, the sines s[k] of 2 pi |mu_k| tau_k
-template <int DP, bool SINES>
-__device__ __forceinline__ float ksm_mixture(const float (&tau)[DP], const float* __restrict__ mu,
-                                             const float* __restrict__ sg, float (&c)[DP], float (&s)[DP]) {
-  float s2 = 0.0f;
-#pragma unroll
-  for (int k = 0; k < DP; ++k) {
-    const float st = sg[k] * tau[k];
-    s2 = fmaf(st, st, s2);
-    const float p = mu[k] * tau[k];
-    c[k] = ksm_cos2pi(p);
-    if constexpr (SINES) s[k] = kp_sin2pi(p);
-  }
-  return ksm_env(s2);
-}
-
-// ex[k] = prod_{l != k} c_l by a prefix and a suffix product; returns prod_l c_l
-template <int DP>
-__device__ __forceinline__ float ksm_leave_one_out(const float (&c)[DP], float (&ex)[DP]) {
-  float pre = 1.0f;
-#pragma unroll
-  for (int k = 0; k < DP; ++k) {
-    ex[k] = pre;
-    pre *= c[k];
-  }
-  float suf = 1.0f;
-#pragma unroll
-  for (int k = DP - 1; k >= 0; --k) {
-    ex[k] *= suf;
-    suf *= c[k];
-  }
-  return pre;
 }
 
 // grid (row blocks, B, js); part == nullptr: y is written with the diagonal term, else partial products [js, B, M, c]
@@ -369,6 +329,51 @@ static int kernel_sm_mv_run(const float* x1, const float* x2, const float* theta
   return LO_OK;
 }
 
+int ksm_bil_reduce(const float* part, int nblk, int DP, int64_t B, int64_t D, int64_t Q, const float* theta,
+                   float* g_theta, hipStream_t st) {
+  hipLaunchKernelGGL(k_ksm_bil_reduce, dim3((unsigned)(B * Q)), dim3(64), 0, st, part, nblk, DP, (int)D, theta, g_theta);
+  LO_LAUNCH_CHECK();
+  return LO_OK;
+}
+
+// the derivatives on validated arguments: part the partials of ksm_bil_layout / of ko_split_layout with D columns
+static int kernel_sm_bil_run(const float* x1, const float* x2, const float* theta, int Q, int64_t B, int64_t M, int64_t N,
+                             int64_t D, const float* U, const float* V, int64_t t, float* g_theta, float* part,
+                             hipStream_t st) {
+  const KoSweep w(B, M, N, D);
+  if (ksm_bil_wide(t, w.DP))  // many columns: W on the matrix cores (lo_kernel_kinds_bil_wide.hip)
+    return kernel_sm_bil_wide_run(x1, x2, theta, Q, B, M, N, D, U, V, t, g_theta, part, st);
+  const dim3 grid((unsigned)(w.s.rb * Q), (unsigned)B, (unsigned)w.s.js);  // (rb <= 2^23, Q <= 16)
+  LO_PROF_BEGIN("k_ksm_bil", st);
+  ko_pick(ksm_dims{}, w.DP, [&](auto P) {
+    hipLaunchKernelGGL((k_ksm_bil<P()>), grid, dim3(kThreads), 0, st, x1, x2, theta, Q, (int)M, (int)N, (int)D, U, V,
+                       (int)t, part, w.s.jchunk);
+  });
+  LO_PROF_END(st);
+  LO_LAUNCH_CHECK();
+  return ksm_bil_reduce(part, w.s.rb * w.s.js, w.DP, B, D, Q, theta, g_theta, st);
+}
+
+static int kernel_sm_pgrad_run(const float* x1, const float* x2, const float* theta, int Q, int64_t B, int64_t M,
+                               int64_t N, int64_t D, const float* U, const float* V, int64_t t, float* g_x1, float* part,
+                               hipStream_t st) {
+  const KoSweep w(B, M, N, D);
+  if (ksm_bil_wide(t, w.DP))
+    return kernel_sm_pgrad_wide_run(x1, x2, theta, Q, B, M, N, D, U, V, t, g_x1, part, st);
+  float* out = w.s.js > 1 ? part : g_x1;
+  LO_PROF_BEGIN("k_ksm_pgrad", st);
+  ko_pick(ksm_dims{}, w.DP, [&](auto P) {
+    hipLaunchKernelGGL((k_ksm_pgrad<P()>), w.grid, dim3(kThreads), 0, st, x1, x2, theta, Q, (int)M, (int)N, (int)D, U, V,
+                       (int)t, out, w.s.jchunk);
+  });
+  LO_PROF_END(st);
+  LO_LAUNCH_CHECK();
+  if (w.s.js > 1)  // the splits in ascending order (the reduction of the product with D as its columns and no diagonal)
+    return ko_reduce_splits("k_ksm_pgrad_reduce", part, w.s.js, (size_t)M * D, (size_t)B * M * D, (int)D, nullptr,
+                            LO_DIAG_NONE, nullptr, g_x1, nullptr, st);
+  return LO_OK;
+}
+
 int kernel_sm_desc_check(const lo_op_desc* op) {
   if (!op->A0 || !op->A1 || op->R < 1 || op->n2 < 1) return LO_ERR_BADARG;
   return (op->R > LO_KERNEL_SM_MAX_DIM || op->n2 > LO_KERNEL_SM_MAX_MIX) ? LO_ERR_UNSUPPORTED : LO_OK;
@@ -422,23 +427,10 @@ int lo_kernel_sm_bilinear_f32(const float* x1, const float* x2, const float* the
                               size_t ws_bytes, void* stream) {
   if (!x1 || !x2 || !theta || !U || !V || !g_theta || !ksm_args_ok(B, M, N, D, Q, t)) return LO_ERR_BADARG;
   if (!ksm_shape_ok(B, M, N, D, Q, t)) return LO_ERR_UNSUPPORTED;
-  hipStream_t st = (hipStream_t)stream;
   Arena ar(ws, ws_bytes, kKoTail);
   float* part = ksm_bil_layout(ar, B, M, N, D, Q);
   if (!ws || !ar.ok) return LO_ERR_WORKSPACE;
-  const KoSweep w(B, M, N, D);
-  const dim3 grid((unsigned)(w.s.rb * Q), (unsigned)B, (unsigned)w.s.js);  // (rb <= 2^23, Q <= 16)
-  LO_PROF_BEGIN("k_ksm_bil", st);
-  ko_pick(ksm_dims{}, w.DP, [&](auto P) {
-    hipLaunchKernelGGL((k_ksm_bil<P()>), grid, dim3(kThreads), 0, st, x1, x2, theta, (int)Q, (int)M, (int)N, (int)D, U, V,
-                       (int)t, part, w.s.jchunk);
-  });
-  LO_PROF_END(st);
-  LO_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_ksm_bil_reduce, dim3((unsigned)(B * Q)), dim3(64), 0, st, part, w.s.rb * w.s.js, w.DP, (int)D, theta,
-                     g_theta);
-  LO_LAUNCH_CHECK();
-  return LO_OK;
+  return kernel_sm_bil_run(x1, x2, theta, Q, B, M, N, D, U, V, t, g_theta, part, (hipStream_t)stream);
 }
 
 size_t lo_kernel_sm_points_grad_workspace_bytes(int64_t B, int64_t M, int64_t N, int64_t D, int64_t Q, int64_t t) {
@@ -451,23 +443,10 @@ int lo_kernel_sm_points_grad_f32(const float* x1, const float* x2, const float* 
                                  size_t ws_bytes, void* stream) {
   if (!x1 || !x2 || !theta || !U || !V || !g_x1 || !ksm_args_ok(B, M, N, D, Q, t)) return LO_ERR_BADARG;
   if (!ksm_shape_ok(B, M, N, D, Q, t)) return LO_ERR_UNSUPPORTED;
-  hipStream_t st = (hipStream_t)stream;
   Arena ar(ws, ws_bytes, kKoTail);
   float* part = ko_split_layout<float>(ar, B, M, N, D);  // [js, B, M, D]
   if (!ws || !ar.ok) return LO_ERR_WORKSPACE;
-  const KoSweep w(B, M, N, D);
-  float* out = w.s.js > 1 ? part : g_x1;
-  LO_PROF_BEGIN("k_ksm_pgrad", st);
-  ko_pick(ksm_dims{}, w.DP, [&](auto P) {
-    hipLaunchKernelGGL((k_ksm_pgrad<P()>), w.grid, dim3(kThreads), 0, st, x1, x2, theta, (int)Q, (int)M, (int)N, (int)D, U,
-                       V, (int)t, out, w.s.jchunk);
-  });
-  LO_PROF_END(st);
-  LO_LAUNCH_CHECK();
-  if (w.s.js > 1)  // the splits in ascending order (the reduction of the product with D as its columns and no diagonal)
-    return ko_reduce_splits("k_ksm_pgrad_reduce", part, w.s.js, (size_t)M * D, (size_t)B * M * D, (int)D, nullptr,
-                            LO_DIAG_NONE, nullptr, g_x1, nullptr, st);
-  return LO_OK;
+  return kernel_sm_pgrad_run(x1, x2, theta, Q, B, M, N, D, U, V, t, g_x1, part, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -3,6 +3,7 @@
 // instructions it had with the text written out (profiles/r19 holds the comparison, and the helpers that did not pass it).
 #pragma once
 #include "lo_internal.h"
+#include "lo_kernel_fn.h"
 
 namespace lo {
 
@@ -16,7 +17,8 @@ __device__ __forceinline__ void ko_stage_points(const T* __restrict__ x2b, const
   }
 }
 
-// ---- what the kernels of the rational-quadratic / periodic kind share (lo_kernel_param.hip, lo_kernel_kinds_wide.hip) -----
+// ---- what the kernels of the rational-quadratic / periodic kind share (lo_kernel_param.hip, lo_kernel_kinds_wide.hip,
+// lo_kernel_kinds_bil_wide.hip) -----
 // what a workgroup reads of its member's theta: th[k] = t_k, sc[k] = the factor the points are scaled by (RQ: t_k,
 // PERIODIC: nu_k), both 0 for k >= D
 template <int FAMILY, int DP>
@@ -30,7 +32,44 @@ __device__ __forceinline__ void kp_load_theta(const float* __restrict__ tb, int 
   __syncthreads();
 }
 
-// ---- what the kernels of the spectral mixture kind share (lo_kernel_sm.hip, lo_kernel_kinds_wide.hip) --------------------
+constexpr float kKpPi = 3.14159265358979323846f;
+
+// The pair of the two derivative sweeps: from the thread's point a and the tile's point xs[j] the value g and per
+// coordinate what the lengthscale / period / points sums take.
+//   RQ:        g, h, ga as kp_rq_gha; e1[k] = the scaled difference s_k (lengthscale: h s_k^2, points: h s_k)
+//   PERIODIC:  g; e1[k] = (t_k s_k)^2, e2[k] = t_k^2 |phi_k| sin(2 pi |phi_k|) (even in phi), or with POINTS
+//              e2[k] = sin(2 pi phi_k) (odd: the sign put back)
+template <int FAMILY, int DP, bool POINTS>
+__device__ __forceinline__ void kp_pair(const float (&a)[DP], const float* __restrict__ xj, const float* __restrict__ th,
+                                        float alpha, float inv2a, float* g, float* h, float* ga, float (&e1)[DP],
+                                        float (&e2)[DP]) {
+  float sum = 0.0f;
+#pragma unroll
+  for (int k = 0; k < DP; ++k) {
+    const float df = a[k] - xj[k];
+    if constexpr (FAMILY == LO_KERNEL_PERIODIC) {
+      const float p = fabsf(df);
+      const float ts = th[k] * kp_sinpi(p);
+      const float s2 = kp_sin2pi(p);
+      e1[k] = ts * ts;
+      e2[k] = POINTS ? (df < 0.0f ? -s2 : s2) : th[k] * th[k] * p * s2;
+      sum += e1[k];
+    } else {
+      e1[k] = df;
+      sum = fmaf(df, df, sum);
+    }
+  }
+  if constexpr (FAMILY == LO_KERNEL_PERIODIC) {
+    *g = kp_per_g(sum);
+    *h = 0.0f;
+    *ga = 0.0f;
+  } else {
+    kp_rq_gha(sum, alpha, inv2a, g, h, ga);
+  }
+}
+
+// ---- what the kernels of the spectral mixture kind share (lo_kernel_sm.hip, lo_kernel_kinds_wide.hip,
+// lo_kernel_kinds_bil_wide.hip) ----
 constexpr int kKsmQ = LO_KERNEL_SM_MAX_MIX;
 
 // the member's theta in LDS: tw[q] = w_q, tmu[q][k] = |mu_qk|, tsg[q][k] = sigma_qk, both 0 for k >= D (Q DP <= 256 words)
@@ -56,6 +95,40 @@ __device__ __forceinline__ void ksm_stage_points(const float* __restrict__ x2b, 
     const int j = e / DP, dd = e - j * DP;
     xs[e] = dd < D ? x2b[(size_t)(jt + j) * D + dd] : 0.0f;
   }
+}
+
+// one mixture of one pair: the envelope E, the cosines c[k] and, with SINES, the sines s[k] of 2 pi |mu_k| tau_k
+template <int DP, bool SINES>
+__device__ __forceinline__ float ksm_mixture(const float (&tau)[DP], const float* __restrict__ mu,
+                                             const float* __restrict__ sg, float (&c)[DP], float (&s)[DP]) {
+  float s2 = 0.0f;
+#pragma unroll
+  for (int k = 0; k < DP; ++k) {
+    const float st = sg[k] * tau[k];
+    s2 = fmaf(st, st, s2);
+    const float p = mu[k] * tau[k];
+    c[k] = ksm_cos2pi(p);
+    if constexpr (SINES) s[k] = kp_sin2pi(p);
+  }
+  return ksm_env(s2);
+}
+
+// ex[k] = prod_{l != k} c_l by a prefix and a suffix product; returns prod_l c_l
+template <int DP>
+__device__ __forceinline__ float ksm_leave_one_out(const float (&c)[DP], float (&ex)[DP]) {
+  float pre = 1.0f;
+#pragma unroll
+  for (int k = 0; k < DP; ++k) {
+    ex[k] = pre;
+    pre *= c[k];
+  }
+  float suf = 1.0f;
+#pragma unroll
+  for (int k = DP - 1; k >= 0; --k) {
+    ex[k] *= suf;
+    suf *= c[k];
+  }
+  return pre;
 }
 
 // Sum over the 256 threads in a fixed order (wave butterfly, then waves 0..3); `red` >= 4 doubles of LDS

@@ -792,30 +792,46 @@ def kernel_param_mv_wide(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor
     return _kernel_param_mv("kernel_param_mv_wide", "lo_kernel_param_mv_wide", x1, x2, theta, family, v, d, const_diag)
 
 
+def _kernel_param_deriv(what, stem, x1, x2, theta, family, U, V, points):
+    family = _kernel_param_family(what, family)
+    x1, x2, theta, _, U, V, (B, M, N, D, _, t), dtype = _kernel_args(what, x1, x2, theta, V, U,
+                                                                      width=2 * x1.shape[-1] + 2)
+    g = torch.empty((B, M, D) if points else (B, 2 * D + 2), dtype=dtype, device=U.device)
+    name, sizer = _kernel_entry(stem, False)
+    _launch(name, U.device, x1, x2, theta, family, B, M, N, D, U, V, t, g, ws_bytes=sizer(B, M, N, D, t))
+    return g
+
+
 def kernel_param_bilinear(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, family: int, U: torch.Tensor,
                           V: torch.Tensor) -> torch.Tensor:
     """lo_kernel_param_bilinear_f32: g_theta [B, 2 D + 2], the derivative of sum_s u_s^T K(x1, x2) v_s with respect to every
     entry of theta (0 where the family does not read the entry).  x1 [B, M, D], x2 [B, N, D], U [B, M, t], V [B, N, t]."""
-    family = _kernel_param_family("kernel_param_bilinear", family)
-    x1, x2, theta, _, U, V, (B, M, N, D, _, t), dtype = _kernel_args("kernel_param_bilinear", x1, x2, theta, V, U,
-                                                                      width=2 * x1.shape[-1] + 2)
-    g = torch.empty(B, 2 * D + 2, dtype=dtype, device=U.device)
-    name, sizer = _kernel_entry("lo_kernel_param_bilinear", False)
-    _launch(name, U.device, x1, x2, theta, family, B, M, N, D, U, V, t, g, ws_bytes=sizer(B, M, N, D, t))
-    return g
+    return _kernel_param_deriv("kernel_param_bilinear", "lo_kernel_param_bilinear", x1, x2, theta, family, U, V, False)
+
+
+def kernel_param_bilinear_wide(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, family: int, U: torch.Tensor,
+                               V: torch.Tensor) -> torch.Tensor:
+    """lo_kernel_param_bilinear_wide_f32: kernel_param_bilinear on the many-column kernel
+    (csrc/lo_kernel_kinds_bil_wide.hip: W = U V^T on the matrix cores, 32 columns per sweep), whatever the column count.
+    kernel_param_bilinear takes this kernel by itself where it is the faster one."""
+    return _kernel_param_deriv("kernel_param_bilinear_wide", "lo_kernel_param_bilinear_wide", x1, x2, theta, family, U, V,
+                               False)
 
 
 def kernel_param_points_grad(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, family: int, U: torch.Tensor,
                              V: torch.Tensor) -> torch.Tensor:
     """lo_kernel_param_points_grad_f32: g_x1 [B, M, D], the derivative of sum_s u_s^T K(x1, x2) v_s with respect to x1, x2
     held fixed.  The derivative with respect to x2 is kernel_param_points_grad(x2, x1, theta, family, V, U)."""
-    family = _kernel_param_family("kernel_param_points_grad", family)
-    x1, x2, theta, _, U, V, (B, M, N, D, _, t), dtype = _kernel_args("kernel_param_points_grad", x1, x2, theta, V, U,
-                                                                      width=2 * x1.shape[-1] + 2)
-    g = torch.empty(B, M, D, dtype=dtype, device=U.device)
-    name, sizer = _kernel_entry("lo_kernel_param_points_grad", False)
-    _launch(name, U.device, x1, x2, theta, family, B, M, N, D, U, V, t, g, ws_bytes=sizer(B, M, N, D, t))
-    return g
+    return _kernel_param_deriv("kernel_param_points_grad", "lo_kernel_param_points_grad", x1, x2, theta, family, U, V,
+                               True)
+
+
+def kernel_param_points_grad_wide(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, family: int, U: torch.Tensor,
+                                  V: torch.Tensor) -> torch.Tensor:
+    """lo_kernel_param_points_grad_wide_f32: kernel_param_points_grad on the many-column kernel
+    (csrc/lo_kernel_kinds_bil_wide.hip), whatever the column count."""
+    return _kernel_param_deriv("kernel_param_points_grad_wide", "lo_kernel_param_points_grad_wide", x1, x2, theta, family,
+                               U, V, True)
 
 
 def kernel_sm_theta(weights: torch.Tensor, means: torch.Tensor, scales: torch.Tensor, batch, D: int) -> torch.Tensor:
@@ -881,26 +897,41 @@ def kernel_sm_mv_wide(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, v
     return _kernel_sm_mv("kernel_sm_mv_wide", "lo_kernel_sm_mv_wide", x1, x2, theta, v, d, const_diag)
 
 
+def _kernel_sm_deriv(what, stem, x1, x2, theta, U, V, points):
+    x1, x2, theta, U, V, (B, M, N, D, Q, t) = _kernel_sm_args(what, x1, x2, theta, V, U)
+    g = torch.empty((B, M, D) if points else (B, Q, 2 * D + 1), dtype=torch.float32, device=U.device)
+    name, sizer = _kernel_entry(stem, False)
+    _launch(name, U.device, x1, x2, theta, Q, B, M, N, D, U, V, t, g, ws_bytes=sizer(B, M, N, D, Q, t))
+    return g
+
+
 def kernel_sm_bilinear(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, U: torch.Tensor,
                        V: torch.Tensor) -> torch.Tensor:
     """lo_kernel_sm_bilinear_f32: g_theta [B, Q, 2 D + 1], the derivative of sum_s u_s^T K(x1, x2) v_s with respect to every
     entry of theta, in theta's layout.  x1 [B, M, D], x2 [B, N, D], U [B, M, t], V [B, N, t]."""
-    x1, x2, theta, U, V, (B, M, N, D, Q, t) = _kernel_sm_args("kernel_sm_bilinear", x1, x2, theta, V, U)
-    g = torch.empty(B, Q, 2 * D + 1, dtype=torch.float32, device=U.device)
-    name, sizer = _kernel_entry("lo_kernel_sm_bilinear", False)
-    _launch(name, U.device, x1, x2, theta, Q, B, M, N, D, U, V, t, g, ws_bytes=sizer(B, M, N, D, Q, t))
-    return g
+    return _kernel_sm_deriv("kernel_sm_bilinear", "lo_kernel_sm_bilinear", x1, x2, theta, U, V, False)
+
+
+def kernel_sm_bilinear_wide(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, U: torch.Tensor,
+                            V: torch.Tensor) -> torch.Tensor:
+    """lo_kernel_sm_bilinear_wide_f32: kernel_sm_bilinear on the many-column kernel (csrc/lo_kernel_kinds_bil_wide.hip:
+    W = U V^T on the matrix cores, 32 columns per sweep), whatever the column count.  kernel_sm_bilinear takes this kernel
+    by itself where it is the faster one."""
+    return _kernel_sm_deriv("kernel_sm_bilinear_wide", "lo_kernel_sm_bilinear_wide", x1, x2, theta, U, V, False)
 
 
 def kernel_sm_points_grad(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, U: torch.Tensor,
                           V: torch.Tensor) -> torch.Tensor:
     """lo_kernel_sm_points_grad_f32: g_x1 [B, M, D], the derivative of sum_s u_s^T K(x1, x2) v_s with respect to x1, x2 held
     fixed.  The derivative with respect to x2 is kernel_sm_points_grad(x2, x1, theta, V, U)."""
-    x1, x2, theta, U, V, (B, M, N, D, Q, t) = _kernel_sm_args("kernel_sm_points_grad", x1, x2, theta, V, U)
-    g = torch.empty(B, M, D, dtype=torch.float32, device=U.device)
-    name, sizer = _kernel_entry("lo_kernel_sm_points_grad", False)
-    _launch(name, U.device, x1, x2, theta, Q, B, M, N, D, U, V, t, g, ws_bytes=sizer(B, M, N, D, Q, t))
-    return g
+    return _kernel_sm_deriv("kernel_sm_points_grad", "lo_kernel_sm_points_grad", x1, x2, theta, U, V, True)
+
+
+def kernel_sm_points_grad_wide(x1: torch.Tensor, x2: torch.Tensor, theta: torch.Tensor, U: torch.Tensor,
+                               V: torch.Tensor) -> torch.Tensor:
+    """lo_kernel_sm_points_grad_wide_f32: kernel_sm_points_grad on the many-column kernel
+    (csrc/lo_kernel_kinds_bil_wide.hip), whatever the column count."""
+    return _kernel_sm_deriv("kernel_sm_points_grad_wide", "lo_kernel_sm_points_grad_wide", x1, x2, theta, U, V, True)
 
 
 def kernel_sum_theta(lengthscales, outputscales, batch, D: int) -> torch.Tensor:

@@ -22,7 +22,7 @@ round, spread next to it; device events after warm-up).
 Shapes 1 x 16384 (D 4) and 8 x 8192 (D 16).  The dense function of the periodic kernel holds [M, N, D] intermediates (64
 GiB per tensor at the second shape), so every dense route runs member by member.  No routing rests on these numbers: inside
 its gate the kernel is always taken, its purpose is memory.
-Usage:  python tools/mb_kernel_param.py [--what product,bilinear,points,solve,wide,widesolve] [--families rq,periodic] [--reps 20] [--rounds 5]
+Usage:  python tools/mb_kernel_param.py [--what product,bilinear,points,solve,wide,widesolve,bilwide,widetrain] [--families rq,periodic] [--reps 20] [--rounds 5]
 One JSON line per measurement.
 """
 from __future__ import annotations
@@ -53,6 +53,7 @@ DERIV_COLS = 8
 SOLVE = (1, 8192, 4)
 WIDE_SHAPES = ((1, 16384, 4), (1, 16384, 8), (8, 8192, 16), (1, 16384, 32))  # one per padded dimension
 WIDE_COLS = (1, 2, 4, 5, 8, 16, 17, 32, 33, 64)
+BIL_COLS = (1, 2, 4, 8, 9, 11, 16, 17, 32, 33, 64)
 NB = {"outputscale": 0, "alpha": 0}
 SHAPE = {"rq": "alpha", "periodic": "period_length"}
 
@@ -199,6 +200,56 @@ def wide_columns(args, dev, gen, family):
                 wide_wins=times[1][2] < times[0][1], rel_diff=rel_diff(fns[1](), fns[0]()))), flush=True)
 
 
+def wide_derivatives(args, dev, gen, family):
+    """--what bilwide: the wide derivative entries against the plain ones over BIL_COLS at WIDE_SHAPES, the two taking turns.
+    kp_bil_wide of csrc/lo_kernel_shape.h is to be set from this table: the comparison is against k_kparam_bil /
+    k_kparam_pgrad only where the rule does not route (today: everywhere)."""
+    fam = covariance.PARAM_FAMILIES[family].native_family
+    for B, n, D in WIDE_SHAPES:
+        x, _, theta = make(family, B, n, D, gen, dev)
+        for t in BIL_COLS:
+            U, V = torch.randn(B, n, t, generator=gen).to(dev), torch.randn(B, n, t, generator=gen).to(dev)
+            for name in ("bilinear", "points_grad"):
+                plain, wide = getattr(K, "kernel_param_" + name), getattr(K, "kernel_param_" + name + "_wide")
+                fns = [lambda: plain(x, x, theta, fam, U, V), lambda: wide(x, x, theta, fam, U, V)]
+                times = alternated(fns, args.reps, args.rounds)
+                print(json.dumps(dict(
+                    what="kernel_param_" + name + "_wide", family=family, B=B, n=n, D=D, t=t, plain_us=r1(times[0]),
+                    wide_us=r1(times[1]), wide_over_plain=round(times[1][0] / times[0][0], 3),
+                    wide_wins=times[1][2] < times[0][1], rel_diff=rel_diff(fns[1](), fns[0]()))), flush=True)
+
+
+def wide_training(args, dev, gen, family):
+    """--what widetrain: inv_quad_logdet forward + backward of ParamKernel + Diag at 1 x 8192 (D 4), 16 probes, gradients of
+    the hyperparameters and the points; host clock around a synchronise, one build per process (alternate processes of two
+    builds)."""
+    n, c = 8192, 16
+    x, p, _ = make(family, 1, n, 4, gen, dev)
+    noise = (0.05 + 0.1 * torch.rand(1, n, generator=gen)).to(dev)
+    rhs = torch.randn(1, n, 1, generator=gen).to(dev)
+
+    def run():
+        leaves = {k: v.detach().requires_grad_(True) for k, v in p.items()}
+        xg = x.detach().requires_grad_(True)
+        kern = KernelLinearOperator(xg, xg, covariance.PARAM_FAMILIES[family], num_nonbatch_dimensions=NB, **leaves)
+        iq, ld = AddedDiagLinearOperator(kern, DiagLinearOperator(noise)).inv_quad_logdet(rhs, logdet=True)
+        (iq.sum() + ld.sum()).backward()
+
+    def clock():
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        run()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    with settings.max_cholesky_size(0), settings.min_preconditioning_size(0), settings.cg_tolerance(1e-3), \
+            settings.max_preconditioner_size(15), settings.num_trace_samples(c):
+        run()  # (warm-up)
+        times = [clock() for _ in range(args.rounds)]
+    print(json.dumps(dict(what="wide_train", family=family, n=n, D=4, probes=c,
+                          ms=[round(t, 2) for t in (statistics.median(times), min(times), max(times))])), flush=True)
+
+
 def wide_solves(args, dev, gen, family):
     def clock(fn):
         torch.cuda.synchronize()
@@ -245,6 +296,10 @@ def main():
                 wide_columns(args, "cuda", gen, family)
             elif what == "widesolve":
                 wide_solves(args, "cuda", gen, family)
+            elif what == "bilwide":
+                wide_derivatives(args, "cuda", gen, family)
+            elif what == "widetrain":
+                wide_training(args, "cuda", gen, family)
             else:
                 derivatives(args, "cuda", gen, family, what)
 

@@ -23,7 +23,7 @@ Shapes 1 x 16384 (D 1, Q 4: the time-series shape) and 8 x 8192 (D 4, Q 4).  The
 intermediates (4 GiB per tensor per member at both shapes), so every dense route runs member by member; a route that runs
 out of memory is reported as null.  No routing rests on these numbers: inside its gate the kernel is always taken, its
 purpose is memory.
-Usage:  python tools/mb_kernel_sm.py [--what product,bilinear,points,solve,wide,widesolve] [--reps 20] [--rounds 5]
+Usage:  python tools/mb_kernel_sm.py [--what product,bilinear,points,solve,wide,widesolve,bilwide,widetrain] [--reps 20] [--rounds 5]
 One JSON line per measurement.
 """
 from __future__ import annotations
@@ -54,6 +54,7 @@ DERIV_COLS = 8
 SOLVE = (1, 8192, 1, 4)
 WIDE_SHAPES = ((1, 16384, 1, 4), (1, 16384, 4, 4), (1, 16384, 16, 4), (1, 16384, 4, 16))  # (B, n, D, Q): every padded D, both Q
 WIDE_COLS = (1, 2, 4, 5, 8, 16, 17, 32, 33, 64)
+BIL_COLS = (1, 2, 4, 8, 9, 11, 16, 17, 32, 33, 64)
 NB = {"mixture_weights": 1}
 NAMES = ("mixture_weights", "mixture_means", "mixture_scales")
 FN = covariance.spectral_mixture
@@ -201,6 +202,55 @@ def wide_columns(args, dev, gen):
                 wide_wins=times[1][2] < times[0][1], rel_diff=rel_diff(fns[1](), fns[0]()))), flush=True)
 
 
+def wide_derivatives(args, dev, gen):
+    """--what bilwide: the wide derivative entries against the plain ones over BIL_COLS at WIDE_SHAPES, the two taking turns.
+    ksm_bil_wide of csrc/lo_kernel_shape.h is to be set from this table: the comparison is against k_ksm_bil / k_ksm_pgrad
+    only where the rule does not route (today: everywhere)."""
+    for B, n, D, Q in WIDE_SHAPES:
+        x, _, theta = make(B, n, D, Q, gen, dev)
+        for t in BIL_COLS:
+            U, V = torch.randn(B, n, t, generator=gen).to(dev), torch.randn(B, n, t, generator=gen).to(dev)
+            for name in ("bilinear", "points_grad"):
+                plain, wide = getattr(K, "kernel_sm_" + name), getattr(K, "kernel_sm_" + name + "_wide")
+                fns = [lambda: plain(x, x, theta, U, V), lambda: wide(x, x, theta, U, V)]
+                times = alternated(fns, args.reps, args.rounds)
+                print(json.dumps(dict(
+                    what="kernel_sm_" + name + "_wide", B=B, n=n, D=D, Q=Q, t=t, plain_us=r1(times[0]),
+                    wide_us=r1(times[1]), wide_over_plain=round(times[1][0] / times[0][0], 3),
+                    wide_wins=times[1][2] < times[0][1], rel_diff=rel_diff(fns[1](), fns[0]()))), flush=True)
+
+
+def wide_training(args, dev, gen):
+    """--what widetrain: inv_quad_logdet forward + backward of SM + Diag at 1 x 8192 (D 1, Q 4), 16 probes, gradients of the
+    mixtures and the points; host clock around a synchronise, one build per process (alternate processes of two builds)."""
+    n, c = 8192, 16
+    x, p, _ = make(1, n, 1, 4, gen, dev)
+    noise = (0.05 + 0.1 * torch.rand(1, n, generator=gen)).to(dev)
+    rhs = torch.randn(1, n, 1, generator=gen).to(dev)
+
+    def run():
+        leaves = {k: v.detach().requires_grad_(True) for k, v in p.items()}
+        xg = x.detach().requires_grad_(True)
+        A = AddedDiagLinearOperator(KernelLinearOperator(xg, xg, FN, num_nonbatch_dimensions=NB, **leaves),
+                                    DiagLinearOperator(noise))
+        iq, ld = A.inv_quad_logdet(rhs, logdet=True)
+        (iq.sum() + ld.sum()).backward()
+
+    def clock():
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        run()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    with settings.max_cholesky_size(0), settings.min_preconditioning_size(0), settings.cg_tolerance(1e-3), \
+            settings.max_preconditioner_size(15), settings.num_trace_samples(c):
+        run()  # (warm-up)
+        times = [clock() for _ in range(args.rounds)]
+    print(json.dumps(dict(what="wide_train", n=n, D=1, Q=4, probes=c,
+                          ms=[round(t, 2) for t in (statistics.median(times), min(times), max(times))])), flush=True)
+
+
 def wide_solves(args, dev, gen):
     def clock(fn):
         torch.cuda.synchronize()
@@ -245,6 +295,10 @@ def main():
             wide_columns(args, "cuda", gen)
         elif what == "widesolve":
             wide_solves(args, "cuda", gen)
+        elif what == "bilwide":
+            wide_derivatives(args, "cuda", gen)
+        elif what == "widetrain":
+            wide_training(args, "cuda", gen)
         else:
             derivatives(args, "cuda", gen, what)
 
